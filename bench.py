@@ -34,12 +34,8 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-# HIP multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share a queue
-# are served in submission order.  The pipelined step uses three internal streams beside the caller's; with the gather's
-# side stream (N > 1 ranks) that is five, two of them alias, and a stage ends up queued behind another stage's event wait:
-# measured 2.59 instead of 1.85 ms per step.  Has to be set before the HIP runtime initialises (conan_amd/__init__.py does
-# the same for callers that import the package first).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# The number of hardware queues HIP serves this process's streams from is left to the environment the benchmark runs in: on a
+# GPU shared with other processes it is the host's setting, and streams beyond it share queues.
 # multi-process GPU work on this pool needs dmabuf IPC (RCCL otherwise fails with hipIpcGetMemHandle: invalid argument)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
@@ -244,9 +240,12 @@ class Runner:
         # Windowed workloads: one blocking windowed step (Emformer step, reset, decoder + vocoder over window + chunk frames).
         self.ring = AudioGatherRing(lambda: torch.empty_like(self.wav), world, rank, nb=4, always=comm,
                                     every=int(os.environ.get("CONAN_BENCH_GATHER_EVERY", "4")))
-        self.hist = [torch.randint(0, 100, (B, self.window), dtype=torch.int32, device="cuda")] if self.window else None
+        # (seeded: the same arguments give the same inputs, run to run)
+        self.hist = [torch.randint(0, 100, (B, self.window), dtype=torch.int32, generator=torch.Generator().manual_seed(rank * B)).cuda()] \
+            if self.window else None
         self.j = 0
         self.primed = 0
+        self.last = None         # what the caller received from the newest step: {name: tensor}
 
     def step(self):
         j, eng, seg = self.j, self.eng, self.seg
@@ -256,12 +255,19 @@ class Runner:
             buf, fence = self.ring.acquire(j, fence=True)
             eng.st.step_async(eng.slots, chunk, buf, emit=seg, codes=self.codes, mel_out=self.mel_out, out_fence=fence)
             self.ring.submit(j, join=eng.st.join)
+            self.last = {"codes": self.codes, "mel": self.mel_out, "wav": buf}
             return
         buf = self.ring.acquire(j)
         c, w = eng.windowed_step(chunk, self.hist[0])
         self.hist[0] = torch.cat([self.hist[0][:, seg:], c], 1)
         buf.copy_(w)
         self.ring.submit(j, wait_current=True)
+        self.last = {"codes": c, "wav": buf}
+
+    def last_outputs(self):
+        """Host copies of what the newest step (`step`) handed its caller, after a barrier: {name: float32 / float64 array}
+        (codes as float64, exact)."""
+        return {k: v.cpu().numpy().astype(np.float64 if v.dtype == torch.int32 else np.float32) for k, v in self.last.items()}
 
     def blocking_step(self):
         eng, seg = self.eng, self.seg
@@ -429,6 +435,24 @@ def check_ranks(gpus, world, devices):
     return None
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, outputs):
+    """outputs {name: array [streams, ...]} -> path/<name>.npy.  Beyond DUMP_MAX_BYTES in all, a fixed, seeded sample of the
+    streams (the same rows of every array) is written instead.  -> what was written, for the result line."""
+    n = len(next(iter(outputs.values())))
+    per_stream = sum(a[0].nbytes for a in outputs.values())
+    rows = np.arange(n)
+    if per_stream * n > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // per_stream, replace=False))
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a[rows])
+    return {"dir": path, "arrays": {k: [len(rows)] + list(a.shape[1:]) for k, a in outputs.items()},
+            "streams": "all" if len(rows) == n else rows.tolist()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -448,7 +472,11 @@ def main():
     ap.add_argument("--no-other", action="store_true", help="skip the datapoint of the other arithmetic form")
     ap.add_argument("--marks", action="store_true", help="bracket the timed steps with cnk::profile_mark_kernel dispatches and skip "
                                                          "every other leg (rocprofv3 --pmc passes: tools/summarize_pmc.py keeps the dispatches between the marks)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (rank 0's streams: codes, mel, wav) as DIR/<name>.npy, for comparing builds")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rc = spawn_ranks(args.gpus, sys.argv[1:])      # --gpus N > 1 outside a launcher: this process only starts the N ranks
     if rc is not None:
@@ -480,6 +508,7 @@ def main():
         run.prime(args.prime)
     dt = run.timed(args.steps, args.warmup, marks=args.marks)
     j = run.j
+    outputs = run.last_outputs() if args.dump_outputs and rank == 0 else None
     # Every rank's own clock, its device, and a check of the exchange: the audio rank 0 gathered for the LAST gathered step must
     # be, bit for bit, what each rank produced for it (one all_gather of integer checksums, outside the timed region).
     ring = run.ring
@@ -664,6 +693,8 @@ def main():
             out["latency_b1"] = b1
         if fe is not None:
             out["frontend"] = fe
+        if outputs is not None:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out))
     run.close()
     if world > 1:

@@ -159,29 +159,24 @@ def test_wav_io_roundtrip_and_pad(tmp_path):
     assert librosa_pad_lr(np.zeros(960), 1024, 320, 2) == (160, 160)
 
 
-REFERENCE = "/root/reference"
-
-
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="the reference tree exists in the build container only")
 @pytest.mark.parametrize("cfg,table", [("egs/conan_emformer.yaml", "CONAN_EMFORMER"), ("egs/hifi_16k320_shuffle.yaml", "HIFIGAN_16K320_SHUFFLE")])
-def test_set_hparams_equals_the_reference_parser_and_configs_py(cfg, table):
-    """conan_amd's yaml-chain parser against the reference's own utils/commons/hparams.py run in a subprocess on the
-    reference's egs/ files (key for key), and conan_amd/configs.py against those resolved chains."""
+def test_set_hparams_equals_the_reference_parser_and_configs_py(cfg, table, tmp_path):
+    """conan_amd's yaml-chain parser against the reference's own utils/commons/hparams.py on the reference's egs/ files (key for
+    key), and conan_amd/configs.py against those resolved chains.  The chain's files and the reference parser's result are the
+    fixture tests/golden/hparams_chains.json (tools/make_hparams_golden.py)."""
     import json
-    import subprocess
-    import sys
-    code = ("import json,sys; sys.dont_write_bytecode=True\n"
-            "from utils.commons.hparams import set_hparams\n"
-            f"hp = set_hparams(config={cfg!r}, exp_name='', print_hparams=False, global_hparams=False)\n"
-            "print('JSON' + json.dumps(hp, sort_keys=True, default=str))\n")
-    env = dict(os.environ, PYTHONPATH=REFERENCE, PYTHONDONTWRITEBYTECODE="1")
-    out = subprocess.run([sys.executable, "-c", code], cwd=REFERENCE, env=env, capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr[-2000:]
-    ref = json.loads([l for l in out.stdout.splitlines() if l.startswith("JSON")][-1][4:])
+    from tests.conftest import GOLDEN
+    with open(os.path.join(GOLDEN, "hparams_chains.json")) as f:
+        fixture = json.load(f)[cfg]
+    for rel, content in fixture["files"].items():
+        path = tmp_path / rel
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(yaml.safe_dump(content))
+    ref = fixture["resolved"]
     from conan_amd.utils.commons import hparams as hpm
     cwd = os.getcwd()
     try:
-        os.chdir(REFERENCE)
+        os.chdir(tmp_path)
         ours = hpm.set_hparams(config=cfg, exp_name="", print_hparams=False, global_hparams=False)
     finally:
         os.chdir(cwd)
