@@ -332,8 +332,9 @@ bool conv_tall_plan(const ConvArgs& a, int num_cu, int plan_n, ConvTallArgs* out
   const int ntiles = a.Cout / CT_TN;
   const long long ptiles = ((Mp + CT_TM - 1) / CT_TM) * ntiles;
   // (an item for every CU, with slices of at least 8 blocks: below that conv_mfma's small-M plans are the better fit - measured at 16
-  // streams, where ups.1 had 200 items: 0.609 against 0.597 ms per vocoder step; from 24 streams on this kernel wins: 0.701 / 0.793 /
-  // 0.981 / 1.169 against 0.712 / 0.804 / 1.056 / 1.202 at 24 / 32 / 48 / 64)
+  // streams, where ups.1 had 200 items: 0.609 against 0.597 ms per vocoder step; at 24 streams and more this kernel wins: 0.701 / 0.793 /
+  // 0.981 / 1.169 against 0.712 / 0.804 / 1.056 / 1.202 at 24 / 32 / 48 / 64.  On 256 CUs with 4-frame steps it takes ups.1 from 21
+  // streams on and ups.0 from 32: tests/test_gpu_conv_tall.py restates this predicate)
   if (ptiles * std::min<long long>(16, NB / 8) < num_cu) return false;
   int S = (int)std::max<long long>(1, std::min<long long>(16, num_cu / ptiles));
   int nbps = (NB + S - 1) / S;

@@ -88,6 +88,7 @@ def test_loop_golden_at_48_slots(S, K, arith):
     if arith == "limb":
         assert all(any(("resblock_limb_kernel<%d," % c) in k for k in vn) for c in (128, 64, 32)), sorted(vn)
         assert sum(n for k, n in vn.items() if "conv_limb_kernel" in k) >= 6 and not any("resblock_pair_kernel" in k or "resblock_fused_kernel" in k for k in vn), sorted(vn)
+        assert vn.get("cnk::conv_tall_kernel") == 2, sorted(vn.items())                      # ups.0 and ups.1 (conv_tall.hip)
     else:
         assert any("resblock_pair_kernel" in k for k in vn) and any("resblock_fused_kernel<128" in k for k in vn), sorted(vn)
     st.close(); ctx.close()

@@ -8,6 +8,7 @@ import torch
 
 from conan_amd import _lib, configs, synth
 from tests.conftest import ARITHS, assert_arith_ran, kernels_of, load_golden
+from tests.test_gpu_conv_tall import tall_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -146,7 +147,7 @@ def test_xcd_mode_election_fault_is_reported():
 # stages from 4 slots on and run the C = 256 stage as grouped conv_limb launches from 16 slots on; f32 stream-sets fuse from 8 slots
 # on and take the pair kernel from 16 slots on
 @pytest.mark.parametrize("arith", ARITHS)
-@pytest.mark.parametrize("S", [3, 4, 15, 16, 17, 40, 96])
+@pytest.mark.parametrize("S", [3, 4, 15, 16, 17, 20, 21, 31, 32, 33, 40, 96])
 def test_vocoder_golden_at_the_plan_switch_boundaries(S, arith):
     """tests/golden/loop_full.npz's mel (the reference loop's mel for a given code sequence) -> wav through slot S - 2 of an S-slot
     stream-set, chunk by chunk, at the stream counts on both sides of every plan switch, both arithmetic forms, the kernels that ran
@@ -174,10 +175,14 @@ def test_vocoder_golden_at_the_plan_switch_boundaries(S, arith):
         assert (n_mfma <= 4) == (S >= 16), (n_mfma, sorted(vn.items()))
         assert (sum(n for k, n in vn.items() if "conv_limb_kernel<4, 1, 1, 4>" in k) >= 6) or S < 16, sorted(vn.items())
         assert not has("resblock_pair_kernel") and not has("resblock_fused_kernel"), sorted(vn)
+        # ups.1 / ups.0 on conv_tall from 21 / 32 slots of 4 frames on (tests/test_gpu_conv_tall.py restates the plan)
+        cu = torch.cuda.get_device_properties(0).multi_processor_count
+        assert vn.get("cnk::conv_tall_kernel", 0) == tall_launches(S, 4, cu), sorted(vn.items())
     else:
         assert_arith_ran(vn, "f32")
         assert has("resblock_fused_kernel<32,")
         assert has("resblock_fused_kernel<128,") == (S >= 8) and has("resblock_pair_kernel") == (S >= 16), sorted(vn)
+        assert not has("conv_tall_kernel"), sorted(vn)
     st.close(); ctx.close()
 
 
