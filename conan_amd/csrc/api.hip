@@ -1,4 +1,6 @@
 // extern "C" surface of libconan_hip.so (include/conan_hip.h).
+#include <functional>
+
 #include "streams.h"
 
 static thread_local std::string g_err;
@@ -185,6 +187,15 @@ int conan_streams_create_opts(conan_ctx* ctx, int max_slots, int max_frames, int
       std::vector<int> id(max_slots);
       for (int i = 0; i < max_slots; ++i) id[i] = i;
       HIP_CHECK(hipMemcpy(s->d_ident, id.data(), max_slots * sizeof(int), hipMemcpyHostToDevice));
+      s->fe_slot.assign(max_slots, conan_streams::FeSlot());
+      if ((ctx->cfg.models & 7) == 7) {     // streaming front-end rings, sized for fft_size <= 2048 at the vocoder's hop
+        const int seg = ctx->cfg.emf_segment, rc = ctx->cfg.emf_right_context, hop = ctx->hop;
+        s->fe_LA = ch::next_pow2(2048 + seg * hop);
+        s->fe_LM = ch::next_pow2(2 * (seg + rc) + seg + 2048 / hop + 4);
+        s->fe_audio = s->alloc((size_t)max_slots * s->fe_LA);
+        s->fe_mel = s->alloc((size_t)max_slots * s->fe_LM * ctx->cfg.emf_input_dim);
+        s->fe_chunk = s->alloc((size_t)max_slots * (seg + rc) * ctx->cfg.emf_input_dim);
+      }
       if (ctx->cfg.models & CONAN_MODEL_HIFIGAN) s->build_vocoder();
       if (ctx->cfg.models & CONAN_MODEL_EMFORMER) s->build_emformer();
       if (ctx->cfg.models & CONAN_MODEL_CONAN) s->build_decoder();
@@ -215,6 +226,12 @@ int conan_streams_reset(conan_streams* s, const int32_t* slots, int n, int which
     }
     if (models & CONAN_MODEL_EMFORMER) zero(s->emf_state, s->pos_emf);
     if (models & CONAN_MODEL_CONAN) zero(s->dec_state, s->pos_dec);
+    if ((which & CONAN_MODEL_FRONTEND) && s->fe_audio) {
+      cnk::launch_zero_slots(s->fe_audio, s->fe_LA, s->fe_LA, s->d_slots, n, st);
+      const long long mel_floats = (long long)s->fe_LM * s->ctx->cfg.emf_input_dim;
+      cnk::launch_zero_slots(s->fe_mel, mel_floats, mel_floats, s->d_slots, n, st);
+      for (int i = 0; i < n; ++i) s->fe_slot[slots[i]] = conan_streams::FeSlot();
+    }
   });
 }
 
@@ -369,6 +386,23 @@ int conan_hifigan_step(conan_streams* s, const int32_t* slots, int n, int frames
   });
 }
 
+// The stages of one chunk step on `st` for the slots set_slots has just installed (conan_step, conan_step_wav).
+static void step_blocking(conan_streams* s, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev, float* mel_out_dev,
+                          float* wav_out_dev, hipStream_t st) {
+  const int seg = s->ctx->cfg.emf_segment;
+  int* codes_seg = codes_dev ? codes_dev : s->d_codes;
+  s->emformer_step(n, mel_chunk_dev, nullptr, nullptr, codes_seg, st);
+  const int* codes_emit = codes_seg;
+  if (emit != seg && n > 1) {
+    int* compact = s->d_codes + (size_t)s->max_slots * s->max_frames;
+    cnk::launch_copy_int_rows(compact, codes_seg, n, emit, seg, st);
+    codes_emit = compact;
+  }
+  float* mel = mel_out_dev ? mel_out_dev : s->c_mel.base;
+  { conan_decoder_taps none; memset(&none, 0, sizeof(none)); s->decoder_step(n, emit, codes_emit, mel, none, st); }
+  s->hifigan_step(n, emit, mel, wav_out_dev, nullptr, st);
+}
+
 int conan_step(conan_streams* s, const int32_t* slots, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev,
                float* mel_out_dev, float* wav_out_dev, void* stream) {
   return guarded([&] {
@@ -383,18 +417,99 @@ int conan_step(conan_streams* s, const int32_t* slots, int n, int emit, const fl
     HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
     s->join((hipStream_t)stream);
     s->set_slots(slots, n, st);
-    int* codes_seg = codes_dev ? codes_dev : s->d_codes;
-    s->emformer_step(n, mel_chunk_dev, nullptr, nullptr, codes_seg, st);
-    const int* codes_emit = codes_seg;
-    if (emit != seg && n > 1) {
-      int* compact = s->d_codes + (size_t)s->max_slots * s->max_frames;
-      cnk::launch_copy_int_rows(compact, codes_seg, n, emit, seg, st);
-      codes_emit = compact;
-    }
-    float* mel = mel_out_dev ? mel_out_dev : s->c_mel.base;
-    { conan_decoder_taps none; memset(&none, 0, sizeof(none)); s->decoder_step(n, emit, codes_emit, mel, none, st); }
-    s->hifigan_step(n, emit, mel, wav_out_dev, nullptr, st);
+    step_blocking(s, n, emit, mel_chunk_dev, codes_dev, mel_out_dev, wav_out_dev, st);
   });
+}
+
+// Everything of conan_step_async after its argument checks; `pre` (may be empty) enqueues work on the Emformer stream right
+// before the step's Emformer launch, behind the step's input event and slot table.
+static void step_pipelined(conan_streams* s, const int32_t* slots, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev,
+                           float* mel_out_dev, float* wav_out_dev, void* stream, const std::function<void(hipStream_t)>& pre) {
+  const int seg = s->ctx->cfg.emf_segment;
+  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+  s->async_init();
+  const long long t = s->async_steps;
+  constexpr int NP = conan_streams::NP;
+  const int p = (int)(t % NP), pl = (int)((t + NP - 1) % NP);      // hand-off ring positions of this step and of the previous one
+  // Three stages on three internal streams: Emformer(t) -> codes, decoder(t) -> mel, vocoder(t) -> audio.  With steps
+  // issued back to back the stages work on consecutive chunks at the same time (Emformer of chunk t+2 beside the decoder
+  // of t+1 beside the vocoder of t): the decoder's ~50 latency-bound launches no longer queue behind the Emformer's
+  // one long launch, and their tail no longer leaves the vocoder stream idle.
+  // An EMPTY pipeline (the first step, or every earlier step has completed - e.g. behind the caller's join + synchronize): nothing of
+  // this stream-set can overlap this step's Emformer launch, which the decoder and vocoder of the same chunk wait for - it may take
+  // the blocking steps' launch shape (one workgroup per CU where the stream-set is alone on the device: 136 instead of 190 us on
+  // the first chunk's critical path; the feed-forward's sum does not depend on the cluster size, so the bits are the same).
+  s->pipe_idle = t == 0 || (hipEventQuery(s->ev_emf[pl]) == hipSuccess && hipEventQuery(s->ev_front[pl]) == hipSuccess && hipEventQuery(s->ev_voc[pl]) == hipSuccess);
+  (void)hipGetLastError();      // (hipErrorNotReady from a query is an answer, not an error)
+  // inputs are ready in the caller's stream order
+  HIP_CHECK(hipEventRecord(s->ev_in[p], (hipStream_t)stream));
+  HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_in[p], 0));
+  const bool tl = s->tl_on && s->tl_n < (int)s->tl_ev.size() / 6;
+  hipEvent_t* te = tl ? &s->tl_ev[(size_t)s->tl_n * 6] : nullptr;
+  // a changed slot list rewrites the table the in-flight decoder / vocoder still read: drain them first
+  bool same = (int)s->h_slots.size() == n;
+  for (int i = 0; same && i < n; ++i) same = s->h_slots[i] == slots[i];
+  if (!same && t >= 1) {
+    HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_front[pl], 0));
+    HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_voc[pl], 0));
+  }
+  s->set_slots(slots, n, s->st_emf);
+  // the code buffer at this ring position is free once the decoder of step t-NP has read it: the Emformer may run
+  // NP steps ahead of the decoder (it is dispatched late - its 129 KB of LDS per block only fit on CUs that a vocoder
+  // launch has left - so the decoder must not have to wait for the Emformer of its own chunk)
+  if (t >= NP) HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_front[p], 0));
+  int* codes_seg = s->codes_hand[p];
+  // developer timing switch (results are then meaningless): CONAN_SKIP_STAGE bit 0 skips the Emformer launch, bit 1 the decoder's
+#ifdef CONAN_DEV_SWITCHES        // `make DEV=1`: timing experiments only, never in the shipped library (a skipped stage returns garbage with CONAN_OK)
+  static const int skip = ch::dev_getenv("CONAN_SKIP_STAGE") ? atoi(ch::dev_getenv("CONAN_SKIP_STAGE")) : 0;
+  // (the Emformer's workgroups need whole CUs for ~0.15 ms; they are kept away from the pair kernel's launches: see ev_wide)
+  static const bool hold = ch::dev_getenv("CONAN_EMF_HOLD") != nullptr;      // (off by default: see streams.h, ev_wide)
+#else
+  constexpr int skip = 0; constexpr bool hold = false;
+#endif
+  if (hold && t >= 2 && s->ev_wide[(t + NP - 2) % NP] && s->wide_marked[(t + NP - 2) % NP]) HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_wide[(t + NP - 2) % NP], 0));
+  if (pre) pre(s->st_emf);      // conan_step_wav_async: the streaming front-end writes the chunk this step consumes
+  if (tl) HIP_CHECK(hipEventRecord(te[0], s->st_emf));
+  if (!(skip & 1)) s->emformer_step(n, mel_chunk_dev, nullptr, nullptr, codes_seg, s->st_emf);
+  if (tl) HIP_CHECK(hipEventRecord(te[1], s->st_emf));
+  HIP_CHECK(hipEventRecord(s->ev_emf[p], s->st_emf));
+  HIP_CHECK(hipStreamWaitEvent(s->st_front, s->ev_emf[p], 0));
+  // the mel hand-off buffer at this ring position is free once the vocoder of step t-NP has copied it into its ring
+  if (t >= NP) HIP_CHECK(hipStreamWaitEvent(s->st_front, s->ev_voc[p], 0));
+  if (tl) HIP_CHECK(hipEventRecord(te[2], s->st_front));
+  // the caller's copies of the step's codes and mel frames travel with the decoder step (operators of its one launch)
+  conan_streams::DecExtra ex;
+  if (codes_dev) { ex.codes_dst = codes_dev; ex.codes_src = codes_seg; ex.codes_words = n * seg; }
+  ex.mel_out2 = mel_out_dev;
+  const int* codes_emit = codes_seg;
+  if (emit != seg && n > 1) {
+    int* compact = s->d_codes + (size_t)s->max_slots * s->max_frames;
+    cnk::launch_copy_int_rows(compact, codes_seg, n, emit, seg, s->st_front);
+    codes_emit = compact;
+  }
+  float* mel = s->mel_hand[p];
+  if (!(skip & 2)) { conan_decoder_taps none; memset(&none, 0, sizeof(none)); s->decoder_step(n, emit, codes_emit, mel, none, s->st_front, &ex); }
+  if (tl) HIP_CHECK(hipEventRecord(te[3], s->st_front));
+  HIP_CHECK(hipEventRecord(s->ev_front[p], s->st_front));
+  HIP_CHECK(hipStreamWaitEvent(s->st_voc, s->ev_front[p], 0));
+  if (s->fence_set) {      // the caller's output fence: only the stage that writes the audio buffer waits for it
+    if (s->fence_event) HIP_CHECK(hipStreamWaitEvent(s->st_voc, s->fence_event, 0));
+    else {
+      HIP_CHECK(hipEventRecord(s->ev_fence[p], s->fence_stream));
+      HIP_CHECK(hipStreamWaitEvent(s->st_voc, s->ev_fence[p], 0));
+    }
+    s->fence_set = false; s->fence_event = nullptr;
+  }
+  if (tl) HIP_CHECK(hipEventRecord(te[4], s->st_voc));
+  if (!s->ev_wide[p]) HIP_CHECK(hipEventCreateWithFlags(&s->ev_wide[p], hipEventDisableTiming));
+  s->mark_wide = s->ev_wide[p];
+  s->wide_marked[p] = false;
+  s->hifigan_step(n, emit, mel, wav_out_dev, nullptr, s->st_voc);
+  s->mark_wide = nullptr;
+  if (tl) { HIP_CHECK(hipEventRecord(te[5], s->st_voc)); s->tl_n++; }
+  HIP_CHECK(hipEventRecord(s->ev_voc[p], s->st_voc));
+  if (s->clock_on && s->clock_n < (int)s->clock_ev.size()) HIP_CHECK(hipEventRecord(s->clock_ev[s->clock_n++], s->st_voc));   // step completion stamp
+  s->async_steps = t + 1;
 }
 
 // Pipelined variant of conan_step.  Within one stream-set the three stages of a chunk are strictly ordered, but the
@@ -412,89 +527,119 @@ int conan_step_async(conan_streams* s, const int32_t* slots, int n, int emit, co
     const int seg = s->ctx->cfg.emf_segment;
     if (emit < 1 || emit > seg) throw Error(CONAN_ERR_INVALID, "emit must be in [1, segment]");
     if (s->prof_on) throw Error(CONAN_ERR_STATE, "profiling is not available for pipelined steps");
+    step_pipelined(s, slots, n, emit, mel_chunk_dev, codes_dev, mel_out_dev, wav_out_dev, stream, nullptr);
+  });
+}
+
+// Waveform-in chunk steps (conan_step_wav / _async).  The host keeps each slot's position in its utterance; a call plans which
+// frames became complete (centred framing: frame f needs samples up to f * hop + n_fft / 2 - 1, or the final call: every frame of
+// 1 + samples / hop, zero padding past the end) and whether chunk t = chunks emitted so far is ready: frames [t * seg, t * seg +
+// seg + rc) complete, or - after the final call - any frame left (the short last chunks of engine.chunks: repeat-last padding).
+// One mel_stream_kernel launch (64 workgroups at 64 streams) computes the new frames, copies the chunk rows of earlier calls from the
+// mel ring and appends the samples to the audio ring (mel_stream_copy_kernel alone in drain calls that complete no frame); the chunk
+// then goes through the mel-in step.
+static void step_wav(conan_streams* s, const int32_t* slots, int n, int samples, int final_, const float* wav_dev, const conan_mel_cfg* mel,
+                     int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream, bool pipelined) {
+  if (!s || !slots || !mel || !wav_out_dev || !emit_out || (samples > 0 && !wav_dev)) throw Error(CONAN_ERR_INVALID, "null argument");
+  *emit_out = 0;
+  const conan_cfg& c = s->ctx->cfg;
+  const int all = CONAN_MODEL_EMFORMER | CONAN_MODEL_CONAN | CONAN_MODEL_HIFIGAN;
+  if ((c.models & all) != all || !s->fe_audio) throw Error(CONAN_ERR_STATE, "conan_step_wav needs all three models in the context");
+  if (c.voc_upsample == 2) throw Error(CONAN_ERR_UNSUPPORTED, "fused chunk steps carry vocoder state from chunk to chunk; upsample 'nn' (CausalUpsampleBlock1) looks ahead");
+  const conan_mel_cfg& m = *mel;
+  if (m.framing != 0) throw Error(CONAN_ERR_INVALID, "conan_step_wav: only framing 0 (centred frames, zero padding) streams");
+  if (m.fft_size < 64 || (m.fft_size & (m.fft_size - 1)) || m.fft_size > 2048) throw Error(CONAN_ERR_INVALID, "conan_step_wav: fft_size must be a power of two in [64, 2048]");
+  if (m.hop_size != s->ctx->hop) throw Error(CONAN_ERR_INVALID, "conan_step_wav: hop_size must be the vocoder's hop (conan_hop_size)");
+  if (m.num_mels != c.emf_input_dim) throw Error(CONAN_ERR_INVALID, "conan_step_wav: num_mels must be the Emformer's input width");
+  if (m.natural_log != 0 && m.natural_log != 1) throw Error(CONAN_ERR_INVALID, "conan_step_wav: natural_log must be 0 (log10) or 1 (ln)");
+  if (m.win_length < 1 || m.win_length > m.fft_size || m.sample_rate < 1 || !(m.eps > 0.f) || !(m.mag_eps >= 0.f))
+    throw Error(CONAN_ERR_INVALID, "mel front-end configuration");
+  if (n < 1 || n > s->max_slots) throw Error(CONAN_ERR_INVALID, "slot count out of range");
+  if (pipelined && s->prof_on) throw Error(CONAN_ERR_STATE, "profiling is not available for pipelined steps");
+  const int seg = c.emf_segment, rc = c.emf_right_context, hop = m.hop_size, N = m.fft_size, rows = seg + rc;
+  for (int i = 0; i < n; ++i) if (slots[i] < 0 || slots[i] >= s->max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
+  const conan_streams::FeSlot st0 = s->fe_slot[slots[0]];
+  for (int i = 1; i < n; ++i) {
+    const conan_streams::FeSlot& o = s->fe_slot[slots[i]];
+    if (o.recv != st0.recv || o.frames != st0.frames || o.chunks != st0.chunks || o.phase != st0.phase)
+      throw Error(CONAN_ERR_INVALID, "conan_step_wav: the slots of one call must be at the same position of their utterances");
+  }
+  if (st0.phase == 2) throw Error(CONAN_ERR_INVALID, "conan_step_wav: the utterance has been drained; reset the slots with CONAN_MODEL_FRONTEND first");
+  if (st0.phase == 1 && (!final_ || samples != 0)) throw Error(CONAN_ERR_INVALID, "conan_step_wav: after the final call only samples = 0, final = 1 may follow");
+  if (!final_ && samples != seg * hop) throw Error(CONAN_ERR_INVALID, "conan_step_wav: a non-final call takes exactly segment * hop samples per slot");
+  if (final_ && (samples < 0 || samples > seg * hop)) throw Error(CONAN_ERR_INVALID, "conan_step_wav: a final call takes 0 .. segment * hop samples per slot");
+  const long long R = st0.recv + samples;
+  if (final_ && R < 1) throw Error(CONAN_ERR_INVALID, "conan_step_wav: an utterance needs at least one sample");
+  // frames complete after this call, and the chunk (if any) it runs
+  const long long total_frames = final_ ? 1 + R / hop : -1;
+  const int fc = final_ ? (int)total_frames : (R >= N / 2 ? (int)((R - N / 2) / hop) + 1 : 0);
+  const int f0 = st0.frames, nnew = std::max(0, fc - f0), pos = st0.chunks * seg;
+  int emit = 0, real = 0;
+  if (final_) {
+    if (pos < fc) { emit = std::min(seg, fc - pos); real = emit + std::min(rc, fc - pos - emit); }
+  } else if (pos + rows <= fc) {
+    emit = seg; real = rows;
+  }
+  // ring spans: the samples a new frame reads and the samples appended; the frames a chunk row reads and the frames written
+  const long long a_lo = std::min<long long>(st0.recv, (long long)f0 * hop - N / 2);
+  if (R - std::max(0ll, a_lo) > s->fe_LA || fc - std::min(pos, f0) > s->fe_LM)
+    throw Error(CONAN_ERR_UNSUPPORTED, "conan_step_wav: front-end rings too small for this configuration");
+  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+  const bool run = nnew > 0 || samples > 0 || emit > 0;
+  std::function<void(hipStream_t)> front;
+  if (run) {
+    const std::string k = s->ctx->mel_tables(m);
+    const float* rg = s->ctx->vec(k + ".range");
+    cnk::MelStreamArgs a;
+    a.wav = wav_dev; a.aring = s->fe_audio; a.mring = s->fe_mel; a.chunk = s->fe_chunk; a.slots = s->d_slots;
+    a.win = s->ctx->vec(k + ".win"); a.tw = reinterpret_cast<const double2*>(s->ctx->vec(k + ".tw")); a.fb = s->ctx->vec(k + ".fb");
+    a.lo = reinterpret_cast<const int*>(rg); a.hi = reinterpret_cast<const int*>(rg) + m.num_mels;
+    a.r_prev = st0.recv; a.total = final_ ? R : -1;
+    a.m = samples; a.n = n; a.f0 = f0; a.nnew = nnew; a.pos = pos; a.rows = emit > 0 ? rows : 0; a.real = real;
+    a.LA = s->fe_LA; a.LM = s->fe_LM; a.nm = m.num_mels; a.n_fft = N; a.hop = hop; a.nb = N / 2 + 1; a.cmag = (N / 2 + 1 + 3) & ~3;
+    a.eps = m.eps; a.vmin = m.vmin; a.vmax = m.vmax; a.mag_eps = m.mag_eps; a.natural_log = m.natural_log;
+    const double flops = 4.0 * n * nnew * (double)(N / 2 + 1) * N;
+    front = [s, a, flops](hipStream_t st) {
+      if (a.nnew > 0) s->profiled("mel_stream_kernel", flops, st, [&] { cnk::launch_mel_stream(a, st); });
+      else s->profiled("mel_stream_copy_kernel", 0.0, st, [&] { cnk::launch_mel_stream_copy(a, st); });
+    };
+  }
+  if (pipelined && emit > 0) {
+    step_pipelined(s, slots, n, emit, s->fe_chunk, codes_dev, mel_out_dev, wav_out_dev, stream, front);
+  } else {
+    hipStream_t st = (hipStream_t)stream;
+    s->join(st);
+    s->set_slots(slots, n, st);
+    if (run) front(st);
+    if (emit > 0) step_blocking(s, n, emit, s->fe_chunk, codes_dev, mel_out_dev, wav_out_dev, st);
+  }
+  for (int i = 0; i < n; ++i) {
+    conan_streams::FeSlot& o = s->fe_slot[slots[i]];
+    o.recv = R; o.frames = std::max(f0, fc); o.chunks += emit > 0 ? 1 : 0;
+    o.phase = final_ ? (emit > 0 ? 1 : 2) : 0;
+  }
+  s->fe_last_n = n;
+  *emit_out = emit;
+}
+
+int conan_step_wav(conan_streams* s, const int32_t* slots, int n, int samples, int final, const float* wav_dev, const conan_mel_cfg* mel,
+                   int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream) {
+  return guarded([&] { step_wav(s, slots, n, samples, final, wav_dev, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false); });
+}
+
+int conan_step_wav_async(conan_streams* s, const int32_t* slots, int n, int samples, int final, const float* wav_dev, const conan_mel_cfg* mel,
+                         int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream) {
+  return guarded([&] { step_wav(s, slots, n, samples, final, wav_dev, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true); });
+}
+
+int conan_step_wav_chunk(conan_streams* s, float* chunk_dev, void* stream) {
+  return guarded([&] {
+    if (!s || !chunk_dev) throw Error(CONAN_ERR_INVALID, "null argument");
+    if (!s->fe_chunk || s->fe_last_n == 0) throw Error(CONAN_ERR_STATE, "conan_step_wav_chunk: no conan_step_wav call yet");
     HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-    s->async_init();
-    const long long t = s->async_steps;
-    constexpr int NP = conan_streams::NP;
-    const int p = (int)(t % NP), pl = (int)((t + NP - 1) % NP);      // hand-off ring positions of this step and of the previous one
-    // Three stages on three internal streams: Emformer(t) -> codes, decoder(t) -> mel, vocoder(t) -> audio.  With steps
-    // issued back to back the stages work on consecutive chunks at the same time (Emformer of chunk t+2 beside the decoder
-    // of t+1 beside the vocoder of t): the decoder's ~50 latency-bound launches no longer queue behind the Emformer's
-    // one long launch, and their tail no longer leaves the vocoder stream idle.
-    // An EMPTY pipeline (the first step, or every earlier step has completed - e.g. behind the caller's join + synchronize): nothing of
-    // this stream-set can overlap this step's Emformer launch, which the decoder and vocoder of the same chunk wait for - it may take
-    // the blocking steps' launch shape (one workgroup per CU where the stream-set is alone on the device: 136 instead of 190 us on
-    // the first chunk's critical path; the feed-forward's sum does not depend on the cluster size, so the bits are the same).
-    s->pipe_idle = t == 0 || (hipEventQuery(s->ev_emf[pl]) == hipSuccess && hipEventQuery(s->ev_front[pl]) == hipSuccess && hipEventQuery(s->ev_voc[pl]) == hipSuccess);
-    (void)hipGetLastError();      // (hipErrorNotReady from a query is an answer, not an error)
-    // inputs are ready in the caller's stream order
-    HIP_CHECK(hipEventRecord(s->ev_in[p], (hipStream_t)stream));
-    HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_in[p], 0));
-    const bool tl = s->tl_on && s->tl_n < (int)s->tl_ev.size() / 6;
-    hipEvent_t* te = tl ? &s->tl_ev[(size_t)s->tl_n * 6] : nullptr;
-    // a changed slot list rewrites the table the in-flight decoder / vocoder still read: drain them first
-    bool same = (int)s->h_slots.size() == n;
-    for (int i = 0; same && i < n; ++i) same = s->h_slots[i] == slots[i];
-    if (!same && t >= 1) {
-      HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_front[pl], 0));
-      HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_voc[pl], 0));
-    }
-    s->set_slots(slots, n, s->st_emf);
-    // the code buffer at this ring position is free once the decoder of step t-NP has read it: the Emformer may run
-    // NP steps ahead of the decoder (it is dispatched late - its 129 KB of LDS per block only fit on CUs that a vocoder
-    // launch has left - so the decoder must not have to wait for the Emformer of its own chunk)
-    if (t >= NP) HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_front[p], 0));
-    int* codes_seg = s->codes_hand[p];
-    // developer timing switch (results are then meaningless): CONAN_SKIP_STAGE bit 0 skips the Emformer launch, bit 1 the decoder's
-#ifdef CONAN_DEV_SWITCHES        // `make DEV=1`: timing experiments only, never in the shipped library (a skipped stage returns garbage with CONAN_OK)
-    static const int skip = ch::dev_getenv("CONAN_SKIP_STAGE") ? atoi(ch::dev_getenv("CONAN_SKIP_STAGE")) : 0;
-    // (the Emformer's workgroups need whole CUs for ~0.15 ms; they are kept away from the pair kernel's launches: see ev_wide)
-    static const bool hold = ch::dev_getenv("CONAN_EMF_HOLD") != nullptr;      // (off by default: see streams.h, ev_wide)
-#else
-    constexpr int skip = 0; constexpr bool hold = false;
-#endif
-    if (hold && t >= 2 && s->ev_wide[(t + NP - 2) % NP] && s->wide_marked[(t + NP - 2) % NP]) HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_wide[(t + NP - 2) % NP], 0));
-    if (tl) HIP_CHECK(hipEventRecord(te[0], s->st_emf));
-    if (!(skip & 1)) s->emformer_step(n, mel_chunk_dev, nullptr, nullptr, codes_seg, s->st_emf);
-    if (tl) HIP_CHECK(hipEventRecord(te[1], s->st_emf));
-    HIP_CHECK(hipEventRecord(s->ev_emf[p], s->st_emf));
-    HIP_CHECK(hipStreamWaitEvent(s->st_front, s->ev_emf[p], 0));
-    // the mel hand-off buffer at this ring position is free once the vocoder of step t-NP has copied it into its ring
-    if (t >= NP) HIP_CHECK(hipStreamWaitEvent(s->st_front, s->ev_voc[p], 0));
-    if (tl) HIP_CHECK(hipEventRecord(te[2], s->st_front));
-    // the caller's copies of the step's codes and mel frames travel with the decoder step (operators of its one launch)
-    conan_streams::DecExtra ex;
-    if (codes_dev) { ex.codes_dst = codes_dev; ex.codes_src = codes_seg; ex.codes_words = n * seg; }
-    ex.mel_out2 = mel_out_dev;
-    const int* codes_emit = codes_seg;
-    if (emit != seg && n > 1) {
-      int* compact = s->d_codes + (size_t)s->max_slots * s->max_frames;
-      cnk::launch_copy_int_rows(compact, codes_seg, n, emit, seg, s->st_front);
-      codes_emit = compact;
-    }
-    float* mel = s->mel_hand[p];
-    if (!(skip & 2)) { conan_decoder_taps none; memset(&none, 0, sizeof(none)); s->decoder_step(n, emit, codes_emit, mel, none, s->st_front, &ex); }
-    if (tl) HIP_CHECK(hipEventRecord(te[3], s->st_front));
-    HIP_CHECK(hipEventRecord(s->ev_front[p], s->st_front));
-    HIP_CHECK(hipStreamWaitEvent(s->st_voc, s->ev_front[p], 0));
-    if (s->fence_set) {      // the caller's output fence: only the stage that writes the audio buffer waits for it
-      if (s->fence_event) HIP_CHECK(hipStreamWaitEvent(s->st_voc, s->fence_event, 0));
-      else {
-        HIP_CHECK(hipEventRecord(s->ev_fence[p], s->fence_stream));
-        HIP_CHECK(hipStreamWaitEvent(s->st_voc, s->ev_fence[p], 0));
-      }
-      s->fence_set = false; s->fence_event = nullptr;
-    }
-    if (tl) HIP_CHECK(hipEventRecord(te[4], s->st_voc));
-    if (!s->ev_wide[p]) HIP_CHECK(hipEventCreateWithFlags(&s->ev_wide[p], hipEventDisableTiming));
-    s->mark_wide = s->ev_wide[p];
-    s->wide_marked[p] = false;
-    s->hifigan_step(n, emit, mel, wav_out_dev, nullptr, s->st_voc);
-    s->mark_wide = nullptr;
-    if (tl) { HIP_CHECK(hipEventRecord(te[5], s->st_voc)); s->tl_n++; }
-    HIP_CHECK(hipEventRecord(s->ev_voc[p], s->st_voc));
-    if (s->clock_on && s->clock_n < (int)s->clock_ev.size()) HIP_CHECK(hipEventRecord(s->clock_ev[s->clock_n++], s->st_voc));   // step completion stamp
-    s->async_steps = t + 1;
+    s->join((hipStream_t)stream);
+    const size_t floats = (size_t)s->fe_last_n * (s->ctx->cfg.emf_segment + s->ctx->cfg.emf_right_context) * s->ctx->cfg.emf_input_dim;
+    HIP_CHECK(hipMemcpyAsync(chunk_dev, s->fe_chunk, floats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   });
 }
 

@@ -79,6 +79,100 @@ __global__ __launch_bounds__(256) void mel_log_kernel(const MelArgs a) {
   a.y[e] = fminf(fmaxf(v, a.vmin), a.vmax);
 }
 
+// The part of a call's front-end that computes nothing, for slot i: the chunk rows that earlier calls computed, from the mel ring,
+// and this call's samples appended to the audio ring.  Neither touches a ring position that the frame computation of the same call
+// reads or writes (the host checks the ring spans), so it runs beside it in any order.
+__device__ inline void mel_stream_copy(const MelStreamArgs& a, int i) {
+  const int slot = a.slots[i];
+  const float* mr = a.mring + (long long)slot * a.LM * a.nm;
+  for (int e = threadIdx.x; e < a.rows * a.nm; e += blockDim.x) {
+    const int r = e / a.nm, mm = e - r * a.nm, src = a.pos + min(r, a.real - 1);
+    if (src < a.f0) a.chunk[((long long)i * a.rows + r) * a.nm + mm] = mr[(long long)(src & (a.LM - 1)) * a.nm + mm];
+  }
+  float* ar = a.aring + (long long)slot * a.LA;
+  for (int j = threadIdx.x; j < a.m; j += blockDim.x) ar[(a.r_prev + j) & (a.LA - 1)] = a.wav[(long long)i * a.m + j];
+}
+
+// Streaming front-end (conan_step_wav): only the frames that became complete in this call, for all active slots in ONE launch,
+// written straight into the slot's mel ring and the [n][rows][nm] chunk the step consumes.  Each frame is bit-identical to
+// stft_frames_kernel -> dft_mag_kernel -> mel_log_kernel: the same f32 windowed samples, the same f64 FMA chains over t in the
+// same order per bin, the same magnitude and filterbank expressions (a frame depends on its own n_fft samples only).
+// Tiling: a workgroup takes kMelStreamFrames frames; its threads take bins, each thread all the workgroup's frames of its bin, so a
+// twiddle read from LDS (a gather: 16 B per lane) feeds 2 * kMelStreamFrames f64 FMAs and the samples of the frames are LDS
+// broadcasts.  64 streams x 4 frames = 64 workgroups: a quarter of the CUs, beside the previous chunk's vocoder.  The same
+// workgroups also do the call's copy / append work (mel_stream_copy), so the front-end is one launch per call.
+__global__ __launch_bounds__(1024) void mel_stream_kernel(const MelStreamArgs a) {
+  constexpr int F = kMelStreamFrames;
+  extern __shared__ __attribute__((aligned(16))) double msm[];
+  const int N = a.n_fft;
+  const int jobs = a.n * a.nnew;
+  for (int i = blockIdx.x; i < a.n; i += gridDim.x) mel_stream_copy(a, i);     // the copy / append work of the call, spread over the grid
+  double* x = msm;                                                   // [N][F]
+  double2* tw = reinterpret_cast<double2*>(msm + (size_t)N * F);     // [N]
+  float* mag = reinterpret_cast<float*>(tw + N);                     // [F][cmag]
+  const int job0 = blockIdx.x * F;
+  for (int e = threadIdx.x; e < N * F; e += blockDim.x) {
+    const int j = e / N, k = e - j * N, job = job0 + j;
+    float v = 0.f;
+    if (job < jobs) {
+      const int i = job / a.nnew, f = a.f0 + (job - i * a.nnew);
+      const long long smp = (long long)f * a.hop - N / 2 + k;      // center=True, pad_mode='constant'
+      if (smp >= 0 && (a.total < 0 || smp < a.total)) {
+        const float xs = smp >= a.r_prev ? a.wav[(long long)i * a.m + (smp - a.r_prev)] : a.aring[(long long)a.slots[i] * a.LA + (smp & (a.LA - 1))];
+        v = xs * a.win[k];
+      }
+    }
+    x[(size_t)k * F + j] = (double)v;
+  }
+  for (int t = threadIdx.x; t < N; t += blockDim.x) tw[t] = a.tw[t];
+  __syncthreads();
+  const int mask = N - 1;
+  for (int b = threadIdx.x; b < a.cmag; b += blockDim.x) {
+    if (b >= a.nb) { for (int j = 0; j < F; ++j) mag[j * a.cmag + b] = 0.f; continue; }
+    double re[F], im[F];
+    for (int j = 0; j < F; ++j) { re[j] = 0.0; im[j] = 0.0; }
+    int idx = 0;
+    for (int t = 0; t < N; ++t) {
+      const double2 w = tw[idx];
+#pragma unroll
+      for (int j = 0; j < F; ++j) { const double xv = x[(size_t)t * F + j]; re[j] = fma(xv, w.x, re[j]); im[j] = fma(xv, w.y, im[j]); }
+      idx = (idx + b) & mask;
+    }
+#pragma unroll
+    for (int j = 0; j < F; ++j) mag[j * a.cmag + b] = (float)sqrt(re[j] * re[j] + im[j] * im[j] + (double)a.mag_eps);
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < F * a.nm; e += blockDim.x) {
+    const int j = e / a.nm, mm = e - j * a.nm, job = job0 + j;
+    if (job >= jobs) continue;
+    const int i = job / a.nnew, f = a.f0 + (job - i * a.nnew);
+    const float* mg = mag + j * a.cmag;
+    const float* w = a.fb + (long long)mm * a.cmag;
+    double s = 0.0;
+    for (int b = a.lo[mm]; b < a.hi[mm]; ++b) s = fma((double)w[b], (double)mg[b], s);
+    const float c = fmaxf(a.eps, (float)s);
+    const float v = fminf(fmaxf(a.natural_log ? logf(c) : log10f(c), a.vmin), a.vmax);
+    a.mring[((long long)a.slots[i] * a.LM + (f & (a.LM - 1))) * a.nm + mm] = v;
+    for (int r = 0; r < a.rows; ++r)
+      if (a.pos + min(r, a.real - 1) == f) a.chunk[((long long)i * a.rows + r) * a.nm + mm] = v;
+  }
+}
+
+// Drain calls that complete no frame: the copy / append part alone, one small workgroup per slot (no LDS).
+__global__ __launch_bounds__(256) void mel_stream_copy_kernel(const MelStreamArgs a) { mel_stream_copy(a, blockIdx.x); }
+
+void launch_mel_stream(const MelStreamArgs& a, hipStream_t st) {
+  const int blocks = (a.n * a.nnew + kMelStreamFrames - 1) / kMelStreamFrames;
+  const int threads = std::min(1024, (a.nb + 63) / 64 * 64);
+  const size_t lds = mel_stream_lds_bytes(a.n_fft, a.cmag);
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)mel_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipLaunchKernelGGL(mel_stream_kernel, dim3(blocks), dim3(threads), lds, st, a);
+}
+
+void launch_mel_stream_copy(const MelStreamArgs& a, hipStream_t st) {    // only for calls without new frames
+  hipLaunchKernelGGL(mel_stream_copy_kernel, dim3(a.n), dim3(256), 0, st, a);
+}
+
 }  // namespace cnk
 
 namespace {
@@ -101,15 +195,9 @@ int conan_mel_frames(const conan_mel_cfg& m, int samples) {
   return padded < m.fft_size ? 0 : (padded - m.fft_size) / m.hop_size + 1;
 }
 
-void conan_ctx::wav2mel(const conan_mel_cfg& m, const float* wav, int n, int samples, float* mel_out, hipStream_t st) {
-  using ch::Error;
-  if (m.fft_size < 64 || (m.fft_size & (m.fft_size - 1)) || m.fft_size > 2048 || m.hop_size < 1 || m.win_length < 1 || m.win_length > m.fft_size ||
-      m.num_mels < 1 || m.num_mels > 512 || m.sample_rate < 1 || !(m.eps > 0.f))
-    throw Error(CONAN_ERR_INVALID, "mel front-end configuration");
-  if (n < 1 || samples < 1) throw Error(CONAN_ERR_INVALID, "wav2mel batch / samples");
-  if (m.framing < 0 || m.framing > 1 || !(m.mag_eps >= 0.f)) throw Error(CONAN_ERR_INVALID, "mel front-end framing / mag_eps");
-  // reflect padding needs pad < samples (torch raises otherwise); frames = (samples + 2 pad - n_fft) / hop + 1
-  if (m.framing == 1 && ((m.fft_size - m.hop_size) / 2 >= samples || m.hop_size > m.fft_size)) throw Error(CONAN_ERR_INVALID, "wav2mel: reflect padding longer than the signal");
+// Window, twiddle and filterbank tables of a mel configuration, built and uploaded on first use; returns their key prefix
+// in vecs ("<key>.win", ".tw", ".fb", ".range").  Shared by conan_wav2mel and the streaming front-end (streams.hip).
+std::string conan_ctx::mel_tables(const conan_mel_cfg& m) {
   const int N = m.fft_size, NB = N / 2 + 1, CM = (NB + 3) & ~3;
   const double fmin = m.fmin < 0 ? 0.0 : m.fmin, fmax = m.fmax < 0 ? m.sample_rate / 2.0 : m.fmax;
   char key[160];
@@ -152,6 +240,20 @@ void conan_ctx::wav2mel(const conan_mel_cfg& m, const float* wav, int n, int sam
     vecs[k + ".fb"] = upload(B);
     vecs[k + ".range"] = upload(range);
   }
+  return k;
+}
+
+void conan_ctx::wav2mel(const conan_mel_cfg& m, const float* wav, int n, int samples, float* mel_out, hipStream_t st) {
+  using ch::Error;
+  if (m.fft_size < 64 || (m.fft_size & (m.fft_size - 1)) || m.fft_size > 2048 || m.hop_size < 1 || m.win_length < 1 || m.win_length > m.fft_size ||
+      m.num_mels < 1 || m.num_mels > 512 || m.sample_rate < 1 || !(m.eps > 0.f))
+    throw Error(CONAN_ERR_INVALID, "mel front-end configuration");
+  if (n < 1 || samples < 1) throw Error(CONAN_ERR_INVALID, "wav2mel batch / samples");
+  if (m.framing < 0 || m.framing > 1 || !(m.mag_eps >= 0.f)) throw Error(CONAN_ERR_INVALID, "mel front-end framing / mag_eps");
+  // reflect padding needs pad < samples (torch raises otherwise); frames = (samples + 2 pad - n_fft) / hop + 1
+  if (m.framing == 1 && ((m.fft_size - m.hop_size) / 2 >= samples || m.hop_size > m.fft_size)) throw Error(CONAN_ERR_INVALID, "wav2mel: reflect padding longer than the signal");
+  const int N = m.fft_size, NB = N / 2 + 1, CM = (NB + 3) & ~3;
+  const std::string k = mel_tables(m);
   const int frames = conan_mel_frames(m, samples);
   if (frames < 1) throw Error(CONAN_ERR_INVALID, "wav2mel: signal shorter than one frame");
   const long long rows = (long long)n * frames;

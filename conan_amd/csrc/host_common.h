@@ -123,5 +123,6 @@ struct conan_ctx {
   // mel front-end (frontend.hip): tables are built on first use per configuration; one workspace, regrown when a call needs more
   float* fe_ws = nullptr; size_t fe_ws_floats = 0;
   void wav2mel(const conan_mel_cfg& m, const float* wav, int n, int samples, float* mel_out, hipStream_t st);
+  std::string mel_tables(const conan_mel_cfg& m);          // window / twiddle / filterbank tables (vecs key prefix)
   ~conan_ctx();
 };

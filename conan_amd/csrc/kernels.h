@@ -506,6 +506,25 @@ void launch_scatter_ids(int* dst, const int* slots, const int* src, const int* l
 void launch_gather_ids(int* dst, int* cnt, const int* src, const int* slen, const int* slots, int n, int S_max, hipStream_t st);
 void launch_scatter_rows(float* dst, const float* src, const int* slots, int n, int C, hipStream_t st);   // dst[slots[i]][:] = src[i][:]
 void launch_zero_slots(float* base, long long slot_stride, long long count, const int* slots, int n, hipStream_t st);
+// streaming mel front-end (frontend.hip, conan_step_wav): the frames [f0, f0 + nnew) of each of the n slots plus the chunk rows
+// row r <- frame pos + min(r, real - 1), r < rows (rows = 0: no chunk in this call)
+constexpr int kMelStreamFrames = 4;     // frames per workgroup
+struct MelStreamArgs {
+  const float* wav;          // [n][m] this call's samples
+  float* aring;              // [slot][LA] audio ring: sample s at s & (LA - 1)
+  float* mring;              // [slot][LM][nm] mel ring: frame f at f & (LM - 1)
+  float* chunk;              // [n][rows][nm]
+  const int* slots;
+  const float* win; const double2* tw; const float* fb; const int* lo; const int* hi;
+  long long r_prev, total;   // samples received before this call; utterance length once final (-1 before)
+  int m, n, f0, nnew, pos, rows, real;
+  int LA, LM, nm, n_fft, hop, nb, cmag;
+  float eps, vmin, vmax, mag_eps;
+  int natural_log;           // 0: log10, 1: ln (as mel_log_kernel)
+};
+inline size_t mel_stream_lds_bytes(int n_fft, int cmag) { return (size_t)n_fft * kMelStreamFrames * 8 + (size_t)n_fft * 16 + (size_t)kMelStreamFrames * cmag * 4; }
+void launch_mel_stream(const MelStreamArgs& a, hipStream_t st);        // nnew > 0: the new frames, the old chunk rows, the samples
+void launch_mel_stream_copy(const MelStreamArgs& a, hipStream_t st);   // nnew = 0: old chunk rows from the mel ring, samples into the audio ring
 
 // ---- style pass (per utterance) helpers
 struct RowMaskArgs { TRef x; TRef m; const int* lens; int T, n, C; int mode; };  // mode 0: sum|x|>0, 1: x[0]!=0

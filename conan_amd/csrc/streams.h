@@ -127,6 +127,13 @@ struct conan_streams {
                                        "): results since then are invalid and this stream-set is unusable - destroy it and create a new one");
   }
 
+  // --- streaming front-end (conan_step_wav): per slot an audio ring (sample s at s & (fe_LA - 1)) and a ring of computed log-mel
+  // frames (frame f at f & (fe_LM - 1)); fe_chunk = the [n][seg + rc][num_mels] chunk the step consumes.  Host side, per slot: samples
+  // received, frames computed, chunks emitted, phase (0 open, 1 the final call has come, 2 drained)
+  float* fe_audio = nullptr; float* fe_mel = nullptr; float* fe_chunk = nullptr;
+  int fe_LA = 0, fe_LM = 0, fe_last_n = 0;
+  struct FeSlot { long long recv = 0; int frames = 0, chunks = 0, phase = 0; };
+  std::vector<FeSlot> fe_slot;
   // --- vocoder
   Ring v_mel, v_pre;
   std::vector<VocStage> v_st;

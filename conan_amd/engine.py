@@ -212,9 +212,51 @@ class StreamingVoiceConversionEngine:
         self.slots = list(range(n_streams))
         self.seg, self.rc = ctx.cfg.emf_segment, ctx.cfg.emf_right_context
 
-    def start(self, ref_mel, ref_len=None):
-        self.st.reset(self.slots)
+    def start(self, ref_mel, ref_len=None, which=7):
+        self.st.reset(self.slots, which=which)
         self.st.set_reference(self.slots, ref_mel, ref_len)
+
+    def start_wav(self, ref_mel, ref_len=None):
+        """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio."""
+        self.start(ref_mel, ref_len, which=7 | 8)
+
+    @torch.no_grad()
+    def feed(self, wav_chunk, final=False, pipelined=False, mel=None):
+        """Streaming waveform input (conan_step_wav): wav_chunk [B, seg*hop] (cuda; 0 .. seg*hop samples when final) ->
+        (wav [B, emit*hop], mel [B, emit, 80], codes [B, emit]) of the chunk this call emitted (emit = 0 on the first call: one
+        chunk of algorithmic latency).  After final=True keep calling feed(empty, final=True) until it returns 0 frames.
+        pipelined: conan_step_wav_async - the tensors are complete after self.st.join()."""
+        fn = self.st.step_wav_async if pipelined else self.st.step_wav
+        emit, c, m, w = fn(self.slots, wav_chunk, final=final, mel=mel)
+        return w, m, c[:, :emit]
+
+    @torch.no_grad()
+    def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None):
+        """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
+        the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit."""
+        self.start_wav(ref_mel, ref_len)
+        B, N = src_wav.shape
+        L = self.seg * self.ctx.hop
+        last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
+        empty = src_wav.new_zeros(B, 0)
+        wavs, mels, codes = [], [], []
+        pos, final = 0, False
+        while True:
+            if pos < last:
+                w, m, c = self.feed(src_wav[:, pos:pos + L], pipelined=pipelined, mel=mel)
+                pos += L
+            else:
+                w, m, c = self.feed(src_wav[:, pos:] if not final else empty, final=True, pipelined=pipelined, mel=mel)
+                pos, done, final = N, final and m.shape[1] == 0, True
+                if done:
+                    break
+            if m.shape[1]:
+                wavs.append(w)
+                mels.append(m)
+                codes.append(c)
+        if pipelined:
+            self.st.join()
+        return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     def chunks(self, src_mel):
         """inference/Conan.py:95-110: (pos, emit, chunk[B, seg+rc, 80]) with repeat-last padding."""

@@ -30,6 +30,13 @@ def _i32(a):
     return a, a.ctypes.data_as(C.c_void_p)
 
 
+def mel_cfg(fft_size=1024, hop_size=320, win_length=1024, num_mels=80, fmin=80, fmax=7600, sample_rate=16000, eps=1e-6,
+            mel_vmin=-6.0, mel_vmax=1.5, framing=0, natural_log=False, mag_eps=0.0):
+    """conan_mel_cfg with Context.wav2mel's defaults (inference/Conan.py:57-70)."""
+    return _lib.MelCfg(fft_size, hop_size, win_length, num_mels, sample_rate, float(fmin), float(fmax), eps, mel_vmin, mel_vmax,
+                       int(framing), int(bool(natural_log)), float(mag_eps))
+
+
 class Context:
     """conan_ctx: packed weights of up to three models on one device."""
 
@@ -314,6 +321,47 @@ class Streams:
             else:
                 _lib.check(self.lib.conan_streams_output_fence(self.h, C.c_void_p(out_fence.cuda_stream)))
         _lib.check(self.lib.conan_step_async(self.h, p, n, emit, _ptr(mel_chunk), _ptr(codes), _ptr(mel_out), _ptr(wav_out), _stream()))
+
+    def step_wav(self, slots, wav, final=False, codes=None, mel_out=None, wav_out=None, mel=None):
+        """Waveform-in chunk step (conan_step_wav): wav [n, samples] cuda float32, samples = seg*hop (0 .. seg*hop when final).
+        -> (emit, codes [n, seg], mel [n, emit, 80], wav [n, emit*hop]); emit = 0: no chunk this call (the first call, the end of a
+        drain).  mel: dict of Context.wav2mel's front-end keywords (framing 0 only)."""
+        return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, False)
+
+    def step_wav_async(self, slots, wav, final=False, codes=None, mel_out=None, wav_out=None, mel=None):
+        """Pipelined step_wav (conan_step_wav_async): the outputs are complete after join(); same return value."""
+        return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, True)
+
+    def _step_wav(self, slots, wav, final, codes, mel_out, wav_out, mel, pipelined):
+        a, p = _i32(slots)
+        n = len(a)
+        hop, nm = self.ctx.hop, self.ctx.cfg.num_mels
+        wav = wav.to(self.dev, torch.float32).contiguous()
+        assert wav.dim() == 2 and wav.shape[0] == n, wav.shape
+        if codes is None:
+            codes = torch.empty(n, self.seg, dtype=torch.int32, device=self.dev)
+        if mel_out is None:
+            mel_out = torch.empty(n, self.seg, nm, device=self.dev)
+        if wav_out is None:
+            wav_out = torch.empty(n, self.seg * hop, device=self.dev)
+        mc = mel_cfg(**(mel or {}))
+        emit = C.c_int32(0)
+        fn = self.lib.conan_step_wav_async if pipelined else self.lib.conan_step_wav
+        if pipelined:
+            self._keep.append((wav, wav_out, codes, mel_out))
+        _lib.check(fn(self.h, p, n, wav.shape[1], int(bool(final)), _ptr(wav), C.byref(mc), _ptr(codes), _ptr(mel_out), _ptr(wav_out),
+                      C.byref(emit), _stream()))
+        if not pipelined:
+            self._release()
+        e = emit.value
+        return e, codes, mel_out.view(-1)[:n * e * nm].view(n, e, nm), wav_out.view(-1)[:n * e * hop].view(n, e * hop)
+
+    def wav_chunk(self, n):
+        """The [n, seg+rc, 80] mel chunk the last step_wav call assembled (conan_step_wav_chunk; joins pipelined work)."""
+        out = torch.empty(n, self.seg + self.rc, self.ctx.cfg.emf_input_dim, device=self.dev)
+        _lib.check(self.lib.conan_step_wav_chunk(self.h, _ptr(out), _stream()))
+        self._release()
+        return out
 
     def join(self):
         """Make the current torch stream wait for every pipelined step enqueued so far."""

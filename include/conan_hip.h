@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define CONAN_HIP_ABI_VERSION 8
+#define CONAN_HIP_ABI_VERSION 9
 
 typedef enum conan_status {
   CONAN_OK = 0,
@@ -89,6 +89,7 @@ typedef struct conan_cfg {
 #define CONAN_MODEL_EMFORMER 1
 #define CONAN_MODEL_CONAN 2
 #define CONAN_MODEL_HIFIGAN 4
+#define CONAN_MODEL_FRONTEND 8   /* conan_streams_reset only (ABI 9): the streaming front-end of conan_step_wav */
 
 typedef struct conan_ctx conan_ctx;          /* per device: packed weights, workspaces */
 typedef struct conan_streams conan_streams;  /* per-slot streaming state               */
@@ -183,7 +184,8 @@ int conan_streams_create_opts(conan_ctx* ctx, int max_slots, int max_frames, int
 int conan_streams_arith(const conan_streams* s);
 
 /* Start of utterance for the given slots (replaces `state = None` inference/Conan.py:92 and the
- * zero left-padding of every causal conv).  which = bitmask of CONAN_MODEL_*. */
+ * zero left-padding of every causal conv).  which = bitmask of CONAN_MODEL_*; CONAN_MODEL_FRONTEND clears the slots'
+ * conan_step_wav state (no samples seen yet: the zero left-padding of centred framing). */
 int conan_streams_reset(conan_streams* s, const int32_t* slots, int n, int which, void* stream);
 
 /* Per-utterance style pass = the reference-mel-only part of Conan.forward
@@ -318,6 +320,30 @@ typedef struct conan_mel_cfg {
 } conan_mel_cfg;
 int conan_wav2mel(conan_ctx* ctx, const conan_mel_cfg* cfg, const float* wav_dev, int n, int samples,
                   float* mel_out_dev, int32_t* frames_out, void* stream);
+
+/* Waveform-in chunk step (ABI 9): the whole-utterance front-end of conan_wav2mel (framing 0) computed incrementally per slot, then
+ * conan_step / conan_step_async on the chunk.  wav_dev[n][samples] are the slots' next samples; all slots of a call must be at the
+ * same position of their utterances (started by a reset with CONAN_MODEL_FRONTEND, then fed the same calls).
+ *   - a non-final call passes exactly seg * hop samples per slot (1280 at the shipped config), a final call 0 .. seg * hop;
+ *   - a call runs at most ONE chunk step and reports its frame count in *emit_out (host): chunk t runs as soon as its frames
+ *     [t * seg, t * seg + seg + rc) are complete - centred frame f needs samples up to f * hop + fft_size / 2 - 1 - so chunk t
+ *     comes out of call t + 1 and the first call emits 0: an algorithmic latency of one chunk (80 ms);
+ *   - after the final call the caller keeps calling with samples = 0, final = 1 until *emit_out == 0 (one or two more chunks).
+ *     The drain frames the whole utterance as conan_wav2mel does (zero padding past the end, 1 + N / hop frames) and pads a
+ *     short last chunk by repeating its last frame (StreamingVoiceConversionEngine.chunks, inference/Conan.py:95-110);
+ *   - the outputs are those of conan_step fed the same chunk: codes_dev[n][seg], mel_out_dev[n][emit][num_mels] (may be NULL),
+ *     wav_out_dev[n][emit * hop]; size them for emit = seg.  Each frame equals conan_wav2mel's bit for bit.
+ * mel: framing 0 only (natural_log and mag_eps are honoured as by conan_wav2mel); fft_size a power of two <= 2048;
+ * hop_size = conan_hop_size(); num_mels = the Emformer's input width.
+ * Anything else, a wrong `samples`, or a call after the drain returned 0 is CONAN_ERR_INVALID. */
+int conan_step_wav(conan_streams* s, const int32_t* slots, int n, int samples, int final, const float* wav_dev, const conan_mel_cfg* mel,
+                   int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream);
+/* Pipelined conan_step_wav: the front-end launch and the step go to the internal streams as in conan_step_async (same ordering
+ * rules; wav_dev and the outputs must stay valid until conan_streams_join).  Calls that emit nothing run on `stream`. */
+int conan_step_wav_async(conan_streams* s, const int32_t* slots, int n, int samples, int final, const float* wav_dev, const conan_mel_cfg* mel,
+                         int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream);
+/* Test / debug hook: copy the mel chunk the last conan_step_wav call assembled, chunk_dev[n][seg + rc][num_mels] (joins first). */
+int conan_step_wav_chunk(conan_streams* s, float* chunk_dev, void* stream);
 
 /* Measurement hook (replaces the reference's Timer('hifigan') around the vocoder forward,
  * utils/commons/meters.py:21-42, tasks/tts/vocoder_infer/hifigan.py:28): between begin and end every
