@@ -90,6 +90,10 @@ _PROTOS = {
     "conan_step_wav_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_step_wav_chunk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_step_wav_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_step_wav_ragged_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_streams_output_fence": (C.c_int, [C.c_void_p, C.c_void_p]),
     "conan_streams_output_fence_event": (C.c_int, [C.c_void_p, C.c_void_p]),
     "conan_streams_test_fault": (C.c_int, [C.c_void_p, C.c_int]),

@@ -619,6 +619,7 @@ static void step_wav(conan_streams* s, const int32_t* slots, int n, int samples,
     o.phase = final_ ? (emit > 0 ? 1 : 2) : 0;
   }
   s->fe_last_n = n;
+  s->fe_last_ragged = false;
   *emit_out = emit;
 }
 
@@ -632,10 +633,195 @@ int conan_step_wav_async(conan_streams* s, const int32_t* slots, int n, int samp
   return guarded([&] { step_wav(s, slots, n, samples, final, wav_dev, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true); });
 }
 
+void conan_streams::ragged_init() {
+  if (rg_tab[0]) return;
+  const conan_cfg& c = ctx->cfg;
+  const size_t seg = c.emf_segment;
+  auto dev = [&](size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, bytes)); allocs.push_back(p); return p; };
+  for (int q = 0; q < NS; ++q) {
+    rg_tab[q] = (int*)dev((size_t)max_slots * cnk::kRaggedWords * sizeof(int));
+    rg_codes[q] = (int*)dev((size_t)max_slots * seg * sizeof(int));
+    rg_mel[q] = (float*)dev((size_t)max_slots * seg * c.num_mels * sizeof(float));
+    rg_wav[q] = (float*)dev((size_t)max_slots * seg * ctx->hop * sizeof(float));
+    HIP_CHECK(hipEventCreateWithFlags(&ev_stage[q], hipEventDisableTiming));
+  }
+  fe_pin.init((size_t)max_slots * cnk::kRaggedWords);
+}
+
+// Waveform-in chunk steps for slots at different positions of their utterances (conan_step_wav_ragged / _async).  Each slot gets
+// step_wav's plan from its own FeSlot; the emitting slots are grouped by emit and each group runs one mel-in chunk step (blocking or
+// pipelined) on its own slot list.  One mel_stream_ragged_kernel launch, in front of the first group's Emformer, does the front-end
+// work of every slot of the call, driven by a [n][kRaggedWords] row table; it writes each group's chunk contiguously into fe_chunk.
+// A call whose slots all emit a full chunk is one group in call order and writes the caller's buffers directly; otherwise the groups
+// write staging (set q of NS) and wav_rows_scatter_kernel puts the rows in call order.
+static void step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final_, const float* wav_dev,
+                            const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream,
+                            bool pipelined) {
+  if (!s || !slots || !samples || !final_ || !mel || !wav_out_dev || !emit_out) throw Error(CONAN_ERR_INVALID, "null argument");
+  const conan_cfg& c = s->ctx->cfg;
+  const int all = CONAN_MODEL_EMFORMER | CONAN_MODEL_CONAN | CONAN_MODEL_HIFIGAN;
+  if ((c.models & all) != all || !s->fe_audio) throw Error(CONAN_ERR_STATE, "conan_step_wav_ragged needs all three models in the context");
+  if (c.voc_upsample == 2) throw Error(CONAN_ERR_UNSUPPORTED, "fused chunk steps carry vocoder state from chunk to chunk; upsample 'nn' (CausalUpsampleBlock1) looks ahead");
+  const conan_mel_cfg& m = *mel;
+  if (m.framing != 0) throw Error(CONAN_ERR_INVALID, "conan_step_wav_ragged: only framing 0 (centred frames, zero padding) streams");
+  if (m.fft_size < 64 || (m.fft_size & (m.fft_size - 1)) || m.fft_size > 2048) throw Error(CONAN_ERR_INVALID, "conan_step_wav_ragged: fft_size must be a power of two in [64, 2048]");
+  if (m.hop_size != s->ctx->hop) throw Error(CONAN_ERR_INVALID, "conan_step_wav_ragged: hop_size must be the vocoder's hop (conan_hop_size)");
+  if (m.num_mels != c.emf_input_dim) throw Error(CONAN_ERR_INVALID, "conan_step_wav_ragged: num_mels must be the Emformer's input width");
+  if (m.natural_log != 0 && m.natural_log != 1) throw Error(CONAN_ERR_INVALID, "conan_step_wav_ragged: natural_log must be 0 (log10) or 1 (ln)");
+  if (m.win_length < 1 || m.win_length > m.fft_size || m.sample_rate < 1 || !(m.eps > 0.f) || !(m.mag_eps >= 0.f))
+    throw Error(CONAN_ERR_INVALID, "mel front-end configuration");
+  if (n < 1 || n > s->max_slots) throw Error(CONAN_ERR_INVALID, "slot count out of range");
+  if (pipelined && s->prof_on) throw Error(CONAN_ERR_STATE, "profiling is not available for pipelined steps");
+  const int seg = c.emf_segment, rc = c.emf_right_context, hop = m.hop_size, N = m.fft_size, rows = seg + rc;
+  std::vector<char> seen(s->max_slots, 0);
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] >= s->max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
+    if (seen[slots[i]]) throw Error(CONAN_ERR_INVALID, "duplicate slot");
+    seen[slots[i]] = 1;
+  }
+  // every slot's plan first (step_wav's, from the slot's own position): nothing changes before all of them have passed
+  struct Plan { long long R, total; int fc, f0, nnew, pos, emit, real; };
+  std::vector<Plan> pl(n);
+  bool run = false;
+  for (int i = 0; i < n; ++i) {
+    const conan_streams::FeSlot& o = s->fe_slot[slots[i]];
+    const int sm = samples[i], fin = final_[i];
+    auto bad = [&](const char* what) {
+      throw Error(CONAN_ERR_INVALID, std::string("conan_step_wav_ragged: slot ") + std::to_string(slots[i]) + " (call row " + std::to_string(i) + "): " + what);
+    };
+    if (fin != 0 && fin != 1) bad("final must be 0 or 1");
+    if (o.phase == 2) bad("the utterance has been drained; reset the slot with CONAN_MODEL_FRONTEND first");
+    if (o.phase == 1 && (!fin || sm != 0)) bad("after the final call only samples = 0, final = 1 may follow");
+    if (!fin && sm != seg * hop) bad("a non-final call takes exactly segment * hop samples per slot");
+    if (fin && (sm < 0 || sm > seg * hop)) bad("a final call takes 0 .. segment * hop samples per slot");
+    if (sm > 0 && !wav_dev) throw Error(CONAN_ERR_INVALID, "null argument (wav_dev with samples > 0)");
+    Plan& p = pl[i];
+    p.R = o.recv + sm;
+    if (fin && p.R < 1) bad("an utterance needs at least one sample");
+    p.total = fin ? p.R : -1;
+    p.fc = fin ? (int)(1 + p.R / hop) : (p.R >= N / 2 ? (int)((p.R - N / 2) / hop) + 1 : 0);
+    p.f0 = o.frames; p.nnew = std::max(0, p.fc - p.f0); p.pos = o.chunks * seg;
+    p.emit = 0; p.real = 0;
+    if (fin) {
+      if (p.pos < p.fc) { p.emit = std::min(seg, p.fc - p.pos); p.real = p.emit + std::min(rc, p.fc - p.pos - p.emit); }
+    } else if (p.pos + rows <= p.fc) {
+      p.emit = seg; p.real = rows;
+    }
+    const long long a_lo = std::min<long long>(o.recv, (long long)p.f0 * hop - N / 2);
+    if (p.R - std::max(0ll, a_lo) > s->fe_LA || p.fc - std::min(p.pos, p.f0) > s->fe_LM)
+      throw Error(CONAN_ERR_UNSUPPORTED, "conan_step_wav_ragged: front-end rings too small for this configuration");
+    run = run || p.nnew > 0 || sm > 0 || p.emit > 0;
+  }
+  // emit groups, largest emit first; a group's rows keep call order
+  std::vector<std::vector<int>> groups;      // call rows per group
+  for (int e = seg; e >= 1; --e) {
+    std::vector<int> g;
+    for (int i = 0; i < n; ++i) if (pl[i].emit == e) g.push_back(i);
+    if (!g.empty()) groups.push_back(std::move(g));
+  }
+  const bool direct = groups.size() == 1 && (int)groups[0].size() == n && pl[0].emit == seg;
+  const int nm_in = m.num_mels, nm = c.num_mels;
+  std::vector<int> tab((size_t)n * cnk::kRaggedWords, 0);
+  int jobs = 0;
+  for (int i = 0; i < n; ++i) {
+    const Plan& p = pl[i];
+    int* d = &tab[(size_t)i * cnk::kRaggedWords];
+    const long long r_prev = s->fe_slot[slots[i]].recv;
+    d[cnk::kRgSlot] = slots[i];
+    d[cnk::kRgRecvLo] = (int)(uint32_t)r_prev; d[cnk::kRgRecvHi] = (int)(r_prev >> 32);
+    d[cnk::kRgTotalLo] = (int)(uint32_t)p.total; d[cnk::kRgTotalHi] = (int)(p.total >> 32);
+    d[cnk::kRgM] = samples[i]; d[cnk::kRgF0] = p.f0; d[cnk::kRgNnew] = p.nnew; d[cnk::kRgPos] = p.pos;
+    d[cnk::kRgRows] = p.emit > 0 ? rows : 0; d[cnk::kRgReal] = p.real; d[cnk::kRgEmit] = p.emit;
+    d[cnk::kRgJob] = jobs;
+    jobs += p.nnew;
+  }
+  for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g)
+    for (int k = 0; k < (int)groups[g].size(); ++k) {
+      int* d = &tab[(size_t)groups[g][k] * cnk::kRaggedWords];
+      d[cnk::kRgChunk] = off + k; d[cnk::kRgGroup] = off; d[cnk::kRgIndex] = k;
+    }
+  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+  s->ragged_init();
+  const int q = (int)(s->rg_calls % conan_streams::NS);
+  hipStream_t cst = (hipStream_t)stream;
+  if (!pipelined || groups.empty()) s->join(cst);
+  // the row table of set q: the call that used it last has finished reading it (and its staging)
+  HIP_CHECK(hipStreamWaitEvent(cst, s->ev_stage[q], 0));
+  s->fe_pin.upload(s->rg_tab[q], tab.data(), tab.size(), cst);
+  std::function<void(hipStream_t)> front;
+  if (run) {
+    const std::string k = s->ctx->mel_tables(m);
+    const float* rg = s->ctx->vec(k + ".range");
+    cnk::MelRaggedArgs a;
+    a.wav = wav_dev; a.aring = s->fe_audio; a.mring = s->fe_mel; a.chunk = s->fe_chunk; a.tab = s->rg_tab[q];
+    a.win = s->ctx->vec(k + ".win"); a.tw = reinterpret_cast<const double2*>(s->ctx->vec(k + ".tw")); a.fb = s->ctx->vec(k + ".fb");
+    a.lo = reinterpret_cast<const int*>(rg); a.hi = reinterpret_cast<const int*>(rg) + m.num_mels;
+    a.n = n; a.jobs = jobs; a.wstride = seg * hop;
+    a.LA = s->fe_LA; a.LM = s->fe_LM; a.nm = nm_in; a.n_fft = N; a.hop = hop; a.nb = N / 2 + 1; a.cmag = (N / 2 + 1 + 3) & ~3;
+    a.eps = m.eps; a.vmin = m.vmin; a.vmax = m.vmax; a.mag_eps = m.mag_eps; a.natural_log = m.natural_log;
+    const double flops = 4.0 * jobs * (double)(N / 2 + 1) * N;
+    front = [s, a, flops](hipStream_t st) { s->profiled("mel_stream_ragged_kernel", flops, st, [&] { cnk::launch_mel_ragged(a, st); }); };
+  }
+  cnk::WavScatterArgs sc;
+  sc.tab = s->rg_tab[q]; sc.n = n; sc.seg = seg; sc.nm = nm; sc.hop = hop;
+  sc.codes_src = s->rg_codes[q]; sc.mel_src = s->rg_mel[q]; sc.wav_src = s->rg_wav[q];
+  sc.codes = codes_dev; sc.mel = mel_out_dev; sc.wav = wav_out_dev;
+  auto group_step = [&](int g, int off, hipStream_t st) {
+    std::vector<int32_t> gs;
+    for (int i : groups[g]) gs.push_back(slots[i]);
+    const int ng = (int)gs.size(), e = pl[groups[g][0]].emit;
+    const float* chunk = s->fe_chunk + (size_t)off * rows * nm_in;
+    int32_t* cd = direct ? codes_dev : s->rg_codes[q] + (size_t)off * seg;
+    float* md = direct ? mel_out_dev : s->rg_mel[q] + (size_t)off * seg * nm;
+    float* wd = direct ? wav_out_dev : s->rg_wav[q] + (size_t)off * seg * hop;
+    if (pipelined) {
+      step_pipelined(s, gs.data(), ng, e, chunk, cd, md, wd, stream, g == 0 ? front : std::function<void(hipStream_t)>());
+    } else {
+      s->set_slots(gs.data(), ng, st);
+      step_blocking(s, ng, e, chunk, cd, md, wd, st);
+    }
+  };
+  if (pipelined && !groups.empty()) {
+    for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g) group_step(g, off, cst);
+    if (!direct) {
+      cnk::launch_wav_scatter(sc, s->st_voc);
+      // join() waits for the last step's vocoder event: it now covers the scatter too
+      HIP_CHECK(hipEventRecord(s->ev_voc[(s->async_steps - 1) % conan_streams::NP], s->st_voc));
+    }
+    HIP_CHECK(hipEventRecord(s->ev_stage[q], s->st_voc));
+  } else {
+    if (run) front(cst);
+    for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g) group_step(g, off, cst);
+    if (!direct && !groups.empty()) s->profiled("wav_rows_scatter_kernel", 0.0, cst, [&] { cnk::launch_wav_scatter(sc, cst); });
+    HIP_CHECK(hipEventRecord(s->ev_stage[q], cst));
+  }
+  for (int i = 0; i < n; ++i) {
+    conan_streams::FeSlot& o = s->fe_slot[slots[i]];
+    const Plan& p = pl[i];
+    o.recv = p.R; o.frames = std::max(p.f0, p.fc); o.chunks += p.emit > 0 ? 1 : 0;
+    o.phase = final_[i] ? (p.emit > 0 ? 1 : 2) : 0;
+    emit_out[i] = p.emit;
+  }
+  s->fe_last_n = n;
+  s->fe_last_ragged = true;
+  s->rg_calls++;
+}
+
+int conan_step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final, const float* wav_dev,
+                          const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream) {
+  return guarded([&] { step_wav_ragged(s, slots, n, samples, final, wav_dev, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false); });
+}
+
+int conan_step_wav_ragged_async(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final, const float* wav_dev,
+                                const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream) {
+  return guarded([&] { step_wav_ragged(s, slots, n, samples, final, wav_dev, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true); });
+}
+
 int conan_step_wav_chunk(conan_streams* s, float* chunk_dev, void* stream) {
   return guarded([&] {
     if (!s || !chunk_dev) throw Error(CONAN_ERR_INVALID, "null argument");
     if (!s->fe_chunk || s->fe_last_n == 0) throw Error(CONAN_ERR_STATE, "conan_step_wav_chunk: no conan_step_wav call yet");
+    if (s->fe_last_ragged) throw Error(CONAN_ERR_STATE, "conan_step_wav_chunk: the last wav-in call was conan_step_wav_ragged, whose chunk rows are grouped by emit");
     HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
     s->join((hipStream_t)stream);
     const size_t floats = (size_t)s->fe_last_n * (s->ctx->cfg.emf_segment + s->ctx->cfg.emf_right_context) * s->ctx->cfg.emf_input_dim;

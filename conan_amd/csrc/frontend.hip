@@ -3,6 +3,7 @@
 //   centred, zero-padded frames x periodic Hann -> |rfft| -> Slaney mel filterbank -> log10(max(eps, .)) -> clip.
 // The DFT sums and the filterbank products are accumulated in f64 (VALU; 1.1 MMAC per frame, < 0.4 % of the vocoder's
 // work per frame): what is left against librosa is librosa's own float32 FFT rounding.
+#include <climits>
 #include <cmath>
 
 #include "host_common.h"
@@ -77,6 +78,38 @@ __global__ __launch_bounds__(256) void mel_log_kernel(const MelArgs a) {
   const float c = fmaxf(a.eps, (float)s);
   const float v = a.natural_log ? logf(c) : log10f(c);
   a.y[e] = fminf(fmaxf(v, a.vmin), a.vmax);
+}
+
+// The two computing parts of mel_stream_ragged_kernel, written as in mel_stream_kernel (dft_mag_kernel's and mel_log_kernel's
+// expressions, the same FMA order).  |X| of kMelStreamFrames frames staged in LDS (x [N][F] as f64, tw [N]) into
+// mag [F][cmag]: a thread per bin, the f64 FMA chain over t in dft_mag_kernel's order.
+__device__ __forceinline__ void mel_dft_mag(const double* x, const double2* tw, float* mag, int N, int nb, int cmag, float mag_eps) {
+  constexpr int F = kMelStreamFrames;
+  const int mask = N - 1;
+  for (int b = threadIdx.x; b < cmag; b += blockDim.x) {
+    if (b >= nb) { for (int j = 0; j < F; ++j) mag[j * cmag + b] = 0.f; continue; }
+    double re[F], im[F];
+    for (int j = 0; j < F; ++j) { re[j] = 0.0; im[j] = 0.0; }
+    int idx = 0;
+    for (int t = 0; t < N; ++t) {
+      const double2 w = tw[idx];
+#pragma unroll
+      for (int j = 0; j < F; ++j) { const double xv = x[(size_t)t * F + j]; re[j] = fma(xv, w.x, re[j]); im[j] = fma(xv, w.y, im[j]); }
+      idx = (idx + b) & mask;
+    }
+#pragma unroll
+    for (int j = 0; j < F; ++j) mag[j * cmag + b] = (float)sqrt(re[j] * re[j] + im[j] * im[j] + (double)mag_eps);
+  }
+}
+
+// Mel bin mm of one frame's magnitudes mg: mel_log_kernel's f64 filterbank sum, log and clip.
+__device__ __forceinline__ float mel_log_value(const float* fb, const int* lo, const int* hi, const float* mg, int mm, int cmag, float eps,
+                                               float vmin, float vmax, int natural_log) {
+  const float* w = fb + (long long)mm * cmag;
+  double s = 0.0;
+  for (int b = lo[mm]; b < hi[mm]; ++b) s = fma((double)w[b], (double)mg[b], s);
+  const float c = fmaxf(eps, (float)s);
+  return fminf(fmaxf(natural_log ? logf(c) : log10f(c), vmin), vmax);
 }
 
 // The part of a call's front-end that computes nothing, for slot i: the chunk rows that earlier calls computed, from the mel ring,
@@ -173,6 +206,121 @@ void launch_mel_stream_copy(const MelStreamArgs& a, hipStream_t st) {    // only
   hipLaunchKernelGGL(mel_stream_copy_kernel, dim3(a.n), dim3(256), 0, st, a);
 }
 
+
+// Ragged streaming front-end (conan_step_wav_ragged): every call row i has its own position (tab[i]: kRaggedWords ints), so the
+// frame jobs of all rows are numbered by the prefix sums tab[i].kRgJob and a workgroup's kMelStreamFrames frames may belong to
+// different rows.  The frames are those of mel_stream_kernel bit for bit (same windowed f32 samples, mel_dft_mag, mel_log_value);
+// the chunk rows go to the row block tab[i].kRgChunk, so each emit group's chunk is contiguous.
+__device__ __forceinline__ long long ragged_ll(const int* d, int lo) {
+  return (long long)(((unsigned long long)(unsigned)d[lo + 1] << 32) | (unsigned)d[lo]);
+}
+
+// the call row owning frame job `job`: the last row whose first job is <= job (rows without frames share their successor's prefix)
+__device__ __forceinline__ int ragged_row(const MelRaggedArgs& a, int job) {
+  int lo = 0, hi = a.n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (a.tab[mid * kRaggedWords + kRgJob] <= job) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// mel_stream_copy for row i of a ragged call: its chunk rows of earlier calls, its samples into its audio ring
+__device__ inline void mel_ragged_copy(const MelRaggedArgs& a, int i) {
+  const int* d = a.tab + (long long)i * kRaggedWords;
+  const int slot = d[kRgSlot], rows = d[kRgRows], real = d[kRgReal], pos = d[kRgPos], f0 = d[kRgF0], m = d[kRgM];
+  const float* mr = a.mring + (long long)slot * a.LM * a.nm;
+  float* ch = a.chunk + (long long)d[kRgChunk] * rows * a.nm;
+  for (int e = threadIdx.x; e < rows * a.nm; e += blockDim.x) {
+    const int r = e / a.nm, mm = e - r * a.nm, src = pos + min(r, real - 1);
+    if (src < f0) ch[e] = mr[(long long)(src & (a.LM - 1)) * a.nm + mm];
+  }
+  const long long r_prev = ragged_ll(d, kRgRecvLo);
+  float* ar = a.aring + (long long)slot * a.LA;
+  const float* w = a.wav + (long long)i * a.wstride;
+  for (int j = threadIdx.x; j < m; j += blockDim.x) ar[(r_prev + j) & (a.LA - 1)] = w[j];
+}
+
+__global__ __launch_bounds__(1024) void mel_stream_ragged_kernel(const MelRaggedArgs a) {
+  constexpr int F = kMelStreamFrames;
+  extern __shared__ __attribute__((aligned(16))) double msm[];
+  const int N = a.n_fft;
+  for (int i = blockIdx.x; i < a.n; i += gridDim.x) mel_ragged_copy(a, i);
+  const int job0 = blockIdx.x * F;
+  if (job0 >= a.jobs) return;                                        // copy-only workgroups (the whole workgroup leaves)
+  double* x = msm;                                                   // [N][F]
+  double2* tw = reinterpret_cast<double2*>(msm + (size_t)N * F);     // [N]
+  float* mag = reinterpret_cast<float*>(tw + N);                     // [F][cmag]
+  int* row_of = reinterpret_cast<int*>(mag + (size_t)F * a.cmag);    // [F] call row of each frame
+  // the frame's samples; j, its row and its position are uniform in the workgroup.  The choice between this call's samples and the
+  // audio ring is data-dependent per sample: both loads are issued unconditionally at clamped addresses and the value is selected
+  // (a load behind that branch would be serialised)
+  for (int j = 0; j < F; ++j) {
+    const int job = job0 + j;
+    if (job >= a.jobs) {
+      for (int k = threadIdx.x; k < N; k += blockDim.x) x[(size_t)k * F + j] = 0.0;
+      continue;
+    }
+    const int i = ragged_row(a, job);
+    const int* d = a.tab + (long long)i * kRaggedWords;
+    const int f = d[kRgF0] + (job - d[kRgJob]), m = d[kRgM];
+    const long long r_prev = ragged_ll(d, kRgRecvLo), total = ragged_ll(d, kRgTotalLo);
+    const long long end = total < 0 ? LLONG_MAX : total;
+    const float* wr = m > 0 ? a.wav + (long long)i * a.wstride : a.aring;     // (no samples: the clamped load reads a valid word)
+    const float* ar = a.aring + (long long)d[kRgSlot] * a.LA;
+    const long long base = (long long)f * a.hop - N / 2;                     // center=True, pad_mode='constant'
+    const long long wlast = m > 0 ? m - 1 : 0;
+    if (threadIdx.x == 0) row_of[j] = i;
+    for (int k = threadIdx.x; k < N; k += blockDim.x) {
+      const long long smp = base + k;
+      const float xw = wr[min(max(smp - r_prev, 0ll), wlast)];
+      const float xr = ar[smp & (a.LA - 1)];
+      const float xs = smp >= r_prev ? xw : xr;
+      x[(size_t)k * F + j] = (double)(smp >= 0 && smp < end ? xs * a.win[k] : 0.f);
+    }
+  }
+  for (int t = threadIdx.x; t < N; t += blockDim.x) tw[t] = a.tw[t];
+  __syncthreads();
+  mel_dft_mag(x, tw, mag, N, a.nb, a.cmag, a.mag_eps);
+  __syncthreads();
+  for (int e = threadIdx.x; e < F * a.nm; e += blockDim.x) {
+    const int j = e / a.nm, mm = e - j * a.nm, job = job0 + j;
+    if (job >= a.jobs) continue;
+    const int i = row_of[j];
+    const int* d = a.tab + (long long)i * kRaggedWords;
+    const int f = d[kRgF0] + (job - d[kRgJob]), rows = d[kRgRows], pos = d[kRgPos], real = d[kRgReal];
+    const float v = mel_log_value(a.fb, a.lo, a.hi, mag + j * a.cmag, mm, a.cmag, a.eps, a.vmin, a.vmax, a.natural_log);
+    a.mring[((long long)d[kRgSlot] * a.LM + (f & (a.LM - 1))) * a.nm + mm] = v;
+    float* ch = a.chunk + (long long)d[kRgChunk] * rows * a.nm;
+    for (int r = 0; r < rows; ++r)
+      if (pos + min(r, real - 1) == f) ch[(long long)r * a.nm + mm] = v;
+  }
+}
+
+// Rows of the emit groups' staged outputs into the caller's rows (call order); frames past a row's emit stay untouched.
+__global__ __launch_bounds__(256) void wav_rows_scatter_kernel(const WavScatterArgs a) {
+  const int i = blockIdx.x;
+  const int* d = a.tab + (long long)i * kRaggedWords;
+  const int e = d[kRgEmit], g = d[kRgGroup], k = d[kRgIndex];
+  if (e == 0) return;
+  const long long src = (long long)g * a.seg + (long long)k * e;      // the group's compact [rows][e] frames start at g * seg
+  if (a.codes) for (int t = threadIdx.x; t < e; t += blockDim.x) a.codes[(long long)i * a.seg + t] = a.codes_src[(long long)(g + k) * a.seg + t];
+  if (a.mel) for (int t = threadIdx.x; t < e * a.nm; t += blockDim.x) a.mel[(long long)i * a.seg * a.nm + t] = a.mel_src[src * a.nm + t];
+  for (int t = threadIdx.x; t < e * a.hop; t += blockDim.x) a.wav[(long long)i * a.seg * a.hop + t] = a.wav_src[src * a.hop + t];
+}
+
+void launch_mel_ragged(const MelRaggedArgs& a, hipStream_t st) {
+  const int threads = std::min(1024, (a.nb + 63) / 64 * 64);
+  if (a.jobs == 0) { hipLaunchKernelGGL(mel_stream_ragged_kernel, dim3(a.n), dim3(threads), 0, st, a); return; }
+  const int blocks = std::max((a.jobs + kMelStreamFrames - 1) / kMelStreamFrames, std::min(a.n, 64));
+  const size_t lds = mel_stream_lds_bytes(a.n_fft, a.cmag) + kMelStreamFrames * sizeof(int);
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)mel_stream_ragged_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipLaunchKernelGGL(mel_stream_ragged_kernel, dim3(blocks), dim3(threads), lds, st, a);
+}
+
+void launch_wav_scatter(const WavScatterArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(wav_rows_scatter_kernel, dim3(a.n), dim3(256), 0, st, a);
+}
 }  // namespace cnk
 
 namespace {

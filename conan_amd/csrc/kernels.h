@@ -525,6 +525,34 @@ struct MelStreamArgs {
 inline size_t mel_stream_lds_bytes(int n_fft, int cmag) { return (size_t)n_fft * kMelStreamFrames * 8 + (size_t)n_fft * 16 + (size_t)kMelStreamFrames * cmag * 4; }
 void launch_mel_stream(const MelStreamArgs& a, hipStream_t st);        // nnew > 0: the new frames, the old chunk rows, the samples
 void launch_mel_stream_copy(const MelStreamArgs& a, hipStream_t st);   // nnew = 0: old chunk rows from the mel ring, samples into the audio ring
+// ragged streaming front-end (conan_step_wav_ragged): slots at different positions of their utterances.  The per-slot fields
+// live in a device table of kRaggedWords ints per call row (uploaded through PinRing); the shared fields stay in the arguments.
+enum RaggedField {
+  kRgSlot, kRgRecvLo, kRgRecvHi, kRgTotalLo, kRgTotalHi,   // slot; samples received before this call; utterance length (-1: not final)
+  kRgM, kRgF0, kRgNnew, kRgPos, kRgRows, kRgReal,          // samples of this call; frames [f0, f0 + nnew); chunk rows pos + min(r, real - 1)
+  kRgChunk,                                                // destination chunk row block (rows = 0: no chunk)
+  kRgJob,                                                  // prefix sum of nnew: this row's first frame job
+  kRgGroup, kRgIndex, kRgEmit,                             // scatter: the emit group's first staging row, the row's index in it, frames emitted
+  kRaggedWords = 16
+};
+struct MelRaggedArgs {
+  const float* wav;          // [n][wstride] this call's samples, row i: tab[i].m used
+  float* aring; float* mring; float* chunk;
+  const int* tab;            // [n][kRaggedWords]
+  const float* win; const double2* tw; const float* fb; const int* lo; const int* hi;
+  int n, jobs, wstride;
+  int LA, LM, nm, n_fft, hop, nb, cmag;
+  float eps, vmin, vmax, mag_eps;
+  int natural_log;
+};
+void launch_mel_ragged(const MelRaggedArgs& a, hipStream_t st);         // one launch per call (jobs may be 0: copy / append only)
+// rows of the emit groups' staged outputs into call order: row i <- row kRgIndex of the group staged at row kRgGroup, its first kRgEmit frames
+struct WavScatterArgs {
+  const int* tab; int n, seg, nm, hop;
+  const int* codes_src; const float* mel_src; const float* wav_src;     // staging: group-compact rows ([k][emit][.]) at group offsets
+  int* codes; float* mel; float* wav;                                    // caller's [n][seg], [n][seg][nm], [n][seg * hop]; codes / mel may be null
+};
+void launch_wav_scatter(const WavScatterArgs& a, hipStream_t st);
 
 // ---- style pass (per utterance) helpers
 struct RowMaskArgs { TRef x; TRef m; const int* lens; int T, n, C; int mode; };  // mode 0: sum|x|>0, 1: x[0]!=0

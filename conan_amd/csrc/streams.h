@@ -134,6 +134,16 @@ struct conan_streams {
   int fe_LA = 0, fe_LM = 0, fe_last_n = 0;
   struct FeSlot { long long recv = 0; int frames = 0, chunks = 0, phase = 0; };
   std::vector<FeSlot> fe_slot;
+  // conan_step_wav_ragged: per call a [n][kRaggedWords] row table (uploaded through fe_pin) and, when the emit groups' outputs need
+  // reordering, staging for them; NS sets used round robin, set q reused only after ev_stage[q] (the last reader of the call that
+  // used it) has completed.  Allocated on the first ragged call; not stream state (state_bytes).
+  static constexpr int NS = 4;
+  PinRing fe_pin;
+  int* rg_tab[NS] = {}; int* rg_codes[NS] = {}; float* rg_mel[NS] = {}; float* rg_wav[NS] = {};
+  hipEvent_t ev_stage[NS] = {};
+  long long rg_calls = 0;
+  bool fe_last_ragged = false;      // the last wav-in call was ragged: fe_chunk holds its rows grouped by emit (conan_step_wav_chunk refuses)
+  void ragged_init();
   // --- vocoder
   Ring v_mel, v_pre;
   std::vector<VocStage> v_st;
@@ -223,6 +233,7 @@ struct conan_streams {
     if (st_voc) (void)hipStreamDestroy(st_voc);
     for (int i = 0; i < NP; ++i) { if (ev_in[i]) (void)hipEventDestroy(ev_in[i]); if (ev_fence[i]) (void)hipEventDestroy(ev_fence[i]); }
     for (int i = 0; i < NP; ++i) { if (ev_wide[i]) (void)hipEventDestroy(ev_wide[i]); if (ev_emf[i]) (void)hipEventDestroy(ev_emf[i]); if (ev_front[i]) (void)hipEventDestroy(ev_front[i]); if (ev_voc[i]) (void)hipEventDestroy(ev_voc[i]); }
+    for (int i = 0; i < NS; ++i) if (ev_stage[i]) (void)hipEventDestroy(ev_stage[i]);
     for (void* p : allocs) (void)hipFree(p);
     if (h_guard) (void)hipHostFree(h_guard);
     for (auto& e : prof_ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }

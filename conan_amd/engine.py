@@ -258,6 +258,82 @@ class StreamingVoiceConversionEngine:
             self.st.join()
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
+    def open_slots(self, slots, ref_mel, ref_len=None):
+        """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
+        which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80])."""
+        self.st.reset(slots, which=7 | 8)
+        self.st.set_reference(slots, ref_mel, ref_len)
+
+    @torch.no_grad()
+    def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None):
+        """Streaming waveform input for slots at different positions of their utterances (conan_step_wav_ragged): slot i takes the
+        first samples[i] samples of wav row i (wav [n, <= seg*hop] cuda) with its own final flag; the rules per slot are feed()'s.
+        -> one (wav [emit*hop], mel [emit, 80], codes [emit]) per slot, of the chunk it emitted (emit = 0: empty).
+        pipelined: conan_step_wav_ragged_async - the tensors are complete after self.st.join()."""
+        fn = self.st.step_wav_ragged_async if pipelined else self.st.step_wav_ragged
+        emit, c, m, w = fn(slots, wav, samples, final, mel=mel)
+        hop = self.ctx.hop
+        return [(w[i, :e * hop], m[i, :e], c[i, :e]) for i, e in enumerate(emit)]
+
+    @torch.no_grad()
+    def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None):
+        """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
+        (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
+        Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
+        frames; with no slot free the utterance waits for one); every tick is one feed_ragged over the slots live in it.
+        -> one (wav, mel [T, 80], codes [T]) per utterance: what infer_wav would give for it alone.  The slot each utterance used is
+        left in self.staggered_slots."""
+        L = self.seg * self.ctx.hop
+        U = len(src_wavs)
+        assert len(starts) == U and len(ref_mel) == U
+        pending = sorted(range(U), key=lambda u: (starts[u], u))
+        free = sorted(self.slots)
+        live = {}                                         # utterance -> [slot, samples fed, final fed]
+        outs = [[] for _ in range(U)]
+        self.staggered_slots = [None] * U
+        tick = 0
+        while pending or live:
+            new = []
+            while pending and starts[pending[0]] <= tick and free:
+                u = pending.pop(0)
+                live[u] = [free.pop(0), 0, False]
+                self.staggered_slots[u] = live[u][0]
+                new.append(u)
+            if new:
+                self.open_slots([live[u][0] for u in new], torch.stack([ref_mel[u] for u in new]))
+            if not live:
+                tick += 1
+                continue
+            us = list(live)
+            rows, samples, final, draining = [], [], [], []
+            for u in us:
+                x, (slot, pos, fin) = src_wavs[u], live[u]
+                N = x.shape[0]
+                last = (N - 1) // L * L                   # the final call takes the remaining 1 .. L samples
+                draining.append(fin)
+                if pos < last:
+                    piece, live[u][1] = x[pos:pos + L], pos + L
+                    final.append(0)
+                elif not fin:
+                    piece, live[u][1], live[u][2] = x[pos:], N, True
+                    final.append(1)
+                else:
+                    piece = x[:0]
+                    final.append(1)
+                samples.append(piece.shape[0])
+                rows.append(torch.nn.functional.pad(piece, (0, L - piece.shape[0])))
+            res = self.feed_ragged([live[u][0] for u in us], torch.stack(rows), samples, final, pipelined=pipelined, mel=mel)
+            for u, was_final, (w, m, c) in zip(us, draining, res):
+                if m.shape[0]:
+                    outs[u].append((w, m, c))
+                elif was_final:                           # the drain's empty answer: the slot is free again
+                    free.append(live.pop(u)[0])
+                    free.sort()
+            tick += 1
+        if pipelined:
+            self.st.join()
+        return [tuple(torch.cat(t, 0) for t in zip(*o)) for o in outs]
+
     def chunks(self, src_mel):
         """inference/Conan.py:95-110: (pos, emit, chunk[B, seg+rc, 80]) with repeat-last padding."""
         B, T, F = src_mel.shape

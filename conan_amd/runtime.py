@@ -356,6 +356,46 @@ class Streams:
         e = emit.value
         return e, codes, mel_out.view(-1)[:n * e * nm].view(n, e, nm), wav_out.view(-1)[:n * e * hop].view(n, e * hop)
 
+    def step_wav_ragged(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None):
+        """Waveform-in chunk step for slots at different positions of their utterances (conan_step_wav_ragged): slot i takes the
+        first samples[i] samples of wav row i (wav [n, <= seg*hop] cuda float32, or None when every samples[i] is 0) and is stepped
+        as step_wav([slot], samples[i], final[i]) alone would step it.  -> (emit: list of n ints, codes [n, seg], mel [n, seg, 80],
+        wav [n, seg*hop]): row i holds emit[i] frames; the rest of the row is left as it was."""
+        return self._step_wav_ragged(slots, wav, samples, final, codes, mel_out, wav_out, mel, False)
+
+    def step_wav_ragged_async(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None):
+        """Pipelined step_wav_ragged (conan_step_wav_ragged_async): the outputs are complete after join(); same return value."""
+        return self._step_wav_ragged(slots, wav, samples, final, codes, mel_out, wav_out, mel, True)
+
+    def _step_wav_ragged(self, slots, wav, samples, final, codes, mel_out, wav_out, mel, pipelined):
+        a, p = _i32(slots)
+        n = len(a)
+        hop, nm, L = self.ctx.hop, self.ctx.cfg.num_mels, self.seg * self.ctx.hop
+        sm, sp = _i32(samples)
+        fi, fp = _i32([int(bool(f)) for f in final])
+        assert len(sm) == n and len(fi) == n, (n, len(sm), len(fi))
+        if wav is not None:
+            wav = wav.to(self.dev, torch.float32)
+            assert wav.dim() == 2 and wav.shape[0] == n and wav.shape[1] <= L, wav.shape
+            if wav.shape[1] < L:                      # rows are seg*hop apart in the C-ABI
+                wav = torch.nn.functional.pad(wav, (0, L - wav.shape[1]))
+            wav = wav.contiguous()
+        if codes is None:
+            codes = torch.empty(n, self.seg, dtype=torch.int32, device=self.dev)
+        if mel_out is None:
+            mel_out = torch.empty(n, self.seg, nm, device=self.dev)
+        if wav_out is None:
+            wav_out = torch.empty(n, L, device=self.dev)
+        mc = mel_cfg(**(mel or {}))
+        emit = (C.c_int32 * n)()
+        fn = self.lib.conan_step_wav_ragged_async if pipelined else self.lib.conan_step_wav_ragged
+        if pipelined:
+            self._keep.append((wav, wav_out, codes, mel_out))
+        _lib.check(fn(self.h, p, n, sp, fp, _ptr(wav), C.byref(mc), _ptr(codes), _ptr(mel_out), _ptr(wav_out), emit, _stream()))
+        if not pipelined:
+            self._release()
+        return list(emit), codes, mel_out, wav_out
+
     def wav_chunk(self, n):
         """The [n, seg+rc, 80] mel chunk the last step_wav call assembled (conan_step_wav_chunk; joins pipelined work)."""
         out = torch.empty(n, self.seg + self.rc, self.ctx.cfg.emf_input_dim, device=self.dev)

@@ -342,8 +342,27 @@ int conan_step_wav(conan_streams* s, const int32_t* slots, int n, int samples, i
  * rules; wav_dev and the outputs must stay valid until conan_streams_join).  Calls that emit nothing run on `stream`. */
 int conan_step_wav_async(conan_streams* s, const int32_t* slots, int n, int samples, int final, const float* wav_dev, const conan_mel_cfg* mel,
                          int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream);
-/* Test / debug hook: copy the mel chunk the last conan_step_wav call assembled, chunk_dev[n][seg + rc][num_mels] (joins first). */
+/* Test / debug hook: copy the mel chunk the last conan_step_wav call assembled, chunk_dev[n][seg + rc][num_mels] (joins first).
+ * After a conan_step_wav_ragged call it is CONAN_ERR_STATE (that call's chunk rows are grouped by emit, not in call order). */
 int conan_step_wav_chunk(conan_streams* s, float* chunk_dev, void* stream);
+
+/* Waveform-in chunk step for slots at DIFFERENT positions of their utterances (streams that started at different times).
+ * Added within ABI 9 (no struct changed): a caller detects it by the exported symbol.  Slot i of the call is stepped exactly as a
+ * one-slot conan_step_wav(samples[i], final[i]) would step it - same rules (a non-final slot takes seg*hop samples, a final one
+ * 0 .. seg*hop; after its final call only samples = 0, final = 1 until it emits 0 frames; a drained slot is an error until a reset
+ * with CONAN_MODEL_FRONTEND), same emit_out[i], same bits.  wav_dev [n][seg*hop]: slot i's samples in row i, the first samples[i]
+ * used (may be null when every samples[i] is 0).  Outputs in call order with row strides of a full chunk: codes_dev [n][seg]
+ * (may be null), mel_out_dev [n][seg][num_mels] (may be null), wav_out_dev [n][seg*hop]; row i holds emit_out[i] frames and
+ * everything past them in the row is left untouched.  Every slot is checked before anything changes: an error leaves every slot
+ * where it was.  The emitting slots are stepped in one chunk step per distinct emit value (one in the steady state, where the call
+ * runs exactly the front-end launch and the mel-in step's launches); calls with several groups, or whose slots do not all emit a
+ * full chunk, write the steps' outputs to library staging and copy them into place with one more launch. */
+int conan_step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final, const float* wav_dev,
+                          const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream);
+/* Pipelined conan_step_wav_ragged (ordering as conan_step_wav_async; outputs complete after conan_streams_join).  A call whose slot
+ * list per emit group differs from the previous step's drains the pipeline first, as conan_step_async does. */
+int conan_step_wav_ragged_async(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final, const float* wav_dev,
+                                const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream);
 
 /* Measurement hook (replaces the reference's Timer('hifigan') around the vocoder forward,
  * utils/commons/meters.py:21-42, tasks/tts/vocoder_infer/hifigan.py:28): between begin and end every
