@@ -94,6 +94,13 @@ _PROTOS = {
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_step_wav_ragged_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_step_wav_ragged_ld": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_step_wav_ragged_ld_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_resample_length": (C.c_int64, [C.c_void_p, C.c_int64]),
+    "conan_resample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_streams_set_input_rate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "conan_streams_output_fence": (C.c_int, [C.c_void_p, C.c_void_p]),
     "conan_streams_output_fence_event": (C.c_int, [C.c_void_p, C.c_void_p]),
     "conan_streams_test_fault": (C.c_int, [C.c_void_p, C.c_int]),
@@ -155,6 +162,38 @@ class MelCfg(C.Structure):
                 ("sample_rate", C.c_int32), ("fmin", C.c_float), ("fmax", C.c_float), ("eps", C.c_float),
                 ("vmin", C.c_float), ("vmax", C.c_float), ("framing", C.c_int32), ("natural_log", C.c_int32),
                 ("mag_eps", C.c_float)]
+
+
+# conan_resample_cfg.window
+RESAMPLE_HANN, RESAMPLE_KAISER = 0, 1
+RESAMPLE_MAX_TAPS = 8192
+KAISER_BEST_BETA = 14.769656459379492     # conan_resample_cfg.beta <= 0 selects it (in double; a float beta is rounded to f32)
+# named filter presets: torchaudio's defaults, and torchaudio's documented values that mimic resampy's kaiser_best
+RESAMPLE_PRESETS = {
+    "hann": dict(lowpass_filter_width=6, rolloff=0.99, resampling_method="sinc_interp_hann", beta=None),
+    "kaiser_best": dict(lowpass_filter_width=64, rolloff=0.9475937167399596, resampling_method="sinc_interp_kaiser", beta=None),
+}
+
+
+class ResampleCfg(C.Structure):
+    """conan_resample_cfg (include/conan_hip.h)."""
+    _fields_ = [("in_rate", C.c_int32), ("out_rate", C.c_int32), ("lowpass_filter_width", C.c_int32), ("rolloff", C.c_float),
+                ("window", C.c_int32), ("beta", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+def resample_cfg(orig_freq, new_freq=16000, lowpass_filter_width=6, rolloff=0.99, resampling_method="sinc_interp_hann", beta=None,
+                 preset=None):
+    """conan_resample_cfg with torchaudio.functional.resample's keywords; preset='hann' / 'kaiser_best' replaces the filter keywords."""
+    if preset is not None:
+        if preset not in RESAMPLE_PRESETS:
+            raise ValueError("preset must be one of %s" % sorted(RESAMPLE_PRESETS))
+        p = RESAMPLE_PRESETS[preset]
+        lowpass_filter_width, rolloff, resampling_method, beta = p["lowpass_filter_width"], p["rolloff"], p["resampling_method"], p["beta"]
+    if resampling_method not in ("sinc_interp_hann", "sinc_interp_kaiser"):
+        raise ValueError("resampling_method must be 'sinc_interp_hann' or 'sinc_interp_kaiser'")
+    window = RESAMPLE_HANN if resampling_method == "sinc_interp_hann" else RESAMPLE_KAISER
+    return ResampleCfg(int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff), window,
+                       float(beta) if beta is not None else 0.0, (C.c_int32 * 2)(0, 0))
 
 
 class DecoderTaps(C.Structure):

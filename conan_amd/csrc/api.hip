@@ -1,4 +1,5 @@
 // extern "C" surface of libconan_hip.so (include/conan_hip.h).
+#include <climits>
 #include <functional>
 
 #include "streams.h"
@@ -231,6 +232,9 @@ int conan_streams_reset(conan_streams* s, const int32_t* slots, int n, int which
       const long long mel_floats = (long long)s->fe_LM * s->ctx->cfg.emf_input_dim;
       cnk::launch_zero_slots(s->fe_mel, mel_floats, mel_floats, s->d_slots, n, st);
       for (int i = 0; i < n; ++i) s->fe_slot[slots[i]] = conan_streams::FeSlot();
+      // the input rate stays; the resampler's history restarts (inputs before the first are zero, the ring needs no clearing)
+      if (!s->rs_slot.empty())
+        for (int i = 0; i < n; ++i) { conan_streams::RsSlot& r = s->rs_slot[slots[i]]; r.in = 0; r.out = 0; r.phase = 0; }
     }
   });
 }
@@ -531,6 +535,118 @@ int conan_step_async(conan_streams* s, const int32_t* slots, int n, int emit, co
   });
 }
 
+// Input resampler of a wav-in call (conan_streams_set_input_rate).  Per call row: the model-rate samples and final flag the front-end
+// gets - a row without a rate passes its own; a row with one hands over the longest prefix of outputs whose last tap has arrived (at
+// most seg * hop; after the input's final call, what is left, seg * hop at a time, final on the call that delivers the last sample).
+// When a row with a rate has input or owed output, one resample_stream_kernel launch writes every row's model-rate samples to
+// staging (rows without a rate copied verbatim) and the front-end reads them there.  rs_plan checks every row and changes nothing.
+struct RsPlan {
+  std::vector<int32_t> mm, ff;          // per row: front-end samples and final flag
+  std::vector<char> rate;               // per row: the slot has a rate
+  std::vector<long long> in_after;      // per row with a rate: input samples received after the call
+  std::vector<cnk::RsRow> rows;
+  bool any = false, launch = false;
+  int tiles = 1, win = 0;
+  double flops = 0;
+};
+
+static RsPlan rs_plan(const conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final_, const float* wav_dev,
+                      long long wav_ld, const conan_mel_cfg& m, const char* who) {
+  RsPlan P;
+  P.mm.assign(samples, samples + n); P.ff.assign(final_, final_ + n); P.rate.assign(n, 0); P.in_after.assign(n, 0);
+  if (s->rs_slot.empty()) return P;
+  const int S = s->ctx->cfg.emf_segment * s->ctx->hop;
+  P.rows.resize(n);
+  for (int i = 0; i < n; ++i) {
+    const conan_streams::RsSlot& r = s->rs_slot[slots[i]];
+    cnk::RsRow& row = P.rows[i];
+    memset(&row, 0, sizeof(row));
+    row.slot = slots[i]; row.copy = 1; row.m = samples[i]; row.h = samples[i];
+    if (!r.f) continue;
+    const ch::RsTable& t = *r.f;
+    auto bad = [&](const std::string& what) {
+      throw Error(CONAN_ERR_INVALID, std::string(who) + ": slot " + std::to_string(slots[i]) + " (input at " + std::to_string(t.in_rate) + " Hz): " + what);
+    };
+    const int sm = samples[i], fin = final_[i];
+    const int s_in = (int)((long long)S * t.in_rate / t.out_rate);
+    if (fin != 0 && fin != 1) bad("final must be 0 or 1");
+    if (m.sample_rate != t.out_rate) bad("conan_mel_cfg.sample_rate must be the resampler's out_rate");
+    if (r.phase == 1 && (!fin || sm != 0)) bad("after the final call only samples = 0, final = 1 may follow");
+    if (!fin && sm != s_in) bad("a non-final call takes exactly segment * hop * in_rate / out_rate samples");
+    if (fin && (sm < 0 || sm > s_in)) bad("a final call takes 0 .. segment * hop * in_rate / out_rate samples");
+    if (sm > wav_ld) bad("the row holds more samples than the row stride of wav_dev");
+    if (sm > 0 && !wav_dev) throw Error(CONAN_ERR_INVALID, "null argument (wav_dev with samples > 0)");
+    const long long I = r.in + sm;
+    long long J;
+    if (fin) {
+      const long long T = t.length(I);
+      J = std::min(T, r.out + S);
+      P.ff[i] = J == T;
+    } else {
+      J = std::min(std::max(t.ready(I), r.out), r.out + S);
+      P.ff[i] = 0;
+    }
+    // the inputs still to be read ([first tap of output r.out, I), up to a rounding step) must fit the history ring
+    if (I - (t.first(r.out) - 4) > cnk::kRsRing) throw Error(CONAN_ERR_UNSUPPORTED, std::string(who) + ": resampler history ring too small for this configuration");
+    P.mm[i] = (int)(J - r.out);
+    P.rate[i] = 1; P.any = true; P.in_after[i] = I;
+    row.in0 = r.in; row.out0 = r.out; row.taps = t.f.taps; row.ph = t.f.ph;
+    row.m = sm; row.h = P.mm[i]; row.orig = t.f.orig; row.nph = t.f.nph; row.w = t.f.w; row.L = t.f.L; row.copy = 0;
+    P.launch = P.launch || sm > 0 || P.mm[i] > 0;
+    P.win = std::max(P.win, t.win);
+    P.flops += 2.0 * P.mm[i] * t.f.L;
+  }
+  if (P.launch)
+    for (int i = 0; i < n; ++i) {
+      const cnk::RsRow& row = P.rows[i];
+      P.tiles = std::max(P.tiles, (std::max(row.h, row.m) + cnk::kRsTile - 1) / cnk::kRsTile);
+    }
+  return P;
+}
+
+// Uploads the plan's row table (set q of NS, after the call that used the set last has read it) on `cst` and returns the launch;
+// `mel_front` (may be empty) follows it on the same stream, then ev_rs[q].
+static std::function<void(hipStream_t)> rs_front(conan_streams* s, const RsPlan& P, int n, const float* wav_dev, long long wav_ld, long long out_ld,
+                                                 std::function<void(hipStream_t)> mel_front, hipStream_t cst) {
+  const int q = (int)(s->rs_calls++ % conan_streams::NS);
+  HIP_CHECK(hipStreamWaitEvent(cst, s->ev_rs[q], 0));
+  s->rs_pin.upload(reinterpret_cast<int*>(s->rs_rows[q]), reinterpret_cast<const int*>(P.rows.data()), (size_t)n * sizeof(cnk::RsRow) / sizeof(int), cst);
+  cnk::ResampleStreamArgs a;
+  a.wav = wav_dev ? wav_dev : s->rs_wav[q]; a.wav_ld = wav_dev ? wav_ld : 0;
+  a.ring = s->rs_ring; a.out = s->rs_wav[q]; a.out_ld = out_ld;
+  a.rows = s->rs_rows[q]; a.n = n; a.tiles = P.tiles; a.win = P.win;
+  const double flops = P.flops;
+  hipEvent_t ev = s->ev_rs[q];
+  return [s, a, flops, mel_front, ev](hipStream_t st) {
+    s->profiled("resample_stream_kernel", flops, st, [&] { cnk::launch_resample_stream(a, st); });
+    if (mel_front) mel_front(st);
+    HIP_CHECK(hipEventRecord(ev, st));
+  };
+}
+
+static void rs_commit(conan_streams* s, const int32_t* slots, int n, const RsPlan& P, const int32_t* final_) {
+  for (int i = 0; i < n; ++i) {
+    if (!P.rate[i]) continue;
+    conan_streams::RsSlot& r = s->rs_slot[slots[i]];
+    r.in = P.in_after[i]; r.out += P.mm[i];
+    if (final_[i]) r.phase = 1;
+  }
+}
+
+void conan_streams::resample_init() {
+  if (rs_ring) return;
+  const size_t S = (size_t)ctx->cfg.emf_segment * ctx->hop;
+  rs_ring = alloc((size_t)max_slots * cnk::kRsRing);        // stream state (state_bytes)
+  auto dev = [&](size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, bytes)); allocs.push_back(p); return p; };
+  for (int q = 0; q < NS; ++q) {
+    rs_rows[q] = (cnk::RsRow*)dev((size_t)max_slots * sizeof(cnk::RsRow));
+    rs_wav[q] = (float*)dev((size_t)max_slots * S * sizeof(float));
+    HIP_CHECK(hipEventCreateWithFlags(&ev_rs[q], hipEventDisableTiming));
+  }
+  rs_pin.init((size_t)max_slots * sizeof(cnk::RsRow) / sizeof(int));
+  rs_slot.assign(max_slots, RsSlot());
+}
+
 // Waveform-in chunk steps (conan_step_wav / _async).  The host keeps each slot's position in its utterance; a call plans which
 // frames became complete (centred framing: frame f needs samples up to f * hop + n_fft / 2 - 1, or the final call: every frame of
 // 1 + samples / hop, zero padding past the end) and whether chunk t = chunks emitted so far is ready: frames [t * seg, t * seg +
@@ -538,9 +654,9 @@ int conan_step_async(conan_streams* s, const int32_t* slots, int n, int emit, co
 // One mel_stream_kernel launch (64 workgroups at 64 streams) computes the new frames, copies the chunk rows of earlier calls from the
 // mel ring and appends the samples to the audio ring (mel_stream_copy_kernel alone in drain calls that complete no frame); the chunk
 // then goes through the mel-in step.
-static void step_wav(conan_streams* s, const int32_t* slots, int n, int samples, int final_, const float* wav_dev, const conan_mel_cfg* mel,
+static void step_wav(conan_streams* s, const int32_t* slots, int n, int in_samples, int in_final, const float* wav_dev, const conan_mel_cfg* mel,
                      int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream, bool pipelined) {
-  if (!s || !slots || !mel || !wav_out_dev || !emit_out || (samples > 0 && !wav_dev)) throw Error(CONAN_ERR_INVALID, "null argument");
+  if (!s || !slots || !mel || !wav_out_dev || !emit_out || (in_samples > 0 && !wav_dev)) throw Error(CONAN_ERR_INVALID, "null argument");
   *emit_out = 0;
   const conan_cfg& c = s->ctx->cfg;
   const int all = CONAN_MODEL_EMFORMER | CONAN_MODEL_CONAN | CONAN_MODEL_HIFIGAN;
@@ -564,9 +680,21 @@ static void step_wav(conan_streams* s, const int32_t* slots, int n, int samples,
     if (o.recv != st0.recv || o.frames != st0.frames || o.chunks != st0.chunks || o.phase != st0.phase)
       throw Error(CONAN_ERR_INVALID, "conan_step_wav: the slots of one call must be at the same position of their utterances");
   }
+  // input resampler: the slots of a call share one configuration (or have none) and one position
+  const std::vector<int32_t> in_sm(n, in_samples), in_fin(n, in_final);
+  const RsPlan P = rs_plan(s, slots, n, in_sm.data(), in_fin.data(), wav_dev, in_samples, m, "conan_step_wav");
+  if (P.any) {
+    const conan_streams::RsSlot& r0 = s->rs_slot[slots[0]];
+    for (int i = 0; i < n; ++i) {
+      const conan_streams::RsSlot& r = s->rs_slot[slots[i]];
+      if (r.f != r0.f || r.in != r0.in || r.out != r0.out || r.phase != r0.phase)
+        throw Error(CONAN_ERR_INVALID, "conan_step_wav: the slots of one call must share one input rate configuration (conan_streams_set_input_rate) and position");
+    }
+  }
+  const int samples = P.mm[0], final_ = P.ff[0];      // what the front-end gets (model rate)
   if (st0.phase == 2) throw Error(CONAN_ERR_INVALID, "conan_step_wav: the utterance has been drained; reset the slots with CONAN_MODEL_FRONTEND first");
   if (st0.phase == 1 && (!final_ || samples != 0)) throw Error(CONAN_ERR_INVALID, "conan_step_wav: after the final call only samples = 0, final = 1 may follow");
-  if (!final_ && samples != seg * hop) throw Error(CONAN_ERR_INVALID, "conan_step_wav: a non-final call takes exactly segment * hop samples per slot");
+  if (!final_ && samples != seg * hop && !P.any) throw Error(CONAN_ERR_INVALID, "conan_step_wav: a non-final call takes exactly segment * hop samples per slot");
   if (final_ && (samples < 0 || samples > seg * hop)) throw Error(CONAN_ERR_INVALID, "conan_step_wav: a final call takes 0 .. segment * hop samples per slot");
   const long long R = st0.recv + samples;
   if (final_ && R < 1) throw Error(CONAN_ERR_INVALID, "conan_step_wav: an utterance needs at least one sample");
@@ -591,7 +719,8 @@ static void step_wav(conan_streams* s, const int32_t* slots, int n, int samples,
     const std::string k = s->ctx->mel_tables(m);
     const float* rg = s->ctx->vec(k + ".range");
     cnk::MelStreamArgs a;
-    a.wav = wav_dev; a.aring = s->fe_audio; a.mring = s->fe_mel; a.chunk = s->fe_chunk; a.slots = s->d_slots;
+    a.wav = P.launch ? s->rs_wav[s->rs_calls % conan_streams::NS] : wav_dev;     // (rs_front takes set rs_calls % NS below)
+    a.aring = s->fe_audio; a.mring = s->fe_mel; a.chunk = s->fe_chunk; a.slots = s->d_slots;
     a.win = s->ctx->vec(k + ".win"); a.tw = reinterpret_cast<const double2*>(s->ctx->vec(k + ".tw")); a.fb = s->ctx->vec(k + ".fb");
     a.lo = reinterpret_cast<const int*>(rg); a.hi = reinterpret_cast<const int*>(rg) + m.num_mels;
     a.r_prev = st0.recv; a.total = final_ ? R : -1;
@@ -604,13 +733,14 @@ static void step_wav(conan_streams* s, const int32_t* slots, int n, int samples,
       else s->profiled("mel_stream_copy_kernel", 0.0, st, [&] { cnk::launch_mel_stream_copy(a, st); });
     };
   }
+  if (P.launch) front = rs_front(s, P, n, wav_dev, in_samples, samples, front, (hipStream_t)stream);
   if (pipelined && emit > 0) {
     step_pipelined(s, slots, n, emit, s->fe_chunk, codes_dev, mel_out_dev, wav_out_dev, stream, front);
   } else {
     hipStream_t st = (hipStream_t)stream;
     s->join(st);
     s->set_slots(slots, n, st);
-    if (run) front(st);
+    if (front) front(st);
     if (emit > 0) step_blocking(s, n, emit, s->fe_chunk, codes_dev, mel_out_dev, wav_out_dev, st);
   }
   for (int i = 0; i < n; ++i) {
@@ -618,6 +748,7 @@ static void step_wav(conan_streams* s, const int32_t* slots, int n, int samples,
     o.recv = R; o.frames = std::max(f0, fc); o.chunks += emit > 0 ? 1 : 0;
     o.phase = final_ ? (emit > 0 ? 1 : 2) : 0;
   }
+  rs_commit(s, slots, n, P, in_fin.data());
   s->fe_last_n = n;
   s->fe_last_ragged = false;
   *emit_out = emit;
@@ -654,10 +785,10 @@ void conan_streams::ragged_init() {
 // work of every slot of the call, driven by a [n][kRaggedWords] row table; it writes each group's chunk contiguously into fe_chunk.
 // A call whose slots all emit a full chunk is one group in call order and writes the caller's buffers directly; otherwise the groups
 // write staging (set q of NS) and wav_rows_scatter_kernel puts the rows in call order.
-static void step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final_, const float* wav_dev,
-                            const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream,
-                            bool pipelined) {
-  if (!s || !slots || !samples || !final_ || !mel || !wav_out_dev || !emit_out) throw Error(CONAN_ERR_INVALID, "null argument");
+static void step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const int32_t* in_samples, const int32_t* in_final, const float* wav_dev,
+                            long long wav_ld, const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out,
+                            void* stream, bool pipelined) {
+  if (!s || !slots || !in_samples || !in_final || !mel || !wav_out_dev || !emit_out) throw Error(CONAN_ERR_INVALID, "null argument");
   const conan_cfg& c = s->ctx->cfg;
   const int all = CONAN_MODEL_EMFORMER | CONAN_MODEL_CONAN | CONAN_MODEL_HIFIGAN;
   if ((c.models & all) != all || !s->fe_audio) throw Error(CONAN_ERR_STATE, "conan_step_wav_ragged needs all three models in the context");
@@ -679,6 +810,11 @@ static void step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const
     if (seen[slots[i]]) throw Error(CONAN_ERR_INVALID, "duplicate slot");
     seen[slots[i]] = 1;
   }
+  if (wav_ld < 0 || wav_ld > INT_MAX) throw Error(CONAN_ERR_INVALID, "conan_step_wav_ragged: wav_ld out of range");
+  // the input resampler's rows first: what each slot's front-end gets this call
+  const RsPlan P = rs_plan(s, slots, n, in_samples, in_final, wav_dev, wav_ld, m, "conan_step_wav_ragged");
+  const int32_t* samples = P.mm.data();
+  const int32_t* final_ = P.ff.data();
   // every slot's plan first (step_wav's, from the slot's own position): nothing changes before all of them have passed
   struct Plan { long long R, total; int fc, f0, nnew, pos, emit, real; };
   std::vector<Plan> pl(n);
@@ -692,8 +828,9 @@ static void step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const
     if (fin != 0 && fin != 1) bad("final must be 0 or 1");
     if (o.phase == 2) bad("the utterance has been drained; reset the slot with CONAN_MODEL_FRONTEND first");
     if (o.phase == 1 && (!fin || sm != 0)) bad("after the final call only samples = 0, final = 1 may follow");
-    if (!fin && sm != seg * hop) bad("a non-final call takes exactly segment * hop samples per slot");
+    if (!fin && sm != seg * hop && !P.rate[i]) bad("a non-final call takes exactly segment * hop samples per slot");
     if (fin && (sm < 0 || sm > seg * hop)) bad("a final call takes 0 .. segment * hop samples per slot");
+    if (sm > wav_ld && !P.rate[i]) bad("the row holds more samples than the row stride of wav_dev");
     if (sm > 0 && !wav_dev) throw Error(CONAN_ERR_INVALID, "null argument (wav_dev with samples > 0)");
     Plan& p = pl[i];
     p.R = o.recv + sm;
@@ -753,15 +890,17 @@ static void step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const
     const std::string k = s->ctx->mel_tables(m);
     const float* rg = s->ctx->vec(k + ".range");
     cnk::MelRaggedArgs a;
-    a.wav = wav_dev; a.aring = s->fe_audio; a.mring = s->fe_mel; a.chunk = s->fe_chunk; a.tab = s->rg_tab[q];
+    a.wav = P.launch ? s->rs_wav[s->rs_calls % conan_streams::NS] : wav_dev;     // (rs_front takes set rs_calls % NS below)
+    a.aring = s->fe_audio; a.mring = s->fe_mel; a.chunk = s->fe_chunk; a.tab = s->rg_tab[q];
     a.win = s->ctx->vec(k + ".win"); a.tw = reinterpret_cast<const double2*>(s->ctx->vec(k + ".tw")); a.fb = s->ctx->vec(k + ".fb");
     a.lo = reinterpret_cast<const int*>(rg); a.hi = reinterpret_cast<const int*>(rg) + m.num_mels;
-    a.n = n; a.jobs = jobs; a.wstride = seg * hop;
+    a.n = n; a.jobs = jobs; a.wstride = P.launch ? seg * hop : (int)wav_ld;
     a.LA = s->fe_LA; a.LM = s->fe_LM; a.nm = nm_in; a.n_fft = N; a.hop = hop; a.nb = N / 2 + 1; a.cmag = (N / 2 + 1 + 3) & ~3;
     a.eps = m.eps; a.vmin = m.vmin; a.vmax = m.vmax; a.mag_eps = m.mag_eps; a.natural_log = m.natural_log;
     const double flops = 4.0 * jobs * (double)(N / 2 + 1) * N;
     front = [s, a, flops](hipStream_t st) { s->profiled("mel_stream_ragged_kernel", flops, st, [&] { cnk::launch_mel_ragged(a, st); }); };
   }
+  if (P.launch) front = rs_front(s, P, n, wav_dev, wav_ld, seg * hop, front, cst);
   cnk::WavScatterArgs sc;
   sc.tab = s->rg_tab[q]; sc.n = n; sc.seg = seg; sc.nm = nm; sc.hop = hop;
   sc.codes_src = s->rg_codes[q]; sc.mel_src = s->rg_mel[q]; sc.wav_src = s->rg_wav[q];
@@ -790,7 +929,7 @@ static void step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const
     }
     HIP_CHECK(hipEventRecord(s->ev_stage[q], s->st_voc));
   } else {
-    if (run) front(cst);
+    if (front) front(cst);
     for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g) group_step(g, off, cst);
     if (!direct && !groups.empty()) s->profiled("wav_rows_scatter_kernel", 0.0, cst, [&] { cnk::launch_wav_scatter(sc, cst); });
     HIP_CHECK(hipEventRecord(s->ev_stage[q], cst));
@@ -802,19 +941,82 @@ static void step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const
     o.phase = final_[i] ? (p.emit > 0 ? 1 : 2) : 0;
     emit_out[i] = p.emit;
   }
+  rs_commit(s, slots, n, P, in_final);
   s->fe_last_n = n;
   s->fe_last_ragged = true;
   s->rg_calls++;
 }
 
+static long long ragged_ld(const conan_streams* s) { return s ? (long long)s->ctx->cfg.emf_segment * s->ctx->hop : 0; }
+
 int conan_step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final, const float* wav_dev,
                           const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream) {
-  return guarded([&] { step_wav_ragged(s, slots, n, samples, final, wav_dev, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false); });
+  return guarded([&] { step_wav_ragged(s, slots, n, samples, final, wav_dev, ragged_ld(s), mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false); });
 }
 
 int conan_step_wav_ragged_async(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final, const float* wav_dev,
                                 const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream) {
-  return guarded([&] { step_wav_ragged(s, slots, n, samples, final, wav_dev, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true); });
+  return guarded([&] { step_wav_ragged(s, slots, n, samples, final, wav_dev, ragged_ld(s), mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true); });
+}
+
+int conan_step_wav_ragged_ld(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final, const float* wav_dev,
+                             int64_t wav_ld, const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev,
+                             int32_t* emit_out, void* stream) {
+  return guarded([&] { step_wav_ragged(s, slots, n, samples, final, wav_dev, wav_ld, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false); });
+}
+
+int conan_step_wav_ragged_ld_async(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final,
+                                   const float* wav_dev, int64_t wav_ld, const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev,
+                                   float* wav_out_dev, int32_t* emit_out, void* stream) {
+  return guarded([&] { step_wav_ragged(s, slots, n, samples, final, wav_dev, wav_ld, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true); });
+}
+
+int conan_resample(conan_ctx* ctx, const conan_resample_cfg* cfg, const float* x_dev, int n, int64_t samples, float* y_dev, int64_t* out_samples,
+                   void* stream) {
+  return guarded([&] {
+    if (!ctx || !cfg || !x_dev || !y_dev) throw Error(CONAN_ERR_INVALID, "null argument");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    conan_ctx_resample(ctx, *cfg, x_dev, n, samples, y_dev, out_samples, (hipStream_t)stream);
+  });
+}
+
+int conan_streams_set_input_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg) {
+  return guarded([&] {
+    if (!s || !slots || !cfg) throw Error(CONAN_ERR_INVALID, "null argument");
+    if (!s->fe_audio) throw Error(CONAN_ERR_STATE, "conan_streams_set_input_rate: the stream-set has no streaming front-end (all three models)");
+    if (n < 1 || n > s->max_slots) throw Error(CONAN_ERR_INVALID, "slot count out of range");
+    const int S = s->ctx->cfg.emf_segment * s->ctx->hop, model_rate = 50 * s->ctx->hop;
+    const conan_resample_cfg& c = *cfg;
+    if (c.out_rate != model_rate)
+      throw Error(CONAN_ERR_INVALID, "conan_streams_set_input_rate: out_rate must be the model rate (hop * 50 = " + std::to_string(model_rate) + " Hz)");
+    std::vector<char> seen(s->max_slots, 0);
+    for (int i = 0; i < n; ++i) {
+      if (slots[i] < 0 || slots[i] >= s->max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
+      if (seen[slots[i]]) throw Error(CONAN_ERR_INVALID, "duplicate slot");
+      seen[slots[i]] = 1;
+    }
+    const ch::RsTable* t = nullptr;
+    if (c.in_rate != c.out_rate) {
+      t = &s->ctx->resample_table(c);
+      const long long num = (long long)S * c.in_rate;
+      if (num % c.out_rate || (num / c.out_rate) % t->f.orig)
+        throw Error(CONAN_ERR_INVALID, "conan_streams_set_input_rate: segment * hop samples at the model rate must be a whole number of input samples and a multiple of in_rate / gcd(in_rate, out_rate)");
+      const long long s_in = num / c.out_rate;
+      if (t->length(s_in) - t->ready(s_in) > S) throw Error(CONAN_ERR_INVALID, "conan_streams_set_input_rate: the filter's look-ahead is longer than segment * hop samples");
+    } else {
+      conan_resample_cfg probe = c;     // the configuration must still be a valid one
+      if (conan_resample_length(&probe, 0) < 0) throw Error(CONAN_ERR_INVALID, "conan_streams_set_input_rate: invalid resampler configuration");
+    }
+    for (int i = 0; i < n; ++i) {
+      const conan_streams::FeSlot& o = s->fe_slot[slots[i]];
+      const bool rs_fresh = s->rs_slot.empty() || (s->rs_slot[slots[i]].in == 0 && s->rs_slot[slots[i]].phase == 0);
+      if (o.recv != 0 || o.phase != 0 || o.frames != 0 || o.chunks != 0 || !rs_fresh)
+        throw Error(CONAN_ERR_STATE, "conan_streams_set_input_rate: slot " + std::to_string(slots[i]) + " is not at the start of an utterance (reset it with CONAN_MODEL_FRONTEND first)");
+    }
+    HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+    s->resample_init();
+    for (int i = 0; i < n; ++i) s->rs_slot[slots[i]] = conan_streams::RsSlot{t, 0, 0, 0};
+  });
 }
 
 int conan_step_wav_chunk(conan_streams* s, float* chunk_dev, void* stream) {

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstring>
 #include <map>
+#include <algorithm>
 #include <atomic>
 #include <memory>
 #include <mutex>
@@ -88,6 +89,29 @@ inline std::atomic<int>& device_live_streams(int device) {
   return counts[device & 63];
 }
 
+namespace ch {
+// One resampler configuration (resample.hip): the device tables and host copies of what the host plans with.
+struct RsTable {
+  cnk::RsFilter f;
+  std::vector<int> ph;                // [nph][2] klo, cnt
+  int win = 0;                        // LDS floats of a tile's input window (upper bound)
+  int in_rate = 0, out_rate = 0;
+  long long first(long long j) const { const long long q = j / f.nph; const int p = (int)(j - q * f.nph); return q * f.orig - f.w + ph[2 * p]; }
+  long long last(long long j) const { const long long q = j / f.nph; const int p = (int)(j - q * f.nph); return q * f.orig - f.w + ph[2 * p] + ph[2 * p + 1] - 1; }
+  long long length(long long samples) const { return (long long)(((__int128)f.nph * samples + f.orig - 1) / f.orig); }
+  // the longest prefix of outputs whose last tap is below `in` (and, like the whole signal, below length(in))
+  long long ready(long long in) const {
+    long long best = length(in);
+    for (int p = 0; p < f.nph; ++p) {
+      const long long c = (long long)ph[2 * p] + ph[2 * p + 1] - 1 - f.w;      // last(p + nph * q) = q * orig + c
+      const long long q = in - c <= 0 ? 0 : (in - c + f.orig - 1) / f.orig;
+      best = std::min(best, p + (long long)f.nph * q);
+    }
+    return best;
+  }
+};
+}  // namespace ch
+
 struct conan_ctx {
   int device = 0;
   conan_cfg cfg;
@@ -124,5 +148,11 @@ struct conan_ctx {
   float* fe_ws = nullptr; size_t fe_ws_floats = 0;
   void wav2mel(const conan_mel_cfg& m, const float* wav, int n, int samples, float* mel_out, hipStream_t st);
   std::string mel_tables(const conan_mel_cfg& m);          // window / twiddle / filterbank tables (vecs key prefix)
+  // resampler (resample.hip): taps built on first use per configuration (CONAN_ERR_INVALID for a configuration it refuses)
+  std::map<std::string, ch::RsTable> rs_tabs;
+  const ch::RsTable& resample_table(const conan_resample_cfg& c);
   ~conan_ctx();
 };
+
+// conan_resample's body (resample.hip)
+void conan_ctx_resample(conan_ctx* ctx, const conan_resample_cfg& c, const float* x, int n, int64_t samples, float* y, int64_t* out_samples, hipStream_t st);

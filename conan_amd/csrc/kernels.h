@@ -554,6 +554,33 @@ struct WavScatterArgs {
 };
 void launch_wav_scatter(const WavScatterArgs& a, hipStream_t st);
 
+// ---- polyphase resampler (resample.hip): torchaudio's windowed sinc (include/conan_hip.h, conan_resample_cfg).  Output j = p + nph * q
+// of a row is rs_dot over the inputs [first, first + cnt) with first = q * orig - w + klo[p]; a workgroup takes kRsTile outputs of one
+// row and stages their input window in LDS.
+constexpr int kRsTile = 256;
+constexpr int kRsRing = 32768;        // streaming input history per slot (floats; input sample i at i & (kRsRing - 1))
+constexpr int kRsMaxWindow = 16384;   // LDS floats of a tile's input window (a configuration that needs more is refused)
+struct RsFilter {
+  const float* taps;                  // [L][nph]: tap k' of phase p at k' * nph + p (zero past the phase's count)
+  const int* ph;                      // [nph][2]: klo (first tap, relative to q * orig - w), cnt
+  int orig, nph, w, L;
+};
+struct RsRow {                        // one call row of resample_stream_kernel (16 ints, uploaded through PinRing)
+  long long in0, out0;                // input samples received before this call; model-rate samples handed over before it
+  const float* taps; const int* ph;
+  int slot, m, h, orig, nph, w, L, copy;   // m input samples this call, h outputs; copy: the row has no rate (h = m samples verbatim)
+};
+static_assert(sizeof(RsRow) == 16 * sizeof(int), "RsRow is uploaded as 16 ints");
+struct ResampleArgs { const float* x; float* y; long long samples, nout; RsFilter f; int win; };
+void launch_resample(const ResampleArgs& a, int n, hipStream_t st);            // whole signals: x [n][samples] -> y [n][nout]
+struct ResampleStreamArgs {
+  const float* wav; long long wav_ld;   // this call's input, row r at r * wav_ld (never null: a dummy when no row has samples)
+  float* ring;                          // [max_slots][kRsRing]
+  float* out; long long out_ld;         // model-rate rows for the front-end
+  const RsRow* rows; int n, tiles, win;
+};
+void launch_resample_stream(const ResampleStreamArgs& a, hipStream_t st);
+
 // ---- style pass (per utterance) helpers
 struct RowMaskArgs { TRef x; TRef m; const int* lens; int T, n, C; int mode; };  // mode 0: sum|x|>0, 1: x[0]!=0
 void launch_rowmask(const RowMaskArgs& a, hipStream_t st);

@@ -1,0 +1,230 @@
+// Polyphase resampler for waveform input at other sample rates: torchaudio.functional.resample's windowed sinc (the reference
+// resamples on its input paths: librosa.core.load(sr=...), resampy.resample, torchaudio's Resample), restated in
+// include/conan_hip.h (conan_resample_cfg).  Taps are built on the host in double and rounded once to f32; every output is one
+// f32 FMA chain over its phase's taps in ascending order (rs_dot), shared by the whole-signal kernel (conan_resample) and the
+// streaming kernel (conan_step_wav* with conan_streams_set_input_rate), so the two agree bit for bit whatever their tiles.
+#include <climits>
+#include <cmath>
+#include <cstdio>
+
+#include "host_common.h"
+
+namespace cnk {
+
+// output of phase p: sum over k < cnt of taps[k][p] * win[off + k], ascending k.  The loop runs to the table's L for every lane
+// (no divergence); the select keeps the terms past the phase's count out of the sum, and the clamped index keeps the load in the window.
+__device__ __forceinline__ float rs_dot(const float* win, int off, int wlen, const float* __restrict__ taps, int nph, int p, int L, int cnt) {
+  float acc = 0.f;
+#pragma unroll 8      // the loads of 8 taps issue together; the FMA chain keeps its order
+  for (int k = 0; k < L; ++k) {
+    const float h = taps[(size_t)k * nph + p];
+    const float x = win[min(off + k, wlen - 1)];
+    const float t = fmaf(h, x, acc);
+    acc = k < cnt ? t : acc;
+  }
+  return acc;
+}
+
+// Output j of one row (the caller clamps j into the tile's valid outputs; j0 = the tile's first output): the tile's input window
+// [lo, lo + wlen) is the span of its outputs' taps (block min / max through two LDS words), loaded once with fetch(i) (input i,
+// zero outside the signal), then one output per thread.  Every thread of the block must call it (barriers).
+template <class Fetch>
+__device__ __forceinline__ float rs_output(float* lds, long long j0, long long j, const RsFilter& f, int win, const Fetch& fetch) {
+  int* red = reinterpret_cast<int*>(lds);
+  float* w = lds + 2;
+  const long long q0 = j0 / f.nph;
+  const long long base = q0 * f.orig - f.w + f.ph[2 * (int)(j0 - q0 * f.nph)];
+  const long long q = j / f.nph;
+  const int p = (int)(j - q * f.nph);
+  const int klo = f.ph[2 * p], cnt = f.ph[2 * p + 1];
+  const long long first = q * f.orig - f.w + klo;
+  if (threadIdx.x == 0) { red[0] = INT_MAX; red[1] = INT_MIN; }
+  __syncthreads();
+  atomicMin(&red[0], (int)(first - base));
+  atomicMax(&red[1], (int)(first + cnt - 1 - base));
+  __syncthreads();
+  const long long lo = base + red[0];
+  const int wlen = min(red[1] - red[0] + 1, win);
+  for (int t = threadIdx.x; t < wlen; t += blockDim.x) w[t] = fetch(lo + t);
+  __syncthreads();
+  return rs_dot(w, (int)(first - lo), wlen, f.taps, f.nph, p, f.L, cnt);
+}
+
+__global__ __launch_bounds__(kRsTile) void resample_kernel(const ResampleArgs a) {
+  extern __shared__ float lds[];
+  const long long j0 = (long long)blockIdx.x * kRsTile, jt = j0 + threadIdx.x;
+  const bool act = jt < a.nout;
+  const float* x = a.x + (size_t)blockIdx.y * a.samples;
+  const long long N = a.samples;
+  auto fetch = [&](long long i) {
+    const float v = x[i < 0 ? 0 : (i >= N ? N - 1 : i)];
+    return (i >= 0 && i < N) ? v : 0.f;
+  };
+  const float y = rs_output(lds, j0, act ? jt : a.nout - 1, a.f, a.win, fetch);
+  if (act) a.y[(size_t)blockIdx.y * a.nout + jt] = y;
+}
+
+// One launch per wav-in call: row r (blockIdx.y) resamples this call's h outputs of its slot - inputs before in0 from the slot's
+// history ring, this call's m inputs from the caller's row - into out row r, and appends the m inputs to the ring.  The host has
+// checked that the ring positions a call reads ([first tap of its first output, in0)) and the ones it writes ([in0, in0 + m))
+// are disjoint, so the workgroups of a row need no ordering.  Rows without a rate (copy) are copied verbatim.
+__global__ __launch_bounds__(kRsTile) void resample_stream_kernel(const ResampleStreamArgs a) {
+  extern __shared__ float lds[];
+  const RsRow R = a.rows[blockIdx.y];
+  const float* wav = a.wav + blockIdx.y * a.wav_ld;
+  float* out = a.out + blockIdx.y * a.out_ld;
+  const int stride = gridDim.x * kRsTile, t0 = blockIdx.x * kRsTile + threadIdx.x;
+  if (R.copy) {
+    for (int t = t0; t < R.m; t += stride) out[t] = wav[t];
+    return;
+  }
+  float* ring = a.ring + (size_t)R.slot * kRsRing;
+  if ((int)blockIdx.x * kRsTile < R.h) {          // uniform per block
+    const long long j0 = R.out0 + (long long)blockIdx.x * kRsTile, jt = j0 + threadIdx.x;
+    const bool act = t0 < R.h;
+    const long long end = R.in0 + R.m;
+    const int mlast = R.m > 0 ? R.m - 1 : 0;
+    auto fetch = [&](long long i) {
+      const long long d = i - R.in0;
+      const float vw = wav[d < 0 ? 0 : (d > mlast ? mlast : d)];
+      const float vr = ring[i & (kRsRing - 1)];
+      return (i < 0 || i >= end) ? 0.f : (d >= 0 ? vw : vr);
+    };
+    RsFilter f; f.taps = R.taps; f.ph = R.ph; f.orig = R.orig; f.nph = R.nph; f.w = R.w; f.L = R.L;
+    const float y = rs_output(lds, j0, act ? jt : R.out0 + R.h - 1, f, a.win, fetch);
+    if (act) out[jt - R.out0] = y;
+  }
+  for (int t = t0; t < R.m; t += stride) ring[(R.in0 + t) & (kRsRing - 1)] = wav[t];
+}
+
+void launch_resample(const ResampleArgs& a, int n, hipStream_t st) {
+  const dim3 grid((unsigned)((a.nout + kRsTile - 1) / kRsTile), (unsigned)n);
+  hipLaunchKernelGGL(resample_kernel, grid, dim3(kRsTile), (size_t)(a.win + 2) * sizeof(float), st, a);
+}
+
+void launch_resample_stream(const ResampleStreamArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(resample_stream_kernel, dim3((unsigned)a.tiles, (unsigned)a.n), dim3(kRsTile), (size_t)(a.win + 2) * sizeof(float), st, a);
+}
+
+}  // namespace cnk
+
+namespace {
+
+constexpr double kKaiserBeta = 14.769656459379492;
+
+long long gcd_ll(long long a, long long b) { while (b) { const long long t = a % b; a = b; b = t; } return a; }
+
+double bessel_i0(double x) {      // power series: every term positive, converges for the betas in use
+  double sum = 1.0, term = 1.0;
+  const double h = 0.25 * x * x;
+  for (int k = 1; k < 500; ++k) {
+    term *= h / ((double)k * k);
+    sum += term;
+    if (term < sum * 1e-17) break;
+  }
+  return sum;
+}
+
+// The configuration's reduced rates and filter size; CONAN_ERR_INVALID for a configuration the library refuses.
+struct RsShape { long long orig, nph; double base, half; int w; };
+RsShape rs_shape(const conan_resample_cfg& c) {
+  using ch::Error;
+  if (c.in_rate < 8000 || c.in_rate > 192000 || c.out_rate < 8000 || c.out_rate > 192000) throw Error(CONAN_ERR_INVALID, "resample: rates must be in 8000 .. 192000 Hz");
+  if (c.lowpass_filter_width < 1 || c.lowpass_filter_width > 128) throw Error(CONAN_ERR_INVALID, "resample: lowpass_filter_width must be in 1 .. 128");
+  if (!(c.rolloff > 0.f) || !(c.rolloff <= 1.f)) throw Error(CONAN_ERR_INVALID, "resample: rolloff must be in (0, 1]");
+  if (c.window != CONAN_RESAMPLE_HANN && c.window != CONAN_RESAMPLE_KAISER) throw Error(CONAN_ERR_INVALID, "resample: window must be CONAN_RESAMPLE_HANN or CONAN_RESAMPLE_KAISER");
+  if (c.window == CONAN_RESAMPLE_KAISER && !(c.beta <= 500.f)) throw Error(CONAN_ERR_INVALID, "resample: beta must be <= 500");
+  if (c.reserved[0] || c.reserved[1]) throw Error(CONAN_ERR_INVALID, "resample: reserved fields must be 0");
+  const long long g = gcd_ll(c.in_rate, c.out_rate);
+  RsShape s;
+  s.orig = c.in_rate / g; s.nph = c.out_rate / g;
+  s.base = (double)std::min(s.orig, s.nph) * (double)c.rolloff;
+  s.w = (int)std::ceil(c.lowpass_filter_width * (double)s.orig / s.base);
+  s.half = c.lowpass_filter_width * (double)s.orig / s.base;       // a phase's taps span (-half, half) input samples around its centre
+  if (2.0 * s.half > CONAN_RESAMPLE_MAX_TAPS - 2) throw Error(CONAN_ERR_INVALID, "resample: more than CONAN_RESAMPLE_MAX_TAPS taps per phase (rolloff too small for these rates)");
+  if ((double)s.nph * (2.0 * s.half + 2) > (double)(1 << 24)) throw Error(CONAN_ERR_INVALID, "resample: filter table above 2^24 taps for these rates");
+  if ((cnk::kRsTile - 1) * (double)s.orig / s.nph + 2.0 * s.half + 8 > cnk::kRsMaxWindow) throw Error(CONAN_ERR_INVALID, "resample: input window of a tile too large");
+  return s;
+}
+
+}  // namespace
+
+const ch::RsTable& conan_ctx::resample_table(const conan_resample_cfg& c) {
+  const RsShape s = rs_shape(c);
+  const double beta = c.window == CONAN_RESAMPLE_KAISER ? (c.beta > 0.f ? (double)c.beta : kKaiserBeta) : 0.0;
+  char key[160];
+  snprintf(key, sizeof(key), "rs.%d.%d.%d.%.9g.%d.%.17g", c.in_rate, c.out_rate, c.lowpass_filter_width, (double)c.rolloff, c.window, beta);
+  auto it = rs_tabs.find(key);
+  if (it != rs_tabs.end()) return it->second;
+  const int lpw = c.lowpass_filter_width, nph = (int)s.nph, orig = (int)s.orig, w = s.w;
+  const double PI = 3.14159265358979323846, scale = s.base / orig, i0b = beta > 0 ? bessel_i0(beta) : 1.0;
+  // per phase the contiguous range of taps with |t| < lpw (torchaudio clamps the others to +-lpw, where the window is < 1e-20)
+  std::vector<int> ph((size_t)2 * nph);
+  std::vector<std::vector<double>> val(nph);
+  int L = 0;
+  for (int p = 0; p < nph; ++p) {
+    const double centre = w + (double)orig * p / nph;
+    const long long k0 = std::max(0ll, (long long)std::floor(centre - s.half) - 2), k1 = std::min((long long)2 * w + orig - 1, (long long)std::ceil(centre + s.half) + 2);
+    int klo = -1;
+    for (long long k = k0; k <= k1; ++k) {
+      const double idx = (double)(k - w) / orig;
+      double t = (-(double)p / nph + idx) * s.base;          // torchaudio: arange(0, -new, -1) / new + idx, then * base_freq
+      if (!(std::fabs(t) < lpw)) continue;
+      if (klo < 0) klo = (int)k;
+      if ((int)k != klo + (int)val[p].size()) throw ch::Error(CONAN_ERR_INVALID, "resample: non-contiguous taps");
+      const double window = beta > 0 ? bessel_i0(beta * std::sqrt(1.0 - (t / lpw) * (t / lpw))) / i0b
+                                      : std::pow(std::cos(t * PI / lpw / 2), 2);
+      t *= PI;
+      const double sinc = t == 0 ? 1.0 : std::sin(t) / t;
+      val[p].push_back(sinc * (window * scale));
+    }
+    if (klo < 0) throw ch::Error(CONAN_ERR_INVALID, "resample: a phase without taps");
+    ph[2 * p] = klo; ph[2 * p + 1] = (int)val[p].size();
+    L = std::max(L, (int)val[p].size());
+  }
+  if (L > CONAN_RESAMPLE_MAX_TAPS) throw ch::Error(CONAN_ERR_INVALID, "resample: more than CONAN_RESAMPLE_MAX_TAPS taps per phase");
+  std::vector<float> taps((size_t)L * nph, 0.f);
+  for (int p = 0; p < nph; ++p)
+    for (size_t k = 0; k < val[p].size(); ++k) taps[k * nph + p] = (float)val[p][k];
+  ch::RsTable& t = rs_tabs[key];
+  float* d_taps = dev_alloc(taps.size(), false);
+  HIP_CHECK(hipMemcpy(d_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice));
+  int* d_ph = reinterpret_cast<int*>(dev_alloc(ph.size(), false));
+  HIP_CHECK(hipMemcpy(d_ph, ph.data(), ph.size() * sizeof(int), hipMemcpyHostToDevice));
+  t.f.taps = d_taps; t.f.ph = d_ph; t.f.orig = orig; t.f.nph = nph; t.f.w = w; t.f.L = L;
+  t.ph = std::move(ph);
+  t.in_rate = c.in_rate; t.out_rate = c.out_rate;
+  // a tile's window: the taps of kRsTile consecutive outputs span at most (kRsTile - 1) * orig / new + 2 * half + 2 inputs
+  t.win = (int)std::ceil((cnk::kRsTile - 1) * (double)orig / nph + 2.0 * s.half) + 8;
+  return t;
+}
+
+int64_t conan_resample_length(const conan_resample_cfg* cfg, int64_t samples) {
+  if (!cfg || samples < 0) return -1;
+  try {
+    const RsShape s = rs_shape(*cfg);
+    return (int64_t)(((__int128)s.nph * samples + s.orig - 1) / s.orig);
+  } catch (...) {
+    return -1;
+  }
+}
+
+void conan_ctx_resample(conan_ctx* ctx, const conan_resample_cfg& c, const float* x, int n, int64_t samples, float* y, int64_t* out_samples, hipStream_t st) {
+  using ch::Error;
+  if (n < 1 || n > 65535) throw Error(CONAN_ERR_INVALID, "resample: n must be in 1 .. 65535");
+  if (samples < 1) throw Error(CONAN_ERR_INVALID, "resample: samples must be >= 1");
+  if (c.in_rate == c.out_rate) {
+    (void)rs_shape(c);
+    HIP_CHECK(hipMemcpyAsync(y, x, (size_t)n * samples * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (out_samples) *out_samples = samples;
+    return;
+  }
+  const ch::RsTable& t = ctx->resample_table(c);
+  const long long nout = t.length(samples);
+  if ((nout + cnk::kRsTile - 1) / cnk::kRsTile > INT_MAX) throw Error(CONAN_ERR_INVALID, "resample: signal too long");
+  cnk::ResampleArgs a;
+  a.x = x; a.y = y; a.samples = samples; a.nout = nout; a.f = t.f; a.win = t.win;
+  cnk::launch_resample(a, n, st);
+  HIP_CHECK(hipGetLastError());
+  if (out_samples) *out_samples = nout;
+}

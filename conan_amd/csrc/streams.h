@@ -144,6 +144,18 @@ struct conan_streams {
   long long rg_calls = 0;
   bool fe_last_ragged = false;      // the last wav-in call was ragged: fe_chunk holds its rows grouped by emit (conan_step_wav_chunk refuses)
   void ragged_init();
+  // input resampler (conan_streams_set_input_rate): per slot the filter (null: input at the model rate), input samples received,
+  // model-rate samples handed to the front-end, phase (1: the input's final call has come).  The history ring ([max_slots][kRsRing],
+  // stream state) and per call a row table and model-rate staging (NS sets, set q reused after ev_rs[q]: the front-end launch that
+  // read it has completed) are allocated by the first conan_streams_set_input_rate.
+  struct RsSlot { const ch::RsTable* f = nullptr; long long in = 0, out = 0; int phase = 0; };
+  std::vector<RsSlot> rs_slot;
+  float* rs_ring = nullptr;
+  PinRing rs_pin;
+  cnk::RsRow* rs_rows[NS] = {}; float* rs_wav[NS] = {};
+  hipEvent_t ev_rs[NS] = {};
+  long long rs_calls = 0;
+  void resample_init();
   // --- vocoder
   Ring v_mel, v_pre;
   std::vector<VocStage> v_st;
@@ -234,6 +246,7 @@ struct conan_streams {
     for (int i = 0; i < NP; ++i) { if (ev_in[i]) (void)hipEventDestroy(ev_in[i]); if (ev_fence[i]) (void)hipEventDestroy(ev_fence[i]); }
     for (int i = 0; i < NP; ++i) { if (ev_wide[i]) (void)hipEventDestroy(ev_wide[i]); if (ev_emf[i]) (void)hipEventDestroy(ev_emf[i]); if (ev_front[i]) (void)hipEventDestroy(ev_front[i]); if (ev_voc[i]) (void)hipEventDestroy(ev_voc[i]); }
     for (int i = 0; i < NS; ++i) if (ev_stage[i]) (void)hipEventDestroy(ev_stage[i]);
+    for (int i = 0; i < NS; ++i) if (ev_rs[i]) (void)hipEventDestroy(ev_rs[i]);
     for (void* p : allocs) (void)hipFree(p);
     if (h_guard) (void)hipHostFree(h_guard);
     for (auto& e : prof_ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }

@@ -216,13 +216,27 @@ class StreamingVoiceConversionEngine:
         self.st.reset(self.slots, which=which)
         self.st.set_reference(self.slots, ref_mel, ref_len)
 
-    def start_wav(self, ref_mel, ref_len=None):
-        """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio."""
+    def start_wav(self, ref_mel, ref_len=None, in_rate=None, **filter):
+        """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
+        in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords."""
         self.start(ref_mel, ref_len, which=7 | 8)
+        self._set_rate(self.slots, in_rate, filter)
+
+    def _set_rate(self, slots, in_rate, filter):
+        """The slots' input rate (None: the model rate).  A stream-set that never had another rate is left alone."""
+        if in_rate is None and not self.st.input_rate_set:
+            return
+        self.st.set_input_rate(slots, in_rate or self.st.model_rate, **filter)
+
+    def _in_len(self, in_rate):
+        """Input samples of one non-final feed at `in_rate` (80 ms: seg*hop at the model rate)."""
+        L = self.seg * self.ctx.hop
+        return L if in_rate is None else L * int(in_rate) // self.st.model_rate
 
     @torch.no_grad()
     def feed(self, wav_chunk, final=False, pipelined=False, mel=None):
-        """Streaming waveform input (conan_step_wav): wav_chunk [B, seg*hop] (cuda; 0 .. seg*hop samples when final) ->
+        """Streaming waveform input (conan_step_wav): wav_chunk [B, seg*hop] (cuda; 0 .. seg*hop samples when final; at an input
+        rate set by start_wav, seg*hop*in_rate/model_rate) ->
         (wav [B, emit*hop], mel [B, emit, 80], codes [B, emit]) of the chunk this call emitted (emit = 0 on the first call: one
         chunk of algorithmic latency).  After final=True keep calling feed(empty, final=True) until it returns 0 frames.
         pipelined: conan_step_wav_async - the tensors are complete after self.st.join()."""
@@ -231,12 +245,13 @@ class StreamingVoiceConversionEngine:
         return w, m, c[:, :emit]
 
     @torch.no_grad()
-    def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None):
+    def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
-        the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit."""
-        self.start_wav(ref_mel, ref_len)
+        the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
+        resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit."""
+        self.start_wav(ref_mel, ref_len, in_rate, **filter)
         B, N = src_wav.shape
-        L = self.seg * self.ctx.hop
+        L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
         empty = src_wav.new_zeros(B, 0)
         wavs, mels, codes = [], [], []
@@ -258,11 +273,15 @@ class StreamingVoiceConversionEngine:
             self.st.join()
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
-    def open_slots(self, slots, ref_mel, ref_len=None):
+    def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
-        which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80])."""
+        which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
+        rate), one value or one per slot; filter: Context.resample's filter keywords."""
         self.st.reset(slots, which=7 | 8)
         self.st.set_reference(slots, ref_mel, ref_len)
+        rates = list(in_rate) if isinstance(in_rate, (list, tuple)) else [in_rate] * len(slots)
+        for r in dict.fromkeys(rates):
+            self._set_rate([s for s, x in zip(slots, rates) if x == r], r, filter)
 
     @torch.no_grad()
     def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None):
@@ -276,16 +295,18 @@ class StreamingVoiceConversionEngine:
         return [(w[i, :e * hop], m[i, :e], c[i, :e]) for i, e in enumerate(emit)]
 
     @torch.no_grad()
-    def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None):
+    def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
         frames; with no slot free the utterance waits for one); every tick is one feed_ragged over the slots live in it.
         -> one (wav, mel [T, 80], codes [T]) per utterance: what infer_wav would give for it alone.  The slot each utterance used is
-        left in self.staggered_slots."""
-        L = self.seg * self.ctx.hop
+        left in self.staggered_slots.  in_rates[u] (+ filter keywords): utterance u's sample rate (None: the model rate); one call
+        then mixes rates, with rows as wide as the widest input of the call."""
         U = len(src_wavs)
         assert len(starts) == U and len(ref_mel) == U
+        rates = list(in_rates) if in_rates is not None else [None] * U
+        Ls = [self._in_len(r) for r in rates]
         pending = sorted(range(U), key=lambda u: (starts[u], u))
         free = sorted(self.slots)
         live = {}                                         # utterance -> [slot, samples fed, final fed]
@@ -300,15 +321,16 @@ class StreamingVoiceConversionEngine:
                 self.staggered_slots[u] = live[u][0]
                 new.append(u)
             if new:
-                self.open_slots([live[u][0] for u in new], torch.stack([ref_mel[u] for u in new]))
+                self.open_slots([live[u][0] for u in new], torch.stack([ref_mel[u] for u in new]), in_rate=[rates[u] for u in new], **filter)
             if not live:
                 tick += 1
                 continue
             us = list(live)
             rows, samples, final, draining = [], [], [], []
+            width = max(Ls[u] for u in us)
             for u in us:
                 x, (slot, pos, fin) = src_wavs[u], live[u]
-                N = x.shape[0]
+                N, L = x.shape[0], Ls[u]
                 last = (N - 1) // L * L                   # the final call takes the remaining 1 .. L samples
                 draining.append(fin)
                 if pos < last:
@@ -321,7 +343,7 @@ class StreamingVoiceConversionEngine:
                     piece = x[:0]
                     final.append(1)
                 samples.append(piece.shape[0])
-                rows.append(torch.nn.functional.pad(piece, (0, L - piece.shape[0])))
+                rows.append(torch.nn.functional.pad(piece, (0, width - piece.shape[0])))
             res = self.feed_ragged([live[u][0] for u in us], torch.stack(rows), samples, final, pipelined=pipelined, mel=mel)
             for u, was_final, (w, m, c) in zip(us, draining, res):
                 if m.shape[0]:

@@ -73,11 +73,12 @@ class StreamingVoiceConversion:
         st.close()
 
     def _wav_to_mel(self, wav) -> torch.Tensor:
-        """inference/Conan.py:57-70 on the GPU: path or float array -> clipped log-mel [T, 80] (cuda)."""
-        from ..utils.audio import load_wav
+        """inference/Conan.py:57-70 on the GPU: path or float array -> clipped log-mel [T, 80] (cuda).  A file at another rate is
+        resampled on the GPU (kaiser_best) where the reference's librosa.core.load(sr=...) resamples."""
+        from ..utils.audio import load_wav_resampled
         hp = self.hparams
         if isinstance(wav, str):
-            wav = load_wav(wav, hp["audio_sample_rate"])
+            wav = load_wav_resampled(wav, hp["audio_sample_rate"], self.ctx)
         if hp.get("loud_norm", False):
             raise NotImplementedError("loud_norm is off on the inference path (egs_bases/tts/dataset_params.yaml:15)")
         return self.ctx.wav2mel(torch.as_tensor(np.asarray(wav), dtype=torch.float32), fft_size=hp["fft_size"], hop_size=hp["hop_size"],

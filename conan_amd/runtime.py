@@ -98,6 +98,23 @@ class Context:
         assert got.value == frames
         return mel
 
+    def resample(self, x, orig_freq, new_freq=16000, lowpass_filter_width=6, rolloff=0.99, resampling_method="sinc_interp_hann", beta=None,
+                 preset=None):
+        """torchaudio.functional.resample on the GPU (conan_resample): x [..., N] float32 -> [..., ceil(new * N / orig)] with
+        new / orig = new_freq / orig_freq reduced.  preset='hann' (torchaudio's defaults) or 'kaiser_best' (resampy's kaiser_best
+        as torchaudio documents it) replaces the filter keywords.  orig_freq == new_freq returns a copy."""
+        cfg = _lib.resample_cfg(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta, preset)
+        x = x.to(torch.device("cuda", self.device), torch.float32).contiguous()
+        lead, N = x.shape[:-1], x.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        nout = _lib.check(self.lib.conan_resample_length(C.byref(cfg), N))
+        y = torch.empty(*lead, nout, device=x.device)
+        if n and N:
+            got = C.c_int64(0)
+            _lib.check(self.lib.conan_resample(self.h, C.byref(cfg), _ptr(x), n, N, _ptr(y), C.byref(got), _stream()))
+            assert got.value == nout
+        return y
+
     def streams(self, max_slots, max_frames=4, max_ref_frames=256, arith="auto", flags=0, dev_plan=None):
         """A stream-set.  arith: 'auto' (library default), 'f32' (f32-input MFMA everywhere) or 'limb' (fp32 products of the
         vocoder's matrix kernels as bf16 limb products) - conan_streams_opts.arith; flags: _lib.STREAMS_*; dev_plan: developer /
@@ -132,6 +149,7 @@ class Streams:
         self.dev = torch.device("cuda", ctx.device)
         c = ctx.cfg
         self.seg, self.rc = c.emf_segment, c.emf_right_context
+        self.input_rate_set = False      # set_input_rate has run on this stream-set (its history ring exists)
 
     @property
     def state_bytes(self):
@@ -159,6 +177,21 @@ class Streams:
         a, p = _i32(slots)
         _lib.check(self.lib.conan_streams_reset(self.h, p, len(a), which, _stream()))
         self._release()
+
+    def set_input_rate(self, slots, rate, **filter):
+        """conan_streams_set_input_rate: the slots' wav-in input arrives at `rate` Hz and is resampled on the GPU to the model rate
+        (hop * 50) in front of the streaming front-end.  filter: Context.resample's filter keywords (lowpass_filter_width, rolloff,
+        resampling_method, beta, or preset='hann' / 'kaiser_best'; default hann).  The slots must be at the start of an utterance;
+        the rate survives CONAN_MODEL_FRONTEND resets; rate == the model rate restores the model-rate path."""
+        a, p = _i32(slots)
+        cfg = _lib.resample_cfg(rate, self.model_rate, **filter)
+        _lib.check(self.lib.conan_streams_set_input_rate(self.h, p, len(a), C.byref(cfg)))
+        self.input_rate_set = True
+
+    @property
+    def model_rate(self):
+        """The wav-in steps' model rate: hop * 50 (20 ms frames)."""
+        return self.ctx.hop * 50
 
     def set_reference(self, slots, ref_mel, ref_len=None):
         """ref_mel: cuda float32 [n, Tr, 80]."""
@@ -323,7 +356,8 @@ class Streams:
         _lib.check(self.lib.conan_step_async(self.h, p, n, emit, _ptr(mel_chunk), _ptr(codes), _ptr(mel_out), _ptr(wav_out), _stream()))
 
     def step_wav(self, slots, wav, final=False, codes=None, mel_out=None, wav_out=None, mel=None):
-        """Waveform-in chunk step (conan_step_wav): wav [n, samples] cuda float32, samples = seg*hop (0 .. seg*hop when final).
+        """Waveform-in chunk step (conan_step_wav): wav [n, samples] cuda float32, samples = seg*hop (0 .. seg*hop when final);
+        slots with an input rate (set_input_rate) take seg*hop*rate/model_rate samples instead.
         -> (emit, codes [n, seg], mel [n, emit, 80], wav [n, emit*hop]); emit = 0: no chunk this call (the first call, the end of a
         drain).  mel: dict of Context.wav2mel's front-end keywords (framing 0 only)."""
         return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, False)
@@ -359,7 +393,8 @@ class Streams:
     def step_wav_ragged(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None):
         """Waveform-in chunk step for slots at different positions of their utterances (conan_step_wav_ragged): slot i takes the
         first samples[i] samples of wav row i (wav [n, <= seg*hop] cuda float32, or None when every samples[i] is 0) and is stepped
-        as step_wav([slot], samples[i], final[i]) alone would step it.  -> (emit: list of n ints, codes [n, seg], mel [n, seg, 80],
+        as step_wav([slot], samples[i], final[i]) alone would step it.  Rows wider than seg*hop (slots with an input rate above the
+        model rate) go through conan_step_wav_ragged_ld with the row width as stride.  -> (emit: list of n ints, codes [n, seg], mel [n, seg, 80],
         wav [n, seg*hop]): row i holds emit[i] frames; the rest of the row is left as it was."""
         return self._step_wav_ragged(slots, wav, samples, final, codes, mel_out, wav_out, mel, False)
 
@@ -374,11 +409,13 @@ class Streams:
         sm, sp = _i32(samples)
         fi, fp = _i32([int(bool(f)) for f in final])
         assert len(sm) == n and len(fi) == n, (n, len(sm), len(fi))
+        ld = L
         if wav is not None:
             wav = wav.to(self.dev, torch.float32)
-            assert wav.dim() == 2 and wav.shape[0] == n and wav.shape[1] <= L, wav.shape
-            if wav.shape[1] < L:                      # rows are seg*hop apart in the C-ABI
+            assert wav.dim() == 2 and wav.shape[0] == n, wav.shape
+            if wav.shape[1] < L:                      # rows are seg*hop apart in conan_step_wav_ragged
                 wav = torch.nn.functional.pad(wav, (0, L - wav.shape[1]))
+            ld = wav.shape[1]
             wav = wav.contiguous()
         if codes is None:
             codes = torch.empty(n, self.seg, dtype=torch.int32, device=self.dev)
@@ -388,10 +425,14 @@ class Streams:
             wav_out = torch.empty(n, L, device=self.dev)
         mc = mel_cfg(**(mel or {}))
         emit = (C.c_int32 * n)()
-        fn = self.lib.conan_step_wav_ragged_async if pipelined else self.lib.conan_step_wav_ragged
         if pipelined:
             self._keep.append((wav, wav_out, codes, mel_out))
-        _lib.check(fn(self.h, p, n, sp, fp, _ptr(wav), C.byref(mc), _ptr(codes), _ptr(mel_out), _ptr(wav_out), emit, _stream()))
+        if ld == L:
+            fn = self.lib.conan_step_wav_ragged_async if pipelined else self.lib.conan_step_wav_ragged
+            _lib.check(fn(self.h, p, n, sp, fp, _ptr(wav), C.byref(mc), _ptr(codes), _ptr(mel_out), _ptr(wav_out), emit, _stream()))
+        else:
+            fn = self.lib.conan_step_wav_ragged_ld_async if pipelined else self.lib.conan_step_wav_ragged_ld
+            _lib.check(fn(self.h, p, n, sp, fp, _ptr(wav), ld, C.byref(mc), _ptr(codes), _ptr(mel_out), _ptr(wav_out), emit, _stream()))
         if not pipelined:
             self._release()
         return list(emit), codes, mel_out, wav_out

@@ -1,9 +1,10 @@
 """The reference's wav -> mel front-end interface (utils/audio/__init__.py:37-84) on the HIP path.
 
 `librosa_wav2spec` keeps the reference's keyword arguments; the STFT, mel projection and log run on the GPU
-(conan_wav2mel).  A path argument is read with the standard-library `wave` module (PCM wav at the configured sample
-rate: the reference resamples through librosa.core.load, which is not re-implemented); loud_norm / trim_long_sil (pyloudnorm /
-webrtcvad, both off in egs/conan_emformer.yaml) raise NotImplementedError."""
+(conan_wav2mel).  A path argument is read with the standard-library `wave` module; a file at another rate is resampled on the GPU
+(conan_resample, preset kaiser_best) where the reference's librosa.core.load(sr=...) resamples (with soxr_hq, a different filter:
+the samples are not librosa's bit for bit).  loud_norm / trim_long_sil (pyloudnorm / webrtcvad, both off in egs/conan_emformer.yaml)
+raise NotImplementedError."""
 import wave
 
 import numpy as np
@@ -11,12 +12,27 @@ import torch
 
 
 def load_wav(path, sample_rate):
-    """PCM wav file -> float32 mono in [-1, 1]; the file's rate must equal `sample_rate`."""
+    """PCM wav file -> float32 mono in [-1, 1]; the file's rate must equal `sample_rate` (load_wav_resampled resamples)."""
+    x, sr = read_wav(path)
+    if sr != sample_rate:
+        raise ValueError(f"{path}: sample rate {sr} != {sample_rate} (resampling is outside this front-end)")
+    return x
+
+
+def load_wav_resampled(path, sample_rate, ctx):
+    """PCM wav file -> float32 mono at `sample_rate`: a file at another rate is resampled on the GPU (ctx.resample, preset
+    kaiser_best: resampy's kaiser_best as torchaudio restates it), where the reference's librosa.core.load(sr=sample_rate) resamples."""
+    x, sr = read_wav(path)
+    if sr == sample_rate:
+        return x
+    return ctx.resample(torch.from_numpy(x), sr, sample_rate, preset="kaiser_best").cpu().numpy()
+
+
+def read_wav(path):
+    """PCM wav file -> (float32 mono in [-1, 1], its sample rate)."""
     with wave.open(path, "rb") as f:
         sr, ch, width, n = f.getframerate(), f.getnchannels(), f.getsampwidth(), f.getnframes()
         raw = f.readframes(n)
-    if sr != sample_rate:
-        raise ValueError(f"{path}: sample rate {sr} != {sample_rate} (resampling is outside this front-end)")
     if width == 2:
         x = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
     elif width == 4:
@@ -25,7 +41,7 @@ def load_wav(path, sample_rate):
         x = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
     else:
         raise ValueError(f"{path}: unsupported sample width {width}")
-    return x.reshape(-1, ch).mean(1) if ch > 1 else x
+    return (x.reshape(-1, ch).mean(1) if ch > 1 else x), sr
 
 
 def librosa_pad_lr(x, fsize, fshift, pad_sides=1):
@@ -47,7 +63,7 @@ def librosa_wav2spec(wav_path, fft_size=1024, hop_size=256, win_length=1024, win
         raise NotImplementedError("only the Hann window of the reference configuration")
     if ctx is None:
         raise ValueError("librosa_wav2spec needs ctx= (a finalized conan_amd.runtime.Context): the transform runs on the GPU")
-    wav = load_wav(wav_path, sample_rate) if isinstance(wav_path, str) else np.asarray(wav_path, dtype=np.float32)
+    wav = load_wav_resampled(wav_path, sample_rate, ctx) if isinstance(wav_path, str) else np.asarray(wav_path, dtype=np.float32)
     wav_orig = np.copy(wav)
     mel = ctx.wav2mel(torch.from_numpy(wav), fft_size=fft_size, hop_size=hop_size, win_length=win_length, num_mels=num_mels,
                       fmin=fmin, fmax=fmax, sample_rate=sample_rate, eps=eps, mel_vmin=-1e30, mel_vmax=1e30)[0].cpu().numpy()

@@ -364,6 +364,62 @@ int conan_step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const i
 int conan_step_wav_ragged_async(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final, const float* wav_dev,
                                 const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream);
 
+/* Input sample rates other than the model rate (added within ABI 9: a caller detects it by the exported symbols).
+ * The filter is torchaudio.functional.resample's windowed sinc: with g = gcd(in_rate, out_rate), orig = in_rate / g,
+ * new = out_rate / g, base = min(orig, new) * rolloff, w = ceil(lpw * orig / base), output j = p + new * q is
+ * sum_k K[p][k] x[q * orig + k - w] (x zero outside the signal) with K[p][k] = sinc(pi t) window(t) base / orig,
+ * t = ((k - w) / orig - p / new) * base; taps with |t| >= lpw (clamped by torchaudio, < 1e-20) are dropped.  The taps are
+ * computed in double and rounded once to f32; every output is an f32 FMA chain over its phase's taps in ascending order, the
+ * same in every entry point, so the streaming and whole-signal paths agree bit for bit.  Presets: hann = lpw 6, rolloff 0.99
+ * (torchaudio's defaults); kaiser_best = lpw 64, rolloff 0.9475937167399596, Kaiser beta 14.769656459379492.
+ * Accepted: lpw 1 .. 128, rolloff in (0, 1], rates 8000 .. 192000 Hz, reserved = 0, and at most CONAN_RESAMPLE_MAX_TAPS taps per
+ * phase and 2^24 in all (a very small rolloff exceeds them). */
+#define CONAN_RESAMPLE_HANN 0
+#define CONAN_RESAMPLE_KAISER 1
+#define CONAN_RESAMPLE_MAX_TAPS 8192
+typedef struct conan_resample_cfg {
+  int32_t in_rate, out_rate;          /* Hz */
+  int32_t lowpass_filter_width;       /* 1..128 */
+  float rolloff;                      /* (0, 1] */
+  int32_t window;                     /* CONAN_RESAMPLE_HANN | CONAN_RESAMPLE_KAISER */
+  float beta;                         /* Kaiser; <= 0 selects 14.769656459379492 */
+  int32_t reserved[2];                /* must be 0 */
+} conan_resample_cfg;
+/* ceil(new * samples / orig) (host only); -1 for an invalid configuration or samples < 0. */
+int64_t conan_resample_length(const conan_resample_cfg* cfg, int64_t samples);
+/* Whole signals: x_dev[n][samples] -> y_dev[n][conan_resample_length(cfg, samples)] (*out_samples, may be NULL), on `stream`.
+ * in_rate == out_rate is a copy. */
+int conan_resample(conan_ctx* ctx, const conan_resample_cfg* cfg, const float* x_dev, int n, int64_t samples,
+                   float* y_dev, int64_t* out_samples, void* stream);
+/* Streaming: slots' input arrives at cfg->in_rate and is resampled on the GPU, in front of the streaming front-end, with a
+ * history of its own per slot.  cfg->out_rate must be the model rate, hop * 50 (20 ms frames; 16000 at the shipped config), and
+ * the wav-in steps' conan_mel_cfg.sample_rate must equal it.  80 ms of input, seg * hop * in_rate / out_rate samples, must be a
+ * whole number and a multiple of orig (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000, 176400 and
+ * 192000 Hz pass), and the filter's look-ahead (below) at most seg * hop samples.  Every slot must be at the start of an utterance
+ * (no sample since its last CONAN_MODEL_FRONTEND reset), else CONAN_ERR_STATE; on any error no slot changes.  The rate persists
+ * across CONAN_MODEL_FRONTEND resets, which clear the resampler's history; in_rate == out_rate restores the model-rate path.
+ * The first call allocates a history ring of 32768 floats (128 KB) per slot of the stream-set, which conan_streams_state_bytes
+ * counts from then on.
+ * With a rate set, `samples` of the wav-in steps counts input-rate samples: a non-final call takes exactly
+ * seg * hop * in_rate / out_rate (3840 at 48 kHz), a final call 0 .. that.  A call hands the front-end the longest prefix of
+ * model-rate samples whose last tap has arrived: the first call is short by the filter's look-ahead (at most 12 samples for hann,
+ * 67 for kaiser_best when downsampling, 135 for kaiser_best from 8 kHz, 270 at lpw 128), every later non-final call hands over
+ * seg * hop.  The final call hands over at most seg * hop; the rest goes out on the next drain call, and the front-end sees
+ * `final` on the call that delivers the last sample - so an utterance can take one more drain call than at the model rate.
+ * Look-aheads up to the front-end's slack (fft_size 1024: 448 samples) keep the model-rate emit schedule; longer ones give the
+ * same bits with chunks one call later.  conan_step_wav: all slots of a call share one configuration.  One launch per call
+ * resamples every slot of the call that has a rate. */
+int conan_streams_set_input_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg);
+/* conan_step_wav_ragged with an explicit row stride of wav_dev (floats), so that one call can mix slots at different rates
+ * (wav_ld >= every samples[i]).  conan_step_wav_ragged is this with wav_ld = seg * hop, where a row that needs more samples
+ * than that (a non-final slot above the model rate) is CONAN_ERR_INVALID. */
+int conan_step_wav_ragged_ld(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final, const float* wav_dev,
+                             int64_t wav_ld, const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev,
+                             int32_t* emit_out, void* stream);
+int conan_step_wav_ragged_ld_async(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final,
+                                   const float* wav_dev, int64_t wav_ld, const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev,
+                                   float* wav_out_dev, int32_t* emit_out, void* stream);
+
 /* Measurement hook (replaces the reference's Timer('hifigan') around the vocoder forward,
  * utils/commons/meters.py:21-42, tasks/tts/vocoder_infer/hifigan.py:28): between begin and end every
  * launch of the conv_mfma kernel family is bracketed by HIP events on its launch stream.  end() waits
