@@ -18,10 +18,15 @@ config.priming_steps): the first steps of a freshly built process are not the st
 GPU comes out of seconds of idling).  What K and W do to the reading, one box: K = 200 / W = 30 1.308 ms per step, K = 60 / W = 10
 1.33 (the defaults), K = 20 / W = 5 1.36-1.38 primed and 1.41-1.42 unprimed - a timed region starts from an empty pipeline, so it pays the
 first chunk's Emformer + decoder latency (0.73 ms) before its first vocoder step: 0.037 ms per step at K = 20, 0.004 at K = 200.
-Both readings are in the line (round 5): the very same timed(K, W) runs once BEFORE the priming pass -> roofline.ms_per_step_unprimed
+Both readings are in the `--full` line (round 5): the very same timed(K, W) runs once BEFORE the priming pass -> roofline.ms_per_step_unprimed
 (exactly what `--warmup W` alone gives), and once after it -> ms_per_step / value.  roofline.vocoder_alone_ms is the vocoder stage's
 launches back to back on one stream (conan_hifigan_step loop, no front-end resident), roofline.frontend_cost_ms = ms_per_step minus it:
 what the Emformer + decoder stages cost the pipelined step.
+
+A plain run does what the headline needs and nothing more: setup (including the unprimed pass and the priming pass, which the
+timed steps follow), W + K steps, `--dump-outputs`, and the blocking latency leg the metric names (p50_latency_ms).  `--full` adds
+every other leg: step_time_stats, the roofline (vocoder alone, the per-kernel HIP-event profile), the batch-1 / batch-4 latencies,
+the mel front-end rate, the CPU baseline and the other arithmetic form.  Without it those keys are null or absent.
 """
 import argparse
 import json
@@ -128,7 +133,7 @@ def cpu_baseline():
     encoders and of the vocoder every chunk, numpy hops) and stateful (the arithmetic the GPU path performs) - at the
     host's best thread count ("all-core": PyTorch's CPU convolutions collapse when over-threaded on a 256-thread
     host, so a short probe picks among 8/16/32/64/all) and at 1 thread.  One warm-up + timed runs, median.  The samples
-    are bounded so that the default bench run stays within minutes; each entry says what it covered."""
+    are bounded so that a `--full` bench run stays within minutes; each entry says what it covered."""
     from conan_amd import configs, synth
     from oracle import emformer as oemf
     from oracle import hifigan as ohifi
@@ -466,10 +471,12 @@ def main():
                     help="setup: pipelined steps run once after the stream-set is built, before the W warm-up steps (0: none)")
     ap.add_argument("--fixed-plan", action="store_true", help="CONAN_STREAMS_FIXED_PLAN: the launch plan from max_slots only (a stream's bits do not depend on the other active slots)")
     ap.add_argument("--dev-plan", default=None, help="developer switches of the launch plan, 'NAME=value;...' (conan_streams_opts.dev_plan; A/B runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline: step intervals, roofline and per-kernel "
+                                                        "profile, batch-1 / batch-4 latency, front-end rate, CPU baseline, other arithmetic form")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--latency-steps", type=int, default=40)
-    ap.add_argument("--no-b1", action="store_true", help="skip the batch=1 latency leg (keeps profiler summaries to one workload)")
-    ap.add_argument("--no-other", action="store_true", help="skip the datapoint of the other arithmetic form")
+    ap.add_argument("--no-b1", action="store_true", help="with --full: skip the batch=1 latency leg (keeps profiler summaries to one workload)")
+    ap.add_argument("--no-other", action="store_true", help="with --full: skip the datapoint of the other arithmetic form")
     ap.add_argument("--marks", action="store_true", help="bracket the timed steps with cnk::profile_mark_kernel dispatches and skip "
                                                          "every other leg (rocprofv3 --pmc passes: tools/summarize_pmc.py keeps the dispatches between the marks)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -502,6 +509,7 @@ def main():
     hop, seg = run.hop, run.seg
 
     # the unprimed reading: exactly W warm-up + K timed steps on the freshly built stream-set (what --warmup alone means) ...
+    # (run in a plain line too, where it is not reported: the stream state the timed steps start from includes these steps)
     dt_unprimed = run.timed(args.steps, args.warmup) if (args.prime > 0 and not args.marks) else None
     # ... and the steady-state one behind the priming pass: `value`
     if args.prime > 0:
@@ -546,7 +554,7 @@ def main():
     ms_step = dt / args.steps * 1e3
 
     step_stats = None
-    if not args.marks and not window:
+    if args.full and not args.marks and not window:
         step_stats = run.step_intervals(min(max(args.steps, 2), 60))
     frames_per_step = (window + seg) if window else seg           # decoder / vocoder frames computed per stream per step
 
@@ -555,10 +563,10 @@ def main():
     if not args.marks:
         lat_stats = run.latencies(args.latency_steps)
         p50 = lat_stats["p50_ms"]
-        if rank == 0:
+        if rank == 0 and args.full:
             voc_alone = run.vocoder_alone()
 
-    if rank == 0 and not args.marks:
+    if rank == 0 and args.full and not args.marks:
         # roofline of the dominant kernel: HIP events around every launch of the matrix kernels on their stream
         prof = run.kernel_profile()
         nprof, kernels = prof["nprof"], prof["kernels"]

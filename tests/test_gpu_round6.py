@@ -242,3 +242,33 @@ def test_bench_launcher_child_process_path_with_one_rank():
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["value"] > 0 and d["ranks"]["rccl_world"] == 1
+
+
+def test_bench_plain_line_skips_the_other_legs_and_full_keeps_them(tmp_path):
+    """A plain `bench.py` run does only what the headline needs (setup, W + K steps, --dump-outputs, the latency leg its metric
+    names); `--full` adds the other legs.  Both run the very same headline steps: the dumped outputs are bit-identical."""
+    import json
+    import os
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    lines = {}
+    for mode in ("plain", "full"):
+        cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--prime", "3",
+               "--latency-steps", "2", "--streams", "8", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / mode)]
+        r = subprocess.run(cmd + (["--full"] if mode == "full" else []), env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines[mode] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for d in (plain, full):
+        assert d["value"] > 0 and d["ms_per_step"] > 0 and d["p50_latency_ms"] > 0 and d["config"]["priming_steps"] == 3
+        assert d["unit"] == "chunks/s" and d["higher_is_better"] is True and d["metric"] == full["metric"] and d["dtype"] == full["dtype"]
+    assert plain["roofline"] is None and plain["cpu_baseline"] is None and plain["step_time_stats"] is None and "frontend" not in plain
+    r = full["roofline"]
+    assert r["vocoder_alone_ms"] > 0 and r["ms_per_step_unprimed"] > 0 and r["matrix_kernels"] and full["step_time_stats"]["n"] > 0
+    assert "ms" in full["frontend"]
+    for name in ("codes", "mel", "wav"):
+        assert np.array_equal(np.load(tmp_path / "plain" / (name + ".npy")), np.load(tmp_path / "full" / (name + ".npy"))), name

@@ -3,7 +3,7 @@
 # alternating runs; then one FETCH_SIZE pass per layout (HBM fetch of the decoder launch per step).
 cd /tmp && export TMPDIR=/tmp
 cd /root/repo
-B="python bench.py --no-cpu-baseline --no-b1 --no-other --steps 60 --warmup 10"
+B="python bench.py --full --no-cpu-baseline --no-b1 --no-other --steps 60 --warmup 10"
 P="import sys,json; d=json.loads(sys.stdin.readline()); r=d['roofline']; print(sys.argv[1], 'ms/step %.4f p50 %.3f vocoder alone %.3f' % (d['ms_per_step'], d['p50_latency_ms'], r['vocoder_alone_ms']))"
 for i in 1 2 3; do
   $B 2>/dev/null | python -c "$P" "group-fastest "

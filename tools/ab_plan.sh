@@ -6,6 +6,6 @@ P="import sys,json; d=json.loads(sys.stdin.readline()); r=d['roofline']; print('
 for i in $(seq $N); do
   for plan in "$@"; do
     if [ -z "$plan" ]; then A=""; else A="--dev-plan $plan"; fi
-    timeout 600 python bench.py --no-cpu-baseline --no-b1 --no-other --steps 60 --warmup 10 $A $AB_FLAGS 2>/dev/null | grep '^{' | python3 -c "$P" "$plan"
+    timeout 600 python bench.py --full --no-cpu-baseline --no-b1 --no-other --steps 60 --warmup 10 $A $AB_FLAGS 2>/dev/null | grep '^{' | python3 -c "$P" "$plan"
   done
 done

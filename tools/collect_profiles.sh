@@ -12,7 +12,7 @@ TAG=$W; if [ "$A" != "auto" ]; then TAG=${W}_$A; fi
 cd /tmp && export TMPDIR=/tmp
 cd /root/repo
 O=gpurun_out/${R}_prof_$TAG; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 bench.py --workload $W --arith $A --steps 30 --warmup 5 --no-cpu-baseline --no-b1 --no-other > $O/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 bench.py --full --workload $W --arith $A --steps 30 --warmup 5 --no-cpu-baseline --no-b1 --no-other > $O/stats.log 2>&1
 # the same kernels in blocking steps only (the schedule bench.py's roofline events are taken in), restricted to the dispatches
 # between two profile marks (tools/blocking_trace.py: 6 timed steps; tools/marked_stats.py) - the per-utterance style pass runs
 # the same conv_mfma instantiations as the upsamplers and must not be averaged into them
