@@ -390,6 +390,14 @@ int conan_hifigan_step(conan_streams* s, const int32_t* slots, int n, int frames
   });
 }
 
+// The preconditions of every fused chunk step (conan_step[_async], the wav-in steps): all three models, an upsampler without look-ahead.
+static void check_chunk_step(const conan_streams* s, const char* who) {
+  const int all = CONAN_MODEL_EMFORMER | CONAN_MODEL_CONAN | CONAN_MODEL_HIFIGAN;
+  if ((s->ctx->cfg.models & all) != all) throw Error(CONAN_ERR_STATE, std::string(who) + " needs all three models in the context");
+  if (s->ctx->cfg.voc_upsample == 2) throw Error(CONAN_ERR_UNSUPPORTED, "fused chunk steps carry vocoder state from chunk to chunk; upsample 'nn' (CausalUpsampleBlock1) looks ahead: "
+                                                                      "step the Emformer and decoder per chunk and run conan_hifigan_step over the mel prefix after a reset (inference/Conan.py:147-155)");
+}
+
 // The stages of one chunk step on `st` for the slots set_slots has just installed (conan_step, conan_step_wav).
 static void step_blocking(conan_streams* s, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev, float* mel_out_dev,
                           float* wav_out_dev, hipStream_t st) {
@@ -411,10 +419,7 @@ int conan_step(conan_streams* s, const int32_t* slots, int n, int emit, const fl
                float* mel_out_dev, float* wav_out_dev, void* stream) {
   return guarded([&] {
     if (!s || !slots || !mel_chunk_dev || !wav_out_dev) throw Error(CONAN_ERR_INVALID, "null argument");
-    const int all = CONAN_MODEL_EMFORMER | CONAN_MODEL_CONAN | CONAN_MODEL_HIFIGAN;
-    if ((s->ctx->cfg.models & all) != all) throw Error(CONAN_ERR_STATE, "conan_step needs all three models in the context");
-    if (s->ctx->cfg.voc_upsample == 2) throw Error(CONAN_ERR_UNSUPPORTED, "fused chunk steps carry vocoder state from chunk to chunk; upsample 'nn' (CausalUpsampleBlock1) looks ahead: "
-                                                                        "step the Emformer and decoder per chunk and run conan_hifigan_step over the mel prefix after a reset (inference/Conan.py:147-155)");
+    check_chunk_step(s, "conan_step");
     const int seg = s->ctx->cfg.emf_segment;
     if (emit < 1 || emit > seg) throw Error(CONAN_ERR_INVALID, "emit must be in [1, segment]");
     hipStream_t st = (hipStream_t)stream;
@@ -524,10 +529,7 @@ int conan_step_async(conan_streams* s, const int32_t* slots, int n, int emit, co
                      float* mel_out_dev, float* wav_out_dev, void* stream) {
   return guarded([&] {
     if (!s || !slots || !mel_chunk_dev || !wav_out_dev) throw Error(CONAN_ERR_INVALID, "null argument");
-    const int all = CONAN_MODEL_EMFORMER | CONAN_MODEL_CONAN | CONAN_MODEL_HIFIGAN;
-    if ((s->ctx->cfg.models & all) != all) throw Error(CONAN_ERR_STATE, "conan_step_async needs all three models in the context");
-    if (s->ctx->cfg.voc_upsample == 2) throw Error(CONAN_ERR_UNSUPPORTED, "fused chunk steps carry vocoder state from chunk to chunk; upsample 'nn' (CausalUpsampleBlock1) looks ahead: "
-                                                                        "step the Emformer and decoder per chunk and run conan_hifigan_step over the mel prefix after a reset (inference/Conan.py:147-155)");
+    check_chunk_step(s, "conan_step_async");
     const int seg = s->ctx->cfg.emf_segment;
     if (emit < 1 || emit > seg) throw Error(CONAN_ERR_INVALID, "emit must be in [1, segment]");
     if (s->prof_on) throw Error(CONAN_ERR_STATE, "profiling is not available for pipelined steps");
@@ -647,121 +649,51 @@ void conan_streams::resample_init() {
   rs_slot.assign(max_slots, RsSlot());
 }
 
-// Waveform-in chunk steps (conan_step_wav / _async).  The host keeps each slot's position in its utterance; a call plans which
-// frames became complete (centred framing: frame f needs samples up to f * hop + n_fft / 2 - 1, or the final call: every frame of
-// 1 + samples / hop, zero padding past the end) and whether chunk t = chunks emitted so far is ready: frames [t * seg, t * seg +
-// seg + rc) complete, or - after the final call - any frame left (the short last chunks of engine.chunks: repeat-last padding).
-// One mel_stream_kernel launch (64 workgroups at 64 streams) computes the new frames, copies the chunk rows of earlier calls from the
-// mel ring and appends the samples to the audio ring (mel_stream_copy_kernel alone in drain calls that complete no frame); the chunk
-// then goes through the mel-in step.
-static void step_wav(conan_streams* s, const int32_t* slots, int n, int in_samples, int in_final, const float* wav_dev, const conan_mel_cfg* mel,
-                     int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream, bool pipelined) {
-  if (!s || !slots || !mel || !wav_out_dev || !emit_out || (in_samples > 0 && !wav_dev)) throw Error(CONAN_ERR_INVALID, "null argument");
-  *emit_out = 0;
-  const conan_cfg& c = s->ctx->cfg;
-  const int all = CONAN_MODEL_EMFORMER | CONAN_MODEL_CONAN | CONAN_MODEL_HIFIGAN;
-  if ((c.models & all) != all || !s->fe_audio) throw Error(CONAN_ERR_STATE, "conan_step_wav needs all three models in the context");
-  if (c.voc_upsample == 2) throw Error(CONAN_ERR_UNSUPPORTED, "fused chunk steps carry vocoder state from chunk to chunk; upsample 'nn' (CausalUpsampleBlock1) looks ahead");
-  const conan_mel_cfg& m = *mel;
-  if (m.framing != 0) throw Error(CONAN_ERR_INVALID, "conan_step_wav: only framing 0 (centred frames, zero padding) streams");
-  if (m.fft_size < 64 || (m.fft_size & (m.fft_size - 1)) || m.fft_size > 2048) throw Error(CONAN_ERR_INVALID, "conan_step_wav: fft_size must be a power of two in [64, 2048]");
-  if (m.hop_size != s->ctx->hop) throw Error(CONAN_ERR_INVALID, "conan_step_wav: hop_size must be the vocoder's hop (conan_hop_size)");
-  if (m.num_mels != c.emf_input_dim) throw Error(CONAN_ERR_INVALID, "conan_step_wav: num_mels must be the Emformer's input width");
-  if (m.natural_log != 0 && m.natural_log != 1) throw Error(CONAN_ERR_INVALID, "conan_step_wav: natural_log must be 0 (log10) or 1 (ln)");
+// The conan_mel_cfg of a wav-in call: centred frames at the vocoder's hop into the Emformer's input width.
+static void check_mel_stream(const conan_streams* s, const conan_mel_cfg& m, const std::string& who) {
+  if (m.framing != 0) throw Error(CONAN_ERR_INVALID, who + ": only framing 0 (centred frames, zero padding) streams");
+  if (m.fft_size < 64 || (m.fft_size & (m.fft_size - 1)) || m.fft_size > 2048) throw Error(CONAN_ERR_INVALID, who + ": fft_size must be a power of two in [64, 2048]");
+  if (m.hop_size != s->ctx->hop) throw Error(CONAN_ERR_INVALID, who + ": hop_size must be the vocoder's hop (conan_hop_size)");
+  if (m.num_mels != s->ctx->cfg.emf_input_dim) throw Error(CONAN_ERR_INVALID, who + ": num_mels must be the Emformer's input width");
+  if (m.natural_log != 0 && m.natural_log != 1) throw Error(CONAN_ERR_INVALID, who + ": natural_log must be 0 (log10) or 1 (ln)");
   if (m.win_length < 1 || m.win_length > m.fft_size || m.sample_rate < 1 || !(m.eps > 0.f) || !(m.mag_eps >= 0.f))
     throw Error(CONAN_ERR_INVALID, "mel front-end configuration");
-  if (n < 1 || n > s->max_slots) throw Error(CONAN_ERR_INVALID, "slot count out of range");
-  if (pipelined && s->prof_on) throw Error(CONAN_ERR_STATE, "profiling is not available for pipelined steps");
-  const int seg = c.emf_segment, rc = c.emf_right_context, hop = m.hop_size, N = m.fft_size, rows = seg + rc;
-  for (int i = 0; i < n; ++i) if (slots[i] < 0 || slots[i] >= s->max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
-  const conan_streams::FeSlot st0 = s->fe_slot[slots[0]];
-  for (int i = 1; i < n; ++i) {
-    const conan_streams::FeSlot& o = s->fe_slot[slots[i]];
-    if (o.recv != st0.recv || o.frames != st0.frames || o.chunks != st0.chunks || o.phase != st0.phase)
-      throw Error(CONAN_ERR_INVALID, "conan_step_wav: the slots of one call must be at the same position of their utterances");
-  }
-  // input resampler: the slots of a call share one configuration (or have none) and one position
-  const std::vector<int32_t> in_sm(n, in_samples), in_fin(n, in_final);
-  const RsPlan P = rs_plan(s, slots, n, in_sm.data(), in_fin.data(), wav_dev, in_samples, m, "conan_step_wav");
-  if (P.any) {
-    const conan_streams::RsSlot& r0 = s->rs_slot[slots[0]];
-    for (int i = 0; i < n; ++i) {
-      const conan_streams::RsSlot& r = s->rs_slot[slots[i]];
-      if (r.f != r0.f || r.in != r0.in || r.out != r0.out || r.phase != r0.phase)
-        throw Error(CONAN_ERR_INVALID, "conan_step_wav: the slots of one call must share one input rate configuration (conan_streams_set_input_rate) and position");
-    }
-  }
-  const int samples = P.mm[0], final_ = P.ff[0];      // what the front-end gets (model rate)
-  if (st0.phase == 2) throw Error(CONAN_ERR_INVALID, "conan_step_wav: the utterance has been drained; reset the slots with CONAN_MODEL_FRONTEND first");
-  if (st0.phase == 1 && (!final_ || samples != 0)) throw Error(CONAN_ERR_INVALID, "conan_step_wav: after the final call only samples = 0, final = 1 may follow");
-  if (!final_ && samples != seg * hop && !P.any) throw Error(CONAN_ERR_INVALID, "conan_step_wav: a non-final call takes exactly segment * hop samples per slot");
-  if (final_ && (samples < 0 || samples > seg * hop)) throw Error(CONAN_ERR_INVALID, "conan_step_wav: a final call takes 0 .. segment * hop samples per slot");
-  const long long R = st0.recv + samples;
-  if (final_ && R < 1) throw Error(CONAN_ERR_INVALID, "conan_step_wav: an utterance needs at least one sample");
-  // frames complete after this call, and the chunk (if any) it runs
-  const long long total_frames = final_ ? 1 + R / hop : -1;
-  const int fc = final_ ? (int)total_frames : (R >= N / 2 ? (int)((R - N / 2) / hop) + 1 : 0);
-  const int f0 = st0.frames, nnew = std::max(0, fc - f0), pos = st0.chunks * seg;
-  int emit = 0, real = 0;
+}
+
+// One slot's front-end plan for a wav-in call that gives it `samples` (model rate) and `final_`.  Centred framing: frame f needs the
+// samples up to f * hop + n_fft / 2 - 1, or the final call: every frame of 1 + samples / hop, zero padding past the end.  R = samples
+// received after the call, total = R once final (-1 before); frames [0, fc) complete, [f0, f0 + nnew) of them new in this call; chunk
+// t = chunks emitted so far starts at frame pos and is ready once frames [pos, pos + seg + rc) are complete or - after the final call -
+// any frame is left (emit frames, rows [0, real) backed by frames: the short last chunks of engine.chunks, repeat-last padding).
+struct FePlan { long long R, total; int fc, f0, nnew, pos, emit, real; };
+
+static FePlan fe_plan(const conan_streams* s, const conan_streams::FeSlot& o, int samples, int final_, int n_fft, const std::string& who) {
+  const int seg = s->ctx->cfg.emf_segment, rc = s->ctx->cfg.emf_right_context, hop = s->ctx->hop, N = n_fft;
+  FePlan p;
+  p.R = o.recv + samples;
+  p.total = final_ ? p.R : -1;
+  p.fc = final_ ? (int)(1 + p.R / hop) : (p.R >= N / 2 ? (int)((p.R - N / 2) / hop) + 1 : 0);
+  p.f0 = o.frames; p.nnew = std::max(0, p.fc - p.f0); p.pos = o.chunks * seg;
+  p.emit = 0; p.real = 0;
   if (final_) {
-    if (pos < fc) { emit = std::min(seg, fc - pos); real = emit + std::min(rc, fc - pos - emit); }
-  } else if (pos + rows <= fc) {
-    emit = seg; real = rows;
+    if (p.pos < p.fc) { p.emit = std::min(seg, p.fc - p.pos); p.real = p.emit + std::min(rc, p.fc - p.pos - p.emit); }
+  } else if (p.pos + seg + rc <= p.fc) {
+    p.emit = seg; p.real = seg + rc;
   }
   // ring spans: the samples a new frame reads and the samples appended; the frames a chunk row reads and the frames written
-  const long long a_lo = std::min<long long>(st0.recv, (long long)f0 * hop - N / 2);
-  if (R - std::max(0ll, a_lo) > s->fe_LA || fc - std::min(pos, f0) > s->fe_LM)
-    throw Error(CONAN_ERR_UNSUPPORTED, "conan_step_wav: front-end rings too small for this configuration");
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  const bool run = nnew > 0 || samples > 0 || emit > 0;
-  std::function<void(hipStream_t)> front;
-  if (run) {
-    const std::string k = s->ctx->mel_tables(m);
-    const float* rg = s->ctx->vec(k + ".range");
-    cnk::MelStreamArgs a;
-    a.wav = P.launch ? s->rs_wav[s->rs_calls % conan_streams::NS] : wav_dev;     // (rs_front takes set rs_calls % NS below)
-    a.aring = s->fe_audio; a.mring = s->fe_mel; a.chunk = s->fe_chunk; a.slots = s->d_slots;
-    a.win = s->ctx->vec(k + ".win"); a.tw = reinterpret_cast<const double2*>(s->ctx->vec(k + ".tw")); a.fb = s->ctx->vec(k + ".fb");
-    a.lo = reinterpret_cast<const int*>(rg); a.hi = reinterpret_cast<const int*>(rg) + m.num_mels;
-    a.r_prev = st0.recv; a.total = final_ ? R : -1;
-    a.m = samples; a.n = n; a.f0 = f0; a.nnew = nnew; a.pos = pos; a.rows = emit > 0 ? rows : 0; a.real = real;
-    a.LA = s->fe_LA; a.LM = s->fe_LM; a.nm = m.num_mels; a.n_fft = N; a.hop = hop; a.nb = N / 2 + 1; a.cmag = (N / 2 + 1 + 3) & ~3;
-    a.eps = m.eps; a.vmin = m.vmin; a.vmax = m.vmax; a.mag_eps = m.mag_eps; a.natural_log = m.natural_log;
-    const double flops = 4.0 * n * nnew * (double)(N / 2 + 1) * N;
-    front = [s, a, flops](hipStream_t st) {
-      if (a.nnew > 0) s->profiled("mel_stream_kernel", flops, st, [&] { cnk::launch_mel_stream(a, st); });
-      else s->profiled("mel_stream_copy_kernel", 0.0, st, [&] { cnk::launch_mel_stream_copy(a, st); });
-    };
-  }
-  if (P.launch) front = rs_front(s, P, n, wav_dev, in_samples, samples, front, (hipStream_t)stream);
-  if (pipelined && emit > 0) {
-    step_pipelined(s, slots, n, emit, s->fe_chunk, codes_dev, mel_out_dev, wav_out_dev, stream, front);
-  } else {
-    hipStream_t st = (hipStream_t)stream;
-    s->join(st);
-    s->set_slots(slots, n, st);
-    if (front) front(st);
-    if (emit > 0) step_blocking(s, n, emit, s->fe_chunk, codes_dev, mel_out_dev, wav_out_dev, st);
-  }
+  const long long a_lo = std::min<long long>(o.recv, (long long)p.f0 * hop - N / 2);
+  if (p.R - std::max(0ll, a_lo) > s->fe_LA || p.fc - std::min(p.pos, p.f0) > s->fe_LM)
+    throw Error(CONAN_ERR_UNSUPPORTED, who + ": front-end rings too small for this configuration");
+  return p;
+}
+
+static void fe_commit(conan_streams* s, const int32_t* slots, int n, const std::vector<FePlan>& pl, const int32_t* final_) {
   for (int i = 0; i < n; ++i) {
     conan_streams::FeSlot& o = s->fe_slot[slots[i]];
-    o.recv = R; o.frames = std::max(f0, fc); o.chunks += emit > 0 ? 1 : 0;
-    o.phase = final_ ? (emit > 0 ? 1 : 2) : 0;
+    const FePlan& p = pl[i];
+    o.recv = p.R; o.frames = std::max(p.f0, p.fc); o.chunks += p.emit > 0 ? 1 : 0;
+    o.phase = final_[i] ? (p.emit > 0 ? 1 : 2) : 0;
   }
-  rs_commit(s, slots, n, P, in_fin.data());
-  s->fe_last_n = n;
-  s->fe_last_ragged = false;
-  *emit_out = emit;
-}
-
-int conan_step_wav(conan_streams* s, const int32_t* slots, int n, int samples, int final, const float* wav_dev, const conan_mel_cfg* mel,
-                   int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream) {
-  return guarded([&] { step_wav(s, slots, n, samples, final, wav_dev, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false); });
-}
-
-int conan_step_wav_async(conan_streams* s, const int32_t* slots, int n, int samples, int final, const float* wav_dev, const conan_mel_cfg* mel,
-                         int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream) {
-  return guarded([&] { step_wav(s, slots, n, samples, final, wav_dev, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true); });
 }
 
 void conan_streams::ragged_init() {
@@ -779,30 +711,29 @@ void conan_streams::ragged_init() {
   fe_pin.init((size_t)max_slots * cnk::kRaggedWords);
 }
 
-// Waveform-in chunk steps for slots at different positions of their utterances (conan_step_wav_ragged / _async).  Each slot gets
-// step_wav's plan from its own FeSlot; the emitting slots are grouped by emit and each group runs one mel-in chunk step (blocking or
-// pipelined) on its own slot list.  One mel_stream_ragged_kernel launch, in front of the first group's Emformer, does the front-end
-// work of every slot of the call, driven by a [n][kRaggedWords] row table; it writes each group's chunk contiguously into fe_chunk.
-// A call whose slots all emit a full chunk is one group in call order and writes the caller's buffers directly; otherwise the groups
-// write staging (set q of NS) and wav_rows_scatter_kernel puts the rows in call order.
-static void step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const int32_t* in_samples, const int32_t* in_final, const float* wav_dev,
-                            long long wav_ld, const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out,
-                            void* stream, bool pipelined) {
+// Waveform-in chunk steps (conan_step_wav[_async], conan_step_wav_ragged[_ld][_async]).  The host keeps each slot's position in its
+// utterance (FeSlot); every slot gets its own plan (fe_plan), and the emitting slots are grouped by emit, each group running one
+// mel-in chunk step (blocking or pipelined) on its own slot list.  One front-end launch, in front of the first group's Emformer, does
+// the front-end work of every slot of the call: the new frames, the chunk rows of earlier calls from the mel ring, the samples
+// appended to the audio ring.
+// `common` is conan_step_wav's contract: every slot at the same position with the same input-rate configuration, so the call has at
+// most one group, in call order, and the outputs are rows of emit frames ([n][emit]) written in place.  Its front-end is
+// mel_stream_kernel on the call's one plan (mel_stream_copy_kernel in calls that complete no frame), the same-position kernel: at 64
+// streams a pipelined step is ~10 % slower with the row-table kernel below (1.548 against 1.402 ms per step).
+// Otherwise (ragged calls) mel_stream_ragged_kernel is driven by a [n][kRaggedWords] row table and writes each group's chunk
+// contiguously into fe_chunk; the outputs are rows of a full chunk ([n][seg]).  A call whose slots all emit a full chunk is one group
+// in call order and writes the caller's buffers directly; the groups of any other call write staging (set q of NS) and
+// wav_rows_scatter_kernel puts the rows in call order.
+static void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, int n, const int32_t* in_samples, const int32_t* in_final,
+                     const float* wav_dev, long long wav_ld, const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev,
+                     int32_t* emit_out, void* stream, bool pipelined, bool common) {
   if (!s || !slots || !in_samples || !in_final || !mel || !wav_out_dev || !emit_out) throw Error(CONAN_ERR_INVALID, "null argument");
-  const conan_cfg& c = s->ctx->cfg;
-  const int all = CONAN_MODEL_EMFORMER | CONAN_MODEL_CONAN | CONAN_MODEL_HIFIGAN;
-  if ((c.models & all) != all || !s->fe_audio) throw Error(CONAN_ERR_STATE, "conan_step_wav_ragged needs all three models in the context");
-  if (c.voc_upsample == 2) throw Error(CONAN_ERR_UNSUPPORTED, "fused chunk steps carry vocoder state from chunk to chunk; upsample 'nn' (CausalUpsampleBlock1) looks ahead");
+  check_chunk_step(s, who.c_str());
   const conan_mel_cfg& m = *mel;
-  if (m.framing != 0) throw Error(CONAN_ERR_INVALID, "conan_step_wav_ragged: only framing 0 (centred frames, zero padding) streams");
-  if (m.fft_size < 64 || (m.fft_size & (m.fft_size - 1)) || m.fft_size > 2048) throw Error(CONAN_ERR_INVALID, "conan_step_wav_ragged: fft_size must be a power of two in [64, 2048]");
-  if (m.hop_size != s->ctx->hop) throw Error(CONAN_ERR_INVALID, "conan_step_wav_ragged: hop_size must be the vocoder's hop (conan_hop_size)");
-  if (m.num_mels != c.emf_input_dim) throw Error(CONAN_ERR_INVALID, "conan_step_wav_ragged: num_mels must be the Emformer's input width");
-  if (m.natural_log != 0 && m.natural_log != 1) throw Error(CONAN_ERR_INVALID, "conan_step_wav_ragged: natural_log must be 0 (log10) or 1 (ln)");
-  if (m.win_length < 1 || m.win_length > m.fft_size || m.sample_rate < 1 || !(m.eps > 0.f) || !(m.mag_eps >= 0.f))
-    throw Error(CONAN_ERR_INVALID, "mel front-end configuration");
+  check_mel_stream(s, m, who);
   if (n < 1 || n > s->max_slots) throw Error(CONAN_ERR_INVALID, "slot count out of range");
   if (pipelined && s->prof_on) throw Error(CONAN_ERR_STATE, "profiling is not available for pipelined steps");
+  const conan_cfg& c = s->ctx->cfg;
   const int seg = c.emf_segment, rc = c.emf_right_context, hop = m.hop_size, N = m.fft_size, rows = seg + rc;
   std::vector<char> seen(s->max_slots, 0);
   for (int i = 0; i < n; ++i) {
@@ -810,20 +741,32 @@ static void step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const
     if (seen[slots[i]]) throw Error(CONAN_ERR_INVALID, "duplicate slot");
     seen[slots[i]] = 1;
   }
-  if (wav_ld < 0 || wav_ld > INT_MAX) throw Error(CONAN_ERR_INVALID, "conan_step_wav_ragged: wav_ld out of range");
+  if (wav_ld < 0 || wav_ld > INT_MAX) throw Error(CONAN_ERR_INVALID, who + ": wav_ld out of range");
+  if (common) {
+    const conan_streams::FeSlot& o0 = s->fe_slot[slots[0]];
+    for (int i = 1; i < n; ++i) {
+      const conan_streams::FeSlot& o = s->fe_slot[slots[i]];
+      if (o.recv != o0.recv || o.frames != o0.frames || o.chunks != o0.chunks || o.phase != o0.phase)
+        throw Error(CONAN_ERR_INVALID, who + ": the slots of one call must be at the same position of their utterances");
+    }
+    for (int i = 1; i < n && !s->rs_slot.empty(); ++i) {
+      const conan_streams::RsSlot &r0 = s->rs_slot[slots[0]], &r = s->rs_slot[slots[i]];
+      if (r.f != r0.f || (r.f && (r.in != r0.in || r.out != r0.out || r.phase != r0.phase)))
+        throw Error(CONAN_ERR_INVALID, who + ": the slots of one call must share one input rate configuration (conan_streams_set_input_rate) and position");
+    }
+  }
   // the input resampler's rows first: what each slot's front-end gets this call
-  const RsPlan P = rs_plan(s, slots, n, in_samples, in_final, wav_dev, wav_ld, m, "conan_step_wav_ragged");
+  const RsPlan P = rs_plan(s, slots, n, in_samples, in_final, wav_dev, wav_ld, m, who.c_str());
   const int32_t* samples = P.mm.data();
   const int32_t* final_ = P.ff.data();
-  // every slot's plan first (step_wav's, from the slot's own position): nothing changes before all of them have passed
-  struct Plan { long long R, total; int fc, f0, nnew, pos, emit, real; };
-  std::vector<Plan> pl(n);
+  // every slot's plan first: nothing changes before all of them have passed
+  std::vector<FePlan> pl(n);
   bool run = false;
   for (int i = 0; i < n; ++i) {
     const conan_streams::FeSlot& o = s->fe_slot[slots[i]];
     const int sm = samples[i], fin = final_[i];
     auto bad = [&](const char* what) {
-      throw Error(CONAN_ERR_INVALID, std::string("conan_step_wav_ragged: slot ") + std::to_string(slots[i]) + " (call row " + std::to_string(i) + "): " + what);
+      throw Error(CONAN_ERR_INVALID, who + ": slot " + std::to_string(slots[i]) + " (call row " + std::to_string(i) + "): " + what);
     };
     if (fin != 0 && fin != 1) bad("final must be 0 or 1");
     if (o.phase == 2) bad("the utterance has been drained; reset the slot with CONAN_MODEL_FRONTEND first");
@@ -831,23 +774,10 @@ static void step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const
     if (!fin && sm != seg * hop && !P.rate[i]) bad("a non-final call takes exactly segment * hop samples per slot");
     if (fin && (sm < 0 || sm > seg * hop)) bad("a final call takes 0 .. segment * hop samples per slot");
     if (sm > wav_ld && !P.rate[i]) bad("the row holds more samples than the row stride of wav_dev");
-    if (sm > 0 && !wav_dev) throw Error(CONAN_ERR_INVALID, "null argument (wav_dev with samples > 0)");
-    Plan& p = pl[i];
-    p.R = o.recv + sm;
-    if (fin && p.R < 1) bad("an utterance needs at least one sample");
-    p.total = fin ? p.R : -1;
-    p.fc = fin ? (int)(1 + p.R / hop) : (p.R >= N / 2 ? (int)((p.R - N / 2) / hop) + 1 : 0);
-    p.f0 = o.frames; p.nnew = std::max(0, p.fc - p.f0); p.pos = o.chunks * seg;
-    p.emit = 0; p.real = 0;
-    if (fin) {
-      if (p.pos < p.fc) { p.emit = std::min(seg, p.fc - p.pos); p.real = p.emit + std::min(rc, p.fc - p.pos - p.emit); }
-    } else if (p.pos + rows <= p.fc) {
-      p.emit = seg; p.real = rows;
-    }
-    const long long a_lo = std::min<long long>(o.recv, (long long)p.f0 * hop - N / 2);
-    if (p.R - std::max(0ll, a_lo) > s->fe_LA || p.fc - std::min(p.pos, p.f0) > s->fe_LM)
-      throw Error(CONAN_ERR_UNSUPPORTED, "conan_step_wav_ragged: front-end rings too small for this configuration");
-    run = run || p.nnew > 0 || sm > 0 || p.emit > 0;
+    if (in_samples[i] > 0 && !wav_dev) throw Error(CONAN_ERR_INVALID, "null argument (wav_dev with samples > 0)");
+    if (fin && o.recv + sm < 1) bad("an utterance needs at least one sample");
+    pl[i] = fe_plan(s, o, sm, fin, N, who);
+    run = run || pl[i].nnew > 0 || sm > 0 || pl[i].emit > 0;
   }
   // emit groups, largest emit first; a group's rows keep call order
   std::vector<std::vector<int>> groups;      // call rows per group
@@ -856,51 +786,74 @@ static void step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const
     for (int i = 0; i < n; ++i) if (pl[i].emit == e) g.push_back(i);
     if (!g.empty()) groups.push_back(std::move(g));
   }
-  const bool direct = groups.size() == 1 && (int)groups[0].size() == n && pl[0].emit == seg;
+  const bool direct = common || (groups.size() == 1 && (int)groups[0].size() == n && pl[0].emit == seg);
+  const bool scatter = !direct && !groups.empty();
   const int nm_in = m.num_mels, nm = c.num_mels;
-  std::vector<int> tab((size_t)n * cnk::kRaggedWords, 0);
   int jobs = 0;
-  for (int i = 0; i < n; ++i) {
-    const Plan& p = pl[i];
-    int* d = &tab[(size_t)i * cnk::kRaggedWords];
-    const long long r_prev = s->fe_slot[slots[i]].recv;
-    d[cnk::kRgSlot] = slots[i];
-    d[cnk::kRgRecvLo] = (int)(uint32_t)r_prev; d[cnk::kRgRecvHi] = (int)(r_prev >> 32);
-    d[cnk::kRgTotalLo] = (int)(uint32_t)p.total; d[cnk::kRgTotalHi] = (int)(p.total >> 32);
-    d[cnk::kRgM] = samples[i]; d[cnk::kRgF0] = p.f0; d[cnk::kRgNnew] = p.nnew; d[cnk::kRgPos] = p.pos;
-    d[cnk::kRgRows] = p.emit > 0 ? rows : 0; d[cnk::kRgReal] = p.real; d[cnk::kRgEmit] = p.emit;
-    d[cnk::kRgJob] = jobs;
-    jobs += p.nnew;
-  }
-  for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g)
-    for (int k = 0; k < (int)groups[g].size(); ++k) {
-      int* d = &tab[(size_t)groups[g][k] * cnk::kRaggedWords];
-      d[cnk::kRgChunk] = off + k; d[cnk::kRgGroup] = off; d[cnk::kRgIndex] = k;
+  std::vector<int> tab;
+  if (!common) {
+    tab.assign((size_t)n * cnk::kRaggedWords, 0);
+    for (int i = 0; i < n; ++i) {
+      const FePlan& p = pl[i];
+      int* d = &tab[(size_t)i * cnk::kRaggedWords];
+      const long long r_prev = s->fe_slot[slots[i]].recv;
+      d[cnk::kRgSlot] = slots[i];
+      d[cnk::kRgRecvLo] = (int)(uint32_t)r_prev; d[cnk::kRgRecvHi] = (int)(r_prev >> 32);
+      d[cnk::kRgTotalLo] = (int)(uint32_t)p.total; d[cnk::kRgTotalHi] = (int)(p.total >> 32);
+      d[cnk::kRgM] = samples[i]; d[cnk::kRgF0] = p.f0; d[cnk::kRgNnew] = p.nnew; d[cnk::kRgPos] = p.pos;
+      d[cnk::kRgRows] = p.emit > 0 ? rows : 0; d[cnk::kRgReal] = p.real; d[cnk::kRgEmit] = p.emit;
+      d[cnk::kRgJob] = jobs;
+      jobs += p.nnew;
     }
+    for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g)
+      for (int k = 0; k < (int)groups[g].size(); ++k) {
+        int* d = &tab[(size_t)groups[g][k] * cnk::kRaggedWords];
+        d[cnk::kRgChunk] = off + k; d[cnk::kRgGroup] = off; d[cnk::kRgIndex] = k;
+      }
+  }
   HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  s->ragged_init();
-  const int q = (int)(s->rg_calls % conan_streams::NS);
   hipStream_t cst = (hipStream_t)stream;
   if (!pipelined || groups.empty()) s->join(cst);
-  // the row table of set q: the call that used it last has finished reading it (and its staging)
-  HIP_CHECK(hipStreamWaitEvent(cst, s->ev_stage[q], 0));
-  s->fe_pin.upload(s->rg_tab[q], tab.data(), tab.size(), cst);
+  const int q = (int)(s->rg_calls % conan_streams::NS);
+  if (!common) {
+    s->ragged_init();
+    // the row table of set q: the call that used it last has finished reading it (and its staging)
+    HIP_CHECK(hipStreamWaitEvent(cst, s->ev_stage[q], 0));
+    s->fe_pin.upload(s->rg_tab[q], tab.data(), tab.size(), cst);
+  }
   std::function<void(hipStream_t)> front;
   if (run) {
     const std::string k = s->ctx->mel_tables(m);
     const float* rg = s->ctx->vec(k + ".range");
-    cnk::MelRaggedArgs a;
-    a.wav = P.launch ? s->rs_wav[s->rs_calls % conan_streams::NS] : wav_dev;     // (rs_front takes set rs_calls % NS below)
-    a.aring = s->fe_audio; a.mring = s->fe_mel; a.chunk = s->fe_chunk; a.tab = s->rg_tab[q];
-    a.win = s->ctx->vec(k + ".win"); a.tw = reinterpret_cast<const double2*>(s->ctx->vec(k + ".tw")); a.fb = s->ctx->vec(k + ".fb");
-    a.lo = reinterpret_cast<const int*>(rg); a.hi = reinterpret_cast<const int*>(rg) + m.num_mels;
-    a.n = n; a.jobs = jobs; a.wstride = P.launch ? seg * hop : (int)wav_ld;
-    a.LA = s->fe_LA; a.LM = s->fe_LM; a.nm = nm_in; a.n_fft = N; a.hop = hop; a.nb = N / 2 + 1; a.cmag = (N / 2 + 1 + 3) & ~3;
-    a.eps = m.eps; a.vmin = m.vmin; a.vmax = m.vmax; a.mag_eps = m.mag_eps; a.natural_log = m.natural_log;
-    const double flops = 4.0 * jobs * (double)(N / 2 + 1) * N;
-    front = [s, a, flops](hipStream_t st) { s->profiled("mel_stream_ragged_kernel", flops, st, [&] { cnk::launch_mel_ragged(a, st); }); };
+    const float* wav = P.launch ? s->rs_wav[s->rs_calls % conan_streams::NS] : wav_dev;     // (rs_front takes set rs_calls % NS below)
+    auto fill = [&](auto& a) {      // the fields both front-end kernels share
+      a.wav = wav; a.aring = s->fe_audio; a.mring = s->fe_mel; a.chunk = s->fe_chunk; a.n = n;
+      a.win = s->ctx->vec(k + ".win"); a.tw = reinterpret_cast<const double2*>(s->ctx->vec(k + ".tw")); a.fb = s->ctx->vec(k + ".fb");
+      a.lo = reinterpret_cast<const int*>(rg); a.hi = reinterpret_cast<const int*>(rg) + m.num_mels;
+      a.LA = s->fe_LA; a.LM = s->fe_LM; a.nm = nm_in; a.n_fft = N; a.hop = hop; a.nb = N / 2 + 1; a.cmag = (N / 2 + 1 + 3) & ~3;
+      a.eps = m.eps; a.vmin = m.vmin; a.vmax = m.vmax; a.mag_eps = m.mag_eps; a.natural_log = m.natural_log;
+    };
+    if (common) {
+      const FePlan& p = pl[0];
+      cnk::MelStreamArgs a;
+      fill(a);
+      a.slots = s->d_slots; a.r_prev = s->fe_slot[slots[0]].recv; a.total = p.total;
+      a.m = samples[0]; a.f0 = p.f0; a.nnew = p.nnew; a.pos = p.pos; a.rows = p.emit > 0 ? rows : 0; a.real = p.real;
+      const double flops = 4.0 * n * p.nnew * (double)(N / 2 + 1) * N;
+      front = [s, a, flops](hipStream_t st) {
+        if (a.nnew > 0) s->profiled("mel_stream_kernel", flops, st, [&] { cnk::launch_mel_stream(a, st); });
+        else s->profiled("mel_stream_copy_kernel", 0.0, st, [&] { cnk::launch_mel_stream_copy(a, st); });
+      };
+    } else {
+      cnk::MelRaggedArgs a;
+      fill(a);
+      a.tab = s->rg_tab[q]; a.jobs = jobs; a.wstride = P.launch ? seg * hop : (int)wav_ld;
+      const double flops = 4.0 * jobs * (double)(N / 2 + 1) * N;
+      front = [s, a, flops](hipStream_t st) { s->profiled("mel_stream_ragged_kernel", flops, st, [&] { cnk::launch_mel_ragged(a, st); }); };
+    }
   }
-  if (P.launch) front = rs_front(s, P, n, wav_dev, wav_ld, seg * hop, front, cst);
+  // (the same-position kernel reads the resampler's rows [n][samples], the ragged one [n][seg * hop])
+  if (P.launch) front = rs_front(s, P, n, wav_dev, wav_ld, common ? samples[0] : seg * hop, front, cst);
   cnk::WavScatterArgs sc;
   sc.tab = s->rg_tab[q]; sc.n = n; sc.seg = seg; sc.nm = nm; sc.hop = hop;
   sc.codes_src = s->rg_codes[q]; sc.mel_src = s->rg_mel[q]; sc.wav_src = s->rg_wav[q];
@@ -922,53 +875,72 @@ static void step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const
   };
   if (pipelined && !groups.empty()) {
     for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g) group_step(g, off, cst);
-    if (!direct) {
+    if (scatter) {
       cnk::launch_wav_scatter(sc, s->st_voc);
       // join() waits for the last step's vocoder event: it now covers the scatter too
       HIP_CHECK(hipEventRecord(s->ev_voc[(s->async_steps - 1) % conan_streams::NP], s->st_voc));
     }
-    HIP_CHECK(hipEventRecord(s->ev_stage[q], s->st_voc));
+    if (!common) HIP_CHECK(hipEventRecord(s->ev_stage[q], s->st_voc));
   } else {
+    if (common) s->set_slots(slots, n, cst);      // (mel_stream_kernel reads the slot table)
     if (front) front(cst);
     for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g) group_step(g, off, cst);
-    if (!direct && !groups.empty()) s->profiled("wav_rows_scatter_kernel", 0.0, cst, [&] { cnk::launch_wav_scatter(sc, cst); });
-    HIP_CHECK(hipEventRecord(s->ev_stage[q], cst));
+    if (scatter) s->profiled("wav_rows_scatter_kernel", 0.0, cst, [&] { cnk::launch_wav_scatter(sc, cst); });
+    if (!common) HIP_CHECK(hipEventRecord(s->ev_stage[q], cst));
   }
-  for (int i = 0; i < n; ++i) {
-    conan_streams::FeSlot& o = s->fe_slot[slots[i]];
-    const Plan& p = pl[i];
-    o.recv = p.R; o.frames = std::max(p.f0, p.fc); o.chunks += p.emit > 0 ? 1 : 0;
-    o.phase = final_[i] ? (p.emit > 0 ? 1 : 2) : 0;
-    emit_out[i] = p.emit;
-  }
+  fe_commit(s, slots, n, pl, final_);
+  for (int i = 0; i < n; ++i) emit_out[i] = pl[i].emit;
   rs_commit(s, slots, n, P, in_final);
   s->fe_last_n = n;
-  s->fe_last_ragged = true;
-  s->rg_calls++;
+  s->fe_last_ragged = !common;
+  if (!common) s->rg_calls++;
+}
+
+// conan_step_wav[_async]: `samples` and `final` for every slot, rows of `samples` samples in wav_dev; *emit_out = the common emit
+static void step_wav_common(conan_streams* s, const int32_t* slots, int n, int samples, int final, const float* wav_dev, const conan_mel_cfg* mel,
+                            int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream, bool pipelined) {
+  if (!s || !emit_out) throw Error(CONAN_ERR_INVALID, "null argument");
+  *emit_out = 0;
+  const size_t rows = std::clamp(n, 1, s->max_slots);      // (step_wav checks n)
+  const std::vector<int32_t> sm(rows, samples), fin(rows, final != 0);
+  std::vector<int32_t> emit(rows, 0);
+  step_wav(s, "conan_step_wav", slots, n, sm.data(), fin.data(), wav_dev, std::max(samples, 0), mel, codes_dev, mel_out_dev, wav_out_dev,
+           emit.data(), stream, pipelined, true);
+  *emit_out = emit[0];
+}
+
+int conan_step_wav(conan_streams* s, const int32_t* slots, int n, int samples, int final, const float* wav_dev, const conan_mel_cfg* mel,
+                   int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream) {
+  return guarded([&] { step_wav_common(s, slots, n, samples, final, wav_dev, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false); });
+}
+
+int conan_step_wav_async(conan_streams* s, const int32_t* slots, int n, int samples, int final, const float* wav_dev, const conan_mel_cfg* mel,
+                         int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream) {
+  return guarded([&] { step_wav_common(s, slots, n, samples, final, wav_dev, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true); });
 }
 
 static long long ragged_ld(const conan_streams* s) { return s ? (long long)s->ctx->cfg.emf_segment * s->ctx->hop : 0; }
 
 int conan_step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final, const float* wav_dev,
                           const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream) {
-  return guarded([&] { step_wav_ragged(s, slots, n, samples, final, wav_dev, ragged_ld(s), mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false); });
+  return guarded([&] { step_wav(s, "conan_step_wav_ragged", slots, n, samples, final, wav_dev, ragged_ld(s), mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false, false); });
 }
 
 int conan_step_wav_ragged_async(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final, const float* wav_dev,
                                 const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream) {
-  return guarded([&] { step_wav_ragged(s, slots, n, samples, final, wav_dev, ragged_ld(s), mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true); });
+  return guarded([&] { step_wav(s, "conan_step_wav_ragged", slots, n, samples, final, wav_dev, ragged_ld(s), mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true, false); });
 }
 
 int conan_step_wav_ragged_ld(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final, const float* wav_dev,
                              int64_t wav_ld, const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev,
                              int32_t* emit_out, void* stream) {
-  return guarded([&] { step_wav_ragged(s, slots, n, samples, final, wav_dev, wav_ld, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false); });
+  return guarded([&] { step_wav(s, "conan_step_wav_ragged", slots, n, samples, final, wav_dev, wav_ld, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false, false); });
 }
 
 int conan_step_wav_ragged_ld_async(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final,
                                    const float* wav_dev, int64_t wav_ld, const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev,
                                    float* wav_out_dev, int32_t* emit_out, void* stream) {
-  return guarded([&] { step_wav_ragged(s, slots, n, samples, final, wav_dev, wav_ld, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true); });
+  return guarded([&] { step_wav(s, "conan_step_wav_ragged", slots, n, samples, final, wav_dev, wav_ld, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true, false); });
 }
 
 int conan_resample(conan_ctx* ctx, const conan_resample_cfg* cfg, const float* x_dev, int n, int64_t samples, float* y_dev, int64_t* out_samples,
