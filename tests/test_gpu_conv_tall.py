@@ -17,6 +17,7 @@ import torch
 from conan_amd import _lib, configs, synth
 from tests.conftest import kernels_of, load_golden
 from tests.test_gpu_arith import _fold
+from tests.vocoder_ref import ref_upsampler, ring_rows, slot_errors, steps_to_wrap_twice  # noqa: F401  (the float64 helpers, shared with test_gpu_vocoder_f64.py)
 
 gpu = pytest.mark.gpu
 
@@ -48,38 +49,6 @@ def tall_launches(n, frames, num_cu, plan_n=0, max_t=32):
     return count
 
 
-def ref_upsampler(x, w, b, r, dil=1):
-    """What one causal pixel-shuffle upsampler (hifigan_causal.py:191-212) writes, in float64: x [n, rows, Cin] is the tensor it
-    read over consecutive steps from a slot's reset on ((k - 1) x dil rows of zero history in front), w [Cout, Cin, k] the folded
-    weight, b [Cout] -> [n, rows x r, Cout / r].  im2col of the causal window times the weight matrix (torch.matmul, on x's device),
-    then oracle.hifigan.pixel_shuffle_1d; done in slot chunks that keep the im2col matrix below 2^25 elements."""
-    from oracle import hifigan as ohifi
-    n, rows, cin = x.shape
-    cout, _, k = w.shape
-    x, w, b = x.double(), w.to(x.device, torch.float64), b.to(x.device, torch.float64)
-    wm = w.permute(2, 1, 0).reshape(k * cin, cout)                      # [(tap, channel), Cout]
-    out = []
-    step = max(1, (1 << 25) // (rows * k * cin))
-    for s in range(0, n, step):
-        xp = torch.nn.functional.pad(x[s:s + step], (0, 0, (k - 1) * dil, 0))
-        cols = torch.stack([xp[:, j * dil:j * dil + rows] for j in range(k)], 2).reshape(-1, rows, k * cin)
-        y = torch.matmul(cols, wm) + b                                  # [n, rows, Cout]
-        out.append(ohifi.pixel_shuffle_1d(y.transpose(1, 2), r).transpose(1, 2))
-    return torch.cat(out)
-
-
-def slot_errors(got, want):
-    """Per slot of got [n, rows, C] (fp32) against want (float64): relative rms error, largest |error| / the slot's rms of that
-    channel, and whether got is finite."""
-    got = got.to(want.device)
-    e = got.double() - want
-    rms = e.pow(2).sum((1, 2)).sqrt() / want.pow(2).sum((1, 2)).sqrt()
-    crms = want.pow(2).mean(1, keepdim=True).sqrt().clamp_min(1e-300)
-    mx = (e.abs() / crms).amax((1, 2))
-    fin = torch.isfinite(got).flatten(1).all(1)
-    return rms.cpu(), mx.cpu(), fin.cpu()
-
-
 def test_ref_upsampler_matches_the_oracle_streamed():
     """The float64 helper against oracle.hifigan._cconv + pixel_shuffle_1d (pinned to the reference goldens by
     test_oracle_golden.py), two streaming steps concatenated (the oracle carries its causal history between them), at an ups.1-like
@@ -108,20 +77,6 @@ def test_ref_upsampler_matches_the_oracle_streamed():
 
 
 # ------------------------------------------------------------------------------------------------------------ the sweep
-def ring_rows(hist, rate, max_frames):
-    """Rows of a vocoder ring (streams.h mk_ring): next_pow2(hist + max_frames x rate)."""
-    return 1 << (hist + max_frames * rate - 1).bit_length()
-
-
-def steps_to_wrap_twice(frames, max_frames):
-    """Steps of `frames` frames after which every input ring of ups.0 / ups.1 has wrapped at least twice (at least 12): ups.0 reads
-    conv_pre's ring (15 rows of history, rate 1), ups.1 stage 0's branch mean (9 rows, rate 8)."""
-    need = 12
-    for hist, rate in ((15, 1), (9, 8)):
-        need = max(need, math.ceil(2 * ring_rows(hist, rate, max_frames) / (frames * rate)))
-    return need
-
-
 def _uniform(n, frames, max_frames=4):
     return {"slots": n, "max_frames": max_frames, "steps": [(list(range(n)), frames, [])] * steps_to_wrap_twice(frames, max_frames)}
 

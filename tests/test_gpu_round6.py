@@ -70,6 +70,60 @@ def test_fixed_plan_stream_bits_do_not_depend_on_the_active_slots(arith):
     ctx.close()
 
 
+@pytest.mark.parametrize("arith", ARITHS)
+def test_fixed_plan_stream_bits_do_not_depend_on_the_active_slots_pipelined(arith):
+    """The same promise through PIPELINED steps (conan_step_async), which have plan inputs of their own: the Emformer shape of an idle
+    pipeline, the CUs the vocoder's persistent launches leave to the front end, the single-tile decoder launch's LDS size.  Slot 41 of
+    a 64-slot fixed-plan stream-set with 64, 20 and 1 active slots, 12 steps, a join() + device synchronisation after steps 2, 3, 7
+    and 10 so that steps start on an idle pipeline as well as behind a step in flight: codes, mel and audio bit-identical across the
+    three active sets and to the blocking run of the same steps."""
+    ctx, chp, _ = _ctx()
+    S, K, steps = 64, 41, 12
+    src = torch.from_numpy(synth.mel(4 * steps + 2, 1234, S)).cuda()
+    ref = torch.from_numpy(synth.mel(40, 4321, S)).cuda()
+    lens = [40 - (i % 5) for i in range(S)]
+    actives = [list(range(S)), [K] + [i for i in range(0, 57, 3)], [K]]
+    joins = (2, 3, 7, 10)
+
+    def run(act, pipelined):
+        st = ctx.streams(S, max_frames=4, max_ref_frames=64, arith=arith, flags=_lib.STREAMS_FIXED_PLAN)
+        st.reset(act)
+        idx = torch.tensor(act, device="cuda")
+        st.set_reference(act, ref[idx].contiguous(), [lens[i] for i in act])
+        k, n = act.index(K), len(act)
+        outs = []
+        for t in range(steps):
+            chunk = src[idx, 4 * t:4 * t + 6].contiguous()
+            if pipelined:
+                cc = torch.empty(n, st.seg, dtype=torch.int32, device="cuda")
+                mm = torch.empty(n, st.seg, ctx.cfg.num_mels, device="cuda")
+                ww = torch.empty(n, st.seg * ctx.hop, device="cuda")
+                st.step_async(act, chunk, ww, codes=cc, mel_out=mm)
+                if t in joins:
+                    st.join()
+                    torch.cuda.synchronize()
+            else:
+                cc, mm, ww = st.step(act, chunk)
+            outs.append((cc, mm, ww))
+        if pipelined:
+            st.join()
+        torch.cuda.synchronize()
+        res = tuple(torch.cat([o[q][k].clone() for o in outs]) for q in range(3))
+        st.close()
+        return res
+
+    want = run(actives[0], False)
+    assert torch.isfinite(want[2]).all()
+    for act in actives:
+        got = run(act, True)
+        for name, x, y in zip(("codes", "mel", "wav"), got, want):
+            if not torch.equal(x, y):
+                per = x.reshape(steps, -1) != y.reshape(steps, -1)
+                first = int(per.any(1).nonzero()[0])
+                raise AssertionError((name, "active slots", len(act), "first differing step", first, float((x.float() - y.float()).abs().max())))
+    ctx.close()
+
+
 def test_fixed_plan_with_40ms_chunks_and_ragged_tiles():
     """The same promise at BASELINE configs[4]'s chunk size (40 ms: 2 frames per step, 16 rows per slot in the C = 256 stage - four
     slots per conv_limb tile): slot 17 of a 32-slot fixed-plan stream-set with 32, 9 and 1 active slots (9 and 1 end in ragged tiles
