@@ -101,6 +101,11 @@ _PROTOS = {
     "conan_resample_length": (C.c_int64, [C.c_void_p, C.c_int64]),
     "conan_resample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_streams_set_input_rate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "conan_streams_set_output_rate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "conan_streams_set_output_ld": (C.c_int, [C.c_void_p, C.c_int64]),
+    "conan_streams_output_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "conan_streams_output_pending": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "conan_streams_flush_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_streams_output_fence": (C.c_int, [C.c_void_p, C.c_void_p]),
     "conan_streams_output_fence_event": (C.c_int, [C.c_void_p, C.c_void_p]),
     "conan_streams_test_fault": (C.c_int, [C.c_void_p, C.c_int]),

@@ -182,7 +182,7 @@ int conan_streams_create_opts(conan_ctx* ctx, int max_slots, int max_frames, int
         s->d_guard = reinterpret_cast<unsigned*>(s->alloc(16));
         HIP_CHECK(hipMemcpy(s->d_guard + 2, &hdev, sizeof(hdev), hipMemcpyHostToDevice));
       }
-      s->slot_seen.assign(max_slots, 0); s->has_ref.assign(max_slots, 0); s->voc_fresh.assign(max_slots, 1);
+      s->slot_seen.assign(max_slots, 0); s->has_ref.assign(max_slots, 0); s->voc_fresh.assign(max_slots, 1); s->voc_samples.assign(max_slots, 0);
       s->pin.init((size_t)max_slots + cnk::kSlotTablePad);
       s->pos_emf = (int*)s->alloc(max_slots); s->pos_dec = (int*)s->alloc(max_slots); s->pos_voc = (int*)s->alloc(max_slots);
       std::vector<int> id(max_slots);
@@ -224,6 +224,10 @@ int conan_streams_reset(conan_streams* s, const int32_t* slots, int n, int which
     if (models & CONAN_MODEL_HIFIGAN) {
       zero(s->voc_state, s->pos_voc);
       for (int i = 0; i < n; ++i) s->voc_fresh[slots[i]] = 1;
+      // the output rate stays; the output resampler restarts (output index 0, inputs before the first are zero: the ring needs no clearing)
+      for (int i = 0; i < n; ++i) s->voc_samples[slots[i]] = 0;
+      if (!s->or_slot.empty())
+        for (int i = 0; i < n; ++i) { conan_streams::OrSlot& o = s->or_slot[slots[i]]; o.out = 0; o.flushed = 0; }
     }
     if (models & CONAN_MODEL_EMFORMER) zero(s->emf_state, s->pos_emf);
     if (models & CONAN_MODEL_CONAN) zero(s->dec_state, s->pos_dec);
@@ -371,9 +375,10 @@ int conan_hifigan_step_taps(conan_streams* s, const int32_t* slots, int n, int f
     if (!(s->ctx->cfg.models & CONAN_MODEL_HIFIGAN)) throw Error(CONAN_ERR_STATE, "context holds no HiFi-GAN model");
     if (frames < 1 || frames > s->max_frames) throw Error(CONAN_ERR_INVALID, "frames out of range");
     HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+    const conan_streams::OutPlan op = s->out_plan(slots, n, frames, wav_out_dev, (long long)frames * s->ctx->hop, nullptr, "conan_hifigan_step_taps");
     s->join((hipStream_t)stream);
     s->set_slots(slots, n, (hipStream_t)stream);
-    s->hifigan_step(n, frames, mel_dev, wav_out_dev, pre_tanh_dev, (hipStream_t)stream, taps);
+    s->hifigan_step(n, frames, mel_dev, wav_out_dev, pre_tanh_dev, (hipStream_t)stream, taps, &op);
   });
 }
 
@@ -384,9 +389,10 @@ int conan_hifigan_step(conan_streams* s, const int32_t* slots, int n, int frames
     if (!(s->ctx->cfg.models & CONAN_MODEL_HIFIGAN)) throw Error(CONAN_ERR_STATE, "context holds no HiFi-GAN model");
     if (frames < 1 || frames > s->max_frames) throw Error(CONAN_ERR_INVALID, "frames out of range");
     HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+    const conan_streams::OutPlan op = s->out_plan(slots, n, frames, wav_out_dev, (long long)frames * s->ctx->hop, nullptr, "conan_hifigan_step");
     s->join((hipStream_t)stream);
     s->set_slots(slots, n, (hipStream_t)stream);
-    s->hifigan_step(n, frames, mel_dev, wav_out_dev, pre_tanh_dev, (hipStream_t)stream);
+    s->hifigan_step(n, frames, mel_dev, wav_out_dev, pre_tanh_dev, (hipStream_t)stream, nullptr, &op);
   });
 }
 
@@ -400,7 +406,7 @@ static void check_chunk_step(const conan_streams* s, const char* who) {
 
 // The stages of one chunk step on `st` for the slots set_slots has just installed (conan_step, conan_step_wav).
 static void step_blocking(conan_streams* s, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev, float* mel_out_dev,
-                          float* wav_out_dev, hipStream_t st) {
+                          float* wav_out_dev, hipStream_t st, const conan_streams::OutPlan& op) {
   const int seg = s->ctx->cfg.emf_segment;
   int* codes_seg = codes_dev ? codes_dev : s->d_codes;
   s->emformer_step(n, mel_chunk_dev, nullptr, nullptr, codes_seg, st);
@@ -412,7 +418,7 @@ static void step_blocking(conan_streams* s, int n, int emit, const float* mel_ch
   }
   float* mel = mel_out_dev ? mel_out_dev : s->c_mel.base;
   { conan_decoder_taps none; memset(&none, 0, sizeof(none)); s->decoder_step(n, emit, codes_emit, mel, none, st); }
-  s->hifigan_step(n, emit, mel, wav_out_dev, nullptr, st);
+  s->hifigan_step(n, emit, mel, wav_out_dev, nullptr, st, nullptr, &op);
 }
 
 int conan_step(conan_streams* s, const int32_t* slots, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev,
@@ -424,16 +430,18 @@ int conan_step(conan_streams* s, const int32_t* slots, int n, int emit, const fl
     if (emit < 1 || emit > seg) throw Error(CONAN_ERR_INVALID, "emit must be in [1, segment]");
     hipStream_t st = (hipStream_t)stream;
     HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+    const conan_streams::OutPlan op = s->out_plan(slots, n, emit, wav_out_dev, (long long)emit * s->ctx->hop, nullptr, "conan_step");
     s->join((hipStream_t)stream);
     s->set_slots(slots, n, st);
-    step_blocking(s, n, emit, mel_chunk_dev, codes_dev, mel_out_dev, wav_out_dev, st);
+    step_blocking(s, n, emit, mel_chunk_dev, codes_dev, mel_out_dev, wav_out_dev, st, op);
   });
 }
 
 // Everything of conan_step_async after its argument checks; `pre` (may be empty) enqueues work on the Emformer stream right
 // before the step's Emformer launch, behind the step's input event and slot table.
 static void step_pipelined(conan_streams* s, const int32_t* slots, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev,
-                           float* mel_out_dev, float* wav_out_dev, void* stream, const std::function<void(hipStream_t)>& pre) {
+                           float* mel_out_dev, float* wav_out_dev, void* stream, const std::function<void(hipStream_t)>& pre,
+                           const conan_streams::OutPlan& op) {
   const int seg = s->ctx->cfg.emf_segment;
   HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
   s->async_init();
@@ -513,7 +521,7 @@ static void step_pipelined(conan_streams* s, const int32_t* slots, int n, int em
   if (!s->ev_wide[p]) HIP_CHECK(hipEventCreateWithFlags(&s->ev_wide[p], hipEventDisableTiming));
   s->mark_wide = s->ev_wide[p];
   s->wide_marked[p] = false;
-  s->hifigan_step(n, emit, mel, wav_out_dev, nullptr, s->st_voc);
+  s->hifigan_step(n, emit, mel, wav_out_dev, nullptr, s->st_voc, nullptr, &op);
   s->mark_wide = nullptr;
   if (tl) { HIP_CHECK(hipEventRecord(te[5], s->st_voc)); s->tl_n++; }
   HIP_CHECK(hipEventRecord(s->ev_voc[p], s->st_voc));
@@ -533,7 +541,8 @@ int conan_step_async(conan_streams* s, const int32_t* slots, int n, int emit, co
     const int seg = s->ctx->cfg.emf_segment;
     if (emit < 1 || emit > seg) throw Error(CONAN_ERR_INVALID, "emit must be in [1, segment]");
     if (s->prof_on) throw Error(CONAN_ERR_STATE, "profiling is not available for pipelined steps");
-    step_pipelined(s, slots, n, emit, mel_chunk_dev, codes_dev, mel_out_dev, wav_out_dev, stream, nullptr);
+    const conan_streams::OutPlan op = s->out_plan(slots, n, emit, wav_out_dev, (long long)emit * s->ctx->hop, nullptr, "conan_step_async");
+    step_pipelined(s, slots, n, emit, mel_chunk_dev, codes_dev, mel_out_dev, wav_out_dev, stream, nullptr, op);
   });
 }
 
@@ -788,6 +797,19 @@ static void step_wav(conan_streams* s, const std::string& who, const int32_t* sl
   }
   const bool direct = common || (groups.size() == 1 && (int)groups[0].size() == n && pl[0].emit == seg);
   const bool scatter = !direct && !groups.empty();
+  // the groups' output rows (out_plan): a staged call with an output rate among its emitting rows, or any stride set (a group
+  // of emit < seg frames then differs from it even at seg * hop), has resample_out_kernel write each group's audio straight to
+  // its call-order rows of wav_out_dev (the scatter then places codes and mel only); otherwise no group's plan is active
+  bool route = scatter && s->out_ld != 0;
+  for (int g = 0; scatter && g < (int)groups.size(); ++g)
+    for (int i : groups[g]) route = route || (!s->or_slot.empty() && s->or_slot[slots[i]].f);
+  std::vector<conan_streams::OutPlan> ops;
+  for (int g = 0; g < (int)groups.size(); ++g) {
+    std::vector<int32_t> gs;
+    for (int i : groups[g]) gs.push_back(slots[i]);
+    const int e = pl[groups[g][0]].emit;
+    ops.push_back(s->out_plan(gs.data(), (int)gs.size(), e, wav_out_dev, route ? (long long)seg * hop : (long long)e * hop, route ? &groups[g] : nullptr, who));
+  }
   const int nm_in = m.num_mels, nm = c.num_mels;
   int jobs = 0;
   std::vector<int> tab;
@@ -814,6 +836,7 @@ static void step_wav(conan_streams* s, const std::string& who, const int32_t* sl
   HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
   hipStream_t cst = (hipStream_t)stream;
   if (!pipelined || groups.empty()) s->join(cst);
+  s->out_counts.assign(n, 0);      // (rows that emit no frame; hifigan_step fills the others)
   const int q = (int)(s->rg_calls % conan_streams::NS);
   if (!common) {
     s->ragged_init();
@@ -857,7 +880,7 @@ static void step_wav(conan_streams* s, const std::string& who, const int32_t* sl
   cnk::WavScatterArgs sc;
   sc.tab = s->rg_tab[q]; sc.n = n; sc.seg = seg; sc.nm = nm; sc.hop = hop;
   sc.codes_src = s->rg_codes[q]; sc.mel_src = s->rg_mel[q]; sc.wav_src = s->rg_wav[q];
-  sc.codes = codes_dev; sc.mel = mel_out_dev; sc.wav = wav_out_dev;
+  sc.codes = codes_dev; sc.mel = mel_out_dev; sc.wav = route ? nullptr : wav_out_dev;
   auto group_step = [&](int g, int off, hipStream_t st) {
     std::vector<int32_t> gs;
     for (int i : groups[g]) gs.push_back(slots[i]);
@@ -867,10 +890,10 @@ static void step_wav(conan_streams* s, const std::string& who, const int32_t* sl
     float* md = direct ? mel_out_dev : s->rg_mel[q] + (size_t)off * seg * nm;
     float* wd = direct ? wav_out_dev : s->rg_wav[q] + (size_t)off * seg * hop;
     if (pipelined) {
-      step_pipelined(s, gs.data(), ng, e, chunk, cd, md, wd, stream, g == 0 ? front : std::function<void(hipStream_t)>());
+      step_pipelined(s, gs.data(), ng, e, chunk, cd, md, wd, stream, g == 0 ? front : std::function<void(hipStream_t)>(), ops[g]);
     } else {
       s->set_slots(gs.data(), ng, st);
-      step_blocking(s, ng, e, chunk, cd, md, wd, st);
+      step_blocking(s, ng, e, chunk, cd, md, wd, st, ops[g]);
     }
   };
   if (pipelined && !groups.empty()) {
@@ -887,6 +910,10 @@ static void step_wav(conan_streams* s, const std::string& who, const int32_t* sl
     for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g) group_step(g, off, cst);
     if (scatter) s->profiled("wav_rows_scatter_kernel", 0.0, cst, [&] { cnk::launch_wav_scatter(sc, cst); });
     if (!common) HIP_CHECK(hipEventRecord(s->ev_stage[q], cst));
+  }
+  if (scatter && !route) {      // (each group's step counted its own rows, in group order: back to the call's rows)
+    s->out_counts.assign(n, 0);
+    for (int i = 0; i < n; ++i) s->out_counts[i] = pl[i].emit * hop;
   }
   fe_commit(s, slots, n, pl, final_);
   for (int i = 0; i < n; ++i) emit_out[i] = pl[i].emit;
@@ -988,6 +1015,103 @@ int conan_streams_set_input_rate(conan_streams* s, const int32_t* slots, int n, 
     HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
     s->resample_init();
     for (int i = 0; i < n; ++i) s->rs_slot[slots[i]] = conan_streams::RsSlot{t, 0, 0, 0};
+  });
+}
+
+static void check_slot_list(const conan_streams* s, const int32_t* slots, int n) {
+  if (n < 1 || n > s->max_slots) throw Error(CONAN_ERR_INVALID, "slot count out of range");
+  std::vector<char> seen(s->max_slots, 0);
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] >= s->max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
+    if (seen[slots[i]]) throw Error(CONAN_ERR_INVALID, "duplicate slot");
+    seen[slots[i]] = 1;
+  }
+}
+
+int conan_streams_set_output_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg) {
+  return guarded([&] {
+    if (!s || !slots || !cfg) throw Error(CONAN_ERR_INVALID, "null argument");
+    if (!(s->ctx->cfg.models & CONAN_MODEL_HIFIGAN)) throw Error(CONAN_ERR_STATE, "conan_streams_set_output_rate: context holds no HiFi-GAN model");
+    check_slot_list(s, slots, n);
+    const int model_rate = 50 * s->ctx->hop;
+    const conan_resample_cfg& c = *cfg;
+    if (c.in_rate != model_rate)
+      throw Error(CONAN_ERR_INVALID, "conan_streams_set_output_rate: in_rate must be the model rate (hop * 50 = " + std::to_string(model_rate) + " Hz)");
+    HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+    const ch::RsTable* t = nullptr;
+    // the history holds model-rate audio: the longest span of an accepted filter (CONAN_RESAMPLE_MAX_TAPS) plus the largest step
+    const int ring_len = ch::next_pow2(CONAN_RESAMPLE_MAX_TAPS + 8 + s->max_frames * s->ctx->hop);
+    if (c.in_rate != c.out_rate) {
+      t = &s->ctx->resample_table(c);
+    } else {
+      conan_resample_cfg probe = c;     // the configuration must still be a valid one
+      if (conan_resample_length(&probe, 0) < 0) throw Error(CONAN_ERR_INVALID, "conan_streams_set_output_rate: invalid resampler configuration");
+    }
+    for (int i = 0; i < n; ++i)
+      if (s->voc_samples[slots[i]] != 0)
+        throw Error(CONAN_ERR_STATE, "conan_streams_set_output_rate: slot " + std::to_string(slots[i]) + " is not at the start of its vocoder stream (reset it with CONAN_MODEL_HIFIGAN first)");
+    if (!t && s->or_slot.empty()) return;      // the model-rate path of a stream-set that never had a rate: nothing to allocate
+    if (!s->or_ring) {
+      s->or_ring_len = ring_len;
+      s->or_ring = s->alloc((size_t)s->max_slots * ring_len);        // stream state (state_bytes)
+      s->or_slot.assign(s->max_slots, conan_streams::OrSlot());
+    }
+    for (int i = 0; i < n; ++i) s->or_slot[slots[i]] = conan_streams::OrSlot{t, 0, 0};
+  });
+}
+
+int conan_streams_set_output_ld(conan_streams* s, int64_t ld) {
+  return guarded([&] {
+    if (!s) throw Error(CONAN_ERR_INVALID, "null streams");
+    if (ld < 0 || ld > INT_MAX) throw Error(CONAN_ERR_INVALID, "conan_streams_set_output_ld: ld out of range");
+    s->out_ld = ld;
+  });
+}
+
+int conan_streams_output_samples(conan_streams* s, int32_t* counts, int cap) {
+  int rows = 0;
+  const int rc = guarded([&] {
+    if (!s || (!counts && cap > 0) || cap < 0) throw Error(CONAN_ERR_INVALID, "null argument");
+    rows = (int)s->out_counts.size();
+    for (int i = 0; i < rows && i < cap; ++i) counts[i] = s->out_counts[i];
+  });
+  return rc < 0 ? rc : rows;
+}
+
+int conan_streams_output_pending(conan_streams* s, const int32_t* slots, int n, int32_t* counts) {
+  return guarded([&] {
+    if (!s || !slots || !counts) throw Error(CONAN_ERR_INVALID, "null argument");
+    check_slot_list(s, slots, n);
+    const conan_streams::OutPlan P = s->out_plan(slots, n, 0, nullptr, INT_MAX, nullptr, "conan_streams_output_pending");
+    for (int i = 0; i < n; ++i) counts[i] = P.counts[i];
+  });
+}
+
+int conan_streams_flush_output(conan_streams* s, const int32_t* slots, int n, float* wav_out_dev, int64_t wav_ld, void* stream) {
+  return guarded([&] {
+    if (!s || !slots || !wav_out_dev) throw Error(CONAN_ERR_INVALID, "null argument");
+    if (wav_ld < 0 || wav_ld > INT_MAX) throw Error(CONAN_ERR_INVALID, "conan_streams_flush_output: wav_ld out of range");
+    check_slot_list(s, slots, n);
+    const conan_streams::OutPlan P = s->out_plan(slots, n, 0, wav_out_dev, wav_ld, nullptr, "conan_streams_flush_output");
+    HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+    hipStream_t st = (hipStream_t)stream;
+    s->join(st);
+    if (P.active) {
+      s->out_stage_init();
+      const int q = (int)(s->or_calls++ % conan_streams::NS);
+      HIP_CHECK(hipStreamWaitEvent(st, s->ev_or[q], 0));
+      s->or_pin.upload(reinterpret_cast<int*>(s->or_rows[q]), reinterpret_cast<const int*>(P.rows.data()), (size_t)n * sizeof(cnk::RsOutRow) / sizeof(int), st);
+      cnk::ResampleOutArgs ra;
+      ra.wav = s->or_wav[q]; ra.wav_ld = 0; ra.ring = s->or_ring; ra.ring_len = s->or_ring_len; ra.out = wav_out_dev; ra.out_ld = wav_ld;
+      ra.rows = s->or_rows[q]; ra.n = n; ra.tiles = P.tiles; ra.win = P.win;
+      s->profiled("resample_out_kernel", P.flops, st, [&] { cnk::launch_resample_out(ra, st); });
+      HIP_CHECK(hipEventRecord(s->ev_or[q], st));
+    }
+    for (int i = 0; i < n && !s->or_slot.empty(); ++i) {
+      conan_streams::OrSlot& o = s->or_slot[slots[i]];
+      if (!o.f || s->voc_samples[slots[i]] == 0) continue;
+      o.out += P.counts[i]; o.flushed = 1;
+    }
   });
 }
 

@@ -306,7 +306,7 @@ __global__ __launch_bounds__(256) void wav_rows_scatter_kernel(const WavScatterA
   const long long src = (long long)g * a.seg + (long long)k * e;      // the group's compact [rows][e] frames start at g * seg
   if (a.codes) for (int t = threadIdx.x; t < e; t += blockDim.x) a.codes[(long long)i * a.seg + t] = a.codes_src[(long long)(g + k) * a.seg + t];
   if (a.mel) for (int t = threadIdx.x; t < e * a.nm; t += blockDim.x) a.mel[(long long)i * a.seg * a.nm + t] = a.mel_src[src * a.nm + t];
-  for (int t = threadIdx.x; t < e * a.hop; t += blockDim.x) a.wav[(long long)i * a.seg * a.hop + t] = a.wav_src[src * a.hop + t];
+  if (a.wav) for (int t = threadIdx.x; t < e * a.hop; t += blockDim.x) a.wav[(long long)i * a.seg * a.hop + t] = a.wav_src[src * a.hop + t];
 }
 
 void launch_mel_ragged(const MelRaggedArgs& a, hipStream_t st) {

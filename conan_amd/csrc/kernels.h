@@ -550,7 +550,7 @@ void launch_mel_ragged(const MelRaggedArgs& a, hipStream_t st);         // one l
 struct WavScatterArgs {
   const int* tab; int n, seg, nm, hop;
   const int* codes_src; const float* mel_src; const float* wav_src;     // staging: group-compact rows ([k][emit][.]) at group offsets
-  int* codes; float* mel; float* wav;                                    // caller's [n][seg], [n][seg][nm], [n][seg * hop]; codes / mel may be null
+  int* codes; float* mel; float* wav;                                    // caller's [n][seg], [n][seg][nm], [n][seg * hop]; each may be null (wav: resample_out_kernel places the audio rows)
 };
 void launch_wav_scatter(const WavScatterArgs& a, hipStream_t st);
 
@@ -580,6 +580,22 @@ struct ResampleStreamArgs {
   const RsRow* rows; int n, tiles, win;
 };
 void launch_resample_stream(const ResampleStreamArgs& a, hipStream_t st);
+// Output side (conan_streams_set_output_rate): one call row of resample_out_kernel.  The roles of ring and row are the input side's:
+// the slot's older model-rate samples come from its history ring, the vocoder step's m new ones from staging row r; outputs
+// [out0, out0 + h) go to row `dst` of the caller's buffer.  taps == nullptr: the slot has no rate, its m samples are copied verbatim.
+struct RsOutRow {
+  long long in0, out0;                // model-rate samples produced before this step; output samples delivered before it
+  const float* taps; const int* ph;
+  int slot, m, h, orig, nph, w, L, dst;
+};
+static_assert(sizeof(RsOutRow) == 16 * sizeof(int), "RsOutRow is uploaded as 16 ints");
+struct ResampleOutArgs {
+  const float* wav; long long wav_ld;   // conv_post's model-rate rows (staging), row r at r * wav_ld (a flush: m = 0 everywhere, never null)
+  float* ring; int ring_len;            // [max_slots][ring_len] (a power of two; model-rate sample i at i & (ring_len - 1))
+  float* out; long long out_ld;         // the caller's wav_out_dev at the stride in force
+  const RsOutRow* rows; int n, tiles, win;
+};
+void launch_resample_out(const ResampleOutArgs& a, hipStream_t st);
 
 // ---- style pass (per utterance) helpers
 struct RowMaskArgs { TRef x; TRef m; const int* lens; int T, n, C; int mode; };  // mode 0: sum|x|>0, 1: x[0]!=0

@@ -97,6 +97,41 @@ __global__ __launch_bounds__(kRsTile) void resample_stream_kernel(const Resample
   for (int t = t0; t < R.m; t += stride) ring[(R.in0 + t) & (kRsRing - 1)] = wav[t];
 }
 
+// One launch per vocoder step with an output rate (conan_streams_set_output_rate), behind conv_post_kernel: row r (blockIdx.y)
+// resamples its slot's outputs [out0, out0 + h) - model-rate samples before in0 from the slot's history ring, the step's m new ones from
+// conv_post's staging row - into row `dst` of the caller's buffer, and appends the m samples to the ring.  Samples at or past
+// in0 + m read as zero: a flush (m = 0, h = what is left of the utterance) pads as the whole-signal kernel does.  The host has checked
+// that the ring positions a launch reads and the ones it writes are disjoint.  Rows without a rate are copied verbatim.
+__global__ __launch_bounds__(kRsTile) void resample_out_kernel(const ResampleOutArgs a) {
+  extern __shared__ float lds[];
+  const RsOutRow R = a.rows[blockIdx.y];
+  const float* wav = a.wav + blockIdx.y * a.wav_ld;
+  float* out = a.out + R.dst * a.out_ld;
+  const int stride = gridDim.x * kRsTile, t0 = blockIdx.x * kRsTile + threadIdx.x;
+  if (!R.taps) {
+    for (int t = t0; t < R.m; t += stride) out[t] = wav[t];
+    return;
+  }
+  const int mask = a.ring_len - 1;
+  float* ring = a.ring + (size_t)R.slot * a.ring_len;
+  if ((int)blockIdx.x * kRsTile < R.h) {          // uniform per block
+    const long long j0 = R.out0 + (long long)blockIdx.x * kRsTile, jt = j0 + threadIdx.x;
+    const bool act = t0 < R.h;
+    const long long end = R.in0 + R.m;
+    const int mlast = R.m > 0 ? R.m - 1 : 0;
+    auto fetch = [&](long long i) {
+      const long long d = i - R.in0;
+      const float vw = wav[d < 0 ? 0 : (d > mlast ? mlast : d)];
+      const float vr = ring[i & mask];
+      return (i < 0 || i >= end) ? 0.f : (d >= 0 ? vw : vr);
+    };
+    RsFilter f; f.taps = R.taps; f.ph = R.ph; f.orig = R.orig; f.nph = R.nph; f.w = R.w; f.L = R.L;
+    const float y = rs_output(lds, j0, act ? jt : R.out0 + R.h - 1, f, a.win, fetch);
+    if (act) out[jt - R.out0] = y;
+  }
+  for (int t = t0; t < R.m; t += stride) ring[(R.in0 + t) & mask] = wav[t];
+}
+
 void launch_resample(const ResampleArgs& a, int n, hipStream_t st) {
   const dim3 grid((unsigned)((a.nout + kRsTile - 1) / kRsTile), (unsigned)n);
   hipLaunchKernelGGL(resample_kernel, grid, dim3(kRsTile), (size_t)(a.win + 2) * sizeof(float), st, a);
@@ -104,6 +139,10 @@ void launch_resample(const ResampleArgs& a, int n, hipStream_t st) {
 
 void launch_resample_stream(const ResampleStreamArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(resample_stream_kernel, dim3((unsigned)a.tiles, (unsigned)a.n), dim3(kRsTile), (size_t)(a.win + 2) * sizeof(float), st, a);
+}
+
+void launch_resample_out(const ResampleOutArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(resample_out_kernel, dim3((unsigned)a.tiles, (unsigned)a.n), dim3(kRsTile), (size_t)(a.win + 2) * sizeof(float), st, a);
 }
 
 }  // namespace cnk

@@ -156,6 +156,34 @@ struct conan_streams {
   hipEvent_t ev_rs[NS] = {};
   long long rs_calls = 0;
   void resample_init();
+  // output resampler (conan_streams_set_output_rate): per slot the filter (null: audio leaves at the model rate), output samples
+  // delivered, whether conan_streams_flush_output has ended the utterance.  voc_samples = model-rate samples the slot's vocoder has
+  // produced since its last reset with CONAN_MODEL_HIFIGAN (kept from creation on: pos_voc is device memory).  The history ring
+  // ([max_slots][or_ring_len], stream state) is allocated by the first conan_streams_set_output_rate with a real rate; conv_post's
+  // staging rows and the row table (NS sets, set q reused after ev_or[q]: the launch that read it has completed) by the first
+  // vocoder step that needs them.
+  struct OrSlot { const ch::RsTable* f = nullptr; long long out = 0; int flushed = 0; };
+  std::vector<OrSlot> or_slot;
+  std::vector<long long> voc_samples;
+  float* or_ring = nullptr; int or_ring_len = 0;
+  PinRing or_pin;
+  cnk::RsOutRow* or_rows[NS] = {}; float* or_wav[NS] = {};
+  hipEvent_t ev_or[NS] = {};
+  long long or_calls = 0, out_ld = 0;       // out_ld: conan_streams_set_output_ld (0: each entry point's own stride)
+  std::vector<int32_t> out_counts;          // conan_streams_output_samples: per row of the most recent step call
+  void out_stage_init();
+  // One vocoder step's output rows, checked before anything changes (out_plan) and handed to hifigan_step, which commits the slots'
+  // counters once its launches are enqueued.  active: the step's audio goes through staging and resample_out_kernel.
+  struct OutPlan {
+    bool active = false;
+    std::vector<cnk::RsOutRow> rows;
+    std::vector<int32_t> counts;            // samples per row of this step
+    std::vector<int> dst;                   // rows of the call's buffer and of out_counts (empty: 0 .. n-1)
+    float* base = nullptr; long long ld = 0;
+    int tiles = 1, win = 0;
+    double flops = 0;
+  };
+  OutPlan out_plan(const int32_t* slots, int n, int frames, float* wav_out, long long natural_ld, const std::vector<int>* dst, const std::string& who) const;
   // --- vocoder
   Ring v_mel, v_pre;
   std::vector<VocStage> v_st;
@@ -247,6 +275,7 @@ struct conan_streams {
     for (int i = 0; i < NP; ++i) { if (ev_wide[i]) (void)hipEventDestroy(ev_wide[i]); if (ev_emf[i]) (void)hipEventDestroy(ev_emf[i]); if (ev_front[i]) (void)hipEventDestroy(ev_front[i]); if (ev_voc[i]) (void)hipEventDestroy(ev_voc[i]); }
     for (int i = 0; i < NS; ++i) if (ev_stage[i]) (void)hipEventDestroy(ev_stage[i]);
     for (int i = 0; i < NS; ++i) if (ev_rs[i]) (void)hipEventDestroy(ev_rs[i]);
+    for (int i = 0; i < NS; ++i) if (ev_or[i]) (void)hipEventDestroy(ev_or[i]);
     for (void* p : allocs) (void)hipFree(p);
     if (h_guard) (void)hipHostFree(h_guard);
     for (auto& e : prof_ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -325,7 +354,8 @@ struct conan_streams {
   void op_pitch(const cnk::PitchHeadArgs& a, hipStream_t st);
   void op_advance(int* pos, int n, int delta, hipStream_t st);
 
-  void hifigan_step(int n, int frames, const float* mel_dev, float* wav_out, float* pre_tanh, hipStream_t st, const conan_hifigan_taps* taps = nullptr);
+  void hifigan_step(int n, int frames, const float* mel_dev, float* wav_out, float* pre_tanh, hipStream_t st, const conan_hifigan_taps* taps = nullptr,
+                    const OutPlan* op = nullptr);
   void emformer_step(int n, const float* chunk, float* out, float* logits, int32_t* codes, hipStream_t st);
   void decoder_step(int n, int frames, const int32_t* codes, float* mel_out, const conan_decoder_taps& taps, hipStream_t st, const DecExtra* extra = nullptr);
   void set_reference(const int32_t* slots, int n, const float* ref, const int32_t* ref_len, int max_len, hipStream_t st);

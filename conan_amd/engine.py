@@ -212,15 +212,48 @@ class StreamingVoiceConversionEngine:
         self.slots = list(range(n_streams))
         self.seg, self.rc = ctx.cfg.emf_segment, ctx.cfg.emf_right_context
 
-    def start(self, ref_mel, ref_len=None, which=7):
+    def start(self, ref_mel, ref_len=None, which=7, out_rate=None, out_filter=None):
+        """out_rate: the sample rate the audio leaves at (None: the model rate), resampled on the GPU behind the vocoder; out_filter:
+        dict of Context.resample's filter keywords.  The steps then deliver what the filter has the inputs for, finish() the tail."""
+        if isinstance(out_rate, (list, tuple)):
+            raise ValueError("out_rate: one rate for all slots here (feed / infer return one [B, count] block); open_slots and "
+                             "infer_wav_staggered take a rate per slot / utterance")
         self.st.reset(self.slots, which=which)
         self.st.set_reference(self.slots, ref_mel, ref_len)
+        self._set_out_rate(self.slots, out_rate, out_filter)
 
-    def start_wav(self, ref_mel, ref_len=None, in_rate=None, **filter):
+    def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
-        in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords."""
-        self.start(ref_mel, ref_len, which=7 | 8)
+        in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
+        out_rate / out_filter: as in start()."""
+        self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter)
         self._set_rate(self.slots, in_rate, filter)
+
+    def _set_out_rate(self, slots, out_rate, out_filter):
+        """The slots' output rate (None: the model rate), one value or one per slot, and the stream-set's output stride: wide enough
+        for a full chunk of the fastest slot.  Slots that never had another rate are left alone."""
+        st = self.st
+        rates = list(out_rate) if isinstance(out_rate, (list, tuple)) else [out_rate] * len(slots)
+        for r in dict.fromkeys(rates):
+            group = [s for s, x in zip(slots, rates) if x == r and (x is not None or s in st.output_rates)]
+            if group:
+                if self.ctx.cfg.voc_upsample == 2 and r is not None:
+                    raise ValueError("out_rate with an upsample 'nn' vocoder: run Streams.hifigan_step over the mel prefix and Streams.flush_output instead")
+                st.set_output_rate(group, r or st.model_rate, **(out_filter or {}))
+        L = self.seg * self.ctx.hop
+        ld = max([L] + [-(-L * r // st.model_rate) + 2 for r in st.output_rates.values()]) if st.output_rates else 0
+        if ld != st.output_ld:
+            st.set_output_ld(ld)
+
+    def finish(self, slots=None):
+        """End of utterance on a stream-set with output rates: the slots' remaining output samples (Streams.flush_output), one 1-D
+        tensor per slot (empty for a slot without a rate)."""
+        return self.st.flush_output(self.slots if slots is None else slots)
+
+    @staticmethod
+    def _rows(w):
+        """A step's wav rows (a list on a stream-set with output rates; all slots of these calls deliver the same count) as [B, count]."""
+        return torch.stack(list(w)) if isinstance(w, (list, tuple)) else w
 
     def _set_rate(self, slots, in_rate, filter):
         """The slots' input rate (None: the model rate).  A stream-set that never had another rate is left alone."""
@@ -241,15 +274,21 @@ class StreamingVoiceConversionEngine:
         chunk of algorithmic latency).  After final=True keep calling feed(empty, final=True) until it returns 0 frames.
         pipelined: conan_step_wav_async - the tensors are complete after self.st.join()."""
         fn = self.st.step_wav_async if pipelined else self.st.step_wav
-        emit, c, m, w = fn(self.slots, wav_chunk, final=final, mel=mel)
-        return w, m, c[:, :emit]
+        if not self.st.output_ld:
+            emit, c, m, w = fn(self.slots, wav_chunk, final=final, mel=mel)
+            return w, m, c[:, :emit]
+        # output rates: rows at the engine's stride, all slots at one position and rate here (a view: pipelined steps complete at join())
+        buf = torch.empty(len(self.slots), self.st.output_ld, device=wav_chunk.device)
+        emit, c, m, _ = fn(self.slots, wav_chunk, final=final, mel=mel, wav_out=buf)
+        return buf[:, :self.st.output_samples()[0] if emit else 0], m, c[:, :emit]
 
     @torch.no_grad()
-    def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, **filter):
+    def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
-        resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit."""
-        self.start_wav(ref_mel, ref_len, in_rate, **filter)
+        resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
+        out_rate (+ out_filter): the returned wav is the whole utterance at that rate, ctx.resample of the model-rate wav bit for bit."""
+        self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -271,14 +310,18 @@ class StreamingVoiceConversionEngine:
                 codes.append(c)
         if pipelined:
             self.st.join()
+        if self.st.output_rates:
+            wavs.append(torch.stack(self.finish()))
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
-    def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, **filter):
+    def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
-        rate), one value or one per slot; filter: Context.resample's filter keywords."""
+        rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
+        (None: the model rate), one value or one per slot."""
         self.st.reset(slots, which=7 | 8)
         self.st.set_reference(slots, ref_mel, ref_len)
+        self._set_out_rate(slots, out_rate, out_filter)
         rates = list(in_rate) if isinstance(in_rate, (list, tuple)) else [in_rate] * len(slots)
         for r in dict.fromkeys(rates):
             self._set_rate([s for s, x in zip(slots, rates) if x == r], r, filter)
@@ -291,19 +334,21 @@ class StreamingVoiceConversionEngine:
         pipelined: conan_step_wav_ragged_async - the tensors are complete after self.st.join()."""
         fn = self.st.step_wav_ragged_async if pipelined else self.st.step_wav_ragged
         emit, c, m, w = fn(slots, wav, samples, final, mel=mel)
-        hop = self.ctx.hop
-        return [(w[i, :e * hop], m[i, :e], c[i, :e]) for i, e in enumerate(emit)]
+        counts = self.st.output_samples()        # (emit * hop for a slot without an output rate)
+        return [(w[i, :counts[i]], m[i, :e], c[i, :e]) for i, e in enumerate(emit)]
 
     @torch.no_grad()
-    def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, **filter):
+    def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
         frames; with no slot free the utterance waits for one); every tick is one feed_ragged over the slots live in it.
         -> one (wav, mel [T, 80], codes [T]) per utterance: what infer_wav would give for it alone.  The slot each utterance used is
         left in self.staggered_slots.  in_rates[u] (+ filter keywords): utterance u's sample rate (None: the model rate); one call
-        then mixes rates, with rows as wide as the widest input of the call."""
+        then mixes rates, with rows as wide as the widest input of the call.  out_rates[u] (+ out_filter): the rate utterance u's
+        wav is returned at (None: the model rate)."""
         U = len(src_wavs)
+        orates = list(out_rates) if out_rates is not None else [None] * U
         assert len(starts) == U and len(ref_mel) == U
         rates = list(in_rates) if in_rates is not None else [None] * U
         Ls = [self._in_len(r) for r in rates]
@@ -321,7 +366,8 @@ class StreamingVoiceConversionEngine:
                 self.staggered_slots[u] = live[u][0]
                 new.append(u)
             if new:
-                self.open_slots([live[u][0] for u in new], torch.stack([ref_mel[u] for u in new]), in_rate=[rates[u] for u in new], **filter)
+                self.open_slots([live[u][0] for u in new], torch.stack([ref_mel[u] for u in new]), in_rate=[rates[u] for u in new],
+                                out_rate=[orates[u] for u in new], out_filter=out_filter, **filter)
             if not live:
                 tick += 1
                 continue
@@ -349,6 +395,9 @@ class StreamingVoiceConversionEngine:
                 if m.shape[0]:
                     outs[u].append((w, m, c))
                 elif was_final:                           # the drain's empty answer: the slot is free again
+                    if orates[u] is not None and live[u][0] in self.st.output_rates:      # (the flush joins pipelined work)
+                        tail = self.finish([live[u][0]])[0]
+                        outs[u].append((tail, m[:0], c[:0]))
                     free.append(live.pop(u)[0])
                     free.sort()
             tick += 1
@@ -380,6 +429,9 @@ class StreamingVoiceConversionEngine:
         `seg` frames are kept.  The oracle of this mode is the reference module fed the same window.
         Returns (codes [B, seg], wav [B, seg*hop]) (+ mel [B, seg, 80])."""
         st, seg, hop = self.st, self.seg, self.ctx.hop
+        if st.output_rates or st.output_ld:
+            raise ValueError("windowed_step keeps the last seg * hop model-rate samples of a window: not available on a stream-set whose slots have "
+                             "an output rate (start(..., out_rate=None) restores the model rate)")
         _, _, codes = st.emformer_step(self.slots, chunk, want_out=False, want_logits=False)
         win = torch.cat([ctx_codes.to(codes.dtype), codes], 1) if ctx_codes is not None and ctx_codes.shape[1] else codes
         st.reset(self.slots, which=2 | 4)
@@ -389,15 +441,17 @@ class StreamingVoiceConversionEngine:
         return out + (mel[:, -seg:],) if return_mel else out
 
     @torch.no_grad()
-    def infer(self, src_mel, ref_mel, ref_len=None, pipelined=True):
+    def infer(self, src_mel, ref_mel, ref_len=None, pipelined=True, out_rate=None, out_filter=None):
         """src_mel [B,T,80], ref_mel [B,Tr,80] (cuda) -> wav [B, T*hop], mel [B,T,80], codes [B,T].
 
         The whole source is available here, so by default the chunks are issued as pipelined steps
         (conan_step_async): the Emformer + decoder of chunk t+1 overlap the vocoder of chunk t.  The
-        results are bit-identical to the blocking loop (pipelined=False)."""
+        results are bit-identical to the blocking loop (pipelined=False).  out_rate (+ out_filter): the returned wav is the
+        whole utterance at that rate, ctx.resample of the model-rate wav bit for bit."""
         if self.ctx.cfg.voc_upsample == 2:
+            self._set_out_rate(self.slots, out_rate, out_filter)      # (refuses a rate; restores the model rate)
             return self._infer_prefix_vocoder(src_mel, ref_mel, ref_len)
-        self.start(ref_mel, ref_len)
+        self.start(ref_mel, ref_len, out_rate=out_rate, out_filter=out_filter)
         B = src_mel.shape[0]
         hop, nm = self.ctx.hop, self.ctx.cfg.num_mels
         wavs, mels, codes = [], [], []
@@ -405,15 +459,19 @@ class StreamingVoiceConversionEngine:
             if pipelined:
                 c = torch.empty(B, self.seg, dtype=torch.int32, device=src_mel.device)
                 m = torch.empty(B, emit, nm, device=src_mel.device)
-                w = torch.empty(B, emit * hop, device=src_mel.device)
+                w = torch.empty(B, self.st.output_ld or emit * hop, device=src_mel.device)
                 self.st.step_async(self.slots, chunk, w, emit=emit, codes=c, mel_out=m)
+                if self.st.output_ld:
+                    w = w[:, :self.st.output_samples()[0]]
             else:
                 c, m, w = self.st.step(self.slots, chunk, emit=emit)
-            wavs.append(w)
+            wavs.append(self._rows(w))
             mels.append(m)
             codes.append(c[:, :emit])
         if pipelined:
             self.st.join()
+        if self.st.output_rates:
+            wavs.append(torch.stack(self.finish()))
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     @torch.no_grad()

@@ -62,6 +62,10 @@ class StreamingVoiceConversion:
             self.ctx.load_state_dict(name, state_dicts[name])
         self.ctx.finalize()
         self.engine = None
+        # The rate the converted audio is returned and written at.  Not a key of the reference's yaml (its output is always at
+        # audio_sample_rate): read when present, resampled on the GPU with the filter the input side's loader uses.
+        self.out_rate = int(hp.get("output_sample_rate", hp["audio_sample_rate"]))
+        self.out_filter = {"preset": "kaiser_best"}
         self._vocoder_warm_zero()
 
     def _vocoder_warm_zero(self):
@@ -98,5 +102,10 @@ class StreamingVoiceConversion:
             raise ValueError("pass 'ref_wav' / 'src_wav' or 'ref_mel' / 'src_mel'")
         if self.engine is None or self.engine.st.max_ref_frames < ref.shape[1]:
             self.engine = StreamingVoiceConversionEngine(self.ctx, 1, max_ref_frames=max(256, ref.shape[1]))
-        wav, mel, _ = self.engine.infer(src, ref)
+        rate = hp_rate = self.hparams["audio_sample_rate"]
+        if self.out_rate != hp_rate and self.ctx.cfg.voc_upsample != 2:
+            rate = self.out_rate            # streamed: the vocoder's audio leaves every chunk step at the output rate
+        wav, mel, _ = self.engine.infer(src, ref, out_rate=None if rate == hp_rate else rate, out_filter=self.out_filter)
+        if rate != self.out_rate:           # (a vocoder that looks ahead runs over whole prefixes: its utterance is resampled whole)
+            wav = self.ctx.resample(wav, hp_rate, self.out_rate, **self.out_filter)
         return wav[0].cpu().numpy(), mel[0].cpu().numpy()

@@ -39,7 +39,7 @@ class VoiceConversionRunner:
         try:
             wav_pred, _ = self.vc.infer_once({"ref_wav": pair["ref_wav"], "src_wav": pair["src_wav"]})
             out = os.path.join(self.output_dir, pair["output_name"])
-            save_wav(wav_pred, out, self.hparams["audio_sample_rate"])
+            save_wav(wav_pred, out, self.vc.out_rate)
             return True, out
         except Exception as e:  # noqa: BLE001  (per-file errors are reported, like the reference runner)
             return False, str(e)
@@ -60,11 +60,14 @@ class VoiceConversionRunner:
                 self.engine.st.close()
             self.engine = StreamingVoiceConversionEngine(vc.ctx, B, max_ref_frames=max(256, Tr))
         wav, _, _ = self.engine.infer(srcb, refb, ref_len)
-        hop = vc.ctx.hop
+        hop, rate = vc.ctx.hop, self.hparams["audio_sample_rate"]
         outs = []
         for k, p in enumerate(pairs):
             out = os.path.join(self.output_dir, p["output_name"])
-            save_wav(wav[k, :src[k].shape[0] * hop].cpu().numpy(), out, self.hparams["audio_sample_rate"])
+            w = wav[k, :src[k].shape[0] * hop]
+            if vc.out_rate != rate:          # hparams output_sample_rate: each file's own samples (the batch pads shorter sources), resampled whole
+                w = vc.ctx.resample(w, rate, vc.out_rate, **vc.out_filter)
+            save_wav(w.cpu().numpy(), out, vc.out_rate)
             outs.append(out)
         return outs
 

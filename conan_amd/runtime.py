@@ -150,6 +150,8 @@ class Streams:
         c = ctx.cfg
         self.seg, self.rc = c.emf_segment, c.emf_right_context
         self.input_rate_set = False      # set_input_rate has run on this stream-set (its history ring exists)
+        self.output_rates = {}           # slot -> output rate, for the slots whose audio leaves at another rate than the model's
+        self.output_ld = 0               # set_output_ld: row stride of every step's wav (0: each step's own)
 
     @property
     def state_bytes(self):
@@ -187,6 +189,60 @@ class Streams:
         cfg = _lib.resample_cfg(rate, self.model_rate, **filter)
         _lib.check(self.lib.conan_streams_set_input_rate(self.h, p, len(a), C.byref(cfg)))
         self.input_rate_set = True
+
+    def set_output_rate(self, slots, rate, **filter):
+        """conan_streams_set_output_rate: the slots' audio leaves every step at `rate` Hz, resampled on the GPU behind the vocoder.
+        filter: Context.resample's filter keywords (default hann).  The slots must be at the start of their vocoder stream; the rate
+        survives resets; rate == the model rate restores the model-rate path.  A step then delivers what the filter has the inputs
+        for (output_samples) and flush_output the tail; rows above the model rate need set_output_ld."""
+        a, p = _i32(slots)
+        cfg = _lib.resample_cfg(self.model_rate, rate, **filter)
+        _lib.check(self.lib.conan_streams_set_output_rate(self.h, p, len(a), C.byref(cfg)))
+        for slot in a:
+            if int(rate) != self.model_rate:
+                self.output_rates[int(slot)] = int(rate)
+            else:
+                self.output_rates.pop(int(slot), None)
+
+    def set_output_ld(self, ld):
+        """conan_streams_set_output_ld: row stride (floats) of wav in every step from now on; 0 = each step's own."""
+        _lib.check(self.lib.conan_streams_set_output_ld(self.h, int(ld)))
+        self.output_ld = int(ld)
+
+    def output_samples(self):
+        """Samples the most recent step call wrote to each row of its wav, in call order (known at once, also for pipelined calls)."""
+        n = _lib.check(self.lib.conan_streams_output_samples(self.h, None, 0))
+        buf = (C.c_int32 * max(n, 1))()
+        _lib.check(self.lib.conan_streams_output_samples(self.h, buf, n))
+        return [buf[i] for i in range(n)]
+
+    def output_pending(self, slots):
+        """What flush_output would deliver for these slots now (0 for a slot without a rate)."""
+        a, p = _i32(slots)
+        buf = (C.c_int32 * len(a))()
+        _lib.check(self.lib.conan_streams_output_pending(self.h, p, len(a), buf))
+        return list(buf)
+
+    def flush_output(self, slots, out=None):
+        """conan_streams_flush_output: end of utterance -> one 1-D tensor per slot, its remaining output samples (empty without a
+        rate).  Joins pipelined work.  The slots refuse further steps until a reset that includes the vocoder."""
+        a, p = _i32(slots)
+        counts = self.output_pending(slots)
+        ld = max(counts + [1])
+        wav = out if out is not None else torch.empty(len(a), ld, device=self.dev)
+        assert wav.is_cuda and wav.is_contiguous() and wav.dim() == 2 and wav.shape[0] == len(a)
+        _lib.check(self.lib.conan_streams_flush_output(self.h, p, len(a), _ptr(wav), wav.shape[1], _stream()))
+        self._release()
+        return [wav[i, :c] for i, c in enumerate(counts)]
+
+    def _wav_rows(self, wav, n, ld=None):
+        """A step's wav as the caller sees it: unchanged on a stream-set without output rate or stride, else one 1-D tensor per
+        row (rows `ld` floats apart) trimmed to the count the step reported."""
+        if not (self.output_rates or self.output_ld):
+            return wav
+        counts = self.output_samples()
+        ld = ld or wav.numel() // n
+        return [wav.view(-1)[:n * ld].view(n, ld)[i, :counts[i]] for i in range(n)]
 
     @property
     def model_rate(self):
@@ -289,7 +345,7 @@ class Streams:
         mel = mel.to(self.dev, torch.float32).contiguous()
         T = mel.shape[1]
         hop = self.ctx.hop
-        wav = torch.empty(n, T * hop, device=self.dev)
+        wav = torch.empty(n, self.output_ld or T * hop, device=self.dev)
         pre = torch.empty(n, T * hop, device=self.dev)
         cpre = torch.empty(n, T, c.voc_initial_channel, device=self.dev)
         ups, outs, ch_, rate = [], [], c.voc_initial_channel, 1
@@ -305,6 +361,7 @@ class Streams:
                 t.stage_out[i] = outs[-1].data_ptr()
         _lib.check(self.lib.conan_hifigan_step_taps(self.h, p, n, T, _ptr(mel), _ptr(wav), _ptr(pre), C.byref(t), _stream()))
         self._release()
+        wav = self._wav_rows(wav, n)
         return (wav, pre, cpre, ups, outs) if stage_out else (wav, pre, cpre, ups)
 
     def hifigan_step(self, slots, mel, want_pre_tanh=False, out=None):
@@ -314,10 +371,11 @@ class Streams:
         mel = mel.to(self.dev, torch.float32).contiguous()
         T = mel.shape[1]
         hop = self.ctx.hop
-        wav = out if out is not None else torch.empty(n, T * hop, device=self.dev)
+        wav = out if out is not None else torch.empty(n, self.output_ld or T * hop, device=self.dev)
         pre = torch.empty(n, T * hop, device=self.dev) if want_pre_tanh else None
         _lib.check(self.lib.conan_hifigan_step(self.h, p, n, T, _ptr(mel), _ptr(wav), _ptr(pre), _stream()))
         self._release()
+        wav = self._wav_rows(wav, n)
         return (wav, pre) if want_pre_tanh else wav
 
     def step(self, slots, mel_chunk, emit=None, codes=None, mel_out=None, wav_out=None):
@@ -331,10 +389,10 @@ class Streams:
         if mel_out is None:
             mel_out = torch.empty(n, emit, self.ctx.cfg.num_mels, device=self.dev)
         if wav_out is None:
-            wav_out = torch.empty(n, emit * hop, device=self.dev)
+            wav_out = torch.empty(n, self.output_ld or emit * hop, device=self.dev)
         _lib.check(self.lib.conan_step(self.h, p, n, emit, _ptr(mel_chunk), _ptr(codes), _ptr(mel_out), _ptr(wav_out), _stream()))
         self._release()
-        return codes, mel_out, wav_out
+        return codes, mel_out, self._wav_rows(wav_out, n)
 
     def step_async(self, slots, mel_chunk, wav_out, emit=None, codes=None, mel_out=None, out_fence=None):
         """Pipelined chunk step (conan_step_async): returns at once; the front-end of the next call overlaps this
@@ -346,7 +404,7 @@ class Streams:
         emit = self.seg if emit is None else int(emit)
         mel_chunk = mel_chunk.to(self.dev, torch.float32).contiguous()
         assert mel_chunk.shape == (n, self.seg + self.rc, self.ctx.cfg.emf_input_dim), mel_chunk.shape
-        assert wav_out.is_cuda and wav_out.is_contiguous() and wav_out.numel() >= n * emit * self.ctx.hop
+        assert wav_out.is_cuda and wav_out.is_contiguous() and wav_out.numel() >= n * (self.output_ld or emit * self.ctx.hop)
         self._keep.append((mel_chunk, wav_out, codes, mel_out))
         if out_fence is not None:
             if isinstance(out_fence, torch.cuda.Event):      # an event recorded behind the one operation that read wav_out
@@ -377,7 +435,7 @@ class Streams:
         if mel_out is None:
             mel_out = torch.empty(n, self.seg, nm, device=self.dev)
         if wav_out is None:
-            wav_out = torch.empty(n, self.seg * hop, device=self.dev)
+            wav_out = torch.empty(n, self.output_ld or self.seg * hop, device=self.dev)
         mc = mel_cfg(**(mel or {}))
         emit = C.c_int32(0)
         fn = self.lib.conan_step_wav_async if pipelined else self.lib.conan_step_wav
@@ -388,7 +446,11 @@ class Streams:
         if not pipelined:
             self._release()
         e = emit.value
-        return e, codes, mel_out.view(-1)[:n * e * nm].view(n, e, nm), wav_out.view(-1)[:n * e * hop].view(n, e * hop)
+        if self.output_rates or self.output_ld:
+            w = self._wav_rows(wav_out, n, self.output_ld or e * hop) if e else [wav_out.view(-1)[:0]] * n
+        else:
+            w = wav_out.view(-1)[:n * e * hop].view(n, e * hop)
+        return e, codes, mel_out.view(-1)[:n * e * nm].view(n, e, nm), w
 
     def step_wav_ragged(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None):
         """Waveform-in chunk step for slots at different positions of their utterances (conan_step_wav_ragged): slot i takes the
@@ -422,7 +484,7 @@ class Streams:
         if mel_out is None:
             mel_out = torch.empty(n, self.seg, nm, device=self.dev)
         if wav_out is None:
-            wav_out = torch.empty(n, L, device=self.dev)
+            wav_out = torch.empty(n, self.output_ld or L, device=self.dev)
         mc = mel_cfg(**(mel or {}))
         emit = (C.c_int32 * n)()
         if pipelined:

@@ -420,6 +420,39 @@ int conan_step_wav_ragged_ld_async(conan_streams* s, const int32_t* slots, int n
                                    const float* wav_dev, int64_t wav_ld, const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev,
                                    float* wav_out_dev, int32_t* emit_out, void* stream);
 
+/* Output sample rates other than the model rate (added within ABI 9: a caller detects it by the exported symbols).  The slots'
+ * audio leaves at cfg->out_rate, resampled on the GPU behind the vocoder with conan_resample's filter and a history of its own per
+ * slot; streamed output plus flush equals conan_resample of the model-rate audio bit for bit.  cfg->in_rate must be the model rate
+ * (hop * 50).  Filter fields and limits are conan_resample's.  Every slot must be at the start of its vocoder stream (no frame
+ * since its last reset that included CONAN_MODEL_HIFIGAN), else CONAN_ERR_STATE.  On any error no slot changes.  The rate persists
+ * across resets.  A reset that includes CONAN_MODEL_HIFIGAN restarts the resampler (output index 0, inputs before the first are
+ * zero).  in_rate == out_rate restores the model-rate path for those slots.  The first call with a real rate allocates a history
+ * ring per slot (CONAN_RESAMPLE_MAX_TAPS + max_frames * hop floats, rounded up to a power of two), which
+ * conan_streams_state_bytes counts from then on.
+ * The rate applies to wav_out_dev of every entry point that writes it (conan_hifigan_step[_taps], conan_step[_async],
+ * conan_step_wav[_async], conan_step_wav_ragged[_ld][_async]); pre_tanh_dev, the taps, mel_out_dev and codes_dev stay at the model
+ * rate.  A step that gives a slot e frames adds e * hop model-rate samples to its total I; the row receives outputs
+ * [delivered, ready(I)), the longest prefix of outputs whose last tap has arrived.  So the first step is short by the filter's
+ * look-ahead (hann: 6 output samples at 8 kHz, 18 at 48 kHz, 36 at 96 kHz; kaiser_best: 67 / 202 / 405; at most 8.4 ms), every
+ * later step delivers e * hop * out_rate / in_rate samples (its floor or ceiling when that is no whole number), and
+ * conan_streams_flush_output delivers the tail.  Slots of one call may mix rates, filters and no rate; a slot's samples never
+ * depend on the other slots of the call.  One more launch per vocoder step that has a row with a rate. */
+int conan_streams_set_output_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg);
+/* Row stride, in floats, of wav_out_dev in EVERY step entry point from now on.  0 (the default) = each entry point's stride of
+ * today (frames * hop, or seg * hop for the ragged wav-in steps).  A call in which some row needs more samples than the stride in
+ * force is CONAN_ERR_INVALID before anything changes (the input side's wav_ld rule). */
+int conan_streams_set_output_ld(conan_streams* s, int64_t ld);
+/* Host only.  Samples written to each row of wav_out_dev by the most recent step call, in call order.  Known when the call
+ * returns, also for pipelined calls.  Returns the row count.  Rows without a rate: frames * hop. */
+int conan_streams_output_samples(conan_streams* s, int32_t* counts, int cap);
+/* Host only.  What conan_streams_flush_output would deliver for these slots now (0 for a slot without a rate). */
+int conan_streams_output_pending(conan_streams* s, const int32_t* slots, int n, int32_t* counts);
+/* End of utterance.  Row i receives slot i's remaining outputs, up to conan_resample_length(cfg, samples produced), with the
+ * taps past the end reading zeros, as the whole-signal kernel pads.  Joins pending pipelined work first, then runs on `stream`.
+ * wav_ld below a pending count is CONAN_ERR_INVALID with nothing changed.  A flushed slot refuses further steps with
+ * CONAN_ERR_STATE until a reset that includes CONAN_MODEL_HIFIGAN. */
+int conan_streams_flush_output(conan_streams* s, const int32_t* slots, int n, float* wav_out_dev, int64_t wav_ld, void* stream);
+
 /* Measurement hook (replaces the reference's Timer('hifigan') around the vocoder forward,
  * utils/commons/meters.py:21-42, tasks/tts/vocoder_infer/hifigan.py:28): between begin and end every
  * launch of the conv_mfma kernel family is bracketed by HIP events on its launch stream.  end() waits

@@ -1,0 +1,537 @@
+"""Output sample rates other than the model rate (conan_streams_set_output_rate, _set_output_ld, _output_samples, _output_pending,
+_flush_output) on the GPU: streamed output plus flush bit-identical to conan_resample of the model-rate audio (whose float64
+accuracy tests/test_gpu_stream_wav_resample.py::test_whole_signal_against_float64 holds under resample_ref.bound, so no tolerance
+appears here), per-call counts equal to the schedule restated in tests/test_out_rate_cpu.py, one resample_out_kernel launch per
+vocoder step with a rate row and none on stream-sets without a rate, mixed calls, atomic errors, resets, and the file runner."""
+import ctypes as C
+import json
+
+import numpy as np
+import pytest
+import torch
+
+from conan_amd import _lib, configs, synth
+from conan_amd.engine import StreamingVoiceConversionEngine
+from tests import resample_ref
+from tests.conftest import ARITHS
+from tests.test_gpu_stream_wav import HOP, L, SEG, ctx  # noqa: F401  (ctx: module fixture)
+from tests.test_gpu_stream_wav_resample import _equal, _lin, _ref, _sig
+from tests.test_out_rate_cpu import out_filter, schedule
+
+pytestmark = pytest.mark.gpu
+
+FIXED = _lib.STREAMS_FIXED_PLAN
+RO = "resample_out_kernel"
+RATES = (8000, 11025, 22050, 44100, 48000)
+SENTINEL = 7.0
+
+
+def _mel(B, T, seed):
+    return torch.from_numpy(np.stack([synth.mel(T, seed + i)[0] for i in range(B)])).cuda()
+
+
+def _length(rate, n):
+    return resample_ref.length(16000, rate, n)
+
+
+# ---- 1. streaming = whole signal, bit for bit
+def _stream_cases():
+    out = []
+    for rate in RATES:
+        for preset in ("hann", "kaiser_best"):
+            for arith in (ARITHS if (rate, preset) == (48000, "hann") else ARITHS[:1]):
+                for B in ((1, 4, 64) if (rate, preset) == (48000, "hann") else (1, 4)):
+                    out.append((rate, preset, arith, B))
+    return out
+
+
+@pytest.mark.parametrize("rate,preset,arith,B", _stream_cases())
+def test_stream_equals_whole_signal(ctx, rate, preset, arith, B):
+    """Engine A has no output rate, engine B has one: B's steps plus flush are ctx.resample of A's audio, mel and codes are A's."""
+    a = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64, arith=arith)
+    b = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64, arith=arith)
+    ref = _ref(B)
+    for j, N in enumerate((L // 2, 2 * L + 1, 16000 + 17) if B < 64 else (3 * L + 5,)):
+        src = _sig(B, N, 16000, 60 + j)
+        src_mel = ctx.wav2mel(src)
+        for pipelined in (False, True):
+            for mel_in in (True, False):
+                if mel_in:
+                    wa, ma, ca = a.infer(src_mel, ref, pipelined=pipelined)
+                    wb, mb, cb = b.infer(src_mel, ref, pipelined=pipelined, out_rate=rate, out_filter={"preset": preset})
+                else:
+                    wa, ma, ca = a.infer_wav(src, ref, pipelined=pipelined)
+                    wb, mb, cb = b.infer_wav(src, ref, pipelined=pipelined, out_rate=rate, out_filter={"preset": preset})
+                torch.cuda.synchronize()
+                what = (rate, preset, arith, B, N, pipelined, mel_in)
+                assert torch.equal(ma, mb) and torch.equal(ca, cb), what
+                assert wb.shape == (B, _length(rate, wa.shape[1])), what
+                assert torch.equal(wb, ctx.resample(wa, 16000, rate, preset=preset)), what
+
+
+@pytest.mark.parametrize("rate,preset", [(48000, "hann"), (44100, "kaiser_best"), (8000, "kaiser_best")])
+def test_long_utterance_wraps_the_ring(ctx, rate, preset):
+    """160 frames = 51200 model-rate samples: more than three times the 16384-sample history ring of a 4-frame stream-set."""
+    B = 2
+    a = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64)
+    b = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64)
+    src_mel, ref = _mel(B, 160, 900), _ref(B)
+    for pipelined in (False, True):
+        wa, ma, ca = a.infer(src_mel, ref, pipelined=pipelined)
+        wb, mb, cb = b.infer(src_mel, ref, pipelined=pipelined, out_rate=rate, out_filter={"preset": preset})
+        torch.cuda.synchronize()
+        assert wa.shape[1] == 51200 and torch.equal(ma, mb) and torch.equal(ca, cb)
+        assert torch.equal(wb, ctx.resample(wa, 16000, rate, preset=preset)), (rate, preset, pipelined)
+
+
+# ---- 2. per-call counts; 1- to 4-frame vocoder steps
+def _voc_run(st, slots, mel, sizes, ld=None):
+    """conan_hifigan_step over `mel` in steps of sizes[k % len] frames into sentinel-filled buffers -> (rows per call, counts per call)."""
+    n, T = mel.shape[0], mel.shape[1]
+    pos, k, rows, counts = 0, 0, [], []
+    while pos < T:
+        f = min(sizes[k % len(sizes)], T - pos)
+        buf = torch.full((n, ld or f * HOP), SENTINEL, device="cuda")
+        st.hifigan_step(slots, mel[:, pos:pos + f], out=buf)
+        cnt = st.output_samples()
+        torch.cuda.synchronize()
+        for i in range(n):
+            assert bool((buf[i, cnt[i]:] == SENTINEL).all()), (pos, i, cnt)      # nothing past the count is touched
+        rows.append([buf[i, :cnt[i]].clone() for i in range(n)])
+        counts.append((f, cnt))
+        pos, k = pos + f, k + 1
+    return rows, counts
+
+
+@pytest.mark.parametrize("preset", ["hann", "kaiser_best"])
+@pytest.mark.parametrize("rate", RATES)
+def test_vocoder_steps_counts_and_bits(ctx, rate, preset):
+    """conan_hifigan_step with 1 .. 4 frames per step: every call's counts equal the restated schedule (the first is short by the
+    look-ahead, steady calls deliver frames * hop * new / orig or its floor / ceiling), output_pending equals the flush's delivery,
+    and steps plus flush equal conan_resample of the model-rate run."""
+    n, T = 3, 41
+    mel = _mel(n, T, 300)
+    slots = [2, 0, 1]
+    f = out_filter(rate, preset)
+    orig, new = f[0], f[1]
+    plain = ctx.streams(3, max_frames=4, max_ref_frames=4)
+    for sizes in ((1,), (2,), (4,), (1, 2, 3, 4)):
+        plain.reset(slots, which=4)
+        wa = torch.stack([torch.cat(r) for r in zip(*_voc_run(plain, slots, mel, sizes)[0])])      # the model-rate run, same steps
+        assert wa.shape == (n, T * HOP)
+        st = ctx.streams(3, max_frames=4, max_ref_frames=4)
+        st.reset(slots, which=4)
+        st.set_output_rate(slots, rate, preset=preset)
+        st.set_output_ld(_length(rate, 4 * HOP) + 2)
+        rows, counts = _voc_run(st, slots, mel, sizes, ld=st.output_ld)
+        want, tail = schedule(f, [fr * HOP for fr, _ in counts])
+        assert [c for _, c in counts] == [[w] * n for w in want], (rate, preset, sizes)
+        for (fr, c), k in zip(counts[1:], range(1, len(counts))):
+            exact = fr * HOP * new
+            assert c[0] in (exact // orig, -(-exact // orig)), (rate, preset, sizes, k)
+        assert want[0] < -(-counts[0][0] * HOP * new // orig)                     # short by the look-ahead
+        if (rate, sizes) == (11025, (1,)):
+            assert set(w for w in want[1:]) == {220, 221}
+        assert st.output_pending(slots) == [tail] * n and tail > 0
+        last = st.flush_output(slots)
+        assert [t.shape[0] for t in last] == [tail] * n
+        assert st.output_pending(slots) == [0] * n
+        torch.cuda.synchronize()
+        got = torch.stack([torch.cat([r[i] for r in rows] + [last[i]]) for i in range(n)])
+        assert got.shape[1] == _length(rate, T * HOP)
+        assert torch.equal(got, ctx.resample(wa, 16000, rate, preset=preset)), (rate, preset, sizes)
+        st.close()
+    plain.close()
+
+
+# ---- 3. launch counts
+def _profiled(st, fn):
+    st.profile_begin()
+    out = fn()
+    st.profile_end()
+    return out, {k[0]: k[3] for k in st.profile_kernels()}
+
+
+def test_one_launch_per_vocoder_step(ctx):
+    B = 2
+    eng = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64)
+    src_mel, ref = _mel(B, 4 * SEG + 2, 40), _ref(B)
+    eng.start(ref, out_rate=48000)
+    for _, emit, chunk in eng.chunks(src_mel):
+        _, ks = _profiled(eng.st, lambda: eng.st.step(eng.slots, chunk, emit=emit))
+        assert ks.get(RO) == 1, ks
+    _, ks = _profiled(eng.st, eng.finish)
+    assert ks == {RO: 1}, ks
+    _, ks = _profiled(eng.st, eng.finish)              # nothing pending: no launch, no error
+    assert ks == {}, ks
+    # a mixed call: still one launch
+    with pytest.raises(ValueError):
+        eng.start(ref, out_rate=[44100, None])          # one [B, count] block per feed / infer: one rate
+    eng.open_slots(eng.slots, ref, out_rate=[44100, None], out_filter={"preset": "kaiser_best"})
+    _, ks = _profiled(eng.st, lambda: eng.st.step(eng.slots, next(eng.chunks(src_mel))[2]))
+    assert ks.get(RO) == 1, ks
+
+
+def test_set_without_rate_launches_as_before(ctx):
+    """A stream-set that never sets an output rate makes no resample_out_kernel launch and keeps its state size; its kernels, bits
+    and state bytes are those of a set that sets the model rate (in_rate == out_rate)."""
+    a = StreamingVoiceConversionEngine(ctx, 2, max_ref_frames=64)
+    b = StreamingVoiceConversionEngine(ctx, 2, max_ref_frames=64)
+    c = StreamingVoiceConversionEngine(ctx, 2, max_ref_frames=64)
+    bytes0 = a.st.state_bytes
+    assert b.st.state_bytes == bytes0
+    src = _sig(2, 3 * L + 11, 16000, 5)
+
+    def run(eng, rate):
+        return _profiled(eng.st, lambda: eng.infer_wav(src, _ref(2), pipelined=False, out_rate=rate))
+
+    (wa, ka), (wb, kb), (wc, kc) = run(a, None), run(b, 16000), run(c, 48000)
+    assert RO not in ka and RO not in kb and kc.get(RO, 0) > 0
+    assert ka == kb and _equal(wa, wb)
+    assert {k: v for k, v in kc.items() if k != RO} == ka and _equal(wa[1:], wc[1:])
+    assert a.st.state_bytes == bytes0 and b.st.state_bytes == bytes0 and not b.st.output_rates and b.st.output_ld == 0
+    assert c.st.state_bytes == bytes0 + 2 * 16384 * 4
+    assert a.st.output_samples() == b.st.output_samples()
+
+
+def test_ragged_staged_call_places_audio_with_the_kernel(ctx):
+    """A ragged call whose slots do not all emit a full chunk stages its outputs.  With a rate row the audio is placed by the one
+    resample_out_kernel launch of the call's vocoder step (the scatter launch keeps the codes and the mel); without one the call
+    runs as before.  The rows equal those of each slot stepped alone; a row that emits nothing is left untouched."""
+    refs = _ref(2)
+    x = _sig(2, 3 * L, 16000, 77)
+    ld = _length(48000, L) + 2
+
+    def run(rate0, together):
+        eng = StreamingVoiceConversionEngine(ctx, 2, max_ref_frames=64)
+        eng.open_slots([0, 1], refs, out_rate=[rate0, None])
+        st = eng.st
+        st.step_wav_ragged([0], x[:1, :L], [L], [0])                       # slot 0 one call ahead
+        out = torch.full((2, st.output_ld or L), SENTINEL, device="cuda")
+        if together:
+            (emit, _, _, _), ks = _profiled(st, lambda: st.step_wav_ragged([0, 1], torch.stack([x[0, L:2 * L], x[1, :L]]), [L, L], [0, 0], wav_out=out))
+        else:
+            (emit, _, _, _), ks = _profiled(st, lambda: st.step_wav_ragged([0], x[:1, L:2 * L], [L], [0], wav_out=out))
+            emit = emit + [0]
+        cnt = st.output_samples()
+        torch.cuda.synchronize()
+        return emit, cnt + [0] * (2 - len(cnt)), out, ks
+
+    emit, cnt, out, ks = run(48000, True)
+    _, cnt1, out1, _ = run(48000, False)
+    assert emit == [SEG, 0] and cnt == [cnt1[0], 0] and 0 < cnt[0] < _length(48000, L)
+    assert ks.get(RO) == 1 and ks.get("wav_rows_scatter_kernel") == 1, ks
+    assert out.shape[1] == ld and torch.equal(out[0], out1[0]) and bool((out[0, cnt[0]:] == SENTINEL).all())
+    assert bool((out[1] == SENTINEL).all())
+    emit, cnt, out, ks = run(None, True)
+    assert emit == [SEG, 0] and cnt == [L, 0] and RO not in ks and ks.get("wav_rows_scatter_kernel") == 1, (emit, cnt, ks)
+    assert bool((out[1] == SENTINEL).all())
+
+
+def _ragged_run(st, slots, utts):
+    """Utterances that all start at tick 0, one conan_step_wav_ragged call per tick -> (audio per utterance from the reported
+    counts, whether some call stepped two emit groups)."""
+    n = len(utts)
+    pos, fin, done, outs, two = [0] * n, [False] * n, [False] * n, [[] for _ in range(n)], False
+    while not all(done):
+        live = [i for i in range(n) if not done[i]]
+        rows, samples, final, was = [], [], [], [fin[i] for i in range(n) if not done[i]]
+        for i in live:
+            x = utts[i]
+            N = x.shape[0]
+            last = (N - 1) // L * L
+            if pos[i] < last:
+                piece, pos[i] = x[pos[i]:pos[i] + L], pos[i] + L
+                final.append(0)
+            else:
+                piece, pos[i], fin[i] = (x[pos[i]:] if not fin[i] else x[:0]), N, True
+                final.append(1)
+            samples.append(piece.shape[0])
+            rows.append(torch.nn.functional.pad(piece, (0, L - piece.shape[0])))
+        out = torch.full((len(live), st.output_ld or L), SENTINEL, device="cuda")
+        emit, _, _, _ = st.step_wav_ragged([slots[i] for i in live], torch.stack(rows), samples, final, wav_out=out)
+        cnt = st.output_samples()
+        torch.cuda.synchronize()
+        two = two or len({e for e in emit if e}) > 1
+        assert cnt == [e * HOP for e in emit]
+        for k, i in enumerate(live):
+            assert bool((out[k, cnt[k]:] == SENTINEL).all())
+            if emit[k]:
+                outs[i].append(out[k, :cnt[k]].clone())
+            elif was[k]:
+                done[i] = True
+    return [torch.cat(o) for o in outs], two
+
+
+def test_stride_without_rates_in_a_call_with_two_emit_groups(ctx):
+    """conan_streams_set_output_ld(seg * hop) and no rate anywhere: a ragged call with a full and a short emit group writes what
+    the same call writes at ld = 0, every row in its call-order row."""
+    utts = [_sig(1, 5 * L, 16000, 81)[0], _sig(1, 2 * L + 700, 16000, 82)[0], _sig(1, 3 * L + 50, 16000, 83)[0]]
+    refs = _ref(3)
+    res = []
+    for ld in (0, L, L + 64):
+        eng = StreamingVoiceConversionEngine(ctx, 3, max_ref_frames=64)
+        eng.open_slots([0, 1, 2], refs)
+        eng.st.set_output_ld(ld)
+        wavs, two = _ragged_run(eng.st, [0, 1, 2], utts)
+        assert two
+        res.append(wavs)
+    assert _equal(res[0], res[1]) and _equal(res[0], res[2])
+    assert [w.shape[0] for w in res[0]] == [(1 + u.shape[0] // HOP) * HOP for u in utts]
+
+
+@pytest.mark.parametrize("pipelined", [False, True])
+def test_low_rate_beside_slots_without_rate(ctx, pipelined):
+    """Output rates at or below the model rate leave the engine's stride at seg * hop: a slot without a rate that ends with a short
+    chunk beside another one (a staged call) still equals its solo run, as does the 8 kHz slot."""
+    srcs = [_sig(1, 6 * L, 16000, 91)[0], _sig(1, 2 * L + 700, 16000, 92)[0], _sig(1, 4 * L + 100, 16000, 93)[0]]
+    orates, refs = [8000, None, None], _ref(3, 9)
+    eng = StreamingVoiceConversionEngine(ctx, 4, max_ref_frames=64, flags=FIXED)
+    outs = eng.infer_wav_staggered(srcs, [0, 0, 1], refs, pipelined=pipelined, out_rates=orates)
+    torch.cuda.synchronize()
+    assert eng.st.output_ld == L
+    solo = StreamingVoiceConversionEngine(ctx, 4, max_ref_frames=64, flags=FIXED)
+    for u in range(3):
+        solo.slots = [eng.staggered_slots[u]]
+        w, m, c = solo.infer_wav(srcs[u][None], refs[u][None], pipelined=False, out_rate=orates[u])
+        torch.cuda.synchronize()
+        assert _equal(outs[u], (w[0], m[0], c[0])), (u, pipelined)
+
+
+# ---- 4. mixed calls
+def _staggered_inputs(U, seed):
+    rng = np.random.default_rng(seed)
+    pool = [8000, 11025, 22050, 24000, 32000, 44100, 48000]
+    rates = [None if u % 4 == 0 else int(rng.choice(pool)) for u in range(U)]
+    orates = [None if u % 3 == 1 else int(rng.choice(pool + [96000])) for u in range(U)]
+    srcs = [_sig(1, int(rng.integers((r or 16000) // 10, (r or 16000) // 2 + 2 * _lin(r or 16000))), r or 16000, 100 + u)[0] for u, r in enumerate(rates)]
+    starts = sorted(int(v) for v in rng.integers(0, 10, U))
+    return rates, orates, srcs, starts
+
+
+@pytest.mark.parametrize("pipelined", [False, True])
+def test_staggered_mixed_rates_equal_solo(ctx, pipelined):
+    U, B = 28, 16
+    rates, orates, srcs, starts = _staggered_inputs(U, 13)
+    refs = _ref(U, 5)
+    filt = {"preset": "kaiser_best"}
+    eng = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64, flags=FIXED)
+    outs = eng.infer_wav_staggered(srcs, starts, refs, pipelined=pipelined, in_rates=rates, out_rates=orates, out_filter=filt)
+    torch.cuda.synchronize()
+    used = eng.staggered_slots
+    reused = {}
+    for u, s in enumerate(used):
+        reused.setdefault(s, []).append(orates[u])
+    assert any(len(set(v)) > 1 for v in reused.values()), "no slot was reused with another output rate"
+    solo = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64, flags=FIXED)
+    for u in range(U):
+        solo.slots = [used[u]]
+        w, m, c = solo.infer_wav(srcs[u][None], refs[u][None], pipelined=False, in_rate=rates[u], out_rate=orates[u], out_filter=filt)
+        torch.cuda.synchronize()
+        assert _equal(outs[u], (w[0], m[0], c[0])), (u, rates[u], orates[u], pipelined)
+        if orates[u]:
+            assert w.shape[1] == _length(orates[u], m.shape[1] * HOP)
+
+
+def test_fixed_plan_slot_independent_of_active_slots(ctx):
+    """CONAN_STREAMS_FIXED_PLAN: the chosen slot's whole stream is bit-identical with 64, 20 or 1 active slots around it."""
+    B = 64
+    eng = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64, flags=FIXED)
+    pool = [48000, None, 8000, 44100, 22050]
+    srcs = [_sig(1, 2 * L + 300 + 16 * u, 16000, 200 + u)[0] for u in range(B)]
+    refs = _ref(B, 7)
+    got = []
+    for active in (64, 20, 1):
+        orates = [pool[u % len(pool)] for u in range(active)]
+        outs = eng.infer_wav_staggered(srcs[:active], [0] * active, refs[:active], pipelined=True, out_rates=orates)
+        torch.cuda.synchronize()
+        assert eng.staggered_slots[0] == 0
+        got.append(tuple(t.clone() for t in outs[0]))
+    assert got[0][0].shape[0] == _length(48000, got[0][1].shape[0] * HOP)
+    assert _equal(got[0], got[1]) and _equal(got[0], got[2])
+
+
+# ---- 5. errors leave every slot unchanged
+def test_errors_leave_slots_unchanged(ctx):
+    rate, B = 48000, 2
+    src_mel, ref = _mel(B, 5 * SEG + 1, 50), _ref(B)
+    ld = _length(rate, L) + 2
+
+    def run(eng, hook=None):
+        eng.start(ref, out_rate=rate)
+        rows = []
+        for k, (_, emit, chunk) in enumerate(eng.chunks(src_mel)):
+            if hook:
+                hook(k, chunk)
+            _, _, w = eng.st.step(eng.slots, chunk, emit=emit)
+            rows.append(torch.stack(w))
+        return rows
+
+    clean = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64)
+    want = torch.cat(run(clean) + [torch.stack(clean.finish())], 1)
+
+    eng = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64)
+    lib, h = eng.st.lib, eng.st.h
+    slots = (C.c_int32 * B)(*eng.slots)
+
+    def expect(rc, code):
+        assert rc == code, (rc, code, lib.conan_last_error())
+
+    def hook(k, chunk):
+        if k != 2:
+            return
+        # a rate set mid-utterance
+        expect(lib.conan_streams_set_output_rate(h, slots, B, C.byref(_lib.resample_cfg(16000, 44100))), _lib.ERR_STATE)
+        # in_rate not the model rate; invalid filters
+        bad = [_lib.resample_cfg(22050, rate), _lib.resample_cfg(16000, rate, lowpass_filter_width=0), _lib.resample_cfg(16000, rate, lowpass_filter_width=129),
+               _lib.resample_cfg(16000, rate, rolloff=0.0), _lib.resample_cfg(16000, 7999)]
+        r = _lib.resample_cfg(16000, rate)
+        r.reserved[1] = 1
+        for cfg in bad + [r]:
+            expect(lib.conan_streams_set_output_rate(h, slots, B, C.byref(cfg)), _lib.ERR_INVALID)
+        # a 48 kHz slot with ld = 0: the step's own stride (emit * hop) is too small
+        out = torch.full((B, ld), SENTINEL, device="cuda")
+        eng.st.set_output_ld(0)
+        for fn in (lib.conan_step, lib.conan_step_async):
+            expect(fn(h, slots, B, SEG, C.c_void_p(chunk.data_ptr()), None, None, C.c_void_p(out.data_ptr()), None), _lib.ERR_INVALID)
+        mel = torch.zeros(B, SEG, 80, device="cuda")
+        expect(lib.conan_hifigan_step(h, slots, B, SEG, C.c_void_p(mel.data_ptr()), C.c_void_p(out.data_ptr()), None, None), _lib.ERR_INVALID)
+        eng.st.set_output_ld(ld)
+        torch.cuda.synchronize()
+        assert bool((out == SENTINEL).all())
+
+    got = run(eng, hook)
+    pend = eng.st.output_pending(eng.slots)
+    assert pend == [pend[0]] * B and pend[0] > 0
+    # a flush with wav_ld below the pending count
+    small = torch.full((B, pend[0] - 1), SENTINEL, device="cuda")
+    expect(lib.conan_streams_flush_output(h, slots, B, C.c_void_p(small.data_ptr()), pend[0] - 1, None), _lib.ERR_INVALID)
+    assert eng.st.output_pending(eng.slots) == pend
+    tail = torch.stack(eng.finish())
+    torch.cuda.synchronize()
+    assert bool((small == SENTINEL).all())
+    assert torch.equal(torch.cat(got + [tail], 1), want)
+    # a step after the flush; a flush while nothing is pending
+    chunk = next(eng.chunks(src_mel))[2]
+    out = torch.empty(B, ld, device="cuda")
+    expect(lib.conan_step(h, slots, B, SEG, C.c_void_p(chunk.data_ptr()), None, None, C.c_void_p(out.data_ptr()), None), _lib.ERR_STATE)
+    assert eng.st.output_pending(eng.slots) == [0] * B
+    assert [t.shape[0] for t in eng.finish()] == [0] * B
+    # the slots still serve: the next utterance equals the clean run
+    assert torch.equal(torch.cat(run(eng) + [torch.stack(eng.finish())], 1), want)
+
+
+def test_wav_in_errors_leave_front_end_unchanged(ctx):
+    """A stride error in conan_step_wav / conan_step_wav_ragged changes neither the front-end nor the vocoder: the utterance goes
+    on and equals the run without the error."""
+    from conan_amd.runtime import mel_cfg
+    rate, B = 48000, 2
+    src, ref = _sig(B, 4 * L + 123, 16000, 33), _ref(B)
+    clean = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64)
+    want = clean.infer_wav(src, ref, pipelined=False, out_rate=rate)
+    eng = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64)
+    eng.start_wav(ref, out_rate=rate)
+    lib, h, ld = eng.st.lib, eng.st.h, eng.st.output_ld
+    slots, mc = (C.c_int32 * B)(*eng.slots), mel_cfg()
+    wavs, mels, codes = [], [], []
+    for k in range(4):
+        piece = src[:, k * L:(k + 1) * L].contiguous()
+        if k == 2:          # this call emits a chunk: 3840 samples per row do not fit the steps' own stride
+            out = torch.full((B, ld), SENTINEL, device="cuda")
+            eng.st.set_output_ld(0)
+            e = C.c_int32(5)
+            rc = lib.conan_step_wav(h, slots, B, L, 0, C.c_void_p(piece.data_ptr()), C.byref(mc), None, None, C.c_void_p(out.data_ptr()), C.byref(e), None)
+            assert rc == _lib.ERR_INVALID, lib.conan_last_error()
+            sm, fi, em = (C.c_int32 * B)(L, L), (C.c_int32 * B)(0, 0), (C.c_int32 * B)()
+            rc = lib.conan_step_wav_ragged(h, slots, B, sm, fi, C.c_void_p(piece.data_ptr()), C.byref(mc), None, None, C.c_void_p(out.data_ptr()), em, None)
+            assert rc == _lib.ERR_INVALID, lib.conan_last_error()
+            eng.st.set_output_ld(ld)
+            torch.cuda.synchronize()
+            assert bool((out == SENTINEL).all())
+        w, m, c = eng.feed(piece)
+        wavs, mels, codes = wavs + [w], mels + [m], codes + [c]
+    fin = False
+    while True:
+        w, m, c = eng.feed(src[:, 4 * L:] if not fin else src[:, :0], final=True)
+        if fin and m.shape[1] == 0:
+            break
+        fin = True
+        wavs, mels, codes = wavs + [w], mels + [m], codes + [c]
+    got = (torch.cat(wavs + [torch.stack(eng.finish())], 1), torch.cat(mels, 1), torch.cat(codes, 1))
+    torch.cuda.synchronize()
+    assert _equal(got, want)
+
+
+# ---- 6. resets
+@pytest.mark.parametrize("rate,preset", [(44100, "kaiser_best"), (8000, "hann")])
+def test_reset_keeps_rate_and_restarts_output(ctx, rate, preset):
+    B = 2
+    ma, mb, ref = _mel(B, 3 * SEG + 3, 60), _mel(B, 4 * SEG, 61), _ref(B)
+
+    def utterance(eng, src_mel):
+        rows = [torch.stack(eng.st.step(eng.slots, chunk, emit=emit)[2]) for _, emit, chunk in eng.chunks(src_mel)]
+        return torch.cat(rows + [torch.stack(eng.finish())], 1)
+
+    eng = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64)
+    eng.start(ref, out_rate=rate, out_filter={"preset": preset})
+    utterance(eng, ma)
+    eng.st.reset(eng.slots, which=7)                  # a reset with CONAN_MODEL_HIFIGAN, no new set_output_rate
+    eng.st.set_reference(eng.slots, ref)
+    got = utterance(eng, mb)
+    fresh = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64)
+    fresh.start(ref, out_rate=rate, out_filter={"preset": preset})
+    want = utterance(fresh, mb)
+    torch.cuda.synchronize()
+    assert got.shape[1] == _length(rate, 4 * SEG * HOP) and torch.equal(got, want)
+
+
+def test_windowed_step_refuses_output_rates(ctx):
+    eng = StreamingVoiceConversionEngine(ctx, 1, max_ref_frames=64)
+    eng.start(_ref(1), out_rate=48000)
+    with pytest.raises(ValueError):
+        eng.windowed_step(next(eng.chunks(_mel(1, 8, 1)))[2], None)
+
+
+# ---- 7. file runner
+def test_file_runner_writes_at_the_output_rate(ctx, tmp_path):
+    """hparams output_sample_rate: 48000 -> 48 kHz files whose samples are ctx.resample (the runner's filter) of the 16 kHz
+    conversion's samples after the same int16 conversion; batch and one-by-one conversions agree."""
+    from scipy.io import wavfile
+    from conan_amd.inference.Conan import StreamingVoiceConversion
+    from conan_amd.inference.run_voice_conversion import VoiceConversionRunner
+    from conan_amd.utils.audio.io import save_wav
+    chp, vhp = configs.conan_hparams(True), configs.hifigan_hparams(True)
+    sds = {"emformer": synth.emformer_state_dict(chp, 0), "conan": synth.conan_state_dict(chp, 0), "hifigan": synth.hifigan_state_dict(vhp, 0)}
+    sr = 16000
+    rng = np.random.default_rng(5)
+    pairs = []
+    for k, (ds, dr) in enumerate(((0.50, 0.40), (0.33, 0.61))):
+        ts, tr = np.arange(int(ds * sr)) / sr, np.arange(int(dr * sr)) / sr
+        s = 0.4 * np.sin(2 * np.pi * (200 + 90 * k) * ts) + 0.02 * rng.standard_normal(ts.shape)
+        r = 0.3 * np.sin(2 * np.pi * (150 + 40 * k) * tr) * np.cos(2 * np.pi * 2 * tr)
+        save_wav(s, str(tmp_path / f"s{k}.wav"), sr)
+        save_wav(r, str(tmp_path / f"r{k}.wav"), sr)
+        pairs.append({"src_wav": str(tmp_path / f"s{k}.wav"), "ref_wav": str(tmp_path / f"r{k}.wav"), "output_name": f"out{k}.wav"})
+    cfgp = tmp_path / "pairs.json"
+    cfgp.write_text(json.dumps({"total_pairs": len(pairs), "conversion_pairs": pairs}))
+    hp48 = dict(chp, output_sample_rate=48000)
+    runner = VoiceConversionRunner(str(cfgp), hp48, vhp, sds, output_dir=str(tmp_path / "out"), streams=2)
+    assert runner.run_batch(pairs) == [str(tmp_path / "out" / f"out{k}.wav") for k in range(2)]
+    vc, rs = runner.vc, lambda w: (runner.vc.ctx.resample(w, 16000, 48000, **runner.vc.out_filter).cpu().numpy() * 32767).astype(np.int16)   # + save_wav's conversion
+    # the 16 kHz run of the same batch: the runner's own steps at the model rate
+    src, ref = [vc._wav_to_mel(p["src_wav"]) for p in pairs], [vc._wav_to_mel(p["ref_wav"]) for p in pairs]
+    T, Tr = max(m.shape[0] for m in src), max(m.shape[0] for m in ref)
+    srcb = torch.stack([torch.cat([m, m[-1:].expand(T - m.shape[0], -1)]) for m in src])
+    refb = torch.stack([torch.cat([m, m.new_zeros(Tr - m.shape[0], m.shape[1])]) for m in ref])
+    w16, _, _ = StreamingVoiceConversionEngine(vc.ctx, 2, max_ref_frames=max(256, Tr)).infer(srcb, refb, [m.shape[0] for m in ref])
+    vc16 = StreamingVoiceConversion(chp, vhp, sds)
+    for k, p in enumerate(pairs):
+        n16 = src[k].shape[0] * HOP
+        rate, got = wavfile.read(str(tmp_path / "out" / f"out{k}.wav"))
+        assert rate == 48000 and got.shape == (3 * n16,) and np.array_equal(got, rs(w16[k, :n16])), k
+        # one by one: streamed through the engine's out_rate, against the one-stream 16 kHz conversion
+        one16, _ = vc16.infer_once({"src_wav": p["src_wav"], "ref_wav": p["ref_wav"]})
+        ok, path = runner.run_single_conversion(p, k)
+        assert ok, path
+        rate, one = wavfile.read(path)
+        assert rate == 48000 and np.array_equal(one, rs(torch.from_numpy(one16))), k
