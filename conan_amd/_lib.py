@@ -106,6 +106,9 @@ _PROTOS = {
     "conan_streams_output_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "conan_streams_output_pending": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "conan_streams_flush_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "conan_streams_set_input_format": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "conan_streams_set_output_format": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "conan_convert_samples": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p]),
     "conan_streams_output_fence": (C.c_int, [C.c_void_p, C.c_void_p]),
     "conan_streams_output_fence_event": (C.c_int, [C.c_void_p, C.c_void_p]),
     "conan_streams_test_fault": (C.c_int, [C.c_void_p, C.c_int]),
@@ -178,6 +181,20 @@ RESAMPLE_PRESETS = {
     "hann": dict(lowpass_filter_width=6, rolloff=0.99, resampling_method="sinc_interp_hann", beta=None),
     "kaiser_best": dict(lowpass_filter_width=64, rolloff=0.9475937167399596, resampling_method="sinc_interp_kaiser", beta=None),
 }
+
+
+# CONAN_SAMPLE_*: the sample formats of the audio rows (conan_streams_set_input_format / _output_format, conan_convert_samples)
+SAMPLE_F32, SAMPLE_S16, SAMPLE_ULAW, SAMPLE_ALAW = 0, 1, 2, 3
+SAMPLE_FORMATS = {"f32": SAMPLE_F32, "s16": SAMPLE_S16, "ulaw": SAMPLE_ULAW, "alaw": SAMPLE_ALAW}
+SAMPLE_BYTES = {"f32": 4, "s16": 2, "ulaw": 1, "alaw": 1}
+
+
+def sample_format(fmt):
+    """CONAN_SAMPLE_* of 'f32' | 's16' | 'ulaw' | 'alaw' (None: 'f32')."""
+    fmt = "f32" if fmt is None else fmt
+    if fmt not in SAMPLE_FORMATS:
+        raise ValueError("sample format must be one of %s, got %r" % (sorted(SAMPLE_FORMATS), fmt))
+    return SAMPLE_FORMATS[fmt]
 
 
 class ResampleCfg(C.Structure):

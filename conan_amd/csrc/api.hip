@@ -182,7 +182,7 @@ int conan_streams_create_opts(conan_ctx* ctx, int max_slots, int max_frames, int
         s->d_guard = reinterpret_cast<unsigned*>(s->alloc(16));
         HIP_CHECK(hipMemcpy(s->d_guard + 2, &hdev, sizeof(hdev), hipMemcpyHostToDevice));
       }
-      s->slot_seen.assign(max_slots, 0); s->has_ref.assign(max_slots, 0); s->voc_fresh.assign(max_slots, 1); s->voc_samples.assign(max_slots, 0);
+      s->slot_seen.assign(max_slots, 0); s->has_ref.assign(max_slots, 0); s->voc_fresh.assign(max_slots, 1); s->voc_samples.assign(max_slots, 0); s->in_fmt.assign(max_slots, 0); s->out_fmt.assign(max_slots, 0);
       s->pin.init((size_t)max_slots + cnk::kSlotTablePad);
       s->pos_emf = (int*)s->alloc(max_slots); s->pos_dec = (int*)s->alloc(max_slots); s->pos_voc = (int*)s->alloc(max_slots);
       std::vector<int> id(max_slots);
@@ -549,8 +549,9 @@ int conan_step_async(conan_streams* s, const int32_t* slots, int n, int emit, co
 // Input resampler of a wav-in call (conan_streams_set_input_rate).  Per call row: the model-rate samples and final flag the front-end
 // gets - a row without a rate passes its own; a row with one hands over the longest prefix of outputs whose last tap has arrived (at
 // most seg * hop; after the input's final call, what is left, seg * hop at a time, final on the call that delivers the last sample).
-// When a row with a rate has input or owed output, one resample_stream_kernel launch writes every row's model-rate samples to
-// staging (rows without a rate copied verbatim) and the front-end reads them there.  rs_plan checks every row and changes nothing.
+// When a row with a rate has input or owed output, or a row with a sample format (conan_streams_set_input_format) has input, one
+// resample_stream_kernel launch writes every row's model-rate samples to staging (rows without a rate decoded and copied) and the
+// front-end reads them there.  rs_plan checks every row and changes nothing.
 struct RsPlan {
   std::vector<int32_t> mm, ff;          // per row: front-end samples and final flag
   std::vector<char> rate;               // per row: the slot has a rate
@@ -565,14 +566,23 @@ static RsPlan rs_plan(const conan_streams* s, const int32_t* slots, int n, const
                       long long wav_ld, const conan_mel_cfg& m, const char* who) {
   RsPlan P;
   P.mm.assign(samples, samples + n); P.ff.assign(final_, final_ + n); P.rate.assign(n, 0); P.in_after.assign(n, 0);
-  if (s->rs_slot.empty()) return P;
+  if (s->rs_slot.empty()) return P;      // (neither a rate nor a format was ever set: the caller's rows go to the front-end as they are)
   const int S = s->ctx->cfg.emf_segment * s->ctx->hop;
   P.rows.resize(n);
   for (int i = 0; i < n; ++i) {
     const conan_streams::RsSlot& r = s->rs_slot[slots[i]];
     cnk::RsRow& row = P.rows[i];
     memset(&row, 0, sizeof(row));
-    row.slot = slots[i]; row.copy = 1; row.m = samples[i]; row.h = samples[i];
+    const int fmt = s->in_fmt[slots[i]], bps = fmt == cnk::kFmtF32 ? 4 : (fmt == cnk::kFmtS16 ? 2 : 1);
+    row.slot = slots[i]; row.mode = cnk::kRsCopy | (fmt << cnk::kRsFmtShift); row.m = samples[i]; row.h = samples[i];
+    if (fmt != cnk::kFmtF32 && samples[i] > 0) {
+      if ((long long)samples[i] * bps > wav_ld * 4)
+        throw Error(CONAN_ERR_INVALID, std::string(who) + ": slot " + std::to_string(slots[i]) + ": the row holds more bytes (" + std::to_string(samples[i]) + " samples of " +
+                                           std::to_string(bps) + ") than the row stride of wav_dev (" + std::to_string(wav_ld) + " x 4 bytes)");
+      if (!wav_dev) throw Error(CONAN_ERR_INVALID, "null argument (wav_dev with samples > 0)");
+      if ((uintptr_t)wav_dev & 3) throw Error(CONAN_ERR_INVALID, std::string(who) + ": wav_dev must be 4-byte aligned");
+      if (!r.f) P.launch = true;      // a format alone: the copy rows decode into staging
+    }
     if (!r.f) continue;
     const ch::RsTable& t = *r.f;
     auto bad = [&](const std::string& what) {
@@ -585,7 +595,7 @@ static RsPlan rs_plan(const conan_streams* s, const int32_t* slots, int n, const
     if (r.phase == 1 && (!fin || sm != 0)) bad("after the final call only samples = 0, final = 1 may follow");
     if (!fin && sm != s_in) bad("a non-final call takes exactly segment * hop * in_rate / out_rate samples");
     if (fin && (sm < 0 || sm > s_in)) bad("a final call takes 0 .. segment * hop * in_rate / out_rate samples");
-    if (sm > wav_ld) bad("the row holds more samples than the row stride of wav_dev");
+    if ((long long)sm * bps > wav_ld * 4) bad("the row holds more samples than the row stride of wav_dev");
     if (sm > 0 && !wav_dev) throw Error(CONAN_ERR_INVALID, "null argument (wav_dev with samples > 0)");
     const long long I = r.in + sm;
     long long J;
@@ -602,7 +612,7 @@ static RsPlan rs_plan(const conan_streams* s, const int32_t* slots, int n, const
     P.mm[i] = (int)(J - r.out);
     P.rate[i] = 1; P.any = true; P.in_after[i] = I;
     row.in0 = r.in; row.out0 = r.out; row.taps = t.f.taps; row.ph = t.f.ph;
-    row.m = sm; row.h = P.mm[i]; row.orig = t.f.orig; row.nph = t.f.nph; row.w = t.f.w; row.L = t.f.L; row.copy = 0;
+    row.m = sm; row.h = P.mm[i]; row.orig = t.f.orig; row.nph = t.f.nph; row.w = t.f.w; row.L = t.f.L; row.mode = fmt << cnk::kRsFmtShift;
     P.launch = P.launch || sm > 0 || P.mm[i] > 0;
     P.win = std::max(P.win, t.win);
     P.flops += 2.0 * P.mm[i] * t.f.L;
@@ -645,9 +655,13 @@ static void rs_commit(conan_streams* s, const int32_t* slots, int n, const RsPla
 }
 
 void conan_streams::resample_init() {
-  if (rs_ring) return;
+  rs_stage_init();
+  if (!rs_ring) rs_ring = alloc((size_t)max_slots * cnk::kRsRing);        // stream state (state_bytes)
+}
+
+void conan_streams::rs_stage_init() {
+  if (rs_wav[0]) return;
   const size_t S = (size_t)ctx->cfg.emf_segment * ctx->hop;
-  rs_ring = alloc((size_t)max_slots * cnk::kRsRing);        // stream state (state_bytes)
   auto dev = [&](size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, bytes)); allocs.push_back(p); return p; };
   for (int q = 0; q < NS; ++q) {
     rs_rows[q] = (cnk::RsRow*)dev((size_t)max_slots * sizeof(cnk::RsRow));
@@ -782,7 +796,7 @@ static void step_wav(conan_streams* s, const std::string& who, const int32_t* sl
     if (o.phase == 1 && (!fin || sm != 0)) bad("after the final call only samples = 0, final = 1 may follow");
     if (!fin && sm != seg * hop && !P.rate[i]) bad("a non-final call takes exactly segment * hop samples per slot");
     if (fin && (sm < 0 || sm > seg * hop)) bad("a final call takes 0 .. segment * hop samples per slot");
-    if (sm > wav_ld && !P.rate[i]) bad("the row holds more samples than the row stride of wav_dev");
+    if (sm > wav_ld && !P.rate[i] && !s->in_fmt[slots[i]]) bad("the row holds more samples than the row stride of wav_dev");
     if (in_samples[i] > 0 && !wav_dev) throw Error(CONAN_ERR_INVALID, "null argument (wav_dev with samples > 0)");
     if (fin && o.recv + sm < 1) bad("an utterance needs at least one sample");
     pl[i] = fe_plan(s, o, sm, fin, N, who);
@@ -802,7 +816,7 @@ static void step_wav(conan_streams* s, const std::string& who, const int32_t* sl
   // its call-order rows of wav_out_dev (the scatter then places codes and mel only); otherwise no group's plan is active
   bool route = scatter && s->out_ld != 0;
   for (int g = 0; scatter && g < (int)groups.size(); ++g)
-    for (int i : groups[g]) route = route || (!s->or_slot.empty() && s->or_slot[slots[i]].f);
+    for (int i : groups[g]) route = route || (!s->or_slot.empty() && s->or_slot[slots[i]].f) || s->out_fmt[slots[i]];
   std::vector<conan_streams::OutPlan> ops;
   for (int g = 0; g < (int)groups.size(); ++g) {
     std::vector<int32_t> gs;
@@ -1065,6 +1079,64 @@ int conan_streams_set_output_ld(conan_streams* s, int64_t ld) {
     if (!s) throw Error(CONAN_ERR_INVALID, "null streams");
     if (ld < 0 || ld > INT_MAX) throw Error(CONAN_ERR_INVALID, "conan_streams_set_output_ld: ld out of range");
     s->out_ld = ld;
+  });
+}
+
+static void check_format(int format, const char* who) {
+  if (format != CONAN_SAMPLE_F32 && format != CONAN_SAMPLE_S16 && format != CONAN_SAMPLE_ULAW && format != CONAN_SAMPLE_ALAW)
+    throw Error(CONAN_ERR_INVALID, std::string(who) + ": format must be CONAN_SAMPLE_F32, _S16, _ULAW or _ALAW");
+}
+static_assert(CONAN_SAMPLE_F32 == cnk::kFmtF32 && CONAN_SAMPLE_S16 == cnk::kFmtS16 && CONAN_SAMPLE_ULAW == cnk::kFmtUlaw && CONAN_SAMPLE_ALAW == cnk::kFmtAlaw,
+              "the kernels' format codes are the header's");
+
+int conan_streams_set_input_format(conan_streams* s, const int32_t* slots, int n, int format) {
+  return guarded([&] {
+    if (!s || !slots) throw Error(CONAN_ERR_INVALID, "null argument");
+    if (!s->fe_audio) throw Error(CONAN_ERR_STATE, "conan_streams_set_input_format: the stream-set has no streaming front-end (all three models)");
+    check_format(format, "conan_streams_set_input_format");
+    check_slot_list(s, slots, n);
+    if (format != CONAN_SAMPLE_F32) {      // staging rows and row tables only: a format has no stream state
+      HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+      s->rs_stage_init();
+    }
+    for (int i = 0; i < n; ++i) {
+      s->in_fmt_n += (format != 0) - (s->in_fmt[slots[i]] != 0);
+      s->in_fmt[slots[i]] = (unsigned char)format;
+    }
+  });
+}
+
+int conan_streams_set_output_format(conan_streams* s, const int32_t* slots, int n, int format) {
+  return guarded([&] {
+    if (!s || !slots) throw Error(CONAN_ERR_INVALID, "null argument");
+    if (!(s->ctx->cfg.models & CONAN_MODEL_HIFIGAN)) throw Error(CONAN_ERR_STATE, "conan_streams_set_output_format: context holds no HiFi-GAN model");
+    check_format(format, "conan_streams_set_output_format");
+    check_slot_list(s, slots, n);
+    for (int i = 0; i < n; ++i) {
+      s->out_fmt_n += (format != 0) - (s->out_fmt[slots[i]] != 0);
+      s->out_fmt[slots[i]] = (unsigned char)format;
+    }
+  });
+}
+
+int conan_convert_samples(conan_ctx* ctx, int src_format, const void* src_dev, int64_t src_ld, int dst_format, void* dst_dev, int64_t dst_ld, int n,
+                          int64_t samples, void* stream) {
+  return guarded([&] {
+    if (!ctx || !src_dev || !dst_dev) throw Error(CONAN_ERR_INVALID, "null argument");
+    check_format(src_format, "conan_convert_samples");
+    check_format(dst_format, "conan_convert_samples");
+    if (n < 1 || n > 65535) throw Error(CONAN_ERR_INVALID, "conan_convert_samples: n must be in 1 .. 65535");
+    if (samples < 1) throw Error(CONAN_ERR_INVALID, "conan_convert_samples: samples must be >= 1");
+    auto bps = [](int f) { return f == CONAN_SAMPLE_F32 ? 4 : (f == CONAN_SAMPLE_S16 ? 2 : 1); };
+    const int64_t lim = INT64_MAX / 8;
+    if (src_ld < 0 || dst_ld < 0 || src_ld > lim || dst_ld > lim || samples > lim || samples * bps(src_format) > src_ld * 4 || samples * bps(dst_format) > dst_ld * 4)
+      throw Error(CONAN_ERR_INVALID, "conan_convert_samples: a row of `samples` samples does not fit its stride (4-byte units)");
+    if (((uintptr_t)src_dev | (uintptr_t)dst_dev) & 3) throw Error(CONAN_ERR_INVALID, "conan_convert_samples: src_dev and dst_dev must be 4-byte aligned");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    cnk::ConvertSamplesArgs a;
+    a.src = src_dev; a.dst = dst_dev; a.src_ld = src_ld; a.dst_ld = dst_ld; a.samples = samples; a.src_fmt = src_format; a.dst_fmt = dst_format;
+    cnk::launch_convert_samples(a, n, (hipStream_t)stream);
+    HIP_CHECK(hipGetLastError());
   });
 }
 

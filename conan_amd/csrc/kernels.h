@@ -565,16 +565,21 @@ struct RsFilter {
   const int* ph;                      // [nph][2]: klo (first tap, relative to q * orig - w), cnt
   int orig, nph, w, L;
 };
+// Sample formats of the caller's rows (include/conan_hip.h, CONAN_SAMPLE_*): f32, s16, G.711 mu-law, G.711 A-law.  A row of a format
+// other than f32 is packed from the row's first byte; row strides stay in 4-byte units, so every row starts on a dword.
+constexpr int kFmtF32 = 0, kFmtS16 = 1, kFmtUlaw = 2, kFmtAlaw = 3;
+constexpr int kRsCopy = 1, kRsFmtShift = 8;      // RsRow::mode: bit 0 = the row has no rate, bits 8.. = the format of the caller's row
+constexpr int kOrDstBits = 24;                   // RsOutRow::dst: the row index in the low 24 bits, the format of the caller's row above
 struct RsRow {                        // one call row of resample_stream_kernel (16 ints, uploaded through PinRing)
   long long in0, out0;                // input samples received before this call; model-rate samples handed over before it
   const float* taps; const int* ph;
-  int slot, m, h, orig, nph, w, L, copy;   // m input samples this call, h outputs; copy: the row has no rate (h = m samples verbatim)
+  int slot, m, h, orig, nph, w, L, mode;   // m input samples this call, h outputs; mode: kRsCopy (no rate: h = m samples, decoded) | format << kRsFmtShift
 };
 static_assert(sizeof(RsRow) == 16 * sizeof(int), "RsRow is uploaded as 16 ints");
 struct ResampleArgs { const float* x; float* y; long long samples, nout; RsFilter f; int win; };
 void launch_resample(const ResampleArgs& a, int n, hipStream_t st);            // whole signals: x [n][samples] -> y [n][nout]
 struct ResampleStreamArgs {
-  const float* wav; long long wav_ld;   // this call's input, row r at r * wav_ld (never null: a dummy when no row has samples)
+  const float* wav; long long wav_ld;   // this call's input, row r at r * wav_ld dwords in its slot's format (never null: a dummy when no row has samples)
   float* ring;                          // [max_slots][kRsRing]
   float* out; long long out_ld;         // model-rate rows for the front-end
   const RsRow* rows; int n, tiles, win;
@@ -586,16 +591,19 @@ void launch_resample_stream(const ResampleStreamArgs& a, hipStream_t st);
 struct RsOutRow {
   long long in0, out0;                // model-rate samples produced before this step; output samples delivered before it
   const float* taps; const int* ph;
-  int slot, m, h, orig, nph, w, L, dst;
+  int slot, m, h, orig, nph, w, L, dst;   // dst: row | format << kOrDstBits
 };
 static_assert(sizeof(RsOutRow) == 16 * sizeof(int), "RsOutRow is uploaded as 16 ints");
 struct ResampleOutArgs {
   const float* wav; long long wav_ld;   // conv_post's model-rate rows (staging), row r at r * wav_ld (a flush: m = 0 everywhere, never null)
   float* ring; int ring_len;            // [max_slots][ring_len] (a power of two; model-rate sample i at i & (ring_len - 1))
-  float* out; long long out_ld;         // the caller's wav_out_dev at the stride in force
+  float* out; long long out_ld;         // the caller's wav_out_dev at the stride in force (dwords), each row in its slot's format
   const RsOutRow* rows; int n, tiles, win;
 };
 void launch_resample_out(const ResampleOutArgs& a, hipStream_t st);
+// Whole signals from one sample format to another through the float rule (conan_convert_samples): n rows of `samples`, strides in dwords.
+struct ConvertSamplesArgs { const void* src; void* dst; long long src_ld, dst_ld, samples; int src_fmt, dst_fmt; };
+void launch_convert_samples(const ConvertSamplesArgs& a, int n, hipStream_t st);
 
 // ---- style pass (per utterance) helpers
 struct RowMaskArgs { TRef x; TRef m; const int* lens; int T, n, C; int mode; };  // mode 0: sum|x|>0, 1: x[0]!=0

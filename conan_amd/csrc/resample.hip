@@ -64,18 +64,87 @@ __global__ __launch_bounds__(kRsTile) void resample_kernel(const ResampleArgs a)
   if (act) a.y[(size_t)blockIdx.y * a.nout + jt] = y;
 }
 
+// ---- sample formats (include/conan_hip.h, CONAN_SAMPLE_*).  Decoding is exact: every code is an integer of at most 16 bits over 32768.
+// Sample i of a row in format fmt: ONE unconditional dword load - the aligned dword that holds the sample; the row starts on a dword and
+// its stride is whole dwords, so the dword lies inside the row - then integer arithmetic on the loaded word; the format only selects
+// among values, never around the load.  No table in memory.
+__device__ __forceinline__ float load_sample(int fmt, const void* row, long long i) {
+  const int sh = fmt == kFmtF32 ? 2 : (fmt == kFmtS16 ? 1 : 0);          // log2(bytes per sample)
+  const long long b = i << sh;                                           // the sample's first byte in the row
+  const unsigned wd = reinterpret_cast<const unsigned*>(row)[b >> 2];
+  const unsigned v = wd >> (((unsigned)b & 3u) * 8u);                    // the sample in the low bits
+  const int s16 = (int)(short)(v & 0xFFFFu);
+  const unsigned u = ~v & 0xFFu;                                         // mu-law
+  const int tu = (int)((((u & 15u) << 3) + 0x84u) << ((u >> 4) & 7u));
+  const int vu = (u & 0x80u) ? 0x84 - tu : tu - 0x84;
+  const unsigned al = (v ^ 0x55u) & 0xFFu;                               // A-law
+  const unsigned m = al & 15u, e = (al >> 4) & 7u;
+  const int ta = e == 0 ? (int)((m << 4) + 8u) : (int)(((m << 4) + 0x108u) << (e - 1u));
+  const int va = (al & 0x80u) ? ta : -ta;
+  const int q = fmt == kFmtS16 ? s16 : (fmt == kFmtUlaw ? vu : va);
+  return fmt == kFmtF32 ? __uint_as_float(wd) : (float)q * (1.f / 32768.f);
+}
+
+// s = clamp(rint(x * 32768), -32768, 32767), ties to even (x * 32768 is exact: a power of two; the clamps come before the
+// conversion, so that a product beyond the int range is never converted), then the format's code of s.
+__device__ __forceinline__ unsigned encode_sample(int fmt, float x) {
+  const int s = (int)fminf(fmaxf(rintf(x * 32768.f), -32768.f), 32767.f);
+  if (fmt == kFmtS16) return (unsigned)s & 0xFFFFu;
+  if (fmt == kFmtUlaw) {
+    int p = s >> 2;
+    const bool neg = p < 0;
+    p = min(neg ? -p : p, 8159) + 0x21;                                  // 0x21 .. 0x2000
+    const int seg = 26 - __clz(p);                                       // thresholds 2^(k + 6) - 1 below p: floor(log2 p) - 5, 0 .. 8
+    const unsigned u = seg >= 8 ? 0x7Fu : (unsigned)((seg << 4) | ((p >> (seg + 1)) & 15));
+    return u ^ (neg ? 0x7Fu : 0xFFu);
+  }
+  int p = s >> 3;
+  const bool neg = p < 0;
+  p = neg ? -p - 1 : p;                                                  // 0 .. 4095
+  const int seg = max(27 - __clz(p | 1), 0);                             // thresholds 2^(k + 5) - 1 below p: floor(log2 p) - 4, 0 .. 7
+  const unsigned a = (unsigned)((seg << 4) | ((seg < 2 ? p >> 1 : p >> seg) & 15));
+  return a ^ (neg ? 0x55u : 0xD5u);
+}
+
+// Sample i of a row of n samples in format fmt (uniform over the caller's wave).  Every lane of an aligned group of four consecutive
+// samples must call it together (lane = i mod 4, also the lanes with i >= n, which store nothing): 16- and 8-bit codes travel to the
+// lane that owns the dword and leave as one dword store; the ragged last dword of a row leaves as halfword / byte stores, so that
+// no byte past the row's n samples is written.
+__device__ __forceinline__ void store_sample(int fmt, void* row, long long i, long long n, float x) {
+  if (fmt == kFmtF32) {
+    if (i < n) reinterpret_cast<float*>(row)[i] = x;
+    return;
+  }
+  const unsigned c = encode_sample(fmt, x);
+  const unsigned c1 = __shfl_down(c, 1), c2 = __shfl_down(c, 2), c3 = __shfl_down(c, 3);
+  if (fmt == kFmtS16) {
+    if (i & 1) return;
+    if (i + 1 < n) reinterpret_cast<unsigned*>(row)[i >> 1] = c | (c1 << 16);
+    else if (i < n) reinterpret_cast<unsigned short*>(row)[i] = (unsigned short)c;
+    return;
+  }
+  const long long g = i & ~3ll;
+  if (g + 3 < n) {
+    if (i == g) reinterpret_cast<unsigned*>(row)[i >> 2] = c | (c1 << 8) | (c2 << 16) | (c3 << 24);
+  } else if (i < n) {
+    reinterpret_cast<unsigned char*>(row)[i] = (unsigned char)c;
+  }
+}
+
 // One launch per wav-in call: row r (blockIdx.y) resamples this call's h outputs of its slot - inputs before in0 from the slot's
-// history ring, this call's m inputs from the caller's row - into out row r, and appends the m inputs to the ring.  The host has
-// checked that the ring positions a call reads ([first tap of its first output, in0)) and the ones it writes ([in0, in0 + m))
-// are disjoint, so the workgroups of a row need no ordering.  Rows without a rate (copy) are copied verbatim.
+// history ring, this call's m inputs from the caller's row, decoded from the row's sample format - into out row r, and appends the m
+// decoded inputs to the ring.  The host has checked that the ring positions a call reads ([first tap of its first output, in0)) and
+// the ones it writes ([in0, in0 + m)) are disjoint, so the workgroups of a row need no ordering.  Rows without a rate (kRsCopy) are
+// decoded into the out row and touch no ring.
 __global__ __launch_bounds__(kRsTile) void resample_stream_kernel(const ResampleStreamArgs a) {
   extern __shared__ float lds[];
   const RsRow R = a.rows[blockIdx.y];
   const float* wav = a.wav + blockIdx.y * a.wav_ld;
+  const int fmt = R.mode >> kRsFmtShift;
   float* out = a.out + blockIdx.y * a.out_ld;
   const int stride = gridDim.x * kRsTile, t0 = blockIdx.x * kRsTile + threadIdx.x;
-  if (R.copy) {
-    for (int t = t0; t < R.m; t += stride) out[t] = wav[t];
+  if (R.mode & kRsCopy) {
+    for (int t = t0; t < R.m; t += stride) out[t] = load_sample(fmt, wav, t);
     return;
   }
   float* ring = a.ring + (size_t)R.slot * kRsRing;
@@ -86,7 +155,7 @@ __global__ __launch_bounds__(kRsTile) void resample_stream_kernel(const Resample
     const int mlast = R.m > 0 ? R.m - 1 : 0;
     auto fetch = [&](long long i) {
       const long long d = i - R.in0;
-      const float vw = wav[d < 0 ? 0 : (d > mlast ? mlast : d)];
+      const float vw = load_sample(fmt, wav, d < 0 ? 0 : (d > mlast ? mlast : d));
       const float vr = ring[i & (kRsRing - 1)];
       return (i < 0 || i >= end) ? 0.f : (d >= 0 ? vw : vr);
     };
@@ -94,22 +163,25 @@ __global__ __launch_bounds__(kRsTile) void resample_stream_kernel(const Resample
     const float y = rs_output(lds, j0, act ? jt : R.out0 + R.h - 1, f, a.win, fetch);
     if (act) out[jt - R.out0] = y;
   }
-  for (int t = t0; t < R.m; t += stride) ring[(R.in0 + t) & (kRsRing - 1)] = wav[t];
+  for (int t = t0; t < R.m; t += stride) ring[(R.in0 + t) & (kRsRing - 1)] = load_sample(fmt, wav, t);
 }
 
-// One launch per vocoder step with an output rate (conan_streams_set_output_rate), behind conv_post_kernel: row r (blockIdx.y)
-// resamples its slot's outputs [out0, out0 + h) - model-rate samples before in0 from the slot's history ring, the step's m new ones from
-// conv_post's staging row - into row `dst` of the caller's buffer, and appends the m samples to the ring.  Samples at or past
-// in0 + m read as zero: a flush (m = 0, h = what is left of the utterance) pads as the whole-signal kernel does.  The host has checked
-// that the ring positions a launch reads and the ones it writes are disjoint.  Rows without a rate are copied verbatim.
+// One launch per vocoder step with an output rate (conan_streams_set_output_rate) or format (conan_streams_set_output_format), behind
+// conv_post_kernel: row r (blockIdx.y) resamples its slot's outputs [out0, out0 + h) - model-rate samples before in0 from the slot's
+// history ring, the step's m new ones from conv_post's staging row - into row `dst` of the caller's buffer, encoded in the row's
+// sample format, and appends the m samples to the ring.  Samples at or past in0 + m read as zero: a flush (m = 0, h = what is left of
+// the utterance) pads as the whole-signal kernel does.  The host has checked that the ring positions a launch reads and the ones it
+// writes are disjoint.  Rows without a rate are copied (encoded) verbatim.  Stores go through store_sample: whole groups of four lanes.
 __global__ __launch_bounds__(kRsTile) void resample_out_kernel(const ResampleOutArgs a) {
   extern __shared__ float lds[];
   const RsOutRow R = a.rows[blockIdx.y];
   const float* wav = a.wav + blockIdx.y * a.wav_ld;
-  float* out = a.out + R.dst * a.out_ld;
+  const int fmt = R.dst >> kOrDstBits;
+  float* out = a.out + (R.dst & ((1 << kOrDstBits) - 1)) * a.out_ld;
   const int stride = gridDim.x * kRsTile, t0 = blockIdx.x * kRsTile + threadIdx.x;
   if (!R.taps) {
-    for (int t = t0; t < R.m; t += stride) out[t] = wav[t];
+    const int mlast = R.m > 0 ? R.m - 1 : 0, m4 = (R.m + 3) & ~3;
+    for (int t = t0; t < m4; t += stride) store_sample(fmt, out, t, R.m, wav[min(t, mlast)]);
     return;
   }
   const int mask = a.ring_len - 1;
@@ -127,9 +199,18 @@ __global__ __launch_bounds__(kRsTile) void resample_out_kernel(const ResampleOut
     };
     RsFilter f; f.taps = R.taps; f.ph = R.ph; f.orig = R.orig; f.nph = R.nph; f.w = R.w; f.L = R.L;
     const float y = rs_output(lds, j0, act ? jt : R.out0 + R.h - 1, f, a.win, fetch);
-    if (act) out[jt - R.out0] = y;
+    store_sample(fmt, out, t0, R.h, y);           // (every thread of the block: t0 >= h stores nothing)
   }
   for (int t = t0; t < R.m; t += stride) ring[(R.in0 + t) & mask] = wav[t];
+}
+
+// conan_convert_samples: row r (blockIdx.y), samples [0, samples) in groups of four per lane group, any format to any format.
+__global__ __launch_bounds__(kRsTile) void convert_samples_kernel(const ConvertSamplesArgs a) {
+  const char* src = reinterpret_cast<const char*>(a.src) + (size_t)blockIdx.y * a.src_ld * 4;
+  char* dst = reinterpret_cast<char*>(a.dst) + (size_t)blockIdx.y * a.dst_ld * 4;
+  const long long stride = (long long)gridDim.x * kRsTile, n4 = (a.samples + 3) & ~3ll;
+  for (long long t = (long long)blockIdx.x * kRsTile + threadIdx.x; t < n4; t += stride)
+    store_sample(a.dst_fmt, dst, t, a.samples, load_sample(a.src_fmt, src, min(t, a.samples - 1)));
 }
 
 void launch_resample(const ResampleArgs& a, int n, hipStream_t st) {
@@ -143,6 +224,11 @@ void launch_resample_stream(const ResampleStreamArgs& a, hipStream_t st) {
 
 void launch_resample_out(const ResampleOutArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(resample_out_kernel, dim3((unsigned)a.tiles, (unsigned)a.n), dim3(kRsTile), (size_t)(a.win + 2) * sizeof(float), st, a);
+}
+
+void launch_convert_samples(const ConvertSamplesArgs& a, int n, hipStream_t st) {
+  const long long tiles = (a.samples + kRsTile - 1) / kRsTile;
+  hipLaunchKernelGGL(convert_samples_kernel, dim3((unsigned)std::min(tiles, 4096ll), (unsigned)n), dim3(kRsTile), 0, st, a);
 }
 
 }  // namespace cnk

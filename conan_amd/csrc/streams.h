@@ -155,7 +155,13 @@ struct conan_streams {
   cnk::RsRow* rs_rows[NS] = {}; float* rs_wav[NS] = {};
   hipEvent_t ev_rs[NS] = {};
   long long rs_calls = 0;
-  void resample_init();
+  void resample_init();        // staging, row tables and the history ring (conan_streams_set_input_rate)
+  void rs_stage_init();        // staging and row tables only (conan_streams_set_input_format: no stream state)
+  // sample formats of the caller's rows (conan_streams_set_input_format / _output_format; cnk::kFmt*), per slot; they persist across
+  // resets.  A slot with a format and no rate takes the copy rows of resample_stream_kernel / resample_out_kernel.  *_fmt_n: slots
+  // whose format is not f32 (0: every launch is today's).
+  std::vector<unsigned char> in_fmt, out_fmt;
+  int in_fmt_n = 0, out_fmt_n = 0;
   // output resampler (conan_streams_set_output_rate): per slot the filter (null: audio leaves at the model rate), output samples
   // delivered, whether conan_streams_flush_output has ended the utterance.  voc_samples = model-rate samples the slot's vocoder has
   // produced since its last reset with CONAN_MODEL_HIFIGAN (kept from creation on: pos_voc is device memory).  The history ring

@@ -529,9 +529,9 @@ conan_streams::OutPlan conan_streams::out_plan(const int32_t* slots, int n, int 
   P.counts.assign(n, T);
   if (dst) P.dst = *dst;
   bool any = false;
-  for (int i = 0; i < n && !or_slot.empty(); ++i) {
+  for (int i = 0; i < n && (!or_slot.empty() || out_fmt_n); ++i) {
     if (slots[i] < 0 || slots[i] >= max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
-    any = any || or_slot[slots[i]].f;
+    any = any || (!or_slot.empty() && or_slot[slots[i]].f) || out_fmt[slots[i]];      // (a format alone sends the step through the copy rows)
   }
   P.active = any || dst || P.ld != T;
   if (flush) P.active = false;
@@ -541,7 +541,9 @@ conan_streams::OutPlan conan_streams::out_plan(const int32_t* slots, int n, int 
     if (slots[i] < 0 || slots[i] >= max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
     cnk::RsOutRow& row = P.rows[i];
     memset(&row, 0, sizeof(row));
-    row.slot = slots[i]; row.m = T; row.h = T; row.dst = dst ? (*dst)[i] : i;
+    const int fmt = out_fmt[slots[i]], bps = fmt == cnk::kFmtF32 ? 4 : (fmt == cnk::kFmtS16 ? 2 : 1);
+    row.slot = slots[i]; row.m = T; row.h = T; row.dst = (dst ? (*dst)[i] : i) | (fmt << cnk::kOrDstBits);
+    if (fmt != cnk::kFmtF32 && ((uintptr_t)wav_out & 3)) throw Error(CONAN_ERR_INVALID, who + ": wav_out_dev must be 4-byte aligned");
     if (!or_slot.empty() && or_slot[slots[i]].f) {
       const OrSlot& o = or_slot[slots[i]];
       const ch::RsTable& t = *o.f;
@@ -565,9 +567,10 @@ conan_streams::OutPlan conan_streams::out_plan(const int32_t* slots, int n, int 
       row.h = 0;
     }
     P.counts[i] = row.h;
-    if (row.h > P.ld)
-      throw Error(CONAN_ERR_INVALID, who + ": slot " + std::to_string(slots[i]) + " (call row " + std::to_string(row.dst) + ") delivers " + std::to_string(row.h) +
-                                         " samples, more than the row stride of wav_out_dev in force (" + std::to_string(P.ld) + (flush ? "; conan_streams_output_pending)" : "; conan_streams_set_output_ld)"));
+    if ((long long)row.h * bps > P.ld * 4)
+      throw Error(CONAN_ERR_INVALID, who + ": slot " + std::to_string(slots[i]) + " (call row " + std::to_string(dst ? (*dst)[i] : i) + ") delivers " + std::to_string(row.h) +
+                                         " samples of " + std::to_string(bps) + " bytes, more than the row stride of wav_out_dev in force (" + std::to_string(P.ld) +
+                                         " x 4 bytes" + (flush ? "; conan_streams_output_pending)" : "; conan_streams_set_output_ld)"));
     P.tiles = std::max(P.tiles, (std::max(row.h, row.m) + cnk::kRsTile - 1) / cnk::kRsTile);
   }
   return P;

@@ -212,22 +212,37 @@ class StreamingVoiceConversionEngine:
         self.slots = list(range(n_streams))
         self.seg, self.rc = ctx.cfg.emf_segment, ctx.cfg.emf_right_context
 
-    def start(self, ref_mel, ref_len=None, which=7, out_rate=None, out_filter=None):
+    def start(self, ref_mel, ref_len=None, which=7, out_rate=None, out_filter=None, out_format=None):
         """out_rate: the sample rate the audio leaves at (None: the model rate), resampled on the GPU behind the vocoder; out_filter:
-        dict of Context.resample's filter keywords.  The steps then deliver what the filter has the inputs for, finish() the tail."""
-        if isinstance(out_rate, (list, tuple)):
-            raise ValueError("out_rate: one rate for all slots here (feed / infer return one [B, count] block); open_slots and "
-                             "infer_wav_staggered take a rate per slot / utterance")
+        dict of Context.resample's filter keywords.  The steps then deliver what the filter has the inputs for, finish() the tail.
+        out_format: the sample format the audio leaves in ('f32' | 's16' | 'ulaw' | 'alaw'; None: float32), encoded on the GPU."""
+        if isinstance(out_rate, (list, tuple)) or isinstance(out_format, (list, tuple)):
+            raise ValueError("out_rate / out_format: one value for all slots here (feed / infer return one [B, count] block); open_slots and "
+                             "infer_wav_staggered take one per slot / utterance")
         self.st.reset(self.slots, which=which)
         self.st.set_reference(self.slots, ref_mel, ref_len)
         self._set_out_rate(self.slots, out_rate, out_filter)
+        self._set_format(self.slots, out_format, self.st.output_formats, self.st.set_output_format)
 
-    def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, **filter):
+    def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
         in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
-        out_rate / out_filter: as in start()."""
-        self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter)
+        in_format: the input's sample format (None: float32; 's16' takes int16 rows, 'ulaw' / 'alaw' uint8), decoded on the GPU.
+        out_rate / out_filter / out_format: as in start()."""
+        if isinstance(in_format, (list, tuple)):
+            raise ValueError("in_format: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
+        self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format)
         self._set_rate(self.slots, in_rate, filter)
+        self._set_format(self.slots, in_format, self.st.input_formats, self.st.set_input_format)
+
+    @staticmethod
+    def _set_format(slots, fmt, table, setter):
+        """The slots' sample format (None: float32), one value or one per slot.  Slots that never had another format are left alone."""
+        fmts = list(fmt) if isinstance(fmt, (list, tuple)) else [fmt] * len(slots)
+        for f in dict.fromkeys(fmts):
+            group = [s for s, x in zip(slots, fmts) if x == f and ((x or "f32") != "f32" or s in table)]
+            if group:
+                setter(group, f or "f32")
 
     def _set_out_rate(self, slots, out_rate, out_filter):
         """The slots' output rate (None: the model rate), one value or one per slot, and the stream-set's output stride: wide enough
@@ -274,21 +289,27 @@ class StreamingVoiceConversionEngine:
         chunk of algorithmic latency).  After final=True keep calling feed(empty, final=True) until it returns 0 frames.
         pipelined: conan_step_wav_async - the tensors are complete after self.st.join()."""
         fn = self.st.step_wav_async if pipelined else self.st.step_wav
-        if not self.st.output_ld:
+        st = self.st
+        if not (st.output_ld or st.output_formats):
             emit, c, m, w = fn(self.slots, wav_chunk, final=final, mel=mel)
             return w, m, c[:, :emit]
-        # output rates: rows at the engine's stride, all slots at one position and rate here (a view: pipelined steps complete at join())
-        buf = torch.empty(len(self.slots), self.st.output_ld, device=wav_chunk.device)
+        # output rates / formats: rows at the stride in force, all slots at one position, rate and format here (a view: pipelined
+        # steps complete at join())
+        buf = torch.empty(len(self.slots), st.output_ld or self.seg * self.ctx.hop, device=wav_chunk.device)
         emit, c, m, _ = fn(self.slots, wav_chunk, final=final, mel=mel, wav_out=buf)
-        return buf[:, :self.st.output_samples()[0] if emit else 0], m, c[:, :emit]
+        w = st.wav_block(buf, self.slots, st.output_samples()[0] if emit else 0, st.output_ld or (emit or self.seg) * self.ctx.hop)
+        return w, m, c[:, :emit]
 
     @torch.no_grad()
-    def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, **filter):
+    def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
+                  out_format=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
-        out_rate (+ out_filter): the returned wav is the whole utterance at that rate, ctx.resample of the model-rate wav bit for bit."""
-        self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, **filter)
+        out_rate (+ out_filter): the returned wav is the whole utterance at that rate, ctx.resample of the model-rate wav bit for bit.
+        in_format: src_wav's sample format (int16 / uint8 samples; the results are those of the decoded floats, ctx.convert_samples,
+        bit for bit); out_format: the returned wav's format (ctx.convert_samples of the float wav bit for bit)."""
+        self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -314,14 +335,17 @@ class StreamingVoiceConversionEngine:
             wavs.append(torch.stack(self.finish()))
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
-    def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, **filter):
+    def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
         rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
-        (None: the model rate), one value or one per slot."""
+        (None: the model rate), one value or one per slot.  in_format / out_format: the slots' sample formats (None: float32), one
+        value or one per slot."""
         self.st.reset(slots, which=7 | 8)
         self.st.set_reference(slots, ref_mel, ref_len)
         self._set_out_rate(slots, out_rate, out_filter)
+        self._set_format(slots, in_format, self.st.input_formats, self.st.set_input_format)
+        self._set_format(slots, out_format, self.st.output_formats, self.st.set_output_format)
         rates = list(in_rate) if isinstance(in_rate, (list, tuple)) else [in_rate] * len(slots)
         for r in dict.fromkeys(rates):
             self._set_rate([s for s, x in zip(slots, rates) if x == r], r, filter)
@@ -329,16 +353,18 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None):
         """Streaming waveform input for slots at different positions of their utterances (conan_step_wav_ragged): slot i takes the
-        first samples[i] samples of wav row i (wav [n, <= seg*hop] cuda) with its own final flag; the rules per slot are feed()'s.
+        first samples[i] samples of wav row i (wav [n, <= seg*hop] cuda, or a list of 1-D rows, each in its slot's input format's
+        dtype) with its own final flag; the rules per slot are feed()'s.
         -> one (wav [emit*hop], mel [emit, 80], codes [emit]) per slot, of the chunk it emitted (emit = 0: empty).
         pipelined: conan_step_wav_ragged_async - the tensors are complete after self.st.join()."""
         fn = self.st.step_wav_ragged_async if pipelined else self.st.step_wav_ragged
         emit, c, m, w = fn(slots, wav, samples, final, mel=mel)
         counts = self.st.output_samples()        # (emit * hop for a slot without an output rate)
-        return [(w[i, :counts[i]], m[i, :e], c[i, :e]) for i, e in enumerate(emit)]
+        return [(self.st.wav_row(w, i, slots[i], counts[i]), m[i, :e], c[i, :e]) for i, e in enumerate(emit)]
 
     @torch.no_grad()
-    def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None, **filter):
+    def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
+                            in_formats=None, out_formats=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -346,8 +372,11 @@ class StreamingVoiceConversionEngine:
         -> one (wav, mel [T, 80], codes [T]) per utterance: what infer_wav would give for it alone.  The slot each utterance used is
         left in self.staggered_slots.  in_rates[u] (+ filter keywords): utterance u's sample rate (None: the model rate); one call
         then mixes rates, with rows as wide as the widest input of the call.  out_rates[u] (+ out_filter): the rate utterance u's
-        wav is returned at (None: the model rate)."""
+        wav is returned at (None: the model rate).  in_formats[u] / out_formats[u]: the sample format utterance u arrives / is
+        returned in (None: float32); one call then mixes formats, each row packed in its own."""
         U = len(src_wavs)
+        ifmts = list(in_formats) if in_formats is not None else [None] * U
+        ofmts = list(out_formats) if out_formats is not None else [None] * U
         orates = list(out_rates) if out_rates is not None else [None] * U
         assert len(starts) == U and len(ref_mel) == U
         rates = list(in_rates) if in_rates is not None else [None] * U
@@ -367,7 +396,8 @@ class StreamingVoiceConversionEngine:
                 new.append(u)
             if new:
                 self.open_slots([live[u][0] for u in new], torch.stack([ref_mel[u] for u in new]), in_rate=[rates[u] for u in new],
-                                out_rate=[orates[u] for u in new], out_filter=out_filter, **filter)
+                                out_rate=[orates[u] for u in new], out_filter=out_filter, in_format=[ifmts[u] for u in new],
+                                out_format=[ofmts[u] for u in new], **filter)
             if not live:
                 tick += 1
                 continue
@@ -389,8 +419,9 @@ class StreamingVoiceConversionEngine:
                     piece = x[:0]
                     final.append(1)
                 samples.append(piece.shape[0])
-                rows.append(torch.nn.functional.pad(piece, (0, width - piece.shape[0])))
-            res = self.feed_ragged([live[u][0] for u in us], torch.stack(rows), samples, final, pipelined=pipelined, mel=mel)
+                rows.append(piece if self.st.input_formats else torch.nn.functional.pad(piece, (0, width - piece.shape[0])))
+            # (rows of several dtypes travel as a list, each packed in its slot's format)
+            res = self.feed_ragged([live[u][0] for u in us], rows if self.st.input_formats else torch.stack(rows), samples, final, pipelined=pipelined, mel=mel)
             for u, was_final, (w, m, c) in zip(us, draining, res):
                 if m.shape[0]:
                     outs[u].append((w, m, c))
@@ -429,9 +460,9 @@ class StreamingVoiceConversionEngine:
         `seg` frames are kept.  The oracle of this mode is the reference module fed the same window.
         Returns (codes [B, seg], wav [B, seg*hop]) (+ mel [B, seg, 80])."""
         st, seg, hop = self.st, self.seg, self.ctx.hop
-        if st.output_rates or st.output_ld:
+        if st.output_rates or st.output_ld or st.output_formats:
             raise ValueError("windowed_step keeps the last seg * hop model-rate samples of a window: not available on a stream-set whose slots have "
-                             "an output rate (start(..., out_rate=None) restores the model rate)")
+                             "an output rate or format (start(..., out_rate=None, out_format=None) restores the model rate and float32)")
         _, _, codes = st.emformer_step(self.slots, chunk, want_out=False, want_logits=False)
         win = torch.cat([ctx_codes.to(codes.dtype), codes], 1) if ctx_codes is not None and ctx_codes.shape[1] else codes
         st.reset(self.slots, which=2 | 4)
@@ -441,17 +472,19 @@ class StreamingVoiceConversionEngine:
         return out + (mel[:, -seg:],) if return_mel else out
 
     @torch.no_grad()
-    def infer(self, src_mel, ref_mel, ref_len=None, pipelined=True, out_rate=None, out_filter=None):
+    def infer(self, src_mel, ref_mel, ref_len=None, pipelined=True, out_rate=None, out_filter=None, out_format=None):
         """src_mel [B,T,80], ref_mel [B,Tr,80] (cuda) -> wav [B, T*hop], mel [B,T,80], codes [B,T].
 
         The whole source is available here, so by default the chunks are issued as pipelined steps
         (conan_step_async): the Emformer + decoder of chunk t+1 overlap the vocoder of chunk t.  The
         results are bit-identical to the blocking loop (pipelined=False).  out_rate (+ out_filter): the returned wav is the
-        whole utterance at that rate, ctx.resample of the model-rate wav bit for bit."""
+        whole utterance at that rate, ctx.resample of the model-rate wav bit for bit.  out_format: the returned wav's sample format."""
         if self.ctx.cfg.voc_upsample == 2:
+            if out_format not in (None, "f32"):
+                raise ValueError("out_format with an upsample 'nn' vocoder: convert the returned wav with Context.convert_samples instead")
             self._set_out_rate(self.slots, out_rate, out_filter)      # (refuses a rate; restores the model rate)
             return self._infer_prefix_vocoder(src_mel, ref_mel, ref_len)
-        self.start(ref_mel, ref_len, out_rate=out_rate, out_filter=out_filter)
+        self.start(ref_mel, ref_len, out_rate=out_rate, out_filter=out_filter, out_format=out_format)
         B = src_mel.shape[0]
         hop, nm = self.ctx.hop, self.ctx.cfg.num_mels
         wavs, mels, codes = [], [], []
@@ -461,8 +494,8 @@ class StreamingVoiceConversionEngine:
                 m = torch.empty(B, emit, nm, device=src_mel.device)
                 w = torch.empty(B, self.st.output_ld or emit * hop, device=src_mel.device)
                 self.st.step_async(self.slots, chunk, w, emit=emit, codes=c, mel_out=m)
-                if self.st.output_ld:
-                    w = w[:, :self.st.output_samples()[0]]
+                if self.st.output_ld or self.st.output_formats:
+                    w = self.st.wav_block(w, self.slots, self.st.output_samples()[0])
             else:
                 c, m, w = self.st.step(self.slots, chunk, emit=emit)
             wavs.append(self._rows(w))

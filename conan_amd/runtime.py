@@ -30,6 +30,23 @@ def _i32(a):
     return a, a.ctypes.data_as(C.c_void_p)
 
 
+# torch dtype of a row in each sample format (conan_streams_set_input_format / _output_format, conan_convert_samples)
+SAMPLE_DTYPES = {"f32": torch.float32, "s16": torch.int16, "ulaw": torch.uint8, "alaw": torch.uint8}
+
+
+def _row_bytes(rows, n, ld, device):
+    """Rows of samples (1-D tensors, or one 2-D tensor) packed from the start of rows `ld` * 4 bytes apart: uint8 [n, ld * 4]."""
+    buf = torch.zeros(n, ld * 4, dtype=torch.uint8, device=device)
+    if isinstance(rows, torch.Tensor):
+        if rows.shape[1]:
+            buf.view(rows.dtype)[:, :rows.shape[1]] = rows
+    else:
+        for i, r in enumerate(rows):
+            if r.numel():
+                buf[i].view(r.dtype)[:r.numel()] = r
+    return buf
+
+
 def mel_cfg(fft_size=1024, hop_size=320, win_length=1024, num_mels=80, fmin=80, fmax=7600, sample_rate=16000, eps=1e-6,
             mel_vmin=-6.0, mel_vmax=1.5, framing=0, natural_log=False, mag_eps=0.0):
     """conan_mel_cfg with Context.wav2mel's defaults (inference/Conan.py:57-70)."""
@@ -115,6 +132,29 @@ class Context:
             assert got.value == nout
         return y
 
+    def convert_samples(self, x, src, dst, out=None):
+        """conan_convert_samples: x [..., N] of format `src` ('f32' float32, 's16' int16, 'ulaw' / 'alaw' uint8) -> [..., N] of
+        format `dst`, by the library's one conversion rule (decode exactly, encode with round-to-nearest-even and saturation).
+        out: a contiguous 2-D cuda buffer with one row per signal whose rows are a multiple of 4 bytes; the samples are written
+        from the start of each row, the bytes past them are left alone, and the rows come back as views in dst's dtype."""
+        fs, fd = _lib.sample_format(src), _lib.sample_format(dst)
+        dev = torch.device("cuda", self.device)
+        x = x.to(dev)
+        if x.dtype != SAMPLE_DTYPES[src]:
+            raise ValueError(f"convert_samples: format {src!r} takes {SAMPLE_DTYPES[src]} samples, got {x.dtype}")
+        lead, N = x.shape[:-1], x.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        bs, bd = _lib.SAMPLE_BYTES[src], _lib.SAMPLE_BYTES[dst]
+        src_ld = (N * bs + 3) // 4
+        xin = x.reshape(n, N).contiguous() if N * bs % 4 == 0 else _row_bytes(x.reshape(n, N), n, src_ld, dev)
+        if out is None:
+            out = torch.empty(n, 4 * ((N * bd + 3) // 4), dtype=torch.uint8, device=dev)
+        assert out.is_cuda and out.is_contiguous() and out.dim() == 2 and out.shape[0] == n and out.shape[1] * out.element_size() % 4 == 0
+        dst_ld = out.shape[1] * out.element_size() // 4
+        if n and N:
+            _lib.check(self.lib.conan_convert_samples(self.h, fs, _ptr(xin), src_ld, fd, _ptr(out), dst_ld, n, N, _stream()))
+        return out.view(SAMPLE_DTYPES[dst])[:, :N].reshape(*lead, N)
+
     def streams(self, max_slots, max_frames=4, max_ref_frames=256, arith="auto", flags=0, dev_plan=None):
         """A stream-set.  arith: 'auto' (library default), 'f32' (f32-input MFMA everywhere) or 'limb' (fp32 products of the
         vocoder's matrix kernels as bf16 limb products) - conan_streams_opts.arith; flags: _lib.STREAMS_*; dev_plan: developer /
@@ -152,6 +192,8 @@ class Streams:
         self.input_rate_set = False      # set_input_rate has run on this stream-set (its history ring exists)
         self.output_rates = {}           # slot -> output rate, for the slots whose audio leaves at another rate than the model's
         self.output_ld = 0               # set_output_ld: row stride of every step's wav (0: each step's own)
+        self.input_formats = {}          # slot -> 's16' | 'ulaw' | 'alaw', for the slots whose wav-in rows are not float32
+        self.output_formats = {}         # slot -> the same, for the slots whose audio leaves in another format
 
     @property
     def state_bytes(self):
@@ -204,6 +246,69 @@ class Streams:
             else:
                 self.output_rates.pop(int(slot), None)
 
+    def set_input_format(self, slots, fmt):
+        """conan_streams_set_input_format: the slots' wav-in rows arrive as 'f32' (float32), 's16' (int16), 'ulaw' or 'alaw' (uint8,
+        G.711) and are decoded on the GPU.  Stateless: takes effect from the next call, survives resets; 'f32' restores the default."""
+        a, p = _i32(slots)
+        _lib.check(self.lib.conan_streams_set_input_format(self.h, p, len(a), _lib.sample_format(fmt)))
+        self._note_format(self.input_formats, a, fmt)
+
+    def set_output_format(self, slots, fmt):
+        """conan_streams_set_output_format: the slots' audio leaves every step (and flush_output) as 'f32', 's16', 'ulaw' or 'alaw',
+        encoded on the GPU behind the vocoder and the output resampler.  Row strides stay in 4-byte units; counts stay in samples."""
+        a, p = _i32(slots)
+        _lib.check(self.lib.conan_streams_set_output_format(self.h, p, len(a), _lib.sample_format(fmt)))
+        self._note_format(self.output_formats, a, fmt)
+
+    @staticmethod
+    def _note_format(table, slots, fmt):
+        for slot in slots:
+            if fmt in (None, "f32"):
+                table.pop(int(slot), None)
+            else:
+                table[int(slot)] = fmt
+
+    def _out_dtype(self, slot):
+        return SAMPLE_DTYPES[self.output_formats.get(int(slot), "f32")]
+
+    def wav_row(self, wav, i, slot, count):
+        """Row i of a step's 2-D wav buffer in its slot's output dtype, its first `count` samples."""
+        return wav[i].view(self._out_dtype(slot))[:count]
+
+    def wav_block(self, wav, slots, count, ld=None):
+        """A step's wav buffer (rows `ld` floats apart) as one [n, count] view in the slots' common output dtype."""
+        dts = {self._out_dtype(s) for s in slots}
+        if len(dts) != 1:
+            raise ValueError("the slots deliver different sample formats: take the rows one by one (wav_row)")
+        n = len(slots)
+        ld = ld or wav.numel() // n
+        return wav.view(-1)[:n * ld].view(n, ld).view(dts.pop())[:, :count]
+
+    def _in_rows(self, slots, wav, min_ld):
+        """The wav-in rows as the library takes them: (buffer, row stride in 4-byte units, samples per row).  wav: one 2-D tensor
+        (rows of one dtype) or a list of 1-D tensors, each in its slot's dtype (float32, int16 for 's16', uint8 for G.711)."""
+        n = len(slots)
+        rows = list(wav) if isinstance(wav, (list, tuple)) else None
+        if rows is None and wav.dtype not in (torch.int16, torch.uint8):
+            wav = wav.to(self.dev, torch.float32)
+        for i, slot in enumerate(slots):
+            want = SAMPLE_DTYPES[self.input_formats.get(int(slot), "f32")]
+            got = rows[i].dtype if rows is not None else wav.dtype
+            if got != want:
+                raise ValueError(f"slot {int(slot)} takes {want} samples (set_input_format), row {i} holds {got}")
+        if rows is None:
+            assert wav.dim() == 2 and wav.shape[0] == n, wav.shape
+            samples = [wav.shape[1]] * n
+            if wav.dtype == torch.float32:
+                if wav.shape[1] < min_ld:
+                    wav = torch.nn.functional.pad(wav, (0, min_ld - wav.shape[1]))
+                return wav.to(self.dev).contiguous(), wav.shape[1], samples
+            ld = max(min_ld, (wav.shape[1] * wav.element_size() + 3) // 4)
+            return _row_bytes(wav.to(self.dev), n, ld, self.dev), ld, samples
+        assert len(rows) == n, (n, len(rows))
+        ld = max([min_ld] + [(r.numel() * r.element_size() + 3) // 4 for r in rows])
+        return _row_bytes([r.to(self.dev) for r in rows], n, ld, self.dev), ld, [r.numel() for r in rows]
+
     def set_output_ld(self, ld):
         """conan_streams_set_output_ld: row stride (floats) of wav in every step from now on; 0 = each step's own."""
         _lib.check(self.lib.conan_streams_set_output_ld(self.h, int(ld)))
@@ -230,19 +335,21 @@ class Streams:
         counts = self.output_pending(slots)
         ld = max(counts + [1])
         wav = out if out is not None else torch.empty(len(a), ld, device=self.dev)
-        assert wav.is_cuda and wav.is_contiguous() and wav.dim() == 2 and wav.shape[0] == len(a)
+        assert wav.is_cuda and wav.is_contiguous() and wav.dim() == 2 and wav.shape[0] == len(a) and wav.dtype == torch.float32
         _lib.check(self.lib.conan_streams_flush_output(self.h, p, len(a), _ptr(wav), wav.shape[1], _stream()))
         self._release()
-        return [wav[i, :c] for i, c in enumerate(counts)]
+        return [self.wav_row(wav, i, a[i], c) for i, c in enumerate(counts)]
 
-    def _wav_rows(self, wav, n, ld=None):
-        """A step's wav as the caller sees it: unchanged on a stream-set without output rate or stride, else one 1-D tensor per
-        row (rows `ld` floats apart) trimmed to the count the step reported."""
-        if not (self.output_rates or self.output_ld):
+    def _wav_rows(self, wav, slots, ld=None):
+        """A step's wav as the caller sees it: unchanged on a stream-set without output rate, stride or format, else one 1-D tensor
+        per row (rows `ld` floats apart) in its slot's dtype, trimmed to the count the step reported."""
+        if not (self.output_rates or self.output_ld or self.output_formats):
             return wav
+        n = len(slots)
         counts = self.output_samples()
         ld = ld or wav.numel() // n
-        return [wav.view(-1)[:n * ld].view(n, ld)[i, :counts[i]] for i in range(n)]
+        rows = wav.view(-1)[:n * ld].view(n, ld)
+        return [self.wav_row(rows, i, slots[i], counts[i]) for i in range(n)]
 
     @property
     def model_rate(self):
@@ -361,7 +468,7 @@ class Streams:
                 t.stage_out[i] = outs[-1].data_ptr()
         _lib.check(self.lib.conan_hifigan_step_taps(self.h, p, n, T, _ptr(mel), _ptr(wav), _ptr(pre), C.byref(t), _stream()))
         self._release()
-        wav = self._wav_rows(wav, n)
+        wav = self._wav_rows(wav, a)
         return (wav, pre, cpre, ups, outs) if stage_out else (wav, pre, cpre, ups)
 
     def hifigan_step(self, slots, mel, want_pre_tanh=False, out=None):
@@ -375,7 +482,7 @@ class Streams:
         pre = torch.empty(n, T * hop, device=self.dev) if want_pre_tanh else None
         _lib.check(self.lib.conan_hifigan_step(self.h, p, n, T, _ptr(mel), _ptr(wav), _ptr(pre), _stream()))
         self._release()
-        wav = self._wav_rows(wav, n)
+        wav = self._wav_rows(wav, a)
         return (wav, pre) if want_pre_tanh else wav
 
     def step(self, slots, mel_chunk, emit=None, codes=None, mel_out=None, wav_out=None):
@@ -392,7 +499,7 @@ class Streams:
             wav_out = torch.empty(n, self.output_ld or emit * hop, device=self.dev)
         _lib.check(self.lib.conan_step(self.h, p, n, emit, _ptr(mel_chunk), _ptr(codes), _ptr(mel_out), _ptr(wav_out), _stream()))
         self._release()
-        return codes, mel_out, self._wav_rows(wav_out, n)
+        return codes, mel_out, self._wav_rows(wav_out, a)
 
     def step_async(self, slots, mel_chunk, wav_out, emit=None, codes=None, mel_out=None, out_fence=None):
         """Pipelined chunk step (conan_step_async): returns at once; the front-end of the next call overlaps this
@@ -417,7 +524,9 @@ class Streams:
         """Waveform-in chunk step (conan_step_wav): wav [n, samples] cuda float32, samples = seg*hop (0 .. seg*hop when final);
         slots with an input rate (set_input_rate) take seg*hop*rate/model_rate samples instead.
         -> (emit, codes [n, seg], mel [n, emit, 80], wav [n, emit*hop]); emit = 0: no chunk this call (the first call, the end of a
-        drain).  mel: dict of Context.wav2mel's front-end keywords (framing 0 only)."""
+        drain).  mel: dict of Context.wav2mel's front-end keywords (framing 0 only).  Slots with an input format (set_input_format)
+        take int16 ('s16') or uint8 ('ulaw' / 'alaw') rows; with an output rate, stride or format wav is a list of 1-D rows, each
+        in its slot's dtype."""
         return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, False)
 
     def step_wav_async(self, slots, wav, final=False, codes=None, mel_out=None, wav_out=None, mel=None):
@@ -428,8 +537,9 @@ class Streams:
         a, p = _i32(slots)
         n = len(a)
         hop, nm = self.ctx.hop, self.ctx.cfg.num_mels
-        wav = wav.to(self.dev, torch.float32).contiguous()
         assert wav.dim() == 2 and wav.shape[0] == n, wav.shape
+        samples = wav.shape[1]
+        wav, _, _ = self._in_rows(a, wav, samples)      # (rows samples * 4 bytes apart, whatever the format)
         if codes is None:
             codes = torch.empty(n, self.seg, dtype=torch.int32, device=self.dev)
         if mel_out is None:
@@ -441,13 +551,13 @@ class Streams:
         fn = self.lib.conan_step_wav_async if pipelined else self.lib.conan_step_wav
         if pipelined:
             self._keep.append((wav, wav_out, codes, mel_out))
-        _lib.check(fn(self.h, p, n, wav.shape[1], int(bool(final)), _ptr(wav), C.byref(mc), _ptr(codes), _ptr(mel_out), _ptr(wav_out),
+        _lib.check(fn(self.h, p, n, samples, int(bool(final)), _ptr(wav), C.byref(mc), _ptr(codes), _ptr(mel_out), _ptr(wav_out),
                       C.byref(emit), _stream()))
         if not pipelined:
             self._release()
         e = emit.value
-        if self.output_rates or self.output_ld:
-            w = self._wav_rows(wav_out, n, self.output_ld or e * hop) if e else [wav_out.view(-1)[:0]] * n
+        if self.output_rates or self.output_ld or self.output_formats:
+            w = self._wav_rows(wav_out, a, self.output_ld or e * hop) if e else [wav_out.view(-1)[:0].view(self._out_dtype(s)) for s in a]
         else:
             w = wav_out.view(-1)[:n * e * hop].view(n, e * hop)
         return e, codes, mel_out.view(-1)[:n * e * nm].view(n, e, nm), w
@@ -456,8 +566,10 @@ class Streams:
         """Waveform-in chunk step for slots at different positions of their utterances (conan_step_wav_ragged): slot i takes the
         first samples[i] samples of wav row i (wav [n, <= seg*hop] cuda float32, or None when every samples[i] is 0) and is stepped
         as step_wav([slot], samples[i], final[i]) alone would step it.  Rows wider than seg*hop (slots with an input rate above the
-        model rate) go through conan_step_wav_ragged_ld with the row width as stride.  -> (emit: list of n ints, codes [n, seg], mel [n, seg, 80],
-        wav [n, seg*hop]): row i holds emit[i] frames; the rest of the row is left as it was."""
+        model rate) go through conan_step_wav_ragged_ld with the row width as stride.  wav may also be a list of n 1-D rows, each in the
+        dtype of its slot's input format (float32, int16, uint8): they are packed from the start of rows a whole number of 4-byte
+        units apart.  -> (emit: list of n ints, codes [n, seg], mel [n, seg, 80], wav [n, seg*hop] float32 storage): row i holds
+        emit[i] frames (wav_row(wav, i, slot, count) gives it in the slot's output dtype); the rest of the row is left as it was."""
         return self._step_wav_ragged(slots, wav, samples, final, codes, mel_out, wav_out, mel, False)
 
     def step_wav_ragged_async(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None):
@@ -472,13 +584,8 @@ class Streams:
         fi, fp = _i32([int(bool(f)) for f in final])
         assert len(sm) == n and len(fi) == n, (n, len(sm), len(fi))
         ld = L
-        if wav is not None:
-            wav = wav.to(self.dev, torch.float32)
-            assert wav.dim() == 2 and wav.shape[0] == n, wav.shape
-            if wav.shape[1] < L:                      # rows are seg*hop apart in conan_step_wav_ragged
-                wav = torch.nn.functional.pad(wav, (0, L - wav.shape[1]))
-            ld = wav.shape[1]
-            wav = wav.contiguous()
+        if wav is not None:                           # rows are seg*hop floats apart in conan_step_wav_ragged, wider ones go through _ld
+            wav, ld, _ = self._in_rows(a, wav, L)
         if codes is None:
             codes = torch.empty(n, self.seg, dtype=torch.int32, device=self.dev)
         if mel_out is None:

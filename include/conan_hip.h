@@ -453,6 +453,57 @@ int conan_streams_output_pending(conan_streams* s, const int32_t* slots, int n, 
  * CONAN_ERR_STATE until a reset that includes CONAN_MODEL_HIFIGAN. */
 int conan_streams_flush_output(conan_streams* s, const int32_t* slots, int n, float* wav_out_dev, int64_t wav_ld, void* stream);
 
+/* Sample formats of the audio rows (added within ABI 9: a caller detects it by the exported symbols).  wav_dev and wav_out_dev carry
+ * [-1, 1] floats by default; a slot can take and deliver 16-bit PCM or G.711 instead, converted on the GPU by the arithmetic below,
+ * the same in every entry point. */
+#define CONAN_SAMPLE_F32  0   /* 4 bytes, today's behaviour */
+#define CONAN_SAMPLE_S16  1   /* 2 bytes, little-endian signed */
+#define CONAN_SAMPLE_ULAW 2   /* 1 byte, ITU-T G.711 mu-law */
+#define CONAN_SAMPLE_ALAW 3   /* 1 byte, ITU-T G.711 A-law  */
+/* Decode.  Decoding is exact; every result is a float with at most 16 significant bits.
+ *   S16:  x = v / 32768.0f.
+ *   ULAW (byte b):  u = ~b & 0xFF;  t = (((u & 15) << 3) + 0x84) << ((u >> 4) & 7);  v = (u & 0x80) ? 0x84 - t : t - 0x84 (the range
+ *         is +-32124);  x = v / 32768.
+ *   ALAW (byte b):  a = b ^ 0x55, m = a & 15, e = (a >> 4) & 7;  t = e == 0 ? (m << 4) + 8 : ((m << 4) + 0x108) << (e - 1);
+ *         v = (a & 0x80) ? t : -t (the range is +-32256);  x = v / 32768.
+ * Encode.  The input is a finite float x.  First s = clamp(rint(x * 32768), -32768, 32767), rounding to nearest and ties to even.
+ *   S16:  store s.
+ *   ULAW: p = s >> 2 (arithmetic shift); neg = p < 0; p = neg ? -p : p;  p = min(p, 8159) + 0x21;
+ *         seg = number of values in {0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF, 0x1FFF} that are < p;
+ *         u = seg >= 8 ? 0x7F : (seg << 4) | ((p >> (seg + 1)) & 15);  byte = u ^ (neg ? 0x7F : 0xFF).
+ *   ALAW: p = s >> 3; neg = p < 0; p = neg ? -p - 1 : p;
+ *         seg = number of values in {0x1F, 0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF} that are < p;
+ *         a = seg >= 8 ? 0x7F : (seg << 4) | ((seg < 2 ? p >> 1 : p >> seg) & 15);  byte = a ^ (neg ? 0x55 : 0xD5).
+ * These are the tables of Python's audioop (ulaw2lin, alaw2lin, lin2ulaw, lin2alaw at width 2) on all 256 codes and all 65536 16-bit
+ * values.  encode(decode(b)) == b for every code except mu-law 0x7F (negative zero), which comes back as 0xFF.
+ *
+ * Input format.  It applies to wav_dev of conan_step_wav[_async] and conan_step_wav_ragged[_ld][_async].  Row i holds samples[i] samples
+ * of slot i's format, packed from the start of the row.  Row strides stay in 4-byte units, so existing signatures and every f32 call
+ * are unchanged: row i begins i * wav_ld * 4 bytes after wav_dev; the fixed-stride entry points use samples * 4 or seg * hop * 4.
+ * wav_dev must be 4-byte aligned.  A row fits when samples[i] * bytes_per_sample <= wav_ld * 4; otherwise the call is
+ * CONAN_ERR_INVALID before anything changes (a 48 kHz s16 slot, 7680 bytes, does not fit conan_step_wav_ragged's default stride of
+ * 5120 bytes and needs _ld; a 48 kHz mu-law slot, 3840 bytes, fits).  `samples` keeps counting samples.  Slots of one call may mix
+ * formats freely, with or without input rates.  A format is stateless: it may be set at any time between calls and takes effect from
+ * the next call; it persists across resets; CONAN_SAMPLE_F32 restores today's path.  The decoded float is what the resampler's
+ * history ring stores and what the front end sees.  A slot with a format and no rate is decoded by the input resampler's launch
+ * (one more launch per wav-in call that has such a row with samples); setting a format allocates no stream state
+ * (conan_streams_state_bytes is unchanged). */
+int conan_streams_set_input_format(conan_streams* s, const int32_t* slots, int n, int format);
+/* Output format.  It applies to wav_out_dev of every entry point that writes it: the list in the conan_streams_set_output_rate
+ * comment, plus conan_streams_flush_output.  Packing, stride and alignment follow the input rules: strides come from
+ * conan_streams_set_output_ld and the flush's wav_ld, in 4-byte units; a row fits when count * bytes_per_sample <= ld * 4.
+ * conan_streams_output_samples and _output_pending keep counting samples.  Bytes of a row past its count are left untouched, at byte
+ * granularity.  pre_tanh_dev, the taps, mel_out_dev and codes_dev stay fp32.  Encoding happens after the output resampler, where one
+ * is set; a slot with a format and no rate is encoded by the output resampler's launch (one more launch per vocoder step that has
+ * such a row). */
+int conan_streams_set_output_format(conan_streams* s, const int32_t* slots, int n, int format);
+/* Whole signals: n rows of `samples`, any format to any format, going through the float rule above (f32 -> f32 is a copy); row i of
+ * src_dev / dst_dev begins i * src_ld * 4 / i * dst_ld * 4 bytes after the pointer (both 4-byte aligned; a row fits as above, bytes of
+ * a dst row past `samples` are left untouched).  It is the bit-exact yardstick for both streaming sides, and converts reference clips
+ * that arrive as PCM.  An unknown format, a slot out of range or a null handle returns the usual status with nothing changed. */
+int conan_convert_samples(conan_ctx* ctx, int src_format, const void* src_dev, int64_t src_ld, int dst_format, void* dst_dev, int64_t dst_ld,
+                          int n, int64_t samples, void* stream);
+
 /* Measurement hook (replaces the reference's Timer('hifigan') around the vocoder forward,
  * utils/commons/meters.py:21-42, tasks/tts/vocoder_infer/hifigan.py:28): between begin and end every
  * launch of the conv_mfma kernel family is bracketed by HIP events on its launch stream.  end() waits
