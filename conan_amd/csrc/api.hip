@@ -1,7 +1,4 @@
 // extern "C" surface of libconan_hip.so (include/conan_hip.h).
-#include <climits>
-#include <functional>
-
 #include "streams.h"
 
 static thread_local std::string g_err;
@@ -51,6 +48,122 @@ static void validate_cfg(const conan_cfg& c) {
     if (c.dec_num_blocks < 1 || c.dec_num_blocks > CONAN_MAX_DEC_BLOCKS) throw Error(CONAN_ERR_INVALID, "dec_num_blocks");
     if (c.nvq < 1) throw Error(CONAN_ERR_INVALID, "nvq");
   }
+}
+
+// The preconditions of every fused chunk step (conan_step[_async], the wav-in steps): all three models, an upsampler without look-ahead.
+void check_chunk_step(const conan_streams* s, const char* who) {
+  const int all = CONAN_MODEL_EMFORMER | CONAN_MODEL_CONAN | CONAN_MODEL_HIFIGAN;
+  if ((s->ctx->cfg.models & all) != all) throw Error(CONAN_ERR_STATE, std::string(who) + " needs all three models in the context");
+  if (s->ctx->cfg.voc_upsample == 2) throw Error(CONAN_ERR_UNSUPPORTED, "fused chunk steps carry vocoder state from chunk to chunk; upsample 'nn' (CausalUpsampleBlock1) looks ahead: "
+                                                                      "step the Emformer and decoder per chunk and run conan_hifigan_step over the mel prefix after a reset (inference/Conan.py:147-155)");
+}
+
+// The stages of one chunk step on `st` for the slots set_slots has just installed (conan_step, conan_step_wav).
+void step_blocking(conan_streams* s, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev, float* mel_out_dev,
+                   float* wav_out_dev, hipStream_t st, const conan_streams::OutPlan& op) {
+  const int seg = s->ctx->cfg.emf_segment;
+  int* codes_seg = codes_dev ? codes_dev : s->d_codes;
+  s->emformer_step(n, mel_chunk_dev, nullptr, nullptr, codes_seg, st);
+  const int* codes_emit = codes_seg;
+  if (emit != seg && n > 1) {
+    int* compact = s->d_codes + (size_t)s->max_slots * s->max_frames;
+    cnk::launch_copy_int_rows(compact, codes_seg, n, emit, seg, st);
+    codes_emit = compact;
+  }
+  float* mel = mel_out_dev ? mel_out_dev : s->c_mel.base;
+  { conan_decoder_taps none; memset(&none, 0, sizeof(none)); s->decoder_step(n, emit, codes_emit, mel, none, st); }
+  s->hifigan_step(n, emit, mel, wav_out_dev, nullptr, st, nullptr, &op);
+}
+
+// Everything of conan_step_async after its argument checks; `pre` (may be empty) enqueues work on the Emformer stream right
+// before the step's Emformer launch, behind the step's input event and slot table.
+void step_pipelined(conan_streams* s, const int32_t* slots, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev, float* mel_out_dev,
+                    float* wav_out_dev, void* stream, const std::function<void(hipStream_t)>& pre, const conan_streams::OutPlan& op) {
+  const int seg = s->ctx->cfg.emf_segment;
+  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+  s->async_init();
+  const long long t = s->async_steps;
+  constexpr int NP = conan_streams::NP;
+  const int p = (int)(t % NP), pl = (int)((t + NP - 1) % NP);      // hand-off ring positions of this step and of the previous one
+  // Three stages on three internal streams: Emformer(t) -> codes, decoder(t) -> mel, vocoder(t) -> audio.  With steps
+  // issued back to back the stages work on consecutive chunks at the same time (Emformer of chunk t+2 beside the decoder
+  // of t+1 beside the vocoder of t): the decoder's ~50 latency-bound launches no longer queue behind the Emformer's
+  // one long launch, and their tail no longer leaves the vocoder stream idle.
+  // An EMPTY pipeline (the first step, or every earlier step has completed - e.g. behind the caller's join + synchronize): nothing of
+  // this stream-set can overlap this step's Emformer launch, which the decoder and vocoder of the same chunk wait for - it may take
+  // the blocking steps' launch shape (one workgroup per CU where the stream-set is alone on the device: 136 instead of 190 us on
+  // the first chunk's critical path; the feed-forward's sum does not depend on the cluster size, so the bits are the same).
+  s->pipe_idle = t == 0 || (hipEventQuery(s->ev_emf[pl]) == hipSuccess && hipEventQuery(s->ev_front[pl]) == hipSuccess && hipEventQuery(s->ev_voc[pl]) == hipSuccess);
+  (void)hipGetLastError();      // (hipErrorNotReady from a query is an answer, not an error)
+  // inputs are ready in the caller's stream order
+  HIP_CHECK(hipEventRecord(s->ev_in[p], (hipStream_t)stream));
+  HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_in[p], 0));
+  const bool tl = s->tl_on && s->tl_n < (int)s->tl_ev.size() / 6;
+  hipEvent_t* te = tl ? &s->tl_ev[(size_t)s->tl_n * 6] : nullptr;
+  // a changed slot list rewrites the table the in-flight decoder / vocoder still read: drain them first
+  bool same = (int)s->h_slots.size() == n;
+  for (int i = 0; same && i < n; ++i) same = s->h_slots[i] == slots[i];
+  if (!same && t >= 1) {
+    HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_front[pl], 0));
+    HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_voc[pl], 0));
+  }
+  s->set_slots(slots, n, s->st_emf);
+  // the code buffer at this ring position is free once the decoder of step t-NP has read it: the Emformer may run
+  // NP steps ahead of the decoder (it is dispatched late - its 129 KB of LDS per block only fit on CUs that a vocoder
+  // launch has left - so the decoder must not have to wait for the Emformer of its own chunk)
+  if (t >= NP) HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_front[p], 0));
+  int* codes_seg = s->codes_hand[p];
+  // developer timing switch (results are then meaningless): CONAN_SKIP_STAGE bit 0 skips the Emformer launch, bit 1 the decoder's
+#ifdef CONAN_DEV_SWITCHES        // `make DEV=1`: timing experiments only, never in the shipped library (a skipped stage returns garbage with CONAN_OK)
+  static const int skip = ch::dev_getenv("CONAN_SKIP_STAGE") ? atoi(ch::dev_getenv("CONAN_SKIP_STAGE")) : 0;
+  // (the Emformer's workgroups need whole CUs for ~0.15 ms; they are kept away from the pair kernel's launches: see ev_wide)
+  static const bool hold = ch::dev_getenv("CONAN_EMF_HOLD") != nullptr;      // (off by default: see streams.h, ev_wide)
+#else
+  constexpr int skip = 0; constexpr bool hold = false;
+#endif
+  if (hold && t >= 2 && s->ev_wide[(t + NP - 2) % NP] && s->wide_marked[(t + NP - 2) % NP]) HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_wide[(t + NP - 2) % NP], 0));
+  if (pre) pre(s->st_emf);      // conan_step_wav_async: the streaming front-end writes the chunk this step consumes
+  if (tl) HIP_CHECK(hipEventRecord(te[0], s->st_emf));
+  if (!(skip & 1)) s->emformer_step(n, mel_chunk_dev, nullptr, nullptr, codes_seg, s->st_emf);
+  if (tl) HIP_CHECK(hipEventRecord(te[1], s->st_emf));
+  HIP_CHECK(hipEventRecord(s->ev_emf[p], s->st_emf));
+  HIP_CHECK(hipStreamWaitEvent(s->st_front, s->ev_emf[p], 0));
+  // the mel hand-off buffer at this ring position is free once the vocoder of step t-NP has copied it into its ring
+  if (t >= NP) HIP_CHECK(hipStreamWaitEvent(s->st_front, s->ev_voc[p], 0));
+  if (tl) HIP_CHECK(hipEventRecord(te[2], s->st_front));
+  // the caller's copies of the step's codes and mel frames travel with the decoder step (operators of its one launch)
+  conan_streams::DecExtra ex;
+  if (codes_dev) { ex.codes_dst = codes_dev; ex.codes_src = codes_seg; ex.codes_words = n * seg; }
+  ex.mel_out2 = mel_out_dev;
+  const int* codes_emit = codes_seg;
+  if (emit != seg && n > 1) {
+    int* compact = s->d_codes + (size_t)s->max_slots * s->max_frames;
+    cnk::launch_copy_int_rows(compact, codes_seg, n, emit, seg, s->st_front);
+    codes_emit = compact;
+  }
+  float* mel = s->mel_hand[p];
+  if (!(skip & 2)) { conan_decoder_taps none; memset(&none, 0, sizeof(none)); s->decoder_step(n, emit, codes_emit, mel, none, s->st_front, &ex); }
+  if (tl) HIP_CHECK(hipEventRecord(te[3], s->st_front));
+  HIP_CHECK(hipEventRecord(s->ev_front[p], s->st_front));
+  HIP_CHECK(hipStreamWaitEvent(s->st_voc, s->ev_front[p], 0));
+  if (s->fence_set) {      // the caller's output fence: only the stage that writes the audio buffer waits for it
+    if (s->fence_event) HIP_CHECK(hipStreamWaitEvent(s->st_voc, s->fence_event, 0));
+    else {
+      HIP_CHECK(hipEventRecord(s->ev_fence[p], s->fence_stream));
+      HIP_CHECK(hipStreamWaitEvent(s->st_voc, s->ev_fence[p], 0));
+    }
+    s->fence_set = false; s->fence_event = nullptr;
+  }
+  if (tl) HIP_CHECK(hipEventRecord(te[4], s->st_voc));
+  if (!s->ev_wide[p]) HIP_CHECK(hipEventCreateWithFlags(&s->ev_wide[p], hipEventDisableTiming));
+  s->mark_wide = s->ev_wide[p];
+  s->wide_marked[p] = false;
+  s->hifigan_step(n, emit, mel, wav_out_dev, nullptr, s->st_voc, nullptr, &op);
+  s->mark_wide = nullptr;
+  if (tl) { HIP_CHECK(hipEventRecord(te[5], s->st_voc)); s->tl_n++; }
+  HIP_CHECK(hipEventRecord(s->ev_voc[p], s->st_voc));
+  if (s->clock_on && s->clock_n < (int)s->clock_ev.size()) HIP_CHECK(hipEventRecord(s->clock_ev[s->clock_n++], s->st_voc));   // step completion stamp
+  s->async_steps = t + 1;
 }
 
 extern "C" {
@@ -182,20 +295,20 @@ int conan_streams_create_opts(conan_ctx* ctx, int max_slots, int max_frames, int
         s->d_guard = reinterpret_cast<unsigned*>(s->alloc(16));
         HIP_CHECK(hipMemcpy(s->d_guard + 2, &hdev, sizeof(hdev), hipMemcpyHostToDevice));
       }
-      s->slot_seen.assign(max_slots, 0); s->has_ref.assign(max_slots, 0); s->voc_fresh.assign(max_slots, 1); s->voc_samples.assign(max_slots, 0); s->in_fmt.assign(max_slots, 0); s->out_fmt.assign(max_slots, 0);
+      s->slot_seen.assign(max_slots, 0); s->has_ref.assign(max_slots, 0); s->voc_fresh.assign(max_slots, 1); s->wav_out.voc_samples.assign(max_slots, 0); s->wav_in.in_fmt.assign(max_slots, 0); s->wav_out.out_fmt.assign(max_slots, 0);
       s->pin.init((size_t)max_slots + cnk::kSlotTablePad);
       s->pos_emf = (int*)s->alloc(max_slots); s->pos_dec = (int*)s->alloc(max_slots); s->pos_voc = (int*)s->alloc(max_slots);
       std::vector<int> id(max_slots);
       for (int i = 0; i < max_slots; ++i) id[i] = i;
       HIP_CHECK(hipMemcpy(s->d_ident, id.data(), max_slots * sizeof(int), hipMemcpyHostToDevice));
-      s->fe_slot.assign(max_slots, conan_streams::FeSlot());
+      s->wav_in.fe_slot.assign(max_slots, conan_streams::FeSlot());
       if ((ctx->cfg.models & 7) == 7) {     // streaming front-end rings, sized for fft_size <= 2048 at the vocoder's hop
         const int seg = ctx->cfg.emf_segment, rc = ctx->cfg.emf_right_context, hop = ctx->hop;
-        s->fe_LA = ch::next_pow2(2048 + seg * hop);
-        s->fe_LM = ch::next_pow2(2 * (seg + rc) + seg + 2048 / hop + 4);
-        s->fe_audio = s->alloc((size_t)max_slots * s->fe_LA);
-        s->fe_mel = s->alloc((size_t)max_slots * s->fe_LM * ctx->cfg.emf_input_dim);
-        s->fe_chunk = s->alloc((size_t)max_slots * (seg + rc) * ctx->cfg.emf_input_dim);
+        s->wav_in.fe_LA = ch::next_pow2(2048 + seg * hop);
+        s->wav_in.fe_LM = ch::next_pow2(2 * (seg + rc) + seg + 2048 / hop + 4);
+        s->wav_in.fe_audio = s->alloc((size_t)max_slots * s->wav_in.fe_LA);
+        s->wav_in.fe_mel = s->alloc((size_t)max_slots * s->wav_in.fe_LM * ctx->cfg.emf_input_dim);
+        s->wav_in.fe_chunk = s->alloc((size_t)max_slots * (seg + rc) * ctx->cfg.emf_input_dim);
       }
       if (ctx->cfg.models & CONAN_MODEL_HIFIGAN) s->build_vocoder();
       if (ctx->cfg.models & CONAN_MODEL_EMFORMER) s->build_emformer();
@@ -225,20 +338,20 @@ int conan_streams_reset(conan_streams* s, const int32_t* slots, int n, int which
       zero(s->voc_state, s->pos_voc);
       for (int i = 0; i < n; ++i) s->voc_fresh[slots[i]] = 1;
       // the output rate stays; the output resampler restarts (output index 0, inputs before the first are zero: the ring needs no clearing)
-      for (int i = 0; i < n; ++i) s->voc_samples[slots[i]] = 0;
-      if (!s->or_slot.empty())
-        for (int i = 0; i < n; ++i) { conan_streams::OrSlot& o = s->or_slot[slots[i]]; o.out = 0; o.flushed = 0; }
+      for (int i = 0; i < n; ++i) s->wav_out.voc_samples[slots[i]] = 0;
+      if (!s->wav_out.or_slot.empty())
+        for (int i = 0; i < n; ++i) { conan_streams::OrSlot& o = s->wav_out.or_slot[slots[i]]; o.out = 0; o.flushed = 0; }
     }
     if (models & CONAN_MODEL_EMFORMER) zero(s->emf_state, s->pos_emf);
     if (models & CONAN_MODEL_CONAN) zero(s->dec_state, s->pos_dec);
-    if ((which & CONAN_MODEL_FRONTEND) && s->fe_audio) {
-      cnk::launch_zero_slots(s->fe_audio, s->fe_LA, s->fe_LA, s->d_slots, n, st);
-      const long long mel_floats = (long long)s->fe_LM * s->ctx->cfg.emf_input_dim;
-      cnk::launch_zero_slots(s->fe_mel, mel_floats, mel_floats, s->d_slots, n, st);
-      for (int i = 0; i < n; ++i) s->fe_slot[slots[i]] = conan_streams::FeSlot();
+    if ((which & CONAN_MODEL_FRONTEND) && s->wav_in.fe_audio) {
+      cnk::launch_zero_slots(s->wav_in.fe_audio, s->wav_in.fe_LA, s->wav_in.fe_LA, s->d_slots, n, st);
+      const long long mel_floats = (long long)s->wav_in.fe_LM * s->ctx->cfg.emf_input_dim;
+      cnk::launch_zero_slots(s->wav_in.fe_mel, mel_floats, mel_floats, s->d_slots, n, st);
+      for (int i = 0; i < n; ++i) s->wav_in.fe_slot[slots[i]] = conan_streams::FeSlot();
       // the input rate stays; the resampler's history restarts (inputs before the first are zero, the ring needs no clearing)
-      if (!s->rs_slot.empty())
-        for (int i = 0; i < n; ++i) { conan_streams::RsSlot& r = s->rs_slot[slots[i]]; r.in = 0; r.out = 0; r.phase = 0; }
+      if (!s->wav_in.rs_slot.empty())
+        for (int i = 0; i < n; ++i) { conan_streams::RsSlot& r = s->wav_in.rs_slot[slots[i]]; r.in = 0; r.out = 0; r.phase = 0; }
     }
   });
 }
@@ -396,31 +509,6 @@ int conan_hifigan_step(conan_streams* s, const int32_t* slots, int n, int frames
   });
 }
 
-// The preconditions of every fused chunk step (conan_step[_async], the wav-in steps): all three models, an upsampler without look-ahead.
-static void check_chunk_step(const conan_streams* s, const char* who) {
-  const int all = CONAN_MODEL_EMFORMER | CONAN_MODEL_CONAN | CONAN_MODEL_HIFIGAN;
-  if ((s->ctx->cfg.models & all) != all) throw Error(CONAN_ERR_STATE, std::string(who) + " needs all three models in the context");
-  if (s->ctx->cfg.voc_upsample == 2) throw Error(CONAN_ERR_UNSUPPORTED, "fused chunk steps carry vocoder state from chunk to chunk; upsample 'nn' (CausalUpsampleBlock1) looks ahead: "
-                                                                      "step the Emformer and decoder per chunk and run conan_hifigan_step over the mel prefix after a reset (inference/Conan.py:147-155)");
-}
-
-// The stages of one chunk step on `st` for the slots set_slots has just installed (conan_step, conan_step_wav).
-static void step_blocking(conan_streams* s, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev, float* mel_out_dev,
-                          float* wav_out_dev, hipStream_t st, const conan_streams::OutPlan& op) {
-  const int seg = s->ctx->cfg.emf_segment;
-  int* codes_seg = codes_dev ? codes_dev : s->d_codes;
-  s->emformer_step(n, mel_chunk_dev, nullptr, nullptr, codes_seg, st);
-  const int* codes_emit = codes_seg;
-  if (emit != seg && n > 1) {
-    int* compact = s->d_codes + (size_t)s->max_slots * s->max_frames;
-    cnk::launch_copy_int_rows(compact, codes_seg, n, emit, seg, st);
-    codes_emit = compact;
-  }
-  float* mel = mel_out_dev ? mel_out_dev : s->c_mel.base;
-  { conan_decoder_taps none; memset(&none, 0, sizeof(none)); s->decoder_step(n, emit, codes_emit, mel, none, st); }
-  s->hifigan_step(n, emit, mel, wav_out_dev, nullptr, st, nullptr, &op);
-}
-
 int conan_step(conan_streams* s, const int32_t* slots, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev,
                float* mel_out_dev, float* wav_out_dev, void* stream) {
   return guarded([&] {
@@ -435,98 +523,6 @@ int conan_step(conan_streams* s, const int32_t* slots, int n, int emit, const fl
     s->set_slots(slots, n, st);
     step_blocking(s, n, emit, mel_chunk_dev, codes_dev, mel_out_dev, wav_out_dev, st, op);
   });
-}
-
-// Everything of conan_step_async after its argument checks; `pre` (may be empty) enqueues work on the Emformer stream right
-// before the step's Emformer launch, behind the step's input event and slot table.
-static void step_pipelined(conan_streams* s, const int32_t* slots, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev,
-                           float* mel_out_dev, float* wav_out_dev, void* stream, const std::function<void(hipStream_t)>& pre,
-                           const conan_streams::OutPlan& op) {
-  const int seg = s->ctx->cfg.emf_segment;
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  s->async_init();
-  const long long t = s->async_steps;
-  constexpr int NP = conan_streams::NP;
-  const int p = (int)(t % NP), pl = (int)((t + NP - 1) % NP);      // hand-off ring positions of this step and of the previous one
-  // Three stages on three internal streams: Emformer(t) -> codes, decoder(t) -> mel, vocoder(t) -> audio.  With steps
-  // issued back to back the stages work on consecutive chunks at the same time (Emformer of chunk t+2 beside the decoder
-  // of t+1 beside the vocoder of t): the decoder's ~50 latency-bound launches no longer queue behind the Emformer's
-  // one long launch, and their tail no longer leaves the vocoder stream idle.
-  // An EMPTY pipeline (the first step, or every earlier step has completed - e.g. behind the caller's join + synchronize): nothing of
-  // this stream-set can overlap this step's Emformer launch, which the decoder and vocoder of the same chunk wait for - it may take
-  // the blocking steps' launch shape (one workgroup per CU where the stream-set is alone on the device: 136 instead of 190 us on
-  // the first chunk's critical path; the feed-forward's sum does not depend on the cluster size, so the bits are the same).
-  s->pipe_idle = t == 0 || (hipEventQuery(s->ev_emf[pl]) == hipSuccess && hipEventQuery(s->ev_front[pl]) == hipSuccess && hipEventQuery(s->ev_voc[pl]) == hipSuccess);
-  (void)hipGetLastError();      // (hipErrorNotReady from a query is an answer, not an error)
-  // inputs are ready in the caller's stream order
-  HIP_CHECK(hipEventRecord(s->ev_in[p], (hipStream_t)stream));
-  HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_in[p], 0));
-  const bool tl = s->tl_on && s->tl_n < (int)s->tl_ev.size() / 6;
-  hipEvent_t* te = tl ? &s->tl_ev[(size_t)s->tl_n * 6] : nullptr;
-  // a changed slot list rewrites the table the in-flight decoder / vocoder still read: drain them first
-  bool same = (int)s->h_slots.size() == n;
-  for (int i = 0; same && i < n; ++i) same = s->h_slots[i] == slots[i];
-  if (!same && t >= 1) {
-    HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_front[pl], 0));
-    HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_voc[pl], 0));
-  }
-  s->set_slots(slots, n, s->st_emf);
-  // the code buffer at this ring position is free once the decoder of step t-NP has read it: the Emformer may run
-  // NP steps ahead of the decoder (it is dispatched late - its 129 KB of LDS per block only fit on CUs that a vocoder
-  // launch has left - so the decoder must not have to wait for the Emformer of its own chunk)
-  if (t >= NP) HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_front[p], 0));
-  int* codes_seg = s->codes_hand[p];
-  // developer timing switch (results are then meaningless): CONAN_SKIP_STAGE bit 0 skips the Emformer launch, bit 1 the decoder's
-#ifdef CONAN_DEV_SWITCHES        // `make DEV=1`: timing experiments only, never in the shipped library (a skipped stage returns garbage with CONAN_OK)
-  static const int skip = ch::dev_getenv("CONAN_SKIP_STAGE") ? atoi(ch::dev_getenv("CONAN_SKIP_STAGE")) : 0;
-  // (the Emformer's workgroups need whole CUs for ~0.15 ms; they are kept away from the pair kernel's launches: see ev_wide)
-  static const bool hold = ch::dev_getenv("CONAN_EMF_HOLD") != nullptr;      // (off by default: see streams.h, ev_wide)
-#else
-  constexpr int skip = 0; constexpr bool hold = false;
-#endif
-  if (hold && t >= 2 && s->ev_wide[(t + NP - 2) % NP] && s->wide_marked[(t + NP - 2) % NP]) HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_wide[(t + NP - 2) % NP], 0));
-  if (pre) pre(s->st_emf);      // conan_step_wav_async: the streaming front-end writes the chunk this step consumes
-  if (tl) HIP_CHECK(hipEventRecord(te[0], s->st_emf));
-  if (!(skip & 1)) s->emformer_step(n, mel_chunk_dev, nullptr, nullptr, codes_seg, s->st_emf);
-  if (tl) HIP_CHECK(hipEventRecord(te[1], s->st_emf));
-  HIP_CHECK(hipEventRecord(s->ev_emf[p], s->st_emf));
-  HIP_CHECK(hipStreamWaitEvent(s->st_front, s->ev_emf[p], 0));
-  // the mel hand-off buffer at this ring position is free once the vocoder of step t-NP has copied it into its ring
-  if (t >= NP) HIP_CHECK(hipStreamWaitEvent(s->st_front, s->ev_voc[p], 0));
-  if (tl) HIP_CHECK(hipEventRecord(te[2], s->st_front));
-  // the caller's copies of the step's codes and mel frames travel with the decoder step (operators of its one launch)
-  conan_streams::DecExtra ex;
-  if (codes_dev) { ex.codes_dst = codes_dev; ex.codes_src = codes_seg; ex.codes_words = n * seg; }
-  ex.mel_out2 = mel_out_dev;
-  const int* codes_emit = codes_seg;
-  if (emit != seg && n > 1) {
-    int* compact = s->d_codes + (size_t)s->max_slots * s->max_frames;
-    cnk::launch_copy_int_rows(compact, codes_seg, n, emit, seg, s->st_front);
-    codes_emit = compact;
-  }
-  float* mel = s->mel_hand[p];
-  if (!(skip & 2)) { conan_decoder_taps none; memset(&none, 0, sizeof(none)); s->decoder_step(n, emit, codes_emit, mel, none, s->st_front, &ex); }
-  if (tl) HIP_CHECK(hipEventRecord(te[3], s->st_front));
-  HIP_CHECK(hipEventRecord(s->ev_front[p], s->st_front));
-  HIP_CHECK(hipStreamWaitEvent(s->st_voc, s->ev_front[p], 0));
-  if (s->fence_set) {      // the caller's output fence: only the stage that writes the audio buffer waits for it
-    if (s->fence_event) HIP_CHECK(hipStreamWaitEvent(s->st_voc, s->fence_event, 0));
-    else {
-      HIP_CHECK(hipEventRecord(s->ev_fence[p], s->fence_stream));
-      HIP_CHECK(hipStreamWaitEvent(s->st_voc, s->ev_fence[p], 0));
-    }
-    s->fence_set = false; s->fence_event = nullptr;
-  }
-  if (tl) HIP_CHECK(hipEventRecord(te[4], s->st_voc));
-  if (!s->ev_wide[p]) HIP_CHECK(hipEventCreateWithFlags(&s->ev_wide[p], hipEventDisableTiming));
-  s->mark_wide = s->ev_wide[p];
-  s->wide_marked[p] = false;
-  s->hifigan_step(n, emit, mel, wav_out_dev, nullptr, s->st_voc, nullptr, &op);
-  s->mark_wide = nullptr;
-  if (tl) { HIP_CHECK(hipEventRecord(te[5], s->st_voc)); s->tl_n++; }
-  HIP_CHECK(hipEventRecord(s->ev_voc[p], s->st_voc));
-  if (s->clock_on && s->clock_n < (int)s->clock_ev.size()) HIP_CHECK(hipEventRecord(s->clock_ev[s->clock_n++], s->st_voc));   // step completion stamp
-  s->async_steps = t + 1;
 }
 
 // Pipelined variant of conan_step.  Within one stream-set the three stages of a chunk are strictly ordered, but the
@@ -546,442 +542,38 @@ int conan_step_async(conan_streams* s, const int32_t* slots, int n, int emit, co
   });
 }
 
-// Input resampler of a wav-in call (conan_streams_set_input_rate).  Per call row: the model-rate samples and final flag the front-end
-// gets - a row without a rate passes its own; a row with one hands over the longest prefix of outputs whose last tap has arrived (at
-// most seg * hop; after the input's final call, what is left, seg * hop at a time, final on the call that delivers the last sample).
-// When a row with a rate has input or owed output, or a row with a sample format (conan_streams_set_input_format) has input, one
-// resample_stream_kernel launch writes every row's model-rate samples to staging (rows without a rate decoded and copied) and the
-// front-end reads them there.  rs_plan checks every row and changes nothing.
-struct RsPlan {
-  std::vector<int32_t> mm, ff;          // per row: front-end samples and final flag
-  std::vector<char> rate;               // per row: the slot has a rate
-  std::vector<long long> in_after;      // per row with a rate: input samples received after the call
-  std::vector<cnk::RsRow> rows;
-  bool any = false, launch = false;
-  int tiles = 1, win = 0;
-  double flops = 0;
-};
-
-static RsPlan rs_plan(const conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final_, const float* wav_dev,
-                      long long wav_ld, const conan_mel_cfg& m, const char* who) {
-  RsPlan P;
-  P.mm.assign(samples, samples + n); P.ff.assign(final_, final_ + n); P.rate.assign(n, 0); P.in_after.assign(n, 0);
-  if (s->rs_slot.empty()) return P;      // (neither a rate nor a format was ever set: the caller's rows go to the front-end as they are)
-  const int S = s->ctx->cfg.emf_segment * s->ctx->hop;
-  P.rows.resize(n);
-  for (int i = 0; i < n; ++i) {
-    const conan_streams::RsSlot& r = s->rs_slot[slots[i]];
-    cnk::RsRow& row = P.rows[i];
-    memset(&row, 0, sizeof(row));
-    const int fmt = s->in_fmt[slots[i]], bps = fmt == cnk::kFmtF32 ? 4 : (fmt == cnk::kFmtS16 ? 2 : 1);
-    row.slot = slots[i]; row.mode = cnk::kRsCopy | (fmt << cnk::kRsFmtShift); row.m = samples[i]; row.h = samples[i];
-    if (fmt != cnk::kFmtF32 && samples[i] > 0) {
-      if ((long long)samples[i] * bps > wav_ld * 4)
-        throw Error(CONAN_ERR_INVALID, std::string(who) + ": slot " + std::to_string(slots[i]) + ": the row holds more bytes (" + std::to_string(samples[i]) + " samples of " +
-                                           std::to_string(bps) + ") than the row stride of wav_dev (" + std::to_string(wav_ld) + " x 4 bytes)");
-      if (!wav_dev) throw Error(CONAN_ERR_INVALID, "null argument (wav_dev with samples > 0)");
-      if ((uintptr_t)wav_dev & 3) throw Error(CONAN_ERR_INVALID, std::string(who) + ": wav_dev must be 4-byte aligned");
-      if (!r.f) P.launch = true;      // a format alone: the copy rows decode into staging
-    }
-    if (!r.f) continue;
-    const ch::RsTable& t = *r.f;
-    auto bad = [&](const std::string& what) {
-      throw Error(CONAN_ERR_INVALID, std::string(who) + ": slot " + std::to_string(slots[i]) + " (input at " + std::to_string(t.in_rate) + " Hz): " + what);
-    };
-    const int sm = samples[i], fin = final_[i];
-    const int s_in = (int)((long long)S * t.in_rate / t.out_rate);
-    if (fin != 0 && fin != 1) bad("final must be 0 or 1");
-    if (m.sample_rate != t.out_rate) bad("conan_mel_cfg.sample_rate must be the resampler's out_rate");
-    if (r.phase == 1 && (!fin || sm != 0)) bad("after the final call only samples = 0, final = 1 may follow");
-    if (!fin && sm != s_in) bad("a non-final call takes exactly segment * hop * in_rate / out_rate samples");
-    if (fin && (sm < 0 || sm > s_in)) bad("a final call takes 0 .. segment * hop * in_rate / out_rate samples");
-    if ((long long)sm * bps > wav_ld * 4) bad("the row holds more samples than the row stride of wav_dev");
-    if (sm > 0 && !wav_dev) throw Error(CONAN_ERR_INVALID, "null argument (wav_dev with samples > 0)");
-    const long long I = r.in + sm;
-    long long J;
-    if (fin) {
-      const long long T = t.length(I);
-      J = std::min(T, r.out + S);
-      P.ff[i] = J == T;
-    } else {
-      J = std::min(std::max(t.ready(I), r.out), r.out + S);
-      P.ff[i] = 0;
-    }
-    // the inputs still to be read ([first tap of output r.out, I), up to a rounding step) must fit the history ring
-    if (I - (t.first(r.out) - 4) > cnk::kRsRing) throw Error(CONAN_ERR_UNSUPPORTED, std::string(who) + ": resampler history ring too small for this configuration");
-    P.mm[i] = (int)(J - r.out);
-    P.rate[i] = 1; P.any = true; P.in_after[i] = I;
-    row.in0 = r.in; row.out0 = r.out; row.taps = t.f.taps; row.ph = t.f.ph;
-    row.m = sm; row.h = P.mm[i]; row.orig = t.f.orig; row.nph = t.f.nph; row.w = t.f.w; row.L = t.f.L; row.mode = fmt << cnk::kRsFmtShift;
-    P.launch = P.launch || sm > 0 || P.mm[i] > 0;
-    P.win = std::max(P.win, t.win);
-    P.flops += 2.0 * P.mm[i] * t.f.L;
-  }
-  if (P.launch)
-    for (int i = 0; i < n; ++i) {
-      const cnk::RsRow& row = P.rows[i];
-      P.tiles = std::max(P.tiles, (std::max(row.h, row.m) + cnk::kRsTile - 1) / cnk::kRsTile);
-    }
-  return P;
-}
-
-// Uploads the plan's row table (set q of NS, after the call that used the set last has read it) on `cst` and returns the launch;
-// `mel_front` (may be empty) follows it on the same stream, then ev_rs[q].
-static std::function<void(hipStream_t)> rs_front(conan_streams* s, const RsPlan& P, int n, const float* wav_dev, long long wav_ld, long long out_ld,
-                                                 std::function<void(hipStream_t)> mel_front, hipStream_t cst) {
-  const int q = (int)(s->rs_calls++ % conan_streams::NS);
-  HIP_CHECK(hipStreamWaitEvent(cst, s->ev_rs[q], 0));
-  s->rs_pin.upload(reinterpret_cast<int*>(s->rs_rows[q]), reinterpret_cast<const int*>(P.rows.data()), (size_t)n * sizeof(cnk::RsRow) / sizeof(int), cst);
-  cnk::ResampleStreamArgs a;
-  a.wav = wav_dev ? wav_dev : s->rs_wav[q]; a.wav_ld = wav_dev ? wav_ld : 0;
-  a.ring = s->rs_ring; a.out = s->rs_wav[q]; a.out_ld = out_ld;
-  a.rows = s->rs_rows[q]; a.n = n; a.tiles = P.tiles; a.win = P.win;
-  const double flops = P.flops;
-  hipEvent_t ev = s->ev_rs[q];
-  return [s, a, flops, mel_front, ev](hipStream_t st) {
-    s->profiled("resample_stream_kernel", flops, st, [&] { cnk::launch_resample_stream(a, st); });
-    if (mel_front) mel_front(st);
-    HIP_CHECK(hipEventRecord(ev, st));
-  };
-}
-
-static void rs_commit(conan_streams* s, const int32_t* slots, int n, const RsPlan& P, const int32_t* final_) {
-  for (int i = 0; i < n; ++i) {
-    if (!P.rate[i]) continue;
-    conan_streams::RsSlot& r = s->rs_slot[slots[i]];
-    r.in = P.in_after[i]; r.out += P.mm[i];
-    if (final_[i]) r.phase = 1;
-  }
-}
-
-void conan_streams::resample_init() {
-  rs_stage_init();
-  if (!rs_ring) rs_ring = alloc((size_t)max_slots * cnk::kRsRing);        // stream state (state_bytes)
-}
-
-void conan_streams::rs_stage_init() {
-  if (rs_wav[0]) return;
-  const size_t S = (size_t)ctx->cfg.emf_segment * ctx->hop;
-  auto dev = [&](size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, bytes)); allocs.push_back(p); return p; };
-  for (int q = 0; q < NS; ++q) {
-    rs_rows[q] = (cnk::RsRow*)dev((size_t)max_slots * sizeof(cnk::RsRow));
-    rs_wav[q] = (float*)dev((size_t)max_slots * S * sizeof(float));
-    HIP_CHECK(hipEventCreateWithFlags(&ev_rs[q], hipEventDisableTiming));
-  }
-  rs_pin.init((size_t)max_slots * sizeof(cnk::RsRow) / sizeof(int));
-  rs_slot.assign(max_slots, RsSlot());
-}
-
-// The conan_mel_cfg of a wav-in call: centred frames at the vocoder's hop into the Emformer's input width.
-static void check_mel_stream(const conan_streams* s, const conan_mel_cfg& m, const std::string& who) {
-  if (m.framing != 0) throw Error(CONAN_ERR_INVALID, who + ": only framing 0 (centred frames, zero padding) streams");
-  if (m.fft_size < 64 || (m.fft_size & (m.fft_size - 1)) || m.fft_size > 2048) throw Error(CONAN_ERR_INVALID, who + ": fft_size must be a power of two in [64, 2048]");
-  if (m.hop_size != s->ctx->hop) throw Error(CONAN_ERR_INVALID, who + ": hop_size must be the vocoder's hop (conan_hop_size)");
-  if (m.num_mels != s->ctx->cfg.emf_input_dim) throw Error(CONAN_ERR_INVALID, who + ": num_mels must be the Emformer's input width");
-  if (m.natural_log != 0 && m.natural_log != 1) throw Error(CONAN_ERR_INVALID, who + ": natural_log must be 0 (log10) or 1 (ln)");
-  if (m.win_length < 1 || m.win_length > m.fft_size || m.sample_rate < 1 || !(m.eps > 0.f) || !(m.mag_eps >= 0.f))
-    throw Error(CONAN_ERR_INVALID, "mel front-end configuration");
-}
-
-// One slot's front-end plan for a wav-in call that gives it `samples` (model rate) and `final_`.  Centred framing: frame f needs the
-// samples up to f * hop + n_fft / 2 - 1, or the final call: every frame of 1 + samples / hop, zero padding past the end.  R = samples
-// received after the call, total = R once final (-1 before); frames [0, fc) complete, [f0, f0 + nnew) of them new in this call; chunk
-// t = chunks emitted so far starts at frame pos and is ready once frames [pos, pos + seg + rc) are complete or - after the final call -
-// any frame is left (emit frames, rows [0, real) backed by frames: the short last chunks of engine.chunks, repeat-last padding).
-struct FePlan { long long R, total; int fc, f0, nnew, pos, emit, real; };
-
-static FePlan fe_plan(const conan_streams* s, const conan_streams::FeSlot& o, int samples, int final_, int n_fft, const std::string& who) {
-  const int seg = s->ctx->cfg.emf_segment, rc = s->ctx->cfg.emf_right_context, hop = s->ctx->hop, N = n_fft;
-  FePlan p;
-  p.R = o.recv + samples;
-  p.total = final_ ? p.R : -1;
-  p.fc = final_ ? (int)(1 + p.R / hop) : (p.R >= N / 2 ? (int)((p.R - N / 2) / hop) + 1 : 0);
-  p.f0 = o.frames; p.nnew = std::max(0, p.fc - p.f0); p.pos = o.chunks * seg;
-  p.emit = 0; p.real = 0;
-  if (final_) {
-    if (p.pos < p.fc) { p.emit = std::min(seg, p.fc - p.pos); p.real = p.emit + std::min(rc, p.fc - p.pos - p.emit); }
-  } else if (p.pos + seg + rc <= p.fc) {
-    p.emit = seg; p.real = seg + rc;
-  }
-  // ring spans: the samples a new frame reads and the samples appended; the frames a chunk row reads and the frames written
-  const long long a_lo = std::min<long long>(o.recv, (long long)p.f0 * hop - N / 2);
-  if (p.R - std::max(0ll, a_lo) > s->fe_LA || p.fc - std::min(p.pos, p.f0) > s->fe_LM)
-    throw Error(CONAN_ERR_UNSUPPORTED, who + ": front-end rings too small for this configuration");
-  return p;
-}
-
-static void fe_commit(conan_streams* s, const int32_t* slots, int n, const std::vector<FePlan>& pl, const int32_t* final_) {
-  for (int i = 0; i < n; ++i) {
-    conan_streams::FeSlot& o = s->fe_slot[slots[i]];
-    const FePlan& p = pl[i];
-    o.recv = p.R; o.frames = std::max(p.f0, p.fc); o.chunks += p.emit > 0 ? 1 : 0;
-    o.phase = final_[i] ? (p.emit > 0 ? 1 : 2) : 0;
-  }
-}
-
-void conan_streams::ragged_init() {
-  if (rg_tab[0]) return;
-  const conan_cfg& c = ctx->cfg;
-  const size_t seg = c.emf_segment;
-  auto dev = [&](size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, bytes)); allocs.push_back(p); return p; };
-  for (int q = 0; q < NS; ++q) {
-    rg_tab[q] = (int*)dev((size_t)max_slots * cnk::kRaggedWords * sizeof(int));
-    rg_codes[q] = (int*)dev((size_t)max_slots * seg * sizeof(int));
-    rg_mel[q] = (float*)dev((size_t)max_slots * seg * c.num_mels * sizeof(float));
-    rg_wav[q] = (float*)dev((size_t)max_slots * seg * ctx->hop * sizeof(float));
-    HIP_CHECK(hipEventCreateWithFlags(&ev_stage[q], hipEventDisableTiming));
-  }
-  fe_pin.init((size_t)max_slots * cnk::kRaggedWords);
-}
-
-// Waveform-in chunk steps (conan_step_wav[_async], conan_step_wav_ragged[_ld][_async]).  The host keeps each slot's position in its
-// utterance (FeSlot); every slot gets its own plan (fe_plan), and the emitting slots are grouped by emit, each group running one
-// mel-in chunk step (blocking or pipelined) on its own slot list.  One front-end launch, in front of the first group's Emformer, does
-// the front-end work of every slot of the call: the new frames, the chunk rows of earlier calls from the mel ring, the samples
-// appended to the audio ring.
-// `common` is conan_step_wav's contract: every slot at the same position with the same input-rate configuration, so the call has at
-// most one group, in call order, and the outputs are rows of emit frames ([n][emit]) written in place.  Its front-end is
-// mel_stream_kernel on the call's one plan (mel_stream_copy_kernel in calls that complete no frame), the same-position kernel: at 64
-// streams a pipelined step is ~10 % slower with the row-table kernel below (1.548 against 1.402 ms per step).
-// Otherwise (ragged calls) mel_stream_ragged_kernel is driven by a [n][kRaggedWords] row table and writes each group's chunk
-// contiguously into fe_chunk; the outputs are rows of a full chunk ([n][seg]).  A call whose slots all emit a full chunk is one group
-// in call order and writes the caller's buffers directly; the groups of any other call write staging (set q of NS) and
-// wav_rows_scatter_kernel puts the rows in call order.
-static void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, int n, const int32_t* in_samples, const int32_t* in_final,
-                     const float* wav_dev, long long wav_ld, const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev,
-                     int32_t* emit_out, void* stream, bool pipelined, bool common) {
-  if (!s || !slots || !in_samples || !in_final || !mel || !wav_out_dev || !emit_out) throw Error(CONAN_ERR_INVALID, "null argument");
-  check_chunk_step(s, who.c_str());
-  const conan_mel_cfg& m = *mel;
-  check_mel_stream(s, m, who);
-  if (n < 1 || n > s->max_slots) throw Error(CONAN_ERR_INVALID, "slot count out of range");
-  if (pipelined && s->prof_on) throw Error(CONAN_ERR_STATE, "profiling is not available for pipelined steps");
-  const conan_cfg& c = s->ctx->cfg;
-  const int seg = c.emf_segment, rc = c.emf_right_context, hop = m.hop_size, N = m.fft_size, rows = seg + rc;
-  std::vector<char> seen(s->max_slots, 0);
-  for (int i = 0; i < n; ++i) {
-    if (slots[i] < 0 || slots[i] >= s->max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
-    if (seen[slots[i]]) throw Error(CONAN_ERR_INVALID, "duplicate slot");
-    seen[slots[i]] = 1;
-  }
-  if (wav_ld < 0 || wav_ld > INT_MAX) throw Error(CONAN_ERR_INVALID, who + ": wav_ld out of range");
-  if (common) {
-    const conan_streams::FeSlot& o0 = s->fe_slot[slots[0]];
-    for (int i = 1; i < n; ++i) {
-      const conan_streams::FeSlot& o = s->fe_slot[slots[i]];
-      if (o.recv != o0.recv || o.frames != o0.frames || o.chunks != o0.chunks || o.phase != o0.phase)
-        throw Error(CONAN_ERR_INVALID, who + ": the slots of one call must be at the same position of their utterances");
-    }
-    for (int i = 1; i < n && !s->rs_slot.empty(); ++i) {
-      const conan_streams::RsSlot &r0 = s->rs_slot[slots[0]], &r = s->rs_slot[slots[i]];
-      if (r.f != r0.f || (r.f && (r.in != r0.in || r.out != r0.out || r.phase != r0.phase)))
-        throw Error(CONAN_ERR_INVALID, who + ": the slots of one call must share one input rate configuration (conan_streams_set_input_rate) and position");
-    }
-  }
-  // the input resampler's rows first: what each slot's front-end gets this call
-  const RsPlan P = rs_plan(s, slots, n, in_samples, in_final, wav_dev, wav_ld, m, who.c_str());
-  const int32_t* samples = P.mm.data();
-  const int32_t* final_ = P.ff.data();
-  // every slot's plan first: nothing changes before all of them have passed
-  std::vector<FePlan> pl(n);
-  bool run = false;
-  for (int i = 0; i < n; ++i) {
-    const conan_streams::FeSlot& o = s->fe_slot[slots[i]];
-    const int sm = samples[i], fin = final_[i];
-    auto bad = [&](const char* what) {
-      throw Error(CONAN_ERR_INVALID, who + ": slot " + std::to_string(slots[i]) + " (call row " + std::to_string(i) + "): " + what);
-    };
-    if (fin != 0 && fin != 1) bad("final must be 0 or 1");
-    if (o.phase == 2) bad("the utterance has been drained; reset the slot with CONAN_MODEL_FRONTEND first");
-    if (o.phase == 1 && (!fin || sm != 0)) bad("after the final call only samples = 0, final = 1 may follow");
-    if (!fin && sm != seg * hop && !P.rate[i]) bad("a non-final call takes exactly segment * hop samples per slot");
-    if (fin && (sm < 0 || sm > seg * hop)) bad("a final call takes 0 .. segment * hop samples per slot");
-    if (sm > wav_ld && !P.rate[i] && !s->in_fmt[slots[i]]) bad("the row holds more samples than the row stride of wav_dev");
-    if (in_samples[i] > 0 && !wav_dev) throw Error(CONAN_ERR_INVALID, "null argument (wav_dev with samples > 0)");
-    if (fin && o.recv + sm < 1) bad("an utterance needs at least one sample");
-    pl[i] = fe_plan(s, o, sm, fin, N, who);
-    run = run || pl[i].nnew > 0 || sm > 0 || pl[i].emit > 0;
-  }
-  // emit groups, largest emit first; a group's rows keep call order
-  std::vector<std::vector<int>> groups;      // call rows per group
-  for (int e = seg; e >= 1; --e) {
-    std::vector<int> g;
-    for (int i = 0; i < n; ++i) if (pl[i].emit == e) g.push_back(i);
-    if (!g.empty()) groups.push_back(std::move(g));
-  }
-  const bool direct = common || (groups.size() == 1 && (int)groups[0].size() == n && pl[0].emit == seg);
-  const bool scatter = !direct && !groups.empty();
-  // the groups' output rows (out_plan): a staged call with an output rate among its emitting rows, or any stride set (a group
-  // of emit < seg frames then differs from it even at seg * hop), has resample_out_kernel write each group's audio straight to
-  // its call-order rows of wav_out_dev (the scatter then places codes and mel only); otherwise no group's plan is active
-  bool route = scatter && s->out_ld != 0;
-  for (int g = 0; scatter && g < (int)groups.size(); ++g)
-    for (int i : groups[g]) route = route || (!s->or_slot.empty() && s->or_slot[slots[i]].f) || s->out_fmt[slots[i]];
-  std::vector<conan_streams::OutPlan> ops;
-  for (int g = 0; g < (int)groups.size(); ++g) {
-    std::vector<int32_t> gs;
-    for (int i : groups[g]) gs.push_back(slots[i]);
-    const int e = pl[groups[g][0]].emit;
-    ops.push_back(s->out_plan(gs.data(), (int)gs.size(), e, wav_out_dev, route ? (long long)seg * hop : (long long)e * hop, route ? &groups[g] : nullptr, who));
-  }
-  const int nm_in = m.num_mels, nm = c.num_mels;
-  int jobs = 0;
-  std::vector<int> tab;
-  if (!common) {
-    tab.assign((size_t)n * cnk::kRaggedWords, 0);
-    for (int i = 0; i < n; ++i) {
-      const FePlan& p = pl[i];
-      int* d = &tab[(size_t)i * cnk::kRaggedWords];
-      const long long r_prev = s->fe_slot[slots[i]].recv;
-      d[cnk::kRgSlot] = slots[i];
-      d[cnk::kRgRecvLo] = (int)(uint32_t)r_prev; d[cnk::kRgRecvHi] = (int)(r_prev >> 32);
-      d[cnk::kRgTotalLo] = (int)(uint32_t)p.total; d[cnk::kRgTotalHi] = (int)(p.total >> 32);
-      d[cnk::kRgM] = samples[i]; d[cnk::kRgF0] = p.f0; d[cnk::kRgNnew] = p.nnew; d[cnk::kRgPos] = p.pos;
-      d[cnk::kRgRows] = p.emit > 0 ? rows : 0; d[cnk::kRgReal] = p.real; d[cnk::kRgEmit] = p.emit;
-      d[cnk::kRgJob] = jobs;
-      jobs += p.nnew;
-    }
-    for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g)
-      for (int k = 0; k < (int)groups[g].size(); ++k) {
-        int* d = &tab[(size_t)groups[g][k] * cnk::kRaggedWords];
-        d[cnk::kRgChunk] = off + k; d[cnk::kRgGroup] = off; d[cnk::kRgIndex] = k;
-      }
-  }
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  hipStream_t cst = (hipStream_t)stream;
-  if (!pipelined || groups.empty()) s->join(cst);
-  s->out_counts.assign(n, 0);      // (rows that emit no frame; hifigan_step fills the others)
-  const int q = (int)(s->rg_calls % conan_streams::NS);
-  if (!common) {
-    s->ragged_init();
-    // the row table of set q: the call that used it last has finished reading it (and its staging)
-    HIP_CHECK(hipStreamWaitEvent(cst, s->ev_stage[q], 0));
-    s->fe_pin.upload(s->rg_tab[q], tab.data(), tab.size(), cst);
-  }
-  std::function<void(hipStream_t)> front;
-  if (run) {
-    const std::string k = s->ctx->mel_tables(m);
-    const float* rg = s->ctx->vec(k + ".range");
-    const float* wav = P.launch ? s->rs_wav[s->rs_calls % conan_streams::NS] : wav_dev;     // (rs_front takes set rs_calls % NS below)
-    auto fill = [&](auto& a) {      // the fields both front-end kernels share
-      a.wav = wav; a.aring = s->fe_audio; a.mring = s->fe_mel; a.chunk = s->fe_chunk; a.n = n;
-      a.win = s->ctx->vec(k + ".win"); a.tw = reinterpret_cast<const double2*>(s->ctx->vec(k + ".tw")); a.fb = s->ctx->vec(k + ".fb");
-      a.lo = reinterpret_cast<const int*>(rg); a.hi = reinterpret_cast<const int*>(rg) + m.num_mels;
-      a.LA = s->fe_LA; a.LM = s->fe_LM; a.nm = nm_in; a.n_fft = N; a.hop = hop; a.nb = N / 2 + 1; a.cmag = (N / 2 + 1 + 3) & ~3;
-      a.eps = m.eps; a.vmin = m.vmin; a.vmax = m.vmax; a.mag_eps = m.mag_eps; a.natural_log = m.natural_log;
-    };
-    if (common) {
-      const FePlan& p = pl[0];
-      cnk::MelStreamArgs a;
-      fill(a);
-      a.slots = s->d_slots; a.r_prev = s->fe_slot[slots[0]].recv; a.total = p.total;
-      a.m = samples[0]; a.f0 = p.f0; a.nnew = p.nnew; a.pos = p.pos; a.rows = p.emit > 0 ? rows : 0; a.real = p.real;
-      const double flops = 4.0 * n * p.nnew * (double)(N / 2 + 1) * N;
-      front = [s, a, flops](hipStream_t st) {
-        if (a.nnew > 0) s->profiled("mel_stream_kernel", flops, st, [&] { cnk::launch_mel_stream(a, st); });
-        else s->profiled("mel_stream_copy_kernel", 0.0, st, [&] { cnk::launch_mel_stream_copy(a, st); });
-      };
-    } else {
-      cnk::MelRaggedArgs a;
-      fill(a);
-      a.tab = s->rg_tab[q]; a.jobs = jobs; a.wstride = P.launch ? seg * hop : (int)wav_ld;
-      const double flops = 4.0 * jobs * (double)(N / 2 + 1) * N;
-      front = [s, a, flops](hipStream_t st) { s->profiled("mel_stream_ragged_kernel", flops, st, [&] { cnk::launch_mel_ragged(a, st); }); };
-    }
-  }
-  // (the same-position kernel reads the resampler's rows [n][samples], the ragged one [n][seg * hop])
-  if (P.launch) front = rs_front(s, P, n, wav_dev, wav_ld, common ? samples[0] : seg * hop, front, cst);
-  cnk::WavScatterArgs sc;
-  sc.tab = s->rg_tab[q]; sc.n = n; sc.seg = seg; sc.nm = nm; sc.hop = hop;
-  sc.codes_src = s->rg_codes[q]; sc.mel_src = s->rg_mel[q]; sc.wav_src = s->rg_wav[q];
-  sc.codes = codes_dev; sc.mel = mel_out_dev; sc.wav = route ? nullptr : wav_out_dev;
-  auto group_step = [&](int g, int off, hipStream_t st) {
-    std::vector<int32_t> gs;
-    for (int i : groups[g]) gs.push_back(slots[i]);
-    const int ng = (int)gs.size(), e = pl[groups[g][0]].emit;
-    const float* chunk = s->fe_chunk + (size_t)off * rows * nm_in;
-    int32_t* cd = direct ? codes_dev : s->rg_codes[q] + (size_t)off * seg;
-    float* md = direct ? mel_out_dev : s->rg_mel[q] + (size_t)off * seg * nm;
-    float* wd = direct ? wav_out_dev : s->rg_wav[q] + (size_t)off * seg * hop;
-    if (pipelined) {
-      step_pipelined(s, gs.data(), ng, e, chunk, cd, md, wd, stream, g == 0 ? front : std::function<void(hipStream_t)>(), ops[g]);
-    } else {
-      s->set_slots(gs.data(), ng, st);
-      step_blocking(s, ng, e, chunk, cd, md, wd, st, ops[g]);
-    }
-  };
-  if (pipelined && !groups.empty()) {
-    for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g) group_step(g, off, cst);
-    if (scatter) {
-      cnk::launch_wav_scatter(sc, s->st_voc);
-      // join() waits for the last step's vocoder event: it now covers the scatter too
-      HIP_CHECK(hipEventRecord(s->ev_voc[(s->async_steps - 1) % conan_streams::NP], s->st_voc));
-    }
-    if (!common) HIP_CHECK(hipEventRecord(s->ev_stage[q], s->st_voc));
-  } else {
-    if (common) s->set_slots(slots, n, cst);      // (mel_stream_kernel reads the slot table)
-    if (front) front(cst);
-    for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g) group_step(g, off, cst);
-    if (scatter) s->profiled("wav_rows_scatter_kernel", 0.0, cst, [&] { cnk::launch_wav_scatter(sc, cst); });
-    if (!common) HIP_CHECK(hipEventRecord(s->ev_stage[q], cst));
-  }
-  if (scatter && !route) {      // (each group's step counted its own rows, in group order: back to the call's rows)
-    s->out_counts.assign(n, 0);
-    for (int i = 0; i < n; ++i) s->out_counts[i] = pl[i].emit * hop;
-  }
-  fe_commit(s, slots, n, pl, final_);
-  for (int i = 0; i < n; ++i) emit_out[i] = pl[i].emit;
-  rs_commit(s, slots, n, P, in_final);
-  s->fe_last_n = n;
-  s->fe_last_ragged = !common;
-  if (!common) s->rg_calls++;
-}
-
-// conan_step_wav[_async]: `samples` and `final` for every slot, rows of `samples` samples in wav_dev; *emit_out = the common emit
-static void step_wav_common(conan_streams* s, const int32_t* slots, int n, int samples, int final, const float* wav_dev, const conan_mel_cfg* mel,
-                            int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream, bool pipelined) {
-  if (!s || !emit_out) throw Error(CONAN_ERR_INVALID, "null argument");
-  *emit_out = 0;
-  const size_t rows = std::clamp(n, 1, s->max_slots);      // (step_wav checks n)
-  const std::vector<int32_t> sm(rows, samples), fin(rows, final != 0);
-  std::vector<int32_t> emit(rows, 0);
-  step_wav(s, "conan_step_wav", slots, n, sm.data(), fin.data(), wav_dev, std::max(samples, 0), mel, codes_dev, mel_out_dev, wav_out_dev,
-           emit.data(), stream, pipelined, true);
-  *emit_out = emit[0];
-}
-
 int conan_step_wav(conan_streams* s, const int32_t* slots, int n, int samples, int final, const float* wav_dev, const conan_mel_cfg* mel,
                    int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream) {
-  return guarded([&] { step_wav_common(s, slots, n, samples, final, wav_dev, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false); });
+  return guarded([&] { wavio::step_wav_common(s, slots, n, samples, final, wav_dev, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false); });
 }
 
 int conan_step_wav_async(conan_streams* s, const int32_t* slots, int n, int samples, int final, const float* wav_dev, const conan_mel_cfg* mel,
                          int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream) {
-  return guarded([&] { step_wav_common(s, slots, n, samples, final, wav_dev, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true); });
+  return guarded([&] { wavio::step_wav_common(s, slots, n, samples, final, wav_dev, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true); });
 }
 
 static long long ragged_ld(const conan_streams* s) { return s ? (long long)s->ctx->cfg.emf_segment * s->ctx->hop : 0; }
 
 int conan_step_wav_ragged(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final, const float* wav_dev,
                           const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream) {
-  return guarded([&] { step_wav(s, "conan_step_wav_ragged", slots, n, samples, final, wav_dev, ragged_ld(s), mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false, false); });
+  return guarded([&] { wavio::step_wav(s, "conan_step_wav_ragged", slots, n, samples, final, wav_dev, ragged_ld(s), mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false, false); });
 }
 
 int conan_step_wav_ragged_async(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final, const float* wav_dev,
                                 const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream) {
-  return guarded([&] { step_wav(s, "conan_step_wav_ragged", slots, n, samples, final, wav_dev, ragged_ld(s), mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true, false); });
+  return guarded([&] { wavio::step_wav(s, "conan_step_wav_ragged", slots, n, samples, final, wav_dev, ragged_ld(s), mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true, false); });
 }
 
 int conan_step_wav_ragged_ld(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final, const float* wav_dev,
                              int64_t wav_ld, const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev,
                              int32_t* emit_out, void* stream) {
-  return guarded([&] { step_wav(s, "conan_step_wav_ragged", slots, n, samples, final, wav_dev, wav_ld, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false, false); });
+  return guarded([&] { wavio::step_wav(s, "conan_step_wav_ragged", slots, n, samples, final, wav_dev, wav_ld, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, false, false); });
 }
 
 int conan_step_wav_ragged_ld_async(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const int32_t* final,
                                    const float* wav_dev, int64_t wav_ld, const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev,
                                    float* wav_out_dev, int32_t* emit_out, void* stream) {
-  return guarded([&] { step_wav(s, "conan_step_wav_ragged", slots, n, samples, final, wav_dev, wav_ld, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true, false); });
+  return guarded([&] { wavio::step_wav(s, "conan_step_wav_ragged", slots, n, samples, final, wav_dev, wav_ld, mel, codes_dev, mel_out_dev, wav_out_dev, emit_out, stream, true, false); });
 }
 
 int conan_resample(conan_ctx* ctx, const conan_resample_cfg* cfg, const float* x_dev, int n, int64_t samples, float* y_dev, int64_t* out_samples,
@@ -994,142 +586,29 @@ int conan_resample(conan_ctx* ctx, const conan_resample_cfg* cfg, const float* x
 }
 
 int conan_streams_set_input_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg) {
-  return guarded([&] {
-    if (!s || !slots || !cfg) throw Error(CONAN_ERR_INVALID, "null argument");
-    if (!s->fe_audio) throw Error(CONAN_ERR_STATE, "conan_streams_set_input_rate: the stream-set has no streaming front-end (all three models)");
-    if (n < 1 || n > s->max_slots) throw Error(CONAN_ERR_INVALID, "slot count out of range");
-    const int S = s->ctx->cfg.emf_segment * s->ctx->hop, model_rate = 50 * s->ctx->hop;
-    const conan_resample_cfg& c = *cfg;
-    if (c.out_rate != model_rate)
-      throw Error(CONAN_ERR_INVALID, "conan_streams_set_input_rate: out_rate must be the model rate (hop * 50 = " + std::to_string(model_rate) + " Hz)");
-    std::vector<char> seen(s->max_slots, 0);
-    for (int i = 0; i < n; ++i) {
-      if (slots[i] < 0 || slots[i] >= s->max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
-      if (seen[slots[i]]) throw Error(CONAN_ERR_INVALID, "duplicate slot");
-      seen[slots[i]] = 1;
-    }
-    const ch::RsTable* t = nullptr;
-    if (c.in_rate != c.out_rate) {
-      t = &s->ctx->resample_table(c);
-      const long long num = (long long)S * c.in_rate;
-      if (num % c.out_rate || (num / c.out_rate) % t->f.orig)
-        throw Error(CONAN_ERR_INVALID, "conan_streams_set_input_rate: segment * hop samples at the model rate must be a whole number of input samples and a multiple of in_rate / gcd(in_rate, out_rate)");
-      const long long s_in = num / c.out_rate;
-      if (t->length(s_in) - t->ready(s_in) > S) throw Error(CONAN_ERR_INVALID, "conan_streams_set_input_rate: the filter's look-ahead is longer than segment * hop samples");
-    } else {
-      conan_resample_cfg probe = c;     // the configuration must still be a valid one
-      if (conan_resample_length(&probe, 0) < 0) throw Error(CONAN_ERR_INVALID, "conan_streams_set_input_rate: invalid resampler configuration");
-    }
-    for (int i = 0; i < n; ++i) {
-      const conan_streams::FeSlot& o = s->fe_slot[slots[i]];
-      const bool rs_fresh = s->rs_slot.empty() || (s->rs_slot[slots[i]].in == 0 && s->rs_slot[slots[i]].phase == 0);
-      if (o.recv != 0 || o.phase != 0 || o.frames != 0 || o.chunks != 0 || !rs_fresh)
-        throw Error(CONAN_ERR_STATE, "conan_streams_set_input_rate: slot " + std::to_string(slots[i]) + " is not at the start of an utterance (reset it with CONAN_MODEL_FRONTEND first)");
-    }
-    HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-    s->resample_init();
-    for (int i = 0; i < n; ++i) s->rs_slot[slots[i]] = conan_streams::RsSlot{t, 0, 0, 0};
-  });
-}
-
-static void check_slot_list(const conan_streams* s, const int32_t* slots, int n) {
-  if (n < 1 || n > s->max_slots) throw Error(CONAN_ERR_INVALID, "slot count out of range");
-  std::vector<char> seen(s->max_slots, 0);
-  for (int i = 0; i < n; ++i) {
-    if (slots[i] < 0 || slots[i] >= s->max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
-    if (seen[slots[i]]) throw Error(CONAN_ERR_INVALID, "duplicate slot");
-    seen[slots[i]] = 1;
-  }
+  return guarded([&] { wavio::set_input_rate(s, slots, n, cfg); });
 }
 
 int conan_streams_set_output_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg) {
-  return guarded([&] {
-    if (!s || !slots || !cfg) throw Error(CONAN_ERR_INVALID, "null argument");
-    if (!(s->ctx->cfg.models & CONAN_MODEL_HIFIGAN)) throw Error(CONAN_ERR_STATE, "conan_streams_set_output_rate: context holds no HiFi-GAN model");
-    check_slot_list(s, slots, n);
-    const int model_rate = 50 * s->ctx->hop;
-    const conan_resample_cfg& c = *cfg;
-    if (c.in_rate != model_rate)
-      throw Error(CONAN_ERR_INVALID, "conan_streams_set_output_rate: in_rate must be the model rate (hop * 50 = " + std::to_string(model_rate) + " Hz)");
-    HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-    const ch::RsTable* t = nullptr;
-    // the history holds model-rate audio: the longest span of an accepted filter (CONAN_RESAMPLE_MAX_TAPS) plus the largest step
-    const int ring_len = ch::next_pow2(CONAN_RESAMPLE_MAX_TAPS + 8 + s->max_frames * s->ctx->hop);
-    if (c.in_rate != c.out_rate) {
-      t = &s->ctx->resample_table(c);
-    } else {
-      conan_resample_cfg probe = c;     // the configuration must still be a valid one
-      if (conan_resample_length(&probe, 0) < 0) throw Error(CONAN_ERR_INVALID, "conan_streams_set_output_rate: invalid resampler configuration");
-    }
-    for (int i = 0; i < n; ++i)
-      if (s->voc_samples[slots[i]] != 0)
-        throw Error(CONAN_ERR_STATE, "conan_streams_set_output_rate: slot " + std::to_string(slots[i]) + " is not at the start of its vocoder stream (reset it with CONAN_MODEL_HIFIGAN first)");
-    if (!t && s->or_slot.empty()) return;      // the model-rate path of a stream-set that never had a rate: nothing to allocate
-    if (!s->or_ring) {
-      s->or_ring_len = ring_len;
-      s->or_ring = s->alloc((size_t)s->max_slots * ring_len);        // stream state (state_bytes)
-      s->or_slot.assign(s->max_slots, conan_streams::OrSlot());
-    }
-    for (int i = 0; i < n; ++i) s->or_slot[slots[i]] = conan_streams::OrSlot{t, 0, 0};
-  });
+  return guarded([&] { wavio::set_output_rate(s, slots, n, cfg); });
 }
 
-int conan_streams_set_output_ld(conan_streams* s, int64_t ld) {
-  return guarded([&] {
-    if (!s) throw Error(CONAN_ERR_INVALID, "null streams");
-    if (ld < 0 || ld > INT_MAX) throw Error(CONAN_ERR_INVALID, "conan_streams_set_output_ld: ld out of range");
-    s->out_ld = ld;
-  });
-}
+int conan_streams_set_output_ld(conan_streams* s, int64_t ld) { return guarded([&] { wavio::set_output_ld(s, ld); }); }
 
-static void check_format(int format, const char* who) {
-  if (format != CONAN_SAMPLE_F32 && format != CONAN_SAMPLE_S16 && format != CONAN_SAMPLE_ULAW && format != CONAN_SAMPLE_ALAW)
-    throw Error(CONAN_ERR_INVALID, std::string(who) + ": format must be CONAN_SAMPLE_F32, _S16, _ULAW or _ALAW");
-}
-static_assert(CONAN_SAMPLE_F32 == cnk::kFmtF32 && CONAN_SAMPLE_S16 == cnk::kFmtS16 && CONAN_SAMPLE_ULAW == cnk::kFmtUlaw && CONAN_SAMPLE_ALAW == cnk::kFmtAlaw,
-              "the kernels' format codes are the header's");
+int conan_streams_set_input_format(conan_streams* s, const int32_t* slots, int n, int format) { return guarded([&] { wavio::set_input_format(s, slots, n, format); }); }
 
-int conan_streams_set_input_format(conan_streams* s, const int32_t* slots, int n, int format) {
-  return guarded([&] {
-    if (!s || !slots) throw Error(CONAN_ERR_INVALID, "null argument");
-    if (!s->fe_audio) throw Error(CONAN_ERR_STATE, "conan_streams_set_input_format: the stream-set has no streaming front-end (all three models)");
-    check_format(format, "conan_streams_set_input_format");
-    check_slot_list(s, slots, n);
-    if (format != CONAN_SAMPLE_F32) {      // staging rows and row tables only: a format has no stream state
-      HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-      s->rs_stage_init();
-    }
-    for (int i = 0; i < n; ++i) {
-      s->in_fmt_n += (format != 0) - (s->in_fmt[slots[i]] != 0);
-      s->in_fmt[slots[i]] = (unsigned char)format;
-    }
-  });
-}
-
-int conan_streams_set_output_format(conan_streams* s, const int32_t* slots, int n, int format) {
-  return guarded([&] {
-    if (!s || !slots) throw Error(CONAN_ERR_INVALID, "null argument");
-    if (!(s->ctx->cfg.models & CONAN_MODEL_HIFIGAN)) throw Error(CONAN_ERR_STATE, "conan_streams_set_output_format: context holds no HiFi-GAN model");
-    check_format(format, "conan_streams_set_output_format");
-    check_slot_list(s, slots, n);
-    for (int i = 0; i < n; ++i) {
-      s->out_fmt_n += (format != 0) - (s->out_fmt[slots[i]] != 0);
-      s->out_fmt[slots[i]] = (unsigned char)format;
-    }
-  });
-}
+int conan_streams_set_output_format(conan_streams* s, const int32_t* slots, int n, int format) { return guarded([&] { wavio::set_output_format(s, slots, n, format); }); }
 
 int conan_convert_samples(conan_ctx* ctx, int src_format, const void* src_dev, int64_t src_ld, int dst_format, void* dst_dev, int64_t dst_ld, int n,
                           int64_t samples, void* stream) {
   return guarded([&] {
     if (!ctx || !src_dev || !dst_dev) throw Error(CONAN_ERR_INVALID, "null argument");
-    check_format(src_format, "conan_convert_samples");
-    check_format(dst_format, "conan_convert_samples");
+    wavio::check_format(src_format, "conan_convert_samples");
+    wavio::check_format(dst_format, "conan_convert_samples");
     if (n < 1 || n > 65535) throw Error(CONAN_ERR_INVALID, "conan_convert_samples: n must be in 1 .. 65535");
     if (samples < 1) throw Error(CONAN_ERR_INVALID, "conan_convert_samples: samples must be >= 1");
-    auto bps = [](int f) { return f == CONAN_SAMPLE_F32 ? 4 : (f == CONAN_SAMPLE_S16 ? 2 : 1); };
     const int64_t lim = INT64_MAX / 8;
-    if (src_ld < 0 || dst_ld < 0 || src_ld > lim || dst_ld > lim || samples > lim || samples * bps(src_format) > src_ld * 4 || samples * bps(dst_format) > dst_ld * 4)
+    if (src_ld < 0 || dst_ld < 0 || src_ld > lim || dst_ld > lim || samples > lim || samples * wavio::bytes_per_sample(src_format) > src_ld * 4 || samples * wavio::bytes_per_sample(dst_format) > dst_ld * 4)
       throw Error(CONAN_ERR_INVALID, "conan_convert_samples: a row of `samples` samples does not fit its stride (4-byte units)");
     if (((uintptr_t)src_dev | (uintptr_t)dst_dev) & 3) throw Error(CONAN_ERR_INVALID, "conan_convert_samples: src_dev and dst_dev must be 4-byte aligned");
     HIP_CHECK(hipSetDevice(ctx->device));
@@ -1142,62 +621,17 @@ int conan_convert_samples(conan_ctx* ctx, int src_format, const void* src_dev, i
 
 int conan_streams_output_samples(conan_streams* s, int32_t* counts, int cap) {
   int rows = 0;
-  const int rc = guarded([&] {
-    if (!s || (!counts && cap > 0) || cap < 0) throw Error(CONAN_ERR_INVALID, "null argument");
-    rows = (int)s->out_counts.size();
-    for (int i = 0; i < rows && i < cap; ++i) counts[i] = s->out_counts[i];
-  });
+  const int rc = guarded([&] { rows = wavio::output_samples(s, counts, cap); });
   return rc < 0 ? rc : rows;
 }
 
-int conan_streams_output_pending(conan_streams* s, const int32_t* slots, int n, int32_t* counts) {
-  return guarded([&] {
-    if (!s || !slots || !counts) throw Error(CONAN_ERR_INVALID, "null argument");
-    check_slot_list(s, slots, n);
-    const conan_streams::OutPlan P = s->out_plan(slots, n, 0, nullptr, INT_MAX, nullptr, "conan_streams_output_pending");
-    for (int i = 0; i < n; ++i) counts[i] = P.counts[i];
-  });
-}
+int conan_streams_output_pending(conan_streams* s, const int32_t* slots, int n, int32_t* counts) { return guarded([&] { wavio::output_pending(s, slots, n, counts); }); }
 
 int conan_streams_flush_output(conan_streams* s, const int32_t* slots, int n, float* wav_out_dev, int64_t wav_ld, void* stream) {
-  return guarded([&] {
-    if (!s || !slots || !wav_out_dev) throw Error(CONAN_ERR_INVALID, "null argument");
-    if (wav_ld < 0 || wav_ld > INT_MAX) throw Error(CONAN_ERR_INVALID, "conan_streams_flush_output: wav_ld out of range");
-    check_slot_list(s, slots, n);
-    const conan_streams::OutPlan P = s->out_plan(slots, n, 0, wav_out_dev, wav_ld, nullptr, "conan_streams_flush_output");
-    HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-    hipStream_t st = (hipStream_t)stream;
-    s->join(st);
-    if (P.active) {
-      s->out_stage_init();
-      const int q = (int)(s->or_calls++ % conan_streams::NS);
-      HIP_CHECK(hipStreamWaitEvent(st, s->ev_or[q], 0));
-      s->or_pin.upload(reinterpret_cast<int*>(s->or_rows[q]), reinterpret_cast<const int*>(P.rows.data()), (size_t)n * sizeof(cnk::RsOutRow) / sizeof(int), st);
-      cnk::ResampleOutArgs ra;
-      ra.wav = s->or_wav[q]; ra.wav_ld = 0; ra.ring = s->or_ring; ra.ring_len = s->or_ring_len; ra.out = wav_out_dev; ra.out_ld = wav_ld;
-      ra.rows = s->or_rows[q]; ra.n = n; ra.tiles = P.tiles; ra.win = P.win;
-      s->profiled("resample_out_kernel", P.flops, st, [&] { cnk::launch_resample_out(ra, st); });
-      HIP_CHECK(hipEventRecord(s->ev_or[q], st));
-    }
-    for (int i = 0; i < n && !s->or_slot.empty(); ++i) {
-      conan_streams::OrSlot& o = s->or_slot[slots[i]];
-      if (!o.f || s->voc_samples[slots[i]] == 0) continue;
-      o.out += P.counts[i]; o.flushed = 1;
-    }
-  });
+  return guarded([&] { wavio::flush_output(s, slots, n, wav_out_dev, wav_ld, stream); });
 }
 
-int conan_step_wav_chunk(conan_streams* s, float* chunk_dev, void* stream) {
-  return guarded([&] {
-    if (!s || !chunk_dev) throw Error(CONAN_ERR_INVALID, "null argument");
-    if (!s->fe_chunk || s->fe_last_n == 0) throw Error(CONAN_ERR_STATE, "conan_step_wav_chunk: no conan_step_wav call yet");
-    if (s->fe_last_ragged) throw Error(CONAN_ERR_STATE, "conan_step_wav_chunk: the last wav-in call was conan_step_wav_ragged, whose chunk rows are grouped by emit");
-    HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-    s->join((hipStream_t)stream);
-    const size_t floats = (size_t)s->fe_last_n * (s->ctx->cfg.emf_segment + s->ctx->cfg.emf_right_context) * s->ctx->cfg.emf_input_dim;
-    HIP_CHECK(hipMemcpyAsync(chunk_dev, s->fe_chunk, floats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  });
-}
+int conan_step_wav_chunk(conan_streams* s, float* chunk_dev, void* stream) { return guarded([&] { wavio::step_wav_chunk(s, chunk_dev, stream); }); }
 
 int conan_step_clock(conan_streams* s, int capacity) {
   return guarded([&] {

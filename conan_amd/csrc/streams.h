@@ -1,5 +1,8 @@
 // conan_streams: per-slot streaming state and launch plans (see streams.hip, decoder.hip, style.hip).
 #pragma once
+#include <array>
+#include <functional>
+
 #include "host_common.h"
 
 using ch::Error;
@@ -52,6 +55,41 @@ struct PinRing {
     for (int i = 0; i < N; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]);
     if (buf) (void)hipHostFree(buf);
   }
+};
+
+// Per-call row tables of the waveform I/O kernels (wavio.hip): kStageSets device tables used round robin, set q reused only after the
+// last reader of the call that used it has completed (event).  begin() takes the next set on `st` - wait for its event, upload the
+// call's rows through the pinned ring - and returns q; the caller enqueues the kernels that read the table and calls end(q, their
+// stream).  Staging buffers a call needs sit beside the tables in the owner, indexed by the same q.  Not stream state (state_bytes).
+constexpr int kStageSets = 4;
+using RgRow = std::array<int, cnk::kRaggedWords>;      // one call row of mel_stream_ragged_kernel / wav_rows_scatter_kernel
+template <typename Row>
+struct StageSets {
+  static_assert(sizeof(Row) % sizeof(int) == 0, "rows are uploaded as ints");
+  Row* rows[kStageSets] = {};
+  hipEvent_t ev[kStageSets] = {};
+  PinRing pin;
+  long long calls = 0;
+  StageSets() = default;
+  StageSets(const StageSets&) = delete;
+  StageSets& operator=(const StageSets&) = delete;
+  void init(int max_rows, std::vector<void*>& allocs) {      // (the tables are freed with the owner's allocations)
+    if (pin.buf) return;
+    for (int q = 0; q < kStageSets; ++q) {
+      HIP_CHECK(hipMalloc((void**)&rows[q], (size_t)max_rows * sizeof(Row)));
+      allocs.push_back(rows[q]);
+      if (!ev[q]) HIP_CHECK(hipEventCreateWithFlags(&ev[q], hipEventDisableTiming));
+    }
+    pin.init((size_t)max_rows * sizeof(Row) / sizeof(int));
+  }
+  int begin(const Row* host_rows, int n, hipStream_t st) {
+    const int q = (int)(calls++ % kStageSets);
+    HIP_CHECK(hipStreamWaitEvent(st, ev[q], 0));
+    pin.upload(reinterpret_cast<int*>(rows[q]), reinterpret_cast<const int*>(host_rows), (size_t)n * sizeof(Row) / sizeof(int), st);
+    return q;
+  }
+  void end(int q, hipStream_t st) { HIP_CHECK(hipEventRecord(ev[q], st)); }
+  ~StageSets() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
 struct conan_streams {
@@ -127,56 +165,57 @@ struct conan_streams {
                                        "): results since then are invalid and this stream-set is unusable - destroy it and create a new one");
   }
 
-  // --- streaming front-end (conan_step_wav): per slot an audio ring (sample s at s & (fe_LA - 1)) and a ring of computed log-mel
-  // frames (frame f at f & (fe_LM - 1)); fe_chunk = the [n][seg + rc][num_mels] chunk the step consumes.  Host side, per slot: samples
-  // received, frames computed, chunks emitted, phase (0 open, 1 the final call has come, 2 drained)
-  float* fe_audio = nullptr; float* fe_mel = nullptr; float* fe_chunk = nullptr;
-  int fe_LA = 0, fe_LM = 0, fe_last_n = 0;
+  // --- waveform input (wavio.hip).  Streaming front-end (conan_step_wav): per slot an audio ring (sample s at s & (fe_LA - 1)) and a
+  // ring of computed log-mel frames (frame f at f & (fe_LM - 1)); fe_chunk = the [n][seg + rc][num_mels] chunk the step consumes.  Host
+  // side, per slot: samples received, frames computed, chunks emitted, phase (0 open, 1 the final call has come, 2 drained)
   struct FeSlot { long long recv = 0; int frames = 0, chunks = 0, phase = 0; };
-  std::vector<FeSlot> fe_slot;
-  // conan_step_wav_ragged: per call a [n][kRaggedWords] row table (uploaded through fe_pin) and, when the emit groups' outputs need
-  // reordering, staging for them; NS sets used round robin, set q reused only after ev_stage[q] (the last reader of the call that
-  // used it) has completed.  Allocated on the first ragged call; not stream state (state_bytes).
-  static constexpr int NS = 4;
-  PinRing fe_pin;
-  int* rg_tab[NS] = {}; int* rg_codes[NS] = {}; float* rg_mel[NS] = {}; float* rg_wav[NS] = {};
-  hipEvent_t ev_stage[NS] = {};
-  long long rg_calls = 0;
-  bool fe_last_ragged = false;      // the last wav-in call was ragged: fe_chunk holds its rows grouped by emit (conan_step_wav_chunk refuses)
-  void ragged_init();
-  // input resampler (conan_streams_set_input_rate): per slot the filter (null: input at the model rate), input samples received,
-  // model-rate samples handed to the front-end, phase (1: the input's final call has come).  The history ring ([max_slots][kRsRing],
-  // stream state) and per call a row table and model-rate staging (NS sets, set q reused after ev_rs[q]: the front-end launch that
-  // read it has completed) are allocated by the first conan_streams_set_input_rate.
   struct RsSlot { const ch::RsTable* f = nullptr; long long in = 0, out = 0; int phase = 0; };
-  std::vector<RsSlot> rs_slot;
-  float* rs_ring = nullptr;
-  PinRing rs_pin;
-  cnk::RsRow* rs_rows[NS] = {}; float* rs_wav[NS] = {};
-  hipEvent_t ev_rs[NS] = {};
-  long long rs_calls = 0;
+  struct WavIn {
+    float* fe_audio = nullptr; float* fe_mel = nullptr; float* fe_chunk = nullptr;
+    int fe_LA = 0, fe_LM = 0, fe_last_n = 0;
+    std::vector<FeSlot> fe_slot;
+    // conan_step_wav_ragged: per call a [n][kRaggedWords] row table (set q of rg_sets) and, when the emit groups' outputs need
+    // reordering, staging for them beside it; the set's event follows the last reader of the call.  Allocated on the first ragged
+    // call; not stream state (state_bytes).
+    StageSets<RgRow> rg_sets;
+    int* rg_codes[kStageSets] = {}; float* rg_mel[kStageSets] = {}; float* rg_wav[kStageSets] = {};
+    bool fe_last_ragged = false;      // the last wav-in call was ragged: fe_chunk holds its rows grouped by emit (conan_step_wav_chunk refuses)
+    // input resampler (conan_streams_set_input_rate): per slot the filter (null: input at the model rate), input samples received,
+    // model-rate samples handed to the front-end, phase (1: the input's final call has come).  The history ring ([max_slots][kRsRing],
+    // stream state) and per call a row table (set q of rs_sets) and model-rate staging beside it (the set's event follows the
+    // front-end launch that read it) are allocated by the first conan_streams_set_input_rate.
+    std::vector<RsSlot> rs_slot;
+    float* rs_ring = nullptr;
+    StageSets<cnk::RsRow> rs_sets;
+    float* rs_wav[kStageSets] = {};
+    // sample formats of the caller's rows (conan_streams_set_input_format; cnk::kFmt*), per slot; they persist across resets.  A slot
+    // with a format and no rate takes the copy rows of resample_stream_kernel.  in_fmt_n: slots whose format is not f32 (0: every
+    // launch is today's).
+    std::vector<unsigned char> in_fmt;
+    int in_fmt_n = 0;
+  } wav_in;
+  void ragged_init();
   void resample_init();        // staging, row tables and the history ring (conan_streams_set_input_rate)
   void rs_stage_init();        // staging and row tables only (conan_streams_set_input_format: no stream state)
-  // sample formats of the caller's rows (conan_streams_set_input_format / _output_format; cnk::kFmt*), per slot; they persist across
-  // resets.  A slot with a format and no rate takes the copy rows of resample_stream_kernel / resample_out_kernel.  *_fmt_n: slots
-  // whose format is not f32 (0: every launch is today's).
-  std::vector<unsigned char> in_fmt, out_fmt;
-  int in_fmt_n = 0, out_fmt_n = 0;
-  // output resampler (conan_streams_set_output_rate): per slot the filter (null: audio leaves at the model rate), output samples
-  // delivered, whether conan_streams_flush_output has ended the utterance.  voc_samples = model-rate samples the slot's vocoder has
-  // produced since its last reset with CONAN_MODEL_HIFIGAN (kept from creation on: pos_voc is device memory).  The history ring
-  // ([max_slots][or_ring_len], stream state) is allocated by the first conan_streams_set_output_rate with a real rate; conv_post's
-  // staging rows and the row table (NS sets, set q reused after ev_or[q]: the launch that read it has completed) by the first
-  // vocoder step that needs them.
+  // --- waveform output (wavio.hip).  Output resampler (conan_streams_set_output_rate): per slot the filter (null: audio leaves at the
+  // model rate), output samples delivered, whether conan_streams_flush_output has ended the utterance.  voc_samples = model-rate
+  // samples the slot's vocoder has produced since its last reset with CONAN_MODEL_HIFIGAN (kept from creation on: pos_voc is device
+  // memory).  The history ring ([max_slots][or_ring_len], stream state) is allocated by the first conan_streams_set_output_rate with a
+  // real rate; conv_post's staging rows and the row table (set q of or_sets; the set's event follows the resample_out_kernel launch
+  // that read it) by the first vocoder step that needs them.
   struct OrSlot { const ch::RsTable* f = nullptr; long long out = 0; int flushed = 0; };
-  std::vector<OrSlot> or_slot;
-  std::vector<long long> voc_samples;
-  float* or_ring = nullptr; int or_ring_len = 0;
-  PinRing or_pin;
-  cnk::RsOutRow* or_rows[NS] = {}; float* or_wav[NS] = {};
-  hipEvent_t ev_or[NS] = {};
-  long long or_calls = 0, out_ld = 0;       // out_ld: conan_streams_set_output_ld (0: each entry point's own stride)
-  std::vector<int32_t> out_counts;          // conan_streams_output_samples: per row of the most recent step call
+  struct WavOut {
+    std::vector<OrSlot> or_slot;
+    std::vector<long long> voc_samples;
+    float* or_ring = nullptr; int or_ring_len = 0;
+    StageSets<cnk::RsOutRow> or_sets;
+    float* or_wav[kStageSets] = {};
+    long long out_ld = 0;                     // conan_streams_set_output_ld (0: each entry point's own stride)
+    std::vector<int32_t> out_counts;          // conan_streams_output_samples: per row of the most recent step call
+    // sample formats of the caller's rows (conan_streams_set_output_format), as wav_in.in_fmt; the copy rows are resample_out_kernel's
+    std::vector<unsigned char> out_fmt;
+    int out_fmt_n = 0;
+  } wav_out;
   void out_stage_init();
   // One vocoder step's output rows, checked before anything changes (out_plan) and handed to hifigan_step, which commits the slots'
   // counters once its launches are enqueued.  active: the step's audio goes through staging and resample_out_kernel.
@@ -189,7 +228,9 @@ struct conan_streams {
     int tiles = 1, win = 0;
     double flops = 0;
   };
-  OutPlan out_plan(const int32_t* slots, int n, int frames, float* wav_out, long long natural_ld, const std::vector<int>* dst, const std::string& who) const;
+  OutPlan out_plan(const int32_t* slots, int n, int frames, float* wav_out_dev, long long natural_ld, const std::vector<int>* dst, const std::string& who) const;
+  // the plan's resample_out_kernel launch behind or_sets.begin() = q, then the set's event; src_ld: stride of the staged rows (a flush: 0)
+  void resample_out(const OutPlan& op, int q, long long src_ld, hipStream_t st);
   // --- vocoder
   Ring v_mel, v_pre;
   std::vector<VocStage> v_st;
@@ -229,6 +270,7 @@ struct conan_streams {
     state_bytes += (int64_t)floats * 4;
     return (float*)p;
   }
+  void* stage_alloc(size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, bytes)); allocs.push_back(p); return p; }   // per-call staging: not stream state
   Ring mk_ring(int C, int rate, int hist, std::vector<std::pair<float*, long long>>* reg) {
     Ring r; r.C = C; r.rate = rate;
     r.L = ch::next_pow2(hist + max_frames * rate);
@@ -279,9 +321,6 @@ struct conan_streams {
     if (st_voc) (void)hipStreamDestroy(st_voc);
     for (int i = 0; i < NP; ++i) { if (ev_in[i]) (void)hipEventDestroy(ev_in[i]); if (ev_fence[i]) (void)hipEventDestroy(ev_fence[i]); }
     for (int i = 0; i < NP; ++i) { if (ev_wide[i]) (void)hipEventDestroy(ev_wide[i]); if (ev_emf[i]) (void)hipEventDestroy(ev_emf[i]); if (ev_front[i]) (void)hipEventDestroy(ev_front[i]); if (ev_voc[i]) (void)hipEventDestroy(ev_voc[i]); }
-    for (int i = 0; i < NS; ++i) if (ev_stage[i]) (void)hipEventDestroy(ev_stage[i]);
-    for (int i = 0; i < NS; ++i) if (ev_rs[i]) (void)hipEventDestroy(ev_rs[i]);
-    for (int i = 0; i < NS; ++i) if (ev_or[i]) (void)hipEventDestroy(ev_or[i]);
     for (void* p : allocs) (void)hipFree(p);
     if (h_guard) (void)hipHostFree(h_guard);
     for (auto& e : prof_ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -360,7 +399,7 @@ struct conan_streams {
   void op_pitch(const cnk::PitchHeadArgs& a, hipStream_t st);
   void op_advance(int* pos, int n, int delta, hipStream_t st);
 
-  void hifigan_step(int n, int frames, const float* mel_dev, float* wav_out, float* pre_tanh, hipStream_t st, const conan_hifigan_taps* taps = nullptr,
+  void hifigan_step(int n, int frames, const float* mel_dev, float* wav_out_dev, float* pre_tanh, hipStream_t st, const conan_hifigan_taps* taps = nullptr,
                     const OutPlan* op = nullptr);
   void emformer_step(int n, const float* chunk, float* out, float* logits, int32_t* codes, hipStream_t st);
   void decoder_step(int n, int frames, const int32_t* codes, float* mel_out, const conan_decoder_taps& taps, hipStream_t st, const DecExtra* extra = nullptr);
@@ -388,4 +427,30 @@ inline void conan_streams::profiled(const std::string& name, double flops, hipSt
   prof_rec.push_back({name, flops});
 }
 
+// ---- the chunk step's stages (api.hip), shared by the mel-in entry points and the wav-in steps (wavio.hip)
+void check_chunk_step(const conan_streams* s, const char* who);
+void step_blocking(conan_streams* s, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev,
+                   hipStream_t st, const conan_streams::OutPlan& op);
+void step_pipelined(conan_streams* s, const int32_t* slots, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev, float* mel_out_dev,
+                    float* wav_out_dev, void* stream, const std::function<void(hipStream_t)>& pre, const conan_streams::OutPlan& op);
 
+// ---- waveform I/O host layer (wavio.hip): the bodies of api.hip's wav-in steps, rate / stride / format setters and output queries
+namespace wavio {
+int bytes_per_sample(int fmt);      // of a CONAN_SAMPLE_* / cnk::kFmt* code
+void check_format(int format, const char* who);
+void check_slot_list(const conan_streams* s, const int32_t* slots, int n);      // count, range, duplicates
+void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, int n, const int32_t* in_samples, const int32_t* in_final, const float* wav_dev,
+              long long wav_ld, const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream,
+              bool pipelined, bool common);
+void step_wav_common(conan_streams* s, const int32_t* slots, int n, int samples, int final, const float* wav_dev, const conan_mel_cfg* mel,
+                     int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream, bool pipelined);
+void step_wav_chunk(conan_streams* s, float* chunk_dev, void* stream);
+void set_input_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg);
+void set_output_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg);
+void set_output_ld(conan_streams* s, int64_t ld);
+void set_input_format(conan_streams* s, const int32_t* slots, int n, int format);
+void set_output_format(conan_streams* s, const int32_t* slots, int n, int format);
+int output_samples(conan_streams* s, int32_t* counts, int cap);      // -> rows of the most recent step call
+void output_pending(conan_streams* s, const int32_t* slots, int n, int32_t* counts);
+void flush_output(conan_streams* s, const int32_t* slots, int n, float* wav_out_dev, int64_t wav_ld, void* stream);
+}  // namespace wavio

@@ -503,80 +503,7 @@ void conan_streams::build_vocoder() {
   }
 }
 
-void conan_streams::out_stage_init() {
-  if (or_wav[0]) return;
-  const size_t S = (size_t)max_frames * ctx->hop;
-  auto dev = [&](size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, bytes)); allocs.push_back(p); return p; };
-  for (int q = 0; q < NS; ++q) {
-    or_rows[q] = (cnk::RsOutRow*)dev((size_t)max_slots * sizeof(cnk::RsOutRow));
-    or_wav[q] = (float*)dev((size_t)max_slots * S * sizeof(float));
-    HIP_CHECK(hipEventCreateWithFlags(&ev_or[q], hipEventDisableTiming));
-  }
-  or_pin.init((size_t)max_slots * sizeof(cnk::RsOutRow) / sizeof(int));
-}
-
-// The output rows of one vocoder step that gives each of `slots` `frames` frames (frames = 0: conan_streams_flush_output, the rest of
-// the utterance).  Row i goes to row dst[i] (i without a table) of wav_out at the stride in force: conan_streams_set_output_ld, else
-// natural_ld.  A slot with a rate receives outputs [delivered, ready(I)) for I = its model-rate samples after the step (a flush:
-// up to length(I)), any other slot its frames * hop samples.  Every row is checked and nothing changes.
-conan_streams::OutPlan conan_streams::out_plan(const int32_t* slots, int n, int frames, float* wav_out, long long natural_ld, const std::vector<int>* dst,
-                                               const std::string& who) const {
-  if (n < 1 || n > max_slots) throw Error(CONAN_ERR_INVALID, "slot count out of range");
-  OutPlan P;
-  const int T = frames * ctx->hop;
-  const bool flush = frames == 0;
-  P.base = wav_out; P.ld = (out_ld && !flush) ? out_ld : natural_ld;      // (a flush brings its own stride)
-  P.counts.assign(n, T);
-  if (dst) P.dst = *dst;
-  bool any = false;
-  for (int i = 0; i < n && (!or_slot.empty() || out_fmt_n); ++i) {
-    if (slots[i] < 0 || slots[i] >= max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
-    any = any || (!or_slot.empty() && or_slot[slots[i]].f) || out_fmt[slots[i]];      // (a format alone sends the step through the copy rows)
-  }
-  P.active = any || dst || P.ld != T;
-  if (flush) P.active = false;
-  if (!P.active && !flush) return P;
-  P.rows.resize(n);
-  for (int i = 0; i < n; ++i) {
-    if (slots[i] < 0 || slots[i] >= max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
-    cnk::RsOutRow& row = P.rows[i];
-    memset(&row, 0, sizeof(row));
-    const int fmt = out_fmt[slots[i]], bps = fmt == cnk::kFmtF32 ? 4 : (fmt == cnk::kFmtS16 ? 2 : 1);
-    row.slot = slots[i]; row.m = T; row.h = T; row.dst = (dst ? (*dst)[i] : i) | (fmt << cnk::kOrDstBits);
-    if (fmt != cnk::kFmtF32 && ((uintptr_t)wav_out & 3)) throw Error(CONAN_ERR_INVALID, who + ": wav_out_dev must be 4-byte aligned");
-    if (!or_slot.empty() && or_slot[slots[i]].f) {
-      const OrSlot& o = or_slot[slots[i]];
-      const ch::RsTable& t = *o.f;
-      const std::string where = who + ": slot " + std::to_string(slots[i]) + " (output at " + std::to_string(t.out_rate) + " Hz): ";
-      const long long in0 = voc_samples[slots[i]], I = in0 + T;
-      long long J = o.out;
-      if (flush) { if (!o.flushed) J = t.length(I); }
-      else {
-        if (o.flushed) throw Error(CONAN_ERR_STATE, where + "conan_streams_flush_output has ended the utterance; reset the slot with CONAN_MODEL_HIFIGAN first");
-        J = std::max(t.ready(I), o.out);
-      }
-      // the samples still to be read ([first tap of output o.out, I), up to a rounding step) must fit the history ring
-      if (I - (t.first(o.out) - 4) > or_ring_len) throw Error(CONAN_ERR_UNSUPPORTED, where + "resampler history ring too small for this configuration");
-      if (J - o.out > INT_MAX) throw Error(CONAN_ERR_INVALID, where + "too many samples in one call");
-      row.in0 = in0; row.out0 = o.out; row.taps = t.f.taps; row.ph = t.f.ph;
-      row.h = (int)(J - o.out); row.orig = t.f.orig; row.nph = t.f.nph; row.w = t.f.w; row.L = t.f.L;
-      P.active = P.active || row.h > 0;
-      P.win = std::max(P.win, t.win);
-      P.flops += 2.0 * row.h * t.f.L;
-    } else if (flush) {
-      row.h = 0;
-    }
-    P.counts[i] = row.h;
-    if ((long long)row.h * bps > P.ld * 4)
-      throw Error(CONAN_ERR_INVALID, who + ": slot " + std::to_string(slots[i]) + " (call row " + std::to_string(dst ? (*dst)[i] : i) + ") delivers " + std::to_string(row.h) +
-                                         " samples of " + std::to_string(bps) + " bytes, more than the row stride of wav_out_dev in force (" + std::to_string(P.ld) +
-                                         " x 4 bytes" + (flush ? "; conan_streams_output_pending)" : "; conan_streams_set_output_ld)"));
-    P.tiles = std::max(P.tiles, (std::max(row.h, row.m) + cnk::kRsTile - 1) / cnk::kRsTile);
-  }
-  return P;
-}
-
-void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float* wav_out, float* pre_tanh, hipStream_t st, const conan_hifigan_taps* taps,
+void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float* wav_out_dev, float* pre_tanh, hipStream_t st, const conan_hifigan_taps* taps,
                                  const OutPlan* op) {
   const conan_cfg& c = ctx->cfg;
   const int* pos = pos_voc;
@@ -597,9 +524,7 @@ void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float*
   int oq = -1;
   if (out_rows) {
     out_stage_init();
-    oq = (int)(or_calls++ % NS);
-    HIP_CHECK(hipStreamWaitEvent(st, ev_or[oq], 0));
-    or_pin.upload(reinterpret_cast<int*>(or_rows[oq]), reinterpret_cast<const int*>(op->rows.data()), (size_t)n * sizeof(cnk::RsOutRow) / sizeof(int), st);
+    oq = wav_out.or_sets.begin(op->rows.data(), n, st);
   }
   {  // mel chunk -> ring (conv_pre needs 6 frames of left context)
     cnk::CopyArgs ca; memset(&ca, 0, sizeof(ca));
@@ -728,25 +653,19 @@ void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float*
     else { for (int b = 0; b < NB; ++b) a.x[b] = s.xo[b][ND - 1].ref(); a.nsrc = NB; a.xmean = s.xs.ref(); }   // raw branch outputs: the mean is formed (and appended to xs) in the kernel
     a.slope = LR;
     a.w = ctx->vec("voc.conv_post.w"); a.bias = ctx->scalars.at("voc.conv_post.b");
-    a.wav = out_rows ? or_wav[oq] : wav_out; a.pre = pre_tanh; a.slots = d_slots; a.pos = pos; a.T = T; a.n = n; a.C = s.C; a.k = (int)ctx->scalars.at("voc.conv_post.k");
+    a.wav = out_rows ? wav_out.or_wav[oq] : wav_out_dev; a.pre = pre_tanh; a.slots = d_slots; a.pos = pos; a.T = T; a.n = n; a.C = s.C; a.k = (int)ctx->scalars.at("voc.conv_post.k");
     // the step's last kernel also advances the per-slot frame counters (one launch less)
     a.adv_pos = pos_voc; a.adv_delta = frames; a.adv_ticket = cp_ticket[ws_index(st)];
     cnk::launch_conv_post(a, st);
-    if (out_rows) {
-      cnk::ResampleOutArgs ra;
-      ra.wav = or_wav[oq]; ra.wav_ld = T; ra.ring = or_ring; ra.ring_len = or_ring_len; ra.out = op->base; ra.out_ld = op->ld;
-      ra.rows = or_rows[oq]; ra.n = n; ra.tiles = op->tiles; ra.win = op->win;
-      profiled("resample_out_kernel", op->flops, st, [&] { cnk::launch_resample_out(ra, st); });
-      HIP_CHECK(hipEventRecord(ev_or[oq], st));
-    }
+    if (out_rows) resample_out(*op, oq, T, st);
     // the launches are enqueued: the slots' host counters, and the counts conan_streams_output_samples reports
-    if (!op || op->dst.empty()) out_counts.assign(n, T);
+    if (!op || op->dst.empty()) wav_out.out_counts.assign(n, T);
     for (int i = 0; i < n; ++i) {
       const int slot = h_slots[i];
-      voc_samples[slot] += T;
+      wav_out.voc_samples[slot] += T;
       if (!op) continue;
-      if (!or_slot.empty() && or_slot[slot].f && out_rows) or_slot[slot].out += op->counts[i];
-      out_counts[op->dst.empty() ? i : op->dst[i]] = op->counts[i];
+      if (!wav_out.or_slot.empty() && wav_out.or_slot[slot].f && out_rows) wav_out.or_slot[slot].out += op->counts[i];
+      wav_out.out_counts[op->dst.empty() ? i : op->dst[i]] = op->counts[i];
     }
   }
 }

@@ -198,6 +198,16 @@ class AudioGatherRing:
             self.comm.synchronize()
 
 
+def _per_slot(value, n):
+    """One value per slot: a list or tuple as it is, anything else for all n."""
+    return list(value) if isinstance(value, (list, tuple)) else [value] * n
+
+
+def _by_value(slots, values):
+    """[(value, the slots that have it)], values in order of first appearance."""
+    return [(v, [s for s, x in zip(slots, values) if x == v]) for v in dict.fromkeys(values)]
+
+
 class StreamingVoiceConversionEngine:
     """The chunk loop of StreamingVoiceConversion.infer_once (inference/Conan.py:72-166) for many
     streams at once: mel in -> (wav, mel, codes) out, state carried in a conan_streams handle."""
@@ -238,9 +248,8 @@ class StreamingVoiceConversionEngine:
     @staticmethod
     def _set_format(slots, fmt, table, setter):
         """The slots' sample format (None: float32), one value or one per slot.  Slots that never had another format are left alone."""
-        fmts = list(fmt) if isinstance(fmt, (list, tuple)) else [fmt] * len(slots)
-        for f in dict.fromkeys(fmts):
-            group = [s for s, x in zip(slots, fmts) if x == f and ((x or "f32") != "f32" or s in table)]
+        for f, group in _by_value(slots, _per_slot(fmt, len(slots))):
+            group = [s for s in group if (f or "f32") != "f32" or s in table]
             if group:
                 setter(group, f or "f32")
 
@@ -248,9 +257,8 @@ class StreamingVoiceConversionEngine:
         """The slots' output rate (None: the model rate), one value or one per slot, and the stream-set's output stride: wide enough
         for a full chunk of the fastest slot.  Slots that never had another rate are left alone."""
         st = self.st
-        rates = list(out_rate) if isinstance(out_rate, (list, tuple)) else [out_rate] * len(slots)
-        for r in dict.fromkeys(rates):
-            group = [s for s, x in zip(slots, rates) if x == r and (x is not None or s in st.output_rates)]
+        for r, group in _by_value(slots, _per_slot(out_rate, len(slots))):
+            group = [s for s in group if r is not None or s in st.output_rates]
             if group:
                 if self.ctx.cfg.voc_upsample == 2 and r is not None:
                     raise ValueError("out_rate with an upsample 'nn' vocoder: run Streams.hifigan_step over the mel prefix and Streams.flush_output instead")
@@ -346,9 +354,8 @@ class StreamingVoiceConversionEngine:
         self._set_out_rate(slots, out_rate, out_filter)
         self._set_format(slots, in_format, self.st.input_formats, self.st.set_input_format)
         self._set_format(slots, out_format, self.st.output_formats, self.st.set_output_format)
-        rates = list(in_rate) if isinstance(in_rate, (list, tuple)) else [in_rate] * len(slots)
-        for r in dict.fromkeys(rates):
-            self._set_rate([s for s, x in zip(slots, rates) if x == r], r, filter)
+        for r, group in _by_value(slots, _per_slot(in_rate, len(slots))):
+            self._set_rate(group, r, filter)
 
     @torch.no_grad()
     def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None):
@@ -375,11 +382,8 @@ class StreamingVoiceConversionEngine:
         wav is returned at (None: the model rate).  in_formats[u] / out_formats[u]: the sample format utterance u arrives / is
         returned in (None: float32); one call then mixes formats, each row packed in its own."""
         U = len(src_wavs)
-        ifmts = list(in_formats) if in_formats is not None else [None] * U
-        ofmts = list(out_formats) if out_formats is not None else [None] * U
-        orates = list(out_rates) if out_rates is not None else [None] * U
+        ifmts, ofmts, orates, rates = (list(v) if v is not None else [None] * U for v in (in_formats, out_formats, out_rates, in_rates))
         assert len(starts) == U and len(ref_mel) == U
-        rates = list(in_rates) if in_rates is not None else [None] * U
         Ls = [self._in_len(r) for r in rates]
         pending = sorted(range(U), key=lambda u: (starts[u], u))
         free = sorted(self.slots)

@@ -533,6 +533,23 @@ class Streams:
         """Pipelined step_wav (conan_step_wav_async): the outputs are complete after join(); same return value."""
         return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, True)
 
+    def _wav_in_call(self, n, wav, codes, mel_out, wav_out, mel, pipelined, call):
+        """What the wav-in steps share: the default output buffers and their lifetime (a pipelined call's are kept until the next
+        join, a blocking call releases the kept ones) around call(mel_cfg, codes, mel_out, wav_out).  -> (codes, mel_out, wav_out)"""
+        if codes is None:
+            codes = torch.empty(n, self.seg, dtype=torch.int32, device=self.dev)
+        if mel_out is None:
+            mel_out = torch.empty(n, self.seg, self.ctx.cfg.num_mels, device=self.dev)
+        if wav_out is None:
+            wav_out = torch.empty(n, self.output_ld or self.seg * self.ctx.hop, device=self.dev)
+        mc = mel_cfg(**(mel or {}))
+        if pipelined:
+            self._keep.append((wav, wav_out, codes, mel_out))
+        call(mc, codes, mel_out, wav_out)
+        if not pipelined:
+            self._release()
+        return codes, mel_out, wav_out
+
     def _step_wav(self, slots, wav, final, codes, mel_out, wav_out, mel, pipelined):
         a, p = _i32(slots)
         n = len(a)
@@ -540,21 +557,10 @@ class Streams:
         assert wav.dim() == 2 and wav.shape[0] == n, wav.shape
         samples = wav.shape[1]
         wav, _, _ = self._in_rows(a, wav, samples)      # (rows samples * 4 bytes apart, whatever the format)
-        if codes is None:
-            codes = torch.empty(n, self.seg, dtype=torch.int32, device=self.dev)
-        if mel_out is None:
-            mel_out = torch.empty(n, self.seg, nm, device=self.dev)
-        if wav_out is None:
-            wav_out = torch.empty(n, self.output_ld or self.seg * hop, device=self.dev)
-        mc = mel_cfg(**(mel or {}))
         emit = C.c_int32(0)
         fn = self.lib.conan_step_wav_async if pipelined else self.lib.conan_step_wav
-        if pipelined:
-            self._keep.append((wav, wav_out, codes, mel_out))
-        _lib.check(fn(self.h, p, n, samples, int(bool(final)), _ptr(wav), C.byref(mc), _ptr(codes), _ptr(mel_out), _ptr(wav_out),
-                      C.byref(emit), _stream()))
-        if not pipelined:
-            self._release()
+        codes, mel_out, wav_out = self._wav_in_call(n, wav, codes, mel_out, wav_out, mel, pipelined, lambda mc, c, m, w: _lib.check(
+            fn(self.h, p, n, samples, int(bool(final)), _ptr(wav), C.byref(mc), _ptr(c), _ptr(m), _ptr(w), C.byref(emit), _stream())))
         e = emit.value
         if self.output_rates or self.output_ld or self.output_formats:
             w = self._wav_rows(wav_out, a, self.output_ld or e * hop) if e else [wav_out.view(-1)[:0].view(self._out_dtype(s)) for s in a]
@@ -579,31 +585,20 @@ class Streams:
     def _step_wav_ragged(self, slots, wav, samples, final, codes, mel_out, wav_out, mel, pipelined):
         a, p = _i32(slots)
         n = len(a)
-        hop, nm, L = self.ctx.hop, self.ctx.cfg.num_mels, self.seg * self.ctx.hop
+        L = self.seg * self.ctx.hop
         sm, sp = _i32(samples)
         fi, fp = _i32([int(bool(f)) for f in final])
         assert len(sm) == n and len(fi) == n, (n, len(sm), len(fi))
         ld = L
         if wav is not None:                           # rows are seg*hop floats apart in conan_step_wav_ragged, wider ones go through _ld
             wav, ld, _ = self._in_rows(a, wav, L)
-        if codes is None:
-            codes = torch.empty(n, self.seg, dtype=torch.int32, device=self.dev)
-        if mel_out is None:
-            mel_out = torch.empty(n, self.seg, nm, device=self.dev)
-        if wav_out is None:
-            wav_out = torch.empty(n, self.output_ld or L, device=self.dev)
-        mc = mel_cfg(**(mel or {}))
         emit = (C.c_int32 * n)()
-        if pipelined:
-            self._keep.append((wav, wav_out, codes, mel_out))
         if ld == L:
-            fn = self.lib.conan_step_wav_ragged_async if pipelined else self.lib.conan_step_wav_ragged
-            _lib.check(fn(self.h, p, n, sp, fp, _ptr(wav), C.byref(mc), _ptr(codes), _ptr(mel_out), _ptr(wav_out), emit, _stream()))
+            fn, stride = self.lib.conan_step_wav_ragged_async if pipelined else self.lib.conan_step_wav_ragged, ()
         else:
-            fn = self.lib.conan_step_wav_ragged_ld_async if pipelined else self.lib.conan_step_wav_ragged_ld
-            _lib.check(fn(self.h, p, n, sp, fp, _ptr(wav), ld, C.byref(mc), _ptr(codes), _ptr(mel_out), _ptr(wav_out), emit, _stream()))
-        if not pipelined:
-            self._release()
+            fn, stride = self.lib.conan_step_wav_ragged_ld_async if pipelined else self.lib.conan_step_wav_ragged_ld, (ld,)
+        codes, mel_out, wav_out = self._wav_in_call(n, wav, codes, mel_out, wav_out, mel, pipelined, lambda mc, c, m, w: _lib.check(
+            fn(self.h, p, n, sp, fp, _ptr(wav), *stride, C.byref(mc), _ptr(c), _ptr(m), _ptr(w), emit, _stream())))
         return list(emit), codes, mel_out, wav_out
 
     def wav_chunk(self, n):

@@ -9,14 +9,14 @@ import numpy as np
 import pytest
 import torch
 
-from conan_amd import _lib, synth
+from conan_amd import _lib
 from conan_amd.engine import StreamingVoiceConversionEngine
 from conan_amd.runtime import mel_cfg
 from tests import sample_format_ref as sf
 from tests.conftest import ARITHS
-from tests.test_gpu_stream_wav import HOP, L, SEG, ctx  # noqa: F401  (ctx: module fixture)
-from tests.test_gpu_stream_wav_resample import _equal, _lin, _ref, _sig
 from tests.test_out_rate_cpu import out_filter, schedule
+from tests.wav_helpers import (HOP, L, SEG, SENT, _equal, _lin, _mel, _profiled, _ref, _run_manual, _sig, _voc_run_bytes,  # noqa: F401
+                               ctx)  # (ctx: module fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +24,6 @@ FIXED = _lib.STREAMS_FIXED_PLAN
 RS, RO = "resample_stream_kernel", "resample_out_kernel"
 FORMATS = ("s16", "ulaw", "alaw")
 BYTES = sf.BYTES
-SENT = 0xA5
 
 
 def _cuda(a):
@@ -138,33 +137,35 @@ def test_staggered_mixed_formats_equal_decoded_floats(ctx, pipelined):
         assert _equal(got[u], want[u]), (u, pipelined)
 
 
-# ---- 3. output side: every row = conan_convert_samples of the float engine's row
-def _mel(B, T, seed):
-    return torch.from_numpy(np.stack([synth.mel(T, seed + i)[0] for i in range(B)])).cuda()
-
-
-def _voc_run(st, slots, mel, sizes, ld=None):
-    """conan_hifigan_step over `mel` in steps of sizes[k % len] frames into sentinel-filled byte buffers -> (rows per call in the
-    slots' dtypes, (frames, counts) per call).  Every byte past a row's count must keep the sentinel."""
-    n, T = mel.shape[0], mel.shape[1]
-    pos, k, rows, counts = 0, 0, [], []
-    while pos < T:
-        f = min(sizes[k % len(sizes)], T - pos)
-        raw = torch.full((n, (ld or f * HOP) * 4), SENT, dtype=torch.uint8, device="cuda")
-        got = st.hifigan_step(slots, mel[:, pos:pos + f], out=raw.view(torch.float32))
-        cnt = st.output_samples()
+@pytest.mark.parametrize("pipelined", [False, True])
+def test_staggered_all_rates_and_formats_equal_solo(ctx, pipelined):
+    """Input rates and formats and output rates and formats in the same calls, long enough (9 to 11 input chunks each, five
+    utterances on four slots, so one slot is reopened mid-run) that the ragged, input-resampler and output-resampler staging sets
+    are all reused several times over.  Each utterance equals its run alone in the slot it was given, bit for bit."""
+    ins = [(None, None), ("s16", 48000), ("ulaw", 8000), ("alaw", None), ("s16", 8000)]
+    outs_ = [(None, None), ("s16", 48000), ("ulaw", 8000), (None, 8000), ("alaw", None)]
+    ifmts, rates = [f for f, _ in ins], [r for _, r in ins]
+    ofmts, orates = [f for f, _ in outs_], [r for _, r in outs_]
+    srcs = []
+    for u, (f, r) in enumerate(ins):
+        N = (9 + u % 3) * _lin(r or 16000) + 100 * u + 37
+        srcs.append(_sig(1, N, r or 16000, 800 + u)[0] if f is None else _coded(1, N, r or 16000, 800 + u, f)[0][0])
+    U, refs, starts = 5, _ref(5, 8), [0, 0, 1, 2, 5]
+    eng = StreamingVoiceConversionEngine(ctx, 4, max_ref_frames=64, flags=FIXED)
+    outs = eng.infer_wav_staggered(srcs, starts, refs, pipelined=pipelined, in_rates=rates, out_rates=orates, in_formats=ifmts, out_formats=ofmts)
+    torch.cuda.synchronize()
+    used = eng.staggered_slots
+    assert len(set(used)) < U, "no slot was reopened"
+    solo = StreamingVoiceConversionEngine(ctx, 4, max_ref_frames=64, flags=FIXED)
+    for u in range(U):
+        solo.slots = [used[u]]
+        w, m, c = solo.infer_wav(srcs[u][None], refs[u][None], pipelined=False, in_rate=rates[u], out_rate=orates[u], in_format=ifmts[u], out_format=ofmts[u])
         torch.cuda.synchronize()
-        if not isinstance(got, (list, tuple)):
-            got = [got[i, :cnt[i]] for i in range(n)]
-        for i in range(n):
-            nb = cnt[i] * got[i].element_size()
-            assert got[i].shape[0] == cnt[i] and bool((raw[i, nb:] == SENT).all()), (pos, i, cnt)
-        rows.append([g.clone() for g in got])
-        counts.append((f, cnt))
-        pos, k = pos + f, k + 1
-    return rows, counts
+        assert outs[u][0].dtype == sf_dtype(ofmts[u] or "f32")
+        assert _equal(outs[u], (w[0], m[0], c[0])), (u, ins[u], outs_[u], pipelined)
 
 
+# ---- 3. output side: every row = conan_convert_samples of the float engine's row
 def _out_cases():
     out = []
     for fmt in FORMATS:
@@ -191,8 +192,8 @@ def test_output_format_equals_converted_rows(ctx, fmt, rate, preset, arith):
         bytes0 = b.state_bytes
         b.set_output_format(slots, fmt)
         assert b.state_bytes == bytes0 == a.state_bytes
-        rows_a, counts_a = _voc_run(a, slots, mel, sizes, ld)
-        rows_b, counts_b = _voc_run(b, slots, mel, sizes, ld)
+        rows_a, counts_a = _voc_run_bytes(a, slots, mel, sizes, ld)
+        rows_b, counts_b = _voc_run_bytes(b, slots, mel, sizes, ld)
         assert counts_a == counts_b, (fmt, rate, sizes)
         if rate:
             want, tail = schedule(out_filter(rate, preset), [fr * HOP for fr, _ in counts_b])
@@ -267,13 +268,6 @@ def test_telephony_ulaw_8k_in_and_out(ctx):
 
 
 # ---- 5. launch accounting
-def _profiled(st, fn):
-    st.profile_begin()
-    out = fn()
-    st.profile_end()
-    return out, {k[0]: k[3] for k in st.profile_kernels()}
-
-
 def _launches_per_call(eng, src, **start):
     """(samples > 0, emit, resample_stream_kernel launches, resample_out_kernel launches) per call of a blocking feed loop, drain included."""
     eng.start_wav(_ref(src.shape[0]), **start)
@@ -327,30 +321,6 @@ def test_launch_accounting(ctx):
 
 
 # ---- 6. errors and persistence
-def _run_manual(eng, src, Li, hook=None):
-    """Blocking step_wav loop of one utterance on eng.slots (rates and formats already set); hook(call index) runs before each call."""
-    N = src.shape[1]
-    last = (N - 1) // Li * Li
-    outs, pos, fin, i = [], 0, False, 0
-    while True:
-        if hook:
-            hook(i)
-        i += 1
-        if pos < last:
-            e, c, m, w = eng.st.step_wav(eng.slots, src[:, pos:pos + Li])
-            pos += Li
-        else:
-            e, c, m, w = eng.st.step_wav(eng.slots, src[:, pos:] if not fin else src[:, :0], final=True)
-            pos, done, fin = N, fin and e == 0, True
-            if done:
-                break
-        if e:
-            w = torch.stack(list(w)) if isinstance(w, (list, tuple)) else w
-            outs.append((w.clone(), m.clone(), c[:, :e].clone()))
-    torch.cuda.synchronize()
-    return [torch.cat(t, 1) for t in zip(*outs)]
-
-
 def test_unknown_format_and_wrong_dtype(ctx):
     eng = StreamingVoiceConversionEngine(ctx, 2, max_ref_frames=64)
     eng.start_wav(_ref(2))

@@ -13,6 +13,7 @@ from conan_amd.engine import StreamingVoiceConversionEngine
 from conan_amd.runtime import mel_cfg
 from tests.conftest import ARITHS
 from tests.test_gpu_stream_wav import HOP, L, LENGTHS, SEG, _calls, _ref, _wav, ctx  # noqa: F401  (ctx: module fixture)
+from tests.wav_helpers import _equal
 
 pytestmark = pytest.mark.gpu
 
@@ -47,10 +48,6 @@ def _solo(eng, x, ref):
     w, m, c = eng.infer_wav(x[None], ref[None], pipelined=False)
     torch.cuda.synchronize()
     return w[0], m[0], c[0]
-
-
-def _equal(a, b):
-    return all(torch.equal(x, y) for x, y in zip(a, b))
 
 
 # ---- 1. slots at a common position: the ragged step is conan_step_wav

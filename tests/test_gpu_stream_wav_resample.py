@@ -14,33 +14,13 @@ from conan_amd.engine import StreamingVoiceConversionEngine
 from conan_amd.runtime import mel_cfg
 from tests import resample_ref
 from tests.conftest import ARITHS
-from tests.test_gpu_stream_wav import HOP, L, SEG, ctx  # noqa: F401  (ctx: module fixture)
+from tests.wav_helpers import HOP, L, SEG, _equal, _lin, _ref, _run_manual_at_rate, _sig, _staggered_in_rates, ctx  # noqa: F401  (ctx: module fixture)
 
 pytestmark = pytest.mark.gpu
 
 FIXED = _lib.STREAMS_FIXED_PLAN
 RS = "resample_stream_kernel"
 PRESET_ARGS = {"hann": (6, 0.99, "hann", None), "kaiser_best": (64, 0.9475937167399596, "kaiser", None)}
-
-
-def _sig(B, N, rate, seed):
-    """Speech-band tones plus noise at `rate` Hz, [B, N] cuda float32."""
-    rng = np.random.default_rng(seed)
-    t = np.arange(N) / float(rate)
-    w = [0.3 * np.sin(2 * np.pi * (150 + 70 * i) * t) + 0.1 * np.sin(2 * np.pi * 2300 * t) + 0.05 * rng.standard_normal(N) for i in range(B)]
-    return torch.from_numpy(np.stack(w).astype(np.float32)).cuda()
-
-
-def _ref(B, seed=3):
-    return torch.from_numpy(synth.mel(40, seed, B)).cuda()
-
-
-def _lin(rate):
-    return L * rate // 16000
-
-
-def _equal(a, b):
-    return all(torch.equal(x, y) for x, y in zip(a, b))
 
 
 # ---- 1. whole signals against float64
@@ -166,19 +146,10 @@ def test_set_without_rate_launches_as_before(ctx):
 
 
 # ---- 4. ragged calls mixing rates
-def _staggered_inputs(U, seed):
-    rng = np.random.default_rng(seed)
-    pool = [8000, 11025, 22050, 24000, 32000, 44100, 48000, 96000]
-    rates = [16000 if u % 4 == 0 else int(rng.choice(pool)) for u in range(U)]
-    srcs = [_sig(1, int(rng.integers(r // 10, r // 2 + 2 * _lin(r))), r, 100 + u)[0] for u, r in enumerate(rates)]
-    starts = sorted(int(v) for v in rng.integers(0, 12, U))
-    return rates, srcs, starts
-
-
 @pytest.mark.parametrize("pipelined", [False, True])
 def test_staggered_mixed_rates_equal_solo(ctx, pipelined):
     U, B = 72, 64
-    rates, srcs, starts = _staggered_inputs(U, 11)
+    rates, srcs, starts = _staggered_in_rates(U, 11)
     refs = _ref(U, 5)
     eng = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64, flags=FIXED)
     outs = eng.infer_wav_staggered(srcs, starts, refs, pipelined=pipelined, in_rates=rates)
@@ -209,37 +180,13 @@ def test_mixed_rate_call_one_launch(ctx):
 
 
 # ---- 5. errors leave every slot unchanged; resets
-def _run_manual(eng, src, rate, preset, hook=None):
-    """Blocking feed loop of one utterance on eng.slots (the rate already set); hook(call_index) runs before each call."""
-    Li = _lin(rate)
-    N = src.shape[1]
-    last = (N - 1) // Li * Li
-    outs, pos, fin, i = [], 0, False, 0
-    while True:
-        if hook:
-            hook(i)
-        i += 1
-        if pos < last:
-            e, c, m, w = eng.st.step_wav(eng.slots, src[:, pos:pos + Li])
-            pos += Li
-        else:
-            e, c, m, w = eng.st.step_wav(eng.slots, src[:, pos:] if not fin else src[:, :0], final=True)
-            pos, done, fin = N, fin and e == 0, True
-            if done:
-                break
-        if e:
-            outs.append((w.clone(), m.clone(), c[:, :e].clone()))
-    torch.cuda.synchronize()
-    return [torch.cat(t, 1) for t in zip(*outs)]
-
-
 def test_errors_leave_slots_unchanged(ctx):
     rate, B = 48000, 2
     src = _sig(B, 3 * _lin(rate) + 101, rate, 21)
     ref = _ref(B)
     clean = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64)
     clean.start_wav(ref, in_rate=rate)
-    want = _run_manual(clean, src, rate, "hann")
+    want = _run_manual_at_rate(clean, src, rate, "hann")
 
     eng = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64)
     eng.start_wav(ref, in_rate=rate)
@@ -273,7 +220,7 @@ def test_errors_leave_slots_unchanged(ctx):
         expect(lib.conan_step_wav(h, slots, B, L, 0, C.c_void_p(wav.data_ptr()), C.byref(mc), None, None, C.c_void_p(out.data_ptr()),
                                   C.byref(e), None), _lib.ERR_INVALID)
 
-    got = _run_manual(eng, src, rate, "hann", hook)
+    got = _run_manual_at_rate(eng, src, rate, "hann", hook)
     assert _equal(got, want)
 
 
@@ -300,12 +247,12 @@ def test_reset_keeps_rate_and_clears_history(ctx, rate, preset):
     ref = _ref(B)
     eng = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64)
     eng.start_wav(ref, in_rate=rate, preset=preset)
-    _run_manual(eng, a, rate, preset)
+    _run_manual_at_rate(eng, a, rate, preset)
     eng.start(ref, which=7 | 8)                 # a reset with CONAN_MODEL_FRONTEND, no new set_input_rate
-    got = _run_manual(eng, b, rate, preset)
+    got = _run_manual_at_rate(eng, b, rate, preset)
     fresh = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64)
     fresh.start_wav(ref, in_rate=rate, preset=preset)
-    assert _equal(got, _run_manual(fresh, b, rate, preset))
+    assert _equal(got, _run_manual_at_rate(fresh, b, rate, preset))
 
 
 def test_state_bytes(ctx):
