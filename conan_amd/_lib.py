@@ -100,6 +100,7 @@ _PROTOS = {
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_resample_length": (C.c_int64, [C.c_void_p, C.c_int64]),
     "conan_resample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_loud_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "conan_streams_set_input_rate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "conan_streams_set_output_rate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "conan_streams_set_output_ld": (C.c_int, [C.c_void_p, C.c_int64]),
@@ -216,6 +217,11 @@ def resample_cfg(orig_freq, new_freq=16000, lowpass_filter_width=6, rolloff=0.99
     window = RESAMPLE_HANN if resampling_method == "sinc_interp_hann" else RESAMPLE_KAISER
     return ResampleCfg(int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff), window,
                        float(beta) if beta is not None else 0.0, (C.c_int32 * 2)(0, 0))
+
+
+class LoudnessCfg(C.Structure):
+    """conan_loudness_cfg (include/conan_hip.h)."""
+    _fields_ = [("sample_rate", C.c_int32), ("target_lufs", C.c_float), ("peak_limit", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class DecoderTaps(C.Structure):

@@ -585,6 +585,15 @@ int conan_resample(conan_ctx* ctx, const conan_resample_cfg* cfg, const float* x
   });
 }
 
+int conan_loud_norm(conan_ctx* ctx, const conan_loudness_cfg* cfg, const float* x_dev, int64_t x_ld, int n, const int64_t* samples, float* y_dev,
+                    int64_t y_ld, double* stats_dev, void* stream) {
+  return guarded([&] {
+    if (!ctx || !cfg || !x_dev || !samples) throw Error(CONAN_ERR_INVALID, "null argument");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    conan_ctx_loud_norm(ctx, *cfg, x_dev, x_ld, n, samples, y_dev, y_ld, stats_dev, (hipStream_t)stream);
+  });
+}
+
 int conan_streams_set_input_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg) {
   return guarded([&] { wavio::set_input_rate(s, slots, n, cfg); });
 }

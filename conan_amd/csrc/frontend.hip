@@ -391,6 +391,19 @@ std::string conan_ctx::mel_tables(const conan_mel_cfg& m) {
   return k;
 }
 
+float* conan_ctx::workspace(size_t floats, hipStream_t st) {
+  if (floats > fe_ws_floats) {      // grow: the previous block is released once the stream has drained
+    if (fe_ws) {
+      HIP_CHECK(hipStreamSynchronize(st));
+      for (size_t i = 0; i < allocs.size(); ++i) if (allocs[i] == fe_ws) { allocs.erase(allocs.begin() + i); break; }
+      HIP_CHECK(hipFree(fe_ws));
+      fe_ws = nullptr; fe_ws_floats = 0;
+    }
+    fe_ws = dev_alloc(floats, false); fe_ws_floats = floats;
+  }
+  return fe_ws;
+}
+
 void conan_ctx::wav2mel(const conan_mel_cfg& m, const float* wav, int n, int samples, float* mel_out, hipStream_t st) {
   using ch::Error;
   if (m.fft_size < 64 || (m.fft_size & (m.fft_size - 1)) || m.fft_size > 2048 || m.hop_size < 1 || m.win_length < 1 || m.win_length > m.fft_size ||
@@ -408,15 +421,7 @@ void conan_ctx::wav2mel(const conan_mel_cfg& m, const float* wav, int n, int sam
   if (rows > (1ll << 19)) throw Error(CONAN_ERR_INVALID, "wav2mel: more than 2^19 frames in one call");
   // workspace: frames [rows][N] | magnitude [rows][CM]
   const size_t need = (size_t)rows * ((size_t)N + CM);
-  if (need > fe_ws_floats) {      // grow: the previous block is released once the stream has drained
-    if (fe_ws) {
-      HIP_CHECK(hipStreamSynchronize(st));
-      for (size_t i = 0; i < allocs.size(); ++i) if (allocs[i] == fe_ws) { allocs.erase(allocs.begin() + i); break; }
-      HIP_CHECK(hipFree(fe_ws));
-    }
-    fe_ws = dev_alloc(need, false); fe_ws_floats = need;
-  }
-  float* fr = fe_ws; float* mag = fr + (size_t)rows * N;
+  float* fr = workspace(need, st); float* mag = fr + (size_t)rows * N;
   { cnk::FrameArgs a{wav, vec(k + ".win"), fr, n, samples, frames, m.hop_size, N, m.framing}; hipLaunchKernelGGL(cnk::stft_frames_kernel, dim3((unsigned)rows), dim3(256), 0, st, a); }
   { cnk::DftArgs a{fr, reinterpret_cast<const double2*>(vec(k + ".tw")), mag, N, NB, CM, m.mag_eps};
     hipLaunchKernelGGL(cnk::dft_mag_kernel, dim3((unsigned)rows, (unsigned)((CM + 255) / 256)), dim3(256), (size_t)N * 24, st, a); }

@@ -110,6 +110,28 @@ struct RsTable {
     return best;
   }
 };
+// Pinned staging of a whole-signal call's host table (loudness.hip): a buffer is reused only after the copy that read it has
+// completed (the wait is on the host, for a copy four calls old).
+struct TableStage {
+  static constexpr int N = 4;
+  void* buf[N] = {}; size_t cap[N] = {}; hipEvent_t ev[N] = {}; int next = 0;
+  void* take(size_t bytes) {
+    const int q = next;
+    if (!ev[q]) HIP_CHECK(hipEventCreateWithFlags(&ev[q], hipEventDisableTiming));
+    HIP_CHECK(hipEventSynchronize(ev[q]));
+    if (bytes > cap[q]) {
+      if (buf[q]) HIP_CHECK(hipHostFree(buf[q]));
+      buf[q] = nullptr; cap[q] = 0;
+      HIP_CHECK(hipHostMalloc(&buf[q], bytes, hipHostMallocDefault));
+      cap[q] = bytes;
+    }
+    return buf[q];
+  }
+  void sent(hipStream_t st) { HIP_CHECK(hipEventRecord(ev[next], st)); next = (next + 1) % N; }
+  ~TableStage() {
+    for (int q = 0; q < N; ++q) { if (ev[q]) (void)hipEventDestroy(ev[q]); if (buf[q]) (void)hipHostFree(buf[q]); }
+  }
+};
 }  // namespace ch
 
 struct conan_ctx {
@@ -144,15 +166,21 @@ struct conan_ctx {
   void finalize_hifigan();
   void finalize_conan();
   void finalize_emformer();
-  // mel front-end (frontend.hip): tables are built on first use per configuration; one workspace, regrown when a call needs more
+  // mel front-end (frontend.hip): tables are built on first use per configuration; one workspace, shared with conan_loud_norm,
+  // regrown when a call needs more (the previous block is released once `st` has drained)
   float* fe_ws = nullptr; size_t fe_ws_floats = 0;
+  float* workspace(size_t floats, hipStream_t st);
   void wav2mel(const conan_mel_cfg& m, const float* wav, int n, int samples, float* mel_out, hipStream_t st);
   std::string mel_tables(const conan_mel_cfg& m);          // window / twiddle / filterbank tables (vecs key prefix)
   // resampler (resample.hip): taps built on first use per configuration (CONAN_ERR_INVALID for a configuration it refuses)
   std::map<std::string, ch::RsTable> rs_tabs;
   const ch::RsTable& resample_table(const conan_resample_cfg& c);
+  ch::TableStage loud_stage;                               // conan_loud_norm's per-call table (loudness.hip)
   ~conan_ctx();
 };
 
 // conan_resample's body (resample.hip)
 void conan_ctx_resample(conan_ctx* ctx, const conan_resample_cfg& c, const float* x, int n, int64_t samples, float* y, int64_t* out_samples, hipStream_t st);
+// conan_loud_norm's body (loudness.hip)
+void conan_ctx_loud_norm(conan_ctx* ctx, const conan_loudness_cfg& c, const float* x, int64_t x_ld, int n, const int64_t* samples, float* y,
+                         int64_t y_ld, double* stats, hipStream_t st);

@@ -605,6 +605,56 @@ void launch_resample_out(const ResampleOutArgs& a, hipStream_t st);
 struct ConvertSamplesArgs { const void* src; void* dst; long long src_ld, dst_ld, samples; int src_fmt, dst_fmt; };
 void launch_convert_samples(const ConvertSamplesArgs& a, int n, hipStream_t st);
 
+// ---- loudness meter and gain (loudness.hip): BS.1770 K-weighting and gating as include/conan_hip.h states them (conan_loudness_cfg).
+// The K-weighting recursion is serial in time and linear, so a row is cut into segments of kLdSeg samples, one lane each: loud_state_kernel
+// runs every segment from a zero state, loud_scan_kernel turns the segments' end states into their true start states
+// (in[s + 1] = M in[s] + end[s], M = the transition matrix of one whole segment), loud_energy_kernel re-runs every segment from its start
+// state and sums y^2 into the bins between consecutive block edges, loud_gate_kernel (one workgroup per row) sums the bins over the
+// segments and the blocks over their bins, gates, and writes the row's gain, loud_apply_kernel scales.  All filter and energy arithmetic
+// is f64; every sum has one order, fixed by the row alone.
+constexpr int kLdSeg = 128;                      // samples per segment (why 128)
+constexpr int kLdLanes = 64;                     // segments per workgroup of the state / energy passes: one wave
+constexpr int kLdStride = kLdSeg + 1;            // LDS floats between two lanes' segments: lane l, step t reads bank (l + t) mod 32
+constexpr int kLdTile = kLdSeg * kLdLanes;       // samples per workgroup
+constexpr int kLdSlots = 4;                      // bins a segment can touch: at most 3 edges inside a segment (the host checks)
+struct LdBiquad { double b0, b1, b2, a1, a2; };  // normalised by a0; direct form II transposed
+struct LdRow {                                   // one call row (12 ints, uploaded with the edge and block tables)
+  long long samples, seg0;                       // seg0: the row's first segment in the state / partial-sum arrays
+  int nseg, edge0, nedges, blk0, nblocks, pad_[3];   // edge0 / blk0: the row's first entry in the edge / block tables
+};
+static_assert(sizeof(LdRow) == 12 * sizeof(int), "LdRow is uploaded as 12 ints");
+struct LoudArgs {
+  const float* x; long long x_ld;
+  float* y; long long y_ld;                      // y may be null (measure only) or x
+  const LdRow* rows; int n;
+  const int* edges;                              // per row: the sorted distinct block starts and ends; bin b = [edge[b], edge[b + 1])
+  const int* blocks;                             // per row and block: first bin, end bin
+  double* state;                                 // [segments][4]: end states, then (scan) start states
+  double* part;                                  // [segments][kLdSlots]: slot k = the sum over the segment's k-th bin
+  float* peak;                                   // [segments]: max |x|
+  double* binsum;                                // [edges]
+  double* z; double* l;                          // [blocks]: block energies and loudnesses
+  double* gain;                                  // [n][2]: gain, divisor (0: none)
+  double* stats;                                 // caller's [n][4] or null
+  LdBiquad shelf, hp;
+  double M[16];                                  // row-major transition matrix of kLdSeg zero inputs
+  double block_len;                              // T_g * fs
+  double target; int peak_limit;
+  int tiles;                                     // the longest row's workgroups in the state / energy passes
+};
+void launch_loud_measure(const LoudArgs& a, hipStream_t st);      // state, scan, energy, gate
+void launch_loud_apply(const LoudArgs& a, long long longest, hipStream_t st);
+// one step of the cascade (shelf, then high pass) on state s[4]; shared by the kernels and the host (M)
+__host__ __device__ inline double ld_step(const LdBiquad& f, const LdBiquad& g, double* s, double x) {
+  const double u = fma(f.b0, x, s[0]);
+  s[0] = fma(-f.a1, u, fma(f.b1, x, s[1]));
+  s[1] = fma(-f.a2, u, f.b2 * x);
+  const double y = fma(g.b0, u, s[2]);
+  s[2] = fma(-g.a1, y, fma(g.b1, u, s[3]));
+  s[3] = fma(-g.a2, y, g.b2 * u);
+  return y;
+}
+
 // ---- style pass (per utterance) helpers
 struct RowMaskArgs { TRef x; TRef m; const int* lens; int T, n, C; int mode; };  // mode 0: sum|x|>0, 1: x[0]!=0
 void launch_rowmask(const RowMaskArgs& a, hipStream_t st);

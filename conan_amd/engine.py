@@ -295,7 +295,9 @@ class StreamingVoiceConversionEngine:
         rate set by start_wav, seg*hop*in_rate/model_rate) ->
         (wav [B, emit*hop], mel [B, emit, 80], codes [B, emit]) of the chunk this call emitted (emit = 0 on the first call: one
         chunk of algorithmic latency).  After final=True keep calling feed(empty, final=True) until it returns 0 frames.
-        pipelined: conan_step_wav_async - the tensors are complete after self.st.join()."""
+        pipelined: conan_step_wav_async - the tensors are complete after self.st.join().
+        The reference's loud_norm cannot run here: the loudness is a property of the whole utterance, which a streaming call has not
+        seen yet (infer_wav(loud_norm=True) normalises an utterance it holds whole)."""
         fn = self.st.step_wav_async if pipelined else self.st.step_wav
         st = self.st
         if not (st.output_ld or st.output_formats):
@@ -309,14 +311,25 @@ class StreamingVoiceConversionEngine:
         return w, m, c[:, :emit]
 
     @torch.no_grad()
+    def _loud_norm(self, wav, in_rate, in_format):
+        """The reference's loud_norm (Context.loud_norm: -22 LUFS, peak limit) of whole float32 utterances [..., N] at their input rate."""
+        if in_format not in (None, "f32"):
+            raise ValueError("loud_norm takes float32 rows: decode the utterance first (Context.convert_samples) or pass in_format=None")
+        return self.ctx.loud_norm(wav, in_rate or self.st.model_rate)
+
+    @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
-                  out_format=None, **filter):
+                  out_format=None, loud_norm=False, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
         out_rate (+ out_filter): the returned wav is the whole utterance at that rate, ctx.resample of the model-rate wav bit for bit.
         in_format: src_wav's sample format (int16 / uint8 samples; the results are those of the decoded floats, ctx.convert_samples,
-        bit for bit); out_format: the returned wav's format (ctx.convert_samples of the float wav bit for bit)."""
+        bit for bit); out_format: the returned wav's format (ctx.convert_samples of the float wav bit for bit).
+        loud_norm: each whole source utterance is loudness-normalised at its input rate before it is fed (the reference's loud_norm;
+        float32 rows only); the results are those of infer_wav(ctx.loud_norm(src_wav, rate), ...) bit for bit."""
+        if loud_norm:
+            src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
@@ -363,7 +376,8 @@ class StreamingVoiceConversionEngine:
         first samples[i] samples of wav row i (wav [n, <= seg*hop] cuda, or a list of 1-D rows, each in its slot's input format's
         dtype) with its own final flag; the rules per slot are feed()'s.
         -> one (wav [emit*hop], mel [emit, 80], codes [emit]) per slot, of the chunk it emitted (emit = 0: empty).
-        pipelined: conan_step_wav_ragged_async - the tensors are complete after self.st.join()."""
+        pipelined: conan_step_wav_ragged_async - the tensors are complete after self.st.join().
+        As in feed(), the reference's loud_norm cannot run here (infer_wav_staggered(loud_norm=True) holds the utterances whole)."""
         fn = self.st.step_wav_ragged_async if pipelined else self.st.step_wav_ragged
         emit, c, m, w = fn(slots, wav, samples, final, mel=mel)
         counts = self.st.output_samples()        # (emit * hop for a slot without an output rate)
@@ -371,7 +385,7 @@ class StreamingVoiceConversionEngine:
 
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
-                            in_formats=None, out_formats=None, **filter):
+                            in_formats=None, out_formats=None, loud_norm=False, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -380,9 +394,12 @@ class StreamingVoiceConversionEngine:
         left in self.staggered_slots.  in_rates[u] (+ filter keywords): utterance u's sample rate (None: the model rate); one call
         then mixes rates, with rows as wide as the widest input of the call.  out_rates[u] (+ out_filter): the rate utterance u's
         wav is returned at (None: the model rate).  in_formats[u] / out_formats[u]: the sample format utterance u arrives / is
-        returned in (None: float32); one call then mixes formats, each row packed in its own."""
+        returned in (None: float32); one call then mixes formats, each row packed in its own.  loud_norm: every utterance is
+        loudness-normalised whole, at its own input rate, before its first audio is fed (float32 utterances only)."""
         U = len(src_wavs)
         ifmts, ofmts, orates, rates = (list(v) if v is not None else [None] * U for v in (in_formats, out_formats, out_rates, in_rates))
+        if loud_norm:
+            src_wavs = [self._loud_norm(x, rates[u], ifmts[u]) for u, x in enumerate(src_wavs)]
         assert len(starts) == U and len(ref_mel) == U
         Ls = [self._in_len(r) for r in rates]
         pending = sorted(range(U), key=lambda u: (starts[u], u))

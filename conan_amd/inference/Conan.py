@@ -78,14 +78,16 @@ class StreamingVoiceConversion:
 
     def _wav_to_mel(self, wav) -> torch.Tensor:
         """inference/Conan.py:57-70 on the GPU: path or float array -> clipped log-mel [T, 80] (cuda).  A file at another rate is
-        resampled on the GPU (kaiser_best) where the reference's librosa.core.load(sr=...) resamples."""
+        resampled on the GPU (kaiser_best) where the reference's librosa.core.load(sr=...) resamples; hparams['loud_norm'] normalises the
+        loudness on the GPU (conan_loud_norm) where the reference calls pyloudnorm."""
         from ..utils.audio import load_wav_resampled
         hp = self.hparams
         if isinstance(wav, str):
             wav = load_wav_resampled(wav, hp["audio_sample_rate"], self.ctx)
-        if hp.get("loud_norm", False):
-            raise NotImplementedError("loud_norm is off on the inference path (egs_bases/tts/dataset_params.yaml:15)")
-        return self.ctx.wav2mel(torch.as_tensor(np.asarray(wav), dtype=torch.float32), fft_size=hp["fft_size"], hop_size=hp["hop_size"],
+        wav = torch.as_tensor(np.asarray(wav), dtype=torch.float32)
+        if hp.get("loud_norm", False):      # utils/audio/__init__.py:58-63, for the reference wav and the source wav alike
+            wav = self.ctx.loud_norm(wav, hp["audio_sample_rate"], target=-22.0, peak_limit=True)
+        return self.ctx.wav2mel(wav, fft_size=hp["fft_size"], hop_size=hp["hop_size"],
                                 win_length=hp["win_size"], num_mels=hp["audio_num_mel_bins"], fmin=hp["fmin"], fmax=hp["fmax"],
                                 sample_rate=hp["audio_sample_rate"], mel_vmin=hp["mel_vmin"], mel_vmax=hp["mel_vmax"])[0]
 

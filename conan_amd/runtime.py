@@ -96,7 +96,8 @@ class Context:
     def wav2mel(self, wav, fft_size=1024, hop_size=320, win_length=1024, num_mels=80, fmin=80, fmax=7600, sample_rate=16000,
                 eps=1e-6, mel_vmin=-6.0, mel_vmax=1.5, framing=0, natural_log=False, mag_eps=0.0):
         """Mel front-end on the GPU (conan_wav2mel): wav cuda float32 [n, samples] -> mel [n, frames, num_mels].
-        Defaults: clip(librosa_wav2spec(wav)['mel'], mel_vmin, mel_vmax) of inference/Conan.py:57-70 (loud_norm off),
+        Defaults: clip(librosa_wav2spec(wav)['mel'], mel_vmin, mel_vmax) of inference/Conan.py:57-70 (its loud_norm branch is
+        Context.loud_norm, run on the waveform first),
         frames = 1 + samples // hop.  framing=1, natural_log=True, mag_eps=1e-9: the torch.stft front-end of
         inference/Conan_previous.py:100-121 (reflect padding, center=False), frames = samples // hop."""
         wav = wav.to(torch.device("cuda", self.device), torch.float32).contiguous()
@@ -131,6 +132,50 @@ class Context:
             _lib.check(self.lib.conan_resample(self.h, C.byref(cfg), _ptr(x), n, N, _ptr(y), C.byref(got), _stream()))
             assert got.value == nout
         return y
+
+    def _loud_call(self, x, sample_rate, target, peak_limit, lengths, out, measure_only):
+        """One conan_loud_norm call over the rows of x -> (y or None, stats float64 [n, 4], the leading shape)."""
+        dev = torch.device("cuda", self.device)
+        x = x.to(dev, torch.float32)
+        lead, N = x.shape[:-1], x.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        if not (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= N):      # (a 2-D view with a row stride is read in place)
+            x = x.reshape(n, N).contiguous()
+        lens = np.full(n, N, dtype=np.int64) if lengths is None else np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+        if lens.shape[0] != n:
+            raise ValueError(f"loud_norm: {lens.shape[0]} lengths for {n} rows")
+        y = None
+        if not measure_only:
+            if out is not None:
+                if not (out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == n and out.stride(1) == 1):
+                    raise ValueError("loud_norm: out must be a cuda float32 [n, ld] buffer with unit column stride")
+                y = out
+            else:
+                y = x.clone() if lengths is not None else torch.empty(n, N, device=dev)      # (the floats past a row's length stay x's)
+        stats = torch.empty(n, 4, dtype=torch.float64, device=dev)
+        cfg = _lib.LoudnessCfg(int(sample_rate), float(target), int(bool(peak_limit)), (C.c_int32 * 3)(0, 0, 0))
+        _lib.check(self.lib.conan_loud_norm(self.h, C.byref(cfg), _ptr(x), x.stride(0), n, lens.ctypes.data_as(C.c_void_p), _ptr(y),
+                                            y.stride(0) if y is not None else 0, _ptr(stats), _stream()))
+        return y, stats, lead
+
+    def loud_norm(self, x, sample_rate, target=-22.0, peak_limit=True, lengths=None, return_stats=False, out=None):
+        """The reference's loud_norm (librosa_wav2spec, utils/audio/__init__.py:58-63) on the GPU (conan_loud_norm): x [..., N] float32
+        at `sample_rate` -> the rows measured with a BS.1770 meter, scaled to `target` LUFS and, with peak_limit, divided by their
+        peak where that exceeds 1.  lengths: samples per row (default N; the floats past a row's length come back as x's).  A row
+        without a loudness (silence, or nothing above the meter's absolute gate) comes back unchanged; a row shorter than 0.4 s is an
+        error.  return_stats: also the float64 [..., 4] stats (LUFS, gain applied, peak before limiting, blocks in the gated set).
+        out: a cuda float32 [n, ld] buffer to write the rows into (it may be x itself: in place); only the first lengths[i] floats
+        of a row are written."""
+        y, stats, lead = self._loud_call(x, sample_rate, target, peak_limit, lengths, out, False)
+        if out is None:
+            y = y.reshape(*lead, y.shape[-1])
+        return (y, stats.reshape(*lead, 4)) if return_stats else y
+
+    def loudness(self, x, sample_rate, lengths=None):
+        """Integrated loudness (BS.1770, as pyloudnorm's Meter.integrated_loudness) of the rows of x [..., N] -> float64 [...] LUFS
+        (-inf for a row with nothing above the absolute gate).  A measure-only conan_loud_norm call."""
+        _, stats, lead = self._loud_call(x, sample_rate, -22.0, True, lengths, None, True)
+        return stats[:, 0].reshape(*lead) if len(lead) else stats[0, 0]
 
     def convert_samples(self, x, src, dst, out=None):
         """conan_convert_samples: x [..., N] of format `src` ('f32' float32, 's16' int16, 'ulaw' / 'alaw' uint8) -> [..., N] of

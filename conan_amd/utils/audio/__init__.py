@@ -3,8 +3,8 @@
 `librosa_wav2spec` keeps the reference's keyword arguments; the STFT, mel projection and log run on the GPU
 (conan_wav2mel).  A path argument is read with the standard-library `wave` module; a file at another rate is resampled on the GPU
 (conan_resample, preset kaiser_best) where the reference's librosa.core.load(sr=...) resamples (with soxr_hq, a different filter:
-the samples are not librosa's bit for bit).  loud_norm / trim_long_sil (pyloudnorm / webrtcvad, both off in egs/conan_emformer.yaml)
-raise NotImplementedError."""
+the samples are not librosa's bit for bit).  loud_norm (pyloudnorm's BS.1770 meter, a gain to -22 LUFS, a division by the peak above 1)
+runs on the GPU too (conan_loud_norm).  trim_long_sil (webrtcvad, off in egs/conan_emformer.yaml) raises NotImplementedError."""
 import wave
 
 import numpy as np
@@ -57,14 +57,16 @@ def librosa_wav2spec(wav_path, fft_size=1024, hop_size=256, win_length=1024, win
                      eps=1e-6, sample_rate=22050, loud_norm=False, trim_long_sil=False, ctx=None):
     """Same contract as the reference for the keys the inference path reads: {'wav', 'mel' [T, num_mels], 'wav_orig'}
     ('linear' / 'mel_basis' are not produced).  `ctx`: a finalized conan_amd.runtime.Context (device + library)."""
-    if loud_norm or trim_long_sil:
-        raise NotImplementedError("loud_norm / trim_long_sil are off on the inference path (egs_bases/tts/dataset_params.yaml:15)")
+    if trim_long_sil:
+        raise NotImplementedError("trim_long_sil (webrtcvad silence trimming) is not available; it is off in egs/conan_emformer.yaml")
     if window != "hann":
         raise NotImplementedError("only the Hann window of the reference configuration")
     if ctx is None:
         raise ValueError("librosa_wav2spec needs ctx= (a finalized conan_amd.runtime.Context): the transform runs on the GPU")
     wav = load_wav_resampled(wav_path, sample_rate, ctx) if isinstance(wav_path, str) else np.asarray(wav_path, dtype=np.float32)
     wav_orig = np.copy(wav)
+    if loud_norm:       # utils/audio/__init__.py:58-63: after loading / resampling, before the STFT; 'wav_orig' stays untouched
+        wav = ctx.loud_norm(torch.from_numpy(wav), sample_rate, target=-22.0, peak_limit=True).cpu().numpy()
     mel = ctx.wav2mel(torch.from_numpy(wav), fft_size=fft_size, hop_size=hop_size, win_length=win_length, num_mels=num_mels,
                       fmin=fmin, fmax=fmax, sample_rate=sample_rate, eps=eps, mel_vmin=-1e30, mel_vmax=1e30)[0].cpu().numpy()
     l_pad, r_pad = librosa_pad_lr(wav, fft_size, hop_size, 1)

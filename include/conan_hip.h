@@ -303,7 +303,8 @@ int conan_streams_output_fence_event(conan_streams* s, void* event);
 int conan_streams_test_fault(conan_streams* s, int kind);
 
 /* Mel front-end (the step before the hot path): librosa_wav2spec as used by
- * StreamingVoiceConversion._wav_to_mel (utils/audio/__init__.py:37-84, inference/Conan.py:57-70), loud_norm off:
+ * StreamingVoiceConversion._wav_to_mel (utils/audio/__init__.py:37-84, inference/Conan.py:57-70) behind its loud_norm branch
+ * (conan_loud_norm below runs that branch; a caller with loud_norm on normalises the waveform first):
  * centred zero-padded STFT (periodic Hann) -> magnitude -> Slaney mel filterbank -> log10(max(eps, .)) -> clip.
  * wav_dev[n][samples] fp32 in [-1, 1]; mel_out_dev[n][frames][num_mels] with frames = 1 + samples / hop_size
  * (*frames_out, may be NULL).  fmin / fmax < 0 mean 0 / Nyquist.  Not re-entrant per context (shared workspace).
@@ -503,6 +504,46 @@ int conan_streams_set_output_format(conan_streams* s, const int32_t* slots, int 
  * that arrive as PCM.  An unknown format, a slot out of range or a null handle returns the usual status with nothing changed. */
 int conan_convert_samples(conan_ctx* ctx, int src_format, const void* src_dev, int64_t src_ld, int dst_format, void* dst_dev, int64_t dst_ld,
                           int n, int64_t samples, void* stream);
+
+/* Loudness normalisation of whole signals (added within ABI 9: a caller detects it by the exported symbol): the loud_norm branch
+ * of the reference's librosa_wav2spec (utils/audio/__init__.py:58-63) - pyloudnorm's BS.1770 meter, a gain to target_lufs, a
+ * division by the peak where that exceeds 1.  The arithmetic, which this comment defines (tests/loudness_ref.py restates it in
+ * numpy); all filter and energy arithmetic is f64, as scipy.signal.lfilter's on f32 data with f64 coefficients:
+ *   K-weighting.  Two biquads at the signal's own rate fs, each normalised by its a0, passband gain 1; for both
+ *     w0 = 2 pi fc / fs, alpha = sin(w0) / (2 Q).
+ *     High shelf, G = 4.0 dB, Q = 1 / sqrt(2), fc = 1500, A = 10^(G / 40):
+ *       b0 = A ((A+1) + (A-1) cos w0 + 2 sqrt(A) alpha)    a0 = (A+1) - (A-1) cos w0 + 2 sqrt(A) alpha
+ *       b1 = -2 A ((A-1) + (A+1) cos w0)                   a1 = 2 ((A-1) - (A+1) cos w0)
+ *       b2 = A ((A+1) + (A-1) cos w0 - 2 sqrt(A) alpha)    a2 = (A+1) - (A-1) cos w0 - 2 sqrt(A) alpha
+ *     High pass, Q = 0.5, fc = 38:  b = [(1 + cos w0) / 2, -(1 + cos w0), (1 + cos w0) / 2],  a = [1 + alpha, -2 cos w0, 1 - alpha].
+ *     Shelf first, then high pass, each in direct form II transposed from a zero state:
+ *       y = b0 x + z0;  z0 = b1 x - a1 y + z1;  z1 = b2 x - a2 y.
+ *   Gating blocks.  T_g = 0.4, step = 0.25, T = samples / fs, numBlocks = int(round((T - T_g) / (T_g * step)) + 1) (round half
+ *     to even); block j covers [int(T_g * (j * step) * fs), int(T_g * (j * step + 1) * fs)), truncated at the signal's end, all
+ *     evaluated in double in exactly this order on the host.  z_j = sum y^2 / (T_g * fs);  l_j = -0.691 + 10 log10(z_j).
+ *   Gating.  Absolute gate: l_j >= -70.  Gamma_r = -0.691 + 10 log10(mean z over those blocks) - 10.  Final set: l_j > Gamma_r and
+ *     l_j > -70.  L = -0.691 + 10 log10(mean z over the final set); an empty set gives L = -inf.
+ *   Normalise.  gain = 10^((target_lufs - L) / 20);  y = gain * x in double; with peak_limit, if p = gain * max|x| > 1 then
+ *     y = y / p; one rounding to f32 at the end.
+ * Library rules: a row whose L is -inf (silence, or nothing above the absolute gate) is copied unchanged with gain 1 - the
+ * reference's own output there is inf / NaN - and its stats say so (LUFS -inf, 0 blocks); a row shorter than T_g * fs samples is
+ * CONAN_ERR_INVALID before any launch (pyloudnorm raises there).
+ * Every sum has one order, fixed by the row's length and rate alone: a row's result is bit-identical from run to run and does not
+ * depend on the other rows of the call. */
+typedef struct conan_loudness_cfg {
+  int32_t sample_rate;   /* 8000 .. 192000 */
+  float   target_lufs;   /* the reference: -22 */
+  int32_t peak_limit;    /* 1: the reference's divide-by-peak above 1; 0: none */
+  int32_t reserved[3];   /* must be 0 */
+} conan_loudness_cfg;
+/* x_dev: n rows of f32, row i at i * x_ld floats, samples[i] (host) of them used (1 .. 2^30 each, n in 1 .. 65535; rows may have
+ * different lengths).  y_dev: rows at i * y_ld; only the first samples[i] floats of a row are written; NULL measures only; y_dev may
+ * equal x_dev (with y_ld == x_ld).  stats_dev[n][4] (device, may be NULL): the row's LUFS, the gain applied (after the peak
+ * division), the peak gain * max|x| before limiting, and the number of blocks in the final gated set.  Stream-ordered on `stream`;
+ * the call never waits for the device, except for the stream's earlier work when the workspace has to grow.  Every row is checked
+ * before anything is launched.  It uses the context's workspace, like conan_wav2mel: not re-entrant per context. */
+int conan_loud_norm(conan_ctx* ctx, const conan_loudness_cfg* cfg, const float* x_dev, int64_t x_ld, int n, const int64_t* samples,
+                    float* y_dev, int64_t y_ld, double* stats_dev, void* stream);
 
 /* Measurement hook (replaces the reference's Timer('hifigan') around the vocoder forward,
  * utils/commons/meters.py:21-42, tasks/tts/vocoder_infer/hifigan.py:28): between begin and end every
