@@ -124,6 +124,11 @@ _PROTOS = {
     "conan_hop_size": (C.c_int, [C.c_void_p]),
     "conan_ctx_weight_bytes": (C.c_int64, [C.c_void_p]),
     "conan_streams_state_bytes": (C.c_int64, [C.c_void_p]),
+    "conan_streams_layout_id": (C.c_uint64, [C.c_void_p]),
+    "conan_streams_snapshot_bytes": (C.c_int64, [C.c_void_p]),
+    "conan_streams_export_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "conan_streams_import_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "conan_slot_meta_info": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -217,6 +222,20 @@ def resample_cfg(orig_freq, new_freq=16000, lowpass_filter_width=6, rolloff=0.99
     window = RESAMPLE_HANN if resampling_method == "sinc_interp_hann" else RESAMPLE_KAISER
     return ResampleCfg(int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff), window,
                        float(beta) if beta is not None else 0.0, (C.c_int32 * 2)(0, 0))
+
+
+SLOT_META_BYTES = 256
+
+
+class SlotMeta(C.Structure):
+    """conan_slot_meta (include/conan_hip.h): the host half of a slot snapshot, opaque."""
+    _fields_ = [("opaque", C.c_ubyte * SLOT_META_BYTES)]
+
+
+class SlotInfo(C.Structure):
+    """conan_slot_info (include/conan_hip.h): what a caller may read out of a conan_slot_meta."""
+    _fields_ = [("layout_id", C.c_uint64), ("bytes", C.c_int64), ("has_ref", C.c_int32), ("in_format", C.c_int32),
+                ("out_format", C.c_int32), ("reserved", C.c_int32), ("in_rate", ResampleCfg), ("out_rate", ResampleCfg)]
 
 
 class LoudnessCfg(C.Structure):

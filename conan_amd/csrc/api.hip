@@ -788,4 +788,24 @@ int conan_hop_size(const conan_ctx* ctx) { return ctx ? ctx->hop : 0; }
 int64_t conan_ctx_weight_bytes(const conan_ctx* ctx) { return ctx ? ctx->weight_bytes : 0; }
 int64_t conan_streams_state_bytes(const conan_streams* s) { return s ? s->state_bytes : 0; }
 
+// ---- slot snapshots (snapshot.hip)
+uint64_t conan_streams_layout_id(const conan_streams* s) {
+  uint64_t id = 0;
+  guarded([&] { if (!s) throw Error(CONAN_ERR_INVALID, "null streams"); id = snapshot::layout_id(const_cast<conan_streams*>(s)); });
+  return id;
+}
+int64_t conan_streams_snapshot_bytes(const conan_streams* s) {
+  int64_t b = 0;
+  const int rc = guarded([&] { if (!s) throw Error(CONAN_ERR_INVALID, "null streams"); b = snapshot::row_bytes(const_cast<conan_streams*>(s)); });
+  return rc < 0 ? rc : b;
+}
+int conan_streams_export_slots(conan_streams* s, const int32_t* slots, int n, void* blob_dev, int64_t blob_ld_bytes, conan_slot_meta* meta_host, void* stream) {
+  return guarded([&] { snapshot::export_slots(s, slots, n, blob_dev, blob_ld_bytes, meta_host, stream); });
+}
+int conan_streams_import_slots(conan_streams* s, const int32_t* slots, int n, const void* blob_dev, int64_t blob_ld_bytes, const conan_slot_meta* meta_host,
+                               void* stream) {
+  return guarded([&] { snapshot::import_slots(s, slots, n, blob_dev, blob_ld_bytes, meta_host, stream); });
+}
+int conan_slot_meta_info(const conan_slot_meta* meta, conan_slot_info* out) { return guarded([&] { snapshot::meta_info(meta, out); }); }
+
 }  // extern "C"

@@ -50,6 +50,7 @@ struct PackedConv {
 struct Ring {
   float* base = nullptr;
   int L = 0, C = 0, rate = 1;
+  int hist = 0;             // rows before the step's first that a step may still read (slot snapshots save these)
   long long slot_stride = 0;
   cnk::TRef ref(int off = 0) const {
     cnk::TRef r; r.base = base; r.slot_stride = slot_stride; r.C = C; r.lmask = L - 1; r.rate = rate; r.off = off; r.mode = 0; r.pad_ = 0;

@@ -4,6 +4,7 @@
 #include <functional>
 
 #include "host_common.h"
+#include "snapshot_layout.h"
 
 using ch::Error;
 using ch::Lin;
@@ -217,6 +218,21 @@ struct conan_streams {
     int out_fmt_n = 0;
   } wav_out;
   void out_stage_init();
+  void out_ring_init();        // the output resampler's history ring (conan_streams_set_output_rate with a real rate)
+  // --- slot snapshots (snapshot.hip).  rings: every ring of mk_ring in creation order with its position counter (0 pos_emf,
+  // 1 pos_dec, 2 pos_voc).  The layout and its device tables are built by the first export / import and rebuilt when a rate ring is
+  // first allocated; per call a table of snap::CallRow (set q of snap_sets).  Not stream state (state_bytes).  in_cfg / out_cfg: the
+  // rate setters' configurations per slot (in_rate == out_rate: none), which travel with a snapshot.
+  struct Snap {
+    std::vector<std::pair<Ring, int>> rings;
+    snap::Layout layout;
+    bool lay_ok = false, built = false;      // the host layout is current; the device tables hold it
+    const float* lay_rs = nullptr; const float* lay_or = nullptr;      // the rate rings the layout was built with
+    snap::Region* d_regions = nullptr; int* d_item_first = nullptr;
+    StageSets<std::array<int, 4>> sets;
+    std::vector<conan_resample_cfg> in_cfg, out_cfg;
+  } snapshot;
+  void snapshot_build();
   // One vocoder step's output rows, checked before anything changes (out_plan) and handed to hifigan_step, which commits the slots'
   // counters once its launches are enqueued.  active: the step's audio goes through staging and resample_out_kernel.
   struct OutPlan {
@@ -272,11 +288,12 @@ struct conan_streams {
   }
   void* stage_alloc(size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, bytes)); allocs.push_back(p); return p; }   // per-call staging: not stream state
   Ring mk_ring(int C, int rate, int hist, std::vector<std::pair<float*, long long>>* reg) {
-    Ring r; r.C = C; r.rate = rate;
+    Ring r; r.C = C; r.rate = rate; r.hist = hist;
     r.L = ch::next_pow2(hist + max_frames * rate);
     r.slot_stride = (long long)r.L * C;
     r.base = alloc((size_t)max_slots * r.slot_stride);
     if (reg) reg->push_back({r.base, r.slot_stride});
+    if (reg) snapshot.rings.push_back({r, reg == &voc_state ? 2 : (reg == &dec_state ? 1 : 0)});
     return r;
   }
   Lin mk_lin(int rows, int C, int nb = -1) {
@@ -439,6 +456,8 @@ namespace wavio {
 int bytes_per_sample(int fmt);      // of a CONAN_SAMPLE_* / cnk::kFmt* code
 void check_format(int format, const char* who);
 void check_slot_list(const conan_streams* s, const int32_t* slots, int n);      // count, range, duplicates
+const ch::RsTable* rate_table(conan_streams* s, const conan_resample_cfg& c, const char* who);      // null at the model rate
+void store_format(std::vector<unsigned char>& fmt, int& not_f32, const int32_t* slots, int n, int format);
 void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, int n, const int32_t* in_samples, const int32_t* in_final, const float* wav_dev,
               long long wav_ld, const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream,
               bool pipelined, bool common);
@@ -454,3 +473,12 @@ int output_samples(conan_streams* s, int32_t* counts, int cap);      // -> rows 
 void output_pending(conan_streams* s, const int32_t* slots, int n, int32_t* counts);
 void flush_output(conan_streams* s, const int32_t* slots, int n, float* wav_out_dev, int64_t wav_ld, void* stream);
 }  // namespace wavio
+
+// ---- slot snapshots (snapshot.hip): the bodies of api.hip's export / import entry points
+namespace snapshot {
+uint64_t layout_id(conan_streams* s);
+int64_t row_bytes(conan_streams* s);
+void export_slots(conan_streams* s, const int32_t* slots, int n, void* blob_dev, int64_t blob_ld, conan_slot_meta* meta, void* stream);
+void import_slots(conan_streams* s, const int32_t* slots, int n, const void* blob_dev, int64_t blob_ld, const conan_slot_meta* meta, void* stream);
+void meta_info(const conan_slot_meta* meta, conan_slot_info* out);
+}  // namespace snapshot

@@ -19,7 +19,7 @@ static void fill_filter(Row& row, const ch::RsTable& t) {
 static bool ring_fits(const ch::RsTable& t, long long I, long long out, long long ring_len) { return I - (t.first(out) - 4) <= ring_len; }
 
 // The filter table of a rate setter's configuration; null at the model rate, where the configuration must still be a valid one.
-static const ch::RsTable* rate_table(conan_streams* s, const conan_resample_cfg& c, const char* who) {
+const ch::RsTable* rate_table(conan_streams* s, const conan_resample_cfg& c, const char* who) {
   if (c.in_rate != c.out_rate) return &s->ctx->resample_table(c);
   conan_resample_cfg probe = c;
   if (conan_resample_length(&probe, 0) < 0) throw Error(CONAN_ERR_INVALID, std::string(who) + ": invalid resampler configuration");
@@ -441,6 +441,8 @@ void set_input_rate(conan_streams* s, const int32_t* slots, int n, const conan_r
   HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
   s->resample_init();
   for (int i = 0; i < n; ++i) s->wav_in.rs_slot[slots[i]] = conan_streams::RsSlot{t, 0, 0, 0};
+  s->snapshot.in_cfg.resize(s->max_slots, conan_resample_cfg{});
+  for (int i = 0; i < n; ++i) s->snapshot.in_cfg[slots[i]] = c;      // (slot snapshots carry the slot's rate)
 }
 
 void set_output_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg) {
@@ -452,19 +454,15 @@ void set_output_rate(conan_streams* s, const int32_t* slots, int n, const conan_
   if (c.in_rate != model_rate)
     throw Error(CONAN_ERR_INVALID, "conan_streams_set_output_rate: in_rate must be the model rate (hop * 50 = " + std::to_string(model_rate) + " Hz)");
   HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  // the history holds model-rate audio: the longest span of an accepted filter (CONAN_RESAMPLE_MAX_TAPS) plus the largest step
-  const int ring_len = ch::next_pow2(CONAN_RESAMPLE_MAX_TAPS + 8 + s->max_frames * s->ctx->hop);
   const ch::RsTable* t = rate_table(s, c, "conan_streams_set_output_rate");
   for (int i = 0; i < n; ++i)
     if (s->wav_out.voc_samples[slots[i]] != 0)
       throw Error(CONAN_ERR_STATE, "conan_streams_set_output_rate: slot " + std::to_string(slots[i]) + " is not at the start of its vocoder stream (reset it with CONAN_MODEL_HIFIGAN first)");
   if (!t && s->wav_out.or_slot.empty()) return;      // the model-rate path of a stream-set that never had a rate: nothing to allocate
-  if (!s->wav_out.or_ring) {
-    s->wav_out.or_ring_len = ring_len;
-    s->wav_out.or_ring = s->alloc((size_t)s->max_slots * ring_len);        // stream state (state_bytes)
-    s->wav_out.or_slot.assign(s->max_slots, conan_streams::OrSlot());
-  }
+  s->out_ring_init();
   for (int i = 0; i < n; ++i) s->wav_out.or_slot[slots[i]] = conan_streams::OrSlot{t, 0, 0};
+  s->snapshot.out_cfg.resize(s->max_slots, conan_resample_cfg{});
+  for (int i = 0; i < n; ++i) s->snapshot.out_cfg[slots[i]] = c;
 }
 
 void set_output_ld(conan_streams* s, int64_t ld) {
@@ -473,7 +471,7 @@ void set_output_ld(conan_streams* s, int64_t ld) {
   s->wav_out.out_ld = ld;
 }
 
-static void store_format(std::vector<unsigned char>& fmt, int& not_f32, const int32_t* slots, int n, int format) {
+void store_format(std::vector<unsigned char>& fmt, int& not_f32, const int32_t* slots, int n, int format) {
   for (int i = 0; i < n; ++i) {
     not_f32 += (format != 0) - (fmt[slots[i]] != 0);
     fmt[slots[i]] = (unsigned char)format;
@@ -538,6 +536,14 @@ void flush_output(conan_streams* s, const int32_t* slots, int n, float* wav_out_
 void conan_streams::resample_init() {
   rs_stage_init();
   if (!wav_in.rs_ring) wav_in.rs_ring = alloc((size_t)max_slots * cnk::kRsRing);        // stream state (state_bytes)
+}
+
+void conan_streams::out_ring_init() {
+  if (wav_out.or_ring) return;
+  // the history holds model-rate audio: the longest span of an accepted filter (CONAN_RESAMPLE_MAX_TAPS) plus the largest step
+  wav_out.or_ring_len = ch::next_pow2(CONAN_RESAMPLE_MAX_TAPS + 8 + max_frames * ctx->hop);
+  wav_out.or_ring = alloc((size_t)max_slots * wav_out.or_ring_len);        // stream state (state_bytes)
+  wav_out.or_slot.assign(max_slots, OrSlot());
 }
 
 void conan_streams::rs_stage_init() {

@@ -263,10 +263,27 @@ class StreamingVoiceConversionEngine:
                 if self.ctx.cfg.voc_upsample == 2 and r is not None:
                     raise ValueError("out_rate with an upsample 'nn' vocoder: run Streams.hifigan_step over the mel prefix and Streams.flush_output instead")
                 st.set_output_rate(group, r or st.model_rate, **(out_filter or {}))
+        self._fit_output_ld()
+
+    def _fit_output_ld(self):
+        """The stream-set's output stride: wide enough for a full chunk of the fastest slot (0 without output rates)."""
+        st = self.st
         L = self.seg * self.ctx.hop
         ld = max([L] + [-(-L * r // st.model_rate) + 2 for r in st.output_rates.values()]) if st.output_rates else 0
         if ld != st.output_ld:
             st.set_output_ld(ld)
+
+    def export_streams(self, slots):
+        """The streams in `slots` as a runtime.SlotSnapshot (Streams.export_slots): park them, move them to another engine, rank or
+        process, or fork them.  The slots are left as they are."""
+        return self.st.export_slots(slots)
+
+    def import_streams(self, slots, snap):
+        """Continue the streams of `snap` in `slots` of this engine (Streams.import_slots): feed, feed_ragged and finish go on where
+        the exporting engine stopped.  Rates and formats travel with the streams; the output stride follows them."""
+        st = self.st
+        st.import_slots(slots, snap)
+        self._fit_output_ld()
 
     def finish(self, slots=None):
         """End of utterance on a stream-set with output rates: the slots' remaining output samples (Streams.flush_output), one 1-D

@@ -218,6 +218,53 @@ class Context:
             pass
 
 
+class SlotSnapshot:
+    """Exported streams (Streams.export_slots): `meta` - the host records, 256 bytes per stream - and `blob` - a uint8 tensor
+    [n, bytes], one row of device state per stream.  Position independent: it holds no pointers, slot numbers or ring indices, so it
+    may be moved to the host (cpu), to another device (to), pickled, and imported by another process into a stream-set of the same
+    layout_id."""
+
+    def __init__(self, meta, blob):
+        assert len(meta) == blob.shape[0] * _lib.SLOT_META_BYTES and blob.dtype == torch.uint8 and blob.dim() == 2
+        self.meta, self.blob = bytes(meta), blob
+
+    def __len__(self):
+        return self.blob.shape[0]
+
+    def info(self, i):
+        """conan_slot_meta_info of stream i: dict(layout_id, bytes, has_ref, in_format, out_format, in_rate, out_rate); a rate is
+        None for a stream without one."""
+        rec = _lib.SlotMeta.from_buffer_copy(self.meta[i * _lib.SLOT_META_BYTES:(i + 1) * _lib.SLOT_META_BYTES])
+        out = _lib.SlotInfo()
+        _lib.check(_lib.lib().conan_slot_meta_info(C.byref(rec), C.byref(out)))
+        names = {v: k for k, v in _lib.SAMPLE_FORMATS.items()}
+        return dict(layout_id=int(out.layout_id), bytes=int(out.bytes), has_ref=bool(out.has_ref), in_format=names[out.in_format],
+                    out_format=names[out.out_format],
+                    in_rate=out.in_rate.in_rate if out.in_rate.in_rate != out.in_rate.out_rate else None,
+                    out_rate=out.out_rate.out_rate if out.out_rate.in_rate != out.out_rate.out_rate else None,
+                    in_cfg=out.in_rate, out_cfg=out.out_rate)
+
+    def cpu(self):
+        return SlotSnapshot(self.meta, self.blob.cpu())
+
+    def to(self, device):
+        return SlotSnapshot(self.meta, self.blob.to(device))
+
+    def select(self, rows):
+        """The snapshot of the streams `rows` (indices into this one), in that order; a row may repeat (a fork)."""
+        rows = [int(r) for r in rows]
+        M = _lib.SLOT_META_BYTES
+        return SlotSnapshot(b"".join(self.meta[r * M:(r + 1) * M] for r in rows), self.blob[rows])
+
+    def __getstate__(self):
+        b = self.blob.cpu().contiguous()
+        return {"meta": self.meta, "shape": tuple(b.shape), "blob": b.numpy().tobytes()}
+
+    def __setstate__(self, state):
+        self.meta = state["meta"]
+        self.blob = torch.frombuffer(bytearray(state["blob"]), dtype=torch.uint8).reshape(state["shape"])
+
+
 class Streams:
     """conan_streams: per-slot streaming state + the step functions."""
 
@@ -248,6 +295,53 @@ class Streams:
     def arith(self):
         """'f32' or 'limb': the arithmetic this stream-set's vocoder launches use where both forms exist ('auto' resolved)."""
         return {_lib.ARITH_F32: "f32", _lib.ARITH_LIMB: "limb"}[_lib.check(self.lib.conan_streams_arith(self.h))]
+
+    @property
+    def snapshot_bytes(self):
+        """Bytes of one stream's blob row (conan_streams_snapshot_bytes): an upper bound over the slots, a multiple of 256."""
+        return _lib.check(self.lib.conan_streams_snapshot_bytes(self.h))
+
+    @property
+    def layout_id(self):
+        """conan_streams_layout_id: equal for stream-sets a snapshot can move between."""
+        return int(self.lib.conan_streams_layout_id(self.h))
+
+    def export_slots(self, slots, out=None):
+        """conan_streams_export_slots: the streams in `slots` -> SlotSnapshot (blob on this device; complete in stream order, the
+        host records at once).  Joins pipelined work; changes nothing in the slots.  out: a cuda uint8 [n, >= snapshot_bytes] buffer."""
+        a, p = _i32(slots)
+        n = len(a)
+        blob = out if out is not None else torch.empty(n, self.snapshot_bytes, dtype=torch.uint8, device=self.dev)
+        assert blob.is_cuda and blob.dtype == torch.uint8 and blob.dim() == 2 and blob.shape[0] == n and blob.stride(1) == 1
+        meta = (_lib.SlotMeta * n)()
+        _lib.check(self.lib.conan_streams_export_slots(self.h, p, n, _ptr(blob), blob.stride(0), meta, _stream()))
+        self._release()
+        return SlotSnapshot(bytes(meta), blob)
+
+    def import_slots(self, slots, snap):
+        """conan_streams_import_slots: slot slots[i] becomes stream i of `snap` (history, positions, style cache, rates and formats).
+        Every record is checked before anything changes.  The blob is moved to this device if it is elsewhere."""
+        a, p = _i32(slots)
+        n = len(a)
+        if len(snap) != n:
+            raise ValueError(f"import_slots: {n} slots for a snapshot of {len(snap)} streams")
+        blob = snap.blob.to(self.dev)
+        if blob.stride(1) != 1 or blob.stride(0) % 16 or blob.data_ptr() % 16:
+            blob = blob.contiguous()
+        meta = (_lib.SlotMeta * n).from_buffer_copy(snap.meta)
+        _lib.check(self.lib.conan_streams_import_slots(self.h, p, n, _ptr(blob), blob.stride(0), meta, _stream()))
+        blob.record_stream(torch.cuda.current_stream())
+        self._release()
+        for i, slot in enumerate(a):      # the Python-side mirrors of the slot configuration that travelled
+            info = snap.info(i)
+            self._note_format(self.input_formats, [slot], info["in_format"])
+            self._note_format(self.output_formats, [slot], info["out_format"])
+            if info["in_rate"] is not None:
+                self.input_rate_set = True
+            if info["out_rate"] is not None:
+                self.output_rates[int(slot)] = int(info["out_rate"])
+            else:
+                self.output_rates.pop(int(slot), None)
 
     def _release(self):
         """Buffers of pipelined steps may be dropped once the current torch stream waits for the library's internal

@@ -577,6 +577,61 @@ int conan_hop_size(const conan_ctx* ctx);             /* prod(upsample_rates) */
 int64_t conan_ctx_weight_bytes(const conan_ctx* ctx); /* packed device weight bytes */
 int64_t conan_streams_state_bytes(const conan_streams* s);
 
+/* Slot snapshots (added within ABI 9: a caller detects it by the exported symbols).  A stream - everything slot i of a stream-set
+ * holds about its utterance - can be exported to a blob row in device memory plus a 256-byte host record, and imported into any slot
+ * of a stream-set of the same shape: on another GPU, in another process, later, or into several slots at once (a fork).
+ *
+ * What travels.  Device state in the blob row: the position counters, every activation ring of the vocoder and the decoder saved as
+ * its HISTORY (the rows a future step can still read: row (pos * rate - H + j) & lmask for j = 0 .. H-1, oldest first, H = the left
+ * context the ring was sized for; ring sizing L = next_pow2(H + max_frames * rate) is the guarantee that no step reads further back),
+ * the Emformer key / value rings and memory bank whole, the style cache (style vector, cross-attention keys / values and mask, token
+ * count, prosody ids), and - last, only for slots that use them - the streaming front-end's rings, the input resampler's ring and
+ * the output resampler's history.  Host state in the meta record: has_ref, whether the vocoder is freshly reset, the vocoder's
+ * sample count, the front-end's and both resamplers' counters and phases, and the slot's configuration that belongs to the stream:
+ * both rates with their filters and both sample formats.  The output stride (conan_streams_set_output_ld) is a property of the
+ * stream-set and stays behind.  A row holds no pointers, slot numbers or ring indices; it may be copied to the host, to a file or to
+ * another device.
+ *
+ * Layout id.  A 64-bit hash over what decides a slot's state: the conan_cfg fields that size it, the resolved arithmetic, S_max
+ * (from max_ref_frames) and the ordered list of state regions with their row width, rate and saved rows.  Ring lengths, and with
+ * them max_frames, are not part of it; nor are devices or addresses: stream-sets created with equal arguments on contexts of equal
+ * configuration have equal ids in any process.  NOTE: the SET of rings depends on max_slots - the vocoder plan changes at 4, 8 and
+ * 16 slots (build_vocoder: fused stages keep no xt / activated twins, the pair stage adds its own history rings) - and on the
+ * arithmetic (f32 / limb).  A snapshot therefore moves between stream-sets of the same shape (same context configuration, same
+ * arith, same max_ref_frames, max_slots on the same side of those thresholds), not between arbitrary ones; anything else is
+ * CONAN_ERR_INVALID naming both ids.
+ *
+ * conan_streams_snapshot_bytes: bytes of a blob row, an upper bound over all slots (a slot without rates or wav-in uses less:
+ * conan_slot_info.bytes), a multiple of 256.
+ * conan_streams_export_slots: row i of blob_dev (device memory, 16-byte aligned, rows blob_ld_bytes apart, a multiple of 16 and at
+ * least the slot's used bytes) receives slots[i]'s device state, meta_host[i] its host state, complete when the call returns.  Joins
+ * pending pipelined work, then runs as ONE launch on `stream`; it never waits for the device (except that the first export or import
+ * of a stream-set builds its region table with one blocking copy) and changes nothing in the source.  Deterministic: padding inside
+ * the used part is written as zero, bytes past conan_slot_info.bytes are not touched.
+ * conan_streams_import_slots: makes slots[i] of `s` the stream of row i / meta_host[i].  Allocates the rate rings exactly as
+ * conan_streams_set_input_rate / _output_rate would (conan_streams_state_bytes grows as documented there).  Every slot and every
+ * record is checked before anything changes - record magic, version, size and checksum, layout id, bytes <= blob_ld_bytes, slot
+ * range, duplicate slots - and on error no slot changes.  One launch on `stream` behind a join.  Rows of the destination rings
+ * outside the history keep what they held: no step reads them.  With voc_upsample 'nn', whose steps rely on untouched ring rows
+ * being zero, a snapshot of a fresh vocoder slot is restored by the reset's zeroing of the vocoder section first; one of a stepped
+ * slot imports, and the next vocoder step refuses as it does today.
+ * conan_slot_meta_info: host only, no handle: what a caller may read out of a record; CONAN_ERR_INVALID for a record that is not
+ * one (zeroed, wrong version, corrupted). */
+#define CONAN_SLOT_META_BYTES 256
+typedef struct conan_slot_meta { unsigned char opaque[CONAN_SLOT_META_BYTES]; } conan_slot_meta;
+typedef struct conan_slot_info {           /* what a caller may read out of a meta record */
+  uint64_t layout_id; int64_t bytes;       /* bytes of the slot's blob row that are used */
+  int32_t has_ref, in_format, out_format, reserved;
+  conan_resample_cfg in_rate, out_rate;    /* in_rate == out_rate: none set */
+} conan_slot_info;
+uint64_t conan_streams_layout_id(const conan_streams* s);
+int64_t  conan_streams_snapshot_bytes(const conan_streams* s);      /* per slot, upper bound, multiple of 256 */
+int conan_streams_export_slots(conan_streams* s, const int32_t* slots, int n, void* blob_dev, int64_t blob_ld_bytes,
+                               conan_slot_meta* meta_host, void* stream);
+int conan_streams_import_slots(conan_streams* s, const int32_t* slots, int n, const void* blob_dev, int64_t blob_ld_bytes,
+                               const conan_slot_meta* meta_host, void* stream);
+int conan_slot_meta_info(const conan_slot_meta* meta, conan_slot_info* out);   /* host only, no handle */
+
 #ifdef __cplusplus
 }
 #endif
