@@ -101,6 +101,9 @@ _PROTOS = {
     "conan_resample_length": (C.c_int64, [C.c_void_p, C.c_int64]),
     "conan_resample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_loud_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "conan_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "conan_streams_set_input_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "conan_streams_input_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "conan_streams_set_input_rate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "conan_streams_set_output_rate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "conan_streams_set_output_ld": (C.c_int, [C.c_void_p, C.c_int64]),
@@ -129,6 +132,7 @@ _PROTOS = {
     "conan_streams_export_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "conan_streams_import_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "conan_slot_meta_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "conan_slot_meta_level": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -241,6 +245,30 @@ class SlotInfo(C.Structure):
 class LoudnessCfg(C.Structure):
     """conan_loudness_cfg (include/conan_hip.h)."""
     _fields_ = [("sample_rate", C.c_int32), ("target_lufs", C.c_float), ("peak_limit", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+LEVEL_MAX_BLOCKS = 4096
+
+
+class LevelCfg(C.Structure):
+    """conan_level_cfg (include/conan_hip.h)."""
+    _fields_ = [("enabled", C.c_int32), ("target_lufs", C.c_float), ("max_boost_db", C.c_float), ("max_cut_db", C.c_float),
+                ("initial_gain_db", C.c_float), ("window_blocks", C.c_int32), ("peak_limit", C.c_int32), ("clip", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+def level_cfg(target=-22.0, max_boost_db=20.0, max_cut_db=40.0, initial_gain_db=0.0, window_blocks=LEVEL_MAX_BLOCKS, peak_limit=True,
+              clip=False):
+    """An enabled conan_level_cfg.  The defaults are a choice, not a measurement: the reference's loud_norm target, a boost cap that
+    keeps a silent line's noise floor down, a window that is the whole call for anything under 6.8 minutes."""
+    return LevelCfg(1, float(target), float(max_boost_db), float(max_cut_db), float(initial_gain_db), int(window_blocks),
+                    int(bool(peak_limit)), int(bool(clip)), (C.c_int32 * 4)(0, 0, 0, 0))
+
+
+def level_keywords(c):
+    """level_cfg's keywords of an enabled LevelCfg: the one form Streams.input_levels and SlotSnapshot.info report a leveller in."""
+    return dict(target=c.target_lufs, max_boost_db=c.max_boost_db, max_cut_db=c.max_cut_db, initial_gain_db=c.initial_gain_db,
+                window_blocks=c.window_blocks, peak_limit=bool(c.peak_limit), clip=bool(c.clip))
 
 
 class DecoderTaps(C.Structure):

@@ -594,6 +594,25 @@ int conan_loud_norm(conan_ctx* ctx, const conan_loudness_cfg* cfg, const float* 
   });
 }
 
+int conan_level(conan_ctx* ctx, const conan_level_cfg* cfg, const float* x_dev, int64_t x_ld, int n, const int64_t* samples, float* y_dev, int64_t y_ld,
+                double* trace_dev, int64_t trace_ld, void* stream) {
+  return guarded([&] {
+    if (!ctx || !cfg || !x_dev || !samples || !y_dev) throw Error(CONAN_ERR_INVALID, "null argument");
+    level::check_cfg(*cfg, "conan_level");      // (before any GPU use)
+    if (!cfg->enabled) throw Error(CONAN_ERR_INVALID, "conan_level: cfg.enabled must be 1");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    conan_ctx_level(ctx, *cfg, x_dev, x_ld, n, samples, y_dev, y_ld, trace_dev, trace_ld, (hipStream_t)stream);
+  });
+}
+
+int conan_streams_set_input_level(conan_streams* s, const int32_t* slots, int n, const conan_level_cfg* cfg) {
+  return guarded([&] { wavio::set_input_level(s, slots, n, cfg); });
+}
+
+int conan_streams_input_level(conan_streams* s, const int32_t* slots, int n, double* stats_dev, void* stream) {
+  return guarded([&] { wavio::input_level(s, slots, n, stats_dev, stream); });
+}
+
 int conan_streams_set_input_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg) {
   return guarded([&] { wavio::set_input_rate(s, slots, n, cfg); });
 }
@@ -807,5 +826,11 @@ int conan_streams_import_slots(conan_streams* s, const int32_t* slots, int n, co
   return guarded([&] { snapshot::import_slots(s, slots, n, blob_dev, blob_ld_bytes, meta_host, stream); });
 }
 int conan_slot_meta_info(const conan_slot_meta* meta, conan_slot_info* out) { return guarded([&] { snapshot::meta_info(meta, out); }); }
+
+int conan_slot_meta_level(const conan_slot_meta* meta, conan_level_cfg* out) {
+  int has = 0;
+  const int rc = guarded([&] { has = snapshot::meta_level(meta, out); });
+  return rc < 0 ? rc : has;
+}
 
 }  // extern "C"

@@ -182,6 +182,17 @@ struct conan_ctx {
 
 // conan_resample's body (resample.hip)
 void conan_ctx_resample(conan_ctx* ctx, const conan_resample_cfg& c, const float* x, int n, int64_t samples, float* y, int64_t* out_samples, hipStream_t st);
+// the K-weighting biquads at rate fs and the transition matrix M[16] of kLdSeg zero inputs (loudness.hip; shared with level.hip)
+void conan_k_weighting(double fs, cnk::LdBiquad& shelf, cnk::LdBiquad& hp, double* M);
+// conan_level's body, and the leveller's host arithmetic that wavio.hip shares (level.hip)
+void conan_ctx_level(conan_ctx* ctx, const conan_level_cfg& c, const float* x, int64_t x_ld, int n, const int64_t* samples, float* y, int64_t y_ld,
+                     double* trace, int64_t trace_ld, hipStream_t st);
+namespace level {
+void check_cfg(const conan_level_cfg& c, const char* who);
+cnk::LvCfg kernel_cfg(const conan_level_cfg& c);
+cnk::LvFilter filter(const conan_ctx* ctx, const char* who);
+cnk::LvCall plan_call(long long pos0, int m, int U, double fs);
+}  // namespace level
 // conan_loud_norm's body (loudness.hip)
 void conan_ctx_loud_norm(conan_ctx* ctx, const conan_loudness_cfg& c, const float* x, int64_t x_ld, int n, const int64_t* samples, float* y,
                          int64_t y_ld, double* stats, hipStream_t st);

@@ -655,6 +655,71 @@ __host__ __device__ inline double ld_step(const LdBiquad& f, const LdBiquad& g, 
   return y;
 }
 
+// ---- streaming leveller (level.hip): the causal BS.1770 leveller of include/conan_hip.h (conan_level_cfg).  A slot's stream is cut
+// into the meter's kLdSeg-sample segments, aligned to position 0.  A chunk (the samples of one wav-in call, or one update interval
+// of a whole signal; at most U = segment * hop samples) is appended to the slot's pending tail; the complete segments run one lane
+// each - state pass from a zero state, scan from the slot's carried state, energy pass into per-segment bin partials - and are
+// added, in ascending segment order, to the accumulators of the gating blocks they overlap; a block whose end the segments reached
+// goes to the slot's ring of block energies.  At an update instant the window is gated by the whole workgroup and the new gain
+// formed; then the ramps are applied.  One workgroup per row; lv_chunk (level.hip) is the one routine both kernels call.
+constexpr int kLvThreads = 256;
+constexpr int kLvBlocks = 8;                     // gating blocks that can overlap a chunk's complete segments (the host checks)
+constexpr int kLvSegs = 16;                      // LDS segments of a chunk: pending tail + U samples, U <= kLvMaxU
+constexpr int kLvMaxU = (kLvSegs - 1) * kLdSeg;  // 1920
+constexpr int kLvRingPad = 16;                   // blocks a ring holds beyond the window (blocks closed after the instant's J_k)
+struct LvState {                                 // per slot / row, followed by z[zcap] and l[zcap] (doubles)
+  double carry[4];                               // filter state at the start of the first incomplete segment
+  double acc[kLvBlocks];                         // energies of the open blocks, block j at j % kLvBlocks
+  double Gm, Gc, peak;                           // G_{k-1}, G_k of the latest instant k; max |x| of every sample so far
+  double stat[4];                                // {L_k, G_k, P_k, J_k} of the latest instant
+  float tail[kLdSeg];                            // pending raw samples: the first (position % kLdSeg) entries
+  double pad_;                                   // (a multiple of 16 bytes: slot snapshots move the block in 16-byte cells)
+};
+static_assert(sizeof(LvState) == 20 * 8 + kLdSeg * 4 && sizeof(LvState) % 16 == 0, "LvState is sized in include/conan_hip.h");
+constexpr size_t lv_state_bytes(int zcap) { return sizeof(LvState) + (size_t)zcap * 16; }
+struct LvCfg {                                   // conan_level_cfg in the kernels' terms
+  double target, boost, cut, g_init;
+  int window, peak_limit, clip, pad_;
+};
+struct LvCall {                                  // one chunk
+  long long pos0;                                // stream position of the chunk's first sample
+  int m;                                         // samples (1 .. U)
+  int inst;                                      // 1: an update instant lies in [pos0, pos0 + m) (at most one: m <= U)
+  int u, J;                                      // ... at pos0 + u, with J_k complete blocks
+  int j0, nblk;                                  // the blocks that overlap the chunk's complete segments: j0 .. j0 + nblk - 1
+  int lo[kLvBlocks], hi[kLvBlocks];              // their edges relative to the first segment's start, pos0 - pos0 % kLdSeg
+};
+struct LvRow {                                   // one call row of level_stream_kernel (uploaded through PinRing)
+  LvCall c;
+  LvCfg cfg;
+  int slot, row, fresh, copy;                    // row: the call row whose samples these are; fresh: conan_streams_input_level before any sample;
+                                                 // copy: an unlevelled row of a call whose staging the kernel writes - c.m samples, x -> y as they are
+};
+static_assert(sizeof(LvRow) % sizeof(int) == 0 && sizeof(LvCall) == 24 * sizeof(int), "LvRow is uploaded as ints");
+struct LvFilter { LdBiquad shelf, hp; double M[16]; double block_len; int U; };
+struct LevelStreamArgs {
+  const float* x; long long x_ld;                // the call's model-rate rows
+  float* y; long long y_ld;                      // the rows the front-end reads (may be x)
+  char* state; long long state_stride; int zcap; // [max_slots] LvState + rings
+  const LvRow* rows; int n;                      // the levelled rows with samples (and, where x is not y, the call's other rows as copy rows)
+  LvFilter f;
+};
+void launch_level_stream(const LevelStreamArgs& a, hipStream_t st);
+struct LevelStatsArgs { const char* state; long long state_stride; const LvRow* rows; int n; double* out; };
+void launch_level_stats(const LevelStatsArgs& a, hipStream_t st);
+struct LvSigRow { long long samples, blk0; int nblocks, pad_; };      // blk0: the row's first entry of the block table
+struct LevelSignalArgs {
+  const float* x; long long x_ld;
+  float* y; long long y_ld;
+  char* state; long long state_stride; int zcap; // [n] scratch states
+  const LvSigRow* rows; int n;
+  const int* blocks;                             // per row and block: lo, hi (every block that starts inside the row)
+  double* trace; long long trace_ld;             // [n][trace_ld][2] or null
+  LvCfg cfg;
+  LvFilter f;
+};
+void launch_level_signal(const LevelSignalArgs& a, hipStream_t st);
+
 // ---- style pass (per utterance) helpers
 struct RowMaskArgs { TRef x; TRef m; const int* lens; int T, n, C; int mode; };  // mode 0: sum|x|>0, 1: x[0]!=0
 void launch_rowmask(const RowMaskArgs& a, hipStream_t st);

@@ -204,8 +204,12 @@ namespace {
 constexpr double kPi = 3.14159265358979323846;
 constexpr double kTg = 0.4, kStep = 0.25;            // gating block length (s) and its step as a fraction of the block
 
-// The two K-weighting biquads at rate fs, normalised by a0 (include/conan_hip.h).
-void k_weighting(double fs, cnk::LdBiquad& shelf, cnk::LdBiquad& hp) {
+size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
+
+}  // namespace
+
+// The two K-weighting biquads at rate fs, normalised by a0 (include/conan_hip.h), and M, the transition matrix of one segment.
+void conan_k_weighting(double fs, cnk::LdBiquad& shelf, cnk::LdBiquad& hp, double* M) {
   {
     const double G = 4.0, Q = 1.0 / std::sqrt(2.0), fc = 1500.0;
     const double A = std::pow(10.0, G / 40.0), w0 = 2.0 * kPi * (fc / fs), alpha = std::sin(w0) / (2.0 * Q), c = std::cos(w0), r = 2.0 * std::sqrt(A) * alpha;
@@ -219,11 +223,13 @@ void k_weighting(double fs, cnk::LdBiquad& shelf, cnk::LdBiquad& hp) {
     const double b0 = (1 + c) / 2, b1 = -(1 + c), b2 = (1 + c) / 2, a0 = 1 + alpha, a1 = -2 * c, a2 = 1 - alpha;
     hp = {b0 / a0, b1 / a0, b2 / a0, a1 / a0, a2 / a0};
   }
+  for (int col = 0; col < 4; ++col) {                 // M's columns: kLdSeg zero inputs from each unit state
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    s[col] = 1.0;
+    for (int t = 0; t < cnk::kLdSeg; ++t) (void)cnk::ld_step(shelf, hp, s, 0.0);
+    for (int r = 0; r < 4; ++r) M[4 * r + col] = s[r];
+  }
 }
-
-size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
-
-}  // namespace
 
 void conan_ctx_loud_norm(conan_ctx* ctx, const conan_loudness_cfg& c, const float* x, int64_t x_ld, int n, const int64_t* samples, float* y,
                          int64_t y_ld, double* stats, hipStream_t st) {
@@ -292,13 +298,7 @@ void conan_ctx_loud_norm(conan_ctx* ctx, const conan_loudness_cfg& c, const floa
   a.z = reinterpret_cast<double*>(ws + o_z); a.l = reinterpret_cast<double*>(ws + o_l); a.gain = reinterpret_cast<double*>(ws + o_gain);
   a.peak = reinterpret_cast<float*>(ws + o_peak);
   a.stats = stats;
-  k_weighting(fs, a.shelf, a.hp);
-  for (int col = 0; col < 4; ++col) {                 // M's columns: kLdSeg zero inputs from each unit state
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    s[col] = 1.0;
-    for (int t = 0; t < cnk::kLdSeg; ++t) (void)cnk::ld_step(a.shelf, a.hp, s, 0.0);
-    for (int r = 0; r < 4; ++r) a.M[4 * r + col] = s[r];
-  }
+  conan_k_weighting(fs, a.shelf, a.hp, a.M);
   a.block_len = kTg * fs;
   a.target = (double)c.target_lufs; a.peak_limit = c.peak_limit;
   a.tiles = (int)((longest + cnk::kLdTile - 1) / cnk::kLdTile);

@@ -42,7 +42,8 @@ struct Meta {
   int32_t or_flushed, has_rs;
   conan_resample_cfg in_cfg, out_cfg;
   uint64_t checksum;                 // FNV-1a over the record with this field zero
-  unsigned char pad[CONAN_SLOT_META_BYTES - 184];
+  conan_level_cfg lv;                // the input leveller (all zero: none - every record written before it existed)
+  unsigned char pad[CONAN_SLOT_META_BYTES - 184 - sizeof(conan_level_cfg)];
 };
 static_assert(sizeof(Meta) == CONAN_SLOT_META_BYTES && sizeof(conan_slot_meta) == CONAN_SLOT_META_BYTES, "the meta record is 256 bytes");
 
@@ -98,14 +99,11 @@ int present_of(const conan_streams* s, int slot) {
   }
   if (!s->wav_in.rs_slot.empty() && s->wav_in.rs_slot[slot].f) p |= (1 << snap::SEC_RS_IN) | (1 << snap::SEC_FE);
   if (!s->wav_out.or_slot.empty() && s->wav_out.or_slot[slot].f) p |= 1 << snap::SEC_RS_OUT;
+  if (s->wav_in.levelled(slot)) p |= 1 << snap::SEC_LEVEL;
   return p;
 }
 
-long long used_bytes(const snap::Layout& l, int present) {
-  long long u = l.sec_end[snap::SEC_CORE];
-  for (int sec = 1; sec < snap::SEC_COUNT; ++sec) if ((present >> sec) & 1) u = l.sec_end[sec];
-  return u;
-}
+using snap::used_bytes;
 
 void check_blob(const void* blob, int64_t ld, const char* who) {
   if (reinterpret_cast<uintptr_t>(blob) % snap::kCell || ld % snap::kCell || ld < 0)
@@ -118,7 +116,7 @@ void check_blob(const void* blob, int64_t ld, const char* who) {
 // its id) whether or not this stream-set has allocated them yet.
 void conan_streams::snapshot_build() {
   Snap& sn = snapshot;
-  if (sn.lay_ok && sn.lay_rs == wav_in.rs_ring && sn.lay_or == wav_out.or_ring) return;
+  if (sn.lay_ok && sn.lay_rs == wav_in.rs_ring && sn.lay_or == wav_out.or_ring && sn.lay_lv == wav_in.lv_state) return;
   snap::Layout l;
   const conan_cfg& c = ctx->cfg;
   int* pos_arr[3] = {pos_emf, pos_dec, pos_voc};
@@ -148,12 +146,16 @@ void conan_streams::snapshot_build() {
     const int ring_len = wav_out.or_ring ? wav_out.or_ring_len : ch::next_pow2(CONAN_RESAMPLE_MAX_TAPS + 8 + max_frames * ctx->hop);
     snap::add_ring(l, wav_out.or_ring, (long long)ring_len * 4, 1, ring_len, 1, CONAN_RESAMPLE_MAX_TAPS + 8, nullptr, -1, snap::SEC_RS_OUT);
   }
+  if (wav_in.fe_audio) {      // the leveller's block (not part of the id: snapshot_layout.h)
+    const long long lv_bytes = (long long)cnk::lv_state_bytes(CONAN_LEVEL_MAX_BLOCKS + cnk::kLvRingPad);
+    snap::add_whole(l, wav_in.lv_state, lv_bytes, (int)lv_bytes, snap::SEC_LEVEL);
+  }
   for (int sec = 1; sec < snap::SEC_COUNT; ++sec) if (l.sec_end[sec] == 0) l.sec_end[sec] = l.sec_end[sec - 1];
   const int32_t words[] = {(int32_t)kVersion, c.models, c.hidden_size, c.num_mels, c.emf_input_dim, c.emf_layers, c.emf_segment, c.emf_left_context,
                            c.emf_right_context, c.emf_max_memory_size, c.voc_upsample, c.voc_resblock, ctx->hop, rb_limb ? 2 : 1, S_max};
   snap::finish(l, words, (int)(sizeof(words) / sizeof(words[0])));
   sn.layout = std::move(l);
-  sn.lay_ok = true; sn.lay_rs = wav_in.rs_ring; sn.lay_or = wav_out.or_ring;
+  sn.lay_ok = true; sn.lay_rs = wav_in.rs_ring; sn.lay_or = wav_out.or_ring; sn.lay_lv = wav_in.lv_state;
   sn.built = false;      // (the device tables follow on the next export / import)
 }
 
@@ -201,6 +203,7 @@ void export_slots(conan_streams* s, const int32_t* slots, int n, void* blob_dev,
       m.or_out = o.out; m.or_flushed = o.flushed;
       if (o.f) m.out_cfg = s->snapshot.out_cfg[slot];
     }
+    if (s->wav_in.levelled(slot)) m.lv = s->wav_in.lv_cfg[slot];
     m.checksum = meta_sum(m);
     memcpy(&meta[i], &m, sizeof(m));
   }
@@ -215,7 +218,8 @@ void import_slots(conan_streams* s, const int32_t* slots, int n, const void* blo
   const uint64_t id = s->snapshot.layout.id;
   std::vector<Meta> ms(n);
   std::vector<const ch::RsTable*> tin(n, nullptr), tout(n, nullptr);
-  bool need_rs_stage = false, need_rs = false, need_or = false;
+  bool need_rs_stage = false, need_rs = false, need_or = false, need_lv = false;
+  cnk::LvFilter lvf;
   for (int i = 0; i < n; ++i) {
     const std::string where = std::string(who) + ": record " + std::to_string(i) + ": ";
     Meta& m = ms[i];
@@ -231,6 +235,12 @@ void import_slots(conan_streams* s, const int32_t* slots, int n, const void* blo
     if (has_rate(m.out_cfg)) { tout[i] = wavio::rate_table(s, m.out_cfg, who); need_or = true; }
     if (((present >> snap::SEC_RS_IN) & 1) != (tin[i] != nullptr) || ((present >> snap::SEC_RS_OUT) & 1) != (tout[i] != nullptr)) throw Error(CONAN_ERR_INVALID, where + "inconsistent sections");
     need_rs_stage = need_rs_stage || m.in_fmt != CONAN_SAMPLE_F32 || m.has_rs;
+    level::check_cfg(m.lv, who);
+    if (((present >> snap::SEC_LEVEL) & 1) != (m.lv.enabled != 0)) throw Error(CONAN_ERR_INVALID, where + "inconsistent sections");
+    if (m.lv.enabled) {
+      if (!s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, where + "the stream carries an input leveller and this stream-set has no streaming front-end");
+      lvf = level::filter(s->ctx, who); need_lv = true;
+    }
   }
   HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
   hipStream_t st = (hipStream_t)stream;
@@ -238,6 +248,7 @@ void import_slots(conan_streams* s, const int32_t* slots, int n, const void* blo
   // the rate rings, exactly as the setters allocate them
   if (need_rs) s->resample_init(); else if (need_rs_stage && s->wav_in.fe_audio) s->rs_stage_init();
   if (need_or) s->out_ring_init();
+  if (need_lv) s->level_init(lvf);      // (the leveller's state, exactly as conan_streams_set_input_level allocates it)
   s->snapshot_build();
   std::vector<snap::CallRow> rows(n);
   std::vector<int32_t> fresh_nn;
@@ -265,6 +276,10 @@ void import_slots(conan_streams* s, const int32_t* slots, int n, const void* blo
       s->snapshot.in_cfg.resize(s->max_slots, conan_resample_cfg{});
       s->snapshot.in_cfg[slot] = m.in_cfg;
     }
+    if (!s->wav_in.lv_cfg.empty()) {      // (a record without a leveller turns the slot's off)
+      s->wav_in.lv_n += (m.lv.enabled != 0) - (s->wav_in.lv_cfg[slot].enabled != 0);
+      s->wav_in.lv_cfg[slot] = m.lv;
+    }
     if (!s->wav_out.or_slot.empty()) {
       s->wav_out.or_slot[slot] = conan_streams::OrSlot{tout[i], m.or_out, m.or_flushed};
       s->snapshot.out_cfg.resize(s->max_slots, conan_resample_cfg{});
@@ -279,6 +294,13 @@ void meta_info(const conan_slot_meta* meta, conan_slot_info* out) {
   memset(out, 0, sizeof(*out));
   out->layout_id = m.layout_id; out->bytes = m.bytes; out->has_ref = m.has_ref; out->in_format = m.in_fmt; out->out_format = m.out_fmt;
   out->in_rate = m.in_cfg; out->out_rate = m.out_cfg;
+}
+
+int meta_level(const conan_slot_meta* meta, conan_level_cfg* out) {
+  if (!meta || !out) throw Error(CONAN_ERR_INVALID, "null argument");
+  const Meta m = read_meta(meta, "conan_slot_meta_level: ");
+  *out = m.lv;
+  return m.lv.enabled != 0;
 }
 
 }  // namespace snapshot

@@ -23,8 +23,10 @@ constexpr int kItemBytes = 8192;      // a work item: 256 lanes x 2 cells
 constexpr int kRowAlign = 256;        // snapshot_bytes is a multiple of this
 
 enum Kind : int { KIND_RING = 0, KIND_WHOLE = 1 };
-// sections of the row, in this order; the core is always present, the others only for slots that use them
-enum Section : int { SEC_CORE = 0, SEC_FE = 1, SEC_RS_IN = 2, SEC_RS_OUT = 3, SEC_COUNT = 4 };
+// sections of the row, in this order; the core is always present, the others only for slots that use them.  SEC_LEVEL (the input
+// leveller's state, one whole block) came later: its regions are not part of the layout id, so the ids of stream-sets - and the
+// blobs written before it existed, which simply end before it - stay what they were.
+enum Section : int { SEC_CORE = 0, SEC_FE = 1, SEC_RS_IN = 2, SEC_RS_OUT = 3, SEC_LEVEL = 4, SEC_COUNT = 5 };
 
 struct Region {
   char* base;               // slot 0's block on the device (null: not allocated - only in sections no slot can have yet)
@@ -103,7 +105,7 @@ struct Layout {
   std::vector<Region> regions;
   std::vector<int> item_first;          // per work item of kItemBytes: the region that holds its first cell
   long long bytes = 0;                  // per slot, all sections, a multiple of kRowAlign (after finish)
-  long long sec_end[SEC_COUNT] = {0, 0, 0, 0};      // end of each section's last region
+  long long sec_end[SEC_COUNT] = {};      // end of each section's last region
   uint64_t id = 0;
   int items(long long used_bytes) const { return (int)((used_bytes + kItemBytes - 1) / kItemBytes); }
 };
@@ -144,7 +146,7 @@ inline int add_whole(Layout& l, void* base, long long slot_stride_bytes, int byt
 
 // Closes the layout: the work items' prefix table, the row size and the id - a hash over `cfg` (the caller's words: the configuration
 // fields that size state, the arithmetic, S_max) and the ordered regions' kind, section, row width, rate and saved rows / bytes.
-// Addresses, strides and ring lengths are not part of it.
+// Addresses, strides, ring lengths and the regions of SEC_LEVEL are not part of it.
 inline void finish(Layout& l, const int32_t* cfg, int ncfg) {
   l.bytes = (l.bytes + kRowAlign - 1) / kRowAlign * kRowAlign;
   l.item_first.clear();
@@ -155,10 +157,18 @@ inline void finish(Layout& l, const int32_t* cfg, int ncfg) {
   }
   uint64_t h = fnv1a(kFnvSeed, cfg, sizeof(int32_t) * (size_t)ncfg);
   for (const Region& r : l.regions) {
+    if (r.section == SEC_LEVEL) continue;
     const int32_t w[6] = {r.kind, r.section, r.row_bytes, r.rate, r.rows, r.bytes};
     h = fnv1a(h, w, sizeof(w));
   }
   l.id = h;
+}
+
+// bytes of a row that carries the sections of `present` (bit per section; the core always): up to the end of its last section
+inline long long used_bytes(const Layout& l, int present) {
+  long long u = l.sec_end[SEC_CORE];
+  for (int sec = 1; sec < SEC_COUNT; ++sec) if ((present >> sec) & 1) u = l.sec_end[sec];
+  return u;
 }
 
 }  // namespace snap

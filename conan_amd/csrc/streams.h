@@ -194,7 +194,18 @@ struct conan_streams {
     // launch is today's).
     std::vector<unsigned char> in_fmt;
     int in_fmt_n = 0;
+    // input leveller (conan_streams_set_input_level; level.hip): per slot its cfg (enabled = 0: none), which persists across resets;
+    // lv_n: slots with one.  The first enabling call allocates the per-slot state ([max_slots] of lv_stride bytes: cnk::LvState and
+    // the two block rings; stream state) and, per call, a row table (set q of lv_sets; the set's event follows the front-end launch).
+    // The kernel works in place on the resampler's staging rows (rs_wav), so such a stream-set has those too.
+    std::vector<conan_level_cfg> lv_cfg;
+    int lv_n = 0;
+    char* lv_state = nullptr; long long lv_stride = 0;
+    StageSets<cnk::LvRow> lv_sets;
+    cnk::LvFilter lv_filter;
+    bool levelled(int slot) const { return lv_n > 0 && lv_cfg[slot].enabled; }
   } wav_in;
+  void level_init(const cnk::LvFilter& f);      // the leveller's state and row tables (conan_streams_set_input_level)
   void ragged_init();
   void resample_init();        // staging, row tables and the history ring (conan_streams_set_input_rate)
   void rs_stage_init();        // staging and row tables only (conan_streams_set_input_format: no stream state)
@@ -228,6 +239,7 @@ struct conan_streams {
     snap::Layout layout;
     bool lay_ok = false, built = false;      // the host layout is current; the device tables hold it
     const float* lay_rs = nullptr; const float* lay_or = nullptr;      // the rate rings the layout was built with
+    const char* lay_lv = nullptr;                                      // ... and the leveller's state
     snap::Region* d_regions = nullptr; int* d_item_first = nullptr;
     StageSets<std::array<int, 4>> sets;
     std::vector<conan_resample_cfg> in_cfg, out_cfg;
@@ -468,6 +480,8 @@ void set_input_rate(conan_streams* s, const int32_t* slots, int n, const conan_r
 void set_output_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg);
 void set_output_ld(conan_streams* s, int64_t ld);
 void set_input_format(conan_streams* s, const int32_t* slots, int n, int format);
+void set_input_level(conan_streams* s, const int32_t* slots, int n, const conan_level_cfg* cfg);
+void input_level(conan_streams* s, const int32_t* slots, int n, double* stats_dev, void* stream);
 void set_output_format(conan_streams* s, const int32_t* slots, int n, int format);
 int output_samples(conan_streams* s, int32_t* counts, int cap);      // -> rows of the most recent step call
 void output_pending(conan_streams* s, const int32_t* slots, int n, int32_t* counts);
@@ -481,4 +495,5 @@ int64_t row_bytes(conan_streams* s);
 void export_slots(conan_streams* s, const int32_t* slots, int n, void* blob_dev, int64_t blob_ld, conan_slot_meta* meta, void* stream);
 void import_slots(conan_streams* s, const int32_t* slots, int n, const void* blob_dev, int64_t blob_ld, const conan_slot_meta* meta, void* stream);
 void meta_info(const conan_slot_meta* meta, conan_slot_info* out);
+int meta_level(const conan_slot_meta* meta, conan_level_cfg* out);      // 1: the record carries a leveller
 }  // namespace snapshot

@@ -231,6 +231,11 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
       if (r.f != r0.f || (r.f && (r.in != r0.in || r.out != r0.out || r.phase != r0.phase)))
         throw Error(CONAN_ERR_INVALID, who + ": the slots of one call must share one input rate configuration (conan_streams_set_input_rate) and position");
     }
+    for (int i = 1; i < n && s->wav_in.lv_n > 0; ++i) {
+      const conan_level_cfg &l0 = s->wav_in.lv_cfg[slots[0]], &l = s->wav_in.lv_cfg[slots[i]];
+      if (l.enabled != l0.enabled || (l.enabled && memcmp(&l, &l0, sizeof(l))))
+        throw Error(CONAN_ERR_INVALID, who + ": the slots of one call must share one input level configuration (conan_streams_set_input_level)");
+    }
   }
   // the input resampler's rows first: what each slot's front-end gets this call
   const RsPlan P = rs_plan(s, slots, n, in_samples, in_final, wav_dev, wav_ld, m, who.c_str());
@@ -255,6 +260,27 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
     if (fin && o.recv + sm < 1) bad("an utterance needs at least one sample");
     pl[i] = fe_plan(s, o, sm, fin, N, who);
     run = run || pl[i].nnew > 0 || sm > 0 || pl[i].emit > 0;
+  }
+  // the leveller's rows: the levelled slots that hand their front-end samples this call.  Behind a resampler launch the kernel works
+  // in place on the staged rows; in a call without one it reads the caller's rows and writes the staging itself, so the call's
+  // unlevelled rows with samples ride along as copy rows and the front-end still finds every row in one place.
+  std::vector<cnk::LvRow> lv_rows;
+  bool lv_any = false;
+  for (int i = 0; i < n && s->wav_in.lv_n > 0; ++i) lv_any = lv_any || (s->wav_in.levelled(slots[i]) && samples[i] > 0);
+  const bool lv_stages = lv_any && !P.launch;
+  for (int i = 0; i < n && lv_any; ++i) {
+    const bool on = s->wav_in.levelled(slots[i]);
+    if (samples[i] < 1 || (!on && !lv_stages)) continue;
+    cnk::LvRow R;
+    memset(&R, 0, sizeof(R));
+    if (on) {
+      R.c = level::plan_call(s->wav_in.fe_slot[slots[i]].recv, samples[i], s->wav_in.lv_filter.U, 50.0 * hop);
+      R.cfg = level::kernel_cfg(s->wav_in.lv_cfg[slots[i]]);
+    } else {
+      R.c.m = samples[i]; R.copy = 1;
+    }
+    R.slot = slots[i]; R.row = i;
+    lv_rows.push_back(R);
   }
   // emit groups, largest emit first; a group's rows keep call order
   std::vector<std::vector<int>> groups;      // call rows per group
@@ -313,12 +339,13 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
     s->ragged_init();
     q = s->wav_in.rg_sets.begin(tab.data(), n, cst);
   }
-  if (P.launch) rq = s->wav_in.rs_sets.begin(P.rows.data(), n, cst);
+  if (P.launch || lv_stages) rq = s->wav_in.rs_sets.begin(P.rows.data(), n, cst);      // (a leveller alone takes the set for its staging)
+  const int lq = lv_rows.empty() ? 0 : s->wav_in.lv_sets.begin(lv_rows.data(), (int)lv_rows.size(), cst);
   const int* rg_tab = reinterpret_cast<const int*>(s->wav_in.rg_sets.rows[q]);
   std::function<void(hipStream_t)> front;
   if (run) {
     const float* rg = s->ctx->vec(k + ".range");
-    const float* wav = P.launch ? s->wav_in.rs_wav[rq] : wav_dev;
+    const float* wav = P.launch || lv_stages ? s->wav_in.rs_wav[rq] : wav_dev;
     auto fill = [&](auto& a) {      // the fields both front-end kernels share
       a.wav = wav; a.aring = s->wav_in.fe_audio; a.mring = s->wav_in.fe_mel; a.chunk = s->wav_in.fe_chunk; a.n = n;
       a.win = s->ctx->vec(k + ".win"); a.tw = reinterpret_cast<const double2*>(s->ctx->vec(k + ".tw")); a.fb = s->ctx->vec(k + ".fb");
@@ -340,10 +367,24 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
     } else {
       cnk::MelRaggedArgs a;
       fill(a);
-      a.tab = rg_tab; a.jobs = jobs; a.wstride = P.launch ? seg * hop : (int)wav_ld;
+      a.tab = rg_tab; a.jobs = jobs; a.wstride = P.launch || lv_stages ? seg * hop : (int)wav_ld;
       const double flops = 4.0 * jobs * (double)(N / 2 + 1) * N;
       front = [s, a, flops](hipStream_t st) { s->profiled("mel_stream_ragged_kernel", flops, st, [&] { cnk::launch_mel_ragged(a, st); }); };
     }
+  }
+  // the leveller, between the resampler's launch (or the caller's rows) and the front-end's
+  if (!lv_rows.empty()) {
+    cnk::LevelStreamArgs a;
+    a.y = s->wav_in.rs_wav[rq]; a.y_ld = common ? samples[0] : seg * hop;
+    a.x = lv_stages ? wav_dev : a.y; a.x_ld = lv_stages ? wav_ld : a.y_ld;
+    a.state = s->wav_in.lv_state; a.state_stride = s->wav_in.lv_stride; a.zcap = CONAN_LEVEL_MAX_BLOCKS + cnk::kLvRingPad;
+    a.rows = s->wav_in.lv_sets.rows[lq]; a.n = (int)lv_rows.size(); a.f = s->wav_in.lv_filter;
+    front = [s, a, lq, rq, lv_stages, mel_front = front](hipStream_t st) {
+      s->profiled("level_stream_kernel", 0.0, st, [&] { cnk::launch_level_stream(a, st); });
+      mel_front(st);
+      s->wav_in.lv_sets.end(lq, st);
+      if (lv_stages) s->wav_in.rs_sets.end(rq, st);
+    };
   }
   // (the same-position kernel reads the resampler's rows [n][samples], the ragged one [n][seg * hop])
   if (P.launch) front = rs_front(s, P, n, rq, wav_dev, wav_ld, common ? samples[0] : seg * hop, front);
@@ -490,6 +531,53 @@ void set_input_format(conan_streams* s, const int32_t* slots, int n, int format)
   store_format(s->wav_in.in_fmt, s->wav_in.in_fmt_n, slots, n, format);
 }
 
+void set_input_level(conan_streams* s, const int32_t* slots, int n, const conan_level_cfg* cfg) {
+  if (!s || !slots || !cfg) throw Error(CONAN_ERR_INVALID, "null argument");
+  level::check_cfg(*cfg, "conan_streams_set_input_level");
+  if (!s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, "conan_streams_set_input_level: the stream-set has no streaming front-end (all three models)");
+  check_slot_list(s, slots, n);
+  cnk::LvFilter f;
+  if (cfg->enabled) f = level::filter(s->ctx, "conan_streams_set_input_level");
+  for (int i = 0; i < n; ++i) {
+    const conan_streams::FeSlot& o = s->wav_in.fe_slot[slots[i]];
+    const bool rs_fresh = s->wav_in.rs_slot.empty() || (s->wav_in.rs_slot[slots[i]].in == 0 && s->wav_in.rs_slot[slots[i]].phase == 0);
+    if (o.recv != 0 || o.phase != 0 || o.frames != 0 || o.chunks != 0 || !rs_fresh)
+      throw Error(CONAN_ERR_STATE, "conan_streams_set_input_level: slot " + std::to_string(slots[i]) + " is not at the start of an utterance (reset it with CONAN_MODEL_FRONTEND first)");
+  }
+  if (!cfg->enabled && s->wav_in.lv_cfg.empty()) return;      // a stream-set that never had a leveller: nothing to allocate
+  if (cfg->enabled) {
+    HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+    s->level_init(f);
+  }
+  conan_level_cfg c = *cfg;
+  if (!c.enabled) memset(&c, 0, sizeof(c));
+  for (int i = 0; i < n; ++i) {
+    s->wav_in.lv_n += c.enabled - s->wav_in.lv_cfg[slots[i]].enabled;
+    s->wav_in.lv_cfg[slots[i]] = c;
+  }
+}
+
+void input_level(conan_streams* s, const int32_t* slots, int n, double* stats_dev, void* stream) {
+  if (!s || !slots || !stats_dev) throw Error(CONAN_ERR_INVALID, "null argument");
+  check_slot_list(s, slots, n);
+  std::vector<cnk::LvRow> rows((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    if (!s->wav_in.levelled(slots[i])) throw Error(CONAN_ERR_STATE, "conan_streams_input_level: slot " + std::to_string(slots[i]) + " has no leveller (conan_streams_set_input_level)");
+    memset(&rows[i], 0, sizeof(cnk::LvRow));
+    rows[i].cfg = level::kernel_cfg(s->wav_in.lv_cfg[slots[i]]);
+    rows[i].slot = slots[i]; rows[i].row = i; rows[i].fresh = s->wav_in.fe_slot[slots[i]].recv == 0;
+  }
+  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+  hipStream_t st = (hipStream_t)stream;
+  s->join(st);
+  const int q = s->wav_in.lv_sets.begin(rows.data(), n, st);
+  cnk::LevelStatsArgs a;
+  a.state = s->wav_in.lv_state; a.state_stride = s->wav_in.lv_stride; a.rows = s->wav_in.lv_sets.rows[q]; a.n = n; a.out = stats_dev;
+  cnk::launch_level_stats(a, st);
+  HIP_CHECK(hipGetLastError());
+  s->wav_in.lv_sets.end(q, st);
+}
+
 void set_output_format(conan_streams* s, const int32_t* slots, int n, int format) {
   if (!s || !slots) throw Error(CONAN_ERR_INVALID, "null argument");
   if (!(s->ctx->cfg.models & CONAN_MODEL_HIFIGAN)) throw Error(CONAN_ERR_STATE, "conan_streams_set_output_format: context holds no HiFi-GAN model");
@@ -536,6 +624,16 @@ void flush_output(conan_streams* s, const int32_t* slots, int n, float* wav_out_
 void conan_streams::resample_init() {
   rs_stage_init();
   if (!wav_in.rs_ring) wav_in.rs_ring = alloc((size_t)max_slots * cnk::kRsRing);        // stream state (state_bytes)
+}
+
+void conan_streams::level_init(const cnk::LvFilter& f) {
+  rs_stage_init();
+  if (wav_in.lv_state) return;
+  wav_in.lv_filter = f;
+  wav_in.lv_stride = (long long)cnk::lv_state_bytes(CONAN_LEVEL_MAX_BLOCKS + cnk::kLvRingPad);
+  wav_in.lv_state = reinterpret_cast<char*>(alloc((size_t)max_slots * wav_in.lv_stride / sizeof(float)));        // stream state (state_bytes)
+  wav_in.lv_sets.init(max_slots, allocs);
+  wav_in.lv_cfg.assign(max_slots, conan_level_cfg{});
 }
 
 void conan_streams::out_ring_init() {

@@ -234,16 +234,32 @@ class StreamingVoiceConversionEngine:
         self._set_out_rate(self.slots, out_rate, out_filter)
         self._set_format(self.slots, out_format, self.st.output_formats, self.st.set_output_format)
 
-    def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, **filter):
+    def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
+                  **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
         in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
         in_format: the input's sample format (None: float32; 's16' takes int16 rows, 'ulaw' / 'alaw' uint8), decoded on the GPU.
-        out_rate / out_filter / out_format: as in start()."""
-        if isinstance(in_format, (list, tuple)):
-            raise ValueError("in_format: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
+        out_rate / out_filter / out_format: as in start().
+        level: the input leveller (Streams.set_input_level) - None / False: none; True: Context.level's defaults; a dict: its
+        keywords.  It runs on the GPU on the decoded, resampled samples in front of the front-end, causally: feed() gains no latency."""
+        if isinstance(in_format, (list, tuple)) or isinstance(level, (list, tuple)):
+            raise ValueError("in_format / level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
         self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format)
         self._set_rate(self.slots, in_rate, filter)
         self._set_format(self.slots, in_format, self.st.input_formats, self.st.set_input_format)
+        self._set_level(self.slots, level)
+
+    def _set_level(self, slots, level):
+        """The slots' input leveller (None / False: none; True: the defaults; a dict of Streams.set_input_level's keywords), one value
+        or one per slot.  Slots that never had one are left alone."""
+        levels = list(level) if isinstance(level, (list, tuple)) else [level] * len(slots)
+        assert len(levels) == len(slots), (len(levels), len(slots))
+        for slot, lv in zip(slots, levels):
+            if lv is None or lv is False:
+                if int(slot) in self.st.input_levels:
+                    self.st.set_input_level([slot], None)
+            else:
+                self.st.set_input_level([slot], True if lv is True else dict(lv))
 
     @staticmethod
     def _set_format(slots, fmt, table, setter):
@@ -313,8 +329,10 @@ class StreamingVoiceConversionEngine:
         (wav [B, emit*hop], mel [B, emit, 80], codes [B, emit]) of the chunk this call emitted (emit = 0 on the first call: one
         chunk of algorithmic latency).  After final=True keep calling feed(empty, final=True) until it returns 0 frames.
         pipelined: conan_step_wav_async - the tensors are complete after self.st.join().
-        The reference's loud_norm cannot run here: the loudness is a property of the whole utterance, which a streaming call has not
-        seen yet (infer_wav(loud_norm=True) normalises an utterance it holds whole)."""
+        The reference's whole-utterance loud_norm still cannot run here: that loudness is a property of the whole utterance, which a
+        streaming call has not seen yet (infer_wav(loud_norm=True) normalises an utterance it holds whole).  What can stream is the
+        input leveller, start_wav(level=...): a causal BS.1770 meter of the audio so far steers a ramped gain towards the same
+        target, on the GPU in front of the front-end, without look-ahead or added latency (Context.level is its whole-signal form)."""
         fn = self.st.step_wav_async if pipelined else self.st.step_wav
         st = self.st
         if not (st.output_ld or st.output_formats):
@@ -336,7 +354,7 @@ class StreamingVoiceConversionEngine:
 
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
-                  out_format=None, loud_norm=False, **filter):
+                  out_format=None, loud_norm=False, level=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
@@ -344,10 +362,13 @@ class StreamingVoiceConversionEngine:
         in_format: src_wav's sample format (int16 / uint8 samples; the results are those of the decoded floats, ctx.convert_samples,
         bit for bit); out_format: the returned wav's format (ctx.convert_samples of the float wav bit for bit).
         loud_norm: each whole source utterance is loudness-normalised at its input rate before it is fed (the reference's loud_norm;
-        float32 rows only); the results are those of infer_wav(ctx.loud_norm(src_wav, rate), ...) bit for bit."""
+        float32 rows only); the results are those of infer_wav(ctx.loud_norm(src_wav, rate), ...) bit for bit.
+        level: the streaming input leveller (start_wav); the results are those of infer_wav(ctx.level(x, **level), ...) bit for bit,
+        x = the decoded, resampled utterance."""
         if loud_norm:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
-        self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, **filter)
+        self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
+                       **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -373,12 +394,13 @@ class StreamingVoiceConversionEngine:
             wavs.append(torch.stack(self.finish()))
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
-    def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, **filter):
+    def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
+                   **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
         rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
         (None: the model rate), one value or one per slot.  in_format / out_format: the slots' sample formats (None: float32), one
-        value or one per slot."""
+        value or one per slot.  level: the slots' input leveller (start_wav), one value or a list with one per slot."""
         self.st.reset(slots, which=7 | 8)
         self.st.set_reference(slots, ref_mel, ref_len)
         self._set_out_rate(slots, out_rate, out_filter)
@@ -386,6 +408,7 @@ class StreamingVoiceConversionEngine:
         self._set_format(slots, out_format, self.st.output_formats, self.st.set_output_format)
         for r, group in _by_value(slots, _per_slot(in_rate, len(slots))):
             self._set_rate(group, r, filter)
+        self._set_level(slots, level)
 
     @torch.no_grad()
     def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None):
@@ -394,7 +417,9 @@ class StreamingVoiceConversionEngine:
         dtype) with its own final flag; the rules per slot are feed()'s.
         -> one (wav [emit*hop], mel [emit, 80], codes [emit]) per slot, of the chunk it emitted (emit = 0: empty).
         pipelined: conan_step_wav_ragged_async - the tensors are complete after self.st.join().
-        As in feed(), the reference's loud_norm cannot run here (infer_wav_staggered(loud_norm=True) holds the utterances whole)."""
+        As in feed(), the reference's whole-utterance loud_norm cannot run here (infer_wav_staggered(loud_norm=True) holds the
+        utterances whole); open_slots(level=...) gives a slot the causal input leveller, which can, and a call may mix levelled
+        and unlevelled slots."""
         fn = self.st.step_wav_ragged_async if pipelined else self.st.step_wav_ragged
         emit, c, m, w = fn(slots, wav, samples, final, mel=mel)
         counts = self.st.output_samples()        # (emit * hop for a slot without an output rate)
@@ -402,7 +427,7 @@ class StreamingVoiceConversionEngine:
 
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
-                            in_formats=None, out_formats=None, loud_norm=False, **filter):
+                            in_formats=None, out_formats=None, loud_norm=False, level=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -412,8 +437,10 @@ class StreamingVoiceConversionEngine:
         then mixes rates, with rows as wide as the widest input of the call.  out_rates[u] (+ out_filter): the rate utterance u's
         wav is returned at (None: the model rate).  in_formats[u] / out_formats[u]: the sample format utterance u arrives / is
         returned in (None: float32); one call then mixes formats, each row packed in its own.  loud_norm: every utterance is
-        loudness-normalised whole, at its own input rate, before its first audio is fed (float32 utterances only)."""
+        loudness-normalised whole, at its own input rate, before its first audio is fed (float32 utterances only).  level: the
+        streaming input leveller (start_wav), one value for every utterance or a list with one per utterance."""
         U = len(src_wavs)
+        levels = list(level) if isinstance(level, (list, tuple)) else [level] * U
         ifmts, ofmts, orates, rates = (list(v) if v is not None else [None] * U for v in (in_formats, out_formats, out_rates, in_rates))
         if loud_norm:
             src_wavs = [self._loud_norm(x, rates[u], ifmts[u]) for u, x in enumerate(src_wavs)]
@@ -435,7 +462,7 @@ class StreamingVoiceConversionEngine:
             if new:
                 self.open_slots([live[u][0] for u in new], torch.stack([ref_mel[u] for u in new]), in_rate=[rates[u] for u in new],
                                 out_rate=[orates[u] for u in new], out_filter=out_filter, in_format=[ifmts[u] for u in new],
-                                out_format=[ofmts[u] for u in new], **filter)
+                                out_format=[ofmts[u] for u in new], level=[levels[u] for u in new], **filter)
             if not live:
                 tick += 1
                 continue

@@ -177,6 +177,41 @@ class Context:
         _, stats, lead = self._loud_call(x, sample_rate, -22.0, True, lengths, None, True)
         return stats[:, 0].reshape(*lead) if len(lead) else stats[0, 0]
 
+    def level(self, x, target=-22.0, max_boost_db=20.0, max_cut_db=40.0, initial_gain_db=0.0, window_blocks=_lib.LEVEL_MAX_BLOCKS,
+              peak_limit=True, clip=False, lengths=None, return_trace=False, out=None):
+        """The streaming leveller's law on whole signals (conan_level; include/conan_hip.h, conan_level_cfg): x [..., N] float32 at
+        the model rate (hop * 50) -> the rows as a wav-in slot with Streams.set_input_level(**cfg) hands them to its front-end, bit
+        for bit.  A causal BS.1770 meter read every segment * hop samples steers a gain towards `target` LUFS within
+        [-max_cut_db, +max_boost_db], from initial_gain_db, over the last window_blocks 100 ms blocks; peak_limit keeps the gain
+        times the peak so far at or under 1, clip clamps the samples to [-1, 1].  The defaults are a choice, not a measurement.
+        lengths: samples per row (default N; the floats past a row's length come back as x's).  return_trace: also the float64
+        [..., ceil(N / U), 2] rows (L_k, G_k) of the update instants (rows past a shorter row's last instant are NaN).  out: a cuda
+        float32 [n, ld] buffer to write the rows into (it may be x itself: in place)."""
+        dev = torch.device("cuda", self.device)
+        x = x.to(dev, torch.float32)
+        lead, N = x.shape[:-1], x.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        if not (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= N):
+            x = x.reshape(n, N).contiguous()
+        lens = np.full(n, N, dtype=np.int64) if lengths is None else np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+        if lens.shape[0] != n:
+            raise ValueError(f"level: {lens.shape[0]} lengths for {n} rows")
+        if out is not None:
+            if not (out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == n and out.stride(1) == 1):
+                raise ValueError("level: out must be a cuda float32 [n, ld] buffer with unit column stride")
+            y = out
+        else:
+            y = x.clone() if lengths is not None else torch.empty(n, N, device=dev)
+        U = self.cfg.emf_segment * self.hop
+        K = max(1, -(-N // U)) if U > 0 else 1
+        trace = torch.full((n, K, 2), float("nan"), dtype=torch.float64, device=dev) if return_trace else None
+        cfg = _lib.level_cfg(target, max_boost_db, max_cut_db, initial_gain_db, window_blocks, peak_limit, clip)
+        _lib.check(self.lib.conan_level(self.h, C.byref(cfg), _ptr(x), x.stride(0), n, lens.ctypes.data_as(C.c_void_p), _ptr(y), y.stride(0),
+                                        _ptr(trace), K, _stream()))
+        if out is None:
+            y = y.reshape(*lead, y.shape[-1])
+        return (y, trace.reshape(*lead, K, 2)) if return_trace else y
+
     def convert_samples(self, x, src, dst, out=None):
         """conan_convert_samples: x [..., N] of format `src` ('f32' float32, 's16' int16, 'ulaw' / 'alaw' uint8) -> [..., N] of
         format `dst`, by the library's one conversion rule (decode exactly, encode with round-to-nearest-even and saturation).
@@ -232,13 +267,18 @@ class SlotSnapshot:
         return self.blob.shape[0]
 
     def info(self, i):
-        """conan_slot_meta_info of stream i: dict(layout_id, bytes, has_ref, in_format, out_format, in_rate, out_rate); a rate is
-        None for a stream without one."""
+        """conan_slot_meta_info of stream i: dict(layout_id, bytes, has_ref, in_format, out_format, in_rate, out_rate, level); a rate
+        is None for a stream without one; level (conan_slot_meta_level) is the input leveller's keywords as Streams.set_input_level
+        takes them, None for a stream without one."""
         rec = _lib.SlotMeta.from_buffer_copy(self.meta[i * _lib.SLOT_META_BYTES:(i + 1) * _lib.SLOT_META_BYTES])
         out = _lib.SlotInfo()
         _lib.check(_lib.lib().conan_slot_meta_info(C.byref(rec), C.byref(out)))
         names = {v: k for k, v in _lib.SAMPLE_FORMATS.items()}
-        return dict(layout_id=int(out.layout_id), bytes=int(out.bytes), has_ref=bool(out.has_ref), in_format=names[out.in_format],
+        lv = _lib.LevelCfg()
+        level = None
+        if _lib.check(_lib.lib().conan_slot_meta_level(C.byref(rec), C.byref(lv))):
+            level = _lib.level_keywords(lv)
+        return dict(level=level, layout_id=int(out.layout_id), bytes=int(out.bytes), has_ref=bool(out.has_ref), in_format=names[out.in_format],
                     out_format=names[out.out_format],
                     in_rate=out.in_rate.in_rate if out.in_rate.in_rate != out.in_rate.out_rate else None,
                     out_rate=out.out_rate.out_rate if out.out_rate.in_rate != out.out_rate.out_rate else None,
@@ -286,6 +326,7 @@ class Streams:
         self.output_ld = 0               # set_output_ld: row stride of every step's wav (0: each step's own)
         self.input_formats = {}          # slot -> 's16' | 'ulaw' | 'alaw', for the slots whose wav-in rows are not float32
         self.output_formats = {}         # slot -> the same, for the slots whose audio leaves in another format
+        self.input_levels = {}           # slot -> dict of set_input_level's keywords, for the slots with an input leveller
 
     @property
     def state_bytes(self):
@@ -319,8 +360,8 @@ class Streams:
         return SlotSnapshot(bytes(meta), blob)
 
     def import_slots(self, slots, snap):
-        """conan_streams_import_slots: slot slots[i] becomes stream i of `snap` (history, positions, style cache, rates and formats).
-        Every record is checked before anything changes.  The blob is moved to this device if it is elsewhere."""
+        """conan_streams_import_slots: slot slots[i] becomes stream i of `snap` (history, positions, style cache, rates, formats,
+        input leveller).  Every record is checked before anything changes.  The blob is moved to this device if it is elsewhere."""
         a, p = _i32(slots)
         n = len(a)
         if len(snap) != n:
@@ -342,6 +383,10 @@ class Streams:
                 self.output_rates[int(slot)] = int(info["out_rate"])
             else:
                 self.output_rates.pop(int(slot), None)
+            if info["level"] is not None:
+                self.input_levels[int(slot)] = info["level"]
+            else:
+                self.input_levels.pop(int(slot), None)
 
     def _release(self):
         """Buffers of pipelined steps may be dropped once the current torch stream waits for the library's internal
@@ -391,6 +436,36 @@ class Streams:
         a, p = _i32(slots)
         _lib.check(self.lib.conan_streams_set_input_format(self.h, p, len(a), _lib.sample_format(fmt)))
         self._note_format(self.input_formats, a, fmt)
+
+    def set_input_level(self, slots, cfg=True, **kw):
+        """conan_streams_set_input_level: a causal BS.1770 leveller on the slots' model-rate samples, behind format decoding and the
+        input resampler, in front of the streaming front-end.  Context.level's keywords (target, max_boost_db, max_cut_db,
+        initial_gain_db, window_blocks, peak_limit, clip) set it, as keywords or as a dict in cfg; those not given keep
+        Context.level's defaults, so set_input_level(slots) is the default leveller.  Only cfg=None turns it off.
+        The slots must be at the start of an utterance; the setting survives resets, which clear the meter.
+        input_levels[slot] holds every keyword of a levelled slot, as SlotSnapshot.info reports them."""
+        a, p = _i32(slots)
+        if cfg is None:
+            if kw:
+                raise ValueError("set_input_level: cfg=None turns the leveller off and takes no keywords")
+            c = _lib.LevelCfg()      # (enabled = 0)
+        else:
+            c = _lib.level_cfg(**dict({} if cfg is True else cfg, **kw))
+        _lib.check(self.lib.conan_streams_set_input_level(self.h, p, len(a), C.byref(c)))
+        for slot in a:
+            if c.enabled:
+                self.input_levels[int(slot)] = _lib.level_keywords(c)
+            else:
+                self.input_levels.pop(int(slot), None)
+
+    def input_level(self, slots):
+        """conan_streams_input_level: float64 [n, 4] (cuda) rows (L_k, G_k, P_k, J_k) of the slots' latest update instants - the
+        loudness read, the gain the current ramp ends at, the peak so far, the complete blocks.  Joins pipelined work."""
+        a, p = _i32(slots)
+        out = torch.empty(len(a), 4, dtype=torch.float64, device=self.dev)
+        _lib.check(self.lib.conan_streams_input_level(self.h, p, len(a), _ptr(out), _stream()))
+        self._release()
+        return out
 
     def set_output_format(self, slots, fmt):
         """conan_streams_set_output_format: the slots' audio leaves every step (and flush_output) as 'f32', 's16', 'ulaw' or 'alaw',

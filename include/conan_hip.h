@@ -545,6 +545,79 @@ typedef struct conan_loudness_cfg {
 int conan_loud_norm(conan_ctx* ctx, const conan_loudness_cfg* cfg, const float* x_dev, int64_t x_ld, int n, const int64_t* samples,
                     float* y_dev, int64_t y_ld, double* stats_dev, void* stream);
 
+/* Live input levelling (added within ABI 9: a caller detects it by the exported symbols): a causal leveller for wav-in slots, the
+ * streaming counterpart of conan_loud_norm, whose reading needs the whole utterance.  It runs on the GPU between the input resampler
+ * and the streaming front-end, on the model-rate samples the front-end is about to read.  This comment defines it
+ * (tests/level_ref.py restates it in numpy).  Per slot: fs = conan_hop_size() * 50, U = segment * hop (the samples of one chunk:
+ * 1280 at the shipped configuration), x_t = the model-rate float sample at position t, position 0 being the slot's first sample
+ * after a CONAN_MODEL_FRONTEND reset - after format decoding, after the input resampler.
+ *   Meter.  conan_loud_norm's K-weighting at fs from a zero state, f64 throughout.  Gating block j covers [lo_j, hi_j),
+ *     lo_j = int(0.4 * (j * 0.25) * fs), hi_j = int(0.4 * (j * 0.25 + 1) * fs), both evaluated in double in exactly this order on the
+ *     host; z_j = sum y^2 / (0.4 * fs); l_j = -0.691 + 10 log10(z_j).  Only complete blocks count: there is no truncated last block.
+ *   Update instants u_k = k * U, k >= 0.  At u_k: J_k = the number of blocks with hi_j <= u_k; the window is blocks
+ *     max(0, J_k - window_blocks) .. J_k - 1; L_k = conan_loud_norm's two-gate integrated loudness over the window (absolute gate
+ *     l_j >= -70; relative gate 10 LU under the mean z of the blocks that passed; final set: l_j above both, strictly; -inf when the
+ *     window or the final set is empty).  P_k = max |x_t| over t < u_k (P_0 = 0).  G_{-1} = 10^(initial_gain_db / 20).
+ *     G_k = G_{k-1} if L_k = -inf, else 10^(clamp(target_lufs - L_k, -max_cut_db, +max_boost_db) / 20).  Then, in either case, with
+ *     peak_limit: if G_k * P_k > 1 then G_k = 1 / P_k.
+ *   Samples.  For t in [u_k, u_{k+1}): g_t = G_{k-1} + (G_k - G_{k-1}) * ((t - u_k + 1) / U) in double (a division, a
+ *     multiplication and an addition, each rounded); y_t = (float)((double)x_t * g_t), one rounding; with clip, y_t is then clamped
+ *     to [-1, 1].  The front-end, and its audio ring, see y.
+ * What follows: G_k depends only on samples before u_k - no look-ahead, no added latency; the gain is continuous and moves over ramps
+ * of U samples (80 ms); y is a function of the slot's own sample stream alone - not of how calls cut the stream, of the other slots
+ * of a call, or of blocking against pipelined stepping.  The peak limit bounds a ramp's END gain, not every sample of the ramp: a
+ * transient louder than anything before it passes at the old gain until the next instant (a 0.9 spike during a +20 dB boost leaves
+ * at 9); clip exists for that.  On every prefix that ends at a gating block's end, with window_blocks at least the block
+ * count, L_k is conan_loud_norm's reading of that prefix.
+ * The order of every sum, fixed by stream positions alone: the stream is cut into 128-sample segments aligned to position 0; a
+ * segment's start state is M applied to its predecessor's start state plus the predecessor's end state from zero (conan_loud_norm's
+ * scan); inside a segment y^2 is summed in time order (fma) into the bins that the block edges strictly inside the segment cut it
+ * into; a block's energy adds, segment by segment in ascending order, the sum of the segment's bins inside the block (ascending);
+ * at an instant, lane i of 256 adds the window's blocks i, i + 256, ... oldest first, and the lanes' sums meet in a binary tree
+ * (lane i + lane i + w for w = 128, 64, .. 1).
+ * Limits: U must be a multiple of 128 and at most 1920, fs at least 2000 Hz, else CONAN_ERR_UNSUPPORTED. */
+#define CONAN_LEVEL_MAX_BLOCKS 4096
+typedef struct conan_level_cfg {
+  int32_t enabled;          /* 0 restores today's path for the slots; the other fields are then ignored */
+  float   target_lufs;      /* the reference's loud_norm: -22 */
+  float   max_boost_db, max_cut_db;   /* >= 0, finite */
+  float   initial_gain_db;  /* finite */
+  int32_t window_blocks;    /* 1 .. CONAN_LEVEL_MAX_BLOCKS (100 ms each) */
+  int32_t peak_limit, clip; /* 0 | 1 */
+  int32_t reserved[4];      /* must be 0 */
+} conan_level_cfg;
+/* Sets (cfg->enabled = 1) or removes (0) the leveller of `slots`, by conan_streams_set_input_rate's rules: every slot must be at the
+ * start of an utterance, else CONAN_ERR_STATE; every slot and the cfg are checked before anything changes.  The setting persists
+ * across CONAN_MODEL_FRONTEND resets; a reset clears the meter and returns the gain to initial_gain_db.  It applies to
+ * conan_step_wav[_async] and conan_step_wav_ragged[_ld][_async]; the slots of one ragged call may mix levelled and unlevelled rows
+ * with any rates and formats, and conan_step_wav's "one configuration per call" rule extends to the level cfg.  A call that gives a
+ * levelled slot front-end samples runs one more launch (level_stream_kernel, one workgroup per such row) in front of the front-end
+ * launch, on the same stream, so pipelined calls stay pipelined; behind an input resampler's launch it works in place on that
+ * launch's staging rows, and in a call without one it reads the caller's rows and writes the staging itself (the call's unlevelled
+ * rows ride along as copies), so levelling adds exactly one launch.  A stream-set that never enabled a leveller runs exactly the
+ * launches it ran before.  The first enabling call allocates, per slot of the stream-set, the leveller's
+ * state - 672 bytes (filter carry, pending samples, open blocks, gains, peak) and two rings of CONAN_LEVEL_MAX_BLOCKS + 16 doubles
+ * (block energies and loudnesses): 66464 bytes - which conan_streams_state_bytes counts from then on.  Slot snapshots carry a
+ * slot's leveller - its cfg in the record, its state as the row's last section - so a levelled stream exported mid-utterance
+ * continues bit for bit elsewhere (conan_streams_import_slots allocates the state exactly as this call would, and a record without
+ * a leveller turns the destination slot's off).  conan_streams_snapshot_bytes of every stream-set with a streaming front-end
+ * includes that section (66464 bytes, rounded up to 256) whether or not a leveller was ever set - like the rate rings' sections, so
+ * that equal stream-sets keep equal row sizes - and is therefore larger than a library without the leveller reports for the same
+ * stream-set; a caller that sizes blob rows must ask this library.  conan_slot_info.bytes of a slot without a leveller, the layout id
+ * and the blobs themselves are unchanged, and blobs written before the leveller existed still import. */
+int conan_streams_set_input_level(conan_streams* s, const int32_t* slots, int n, const conan_level_cfg* cfg);
+/* Joins pending pipelined work, then writes per slot {L_k, G_k, P_k, J_k} (stats_dev[n][4], device) on `stream`, for the latest
+ * instant k = (recv - 1) / U, recv = the model-rate samples the slot's front-end has received; before any sample
+ * {-inf, G_{-1}, 0, 0}.  A slot without a leveller is CONAN_ERR_STATE. */
+int conan_streams_input_level(conan_streams* s, const int32_t* slots, int n, double* stats_dev, void* stream);
+/* The whole-signal form, and the bit-exact yardstick of the streaming one: the same law at the context's fs and U (a context with
+ * an Emformer model) on n rows (1 .. 65535) of samples[i] (host; 1 .. 2^30, rows may differ) f32 samples at i * x_ld; y_dev rows at
+ * i * y_ld, only the first samples[i] floats written; y_dev may equal x_dev (with y_ld == x_ld).  trace_dev (may be NULL): row k of
+ * [n][trace_ld][2] is (L_k, G_k) for k < ceil(samples[i] / U) <= trace_ld.  cfg->enabled must be 1.  One workgroup walks a row's
+ * intervals in order: a yardstick, not a throughput path.  Stream-ordered; it uses the context's workspace like conan_loud_norm. */
+int conan_level(conan_ctx* ctx, const conan_level_cfg* cfg, const float* x_dev, int64_t x_ld, int n, const int64_t* samples,
+                float* y_dev, int64_t y_ld, double* trace_dev, int64_t trace_ld, void* stream);
+
 /* Measurement hook (replaces the reference's Timer('hifigan') around the vocoder forward,
  * utils/commons/meters.py:21-42, tasks/tts/vocoder_infer/hifigan.py:28): between begin and end every
  * launch of the conv_mfma kernel family is bracketed by HIP events on its launch stream.  end() waits
@@ -631,6 +704,10 @@ int conan_streams_export_slots(conan_streams* s, const int32_t* slots, int n, vo
 int conan_streams_import_slots(conan_streams* s, const int32_t* slots, int n, const void* blob_dev, int64_t blob_ld_bytes,
                                const conan_slot_meta* meta_host, void* stream);
 int conan_slot_meta_info(const conan_slot_meta* meta, conan_slot_info* out);   /* host only, no handle */
+/* Host only, no handle (added within ABI 9 with conan_streams_set_input_level): the input leveller a record carries -> 1 and *out
+ * = its cfg, or 0 and *out zeroed (enabled = 0) for a record without one - every record written before the leveller existed.
+ * CONAN_ERR_INVALID for a record that is not one, as conan_slot_meta_info. */
+int conan_slot_meta_level(const conan_slot_meta* meta, conan_level_cfg* out);
 
 #ifdef __cplusplus
 }
