@@ -133,6 +133,11 @@ _PROTOS = {
     "conan_streams_import_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "conan_slot_meta_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "conan_slot_meta_level": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "conan_streams_set_pitch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "conan_streams_pitch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "conan_decoder_step_pitch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "conan_slot_meta_pitch": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -269,6 +274,26 @@ def level_keywords(c):
     """level_cfg's keywords of an enabled LevelCfg: the one form Streams.input_levels and SlotSnapshot.info report a leveller in."""
     return dict(target=c.target_lufs, max_boost_db=c.max_boost_db, max_cut_db=c.max_cut_db, initial_gain_db=c.initial_gain_db,
                 window_blocks=c.window_blocks, peak_limit=bool(c.peak_limit), clip=bool(c.clip))
+
+
+class PitchCfg(C.Structure):
+    """conan_pitch_cfg (include/conan_hip.h)."""
+    _fields_ = [("enabled", C.c_int32), ("shift_semitones", C.c_float), ("range", C.c_float), ("pivot", C.c_float),
+                ("uv_threshold", C.c_float), ("reserved", C.c_int32)]
+
+
+PITCH_PIVOT = 7.5      # log2 Hz (181 Hz): where `range` pivots unless the caller says otherwise
+
+
+def pitch_cfg(shift_semitones=0.0, range=1.0, pivot=PITCH_PIVOT, uv_threshold=0.0):
+    """An enabled conan_pitch_cfg: transpose by shift_semitones, scale the contour's excursion around `pivot` (log2 Hz) by `range`,
+    call a frame unvoiced when the head's d0 exceeds uv_threshold.  The defaults change nothing but the code path."""
+    return PitchCfg(1, float(shift_semitones), float(range), float(pivot), float(uv_threshold), 0)
+
+
+def pitch_keywords(c):
+    """pitch_cfg's keywords of an enabled PitchCfg: the form Streams.pitch and SlotSnapshot.info report a pitch control in."""
+    return dict(shift_semitones=c.shift_semitones, range=c.range, pivot=c.pivot, uv_threshold=c.uv_threshold)
 
 
 class DecoderTaps(C.Structure):

@@ -435,6 +435,28 @@ int conan_decoder_step_taps(conan_streams* s, const int32_t* slots, int n, int f
   });
 }
 
+int conan_decoder_step_pitch(conan_streams* s, const int32_t* slots, int n, int frames, const int32_t* codes_dev, const float* f0_in_dev,
+                             const float* uv_in_dev, float* mel_out_dev, const conan_decoder_taps* taps, void* stream) {
+  return guarded([&] {
+    if (!s || !slots || !codes_dev || !mel_out_dev) throw Error(CONAN_ERR_INVALID, "null argument");
+    if (!(s->ctx->cfg.models & CONAN_MODEL_CONAN)) throw Error(CONAN_ERR_STATE, "context holds no Conan model");
+    if (frames < 1 || frames > s->max_frames) throw Error(CONAN_ERR_INVALID, "frames out of range");
+    HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+    s->join((hipStream_t)stream);
+    s->set_slots(slots, n, (hipStream_t)stream);
+    conan_decoder_taps none; memset(&none, 0, sizeof(none));
+    conan_streams::DecExtra ex;      // (the contour pointers travel in PitchHeadArgs; a step without taps keeps the persistent launch)
+    ex.f0_in = f0_in_dev; ex.uv_in = f0_in_dev ? uv_in_dev : nullptr;
+    s->decoder_step(n, frames, codes_dev, mel_out_dev, taps ? *taps : none, (hipStream_t)stream, &ex);
+  });
+}
+
+int conan_streams_set_pitch(conan_streams* s, const int32_t* slots, int n, const conan_pitch_cfg* cfg, void* stream) {
+  return guarded([&] { pitch::set_pitch(s, slots, n, cfg, stream); });
+}
+
+int conan_streams_pitch(const conan_streams* s, int slot, conan_pitch_cfg* out) { return guarded([&] { pitch::get_pitch(s, slot, out); }); }
+
 int conan_get_style(conan_streams* s, const int32_t* slots, int n, float* style_dev, int32_t* max_tokens_out, void* stream) {
   return guarded([&] {
     if (!s || !slots || !style_dev) throw Error(CONAN_ERR_INVALID, "null argument");
@@ -830,6 +852,12 @@ int conan_slot_meta_info(const conan_slot_meta* meta, conan_slot_info* out) { re
 int conan_slot_meta_level(const conan_slot_meta* meta, conan_level_cfg* out) {
   int has = 0;
   const int rc = guarded([&] { has = snapshot::meta_level(meta, out); });
+  return rc < 0 ? rc : has;
+}
+
+int conan_slot_meta_pitch(const conan_slot_meta* meta, conan_pitch_cfg* out) {
+  int has = 0;
+  const int rc = guarded([&] { has = snapshot::meta_pitch(meta, out); });
   return rc < 0 ? rc : has;
 }
 

@@ -434,7 +434,11 @@ struct XAttnArgs {
 };
 void launch_xattn(const XAttnArgs& a, hipStream_t st);
 
-// uv/f0 head: LN(128) -> Linear(128->2) -> uv/f0 -> coarse bin -> decoder_inp = pitch_inp + pitch_embed[bin]
+// A slot's entry of the pitch-control table (include/conan_hip.h, conan_pitch_cfg, as the kernels read it): shift_oct is the host's
+// (float)((double)shift_semitones / 12.0); a disabled slot's entry is all zero (thr = 0: the model's own threshold).
+struct PitchSlot { int enabled; float shift_oct, range, pivot, thr; int pad_; };
+static_assert(sizeof(PitchSlot) == 24, "24 bytes per slot");
+// uv/f0 head: LN(128) -> Linear(128->2) -> uv/f0 -> pitch control -> coarse bin -> decoder_inp = pitch_inp + pitch_embed[bin]
 struct PitchHeadArgs {
   TRef h;              // [i][t][Cp]
   TRef pitch_inp;      // [i][t][E]
@@ -445,8 +449,15 @@ struct PitchHeadArgs {
   float* uv_pred; float* f0; int* bins;   // optional taps, [n][T][2], [n][T], [n][T]
   const int* slots; const int* pos;
   int T, n, Cp, E, silent_token;
+  int pad_;
+  const PitchSlot* ptab;        // [max_slots] per-slot pitch control, indexed by slot (conan_streams_set_pitch); never null
+  const float* f0_in; const float* uv_in;   // optional caller contour [n][T] (log2 Hz; > 0: unvoiced), conan_decoder_step_pitch
 };
 void launch_pitch_head(const PitchHeadArgs& a, hipStream_t st);
+// table[rows[i].slot] = rows[i].v for i < n (conan_streams_set_pitch, snapshot import); slots checked by the host
+struct PitchRow { int slot; PitchSlot v; int pad_; };
+static_assert(sizeof(PitchRow) == 32, "uploaded as 8 ints");
+void launch_pitch_table(PitchSlot* table, const PitchRow* rows, int n, hipStream_t st);
 
 // y = leaky_relu((x0 + x1 + x2) / nsrc): the MRF mean of HifiGanGenerator.forward (hifigan_causal.py:324-331) with the
 // following LeakyReLU, materialised once so that the consuming conv runs the single-source direct-to-LDS path.

@@ -267,6 +267,15 @@ void launch_pitch_head(const PitchHeadArgs& a, hipStream_t st) {
   const double mn = 1127.0 * log(1.0 + 50.0 / 700.0), mxx = 1127.0 * log(1.0 + 900.0 / 700.0);
   hipLaunchKernelGGL(pitch_head_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, a, (float)mn, (float)(mxx - mn));
 }
+// the pitch-control table's entries of the rows' slots (conan_streams_set_pitch; the host has checked the slots)
+__global__ __launch_bounds__(64) void pitch_table_kernel(PitchSlot* table, const PitchRow* rows, int n) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i < n) { const PitchRow r = rows[i]; table[r.slot] = r.v; }
+}
+void launch_pitch_table(PitchSlot* table, const PitchRow* rows, int n, hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(pitch_table_kernel, dim3((n + 63) / 64), dim3(64), 0, st, table, rows, n);
+}
 
 // ------------------------------------------------------------------------------------ MRF mean + LeakyReLU
 __global__ __launch_bounds__(256) void mean_act_kernel(const MeanActArgs a) {

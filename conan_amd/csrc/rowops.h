@@ -565,6 +565,33 @@ __device__ __forceinline__ void xattn_tile(const A& a, const int bx, float* __re
 }
 
 // ------------------------------------------------------------------------------------------------ uv / f0 head
+// Per-slot pitch control (include/conan_hip.h, conan_pitch_cfg): a slot's table entry - five words, loaded unconditionally at the head of
+// the row, in front of every branch - and the law between the head's output and denorm_f0.  A disabled slot's entry is
+// zero: v = d1 and the threshold 0 are the arithmetic of a library without the table.
+struct PitchCtl { int en; float so, rg, pv, th; };
+__device__ __forceinline__ PitchCtl pitch_ctl(const PitchSlot* tab, const int slot) {
+  const float* p = reinterpret_cast<const float*>(tab + slot);
+  PitchCtl c;
+  c.en = ldi(reinterpret_cast<const int*>(p)); c.so = ldw1(p + 1); c.rg = ldw1(p + 2); c.pv = ldw1(p + 3); c.th = ldw1(p + 4);
+  return c;
+}
+// (v, uv) of row m: the caller's contour where the step has one (no silent-token forcing: the reference's non-infer branch), else the head's
+template <class A>
+__device__ __forceinline__ float pitch_law(const A& a, const PitchCtl& pc, const int m, const float d0, const float d1, const int code, bool& uv) {
+  float v = d1;
+  if (a.f0_in) {
+    v = ldw1(a.f0_in + m);
+    uv = a.uv_in ? ldw1(a.uv_in + m) > 0.f : false;
+  } else {
+    uv = (d0 > pc.th) || (code == a.silent_token);
+  }
+  if (pc.en) {
+    if (pc.rg != 1.f) v = fmaf(pc.rg, v - pc.pv, pc.pv);
+    v = v + pc.so;
+  }
+  return v;
+}
+
 // PitchPredictor tail (nar_tts_modules.py:141-146) + add_orig_pitch (Conan.py:330-340) + denorm_f0 /
 // f0_to_coarse (pitch/utils.py:71-82, :17-28) + pitch_embed add (Conan.py:301, :181); fp32 op order kept.  4 rows per tile.
 template <bool COH, class A>
@@ -575,6 +602,7 @@ __device__ __forceinline__ void pitch_head_tile(const A& a, const float mel_min,
   const int i = m / a.T, t = m - i * a.T;
   const int slot = ldi(a.slots + i);
   const int pos = a.pos ? ldi(a.pos + slot) : 0;
+  const PitchCtl pc = pitch_ctl(a.ptab, slot);
   const float* x = row(a.h, i, slot, pos, t);
   float v[4];
   float s = 0.f;
@@ -596,8 +624,8 @@ __device__ __forceinline__ void pitch_head_tile(const A& a, const float mel_min,
   d0 = wave_sum(d0) + ldw1(a.b);
   d1 = wave_sum(d1) + ldw1(a.b + 1);
   const int code = ldi(a.codes + m);
-  const bool uv = (d0 > 0.f) || (code == a.silent_token);
-  float f0 = exp2f(d1);
+  bool uv;
+  float f0 = exp2f(pitch_law(a, pc, m, d0, d1, code, uv));
   f0 = fminf(fmaxf(f0, 50.f), 900.f);
   if (uv) f0 = 0.f;
   float fm = 1127.f * logf(1.f + f0 / 700.f);
@@ -1517,6 +1545,7 @@ __device__ __forceinline__ void mg_pitch_row(const A& a, const RowTab& tb, const
   const int lane = threadIdx.x & 63;
   const RowId id = row_id(tb, r);
   const int m = id.i * a.T + id.t;
+  const PitchCtl pc = pitch_ctl(a.ptab, id.slot);
   const float* x = row(a.h, id.i, id.slot, id.pos, id.t);
   float v[4];
   float s = 0.f;
@@ -1538,8 +1567,8 @@ __device__ __forceinline__ void mg_pitch_row(const A& a, const RowTab& tb, const
   d0 = wave_sum(d0) + ldw1(a.b);
   d1 = wave_sum(d1) + ldw1(a.b + 1);
   const int code = ldi(a.codes + m);
-  const bool uv = (d0 > 0.f) || (code == a.silent_token);
-  float f0 = exp2f(d1);
+  bool uv;
+  float f0 = exp2f(pitch_law(a, pc, m, d0, d1, code, uv));
   f0 = fminf(fmaxf(f0, 50.f), 900.f);
   if (uv) f0 = 0.f;
   float fm = 1127.f * logf(1.f + f0 / 700.f);

@@ -43,8 +43,9 @@ struct Meta {
   conan_resample_cfg in_cfg, out_cfg;
   uint64_t checksum;                 // FNV-1a over the record with this field zero
   conan_level_cfg lv;                // the input leveller (all zero: none - every record written before it existed)
-  unsigned char pad[CONAN_SLOT_META_BYTES - 184 - sizeof(conan_level_cfg)];
+  conan_pitch_cfg pt;                // the pitch control (all zero: none - every record written before it existed); it fills what was padding
 };
+static_assert(sizeof(conan_pitch_cfg) == 24 && CONAN_SLOT_META_BYTES - 184 - sizeof(conan_level_cfg) == sizeof(conan_pitch_cfg), "the pitch cfg takes the record's last 24 bytes");
 static_assert(sizeof(Meta) == CONAN_SLOT_META_BYTES && sizeof(conan_slot_meta) == CONAN_SLOT_META_BYTES, "the meta record is 256 bytes");
 
 uint64_t meta_sum(Meta m) { m.checksum = 0; return snap::fnv1a(snap::kFnvSeed, &m, sizeof(m)); }
@@ -204,6 +205,7 @@ void export_slots(conan_streams* s, const int32_t* slots, int n, void* blob_dev,
       if (o.f) m.out_cfg = s->snapshot.out_cfg[slot];
     }
     if (s->wav_in.levelled(slot)) m.lv = s->wav_in.lv_cfg[slot];
+    if (!s->pt_cfg.empty() && s->pt_cfg[slot].enabled) m.pt = s->pt_cfg[slot];
     m.checksum = meta_sum(m);
     memcpy(&meta[i], &m, sizeof(m));
   }
@@ -236,6 +238,8 @@ void import_slots(conan_streams* s, const int32_t* slots, int n, const void* blo
     if (((present >> snap::SEC_RS_IN) & 1) != (tin[i] != nullptr) || ((present >> snap::SEC_RS_OUT) & 1) != (tout[i] != nullptr)) throw Error(CONAN_ERR_INVALID, where + "inconsistent sections");
     need_rs_stage = need_rs_stage || m.in_fmt != CONAN_SAMPLE_F32 || m.has_rs;
     level::check_cfg(m.lv, who);
+    pitch::check_cfg(m.pt, who);
+    if (m.pt.enabled && s->pt_cfg.empty()) throw Error(CONAN_ERR_STATE, where + "the stream carries a pitch control and this stream-set has no Conan model");
     if (((present >> snap::SEC_LEVEL) & 1) != (m.lv.enabled != 0)) throw Error(CONAN_ERR_INVALID, where + "inconsistent sections");
     if (m.lv.enabled) {
       if (!s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, where + "the stream carries an input leveller and this stream-set has no streaming front-end");
@@ -263,6 +267,11 @@ void import_slots(conan_streams* s, const int32_t* slots, int n, const void* blo
     for (auto& b : s->voc_state) cnk::launch_zero_slots(b.first, b.second, b.second, s->d_slots, (int)fresh_nn.size(), st);
   }
   launch<false>(s, rows, const_cast<char*>(static_cast<const char*>(blob_dev)), blob_ld, st);
+  {      // the destination slots' pitch-control entries (a record without one turns the slot's off)
+    std::vector<conan_pitch_cfg> pts((size_t)n);
+    for (int i = 0; i < n; ++i) pts[i] = ms[i].pt;
+    s->pitch_write(slots, n, pts.data(), st);
+  }
   for (int i = 0; i < n; ++i) {
     const int slot = slots[i];
     const Meta& m = ms[i];
@@ -301,6 +310,13 @@ int meta_level(const conan_slot_meta* meta, conan_level_cfg* out) {
   const Meta m = read_meta(meta, "conan_slot_meta_level: ");
   *out = m.lv;
   return m.lv.enabled != 0;
+}
+
+int meta_pitch(const conan_slot_meta* meta, conan_pitch_cfg* out) {
+  if (!meta || !out) throw Error(CONAN_ERR_INVALID, "null argument");
+  const Meta m = read_meta(meta, "conan_slot_meta_pitch: ");
+  *out = m.pt;
+  return m.pt.enabled != 0;
 }
 
 }  // namespace snapshot

@@ -282,6 +282,14 @@ struct conan_streams {
   int* c_slen = nullptr;        // [slot]
   int* c_vqids = nullptr;       // [slot][S_max] VQ indices of the prosody tokens (-1 past the token count)
   std::vector<char> has_ref;    // per slot: conan_set_reference has run for it
+  // pitch control (pitch.hip; conan_streams_set_pitch): the kernels' table [max_slots], indexed by slot, allocated with the decoder
+  // (stream state: 24 bytes per slot, zero = disabled) and the cfgs as set (they persist across resets and travel with a snapshot).
+  // pt_stage / pt_pin: the setter's call rows on their way to the device, allocated by the first call; not stream state.
+  cnk::PitchSlot* d_ptab = nullptr;
+  std::vector<conan_pitch_cfg> pt_cfg;
+  cnk::PitchRow* pt_stage = nullptr;
+  PinRing pt_pin;
+  void pitch_write(const int32_t* slots, int n, const conan_pitch_cfg* cfgs, hipStream_t st);      // cfgs[i] -> slot slots[i], host and device
   std::vector<char> voc_fresh;  // per slot: vocoder state reset and not stepped since (voc_upsample 2 steps need it)
   // --- style pass workspace (batch indexed, max_slots_sp at a time)
   int sp_batch = 0;
@@ -386,9 +394,10 @@ struct conan_streams {
 
   // --- decoder megakernel (decoder_mega.hip): the decoder step's operator list, recorded once per (slot count, frames,
   // buffer set) and replayed as one persistent launch
-  struct DecExtra { float* mel_out2 = nullptr; int* codes_dst = nullptr; const int* codes_src = nullptr; int codes_words = 0; };
+  struct DecExtra { float* mel_out2 = nullptr; int* codes_dst = nullptr; const int* codes_src = nullptr; int codes_words = 0;
+                    const float* f0_in = nullptr; const float* uv_in = nullptr; };      // the caller's contour (conan_decoder_step_pitch)
   struct MegaProgram {
-    long long key[6] = {0, 0, 0, 0, 0, 0};
+    long long key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     bool ok = false;
     int nops = 0, groups = 0, group_size = 0, njobs = 0, kw4 = 0, lds_bytes = 0, barriers = 0, n = 0, T = 0;
     int lds_need = 0;                  // what the operators need (lds_bytes may be padded: xcd mode, blocking steps)
@@ -421,7 +430,8 @@ struct conan_streams {
   void mega_push(cnk::MegaOp& op, int lds_floats);
   bool run_mega(int n, int T, const int32_t* codes, float* mel_out, const DecExtra& ex, hipStream_t st);
   void launch_mega(MegaProgram& e, hipStream_t st);
-  void decoder_ops(int n, int frames, const int32_t* codes, float* mel_out, const conan_decoder_taps& taps, hipStream_t st);
+  void decoder_ops(int n, int frames, const int32_t* codes, float* mel_out, const conan_decoder_taps& taps, hipStream_t st, const float* f0_in = nullptr,
+                   const float* uv_in = nullptr);
   void op_embed(const cnk::EmbedArgs& a, hipStream_t st);
   void op_ln(const cnk::LNArgs& a, hipStream_t st);
   void op_xattn(const cnk::XAttnArgs& a, hipStream_t st);
@@ -496,4 +506,12 @@ void export_slots(conan_streams* s, const int32_t* slots, int n, void* blob_dev,
 void import_slots(conan_streams* s, const int32_t* slots, int n, const void* blob_dev, int64_t blob_ld, const conan_slot_meta* meta, void* stream);
 void meta_info(const conan_slot_meta* meta, conan_slot_info* out);
 int meta_level(const conan_slot_meta* meta, conan_level_cfg* out);      // 1: the record carries a leveller
+int meta_pitch(const conan_slot_meta* meta, conan_pitch_cfg* out);      // 1: the record carries a pitch control
 }  // namespace snapshot
+
+// ---- per-slot pitch control (pitch.hip): the bodies of api.hip's entry points
+namespace pitch {
+void check_cfg(const conan_pitch_cfg& c, const char* who);      // host only
+void set_pitch(conan_streams* s, const int32_t* slots, int n, const conan_pitch_cfg* cfg, void* stream);
+void get_pitch(const conan_streams* s, int slot, conan_pitch_cfg* out);
+}  // namespace pitch

@@ -866,6 +866,9 @@ void conan_streams::build_decoder() {
   const conan_cfg& c = ctx->cfg;
   const int H = c.hidden_size, F = max_frames;
   c_emb = mk_ring(H, 1, c.content_kernel - 1, &dec_state);
+  // per-slot pitch control (pitch.hip): zero = disabled.  Not in dec_state: the setting persists across resets
+  d_ptab = reinterpret_cast<cnk::PitchSlot*>(alloc((size_t)max_slots * sizeof(cnk::PitchSlot) / sizeof(float)));
+  pt_cfg.assign(max_slots, conan_pitch_cfg{});
   c_pin2 = mk_ring(H, 1, c.predictor_kernel - 1, &dec_state);
   // (uv predictor depth / width and the aligner's feed-forward width come from the checkpoint's tensors, ctx.hip finalize_conan)
   const int n_uv = (int)ctx->scalars.at("conan.uv.n"), uvh = (int)ctx->scalars.at("conan.uv.hidden"), ffn = (int)ctx->scalars.at("conan.align.ffn");

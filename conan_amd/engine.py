@@ -222,8 +222,10 @@ class StreamingVoiceConversionEngine:
         self.slots = list(range(n_streams))
         self.seg, self.rc = ctx.cfg.emf_segment, ctx.cfg.emf_right_context
 
-    def start(self, ref_mel, ref_len=None, which=7, out_rate=None, out_filter=None, out_format=None):
-        """out_rate: the sample rate the audio leaves at (None: the model rate), resampled on the GPU behind the vocoder; out_filter:
+    def start(self, ref_mel, ref_len=None, which=7, out_rate=None, out_filter=None, out_format=None, pitch=None):
+        """pitch: the slots' pitch control in the decoder step (Streams.set_pitch) - None / False: none; a dict of its keywords
+        (shift_semitones, range, pivot, uv_threshold), or a list with one per slot.
+        out_rate: the sample rate the audio leaves at (None: the model rate), resampled on the GPU behind the vocoder; out_filter:
         dict of Context.resample's filter keywords.  The steps then deliver what the filter has the inputs for, finish() the tail.
         out_format: the sample format the audio leaves in ('f32' | 's16' | 'ulaw' | 'alaw'; None: float32), encoded on the GPU."""
         if isinstance(out_rate, (list, tuple)) or isinstance(out_format, (list, tuple)):
@@ -233,18 +235,20 @@ class StreamingVoiceConversionEngine:
         self.st.set_reference(self.slots, ref_mel, ref_len)
         self._set_out_rate(self.slots, out_rate, out_filter)
         self._set_format(self.slots, out_format, self.st.output_formats, self.st.set_output_format)
+        self._set_pitch(self.slots, pitch)
 
     def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                  **filter):
+                  pitch=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
         in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
         in_format: the input's sample format (None: float32; 's16' takes int16 rows, 'ulaw' / 'alaw' uint8), decoded on the GPU.
         out_rate / out_filter / out_format: as in start().
         level: the input leveller (Streams.set_input_level) - None / False: none; True: Context.level's defaults; a dict: its
-        keywords.  It runs on the GPU on the decoded, resampled samples in front of the front-end, causally: feed() gains no latency."""
+        keywords.  It runs on the GPU on the decoded, resampled samples in front of the front-end, causally: feed() gains no latency.
+        pitch: as in start()."""
         if isinstance(in_format, (list, tuple)) or isinstance(level, (list, tuple)):
             raise ValueError("in_format / level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
-        self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format)
+        self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch)
         self._set_rate(self.slots, in_rate, filter)
         self._set_format(self.slots, in_format, self.st.input_formats, self.st.set_input_format)
         self._set_level(self.slots, level)
@@ -260,6 +264,23 @@ class StreamingVoiceConversionEngine:
                     self.st.set_input_level([slot], None)
             else:
                 self.st.set_input_level([slot], True if lv is True else dict(lv))
+
+    def _set_pitch(self, slots, pitch):
+        """The slots' pitch control (None / False: none; True: the defaults; a dict of Streams.set_pitch's keywords), one value or one
+        per slot.  Slots that never had one are left alone."""
+        pitches = list(pitch) if isinstance(pitch, (list, tuple)) else [pitch] * len(slots)
+        assert len(pitches) == len(slots), (len(pitches), len(slots))
+        for slot, pt in zip(slots, pitches):
+            if pt is None or pt is False:
+                if int(slot) in self.st.pitch_cfgs:
+                    self.st.set_pitch([slot], None)
+            else:
+                self.st.set_pitch([slot], True if pt is True else dict(pt))
+
+    def set_pitch(self, slots=None, **kw):
+        """A live change of the slots' pitch control (all slots by default) between feed / feed_ragged calls, also mid-utterance and
+        with pipelined steps in flight: Streams.set_pitch's keywords; no keyword at all turns it off.  In force from the next call."""
+        self.st.set_pitch(self.slots if slots is None else slots, dict(kw) if kw else None)
 
     @staticmethod
     def _set_format(slots, fmt, table, setter):
@@ -296,7 +317,8 @@ class StreamingVoiceConversionEngine:
 
     def import_streams(self, slots, snap):
         """Continue the streams of `snap` in `slots` of this engine (Streams.import_slots): feed, feed_ragged and finish go on where
-        the exporting engine stopped.  Rates and formats travel with the streams; the output stride follows them."""
+        the exporting engine stopped.  Rates, formats, the input leveller and the pitch control travel with the streams; the output
+        stride follows them."""
         st = self.st
         st.import_slots(slots, snap)
         self._fit_output_ld()
@@ -354,7 +376,7 @@ class StreamingVoiceConversionEngine:
 
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
-                  out_format=None, loud_norm=False, level=None, **filter):
+                  out_format=None, loud_norm=False, level=None, pitch=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
@@ -364,11 +386,11 @@ class StreamingVoiceConversionEngine:
         loud_norm: each whole source utterance is loudness-normalised at its input rate before it is fed (the reference's loud_norm;
         float32 rows only); the results are those of infer_wav(ctx.loud_norm(src_wav, rate), ...) bit for bit.
         level: the streaming input leveller (start_wav); the results are those of infer_wav(ctx.level(x, **level), ...) bit for bit,
-        x = the decoded, resampled utterance."""
+        x = the decoded, resampled utterance.  pitch: the slots' pitch control in the decoder step (start)."""
         if loud_norm:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
-                       **filter)
+                       pitch=pitch, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -395,12 +417,13 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                   **filter):
+                   pitch=None, **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
         rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
         (None: the model rate), one value or one per slot.  in_format / out_format: the slots' sample formats (None: float32), one
-        value or one per slot.  level: the slots' input leveller (start_wav), one value or a list with one per slot."""
+        value or one per slot.  level: the slots' input leveller (start_wav), one value or a list with one per slot.  pitch: the
+        slots' pitch control (start), one value or a list with one per slot."""
         self.st.reset(slots, which=7 | 8)
         self.st.set_reference(slots, ref_mel, ref_len)
         self._set_out_rate(slots, out_rate, out_filter)
@@ -409,6 +432,7 @@ class StreamingVoiceConversionEngine:
         for r, group in _by_value(slots, _per_slot(in_rate, len(slots))):
             self._set_rate(group, r, filter)
         self._set_level(slots, level)
+        self._set_pitch(slots, pitch)
 
     @torch.no_grad()
     def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None):
@@ -427,7 +451,7 @@ class StreamingVoiceConversionEngine:
 
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
-                            in_formats=None, out_formats=None, loud_norm=False, level=None, **filter):
+                            in_formats=None, out_formats=None, loud_norm=False, level=None, pitch=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -438,9 +462,11 @@ class StreamingVoiceConversionEngine:
         wav is returned at (None: the model rate).  in_formats[u] / out_formats[u]: the sample format utterance u arrives / is
         returned in (None: float32); one call then mixes formats, each row packed in its own.  loud_norm: every utterance is
         loudness-normalised whole, at its own input rate, before its first audio is fed (float32 utterances only).  level: the
-        streaming input leveller (start_wav), one value for every utterance or a list with one per utterance."""
+        streaming input leveller (start_wav), one value for every utterance or a list with one per utterance.  pitch: the pitch
+        control (start), one value for every utterance or a list with one per utterance."""
         U = len(src_wavs)
         levels = list(level) if isinstance(level, (list, tuple)) else [level] * U
+        pitches = list(pitch) if isinstance(pitch, (list, tuple)) else [pitch] * U
         ifmts, ofmts, orates, rates = (list(v) if v is not None else [None] * U for v in (in_formats, out_formats, out_rates, in_rates))
         if loud_norm:
             src_wavs = [self._loud_norm(x, rates[u], ifmts[u]) for u, x in enumerate(src_wavs)]
@@ -462,7 +488,7 @@ class StreamingVoiceConversionEngine:
             if new:
                 self.open_slots([live[u][0] for u in new], torch.stack([ref_mel[u] for u in new]), in_rate=[rates[u] for u in new],
                                 out_rate=[orates[u] for u in new], out_filter=out_filter, in_format=[ifmts[u] for u in new],
-                                out_format=[ofmts[u] for u in new], level=[levels[u] for u in new], **filter)
+                                out_format=[ofmts[u] for u in new], level=[levels[u] for u in new], pitch=[pitches[u] for u in new], **filter)
             if not live:
                 tick += 1
                 continue
@@ -537,19 +563,20 @@ class StreamingVoiceConversionEngine:
         return out + (mel[:, -seg:],) if return_mel else out
 
     @torch.no_grad()
-    def infer(self, src_mel, ref_mel, ref_len=None, pipelined=True, out_rate=None, out_filter=None, out_format=None):
+    def infer(self, src_mel, ref_mel, ref_len=None, pipelined=True, out_rate=None, out_filter=None, out_format=None, pitch=None):
         """src_mel [B,T,80], ref_mel [B,Tr,80] (cuda) -> wav [B, T*hop], mel [B,T,80], codes [B,T].
 
         The whole source is available here, so by default the chunks are issued as pipelined steps
         (conan_step_async): the Emformer + decoder of chunk t+1 overlap the vocoder of chunk t.  The
         results are bit-identical to the blocking loop (pipelined=False).  out_rate (+ out_filter): the returned wav is the
-        whole utterance at that rate, ctx.resample of the model-rate wav bit for bit.  out_format: the returned wav's sample format."""
+        whole utterance at that rate, ctx.resample of the model-rate wav bit for bit.  out_format: the returned wav's sample format.
+        pitch: the slots' pitch control in the decoder step (start)."""
         if self.ctx.cfg.voc_upsample == 2:
             if out_format not in (None, "f32"):
                 raise ValueError("out_format with an upsample 'nn' vocoder: convert the returned wav with Context.convert_samples instead")
             self._set_out_rate(self.slots, out_rate, out_filter)      # (refuses a rate; restores the model rate)
-            return self._infer_prefix_vocoder(src_mel, ref_mel, ref_len)
-        self.start(ref_mel, ref_len, out_rate=out_rate, out_filter=out_filter, out_format=out_format)
+            return self._infer_prefix_vocoder(src_mel, ref_mel, ref_len, pitch)
+        self.start(ref_mel, ref_len, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch)
         B = src_mel.shape[0]
         hop, nm = self.ctx.hop, self.ctx.cfg.num_mels
         wavs, mels, codes = [], [], []
@@ -573,7 +600,7 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     @torch.no_grad()
-    def _infer_prefix_vocoder(self, src_mel, ref_mel, ref_len=None):
+    def _infer_prefix_vocoder(self, src_mel, ref_mel, ref_len=None, pitch=None):
         """Vocoders that look ahead (`upsample: nn`, CausalUpsampleBlock1) cannot carry state from chunk to chunk; the
         reference loop does not need them to: it runs the vocoder on ALL mel frames so far and keeps the samples of the
         current chunk (inference/Conan.py:147-155).  Same here: Emformer and decoder step statefully, the vocoder is reset
@@ -583,7 +610,7 @@ class StreamingVoiceConversionEngine:
             mr = self.st.max_ref_frames
             self.st.close()
             self.st = self.ctx.streams(self.n, max_frames=T, max_ref_frames=mr, arith=self.arith, flags=self.flags, dev_plan=self.dev_plan)
-        self.start(ref_mel, ref_len)
+        self.start(ref_mel, ref_len, pitch=pitch)
         hop = self.ctx.hop
         wavs, mels, codes = [], [], []
         for pos, emit, chunk in self.chunks(src_mel):

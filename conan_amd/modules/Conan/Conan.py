@@ -1,6 +1,7 @@
 """Conan with the reference's constructor / forward / state_dict contract (modules/Conan/Conan.py:45-198),
-inference path only (infer=True, style=true, f0_gen='orig', decoder_type='conv'), computed by the HIP path:
-per-utterance style pass (conan_set_reference) + stateful decoder steps over the content codes."""
+inference path (infer=True, or infer=False with a caller contour f0= / uv=: Conan.py:174-178, :324-351; style=true, f0_gen='orig',
+decoder_type='conv'), computed by the HIP path: per-utterance style pass (conan_set_reference) + stateful decoder steps over the
+content codes."""
 import torch
 from torch import nn
 
@@ -56,8 +57,11 @@ class Conan(_tree.ParamTree):
     def forward(self, content, spk_embed=None, target=None, ref=None, f0=None, uv=None, infer=False, global_steps=0, **kwargs):
         if spk_embed is None and ref is None:
             raise ValueError("When spk_embed is None, need target tensor to extract speaker embedding.")   # Conan.py:152-155
-        if not infer:
-            raise NotImplementedError("the HIP hot path covers Conan.forward(..., infer=True) (inference/Conan.py:132-141)")
+        if infer:
+            f0, uv = None, None      # Conan.py:174-175
+        elif f0 is None:
+            raise NotImplementedError("the HIP hot path covers Conan.forward(..., infer=True) (inference/Conan.py:132-141) and "
+                                      "infer=False with a caller contour f0= (Conan.py:174-178); training-side calls are not covered")
         if ref is None:
             # the reference reaches get_prosody(pitch_inp, ref, ...) with ref=None and fails there (Conan.py:166, style: true)
             raise ValueError("ref is required: the prosody tokens are extracted from the reference mel (Conan.py:166)")
@@ -75,7 +79,8 @@ class Conan(_tree.ParamTree):
         mels, taps = [], {"uv_pred": [], "f0_denorm_pred": [], "pitch_bins": [], "decoder_inp": [], "content_embed_proj": []}
         attn = [[], []]
         for p in range(0, T, self.STEP_FRAMES):
-            m, tp = st.decoder_step(slots, codes[:, p:p + self.STEP_FRAMES], taps=True)
+            q = slice(p, p + self.STEP_FRAMES)
+            m, tp = st.decoder_step(slots, codes[:, q], taps=True, f0=None if f0 is None else f0[:, q], uv=None if uv is None else uv[:, q])
             mels.append(m)
             for k in taps:
                 taps[k].append(tp[k])
@@ -90,4 +95,8 @@ class Conan(_tree.ParamTree):
         S = (Tr + 3) // 4
         ret["attn"] = [torch.cat(a, 1)[:, :, :S].unsqueeze(1) for a in attn]
         ret["ref_upsample"] = (torch.arange(Tr, device=content.device) // 4 + 1).unsqueeze(0).expand(B, -1)
+        if f0 is not None:      # add_orig_pitch's non-infer branch (Conan.py:343-350), from the raw head output
+            nonpadding = (uv == 0).float() if uv is not None else torch.ones_like(f0, dtype=torch.float32)
+            sq = (ret["uv_pred"][:, :, 1] - f0.float()) ** 2
+            ret["fdiff"] = (sq * nonpadding).sum() / nonpadding.sum() * self.hparams.get("lambda_f0", 1.0)
         return ret

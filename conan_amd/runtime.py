@@ -267,9 +267,10 @@ class SlotSnapshot:
         return self.blob.shape[0]
 
     def info(self, i):
-        """conan_slot_meta_info of stream i: dict(layout_id, bytes, has_ref, in_format, out_format, in_rate, out_rate, level); a rate
-        is None for a stream without one; level (conan_slot_meta_level) is the input leveller's keywords as Streams.set_input_level
-        takes them, None for a stream without one."""
+        """conan_slot_meta_info of stream i: dict(layout_id, bytes, has_ref, in_format, out_format, in_rate, out_rate, level, pitch); a
+        rate is None for a stream without one; level (conan_slot_meta_level) is the input leveller's keywords as
+        Streams.set_input_level takes them, pitch (conan_slot_meta_pitch) the pitch control's as Streams.set_pitch takes them; each
+        None for a stream without one."""
         rec = _lib.SlotMeta.from_buffer_copy(self.meta[i * _lib.SLOT_META_BYTES:(i + 1) * _lib.SLOT_META_BYTES])
         out = _lib.SlotInfo()
         _lib.check(_lib.lib().conan_slot_meta_info(C.byref(rec), C.byref(out)))
@@ -278,7 +279,9 @@ class SlotSnapshot:
         level = None
         if _lib.check(_lib.lib().conan_slot_meta_level(C.byref(rec), C.byref(lv))):
             level = _lib.level_keywords(lv)
-        return dict(level=level, layout_id=int(out.layout_id), bytes=int(out.bytes), has_ref=bool(out.has_ref), in_format=names[out.in_format],
+        pt = _lib.PitchCfg()
+        pitch = _lib.pitch_keywords(pt) if _lib.check(_lib.lib().conan_slot_meta_pitch(C.byref(rec), C.byref(pt))) else None
+        return dict(level=level, pitch=pitch, layout_id=int(out.layout_id), bytes=int(out.bytes), has_ref=bool(out.has_ref), in_format=names[out.in_format],
                     out_format=names[out.out_format],
                     in_rate=out.in_rate.in_rate if out.in_rate.in_rate != out.in_rate.out_rate else None,
                     out_rate=out.out_rate.out_rate if out.out_rate.in_rate != out.out_rate.out_rate else None,
@@ -327,6 +330,7 @@ class Streams:
         self.input_formats = {}          # slot -> 's16' | 'ulaw' | 'alaw', for the slots whose wav-in rows are not float32
         self.output_formats = {}         # slot -> the same, for the slots whose audio leaves in another format
         self.input_levels = {}           # slot -> dict of set_input_level's keywords, for the slots with an input leveller
+        self.pitch_cfgs = {}             # slot -> dict of set_pitch's keywords, for the slots with a pitch control
 
     @property
     def state_bytes(self):
@@ -387,6 +391,10 @@ class Streams:
                 self.input_levels[int(slot)] = info["level"]
             else:
                 self.input_levels.pop(int(slot), None)
+            if info["pitch"] is not None:
+                self.pitch_cfgs[int(slot)] = info["pitch"]
+            else:
+                self.pitch_cfgs.pop(int(slot), None)
 
     def _release(self):
         """Buffers of pipelined steps may be dropped once the current torch stream waits for the library's internal
@@ -457,6 +465,36 @@ class Streams:
                 self.input_levels[int(slot)] = _lib.level_keywords(c)
             else:
                 self.input_levels.pop(int(slot), None)
+
+    def set_pitch(self, slots, cfg=True, **kw):
+        """conan_streams_set_pitch: the slots' pitch control in the decoder step - shift_semitones (a key change), range (the
+        contour's excursion around `pivot`, log2 Hz: 1 unchanged, 0 monotone), uv_threshold (a frame is unvoiced when the head's d0
+        exceeds it: +inf voices every frame whose code is not the silent token, -inf whispers) - as keywords or as a dict in cfg;
+        those not given keep _lib.pitch_cfg's defaults.  Only cfg=None turns it off.  It may be called at any time, also
+        mid-utterance (it joins pipelined work); the change takes effect from the next step and survives resets."""
+        a, p = _i32(slots)
+        if cfg is None:
+            if kw:
+                raise ValueError("set_pitch: cfg=None turns the pitch control off and takes no keywords")
+            c = _lib.PitchCfg()      # (enabled = 0)
+        else:
+            c = _lib.pitch_cfg(**dict({} if cfg is True else cfg, **kw))
+        _lib.check(self.lib.conan_streams_set_pitch(self.h, p, len(a), C.byref(c), _stream()))
+        self._release()
+        for slot in a:
+            if c.enabled:
+                self.pitch_cfgs[int(slot)] = _lib.pitch_keywords(c)
+            else:
+                self.pitch_cfgs.pop(int(slot), None)
+
+    def pitch(self, slots):
+        """conan_streams_pitch: per slot the pitch control's keywords as set_pitch takes them, None for a slot without one."""
+        out = []
+        for slot in slots:
+            c = _lib.PitchCfg()
+            _lib.check(self.lib.conan_streams_pitch(self.h, int(slot), C.byref(c)))
+            out.append(_lib.pitch_keywords(c) if c.enabled else None)
+        return out
 
     def input_level(self, slots):
         """conan_streams_input_level: float64 [n, 4] (cuda) rows (L_k, G_k, P_k, J_k) of the slots' latest update instants - the
@@ -607,15 +645,26 @@ class Streams:
         self._release()
         return y.reshape(*x.shape[:-1], K)
 
-    def decoder_step(self, slots, codes, taps=False):
+    def decoder_step(self, slots, codes, taps=False, f0=None, uv=None):
+        """codes [n, T] -> mel [n, T, 80] (+ the taps dict).  f0 [n, T] (log2 Hz, the reference's norm_f0) / uv [n, T] (> 0: unvoiced;
+        None: voiced): the caller's contour instead of the predictor's (conan_decoder_step_pitch; Conan.forward(f0=, uv=,
+        infer=False)); the slots' pitch control (set_pitch) applies on top of it."""
         a, p = _i32(slots)
         n = len(a)
         c = self.ctx.cfg
         codes = codes.to(self.dev, torch.int32).contiguous()
         T = codes.shape[1]
         mel = torch.empty(n, T, c.num_mels, device=self.dev)
+        if f0 is None and uv is not None:
+            raise ValueError("decoder_step: uv without f0 (the reference ignores both unless f0 is given)")
+        if f0 is not None:
+            f0 = f0.to(self.dev, torch.float32).reshape(n, T).contiguous()
+            uv = uv.to(self.dev, torch.float32).reshape(n, T).contiguous() if uv is not None else None
         if not taps:
-            _lib.check(self.lib.conan_decoder_step(self.h, p, n, T, _ptr(codes), _ptr(mel), None, None, None, None, _stream()))
+            if f0 is not None:
+                _lib.check(self.lib.conan_decoder_step_pitch(self.h, p, n, T, _ptr(codes), _ptr(f0), _ptr(uv), _ptr(mel), None, _stream()))
+            else:
+                _lib.check(self.lib.conan_decoder_step(self.h, p, n, T, _ptr(codes), _ptr(mel), None, None, None, None, _stream()))
             self._release()
             return mel
         S = (self.max_ref_frames + 3) // 4 if self.max_ref_frames >= 4 else 1
@@ -628,7 +677,10 @@ class Streams:
         t.uv_pred, t.f0_denorm_pred, t.pitch_bins = out["uv_pred"].data_ptr(), out["f0_denorm_pred"].data_ptr(), out["pitch_bins"].data_ptr()
         t.decoder_inp, t.content_embed_proj = out["decoder_inp"].data_ptr(), out["content_embed_proj"].data_ptr()
         t.attn[0], t.attn[1] = out["attn"][0].data_ptr(), out["attn"][1].data_ptr()
-        _lib.check(self.lib.conan_decoder_step_taps(self.h, p, n, T, _ptr(codes), _ptr(mel), C.byref(t), _stream()))
+        if f0 is not None:
+            _lib.check(self.lib.conan_decoder_step_pitch(self.h, p, n, T, _ptr(codes), _ptr(f0), _ptr(uv), _ptr(mel), C.byref(t), _stream()))
+        else:
+            _lib.check(self.lib.conan_decoder_step_taps(self.h, p, n, T, _ptr(codes), _ptr(mel), C.byref(t), _stream()))
         self._release()
         return mel, out
 

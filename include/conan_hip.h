@@ -709,6 +709,52 @@ int conan_slot_meta_info(const conan_slot_meta* meta, conan_slot_info* out);   /
  * CONAN_ERR_INVALID for a record that is not one, as conan_slot_meta_info. */
 int conan_slot_meta_level(const conan_slot_meta* meta, conan_level_cfg* out);
 
+/* Per-slot pitch control in the decoder step (added within ABI 9: a caller detects it by the exported symbols; no existing struct
+ * changes).  The decoder step ends its pitch head as the reference's add_orig_pitch -> denorm_f0 -> f0_to_coarse -> pitch_embed chain
+ * does (modules/Conan/Conan.py:324-351, utils/audio/pitch/utils.py:71-82, :17-28).  A slot can transpose the contour, scale its
+ * excursion and move the voicing threshold, and a decoder step can take the caller's normalised contour instead of the predictor's -
+ * the reference's Conan.forward(f0=, uv=, infer=False) (Conan.py:174-178).  This comment defines the law (tests/pitch_ref.py restates it
+ * in numpy).  Per frame row of slot k, (d0, d1) = the uv / f0 head's output; the uv_pred tap keeps reporting it raw, as ret['uv_pred'].
+ *   Source of v and uv.  With a caller contour (conan_decoder_step_pitch, f0_in_dev != NULL): v = f0_in, uv = uv_in > 0 (uv_in_dev
+ *     NULL: voiced) - no silent-token forcing, the reference's non-infer branch.  Otherwise v = d1 and
+ *     uv = (d0 > thr) || code == silent_token, thr = uv_threshold of an enabled slot, 0 of a disabled one.
+ *   Disabled slot (enabled = 0): exactly the arithmetic and the bits of a library without this feature.
+ *   Enabled slot, in f32: if range != 1 then v = fmaf(range, v - pivot, pivot); then v = v + shift_oct, with
+ *     shift_oct = (float)((double)shift_semitones / 12.0) formed once on the host.
+ *   Then, as ever: f0 = fminf(fmaxf(exp2f(v), 50), 900); uv -> f0 = 0; the mel-scale bin of f0_to_coarse;
+ *     decoder_inp = pitch_inp + pitch_embed[bin].  The fmaxf / fminf order sends a NaN to 50 Hz: the bin is in 1 .. 255 for every
+ *     float input.
+ * The taps f0_denorm_pred and pitch_bins report the values after the law. */
+typedef struct conan_pitch_cfg {
+  int32_t enabled;          /* 0: today's path for the slots, other fields ignored */
+  float   shift_semitones;  /* finite, |.| <= 48 */
+  float   range;            /* finite, 0 .. 4: scales the contour's excursion around pivot (1: unchanged, 0: monotone) */
+  float   pivot;            /* log2 Hz, finite; the contour value that `range` leaves in place */
+  float   uv_threshold;     /* frame is unvoiced when d0 > uv_threshold (model: 0; +inf: voiced wherever the code is not the silent
+                               token; -inf: all unvoiced); NaN refused */
+  int32_t reserved;         /* must be 0 */
+} conan_pitch_cfg;          /* 24 bytes */
+/* Sets the pitch control of `slots`.  It may be called at any time, also mid-utterance; every slot and the cfg are checked before
+ * anything changes.  It joins pending pipelined work, then updates a per-slot device table [max_slots] - indexed by slot, not by call
+ * row - in the order of `stream`; the change takes effect from the next step of every entry point that runs a decoder step
+ * (conan_decoder_step[_taps / _pitch], conan_step[_async], conan_step_wav[_async], conan_step_wav_ragged[_ld][_async]).  The setting
+ * persists across resets.  The table is allocated with the stream-set (24 bytes per slot, part of conan_streams_state_bytes) and
+ * initialised to disabled; a stream-set that never calls the setter runs the launches it ran before.  Slot snapshots carry the cfg in
+ * the host record: conan_streams_import_slots writes the destination slots' entries (a record without one - every record written
+ * before this existed - turns the destination's off); the layout id, blob rows and conan_streams_snapshot_bytes are unchanged. */
+int conan_streams_set_pitch(conan_streams* s, const int32_t* slots, int n, const conan_pitch_cfg* cfg, void* stream);
+/* Host only: the cfg of `slot` as set (enabled = 0 and zeros for a slot without one). */
+int conan_streams_pitch(const conan_streams* s, int slot, conan_pitch_cfg* out);
+/* conan_decoder_step_taps with a caller contour: f0_in_dev[n][frames] in log2 Hz (the reference's norm_f0 with pitch_norm 'log'),
+ * uv_in_dev[n][frames] (> 0: unvoiced; may be NULL: all voiced) - Conan.forward(content, ref=, f0=, uv=, infer=False).  The slots'
+ * pitch control applies on top of the contour.  f0_in_dev == NULL is conan_decoder_step_taps (uv_in_dev is then ignored); taps may be
+ * NULL.  The fused chunk steps take no contour: they replace the loop of inference/Conan.py, which passes f0=None. */
+int conan_decoder_step_pitch(conan_streams* s, const int32_t* slots, int n, int frames, const int32_t* codes_dev, const float* f0_in_dev,
+                             const float* uv_in_dev, float* mel_out_dev, const conan_decoder_taps* taps, void* stream);
+/* Host only, no handle: the pitch control a record carries -> 1 and *out = its cfg, or 0 and *out zeroed for a record without one.
+ * CONAN_ERR_INVALID for a record that is not one, as conan_slot_meta_info. */
+int conan_slot_meta_pitch(const conan_slot_meta* meta, conan_pitch_cfg* out);
+
 #ifdef __cplusplus
 }
 #endif
