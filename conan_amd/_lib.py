@@ -138,6 +138,18 @@ _PROTOS = {
     "conan_decoder_step_pitch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
     "conan_slot_meta_pitch": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "conan_voices_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "conan_voices_destroy": (C.c_int, [C.c_void_p]),
+    "conan_voices_enroll": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "conan_voices_remove": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "conan_voices_info": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "conan_streams_set_voice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_streams_set_voice_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "conan_streams_voice": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
+    "conan_voices_blob_bytes": (C.c_int64, [C.c_void_p]),
+    "conan_voices_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "conan_voices_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "conan_voice_meta_info": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -245,6 +257,21 @@ class SlotInfo(C.Structure):
     """conan_slot_info (include/conan_hip.h): what a caller may read out of a conan_slot_meta."""
     _fields_ = [("layout_id", C.c_uint64), ("bytes", C.c_int64), ("has_ref", C.c_int32), ("in_format", C.c_int32),
                 ("out_format", C.c_int32), ("reserved", C.c_int32), ("in_rate", ResampleCfg), ("out_rate", ResampleCfg)]
+
+
+VOICE_META_BYTES = 256
+VOICE_MAX_MIX = 4      # voices conan_streams_set_voice_mix blends into one style vector
+
+
+class VoiceMeta(C.Structure):
+    """conan_voice_meta (include/conan_hip.h): the host half of an exported voice, opaque."""
+    _fields_ = [("opaque", C.c_ubyte * VOICE_META_BYTES)]
+
+
+class VoiceInfo(C.Structure):
+    """conan_voice_info (include/conan_hip.h): a bank entry, or what a caller may read out of a conan_voice_meta."""
+    _fields_ = [("enrolled", C.c_int32), ("ref_frames", C.c_int32), ("tokens", C.c_int32), ("reserved", C.c_int32),
+                ("bytes", C.c_int64), ("layout_id", C.c_uint64)]
 
 
 class LoudnessCfg(C.Structure):

@@ -295,7 +295,7 @@ int conan_streams_create_opts(conan_ctx* ctx, int max_slots, int max_frames, int
         s->d_guard = reinterpret_cast<unsigned*>(s->alloc(16));
         HIP_CHECK(hipMemcpy(s->d_guard + 2, &hdev, sizeof(hdev), hipMemcpyHostToDevice));
       }
-      s->slot_seen.assign(max_slots, 0); s->has_ref.assign(max_slots, 0); s->voc_fresh.assign(max_slots, 1); s->wav_out.voc_samples.assign(max_slots, 0); s->wav_in.in_fmt.assign(max_slots, 0); s->wav_out.out_fmt.assign(max_slots, 0);
+      s->slot_seen.assign(max_slots, 0); s->has_ref.assign(max_slots, 0); s->voice_of.assign(max_slots, -1); s->voc_fresh.assign(max_slots, 1); s->wav_out.voc_samples.assign(max_slots, 0); s->wav_in.in_fmt.assign(max_slots, 0); s->wav_out.out_fmt.assign(max_slots, 0);
       s->pin.init((size_t)max_slots + cnk::kSlotTablePad);
       s->pos_emf = (int*)s->alloc(max_slots); s->pos_dec = (int*)s->alloc(max_slots); s->pos_voc = (int*)s->alloc(max_slots);
       std::vector<int> id(max_slots);
@@ -487,6 +487,7 @@ int conan_set_style(conan_streams* s, const int32_t* slots, int n, const float* 
     for (int i = 0; i < n; ++i)
       if (!s->has_ref[slots[i]]) throw Error(CONAN_ERR_STATE, "conan_set_style before conan_set_reference (the prosody tokens come from the reference mel)");
     cnk::launch_scatter_rows(s->c_style, style_dev, s->d_slots, n, s->ctx->cfg.hidden_size, (hipStream_t)stream);
+    for (int i = 0; i < n; ++i) s->voice_of[slots[i]] = -1;
   });
 }
 
@@ -860,5 +861,33 @@ int conan_slot_meta_pitch(const conan_slot_meta* meta, conan_pitch_cfg* out) {
   const int rc = guarded([&] { has = snapshot::meta_pitch(meta, out); });
   return rc < 0 ? rc : has;
 }
+
+// ---- voice bank (voices.hip)
+int conan_voices_create(conan_ctx* ctx, int capacity, int max_ref_frames, conan_voices** out) { return guarded([&] { voices::create(ctx, capacity, max_ref_frames, out); }); }
+int conan_voices_destroy(conan_voices* v) { return guarded([&] { voices::destroy(v); }); }
+int conan_voices_enroll(conan_voices* v, conan_streams* via, const int32_t* ids, int n, const float* ref_mel_dev, const int32_t* ref_len, int max_len, void* stream) {
+  return guarded([&] { voices::enroll(v, via, ids, n, ref_mel_dev, ref_len, max_len, stream); });
+}
+int conan_voices_remove(conan_voices* v, const int32_t* ids, int n) { return guarded([&] { voices::remove(v, ids, n); }); }
+int conan_voices_info(const conan_voices* v, int id, conan_voice_info* out) { return guarded([&] { voices::info(v, id, out); }); }
+int conan_streams_set_voice(conan_streams* s, const int32_t* slots, int n, const conan_voices* v, const int32_t* voice_ids, void* stream) {
+  return guarded([&] { voices::set_voice(s, slots, n, v, voice_ids, nullptr, 1, false, stream); });
+}
+int conan_streams_set_voice_mix(conan_streams* s, const int32_t* slots, int n, const conan_voices* v, const int32_t* voice_ids, const float* weights, int k, void* stream) {
+  return guarded([&] { voices::set_voice(s, slots, n, v, voice_ids, weights, k, true, stream); });
+}
+int conan_streams_voice(const conan_streams* s, int slot, int32_t* voice_id) { return guarded([&] { voices::get_voice(s, slot, voice_id); }); }
+int64_t conan_voices_blob_bytes(const conan_voices* v) {
+  int64_t b = 0;
+  const int rc = guarded([&] { b = voices::blob_bytes(v); });
+  return rc < 0 ? rc : b;
+}
+int conan_voices_export(conan_voices* v, const int32_t* ids, int n, void* blob_dev, int64_t blob_ld_bytes, conan_voice_meta* meta_host, void* stream) {
+  return guarded([&] { voices::export_voices(v, ids, n, blob_dev, blob_ld_bytes, meta_host, stream); });
+}
+int conan_voices_import(conan_voices* v, const int32_t* ids, int n, const void* blob_dev, int64_t blob_ld_bytes, const conan_voice_meta* meta_host, void* stream) {
+  return guarded([&] { voices::import_voices(v, ids, n, blob_dev, blob_ld_bytes, meta_host, stream); });
+}
+int conan_voice_meta_info(const conan_voice_meta* meta, conan_voice_info* out) { return guarded([&] { voices::meta_info(meta, out); }); }
 
 }  // extern "C"

@@ -423,16 +423,25 @@ void conan_streams::conv_blocks_noncausal(const std::string& name, int nblocks, 
 }
 
 void conan_streams::set_reference(const int32_t* slots, int n_all, const float* ref, const int32_t* ref_len, int max_len, hipStream_t st) {
-  const conan_cfg& c = ctx->cfg;
-  const int H = c.hidden_size, NM = c.num_mels;
   for (int i = 0; i < n_all; ++i)
     if (ref_len[i] <= 0 || ref_len[i] > max_len || ref_len[i] > max_ref) throw Error(CONAN_ERR_INVALID, "reference length out of range");
   // (fixed-plan stream-sets: one slot per pass - the batch's longest reference sets every conv's row count, and with it the plan)
+  style_pass(style_cache(), true, slots, n_all, fixed_plan ? 1 : sp_batch, ref, ref_len, max_len, st);
+}
+
+void conan_streams::style_pass(const voice::Cache& dst, bool own, const int32_t* index, int n_all, int batch, const float* ref, const int32_t* ref_len, int max_len,
+                               hipStream_t st) {
+  const conan_cfg& c = ctx->cfg;
+  const int H = c.hidden_size, NM = c.num_mels;
   struct StyleScope { bool& f; StyleScope(bool& x) : f(x) { f = true; } ~StyleScope() { f = false; } } style_scope(in_style_pass);
-  const int batch = fixed_plan ? 1 : sp_batch;
   for (int b0 = 0; b0 < n_all; b0 += batch) {
     const int n = std::min(batch, n_all - b0);
-    set_slots(slots + b0, n, st);
+    if (own) set_slots(index + b0, n, st);
+    else {      // a bank's entries: the index list takes the slot table's place (the next set_slots uploads its own again)
+      h_slots.clear();
+      std::vector<int> up(index + b0, index + b0 + n); up.resize((size_t)n + cnk::kSlotTablePad, up.back());
+      pin.upload(d_slots, up.data(), up.size(), st);
+    }
     std::vector<int> lens(ref_len + b0, ref_len + b0 + n), lens2(n);
     int T = 0;
     for (int i = 0; i < n; ++i) { T = std::max(T, lens[i]); lens2[i] = (lens[i] + 3) / 4; }
@@ -467,7 +476,7 @@ void conan_streams::set_reference(const int32_t* slots, int n_all, const float* 
       a.slots = nullptr; a.lens = d_lens; a.m1 = s_np.ref(PADR); a.has_m1 = 1;
       conv(a, st);
       cnk::MeanArgs m; memset(&m, 0, sizeof(m));
-      m.x = s_x[cur ^ 1].ref(PADR); m.m = s_np.ref(PADR); m.out = c_style; m.out_stride = H; m.slots = d_slots; m.lens = d_lens; m.T = T; m.n = n; m.C = H;
+      m.x = s_x[cur ^ 1].ref(PADR); m.m = s_np.ref(PADR); m.out = dst.style; m.out_stride = H; m.slots = d_slots; m.lens = d_lens; m.T = T; m.n = n; m.C = H;
       cnk::launch_masked_mean(m, st);
     }
     // ---- local prosody tokens: LocalStyleAdaptor (prosody_util.py:183-200)
@@ -506,18 +515,18 @@ void conan_streams::set_reference(const int32_t* slots, int n_all, const float* 
       cnk::launch_vq(a, st);
     }
     { ConvArgs a = mk(ctx->conv("conan.l1"), s_cat.ref(PADR), s_tok.ref(PADR), n, S, nullptr); a.slots = nullptr; a.lens = d_lens2; conv(a, st); }
-    { cnk::KMaskArgs a; memset(&a, 0, sizeof(a)); a.tok = s_tok.ref(PADR); a.kmask = c_kmask; a.kmask_stride = S_max; a.slots = d_slots; a.lens = d_lens2; a.S = S; a.n = n; a.S_max = S_max;
+    { cnk::KMaskArgs a; memset(&a, 0, sizeof(a)); a.tok = s_tok.ref(PADR); a.kmask = dst.kmask; a.kmask_stride = dst.S_max; a.slots = d_slots; a.lens = d_lens2; a.S = S; a.n = n; a.S_max = dst.S_max;
       cnk::launch_kmask(a, st); }
-    cnk::launch_scatter_int(c_slen, d_slots, d_lens2, n, st);
-    cnk::launch_scatter_ids(c_vqids, d_slots, s_ids, d_lens2, n, S_max, st);
+    cnk::launch_scatter_int(dst.slen, d_slots, d_lens2, n, st);
+    cnk::launch_scatter_ids(dst.vqids, d_slots, s_ids, d_lens2, n, dst.S_max, S_max, st);
     // ---- K/V of the two aligner layers, cached per slot
     for (int l = 0; l < 2; ++l) {
-      TRef y; y.base = c_kv + (size_t)l * S_max * 2 * H; y.slot_stride = (long long)2 * S_max * 2 * H; y.C = 2 * H;
-      y.lmask = ch::next_pow2(S_max) - 1; y.rate = 0; y.off = 0; y.mode = 0; y.pad_ = 0;
+      TRef y; y.base = dst.kv + (size_t)l * dst.S_max * 2 * H; y.slot_stride = (long long)2 * dst.S_max * 2 * H; y.C = 2 * H;
+      y.lmask = ch::next_pow2(dst.S_max) - 1; y.rate = 0; y.off = 0; y.mode = 0; y.pad_ = 0;
       ConvArgs a = mk(ctx->conv("conan.align." + std::to_string(l) + ".kv"), s_tok.ref(PADR), y, n, S, nullptr);
       a.slots = d_slots; a.lens = d_lens2;
       conv(a, st);
     }
-    for (int i = 0; i < n; ++i) has_ref[slots[b0 + i]] = 1;
+    if (own) for (int i = 0; i < n; ++i) { has_ref[index[b0 + i]] = 1; voice_of[index[b0 + i]] = -1; }
   }
 }

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "voice_layout.h"
+
 namespace cnk {
 
 // Developer switches read from the ENVIRONMENT exist only in `make DEV=1` builds (CONAN_DEV_SWITCHES): the shipped library reads
@@ -513,7 +515,7 @@ void launch_fill_int(int* p, const int* slots, int n, int value, hipStream_t st)
 void launch_copy_int_rows(int* dst, const int* src, int n, int T, int S, hipStream_t st);
 void launch_profile_mark(hipStream_t st);
 void launch_scatter_int(int* dst, const int* slots, const int* src, int n, hipStream_t st);
-void launch_scatter_ids(int* dst, const int* slots, const int* src, const int* lens, int n, int S_max, hipStream_t st);   // dst[slot][s] = s < lens[i] ? src[i][s] : -1
+void launch_scatter_ids(int* dst, const int* slots, const int* src, const int* lens, int n, int S_max, int src_ld, hipStream_t st);   // dst[slot][s] = s < lens[i] ? src[i][s] : -1 (rows of dst S_max, of src src_ld ints)
 void launch_gather_ids(int* dst, int* cnt, const int* src, const int* slen, const int* slots, int n, int S_max, hipStream_t st);
 void launch_scatter_rows(float* dst, const float* src, const int* slots, int n, int C, hipStream_t st);   // dst[slots[i]][:] = src[i][:]
 void launch_zero_slots(float* base, long long slot_stride, long long count, const int* slots, int n, hipStream_t st);
@@ -753,5 +755,10 @@ struct MeanArgs { TRef x; TRef m; float* out; long long out_stride; const int* s
 void launch_masked_mean(const MeanArgs& a, hipStream_t st);
 struct ScaleMaskArgs { TRef x; TRef m; const int* lens; int T, n, C; };           // x *= m (in place)
 void launch_mul_mask(const ScaleMaskArgs& a, hipStream_t st);
+
+// ---- voice bank (voices.hip; the cell functions are voice_layout.h's).  Grid (work items, call rows), 256 lanes.
+__global__ void voice_assign_kernel(const voice::Cache dst, const voice::Cache bank, const voice::AssignRow* __restrict__ rows, int k);      // voice::fill_items(dst) items
+__global__ void voice_unpack_kernel(const voice::Cache bank, const voice::MoveRow* __restrict__ rows, const char* __restrict__ blob, long long blob_ld);
+__global__ void voice_pack_kernel(const voice::Cache bank, const voice::MoveRow* __restrict__ rows, char* __restrict__ blob, long long blob_ld);      // voice::pack_items items
 
 }  // namespace cnk

@@ -475,13 +475,13 @@ __global__ void scatter_int_kernel(int* dst, const int* slots, const int* src, i
 }
 __global__ void profile_mark_kernel() {}
 void launch_profile_mark(hipStream_t st) { hipLaunchKernelGGL(profile_mark_kernel, dim3(1), dim3(64), 0, st); }
-__global__ void scatter_ids_kernel(int* dst, const int* slots, const int* src, const int* lens, int n, int S_max) {
+__global__ void scatter_ids_kernel(int* dst, const int* slots, const int* src, const int* lens, int n, int S_max, int src_ld) {
   const int i = blockIdx.y, s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s < S_max) dst[(long long)slots[i] * S_max + s] = s < lens[i] ? src[(long long)i * S_max + s] : -1;
+  if (s < S_max) dst[(long long)slots[i] * S_max + s] = s < lens[i] ? src[(long long)i * src_ld + s] : -1;
 }
-void launch_scatter_ids(int* dst, const int* slots, const int* src, const int* lens, int n, int S_max, hipStream_t st) {
+void launch_scatter_ids(int* dst, const int* slots, const int* src, const int* lens, int n, int S_max, int src_ld, hipStream_t st) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(scatter_ids_kernel, dim3((S_max + 63) / 64, n), dim3(64), 0, st, dst, slots, src, lens, n, S_max);
+  hipLaunchKernelGGL(scatter_ids_kernel, dim3((S_max + 63) / 64, n), dim3(64), 0, st, dst, slots, src, lens, n, S_max, src_ld);
 }
 __global__ void gather_ids_kernel(int* dst, int* cnt, const int* src, const int* slen, const int* slots, int n, int S_max) {
   const int i = blockIdx.y, s = blockIdx.x * blockDim.x + threadIdx.x;

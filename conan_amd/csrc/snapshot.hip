@@ -275,7 +275,7 @@ void import_slots(conan_streams* s, const int32_t* slots, int n, const void* blo
   for (int i = 0; i < n; ++i) {
     const int slot = slots[i];
     const Meta& m = ms[i];
-    s->has_ref[slot] = (char)m.has_ref; s->voc_fresh[slot] = (char)m.voc_fresh; s->wav_out.voc_samples[slot] = m.voc_samples;
+    s->has_ref[slot] = (char)m.has_ref; s->voice_of[slot] = -1; s->voc_fresh[slot] = (char)m.voc_fresh; s->wav_out.voc_samples[slot] = m.voc_samples;
     wavio::store_format(s->wav_in.in_fmt, s->wav_in.in_fmt_n, &slot, 1, m.in_fmt);
     wavio::store_format(s->wav_out.out_fmt, s->wav_out.out_fmt_n, &slot, 1, m.out_fmt);
     conan_streams::FeSlot f; f.recv = m.fe_recv; f.frames = m.fe_frames; f.chunks = m.fe_chunks; f.phase = m.fe_phase;

@@ -5,6 +5,7 @@
 
 #include "host_common.h"
 #include "snapshot_layout.h"
+#include "voice_layout.h"
 
 using ch::Error;
 using ch::Lin;
@@ -281,7 +282,12 @@ struct conan_streams {
   float* c_kmask = nullptr;     // [slot][S_max]
   int* c_slen = nullptr;        // [slot]
   int* c_vqids = nullptr;       // [slot][S_max] VQ indices of the prosody tokens (-1 past the token count)
-  std::vector<char> has_ref;    // per slot: conan_set_reference has run for it
+  std::vector<char> has_ref;    // per slot: conan_set_reference has run for it (or conan_streams_set_voice)
+  // voice bank (voices.hip): the id last assigned whole to the slot (conan_streams_voice; -1: none, or overwritten since), and the
+  // setter's call rows on their way to the device (allocated by the first call; not stream state)
+  std::vector<int> voice_of;
+  StageSets<std::array<int, sizeof(voice::AssignRow) / sizeof(int)>> voice_sets;
+  voice::Cache style_cache() const { return voice::Cache{c_style, c_kv, c_kmask, c_slen, c_vqids, S_max, ctx->cfg.hidden_size}; }
   // pitch control (pitch.hip; conan_streams_set_pitch): the kernels' table [max_slots], indexed by slot, allocated with the decoder
   // (stream state: 24 bytes per slot, zero = disabled) and the cfgs as set (they persist across resets and travel with a snapshot).
   // pt_stage / pt_pin: the setter's call rows on their way to the device, allocated by the first call; not stream state.
@@ -443,6 +449,9 @@ struct conan_streams {
   void emformer_step(int n, const float* chunk, float* out, float* logits, int32_t* codes, hipStream_t st);
   void decoder_step(int n, int frames, const int32_t* codes, float* mel_out, const conan_decoder_taps& taps, hipStream_t st, const DecExtra* extra = nullptr);
   void set_reference(const int32_t* slots, int n, const float* ref, const int32_t* ref_len, int max_len, hipStream_t st);
+  // The style pass behind conan_set_reference, writing entries index[i] of `dst`: this stream-set's own slots (own: the index list goes
+  // through set_slots, `batch` references per pass) or a voice bank's entries (conan_voices_enroll: batch 1).
+  void style_pass(const voice::Cache& dst, bool own, const int32_t* index, int n, int batch, const float* ref, const int32_t* ref_len, int max_len, hipStream_t st);
   void conv_blocks_noncausal(const std::string& name, int nblocks, int k, int C, Lin* x, Lin& ln, Lin& h, Lin& blkm, const TRef& npm,
                              const int* lens, int n, int T, int& cur, hipStream_t st);
 };
@@ -508,6 +517,21 @@ void meta_info(const conan_slot_meta* meta, conan_slot_info* out);
 int meta_level(const conan_slot_meta* meta, conan_level_cfg* out);      // 1: the record carries a leveller
 int meta_pitch(const conan_slot_meta* meta, conan_pitch_cfg* out);      // 1: the record carries a pitch control
 }  // namespace snapshot
+
+// ---- voice bank (voices.hip): the bodies of api.hip's entry points
+namespace voices {
+void create(conan_ctx* ctx, int capacity, int max_ref_frames, conan_voices** out);
+void destroy(conan_voices* v);
+void enroll(conan_voices* v, conan_streams* via, const int32_t* ids, int n, const float* ref_mel_dev, const int32_t* ref_len, int max_len, void* stream);
+void remove(conan_voices* v, const int32_t* ids, int n);
+void info(const conan_voices* v, int id, conan_voice_info* out);
+void set_voice(conan_streams* s, const int32_t* slots, int n, const conan_voices* v, const int32_t* voice_ids, const float* weights, int k, bool mix, void* stream);
+void get_voice(const conan_streams* s, int slot, int32_t* voice_id);
+int64_t blob_bytes(const conan_voices* v);
+void export_voices(conan_voices* v, const int32_t* ids, int n, void* blob_dev, int64_t blob_ld, conan_voice_meta* meta, void* stream);
+void import_voices(conan_voices* v, const int32_t* ids, int n, const void* blob_dev, int64_t blob_ld, const conan_voice_meta* meta, void* stream);
+void meta_info(const conan_voice_meta* meta, conan_voice_info* out);
+}  // namespace voices
 
 // ---- per-slot pitch control (pitch.hip): the bodies of api.hip's entry points
 namespace pitch {

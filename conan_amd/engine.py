@@ -222,8 +222,36 @@ class StreamingVoiceConversionEngine:
         self.slots = list(range(n_streams))
         self.seg, self.rc = ctx.cfg.emf_segment, ctx.cfg.emf_right_context
 
-    def start(self, ref_mel, ref_len=None, which=7, out_rate=None, out_filter=None, out_format=None, pitch=None):
-        """pitch: the slots' pitch control in the decoder step (Streams.set_pitch) - None / False: none; a dict of its keywords
+    @staticmethod
+    def _check_voice(ref_mel, voice):
+        """Exactly one of ref_mel and voice = (bank, ids) names the target voices; -> (bank, ids) or None.  Host only."""
+        if (ref_mel is None) == (voice is None):
+            raise ValueError("give either ref_mel (a style pass per slot: Streams.set_reference) or voice=(bank, ids) (enrolled voices: "
+                             "Streams.set_voice), not both and not neither")
+        if voice is None:
+            return None
+        bank, ids = voice
+        return bank, [int(i) for i in ids]
+
+    def _reference(self, slots, ref_mel, ref_len, voice):
+        """The slots' target voices: a style pass of ref_mel, or voice = (bank, ids), one enrolled id per slot."""
+        voice = self._check_voice(ref_mel, voice)
+        if voice is None:
+            self.st.set_reference(slots, ref_mel, ref_len)
+        else:
+            self.st.set_voice(slots, voice[0], voice[1])
+
+    def set_voice(self, slots=None, bank=None, ids=None):
+        """A live change of the slots' target voice (all slots by default) to the enrolled voices `ids` of `bank`, between feed /
+        feed_ragged calls, also mid-utterance and with pipelined steps in flight (Streams.set_voice: one launch, no style pass).
+        Steps already enqueued keep the old voice; in force from the next call."""
+        if bank is None or ids is None:
+            raise ValueError("set_voice: bank= and ids= are required")
+        self.st.set_voice(self.slots if slots is None else slots, bank, ids)
+
+    def start(self, ref_mel, ref_len=None, which=7, out_rate=None, out_filter=None, out_format=None, pitch=None, voice=None):
+        """voice: (bank, ids) - enrolled voices of a runtime.VoiceBank, one id per slot, in place of ref_mel (then None).
+        pitch: the slots' pitch control in the decoder step (Streams.set_pitch) - None / False: none; a dict of its keywords
         (shift_semitones, range, pivot, uv_threshold), or a list with one per slot.
         out_rate: the sample rate the audio leaves at (None: the model rate), resampled on the GPU behind the vocoder; out_filter:
         dict of Context.resample's filter keywords.  The steps then deliver what the filter has the inputs for, finish() the tail.
@@ -231,24 +259,26 @@ class StreamingVoiceConversionEngine:
         if isinstance(out_rate, (list, tuple)) or isinstance(out_format, (list, tuple)):
             raise ValueError("out_rate / out_format: one value for all slots here (feed / infer return one [B, count] block); open_slots and "
                              "infer_wav_staggered take one per slot / utterance")
+        self._check_voice(ref_mel, voice)
         self.st.reset(self.slots, which=which)
-        self.st.set_reference(self.slots, ref_mel, ref_len)
+        self._reference(self.slots, ref_mel, ref_len, voice)
         self._set_out_rate(self.slots, out_rate, out_filter)
         self._set_format(self.slots, out_format, self.st.output_formats, self.st.set_output_format)
         self._set_pitch(self.slots, pitch)
 
     def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                  pitch=None, **filter):
+                  pitch=None, voice=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
         in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
         in_format: the input's sample format (None: float32; 's16' takes int16 rows, 'ulaw' / 'alaw' uint8), decoded on the GPU.
         out_rate / out_filter / out_format: as in start().
         level: the input leveller (Streams.set_input_level) - None / False: none; True: Context.level's defaults; a dict: its
         keywords.  It runs on the GPU on the decoded, resampled samples in front of the front-end, causally: feed() gains no latency.
-        pitch: as in start()."""
+        pitch, voice: as in start()."""
+        self._check_voice(ref_mel, voice)
         if isinstance(in_format, (list, tuple)) or isinstance(level, (list, tuple)):
             raise ValueError("in_format / level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
-        self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch)
+        self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice)
         self._set_rate(self.slots, in_rate, filter)
         self._set_format(self.slots, in_format, self.st.input_formats, self.st.set_input_format)
         self._set_level(self.slots, level)
@@ -376,8 +406,8 @@ class StreamingVoiceConversionEngine:
 
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
-                  out_format=None, loud_norm=False, level=None, pitch=None, **filter):
-        """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
+                  out_format=None, loud_norm=False, level=None, pitch=None, voice=None, **filter):
+        """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] (or None with voice = (bank, ids): start) -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
         out_rate (+ out_filter): the returned wav is the whole utterance at that rate, ctx.resample of the model-rate wav bit for bit.
@@ -387,10 +417,11 @@ class StreamingVoiceConversionEngine:
         float32 rows only); the results are those of infer_wav(ctx.loud_norm(src_wav, rate), ...) bit for bit.
         level: the streaming input leveller (start_wav); the results are those of infer_wav(ctx.level(x, **level), ...) bit for bit,
         x = the decoded, resampled utterance.  pitch: the slots' pitch control in the decoder step (start)."""
+        self._check_voice(ref_mel, voice)
         if loud_norm:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
-                       pitch=pitch, **filter)
+                       pitch=pitch, voice=voice, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -417,15 +448,17 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                   pitch=None, **filter):
+                   pitch=None, voice=None, **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
         rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
         (None: the model rate), one value or one per slot.  in_format / out_format: the slots' sample formats (None: float32), one
         value or one per slot.  level: the slots' input leveller (start_wav), one value or a list with one per slot.  pitch: the
-        slots' pitch control (start), one value or a list with one per slot."""
+        slots' pitch control (start), one value or a list with one per slot.  voice: (bank, ids) - enrolled voices, one id per slot, in
+        place of ref_mel (then None): one launch instead of a style pass per slot."""
+        self._check_voice(ref_mel, voice)
         self.st.reset(slots, which=7 | 8)
-        self.st.set_reference(slots, ref_mel, ref_len)
+        self._reference(slots, ref_mel, ref_len, voice)
         self._set_out_rate(slots, out_rate, out_filter)
         self._set_format(slots, in_format, self.st.input_formats, self.st.set_input_format)
         self._set_format(slots, out_format, self.st.output_formats, self.st.set_output_format)
@@ -451,7 +484,7 @@ class StreamingVoiceConversionEngine:
 
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
-                            in_formats=None, out_formats=None, loud_norm=False, level=None, pitch=None, **filter):
+                            in_formats=None, out_formats=None, loud_norm=False, level=None, pitch=None, voice=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -463,14 +496,16 @@ class StreamingVoiceConversionEngine:
         returned in (None: float32); one call then mixes formats, each row packed in its own.  loud_norm: every utterance is
         loudness-normalised whole, at its own input rate, before its first audio is fed (float32 utterances only).  level: the
         streaming input leveller (start_wav), one value for every utterance or a list with one per utterance.  pitch: the pitch
-        control (start), one value for every utterance or a list with one per utterance."""
+        control (start), one value for every utterance or a list with one per utterance.  voice: (bank, ids) - one enrolled id per
+        utterance, in place of ref_mel (then None)."""
+        voice = self._check_voice(ref_mel, voice)
         U = len(src_wavs)
         levels = list(level) if isinstance(level, (list, tuple)) else [level] * U
         pitches = list(pitch) if isinstance(pitch, (list, tuple)) else [pitch] * U
         ifmts, ofmts, orates, rates = (list(v) if v is not None else [None] * U for v in (in_formats, out_formats, out_rates, in_rates))
         if loud_norm:
             src_wavs = [self._loud_norm(x, rates[u], ifmts[u]) for u, x in enumerate(src_wavs)]
-        assert len(starts) == U and len(ref_mel) == U
+        assert len(starts) == U and len(ref_mel if voice is None else voice[1]) == U
         Ls = [self._in_len(r) for r in rates]
         pending = sorted(range(U), key=lambda u: (starts[u], u))
         free = sorted(self.slots)
@@ -486,7 +521,8 @@ class StreamingVoiceConversionEngine:
                 self.staggered_slots[u] = live[u][0]
                 new.append(u)
             if new:
-                self.open_slots([live[u][0] for u in new], torch.stack([ref_mel[u] for u in new]), in_rate=[rates[u] for u in new],
+                self.open_slots([live[u][0] for u in new], torch.stack([ref_mel[u] for u in new]) if voice is None else None,
+                                voice=None if voice is None else (voice[0], [voice[1][u] for u in new]), in_rate=[rates[u] for u in new],
                                 out_rate=[orates[u] for u in new], out_filter=out_filter, in_format=[ifmts[u] for u in new],
                                 out_format=[ofmts[u] for u in new], level=[levels[u] for u in new], pitch=[pitches[u] for u in new], **filter)
             if not live:
@@ -563,20 +599,21 @@ class StreamingVoiceConversionEngine:
         return out + (mel[:, -seg:],) if return_mel else out
 
     @torch.no_grad()
-    def infer(self, src_mel, ref_mel, ref_len=None, pipelined=True, out_rate=None, out_filter=None, out_format=None, pitch=None):
+    def infer(self, src_mel, ref_mel, ref_len=None, pipelined=True, out_rate=None, out_filter=None, out_format=None, pitch=None, voice=None):
         """src_mel [B,T,80], ref_mel [B,Tr,80] (cuda) -> wav [B, T*hop], mel [B,T,80], codes [B,T].
 
         The whole source is available here, so by default the chunks are issued as pipelined steps
         (conan_step_async): the Emformer + decoder of chunk t+1 overlap the vocoder of chunk t.  The
         results are bit-identical to the blocking loop (pipelined=False).  out_rate (+ out_filter): the returned wav is the
         whole utterance at that rate, ctx.resample of the model-rate wav bit for bit.  out_format: the returned wav's sample format.
-        pitch: the slots' pitch control in the decoder step (start)."""
+        pitch: the slots' pitch control in the decoder step (start).  voice: (bank, ids) in place of ref_mel (then None; start)."""
+        self._check_voice(ref_mel, voice)
         if self.ctx.cfg.voc_upsample == 2:
             if out_format not in (None, "f32"):
                 raise ValueError("out_format with an upsample 'nn' vocoder: convert the returned wav with Context.convert_samples instead")
             self._set_out_rate(self.slots, out_rate, out_filter)      # (refuses a rate; restores the model rate)
-            return self._infer_prefix_vocoder(src_mel, ref_mel, ref_len, pitch)
-        self.start(ref_mel, ref_len, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch)
+            return self._infer_prefix_vocoder(src_mel, ref_mel, ref_len, pitch, voice)
+        self.start(ref_mel, ref_len, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice)
         B = src_mel.shape[0]
         hop, nm = self.ctx.hop, self.ctx.cfg.num_mels
         wavs, mels, codes = [], [], []
@@ -600,7 +637,7 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     @torch.no_grad()
-    def _infer_prefix_vocoder(self, src_mel, ref_mel, ref_len=None, pitch=None):
+    def _infer_prefix_vocoder(self, src_mel, ref_mel, ref_len=None, pitch=None, voice=None):
         """Vocoders that look ahead (`upsample: nn`, CausalUpsampleBlock1) cannot carry state from chunk to chunk; the
         reference loop does not need them to: it runs the vocoder on ALL mel frames so far and keeps the samples of the
         current chunk (inference/Conan.py:147-155).  Same here: Emformer and decoder step statefully, the vocoder is reset
@@ -610,7 +647,7 @@ class StreamingVoiceConversionEngine:
             mr = self.st.max_ref_frames
             self.st.close()
             self.st = self.ctx.streams(self.n, max_frames=T, max_ref_frames=mr, arith=self.arith, flags=self.flags, dev_plan=self.dev_plan)
-        self.start(ref_mel, ref_len, pitch=pitch)
+        self.start(ref_mel, ref_len, pitch=pitch, voice=voice)
         hop = self.ctx.hop
         wavs, mels, codes = [], [], []
         for pos, emit, chunk in self.chunks(src_mel):

@@ -241,6 +241,11 @@ class Context:
         test switches of the launch plan, "NAME=value;..." (conan_streams_opts.dev_plan; None in deployments)."""
         return Streams(self, max_slots, max_frames, max_ref_frames, arith, flags, dev_plan)
 
+    def voices(self, capacity, max_ref_frames=256):
+        """A voice bank (conan_voices_create): up to `capacity` enrolled target voices of up to max_ref_frames reference frames, kept
+        on the device outside any slot; Streams.set_voice assigns them to slots in one launch."""
+        return VoiceBank(self, capacity, max_ref_frames)
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.conan_ctx_destroy(self.h)
@@ -306,6 +311,141 @@ class SlotSnapshot:
     def __setstate__(self, state):
         self.meta = state["meta"]
         self.blob = torch.frombuffer(bytearray(state["blob"]), dtype=torch.uint8).reshape(state["shape"])
+
+
+class VoiceSet:
+    """Exported voices (VoiceBank.export): `meta` - the host records, 256 bytes per voice - and `blob` - a uint8 tensor [n, bytes],
+    one row per voice.  A row is sized by the voice's tokens alone and holds no pointers or indices: it may be moved to the host
+    (cpu), to another device (to), pickled, written to a file, and imported into any bank of the same model shape whose
+    max_ref_frames holds the voice."""
+
+    def __init__(self, meta, blob):
+        assert len(meta) == blob.shape[0] * _lib.VOICE_META_BYTES and blob.dtype == torch.uint8 and blob.dim() == 2
+        self.meta, self.blob = bytes(meta), blob
+
+    def __len__(self):
+        return self.blob.shape[0]
+
+    def info(self, i):
+        """conan_voice_meta_info of voice i: dict(layout_id, bytes, ref_frames, tokens)."""
+        M = _lib.VOICE_META_BYTES
+        rec = _lib.VoiceMeta.from_buffer_copy(self.meta[i * M:(i + 1) * M])
+        out = _lib.VoiceInfo()
+        _lib.check(_lib.lib().conan_voice_meta_info(C.byref(rec), C.byref(out)))
+        return dict(layout_id=int(out.layout_id), bytes=int(out.bytes), ref_frames=int(out.ref_frames), tokens=int(out.tokens))
+
+    def cpu(self):
+        return VoiceSet(self.meta, self.blob.cpu())
+
+    def to(self, device):
+        return VoiceSet(self.meta, self.blob.to(device))
+
+    def select(self, rows):
+        """The set of the voices `rows` (indices into this one), in that order; a row may repeat."""
+        rows = [int(r) for r in rows]
+        M = _lib.VOICE_META_BYTES
+        return VoiceSet(b"".join(self.meta[r * M:(r + 1) * M] for r in rows), self.blob[rows])
+
+    def __getstate__(self):
+        b = self.blob.cpu().contiguous()
+        return {"meta": self.meta, "shape": tuple(b.shape), "blob": b.numpy().tobytes()}
+
+    def __setstate__(self, state):
+        self.meta = state["meta"]
+        self.blob = torch.frombuffer(bytearray(state["blob"]), dtype=torch.uint8).reshape(state["shape"])
+
+
+class VoiceBank:
+    """conan_voices: enrolled target voices - the cached result of set_reference's style pass - on the device, outside any slot."""
+
+    def __init__(self, ctx, capacity, max_ref_frames=256):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.capacity, self.max_ref_frames = int(capacity), int(max_ref_frames)
+        h = C.c_void_p()
+        _lib.check(self.lib.conan_voices_create(ctx.h, self.capacity, self.max_ref_frames, C.byref(h)))
+        self.h = h
+        self.dev = torch.device("cuda", ctx.device)
+
+    def enroll(self, ids, ref_mel, ref_len=None, via=None):
+        """conan_voices_enroll: the style pass of ref_mel [n, Tr, num_mels] (as Streams.set_reference) into entries `ids`, one voice
+        per pass on the workspace of the stream-set `via`."""
+        if via is None:
+            raise ValueError("VoiceBank.enroll: via= (a Streams of this context, whose workspace the style pass runs on) is required")
+        a, p = _i32(ids)
+        ref_mel = ref_mel.to(self.dev, torch.float32).contiguous()
+        if ref_mel.dim() == 2:
+            ref_mel = ref_mel[None]
+        n, tr = ref_mel.shape[0], ref_mel.shape[1]
+        if n != len(a):
+            raise ValueError(f"VoiceBank.enroll: {len(a)} ids for {n} reference mels")
+        if ref_len is None:
+            ref_len = [tr] * n
+        l, lp = _i32(ref_len)
+        if len(l) != n:
+            raise ValueError(f"VoiceBank.enroll: {len(l)} lengths for {n} reference mels")
+        _lib.check(self.lib.conan_voices_enroll(self.h, via.h, p, n, _ptr(ref_mel), lp, tr, _stream()))
+        via._release()
+
+    def enroll_wav(self, ids, wav, via=None, sample_rate=None, loud_norm=False, **mel):
+        """Context.wav2mel of wav [n, samples] - resampled from sample_rate to the mel front-end's rate and loudness-normalised
+        first where asked - then enroll.  **mel: wav2mel's keywords."""
+        rate = int(mel.get("sample_rate", 16000))
+        wav = wav.to(self.dev, torch.float32)
+        if wav.dim() == 1:
+            wav = wav[None]
+        if sample_rate is not None and int(sample_rate) != rate:
+            wav = self.ctx.resample(wav, int(sample_rate), rate)
+        if loud_norm:
+            wav = self.ctx.loud_norm(wav, rate)
+        self.enroll(ids, self.ctx.wav2mel(wav, **mel), via=via)
+
+    def remove(self, ids):
+        a, p = _i32(ids)
+        _lib.check(self.lib.conan_voices_remove(self.h, p, len(a)))
+
+    def info(self, id):
+        """conan_voices_info: dict(ref_frames, tokens, bytes) of an enrolled id, None for one that holds no voice."""
+        out = _lib.VoiceInfo()
+        _lib.check(self.lib.conan_voices_info(self.h, int(id), C.byref(out)))
+        return dict(ref_frames=int(out.ref_frames), tokens=int(out.tokens), bytes=int(out.bytes)) if out.enrolled else None
+
+    @property
+    def blob_bytes(self):
+        """Bytes a row of this bank can need (conan_voices_blob_bytes), a multiple of 256."""
+        return _lib.check(self.lib.conan_voices_blob_bytes(self.h))
+
+    def export(self, ids):
+        """conan_voices_export: the voices `ids` -> VoiceSet (blob on this device, complete in stream order)."""
+        a, p = _i32(ids)
+        n = len(a)
+        blob = torch.zeros(n, self.blob_bytes, dtype=torch.uint8, device=self.dev)
+        meta = (_lib.VoiceMeta * n)()
+        _lib.check(self.lib.conan_voices_export(self.h, p, n, _ptr(blob), blob.stride(0), meta, _stream()))
+        return VoiceSet(bytes(meta), blob)
+
+    def import_voices(self, ids, voice_set):
+        """conan_voices_import: entry ids[i] becomes voice i of `voice_set`.  Every record is checked before anything changes."""
+        a, p = _i32(ids)
+        n = len(a)
+        if len(voice_set) != n:
+            raise ValueError(f"import_voices: {n} ids for a set of {len(voice_set)} voices")
+        blob = voice_set.blob.to(self.dev)
+        if blob.stride(1) != 1 or blob.stride(0) % 16 or blob.data_ptr() % 16:
+            blob = blob.contiguous()
+        meta = (_lib.VoiceMeta * n).from_buffer_copy(voice_set.meta)
+        _lib.check(self.lib.conan_voices_import(self.h, p, n, _ptr(blob), blob.stride(0), meta, _stream()))
+        blob.record_stream(torch.cuda.current_stream())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.conan_voices_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Streams:
@@ -618,6 +758,37 @@ class Streams:
         l, lp = _i32(ref_len)
         _lib.check(self.lib.conan_set_reference(self.h, p, len(a), _ptr(ref_mel), lp, tr, _stream()))
         self._release()
+
+    def set_voice(self, slots, bank, ids):
+        """conan_streams_set_voice: slot slots[i] gets voice ids[i] of `bank` (a VoiceBank) - one launch instead of a style pass.
+        In the order of the current stream: steps already enqueued keep the old voice, the next one uses the new."""
+        a, p = _i32(slots)
+        v, vp = _i32(ids)
+        if len(v) != len(a):
+            raise ValueError(f"set_voice: {len(a)} slots for {len(v)} voice ids")
+        _lib.check(self.lib.conan_streams_set_voice(self.h, p, len(a), bank.h, vp, _stream()))
+        self._release()
+
+    def set_voice_mix(self, slots, bank, ids, weights):
+        """conan_streams_set_voice_mix: ids / weights [n, k] (k <= 4): slot i gets the prosody side of ids[i][0] and the style vector
+        sum_k weights[i][k] * style[ids[i][k]] (an fp32 fma chain in k order; the weights are not normalised)."""
+        a, p = _i32(slots)
+        v = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(len(a), -1))
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(len(a), -1))
+        if v.shape != w.shape:
+            raise ValueError(f"set_voice_mix: ids {v.shape} and weights {w.shape} differ")
+        _lib.check(self.lib.conan_streams_set_voice_mix(self.h, p, len(a), bank.h, v.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p),
+                                                        v.shape[1], _stream()))
+        self._release()
+
+    def voice(self, slots):
+        """conan_streams_voice: per slot the voice id last assigned whole by set_voice, -1 otherwise."""
+        out = []
+        for slot in np.atleast_1d(np.asarray(slots, dtype=np.int32)):
+            r = C.c_int32(0)
+            _lib.check(self.lib.conan_streams_voice(self.h, int(slot), C.byref(r)))
+            out.append(int(r.value))
+        return out
 
     def emformer_step(self, slots, chunk, want_out=True, want_logits=True, want_codes=True):
         a, p = _i32(slots)

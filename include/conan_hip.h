@@ -755,6 +755,72 @@ int conan_decoder_step_pitch(conan_streams* s, const int32_t* slots, int n, int 
  * CONAN_ERR_INVALID for a record that is not one, as conan_slot_meta_info. */
 int conan_slot_meta_pitch(const conan_slot_meta* meta, conan_pitch_cfg* out);
 
+/* Voice bank (added within ABI 9: a caller detects it by the exported symbols; no existing struct or call changes).  A bank holds the
+ * result of conan_set_reference's style pass for up to `capacity` target voices in device memory, outside any slot: the style vector,
+ * both aligner layers' K/V rows of the prosody tokens, their key mask, the token count and the VQ ids.  A server enrols its catalogue
+ * once; starting a call, or changing a call's voice mid-utterance, is then conan_streams_set_voice: one upload of the call's rows and
+ * one launch (cnk::voice_assign_kernel) instead of a style pass, and no reference mel to upload.
+ *
+ * conan_voices_create: capacity >= 1 entries for references of up to max_ref_frames (4 .. 2048) frames on ctx's device (a context with
+ *   a Conan model, finalized).  conan_voices_destroy waits for the device.  Neither is stream-ordered.
+ * conan_voices_enroll: the style pass of ref_mel_dev[n][max_len][num_mels] / ref_len[n] (host), exactly as conan_set_reference runs it,
+ *   into entries ids[i] (0 .. capacity-1, distinct) - on the workspace and launch plan of `via`, a stream-set of the bank's context
+ *   (else CONAN_ERR_INVALID), ONE voice per pass whatever via's flags, in the order of `stream` behind a join of via's pipelined work.
+ *   An entry's bits therefore do not depend on what it was enrolled with, and equal those of conan_set_reference(via, one slot, the
+ *   same mel).  ref_len[i] must be 1 .. min(max_len, the bank's max_ref_frames, via's): else CONAN_ERR_INVALID, nothing enqueued.
+ *   Enrolling an id again replaces it.  The call uses via's slot table: it must not overlap via's pipelined steps from another thread.
+ * conan_voices_remove: host only; the ids become "not enrolled" (an id that is not enrolled is skipped).
+ * conan_voices_info: host only; enrolled = 0 for an id that holds no voice.
+ * conan_streams_set_voice: slot slots[i] (distinct, as every slot list) gets voice voice_ids[i] (ids may repeat).  Every row is checked
+ *   before anything changes: a bank of another context or an id out of range is CONAN_ERR_INVALID, an id that is not enrolled
+ *   CONAN_ERR_STATE, a voice with more tokens than the stream-set holds ((max_ref_frames + 3) / 4) CONAN_ERR_SHAPE.  Host bookkeeping
+ *   (the slot has a reference; conan_streams_voice) changes at once; the device write runs in the order of `stream` behind a join of
+ *   pending pipelined work, like conan_streams_set_pitch: steps already enqueued still run with the old voice, the next step uses the
+ *   new one.  The bank's and the stream-set's max_ref_frames may differ.  Rows past the voice's token count are written as
+ *   conan_set_reference leaves them in a freshly created slot (mask 0, ids -1, K/V 0): a slot's cache is a function of the voice
+ *   alone.  It is a COPY: enrolling the id again, removing it or destroying the bank later (destroy waits for the device) does not
+ *   change the slot, and slot snapshots carry it like any other reference.
+ * conan_streams_set_voice_mix: as above with the prosody side (K/V, mask, count, ids) of voice_ids[i][0] and the style vector
+ *   w[i][0] * style_0, then fmaf(w[i][j], style_j, .) for j = 1 .. k-1 in fp32, in the same launch - Conan.forward(spk_embed=...)
+ *   with a blended vector.  1 <= k <= 4; weights (host) must be finite and are not normalised.  k = 1 with weight 1 gives
+ *   conan_streams_set_voice's bits.
+ * conan_streams_voice: host only; the id last assigned WHOLE to `slot` (conan_streams_set_voice), -1 otherwise: never assigned, or
+ *   since then conan_set_reference, conan_set_style, a mix or a snapshot import.  The id is the caller's: the stream-set does not know
+ *   whether the bank still holds that voice.
+ * Persistence.  conan_voices_export writes entry ids[i] to row i of blob_dev (device, 16-byte aligned, rows blob_ld_bytes apart, a
+ *   multiple of 16) and its record to meta_host[i]; one launch on `stream`.  A row is sized by the voice's tokens alone -
+ *   style [hidden_size], count, ids [tokens], mask [tokens], then per layer the K/V rows [tokens][2 * hidden_size], each region padded
+ *   to 16 bytes, padding zero - and holds no pointers or indices.  conan_voices_blob_bytes: what a row of this bank can need (a
+ *   multiple of 256); conan_voice_info.bytes: what a voice uses.  conan_voices_import makes ids[i] the voice of row i; it succeeds
+ *   for a bank of another capacity or another max_ref_frames that still holds the voice.  Every record is checked before anything
+ *   changes: not a record / corrupted: CONAN_ERR_INVALID; another layout id (a hash over hidden_size, heads, num_mels, nvq and the row
+ *   structure) or a voice that does not fit the bank, or the row stride: CONAN_ERR_SHAPE. */
+typedef struct conan_voices conan_voices;
+#define CONAN_VOICE_META_BYTES 256
+typedef struct conan_voice_meta { unsigned char opaque[CONAN_VOICE_META_BYTES]; } conan_voice_meta;
+typedef struct conan_voice_info {
+  int32_t enrolled, ref_frames, tokens, reserved;
+  int64_t bytes;                           /* of an exported row */
+  uint64_t layout_id;
+} conan_voice_info;
+int conan_voices_create(conan_ctx* ctx, int capacity, int max_ref_frames, conan_voices** out);
+int conan_voices_destroy(conan_voices* v);
+int conan_voices_enroll(conan_voices* v, conan_streams* via, const int32_t* ids, int n, const float* ref_mel_dev, const int32_t* ref_len,
+                        int max_len, void* stream);
+int conan_voices_remove(conan_voices* v, const int32_t* ids, int n);
+int conan_voices_info(const conan_voices* v, int id, conan_voice_info* out);
+int conan_streams_set_voice(conan_streams* s, const int32_t* slots, int n, const conan_voices* v, const int32_t* voice_ids, void* stream);
+int conan_streams_set_voice_mix(conan_streams* s, const int32_t* slots, int n, const conan_voices* v, const int32_t* voice_ids,
+                                const float* weights, int k, void* stream);
+int conan_streams_voice(const conan_streams* s, int slot, int32_t* voice_id);
+int64_t conan_voices_blob_bytes(const conan_voices* v);
+int conan_voices_export(conan_voices* v, const int32_t* ids, int n, void* blob_dev, int64_t blob_ld_bytes, conan_voice_meta* meta_host,
+                        void* stream);
+int conan_voices_import(conan_voices* v, const int32_t* ids, int n, const void* blob_dev, int64_t blob_ld_bytes,
+                        const conan_voice_meta* meta_host, void* stream);
+/* Host only, no handle: what a caller may read out of a record (enrolled = 1).  CONAN_ERR_INVALID for what is not one. */
+int conan_voice_meta_info(const conan_voice_meta* meta, conan_voice_info* out);
+
 #ifdef __cplusplus
 }
 #endif
