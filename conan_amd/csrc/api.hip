@@ -113,14 +113,11 @@ void step_pipelined(conan_streams* s, const int32_t* slots, int n, int emit, con
   // launch has left - so the decoder must not have to wait for the Emformer of its own chunk)
   if (t >= NP) HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_front[p], 0));
   int* codes_seg = s->codes_hand[p];
-  // developer timing switch (results are then meaningless): CONAN_SKIP_STAGE bit 0 skips the Emformer launch, bit 1 the decoder's
-#ifdef CONAN_DEV_SWITCHES        // `make DEV=1`: timing experiments only, never in the shipped library (a skipped stage returns garbage with CONAN_OK)
-  static const int skip = ch::dev_getenv("CONAN_SKIP_STAGE") ? atoi(ch::dev_getenv("CONAN_SKIP_STAGE")) : 0;
-  // (the Emformer's workgroups need whole CUs for ~0.15 ms; they are kept away from the pair kernel's launches: see ev_wide)
-  static const bool hold = ch::dev_getenv("CONAN_EMF_HOLD") != nullptr;      // (off by default: see streams.h, ev_wide)
-#else
-  constexpr int skip = 0; constexpr bool hold = false;
-#endif
+  // developer timing switches of `make DEV=1` builds, never of the shipped library (plan_switches.h): SKIP_STAGE bit 0 skips the Emformer
+  // launch, bit 1 the decoder's (a skipped stage returns garbage with CONAN_OK); EMF_HOLD keeps the Emformer's workgroups, which need
+  // whole CUs for ~0.15 ms, away from the pair kernel's launches (off by default: see streams.h, ev_wide)
+  const int skip = s->sw.skip_stage;
+  const bool hold = s->sw.emf_hold;
   if (hold && t >= 2 && s->ev_wide[(t + NP - 2) % NP] && s->wide_marked[(t + NP - 2) % NP]) HIP_CHECK(hipStreamWaitEvent(s->st_emf, s->ev_wide[(t + NP - 2) % NP], 0));
   if (pre) pre(s->st_emf);      // conan_step_wav_async: the streaming front-end writes the chunk this step consumes
   if (tl) HIP_CHECK(hipEventRecord(te[0], s->st_emf));
@@ -252,9 +249,9 @@ int conan_streams_create_opts(conan_ctx* ctx, int max_slots, int max_frames, int
     if (!ctx->finalized) throw Error(CONAN_ERR_STATE, "conan_ctx_finalize must run before conan_streams_create");
     if (max_slots < 1 || max_frames < 1) throw Error(CONAN_ERR_INVALID, "max_slots / max_frames");
     HIP_CHECK(hipSetDevice(ctx->device));
-    conan_streams* s = new conan_streams();
+    conan_streams* s = new conan_streams(plan::resolve(opts ? opts->dev_plan : nullptr));      // (an unknown switch name: CONAN_ERR_INVALID, nothing allocated)
+    const plan::PlanSwitches& sw = s->sw;
     try {
-      s->parse_dev_plan(opts ? opts->dev_plan : nullptr);
       s->fixed_plan = (flags & CONAN_STREAMS_FIXED_PLAN) != 0; s->shared_device = (flags & CONAN_STREAMS_SHARED_DEVICE) != 0;
       s->ctx = ctx; s->live = &device_live_streams(ctx->device); s->live->fetch_add(1); s->max_slots = max_slots; s->max_frames = std::max(max_frames, ctx->cfg.emf_segment); s->max_ref = std::max(4, max_ref_frames);
       s->d_slots = (int*)s->alloc(max_slots + cnk::kSlotTablePad); s->d_ident = (int*)s->alloc(max_slots + 1); s->d_zero = (int*)s->alloc(max_slots);
@@ -264,26 +261,19 @@ int conan_streams_create_opts(conan_ctx* ctx, int max_slots, int max_frames, int
       for (int w = 0; w < 3; ++w) { s->sk_slab[w] = s->alloc((size_t)s->sk_slab_floats); s->sk_counters[w] = (int*)s->alloc(s->sk_max_tiles); }
       for (int w = 0; w < 2; ++w) s->rb_sched[w] = (int*)s->alloc(4);
       for (int w = 0; w < 3; ++w) s->cp_ticket[w] = (int*)s->alloc(4);
-      { const char* e = s->dev("RESERVE_CUS"); s->reserve_cus = e ? atoi(e) : 0; }
-      { const char* e = s->dev("ROWCONV"); s->use_rowconv = !(e && e[0] == '0'); }
-      s->rb_merge = s->dev("RB_NOMERGE") == nullptr;
       // fp32 products of the vocoder's matrix kernels as six bf16 limb products (resblock_limb.hip, conv_limb.hip) or on the
       // f32-input MFMA: conan_streams_opts.arith.  AUTO = the limb form wherever the context packed limb weights (ResBlock1
-      // vocoders); the developer switch CONAN_RB_NOLIMB=1 turns AUTO into F32 for A/B runs - it never overrides an explicit request.
+      // vocoders); the developer switch RB_NOLIMB turns AUTO into F32 for A/B runs - it never overrides an explicit request.
       if (arith == CONAN_ARITH_LIMB && !((ctx->cfg.models & CONAN_MODEL_HIFIGAN) && ctx->has_limb_weights))
         throw Error(CONAN_ERR_UNSUPPORTED, "arith = limb: this context holds no bf16-limb weights (no HiFi-GAN model, or a vocoder configuration without limb kernels)");
       s->arith_auto = arith == CONAN_ARITH_AUTO;
-      s->rb_limb = arith == CONAN_ARITH_LIMB || (arith == CONAN_ARITH_AUTO && ctx->has_limb_weights && s->dev("RB_NOLIMB") == nullptr);
+      s->rb_limb = arith == CONAN_ARITH_LIMB || (arith == CONAN_ARITH_AUTO && ctx->has_limb_weights && !sw.rb_nolimb);
       // deployment flags (conan_streams_opts.flags)
       s->opt_flags = flags;
       s->mega_single = !(s->opt_flags & CONAN_STREAMS_SEPARATE_SMALL_STEPS);
-      { const char* e = s->dev("FENCED"); s->fenced = e && e[0] == '1'; }
-      { const char* e = s->dev("DEC_MEGA"); s->use_mega = !(e && e[0] == '0'); }
-      { const char* e = s->dev("MEGA_GRID"); if (e && atoi(e) > 0) s->mega_grid = std::min(atoi(e), ctx->num_cu); }
       // (a CU-masked front-end stream - developer switch - cannot hold the megakernel's grid resident: its barriers would never complete)
-      { const char* e = s->dev("FRONT_CUSTRIDE"); if (e && atoi(e) >= 2) s->use_mega = false; }
-      { const char* e = s->dev("MEGA_GS"); if (e && (atoi(e) == 4 || atoi(e) == 8 || atoi(e) == 16)) s->mega_gs = atoi(e); }
-      { const char* e = s->dev("MEGA_NARROW"); if (e && e[0] == '0') s->mega_narrow_ksplit = false; }      // developer A/B switch
+      s->use_mega = sw.dec_mega && sw.front_custride < 2;
+      s->mega_grid = plan::mega_grid(sw, ctx->num_cu);
       s->mega_bar = reinterpret_cast<unsigned*>(s->alloc(16 * (size_t)(ctx->num_cu + 2)));
       s->mega_x = reinterpret_cast<unsigned*>(s->alloc(256 + 32 * 64));
 

@@ -185,8 +185,8 @@ int conv_limb_tail_slices(const ConvArgs& a, int shape, int num_cu) { return sha
 // makespan among those that fit and give every CU a tile
 // plan_n > 0 (fixed-plan stream-sets): tile counts, the fill-the-chip thresholds and the cost model use plan_n slots instead of the
 // launch's own, and the launch's own last tile may be ragged where the full set's is not - the choice must not depend on the active slots
-int conv_limb_shape(const ConvArgs* p, int nprob, int num_cu, int plan_n, bool tail_split) {
-  static const int forced = (dev_getenv("CONAN_CL_SHAPE") && *dev_getenv("CONAN_CL_SHAPE")) ? atoi(dev_getenv("CONAN_CL_SHAPE")) : -1;      // developer switch
+// forced >= 0 (developer switch CL_SHAPE): that shape wherever it fits, no other
+int conv_limb_shape(const ConvArgs* p, int nprob, int num_cu, int plan_n, bool tail_split, int forced) {
   int best = -1; double best_cost = 1e30;
   for (int si = 0; si < kNumShapes; ++si) {
     const CLShape& s = kShapes[si];

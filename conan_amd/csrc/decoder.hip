@@ -78,7 +78,7 @@ bool conan_streams::run_mega(int n, int T, const int32_t* codes, float* mel_out,
     mega_rec = &ops; mega_rec_ok = true; mega_rec_lds = 0; mega_rec_flops = 0.0;
     // members a fused feed-forward's hidden columns are split over: the group's workgroups, or - a single row tile, whose group forms
     // at run time (xcd mode) - one virtual member per 64 hidden columns
-    mega_ffn_gs = plan_n(n) * T <= 16 ? std::max(1, (int)ctx->conv("conan.align.0.ff1").Cout / 64) : mega_gs;
+    mega_ffn_gs = plan_n(n) * T <= 16 ? std::max(1, (int)ctx->conv("conan.align.0.ff1").Cout / 64) : sw.mega_gs;
     try {
       if (ex.codes_dst) {      // the caller's copy of the step's codes: independent of everything else
         cnk::MegaOp op; memset(&op, 0, sizeof(op));
@@ -121,11 +121,11 @@ bool conan_streams::run_mega(int n, int T, const int32_t* codes, float* mel_out,
       e->xcd = plan_n(n) * T <= 16;      // (fixed-plan stream-sets: by max_slots - a single active tile of a larger set runs the multi-tile form)
       if (e->xcd) { e->groups = 1; e->group_size = ctx->num_cu; }
       else {
-        e->group_size = mega_gs; e->groups = std::max(1, std::min(njobs, mega_grid / mega_gs));
+        e->group_size = sw.mega_gs; e->groups = std::max(1, std::min(njobs, mega_grid / sw.mega_gs));
         // (group-fastest layout: with a group count that is a multiple of 8 a group's members share an XCD - decoder_mega.hip, CM = 3;
         // groups beyond the job count have no tile and only join the launch's last barrier)
         const int padded = (e->groups + 7) / 8 * 8;
-        if (padded * mega_gs <= std::max(mega_grid, 64) && padded <= 32) e->groups = padded;
+        if (padded * sw.mega_gs <= std::max(mega_grid, 64) && padded <= 32) e->groups = padded;
       }
       e->nops = (int)ops.size(); e->barriers = nb; e->flops = mega_rec_flops;
       // (xcd mode, blocking steps: enough dynamic LDS that two workgroups do not share a CU - one per CU, ~32 on the elected XCD;
@@ -162,7 +162,7 @@ void conan_streams::decoder_step(int n, int T, const int32_t* codes, float* mel_
   // step must all fall into one tile - 16 % frames == 0, or a single tile in all)
   // A single tile (<= 4 streams): round 3 kept the separate launches for it - a grid-wide barrier through memory per operator cost
   // what the launch boundaries do (0.47 against 0.39 ms at one stream).  Round 5: such steps run the persistent launch in xcd mode
-  // (run_mega), whose barriers and hand-offs stay inside one XCD's L2; mega_single (conan_streams_opts / CONAN_MEGA_SINGLE=0) turns it off.
+  // (run_mega), whose barriers and hand-offs stay inside one XCD's L2; mega_single (conan_streams_opts.flags: CONAN_STREAMS_SEPARATE_SMALL_STEPS) turns it off.
   const int prows = plan_n(n) * T;      // the rows the plan is made for: the step's own, or - CONAN_STREAMS_FIXED_PLAN - the full stream-set's
   const bool tiles_ok = (16 % T == 0 && prows > 16) || (prows <= 16 && T >= 2 && mega_single);
   // (the per-op Emformer plan - memory bank, shapes the fused step does not cover - is ~90 launches whose conv_mfma workgroups
@@ -217,7 +217,7 @@ void conan_streams::decoder_ops(int n, int T, const int32_t* codes, float* mel_o
   // Megakernel, several row tiles: the feed-forward of a layer is ONE operator (ff1 -> ReLU -> ff2 with the hidden columns
   // split over the 8 members of a group, decoder_mega.hip MOP_FFN); what ff2 would have written to c_a1 then exists as 8
   // partial tensors + bias + residual, summed by whoever reads it (the norm2 behind it).
-  static const bool ffn_fuse_on = ch::dev_getenv("CONAN_MEGA_NOFFN") == nullptr;
+  const bool ffn_fuse_on = !sw.mega_noffn;
   bool ffn_parts = false;
   const long long part_stride = (long long)max_slots * max_frames * H;
   auto x_parts = [&](auto& a, const PackedConv& ff2) {
@@ -320,7 +320,7 @@ void conan_streams::decoder_ops(int n, int T, const int32_t* codes, float* mel_o
   struct BlkParts { bool on = false; const float* xp = nullptr; const float* bias = nullptr; TRef xres, m1, m2; int has_m2 = 0; } bp;
   int pset = 0;
   auto blk_consume = [&](cnk::RowConvArgs& a, bool store) {
-    a.xp = bp.xp; a.xp_stride = part_stride; a.xparts = mega_gs; a.xp_ld = H; a.xbias = bp.bias; a.xres = bp.xres; a.has_xres = 1;
+    a.xp = bp.xp; a.xp_stride = part_stride; a.xparts = sw.mega_gs; a.xp_ld = H; a.xbias = bp.bias; a.xres = bp.xres; a.has_xres = 1;
     a.xm1 = bp.m1; a.has_xm1 = 1; a.xm2 = bp.m2; a.has_xm2 = bp.has_m2; a.xstore = store ? 1 : 0;
   };
   for (int b = 0; b < c.dec_num_blocks; ++b) {
@@ -332,8 +332,8 @@ void conan_streams::decoder_ops(int n, int T, const int32_t* codes, float* mel_o
       const bool last_sub = b == c.dec_num_blocks - 1 && j == c.dec_layers_in_block - 1;
       {
         const PackedConv &p1 = ctx->conv(nm + ".c1"), &p2 = ctx->conv(nm + ".c2");
-        if (mega_rec && blk_fuse_on && plan_n(n) * T > 16 && rowconv_ok(p1, c.dec_dilations[b], T) && p2.wf && p2.k == 1 && p1.Cout % (64 * mega_gs) == 0 &&
-            p1.Cout / mega_gs <= 256 && (p1.Cout / mega_gs == 64 || (p1.Cout / mega_gs) % 128 == 0) && p2.Cin == p1.Cout && p2.Cout == H && H % 64 == 0) {
+        if (mega_rec && blk_fuse_on && plan_n(n) * T > 16 && rowconv_ok(p1, c.dec_dilations[b], T) && p2.wf && p2.k == 1 && p1.Cout % (64 * sw.mega_gs) == 0 &&
+            p1.Cout / sw.mega_gs <= 256 && (p1.Cout / sw.mega_gs == 64 || (p1.Cout / sw.mega_gs) % 128 == 0) && p2.Cin == p1.Cout && p2.Cout == H && H % 64 == 0) {
           cnk::RowConvArgs a = mk_rc(p1, c_x[cur].ref(), c_h.ref(), n, T, c.dec_dilations[b]);
           a.ln = 1; a.hist = lr.ref(); a.gamma = ctx->vec(nm + ".ln.g"); a.beta = ctx->vec(nm + ".ln.b");
           if (j == 0) { a.mask_out = blkmask; a.has_mask_out = 1; }

@@ -26,8 +26,6 @@ struct Error : std::runtime_error {
 
 void hip_check(hipError_t e, const char* what);
 
-using cnk::dev_getenv;
-
 struct HostTensor {
   std::vector<int64_t> shape;
   std::vector<float> data;

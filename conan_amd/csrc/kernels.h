@@ -8,17 +8,6 @@
 
 namespace cnk {
 
-// Developer switches read from the ENVIRONMENT exist only in `make DEV=1` builds (CONAN_DEV_SWITCHES): the shipped library reads
-// no environment variable - a deployed process's launch plan is a function of the arguments it passes (conan_streams_opts.flags,
-// .dev_plan), not of its environment.
-inline const char* dev_getenv(const char* name) {
-#ifdef CONAN_DEV_SWITCHES
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
 #define HIP_CHECK(x) ::ch::hip_check((x), #x)
 
 
@@ -188,7 +177,7 @@ struct ConvLimbGroup {
   long long slab_floats; int max_counters;
 };
 bool conv_limb_supported(const ConvArgs& a);
-int conv_limb_shape(const ConvArgs* p, int nprob, int num_cu, int plan_n = 0, bool tail_split = false);      // tile shape for these problems, -1: none fits (plan_n: conv_limb.hip)
+int conv_limb_shape(const ConvArgs* p, int nprob, int num_cu, int plan_n = 0, bool tail_split = false, int forced = -1);      // tile shape for these problems, -1: none fits (plan_n: conv_limb.hip)
 bool launch_conv_limb(const ConvLimbGroup& g, int shape, int num_cu, hipStream_t st);
 int conv_limb_tail_slices(const ConvArgs& a, int shape, int num_cu);      // K slices of the split tail this launch would run with (1: none)
 const char* conv_limb_name(int shape);
@@ -301,9 +290,10 @@ struct RowConvArgs {
 };
 bool rowconv_supported(int Cin, int ktaps, int dil, int T);
 // plan_rows (all three): the row count the kernel variant is chosen for; 0 = the launch's own n * T (rowconv.hip)
-void launch_rowconv(const RowConvArgs& a, hipStream_t st, int plan_rows = 0);
-const char* rowconv_kernel_name(const RowConvArgs& a, int plan_rows = 0);   // as rocprofv3 prints it
-int rowconv_plan(RowConvArgs& a, int* nbx, int* nby, int* lds_floats, int plan_rows = 0);   // tile geometry for the decoder megakernel
+struct RowConvTune { bool no_ksplit = false; int wide_min = 1024; };      // developer switches of the variant choice (plan_switches.h: RC_NOKSPLIT, RC_WIDE_MIN)
+void launch_rowconv(const RowConvArgs& a, hipStream_t st, int plan_rows = 0, const RowConvTune& tune = {});
+const char* rowconv_kernel_name(const RowConvArgs& a, int plan_rows = 0, const RowConvTune& tune = {});   // as rocprofv3 prints it
+int rowconv_plan(RowConvArgs& a, int* nbx, int* nby, int* lds_floats, int plan_rows = 0, const RowConvTune& tune = {});   // tile geometry for the decoder megakernel
 
 // LayerNorm over the channel axis of each row:
 //   y[i][t][:] = (LN(x[i][t][:] (+ pre[i][t][:])) * gamma + beta) * m1 * m2 (+ post[i][t][:])

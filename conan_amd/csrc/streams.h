@@ -4,6 +4,7 @@
 #include <functional>
 
 #include "host_common.h"
+#include "plan_switches.h"
 #include "snapshot_layout.h"
 #include "voice_layout.h"
 
@@ -16,6 +17,7 @@ using cnk::ConvGroup;
 using cnk::TRef;
 
 constexpr int kMaxBranches = 3;
+static_assert(plan::kMaxUps == CONAN_MAX_UPS, "plan_switches.h: one UPS_CFG entry per upsampler");
 constexpr int PADR = 16;   // zero rows before/after a reference utterance in the style-pass buffers (k31 -> 15)
 
 struct VocStage {
@@ -97,20 +99,9 @@ struct StageSets {
 struct conan_streams {
   conan_ctx* ctx = nullptr;
   std::atomic<int>* live = nullptr;            // this device's count of live stream-sets (device_live_streams)
-  // developer / test switches of the launch plan: conan_streams_opts.dev_plan ("NAME=value;..."; DEV builds: also CONAN_<NAME> in the environment)
-  std::map<std::string, std::string> dev_plan;
-  void parse_dev_plan(const char* text);
-  const char* dev(const char* name) const {
-    if (!dev_plan.empty()) {
-      auto it = dev_plan.find(name);
-      if (it != dev_plan.end()) return it->second.c_str();
-    }
-#ifdef CONAN_DEV_SWITCHES
-    return getenv((std::string("CONAN_") + name).c_str());
-#else
-    return nullptr;
-#endif
-  }
+  // developer / test switches of the launch plan (plan_switches.h), resolved once by conan_streams_create_opts from conan_streams_opts.dev_plan
+  const plan::PlanSwitches sw;
+  explicit conan_streams(const plan::PlanSwitches& p) : sw(p) {}
   // CONAN_STREAMS_FIXED_PLAN: every plan choice from max_slots, never from the step's active slot count
   bool fixed_plan = false;
   // (the per-utterance style pass of a fixed-plan stream-set runs one slot at a time: its plan follows the slot's own reference length)
@@ -134,11 +125,8 @@ struct conan_streams {
   // (conan_step_async runs the three concurrently, and all split K at small batch sizes)
   float* sk_slab[3] = {nullptr, nullptr, nullptr};
   int* sk_counters[3] = {nullptr, nullptr, nullptr};
-  int reserve_cus = 0;                     // CUs the pipelined vocoder's persistent launches leave to the front-end stream (CONAN_RESERVE_CUS)
-  bool fenced = false;          // CONAN_FENCED=1 at creation: release / acquire fences around the inter-workgroup hand-offs too
   bool rb_limb = false;         // bf16-limb form of the vocoder's matrix kernels where it exists (conan_streams_opts.arith, resolved at creation)
   bool arith_auto = true;       // the caller left the choice to the library (conan_streams_opts.arith == AUTO)
-  bool rb_merge = true;         // merged-branch last-dilation launches (CONAN_RB_NOMERGE=1 at creation: separate branches + mean_act)
   int* cp_ticket[3] = {nullptr, nullptr, nullptr};   // conv_post's last-workgroup ticket, per internal stream
   int* rb_sched[2] = {nullptr, nullptr};   // work-queue counters of the fused resblock launches, per stream like the split-K workspaces
   // resblock_pair workspaces (per stream like rb_sched): exchange buffers, and one block of zero-initialised words:
@@ -270,7 +258,6 @@ struct conan_streams {
   float* e_mems[2] = {nullptr, nullptr};   // memory input / output of a layer, [n][D]
   Lin e_x[2], e_ln, e_q, e_kv, e_att, e_r1, e_ffn, e_h, e_r2, e_logits;
   bool emf_fused = false;
-  int emf_cluster = 0;          // workgroups per stream group of the fused step (0: per launch; CONAN_EMF_CLUSTER)
   cnk::EmfFusedArgs emf_fused_args;
   // --- conan decoder
   Ring c_emb, c_pin2, c_lastr;
@@ -330,7 +317,7 @@ struct conan_streams {
   // --- pipelined stepping (conan_step_async): front-end (Emformer + decoder) and vocoder on two internal streams
   hipStream_t st_emf = nullptr, st_front = nullptr, st_voc = nullptr;
   // pipelined steps: recorded on the vocoder stream behind the wide first stage's pair-kernel launches (its workgroups wait for
-  // their partners: a CU that an Emformer workgroup holds stalls a whole pair).  Developer switch CONAN_EMF_HOLD=1: the Emformer of
+  // their partners: a CU that an Emformer workgroup holds stalls a whole pair).  Developer switch EMF_HOLD (sw.emf_hold): the Emformer of
   // step t is held back until the vocoder of step t-2 has passed that point.  Measured: with the limb kernels and the pair kernel
   // (CONAN_RB_PAIR=1) the mean step is unchanged and the p95 of the step intervals falls from 1.63 to 1.57 ms; with the exact-f32
   // kernels (1.77 ms steps) it costs 2.6 % (1.815 against 1.769 ms) - off by default.
@@ -390,8 +377,8 @@ struct conan_streams {
   void launch_group(const ConvGroup& g, int nprob, int cfg, hipStream_t st);
   bool launch_rb(const cnk::RBArgs& a, int C, hipStream_t st, const TRef* ymean = nullptr);   // true: the launch stored the branch mean (merged)
   void launch_rp(const cnk::RPArgs& a, hipStream_t st);
-  bool use_rowconv = true;                  // frame-rate decoder layers through rowconv.hip (CONAN_ROWCONV=0: conv_mfma + LayerNorm launches)
-  bool rowconv_ok(const PackedConv& pc, int dil, int T) const { return use_rowconv && pc.wf && cnk::rowconv_supported(pc.Cin, pc.k, dil, T); }
+  cnk::RowConvTune rc_tune() const { return {sw.rc_noksplit, sw.rc_wide_min}; }
+  bool rowconv_ok(const PackedConv& pc, int dil, int T) const { return sw.rowconv && pc.wf && cnk::rowconv_supported(pc.Cin, pc.k, dil, T); }
   cnk::RowConvArgs mk_rc(const PackedConv& pc, const TRef& x, const TRef& y, int n, int T, int dil = 1) const;
   void rowconv(const cnk::RowConvArgs& a, hipStream_t st);
   template <typename F> void profiled(const std::string& name, double flops, hipStream_t st, F&& launch);
@@ -417,19 +404,17 @@ struct conan_streams {
   static constexpr int kMegaMaxOps = cnk::kMegaMaxOps, kMegaEntries = 12;
   std::vector<MegaProgram> mega_cache;
   long long mega_clock = 0;
-  bool use_mega = true;                          // CONAN_DEC_MEGA=0: the decoder step as separate launches
-  int mega_grid = 128;                           // CONAN_MEGA_GRID
-  int mega_gs = 8;                               // workgroups per group (CONAN_MEGA_GS: 4, 8 or 16)
-  bool mega_narrow_ksplit = true;                // narrow layers of multi-tile launches as K-split 16-column strips (CONAN_MEGA_NARROW=0: off)
+  bool use_mega = true;                          // sw.dec_mega, and no CU-masked front-end stream (sw.front_custride)
+  int mega_grid = 128;                           // plan::mega_grid: sw.mega_grid clamped to the CU count
   int mega_ffn_gs = 8;                           // members of a fused feed-forward while a program is recorded (run_mega)
   unsigned* mega_bar = nullptr;                  // the grid barrier's arrival counter (counts for ever); the group counters follow it, 16 words apart
   unsigned mega_bar_count = 0;                   // its value once every launch enqueued so far has finished
   unsigned* mega_x = nullptr;                    // xcd mode: election word, rank counter, "decided" counter, barrier flags (decoder_mega.hip)
   unsigned mega_gseq = 0;                        // multi-tile launches so far (epochs of their groups' flag barriers)
   unsigned mega_xseq = 0, mega_xdec = 0;         // launches in xcd mode so far (24 bits), the decided counter's value once they have all finished
-  int opt_flags = 0;                             // conan_streams_opts.flags (+ the developer environment overrides)
-  bool mega_single = true;                       // single-tile steps take the persistent launch (xcd mode); CONAN_MEGA_SINGLE=0: separate launches
-  unsigned long long* mega_dbg = nullptr;        // CONAN_MEGA_STAMPS=1: per-operator clock stamps of the last launch (printed at destruction)
+  int opt_flags = 0;                             // conan_streams_opts.flags
+  bool mega_single = true;                       // single-tile steps take the persistent launch (xcd mode); CONAN_STREAMS_SEPARATE_SMALL_STEPS: separate launches
+  unsigned long long* mega_dbg = nullptr;        // sw.mega_stamps: per-operator clock stamps of the last launch (printed at destruction)
   int mega_dbg_prog = -1;                        // index into mega_cache (the vector may reallocate)
   std::vector<cnk::MegaOp>* mega_rec = nullptr;  // != nullptr: decoder_ops() records its operators instead of launching them
   bool mega_rec_ok = true; int mega_rec_lds = 0; double mega_rec_flops = 0.0;

@@ -61,11 +61,11 @@ void conan_streams::launch_group(const ConvGroup& gin, int nprob, int cfg, hipSt
     if (a.y2_base && ((a.Cout & 3) || (a.y.C & 3) || ((a.Cout / a.shuffle_r) & 3))) throw Error(CONAN_ERR_UNSUPPORTED, "activated twin output needs channel counts that are multiples of 4");
   }
   // few rows per slot and a long K (ups.0: 4 rows per stream, K = 8192): the split-K limb GEMM of conv_tall.hip
-  if (rb_limb && nprob == 1 && dev("NO_TALL") == nullptr) {
-    const int cus = std::max(8, ctx->num_cu - (ws_index(st) == 1 ? reserve_cus : 0));
+  if (rb_limb && nprob == 1 && !sw.no_tall) {
+    const int cus = std::max(8, ctx->num_cu - (ws_index(st) == 1 ? sw.reserve_cus : 0));
     const int wsi = ws_index(st);
     cnk::ConvTallArgs ta;
-    if (cnk::conv_tall_plan(gin.p[0], cus, fixed_plan ? plan_n(gin.p[0].n) : 0, &ta, sk_slab_floats, sk_max_tiles, dev("TALL_MAXT") ? atoi(dev("TALL_MAXT")) : 32)) {
+    if (cnk::conv_tall_plan(gin.p[0], cus, fixed_plan ? plan_n(gin.p[0].n) : 0, &ta, sk_slab_floats, sk_max_tiles, sw.tall_maxt)) {
       ta.slab = sk_slab[wsi]; ta.counters = sk_counters[wsi];
       const ConvArgs& a = gin.p[0];
       profiled("cnk::conv_tall_kernel", 2.0 * (double)a.n * a.T * a.Cout * a.ktaps * a.Cin, st, [&] { cnk::launch_conv_tall(ta, st); });
@@ -76,10 +76,10 @@ void conan_streams::launch_group(const ConvGroup& gin, int nprob, int cfg, hipSt
   if (rb_limb && nprob >= 1 && nprob <= 3) {
     bool ok = true;
     for (int p = 0; p < nprob; ++p) ok = ok && cnk::conv_limb_supported(gin.p[p]) && gin.p[p].n == gin.p[0].n && gin.p[p].T == gin.p[0].T && gin.p[p].Cout == gin.p[0].Cout;
-    const int cus = std::max(8, ctx->num_cu - (ws_index(st) == 1 ? reserve_cus : 0));
+    const int cus = std::max(8, ctx->num_cu - (ws_index(st) == 1 ? sw.reserve_cus : 0));
     // (a single problem may split the K range of its tail tiles - conv_limb.hip; not in a fixed-plan stream-set: which tiles are the
     // tail follows a slot's position in the active list)
-    const int shape = ok ? cnk::conv_limb_shape(gin.p, nprob, cus, fixed_plan ? plan_n(gin.p[0].n) : 0, !fixed_plan) : -1;
+    const int shape = ok ? cnk::conv_limb_shape(gin.p, nprob, cus, fixed_plan ? plan_n(gin.p[0].n) : 0, !fixed_plan, sw.cl_shape) : -1;
     if (shape >= 0) {
       cnk::ConvLimbGroup lg; memset(&lg, 0, sizeof(lg));
       for (int p = 0; p < nprob; ++p) lg.p[p] = gin.p[p];
@@ -108,21 +108,20 @@ void conan_streams::launch_group(const ConvGroup& gin, int nprob, int cfg, hipSt
   }
   // inter-block split-K for launches that cannot fill the chip with tiles but have a long K loop
   const int wsi = ws_index(st);
-  g.slab = sk_slab[wsi]; g.counters = sk_counters[wsi]; g.ksplit = 1; g.split_from = 0; g.fenced = fenced ? 1 : 0;
-  const int cus_all = std::max(8, ctx->num_cu - (wsi == 1 ? reserve_cus : 0));
+  g.slab = sk_slab[wsi]; g.counters = sk_counters[wsi]; g.ksplit = 1; g.split_from = 0; g.fenced = sw.fenced ? 1 : 0;
+  const int cus_all = std::max(8, ctx->num_cu - (wsi == 1 ? sw.reserve_cus : 0));
   if (cnk::conv_cfg_tm(cfg) != 32 && nprob == 1 && cnk::conv_cfg_splitk(cfg)) {
     // Streaming shapes whose tile count is not a multiple of the CU count (ups[1]: 320 tiles of 64 x 64 on 256 CUs): the
     // last `rem` tiles are cut into S K-slices each, rem * S <= CUs, so that every CU gets the same 1 + 1/S (2 + 1/S ...)
     // tiles of MFMA work instead of some CUs getting one tile more than the others - the tail of a stream-K schedule,
     // with the fence-free partial-tile hand-off of the small-M shapes.
-    static const bool off = ch::dev_getenv("CONAN_NO_TAILSPLIT") != nullptr;
     const ConvArgs& a = g.p[0];
     const int TM = cnk::conv_cfg_tm(cfg), TN = cnk::conv_cfg_tn(cfg), KS = cnk::conv_cfg_ks(cfg);
     const long long tiles = (long long)((a.n * a.T + TM - 1) / TM) * ((a.Cout + TN - 1) / TN);
     const int nks = a.ktaps * ((a.Cin_pad + KS - 1) / KS);
     const long long rem = tiles % cus_all;
     // (a fixed-plan stream-set has no split tail: WHICH tiles would be split follows a slot's position in the active list)
-    if (!off && !fixed_plan && tiles > cus_all && rem > 0 && tiles <= sk_max_tiles) {
+    if (!sw.no_tailsplit && !fixed_plan && tiles > cus_all && rem > 0 && tiles <= sk_max_tiles) {
       int S = (int)std::min<long long>(8, cus_all / rem);
       S = std::min(S, nks / 8);                                  // at least 8 K-steps per slice (ups[3], 8 K-steps in all: the hand-off costs more than the tail it removes, 27 against 23 us)
       while (S > 1 && rem * S * TM * TN > sk_slab_floats) --S;
@@ -150,8 +149,7 @@ void conan_streams::launch_group(const ConvGroup& gin, int nprob, int cfg, hipSt
     // the hand-off (write-through partial-tile stores, ticket, sc1 loads) is not free - with fences it cost about 6 K-steps
     // of 32 channels -: split only when it removes clearly more than that from the critical path (thresholds of 2 .. 12
     // measure the same at one and four streams)
-    static const int min_saved = ch::dev_getenv("CONAN_SK_MIN") ? atoi(ch::dev_getenv("CONAN_SK_MIN")) : 12;
-    if (S >= 2 && tiles <= sk_max_tiles && (nks - nks / S) * (KS / 32) >= min_saved) g.ksplit = S;
+    if (S >= 2 && tiles <= sk_max_tiles && (nks - nks / S) * (KS / 32) >= sw.sk_min) g.ksplit = S;
   }
   double fl = 0.0;
   for (int p = 0; p < nprob; ++p) fl += 2.0 * (double)g.p[p].n * g.p[p].T * g.p[p].Cout * g.p[p].ktaps * g.p[p].Cin;
@@ -176,7 +174,7 @@ void conan_streams::rowconv(const cnk::RowConvArgs& a, hipStream_t st) {
     op.u.rc = a;
     int ldsf = 0;
     const int prows = fixed_plan ? plan_n(a.n) * a.T : 0;
-    const int v = cnk::rowconv_plan(op.u.rc, &op.nbx, &op.nby, &ldsf, prows);
+    const int v = cnk::rowconv_plan(op.u.rc, &op.nbx, &op.nby, &ldsf, prows, rc_tune());
     op.type = v == 3 ? cnk::MOP_ROWLIN : (v == 2 ? cnk::MOP_RC114 : cnk::MOP_RC111);
     // Several row tiles, a narrow layer (at most half as many 64-column strips as the group has members: the uv predictor's 128-wide
     // convs, the 256-wide 1x1 / k3 layers): 16-column strips with the K groups split over a workgroup's waves instead - every member
@@ -186,7 +184,7 @@ void conan_streams::rowconv(const cnk::RowConvArgs& a, hipStream_t st) {
     // 10.5 / 12.0 -> 9.8 / 10.6 - but the 256 -> 256 1x1 layers 6.5 -> 8.0: four waves' partial tiles through LDS for 16 K groups each
     // is more than the chain it shortens.  So: a quarter as many strips as members, or half as many with at least 3 taps.)
     const int strips64 = (op.u.rc.Cout_pad + 63) / 64;
-    if (v == 0 && !a.w2 && plan_n(a.n) * a.T > 16 && mega_narrow_ksplit && (strips64 * 4 <= mega_gs || (strips64 * 2 <= mega_gs && a.ktaps >= 3)) && (a.ktaps * (a.Cin >> 4)) % 4 == 0) {
+    if (v == 0 && !a.w2 && plan_n(a.n) * a.T > 16 && sw.mega_narrow && (strips64 * 4 <= sw.mega_gs || (strips64 * 2 <= sw.mega_gs && a.ktaps >= 3)) && (a.ktaps * (a.Cin >> 4)) % 4 == 0) {
       const int ldsk = (32 + op.u.rc.wr_max * (a.Cin + 8) + 3 * 64 * 4);      // rowconv_lds_bytes(a, true) / 4
       cnk::MegaOp t = op; t.type = cnk::MOP_RC114;
       if (cnk::decoder_mega_lds_floats(t, ldsk) * 4 <= (96 + 32 * 264) * 4) {
@@ -209,7 +207,7 @@ void conan_streams::rowconv(const cnk::RowConvArgs& a, hipStream_t st) {
     return;
   }
   const int prows = fixed_plan ? plan_n(a.n) * a.T : 0;
-  profiled(cnk::rowconv_kernel_name(a, prows), fl, st, [&] { cnk::launch_rowconv(a, st, prows); });
+  profiled(cnk::rowconv_kernel_name(a, prows, rc_tune()), fl, st, [&] { cnk::launch_rowconv(a, st, prows, rc_tune()); });
 }
 
 // one ResBlock1 unit per branch (c1 -> LeakyReLU -> c2 -> + residual) as one tile pass
@@ -222,7 +220,7 @@ bool conan_streams::launch_rb(const cnk::RBArgs& ain, int C, hipStream_t st, con
   // CUs left to the other internal stream while a pipelined step is in flight (conan_step_async): the persistent
   // blocks of this launch hold their CU for its whole duration, so without a few free CUs every one of the ~60
   // dependent front-end launches of the next chunk waits for a vocoder kernel boundary
-  const int cus = std::max(8, ctx->num_cu - (ws_index(st) == 1 ? reserve_cus : 0));
+  const int cus = std::max(8, ctx->num_cu - (ws_index(st) == 1 ? sw.reserve_cus : 0));
   // bf16-limb form (resblock_limb.hip) where the weights were packed for it and every branch's span fits its window
   int span = 0;
   bool limb = rb_limb;
@@ -239,7 +237,7 @@ bool conan_streams::launch_rb(const cnk::RBArgs& ain, int C, hipStream_t st, con
   // CUs, the limb build of the C = 128 stage at 64 streams, ran 137 us merged against 98 + 6 us as separate branches + mean_act)
   const long long rounds = (groups + cus - 1) / cus;
   const bool balanced = groups * 10 >= rounds * cus * 9;
-  a.merge = (ymean && rb_merge && a.nprob > 1 && groups >= cus && balanced && (limb ? cnk::resblock_limb_can_merge(C, rows) : cnk::resblock_fused_can_merge(C, rows))) ? 1 : 0;
+  a.merge = (ymean && !sw.rb_nomerge && a.nprob > 1 && groups >= cus && balanced && (limb ? cnk::resblock_limb_can_merge(C, rows) : cnk::resblock_fused_can_merge(C, rows))) ? 1 : 0;
   if (a.merge) a.ymean = *ymean;
   profiled(limb ? cnk::resblock_limb_name(C, rows, a.merge != 0) : cnk::resblock_fused_name(C, rows, a.merge != 0), fl, st, [&] {
     if (!(limb ? cnk::launch_resblock_limb(a, C, rows, cus, st) : cnk::launch_resblock_fused(a, C, rows, cus, st))) throw Error(CONAN_ERR_HIP, "fused resblock launch failed");
@@ -291,7 +289,7 @@ void conan_streams::mega_print_stamps() {
 }
 
 void conan_streams::launch_mega(MegaProgram& e, hipStream_t st) {
-  static const bool stamps = ch::dev_getenv("CONAN_MEGA_STAMPS") != nullptr;
+  const bool stamps = sw.mega_stamps;
   if (stamps && !mega_dbg) mega_dbg = reinterpret_cast<unsigned long long*>(alloc(2 * (size_t)cnk::kMegaDbgWords));
   if (stamps) HIP_CHECK(hipMemsetAsync(mega_dbg, 0, sizeof(unsigned long long) * cnk::kMegaDbgWords, st));      // (no stale stamps of another program)
   if (stamps) mega_dbg_prog = (int)(&e - mega_cache.data());
@@ -306,8 +304,7 @@ void conan_streams::launch_mega(MegaProgram& e, hipStream_t st) {
     // vocoder's conv_mfma workgroups (112.5 KB since round 6) find room beside them (round 5 launched 84 KB here as well: 32 blocks of
     // every vocoder launch then waited for the decoder step to end - 0.635 ms per one-stream pipelined step, 0.40 now).  Same program,
     // same bits.
-    static const bool pad_always = ch::dev_getenv("CONAN_MEGA_XCD_PAD") != nullptr;
-    if (pipelined && !pad_always) m.lds_bytes = e.lds_need;
+    if (pipelined && !sw.mega_xcd_pad) m.lds_bytes = e.lds_need;
     mega_xseq = mega_xseq + 1u;       // (20 bits of it travel in the election word; consecutive launches differ)
     m.xs = mega_x; m.xseq = mega_xseq; m.xdec_base = mega_xdec;
     if (test_fault == 1) { m.xseq += 7u; mega_xseq += 7u; test_fault = 0; }     // test hook: the election word is not in the state this launch expects - nobody can claim
@@ -318,7 +315,7 @@ void conan_streams::launch_mega(MegaProgram& e, hipStream_t st) {
   if (test_fault == 1) { m.bar_base += 1u; test_fault = 0; }       // test hook: the grid barrier waits for one arrival too many
   mega_gseq = mega_gseq + 1u;             // (its own sequence: the xcd mode's election word tracks mega_xseq launch by launch)
   m.xs = mega_x; m.xseq = mega_gseq;      // (the flag barriers of groups that sit on one XCD count in epochs of this sequence number)
-  { const bool nol2 = dev("MEGA_NOL2") != nullptr;
+  {
     // Layout of the multi-tile launch's groups: group-fastest (a group on one XCD, hand-offs through its L2) for every step.
     // Member-fastest (member s of every group on XCD s: strip s's weights stay in that XCD's L2 for all groups - 159 instead of
     // 387 MB fetched per step, profiles/r6_*) for PIPELINED steps was tried in round 6 as VERDICT round 5 asked: the step time is the
@@ -327,37 +324,9 @@ void conan_streams::launch_mega(MegaProgram& e, hipStream_t st) {
     // ended in a GPU memory fault, against 0 of 16 with this layout (tools/stress_repro.py; profiles/r6_stress_layout.txt).  The
     // bytes are not worth a launch shape whose forward progress beside other waiting launches is not understood: MEGA_LAYOUT=m
     // stays a developer switch.
-    const char* lay = dev("MEGA_LAYOUT");
-    const bool mfast = lay && lay[0] == 'm';
-    m.xdec_base = (nol2 ? 1u : 0u) | (mfast ? 2u : 0u); }
+    m.xdec_base = (sw.mega_nol2 ? 1u : 0u) | (sw.mega_layout_member_fastest ? 2u : 0u); }
   profiled(rb_limb ? "cnk::decoder_mega_kernel<4, 3>" : "cnk::decoder_mega_kernel<6, 3>", e.flops, st, [&] { cnk::launch_decoder_mega(m, st); });
   mega_bar_count += (unsigned)(e.groups * e.group_size);
-}
-
-// conan_streams_opts.dev_plan: "NAME=value;NAME=value" (a bare NAME means NAME=1)
-void conan_streams::parse_dev_plan(const char* text) {
-  static const char* known[] = {"RESERVE_CUS", "ROWCONV", "RB_NOMERGE", "RB_NOLIMB", "FENCED", "DEC_MEGA", "MEGA_GRID", "FRONT_CUSTRIDE", "EMF_CUSTRIDE", "MEGA_GS",
-                                "MEGA_NARROW", "MEGA_NOL2", "MEGA_LAYOUT", "FRONT_PRIO", "RB_UNFUSED", "RB_FUSED", "RB_PAIR", "RB_NOPAIR", "RP_MIN_SLOTS",
-                                "UPS_CFG", "EMF_CLUSTER", "EMF_UNFUSED", "NO_TALL", "TALL_MAXT"};
-  dev_plan.clear();
-  if (!text) return;
-  const std::string t(text);
-  size_t p = 0;
-  while (p < t.size()) {
-    size_t q = t.find(';', p);
-    if (q == std::string::npos) q = t.size();
-    std::string item = t.substr(p, q - p);
-    p = q + 1;
-    while (!item.empty() && item.front() == ' ') item.erase(item.begin());
-    while (!item.empty() && item.back() == ' ') item.pop_back();
-    if (item.empty()) continue;
-    const size_t eq = item.find('=');
-    const std::string name = item.substr(0, eq), value = eq == std::string::npos ? "1" : item.substr(eq + 1);
-    bool ok = false;
-    for (const char* k : known) ok = ok || name == k;
-    if (!ok) throw Error(CONAN_ERR_INVALID, "conan_streams_opts.dev_plan: unknown switch '" + name + "'");
-    dev_plan[name] = value;
-  }
 }
 
 void conan_streams::set_slots(const int32_t* slots, int n, hipStream_t st) {
@@ -388,21 +357,18 @@ void conan_streams::async_init() {
     // CONAN_FRONT_PRIO: 1 = front-end stream at the highest priority, -1 = at the lowest, 0 = default (experiment knob)
     int lo = 0, hi = 0;
     HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    const char* e = dev("FRONT_PRIO");
-    const int mode = e ? atoi(e) : 0;
+    const int mode = sw.front_prio;
     // CONAN_FRONT_CUSTRIDE / CONAN_EMF_CUSTRIDE = s: that stage's stream may only use CUs i with i % s == 0 (experiment knob)
-    auto masked = [&](hipStream_t* st, const char* env) {
-      const char* v = dev(env);
-      const int stride = v ? atoi(v) : 0;
+    auto masked = [&](hipStream_t* st, int stride) {
       if (stride < 2) { HIP_CHECK(hipStreamCreateWithFlags(st, hipStreamNonBlocking)); return; }
       std::vector<uint32_t> mask((ctx->num_cu + 31) / 32, 0u);
       for (int i = 0; i < ctx->num_cu; i += stride) mask[i / 32] |= 1u << (i % 32);
       HIP_CHECK(hipExtStreamCreateWithCUMask(st, (uint32_t)mask.size(), mask.data()));
     };
     if (mode == 0) {
-      masked(&st_front, "FRONT_CUSTRIDE");
+      masked(&st_front, sw.front_custride);
       HIP_CHECK(hipStreamCreateWithFlags(&st_voc, hipStreamNonBlocking));
-      masked(&st_emf, "EMF_CUSTRIDE");
+      masked(&st_emf, sw.emf_custride);
     } else {
       HIP_CHECK(hipStreamCreateWithPriority(&st_emf, hipStreamNonBlocking, mode > 0 ? hi : lo));
       HIP_CHECK(hipStreamCreateWithPriority(&st_front, hipStreamNonBlocking, mode > 0 ? hi : lo));
@@ -449,7 +415,7 @@ void conan_streams::build_vocoder() {
     // stages; at C = 32 a tile is short enough that the single pass wins even for one stream: 0.99 -> 0.95 ms per chunk)
     // (limb stream-sets: from 4 slots - measured per chunk at 4 / 6 streams 0.591 / 0.676 ms fused against 0.603 / 0.714 ms with the
     // two-launch plan in the wide stages, blocking p50 0.98 / 1.14 against 1.03 / 1.19 ms; at 1-3 streams the two-launch plan is as fast or faster)
-    s.fused = c.voc_resblock != 2 && dev("RB_UNFUSED") == nullptr && (max_slots >= (rb_limb ? 4 : 8) || ch_ <= 32 || dev("RB_FUSED") != nullptr);
+    s.fused = c.voc_resblock != 2 && !sw.rb_unfused && (max_slots >= (rb_limb ? 4 : 8) || ch_ <= 32 || sw.rb_fused);
     for (int b = 0; b < c.voc_num_resblocks && s.fused; ++b)
       for (int d = 0; d < c.voc_rb_num_dil; ++d)
         s.fused = s.fused && cnk::resblock_fused_supported(ch_, c.voc_rb_kernels[b], (c.voc_rb_kernels[b] - 1) * c.voc_rb_dilations[b][d]);
@@ -464,9 +430,9 @@ void conan_streams::build_vocoder() {
     // (round 4, late; until then from 48 slots on, where the two took the same time alone before conv_limb's last 10 %).  Below 16
     // slots the stage keeps conv_mfma's two-launch plan with its split-K tails: the grouped limb launches would be 2-5 % faster per
     // pipelined step there and 5-9 % slower per blocking step.  CONAN_RB_PAIR=1 keeps the pair kernel.
-    const bool limb_groups = rb_limb && max_slots >= 16 && dev("RB_PAIR") == nullptr;
-    if (!s.fused && !limb_groups && c.voc_resblock != 2 && dev("RB_UNFUSED") == nullptr && dev("RB_NOPAIR") == nullptr &&
-        c.voc_num_resblocks <= kMaxBranches && max_slots >= (dev("RP_MIN_SLOTS") ? atoi(dev("RP_MIN_SLOTS")) : 16) && max_frames * rate <= 32) {
+    const bool limb_groups = rb_limb && max_slots >= 16 && !sw.rb_pair;
+    if (!s.fused && !limb_groups && c.voc_resblock != 2 && !sw.rb_unfused && !sw.rb_nopair &&
+        c.voc_num_resblocks <= kMaxBranches && max_slots >= sw.rp_min_slots && max_frames * rate <= 32) {
       s.pair = true;
       for (int b = 0; b < c.voc_num_resblocks; ++b)
         for (int d = 0; d < c.voc_rb_num_dil; ++d)
@@ -558,12 +524,9 @@ void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float*
       ConvArgs a = mk(ctx->conv("voc.ups." + std::to_string(i)), i == 0 ? v_pre.ref() : v_st[i - 1].xs.ref(), s.up.ref(), n, Tin, pos, 1,
                       lookahead ? 0 : -1);
       if (!s.fused) { a.y2_base = s.upa.base; a.y2_slope = LR; }
-      {
-        // developer switch: CONAN_UPS_CFG=c0,c1,c2,c3 forces the tile configuration (ConvCfg index) of the i-th upsampler
-        const std::vector<int> forced = [&] { std::vector<int> v; const char* e = dev("UPS_CFG"); if (e) { std::string t(e); size_t p = 0; while (p <= t.size()) { size_t q = t.find(',', p); if (q == std::string::npos) q = t.size(); v.push_back(atoi(t.substr(p, q - p).c_str())); p = q + 1; } } return v; }();
-        if (i < (int)forced.size() && forced[i] >= 0 && forced[i] < cnk::NUM_CFG) { ConvGroup g; g.p[0] = a; launch_group(g, 1, forced[i], st); }
-        else conv(a, st);
-      }
+      // developer switch UPS_CFG=c0,c1,c2,c3: the tile configuration (ConvCfg index) forced on the i-th upsampler
+      if (sw.ups_cfg[i] >= 0 && sw.ups_cfg[i] < cnk::NUM_CFG) { ConvGroup g; g.p[0] = a; launch_group(g, 1, sw.ups_cfg[i], st); }
+      else conv(a, st);
       if (taps) tap(taps->ups[i], s.up, T);
     }
     for (int d = 0; d < ND && s.pair; ++d) {    // ResBlock1 of the wide first stage: pairs of workgroups per (branch, stream) tile
@@ -740,11 +703,8 @@ void conan_streams::build_emformer() {
       unsigned* words = reinterpret_cast<unsigned*>(alloc(fw));
       HIP_CHECK(hipMemset(words, 0, fw * sizeof(unsigned)));
       a.xflag = words; a.xepoch = words + (size_t)max_slots * cnk::EMF_MAX_LAYERS * cnk::EMF_MAX_CLUSTER;
-      const char* e = dev("EMF_CLUSTER");
-      emf_cluster = e ? atoi(e) : 0;       // 0: chosen per launch from the stream count
     }
-    const char* off = dev("EMF_UNFUSED");
-    emf_fused = cnk::emformer_fused_supported(a) && !(off && off[0] == '1');
+    emf_fused = cnk::emformer_fused_supported(a) && !sw.emf_unfused;
   }
 }
 
@@ -753,7 +713,7 @@ void conan_streams::emformer_step(int n, const float* chunk, float* out, float* 
   const int D = c.emf_input_dim, R = c.emf_right_context, U = c.emf_segment, Q = R + U;
   if (emf_fused) {   // whole step in one launch (emformer_fused.hip)
     cnk::EmfFusedArgs a = emf_fused_args;
-    a.chunk = chunk; a.out = out; a.logits = logits; a.codes = codes; a.n = n; a.fenced = fenced ? 1 : 0;
+    a.chunk = chunk; a.out = out; a.logits = logits; a.codes = codes; a.n = n; a.fenced = sw.fenced ? 1 : 0;
     a.guard = d_guard; a.fault = 0;
     // Workgroups per stream group: the step is a chain of latency-bound phases on one 16-row tile, so a few streams are
     // spread over up to 8 CUs each (feed-forward hidden units split 8 ways, one exchange per layer); with many streams
@@ -763,7 +723,7 @@ void conan_streams::emformer_step(int n, const float* chunk, float* out, float* 
       // The members of a cluster spin on each other's flags: every workgroup of the launch must be able to be resident at
       // once (one 129 KB workgroup per CU).  The developer override is clamped to that like the automatic choice, and a
       // CU-masked Emformer stream (CONAN_EMF_CUSTRIDE) gets no clusters at all.
-      const bool masked = dev("EMF_CUSTRIDE") != nullptr && atoi(dev("EMF_CUSTRIDE")) >= 2;
+      const bool masked = sw.emf_custride >= 2;
       // (At most 64 workgroups - unless this launch cannot overlap anything else of the context.  A workgroup needs a whole CU for the
       // launch's 150-250 us.  In pipelined steps - the launch is on the stream-set's own Emformer stream - the vocoder's persistent
       // launches run beside it on what is left: 128 -> 64 workgroups measured 0.990 -> 0.979, 1.175 -> 1.154, 1.336 -> 1.317, 1.516 ->
@@ -778,8 +738,8 @@ void conan_streams::emformer_step(int n, const float* chunk, float* out, float* 
       // cluster size (emformer_fused.hip), so the step styles and both policies produce the same bits.)
       const bool pipelined = st_emf != nullptr && st == st_emf;       // (the internal stream exists only once a pipelined step has run; a caller's null stream is not it)
       const bool alone = (!pipelined || pipe_idle) && !shared_device && live && live->load() == 1;      // (pipe_idle: a pipelined step into an EMPTY pipeline, conan_step_async)
-      const int cap = (emf_cluster > 0 || alone) ? ctx->num_cu : 64;
-      a.cs = emf_cluster > 0 ? std::min(emf_cluster, (int)cnk::EMF_MAX_CLUSTER) : cnk::EMF_MAX_CLUSTER;
+      const int cap = (sw.emf_cluster > 0 || alone) ? ctx->num_cu : 64;      // (sw.emf_cluster 0: chosen per launch from the stream count)
+      a.cs = sw.emf_cluster > 0 ? std::min(sw.emf_cluster, (int)cnk::EMF_MAX_CLUSTER) : cnk::EMF_MAX_CLUSTER;
       while (a.cs & (a.cs - 1)) a.cs &= a.cs - 1;             // a power of two
       while (a.cs > 1 && groups * a.cs > cap) a.cs >>= 1;
       if (masked && st == st_emf) a.cs = 1;

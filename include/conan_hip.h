@@ -171,8 +171,11 @@ typedef struct conan_streams_opts {
   /* NULL in deployments.  Developer / test switches of the launch plan as "NAME=value;NAME=value" (A/B runs, the cross-checks of
    * tests/test_gpu_round3.py: e.g. "FENCED=1", "EMF_UNFUSED=1", "DEC_MEGA=0"); unknown names are CONAN_ERR_INVALID.  Since ABI 8 the
    * shipped library reads NO environment variable: a process's plan is a function of the arguments it passes, not of its
-   * environment (until ABI 7 these were CONAN_* environment variables; `make DEV=1` builds still accept those).  The one runtime
-   * knob that stays in the environment is HIP's own GPU_MAX_HW_QUEUES (Multi-GPU). */
+   * environment (until ABI 7 these were CONAN_* environment variables; `make DEV=1` builds still accept those).  The names, their
+   * value rules and defaults are the table in csrc/plan_switches.h (listed in tools/README.md); the text is resolved once, at
+   * creation.  Names of switches that are known to be unsafe exist in `make DEV=1` builds only and are unknown names here:
+   * MEGA_LAYOUT (a GPU memory fault under "MEGA_LAYOUT=m" is on record and unexplained).  The one runtime knob that stays in the
+   * environment is HIP's own GPU_MAX_HW_QUEUES (Multi-GPU). */
   const char* dev_plan;
   int32_t reserved[2];   /* must be 0 */
 } conan_streams_opts;

@@ -257,6 +257,11 @@ def test_option_block_abi8():
     with pytest.raises(_lib.ConanError) as ei:
         ctx.streams(2, dev_plan="EMF_UNFUSED=1;BOGUS=2")
     assert ei.value.code == _lib.ERR_INVALID and "BOGUS" in str(ei.value)
+    # the member-fastest decoder layout has a GPU memory fault on record (profiles/r6_stress_layout.txt): its name exists in `make DEV=1`
+    # builds only, the shipped library rejects it like any unknown one (creation only: no step runs)
+    with pytest.raises(_lib.ConanError) as ei:
+        ctx.streams(2, dev_plan="MEGA_LAYOUT=m")
+    assert ei.value.code == _lib.ERR_INVALID and "MEGA_LAYOUT" in str(ei.value)
     chunk = torch.from_numpy(synth.mel(6, 3, 2)).cuda()
     old = os.environ.get("CONAN_EMF_UNFUSED")
     os.environ["CONAN_EMF_UNFUSED"] = "1"

@@ -296,8 +296,9 @@ def test_ctypes_mirror_matches_the_c_header(tmp_path):
 
 def test_shipped_library_reads_no_environment_variable():
     """Since ABI 8 the launch plan is a function of the arguments (conan_streams_opts.flags / .dev_plan), never of the process
-    environment: the only getenv call in the library's sources is the one inside dev_getenv's `make DEV=1` branch, and the built
-    library carries none of the former CONAN_* variable names that were plan switches."""
+    environment: the only getenv call in the library's sources is the one in plan_switches.h's `make DEV=1` branch - the resolver
+    there is the only reader of switches, the per-site readers (dev_getenv, conan_streams::dev) are gone - and the built library
+    carries none of the former CONAN_* variable names that were plan switches."""
     import glob
     import re
     csrc = os.path.join(os.path.dirname(_lib.LIB_PATH), "csrc")
@@ -307,8 +308,10 @@ def test_shipped_library_reads_no_environment_variable():
         for m in re.finditer(r"(?<![A-Za-z_])getenv\(", text):
             line = text.count("\n", 0, m.start()) + 1
             hits.append((os.path.basename(path), line))
-    # kernels.h: dev_getenv's body; streams.h: conan_streams::dev()'s CONAN_DEV_SWITCHES branch
-    assert sorted(set(f for f, _ in hits)) == ["kernels.h", "streams.h"], hits
+        for gone in ("dev_getenv", "->dev(", 'dev("'):
+            assert gone not in text, (os.path.basename(path), gone)
+    # plan_switches.h: process_env's CONAN_DEV_SWITCHES branch
+    assert sorted(set(f for f, _ in hits)) == ["plan_switches.h"], hits
     for f, line in hits:
         src = open(os.path.join(csrc, f)).read().split("\n")
         window = "\n".join(src[max(0, line - 4):line])

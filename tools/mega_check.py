@@ -1,4 +1,4 @@
-"""Developer check: multi-tile decoder steps (megakernel, groups) against the separate launches (CONAN_DEC_MEGA=0) for several (slots, frames)."""
+"""Developer check: multi-tile decoder steps (megakernel, groups) against the separate launches (dev_plan="DEC_MEGA=0") for several (slots, frames)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -10,11 +10,8 @@ ctx = Context(chp, None, 0, False, True, False)
 ctx.load_state_dict("conan", synth.conan_state_dict(chp, 0))
 ctx.finalize()
 for S in (24, 128):
-    os.environ.pop("CONAN_DEC_MEGA", None)
     a = ctx.streams(S, max_frames=18, max_ref_frames=64)
-    os.environ["CONAN_DEC_MEGA"] = "0"
-    b = ctx.streams(S, max_frames=18, max_ref_frames=64)
-    os.environ.pop("CONAN_DEC_MEGA", None)
+    b = ctx.streams(S, max_frames=18, max_ref_frames=64, dev_plan="DEC_MEGA=0")
     ids = list(range(S))
     ref = torch.from_numpy(synth.mel(40, 60, S)).cuda()
     for st in (a, b):

@@ -1,5 +1,7 @@
 """Repeat the 128-stream f32 case of tests/test_gpu_stress.py (a pipelined and a blocking stream-set overlapping on the device) and
-count the runs that end in a bounded-wait give-up:  python tools/stress_repro.py [iterations] [dev_plan] [S] [arith]"""
+count the runs that end in a bounded-wait give-up:  python tools/stress_repro.py [iterations] [dev_plan] [S] [arith]
+A plan that names MEGA_LAYOUT needs a `make DEV=1` library: with the shipped one the script says so and stops, it does not fall back
+to the default layout."""
 import os
 import sys
 
@@ -10,6 +12,7 @@ import torch  # noqa: E402
 
 from conan_amd import _lib, configs, synth  # noqa: E402
 from conan_amd.runtime import Context  # noqa: E402
+from dev_build import require_dev_build  # noqa: E402
 
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 plan = (sys.argv[2] if len(sys.argv) > 2 else "") or None
@@ -21,6 +24,8 @@ ctx.load_state_dict("emformer", synth.emformer_state_dict(chp, 0))
 ctx.load_state_dict("conan", synth.conan_state_dict(chp, 0))
 ctx.load_state_dict("hifigan", synth.hifigan_state_dict(vhp, 0))
 ctx.finalize()
+if plan and "MEGA_LAYOUT" in plan:
+    require_dev_build(ctx, "tools/stress_repro.py")
 hop = ctx.hop
 ids = list(range(S))
 ref = torch.from_numpy(synth.mel(40, 8, S)).cuda()

@@ -1,5 +1,5 @@
 """Developer check of the decoder megakernel's xcd mode (single-tile steps: one to four streams) against the separate launches
-(CONAN_MEGA_SINGLE=0) on the same inputs, and of the one-launch vocoder step (CONAN_VOC_CHAIN): python tools/xcd_check.py [slots]"""
+(conan_streams_opts.flags: STREAMS_SEPARATE_SMALL_STEPS) on the same inputs: python tools/xcd_check.py [slots]"""
 import os
 import sys
 import time
@@ -8,17 +8,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from conan_amd import configs, synth
+from conan_amd import _lib, configs, synth
 from conan_amd.runtime import Context
 
 
 def run(S, single, steps=10):
-    os.environ["CONAN_MEGA_SINGLE"] = "1" if single else "0"
     chp = configs.conan_hparams()
     ctx = Context(chp, None, 0, False, True, False)
     ctx.load_state_dict("conan", synth.conan_state_dict(chp, 0))
     ctx.finalize()
-    st = ctx.streams(S, max_frames=4, max_ref_frames=64)
+    st = ctx.streams(S, max_frames=4, max_ref_frames=64, flags=0 if single else _lib.STREAMS_SEPARATE_SMALL_STEPS)
     ids = list(range(S))
     st.reset(ids)
     st.set_reference(ids, torch.from_numpy(synth.mel(40, 60, S)).cuda())

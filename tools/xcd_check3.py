@@ -15,9 +15,8 @@ T = 11 * SEG + 2
 src = torch.from_numpy(np.concatenate([synth.mel(T, 1234 + s) for s in range(B)])).cuda()
 ref = torch.from_numpy(np.concatenate([synth.mel(40, 4321 + s) for s in range(B)])).cuda()
 res = {}
-for name, env in (("xcd", "1"), ("launches", "0")):
-    os.environ["CONAN_MEGA_SINGLE"] = env
-    eng = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64, max_frames=CTX + SEG)
+for name, flags in (("xcd", 0), ("launches", _lib.STREAMS_SEPARATE_SMALL_STEPS)):
+    eng = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64, max_frames=CTX + SEG, flags=flags)
     eng.start(ref)
     h = torch.zeros(B, 0, dtype=torch.int32, device="cuda")
     out = []
