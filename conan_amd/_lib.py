@@ -138,6 +138,10 @@ _PROTOS = {
     "conan_decoder_step_pitch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
     "conan_slot_meta_pitch": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "conan_f0": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "conan_streams_set_pitch_follow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "conan_streams_pitch_follow": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "conan_step_wav_contour": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_voices_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "conan_voices_destroy": (C.c_int, [C.c_void_p]),
     "conan_voices_enroll": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -321,6 +325,23 @@ def pitch_cfg(shift_semitones=0.0, range=1.0, pivot=PITCH_PIVOT, uv_threshold=0.
 def pitch_keywords(c):
     """pitch_cfg's keywords of an enabled PitchCfg: the form Streams.pitch and SlotSnapshot.info report a pitch control in."""
     return dict(shift_semitones=c.shift_semitones, range=c.range, pivot=c.pivot, uv_threshold=c.uv_threshold)
+
+
+class F0Cfg(C.Structure):
+    """conan_f0_cfg (include/conan_hip.h)."""
+    _fields_ = [("enabled", C.c_int32), ("fmin", C.c_float), ("fmax", C.c_float), ("threshold", C.c_float), ("floor_db", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+def f0_cfg(fmin=50.0, fmax=900.0, threshold=0.15, floor_db=-60.0):
+    """An enabled conan_f0_cfg: the YIN tracker's search range in Hz, its absolute threshold and the power floor under which a frame
+    is unvoiced.  The defaults are the range of denorm_f0's clamp and YIN's usual threshold."""
+    return F0Cfg(1, float(fmin), float(fmax), float(threshold), float(floor_db), 0)
+
+
+def f0_keywords(c):
+    """f0_cfg's keywords of an enabled F0Cfg: the form Streams.pitch_follow reports a follow setting in."""
+    return dict(fmin=c.fmin, fmax=c.fmax, threshold=c.threshold, floor_db=c.floor_db)
 
 
 class DecoderTaps(C.Structure):

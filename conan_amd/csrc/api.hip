@@ -60,7 +60,7 @@ void check_chunk_step(const conan_streams* s, const char* who) {
 
 // The stages of one chunk step on `st` for the slots set_slots has just installed (conan_step, conan_step_wav).
 void step_blocking(conan_streams* s, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev, float* mel_out_dev,
-                   float* wav_out_dev, hipStream_t st, const conan_streams::OutPlan& op) {
+                   float* wav_out_dev, hipStream_t st, const conan_streams::OutPlan& op, const float* trk_f0, const float* trk_uv) {
   const int seg = s->ctx->cfg.emf_segment;
   int* codes_seg = codes_dev ? codes_dev : s->d_codes;
   s->emformer_step(n, mel_chunk_dev, nullptr, nullptr, codes_seg, st);
@@ -71,14 +71,17 @@ void step_blocking(conan_streams* s, int n, int emit, const float* mel_chunk_dev
     codes_emit = compact;
   }
   float* mel = mel_out_dev ? mel_out_dev : s->c_mel.base;
-  { conan_decoder_taps none; memset(&none, 0, sizeof(none)); s->decoder_step(n, emit, codes_emit, mel, none, st); }
+  conan_streams::DecExtra ex;
+  ex.trk_f0 = trk_f0; ex.trk_uv = trk_uv;
+  { conan_decoder_taps none; memset(&none, 0, sizeof(none)); s->decoder_step(n, emit, codes_emit, mel, none, st, &ex); }
   s->hifigan_step(n, emit, mel, wav_out_dev, nullptr, st, nullptr, &op);
 }
 
 // Everything of conan_step_async after its argument checks; `pre` (may be empty) enqueues work on the Emformer stream right
 // before the step's Emformer launch, behind the step's input event and slot table.
 void step_pipelined(conan_streams* s, const int32_t* slots, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev, float* mel_out_dev,
-                    float* wav_out_dev, void* stream, const std::function<void(hipStream_t)>& pre, const conan_streams::OutPlan& op) {
+                    float* wav_out_dev, void* stream, const std::function<void(hipStream_t)>& pre, const conan_streams::OutPlan& op,
+                    const float* trk_f0, const float* trk_uv) {
   const int seg = s->ctx->cfg.emf_segment;
   HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
   s->async_init();
@@ -132,6 +135,7 @@ void step_pipelined(conan_streams* s, const int32_t* slots, int n, int emit, con
   conan_streams::DecExtra ex;
   if (codes_dev) { ex.codes_dst = codes_dev; ex.codes_src = codes_seg; ex.codes_words = n * seg; }
   ex.mel_out2 = mel_out_dev;
+  ex.trk_f0 = trk_f0; ex.trk_uv = trk_uv;
   const int* codes_emit = codes_seg;
   if (emit != seg && n > 1) {
     int* compact = s->d_codes + (size_t)s->max_slots * s->max_frames;
@@ -440,6 +444,19 @@ int conan_decoder_step_pitch(conan_streams* s, const int32_t* slots, int n, int 
     s->decoder_step(n, frames, codes_dev, mel_out_dev, taps ? *taps : none, (hipStream_t)stream, &ex);
   });
 }
+
+int conan_f0(conan_ctx* ctx, const conan_mel_cfg* mel, const conan_f0_cfg* cfg, const float* wav_dev, int n, int samples, float* f0_out_dev,
+             float* uv_out_dev, int32_t* frames_out, void* stream) {
+  return guarded([&] { f0::whole(ctx, mel, cfg, wav_dev, n, samples, f0_out_dev, uv_out_dev, frames_out, stream); });
+}
+
+int conan_streams_set_pitch_follow(conan_streams* s, const int32_t* slots, int n, const conan_f0_cfg* cfg, void* stream) {
+  return guarded([&] { f0::set_follow(s, slots, n, cfg, stream); });
+}
+
+int conan_streams_pitch_follow(const conan_streams* s, int slot, conan_f0_cfg* out) { return guarded([&] { f0::get_follow(s, slot, out); }); }
+
+int conan_step_wav_contour(conan_streams* s, float* f0_dev, float* uv_dev, void* stream) { return guarded([&] { f0::contour(s, f0_dev, uv_dev, stream); }); }
 
 int conan_streams_set_pitch(conan_streams* s, const int32_t* slots, int n, const conan_pitch_cfg* cfg, void* stream) {
   return guarded([&] { pitch::set_pitch(s, slots, n, cfg, stream); });

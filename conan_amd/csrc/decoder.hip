@@ -61,9 +61,9 @@ void conan_streams::op_advance(int* pos, int n, int delta, hipStream_t st) {
 // buffers: 4 entries that hit for ever) and replayed.  false: this step has an operator the megakernel does not cover.
 bool conan_streams::run_mega(int n, int T, const int32_t* codes, float* mel_out, const DecExtra& ex, hipStream_t st) {
   // (the pitch-control table is part of no key: a program holds the table's address, never a slot's cfg)
-  const long long key[8] = {((long long)n << 32) | (unsigned)T, (long long)(uintptr_t)codes, (long long)(uintptr_t)mel_out, (long long)(uintptr_t)ex.mel_out2,
+  const long long key[9] = {((long long)n << 32) | (unsigned)T, (long long)(uintptr_t)codes, (long long)(uintptr_t)mel_out, (long long)(uintptr_t)ex.mel_out2,
                             (long long)(uintptr_t)ex.codes_dst, (long long)(uintptr_t)ex.codes_src ^ ((long long)ex.codes_words << 48),
-                            (long long)(uintptr_t)ex.f0_in, (long long)(uintptr_t)ex.uv_in};
+                            (long long)(uintptr_t)ex.f0_in, (long long)(uintptr_t)ex.uv_in, (long long)(uintptr_t)ex.trk_f0};
   MegaProgram* e = nullptr;
   for (auto& m : mega_cache) if (m.dev && memcmp(m.key, key, sizeof(key)) == 0) { e = &m; break; }
   if (!e) {
@@ -88,7 +88,7 @@ bool conan_streams::run_mega(int n, int T, const int32_t* codes, float* mel_out,
         ops.back().barrier = 0;
       }
       conan_decoder_taps none; memset(&none, 0, sizeof(none));
-      decoder_ops(n, T, codes, mel_out, none, st, ex.f0_in, ex.uv_in);
+      decoder_ops(n, T, codes, mel_out, none, st, ex);
       if (ex.mel_out2 && mega_rec_ok) {
         // the caller's copy of the mel frames: the mel_out layer once more into the second buffer (the operator before the
         // counter advance is mel_out; both read the same input, no barrier between them)
@@ -170,12 +170,12 @@ void conan_streams::decoder_step(int n, int T, const int32_t* codes, float* mel_
   const bool emf_ok = !(ctx->cfg.models & CONAN_MODEL_EMFORMER) || emf_fused;
   if (use_mega && notaps && tiles_ok && emf_ok && mega_bar && run_mega(n, T, codes, mel_out, ex, st)) return;
   if (ex.codes_dst) HIP_CHECK(hipMemcpyAsync(ex.codes_dst, ex.codes_src, (size_t)ex.codes_words * sizeof(int), hipMemcpyDeviceToDevice, st));
-  decoder_ops(n, T, codes, mel_out, taps, st, ex.f0_in, ex.uv_in);
+  decoder_ops(n, T, codes, mel_out, taps, st, ex);
   if (ex.mel_out2) HIP_CHECK(hipMemcpyAsync(ex.mel_out2, mel_out, (size_t)n * T * ctx->cfg.num_mels * sizeof(float), hipMemcpyDeviceToDevice, st));
 }
 
-void conan_streams::decoder_ops(int n, int T, const int32_t* codes, float* mel_out, const conan_decoder_taps& taps, hipStream_t st, const float* f0_in,
-                                const float* uv_in) {
+void conan_streams::decoder_ops(int n, int T, const int32_t* codes, float* mel_out, const conan_decoder_taps& taps, hipStream_t st, const DecExtra& ex) {
+  const float* const f0_in = ex.f0_in; const float* const uv_in = ex.uv_in;
   float* const uv_pred = taps.uv_pred; float* const f0 = taps.f0_denorm_pred; int32_t* const bins = taps.pitch_bins;
   float* const dec_inp = taps.decoder_inp;
   const conan_cfg& c = ctx->cfg;
@@ -295,6 +295,7 @@ void conan_streams::decoder_ops(int n, int T, const int32_t* codes, float* mel_o
     a.pitch_embed = ctx->vec("conan.pitch_embed"); a.codes = codes; a.uv_pred = uv_pred; a.f0 = f0; a.bins = bins;
     a.slots = d_slots; a.pos = pos; a.T = T; a.n = n; a.Cp = (int)ctx->scalars.at("conan.uv.hidden"); a.E = H; a.silent_token = c.silent_token;
     a.ptab = d_ptab; a.f0_in = f0_in; a.uv_in = f0_in ? uv_in : nullptr;      // (per-slot pitch control, the caller's contour: pitch.hip)
+    a.trk_f0 = f0_in ? nullptr : ex.trk_f0; a.trk_uv = a.trk_f0 ? ex.trk_uv : nullptr; a.trk_ld = c.emf_segment;      // (a caller contour wins over following: f0.hip)
     op_pitch(a, st);
   }
   if (dec_inp) {

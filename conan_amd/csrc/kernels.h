@@ -428,7 +428,8 @@ void launch_xattn(const XAttnArgs& a, hipStream_t st);
 
 // A slot's entry of the pitch-control table (include/conan_hip.h, conan_pitch_cfg, as the kernels read it): shift_oct is the host's
 // (float)((double)shift_semitones / 12.0); a disabled slot's entry is all zero (thr = 0: the model's own threshold).
-struct PitchSlot { int enabled; float shift_oct, range, pivot, thr; int pad_; };
+// follow (conan_streams_set_pitch_follow): 1 = v / uv of the slot come from the step's tracked contour where the step has one (f0.hip).
+struct PitchSlot { int enabled; float shift_oct, range, pivot, thr; int follow; };
 static_assert(sizeof(PitchSlot) == 24, "24 bytes per slot");
 // uv/f0 head: LN(128) -> Linear(128->2) -> uv/f0 -> pitch control -> coarse bin -> decoder_inp = pitch_inp + pitch_embed[bin]
 struct PitchHeadArgs {
@@ -441,15 +442,32 @@ struct PitchHeadArgs {
   float* uv_pred; float* f0; int* bins;   // optional taps, [n][T][2], [n][T], [n][T]
   const int* slots; const int* pos;
   int T, n, Cp, E, silent_token;
-  int pad_;
+  int trk_ld;                   // row stride of the tracked contour (the segment)
   const PitchSlot* ptab;        // [max_slots] per-slot pitch control, indexed by slot (conan_streams_set_pitch); never null
   const float* f0_in; const float* uv_in;   // optional caller contour [n][T] (log2 Hz; > 0: unvoiced), conan_decoder_step_pitch
+  // optional tracked contour of a wav-in step (source-pitch following, f0.hip): library staging [n][trk_ld], row i = the step's row i;
+  // read by the rows whose slot follows (PitchSlot::follow) in a step without a caller contour
+  const float* trk_f0; const float* trk_uv;
 };
 void launch_pitch_head(const PitchHeadArgs& a, hipStream_t st);
 // table[rows[i].slot] = rows[i].v for i < n (conan_streams_set_pitch, snapshot import); slots checked by the host
 struct PitchRow { int slot; PitchSlot v; int pad_; };
 static_assert(sizeof(PitchRow) == 32, "uploaded as 8 ints");
 void launch_pitch_table(PitchSlot* table, const PitchRow* rows, int n, hipStream_t st);
+
+// Source-pitch tracker (f0.hip; include/conan_hip.h, conan_f0_cfg): one workgroup per (row, frame) job.  A row reads `src` at
+// src_off + (s & mask) for sample s of its signal (mask = -1: a plain row; LA - 1: a slot's audio ring), samples outside [0, valid) are
+// zero; its frames f_first .. f_first + nframes - 1 are jobs job0 .. and go to out_f0 / out_uv [out_off + j].
+struct F0Row { long long src_off, valid; double thr, gate; int mask, f_first, nframes, job0, out_off, tmin, tmax, pad_; };
+static_assert(sizeof(F0Row) == 64, "uploaded as 16 ints");
+struct F0Args {
+  const float* src; float* out_f0; float* out_uv;
+  const F0Row* tab; int rows;      // tab == nullptr: `rows` rows shaped like `uni`, row r at src_off * r, job0 = out_off = nframes * r
+  F0Row uni;
+  int jobs, n_fft, hop; double sr;
+};
+constexpr int kF0MaxFft = 2048;
+void launch_f0(const F0Args& a, hipStream_t st);
 
 // y = leaky_relu((x0 + x1 + x2) / nsrc): the MRF mean of HifiGanGenerator.forward (hifigan_causal.py:324-331) with the
 // following LeakyReLU, materialised once so that the consuming conv runs the single-source direct-to-LDS path.

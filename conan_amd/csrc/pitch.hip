@@ -54,6 +54,7 @@ void conan_streams::pitch_write(const int32_t* slots, int n, const conan_pitch_c
     cnk::PitchRow& r = rows[i];
     memset(&r, 0, sizeof(r));
     r.slot = slots[i];
+    r.v.follow = follow.on(slots[i]) ? 1 : 0;      // (conan_streams_set_pitch_follow: the entry's sixth word, whatever the cfg)
     if (c.enabled) {
       r.v.enabled = 1; r.v.shift_oct = (float)((double)c.shift_semitones / 12.0); r.v.range = c.range; r.v.pivot = c.pivot; r.v.thr = c.uv_threshold;
     }

@@ -567,23 +567,32 @@ __device__ __forceinline__ void xattn_tile(const A& a, const int bx, float* __re
 // ------------------------------------------------------------------------------------------------ uv / f0 head
 // Per-slot pitch control (include/conan_hip.h, conan_pitch_cfg): a slot's table entry - five words, loaded unconditionally at the head of
 // the row, in front of every branch - and the law between the head's output and denorm_f0.  A disabled slot's entry is
-// zero: v = d1 and the threshold 0 are the arithmetic of a library without the table.
-struct PitchCtl { int en; float so, rg, pv, th; };
+// zero: v = d1 and the threshold 0 are the arithmetic of a library without the table.  The sixth word is the slot's follow flag
+// (conan_streams_set_pitch_follow), loaded with the other five.
+struct PitchCtl { int en; float so, rg, pv, th; int fo; };
 __device__ __forceinline__ PitchCtl pitch_ctl(const PitchSlot* tab, const int slot) {
   const float* p = reinterpret_cast<const float*>(tab + slot);
   PitchCtl c;
   c.en = ldi(reinterpret_cast<const int*>(p)); c.so = ldw1(p + 1); c.rg = ldw1(p + 2); c.pv = ldw1(p + 3); c.th = ldw1(p + 4);
+  c.fo = ldi(reinterpret_cast<const int*>(p) + 5);
   return c;
 }
-// (v, uv) of row m: the caller's contour where the step has one (no silent-token forcing: the reference's non-infer branch), else the head's
+// (v, uv) of row m: the caller's contour where the step has one (no silent-token forcing: the reference's non-infer branch), else - a
+// following slot in a step with a tracked contour, entry mt of it - the tracker's, by the same rule, else the head's.  The tracked words
+// are loaded for every row of such a step (the staging holds a row per step row) and selected after the loads.
 template <class A>
-__device__ __forceinline__ float pitch_law(const A& a, const PitchCtl& pc, const int m, const float d0, const float d1, const int code, bool& uv) {
+__device__ __forceinline__ float pitch_law(const A& a, const PitchCtl& pc, const int m, const int mt, const float d0, const float d1, const int code, bool& uv) {
   float v = d1;
   if (a.f0_in) {
     v = ldw1(a.f0_in + m);
     uv = a.uv_in ? ldw1(a.uv_in + m) > 0.f : false;
   } else {
     uv = (d0 > pc.th) || (code == a.silent_token);
+    if (a.trk_f0) {
+      const float tv = ldw1(a.trk_f0 + mt), tu = ldw1(a.trk_uv + mt);
+      v = pc.fo ? tv : v;
+      uv = pc.fo ? tu > 0.f : uv;
+    }
   }
   if (pc.en) {
     if (pc.rg != 1.f) v = fmaf(pc.rg, v - pc.pv, pc.pv);
@@ -625,7 +634,7 @@ __device__ __forceinline__ void pitch_head_tile(const A& a, const float mel_min,
   d1 = wave_sum(d1) + ldw1(a.b + 1);
   const int code = ldi(a.codes + m);
   bool uv;
-  float f0 = exp2f(pitch_law(a, pc, m, d0, d1, code, uv));
+  float f0 = exp2f(pitch_law(a, pc, m, i * a.trk_ld + t, d0, d1, code, uv));
   f0 = fminf(fmaxf(f0, 50.f), 900.f);
   if (uv) f0 = 0.f;
   float fm = 1127.f * logf(1.f + f0 / 700.f);
@@ -1568,7 +1577,7 @@ __device__ __forceinline__ void mg_pitch_row(const A& a, const RowTab& tb, const
   d1 = wave_sum(d1) + ldw1(a.b + 1);
   const int code = ldi(a.codes + m);
   bool uv;
-  float f0 = exp2f(pitch_law(a, pc, m, d0, d1, code, uv));
+  float f0 = exp2f(pitch_law(a, pc, m, id.i * a.trk_ld + id.t, d0, d1, code, uv));
   f0 = fminf(fmaxf(f0, 50.f), 900.f);
   if (uv) f0 = 0.f;
   float fm = 1127.f * logf(1.f + f0 / 700.f);

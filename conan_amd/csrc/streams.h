@@ -195,6 +195,23 @@ struct conan_streams {
     bool levelled(int slot) const { return lv_n > 0 && lv_cfg[slot].enabled; }
   } wav_in;
   void level_init(const cnk::LvFilter& f);      // the leveller's state and row tables (conan_streams_set_input_level)
+  // source-pitch following (conan_streams_set_pitch_follow; f0.hip): per slot its cfg (enabled = 0: none), which persists across resets;
+  // n_on: slots with one.  The tracker keeps no state of its own: a wav-in call that emits a chunk tracks the chunk's frames from the
+  // slot's audio ring.  Per call a row table (set q of `sets`) and beside it the contour the call's decoder steps read, ct_f0 / ct_uv
+  // [q][chunk row][seg] (chunk row = the row's place in the call's emit groups, as fe_chunk); the set's event follows the last decoder
+  // step of the call, so the contour of a pipelined call outlives the front-ends of the calls behind it.  Allocated by the first
+  // enabling call; the contour sets count as stream state.  last: the rows of the most recent wav-in call that followed
+  // (conan_step_wav_contour).
+  struct Follow {
+    std::vector<conan_f0_cfg> cfg;
+    int n_on = 0;
+    float* ct_f0[kStageSets] = {}; float* ct_uv[kStageSets] = {};
+    StageSets<cnk::F0Row> sets;
+    struct LastRow { int row, set, src, emit; };
+    std::vector<LastRow> last;
+    bool on(int slot) const { return n_on > 0 && cfg[slot].enabled; }
+  } follow;
+  void follow_init();
   void ragged_init();
   void resample_init();        // staging, row tables and the history ring (conan_streams_set_input_rate)
   void rs_stage_init();        // staging and row tables only (conan_streams_set_input_format: no stream state)
@@ -388,9 +405,10 @@ struct conan_streams {
   // --- decoder megakernel (decoder_mega.hip): the decoder step's operator list, recorded once per (slot count, frames,
   // buffer set) and replayed as one persistent launch
   struct DecExtra { float* mel_out2 = nullptr; int* codes_dst = nullptr; const int* codes_src = nullptr; int codes_words = 0;
-                    const float* f0_in = nullptr; const float* uv_in = nullptr; };      // the caller's contour (conan_decoder_step_pitch)
+                    const float* f0_in = nullptr; const float* uv_in = nullptr;         // the caller's contour (conan_decoder_step_pitch)
+                    const float* trk_f0 = nullptr; const float* trk_uv = nullptr; };    // the tracked contour of a wav-in step (f0.hip)
   struct MegaProgram {
-    long long key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    long long key[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     bool ok = false;
     int nops = 0, groups = 0, group_size = 0, njobs = 0, kw4 = 0, lds_bytes = 0, barriers = 0, n = 0, T = 0;
     int lds_need = 0;                  // what the operators need (lds_bytes may be padded: xcd mode, blocking steps)
@@ -421,8 +439,7 @@ struct conan_streams {
   void mega_push(cnk::MegaOp& op, int lds_floats);
   bool run_mega(int n, int T, const int32_t* codes, float* mel_out, const DecExtra& ex, hipStream_t st);
   void launch_mega(MegaProgram& e, hipStream_t st);
-  void decoder_ops(int n, int frames, const int32_t* codes, float* mel_out, const conan_decoder_taps& taps, hipStream_t st, const float* f0_in = nullptr,
-                   const float* uv_in = nullptr);
+  void decoder_ops(int n, int frames, const int32_t* codes, float* mel_out, const conan_decoder_taps& taps, hipStream_t st, const DecExtra& ex);
   void op_embed(const cnk::EmbedArgs& a, hipStream_t st);
   void op_ln(const cnk::LNArgs& a, hipStream_t st);
   void op_xattn(const cnk::XAttnArgs& a, hipStream_t st);
@@ -462,10 +479,12 @@ inline void conan_streams::profiled(const std::string& name, double flops, hipSt
 
 // ---- the chunk step's stages (api.hip), shared by the mel-in entry points and the wav-in steps (wavio.hip)
 void check_chunk_step(const conan_streams* s, const char* who);
+// trk_f0 / trk_uv (may be null): the step's tracked contour [n][seg], for its rows whose slot follows (f0.hip)
 void step_blocking(conan_streams* s, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev,
-                   hipStream_t st, const conan_streams::OutPlan& op);
+                   hipStream_t st, const conan_streams::OutPlan& op, const float* trk_f0 = nullptr, const float* trk_uv = nullptr);
 void step_pipelined(conan_streams* s, const int32_t* slots, int n, int emit, const float* mel_chunk_dev, int32_t* codes_dev, float* mel_out_dev,
-                    float* wav_out_dev, void* stream, const std::function<void(hipStream_t)>& pre, const conan_streams::OutPlan& op);
+                    float* wav_out_dev, void* stream, const std::function<void(hipStream_t)>& pre, const conan_streams::OutPlan& op,
+                    const float* trk_f0 = nullptr, const float* trk_uv = nullptr);
 
 // ---- waveform I/O host layer (wavio.hip): the bodies of api.hip's wav-in steps, rate / stride / format setters and output queries
 namespace wavio {
@@ -517,6 +536,19 @@ void export_voices(conan_voices* v, const int32_t* ids, int n, void* blob_dev, i
 void import_voices(conan_voices* v, const int32_t* ids, int n, const void* blob_dev, int64_t blob_ld, const conan_voice_meta* meta, void* stream);
 void meta_info(const conan_voice_meta* meta, conan_voice_info* out);
 }  // namespace voices
+
+// ---- source-pitch following (f0.hip): the tracker's host side and the bodies of api.hip's entry points
+namespace f0 {
+struct Lags { int tmin, tmax; };
+Lags lags(const conan_f0_cfg& c, double sr);
+void check_cfg(const conan_f0_cfg& c, double sr, int n_fft, const char* who);      // host only
+cnk::F0Row row(const conan_f0_cfg& c, double sr);      // the cfg's fields of a kernel row
+void whole(conan_ctx* ctx, const conan_mel_cfg* mel, const conan_f0_cfg* cfg, const float* wav_dev, int n, int samples, float* f0_out_dev, float* uv_out_dev,
+           int32_t* frames_out, void* stream);
+void set_follow(conan_streams* s, const int32_t* slots, int n, const conan_f0_cfg* cfg, void* stream);
+void get_follow(const conan_streams* s, int slot, conan_f0_cfg* out);
+void contour(conan_streams* s, float* f0_dev, float* uv_dev, void* stream);
+}  // namespace f0
 
 // ---- per-slot pitch control (pitch.hip): the bodies of api.hip's entry points
 namespace pitch {

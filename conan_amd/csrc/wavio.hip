@@ -305,6 +305,35 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
     const int e = pl[groups[g][0]].emit;
     ops.push_back(s->out_plan(gs.data(), (int)gs.size(), e, wav_out_dev, route ? (long long)seg * hop : (long long)e * hop, route ? &groups[g] : nullptr, who));
   }
+  // source-pitch following (f0.hip): the following slots that emit have their chunk's frames tracked, from their audio rings, into
+  // the call's contour rows (chunk row = the row's place in the emit groups, as fe_chunk's)
+  std::vector<cnk::F0Row> f0_rows;
+  std::vector<conan_streams::Follow::LastRow> f0_last;
+  std::vector<char> f0_group(groups.size(), 0);
+  int f0_jobs = 0;
+  if (s->follow.n_on > 0) {
+    const double sr = 50.0 * hop;
+    for (int i = 0; i < n; ++i) {
+      if (!s->follow.on(slots[i])) continue;
+      if (m.sample_rate != 50 * hop) throw Error(CONAN_ERR_INVALID, who + ": slot " + std::to_string(slots[i]) + " follows the source pitch: conan_mel_cfg.sample_rate must be 50 * hop_size");
+      f0::check_cfg(s->follow.cfg[slots[i]], sr, N, who.c_str());
+    }
+    for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g)
+      for (int k = 0; k < (int)groups[g].size(); ++k) {
+        const int i = groups[g][k];
+        if (!s->follow.on(slots[i])) continue;
+        const FePlan& p = pl[i];
+        if (p.R - std::max(0ll, (long long)p.pos * hop - N / 2) > s->wav_in.fe_LA)
+          throw Error(CONAN_ERR_UNSUPPORTED, who + ": slot " + std::to_string(slots[i]) + " follows the source pitch: the chunk's frames have left the audio ring at this fft_size");
+        cnk::F0Row r = f0::row(s->follow.cfg[slots[i]], sr);
+        r.src_off = (long long)slots[i] * s->wav_in.fe_LA; r.valid = p.R; r.mask = s->wav_in.fe_LA - 1;
+        r.f_first = p.pos; r.nframes = p.emit; r.job0 = f0_jobs; r.out_off = (off + k) * seg;
+        f0_jobs += p.emit;
+        f0_rows.push_back(r);
+        f0_last.push_back({i, 0, off + k, p.emit});
+        f0_group[g] = 1;
+      }
+  }
   const int nm_in = m.num_mels, nm = c.num_mels;
   int jobs = 0;
   std::vector<RgRow> tab;
@@ -341,6 +370,7 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
   }
   if (P.launch || lv_stages) rq = s->wav_in.rs_sets.begin(P.rows.data(), n, cst);      // (a leveller alone takes the set for its staging)
   const int lq = lv_rows.empty() ? 0 : s->wav_in.lv_sets.begin(lv_rows.data(), (int)lv_rows.size(), cst);
+  const int fq = f0_rows.empty() ? 0 : s->follow.sets.begin(f0_rows.data(), (int)f0_rows.size(), cst);
   const int* rg_tab = reinterpret_cast<const int*>(s->wav_in.rg_sets.rows[q]);
   std::function<void(hipStream_t)> front;
   if (run) {
@@ -388,6 +418,19 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
   }
   // (the same-position kernel reads the resampler's rows [n][samples], the ragged one [n][seg * hop])
   if (P.launch) front = rs_front(s, P, n, rq, wav_dev, wav_ld, common ? samples[0] : seg * hop, front);
+  // the tracker, behind the front-end launch: the call's samples are in the audio rings
+  if (!f0_rows.empty()) {
+    cnk::F0Args a;
+    memset(&a, 0, sizeof(a));
+    a.src = s->wav_in.fe_audio; a.out_f0 = s->follow.ct_f0[fq]; a.out_uv = s->follow.ct_uv[fq];
+    a.tab = s->follow.sets.rows[fq]; a.rows = (int)f0_rows.size(); a.jobs = f0_jobs; a.n_fft = N; a.hop = hop; a.sr = 50.0 * hop;
+    double flops = 0.0;
+    for (const cnk::F0Row& r : f0_rows) flops += 3.0 * r.nframes * (double)(N - r.tmax - 1) * (r.tmax + 2);
+    front = [s, a, flops, mel_front = front](hipStream_t st) {
+      if (mel_front) mel_front(st);
+      s->profiled("f0_yin_kernel", flops, st, [&] { cnk::launch_f0(a, st); });
+    };
+  }
   cnk::WavScatterArgs sc;
   sc.tab = rg_tab; sc.n = n; sc.seg = seg; sc.nm = nm; sc.hop = hop;
   sc.codes_src = s->wav_in.rg_codes[q]; sc.mel_src = s->wav_in.rg_mel[q]; sc.wav_src = s->wav_in.rg_wav[q];
@@ -399,11 +442,13 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
     int32_t* cd = direct ? codes_dev : s->wav_in.rg_codes[q] + (size_t)off * seg;
     float* md = direct ? mel_out_dev : s->wav_in.rg_mel[q] + (size_t)off * seg * nm;
     float* wd = direct ? wav_out_dev : s->wav_in.rg_wav[q] + (size_t)off * seg * hop;
+    const float* tf = f0_group[g] ? s->follow.ct_f0[fq] + (size_t)off * seg : nullptr;      // (a group without a following row keeps its program)
+    const float* tu = f0_group[g] ? s->follow.ct_uv[fq] + (size_t)off * seg : nullptr;
     if (pipelined) {
-      step_pipelined(s, gs.data(), ng, e, chunk, cd, md, wd, stream, g == 0 ? front : std::function<void(hipStream_t)>(), ops[g]);
+      step_pipelined(s, gs.data(), ng, e, chunk, cd, md, wd, stream, g == 0 ? front : std::function<void(hipStream_t)>(), ops[g], tf, tu);
     } else {
       s->set_slots(gs.data(), ng, st);
-      step_blocking(s, ng, e, chunk, cd, md, wd, st, ops[g]);
+      step_blocking(s, ng, e, chunk, cd, md, wd, st, ops[g], tf, tu);
     }
   };
   const bool piped = pipelined && !groups.empty();      // (the first group's step_pipelined runs `front`)
@@ -422,6 +467,9 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
     s->profiled("wav_rows_scatter_kernel", 0.0, cst, [&] { cnk::launch_wav_scatter(sc, cst); });
   }
   if (!common) s->wav_in.rg_sets.end(q, last);
+  if (!f0_rows.empty()) s->follow.sets.end(fq, piped ? s->st_front : cst);      // (behind the call's last decoder step, the contour's last reader)
+  for (conan_streams::Follow::LastRow& r : f0_last) r.set = fq;
+  s->follow.last = std::move(f0_last);
   if (scatter && !route) {      // (each group's step counted its own rows, in group order: back to the call's rows)
     s->wav_out.out_counts.assign(n, 0);
     for (int i = 0; i < n; ++i) s->wav_out.out_counts[i] = pl[i].emit * hop;

@@ -221,6 +221,7 @@ class StreamingVoiceConversionEngine:
                               flags=flags, dev_plan=dev_plan)
         self.slots = list(range(n_streams))
         self.seg, self.rc = ctx.cfg.emf_segment, ctx.cfg.emf_right_context
+        self._followed = False      # set_pitch_follow has been called on the stream-set
 
     @staticmethod
     def _check_voice(ref_mel, voice):
@@ -267,14 +268,17 @@ class StreamingVoiceConversionEngine:
         self._set_pitch(self.slots, pitch)
 
     def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                  pitch=None, voice=None, **filter):
+                  pitch=None, voice=None, follow=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
         in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
         in_format: the input's sample format (None: float32; 's16' takes int16 rows, 'ulaw' / 'alaw' uint8), decoded on the GPU.
         out_rate / out_filter / out_format: as in start().
         level: the input leveller (Streams.set_input_level) - None / False: none; True: Context.level's defaults; a dict: its
         keywords.  It runs on the GPU on the decoded, resampled samples in front of the front-end, causally: feed() gains no latency.
-        pitch, voice: as in start()."""
+        pitch, voice: as in start().
+        follow: source-pitch following (Streams.set_pitch_follow) - None / False: none; True: the tracker's defaults; a dict of its
+        keywords (fmin, fmax, threshold, floor_db).  The decoder steps then take f0 / uv from the input's own contour, tracked on the
+        GPU on the samples the front-end reads; `pitch` applies on top."""
         self._check_voice(ref_mel, voice)
         if isinstance(in_format, (list, tuple)) or isinstance(level, (list, tuple)):
             raise ValueError("in_format / level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
@@ -282,6 +286,25 @@ class StreamingVoiceConversionEngine:
         self._set_rate(self.slots, in_rate, filter)
         self._set_format(self.slots, in_format, self.st.input_formats, self.st.set_input_format)
         self._set_level(self.slots, level)
+        self._set_follow(self.slots, follow)
+
+    def _set_follow(self, slots, follow):
+        """The slots' source-pitch following (None / False: none; True: the defaults; a dict of Streams.set_pitch_follow's keywords),
+        one value or one per slot.  A stream-set that never followed is left alone."""
+        follows = list(follow) if isinstance(follow, (list, tuple)) else [follow] * len(slots)
+        assert len(follows) == len(slots), (len(follows), len(slots))
+        if all(f is None or f is False for f in follows) and not self._followed:
+            return
+        self._followed = True
+        for slot, fo in zip(slots, follows):
+            self.st.set_pitch_follow([slot], None if fo is None or fo is False else (True if fo is True else dict(fo)))
+
+    def set_pitch_follow(self, slots=None, cfg=True, **kw):
+        """A live change of the slots' source-pitch following (all slots by default) between feed / feed_ragged calls, also
+        mid-utterance and with pipelined steps in flight: Streams.set_pitch_follow's arguments (cfg=None turns it off).  In force
+        from the next emitted chunk."""
+        self._followed = True
+        self.st.set_pitch_follow(self.slots if slots is None else slots, cfg, **kw)
 
     def _set_level(self, slots, level):
         """The slots' input leveller (None / False: none; True: the defaults; a dict of Streams.set_input_level's keywords), one value
@@ -406,7 +429,7 @@ class StreamingVoiceConversionEngine:
 
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
-                  out_format=None, loud_norm=False, level=None, pitch=None, voice=None, **filter):
+                  out_format=None, loud_norm=False, level=None, pitch=None, voice=None, follow=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] (or None with voice = (bank, ids): start) -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
@@ -416,12 +439,13 @@ class StreamingVoiceConversionEngine:
         loud_norm: each whole source utterance is loudness-normalised at its input rate before it is fed (the reference's loud_norm;
         float32 rows only); the results are those of infer_wav(ctx.loud_norm(src_wav, rate), ...) bit for bit.
         level: the streaming input leveller (start_wav); the results are those of infer_wav(ctx.level(x, **level), ...) bit for bit,
-        x = the decoded, resampled utterance.  pitch: the slots' pitch control in the decoder step (start)."""
+        x = the decoded, resampled utterance.  pitch: the slots' pitch control in the decoder step (start).  follow: source-pitch
+        following (start_wav): the decoder steps take ctx.f0 of the samples the front-end reads instead of the predictor's contour."""
         self._check_voice(ref_mel, voice)
         if loud_norm:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
-                       pitch=pitch, voice=voice, **filter)
+                       pitch=pitch, voice=voice, follow=follow, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -448,14 +472,15 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                   pitch=None, voice=None, **filter):
+                   pitch=None, voice=None, follow=None, **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
         rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
         (None: the model rate), one value or one per slot.  in_format / out_format: the slots' sample formats (None: float32), one
         value or one per slot.  level: the slots' input leveller (start_wav), one value or a list with one per slot.  pitch: the
         slots' pitch control (start), one value or a list with one per slot.  voice: (bank, ids) - enrolled voices, one id per slot, in
-        place of ref_mel (then None): one launch instead of a style pass per slot."""
+        place of ref_mel (then None): one launch instead of a style pass per slot.  follow: the slots' source-pitch following
+        (start_wav), one value or a list with one per slot."""
         self._check_voice(ref_mel, voice)
         self.st.reset(slots, which=7 | 8)
         self._reference(slots, ref_mel, ref_len, voice)
@@ -466,6 +491,7 @@ class StreamingVoiceConversionEngine:
             self._set_rate(group, r, filter)
         self._set_level(slots, level)
         self._set_pitch(slots, pitch)
+        self._set_follow(slots, follow)
 
     @torch.no_grad()
     def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None):
@@ -484,7 +510,7 @@ class StreamingVoiceConversionEngine:
 
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
-                            in_formats=None, out_formats=None, loud_norm=False, level=None, pitch=None, voice=None, **filter):
+                            in_formats=None, out_formats=None, loud_norm=False, level=None, pitch=None, voice=None, follow=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -497,9 +523,11 @@ class StreamingVoiceConversionEngine:
         loudness-normalised whole, at its own input rate, before its first audio is fed (float32 utterances only).  level: the
         streaming input leveller (start_wav), one value for every utterance or a list with one per utterance.  pitch: the pitch
         control (start), one value for every utterance or a list with one per utterance.  voice: (bank, ids) - one enrolled id per
-        utterance, in place of ref_mel (then None)."""
+        utterance, in place of ref_mel (then None).  follow: source-pitch following (start_wav), one value for every
+        utterance or a list with one per utterance."""
         voice = self._check_voice(ref_mel, voice)
         U = len(src_wavs)
+        follows = list(follow) if isinstance(follow, (list, tuple)) else [follow] * U
         levels = list(level) if isinstance(level, (list, tuple)) else [level] * U
         pitches = list(pitch) if isinstance(pitch, (list, tuple)) else [pitch] * U
         ifmts, ofmts, orates, rates = (list(v) if v is not None else [None] * U for v in (in_formats, out_formats, out_rates, in_rates))
@@ -524,7 +552,8 @@ class StreamingVoiceConversionEngine:
                 self.open_slots([live[u][0] for u in new], torch.stack([ref_mel[u] for u in new]) if voice is None else None,
                                 voice=None if voice is None else (voice[0], [voice[1][u] for u in new]), in_rate=[rates[u] for u in new],
                                 out_rate=[orates[u] for u in new], out_filter=out_filter, in_format=[ifmts[u] for u in new],
-                                out_format=[ofmts[u] for u in new], level=[levels[u] for u in new], pitch=[pitches[u] for u in new], **filter)
+                                out_format=[ofmts[u] for u in new], level=[levels[u] for u in new], pitch=[pitches[u] for u in new],
+                                follow=[follows[u] for u in new], **filter)
             if not live:
                 tick += 1
                 continue

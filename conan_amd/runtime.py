@@ -212,6 +212,26 @@ class Context:
             y = y.reshape(*lead, y.shape[-1])
         return (y, trace.reshape(*lead, K, 2)) if return_trace else y
 
+    def f0(self, wav, fmin=50.0, fmax=900.0, threshold=0.15, floor_db=-60.0, fft_size=1024, hop_size=None):
+        """The source-pitch tracker on whole signals (conan_f0; include/conan_hip.h, conan_f0_cfg): wav [..., N] float32 at the model
+        rate (50 * hop_size; hop_size defaults to the vocoder's hop) -> (f0 [..., 1 + N // hop_size] in log2 Hz, 0 where unvoiced;
+        uv [..., frames] 0 | 1): YIN on the mel front-end's centred frames of fft_size samples.  It is what a following wav-in slot
+        (Streams.set_pitch_follow) hands its decoder steps, bit for bit."""
+        dev = torch.device("cuda", self.device)
+        x = wav.to(dev, torch.float32).contiguous()
+        lead, N = x.shape[:-1], x.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        hop = int(hop_size or self.hop)
+        mc = mel_cfg(fft_size=fft_size, hop_size=hop, win_length=fft_size, sample_rate=50 * hop)
+        cfg = _lib.f0_cfg(fmin, fmax, threshold, floor_db)
+        frames = 1 + N // hop
+        f0 = torch.empty(n, frames, device=dev)
+        uv = torch.empty(n, frames, device=dev)
+        got = C.c_int32(0)
+        _lib.check(self.lib.conan_f0(self.h, C.byref(mc), C.byref(cfg), _ptr(x), n, N, _ptr(f0), _ptr(uv), C.byref(got), _stream()))
+        assert got.value == frames
+        return f0.reshape(*lead, frames), uv.reshape(*lead, frames)
+
     def convert_samples(self, x, src, dst, out=None):
         """conan_convert_samples: x [..., N] of format `src` ('f32' float32, 's16' int16, 'ulaw' / 'alaw' uint8) -> [..., N] of
         format `dst`, by the library's one conversion rule (decode exactly, encode with round-to-nearest-even and saturation).
@@ -471,6 +491,7 @@ class Streams:
         self.output_formats = {}         # slot -> the same, for the slots whose audio leaves in another format
         self.input_levels = {}           # slot -> dict of set_input_level's keywords, for the slots with an input leveller
         self.pitch_cfgs = {}             # slot -> dict of set_pitch's keywords, for the slots with a pitch control
+        self._last_wav_n = 0             # rows of the most recent wav-in call (step_wav_contour)
 
     @property
     def state_bytes(self):
@@ -626,6 +647,42 @@ class Streams:
                 self.pitch_cfgs[int(slot)] = _lib.pitch_keywords(c)
             else:
                 self.pitch_cfgs.pop(int(slot), None)
+
+    def set_pitch_follow(self, slots, cfg=True, **kw):
+        """conan_streams_set_pitch_follow: the slots' decoder steps take f0 / uv from the YIN contour of their own input (wav-in steps
+        only), so the converted voice keeps the source's melody; the slots' pitch control (set_pitch) applies on top.  Context.f0's
+        tracker keywords (fmin, fmax, threshold, floor_db) as keywords or as a dict in cfg; those not given keep the defaults.  Only
+        cfg=None turns it off.  It may be called at any time, also mid-utterance (it joins pipelined work); the change takes effect
+        from the next emitted chunk and survives resets.  Slot snapshots do not carry it."""
+        a, p = _i32(slots)
+        if cfg is None:
+            if kw:
+                raise ValueError("set_pitch_follow: cfg=None turns following off and takes no keywords")
+            c = _lib.F0Cfg()      # (enabled = 0)
+        else:
+            c = _lib.f0_cfg(**dict({} if cfg is True else cfg, **kw))
+        _lib.check(self.lib.conan_streams_set_pitch_follow(self.h, p, len(a), C.byref(c), _stream()))
+        self._release()
+
+    def pitch_follow(self, slots):
+        """conan_streams_pitch_follow: per slot the tracker's keywords as set_pitch_follow takes them, None for a slot that does not
+        follow."""
+        out = []
+        for slot in slots:
+            c = _lib.F0Cfg()
+            _lib.check(self.lib.conan_streams_pitch_follow(self.h, int(slot), C.byref(c)))
+            out.append(_lib.f0_keywords(c) if c.enabled else None)
+        return out
+
+    def step_wav_contour(self):
+        """The contour the last wav-in call handed the decoder (conan_step_wav_contour; joins pipelined work) -> (f0 [n, seg] log2 Hz,
+        uv [n, seg]) in call order; rows that do not follow, and entries past a row's emitted frames, are 0."""
+        n = self._last_wav_n
+        f0 = torch.empty(max(n, 1), self.seg, device=self.dev)      # (before any wav-in call the library answers CONAN_ERR_STATE)
+        uv = torch.empty(max(n, 1), self.seg, device=self.dev)
+        _lib.check(self.lib.conan_step_wav_contour(self.h, _ptr(f0), _ptr(uv), _stream()))
+        self._release()
+        return f0[:n], uv[:n]
 
     def pitch(self, slots):
         """conan_streams_pitch: per slot the pitch control's keywords as set_pitch takes them, None for a slot without one."""
@@ -980,6 +1037,7 @@ class Streams:
         if wav_out is None:
             wav_out = torch.empty(n, self.output_ld or self.seg * self.ctx.hop, device=self.dev)
         mc = mel_cfg(**(mel or {}))
+        self._last_wav_n = n
         if pipelined:
             self._keep.append((wav, wav_out, codes, mel_out))
         call(mc, codes, mel_out, wav_out)

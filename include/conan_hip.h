@@ -751,12 +751,78 @@ int conan_streams_pitch(const conan_streams* s, int slot, conan_pitch_cfg* out);
 /* conan_decoder_step_taps with a caller contour: f0_in_dev[n][frames] in log2 Hz (the reference's norm_f0 with pitch_norm 'log'),
  * uv_in_dev[n][frames] (> 0: unvoiced; may be NULL: all voiced) - Conan.forward(content, ref=, f0=, uv=, infer=False).  The slots'
  * pitch control applies on top of the contour.  f0_in_dev == NULL is conan_decoder_step_taps (uv_in_dev is then ignored); taps may be
- * NULL.  The fused chunk steps take no contour: they replace the loop of inference/Conan.py, which passes f0=None. */
+ * NULL.  The fused chunk steps take no caller contour: they replace the loop of inference/Conan.py, which passes f0=None; the wav-in
+ * steps can track the source's own (conan_streams_set_pitch_follow). */
 int conan_decoder_step_pitch(conan_streams* s, const int32_t* slots, int n, int frames, const int32_t* codes_dev, const float* f0_in_dev,
                              const float* uv_in_dev, float* mel_out_dev, const conan_decoder_taps* taps, void* stream);
 /* Host only, no handle: the pitch control a record carries -> 1 and *out = its cfg, or 0 and *out zeroed for a record without one.
  * CONAN_ERR_INVALID for a record that is not one, as conan_slot_meta_info. */
 int conan_slot_meta_pitch(const conan_slot_meta* meta, conan_pitch_cfg* out);
+
+/* Source-pitch following (added within ABI 9: a caller detects it by the exported symbols; no existing struct changes).  A wav-in
+ * slot can drive its decoder steps with the f0 / uv contour of its own input - the reference's Conan.forward(f0=, uv=, infer=False)
+ * seam fed what the model was trained on, an extractor's contour in which an unvoiced frame has f0 = 0 (utils/audio/pitch_extractors.py,
+ * data_gen) - so the converted voice keeps the source speaker's melody.  The reference's extractors are external programs; the tracker
+ * is defined here (tests/f0_ref.py restates it in float64 numpy).  It is YIN (de Cheveigne and Kawahara 2002) on the mel front-end's own
+ * frames, so frame f of the tracker and frame f of the mel cover the same samples.
+ *   Frame.  N = mel.fft_size, hop = mel.hop_size, sr = 50 * hop.  Frame f is x[k] = s[f * hop - N / 2 + k], k = 0 .. N-1, in f64, s = the
+ *     model-rate samples (behind the input resampler and the leveller); zeros before the utterance, and past its end once it is final.
+ *     No window.  1 + samples / hop frames, as conan_wav2mel framing 0.
+ *   Lags and window.  tmin = floor(sr / fmax), tmax = ceil(sr / fmin), W = N - tmax - 1.  tmin < 2, tmax > N / 2 or fmin >= fmax is
+ *     CONAN_ERR_INVALID.
+ *   Difference function.  d(t) = sum_{k < W} (x[k] - x[k + t])^2 for t = 1 .. tmax + 1, in f64, in this difference form (never as
+ *     energies minus a correlation).
+ *   Normalisation.  d'(t) = d(t) * t / sum_{j <= t} d(j), and d'(t) = 1 where that sum is 0.
+ *   Pick.  The first t in [tmin, tmax] with d'(t) < threshold; then t moves on while t + 1 <= tmax and d'(t + 1) < d'(t).  No such t: the
+ *     frame is unvoiced.
+ *   Power gate.  sum_{k < W} x[k]^2 / W < 10^(floor_db / 10): the frame is unvoiced.
+ *   Interpolation.  a, b, c = d'(t - 1), d'(t), d'(t + 1); off = 0.5 * (a - c) / (a - 2 b + c), clamped to +-1, and 0 where the
+ *     denominator is not positive; f0 = sr / (t + off).
+ *   Output.  v = (float)log2(f0) with log2 in f64 - the seam's unit - and uv = 0; an unvoiced frame gives v = 0, uv = 1.
+ * The order of every sum is fixed by (N, tmax) alone: a frame's bits do not depend on the other frames or rows of a launch, which is
+ * why the streaming contour equals conan_f0's of the same samples bit for bit. */
+typedef struct conan_f0_cfg {
+  int32_t enabled;          /* 0: no following for the slots, other fields ignored */
+  float   fmin, fmax;       /* Hz, finite, 0 < fmin < fmax (50 / 900: the range of denorm_f0's clamp) */
+  float   threshold;        /* in (0, 1); YIN's absolute threshold (0.15) */
+  float   floor_db;         /* finite; frames whose mean power is below 10^(floor_db / 10) are unvoiced (-60) */
+  int32_t reserved;         /* must be 0 */
+} conan_f0_cfg;             /* 24 bytes */
+/* The whole-signal form, and the bit-exact yardstick of the streaming one (the role conan_level plays for the leveller): wav_dev[n][samples]
+ * f32 (n in 1 .. 65535, samples >= 1) -> f0_out_dev[n][frames] (log2 Hz, 0 where unvoiced) and uv_out_dev[n][frames] (0 | 1), frames =
+ * 1 + samples / hop (*frames_out, may be NULL).  Of mel only fft_size (a power of two in 64 .. 2048), hop_size and sample_rate (which must
+ * be 50 * hop_size) are read.  cfg->enabled must be 1.  One launch (cnk::f0_yin_kernel, one workgroup per frame) on `stream`. */
+int conan_f0(conan_ctx* ctx, const conan_mel_cfg* mel, const conan_f0_cfg* cfg, const float* wav_dev, int n, int samples, float* f0_out_dev,
+             float* uv_out_dev, int32_t* frames_out, void* stream);
+/* Sets (cfg->enabled = 1) or removes (0) source-pitch following for `slots`.  It may be called at any time, also mid-utterance; every
+ * slot and the cfg are checked before anything changes (the setter has no frame yet: it refuses tmax > 1024, and a wav-in step whose
+ * fft_size gives a following slot tmax > fft_size / 2 is CONAN_ERR_INVALID before anything changes).  A stream-set without the streaming
+ * front-end is CONAN_ERR_STATE.  It joins pending pipelined work, then writes the slots' follow flag - the sixth word of their
+ * pitch-table entries - in the order of `stream`, like conan_streams_set_pitch: the change takes effect from the next emitted chunk.  The
+ * setting persists across resets.
+ * What a following slot does.  Every conan_step_wav[_async] / conan_step_wav_ragged[_ld][_async] call that emits a chunk for it tracks
+ * the chunk's frames from the slot's audio ring - the tracker keeps no state of its own - in ONE more launch per call (f0_yin_kernel,
+ * behind the front-end launch on the same stream, so pipelined calls stay pipelined; calls in which no following slot emits run the
+ * launches they ran before), and the chunk's decoder step takes v and uv of the slot's rows from that contour: no silent-token
+ * forcing, exactly as with a caller contour.  The slot's conan_pitch_cfg (shift, range) then applies on top; its uv_threshold has
+ * nothing to act on.  Precedence: a caller contour (conan_decoder_step_pitch) wins over following; conan_decoder_step[_taps] and the
+ * mel-in fused steps (conan_step, conan_step_async) take no waveform and run the predictor's path for every slot.  A slot that does
+ * not follow keeps its arithmetic and its bits, also in a call mixed with following slots.  The chunk's frames must still be in the
+ * audio ring when the chunk is emitted, which holds for fft_size <= 1024 at the shipped configuration; otherwise the call is
+ * CONAN_ERR_UNSUPPORTED before anything changes.  conan_mel_cfg.sample_rate of such a call must be 50 * hop.
+ * Memory: the first enabling call allocates the contour staging (4 sets of 2 * max_slots * segment floats) and row tables, which
+ * conan_streams_state_bytes counts from then on.  A stream-set that never calls the setter runs exactly the launches it ran before.
+ * Snapshots: the 256-byte host record is full, so a snapshot does NOT carry the follow setting and conan_streams_import_slots leaves the
+ * destination slot's setting alone.  The tracker has no state beyond the audio ring, which snapshots carry: a following stream exported
+ * mid-utterance and imported into a slot given the same setting continues bit for bit; imported into a slot with following off it
+ * continues on the predictor's path. */
+int conan_streams_set_pitch_follow(conan_streams* s, const int32_t* slots, int n, const conan_f0_cfg* cfg, void* stream);
+/* Host only: the follow cfg of `slot` as set (enabled = 0 and zeros for a slot without one). */
+int conan_streams_pitch_follow(const conan_streams* s, int slot, conan_f0_cfg* out);
+/* Test / debug hook in the spirit of conan_step_wav_chunk: the contour the last wav-in call handed the decoder, in call order (joins
+ * first): f0_dev[n][seg] (log2 Hz) and uv_dev[n][seg]; row i holds the frames the call emitted for slot i, zeros behind them; rows that
+ * do not follow or emitted nothing read v = 0, uv = 0. */
+int conan_step_wav_contour(conan_streams* s, float* f0_dev, float* uv_dev, void* stream);
 
 /* Voice bank (added within ABI 9: a caller detects it by the exported symbols; no existing struct or call changes).  A bank holds the
  * result of conan_set_reference's style pass for up to `capacity` target voices in device memory, outside any slot: the style vector,
