@@ -662,17 +662,19 @@ void launch_kmask(const KMaskArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(kmask_kernel, dim3(a.n), dim3(128), 0, st, a);
 }
 
-// temporal_avg_pool (Conan.py:214-219): sum over non-masked frames / count
+// temporal_avg_pool (Conan.py:214-219): sum over non-masked frames / count.  One thread adds a channel's frames one after the other:
+// in float64, so that the sum of a 2048-frame reference carries no rounding of its own (an fp32 chain of n terms drifts by about
+// sqrt(n) * 2^-24 - DESIGN.md 4 has the figures); the mean is rounded to fp32 once.  The pass runs once per utterance.
 __global__ __launch_bounds__(256) void masked_mean_kernel(const MeanArgs a) {
   const int i = blockIdx.x;
   const int slot = a.slots[i];
   const int len = a.lens ? a.lens[i] : a.T;
-  float cnt = 0.f;
-  for (int t = 0; t < len; ++t) cnt += *trowptr(a.m, i, i, nullptr, t) != 0.f ? 1.f : 0.f;
+  int cnt = 0;
+  for (int t = 0; t < len; ++t) cnt += *trowptr(a.m, i, i, nullptr, t) != 0.f ? 1 : 0;
   for (int c = threadIdx.x; c < a.C; c += blockDim.x) {
-    float acc = 0.f;
-    for (int t = 0; t < len; ++t) { float mk = *trowptr(a.m, i, i, nullptr, t); if (mk != 0.f) acc += trowptr(a.x, i, i, nullptr, t)[c]; }
-    a.out[(long long)slot * a.out_stride + c] = acc / cnt;
+    double acc = 0.0;
+    for (int t = 0; t < len; ++t) { float mk = *trowptr(a.m, i, i, nullptr, t); if (mk != 0.f) acc += (double)trowptr(a.x, i, i, nullptr, t)[c]; }
+    a.out[(long long)slot * a.out_stride + c] = (float)(acc / (double)cnt);
   }
 }
 void launch_masked_mean(const MeanArgs& a, hipStream_t st) {
