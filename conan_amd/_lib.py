@@ -142,6 +142,10 @@ _PROTOS = {
     "conan_streams_set_pitch_follow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "conan_streams_pitch_follow": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "conan_step_wav_contour": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_f0_register": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_streams_set_pitch_register": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "conan_streams_pitch_register": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "conan_streams_pitch_register_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "conan_voices_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "conan_voices_destroy": (C.c_int, [C.c_void_p]),
     "conan_voices_enroll": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -342,6 +346,39 @@ def f0_cfg(fmin=50.0, fmax=900.0, threshold=0.15, floor_db=-60.0):
 def f0_keywords(c):
     """f0_cfg's keywords of an enabled F0Cfg: the form Streams.pitch_follow reports a follow setting in."""
     return dict(fmin=c.fmin, fmax=c.fmax, threshold=c.threshold, floor_db=c.floor_db)
+
+
+class RegisterCfg(C.Structure):
+    """conan_register_cfg (include/conan_hip.h)."""
+    _fields_ = [("enabled", C.c_int32), ("reseed", C.c_int32), ("target", C.c_float), ("max_shift", C.c_float), ("seed_count", C.c_int64),
+                ("seed_sum", C.c_int64)]
+
+
+REGISTER_UNIT = 4194304      # 2^22: quantised log2-f0 units per octave
+
+
+def register_quantise(v):
+    """q of the law for a log2-Hz value: llrint((double)(float)v * 2^22), a Python int."""
+    return int(round(C.c_float(v).value * float(REGISTER_UNIT)))      # (the product is exact in f64; round() ties to even, as llrint)
+
+
+def register_cfg(target, max_shift=2.0, prior=None, prior_frames=50, seed=None, reseed=False):
+    """An enabled conan_register_cfg: move the slot's mean log-f0 to `target` (log2 Hz), by at most max_shift octaves.  The estimate
+    starts from seed = (count, sum) where given - a queried state: the hand-over - and else from the prior: prior_frames voiced frames
+    at `prior` (log2 Hz; default: the target, so the shift starts at 0)."""
+    if target is None:
+        raise ValueError("register: target= (log2 Hz) is required")
+    if seed is not None:
+        count, total = (int(x) for x in seed)
+    else:
+        count = int(prior_frames)
+        total = count * register_quantise(target if prior is None else prior)
+    return RegisterCfg(1, int(bool(reseed)), float(target), float(max_shift), count, total)
+
+
+def register_keywords(c):
+    """register_cfg's keywords of an enabled RegisterCfg: the form a register setting is reported in."""
+    return dict(target=c.target, max_shift=c.max_shift, seed=(int(c.seed_count), int(c.seed_sum)))
 
 
 class DecoderTaps(C.Structure):

@@ -346,6 +346,8 @@ int conan_streams_reset(conan_streams* s, const int32_t* slots, int n, int which
       // the input rate stays; the resampler's history restarts (inputs before the first are zero, the ring needs no clearing)
       if (!s->wav_in.rs_slot.empty())
         for (int i = 0; i < n; ++i) { conan_streams::RsSlot& r = s->wav_in.rs_slot[slots[i]]; r.in = 0; r.out = 0; r.phase = 0; }
+      // the register setting stays; the estimate restarts from its seed in the slot's next register row (a host flag: no launch here)
+      for (int i = 0; i < n && !s->reg.pending.empty(); ++i) s->reg.pending[slots[i]] = 1;
     }
   });
 }
@@ -457,6 +459,21 @@ int conan_streams_set_pitch_follow(conan_streams* s, const int32_t* slots, int n
 int conan_streams_pitch_follow(const conan_streams* s, int slot, conan_f0_cfg* out) { return guarded([&] { f0::get_follow(s, slot, out); }); }
 
 int conan_step_wav_contour(conan_streams* s, float* f0_dev, float* uv_dev, void* stream) { return guarded([&] { f0::contour(s, f0_dev, uv_dev, stream); }); }
+
+int conan_f0_register(conan_ctx* ctx, const conan_register_cfg* cfg, const float* f0_dev, const float* uv_dev, int n, const int32_t* frames, int64_t ld,
+                      float* f0_out_dev, int64_t* state_out_dev, void* stream) {
+  return guarded([&] { reg::whole(ctx, cfg, f0_dev, uv_dev, n, frames, ld, f0_out_dev, state_out_dev, stream); });
+}
+
+int conan_streams_set_pitch_register(conan_streams* s, const int32_t* slots, int n, const conan_register_cfg* cfg, void* stream) {
+  return guarded([&] { reg::set_register(s, slots, n, cfg, stream); });
+}
+
+int conan_streams_pitch_register(const conan_streams* s, int slot, conan_register_cfg* cfg_out) { return guarded([&] { reg::get_register(s, slot, cfg_out); }); }
+
+int conan_streams_pitch_register_state(conan_streams* s, const int32_t* slots, int n, int64_t* state_dev, void* stream) {
+  return guarded([&] { reg::state(s, slots, n, state_dev, stream); });
+}
 
 int conan_streams_set_pitch(conan_streams* s, const int32_t* slots, int n, const conan_pitch_cfg* cfg, void* stream) {
   return guarded([&] { pitch::set_pitch(s, slots, n, cfg, stream); });

@@ -469,6 +469,20 @@ struct F0Args {
 constexpr int kF0MaxFft = 2048;
 void launch_f0(const F0Args& a, hipStream_t st);
 
+// Register matching (register.hip; include/conan_hip.h, conan_register_cfg): one workgroup per row.  A row reads its nframes frames at
+// f0 / uv [in_off + j] and starts from state[slot] (reseed = 0 and slot >= 0) or from its seed; it writes the matched values to
+// out[out_off + j] (out_off < 0: none), the state after the row to state[slot] (slot >= 0) and to state_out[state_row] (state_row >= 0).
+struct RegRow { long long seed_n, seed_S, in_off, out_off; int nframes, slot, reseed, state_row; float target, max_shift; int pad_[2]; };
+static_assert(sizeof(RegRow) == 64, "uploaded as 16 ints");
+struct RegArgs {
+  const float* f0; const float* uv; float* out;
+  long long* state;          // [max_slots][2] = (n, S), indexed by slot; may be null when no row names a slot
+  long long* state_out;      // [rows][2]; may be null when no row has a state_row
+  const RegRow* tab; int rows;
+};
+constexpr int kRegThreads = 256;
+void launch_f0_register(const RegArgs& a, hipStream_t st);
+
 // y = leaky_relu((x0 + x1 + x2) / nsrc): the MRF mean of HifiGanGenerator.forward (hifigan_causal.py:324-331) with the
 // following LeakyReLU, materialised once so that the consuming conv runs the single-source direct-to-LDS path.
 struct MeanActArgs { TRef x[3]; TRef y; const int* slots; const int* pos; int nsrc, T, n, C; float slope; };

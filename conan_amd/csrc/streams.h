@@ -212,6 +212,21 @@ struct conan_streams {
     bool on(int slot) const { return n_on > 0 && cfg[slot].enabled; }
   } follow;
   void follow_init();
+  // register matching (conan_streams_set_pitch_register; register.hip): per slot its cfg as set (enabled = 0: none; reseed kept 0),
+  // which persists across resets; n_on: slots with one.  pending: the slot's estimate restarts from the cfg's seed in its next
+  // register row (set by an enabling or reseeding setter call and by a reset with CONAN_MODEL_FRONTEND; a host flag, no launch).
+  // state: [max_slots][2] = (n, S) on the device, read and written by the rows of f0_register_kernel in the order of the front-end
+  // launches.  Per call a row table (set q of `sets`; the set's event follows the kernel's launch).  Allocated by the first enabling
+  // call; state and row tables count as stream state.
+  struct Register {
+    std::vector<conan_register_cfg> cfg;
+    std::vector<char> pending;
+    int n_on = 0;
+    long long* state = nullptr;
+    StageSets<cnk::RegRow> sets;
+    bool on(int slot) const { return n_on > 0 && cfg[slot].enabled; }
+  } reg;
+  void register_init();
   void ragged_init();
   void resample_init();        // staging, row tables and the history ring (conan_streams_set_input_rate)
   void rs_stage_init();        // staging and row tables only (conan_streams_set_input_format: no stream state)
@@ -549,6 +564,17 @@ void set_follow(conan_streams* s, const int32_t* slots, int n, const conan_f0_cf
 void get_follow(const conan_streams* s, int slot, conan_f0_cfg* out);
 void contour(conan_streams* s, float* f0_dev, float* uv_dev, void* stream);
 }  // namespace f0
+
+// ---- register matching (register.hip): the kernel's host side and the bodies of api.hip's entry points
+namespace reg {
+void check_cfg(const conan_register_cfg& c, const char* who);      // host only
+cnk::RegRow row(const conan_register_cfg& c);      // the cfg's fields of a kernel row that starts from the seed and names no slot
+void whole(conan_ctx* ctx, const conan_register_cfg* cfg, const float* f0_dev, const float* uv_dev, int n, const int32_t* frames, int64_t ld,
+           float* f0_out_dev, int64_t* state_out_dev, void* stream);
+void set_register(conan_streams* s, const int32_t* slots, int n, const conan_register_cfg* cfg, void* stream);
+void get_register(const conan_streams* s, int slot, conan_register_cfg* out);
+void state(conan_streams* s, const int32_t* slots, int n, int64_t* state_dev, void* stream);
+}  // namespace reg
 
 // ---- per-slot pitch control (pitch.hip): the bodies of api.hip's entry points
 namespace pitch {

@@ -311,6 +311,8 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
   std::vector<conan_streams::Follow::LastRow> f0_last;
   std::vector<char> f0_group(groups.size(), 0);
   int f0_jobs = 0;
+  // register matching (register.hip): every such row whose slot has the register on gets a row that rewrites its place in the contour
+  std::vector<cnk::RegRow> reg_rows;
   if (s->follow.n_on > 0) {
     const double sr = 50.0 * hop;
     for (int i = 0; i < n; ++i) {
@@ -332,6 +334,11 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
         f0_rows.push_back(r);
         f0_last.push_back({i, 0, off + k, p.emit});
         f0_group[g] = 1;
+        if (s->reg.on(slots[i])) {
+          cnk::RegRow rr = reg::row(s->reg.cfg[slots[i]]);
+          rr.in_off = r.out_off; rr.out_off = r.out_off; rr.nframes = p.emit; rr.slot = slots[i]; rr.reseed = s->reg.pending[slots[i]];
+          reg_rows.push_back(rr);
+        }
       }
   }
   const int nm_in = m.num_mels, nm = c.num_mels;
@@ -371,6 +378,7 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
   if (P.launch || lv_stages) rq = s->wav_in.rs_sets.begin(P.rows.data(), n, cst);      // (a leveller alone takes the set for its staging)
   const int lq = lv_rows.empty() ? 0 : s->wav_in.lv_sets.begin(lv_rows.data(), (int)lv_rows.size(), cst);
   const int fq = f0_rows.empty() ? 0 : s->follow.sets.begin(f0_rows.data(), (int)f0_rows.size(), cst);
+  const int gq = reg_rows.empty() ? 0 : s->reg.sets.begin(reg_rows.data(), (int)reg_rows.size(), cst);
   const int* rg_tab = reinterpret_cast<const int*>(s->wav_in.rg_sets.rows[q]);
   std::function<void(hipStream_t)> front;
   if (run) {
@@ -431,6 +439,18 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
       s->profiled("f0_yin_kernel", flops, st, [&] { cnk::launch_f0(a, st); });
     };
   }
+  // register matching, directly behind the tracker: the decoder stage reads the matched rows
+  if (!reg_rows.empty()) {
+    cnk::RegArgs a;
+    memset(&a, 0, sizeof(a));
+    a.f0 = s->follow.ct_f0[fq]; a.uv = s->follow.ct_uv[fq]; a.out = s->follow.ct_f0[fq]; a.state = s->reg.state;
+    a.tab = s->reg.sets.rows[gq]; a.rows = (int)reg_rows.size();
+    front = [s, a, gq, f0_front = front](hipStream_t st) {
+      f0_front(st);
+      s->profiled("f0_register_kernel", 0.0, st, [&] { cnk::launch_f0_register(a, st); });
+      s->reg.sets.end(gq, st);
+    };
+  }
   cnk::WavScatterArgs sc;
   sc.tab = rg_tab; sc.n = n; sc.seg = seg; sc.nm = nm; sc.hop = hop;
   sc.codes_src = s->wav_in.rg_codes[q]; sc.mel_src = s->wav_in.rg_mel[q]; sc.wav_src = s->wav_in.rg_wav[q];
@@ -470,6 +490,7 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
   if (!f0_rows.empty()) s->follow.sets.end(fq, piped ? s->st_front : cst);      // (behind the call's last decoder step, the contour's last reader)
   for (conan_streams::Follow::LastRow& r : f0_last) r.set = fq;
   s->follow.last = std::move(f0_last);
+  for (const cnk::RegRow& rr : reg_rows) s->reg.pending[rr.slot] = 0;      // (the rows carried the restarts)
   if (scatter && !route) {      // (each group's step counted its own rows, in group order: back to the call's rows)
     s->wav_out.out_counts.assign(n, 0);
     for (int i = 0; i < n; ++i) s->wav_out.out_counts[i] = pl[i].emit * hop;

@@ -222,6 +222,7 @@ class StreamingVoiceConversionEngine:
         self.slots = list(range(n_streams))
         self.seg, self.rc = ctx.cfg.emf_segment, ctx.cfg.emf_right_context
         self._followed = False      # set_pitch_follow has been called on the stream-set
+        self._registered = False    # set_pitch_register has been called on the stream-set
 
     @staticmethod
     def _check_voice(ref_mel, voice):
@@ -268,7 +269,7 @@ class StreamingVoiceConversionEngine:
         self._set_pitch(self.slots, pitch)
 
     def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                  pitch=None, voice=None, follow=None, **filter):
+                  pitch=None, voice=None, follow=None, register=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
         in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
         in_format: the input's sample format (None: float32; 's16' takes int16 rows, 'ulaw' / 'alaw' uint8), decoded on the GPU.
@@ -278,8 +279,12 @@ class StreamingVoiceConversionEngine:
         pitch, voice: as in start().
         follow: source-pitch following (Streams.set_pitch_follow) - None / False: none; True: the tracker's defaults; a dict of its
         keywords (fmin, fmax, threshold, floor_db).  The decoder steps then take f0 / uv from the input's own contour, tracked on the
-        GPU on the samples the front-end reads; `pitch` applies on top."""
+        GPU on the samples the front-end reads; `pitch` applies on top.
+        register: register matching for following slots (Streams.set_pitch_register) - None / False: none; a float: the target in
+        log2 Hz; "voice": bank.registers[id] of the slot's voice=(bank, ids) (VoiceBank.enroll_wav(register=True)); a dict of
+        set_pitch_register's keywords.  The followed contour is then moved to the target's register by a causal log-f0 mean."""
         self._check_voice(ref_mel, voice)
+        registers = self._registers(self.slots, register, voice)
         if isinstance(in_format, (list, tuple)) or isinstance(level, (list, tuple)):
             raise ValueError("in_format / level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
         self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice)
@@ -287,6 +292,55 @@ class StreamingVoiceConversionEngine:
         self._set_format(self.slots, in_format, self.st.input_formats, self.st.set_input_format)
         self._set_level(self.slots, level)
         self._set_follow(self.slots, follow)
+        self._set_register(self.slots, registers)
+
+    @staticmethod
+    def _registers(slots, register, voice):
+        """register= (one value or one per slot) -> per slot None or a dict of Streams.set_pitch_register's keywords.  Host only:
+        "voice" is looked up in bank.registers of voice = (bank, ids) and is a ValueError where that has nothing to give."""
+        values = list(register) if isinstance(register, (list, tuple)) else [register] * len(slots)
+        if len(values) != len(slots):
+            raise ValueError(f"register: {len(values)} values for {len(slots)} slots")
+        out = []
+        for k, r in enumerate(values):
+            if r is None or r is False:
+                out.append(None)
+            elif isinstance(r, str):
+                if r != "voice":
+                    raise ValueError(f"register: {r!r} (a target in log2 Hz, 'voice', a dict of set_pitch_register's keywords or None)")
+                if voice is None:
+                    raise ValueError("register='voice' needs voice=(bank, ids)")
+                bank, ids = voice
+                if len(ids) != len(slots):
+                    raise ValueError(f"register='voice': {len(ids)} voice ids for {len(slots)} slots")
+                target = bank.registers.get(int(ids[k]))
+                if target is None:
+                    raise ValueError(f"register='voice': voice {int(ids[k])} has no register (VoiceBank.enroll_wav(register=True))")
+                out.append(dict(target=target))
+            elif isinstance(r, dict):
+                out.append(dict(r))
+            else:
+                out.append(dict(target=float(r)))
+        return out
+
+    def _set_register(self, slots, registers):
+        """The slots' register matching from _registers' list, behind the slots' reset: the estimates restart from their seeds at
+        the first emitted chunk.  A stream-set that never used it is left alone."""
+        if all(r is None for r in registers) and not self._registered:
+            return
+        self._registered = True
+        for slot, r in zip(slots, registers):
+            if r is None:
+                self.st.set_pitch_register([slot], cfg=None)
+            else:
+                self.st.set_pitch_register([slot], cfg=r)
+
+    def set_pitch_register(self, slots=None, **kw):
+        """A live change of the slots' register matching (all slots by default) between feed / feed_ragged calls, also mid-utterance
+        and with pipelined steps in flight: Streams.set_pitch_register's keywords (cfg=None turns it off; without reseed=True an
+        enabled slot keeps its estimate: the voice change in the middle of a call).  In force from the next emitted chunk."""
+        self._registered = True
+        self.st.set_pitch_register(self.slots if slots is None else slots, **kw)
 
     def _set_follow(self, slots, follow):
         """The slots' source-pitch following (None / False: none; True: the defaults; a dict of Streams.set_pitch_follow's keywords),
@@ -429,7 +483,7 @@ class StreamingVoiceConversionEngine:
 
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
-                  out_format=None, loud_norm=False, level=None, pitch=None, voice=None, follow=None, **filter):
+                  out_format=None, loud_norm=False, level=None, pitch=None, voice=None, follow=None, register=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] (or None with voice = (bank, ids): start) -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
@@ -440,12 +494,14 @@ class StreamingVoiceConversionEngine:
         float32 rows only); the results are those of infer_wav(ctx.loud_norm(src_wav, rate), ...) bit for bit.
         level: the streaming input leveller (start_wav); the results are those of infer_wav(ctx.level(x, **level), ...) bit for bit,
         x = the decoded, resampled utterance.  pitch: the slots' pitch control in the decoder step (start).  follow: source-pitch
-        following (start_wav): the decoder steps take ctx.f0 of the samples the front-end reads instead of the predictor's contour."""
+        following (start_wav): the decoder steps take ctx.f0 of the samples the front-end reads instead of the predictor's contour.
+        register: register matching of the followed contour (start_wav): the steps take ctx.f0_register of that contour."""
         self._check_voice(ref_mel, voice)
+        self._registers(self.slots, register, voice)      # (host checks before anything runs)
         if loud_norm:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
-                       pitch=pitch, voice=voice, follow=follow, **filter)
+                       pitch=pitch, voice=voice, follow=follow, register=register, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -472,7 +528,7 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                   pitch=None, voice=None, follow=None, **filter):
+                   pitch=None, voice=None, follow=None, register=None, **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
         rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
@@ -480,8 +536,10 @@ class StreamingVoiceConversionEngine:
         value or one per slot.  level: the slots' input leveller (start_wav), one value or a list with one per slot.  pitch: the
         slots' pitch control (start), one value or a list with one per slot.  voice: (bank, ids) - enrolled voices, one id per slot, in
         place of ref_mel (then None): one launch instead of a style pass per slot.  follow: the slots' source-pitch following
-        (start_wav), one value or a list with one per slot."""
+        (start_wav), one value or a list with one per slot.  register: the slots' register matching (start_wav), one value or a list
+        with one per slot."""
         self._check_voice(ref_mel, voice)
+        registers = self._registers(slots, register, voice)
         self.st.reset(slots, which=7 | 8)
         self._reference(slots, ref_mel, ref_len, voice)
         self._set_out_rate(slots, out_rate, out_filter)
@@ -492,6 +550,7 @@ class StreamingVoiceConversionEngine:
         self._set_level(slots, level)
         self._set_pitch(slots, pitch)
         self._set_follow(slots, follow)
+        self._set_register(slots, registers)
 
     @torch.no_grad()
     def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None):
@@ -510,7 +569,8 @@ class StreamingVoiceConversionEngine:
 
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
-                            in_formats=None, out_formats=None, loud_norm=False, level=None, pitch=None, voice=None, follow=None, **filter):
+                            in_formats=None, out_formats=None, loud_norm=False, level=None, pitch=None, voice=None, follow=None, register=None,
+                            **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -524,9 +584,11 @@ class StreamingVoiceConversionEngine:
         streaming input leveller (start_wav), one value for every utterance or a list with one per utterance.  pitch: the pitch
         control (start), one value for every utterance or a list with one per utterance.  voice: (bank, ids) - one enrolled id per
         utterance, in place of ref_mel (then None).  follow: source-pitch following (start_wav), one value for every
-        utterance or a list with one per utterance."""
+        utterance or a list with one per utterance.  register: register matching (start_wav), one value for every utterance or a list
+        with one per utterance."""
         voice = self._check_voice(ref_mel, voice)
         U = len(src_wavs)
+        registers = self._registers(range(U), register, voice)      # (host checks before anything runs; per utterance, as dicts)
         follows = list(follow) if isinstance(follow, (list, tuple)) else [follow] * U
         levels = list(level) if isinstance(level, (list, tuple)) else [level] * U
         pitches = list(pitch) if isinstance(pitch, (list, tuple)) else [pitch] * U
@@ -553,7 +615,7 @@ class StreamingVoiceConversionEngine:
                                 voice=None if voice is None else (voice[0], [voice[1][u] for u in new]), in_rate=[rates[u] for u in new],
                                 out_rate=[orates[u] for u in new], out_filter=out_filter, in_format=[ifmts[u] for u in new],
                                 out_format=[ofmts[u] for u in new], level=[levels[u] for u in new], pitch=[pitches[u] for u in new],
-                                follow=[follows[u] for u in new], **filter)
+                                follow=[follows[u] for u in new], register=[registers[u] for u in new], **filter)
             if not live:
                 tick += 1
                 continue

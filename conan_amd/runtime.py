@@ -232,6 +232,40 @@ class Context:
         assert got.value == frames
         return f0.reshape(*lead, frames), uv.reshape(*lead, frames)
 
+    def f0_register(self, f0, uv, target=None, max_shift=2.0, prior=None, prior_frames=50, seed=None, lengths=None):
+        """Register matching on whole contours (conan_f0_register; include/conan_hip.h, conan_register_cfg): f0 / uv [..., T] as
+        Context.f0 returns them -> (matched [..., T], state [..., 2] int64 = (n, S) after each row): the causal log-f0 mean transform
+        that moves each row's mean log-f0 towards `target` (log2 Hz).  The estimate starts from seed = (count, sum) or from
+        prior_frames frames at `prior` (default: the target).  target=None is the pure measurement: no contour comes back (None) and
+        the estimate starts from (0, 0) unless a seed or a prior is given; a row's mean is S / (n * 2^22).  lengths: frames per row
+        (default T).  It is what a following wav-in slot with Streams.set_pitch_register hands its decoder steps, bit for bit."""
+        dev = torch.device("cuda", self.device)
+        x = f0.to(dev, torch.float32).contiguous()
+        u = uv.to(dev, torch.float32).contiguous()
+        if u.shape != x.shape:
+            raise ValueError(f"f0_register: f0 {tuple(x.shape)} and uv {tuple(u.shape)} differ in shape")
+        lead, T = x.shape[:-1], x.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        lens = np.full(n, T, dtype=np.int32) if lengths is None else np.ascontiguousarray(np.asarray(lengths, dtype=np.int32).reshape(-1))
+        if lens.shape[0] != n:
+            raise ValueError(f"f0_register: {lens.shape[0]} lengths for {n} rows")
+        if target is None:
+            cfg = _lib.register_cfg(0.0, max_shift, prior=prior, prior_frames=0 if prior is None else prior_frames, seed=seed)
+        else:
+            cfg = _lib.register_cfg(target, max_shift, prior=prior, prior_frames=prior_frames, seed=seed)
+        out = torch.empty_like(x) if target is not None else None
+        state = torch.empty(n, 2, dtype=torch.int64, device=dev)
+        _lib.check(self.lib.conan_f0_register(self.h, C.byref(cfg), _ptr(x), _ptr(u), n, lens.ctypes.data_as(C.c_void_p), T, _ptr(out), _ptr(state),
+                                              _stream()))
+        return out, state.reshape(*lead, 2)
+
+    def register_of(self, wav, **f0_keywords):
+        """The register of wav [n, N] (or [N]) at the model rate: per row the mean log2 Hz of its voiced frames - Context.f0 followed
+        by the measurement of f0_register - or None for a row without a counted frame.  **f0_keywords: Context.f0's."""
+        f0, uv = self.f0(wav, **f0_keywords)
+        _, state = self.f0_register(f0, uv)
+        return [int(S) / (int(k) * float(_lib.REGISTER_UNIT)) if k else None for k, S in state.reshape(-1, 2).cpu().tolist()]
+
     def convert_samples(self, x, src, dst, out=None):
         """conan_convert_samples: x [..., N] of format `src` ('f32' float32, 's16' int16, 'ulaw' / 'alaw' uint8) -> [..., N] of
         format `dst`, by the library's one conversion rule (decode exactly, encode with round-to-nearest-even and saturation).
@@ -385,6 +419,7 @@ class VoiceBank:
         _lib.check(self.lib.conan_voices_create(ctx.h, self.capacity, self.max_ref_frames, C.byref(h)))
         self.h = h
         self.dev = torch.device("cuda", ctx.device)
+        self.registers = {}      # id -> mean log2 Hz of the enrolled waveform (enroll_wav(register=True)); host only
 
     def enroll(self, ids, ref_mel, ref_len=None, via=None):
         """conan_voices_enroll: the style pass of ref_mel [n, Tr, num_mels] (as Streams.set_reference) into entries `ids`, one voice
@@ -405,10 +440,14 @@ class VoiceBank:
             raise ValueError(f"VoiceBank.enroll: {len(l)} lengths for {n} reference mels")
         _lib.check(self.lib.conan_voices_enroll(self.h, via.h, p, n, _ptr(ref_mel), lp, tr, _stream()))
         via._release()
+        for i in a:
+            self.registers.pop(int(i), None)      # (the id holds another voice now; enroll_wav(register=True) measures it)
 
-    def enroll_wav(self, ids, wav, via=None, sample_rate=None, loud_norm=False, **mel):
+    def enroll_wav(self, ids, wav, via=None, sample_rate=None, loud_norm=False, register=False, **mel):
         """Context.wav2mel of wav [n, samples] - resampled from sample_rate to the mel front-end's rate and loudness-normalised
-        first where asked - then enroll.  **mel: wav2mel's keywords."""
+        first where asked - then enroll.  **mel: wav2mel's keywords.  register=True also measures each voice's register
+        (Context.register_of of the same prepared wav, which must then be at the model rate) into the host dict self.registers[id] -
+        what register="voice" of the engine's wav-in calls looks up; export / import_voices do not carry it."""
         rate = int(mel.get("sample_rate", 16000))
         wav = wav.to(self.dev, torch.float32)
         if wav.dim() == 1:
@@ -418,10 +457,15 @@ class VoiceBank:
         if loud_norm:
             wav = self.ctx.loud_norm(wav, rate)
         self.enroll(ids, self.ctx.wav2mel(wav, **mel), via=via)
+        if register:
+            for i, r in zip(ids, self.ctx.register_of(wav, hop_size=mel.get("hop_size"))):
+                self.registers[int(i)] = r
 
     def remove(self, ids):
         a, p = _i32(ids)
         _lib.check(self.lib.conan_voices_remove(self.h, p, len(a)))
+        for i in a:
+            self.registers.pop(int(i), None)
 
     def info(self, id):
         """conan_voices_info: dict(ref_frames, tokens, bytes) of an enrolled id, None for one that holds no voice."""
@@ -672,6 +716,54 @@ class Streams:
             c = _lib.F0Cfg()
             _lib.check(self.lib.conan_streams_pitch_follow(self.h, int(slot), C.byref(c)))
             out.append(_lib.f0_keywords(c) if c.enabled else None)
+        return out
+
+    def set_pitch_register(self, slots, target=None, cfg=True, max_shift=2.0, prior=None, prior_frames=50, seed=None, reseed=False):
+        """conan_streams_set_pitch_register: register matching for slots that follow (set_pitch_follow) - the causal log-f0 mean
+        transform moves each slot's mean log-f0 to `target` (log2 Hz; VoiceBank.registers / Context.register_of of the target voice)
+        by at most max_shift octaves, so a converted voice sits in the target's register, not the source's.  The estimate starts
+        from seed = (count, sum) - a state queried with pitch_register: the hand-over - or from prior_frames frames at `prior`
+        (default: the target).  cfg: a dict of these keywords instead; cfg=None turns it off.  It restarts from the seed when a slot
+        is enabled, after reseed=True and at the first chunk after a reset of the front-end; a call with reseed=False on an enabled
+        slot changes target / max_shift from the next emitted chunk and keeps the estimate.  Slot snapshots do not carry it."""
+        a, p = _i32(slots)
+        if cfg is None:
+            c = _lib.RegisterCfg()      # (enabled = 0)
+        else:
+            kw = dict(target=target, max_shift=max_shift, prior=prior, prior_frames=prior_frames, seed=seed, reseed=reseed)
+            if cfg is not True:
+                kw.update(cfg)
+            c = _lib.register_cfg(**kw)
+        _lib.check(self.lib.conan_streams_set_pitch_register(self.h, p, len(a), C.byref(c), _stream()))
+        self._release()
+
+    def pitch_register(self, slots):
+        """Per slot dict(target, max_shift, count, sum, mean, shift) - the setting (conan_streams_pitch_register) and the estimate
+        (conan_streams_pitch_register_state; joins pipelined work, synchronises): (count, sum) = the state, mean = sum / (count * 2^22)
+        in log2 Hz and shift = the clamped target - mean in octaves (None while count is 0) - or None for a slot without the register."""
+        slots = [int(x) for x in slots]
+        cfgs = []
+        for slot in slots:
+            c = _lib.RegisterCfg()
+            _lib.check(self.lib.conan_streams_pitch_register(self.h, slot, C.byref(c)))
+            cfgs.append(c if c.enabled else None)
+        on = [slot for slot, c in zip(slots, cfgs) if c is not None]
+        states = {}
+        if on:
+            a, p = _i32(on)
+            buf = torch.empty(len(on), 2, dtype=torch.int64, device=self.dev)
+            _lib.check(self.lib.conan_streams_pitch_register_state(self.h, p, len(on), _ptr(buf), _stream()))
+            self._release()
+            states = dict(zip(on, buf.cpu().tolist()))
+        out = []
+        for slot, c in zip(slots, cfgs):
+            if c is None:
+                out.append(None)
+                continue
+            k, S = states[slot]
+            mean = S / (k * float(_lib.REGISTER_UNIT)) if k else None
+            shift = None if mean is None else min(max(c.target - mean, -c.max_shift), c.max_shift)
+            out.append(dict(target=c.target, max_shift=c.max_shift, count=k, sum=S, mean=mean, shift=shift))
         return out
 
     def step_wav_contour(self):

@@ -824,6 +824,64 @@ int conan_streams_pitch_follow(const conan_streams* s, int slot, conan_f0_cfg* o
  * do not follow or emitted nothing read v = 0, uv = 0. */
 int conan_step_wav_contour(conan_streams* s, float* f0_dev, float* uv_dev, void* stream);
 
+/* Register matching for pitch following (added within ABI 9: a caller detects it by the exported symbols; no existing struct changes).
+ * A following slot keeps the source's melody and with it the source's register: a low-pitched speaker converted to a high-pitched
+ * voice comes out an octave too low.  The remedy is the log-f0 mean transform of voice conversion - subtract the source's mean log-f0,
+ * add the target's - with a causal, streaming estimate of the source's mean.  The law (tests/register_ref.py restates it in numpy with
+ * Python integers).  Per slot the state is two 64-bit integers (n, S): the voiced frames counted so far and the sum of their quantised
+ * log2-f0.  For every frame of the slot's tracked contour, in stream order, with (v, uv) as the tracker wrote them:
+ *   Counted frame.  uv == 0, v finite and |v| <= 64.  Every other frame passes through unchanged and leaves the state alone.
+ *   Quantisation.  q = llrint((double)v * 4194304.0) (2^22).  An f32 in [2, 16) has a unit in the last place of at least 2^-22, so q is
+ *     exact for every value the tracker can produce (3.96 .. 13.97 at the shipped rate).
+ *   Accumulation.  n += 1; S += q, in int64.  With |q| <= 2^28 the sums are exact and associative for any number of frames the library
+ *     accepts in one call.
+ *   Estimate.  mu = (double)S / ((double)n * 4194304.0), the frame itself included.
+ *   Shift.  d = (double)target - mu; d = fmin(fmax(d, -(double)max_shift), (double)max_shift).
+ *   Result.  v' = (float)((double)v + d); uv stays 0.
+ * Every step is one correctly rounded IEEE operation and the sums are exact integers: the result does not depend on how the frames
+ * are cut into calls, how many lanes scan them or which other rows share the launch, and the GPU and the reference agree bit for
+ * bit.  That is why the streamed form equals the whole-signal form.
+ * The seed is what (n, S) starts from.  As a prior: seed_count = 50, seed_sum = 50 * llrint(target * 2^22) assumes the source sits in
+ * the target's register with the weight of one second of voiced speech - the shift starts at 0 and converges as
+ * (target - v_src) * n / (50 + n) for a steady source.  As a hand-over: a stream whose (n, S) was queried continues on another slot,
+ * stream-set or process bit for bit when those two numbers are given as the seed. */
+typedef struct conan_register_cfg {
+  int32_t enabled;      /* 0: no matching for the slots, other fields ignored */
+  int32_t reseed;       /* 1: the estimate restarts from the seed; 0: it continues (a slot that had none starts from the seed) */
+  float   target;       /* log2 Hz, finite: where the slot's mean log-f0 is moved to */
+  float   max_shift;    /* octaves, finite, >= 0: clamp of |d| */
+  int64_t seed_count;   /* 0 .. 2^34 (the bound keeps the int64 sums from overflowing) */
+  int64_t seed_sum;     /* units of 2^-22 octave; |seed_sum| <= seed_count * 2^28 */
+} conan_register_cfg;   /* 32 bytes */
+/* The whole-signal form, and the bit-exact yardstick of the streaming one: row i of f0_dev / uv_dev [n][ld] holds frames[i] (host,
+ * 0 .. ld) frames of a contour as conan_f0 writes it; every row starts from the seed.  f0_out_dev[n][ld] receives the matched contour
+ * (may equal f0_dev; NULL: the pure measurement), state_out_dev[n][2] = (n, S) after the row (may be NULL).  The measurement is how a
+ * caller obtains a target voice's register: its mean is S / (n * 2^22).  cfg->enabled must be 1, n is 1 .. 65535.  One launch
+ * (cnk::f0_register_kernel, one workgroup per row) on `stream`. */
+int conan_f0_register(conan_ctx* ctx, const conan_register_cfg* cfg, const float* f0_dev, const float* uv_dev, int n, const int32_t* frames,
+                      int64_t ld, float* f0_out_dev, int64_t* state_out_dev, void* stream);
+/* Sets (cfg->enabled = 1) or removes (0) register matching for `slots`; every argument is checked before anything changes, a
+ * stream-set without the streaming front-end is CONAN_ERR_STATE, and pending pipelined work is joined.  What a slot with the register
+ * on AND following on does: in every wav-in call that emits a chunk for it, cnk::f0_register_kernel rewrites the chunk's rows of the
+ * call's contour staging directly behind f0_yin_kernel on the same stream - ONE more launch per call in which such a row emits, none
+ * otherwise - so the decoder step and conan_step_wav_contour read the matched values and pipelined calls stay pipelined.  A slot with
+ * the register on but following off has no contour: nothing happens to it.  The setting persists across resets.
+ * The estimate restarts from the seed at the slot's first emitted chunk after a reset that includes CONAN_MODEL_FRONTEND, after a
+ * setter call with reseed = 1 and after a setter call that enables a slot that was off.  A setter call with reseed = 0 on an enabled
+ * slot changes target / max_shift (and the seed of later restarts) from the next emitted chunk and keeps the estimate: the voice
+ * change in the middle of a call.
+ * Memory: the first enabling call allocates 16 bytes of state per slot and 4 row tables of 64 bytes per slot, which
+ * conan_streams_state_bytes counts from then on.  A stream-set that never calls the setter runs exactly the launches it ran before.
+ * Snapshots carry neither the setting nor the estimate (the 256-byte host record is full), as they do not carry the follow setting;
+ * conan_streams_layout_id and conan_streams_snapshot_bytes do not change.  The hand-over: conan_streams_pitch_register_state, export,
+ * import, conan_streams_set_pitch_follow, then conan_streams_set_pitch_register with seed = the queried pair and reseed = 1. */
+int conan_streams_set_pitch_register(conan_streams* s, const int32_t* slots, int n, const conan_register_cfg* cfg, void* stream);
+/* Host only: the register cfg of `slot` as set, reseed = 0 (enabled = 0 and zeros for a slot without one). */
+int conan_streams_pitch_register(const conan_streams* s, int slot, conan_register_cfg* cfg_out);
+/* The estimates of `slots` -> state_dev[n][2] = (n, S), in the order of `stream` behind a join of pipelined work; a slot whose
+ * estimate is about to restart reports its seed.  A slot without the register is CONAN_ERR_STATE. */
+int conan_streams_pitch_register_state(conan_streams* s, const int32_t* slots, int n, int64_t* state_dev, void* stream);
+
 /* Voice bank (added within ABI 9: a caller detects it by the exported symbols; no existing struct or call changes).  A bank holds the
  * result of conan_set_reference's style pass for up to `capacity` target voices in device memory, outside any slot: the style vector,
  * both aligner layers' K/V rows of the prosody tokens, their key mask, the token count and the VQ ids.  A server enrols its catalogue
