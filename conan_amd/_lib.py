@@ -146,6 +146,13 @@ _PROTOS = {
     "conan_streams_set_pitch_register": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "conan_streams_pitch_register": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "conan_streams_pitch_register_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "conan_activity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.POINTER(C.c_int32), C.c_void_p]),
+    "conan_activity_gate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "conan_streams_set_activity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "conan_streams_activity": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "conan_streams_activity_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "conan_step_wav_activity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_voices_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "conan_voices_destroy": (C.c_int, [C.c_void_p]),
     "conan_voices_enroll": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -379,6 +386,75 @@ def register_cfg(target, max_shift=2.0, prior=None, prior_frames=50, seed=None, 
 def register_keywords(c):
     """register_cfg's keywords of an enabled RegisterCfg: the form a register setting is reported in."""
     return dict(target=c.target, max_shift=c.max_shift, seed=(int(c.seed_count), int(c.seed_sum)))
+
+
+class ActivityState(C.Structure):
+    """conan_activity_state (include/conan_hip.h)."""
+    _fields_ = [("active", C.c_int32), ("hang", C.c_int32), ("level", C.c_int32), ("reserved", C.c_int32), ("floor", C.c_double),
+                ("frames", C.c_int64), ("active_frames", C.c_int64)]
+
+
+class ActivityCfg(C.Structure):
+    """conan_activity_cfg (include/conan_hip.h)."""
+    _fields_ = [("mode", C.c_int32), ("reseed", C.c_int32), ("open_abs", C.c_float), ("close_abs", C.c_float), ("open_ratio", C.c_float),
+                ("close_ratio", C.c_float), ("rise_active", C.c_float), ("rise_idle", C.c_float), ("floor_min", C.c_float),
+                ("hold_frames", C.c_int32), ("up_step", C.c_int32), ("down_step", C.c_int32), ("closed_level", C.c_int32), ("reserved", C.c_int32),
+                ("seed", ActivityState)]
+
+
+ACTIVITY_FULL = 1 << 20      # the open gate's level
+ACTIVITY_STATE_FIELDS = ("active", "hang", "level", "floor", "frames", "active_frames")
+
+
+def db_power(db):
+    """A decibel figure as the linear power the law reads: the f32 nearest to 10^(db / 10), as a Python float."""
+    return C.c_float(10.0 ** (float(db) / 10.0)).value
+
+
+def activity_state(state):
+    """A dict of ACTIVITY_STATE_FIELDS (what Streams.activity_state returns), or an ActivityState, as an ActivityState."""
+    if isinstance(state, ActivityState):
+        return state
+    return ActivityState(int(state["active"]), int(state["hang"]), int(state["level"]), 0, float(state["floor"]), int(state["frames"]),
+                         int(state["active_frames"]))
+
+
+def activity_state_dict(s):
+    return dict(active=int(s.active), hang=int(s.hang), level=int(s.level), floor=float(s.floor), frames=int(s.frames),
+                active_frames=int(s.active_frames))
+
+
+def activity_cfg(gate=True, open_db=-50.0, close_db=-55.0, open_over_db=9.0, close_over_db=6.0, rise_active=1.005, rise_idle=1.02,
+                 floor_min_db=-70.0, floor_db=-60.0, hold_frames=10, attack_frames=1, release_frames=5, closed_db=None, open_abs=None,
+                 close_abs=None, open_ratio=None, close_ratio=None, floor_min=None, up_step=None, down_step=None, closed_level=None, seed=None,
+                 reseed=False):
+    """An enabled conan_activity_cfg: detect (gate=False: mode 1) or detect and gate the output (mode 2).  Thresholds in dBFS of the
+    frame power (open_db / close_db), in dB over the noise floor (open_over_db / close_over_db); the floor's largest growth per 20 ms
+    frame while active / idle; its minimum and its initial value in dB; the hangover in frames; the gate's attack and release in
+    frames and its closed level in dB (None: silence).  The defaults are choices, not measurements.  Every decibel figure is
+    converted to the f32 linear power the law reads (db_power); the linear keywords (open_abs, close_abs, open_ratio, close_ratio,
+    floor_min) and the integer ones (up_step, down_step, closed_level) give a field directly and win over their dB / frame forms.
+    seed: the state to start from (a dict as Streams.activity_state returns - the hand-over - or an ActivityState); default: idle,
+    the gate closed, the floor at floor_db."""
+    cl = int(closed_level) if closed_level is not None else (0 if closed_db is None else int(round(ACTIVITY_FULL * 10.0 ** (float(closed_db) / 20.0))))
+    span = ACTIVITY_FULL - cl
+    up = int(up_step) if up_step is not None else max(1, -(-span // int(attack_frames)))
+    down = int(down_step) if down_step is not None else max(1, -(-span // int(release_frames)))
+    fmin = db_power(floor_min_db) if floor_min is None else float(floor_min)
+    st = ActivityState(0, 0, cl, 0, max(db_power(floor_db), C.c_float(fmin).value), 0, 0) if seed is None else activity_state(seed)
+    return ActivityCfg(2 if gate else 1, int(bool(reseed)),
+                       db_power(open_db) if open_abs is None else float(open_abs), db_power(close_db) if close_abs is None else float(close_abs),
+                       db_power(open_over_db) if open_ratio is None else float(open_ratio),
+                       db_power(close_over_db) if close_ratio is None else float(close_ratio), float(rise_active), float(rise_idle), fmin,
+                       int(hold_frames), up, down, cl, 0, st)
+
+
+def activity_keywords(c):
+    """activity_cfg's keywords of an enabled ActivityCfg, in the linear / integer forms that give the same fields back exactly: the form
+    Streams.activity reports a setting in."""
+    return dict(gate=c.mode == 2, open_abs=c.open_abs, close_abs=c.close_abs, open_ratio=c.open_ratio, close_ratio=c.close_ratio,
+                rise_active=c.rise_active, rise_idle=c.rise_idle, floor_min=c.floor_min, hold_frames=c.hold_frames, up_step=c.up_step,
+                down_step=c.down_step, closed_level=c.closed_level, seed=activity_state_dict(c.seed))
 
 
 class DecoderTaps(C.Structure):

@@ -348,6 +348,8 @@ int conan_streams_reset(conan_streams* s, const int32_t* slots, int n, int which
         for (int i = 0; i < n; ++i) { conan_streams::RsSlot& r = s->wav_in.rs_slot[slots[i]]; r.in = 0; r.out = 0; r.phase = 0; }
       // the register setting stays; the estimate restarts from its seed in the slot's next register row (a host flag: no launch here)
       for (int i = 0; i < n && !s->reg.pending.empty(); ++i) s->reg.pending[slots[i]] = 1;
+      // ... and so does the activity setting, whose state restarts from its seed in the slot's next detector row
+      for (int i = 0; i < n && !s->act.pending.empty(); ++i) s->act.pending[slots[i]] = 1;
     }
   });
 }
@@ -473,6 +475,30 @@ int conan_streams_pitch_register(const conan_streams* s, int slot, conan_registe
 
 int conan_streams_pitch_register_state(conan_streams* s, const int32_t* slots, int n, int64_t* state_dev, void* stream) {
   return guarded([&] { reg::state(s, slots, n, state_dev, stream); });
+}
+
+int conan_activity(conan_ctx* ctx, const conan_mel_cfg* mel, const conan_activity_cfg* cfg, const float* wav_dev, int n, int samples, int32_t* act_out_dev,
+                   int32_t* level_out_dev, double* power_out_dev, conan_activity_state* state_out_dev, int32_t* frames_out, void* stream) {
+  return guarded([&] { act::whole(ctx, mel, cfg, wav_dev, n, samples, act_out_dev, level_out_dev, power_out_dev, state_out_dev, frames_out, stream); });
+}
+
+int conan_activity_gate(conan_ctx* ctx, int hop, const float* wav_dev, int n, int64_t samples, int64_t ld, const int32_t* level_dev, int64_t level_ld,
+                        int32_t start_level, float* out_dev, void* stream) {
+  return guarded([&] { act::gate(ctx, hop, wav_dev, n, samples, ld, level_dev, level_ld, start_level, out_dev, stream); });
+}
+
+int conan_streams_set_activity(conan_streams* s, const int32_t* slots, int n, const conan_activity_cfg* cfg, void* stream) {
+  return guarded([&] { act::set_activity(s, slots, n, cfg, stream); });
+}
+
+int conan_streams_activity(const conan_streams* s, int slot, conan_activity_cfg* cfg_out) { return guarded([&] { act::get_activity(s, slot, cfg_out); }); }
+
+int conan_streams_activity_state(conan_streams* s, const int32_t* slots, int n, conan_activity_state* state_dev, void* stream) {
+  return guarded([&] { act::state(s, slots, n, state_dev, stream); });
+}
+
+int conan_step_wav_activity(conan_streams* s, int32_t* act_dev, int32_t* level_dev, void* stream) {
+  return guarded([&] { act::last_call(s, act_dev, level_dev, stream); });
 }
 
 int conan_streams_set_pitch(conan_streams* s, const int32_t* slots, int n, const conan_pitch_cfg* cfg, void* stream) {

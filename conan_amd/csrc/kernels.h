@@ -483,6 +483,43 @@ struct RegArgs {
 constexpr int kRegThreads = 256;
 void launch_f0_register(const RegArgs& a, hipStream_t st);
 
+// Source activity (activity.hip; include/conan_hip.h, conan_activity_cfg): one workgroup per row.  A row reads `src` at
+// src_off + (s & mask) for sample s of its signal (mask = -1: a plain row; LA - 1: a slot's audio ring), samples outside [0, valid) are
+// zero.  It runs the detector over its frames f_first .. f_first + nframes - 1 from state[slot] (reseed = 0 and slot >= 0) or from its
+// seed, writes flags to act[out_off + j], levels to lvl[lvl_off + j] and - start_lvl = 1 - the level before the row's first frame to
+// lvl[lvl_off - 1], powers to power[out_off + j] (where the launch has a power buffer), and the state after the row to state[slot]
+// (slot >= 0) and state_out[state_row] (state_row >= 0).  mode = 0: a row of a slot without the feature, which shares the table so
+// that the gate finds row i of a vocoder step at entry i: the detector leaves it alone and the gate skips it; mode 2: gated.
+struct ActState { int active, hang, level, reserved; double floor; long long frames, active_frames; };
+static_assert(sizeof(ActState) == 40, "conan_activity_state");
+struct ActRow {
+  long long src_off, valid, out_off, lvl_off;
+  double open_abs, close_abs, open_ratio, close_ratio, rise_active, rise_idle, floor_min;
+  ActState seed;
+  int mask, f_first, nframes, slot, reseed, state_row, mode, start_lvl;
+  int hold, up_step, down_step, closed_level;
+};
+static_assert(sizeof(ActRow) == 176, "uploaded as 44 ints");
+struct ActArgs {
+  const float* src; int* act; int* lvl; double* power;      // power may be null
+  ActState* state;          // [max_slots], indexed by slot; may be null when no row names a slot
+  ActState* state_out;      // [rows]; may be null when no row has a state_row
+  const ActRow* tab; int rows, n_fft, hop;
+  int long_rows;            // 1: rows of many frames (a whole signal): workgroups of kActThreads; 0: of kActStreamThreads
+};
+constexpr int kActThreads = 1024, kActStreamThreads = 256, kActFull = 1 << 20;
+void launch_activity(const ActArgs& a, hipStream_t st);
+// The gate: row i of the launch is x + i * ld -> y + i * ld_y (y may equal x), `samples` samples; its levels are lvl[i * lvl_ld + f] after
+// frame f, and before frame 0 start (start_in_lvl = 0) or lvl[i * lvl_ld - 1] (start_in_lvl = 1: the detector's staging rows).
+// tab != nullptr: row i is gated only where tab[i].mode == 2, every other row is skipped (not multiplied by 1).
+struct ActGateArgs {
+  const float* x; float* y; const int* lvl; const ActRow* tab;
+  long long ld, ld_y, lvl_ld, samples;
+  int n, hop, start, start_in_lvl;
+};
+constexpr int kActGateThreads = 256;
+void launch_activity_gate(const ActGateArgs& a, hipStream_t st);
+
 // y = leaky_relu((x0 + x1 + x2) / nsrc): the MRF mean of HifiGanGenerator.forward (hifigan_causal.py:324-331) with the
 // following LeakyReLU, materialised once so that the consuming conv runs the single-source direct-to-LDS path.
 struct MeanActArgs { TRef x[3]; TRef y; const int* slots; const int* pos; int nsrc, T, n, C; float slope; };

@@ -66,12 +66,19 @@ struct PinRing {
 // call's rows through the pinned ring - and returns q; the caller enqueues the kernels that read the table and calls end(q, their
 // stream).  Staging buffers a call needs sit beside the tables in the owner, indexed by the same q.  Not stream state (state_bytes).
 constexpr int kStageSets = 4;
+// The activity sets (activity.hip) are read last by the gate on the VOCODER stream of a pipelined call, and begin() makes the next
+// call's front-end wait for that.  A pipelined Emformer runs up to 2 * NP steps ahead of the vocoder (it waits for the decoder of step
+// t - NP, which waited for the vocoder of step t - 2 NP): with 2 * NP sets the wait asks for nothing the hand-off rings do not already
+// ask for.  With kStageSets sets it released the Emformer of step t exactly as the vocoder of step t - 3 began its wide first
+// stage, whose workgroup pairs stall on CUs an Emformer workgroup holds (ev_wide below): measured +0.13 ms per 64-stream step
+// against +0.025 ms with 2 * NP sets.
+constexpr int kActSets = 8;
 using RgRow = std::array<int, cnk::kRaggedWords>;      // one call row of mel_stream_ragged_kernel / wav_rows_scatter_kernel
-template <typename Row>
+template <typename Row, int kSets = kStageSets>
 struct StageSets {
   static_assert(sizeof(Row) % sizeof(int) == 0, "rows are uploaded as ints");
-  Row* rows[kStageSets] = {};
-  hipEvent_t ev[kStageSets] = {};
+  Row* rows[kSets] = {};
+  hipEvent_t ev[kSets] = {};
   PinRing pin;
   long long calls = 0;
   StageSets() = default;
@@ -79,7 +86,7 @@ struct StageSets {
   StageSets& operator=(const StageSets&) = delete;
   void init(int max_rows, std::vector<void*>& allocs) {      // (the tables are freed with the owner's allocations)
     if (pin.buf) return;
-    for (int q = 0; q < kStageSets; ++q) {
+    for (int q = 0; q < kSets; ++q) {
       HIP_CHECK(hipMalloc((void**)&rows[q], (size_t)max_rows * sizeof(Row)));
       allocs.push_back(rows[q]);
       if (!ev[q]) HIP_CHECK(hipEventCreateWithFlags(&ev[q], hipEventDisableTiming));
@@ -87,7 +94,7 @@ struct StageSets {
     pin.init((size_t)max_rows * sizeof(Row) / sizeof(int));
   }
   int begin(const Row* host_rows, int n, hipStream_t st) {
-    const int q = (int)(calls++ % kStageSets);
+    const int q = (int)(calls++ % kSets);
     HIP_CHECK(hipStreamWaitEvent(st, ev[q], 0));
     pin.upload(reinterpret_cast<int*>(rows[q]), reinterpret_cast<const int*>(host_rows), (size_t)n * sizeof(Row) / sizeof(int), st);
     return q;
@@ -227,6 +234,29 @@ struct conan_streams {
     bool on(int slot) const { return n_on > 0 && cfg[slot].enabled; }
   } reg;
   void register_init();
+  // source activity (conan_streams_set_activity; activity.hip): per slot its cfg as set (mode = 0: none; reseed kept 0), which persists
+  // across resets; n_on: slots with one.  pending: the slot's state restarts from the cfg's seed in its next detector row (set by an
+  // enabling or reseeding setter call and by a reset with CONAN_MODEL_FRONTEND; a host flag, no launch).  state: [max_slots] on the
+  // device, read and written by the rows of activity_kernel in the order of the front-end launches.  Per call a row table (set q of
+  // `sets`: one row per emitting call row in chunk-row order, mode 0 for a slot without the feature) and beside it the flags
+  // [q][chunk row][seg] and the levels [q][chunk row][seg + 1] (word 0: the level before the chunk) on their way from the front-end
+  // stage to the vocoder stage of the same call, whose gate reads table and levels: the set's event is recorded on the stream of the
+  // call's last vocoder step, behind the gate launch, so under pipelining a set outlives the front-ends of the calls behind it
+  // (kActSets sets, not kStageSets: see there).
+  // Allocated by the first enabling call; state, staging and row tables count as stream state.  last: the rows of the most recent
+  // wav-in call that detected (conan_step_wav_activity).
+  struct Activity {
+    std::vector<conan_activity_cfg> cfg;
+    std::vector<char> pending;
+    int n_on = 0;
+    cnk::ActState* state = nullptr;
+    int* flags[kActSets] = {}; int* levels[kActSets] = {};
+    StageSets<cnk::ActRow, kActSets> sets;
+    struct LastRow { int row, set, src, emit; };
+    std::vector<LastRow> last;
+    bool on(int slot) const { return n_on > 0 && cfg[slot].mode != 0; }
+  } act;
+  void activity_init();
   void ragged_init();
   void resample_init();        // staging, row tables and the history ring (conan_streams_set_input_rate)
   void rs_stage_init();        // staging and row tables only (conan_streams_set_input_format: no stream state)
@@ -276,6 +306,9 @@ struct conan_streams {
     float* base = nullptr; long long ld = 0;
     int tiles = 1, win = 0;
     double flops = 0;
+    // the step's output gate (activity.hip; set by the wav-in step for a group with a gated row): the group's rows of the call's
+    // activity table and of its level staging; hifigan_step launches activity_gate_kernel on the rows conv_post wrote
+    const cnk::ActRow* gate_tab = nullptr; const int* gate_lvl = nullptr; int gate_lvl_ld = 0;
   };
   OutPlan out_plan(const int32_t* slots, int n, int frames, float* wav_out_dev, long long natural_ld, const std::vector<int>* dst, const std::string& who) const;
   // the plan's resample_out_kernel launch behind or_sets.begin() = q, then the set's event; src_ld: stride of the staged rows (a flush: 0)
@@ -475,6 +508,7 @@ struct conan_streams {
 
 // every launch of the matrix kernels goes through here: between conan_profile_begin / _end it is bracketed by HIP
 // events on its launch stream and booked under the kernel's name with its algorithmic FLOPs
+static_assert(kActSets == 2 * conan_streams::NP, "the activity sets cover the pipeline's depth");
 template <typename F>
 inline void conan_streams::profiled(const std::string& name, double flops, hipStream_t st, F&& launch) {
   if (!prof_on) { launch(); return; }
@@ -575,6 +609,20 @@ void set_register(conan_streams* s, const int32_t* slots, int n, const conan_reg
 void get_register(const conan_streams* s, int slot, conan_register_cfg* out);
 void state(conan_streams* s, const int32_t* slots, int n, int64_t* state_dev, void* stream);
 }  // namespace reg
+
+// ---- source activity (activity.hip): the kernels' host side and the bodies of api.hip's entry points
+namespace act {
+void check_cfg(const conan_activity_cfg& c, const char* who);      // host only
+cnk::ActRow row(const conan_activity_cfg& c);      // the cfg's fields of a detector row that starts from the seed and names no slot
+void whole(conan_ctx* ctx, const conan_mel_cfg* mel, const conan_activity_cfg* cfg, const float* wav_dev, int n, int samples, int32_t* act_out_dev,
+           int32_t* level_out_dev, double* power_out_dev, conan_activity_state* state_out_dev, int32_t* frames_out, void* stream);
+void gate(conan_ctx* ctx, int hop, const float* wav_dev, int n, int64_t samples, int64_t ld, const int32_t* level_dev, int64_t level_ld, int32_t start_level,
+          float* out_dev, void* stream);
+void set_activity(conan_streams* s, const int32_t* slots, int n, const conan_activity_cfg* cfg, void* stream);
+void get_activity(const conan_streams* s, int slot, conan_activity_cfg* out);
+void state(conan_streams* s, const int32_t* slots, int n, conan_activity_state* state_dev, void* stream);
+void last_call(conan_streams* s, int32_t* act_dev, int32_t* level_dev, void* stream);
+}  // namespace act
 
 // ---- per-slot pitch control (pitch.hip): the bodies of api.hip's entry points
 namespace pitch {

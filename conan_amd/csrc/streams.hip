@@ -620,6 +620,12 @@ void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float*
     // the step's last kernel also advances the per-slot frame counters (one launch less)
     a.adv_pos = pos_voc; a.adv_delta = frames; a.adv_ticket = cp_ticket[ws_index(st)];
     cnk::launch_conv_post(a, st);
+    if (op && op->gate_tab) {      // the output gate of a wav-in step (activity.hip), in place on the rows just written: [n][T], staged or the caller's
+      cnk::ActGateArgs g; memset(&g, 0, sizeof(g));
+      g.x = a.wav; g.y = a.wav; g.lvl = op->gate_lvl; g.tab = op->gate_tab; g.ld = T; g.ld_y = T; g.lvl_ld = op->gate_lvl_ld; g.samples = T;
+      g.n = n; g.hop = ctx->hop; g.start_in_lvl = 1;
+      profiled("activity_gate_kernel", 0.0, st, [&] { cnk::launch_activity_gate(g, st); });
+    }
     if (out_rows) resample_out(*op, oq, T, st);
     // the launches are enqueued: the slots' host counters, and the counts conan_streams_output_samples reports
     if (!op || op->dst.empty()) wav_out.out_counts.assign(n, T);

@@ -341,6 +341,40 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
         }
       }
   }
+  // source activity (activity.hip): a call in which a slot with the detector emits has one table row per emitting call row, in
+  // chunk-row order - the detector's rows, and mode-0 rows for the other slots so that a group's gate finds its rows by their place
+  std::vector<cnk::ActRow> act_rows;
+  std::vector<conan_streams::Activity::LastRow> act_last;
+  std::vector<char> act_gate(groups.size(), 0);
+  if (s->act.n_on > 0) {
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+      if (!s->act.on(slots[i])) continue;
+      if (m.sample_rate != 50 * hop) throw Error(CONAN_ERR_INVALID, who + ": slot " + std::to_string(slots[i]) + " detects source activity: conan_mel_cfg.sample_rate must be 50 * hop_size");
+      const FePlan& p = pl[i];
+      if (p.emit < 1) continue;
+      if (p.R - std::max(0ll, (long long)p.pos * hop - N / 2) > s->wav_in.fe_LA)
+        throw Error(CONAN_ERR_UNSUPPORTED, who + ": slot " + std::to_string(slots[i]) + " detects source activity: the chunk's frames have left the audio ring at this fft_size");
+      any = true;
+    }
+    for (int g = 0, off = 0; any && g < (int)groups.size(); off += (int)groups[g].size(), ++g)
+      for (int k = 0; k < (int)groups[g].size(); ++k) {
+        const int i = groups[g][k];
+        const FePlan& p = pl[i];
+        cnk::ActRow r;
+        memset(&r, 0, sizeof(r));      // (mode 0, no frames, no slot)
+        r.slot = -1; r.state_row = -1;
+        if (s->act.on(slots[i])) {
+          r = act::row(s->act.cfg[slots[i]]);
+          r.src_off = (long long)slots[i] * s->wav_in.fe_LA; r.valid = p.R; r.mask = s->wav_in.fe_LA - 1;
+          r.f_first = p.pos; r.nframes = p.emit; r.slot = slots[i]; r.reseed = s->act.pending[slots[i]]; r.start_lvl = 1;
+          act_last.push_back({i, 0, off + k, p.emit});
+          if (r.mode == 2) act_gate[g] = 1;
+        }
+        r.out_off = (long long)(off + k) * seg; r.lvl_off = (long long)(off + k) * (seg + 1) + 1;
+        act_rows.push_back(r);
+      }
+  }
   const int nm_in = m.num_mels, nm = c.num_mels;
   int jobs = 0;
   std::vector<RgRow> tab;
@@ -379,6 +413,7 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
   const int lq = lv_rows.empty() ? 0 : s->wav_in.lv_sets.begin(lv_rows.data(), (int)lv_rows.size(), cst);
   const int fq = f0_rows.empty() ? 0 : s->follow.sets.begin(f0_rows.data(), (int)f0_rows.size(), cst);
   const int gq = reg_rows.empty() ? 0 : s->reg.sets.begin(reg_rows.data(), (int)reg_rows.size(), cst);
+  const int aq = act_rows.empty() ? 0 : s->act.sets.begin(act_rows.data(), (int)act_rows.size(), cst);
   const int* rg_tab = reinterpret_cast<const int*>(s->wav_in.rg_sets.rows[q]);
   std::function<void(hipStream_t)> front;
   if (run) {
@@ -451,6 +486,22 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
       s->reg.sets.end(gq, st);
     };
   }
+  // the activity detector, behind the front-end launch (and the tracker's and the register's): the call's samples are in the audio
+  // rings; the groups with a gated row take their rows of the table and of the level staging along to their vocoder step
+  if (!act_rows.empty()) {
+    cnk::ActArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = s->wav_in.fe_audio; a.act = s->act.flags[aq]; a.lvl = s->act.levels[aq]; a.state = s->act.state;
+    a.tab = s->act.sets.rows[aq]; a.rows = (int)act_rows.size(); a.n_fft = N; a.hop = hop;
+    front = [s, a, before = front](hipStream_t st) {
+      if (before) before(st);
+      s->profiled("activity_kernel", 0.0, st, [&] { cnk::launch_activity(a, st); });
+    };
+    for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g) {
+      if (!act_gate[g]) continue;
+      ops[g].gate_tab = s->act.sets.rows[aq] + off; ops[g].gate_lvl = s->act.levels[aq] + (size_t)off * (seg + 1) + 1; ops[g].gate_lvl_ld = seg + 1;
+    }
+  }
   cnk::WavScatterArgs sc;
   sc.tab = rg_tab; sc.n = n; sc.seg = seg; sc.nm = nm; sc.hop = hop;
   sc.codes_src = s->wav_in.rg_codes[q]; sc.mel_src = s->wav_in.rg_mel[q]; sc.wav_src = s->wav_in.rg_wav[q];
@@ -491,6 +542,10 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
   for (conan_streams::Follow::LastRow& r : f0_last) r.set = fq;
   s->follow.last = std::move(f0_last);
   for (const cnk::RegRow& rr : reg_rows) s->reg.pending[rr.slot] = 0;      // (the rows carried the restarts)
+  if (!act_rows.empty()) s->act.sets.end(aq, last);      // (behind the call's last vocoder step: the gate is the last reader of table and levels)
+  for (const cnk::ActRow& ar : act_rows) if (ar.slot >= 0) s->act.pending[ar.slot] = 0;
+  for (conan_streams::Activity::LastRow& r : act_last) r.set = aq;
+  s->act.last = std::move(act_last);
   if (scatter && !route) {      // (each group's step counted its own rows, in group order: back to the call's rows)
     s->wav_out.out_counts.assign(n, 0);
     for (int i = 0; i < n; ++i) s->wav_out.out_counts[i] = pl[i].emit * hop;

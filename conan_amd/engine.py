@@ -223,6 +223,7 @@ class StreamingVoiceConversionEngine:
         self.seg, self.rc = ctx.cfg.emf_segment, ctx.cfg.emf_right_context
         self._followed = False      # set_pitch_follow has been called on the stream-set
         self._registered = False    # set_pitch_register has been called on the stream-set
+        self._activity = False      # set_activity has been called on the stream-set
 
     @staticmethod
     def _check_voice(ref_mel, voice):
@@ -269,7 +270,7 @@ class StreamingVoiceConversionEngine:
         self._set_pitch(self.slots, pitch)
 
     def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                  pitch=None, voice=None, follow=None, register=None, **filter):
+                  pitch=None, voice=None, follow=None, register=None, activity=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
         in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
         in_format: the input's sample format (None: float32; 's16' takes int16 rows, 'ulaw' / 'alaw' uint8), decoded on the GPU.
@@ -282,9 +283,13 @@ class StreamingVoiceConversionEngine:
         GPU on the samples the front-end reads; `pitch` applies on top.
         register: register matching for following slots (Streams.set_pitch_register) - None / False: none; a float: the target in
         log2 Hz; "voice": bank.registers[id] of the slot's voice=(bank, ids) (VoiceBank.enroll_wav(register=True)); a dict of
-        set_pitch_register's keywords.  The followed contour is then moved to the target's register by a causal log-f0 mean."""
+        set_pitch_register's keywords.  The followed contour is then moved to the target's register by a causal log-f0 mean.
+        activity: the source-activity detector (Streams.set_activity) - None / False: none; True: detect and gate the output with
+        the defaults; "detect": detect only; a dict of set_activity's keywords (gate=False: detect only).  chunk_activity() reads
+        the last call's flags."""
         self._check_voice(ref_mel, voice)
         registers = self._registers(self.slots, register, voice)
+        activities = self._activities(self.slots, activity)
         if isinstance(in_format, (list, tuple)) or isinstance(level, (list, tuple)):
             raise ValueError("in_format / level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
         self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice)
@@ -293,6 +298,50 @@ class StreamingVoiceConversionEngine:
         self._set_level(self.slots, level)
         self._set_follow(self.slots, follow)
         self._set_register(self.slots, registers)
+        self._set_activity(self.slots, activities)
+
+    @staticmethod
+    def _activities(slots, activity):
+        """activity= (one value or one per slot) -> per slot None or a dict of Streams.set_activity's keywords.  Host only."""
+        values = list(activity) if isinstance(activity, (list, tuple)) else [activity] * len(slots)
+        if len(values) != len(slots):
+            raise ValueError(f"activity: {len(values)} values for {len(slots)} slots")
+        out = []
+        for a in values:
+            if a is None or a is False:
+                out.append(None)
+            elif a is True:
+                out.append(dict(gate=True))
+            elif isinstance(a, str):
+                if a != "detect":
+                    raise ValueError(f"activity: {a!r} (True, 'detect', a dict of set_activity's keywords or None)")
+                out.append(dict(gate=False))
+            elif isinstance(a, dict):
+                out.append(dict(a))
+            else:
+                raise ValueError(f"activity: {a!r} (True, 'detect', a dict of set_activity's keywords or None)")
+        return out
+
+    def _set_activity(self, slots, activities):
+        """The slots' detector from _activities' list, behind the slots' reset: the states restart from their seeds at the first
+        emitted chunk.  A stream-set that never used it is left alone."""
+        if all(a is None for a in activities) and not self._activity:
+            return
+        self._activity = True
+        for slot, a in zip(slots, activities):
+            self.st.set_activity([slot], cfg=a)
+
+    def set_activity(self, slots=None, cfg=True, **kw):
+        """A live change of the slots' activity detector (all slots by default) between feed / feed_ragged calls, also mid-utterance
+        and with pipelined steps in flight: Streams.set_activity's arguments (cfg=None turns it off; without reseed=True an enabled
+        slot keeps its state).  In force from the next emitted chunk."""
+        self._activity = True
+        self.st.set_activity(self.slots if slots is None else slots, cfg, **kw)
+
+    def chunk_activity(self):
+        """The flags and frame-end gate levels of the last feed / feed_ragged call (Streams.step_wav_activity; joins pipelined work):
+        (act [n, seg], level [n, seg]) int32 in the call's row order, zeros for rows without the detector and past a row's frames."""
+        return self.st.step_wav_activity()
 
     @staticmethod
     def _registers(slots, register, voice):
@@ -483,7 +532,8 @@ class StreamingVoiceConversionEngine:
 
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
-                  out_format=None, loud_norm=False, level=None, pitch=None, voice=None, follow=None, register=None, **filter):
+                  out_format=None, loud_norm=False, level=None, pitch=None, voice=None, follow=None, register=None, activity=None,
+                  activity_log=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] (or None with voice = (bank, ids): start) -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
@@ -495,13 +545,17 @@ class StreamingVoiceConversionEngine:
         level: the streaming input leveller (start_wav); the results are those of infer_wav(ctx.level(x, **level), ...) bit for bit,
         x = the decoded, resampled utterance.  pitch: the slots' pitch control in the decoder step (start).  follow: source-pitch
         following (start_wav): the decoder steps take ctx.f0 of the samples the front-end reads instead of the predictor's contour.
-        register: register matching of the followed contour (start_wav): the steps take ctx.f0_register of that contour."""
+        register: register matching of the followed contour (start_wav): the steps take ctx.f0_register of that contour.
+        activity: the source-activity detector (start_wav): ctx.activity of the samples the front-end reads, and with the gate the
+        returned wav is ctx.activity_gate of the ungated one, bit for bit.  activity_log: a list that receives (act [B, emit],
+        level [B, emit]) per emitted chunk (chunk_activity after each call, which joins pipelined work)."""
         self._check_voice(ref_mel, voice)
         self._registers(self.slots, register, voice)      # (host checks before anything runs)
+        self._activities(self.slots, activity)
         if loud_norm:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
-                       pitch=pitch, voice=voice, follow=follow, register=register, **filter)
+                       pitch=pitch, voice=voice, follow=follow, register=register, activity=activity, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -521,6 +575,9 @@ class StreamingVoiceConversionEngine:
                 wavs.append(w)
                 mels.append(m)
                 codes.append(c)
+                if activity_log is not None:
+                    a, l = self.chunk_activity()
+                    activity_log.append((a[:, :m.shape[1]].clone(), l[:, :m.shape[1]].clone()))
         if pipelined:
             self.st.join()
         if self.st.output_rates:
@@ -528,7 +585,7 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                   pitch=None, voice=None, follow=None, register=None, **filter):
+                   pitch=None, voice=None, follow=None, register=None, activity=None, **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
         rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
@@ -537,9 +594,10 @@ class StreamingVoiceConversionEngine:
         slots' pitch control (start), one value or a list with one per slot.  voice: (bank, ids) - enrolled voices, one id per slot, in
         place of ref_mel (then None): one launch instead of a style pass per slot.  follow: the slots' source-pitch following
         (start_wav), one value or a list with one per slot.  register: the slots' register matching (start_wav), one value or a list
-        with one per slot."""
+        with one per slot.  activity: the slots' activity detector (start_wav), one value or a list with one per slot."""
         self._check_voice(ref_mel, voice)
         registers = self._registers(slots, register, voice)
+        activities = self._activities(slots, activity)
         self.st.reset(slots, which=7 | 8)
         self._reference(slots, ref_mel, ref_len, voice)
         self._set_out_rate(slots, out_rate, out_filter)
@@ -551,6 +609,7 @@ class StreamingVoiceConversionEngine:
         self._set_pitch(slots, pitch)
         self._set_follow(slots, follow)
         self._set_register(slots, registers)
+        self._set_activity(slots, activities)
 
     @torch.no_grad()
     def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None):
@@ -570,7 +629,7 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
                             in_formats=None, out_formats=None, loud_norm=False, level=None, pitch=None, voice=None, follow=None, register=None,
-                            **filter):
+                            activity=None, activity_log=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -585,10 +644,15 @@ class StreamingVoiceConversionEngine:
         control (start), one value for every utterance or a list with one per utterance.  voice: (bank, ids) - one enrolled id per
         utterance, in place of ref_mel (then None).  follow: source-pitch following (start_wav), one value for every
         utterance or a list with one per utterance.  register: register matching (start_wav), one value for every utterance or a list
-        with one per utterance."""
+        with one per utterance.  activity: the activity detector (start_wav), one value for every utterance or a list with one per
+        utterance.  activity_log: a list that receives, per utterance, a list of (act [emit], level [emit]) per emitted chunk
+        (chunk_activity after each call, which joins pipelined work)."""
         voice = self._check_voice(ref_mel, voice)
         U = len(src_wavs)
         registers = self._registers(range(U), register, voice)      # (host checks before anything runs; per utterance, as dicts)
+        activities = self._activities(range(U), activity)
+        if activity_log is not None:
+            activity_log[:] = [[] for _ in range(U)]
         follows = list(follow) if isinstance(follow, (list, tuple)) else [follow] * U
         levels = list(level) if isinstance(level, (list, tuple)) else [level] * U
         pitches = list(pitch) if isinstance(pitch, (list, tuple)) else [pitch] * U
@@ -615,7 +679,8 @@ class StreamingVoiceConversionEngine:
                                 voice=None if voice is None else (voice[0], [voice[1][u] for u in new]), in_rate=[rates[u] for u in new],
                                 out_rate=[orates[u] for u in new], out_filter=out_filter, in_format=[ifmts[u] for u in new],
                                 out_format=[ofmts[u] for u in new], level=[levels[u] for u in new], pitch=[pitches[u] for u in new],
-                                follow=[follows[u] for u in new], register=[registers[u] for u in new], **filter)
+                                follow=[follows[u] for u in new], register=[registers[u] for u in new], activity=[activities[u] for u in new],
+                                **filter)
             if not live:
                 tick += 1
                 continue
@@ -640,6 +705,11 @@ class StreamingVoiceConversionEngine:
                 rows.append(piece if self.st.input_formats else torch.nn.functional.pad(piece, (0, width - piece.shape[0])))
             # (rows of several dtypes travel as a list, each packed in its slot's format)
             res = self.feed_ragged([live[u][0] for u in us], rows if self.st.input_formats else torch.stack(rows), samples, final, pipelined=pipelined, mel=mel)
+            if activity_log is not None and any(m.shape[0] for _, m, _ in res):
+                fl, lv = self.chunk_activity()
+                for r, (u, (_, m, _)) in enumerate(zip(us, res)):
+                    if m.shape[0]:
+                        activity_log[u].append((fl[r, :m.shape[0]].clone(), lv[r, :m.shape[0]].clone()))
             for u, was_final, (w, m, c) in zip(us, draining, res):
                 if m.shape[0]:
                     outs[u].append((w, m, c))

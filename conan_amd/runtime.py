@@ -30,6 +30,13 @@ def _i32(a):
     return a, a.ctypes.data_as(C.c_void_p)
 
 
+def _activity_states(buf):
+    """uint8 [n, sizeof(conan_activity_state)] on the device -> a list of dicts (synchronises)."""
+    raw = buf.cpu().numpy().tobytes()
+    size = C.sizeof(_lib.ActivityState)
+    return [_lib.activity_state_dict(_lib.ActivityState.from_buffer_copy(raw[i * size:(i + 1) * size])) for i in range(buf.shape[0])]
+
+
 # torch dtype of a row in each sample format (conan_streams_set_input_format / _output_format, conan_convert_samples)
 SAMPLE_DTYPES = {"f32": torch.float32, "s16": torch.int16, "ulaw": torch.uint8, "alaw": torch.uint8}
 
@@ -258,6 +265,51 @@ class Context:
         _lib.check(self.lib.conan_f0_register(self.h, C.byref(cfg), _ptr(x), _ptr(u), n, lens.ctypes.data_as(C.c_void_p), T, _ptr(out), _ptr(state),
                                               _stream()))
         return out, state.reshape(*lead, 2)
+
+    def activity(self, wav, cfg=None, power=False, fft_size=1024, hop_size=None, state=True, **kw):
+        """The source-activity detector on whole signals (conan_activity; include/conan_hip.h, conan_activity_cfg): wav [..., N] float32
+        at the model rate (50 * hop_size; hop_size defaults to the vocoder's hop) -> (act [..., frames] int32 0 | 1, level [..., frames]
+        int32 - the gate level after each frame, 2^20 = open -, state: a list with one dict per row (active, hang, level, floor, frames,
+        active_frames) after the row), frames = 1 + N // hop_size; power=True appends the frame powers [..., frames] float64.  cfg: an
+        _lib.ActivityCfg, or **kw = _lib.activity_cfg's keywords.  state=False: no state is fetched (None in its place), and the call
+        does not synchronise.  It is what a wav-in slot with Streams.set_activity computes, bit
+        for bit."""
+        dev = torch.device("cuda", self.device)
+        x = wav.to(dev, torch.float32).contiguous()
+        lead, N = x.shape[:-1], x.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        hop = int(hop_size or self.hop)
+        mc = mel_cfg(fft_size=fft_size, hop_size=hop, win_length=fft_size, sample_rate=50 * hop)
+        c = cfg if cfg is not None else _lib.activity_cfg(**kw)
+        frames = 1 + N // hop
+        act = torch.empty(n, frames, dtype=torch.int32, device=dev)
+        lvl = torch.empty(n, frames, dtype=torch.int32, device=dev)
+        pw = torch.empty(n, frames, dtype=torch.float64, device=dev) if power else None
+        sbuf = torch.empty(n, C.sizeof(_lib.ActivityState), dtype=torch.uint8, device=dev) if state else None
+        got = C.c_int32(0)
+        _lib.check(self.lib.conan_activity(self.h, C.byref(mc), C.byref(c), _ptr(x), n, N, _ptr(act), _ptr(lvl), _ptr(pw), _ptr(sbuf), C.byref(got),
+                                           _stream()))
+        assert got.value == frames
+        out = (act.reshape(*lead, frames), lvl.reshape(*lead, frames), _activity_states(sbuf) if state else None)
+        return out + (pw.reshape(*lead, frames),) if power else out
+
+    def activity_gate(self, wav, level, start_level=0, hop_size=None, out=None):
+        """The gate's gain law on whole signals (conan_activity_gate): wav [..., N] float32 times the gain of level [..., >= ceil(N / hop)]
+        int32 (the level after each frame, as Context.activity returns it; start_level: the level before frame 0) -> [..., N]; the
+        level moves linearly inside a frame and 2^20 at both ends leaves the samples' bits alone.  out=wav gates in place."""
+        dev = torch.device("cuda", self.device)
+        x = wav.to(dev, torch.float32).contiguous()
+        lv = level.to(dev, torch.int32).contiguous()
+        lead, N = x.shape[:-1], x.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        if lv.shape[:-1] != lead:
+            raise ValueError(f"activity_gate: wav {tuple(x.shape)} and level {tuple(lv.shape)} differ in their leading shape")
+        y = torch.empty_like(x) if out is None else out
+        if y.shape != x.shape or y.dtype != torch.float32 or not y.is_contiguous():
+            raise ValueError("activity_gate: out must be a contiguous float32 tensor of wav's shape")
+        _lib.check(self.lib.conan_activity_gate(self.h, int(hop_size or self.hop), _ptr(x), n, N, N, _ptr(lv), lv.shape[-1], int(start_level), _ptr(y),
+                                                _stream()))
+        return y
 
     def register_of(self, wav, **f0_keywords):
         """The register of wav [n, N] (or [N]) at the model rate: per row the mean log2 Hz of its voiced frames - Context.f0 followed
@@ -765,6 +817,57 @@ class Streams:
             shift = None if mean is None else min(max(c.target - mean, -c.max_shift), c.max_shift)
             out.append(dict(target=c.target, max_shift=c.max_shift, count=k, sum=S, mean=mean, shift=shift))
         return out
+
+    def set_activity(self, slots, cfg=True, gate=True, **kw):
+        """conan_streams_set_activity: a causal voice-activity detector on the slots' own input (wav-in steps only), on the frames
+        the front-end reads, one more launch per call; gate=True (mode 2) also gates the vocoder's audio of the slots, click-free,
+        in front of the output resampler and encoder; gate=False (mode 1) only detects.  **kw / a dict in cfg: _lib.activity_cfg's
+        keywords (thresholds, hangover, attack / release, seed=, reseed=); cfg may also be an _lib.ActivityCfg; only cfg=None turns it
+        off.  It may be called at any time (it joins pipelined work); the change takes effect from the next emitted chunk and
+        survives resets.  The state restarts from the seed when a slot is enabled, after reseed=True and at the first chunk after a
+        reset of the front-end; reseed=False on an enabled slot replaces the parameters and keeps the state.  Slot snapshots do not
+        carry it: query activity_state, export, import, then set_activity(seed=state, reseed=True)."""
+        a, p = _i32(slots)
+        if cfg is None:
+            if kw:
+                raise ValueError("set_activity: cfg=None turns the detector off and takes no keywords")
+            c = _lib.ActivityCfg()      # (mode = 0)
+        elif isinstance(cfg, _lib.ActivityCfg):
+            c = cfg
+        else:
+            c = _lib.activity_cfg(**dict(dict(gate=gate), **dict({} if cfg is True else cfg, **kw)))
+        _lib.check(self.lib.conan_streams_set_activity(self.h, p, len(a), C.byref(c), _stream()))
+        self._release()
+
+    def activity(self, slots):
+        """conan_streams_activity: per slot the setting as _lib.activity_keywords reports it (set_activity takes it back), None for a
+        slot without the detector."""
+        out = []
+        for slot in slots:
+            c = _lib.ActivityCfg()
+            _lib.check(self.lib.conan_streams_activity(self.h, int(slot), C.byref(c)))
+            out.append(_lib.activity_keywords(c) if c.mode else None)
+        return out
+
+    def activity_state(self, slots):
+        """conan_streams_activity_state (joins pipelined work, synchronises): per slot dict(active, hang, level, floor, frames,
+        active_frames); a slot whose state is about to restart reports its seed.  A slot without the detector is an error."""
+        a, p = _i32(slots)
+        buf = torch.empty(len(a), C.sizeof(_lib.ActivityState), dtype=torch.uint8, device=self.dev)
+        _lib.check(self.lib.conan_streams_activity_state(self.h, p, len(a), _ptr(buf), _stream()))
+        self._release()
+        return _activity_states(buf)
+
+    def step_wav_activity(self):
+        """The flags and frame-end gate levels the last wav-in call produced (conan_step_wav_activity; joins pipelined work) ->
+        (act [n, seg] int32, level [n, seg] int32) in call order; rows without the detector, rows that emitted nothing and entries
+        past a row's emitted frames are 0."""
+        n = self._last_wav_n
+        act = torch.empty(max(n, 1), self.seg, dtype=torch.int32, device=self.dev)      # (before any wav-in call the library answers CONAN_ERR_STATE)
+        lvl = torch.empty(max(n, 1), self.seg, dtype=torch.int32, device=self.dev)
+        _lib.check(self.lib.conan_step_wav_activity(self.h, _ptr(act), _ptr(lvl), _stream()))
+        self._release()
+        return act[:n], lvl[:n]
 
     def step_wav_contour(self):
         """The contour the last wav-in call handed the decoder (conan_step_wav_contour; joins pipelined work) -> (f0 [n, seg] log2 Hz,

@@ -882,6 +882,108 @@ int conan_streams_pitch_register(const conan_streams* s, int slot, conan_registe
  * estimate is about to restart reports its seed.  A slot without the register is CONAN_ERR_STATE. */
 int conan_streams_pitch_register_state(conan_streams* s, const int32_t* slots, int n, int64_t* state_dev, void* stream);
 
+/* Source activity (added within ABI 9: a caller detects it by the exported symbols; no existing struct or call changes).  On a call leg
+ * the source is silent about half the time; in those stretches the front-end, the tracker and the leveller see line noise and the
+ * model converts it into the target voice's breath and babble.  The only copy of the model-rate audio - behind the input resampler and
+ * the leveller, exactly what the front-end frames - lives in the slot's audio ring on the device, so the detector runs there: a causal
+ * per-slot voice-activity detector on the front-end's own frames, per-frame flags the host can read (discontinuous transmission,
+ * comfort noise) and an optional click-free gate on the vocoder's audio.  The reference's one silence facility (trim_long_sil) is
+ * offline, whole-file and built on an external detector; this is its streaming counterpart, defined here (tests/activity_ref.py
+ * restates it in numpy f64 with Python integers).  Every step below is an integer operation or ONE correctly rounded IEEE operation,
+ * so the GPU and the reference agree bit for bit and the streamed form equals the whole-signal form bit for bit.
+ *   Frame.  N = mel.fft_size (a power of two in 64 .. 2048), hop = mel.hop_size, sample_rate = 50 * hop.  Frame f is
+ *     x[k] = (double)s[f * hop - N / 2 + k], k = 0 .. N-1: the tracker's frames (conan_f0_cfg).  s = the model-rate samples behind the
+ *     input resampler and the leveller; zeros before the utterance, and past its end once it is final.  No window.  A signal of
+ *     `samples` samples has 1 + samples / hop frames.
+ *   Power.  64 partial sums: p_j over k = j, j + 64, j + 128, ... in ascending order, each step p = x * x + p rounded once (the square
+ *     of an f32 is exact in f64, so a fused multiply-add and multiply-then-add give the same bits).  Then the fold p_j += p_(j+32) for
+ *     j < 32, then with 16, 8, 4, 2, 1.  P = p_0 / N.  The order depends on N alone, never on the launch.
+ *   Thresholds, with the state's noise floor nf as it was BEFORE this frame and the cfg's floats taken as (double) of the f32:
+ *     open = fmax(open_abs, nf * open_ratio), close = fmax(close_abs, nf * close_ratio).
+ *   Decision.  raw = P > (active_prev ? close : open).  raw: act = 1, hang = hold_frames.  Else hang > 0: act = 1, hang -= 1.
+ *     Else act = 0.
+ *   Floor.  nf' = fmax(fmin(P, nf * (act ? rise_active : rise_idle)), floor_min): the floor follows the power down at once and up by at
+ *     most the rise per frame.
+ *   Gate level, an integer in [closed_level, 2^20].  act: lvl' = min(lvl + up_step, 2^20); else lvl' = max(lvl - down_step, closed_level).
+ *   Counters.  frames += 1, active_frames += act (int64).
+ *   Gain.  Frame f gates the output samples f * hop + k, k = 0 .. hop-1 (the vocoder's samples of that frame):
+ *     l = lvl_prev * (hop - 1 - k) + lvl' * (k + 1), an integer; g = (float)((double)l / (double)(hop << 20)); y = x * g in f32.  The level
+ *     moves linearly inside a frame, so the gain has no step (click-free), and with both ends at 2^20 g == 1.0f: open audio keeps its bits.
+ * The thresholds and ratios are LINEAR power values: a helper converts decibels to f32 once and the law reads the f32, so no libm
+ * function is part of the law.  conan_amd/_lib.py's activity_cfg gives -50 / -55 dBFS absolute, 9 / 6 dB over the floor, rises of 1.02
+ * (idle) / 1.005 (active) per frame, a floor minimum of -70 dB, an initial floor of -60 dB, a hold of 10 frames, attack in one frame,
+ * release in five and a fully closed gate.  Those defaults are choices, not measurements. */
+typedef struct conan_activity_state {
+  int32_t active;          /* 0 | 1: the last frame's act */
+  int32_t hang;            /* hangover frames left, 0 .. 2^20 */
+  int32_t level;           /* gate level after the last frame, closed_level .. 2^20 */
+  int32_t reserved;        /* must be 0 */
+  double  floor;           /* noise floor nf (linear power) */
+  int64_t frames;          /* frames seen */
+  int64_t active_frames;   /* ... of them active */
+} conan_activity_state;    /* 40 bytes */
+typedef struct conan_activity_cfg {
+  int32_t mode;            /* 0: off (other fields ignored), 1: detect only, 2: detect and gate the vocoder's audio */
+  int32_t reseed;          /* 1: the state restarts from the seed; 0: it continues (a slot that had none starts from the seed) */
+  float   open_abs, close_abs;        /* linear power, finite, 0 <= close_abs <= open_abs */
+  float   open_ratio, close_ratio;    /* linear power ratios over the floor, finite, 0 <= close_ratio <= open_ratio */
+  float   rise_active, rise_idle;     /* finite, >= 1: the floor's largest growth per frame */
+  float   floor_min;                  /* finite, > 0 */
+  int32_t hold_frames;                /* 0 .. 2^20: hangover */
+  int32_t up_step, down_step;         /* 1 .. 2^20: level change per active / inactive frame */
+  int32_t closed_level;               /* 0 .. 2^20 - 1: the closed gate's level (0: silence) */
+  int32_t reserved;                   /* must be 0 */
+  conan_activity_state seed;          /* what the state starts from: active 0 | 1, hang 0 .. 2^20, level in [closed_level, 2^20],
+                                         floor finite and >= floor_min, counters >= 0, reserved 0 */
+} conan_activity_cfg;      /* 96 bytes */
+#define CONAN_ACTIVITY_FULL 1048576   /* 2^20: the open gate's level */
+/* The whole-signal form, and the bit-exact yardstick of the streaming one: wav_dev[n][samples] f32 (n in 1 .. 65535, samples >= 1) ->
+ * act_out_dev[n][frames] (0 | 1) and level_out_dev[n][frames] (the level after each frame), both int32, frames = 1 + samples / hop
+ * (*frames_out, may be NULL); power_out_dev[n][frames] (double, P of each frame; may be NULL); state_out_dev[n] (the state after the
+ * row; may be NULL).  Every row starts from the seed.  Of mel only fft_size, hop_size and sample_rate (which must be 50 * hop_size) are
+ * read.  cfg->mode must be 1 or 2 (no difference here).  One launch (cnk::activity_kernel, one workgroup per row) on `stream`. */
+int conan_activity(conan_ctx* ctx, const conan_mel_cfg* mel, const conan_activity_cfg* cfg, const float* wav_dev, int n, int samples,
+                   int32_t* act_out_dev, int32_t* level_out_dev, double* power_out_dev, conan_activity_state* state_out_dev, int32_t* frames_out,
+                   void* stream);
+/* The gain law on whole signals: row i of wav_dev (n rows of `samples` samples, row stride ld) times the gain of level_dev[i][.] (int32,
+ * row stride level_ld >= ceil(samples / hop): the level after each frame, as conan_activity writes it) with start_level (0 .. 2^20) as
+ * the level before frame 0 -> out_dev (row stride ld; may equal wav_dev).  A last frame that the samples cover only partly is gated
+ * over the part they cover.  One launch (cnk::activity_gate_kernel) on `stream`. */
+int conan_activity_gate(conan_ctx* ctx, int hop, const float* wav_dev, int n, int64_t samples, int64_t ld, const int32_t* level_dev, int64_t level_ld,
+                        int32_t start_level, float* out_dev, void* stream);
+/* Sets (cfg->mode = 1 | 2) or removes (0) the detector for `slots`; every argument is checked before anything changes, a stream-set
+ * without the streaming front-end is CONAN_ERR_STATE, and pending pipelined work is joined.  The change takes effect from the next
+ * emitted chunk and persists across resets.
+ * What a slot with the feature does.  Every conan_step_wav[_async] / conan_step_wav_ragged[_ld][_async] call that emits a chunk for
+ * it runs the detector on the chunk's frames [pos, pos + emit) - every emitted frame is backed by an input frame - from the slot's
+ * audio ring: ONE more launch per call (cnk::activity_kernel, behind the front-end launch on the same stream, after the tracker's
+ * and the register's where present; none in calls in which no such slot emits).  The frames must still be in the audio ring, as for
+ * following: otherwise the call is CONAN_ERR_UNSUPPORTED before anything changes (fft_size 2048 at the shipped configuration), and
+ * conan_mel_cfg.sample_rate of such a call must be 50 * hop.  In mode 2 the chunk's vocoder step gates the rows conv_post just wrote, in
+ * place, in front of the output resampler and the format encoder: ONE more launch (cnk::activity_gate_kernel) per vocoder step in
+ * which a gated row takes part - each emit group of a ragged call is such a step - and none otherwise; rows that are not gated are
+ * skipped, not multiplied by 1, so they keep their bits.  conan_streams_flush_output sees gated audio.  The mel-in steps
+ * (conan_step[_async]) and conan_hifigan_step* take no waveform: they neither detect nor gate.
+ * The state restarts from the seed at the slot's first emitted chunk after a reset that includes CONAN_MODEL_FRONTEND, after a
+ * setter call with reseed = 1 and after a setter call that enables a slot that was off.  A setter call with reseed = 0 on an enabled
+ * slot replaces the parameters (and the seed of later restarts) and keeps the state.
+ * Memory: the first enabling call allocates 40 bytes of state per slot, 8 staging sets of (2 * segment + 1) int32 per slot for the
+ * flags and levels on their way from the front-end stage to the vocoder stage, and 8 row tables; conan_streams_state_bytes counts them
+ * from then on.  A stream-set that never calls the setter allocates nothing and runs exactly the launches it ran before.
+ * Snapshots carry neither the setting nor the state (the 256-byte host record is full); conan_streams_layout_id and
+ * conan_streams_snapshot_bytes do not change.  The hand-over: conan_streams_activity_state, export, import, then this setter with
+ * seed = the queried state and reseed = 1. */
+int conan_streams_set_activity(conan_streams* s, const int32_t* slots, int n, const conan_activity_cfg* cfg, void* stream);
+/* Host only: the activity cfg of `slot` as set, reseed = 0 (mode = 0 and zeros for a slot without one). */
+int conan_streams_activity(const conan_streams* s, int slot, conan_activity_cfg* cfg_out);
+/* The states of `slots` -> state_dev[n], in the order of `stream` behind a join of pipelined work; a slot whose state is about to
+ * restart reports its seed.  A slot without the feature is CONAN_ERR_STATE. */
+int conan_streams_activity_state(conan_streams* s, const int32_t* slots, int n, conan_activity_state* state_dev, void* stream);
+/* Hook in the spirit of conan_step_wav_contour: the flags and frame-end levels the last wav-in call produced, in call order (joins
+ * first): act_dev[n][seg] and level_dev[n][seg], int32.  Rows without the feature, rows that emitted nothing and positions behind the
+ * emitted frames read zero. */
+int conan_step_wav_activity(conan_streams* s, int32_t* act_dev, int32_t* level_dev, void* stream);
+
 /* Voice bank (added within ABI 9: a caller detects it by the exported symbols; no existing struct or call changes).  A bank holds the
  * result of conan_set_reference's style pass for up to `capacity` target voices in device memory, outside any slot: the style vector,
  * both aligner layers' K/V rows of the prosody tokens, their key mask, the token count and the VQ ids.  A server enrols its catalogue
