@@ -153,6 +153,8 @@ _PROTOS = {
     "conan_streams_activity": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "conan_streams_activity_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "conan_step_wav_activity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_trim_silence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "conan_voices_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "conan_voices_destroy": (C.c_int, [C.c_void_p]),
     "conan_voices_enroll": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -455,6 +457,17 @@ def activity_keywords(c):
     return dict(gate=c.mode == 2, open_abs=c.open_abs, close_abs=c.close_abs, open_ratio=c.open_ratio, close_ratio=c.close_ratio,
                 rise_active=c.rise_active, rise_idle=c.rise_idle, floor_min=c.floor_min, hold_frames=c.hold_frames, up_step=c.up_step,
                 down_step=c.down_step, closed_level=c.closed_level, seed=activity_state_dict(c.seed))
+
+
+class TrimCfg(C.Structure):
+    """conan_trim_cfg (include/conan_hip.h)."""
+    _fields_ = [("smooth_frames", C.c_int32), ("max_silence_frames", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+def trim_cfg(smooth_frames=12, max_silence_frames=18):
+    """conan_trim_cfg: the moving average's width and the longest pause that is kept whole, in 20 ms frames.  The defaults are the
+    reference's 8 and 12 windows of 30 ms kept as durations; they are choices, not measurements."""
+    return TrimCfg(int(smooth_frames), int(max_silence_frames), (C.c_int32 * 2)(0, 0))
 
 
 class DecoderTaps(C.Structure):

@@ -210,7 +210,7 @@ cnk::ActRow row(const conan_activity_cfg& c) {
   return r;
 }
 
-static void check_mel(const conan_mel_cfg& m, const char* who) {
+void check_mel(const conan_mel_cfg& m, const char* who) {
   const std::string w = std::string(who) + ": ";
   if (m.fft_size < 64 || (m.fft_size & (m.fft_size - 1)) || m.fft_size > 2048) throw Error(CONAN_ERR_INVALID, w + "fft_size must be a power of two in [64, 2048]");
   if (m.hop_size < 1 || m.hop_size > 2047) throw Error(CONAN_ERR_INVALID, w + "hop_size must be in 1 .. 2047");

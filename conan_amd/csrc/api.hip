@@ -501,6 +501,15 @@ int conan_step_wav_activity(conan_streams* s, int32_t* act_dev, int32_t* level_d
   return guarded([&] { act::last_call(s, act_dev, level_dev, stream); });
 }
 
+int conan_trim_silence(conan_ctx* ctx, const conan_mel_cfg* mel, const conan_activity_cfg* act_cfg, const conan_trim_cfg* cfg, const float* wav_dev, int64_t ld,
+                       int n, int64_t samples, const int64_t* lengths, const int32_t* act_in_dev, int64_t act_ld, float* out_dev, int64_t out_ld,
+                       int32_t* mask_out_dev, int64_t* offset_out_dev, int64_t frame_ld, int64_t* out_len_dev, void* stream) {
+  return guarded([&] {
+    trim::whole(ctx, mel, act_cfg, cfg, wav_dev, ld, n, samples, lengths, act_in_dev, act_ld, out_dev, out_ld, mask_out_dev, offset_out_dev, frame_ld, out_len_dev,
+                stream);
+  });
+}
+
 int conan_streams_set_pitch(conan_streams* s, const int32_t* slots, int n, const conan_pitch_cfg* cfg, void* stream) {
   return guarded([&] { pitch::set_pitch(s, slots, n, cfg, stream); });
 }

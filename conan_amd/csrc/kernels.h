@@ -520,6 +520,21 @@ struct ActGateArgs {
 constexpr int kActGateThreads = 256;
 void launch_activity_gate(const ActGateArgs& a, hipStream_t st);
 
+// Silence trimming (trim.hip; include/conan_hip.h, conan_trim_cfg).  Row i has lens[i] samples at wav + i * ld and F = 1 + lens[i] / hop
+// frames; its flags are act[i * act_ld + f] (any non-zero counts as 1).  The plan kernel (one workgroup per row) writes the row's two
+// prefix arrays pa / pb [i * pre_ld + 0 .. F] (scratch: the prefixes of act and of m1), the kept-frame mask m2 to mask[i * mask_ld + f]
+// (mask may be null), off[f] - or -1 for a dropped frame - to off[i * off_ld + f] and the row's out_len to out_len[i].  The gather
+// kernel (grid: tiles of kTrimGatherFrames frames x rows) reads off / out_len and moves the kept frames' samples to out + i * out_ld,
+// then zero-fills [out_len, lens[i]).
+struct TrimArgs {
+  const float* wav; float* out; const int* act; int* mask; long long* off; long long* out_len; int* pa; int* pb; const long long* lens;
+  long long ld, out_ld, act_ld, mask_ld, off_ld, pre_ld;
+  int n, hop, w, s, tiles, pad_;
+};
+constexpr int kTrimThreads = 256, kTrimGatherThreads = 256, kTrimGatherFrames = 16;
+void launch_trim_plan(const TrimArgs& a, hipStream_t st);
+void launch_trim_gather(const TrimArgs& a, hipStream_t st);
+
 // y = leaky_relu((x0 + x1 + x2) / nsrc): the MRF mean of HifiGanGenerator.forward (hifigan_causal.py:324-331) with the
 // following LeakyReLU, materialised once so that the consuming conv runs the single-source direct-to-LDS path.
 struct MeanActArgs { TRef x[3]; TRef y; const int* slots; const int* pos; int nsrc, T, n, C; float slope; };

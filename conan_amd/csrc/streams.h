@@ -613,6 +613,7 @@ void state(conan_streams* s, const int32_t* slots, int n, int64_t* state_dev, vo
 // ---- source activity (activity.hip): the kernels' host side and the bodies of api.hip's entry points
 namespace act {
 void check_cfg(const conan_activity_cfg& c, const char* who);      // host only
+void check_mel(const conan_mel_cfg& m, const char* who);           // host only: the frame geometry conan_activity accepts
 cnk::ActRow row(const conan_activity_cfg& c);      // the cfg's fields of a detector row that starts from the seed and names no slot
 void whole(conan_ctx* ctx, const conan_mel_cfg* mel, const conan_activity_cfg* cfg, const float* wav_dev, int n, int samples, int32_t* act_out_dev,
            int32_t* level_out_dev, double* power_out_dev, conan_activity_state* state_out_dev, int32_t* frames_out, void* stream);
@@ -623,6 +624,18 @@ void get_activity(const conan_streams* s, int slot, conan_activity_cfg* out);
 void state(conan_streams* s, const int32_t* slots, int n, conan_activity_state* state_dev, void* stream);
 void last_call(conan_streams* s, int32_t* act_dev, int32_t* level_dev, void* stream);
 }  // namespace act
+
+// ---- silence trimming (trim.hip): the kernels' host side and the body of api.hip's entry point
+namespace trim {
+void check_cfg(const conan_trim_cfg& c, const char* who);      // host only
+void detector_rows(const conan_activity_cfg& cfg, const int64_t* lens, int n, int hop, int64_t ld, int64_t frame_ld, cnk::ActRow* rows);      // host only
+void check_args(const conan_ctx* ctx, const conan_mel_cfg* mel, const conan_activity_cfg* act_cfg, const conan_trim_cfg* cfg, const float* wav_dev, int64_t ld,
+                int n, int64_t samples, const int64_t* lengths, const int32_t* act_in_dev, int64_t act_ld, const float* out_dev, int64_t out_ld,
+                const int32_t* mask_out_dev, const int64_t* offset_out_dev, int64_t frame_ld);      // host only
+void whole(conan_ctx* ctx, const conan_mel_cfg* mel, const conan_activity_cfg* act_cfg, const conan_trim_cfg* cfg, const float* wav_dev, int64_t ld, int n,
+           int64_t samples, const int64_t* lengths, const int32_t* act_in_dev, int64_t act_ld, float* out_dev, int64_t out_ld, int32_t* mask_out_dev,
+           int64_t* offset_out_dev, int64_t frame_ld, int64_t* out_len_dev, void* stream);
+}  // namespace trim
 
 // ---- per-slot pitch control (pitch.hip): the bodies of api.hip's entry points
 namespace pitch {

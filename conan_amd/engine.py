@@ -286,7 +286,9 @@ class StreamingVoiceConversionEngine:
         set_pitch_register's keywords.  The followed contour is then moved to the target's register by a causal log-f0 mean.
         activity: the source-activity detector (Streams.set_activity) - None / False: none; True: detect and gate the output with
         the defaults; "detect": detect only; a dict of set_activity's keywords (gate=False: detect only).  chunk_activity() reads
-        the last call's flags."""
+        the last call's flags.
+        There is no trim= here: silence trimming (infer_wav(trim=True)) moves audio forward over pauses it has seen whole, and a
+        stream cannot drop time it has not heard yet; activity= is what a live call has in its place."""
         self._check_voice(ref_mel, voice)
         registers = self._registers(self.slots, register, voice)
         activities = self._activities(self.slots, activity)
@@ -510,7 +512,10 @@ class StreamingVoiceConversionEngine:
         The reference's whole-utterance loud_norm still cannot run here: that loudness is a property of the whole utterance, which a
         streaming call has not seen yet (infer_wav(loud_norm=True) normalises an utterance it holds whole).  What can stream is the
         input leveller, start_wav(level=...): a causal BS.1770 meter of the audio so far steers a ramped gain towards the same
-        target, on the GPU in front of the front-end, without look-ahead or added latency (Context.level is its whole-signal form)."""
+        target, on the GPU in front of the front-end, without look-ahead or added latency (Context.level is its whole-signal form).
+        Silence trimming (infer_wav(trim=True)) cannot run here either: a live call cannot drop time.  What serves there is the
+        activity detector, start_wav(activity=...): per-frame flags and an output gate, and a server that recorded the call can cut
+        the recording afterwards with those flags (Context.trim_silence(flags=...)) without detecting again."""
         fn = self.st.step_wav_async if pipelined else self.st.step_wav
         st = self.st
         if not (st.output_ld or st.output_formats):
@@ -530,9 +535,33 @@ class StreamingVoiceConversionEngine:
             raise ValueError("loud_norm takes float32 rows: decode the utterance first (Context.convert_samples) or pass in_format=None")
         return self.ctx.loud_norm(wav, in_rate or self.st.model_rate)
 
+    @staticmethod
+    def _trim_keywords(trim):
+        """trim= of the whole-utterance calls -> None (off) or Context.trim_silence's keywords: False / None, True, or a dict."""
+        if trim is None or trim is False:
+            return None
+        if trim is True:
+            return {}
+        if isinstance(trim, dict):
+            return dict(trim)
+        raise ValueError(f"trim: {trim!r} is neither True, False nor a dict of Context.trim_silence's keywords")
+
+    @torch.no_grad()
+    def _trim(self, wav, in_rate, in_format, kw):
+        """Context.trim_silence of whole float32 utterances [..., N] at their input rate -> (rows, kept samples per row)."""
+        if in_format not in (None, "f32"):
+            raise ValueError("trim takes float32 rows: decode the utterance first (Context.convert_samples) or pass in_format=None")
+        rate = int(in_rate or self.st.model_rate)
+        if rate % 50:
+            raise ValueError(f"trim: the input rate {rate} must be a multiple of 50 (the detector's frames are 20 ms)")
+        out, kept = self.ctx.trim_silence(wav, hop_size=rate // 50, **kw)
+        if int(np.min(kept)) < 1:
+            raise ValueError("trim: an utterance has no activity, nothing is left of it")
+        return out, kept
+
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
-                  out_format=None, loud_norm=False, level=None, pitch=None, voice=None, follow=None, register=None, activity=None,
+                  out_format=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None, register=None, activity=None,
                   activity_log=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] (or None with voice = (bank, ids): start) -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
@@ -542,6 +571,11 @@ class StreamingVoiceConversionEngine:
         bit for bit); out_format: the returned wav's format (ctx.convert_samples of the float wav bit for bit).
         loud_norm: each whole source utterance is loudness-normalised at its input rate before it is fed (the reference's loud_norm;
         float32 rows only); the results are those of infer_wav(ctx.loud_norm(src_wav, rate), ...) bit for bit.
+        trim: True, or a dict of Context.trim_silence's keywords: the long pauses are cut out of each whole utterance at its input rate
+        (a multiple of 50; float32 rows only) before loud_norm and before anything is fed - every trimmed second is a second of
+        Emformer, decoder and vocoder work not done.  The rows of one call are fed together, so they come back as long as the longest
+        kept one, the shorter ones with zeros behind their audio: the results are those of infer_wav(ctx.trim_silence(src_wav,
+        hop_size=rate // 50)[0], ...) bit for bit (infer_wav_staggered trims every utterance to its own length).
         level: the streaming input leveller (start_wav); the results are those of infer_wav(ctx.level(x, **level), ...) bit for bit,
         x = the decoded, resampled utterance.  pitch: the slots' pitch control in the decoder step (start).  follow: source-pitch
         following (start_wav): the decoder steps take ctx.f0 of the samples the front-end reads instead of the predictor's contour.
@@ -552,6 +586,9 @@ class StreamingVoiceConversionEngine:
         self._check_voice(ref_mel, voice)
         self._registers(self.slots, register, voice)      # (host checks before anything runs)
         self._activities(self.slots, activity)
+        trim = self._trim_keywords(trim)
+        if trim is not None:
+            src_wav = self._trim(src_wav, in_rate, in_format, trim)[0]
         if loud_norm:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
@@ -594,7 +631,9 @@ class StreamingVoiceConversionEngine:
         slots' pitch control (start), one value or a list with one per slot.  voice: (bank, ids) - enrolled voices, one id per slot, in
         place of ref_mel (then None): one launch instead of a style pass per slot.  follow: the slots' source-pitch following
         (start_wav), one value or a list with one per slot.  register: the slots' register matching (start_wav), one value or a list
-        with one per slot.  activity: the slots' activity detector (start_wav), one value or a list with one per slot."""
+        with one per slot.  activity: the slots' activity detector (start_wav), one value or a list with one per slot.
+        No trim=, as in start_wav: the slots stream, and a stream cannot drop time (infer_wav_staggered(trim=True) trims utterances
+        it holds whole)."""
         self._check_voice(ref_mel, voice)
         registers = self._registers(slots, register, voice)
         activities = self._activities(slots, activity)
@@ -628,8 +667,8 @@ class StreamingVoiceConversionEngine:
 
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
-                            in_formats=None, out_formats=None, loud_norm=False, level=None, pitch=None, voice=None, follow=None, register=None,
-                            activity=None, activity_log=None, **filter):
+                            in_formats=None, out_formats=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None,
+                            register=None, activity=None, activity_log=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -639,7 +678,9 @@ class StreamingVoiceConversionEngine:
         then mixes rates, with rows as wide as the widest input of the call.  out_rates[u] (+ out_filter): the rate utterance u's
         wav is returned at (None: the model rate).  in_formats[u] / out_formats[u]: the sample format utterance u arrives / is
         returned in (None: float32); one call then mixes formats, each row packed in its own.  loud_norm: every utterance is
-        loudness-normalised whole, at its own input rate, before its first audio is fed (float32 utterances only).  level: the
+        loudness-normalised whole, at its own input rate, before its first audio is fed (float32 utterances only).  trim: True, or a
+        dict of Context.trim_silence's keywords: the long pauses are cut out of every utterance, whole, at its own input rate (a
+        multiple of 50; float32 utterances only) before loud_norm; each keeps its own trimmed length.  level: the
         streaming input leveller (start_wav), one value for every utterance or a list with one per utterance.  pitch: the pitch
         control (start), one value for every utterance or a list with one per utterance.  voice: (bank, ids) - one enrolled id per
         utterance, in place of ref_mel (then None).  follow: source-pitch following (start_wav), one value for every
@@ -657,6 +698,9 @@ class StreamingVoiceConversionEngine:
         levels = list(level) if isinstance(level, (list, tuple)) else [level] * U
         pitches = list(pitch) if isinstance(pitch, (list, tuple)) else [pitch] * U
         ifmts, ofmts, orates, rates = (list(v) if v is not None else [None] * U for v in (in_formats, out_formats, out_rates, in_rates))
+        trim = self._trim_keywords(trim)
+        if trim is not None:
+            src_wavs = [self._trim(x, rates[u], ifmts[u], trim)[0] for u, x in enumerate(src_wavs)]      # (one row: cut to its kept length)
         if loud_norm:
             src_wavs = [self._loud_norm(x, rates[u], ifmts[u]) for u, x in enumerate(src_wavs)]
         assert len(starts) == U and len(ref_mel if voice is None else voice[1]) == U

@@ -311,6 +311,59 @@ class Context:
                                                 _stream()))
         return y
 
+    def trim_silence(self, wav, lengths=None, flags=None, cfg=None, smooth_frames=12, max_silence_frames=18, norm=False, return_mask=False,
+                     fft_size=1024, hop_size=None, activity_cfg=None, **activity_kw):
+        """The reference's trim_long_sil on the GPU (conan_trim_silence; include/conan_hip.h, conan_trim_cfg): wav [..., N] float32 at
+        the model rate (50 * hop_size; hop_size defaults to the vocoder's hop) -> (out [..., max(out_lengths)] float32: each row's
+        kept frames moved together, zeros behind them; out_lengths: int64 numpy [...], the one host read of the call).  The frames
+        are the detector's (1 + len // hop_size per row, 20 ms each); a frame is kept where the moving average of the flags over
+        smooth_frames frames rounds to 1, or within a pause of at most max_silence_frames frames between such frames.  flags:
+        int32 [..., >= frames] (any non-zero: active) - e.g. what a live call collected from Streams.step_wav_activity - instead of
+        running the detector; else activity_cfg (an _lib.ActivityCfg) or **activity_kw (_lib.activity_cfg's keywords) configure
+        Context.activity's detector, whose flags these then are bit for bit.  cfg: an _lib.TrimCfg instead of the two widths.
+        lengths: samples per row (default N).  norm=True: the rows first go through loud_norm(target=-20.0, peak_limit=True), as the
+        reference's trim_long_silences(norm=True) does, and the normalised, trimmed audio comes back.  return_mask=True appends
+        the kept-frame mask int32 [..., frames] and the offsets int64 [..., frames] (where a kept frame's samples start in `out`;
+        -1 for a dropped frame)."""
+        dev = torch.device("cuda", self.device)
+        x = wav.to(dev, torch.float32)
+        lead, N = x.shape[:-1], x.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        if not (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= N):      # (a 2-D view with a row stride is read in place)
+            x = x.reshape(n, N).contiguous()
+        hop = int(hop_size or self.hop)
+        lens = None
+        if lengths is not None:
+            lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+            if lens.shape[0] != n:
+                raise ValueError(f"trim_silence: {lens.shape[0]} lengths for {n} rows")
+        if flags is not None and (activity_cfg is not None or activity_kw):
+            raise ValueError("trim_silence: flags= replaces the detector; its keywords make no sense beside them")
+        if norm:
+            x = self.loud_norm(x, 50 * hop, target=-20.0, peak_limit=True, lengths=lens)
+        mc = mel_cfg(fft_size=fft_size, hop_size=hop, win_length=fft_size, sample_rate=50 * hop)
+        tc = cfg if cfg is not None else _lib.trim_cfg(smooth_frames, max_silence_frames)
+        frames = 1 + N // hop
+        fl, ac = None, None
+        if flags is not None:
+            fl = flags.to(dev, torch.int32)
+            if fl.shape[:-1] != lead:
+                raise ValueError(f"trim_silence: wav {tuple(wav.shape)} and flags {tuple(fl.shape)} differ in their leading shape")
+            fl = fl.reshape(n, fl.shape[-1]).contiguous()
+        else:
+            ac = activity_cfg if activity_cfg is not None else _lib.activity_cfg(**activity_kw)
+        out = torch.zeros(n, N, device=dev)
+        mask = torch.zeros(n, frames, dtype=torch.int32, device=dev) if return_mask else None
+        off = torch.full((n, frames), -1, dtype=torch.int64, device=dev) if return_mask else None
+        out_len = torch.empty(n, dtype=torch.int64, device=dev)
+        _lib.check(self.lib.conan_trim_silence(self.h, C.byref(mc), C.byref(ac) if ac is not None else None, C.byref(tc), _ptr(x), x.stride(0), n, N,
+                                               lens.ctypes.data_as(C.c_void_p) if lens is not None else None, _ptr(fl),
+                                               fl.shape[1] if fl is not None else 0, _ptr(out), N, _ptr(mask), _ptr(off), frames, _ptr(out_len),
+                                               _stream()))
+        got = out_len.cpu().numpy()
+        res = (out[:, :int(got.max())].reshape(*lead, -1), got.reshape(*lead) if len(lead) else got[0])
+        return res + (mask.reshape(*lead, frames), off.reshape(*lead, frames)) if return_mask else res
+
     def register_of(self, wav, **f0_keywords):
         """The register of wav [n, N] (or [N]) at the model rate: per row the mean log2 Hz of its voiced frames - Context.f0 followed
         by the measurement of f0_register - or None for a row without a counted frame.  **f0_keywords: Context.f0's."""
@@ -495,9 +548,13 @@ class VoiceBank:
         for i in a:
             self.registers.pop(int(i), None)      # (the id holds another voice now; enroll_wav(register=True) measures it)
 
-    def enroll_wav(self, ids, wav, via=None, sample_rate=None, loud_norm=False, register=False, **mel):
-        """Context.wav2mel of wav [n, samples] - resampled from sample_rate to the mel front-end's rate and loudness-normalised
-        first where asked - then enroll.  **mel: wav2mel's keywords.  register=True also measures each voice's register
+    def enroll_wav(self, ids, wav, via=None, sample_rate=None, loud_norm=False, register=False, trim=False, **mel):
+        """Context.wav2mel of wav [n, samples] - resampled from sample_rate to the mel front-end's rate, loudness-normalised and
+        trimmed first where asked - then enroll.  **mel: wav2mel's keywords.  trim: True, or a dict of Context.trim_silence's
+        keywords: the long pauses of each clip are cut out (behind resampling and loud_norm) so that they neither dilute the style
+        vector nor spend prosody tokens; the rows then differ in length, each is enrolled with its own frame count, and the result
+        is that of enroll(ids, wav2mel(trimmed rows), ref_len) bit for bit.  The front-end's rate must be 50 * hop_size, and a clip
+        without any activity is an error.  register=True also measures each voice's register
         (Context.register_of of the same prepared wav, which must then be at the model rate) into the host dict self.registers[id] -
         what register="voice" of the engine's wav-in calls looks up; export / import_voices do not carry it."""
         rate = int(mel.get("sample_rate", 16000))
@@ -508,7 +565,16 @@ class VoiceBank:
             wav = self.ctx.resample(wav, int(sample_rate), rate)
         if loud_norm:
             wav = self.ctx.loud_norm(wav, rate)
-        self.enroll(ids, self.ctx.wav2mel(wav, **mel), via=via)
+        ref_len = None
+        if trim:
+            hop = int(mel.get("hop_size", 320))
+            if rate != 50 * hop:
+                raise ValueError(f"enroll_wav(trim=): the front-end's sample_rate {rate} must be 50 * hop_size {hop}")
+            wav, kept = self.ctx.trim_silence(wav, hop_size=hop, **({} if trim is True else dict(trim)))
+            if int(kept.min()) < 1:
+                raise ValueError("enroll_wav(trim=): a clip has no activity, nothing is left of it")
+            ref_len = [1 + int(k) // hop for k in kept]
+        self.enroll(ids, self.ctx.wav2mel(wav, **mel), ref_len, via=via)
         if register:
             for i, r in zip(ids, self.ctx.register_of(wav, hop_size=mel.get("hop_size"))):
                 self.registers[int(i)] = r

@@ -4,7 +4,10 @@
 (conan_wav2mel).  A path argument is read with the standard-library `wave` module; a file at another rate is resampled on the GPU
 (conan_resample, preset kaiser_best) where the reference's librosa.core.load(sr=...) resamples (with soxr_hq, a different filter:
 the samples are not librosa's bit for bit).  loud_norm (pyloudnorm's BS.1770 meter, a gain to -22 LUFS, a division by the peak above 1)
-runs on the GPU too (conan_loud_norm).  trim_long_sil (webrtcvad, off in egs/conan_emformer.yaml) raises NotImplementedError."""
+runs on the GPU too (conan_loud_norm).  trim_long_sil (off in egs/conan_emformer.yaml) runs on the GPU as well, for a path argument as
+in the reference: conan_trim_silence on the library's own activity detector, where the reference asks webrtcvad - the same smoothing,
+dilation and hard cuts, on 20 ms frames of another detector, so the cuts are not the reference's sample for sample.  An array argument
+with trim_long_sil raises NotImplementedError, since the reference trims only paths; Context.trim_silence takes arrays."""
 import wave
 
 import numpy as np
@@ -57,13 +60,21 @@ def librosa_wav2spec(wav_path, fft_size=1024, hop_size=256, win_length=1024, win
                      eps=1e-6, sample_rate=22050, loud_norm=False, trim_long_sil=False, ctx=None):
     """Same contract as the reference for the keys the inference path reads: {'wav', 'mel' [T, num_mels], 'wav_orig'}
     ('linear' / 'mel_basis' are not produced).  `ctx`: a finalized conan_amd.runtime.Context (device + library)."""
-    if trim_long_sil:
-        raise NotImplementedError("trim_long_sil (webrtcvad silence trimming) is not available; it is off in egs/conan_emformer.yaml")
+    if trim_long_sil and not isinstance(wav_path, str):
+        raise NotImplementedError("trim_long_sil trims a file given by its path, as in the reference; for an array call Context.trim_silence "
+                                  "and pass the trimmed rows")
+    if trim_long_sil and sample_rate % 50:
+        raise ValueError(f"trim_long_sil: sample_rate {sample_rate} must be a multiple of 50 (the detector's frames are 20 ms)")
     if window != "hann":
         raise NotImplementedError("only the Hann window of the reference configuration")
     if ctx is None:
         raise ValueError("librosa_wav2spec needs ctx= (a finalized conan_amd.runtime.Context): the transform runs on the GPU")
     wav = load_wav_resampled(wav_path, sample_rate, ctx) if isinstance(wav_path, str) else np.asarray(wav_path, dtype=np.float32)
+    if trim_long_sil:       # utils/audio/vad.py: loudness to -20 LUFS, then the kept stretches moved together; 'wav_orig' is the trimmed wav
+        kept, kept_len = ctx.trim_silence(torch.from_numpy(wav), norm=True, hop_size=sample_rate // 50)
+        if int(kept_len) < 1:
+            raise ValueError(f"{wav_path}: trim_long_sil found no activity, nothing is left of the file")
+        wav = kept[:int(kept_len)].cpu().numpy()
     wav_orig = np.copy(wav)
     if loud_norm:       # utils/audio/__init__.py:58-63: after loading / resampling, before the STFT; 'wav_orig' stays untouched
         wav = ctx.loud_norm(torch.from_numpy(wav), sample_rate, target=-22.0, peak_limit=True).cpu().numpy()

@@ -984,6 +984,47 @@ int conan_streams_activity_state(conan_streams* s, const int32_t* slots, int n, 
  * emitted frames read zero. */
 int conan_step_wav_activity(conan_streams* s, int32_t* act_dev, int32_t* level_dev, void* stream);
 
+/* Silence trimming (added within ABI 9: a caller detects it by the exported symbol; no existing struct or call changes).  The offline
+ * half of source activity: the reference's trim_long_sil (utils/audio/vad.py, trim_long_silences) cuts the long pauses out of a whole
+ * recording - a moving average over an external detector's flags, a dilation that keeps short pauses, a hard cut - and this call does
+ * the same on the detector above, for enrolment clips, whole-utterance conversion and recorded calls whose per-frame flags a server
+ * already holds.  The law is all integer, so the GPU, numpy (tests/trim_ref.py) and any cut into launches agree bit for bit.
+ *   Input.  A row of len f32 samples at the rate conan_activity accepts (sample_rate == 50 * hop).  The row has F = 1 + len / hop frames,
+ *     as in the detector.  Frame f owns samples f * hop .. min((f + 1) * hop, len) - 1, the gate's convention: the last frame owns
+ *     len % hop samples, possibly none.
+ *   1. Flags.  act[f] is 0 or 1: conan_activity's flags for the row from the cfg's seed (the same kernel, the same bits), or flags the
+ *     caller supplies (any non-zero counts as 1).
+ *   2. Smoothing.  w = smooth_frames.  S[f] = the sum of act[j], j in [f - (w - 1) / 2, f + w / 2] (integer divisions; zeros outside
+ *     0 .. F-1).  m1[f] = 2 * S[f] > w.  This is the reference's centred moving average followed by np.round: a window that is exactly
+ *     half active rounds to even, that is to 0.
+ *   3. Dilation.  s = max_silence_frames + 1.  m2[f] = the OR of m1[j], j in [f - (s - 1 - s / 2), f + s / 2], clipped to 0 .. F-1:
+ *     scipy.ndimage.binary_dilation(m1, ones(s)), including its off-centre origin for even s.
+ *   4. Compaction.  cnt[f] = the number of samples frame f owns; off[f] = the sum of cnt[j] over j < f with m2[j] set;
+ *     out[off[f] + k] = wav[f * hop + k] for every kept frame, as a bit copy (NaN payloads and -0.0 survive); out_len = the sum of
+ *     cnt[f] * m2[f]; out[out_len .. len-1] = 0; nothing past len is written.  Cuts are hard, as in the reference: they fall in
+ *     stretches the detector called silent.
+ * conan_amd/_lib.py's trim_cfg gives smooth_frames = 12 and max_silence_frames = 18: the reference's 8 and 12 windows of 30 ms kept as
+ * durations on 20 ms frames.  Those defaults are choices, not measurements.  Both window steps are differences of prefix sums, so
+ * their width is free: smooth_frames 1 .. 65536, max_silence_frames 0 .. 65536. */
+typedef struct conan_trim_cfg {
+  int32_t smooth_frames;        /* w, 1 .. 65536 */
+  int32_t max_silence_frames;   /* s - 1, 0 .. 65536: the longest pause (between kept stretches) that is kept whole */
+  int32_t reserved[2];          /* must be 0 */
+} conan_trim_cfg;          /* 16 bytes */
+/* wav_dev: n rows (1 .. 65535) of `samples` samples (1 .. 2^30), row stride ld >= samples; lengths[n] (host; NULL: every row has
+ * `samples`) in 1 .. samples.  `mel` is read as conan_activity reads it (fft_size, hop_size, sample_rate == 50 * hop_size).  Exactly one
+ * of act_cfg (the detector runs: mode 1 or 2, every row from the seed) and act_in_dev (int32 rows of stride act_ld >= the frames of
+ * every row) is given.  out_dev: rows of stride out_ld >= samples, which must not overlap wav_dev's (a parallel move towards lower
+ * addresses races: CONAN_ERR_INVALID); NULL: plan only, no audio is written.  mask_out_dev (int32, m2) and offset_out_dev (int64: off[f],
+ * or -1 for a dropped frame), rows of stride frame_ld >= the frames of every row, and out_len_dev[n] (int64) may each be NULL.  Every
+ * argument is checked before anything is launched.  Asynchronous on `stream`: at most three launches (cnk::activity_kernel when act_cfg
+ * is given, cnk::trim_plan_kernel, cnk::trim_gather_kernel when out_dev is given); scratch comes from the context's workspace, which
+ * conan_wav2mel, conan_loud_norm and conan_activity share: calls on one context are ordered by the caller. */
+int conan_trim_silence(conan_ctx* ctx, const conan_mel_cfg* mel, const conan_activity_cfg* act_cfg, const conan_trim_cfg* cfg,
+                       const float* wav_dev, int64_t ld, int n, int64_t samples, const int64_t* lengths, const int32_t* act_in_dev, int64_t act_ld,
+                       float* out_dev, int64_t out_ld, int32_t* mask_out_dev, int64_t* offset_out_dev, int64_t frame_ld, int64_t* out_len_dev,
+                       void* stream);
+
 /* Voice bank (added within ABI 9: a caller detects it by the exported symbols; no existing struct or call changes).  A bank holds the
  * result of conan_set_reference's style pass for up to `capacity` target voices in device memory, outside any slot: the style vector,
  * both aligner layers' K/V rows of the prosody tokens, their key mask, the token count and the VQ ids.  A server enrols its catalogue
