@@ -5,6 +5,7 @@ that the library loads and exports every declared symbol), but every compute ent
 MI355X and the library must have been built (`python -c "import __graft_entry__ as g; g.build()"`).
 """
 import ctypes as C
+import math
 import os
 import re
 
@@ -153,6 +154,12 @@ _PROTOS = {
     "conan_streams_activity": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "conan_streams_activity_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "conan_step_wav_activity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_streams_set_bypass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "conan_streams_bypass": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "conan_streams_bypass_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "conan_step_wav_bypass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_bypass_mix": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                   C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_trim_silence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "conan_voices_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
@@ -468,6 +475,48 @@ def trim_cfg(smooth_frames=12, max_silence_frames=18):
     """conan_trim_cfg: the moving average's width and the longest pause that is kept whole, in 20 ms frames.  The defaults are the
     reference's 8 and 12 windows of 30 ms kept as durations; they are choices, not measurements."""
     return TrimCfg(int(smooth_frames), int(max_silence_frames), (C.c_int32 * 2)(0, 0))
+
+
+class BypassCfg(C.Structure):
+    """conan_bypass_cfg (include/conan_hip.h)."""
+    _fields_ = [("enabled", C.c_int32), ("reseed", C.c_int32), ("wet_target", C.c_int32), ("dry_target", C.c_int32), ("step", C.c_int32),
+                ("fill_gate", C.c_int32), ("seed_wet", C.c_int32), ("seed_dry", C.c_int32)]
+
+
+class BypassState(C.Structure):
+    """conan_bypass_state (include/conan_hip.h)."""
+    _fields_ = [("wet", C.c_int32), ("dry", C.c_int32), ("dry_eff", C.c_int32), ("reserved", C.c_int32)]
+
+
+def bypass_level(share=None, db=None):
+    """A linear share (1.0 = full) or a decibel figure (0 dB = full) as the law's integer level: rint(share * 2^20), converted once on
+    the host.  Host only."""
+    if db is not None:
+        share = 10.0 ** (float(db) / 20.0)
+    return int(round(float(share) * ACTIVITY_FULL))      # (round half to even: rint)
+
+
+def bypass_step(ramp_ms):
+    """The slew per 20 ms frame of a full-scale ramp of ramp_ms: ceil(2^20 / max(1, ramp_ms / 20))."""
+    return int(math.ceil(ACTIVITY_FULL / max(1.0, float(ramp_ms) / 20.0)))
+
+
+def bypass_cfg(wet=1.0, dry=0.0, ramp_ms=40.0, fill_gate=False, start=None, reseed=False, wet_db=None, dry_db=None, step=None):
+    """An enabled conan_bypass_cfg.  wet / dry: the targets as linear shares of the converted and of the source audio (wet_db= / dry_db=
+    give them in decibels instead); ramp_ms: the time a full-scale change takes (step= gives the levels per frame directly); fill_gate:
+    the dry share is scaled by the closed part of the slot's activity gate (the caller's room tone in pauses); start: the (wet, dry)
+    integer levels 0 .. 2^20 a restart begins from (default: the targets, so a fresh slot does not fade in).  The defaults - full wet,
+    no dry, a 40 ms ramp - are choices, not measurements."""
+    w, d = bypass_level(wet, wet_db), bypass_level(dry, dry_db)
+    sw, sd = (w, d) if start is None else (int(start[0]), int(start[1]))
+    return BypassCfg(1, int(bool(reseed)), w, d, bypass_step(ramp_ms) if step is None else int(step), int(bool(fill_gate)), sw, sd)
+
+
+def bypass_keywords(c):
+    """bypass_cfg's keywords of an enabled BypassCfg in the integer forms that give the same fields back exactly (wet / dry as shares
+    k / 2^20, which rint(share * 2^20) maps back to k): the form Streams.bypass reports a setting in."""
+    return dict(wet=c.wet_target / ACTIVITY_FULL, dry=c.dry_target / ACTIVITY_FULL, step=int(c.step), fill_gate=bool(c.fill_gate),
+                start=(int(c.seed_wet), int(c.seed_dry)))
 
 
 class DecoderTaps(C.Structure):

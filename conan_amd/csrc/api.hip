@@ -350,6 +350,8 @@ int conan_streams_reset(conan_streams* s, const int32_t* slots, int n, int which
       for (int i = 0; i < n && !s->reg.pending.empty(); ++i) s->reg.pending[slots[i]] = 1;
       // ... and so does the activity setting, whose state restarts from its seed in the slot's next detector row
       for (int i = 0; i < n && !s->act.pending.empty(); ++i) s->act.pending[slots[i]] = 1;
+      // ... and the bypass setting, whose levels restart from their seeds in the slot's next stage row
+      for (int i = 0; i < n && !s->byp.pending.empty(); ++i) s->byp.pending[slots[i]] = 1;
     }
   });
 }
@@ -499,6 +501,26 @@ int conan_streams_activity_state(conan_streams* s, const int32_t* slots, int n, 
 
 int conan_step_wav_activity(conan_streams* s, int32_t* act_dev, int32_t* level_dev, void* stream) {
   return guarded([&] { act::last_call(s, act_dev, level_dev, stream); });
+}
+
+int conan_streams_set_bypass(conan_streams* s, const int32_t* slots, int n, const conan_bypass_cfg* cfg, void* stream) {
+  return guarded([&] { byp::set_bypass(s, slots, n, cfg, stream); });
+}
+
+int conan_streams_bypass(const conan_streams* s, int slot, conan_bypass_cfg* cfg_out) { return guarded([&] { byp::get_bypass(s, slot, cfg_out); }); }
+
+int conan_streams_bypass_state(conan_streams* s, const int32_t* slots, int n, conan_bypass_state* state_dev, void* stream) {
+  return guarded([&] { byp::state(s, slots, n, state_dev, stream); });
+}
+
+int conan_step_wav_bypass(conan_streams* s, int32_t* wet_lvl_dev, int32_t* dry_lvl_dev, void* stream) {
+  return guarded([&] { byp::last_call(s, wet_lvl_dev, dry_lvl_dev, stream); });
+}
+
+int conan_bypass_mix(conan_ctx* ctx, int hop, const float* wet_dev, int64_t wet_ld, const float* dry_dev, int64_t dry_ld, int n, int64_t samples,
+                     const int32_t* wet_lvl_dev, const int32_t* dry_lvl_dev, int64_t lvl_ld, int32_t start_wet, int32_t start_dry, float* out_dev,
+                     int64_t out_ld, void* stream) {
+  return guarded([&] { byp::mix(ctx, hop, wet_dev, wet_ld, dry_dev, dry_ld, n, samples, wet_lvl_dev, dry_lvl_dev, lvl_ld, start_wet, start_dry, out_dev, out_ld, stream); });
 }
 
 int conan_trim_silence(conan_ctx* ctx, const conan_mel_cfg* mel, const conan_activity_cfg* act_cfg, const conan_trim_cfg* cfg, const float* wav_dev, int64_t ld,

@@ -520,6 +520,44 @@ struct ActGateArgs {
 constexpr int kActGateThreads = 256;
 void launch_activity_gate(const ActGateArgs& a, hipStream_t st);
 
+// Source bypass (bypass.hip; include/conan_hip.h, conan_bypass_cfg).  bypass_stage_kernel: one workgroup per row.  A row with mode 1
+// runs the slew over its nframes <= seg frames from state[slot] (reseed = 0 and slot >= 0) or from its seed, writes the wet and
+// effective dry levels to wet_lvl / dry_lvl [row][seg + 1] (word 0: the level before the chunk), the state after the row to
+// state[slot] (slot >= 0) and state_out[state_row] (state_row >= 0), and copies nframes * hop samples - sample s_first + j of the
+// slot's signal from src[src_off + ((s_first + j) & mask)], zero at and beyond `valid` - to dry[row][seg * hop].  fill = 0: the
+// effective dry level of a frame is the dry level; 1: it is scaled by the closed part of gate_lvl[row][1 + f] (the activity staging of
+// the same call, whose rows are in the same order); 2: the slot fills but has no gate, which counts as open - the effective level is
+// 0.  mode = 0: a row of a slot without the feature, which holds its
+// place in the table so that the mix finds row i of a vocoder step at entry i.
+struct BypState { int wet, dry, dry_eff, reserved; };
+static_assert(sizeof(BypState) == 16, "conan_bypass_state");
+struct BypRow {
+  long long src_off, valid, s_first;
+  BypState seed;
+  int mask, nframes, slot, reseed, state_row, mode;
+  int wet_target, dry_target, step, fill;
+};
+static_assert(sizeof(BypRow) == 80, "uploaded as 20 ints");
+struct BypStageArgs {
+  const float* src; float* dry; int* wet_lvl; int* dry_lvl;
+  const int* gate_lvl;      // [rows][seg + 1]; null when no row has fill = 1
+  BypState* state;          // [max_slots], indexed by slot; may be null when no row names a slot
+  BypState* state_out;      // [rows]; may be null when no row has a state_row
+  const BypRow* tab; int rows, seg, hop;
+};
+constexpr int kBypStageThreads = 256;
+void launch_bypass_stage(const BypStageArgs& a, hipStream_t st);
+// The mix: row i of the launch is wet + i * wet_ld and dry + i * dry_ld -> out + i * out_ld (out may equal wet), `samples` samples; its
+// levels are wet_lvl / dry_lvl [i * lvl_ld + f] after frame f, and before frame 0 start_wet / start_dry (start_in_lvl = 0) or the
+// words at [i * lvl_ld - 1] (start_in_lvl = 1: the stage kernel's rows).  tab != nullptr: rows with tab[i].mode == 0 are skipped.
+struct BypMixArgs {
+  const float* wet; const float* dry; float* out; const int* wet_lvl; const int* dry_lvl; const BypRow* tab;
+  long long wet_ld, dry_ld, out_ld, lvl_ld, samples;
+  int n, hop, start_wet, start_dry, start_in_lvl;
+};
+constexpr int kBypMixThreads = 256;
+void launch_bypass_mix(const BypMixArgs& a, hipStream_t st);
+
 // Silence trimming (trim.hip; include/conan_hip.h, conan_trim_cfg).  Row i has lens[i] samples at wav + i * ld and F = 1 + lens[i] / hop
 // frames; its flags are act[i * act_ld + f] (any non-zero counts as 1).  The plan kernel (one workgroup per row) writes the row's two
 // prefix arrays pa / pb [i * pre_ld + 0 .. F] (scratch: the prefixes of act and of m1), the kept-frame mask m2 to mask[i * mask_ld + f]

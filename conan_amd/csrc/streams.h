@@ -257,6 +257,28 @@ struct conan_streams {
     bool on(int slot) const { return n_on > 0 && cfg[slot].mode != 0; }
   } act;
   void activity_init();
+  // source bypass (conan_streams_set_bypass; bypass.hip): per slot its cfg as set (enabled = 0: none; reseed kept 0), which persists
+  // across resets; n_on: slots with one; pending: the slot's state restarts from the cfg's seed in its next stage row (as act.pending).
+  // state: [max_slots] on the device, read and written by the rows of bypass_stage_kernel in the order of the front-end launches.  Per
+  // call a row table (set q of `sets`: one row per emitting call row in chunk-row order, mode 0 for a slot without the feature) and
+  // beside it the wet and effective dry levels [q][chunk row][seg + 1] (word 0: the level before the chunk) and the dry samples
+  // [q][chunk row][seg * hop] on their way from the front-end stage to the vocoder stage of the same call.  The samples are staged, not
+  // read from the audio ring by the mix: under pipelining the vocoder runs several calls behind the front-end that overwrites the
+  // ring.  The set's event is recorded behind the call's last vocoder step; kActSets sets for the reason given there.  Allocated by the
+  // first enabling call; state, staging and row tables count as stream state.  last: the rows of the most recent wav-in call that
+  // mixed (conan_step_wav_bypass).
+  struct Bypass {
+    std::vector<conan_bypass_cfg> cfg;
+    std::vector<char> pending;
+    int n_on = 0;
+    cnk::BypState* state = nullptr;
+    int* wet_lvl[kActSets] = {}; int* dry_lvl[kActSets] = {}; float* dry[kActSets] = {};
+    StageSets<cnk::BypRow, kActSets> sets;
+    struct LastRow { int row, set, src, emit; };
+    std::vector<LastRow> last;
+    bool on(int slot) const { return n_on > 0 && cfg[slot].enabled; }
+  } byp;
+  void bypass_init();
   void ragged_init();
   void resample_init();        // staging, row tables and the history ring (conan_streams_set_input_rate)
   void rs_stage_init();        // staging and row tables only (conan_streams_set_input_format: no stream state)
@@ -309,6 +331,10 @@ struct conan_streams {
     // the step's output gate (activity.hip; set by the wav-in step for a group with a gated row): the group's rows of the call's
     // activity table and of its level staging; hifigan_step launches activity_gate_kernel on the rows conv_post wrote
     const cnk::ActRow* gate_tab = nullptr; const int* gate_lvl = nullptr; int gate_lvl_ld = 0;
+    // the step's wet/dry mix (bypass.hip; set by the wav-in step for a group with a bypass row): the group's rows of the call's bypass
+    // table, of its level staging and of its dry staging; hifigan_step launches bypass_mix_kernel behind the gate
+    const cnk::BypRow* byp_tab = nullptr; const int* byp_wet_lvl = nullptr; const int* byp_dry_lvl = nullptr; const float* byp_dry = nullptr;
+    int byp_lvl_ld = 0; long long byp_dry_ld = 0;
   };
   OutPlan out_plan(const int32_t* slots, int n, int frames, float* wav_out_dev, long long natural_ld, const std::vector<int>* dst, const std::string& who) const;
   // the plan's resample_out_kernel launch behind or_sets.begin() = q, then the set's event; src_ld: stride of the staged rows (a flush: 0)
@@ -624,6 +650,18 @@ void get_activity(const conan_streams* s, int slot, conan_activity_cfg* out);
 void state(conan_streams* s, const int32_t* slots, int n, conan_activity_state* state_dev, void* stream);
 void last_call(conan_streams* s, int32_t* act_dev, int32_t* level_dev, void* stream);
 }  // namespace act
+
+// ---- source bypass (bypass.hip): the kernels' host side and the bodies of api.hip's entry points
+namespace byp {
+void check_cfg(const conan_bypass_cfg& c, const char* who);      // host only
+cnk::BypRow row(const conan_bypass_cfg& c);      // the cfg's fields of a stage row that starts from the seed and names no slot
+void mix(conan_ctx* ctx, int hop, const float* wet_dev, int64_t wet_ld, const float* dry_dev, int64_t dry_ld, int n, int64_t samples, const int32_t* wet_lvl_dev,
+         const int32_t* dry_lvl_dev, int64_t lvl_ld, int32_t start_wet, int32_t start_dry, float* out_dev, int64_t out_ld, void* stream);
+void set_bypass(conan_streams* s, const int32_t* slots, int n, const conan_bypass_cfg* cfg, void* stream);
+void get_bypass(const conan_streams* s, int slot, conan_bypass_cfg* out);
+void state(conan_streams* s, const int32_t* slots, int n, conan_bypass_state* state_dev, void* stream);
+void last_call(conan_streams* s, int32_t* wet_lvl_dev, int32_t* dry_lvl_dev, void* stream);
+}  // namespace byp
 
 // ---- silence trimming (trim.hip): the kernels' host side and the body of api.hip's entry point
 namespace trim {

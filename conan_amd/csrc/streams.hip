@@ -626,6 +626,12 @@ void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float*
       g.n = n; g.hop = ctx->hop; g.start_in_lvl = 1;
       profiled("activity_gate_kernel", 0.0, st, [&] { cnk::launch_activity_gate(g, st); });
     }
+    if (op && op->byp_tab) {      // the wet/dry mix of a wav-in step (bypass.hip), behind the gate, in place on the same rows
+      cnk::BypMixArgs b; memset(&b, 0, sizeof(b));
+      b.wet = a.wav; b.out = a.wav; b.dry = op->byp_dry; b.wet_lvl = op->byp_wet_lvl; b.dry_lvl = op->byp_dry_lvl; b.tab = op->byp_tab;
+      b.wet_ld = T; b.out_ld = T; b.dry_ld = op->byp_dry_ld; b.lvl_ld = op->byp_lvl_ld; b.samples = T; b.n = n; b.hop = ctx->hop; b.start_in_lvl = 1;
+      profiled("bypass_mix_kernel", 0.0, st, [&] { cnk::launch_bypass_mix(b, st); });
+    }
     if (out_rows) resample_out(*op, oq, T, st);
     // the launches are enqueued: the slots' host counters, and the counts conan_streams_output_samples reports
     if (!op || op->dst.empty()) wav_out.out_counts.assign(n, T);

@@ -375,6 +375,42 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
         act_rows.push_back(r);
       }
   }
+  // source bypass (bypass.hip): a call in which a slot with the feature emits has one table row per emitting call row, in chunk-row
+  // order, as the activity table: the stage rows, and mode-0 rows for the other slots so that a group's mix finds its rows by their place
+  std::vector<cnk::BypRow> byp_rows;
+  std::vector<conan_streams::Bypass::LastRow> byp_last;
+  std::vector<char> byp_mix(groups.size(), 0);
+  bool byp_fill = false;
+  if (s->byp.n_on > 0) {
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+      const FePlan& p = pl[i];
+      if (!s->byp.on(slots[i]) || p.emit < 1) continue;
+      if (p.R - (long long)p.pos * hop > s->wav_in.fe_LA)
+        throw Error(CONAN_ERR_UNSUPPORTED, who + ": slot " + std::to_string(slots[i]) + " mixes its source: the chunk's samples have left the audio ring");
+      any = true;
+    }
+    for (int g = 0, off = 0; any && g < (int)groups.size(); off += (int)groups[g].size(), ++g)
+      for (int k = 0; k < (int)groups[g].size(); ++k) {
+        const int i = groups[g][k];
+        const FePlan& p = pl[i];
+        cnk::BypRow r;
+        memset(&r, 0, sizeof(r));      // (mode 0, no frames, no slot)
+        r.slot = -1; r.state_row = -1;
+        if (s->byp.on(slots[i])) {
+          r = byp::row(s->byp.cfg[slots[i]]);
+          r.src_off = (long long)slots[i] * s->wav_in.fe_LA; r.valid = p.R; r.mask = s->wav_in.fe_LA - 1; r.s_first = (long long)p.pos * hop;
+          r.nframes = p.emit; r.slot = slots[i]; r.reseed = s->byp.pending[slots[i]];
+          // (the fill reads the gate's levels of this call: the activity table has the same rows in the same order; a slot that
+          // is not in activity mode 2 has no gate, which counts as open)
+          if (r.fill) r.fill = s->act.on(slots[i]) && s->act.cfg[slots[i]].mode == 2 ? 1 : 2;
+          byp_fill = byp_fill || r.fill == 1;
+          byp_last.push_back({i, 0, off + k, p.emit});
+          byp_mix[g] = 1;
+        }
+        byp_rows.push_back(r);
+      }
+  }
   const int nm_in = m.num_mels, nm = c.num_mels;
   int jobs = 0;
   std::vector<RgRow> tab;
@@ -414,6 +450,7 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
   const int fq = f0_rows.empty() ? 0 : s->follow.sets.begin(f0_rows.data(), (int)f0_rows.size(), cst);
   const int gq = reg_rows.empty() ? 0 : s->reg.sets.begin(reg_rows.data(), (int)reg_rows.size(), cst);
   const int aq = act_rows.empty() ? 0 : s->act.sets.begin(act_rows.data(), (int)act_rows.size(), cst);
+  const int bq = byp_rows.empty() ? 0 : s->byp.sets.begin(byp_rows.data(), (int)byp_rows.size(), cst);
   const int* rg_tab = reinterpret_cast<const int*>(s->wav_in.rg_sets.rows[q]);
   std::function<void(hipStream_t)> front;
   if (run) {
@@ -502,6 +539,25 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
       ops[g].gate_tab = s->act.sets.rows[aq] + off; ops[g].gate_lvl = s->act.levels[aq] + (size_t)off * (seg + 1) + 1; ops[g].gate_lvl_ld = seg + 1;
     }
   }
+  // the bypass stage, behind the detector (whose levels a filling row reads): the slew, and the chunk's source samples out of the audio
+  // rings into the set's dry staging; the groups with a bypass row take their rows of table, levels and samples along to their vocoder step
+  if (!byp_rows.empty()) {
+    cnk::BypStageArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = s->wav_in.fe_audio; a.dry = s->byp.dry[bq]; a.wet_lvl = s->byp.wet_lvl[bq]; a.dry_lvl = s->byp.dry_lvl[bq];
+    a.gate_lvl = byp_fill ? s->act.levels[aq] : nullptr; a.state = s->byp.state;
+    a.tab = s->byp.sets.rows[bq]; a.rows = (int)byp_rows.size(); a.seg = seg; a.hop = hop;
+    front = [s, a, before = front](hipStream_t st) {
+      if (before) before(st);
+      s->profiled("bypass_stage_kernel", 0.0, st, [&] { cnk::launch_bypass_stage(a, st); });
+    };
+    for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g) {
+      if (!byp_mix[g]) continue;
+      ops[g].byp_tab = s->byp.sets.rows[bq] + off; ops[g].byp_lvl_ld = seg + 1; ops[g].byp_dry_ld = (long long)seg * hop;
+      ops[g].byp_wet_lvl = s->byp.wet_lvl[bq] + (size_t)off * (seg + 1) + 1; ops[g].byp_dry_lvl = s->byp.dry_lvl[bq] + (size_t)off * (seg + 1) + 1;
+      ops[g].byp_dry = s->byp.dry[bq] + (size_t)off * seg * hop;
+    }
+  }
   cnk::WavScatterArgs sc;
   sc.tab = rg_tab; sc.n = n; sc.seg = seg; sc.nm = nm; sc.hop = hop;
   sc.codes_src = s->wav_in.rg_codes[q]; sc.mel_src = s->wav_in.rg_mel[q]; sc.wav_src = s->wav_in.rg_wav[q];
@@ -546,6 +602,10 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
   for (const cnk::ActRow& ar : act_rows) if (ar.slot >= 0) s->act.pending[ar.slot] = 0;
   for (conan_streams::Activity::LastRow& r : act_last) r.set = aq;
   s->act.last = std::move(act_last);
+  if (!byp_rows.empty()) s->byp.sets.end(bq, last);      // (behind the call's last vocoder step: the mix is the last reader of table, levels and samples)
+  for (const cnk::BypRow& br : byp_rows) if (br.slot >= 0) s->byp.pending[br.slot] = 0;
+  for (conan_streams::Bypass::LastRow& r : byp_last) r.set = bq;
+  s->byp.last = std::move(byp_last);
   if (scatter && !route) {      // (each group's step counted its own rows, in group order: back to the call's rows)
     s->wav_out.out_counts.assign(n, 0);
     for (int i = 0; i < n; ++i) s->wav_out.out_counts[i] = pl[i].emit * hop;

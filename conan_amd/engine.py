@@ -224,6 +224,7 @@ class StreamingVoiceConversionEngine:
         self._followed = False      # set_pitch_follow has been called on the stream-set
         self._registered = False    # set_pitch_register has been called on the stream-set
         self._activity = False      # set_activity has been called on the stream-set
+        self._bypass = False        # set_bypass has been called on the stream-set
 
     @staticmethod
     def _check_voice(ref_mel, voice):
@@ -270,7 +271,7 @@ class StreamingVoiceConversionEngine:
         self._set_pitch(self.slots, pitch)
 
     def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                  pitch=None, voice=None, follow=None, register=None, activity=None, **filter):
+                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
         in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
         in_format: the input's sample format (None: float32; 's16' takes int16 rows, 'ulaw' / 'alaw' uint8), decoded on the GPU.
@@ -286,12 +287,15 @@ class StreamingVoiceConversionEngine:
         set_pitch_register's keywords.  The followed contour is then moved to the target's register by a causal log-f0 mean.
         activity: the source-activity detector (Streams.set_activity) - None / False: none; True: detect and gate the output with
         the defaults; "detect": detect only; a dict of set_activity's keywords (gate=False: detect only).  chunk_activity() reads
-        the last call's flags.
+        the last call's flags.  bypass: the wet/dry mix with the slot's own source audio (Streams.set_bypass) - None / False: none;
+        True: enabled at full wet (a later set_bypass toggles it); a dict of set_bypass's keywords.  chunk_bypass() reads
+        the last call's levels.
         There is no trim= here: silence trimming (infer_wav(trim=True)) moves audio forward over pauses it has seen whole, and a
         stream cannot drop time it has not heard yet; activity= is what a live call has in its place."""
         self._check_voice(ref_mel, voice)
         registers = self._registers(self.slots, register, voice)
         activities = self._activities(self.slots, activity)
+        bypasses = self._bypasses(self.slots, bypass)
         if isinstance(in_format, (list, tuple)) or isinstance(level, (list, tuple)):
             raise ValueError("in_format / level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
         self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice)
@@ -301,6 +305,7 @@ class StreamingVoiceConversionEngine:
         self._set_follow(self.slots, follow)
         self._set_register(self.slots, registers)
         self._set_activity(self.slots, activities)
+        self._set_bypass(self.slots, bypasses)
 
     @staticmethod
     def _activities(slots, activity):
@@ -332,6 +337,45 @@ class StreamingVoiceConversionEngine:
         self._activity = True
         for slot, a in zip(slots, activities):
             self.st.set_activity([slot], cfg=a)
+
+    @staticmethod
+    def _bypasses(slots, bypass):
+        """bypass= (one value or one per slot) -> per slot None or a dict of Streams.set_bypass's keywords.  Host only."""
+        values = list(bypass) if isinstance(bypass, (list, tuple)) else [bypass] * len(slots)
+        if len(values) != len(slots):
+            raise ValueError(f"bypass: {len(values)} values for {len(slots)} slots")
+        out = []
+        for b in values:
+            if b is None or b is False:
+                out.append(None)
+            elif b is True:
+                out.append({})
+            elif isinstance(b, dict):
+                out.append(dict(b))
+            else:
+                raise ValueError(f"bypass: {b!r} (True, a dict of set_bypass's keywords or None)")
+        return out
+
+    def _set_bypass(self, slots, bypasses):
+        """The slots' bypass from _bypasses' list, behind the slots' reset: the levels restart from their seeds at the first emitted
+        chunk.  A stream-set that never used it is left alone."""
+        if all(b is None for b in bypasses) and not self._bypass:
+            return
+        self._bypass = True
+        for slot, b in zip(slots, bypasses):
+            self.st.set_bypass([slot], cfg=b)
+
+    def set_bypass(self, slots=None, cfg=True, **kw):
+        """A live change of the slots' bypass (all slots by default) between feed / feed_ragged calls, also mid-utterance and with
+        pipelined steps in flight: Streams.set_bypass's arguments (cfg=None turns it off; without reseed=True an enabled slot keeps
+        its levels and slews to the new targets - the toggle).  In force from the next emitted chunk."""
+        self._bypass = True
+        self.st.set_bypass(self.slots if slots is None else slots, cfg, **kw)
+
+    def chunk_bypass(self):
+        """The frame-end wet and effective dry levels of the last feed / feed_ragged call (Streams.step_wav_bypass; joins pipelined
+        work): (wet [n, seg], dry [n, seg]) int32 in the call's row order, zeros for rows without the feature and past a row's frames."""
+        return self.st.step_wav_bypass()
 
     def set_activity(self, slots=None, cfg=True, **kw):
         """A live change of the slots' activity detector (all slots by default) between feed / feed_ragged calls, also mid-utterance
@@ -562,7 +606,7 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
                   out_format=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None, register=None, activity=None,
-                  activity_log=None, **filter):
+                  activity_log=None, bypass=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] (or None with voice = (bank, ids): start) -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
@@ -582,17 +626,20 @@ class StreamingVoiceConversionEngine:
         register: register matching of the followed contour (start_wav): the steps take ctx.f0_register of that contour.
         activity: the source-activity detector (start_wav): ctx.activity of the samples the front-end reads, and with the gate the
         returned wav is ctx.activity_gate of the ungated one, bit for bit.  activity_log: a list that receives (act [B, emit],
-        level [B, emit]) per emitted chunk (chunk_activity after each call, which joins pipelined work)."""
+        level [B, emit]) per emitted chunk (chunk_activity after each call, which joins pipelined work).
+        bypass: the wet/dry mix (start_wav): the returned wav is ctx.bypass_mix of the unmixed one and of the samples the front-end
+        reads, bit for bit."""
         self._check_voice(ref_mel, voice)
         self._registers(self.slots, register, voice)      # (host checks before anything runs)
         self._activities(self.slots, activity)
+        self._bypasses(self.slots, bypass)
         trim = self._trim_keywords(trim)
         if trim is not None:
             src_wav = self._trim(src_wav, in_rate, in_format, trim)[0]
         if loud_norm:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
-                       pitch=pitch, voice=voice, follow=follow, register=register, activity=activity, **filter)
+                       pitch=pitch, voice=voice, follow=follow, register=register, activity=activity, bypass=bypass, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -622,7 +669,7 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                   pitch=None, voice=None, follow=None, register=None, activity=None, **filter):
+                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
         rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
@@ -631,12 +678,14 @@ class StreamingVoiceConversionEngine:
         slots' pitch control (start), one value or a list with one per slot.  voice: (bank, ids) - enrolled voices, one id per slot, in
         place of ref_mel (then None): one launch instead of a style pass per slot.  follow: the slots' source-pitch following
         (start_wav), one value or a list with one per slot.  register: the slots' register matching (start_wav), one value or a list
-        with one per slot.  activity: the slots' activity detector (start_wav), one value or a list with one per slot.
+        with one per slot.  activity: the slots' activity detector (start_wav), one value or a list with one per slot.  bypass: the
+        slots' wet/dry mix (start_wav), one value or a list with one per slot.
         No trim=, as in start_wav: the slots stream, and a stream cannot drop time (infer_wav_staggered(trim=True) trims utterances
         it holds whole)."""
         self._check_voice(ref_mel, voice)
         registers = self._registers(slots, register, voice)
         activities = self._activities(slots, activity)
+        bypasses = self._bypasses(slots, bypass)
         self.st.reset(slots, which=7 | 8)
         self._reference(slots, ref_mel, ref_len, voice)
         self._set_out_rate(slots, out_rate, out_filter)
@@ -649,6 +698,7 @@ class StreamingVoiceConversionEngine:
         self._set_follow(slots, follow)
         self._set_register(slots, registers)
         self._set_activity(slots, activities)
+        self._set_bypass(slots, bypasses)
 
     @torch.no_grad()
     def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None):
@@ -668,7 +718,7 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
                             in_formats=None, out_formats=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None,
-                            register=None, activity=None, activity_log=None, **filter):
+                            register=None, activity=None, activity_log=None, bypass=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -687,11 +737,13 @@ class StreamingVoiceConversionEngine:
         utterance or a list with one per utterance.  register: register matching (start_wav), one value for every utterance or a list
         with one per utterance.  activity: the activity detector (start_wav), one value for every utterance or a list with one per
         utterance.  activity_log: a list that receives, per utterance, a list of (act [emit], level [emit]) per emitted chunk
-        (chunk_activity after each call, which joins pipelined work)."""
+        (chunk_activity after each call, which joins pipelined work).  bypass: the wet/dry mix (start_wav), one value for every
+        utterance or a list with one per utterance."""
         voice = self._check_voice(ref_mel, voice)
         U = len(src_wavs)
         registers = self._registers(range(U), register, voice)      # (host checks before anything runs; per utterance, as dicts)
         activities = self._activities(range(U), activity)
+        bypasses = self._bypasses(range(U), bypass)
         if activity_log is not None:
             activity_log[:] = [[] for _ in range(U)]
         follows = list(follow) if isinstance(follow, (list, tuple)) else [follow] * U
@@ -724,6 +776,7 @@ class StreamingVoiceConversionEngine:
                                 out_rate=[orates[u] for u in new], out_filter=out_filter, in_format=[ifmts[u] for u in new],
                                 out_format=[ofmts[u] for u in new], level=[levels[u] for u in new], pitch=[pitches[u] for u in new],
                                 follow=[follows[u] for u in new], register=[registers[u] for u in new], activity=[activities[u] for u in new],
+                                bypass=[bypasses[u] for u in new],
                                 **filter)
             if not live:
                 tick += 1

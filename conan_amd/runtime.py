@@ -364,6 +364,45 @@ class Context:
         res = (out[:, :int(got.max())].reshape(*lead, -1), got.reshape(*lead) if len(lead) else got[0])
         return res + (mask.reshape(*lead, frames), off.reshape(*lead, frames)) if return_mask else res
 
+    def bypass_mix(self, wet, dry, wet_levels, dry_levels, start=(_lib.ACTIVITY_FULL, 0), hop_size=None, out=None):
+        """The bypass mix on whole signals (conan_bypass_mix; include/conan_hip.h, conan_bypass_cfg): wet [..., N] (the converted
+        audio) and dry [..., N] (the source) float32, with the frame-end levels wet_levels / dry_levels [..., >= ceil(N / hop)] int32 in
+        0 .. 2^20 (the dry ones are the effective levels, as Streams.step_wav_bypass returns them) and start = (wet0, dry0), the levels
+        before frame 0 -> [..., N].  The levels move linearly inside a frame; full wet and no dry leaves wet's bits alone.  A 2-D
+        operand whose rows are contiguous keeps its row stride (a view of a wider buffer is read in place); out=wet mixes in place.
+        It is what a wav-in slot with Streams.set_bypass computes, bit for bit."""
+        dev = torch.device("cuda", self.device)
+
+        def rows(t, dtype):
+            t = t.to(dev, dtype)
+            if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
+                return t, t.stride(0)
+            t = t.contiguous()
+            return t, t.shape[-1]
+
+        x, x_ld = rows(wet, torch.float32)
+        d, d_ld = rows(dry, torch.float32)
+        lw, lw_ld = rows(wet_levels, torch.int32)
+        ldv, ld_ld = rows(dry_levels, torch.int32)
+        lead, N = x.shape[:-1], x.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        if d.shape != x.shape:
+            raise ValueError(f"bypass_mix: wet {tuple(x.shape)} and dry {tuple(d.shape)} differ in shape")
+        if lw.shape[:-1] != lead or ldv.shape != lw.shape:
+            raise ValueError(f"bypass_mix: wet {tuple(x.shape)}, wet_levels {tuple(lw.shape)} and dry_levels {tuple(ldv.shape)} do not match")
+        if ld_ld != lw_ld:
+            ldv, lw = ldv.contiguous(), lw.contiguous()
+            lw_ld = ld_ld = lw.shape[-1]
+        if out is None:
+            y, y_ld = torch.empty(x.shape, dtype=torch.float32, device=dev), N
+        else:
+            y, y_ld = (out, out.stride(0)) if out.dim() == 2 and out.stride(1) == 1 else (out, N)
+            if y.shape != x.shape or y.dtype != torch.float32 or y.device != dev or not (y.is_contiguous() or (y.dim() == 2 and y.stride(1) == 1 and y_ld >= N)):
+                raise ValueError("bypass_mix: out must be a float32 tensor of wet's shape on the device, contiguous or a 2-D view with contiguous rows")
+        _lib.check(self.lib.conan_bypass_mix(self.h, int(hop_size or self.hop), _ptr(x), x_ld, _ptr(d), d_ld, n, N, _ptr(lw), _ptr(ldv), lw_ld,
+                                             int(start[0]), int(start[1]), _ptr(y), y_ld, _stream()))
+        return y
+
     def register_of(self, wav, **f0_keywords):
         """The register of wav [n, N] (or [N]) at the model rate: per row the mean log2 Hz of its voiced frames - Context.f0 followed
         by the measurement of f0_register - or None for a row without a counted frame.  **f0_keywords: Context.f0's."""
@@ -934,6 +973,60 @@ class Streams:
         _lib.check(self.lib.conan_step_wav_activity(self.h, _ptr(act), _ptr(lvl), _stream()))
         self._release()
         return act[:n], lvl[:n]
+
+    def set_bypass(self, slots, cfg=True, wet=1.0, dry=0.0, ramp_ms=40.0, fill_gate=False, start=None, reseed=False, **kw):
+        """conan_streams_set_bypass: a latency-matched dry path and a wet/dry mix on the slots' output (wav-in steps only).  The chunk's
+        source samples - at the model rate, behind decoding, the input resampler and the leveller - are mixed with the vocoder's audio
+        behind the activity gate and in front of the output resampler and encoder: out = wet * converted + dry * source, sample for
+        sample aligned.  wet / dry: the targets as linear shares (wet_db= / dry_db=: in decibels); ramp_ms: the time a full-scale
+        change takes, in steps of one 20 ms frame, linear inside a frame (step=: levels per frame directly); fill_gate: the dry share is
+        scaled by the closed part of the slot's activity gate (room tone in pauses: set_activity(gate=True) beside it); start: the
+        (wet, dry) integer levels a restart begins from (default: the targets).  cfg: True, a dict of these keywords, an
+        _lib.BypassCfg, or None, which turns the feature off.  The defaults are choices, not measurements.
+        It may be called at any time (it joins pipelined work); the change takes effect from the next emitted chunk and survives
+        resets.  The levels restart from `start` when a slot is enabled, after reseed=True and at the first chunk after a reset of the
+        front-end; reseed=False on an enabled slot replaces targets, ramp and fill_gate and keeps the levels - the toggle.  Slot
+        snapshots do not carry it: query bypass_state, export, import, then set_bypass(start=(wet, dry), reseed=True)."""
+        a, p = _i32(slots)
+        if cfg is None:
+            c = _lib.BypassCfg()      # (enabled = 0)
+        elif isinstance(cfg, _lib.BypassCfg):
+            c = cfg
+        else:
+            base = dict(wet=wet, dry=dry, ramp_ms=ramp_ms, fill_gate=fill_gate, start=start, reseed=reseed)
+            c = _lib.bypass_cfg(**dict(base, **dict({} if cfg is True else cfg, **kw)))
+        _lib.check(self.lib.conan_streams_set_bypass(self.h, p, len(a), C.byref(c), _stream()))
+        self._release()
+
+    def bypass(self, slots):
+        """conan_streams_bypass: per slot the setting as _lib.bypass_keywords reports it (set_bypass takes it back), None for a slot
+        without the feature."""
+        out = []
+        for slot in slots:
+            c = _lib.BypassCfg()
+            _lib.check(self.lib.conan_streams_bypass(self.h, int(slot), C.byref(c)))
+            out.append(_lib.bypass_keywords(c) if c.enabled else None)
+        return out
+
+    def bypass_state(self, slots):
+        """conan_streams_bypass_state (joins pipelined work, synchronises): per slot dict(wet, dry, dry_eff), the levels after the
+        slot's last emitted frame; a slot whose levels are about to restart reports its seed.  A slot without the feature is an error."""
+        a, p = _i32(slots)
+        buf = torch.empty(len(a), 4, dtype=torch.int32, device=self.dev)
+        _lib.check(self.lib.conan_streams_bypass_state(self.h, p, len(a), _ptr(buf), _stream()))
+        self._release()
+        return [dict(wet=int(r[0]), dry=int(r[1]), dry_eff=int(r[2])) for r in buf.cpu().tolist()]
+
+    def step_wav_bypass(self):
+        """The frame-end wet and effective dry levels the last wav-in call produced (conan_step_wav_bypass; joins pipelined work) ->
+        (wet [n, seg] int32, dry [n, seg] int32) in call order; rows without the feature, rows that emitted nothing and entries past a
+        row's emitted frames are 0."""
+        n = self._last_wav_n
+        wet = torch.empty(max(n, 1), self.seg, dtype=torch.int32, device=self.dev)      # (before any wav-in call the library answers CONAN_ERR_STATE)
+        dry = torch.empty(max(n, 1), self.seg, dtype=torch.int32, device=self.dev)
+        _lib.check(self.lib.conan_step_wav_bypass(self.h, _ptr(wet), _ptr(dry), _stream()))
+        self._release()
+        return wet[:n], dry[:n]
 
     def step_wav_contour(self):
         """The contour the last wav-in call handed the decoder (conan_step_wav_contour; joins pipelined work) -> (f0 [n, seg] log2 Hz,

@@ -984,6 +984,78 @@ int conan_streams_activity_state(conan_streams* s, const int32_t* slots, int n, 
  * emitted frames read zero. */
 int conan_step_wav_activity(conan_streams* s, int32_t* act_dev, int32_t* level_dev, void* stream);
 
+/* Source bypass (added within ABI 9: a caller detects it by the symbol conan_streams_set_bypass; no existing struct or call changes).
+ * A latency-matched dry path and a wet/dry mix per slot: a conversion on/off toggle that neither clicks nor jumps in time, a monitor
+ * mix, and the caller's own room tone in place of silence while the activity gate is closed.  Output sample j of a slot's utterance is
+ * made from mel frame j / hop, and source sample j - at the model rate, behind format decoding, the input resampler and the leveller;
+ * zero at and beyond the samples received - is in the slot's audio ring when that frame's chunk is emitted.  The mix runs in front of
+ * the output resampler and the format encoder, so it leaves at the slot's own rate and format, flush included.  The law
+ * (tests/bypass_ref.py restates it in numpy with Python integers); levels are integers in 0 .. 2^20 (CONAN_ACTIVITY_FULL):
+ *   Slew.  Per emitted frame f each of wet and dry moves towards its target by at most step: v += clamp(target - v, -step, step).
+ *   Fill.  dry_eff_f = fill_gate ? (dry_f * (2^20 - gate_f)) >> 20 : dry_f, with gate_f the frame-end level the slot's activity
+ *     detector produced for that frame in the same call, and 2^20 where the slot is not in activity mode 2 (an absent gate is open:
+ *     nothing is filled).
+ *   Gain.  Sample k of frame f takes l = prev * (hop - 1 - k) + next * (k + 1), for the wet levels and for the effective dry levels
+ *     separately; the levels before a chunk's first frame are the state's wet and dry_eff.  g = (float)((double)l / (double)(hop << 20)):
+ *     the gate's formula.
+ *   Mix.  With y the vocoder's sample behind the gate and x the source sample: t = y * g_w (one f32 product);
+ *     out = l_d == 0 ? t : fma(x, g_d, t) (one f32 fused multiply-add).  wet = 2^20, dry = 0 gives y bit for bit; wet = 0, dry = 2^20
+ *     gives x in value (only the sign of a zero can differ).  Nothing here has a tolerance.
+ *   Restart.  The state restarts from the seed - wet = seed_wet, dry = seed_dry, dry_eff = the fill formula on seed_dry and the gate's
+ *     level before the chunk - at the slot's first emitted chunk after a reset that includes CONAN_MODEL_FRONTEND, after a setter call
+ *     with reseed = 1 and when a slot that was off is enabled.  A setter call with reseed = 0 on an enabled slot replaces the targets,
+ *     step and fill_gate and keeps the levels: that call is the toggle. */
+typedef struct conan_bypass_cfg {
+  int32_t enabled;         /* 0: off (other fields ignored) | 1 */
+  int32_t reseed;          /* 0 | 1: the state restarts from the seed */
+  int32_t wet_target;      /* 0 .. 2^20 */
+  int32_t dry_target;      /* 0 .. 2^20 */
+  int32_t step;            /* 1 .. 2^20: levels per 20 ms frame */
+  int32_t fill_gate;       /* 0 | 1: the dry level is scaled by the closed part of the slot's activity gate */
+  int32_t seed_wet;        /* 0 .. 2^20 */
+  int32_t seed_dry;        /* 0 .. 2^20 */
+} conan_bypass_cfg;        /* 32 bytes */
+typedef struct conan_bypass_state {
+  int32_t wet, dry;        /* the levels after the last emitted frame */
+  int32_t dry_eff;         /* the effective dry level after that frame */
+  int32_t reserved;
+} conan_bypass_state;      /* 16 bytes */
+/* Sets (cfg->enabled = 1) or removes (0) the bypass for `slots`.  Every argument is checked before anything changes
+ * (CONAN_ERR_INVALID: flags not 0 / 1, levels outside 0 .. 2^20, step outside 1 .. 2^20), a stream-set without the streaming
+ * front-end is CONAN_ERR_STATE, and pending pipelined work is joined; it may be called at any time, also mid-utterance.  The change
+ * takes effect from the next emitted chunk and persists across resets.
+ * What a slot with the feature does.  Every conan_step_wav[_async] / conan_step_wav_ragged[_ld][_async] call that emits a chunk for
+ * it runs ONE more launch (cnk::bypass_stage_kernel, behind the front-end launch and the activity detector's), which runs the slew
+ * over the chunk's frames and copies the chunk's emit * hop source samples from the slot's audio ring into the call's dry staging;
+ * the chunk's samples must still be in the ring, otherwise the call is CONAN_ERR_UNSUPPORTED before anything changes.  The chunk's
+ * vocoder step mixes the rows conv_post wrote, in place, behind the activity gate and in front of the output resampler and the format
+ * encoder: ONE more launch (cnk::bypass_mix_kernel) per vocoder step in which such a row takes part; rows without the feature are
+ * skipped and keep their bits.  The mel-in steps (conan_step[_async]) and conan_hifigan_step* take no waveform and do not mix.
+ * Memory: the first enabling call allocates 16 bytes of state per slot, 8 staging sets of 2 * (segment + 1) int32 and segment * hop
+ * float per slot, and 8 row tables; conan_streams_state_bytes counts them from then on.  A stream-set that never calls the setter
+ * allocates nothing and runs exactly the launches it ran before.
+ * Snapshots carry neither the setting nor the state (the 256-byte host record is full); conan_streams_layout_id and
+ * conan_streams_snapshot_bytes do not change.  The hand-over: conan_streams_bypass_state, export, import, then this setter with
+ * seed_wet / seed_dry = the queried wet / dry and reseed = 1 (beside the activity hand-over where fill_gate is in use). */
+int conan_streams_set_bypass(conan_streams* s, const int32_t* slots, int n, const conan_bypass_cfg* cfg, void* stream);
+/* Host only: the bypass cfg of `slot` as set, reseed = 0 (zeros for a slot without one). */
+int conan_streams_bypass(const conan_streams* s, int slot, conan_bypass_cfg* cfg_out);
+/* The states of `slots` -> state_dev[n], in the order of `stream` behind a join of pipelined work; a slot whose state is about to
+ * restart reports its seed (dry_eff = seed_dry).  A slot without the feature is CONAN_ERR_STATE. */
+int conan_streams_bypass_state(conan_streams* s, const int32_t* slots, int n, conan_bypass_state* state_dev, void* stream);
+/* The frame-end wet and effective dry levels the last wav-in call produced, in call order (joins first): wet_lvl_dev[n][seg] and
+ * dry_lvl_dev[n][seg], int32.  Rows without the feature, rows that emitted nothing and positions behind the emitted frames read zero.
+ * CONAN_ERR_STATE before any wav-in call. */
+int conan_step_wav_bypass(conan_streams* s, int32_t* wet_lvl_dev, int32_t* dry_lvl_dev, void* stream);
+/* The mix on whole signals, and the bit-exact yardstick of the streaming one: row i of wet_dev (n rows in 1 .. 65535 of `samples`
+ * samples, row stride wet_ld) and of dry_dev (row stride dry_ld) with the frame-end levels wet_lvl_dev[i][.] and dry_lvl_dev[i][.]
+ * (int32, 0 .. 2^20, row stride lvl_ld >= ceil(samples / hop); the dry levels are the EFFECTIVE ones) and start_wet / start_dry as the
+ * levels before frame 0 -> out_dev (row stride out_ld; may equal wet_dev with out_ld = wet_ld).  A last frame that the samples cover
+ * only partly is mixed over the part they cover.  One launch (cnk::bypass_mix_kernel) on `stream`. */
+int conan_bypass_mix(conan_ctx* ctx, int hop, const float* wet_dev, int64_t wet_ld, const float* dry_dev, int64_t dry_ld, int n, int64_t samples,
+                     const int32_t* wet_lvl_dev, const int32_t* dry_lvl_dev, int64_t lvl_ld, int32_t start_wet, int32_t start_dry, float* out_dev,
+                     int64_t out_ld, void* stream);
+
 /* Silence trimming (added within ABI 9: a caller detects it by the exported symbol; no existing struct or call changes).  The offline
  * half of source activity: the reference's trim_long_sil (utils/audio/vad.py, trim_long_silences) cuts the long pauses out of a whole
  * recording - a moving average over an external detector's flags, a dilation that keeps short pauses, a hard cut - and this call does
