@@ -717,6 +717,26 @@ int conan_streams_input_level(conan_streams* s, const int32_t* slots, int n, dou
   return guarded([&] { wavio::input_level(s, slots, n, stats_dev, stream); });
 }
 
+int conan_streams_set_output_level(conan_streams* s, const int32_t* slots, int n, const conan_level_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream) {
+  return guarded([&] { olv::set_level(s, slots, n, cfg, seed_dev, seed_ld, stream); });
+}
+
+int conan_streams_output_level_cfg(const conan_streams* s, int slot, conan_level_cfg* cfg_out) { return guarded([&] { olv::get_level(s, slot, cfg_out); }); }
+
+int conan_streams_output_level(conan_streams* s, const int32_t* slots, int n, double* stats_dev, void* stream) {
+  return guarded([&] { olv::stats(s, slots, n, stats_dev, stream); });
+}
+
+int64_t conan_streams_output_level_state_bytes(const conan_streams* s) {
+  int64_t b = 0;
+  const int rc = guarded([&] { b = olv::state_bytes(s); });
+  return rc < 0 ? rc : b;
+}
+
+int conan_streams_output_level_state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream) {
+  return guarded([&] { olv::state(s, slots, n, state_dev, ld, stream); });
+}
+
 int conan_streams_set_input_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg) {
   return guarded([&] { wavio::set_input_rate(s, slots, n, cfg); });
 }

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "level_plan.h"
 #include "voice_layout.h"
 
 namespace cnk {
@@ -737,7 +738,7 @@ void launch_convert_samples(const ConvertSamplesArgs& a, int n, hipStream_t st);
 // state and sums y^2 into the bins between consecutive block edges, loud_gate_kernel (one workgroup per row) sums the bins over the
 // segments and the blocks over their bins, gates, and writes the row's gain, loud_apply_kernel scales.  All filter and energy arithmetic
 // is f64; every sum has one order, fixed by the row alone.
-constexpr int kLdSeg = 128;                      // samples per segment (why 128)
+// (kLdSeg = 128, the samples per segment, is level_plan.h's: the host planning shares it)
 constexpr int kLdLanes = 64;                     // segments per workgroup of the state / energy passes: one wave
 constexpr int kLdStride = kLdSeg + 1;            // LDS floats between two lanes' segments: lane l, step t reads bank (l + t) mod 32
 constexpr int kLdTile = kLdSeg * kLdLanes;       // samples per workgroup
@@ -788,7 +789,6 @@ __host__ __device__ inline double ld_step(const LdBiquad& f, const LdBiquad& g, 
 // goes to the slot's ring of block energies.  At an update instant the window is gated by the whole workgroup and the new gain
 // formed; then the ramps are applied.  One workgroup per row; lv_chunk (level.hip) is the one routine both kernels call.
 constexpr int kLvThreads = 256;
-constexpr int kLvBlocks = 8;                     // gating blocks that can overlap a chunk's complete segments (the host checks)
 constexpr int kLvSegs = 16;                      // LDS segments of a chunk: pending tail + U samples, U <= kLvMaxU
 constexpr int kLvMaxU = (kLvSegs - 1) * kLdSeg;  // 1920
 constexpr int kLvRingPad = 16;                   // blocks a ring holds beyond the window (blocks closed after the instant's J_k)
@@ -806,14 +806,7 @@ struct LvCfg {                                   // conan_level_cfg in the kerne
   double target, boost, cut, g_init;
   int window, peak_limit, clip, pad_;
 };
-struct LvCall {                                  // one chunk
-  long long pos0;                                // stream position of the chunk's first sample
-  int m;                                         // samples (1 .. U)
-  int inst;                                      // 1: an update instant lies in [pos0, pos0 + m) (at most one: m <= U)
-  int u, J;                                      // ... at pos0 + u, with J_k complete blocks
-  int j0, nblk;                                  // the blocks that overlap the chunk's complete segments: j0 .. j0 + nblk - 1
-  int lo[kLvBlocks], hi[kLvBlocks];              // their edges relative to the first segment's start, pos0 - pos0 % kLdSeg
-};
+// (LvCall, one chunk's plan, and kLvBlocks are level_plan.h's)
 struct LvRow {                                   // one call row of level_stream_kernel (uploaded through PinRing)
   LvCall c;
   LvCfg cfg;
@@ -844,6 +837,39 @@ struct LevelSignalArgs {
   LvFilter f;
 };
 void launch_level_signal(const LevelSignalArgs& a, hipStream_t st);
+
+// ---- output leveller (level_out.hip; conan_streams_set_output_level): the same law on the slot's own vocoder audio, split in two.
+// A vocoder step's row is [u_k, u_k + m) with m <= U, and G_{k-1}, G_k depend only on samples before u_k: level_out_apply_kernel (on
+// the step's critical path, shaped like bypass_mix_kernel) reads the two gains from the slot's LvState - or, at position 0, the cfg's
+// initial gain - and writes the ramp in place, leaving the unlevelled samples in a staging row; level_out_meter_kernel (one
+// workgroup per row, behind the step's last launch) runs lv_meter on the staged samples with the instant at the chunk's end
+// (level::plan_end) and leaves {G_k, G_{k+1}} and the stats for the next step's apply.  Row i of a step is entry i of the table; on = 0:
+// a row of a slot without the feature, which both kernels leave at once.  A slot's state is LvState, its two rings of zcap doubles,
+// then prev[4]: the stats of the instant before the latest one (the reading after a whole chunk k is instant k's, not k + 1's).
+struct OlRow {
+  LvCall c;
+  LvCfg cfg;
+  int slot, on, prev, state_row;                 // prev / state_row: the stats query's (1: read prev[4]; fresh: c.pos0 == 0, c.m == 0)
+};
+static_assert(sizeof(OlRow) == 160, "OlRow is uploaded as 40 ints, and sized in include/conan_hip.h");
+constexpr size_t ol_state_bytes(int zcap) { return lv_state_bytes(zcap) + 4 * sizeof(double); }
+struct LevelOutApplyArgs {
+  float* x; long long ld;                        // the step's rows, levelled in place
+  float* stage; long long stage_ld;              // the unlevelled samples, for the meter
+  const char* state; long long state_stride;
+  const OlRow* tab; int n, samples, U;
+};
+constexpr int kOlApplyThreads = 256;
+void launch_level_out_apply(const LevelOutApplyArgs& a, hipStream_t st);
+struct LevelOutMeterArgs {
+  const float* stage; long long stage_ld;
+  char* state; long long state_stride; int zcap;
+  const OlRow* tab; int n;
+  LvFilter f;
+};
+void launch_level_out_meter(const LevelOutMeterArgs& a, hipStream_t st);
+struct LevelOutStatsArgs { const char* state; long long state_stride; int zcap; const OlRow* tab; int n; double* out; };
+void launch_level_out_stats(const LevelOutStatsArgs& a, hipStream_t st);
 
 // ---- style pass (per utterance) helpers
 struct RowMaskArgs { TRef x; TRef m; const int* lens; int T, n, C; int mode; };  // mode 0: sum|x|>0, 1: x[0]!=0

@@ -301,6 +301,25 @@ struct conan_streams {
     std::vector<unsigned char> out_fmt;
     int out_fmt_n = 0;
   } wav_out;
+  // output leveller (conan_streams_set_output_level; level_out.hip): per slot its cfg as set (enabled = 0: none), which persists across
+  // resets; n_on: slots with one.  state: [max_slots] of `stride` bytes on the device (cnk::LvState, the two block rings, the previous
+  // instant's stats), written by level_out_meter_kernel and read by the next step's level_out_apply_kernel in stream order.  The
+  // restart of a reset with CONAN_MODEL_HIFIGAN needs no flag of its own: it returns voc_samples to 0, and a row at position 0
+  // starts meter and gain in both kernels.  Per vocoder step with a levelled row a row table (set q of `sets`: one row per step row,
+  // on = 0 for a slot without the feature) and beside it the staging rows [q][step row][U] in which the apply leaves the unlevelled
+  // samples for the meter - staged, not read from the step's rows, because the meter runs behind the apply, the gate and the mix,
+  // which all work in place.  The set's event is recorded behind the meter launch.  Allocated by the first enabling call; state,
+  // staging and row tables count as stream state.
+  struct OutLevel {
+    std::vector<conan_level_cfg> cfg;
+    int n_on = 0;
+    char* state = nullptr; long long stride = 0;
+    float* stage[kActSets] = {};
+    StageSets<cnk::OlRow, kActSets> sets;
+    cnk::LvFilter filter;
+    bool on(int slot) const { return n_on > 0 && cfg[slot].enabled; }
+  } out_lv;
+  void out_level_init(const cnk::LvFilter& f);
   void out_stage_init();
   void out_ring_init();        // the output resampler's history ring (conan_streams_set_output_rate with a real rate)
   // --- slot snapshots (snapshot.hip).  rings: every ring of mk_ring in creation order with its position counter (0 pos_emf,
@@ -335,6 +354,9 @@ struct conan_streams {
     // table, of its level staging and of its dry staging; hifigan_step launches bypass_mix_kernel behind the gate
     const cnk::BypRow* byp_tab = nullptr; const int* byp_wet_lvl = nullptr; const int* byp_dry_lvl = nullptr; const float* byp_dry = nullptr;
     int byp_lvl_ld = 0; long long byp_dry_ld = 0;
+    // the step's output levelling (level_out.hip; out_plan's, for a step with a levelled row): one table row per step row;
+    // hifigan_step launches level_out_apply_kernel behind conv_post and level_out_meter_kernel behind the step's last launch
+    std::vector<cnk::OlRow> lvl_rows;
   };
   OutPlan out_plan(const int32_t* slots, int n, int frames, float* wav_out_dev, long long natural_ld, const std::vector<int>* dst, const std::string& who) const;
   // the plan's resample_out_kernel launch behind or_sets.begin() = q, then the set's event; src_ld: stride of the staged rows (a flush: 0)
@@ -662,6 +684,18 @@ void get_bypass(const conan_streams* s, int slot, conan_bypass_cfg* out);
 void state(conan_streams* s, const int32_t* slots, int n, conan_bypass_state* state_dev, void* stream);
 void last_call(conan_streams* s, int32_t* wet_lvl_dev, int32_t* dry_lvl_dev, void* stream);
 }  // namespace byp
+
+// ---- output leveller (level_out.hip): the kernels' host side and the bodies of api.hip's entry points
+namespace olv {
+// the table rows of a vocoder step that gives each of `slots` `frames` frames (empty: no levelled slot among them);
+// CONAN_ERR_UNSUPPORTED for a levelled row the split form does not cover.  Nothing changes.
+std::vector<cnk::OlRow> step_rows(const conan_streams* s, const int32_t* slots, int n, int frames, const std::string& who);
+void set_level(conan_streams* s, const int32_t* slots, int n, const conan_level_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream);
+void get_level(const conan_streams* s, int slot, conan_level_cfg* out);
+void stats(conan_streams* s, const int32_t* slots, int n, double* stats_dev, void* stream);
+int64_t state_bytes(const conan_streams* s);
+void state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream);
+}  // namespace olv
 
 // ---- silence trimming (trim.hip): the kernels' host side and the body of api.hip's entry point
 namespace trim {

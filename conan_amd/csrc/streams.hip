@@ -492,6 +492,9 @@ void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float*
     out_stage_init();
     oq = wav_out.or_sets.begin(op->rows.data(), n, st);
   }
+  // a step with a levelled row (level_out.hip): its row table travels ahead of the step's kernels too
+  const bool levelled = op && !op->lvl_rows.empty();
+  const int lq = levelled ? out_lv.sets.begin(op->lvl_rows.data(), n, st) : -1;
   {  // mel chunk -> ring (conv_pre needs 6 frames of left context)
     cnk::CopyArgs ca; memset(&ca, 0, sizeof(ca));
     ca.x = ch::lin_ref(const_cast<float*>(mel_dev), frames, c.num_mels); ca.y = v_mel.ref();
@@ -620,6 +623,12 @@ void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float*
     // the step's last kernel also advances the per-slot frame counters (one launch less)
     a.adv_pos = pos_voc; a.adv_delta = frames; a.adv_ticket = cp_ticket[ws_index(st)];
     cnk::launch_conv_post(a, st);
+    if (levelled) {      // the output leveller's ramp (level_out.hip), in place on the rows just written, in front of gate, mix and resampler
+      cnk::LevelOutApplyArgs l; memset(&l, 0, sizeof(l));
+      l.x = a.wav; l.ld = T; l.stage = out_lv.stage[lq]; l.stage_ld = out_lv.filter.U; l.state = out_lv.state; l.state_stride = out_lv.stride;
+      l.tab = out_lv.sets.rows[lq]; l.n = n; l.samples = T; l.U = out_lv.filter.U;
+      profiled("level_out_apply_kernel", 0.0, st, [&] { cnk::launch_level_out_apply(l, st); });
+    }
     if (op && op->gate_tab) {      // the output gate of a wav-in step (activity.hip), in place on the rows just written: [n][T], staged or the caller's
       cnk::ActGateArgs g; memset(&g, 0, sizeof(g));
       g.x = a.wav; g.y = a.wav; g.lvl = op->gate_lvl; g.tab = op->gate_tab; g.ld = T; g.ld_y = T; g.lvl_ld = op->gate_lvl_ld; g.samples = T;
@@ -633,6 +642,13 @@ void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float*
       profiled("bypass_mix_kernel", 0.0, st, [&] { cnk::launch_bypass_mix(b, st); });
     }
     if (out_rows) resample_out(*op, oq, T, st);
+    if (levelled) {      // ... and its meter, off the audio's path: the staged samples into the slots' state, for the next step's ramp
+      cnk::LevelOutMeterArgs l; memset(&l, 0, sizeof(l));
+      l.stage = out_lv.stage[lq]; l.stage_ld = out_lv.filter.U; l.state = out_lv.state; l.state_stride = out_lv.stride;
+      l.zcap = CONAN_LEVEL_MAX_BLOCKS + cnk::kLvRingPad; l.tab = out_lv.sets.rows[lq]; l.n = n; l.f = out_lv.filter;
+      profiled("level_out_meter_kernel", 0.0, st, [&] { cnk::launch_level_out_meter(l, st); });
+      out_lv.sets.end(lq, st);
+    }
     // the launches are enqueued: the slots' host counters, and the counts conan_streams_output_samples reports
     if (!op || op->dst.empty()) wav_out.out_counts.assign(n, T);
     for (int i = 0; i < n; ++i) {

@@ -253,13 +253,18 @@ class StreamingVoiceConversionEngine:
             raise ValueError("set_voice: bank= and ids= are required")
         self.st.set_voice(self.slots if slots is None else slots, bank, ids)
 
-    def start(self, ref_mel, ref_len=None, which=7, out_rate=None, out_filter=None, out_format=None, pitch=None, voice=None):
+    def start(self, ref_mel, ref_len=None, which=7, out_rate=None, out_filter=None, out_format=None, pitch=None, voice=None, out_level=None):
         """voice: (bank, ids) - enrolled voices of a runtime.VoiceBank, one id per slot, in place of ref_mel (then None).
         pitch: the slots' pitch control in the decoder step (Streams.set_pitch) - None / False: none; a dict of its keywords
         (shift_semitones, range, pivot, uv_threshold), or a list with one per slot.
         out_rate: the sample rate the audio leaves at (None: the model rate), resampled on the GPU behind the vocoder; out_filter:
         dict of Context.resample's filter keywords.  The steps then deliver what the filter has the inputs for, finish() the tail.
-        out_format: the sample format the audio leaves in ('f32' | 's16' | 'ulaw' | 'alaw'; None: float32), encoded on the GPU."""
+        out_format: the sample format the audio leaves in ('f32' | 's16' | 'ulaw' | 'alaw'; None: float32), encoded on the GPU.
+        out_level: the output leveller (Streams.set_output_level) - None / False: none; True: Context.level's defaults; a dict: its
+        keywords.  The same causal BS.1770 leveller as start_wav(level=...), on the converted voice: on the GPU between the vocoder
+        and the gate, the mix, the output resampler and the encoders, without look-ahead or added latency."""
+        if isinstance(out_level, (list, tuple)):
+            raise ValueError("out_level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
         if isinstance(out_rate, (list, tuple)) or isinstance(out_format, (list, tuple)):
             raise ValueError("out_rate / out_format: one value for all slots here (feed / infer return one [B, count] block); open_slots and "
                              "infer_wav_staggered take one per slot / utterance")
@@ -269,13 +274,14 @@ class StreamingVoiceConversionEngine:
         self._set_out_rate(self.slots, out_rate, out_filter)
         self._set_format(self.slots, out_format, self.st.output_formats, self.st.set_output_format)
         self._set_pitch(self.slots, pitch)
+        self._set_out_level(self.slots, out_level)
 
     def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, **filter):
+                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
         in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
         in_format: the input's sample format (None: float32; 's16' takes int16 rows, 'ulaw' / 'alaw' uint8), decoded on the GPU.
-        out_rate / out_filter / out_format: as in start().
+        out_rate / out_filter / out_format / out_level: as in start().
         level: the input leveller (Streams.set_input_level) - None / False: none; True: Context.level's defaults; a dict: its
         keywords.  It runs on the GPU on the decoded, resampled samples in front of the front-end, causally: feed() gains no latency.
         pitch, voice: as in start().
@@ -298,7 +304,8 @@ class StreamingVoiceConversionEngine:
         bypasses = self._bypasses(self.slots, bypass)
         if isinstance(in_format, (list, tuple)) or isinstance(level, (list, tuple)):
             raise ValueError("in_format / level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
-        self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice)
+        self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice,
+                   out_level=out_level)
         self._set_rate(self.slots, in_rate, filter)
         self._set_format(self.slots, in_format, self.st.input_formats, self.st.set_input_format)
         self._set_level(self.slots, level)
@@ -467,6 +474,26 @@ class StreamingVoiceConversionEngine:
             else:
                 self.st.set_input_level([slot], True if lv is True else dict(lv))
 
+    def _set_out_level(self, slots, out_level):
+        """The slots' output leveller (None / False: none; True: the defaults; a dict of Streams.set_output_level's keywords), one value
+        or one per slot, behind the slots' reset (the vocoder streams are at position 0).  Slots that never had one are left alone."""
+        levels = list(out_level) if isinstance(out_level, (list, tuple)) else [out_level] * len(slots)
+        if len(levels) != len(slots):
+            raise ValueError(f"out_level: {len(levels)} values for {len(slots)} slots")
+        for slot, lv in zip(slots, levels):
+            if lv is None or lv is False:
+                if int(slot) in self.st.output_levels:
+                    self.st.set_output_level([slot], None)
+            elif lv is True or isinstance(lv, dict):
+                self.st.set_output_level([slot], True if lv is True else dict(lv))
+            else:
+                raise ValueError(f"out_level: {lv!r} (True, a dict of set_output_level's keywords or None)")
+
+    def set_output_level(self, slots=None, cfg=True, seed=None, **kw):
+        """The slots' output leveller (all slots by default) between utterances, or mid-utterance with seed= (a hand-over):
+        Streams.set_output_level's arguments (cfg=None turns it off).  Joins pipelined steps in flight."""
+        self.st.set_output_level(self.slots if slots is None else slots, cfg, seed=seed, **kw)
+
     def _set_pitch(self, slots, pitch):
         """The slots' pitch control (None / False: none; True: the defaults; a dict of Streams.set_pitch's keywords), one value or one
         per slot.  Slots that never had one are left alone."""
@@ -606,7 +633,7 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
                   out_format=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None, register=None, activity=None,
-                  activity_log=None, bypass=None, **filter):
+                  activity_log=None, bypass=None, out_level=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] (or None with voice = (bank, ids): start) -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
@@ -628,7 +655,8 @@ class StreamingVoiceConversionEngine:
         returned wav is ctx.activity_gate of the ungated one, bit for bit.  activity_log: a list that receives (act [B, emit],
         level [B, emit]) per emitted chunk (chunk_activity after each call, which joins pipelined work).
         bypass: the wet/dry mix (start_wav): the returned wav is ctx.bypass_mix of the unmixed one and of the samples the front-end
-        reads, bit for bit."""
+        reads, bit for bit.  out_level: the output leveller (start): the returned model-rate wav is ctx.level of the unlevelled
+        one, bit for bit, and gate, mix, output rate and format apply to the levelled audio."""
         self._check_voice(ref_mel, voice)
         self._registers(self.slots, register, voice)      # (host checks before anything runs)
         self._activities(self.slots, activity)
@@ -639,7 +667,7 @@ class StreamingVoiceConversionEngine:
         if loud_norm:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
-                       pitch=pitch, voice=voice, follow=follow, register=register, activity=activity, bypass=bypass, **filter)
+                       pitch=pitch, voice=voice, follow=follow, register=register, activity=activity, bypass=bypass, out_level=out_level, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -669,7 +697,7 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, **filter):
+                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
         rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
@@ -679,7 +707,8 @@ class StreamingVoiceConversionEngine:
         place of ref_mel (then None): one launch instead of a style pass per slot.  follow: the slots' source-pitch following
         (start_wav), one value or a list with one per slot.  register: the slots' register matching (start_wav), one value or a list
         with one per slot.  activity: the slots' activity detector (start_wav), one value or a list with one per slot.  bypass: the
-        slots' wet/dry mix (start_wav), one value or a list with one per slot.
+        slots' wet/dry mix (start_wav), one value or a list with one per slot.  out_level: the slots' output leveller (start), one
+        value or a list with one per slot.
         No trim=, as in start_wav: the slots stream, and a stream cannot drop time (infer_wav_staggered(trim=True) trims utterances
         it holds whole)."""
         self._check_voice(ref_mel, voice)
@@ -699,6 +728,7 @@ class StreamingVoiceConversionEngine:
         self._set_register(slots, registers)
         self._set_activity(slots, activities)
         self._set_bypass(slots, bypasses)
+        self._set_out_level(slots, out_level)
 
     @torch.no_grad()
     def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None):
@@ -718,7 +748,7 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
                             in_formats=None, out_formats=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None,
-                            register=None, activity=None, activity_log=None, bypass=None, **filter):
+                            register=None, activity=None, activity_log=None, bypass=None, out_level=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -738,9 +768,13 @@ class StreamingVoiceConversionEngine:
         with one per utterance.  activity: the activity detector (start_wav), one value for every utterance or a list with one per
         utterance.  activity_log: a list that receives, per utterance, a list of (act [emit], level [emit]) per emitted chunk
         (chunk_activity after each call, which joins pipelined work).  bypass: the wet/dry mix (start_wav), one value for every
-        utterance or a list with one per utterance."""
+        utterance or a list with one per utterance.  out_level: the output leveller (start), one value for every utterance or a
+        list with one per utterance."""
         voice = self._check_voice(ref_mel, voice)
         U = len(src_wavs)
+        out_levels = list(out_level) if isinstance(out_level, (list, tuple)) else [out_level] * U
+        if len(out_levels) != U:
+            raise ValueError(f"out_level: {len(out_levels)} values for {U} utterances")
         registers = self._registers(range(U), register, voice)      # (host checks before anything runs; per utterance, as dicts)
         activities = self._activities(range(U), activity)
         bypasses = self._bypasses(range(U), bypass)
@@ -776,7 +810,7 @@ class StreamingVoiceConversionEngine:
                                 out_rate=[orates[u] for u in new], out_filter=out_filter, in_format=[ifmts[u] for u in new],
                                 out_format=[ofmts[u] for u in new], level=[levels[u] for u in new], pitch=[pitches[u] for u in new],
                                 follow=[follows[u] for u in new], register=[registers[u] for u in new], activity=[activities[u] for u in new],
-                                bypass=[bypasses[u] for u in new],
+                                bypass=[bypasses[u] for u in new], out_level=[out_levels[u] for u in new],
                                 **filter)
             if not live:
                 tick += 1
@@ -857,21 +891,26 @@ class StreamingVoiceConversionEngine:
         return out + (mel[:, -seg:],) if return_mel else out
 
     @torch.no_grad()
-    def infer(self, src_mel, ref_mel, ref_len=None, pipelined=True, out_rate=None, out_filter=None, out_format=None, pitch=None, voice=None):
+    def infer(self, src_mel, ref_mel, ref_len=None, pipelined=True, out_rate=None, out_filter=None, out_format=None, pitch=None, voice=None,
+              out_level=None):
         """src_mel [B,T,80], ref_mel [B,Tr,80] (cuda) -> wav [B, T*hop], mel [B,T,80], codes [B,T].
 
         The whole source is available here, so by default the chunks are issued as pipelined steps
         (conan_step_async): the Emformer + decoder of chunk t+1 overlap the vocoder of chunk t.  The
         results are bit-identical to the blocking loop (pipelined=False).  out_rate (+ out_filter): the returned wav is the
         whole utterance at that rate, ctx.resample of the model-rate wav bit for bit.  out_format: the returned wav's sample format.
-        pitch: the slots' pitch control in the decoder step (start).  voice: (bank, ids) in place of ref_mel (then None; start)."""
+        pitch: the slots' pitch control in the decoder step (start).  voice: (bank, ids) in place of ref_mel (then None; start).
+        out_level: the output leveller (start): the returned model-rate wav is ctx.level of the unlevelled one, bit for bit."""
         self._check_voice(ref_mel, voice)
         if self.ctx.cfg.voc_upsample == 2:
+            if out_level not in (None, False):
+                raise ValueError("out_level with an upsample 'nn' vocoder: its steps are whole prefixes, not update intervals; level the returned wav "
+                                 "with Context.level instead")
             if out_format not in (None, "f32"):
                 raise ValueError("out_format with an upsample 'nn' vocoder: convert the returned wav with Context.convert_samples instead")
             self._set_out_rate(self.slots, out_rate, out_filter)      # (refuses a rate; restores the model rate)
             return self._infer_prefix_vocoder(src_mel, ref_mel, ref_len, pitch, voice)
-        self.start(ref_mel, ref_len, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice)
+        self.start(ref_mel, ref_len, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice, out_level=out_level)
         B = src_mel.shape[0]
         hop, nm = self.ctx.hop, self.ctx.cfg.num_mels
         wavs, mels, codes = [], [], []

@@ -691,6 +691,7 @@ class Streams:
         self.input_formats = {}          # slot -> 's16' | 'ulaw' | 'alaw', for the slots whose wav-in rows are not float32
         self.output_formats = {}         # slot -> the same, for the slots whose audio leaves in another format
         self.input_levels = {}           # slot -> dict of set_input_level's keywords, for the slots with an input leveller
+        self.output_levels = {}          # slot -> dict of set_output_level's keywords, for the slots with an output leveller
         self.pitch_cfgs = {}             # slot -> dict of set_pitch's keywords, for the slots with a pitch control
         self._last_wav_n = 0             # rows of the most recent wav-in call (step_wav_contour)
 
@@ -1053,6 +1054,51 @@ class Streams:
         a, p = _i32(slots)
         out = torch.empty(len(a), 4, dtype=torch.float64, device=self.dev)
         _lib.check(self.lib.conan_streams_input_level(self.h, p, len(a), _ptr(out), _stream()))
+        self._release()
+        return out
+
+    def set_output_level(self, slots, cfg=True, seed=None, **kw):
+        """conan_streams_set_output_level: the same causal BS.1770 leveller on the slots' own vocoder audio, between conv_post and the
+        activity gate, the wet/dry mix, the output resampler and the encoders.  set_input_level's keyword rules: Context.level's
+        keywords as keywords or as a dict in cfg, the rest at their defaults; only cfg=None turns it off.  Without a seed the slots
+        must be at the start of their vocoder streams; seed: uint8 [n, bytes] (cuda) rows of output_level_state from a stream at the
+        same position (a hand-over).  The setting survives resets, which restart the meter.  output_levels[slot] holds every keyword
+        of a levelled slot."""
+        a, p = _i32(slots)
+        if cfg is None:
+            if kw:
+                raise ValueError("set_output_level: cfg=None turns the leveller off and takes no keywords")
+            c = _lib.LevelCfg()      # (enabled = 0)
+        else:
+            c = _lib.level_cfg(**dict({} if cfg is True else cfg, **kw))
+        sp, ld = None, 0
+        if seed is not None:
+            if seed.dtype != torch.uint8 or seed.dim() != 2 or seed.shape[0] != len(a) or not seed.is_cuda or seed.stride(1) != 1:
+                raise ValueError("set_output_level: seed must be a cuda uint8 [n, bytes] tensor, as output_level_state returns it")
+            sp, ld = _ptr(seed), int(seed.stride(0))
+        _lib.check(self.lib.conan_streams_set_output_level(self.h, p, len(a), C.byref(c), sp, ld, _stream()))
+        for slot in a:
+            if c.enabled:
+                self.output_levels[int(slot)] = _lib.level_keywords(c)
+            else:
+                self.output_levels.pop(int(slot), None)
+
+    def output_level(self, slots):
+        """conan_streams_output_level: float64 [n, 4] (cuda) rows (L_k, G_k, P_k, J_k) of the instant the slots' latest ramps end at.
+        Joins pipelined work."""
+        a, p = _i32(slots)
+        out = torch.empty(len(a), 4, dtype=torch.float64, device=self.dev)
+        _lib.check(self.lib.conan_streams_output_level(self.h, p, len(a), _ptr(out), _stream()))
+        self._release()
+        return out
+
+    def output_level_state(self, slots):
+        """conan_streams_output_level_state: uint8 [n, bytes] (cuda), the slots' leveller states for set_output_level(seed=).  Joins
+        pipelined work."""
+        a, p = _i32(slots)
+        nbytes = int(_lib.check(self.lib.conan_streams_output_level_state_bytes(self.h)))
+        out = torch.empty(len(a), nbytes, dtype=torch.uint8, device=self.dev)
+        _lib.check(self.lib.conan_streams_output_level_state(self.h, p, len(a), _ptr(out), nbytes, _stream()))
         self._release()
         return out
 

@@ -1056,6 +1056,52 @@ int conan_bypass_mix(conan_ctx* ctx, int hop, const float* wet_dev, int64_t wet_
                      const int32_t* wet_lvl_dev, const int32_t* dry_lvl_dev, int64_t lvl_ld, int32_t start_wet, int32_t start_dry, float* out_dev,
                      int64_t out_ld, void* stream);
 
+/* Live output levelling (added within ABI 9: a caller detects it by the symbol conan_streams_set_output_level; no existing struct or
+ * call changes).  conan_level_cfg's law, exactly as stated above, on the slot's own vocoder audio, with three substitutions: x_t is
+ * the slot's model-rate vocoder sample t as conv_post wrote it, position 0 being the slot's first sample after a reset that
+ * includes CONAN_MODEL_HIFIGAN (the position conan_slot_info and snapshots already carry); U = segment * hop and u_k = k * U in that
+ * position; y replaces x in place, in front of the activity gate, the wet/dry mix, the output resampler and the encoders - the gate
+ * mutes levelled audio, the mix sees a levelled wet beside the already levelled dry, conan_streams_flush_output and the resampler's
+ * ring see levelled audio; pre_tanh_dev and the taps are not touched.  What follows, bit for bit: a levelled slot's audio over an
+ * utterance is conan_level with the same cfg applied to the audio of the same run without the leveller - however the utterance was
+ * cut into calls, blocking or pipelined, whatever the other rows of a call were.
+ * Rows.  A levelled row of a vocoder step must start at a multiple of U and carry at most U samples: every chunk of
+ * conan_step[_async] and of the wav-in steps does, a short last chunk included.  Any other row - a conan_hifigan_step* with
+ * frames * hop > U or at a position that is not a multiple of U, the whole-prefix vocoder of upsample 'nn' - is
+ * CONAN_ERR_UNSUPPORTED before anything changes; unlevelled rows of the same call are unaffected.  U and fs carry the limits stated
+ * above.  Mel-in steps level too: the feature belongs to the vocoder's output, like the output rate.
+ * Launches.  G_k and P_k depend only on samples before u_k, so the work is split: ONE launch (cnk::level_out_apply_kernel: two gains
+ * from the slot's state, the ramp, the clip) behind conv_post and ONE (cnk::level_out_meter_kernel: the meter over the step's
+ * unlevelled samples, which the apply staged, and the next instant's gain) behind the step's last launch, per vocoder step in which
+ * a levelled row takes part - each emit group of a ragged call is such a step - and none otherwise.
+ * Setter.  cfg->enabled = 0 removes the leveller.  Every argument is checked before anything changes (the cfg by
+ * conan_streams_set_input_level's rules), and pending pipelined work is joined.  With seed_dev == NULL every slot must be at vocoder
+ * position 0, else CONAN_ERR_STATE.  With a seed the slot may be anywhere: row i of the seed, at i * seed_ld bytes (8-byte aligned,
+ * seed_ld a multiple of 8 and at least conan_streams_output_level_state_bytes), is copied into the slot's state on `stream`; the
+ * caller vouches that it was queried from a stream at the same position.  The kernels derive every ring index and tail count from
+ * the host's position, never from the blob: a wrong blob gives meaningless gains and no access outside the slot's state.  The
+ * setting persists across resets; a reset with CONAN_MODEL_HIFIGAN restarts the meter and the gain (the position returns to 0, which
+ * the slot's next rows carry: no launch).  Hand-over: state query, conan_streams_export_slots, import, then this call with the seed.
+ * Snapshots carry neither setting nor state: conan_streams_layout_id, conan_streams_snapshot_bytes and conan_slot_info do not change.
+ * Memory.  The first enabling call allocates, per slot of the stream-set, the state - conan_streams_output_level_state_bytes = 66496
+ * bytes: the input leveller's 66464 (meter state and two rings of CONAN_LEVEL_MAX_BLOCKS + 16 doubles) and the previous instant's
+ * four stats - and eight staging sets of U floats and one 160-byte table row each: max_slots * (66496 + 8 * (4 * U + 160)) bytes,
+ * which conan_streams_state_bytes counts from then on.  A stream-set that never calls the setter allocates nothing and runs exactly
+ * the launches it ran before. */
+int conan_streams_set_output_level(conan_streams* s, const int32_t* slots, int n, const conan_level_cfg* cfg, const void* seed_dev, int64_t seed_ld,
+                                   void* stream);
+/* Host only: the output level cfg of `slot` as set (zeros for a slot without one). */
+int conan_streams_output_level_cfg(const conan_streams* s, int slot, conan_level_cfg* cfg_out);
+/* Joins pending pipelined work, then writes per slot {L_k, G_k, P_k, J_k} (stats_dev[n][4], device) on `stream` for
+ * k = (voc_samples - 1) / U, voc_samples = the slot's vocoder position; before any sample {-inf, G_{-1}, 0, 0}: row k of conan_level's
+ * trace on the audio so far.  A slot without the leveller is CONAN_ERR_STATE. */
+int conan_streams_output_level(conan_streams* s, const int32_t* slots, int n, double* stats_dev, void* stream);
+/* Bytes of one slot's output level state (negative: an error code). */
+int64_t conan_streams_output_level_state_bytes(const conan_streams* s);
+/* The states of `slots` -> row i at state_dev + i * ld bytes (8-byte aligned, ld a multiple of 8 and at least the state's bytes), on
+ * `stream` behind a join of pipelined work.  A slot without the leveller is CONAN_ERR_STATE. */
+int conan_streams_output_level_state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream);
+
 /* Silence trimming (added within ABI 9: a caller detects it by the exported symbol; no existing struct or call changes).  The offline
  * half of source activity: the reference's trim_long_sil (utils/audio/vad.py, trim_long_silences) cuts the long pauses out of a whole
  * recording - a moving average over an external detector's flags, a dilation that keeps short pauses, a hard cut - and this call does
