@@ -165,6 +165,12 @@ _PROTOS = {
     "conan_streams_output_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "conan_streams_output_level_state_bytes": (C.c_int64, [C.c_void_p]),
     "conan_streams_output_level_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "conan_streams_set_conceal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "conan_streams_conceal_cfg": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "conan_streams_conceal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "conan_conceal_state_bytes": (C.c_int64, []),
+    "conan_streams_conceal_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "conan_conceal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_trim_silence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "conan_voices_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
@@ -522,6 +528,39 @@ def bypass_keywords(c):
     k / 2^20, which rint(share * 2^20) maps back to k): the form Streams.bypass reports a setting in."""
     return dict(wet=c.wet_target / ACTIVITY_FULL, dry=c.dry_target / ACTIVITY_FULL, step=int(c.step), fill_gate=bool(c.fill_gate),
                 start=(int(c.seed_wet), int(c.seed_dry)))
+
+
+CONCEAL_MAX_LAG, CONCEAL_MAX_WINDOW = 1024, 1024
+
+
+class ConcealCfg(C.Structure):
+    """conan_conceal_cfg (include/conan_hip.h)."""
+    _fields_ = [("enabled", C.c_int32), ("packet", C.c_int32), ("lag_min", C.c_int32), ("lag_max", C.c_int32), ("window", C.c_int32),
+                ("hold", C.c_int32), ("fall", C.c_int32), ("fade", C.c_int32)]
+
+
+def conceal_keywords(rate):
+    """The documented defaults of the loss concealment for an input rate, or - given an enabled ConcealCfg - its fields: the keywords
+    conceal_cfg takes.  20 ms packets, lags of 2.5 .. 15 ms, a 20 ms comparison window, 10 ms at full level, a 50 ms fall, a 5 ms
+    cross-fade; at 48 kHz every one lies within the library's limits.  They are choices, not measurements."""
+    if isinstance(rate, ConcealCfg):
+        return {f: int(getattr(rate, f)) for f, _ in ConcealCfg._fields_[1:]}
+    r = int(rate)
+    return dict(packet=r // 50, lag_min=r // 400, lag_max=r * 15 // 1000, window=r // 50, hold=r // 100, fall=r // 20, fade=r // 200)
+
+
+def conceal_cfg(rate=None, **kw):
+    """An enabled conan_conceal_cfg: conceal_keywords(rate) with the given fields replaced (rate=None: every field must be given)."""
+    base = conceal_keywords(rate) if rate is not None else {}
+    f = dict(base, **kw)
+    names = [n for n, _ in ConcealCfg._fields_[1:]]
+    unknown = sorted(set(f) - set(names))
+    if unknown:
+        raise ValueError(f"conceal: unknown fields {unknown}")
+    missing = [n for n in names if n not in f]
+    if missing:
+        raise ValueError(f"conceal: without a rate the fields {missing} must be given")
+    return ConcealCfg(1, *[int(f[n]) for n in names])
 
 
 class DecoderTaps(C.Structure):

@@ -352,6 +352,8 @@ int conan_streams_reset(conan_streams* s, const int32_t* slots, int n, int which
       for (int i = 0; i < n && !s->act.pending.empty(); ++i) s->act.pending[slots[i]] = 1;
       // ... and the bypass setting, whose levels restart from their seeds in the slot's next stage row
       for (int i = 0; i < n && !s->byp.pending.empty(); ++i) s->byp.pending[slots[i]] = 1;
+      // ... and the concealment setting, whose state restarts from zeros in the slot's next repair row
+      for (int i = 0; i < n && !s->conc.pending.empty(); ++i) s->conc.pending[slots[i]] = 1;
     }
   });
 }
@@ -735,6 +737,28 @@ int64_t conan_streams_output_level_state_bytes(const conan_streams* s) {
 
 int conan_streams_output_level_state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream) {
   return guarded([&] { olv::state(s, slots, n, state_dev, ld, stream); });
+}
+
+int conan_streams_set_conceal(conan_streams* s, const int32_t* slots, int n, const conan_conceal_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream) {
+  return guarded([&] { conc::set_conceal(s, slots, n, cfg, seed_dev, seed_ld, stream); });
+}
+
+int conan_streams_conceal_cfg(const conan_streams* s, int slot, conan_conceal_cfg* cfg_out) { return guarded([&] { conc::get_conceal(s, slot, cfg_out); }); }
+
+int conan_streams_conceal(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, void* wav_dev, int64_t wav_ld, const int32_t* lost_dev,
+                          int64_t lost_ld, void* stream) {
+  return guarded([&] { conc::repair(s, slots, n, samples, wav_dev, wav_ld, lost_dev, lost_ld, stream); });
+}
+
+int64_t conan_conceal_state_bytes(void) { return (int64_t)cnk::kConcStateBytes; }
+
+int conan_streams_conceal_state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream) {
+  return guarded([&] { conc::state(s, slots, n, state_dev, ld, stream); });
+}
+
+int conan_conceal(conan_ctx* ctx, const conan_conceal_cfg* cfg, int format, void* x_dev, int64_t ld, int n, const int64_t* samples, const int32_t* lost_dev,
+                  int64_t lost_ld, void* stream) {
+  return guarded([&] { conc::whole(ctx, cfg, format, x_dev, ld, n, samples, lost_dev, lost_ld, stream); });
 }
 
 int conan_streams_set_input_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg) {

@@ -559,6 +559,32 @@ struct BypMixArgs {
 constexpr int kBypMixThreads = 256;
 void launch_bypass_mix(const BypMixArgs& a, hipStream_t st);
 
+// Input loss concealment (conceal.hip; include/conan_hip.h, conan_conceal_cfg).  conceal_kernel: one workgroup per table row, which
+// repairs `samples` samples of row `row` of the caller's buffer (wav + row * wav_ld dwords, in format fmt) in place from the flags
+// lost[row * lost_ld + m], packet m = samples [m * packet, (m + 1) * packet) of the row.  The state - header, template, the last
+// kConcHist values of the decoded repaired signal - is read from state[slot] (restart = 0 and slot >= 0) or starts as zeros, and is
+// written back to state[slot] (slot >= 0).  A row is walked in tiles of kConcTile samples, so a whole signal (slot = -1,
+// restart = 1) and a chunk take the same path.
+constexpr int kConcMaxLag = 1024, kConcMaxWindow = 1024;      // CONAN_CONCEAL_MAX_LAG / _MAX_WINDOW
+constexpr int kConcHist = kConcMaxLag + kConcMaxWindow;       // history values kept: the lag search reads the last window + lag_max of them
+constexpr int kConcTile = 4096, kConcThreads = 1024;
+struct ConcHead { int mode, p, j, reserved0; long long k, reserved1; };      // the first 32 bytes of a state record
+static_assert(sizeof(ConcHead) == 32, "the header's record");
+constexpr long long kConcStateBytes = (long long)sizeof(ConcHead) + (kConcMaxLag + kConcHist) * (long long)sizeof(float);
+struct ConcRow {
+  long long samples;
+  int row, slot, restart, fmt;
+  int packet, lag_min, lag_max, window, hold, fall, fade, pad_;
+};
+static_assert(sizeof(ConcRow) == 56, "uploaded as 14 ints");
+struct ConcArgs {
+  void* wav; long long wav_ld;            // the caller's rows, stride in dwords
+  const int* lost; long long lost_ld;     // the caller's flags, stride in ints
+  char* state;                            // [max_slots][kConcStateBytes]; may be null when no row names a slot
+  const ConcRow* tab; int rows;
+};
+void launch_conceal(const ConcArgs& a, hipStream_t st);
+
 // Silence trimming (trim.hip; include/conan_hip.h, conan_trim_cfg).  Row i has lens[i] samples at wav + i * ld and F = 1 + lens[i] / hop
 // frames; its flags are act[i * act_ld + f] (any non-zero counts as 1).  The plan kernel (one workgroup per row) writes the row's two
 // prefix arrays pa / pb [i * pre_ld + 0 .. F] (scratch: the prefixes of act and of m1), the kept-frame mask m2 to mask[i * mask_ld + f]

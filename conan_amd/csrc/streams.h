@@ -279,6 +279,21 @@ struct conan_streams {
     bool on(int slot) const { return n_on > 0 && cfg[slot].enabled; }
   } byp;
   void bypass_init();
+  // input loss concealment (conan_streams_set_conceal; conceal.hip): per slot its cfg as set (enabled = 0: none), which persists across
+  // resets; n_on: slots with one; pending: the slot's state restarts from zeros in its next repair row (set when a slot that was off
+  // is enabled and by a reset with CONAN_MODEL_FRONTEND; a host flag, no launch).  state: [max_slots] records of cnk::kConcStateBytes
+  // on the device, read and written by the rows of conceal_kernel in the order of the caller's stream.  Per repair call a row table
+  // (set q of `sets`; the set's event follows the kernel's launch).  No step path reads any of it: the repair works on the caller's
+  // rows in front of the step call.  Allocated by the first enabling call; state and row tables count as stream state.
+  struct Conceal {
+    std::vector<conan_conceal_cfg> cfg;
+    std::vector<char> pending;
+    int n_on = 0;
+    char* state = nullptr;
+    StageSets<cnk::ConcRow> sets;
+    bool on(int slot) const { return n_on > 0 && cfg[slot].enabled; }
+  } conc;
+  void conceal_init();
   void ragged_init();
   void resample_init();        // staging, row tables and the history ring (conan_streams_set_input_rate)
   void rs_stage_init();        // staging and row tables only (conan_streams_set_input_format: no stream state)
@@ -684,6 +699,19 @@ void get_bypass(const conan_streams* s, int slot, conan_bypass_cfg* out);
 void state(conan_streams* s, const int32_t* slots, int n, conan_bypass_state* state_dev, void* stream);
 void last_call(conan_streams* s, int32_t* wet_lvl_dev, int32_t* dry_lvl_dev, void* stream);
 }  // namespace byp
+
+// ---- input loss concealment (conceal.hip): the kernel's host side and the bodies of api.hip's entry points
+namespace conc {
+void check_cfg(const conan_conceal_cfg& c, const char* who);      // host only
+cnk::ConcRow row(const conan_conceal_cfg& c);      // the cfg's fields of a row that starts from zeros and names no slot
+void whole(conan_ctx* ctx, const conan_conceal_cfg* cfg, int format, void* x_dev, int64_t ld, int n, const int64_t* samples, const int32_t* lost_dev,
+           int64_t lost_ld, void* stream);
+void set_conceal(conan_streams* s, const int32_t* slots, int n, const conan_conceal_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream);
+void get_conceal(const conan_streams* s, int slot, conan_conceal_cfg* out);
+void repair(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, void* wav_dev, int64_t wav_ld, const int32_t* lost_dev, int64_t lost_ld,
+            void* stream);
+void state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream);
+}  // namespace conc
 
 // ---- output leveller (level_out.hip): the kernels' host side and the bodies of api.hip's entry points
 namespace olv {

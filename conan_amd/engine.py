@@ -4,11 +4,14 @@ slot range over the ranks of a torch.distributed job (one process per GPU).
 Streams are independent units (private conv/KV state, no cross-stream arithmetic),
 so the compute path has no collective.  The only exchange is the gather of finished audio to
 rank 0 (RCCL `gather` over xGMI on GPUs, gloo in the CPU tests)."""
+import functools
 import os
 
 import numpy as np
 import torch
 import torch.distributed as dist
+
+from . import _lib
 
 
 def shard_range(total, rank, world):
@@ -225,6 +228,7 @@ class StreamingVoiceConversionEngine:
         self._registered = False    # set_pitch_register has been called on the stream-set
         self._activity = False      # set_activity has been called on the stream-set
         self._bypass = False        # set_bypass has been called on the stream-set
+        self._conceal = False       # set_conceal has been called on the stream-set
 
     @staticmethod
     def _check_voice(ref_mel, voice):
@@ -277,7 +281,7 @@ class StreamingVoiceConversionEngine:
         self._set_out_level(self.slots, out_level)
 
     def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, **filter):
+                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
         in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
         in_format: the input's sample format (None: float32; 's16' takes int16 rows, 'ulaw' / 'alaw' uint8), decoded on the GPU.
@@ -295,13 +299,16 @@ class StreamingVoiceConversionEngine:
         the defaults; "detect": detect only; a dict of set_activity's keywords (gate=False: detect only).  chunk_activity() reads
         the last call's flags.  bypass: the wet/dry mix with the slot's own source audio (Streams.set_bypass) - None / False: none;
         True: enabled at full wet (a later set_bypass toggles it); a dict of set_bypass's keywords.  chunk_bypass() reads
-        the last call's levels.
+        the last call's levels.  conceal: loss concealment of the input rows (Streams.set_conceal) - None / False: none; True: the
+        defaults of the slot's input rate; a dict of conan_conceal_cfg's fields over them.  feed(lost=...) then repairs the packets
+        that never arrived, on the GPU in front of the step.
         There is no trim= here: silence trimming (infer_wav(trim=True)) moves audio forward over pauses it has seen whole, and a
         stream cannot drop time it has not heard yet; activity= is what a live call has in its place."""
         self._check_voice(ref_mel, voice)
         registers = self._registers(self.slots, register, voice)
         activities = self._activities(self.slots, activity)
         bypasses = self._bypasses(self.slots, bypass)
+        conceals = self._conceals(self.slots, conceal)
         if isinstance(in_format, (list, tuple)) or isinstance(level, (list, tuple)):
             raise ValueError("in_format / level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
         self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice,
@@ -313,6 +320,7 @@ class StreamingVoiceConversionEngine:
         self._set_register(self.slots, registers)
         self._set_activity(self.slots, activities)
         self._set_bypass(self.slots, bypasses)
+        self._set_conceal(self.slots, conceals, [in_rate] * len(self.slots))
 
     @staticmethod
     def _activities(slots, activity):
@@ -378,6 +386,61 @@ class StreamingVoiceConversionEngine:
         its levels and slews to the new targets - the toggle).  In force from the next emitted chunk."""
         self._bypass = True
         self.st.set_bypass(self.slots if slots is None else slots, cfg, **kw)
+
+    @staticmethod
+    def _conceals(slots, conceal):
+        """conceal= (one value or one per slot) -> per slot None, a dict of conan_conceal_cfg's fields (over the defaults of the slot's
+        input rate) or an _lib.ConcealCfg.  Host only."""
+        values = list(conceal) if isinstance(conceal, (list, tuple)) else [conceal] * len(slots)
+        if len(values) != len(slots):
+            raise ValueError(f"conceal: {len(values)} values for {len(slots)} slots")
+        out = []
+        for c in values:
+            if c is None or c is False:
+                out.append(None)
+            elif c is True:
+                out.append({})
+            elif isinstance(c, (dict, _lib.ConcealCfg)):
+                out.append(c)
+            else:
+                raise ValueError(f"conceal: {c!r} (True, a dict of conan_conceal_cfg's fields, an _lib.ConcealCfg or None)")
+        return out
+
+    def _set_conceal(self, slots, conceals, rates):
+        """The slots' loss concealment from _conceals' list, behind the slots' reset (which restarts the state); rates: the slots'
+        input rates (None: the model rate).  A stream-set that never used it is left alone."""
+        if all(c is None for c in conceals) and not self._conceal:
+            return
+        self._conceal = True
+        for slot, c, rate in zip(slots, conceals, rates):
+            self.st.set_conceal([slot], cfg=c if c is None or isinstance(c, _lib.ConcealCfg) else (c or True), rate=rate)
+
+    def set_conceal(self, slots=None, cfg=True, **kw):
+        """A live change of the slots' loss concealment (all slots by default) between feed / feed_ragged calls, also mid-utterance:
+        Streams.set_conceal's arguments (cfg=None turns it off; an enabled slot keeps its state)."""
+        self._conceal = True
+        self.st.set_conceal(self.slots if slots is None else slots, cfg, **kw)
+
+    def _lost_rows(self, slots, lost, pos, counts):
+        """The flags of one call's rows cut from whole-utterance flags: row i takes lost[i] from sample position pos[i] on, counts[i]
+        samples -> int32 [n, packets] (zeros for a row without flags or without the feature), or None when no row has any."""
+        cfgs = self.st.conceal_cfg(slots)
+        rows = []
+        for c, fl, p, m in zip(cfgs, lost, pos, counts):
+            if fl is None or c is None or m == 0:
+                rows.append(None)
+                continue
+            if p % c["packet"]:
+                raise ValueError(f"lost: a call begins at sample {p}, off the packets of {c['packet']} samples: the calls' rows must be whole packets long")
+            rows.append(fl[p // c["packet"]:(p + m + c["packet"] - 1) // c["packet"]].to(torch.int32))
+        if all(r is None for r in rows):
+            return None
+        width = max(r.shape[0] for r in rows if r is not None)
+        out = torch.zeros(len(rows), width, dtype=torch.int32, device=self.st.dev)
+        for i, r in enumerate(rows):
+            if r is not None:
+                out[i, :r.shape[0]] = r
+        return out
 
     def chunk_bypass(self):
         """The frame-end wet and effective dry levels of the last feed / feed_ragged call (Streams.step_wav_bypass; joins pipelined
@@ -574,7 +637,7 @@ class StreamingVoiceConversionEngine:
         return L if in_rate is None else L * int(in_rate) // self.st.model_rate
 
     @torch.no_grad()
-    def feed(self, wav_chunk, final=False, pipelined=False, mel=None):
+    def feed(self, wav_chunk, final=False, pipelined=False, mel=None, lost=None):
         """Streaming waveform input (conan_step_wav): wav_chunk [B, seg*hop] (cuda; 0 .. seg*hop samples when final; at an input
         rate set by start_wav, seg*hop*in_rate/model_rate) ->
         (wav [B, emit*hop], mel [B, emit, 80], codes [B, emit]) of the chunk this call emitted (emit = 0 on the first call: one
@@ -586,9 +649,14 @@ class StreamingVoiceConversionEngine:
         target, on the GPU in front of the front-end, without look-ahead or added latency (Context.level is its whole-signal form).
         Silence trimming (infer_wav(trim=True)) cannot run here either: a live call cannot drop time.  What serves there is the
         activity detector, start_wav(activity=...): per-frame flags and an output gate, and a server that recorded the call can cut
-        the recording afterwards with those flags (Context.trim_silence(flags=...)) without detecting again."""
+        the recording afterwards with those flags (Context.trim_silence(flags=...)) without detecting again.
+        lost: [B, packets] integer or bool (cuda), non-zero = that packet of the row never arrived: the slots with start_wav(conceal=...)
+        repair them on the GPU in front of the step (Streams.conceal; packets count from the start of the row).  The chunk is
+        copied first: the caller's tensor keeps its samples."""
         fn = self.st.step_wav_async if pipelined else self.st.step_wav
         st = self.st
+        if lost is not None:
+            wav_chunk, fn = wav_chunk.clone(), functools.partial(fn, lost=lost)
         if not (st.output_ld or st.output_formats):
             emit, c, m, w = fn(self.slots, wav_chunk, final=final, mel=mel)
             return w, m, c[:, :emit]
@@ -598,6 +666,17 @@ class StreamingVoiceConversionEngine:
         emit, c, m, _ = fn(self.slots, wav_chunk, final=final, mel=mel, wav_out=buf)
         w = st.wav_block(buf, self.slots, st.output_samples()[0] if emit else 0, st.output_ld or (emit or self.seg) * self.ctx.hop)
         return w, m, c[:, :emit]
+
+    @staticmethod
+    def _check_lost(lost, conceal, loud_norm, trim):
+        """lost= of the whole-utterance calls: it needs conceal=, and cannot go with loud_norm or trim.  Host only."""
+        if lost is None:
+            return
+        if conceal is None or conceal is False:
+            raise ValueError("lost: the flags need conceal= (True, or conan_conceal_cfg's fields)")
+        if loud_norm or (trim is not None and trim is not False):
+            raise ValueError("lost: loud_norm and trim hold the utterance whole, in front of the streaming repair: repair it whole first "
+                             "(Context.conceal) and pass the repaired utterance without lost=")
 
     @torch.no_grad()
     def _loud_norm(self, wav, in_rate, in_format):
@@ -633,7 +712,7 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
                   out_format=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None, register=None, activity=None,
-                  activity_log=None, bypass=None, out_level=None, **filter):
+                  activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] (or None with voice = (bank, ids): start) -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
@@ -656,30 +735,38 @@ class StreamingVoiceConversionEngine:
         level [B, emit]) per emitted chunk (chunk_activity after each call, which joins pipelined work).
         bypass: the wet/dry mix (start_wav): the returned wav is ctx.bypass_mix of the unmixed one and of the samples the front-end
         reads, bit for bit.  out_level: the output leveller (start): the returned model-rate wav is ctx.level of the unlevelled
-        one, bit for bit, and gate, mix, output rate and format apply to the levelled audio."""
+        one, bit for bit, and gate, mix, output rate and format apply to the levelled audio.
+        conceal + lost: loss concealment (start_wav) with lost [B, packets], the flags of the whole utterance: the results are those
+        of infer_wav(ctx.conceal(src_wav, lost, cfg, in_format), ...) bit for bit.  Not with loud_norm or trim, which hold the
+        utterance whole: repair it whole first (Context.conceal)."""
         self._check_voice(ref_mel, voice)
         self._registers(self.slots, register, voice)      # (host checks before anything runs)
         self._activities(self.slots, activity)
         self._bypasses(self.slots, bypass)
+        self._conceals(self.slots, conceal)
+        self._check_lost(lost, conceal, loud_norm, trim)
         trim = self._trim_keywords(trim)
         if trim is not None:
             src_wav = self._trim(src_wav, in_rate, in_format, trim)[0]
         if loud_norm:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
-                       pitch=pitch, voice=voice, follow=follow, register=register, activity=activity, bypass=bypass, out_level=out_level, **filter)
+                       pitch=pitch, voice=voice, follow=follow, register=register, activity=activity, bypass=bypass, out_level=out_level, conceal=conceal,
+                       **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
         empty = src_wav.new_zeros(B, 0)
+        cut = lambda p, m: None if lost is None else self._lost_rows(self.slots, list(lost), [p] * B, [m] * B)      # noqa: E731
         wavs, mels, codes = [], [], []
         pos, final = 0, False
         while True:
             if pos < last:
-                w, m, c = self.feed(src_wav[:, pos:pos + L], pipelined=pipelined, mel=mel)
+                w, m, c = self.feed(src_wav[:, pos:pos + L], pipelined=pipelined, mel=mel, lost=cut(pos, L))
                 pos += L
             else:
-                w, m, c = self.feed(src_wav[:, pos:] if not final else empty, final=True, pipelined=pipelined, mel=mel)
+                w, m, c = self.feed(src_wav[:, pos:] if not final else empty, final=True, pipelined=pipelined, mel=mel,
+                                    lost=None if final else cut(pos, N - pos))
                 pos, done, final = N, final and m.shape[1] == 0, True
                 if done:
                     break
@@ -697,7 +784,7 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, **filter):
+                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
         rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
@@ -708,13 +795,14 @@ class StreamingVoiceConversionEngine:
         (start_wav), one value or a list with one per slot.  register: the slots' register matching (start_wav), one value or a list
         with one per slot.  activity: the slots' activity detector (start_wav), one value or a list with one per slot.  bypass: the
         slots' wet/dry mix (start_wav), one value or a list with one per slot.  out_level: the slots' output leveller (start), one
-        value or a list with one per slot.
+        value or a list with one per slot.  conceal: the slots' loss concealment (start_wav), one value or a list with one per slot.
         No trim=, as in start_wav: the slots stream, and a stream cannot drop time (infer_wav_staggered(trim=True) trims utterances
         it holds whole)."""
         self._check_voice(ref_mel, voice)
         registers = self._registers(slots, register, voice)
         activities = self._activities(slots, activity)
         bypasses = self._bypasses(slots, bypass)
+        conceals = self._conceals(slots, conceal)
         self.st.reset(slots, which=7 | 8)
         self._reference(slots, ref_mel, ref_len, voice)
         self._set_out_rate(slots, out_rate, out_filter)
@@ -728,10 +816,11 @@ class StreamingVoiceConversionEngine:
         self._set_register(slots, registers)
         self._set_activity(slots, activities)
         self._set_bypass(slots, bypasses)
+        self._set_conceal(slots, conceals, _per_slot(in_rate, len(slots)))
         self._set_out_level(slots, out_level)
 
     @torch.no_grad()
-    def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None):
+    def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None, lost=None):
         """Streaming waveform input for slots at different positions of their utterances (conan_step_wav_ragged): slot i takes the
         first samples[i] samples of wav row i (wav [n, <= seg*hop] cuda, or a list of 1-D rows, each in its slot's input format's
         dtype) with its own final flag; the rules per slot are feed()'s.
@@ -739,16 +828,19 @@ class StreamingVoiceConversionEngine:
         pipelined: conan_step_wav_ragged_async - the tensors are complete after self.st.join().
         As in feed(), the reference's whole-utterance loud_norm cannot run here (infer_wav_staggered(loud_norm=True) holds the
         utterances whole); open_slots(level=...) gives a slot the causal input leveller, which can, and a call may mix levelled
-        and unlevelled slots."""
+        and unlevelled slots.  lost: [n, packets] integer or bool (cuda), as feed()'s: the rows of slots with the concealment are
+        repaired in front of the step, the others keep their bytes."""
         fn = self.st.step_wav_ragged_async if pipelined else self.st.step_wav_ragged
-        emit, c, m, w = fn(slots, wav, samples, final, mel=mel)
+        if lost is not None and isinstance(wav, torch.Tensor):
+            wav = wav.clone()      # (a list of rows is packed into a buffer of its own anyway)
+        emit, c, m, w = fn(slots, wav, samples, final, mel=mel, lost=lost)
         counts = self.st.output_samples()        # (emit * hop for a slot without an output rate)
         return [(self.st.wav_row(w, i, slots[i], counts[i]), m[i, :e], c[i, :e]) for i, e in enumerate(emit)]
 
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
                             in_formats=None, out_formats=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None,
-                            register=None, activity=None, activity_log=None, bypass=None, out_level=None, **filter):
+                            register=None, activity=None, activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -769,9 +861,15 @@ class StreamingVoiceConversionEngine:
         utterance.  activity_log: a list that receives, per utterance, a list of (act [emit], level [emit]) per emitted chunk
         (chunk_activity after each call, which joins pipelined work).  bypass: the wet/dry mix (start_wav), one value for every
         utterance or a list with one per utterance.  out_level: the output leveller (start), one value for every utterance or a
-        list with one per utterance."""
+        list with one per utterance.  conceal: loss concealment (start_wav), one value for every utterance or a list with one per
+        utterance; lost: per utterance its whole flags (a 1-D tensor) or None.  Not with loud_norm or trim (Context.conceal repairs an
+        utterance whole)."""
         voice = self._check_voice(ref_mel, voice)
         U = len(src_wavs)
+        conceals = self._conceals(range(U), conceal)
+        self._check_lost(lost, conceal, loud_norm, trim)
+        if lost is not None and len(lost) != U:
+            raise ValueError(f"lost: {len(lost)} values for {U} utterances")
         out_levels = list(out_level) if isinstance(out_level, (list, tuple)) else [out_level] * U
         if len(out_levels) != U:
             raise ValueError(f"out_level: {len(out_levels)} values for {U} utterances")
@@ -810,19 +908,20 @@ class StreamingVoiceConversionEngine:
                                 out_rate=[orates[u] for u in new], out_filter=out_filter, in_format=[ifmts[u] for u in new],
                                 out_format=[ofmts[u] for u in new], level=[levels[u] for u in new], pitch=[pitches[u] for u in new],
                                 follow=[follows[u] for u in new], register=[registers[u] for u in new], activity=[activities[u] for u in new],
-                                bypass=[bypasses[u] for u in new], out_level=[out_levels[u] for u in new],
+                                bypass=[bypasses[u] for u in new], out_level=[out_levels[u] for u in new], conceal=[conceals[u] for u in new],
                                 **filter)
             if not live:
                 tick += 1
                 continue
             us = list(live)
-            rows, samples, final, draining = [], [], [], []
+            rows, samples, final, draining, first = [], [], [], [], []
             width = max(Ls[u] for u in us)
             for u in us:
                 x, (slot, pos, fin) = src_wavs[u], live[u]
                 N, L = x.shape[0], Ls[u]
                 last = (N - 1) // L * L                   # the final call takes the remaining 1 .. L samples
                 draining.append(fin)
+                first.append(pos)
                 if pos < last:
                     piece, live[u][1] = x[pos:pos + L], pos + L
                     final.append(0)
@@ -835,7 +934,9 @@ class StreamingVoiceConversionEngine:
                 samples.append(piece.shape[0])
                 rows.append(piece if self.st.input_formats else torch.nn.functional.pad(piece, (0, width - piece.shape[0])))
             # (rows of several dtypes travel as a list, each packed in its slot's format)
-            res = self.feed_ragged([live[u][0] for u in us], rows if self.st.input_formats else torch.stack(rows), samples, final, pipelined=pipelined, mel=mel)
+            flags = None if lost is None else self._lost_rows([live[u][0] for u in us], [lost[u] for u in us], first, samples)
+            res = self.feed_ragged([live[u][0] for u in us], rows if self.st.input_formats else torch.stack(rows), samples, final, pipelined=pipelined, mel=mel,
+                                   lost=flags)
             if activity_log is not None and any(m.shape[0] for _, m, _ in res):
                 fl, lv = self.chunk_activity()
                 for r, (u, (_, m, _)) in enumerate(zip(us, res)):

@@ -54,6 +54,22 @@ def _row_bytes(rows, n, ld, device):
     return buf
 
 
+def _conceal_cfg(cfg, rate=None):
+    """An enabled _lib.ConcealCfg of: one itself; True (the defaults of `rate`); an integer rate; a dict of fields over the defaults of
+    `rate` (without a rate every field must be given)."""
+    if isinstance(cfg, _lib.ConcealCfg):
+        return cfg
+    if cfg is True:
+        if rate is None:
+            raise ValueError("conceal: True stands for a rate's defaults, and no rate is known here")
+        return _lib.conceal_cfg(rate)
+    if isinstance(cfg, dict):
+        return _lib.conceal_cfg(rate, **cfg)
+    if isinstance(cfg, (int, np.integer)) and not isinstance(cfg, bool):
+        return _lib.conceal_cfg(int(cfg))
+    raise ValueError(f"conceal: {cfg!r} is neither an _lib.ConcealCfg, a dict of its fields, a rate nor True")
+
+
 def mel_cfg(fft_size=1024, hop_size=320, win_length=1024, num_mels=80, fmin=80, fmax=7600, sample_rate=16000, eps=1e-6,
             mel_vmin=-6.0, mel_vmax=1.5, framing=0, natural_log=False, mag_eps=0.0):
     """conan_mel_cfg with Context.wav2mel's defaults (inference/Conan.py:57-70)."""
@@ -432,6 +448,30 @@ class Context:
         if n and N:
             _lib.check(self.lib.conan_convert_samples(self.h, fs, _ptr(xin), src_ld, fd, _ptr(out), dst_ld, n, N, _stream()))
         return out.view(SAMPLE_DTYPES[dst])[:, :N].reshape(*lead, N)
+
+    def conceal(self, x, lost, cfg, fmt="f32", lengths=None):
+        """conan_conceal: the loss concealment's law (include/conan_hip.h, conan_conceal_cfg) on whole signals from the zero state.
+        x [..., N] of format `fmt` ('f32' float32, 's16' int16, 'ulaw' / 'alaw' uint8); lost [..., >= ceil(N / packet)] integer or
+        bool, non-zero = the packet never arrived; cfg: an _lib.ConcealCfg, a dict of its fields, or an input rate, which stands for
+        that rate's defaults (_lib.conceal_keywords); lengths: per row the samples to repair (default N).  -> the repaired signals
+        [..., N] in fmt's dtype (x itself is left alone: the rows are packed into a buffer of the library's row stride first).  It
+        is what a slot with Streams.set_conceal computes over its rows, bit for bit."""
+        c = _conceal_cfg(cfg)
+        f = _lib.sample_format(fmt)
+        dev = torch.device("cuda", self.device)
+        x = x.to(dev)
+        if x.dtype != SAMPLE_DTYPES[fmt]:
+            raise ValueError(f"conceal: format {fmt!r} takes {SAMPLE_DTYPES[fmt]} samples, got {x.dtype}")
+        lead, N = x.shape[:-1], x.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        ld = (N * _lib.SAMPLE_BYTES[fmt] + 3) // 4
+        buf = _row_bytes(x.reshape(n, N), n, max(ld, 1), dev)
+        flags = lost.to(dev).reshape(n, -1).to(torch.int32).contiguous()
+        sm = np.full(n, N, dtype=np.int64) if lengths is None else np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(n))
+        if n and N:
+            _lib.check(self.lib.conan_conceal(self.h, C.byref(c), f, _ptr(buf), max(ld, 1), n, sm.ctypes.data_as(C.c_void_p), _ptr(flags),
+                                              flags.shape[1], _stream()))
+        return buf.view(SAMPLE_DTYPES[fmt])[:, :N].reshape(*lead, N)
 
     def streams(self, max_slots, max_frames=4, max_ref_frames=256, arith="auto", flags=0, dev_plan=None):
         """A stream-set.  arith: 'auto' (library default), 'f32' (f32-input MFMA everywhere) or 'limb' (fp32 products of the
@@ -1102,6 +1142,67 @@ class Streams:
         self._release()
         return out
 
+    def set_conceal(self, slots, cfg=True, rate=None, seed=None, **kw):
+        """conan_streams_set_conceal: loss concealment on the slots' wav-in rows (include/conan_hip.h, conan_conceal_cfg).  cfg: True
+        (the defaults of `rate`, the slots' input rate; None: the model rate), a dict of fields over those defaults, an
+        _lib.ConcealCfg, or None, which turns the feature off; keywords are fields too.  seed: uint8 [n, bytes] (cuda) rows of
+        conceal_state (a hand-over).  It may be called at any time (it joins pipelined work) and survives resets; the state restarts
+        when a slot that was off is enabled and at the first repair after a reset of the front-end.  Slot snapshots do not carry it.
+        The repair itself is conceal(), or lost= on the wav-in steps."""
+        a, p = _i32(slots)
+        if cfg is None:
+            if kw:
+                raise ValueError("set_conceal: cfg=None turns the concealment off and takes no keywords")
+            c = _lib.ConcealCfg()      # (enabled = 0)
+        elif isinstance(cfg, _lib.ConcealCfg):
+            c = cfg
+        else:
+            c = _conceal_cfg(dict({} if cfg is True else cfg, **kw), self.model_rate if rate is None else int(rate))
+        sp, ld = None, 0
+        if seed is not None:
+            if seed.dtype != torch.uint8 or seed.dim() != 2 or seed.shape[0] != len(a) or not seed.is_cuda or seed.stride(1) != 1:
+                raise ValueError("set_conceal: seed must be a cuda uint8 [n, bytes] tensor, as conceal_state returns it")
+            sp, ld = _ptr(seed), int(seed.stride(0))
+        _lib.check(self.lib.conan_streams_set_conceal(self.h, p, len(a), C.byref(c), sp, ld, _stream()))
+        self._release()
+
+    def conceal_cfg(self, slots):
+        """conan_streams_conceal_cfg: per slot the dict of its fields (set_conceal takes it back), None for a slot without the feature."""
+        out = []
+        for slot in slots:
+            c = _lib.ConcealCfg()
+            _lib.check(self.lib.conan_streams_conceal_cfg(self.h, int(slot), C.byref(c)))
+            out.append(_lib.conceal_keywords(c) if c.enabled else None)
+        return out
+
+    def conceal(self, slots, wav, samples, lost):
+        """conan_streams_conceal: repairs the lost packets of the rows IN PLACE, in front of the step call that takes them.  wav: a
+        2-D cuda tensor with one row per slot, contiguous rows a multiple of 4 bytes apart, row i in the format of slots[i] (a
+        float32 tensor for f32 slots; for other or mixed formats the packed uint8 rows the steps build); samples: an int or one per
+        row; lost [n, >= ceil(samples / packet)] integer or bool, non-zero = lost.  Rows of slots without the feature and rows
+        without samples keep their bytes.  -> wav"""
+        a, p = _i32(slots)
+        n = len(a)
+        if not (wav.is_cuda and wav.dim() == 2 and wav.shape[0] == n and (wav.shape[1] < 2 or wav.stride(1) == 1)
+                and wav.stride(0) * wav.element_size() % 4 == 0 and wav.data_ptr() % 4 == 0):
+            raise ValueError("conceal: wav must be a 2-D cuda tensor [n, .] with contiguous rows a multiple of 4 bytes apart")
+        sm, sp = _i32([int(samples)] * n if isinstance(samples, (int, np.integer)) else samples)
+        assert len(sm) == n, (n, len(sm))
+        flags = lost.to(self.dev).reshape(n, -1).to(torch.int32).contiguous()
+        _lib.check(self.lib.conan_streams_conceal(self.h, p, n, sp, _ptr(wav), wav.stride(0) * wav.element_size() // 4, _ptr(flags), flags.shape[1],
+                                                  _stream()))
+        return wav
+
+    def conceal_state(self, slots):
+        """conan_streams_conceal_state: uint8 [n, bytes] (cuda), the slots' concealment states for set_conceal(seed=).  Joins pipelined
+        work."""
+        a, p = _i32(slots)
+        nbytes = int(self.lib.conan_conceal_state_bytes())
+        out = torch.empty(len(a), nbytes, dtype=torch.uint8, device=self.dev)
+        _lib.check(self.lib.conan_streams_conceal_state(self.h, p, len(a), _ptr(out), nbytes, _stream()))
+        self._release()
+        return out
+
     def set_output_format(self, slots, fmt):
         """conan_streams_set_output_format: the slots' audio leaves every step (and flush_output) as 'f32', 's16', 'ulaw' or 'alaw',
         encoded on the GPU behind the vocoder and the output resampler.  Row strides stay in 4-byte units; counts stay in samples."""
@@ -1414,18 +1515,19 @@ class Streams:
                 _lib.check(self.lib.conan_streams_output_fence(self.h, C.c_void_p(out_fence.cuda_stream)))
         _lib.check(self.lib.conan_step_async(self.h, p, n, emit, _ptr(mel_chunk), _ptr(codes), _ptr(mel_out), _ptr(wav_out), _stream()))
 
-    def step_wav(self, slots, wav, final=False, codes=None, mel_out=None, wav_out=None, mel=None):
+    def step_wav(self, slots, wav, final=False, codes=None, mel_out=None, wav_out=None, mel=None, lost=None):
         """Waveform-in chunk step (conan_step_wav): wav [n, samples] cuda float32, samples = seg*hop (0 .. seg*hop when final);
         slots with an input rate (set_input_rate) take seg*hop*rate/model_rate samples instead.
         -> (emit, codes [n, seg], mel [n, emit, 80], wav [n, emit*hop]); emit = 0: no chunk this call (the first call, the end of a
         drain).  mel: dict of Context.wav2mel's front-end keywords (framing 0 only).  Slots with an input format (set_input_format)
         take int16 ('s16') or uint8 ('ulaw' / 'alaw') rows; with an output rate, stride or format wav is a list of 1-D rows, each
-        in its slot's dtype."""
-        return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, False)
+        in its slot's dtype.  lost: the packet flags of the rows [n, packets] (conceal(), on the rows as packed for the library, in
+        front of the step; a contiguous float32 wav on the device is its own packed form and is repaired in place)."""
+        return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, False, lost)
 
-    def step_wav_async(self, slots, wav, final=False, codes=None, mel_out=None, wav_out=None, mel=None):
+    def step_wav_async(self, slots, wav, final=False, codes=None, mel_out=None, wav_out=None, mel=None, lost=None):
         """Pipelined step_wav (conan_step_wav_async): the outputs are complete after join(); same return value."""
-        return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, True)
+        return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, True, lost)
 
     def _wav_in_call(self, n, wav, codes, mel_out, wav_out, mel, pipelined, call):
         """What the wav-in steps share: the default output buffers and their lifetime (a pipelined call's are kept until the next
@@ -1445,13 +1547,15 @@ class Streams:
             self._release()
         return codes, mel_out, wav_out
 
-    def _step_wav(self, slots, wav, final, codes, mel_out, wav_out, mel, pipelined):
+    def _step_wav(self, slots, wav, final, codes, mel_out, wav_out, mel, pipelined, lost=None):
         a, p = _i32(slots)
         n = len(a)
         hop, nm = self.ctx.hop, self.ctx.cfg.num_mels
         assert wav.dim() == 2 and wav.shape[0] == n, wav.shape
         samples = wav.shape[1]
         wav, _, _ = self._in_rows(a, wav, samples)      # (rows samples * 4 bytes apart, whatever the format)
+        if lost is not None and samples:
+            self.conceal(a, wav, samples, lost)
         emit = C.c_int32(0)
         fn = self.lib.conan_step_wav_async if pipelined else self.lib.conan_step_wav
         codes, mel_out, wav_out = self._wav_in_call(n, wav, codes, mel_out, wav_out, mel, pipelined, lambda mc, c, m, w: _lib.check(
@@ -1463,21 +1567,22 @@ class Streams:
             w = wav_out.view(-1)[:n * e * hop].view(n, e * hop)
         return e, codes, mel_out.view(-1)[:n * e * nm].view(n, e, nm), w
 
-    def step_wav_ragged(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None):
+    def step_wav_ragged(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None, lost=None):
         """Waveform-in chunk step for slots at different positions of their utterances (conan_step_wav_ragged): slot i takes the
         first samples[i] samples of wav row i (wav [n, <= seg*hop] cuda float32, or None when every samples[i] is 0) and is stepped
         as step_wav([slot], samples[i], final[i]) alone would step it.  Rows wider than seg*hop (slots with an input rate above the
         model rate) go through conan_step_wav_ragged_ld with the row width as stride.  wav may also be a list of n 1-D rows, each in the
         dtype of its slot's input format (float32, int16, uint8): they are packed from the start of rows a whole number of 4-byte
         units apart.  -> (emit: list of n ints, codes [n, seg], mel [n, seg, 80], wav [n, seg*hop] float32 storage): row i holds
-        emit[i] frames (wav_row(wav, i, slot, count) gives it in the slot's output dtype); the rest of the row is left as it was."""
-        return self._step_wav_ragged(slots, wav, samples, final, codes, mel_out, wav_out, mel, False)
+        emit[i] frames (wav_row(wav, i, slot, count) gives it in the slot's output dtype); the rest of the row is left as it was.
+        lost: as step_wav's."""
+        return self._step_wav_ragged(slots, wav, samples, final, codes, mel_out, wav_out, mel, False, lost)
 
-    def step_wav_ragged_async(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None):
+    def step_wav_ragged_async(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None, lost=None):
         """Pipelined step_wav_ragged (conan_step_wav_ragged_async): the outputs are complete after join(); same return value."""
-        return self._step_wav_ragged(slots, wav, samples, final, codes, mel_out, wav_out, mel, True)
+        return self._step_wav_ragged(slots, wav, samples, final, codes, mel_out, wav_out, mel, True, lost)
 
-    def _step_wav_ragged(self, slots, wav, samples, final, codes, mel_out, wav_out, mel, pipelined):
+    def _step_wav_ragged(self, slots, wav, samples, final, codes, mel_out, wav_out, mel, pipelined, lost=None):
         a, p = _i32(slots)
         n = len(a)
         L = self.seg * self.ctx.hop
@@ -1487,6 +1592,8 @@ class Streams:
         ld = L
         if wav is not None:                           # rows are seg*hop floats apart in conan_step_wav_ragged, wider ones go through _ld
             wav, ld, _ = self._in_rows(a, wav, L)
+            if lost is not None:
+                self.conceal(a, wav, sm, lost)
         emit = (C.c_int32 * n)()
         if ld == L:
             fn, stride = self.lib.conan_step_wav_ragged_async if pipelined else self.lib.conan_step_wav_ragged, ()

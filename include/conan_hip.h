@@ -1102,6 +1102,84 @@ int64_t conan_streams_output_level_state_bytes(const conan_streams* s);
  * `stream` behind a join of pipelined work.  A slot without the leveller is CONAN_ERR_STATE. */
 int conan_streams_output_level_state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream);
 
+/* Input loss concealment (added within ABI 9: a caller detects it by the symbol conan_streams_set_conceal; no existing struct or call
+ * changes).  A server that assembles an 80 ms chunk from 20 ms packets marks the packets that never arrived, and the library fills
+ * them from the slot's own recent audio before the chunk is stepped: the repair runs on the caller's device row IN FRONT OF the
+ * wav-in step call, in place and in the slot's input format, so decoding, the input resampler, the leveller, the pitch follower, the
+ * activity detector and the bypass's dry path all see the repaired row.  No step path changes.
+ * The law (tests/conceal_ref.py restates it in numpy with Python integers).  Everything is per slot, at the slot's input rate, in
+ * sample positions t = 0, 1, ... counted from the last restart.  y[t] is the decoded repaired signal - what the step call decodes
+ * from the row after the repair - and y[t] = 0 for t < 0.  dec and enc are the sample formats' rules (conan_convert_samples: decoding
+ * is exact, encoding rounds to nearest even and saturates; the identity for f32).  lost[t] is the flag of the packet that holds t:
+ * packet m covers [m * packet, (m + 1) * packet) counted from the start of the row (conan_streams_conceal) or from position 0
+ * (conan_conceal); the two agree when every row but the last is a multiple of `packet` long.  A non-zero flag means lost.
+ * State: mode (0 idle, 1 run, 2 fade), p, k (samples since the run began), j (fade samples done), a template T[0 .. p-1] and the last
+ * window + lag_max values of y.  For t in order:
+ *   Lost sample.  If mode != 1 a run starts:
+ *     Lag.  With q[i] the f32 -> s16 value of y[i] (clamp(rint(y * 32768))), D(p) = sum over i = 1 .. window of
+ *       (q[t-i] - q[t-i-p])^2 in int64; p is the smallest lag in [lag_min, lag_max] with minimal D (an all-zero history gives lag_min).
+ *       The difference function and not a normalised correlation: it is exact in integers, so every implementation agrees on p.
+ *     Template.  T[i] = y[t-p+i]; k = 0; mode = 1.
+ *   Then v = T[k mod p] * g(k), one f32 product; the row's sample becomes enc(v), y[t] = dec(enc(v)), k += 1.
+ *     Level.  l(k) = 2^20 for k < hold; floor(((hold + fall - k) << 20) / fall) for hold <= k < hold + fall; 0 beyond.
+ *       g = (float)((double)l / 2^20).
+ *   Received sample.  x = dec(row[t]).  If mode == 1: j = 0 and mode becomes 2 when fade > 0, else 0.  If mode == 2:
+ *     l_in = floor(((j + 1) << 20) / (fade + 1)), l_out = 2^20 - l_in, gains formed as in Level; s = T[k mod p] * g(k), one f32 product;
+ *     v = fma(s, g_out, x * g_in), one f32 product and one f32 fused multiply-add; the row's sample becomes enc(v), y[t] = dec(enc(v)),
+ *     k += 1, j += 1, and mode = 0 once j == fade.  Otherwise y[t] = x and the row's bytes are NOT written.
+ * A loss that begins during a fade is a new run whose lag search reads the faded y.  There is no overlap-add into samples already
+ * delivered: the repair adds no latency.  Nothing here has a tolerance, and the result depends only on positions, never on how the
+ * signal is cut into calls.  The state restarts (mode = 0, history zero) at the slot's first repair call after a reset that includes
+ * CONAN_MODEL_FRONTEND, when a slot that was off is enabled, and from seed_dev when the setter passes one.
+ * Defaults for a rate R (conan_amd._lib.conceal_keywords): packet R/50 (20 ms), lag_min R/400 (2.5 ms), lag_max R*15/1000 (15 ms),
+ * window R/50 (20 ms), hold R/100 (10 ms), fall R/20 (50 ms), fade R/200 (5 ms); at 48 kHz every one lies within the limits. */
+#define CONAN_CONCEAL_MAX_LAG 1024
+#define CONAN_CONCEAL_MAX_WINDOW 1024
+typedef struct conan_conceal_cfg {
+  int32_t enabled;   /* 0: off (other fields ignored) | 1 */
+  int32_t packet;    /* samples per loss flag, >= 1 */
+  int32_t lag_min;   /* 1 <= lag_min <= lag_max <= CONAN_CONCEAL_MAX_LAG */
+  int32_t lag_max;
+  int32_t window;    /* 1 .. CONAN_CONCEAL_MAX_WINDOW: samples compared by the lag search */
+  int32_t hold;      /* >= 0: samples of a run at full level */
+  int32_t fall;      /* >= 1: samples over which the level then falls to zero */
+  int32_t fade;      /* 0 .. 1024: samples of cross-fade back into received audio */
+} conan_conceal_cfg; /* 32 bytes */
+/* Sets (cfg->enabled = 1) or removes (0) the concealment for `slots`.  Every argument is checked before anything changes
+ * (CONAN_ERR_INVALID: a field outside its range, a seed that is misaligned or whose rows are too close), a stream-set without the
+ * streaming front-end is CONAN_ERR_STATE, and pending pipelined work is joined; it may be called at any time, also mid-utterance, and
+ * the setting persists across resets.  A setter call on an enabled slot without a seed replaces the fields and keeps the state.
+ * seed_dev (may be null): row i at seed_dev + i * seed_ld bytes is a record as conan_streams_conceal_state writes it, and becomes the
+ * state of slots[i] on `stream`.
+ * Memory: the first enabling call allocates conan_conceal_state_bytes() per slot and 4 row tables; conan_streams_state_bytes counts
+ * them from then on.  A stream-set that never calls the setter allocates nothing and runs exactly the launches it ran before; the step
+ * calls of a stream-set that does run exactly the launches they ran before, too.
+ * Snapshots carry neither the setting nor the state; conan_streams_layout_id and conan_streams_snapshot_bytes do not change.  The
+ * hand-over: conan_streams_conceal_state, export, import, then this setter with the record as seed_dev. */
+int conan_streams_set_conceal(conan_streams* s, const int32_t* slots, int n, const conan_conceal_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream);
+/* Host only: the concealment cfg of `slot` as set (zeros for a slot without one). */
+int conan_streams_conceal_cfg(const conan_streams* s, int slot, conan_conceal_cfg* cfg_out);
+/* Repairs row i in place: samples[i] (host, >= 0) samples in the input format of slots[i] at wav_dev + i * wav_ld * 4 bytes (the step
+ * calls' row stride), from the int32 flags lost_dev[i * lost_ld + 0 .. ceil(samples[i] / packet) - 1].  ONE launch
+ * (cnk::conceal_kernel, one workgroup per repaired row) on `stream`; rows of slots without the feature and rows with samples[i] = 0
+ * are skipped and keep their bytes, and a call with no row to repair launches nothing and returns CONAN_OK.  The caller orders it in
+ * front of the step call on the same stream, as it orders its own upload of the row. */
+int conan_streams_conceal(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, void* wav_dev, int64_t wav_ld, const int32_t* lost_dev,
+                          int64_t lost_ld, void* stream);
+/* Bytes of one slot's concealment state: a fixed-size, position-independent record - a 32-byte header {int32 mode, p, j, reserved;
+ * int64 k, reserved}, the template (CONAN_CONCEAL_MAX_LAG floats, T[0 .. p-1] first) and the last CONAN_CONCEAL_MAX_LAG +
+ * CONAN_CONCEAL_MAX_WINDOW values of y, oldest first (the law reads the last window + lag_max of them). */
+int64_t conan_conceal_state_bytes(void);
+/* The states of `slots` -> row i at state_dev + i * ld bytes (8-byte aligned, ld a multiple of 8 and at least the record's bytes), on
+ * `stream` behind a join of pipelined work.  A slot about to restart reports the zero state; a slot without the feature is
+ * CONAN_ERR_STATE. */
+int conan_streams_conceal_state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream);
+/* The law on whole signals from the zero state, in place, and the bit-exact yardstick of the streaming form: row i (n rows in
+ * 1 .. 65535) holds samples[i] (host) samples of `format` (CONAN_SAMPLE_*) at x_dev + i * ld * 4 bytes, its flags are
+ * lost_dev[i * lost_ld + .].  cfg->enabled must be 1.  One launch of the same kernel, which walks a row in tiles. */
+int conan_conceal(conan_ctx* ctx, const conan_conceal_cfg* cfg, int format, void* x_dev, int64_t ld, int n, const int64_t* samples, const int32_t* lost_dev,
+                  int64_t lost_ld, void* stream);
+
 /* Silence trimming (added within ABI 9: a caller detects it by the exported symbol; no existing struct or call changes).  The offline
  * half of source activity: the reference's trim_long_sil (utils/audio/vad.py, trim_long_silences) cuts the long pauses out of a whole
  * recording - a moving average over an external detector's flags, a dilation that keeps short pauses, a hard cut - and this call does
