@@ -1,6 +1,6 @@
 // Source activity (include/conan_hip.h, conan_activity_cfg): the detector's kernel and the gate's, the whole-signal entry points
 // conan_activity / conan_activity_gate and the host side of conan_streams_set_activity.  The wav-in steps launch the detector behind
-// their front-end launch on the rows of the call's activity staging (wavio.hip); the vocoder step of a chunk with a gated row launches
+// their front-end launch on the rows of the call's activity staging (act::WavStage below); the vocoder step of a chunk with a gated row launches
 // the gate between conv_post and the output resampler (streams.hip, hifigan_step).
 #include <climits>
 #include <cmath>
@@ -271,46 +271,17 @@ void gate(conan_ctx* ctx, int hop, const float* wav_dev, int n, int64_t samples,
 void set_activity(conan_streams* s, const int32_t* slots, int n, const conan_activity_cfg* cfg, void* stream) {
   if (!s || !slots || !cfg) throw Error(CONAN_ERR_INVALID, "null argument");
   check_cfg(*cfg, "conan_streams_set_activity");      // (before the handle is touched, before any GPU use)
-  if (!s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, "conan_streams_set_activity: the stream-set has no streaming front-end (all three models)");
-  wavio::check_slot_list(s, slots, n);
-  if (!cfg->mode && s->act.cfg.empty()) return;      // a stream-set that never detected: nothing to allocate, nothing to write
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  s->join((hipStream_t)stream);      // (rows of pipelined calls in flight were built from the old setting)
+  if (!wavio::begin_setter(s, slots, n, cfg->mode != 0, s->act.allocated(), "conan_streams_set_activity", stream)) return;
   s->activity_init();
-  conan_activity_cfg c = *cfg;
-  if (!c.mode) memset(&c, 0, sizeof(c));
-  const bool reseed = c.reseed != 0;
-  c.reseed = 0;
-  for (int i = 0; i < n; ++i) {
-    conan_activity_cfg& o = s->act.cfg[slots[i]];
-    s->act.n_on += (c.mode != 0) - (o.mode != 0);
-    if (c.mode && (reseed || !o.mode)) s->act.pending[slots[i]] = 1;      // the restart travels in the slot's next detector row
-    o = c;
-  }
-}
-
-void get_activity(const conan_streams* s, int slot, conan_activity_cfg* out) {
-  if (!s || !out) throw Error(CONAN_ERR_INVALID, "null argument");
-  if (slot < 0 || slot >= s->max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
-  if (!s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, "conan_streams_activity: the stream-set has no streaming front-end (all three models)");
-  if (s->act.cfg.empty()) memset(out, 0, sizeof(*out));
-  else *out = s->act.cfg[slot];
+  s->act.store_restarting(slots, n, *cfg);      // the restart travels in the slot's next detector row
 }
 
 // rows without frames: a pending slot's row starts from the seed and names no slot, any other reads its state (and writes it back as it is)
 void state(conan_streams* s, const int32_t* slots, int n, conan_activity_state* state_dev, void* stream) {
   if (!s || !slots || !state_dev) throw Error(CONAN_ERR_INVALID, "null argument");
   wavio::check_slot_list(s, slots, n);
-  std::vector<cnk::ActRow> rows((size_t)n);
-  for (int i = 0; i < n; ++i) {
-    if (!s->act.on(slots[i])) throw Error(CONAN_ERR_STATE, "conan_streams_activity_state: slot " + std::to_string(slots[i]) + " has no activity detector (conan_streams_set_activity)");
-    rows[i] = row(s->act.cfg[slots[i]]);
-    rows[i].state_row = i;
-    if (!s->act.pending[slots[i]]) { rows[i].slot = slots[i]; rows[i].reseed = 0; }
-  }
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  hipStream_t st = (hipStream_t)stream;
-  s->join(st);
+  const std::vector<cnk::ActRow> rows = s->act.state_rows<cnk::ActRow>(slots, n, row, "conan_streams_activity_state", " has no activity detector (conan_streams_set_activity)");
+  hipStream_t st = s->enter(stream);
   const int q = s->act.sets.begin(rows.data(), n, st);
   cnk::ActArgs a;
   memset(&a, 0, sizeof(a));
@@ -325,18 +296,59 @@ void state(conan_streams* s, const int32_t* slots, int n, conan_activity_state* 
 // the flags and levels the last wav-in call produced, in call order: rows of `seg`, zeros where a row had no detector or did not emit
 void last_call(conan_streams* s, int32_t* act_dev, int32_t* level_dev, void* stream) {
   if (!s || !act_dev || !level_dev) throw Error(CONAN_ERR_INVALID, "null argument");
-  if (!s->wav_in.fe_chunk || s->wav_in.fe_last_n == 0) throw Error(CONAN_ERR_STATE, "conan_step_wav_activity: no conan_step_wav call yet");
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  hipStream_t st = (hipStream_t)stream;
-  s->join(st);
+  hipStream_t st = wavio::begin_last_call(s, "conan_step_wav_activity", stream);
   const int seg = s->ctx->cfg.emf_segment, n = s->wav_in.fe_last_n;
-  HIP_CHECK(hipMemsetAsync(act_dev, 0, (size_t)n * seg * sizeof(int32_t), st));
-  HIP_CHECK(hipMemsetAsync(level_dev, 0, (size_t)n * seg * sizeof(int32_t), st));
-  for (const conan_streams::Activity::LastRow& r : s->act.last) {
-    HIP_CHECK(hipMemcpyAsync(act_dev + (size_t)r.row * seg, s->act.flags[r.set] + (size_t)r.src * seg, (size_t)r.emit * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(level_dev + (size_t)r.row * seg, s->act.levels[r.set] + (size_t)r.src * (seg + 1) + 1, (size_t)r.emit * sizeof(int32_t),
-                             hipMemcpyDeviceToDevice, st));
+  copy_last_rows(s->act.last, act_dev, n, seg, s->act.flags, seg, 0, st);
+  copy_last_rows(s->act.last, level_dev, n, seg, s->act.levels, seg + 1, 1, st);
+}
+
+void WavStage::plan(const conan_streams* s, const WavCall& c) {
+  if (s->act.n_on < 1) return;
+  bool any = false;
+  for (int i = 0; i < c.n; ++i) {
+    if (!s->act.on(c.slots[i])) continue;
+    if (c.mel.sample_rate != 50 * c.hop) throw Error(CONAN_ERR_INVALID, c.who + ": slot " + std::to_string(c.slots[i]) + " detects source activity: conan_mel_cfg.sample_rate must be 50 * hop_size");
+    const FePlan& p = c.pl[i];
+    if (p.emit < 1) continue;
+    if (p.R - std::max(0ll, (long long)p.pos * c.hop - c.N / 2) > s->wav_in.fe_LA)
+      throw Error(CONAN_ERR_UNSUPPORTED, c.who + ": slot " + std::to_string(c.slots[i]) + " detects source activity: the chunk's frames have left the audio ring at this fft_size");
+    any = true;
   }
+  if (!any) return;
+  gate.assign(c.groups.size(), 0);
+  rows = c.table_rows<cnk::ActRow>([&](int g, int i, int at, cnk::ActRow& r) {
+    const int slot = c.slots[i];
+    if (!s->act.on(slot)) return false;
+    const FePlan& p = c.pl[i];
+    r = row(s->act.cfg[slot]);
+    r.src_off = (long long)slot * s->wav_in.fe_LA; r.valid = p.R; r.mask = s->wav_in.fe_LA - 1;
+    r.f_first = p.pos; r.nframes = p.emit; r.slot = slot; r.reseed = s->act.pending[slot]; r.start_lvl = 1;
+    last.push_back({i, 0, at, p.emit});
+    if (r.mode == 2) gate[g] = 1;
+    return true;
+  });
+  for (size_t at = 0; at < rows.size(); ++at) { rows[at].out_off = (long long)at * c.seg; rows[at].lvl_off = (long long)at * (c.seg + 1) + 1; }
+}
+
+// the detector, behind the front-end launch (and the tracker's and the register's): the call's samples are in the audio rings
+void WavStage::enqueue(conan_streams* s, const WavCall& c, hipStream_t cst, FrontWork& front, std::vector<conan_streams::OutPlan>& ops) {
+  if (rows.empty()) return;
+  q = s->act.sets.begin(rows.data(), (int)rows.size(), cst);
+  for (LastRow& r : last) r.set = q;
+  cnk::ActArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src = s->wav_in.fe_audio; a.act = s->act.flags[q]; a.lvl = s->act.levels[q]; a.state = s->act.state;
+  a.tab = s->act.sets.rows[q]; a.rows = (int)rows.size(); a.n_fft = c.N; a.hop = c.hop;
+  front.at[kFrActivity] = [s, a](hipStream_t st) { s->profiled("activity_kernel", 0.0, st, [&] { cnk::launch_activity(a, st); }); };
+  c.each_group([&](int g, int off) {
+    if (gate[g]) ops[g].gate = {s->act.sets.rows[q] + off, s->act.levels[q] + (size_t)off * (c.seg + 1) + 1, c.seg + 1};
+  });
+}
+
+void WavStage::commit(conan_streams* s, hipStream_t, hipStream_t last_st) {
+  if (!rows.empty()) s->act.sets.end(q, last_st);      // (behind the call's last vocoder step: the gate is the last reader of table and levels)
+  for (const cnk::ActRow& r : rows) if (r.slot >= 0) s->act.pending[r.slot] = 0;      // (the rows carried the restarts)
+  s->act.last = std::move(last);
 }
 
 }  // namespace act
@@ -351,6 +363,5 @@ void conan_streams::activity_init() {
   }
   act.sets.init(max_slots, allocs);
   state_bytes += (int64_t)kActSets * max_slots * sizeof(cnk::ActRow);
-  act.cfg.assign(max_slots, conan_activity_cfg{});
-  act.pending.assign(max_slots, 0);
+  act.assign(max_slots);
 }

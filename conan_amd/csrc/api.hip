@@ -346,14 +346,8 @@ int conan_streams_reset(conan_streams* s, const int32_t* slots, int n, int which
       // the input rate stays; the resampler's history restarts (inputs before the first are zero, the ring needs no clearing)
       if (!s->wav_in.rs_slot.empty())
         for (int i = 0; i < n; ++i) { conan_streams::RsSlot& r = s->wav_in.rs_slot[slots[i]]; r.in = 0; r.out = 0; r.phase = 0; }
-      // the register setting stays; the estimate restarts from its seed in the slot's next register row (a host flag: no launch here)
-      for (int i = 0; i < n && !s->reg.pending.empty(); ++i) s->reg.pending[slots[i]] = 1;
-      // ... and so does the activity setting, whose state restarts from its seed in the slot's next detector row
-      for (int i = 0; i < n && !s->act.pending.empty(); ++i) s->act.pending[slots[i]] = 1;
-      // ... and the bypass setting, whose levels restart from their seeds in the slot's next stage row
-      for (int i = 0; i < n && !s->byp.pending.empty(); ++i) s->byp.pending[slots[i]] = 1;
-      // ... and the concealment setting, whose state restarts from zeros in the slot's next repair row
-      for (int i = 0; i < n && !s->conc.pending.empty(); ++i) s->conc.pending[slots[i]] = 1;
+      // the features' settings stay; their states restart in the slots' next rows
+      s->restart_features(slots, n);
     }
   });
 }
@@ -462,7 +456,7 @@ int conan_streams_set_pitch_follow(conan_streams* s, const int32_t* slots, int n
   return guarded([&] { f0::set_follow(s, slots, n, cfg, stream); });
 }
 
-int conan_streams_pitch_follow(const conan_streams* s, int slot, conan_f0_cfg* out) { return guarded([&] { f0::get_follow(s, slot, out); }); }
+int conan_streams_pitch_follow(const conan_streams* s, int slot, conan_f0_cfg* out) { return guarded([&] { wavio::get_setting(s, &conan_streams::follow, slot, out, "conan_streams_pitch_follow"); }); }
 
 int conan_step_wav_contour(conan_streams* s, float* f0_dev, float* uv_dev, void* stream) { return guarded([&] { f0::contour(s, f0_dev, uv_dev, stream); }); }
 
@@ -475,7 +469,7 @@ int conan_streams_set_pitch_register(conan_streams* s, const int32_t* slots, int
   return guarded([&] { reg::set_register(s, slots, n, cfg, stream); });
 }
 
-int conan_streams_pitch_register(const conan_streams* s, int slot, conan_register_cfg* cfg_out) { return guarded([&] { reg::get_register(s, slot, cfg_out); }); }
+int conan_streams_pitch_register(const conan_streams* s, int slot, conan_register_cfg* cfg_out) { return guarded([&] { wavio::get_setting(s, &conan_streams::reg, slot, cfg_out, "conan_streams_pitch_register"); }); }
 
 int conan_streams_pitch_register_state(conan_streams* s, const int32_t* slots, int n, int64_t* state_dev, void* stream) {
   return guarded([&] { reg::state(s, slots, n, state_dev, stream); });
@@ -495,7 +489,7 @@ int conan_streams_set_activity(conan_streams* s, const int32_t* slots, int n, co
   return guarded([&] { act::set_activity(s, slots, n, cfg, stream); });
 }
 
-int conan_streams_activity(const conan_streams* s, int slot, conan_activity_cfg* cfg_out) { return guarded([&] { act::get_activity(s, slot, cfg_out); }); }
+int conan_streams_activity(const conan_streams* s, int slot, conan_activity_cfg* cfg_out) { return guarded([&] { wavio::get_setting(s, &conan_streams::act, slot, cfg_out, "conan_streams_activity"); }); }
 
 int conan_streams_activity_state(conan_streams* s, const int32_t* slots, int n, conan_activity_state* state_dev, void* stream) {
   return guarded([&] { act::state(s, slots, n, state_dev, stream); });
@@ -509,7 +503,7 @@ int conan_streams_set_bypass(conan_streams* s, const int32_t* slots, int n, cons
   return guarded([&] { byp::set_bypass(s, slots, n, cfg, stream); });
 }
 
-int conan_streams_bypass(const conan_streams* s, int slot, conan_bypass_cfg* cfg_out) { return guarded([&] { byp::get_bypass(s, slot, cfg_out); }); }
+int conan_streams_bypass(const conan_streams* s, int slot, conan_bypass_cfg* cfg_out) { return guarded([&] { wavio::get_setting(s, &conan_streams::byp, slot, cfg_out, "conan_streams_bypass"); }); }
 
 int conan_streams_bypass_state(conan_streams* s, const int32_t* slots, int n, conan_bypass_state* state_dev, void* stream) {
   return guarded([&] { byp::state(s, slots, n, state_dev, stream); });
@@ -712,18 +706,18 @@ int conan_level(conan_ctx* ctx, const conan_level_cfg* cfg, const float* x_dev, 
 }
 
 int conan_streams_set_input_level(conan_streams* s, const int32_t* slots, int n, const conan_level_cfg* cfg) {
-  return guarded([&] { wavio::set_input_level(s, slots, n, cfg); });
+  return guarded([&] { level::set_input_level(s, slots, n, cfg); });
 }
 
 int conan_streams_input_level(conan_streams* s, const int32_t* slots, int n, double* stats_dev, void* stream) {
-  return guarded([&] { wavio::input_level(s, slots, n, stats_dev, stream); });
+  return guarded([&] { level::input_level(s, slots, n, stats_dev, stream); });
 }
 
 int conan_streams_set_output_level(conan_streams* s, const int32_t* slots, int n, const conan_level_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream) {
   return guarded([&] { olv::set_level(s, slots, n, cfg, seed_dev, seed_ld, stream); });
 }
 
-int conan_streams_output_level_cfg(const conan_streams* s, int slot, conan_level_cfg* cfg_out) { return guarded([&] { olv::get_level(s, slot, cfg_out); }); }
+int conan_streams_output_level_cfg(const conan_streams* s, int slot, conan_level_cfg* cfg_out) { return guarded([&] { wavio::get_setting(s, &conan_streams::out_lv, slot, cfg_out, nullptr); }); }
 
 int conan_streams_output_level(conan_streams* s, const int32_t* slots, int n, double* stats_dev, void* stream) {
   return guarded([&] { olv::stats(s, slots, n, stats_dev, stream); });
@@ -743,7 +737,7 @@ int conan_streams_set_conceal(conan_streams* s, const int32_t* slots, int n, con
   return guarded([&] { conc::set_conceal(s, slots, n, cfg, seed_dev, seed_ld, stream); });
 }
 
-int conan_streams_conceal_cfg(const conan_streams* s, int slot, conan_conceal_cfg* cfg_out) { return guarded([&] { conc::get_conceal(s, slot, cfg_out); }); }
+int conan_streams_conceal_cfg(const conan_streams* s, int slot, conan_conceal_cfg* cfg_out) { return guarded([&] { wavio::get_setting(s, &conan_streams::conc, slot, cfg_out, nullptr); }); }
 
 int conan_streams_conceal(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, void* wav_dev, int64_t wav_ld, const int32_t* lost_dev,
                           int64_t lost_ld, void* stream) {

@@ -1,6 +1,6 @@
 // Source bypass (include/conan_hip.h, conan_bypass_cfg): the stage kernel and the mix kernel, the whole-signal entry point
 // conan_bypass_mix and the host side of conan_streams_set_bypass.  The wav-in steps launch the stage kernel behind their front-end
-// launch (and the activity detector's) on the rows of the call's bypass staging (wavio.hip); the vocoder step of a chunk with a bypass
+// launch (and the activity detector's) on the rows of the call's bypass staging (byp::WavStage below); the vocoder step of a chunk with a bypass
 // row launches the mix between the activity gate and the output resampler (streams.hip, hifigan_step).
 #include <climits>
 
@@ -174,46 +174,18 @@ void mix(conan_ctx* ctx, int hop, const float* wet_dev, int64_t wet_ld, const fl
 void set_bypass(conan_streams* s, const int32_t* slots, int n, const conan_bypass_cfg* cfg, void* stream) {
   if (!s || !slots || !cfg) throw Error(CONAN_ERR_INVALID, "null argument");
   check_cfg(*cfg, "conan_streams_set_bypass");      // (before the handle is touched, before any GPU use)
-  if (!s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, "conan_streams_set_bypass: the stream-set has no streaming front-end (all three models)");
-  wavio::check_slot_list(s, slots, n);
-  if (!cfg->enabled && s->byp.cfg.empty()) return;      // a stream-set that never mixed: nothing to allocate, nothing to write
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  s->join((hipStream_t)stream);      // (rows of pipelined calls in flight were built from the old setting)
+  if (!wavio::begin_setter(s, slots, n, cfg->enabled != 0, s->byp.allocated(), "conan_streams_set_bypass", stream)) return;
   s->bypass_init();
-  conan_bypass_cfg c = *cfg;
-  if (!c.enabled) memset(&c, 0, sizeof(c));
-  const bool reseed = c.reseed != 0;
-  c.reseed = 0;
-  for (int i = 0; i < n; ++i) {
-    conan_bypass_cfg& o = s->byp.cfg[slots[i]];
-    s->byp.n_on += (c.enabled != 0) - (o.enabled != 0);
-    if (c.enabled && (reseed || !o.enabled)) s->byp.pending[slots[i]] = 1;      // the restart travels in the slot's next stage row
-    o = c;
-  }
-}
-
-void get_bypass(const conan_streams* s, int slot, conan_bypass_cfg* out) {
-  if (!s || !out) throw Error(CONAN_ERR_INVALID, "null argument");
-  if (slot < 0 || slot >= s->max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
-  if (!s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, "conan_streams_bypass: the stream-set has no streaming front-end (all three models)");
-  if (s->byp.cfg.empty()) memset(out, 0, sizeof(*out));
-  else *out = s->byp.cfg[slot];
+  s->byp.store_restarting(slots, n, *cfg);      // the restart travels in the slot's next stage row
 }
 
 // rows without frames: a pending slot's row starts from the seed and names no slot, any other reads its state (and writes it back as it is)
 void state(conan_streams* s, const int32_t* slots, int n, conan_bypass_state* state_dev, void* stream) {
   if (!s || !slots || !state_dev) throw Error(CONAN_ERR_INVALID, "null argument");
   wavio::check_slot_list(s, slots, n);
-  std::vector<cnk::BypRow> rows((size_t)n);
-  for (int i = 0; i < n; ++i) {
-    if (!s->byp.on(slots[i])) throw Error(CONAN_ERR_STATE, "conan_streams_bypass_state: slot " + std::to_string(slots[i]) + " has no bypass (conan_streams_set_bypass)");
-    rows[i] = row(s->byp.cfg[slots[i]]);
-    rows[i].state_row = i; rows[i].fill = 0;
-    if (!s->byp.pending[slots[i]]) { rows[i].slot = slots[i]; rows[i].reseed = 0; }
-  }
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  hipStream_t st = (hipStream_t)stream;
-  s->join(st);
+  std::vector<cnk::BypRow> rows = s->byp.state_rows<cnk::BypRow>(slots, n, row, "conan_streams_bypass_state", " has no bypass (conan_streams_set_bypass)");
+  for (cnk::BypRow& r : rows) r.fill = 0;
+  hipStream_t st = s->enter(stream);
   const int q = s->byp.sets.begin(rows.data(), n, st);
   cnk::BypStageArgs a;
   memset(&a, 0, sizeof(a));
@@ -229,18 +201,64 @@ void state(conan_streams* s, const int32_t* slots, int n, conan_bypass_state* st
 // the levels the last wav-in call produced, in call order: rows of `seg`, zeros where a row had no bypass or did not emit
 void last_call(conan_streams* s, int32_t* wet_lvl_dev, int32_t* dry_lvl_dev, void* stream) {
   if (!s || !wet_lvl_dev || !dry_lvl_dev) throw Error(CONAN_ERR_INVALID, "null argument");
-  if (!s->wav_in.fe_chunk || s->wav_in.fe_last_n == 0) throw Error(CONAN_ERR_STATE, "conan_step_wav_bypass: no conan_step_wav call yet");
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  hipStream_t st = (hipStream_t)stream;
-  s->join(st);
+  hipStream_t st = wavio::begin_last_call(s, "conan_step_wav_bypass", stream);
   const int seg = s->ctx->cfg.emf_segment, n = s->wav_in.fe_last_n;
-  HIP_CHECK(hipMemsetAsync(wet_lvl_dev, 0, (size_t)n * seg * sizeof(int32_t), st));
-  HIP_CHECK(hipMemsetAsync(dry_lvl_dev, 0, (size_t)n * seg * sizeof(int32_t), st));
-  for (const conan_streams::Bypass::LastRow& r : s->byp.last) {
-    const size_t src = (size_t)r.src * (seg + 1) + 1;
-    HIP_CHECK(hipMemcpyAsync(wet_lvl_dev + (size_t)r.row * seg, s->byp.wet_lvl[r.set] + src, (size_t)r.emit * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(dry_lvl_dev + (size_t)r.row * seg, s->byp.dry_lvl[r.set] + src, (size_t)r.emit * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  copy_last_rows(s->byp.last, wet_lvl_dev, n, seg, s->byp.wet_lvl, seg + 1, 1, st);
+  copy_last_rows(s->byp.last, dry_lvl_dev, n, seg, s->byp.dry_lvl, seg + 1, 1, st);
+}
+
+void WavStage::plan(const conan_streams* s, const WavCall& c) {
+  if (s->byp.n_on < 1) return;
+  bool any = false;
+  for (int i = 0; i < c.n; ++i) {
+    const FePlan& p = c.pl[i];
+    if (!s->byp.on(c.slots[i]) || p.emit < 1) continue;
+    if (p.R - (long long)p.pos * c.hop > s->wav_in.fe_LA)
+      throw Error(CONAN_ERR_UNSUPPORTED, c.who + ": slot " + std::to_string(c.slots[i]) + " mixes its source: the chunk's samples have left the audio ring");
+    any = true;
   }
+  if (!any) return;
+  mix.assign(c.groups.size(), 0);
+  rows = c.table_rows<cnk::BypRow>([&](int g, int i, int at, cnk::BypRow& r) {
+    const int slot = c.slots[i];
+    if (!s->byp.on(slot)) return false;
+    const FePlan& p = c.pl[i];
+    r = row(s->byp.cfg[slot]);
+    r.src_off = (long long)slot * s->wav_in.fe_LA; r.valid = p.R; r.mask = s->wav_in.fe_LA - 1; r.s_first = (long long)p.pos * c.hop;
+    r.nframes = p.emit; r.slot = slot; r.reseed = s->byp.pending[slot];
+    // (the fill reads the gate's levels of this call: the activity table has the same rows in the same order; a slot that
+    // is not in activity mode 2 has no gate, which counts as open)
+    if (r.fill) r.fill = s->act.on(slot) && s->act.cfg[slot].mode == 2 ? 1 : 2;
+    fill = fill || r.fill == 1;
+    last.push_back({i, 0, at, p.emit});
+    mix[g] = 1;
+    return true;
+  });
+}
+
+// the stage kernel, behind the detector: the slew, and the chunk's source samples out of the audio rings into the set's dry staging
+void WavStage::enqueue(conan_streams* s, const WavCall& c, hipStream_t cst, FrontWork& front, std::vector<conan_streams::OutPlan>& ops) {
+  if (rows.empty()) return;
+  q = s->byp.sets.begin(rows.data(), (int)rows.size(), cst);
+  for (LastRow& r : last) r.set = q;
+  cnk::BypStageArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src = s->wav_in.fe_audio; a.dry = s->byp.dry[q]; a.wet_lvl = s->byp.wet_lvl[q]; a.dry_lvl = s->byp.dry_lvl[q];
+  a.gate_lvl = fill ? s->act.levels[gate_stage->q] : nullptr; a.state = s->byp.state;
+  a.tab = s->byp.sets.rows[q]; a.rows = (int)rows.size(); a.seg = c.seg; a.hop = c.hop;
+  front.at[kFrBypass] = [s, a](hipStream_t st) { s->profiled("bypass_stage_kernel", 0.0, st, [&] { cnk::launch_bypass_stage(a, st); }); };
+  c.each_group([&](int g, int off) {
+    if (!mix[g]) return;
+    const size_t lvl = (size_t)off * (c.seg + 1) + 1;
+    ops[g].mix = {s->byp.sets.rows[q] + off, s->byp.wet_lvl[q] + lvl, s->byp.dry_lvl[q] + lvl, s->byp.dry[q] + (size_t)off * c.seg * c.hop,
+                  c.seg + 1, (long long)c.seg * c.hop};
+  });
+}
+
+void WavStage::commit(conan_streams* s, hipStream_t, hipStream_t last_st) {
+  if (!rows.empty()) s->byp.sets.end(q, last_st);      // (behind the call's last vocoder step: the mix is the last reader of table, levels and samples)
+  for (const cnk::BypRow& r : rows) if (r.slot >= 0) s->byp.pending[r.slot] = 0;      // (the rows carried the restarts)
+  s->byp.last = std::move(last);
 }
 
 }  // namespace byp
@@ -256,6 +274,5 @@ void conan_streams::bypass_init() {
   }
   byp.sets.init(max_slots, allocs);
   state_bytes += (int64_t)kActSets * max_slots * sizeof(cnk::BypRow);
-  byp.cfg.assign(max_slots, conan_bypass_cfg{});
-  byp.pending.assign(max_slots, 0);
+  byp.assign(max_slots);
 }

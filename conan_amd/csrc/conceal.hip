@@ -257,34 +257,16 @@ void set_conceal(conan_streams* s, const int32_t* slots, int n, const conan_conc
   if (!s || !slots || !cfg) throw Error(CONAN_ERR_INVALID, "null argument");
   check_cfg(*cfg, "conan_streams_set_conceal");      // (before the handle is touched, before any GPU use)
   if (seed_dev) check_seed("conan_streams_set_conceal", seed_dev, seed_ld);
-  if (!s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, "conan_streams_set_conceal: the stream-set has no streaming front-end (all three models)");
-  wavio::check_slot_list(s, slots, n);
-  if (!cfg->enabled && s->conc.cfg.empty()) return;      // a stream-set that never concealed: nothing to allocate, nothing to write
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+  if (!wavio::begin_setter(s, slots, n, cfg->enabled != 0, s->conc.allocated(), "conan_streams_set_conceal", stream)) return;
   hipStream_t st = (hipStream_t)stream;
-  s->join(st);
   s->conceal_init();
-  conan_conceal_cfg c = *cfg;
-  if (!c.enabled) memset(&c, 0, sizeof(c));
-  for (int i = 0; i < n; ++i) {
-    conan_conceal_cfg& o = s->conc.cfg[slots[i]];
-    s->conc.n_on += (c.enabled != 0) - (o.enabled != 0);
-    if (c.enabled && seed_dev) {
-      HIP_CHECK(hipMemcpyAsync(s->conc.state + (size_t)slots[i] * cnk::kConcStateBytes, static_cast<const char*>(seed_dev) + (size_t)i * seed_ld,
-                               (size_t)cnk::kConcStateBytes, hipMemcpyDeviceToDevice, st));
-      s->conc.pending[slots[i]] = 0;
-    } else if (c.enabled && !o.enabled) {
-      s->conc.pending[slots[i]] = 1;      // the restart travels in the slot's next repair row
-    }
-    o = c;
+  // a slot that was off restarts from zeros in its next repair row - or from its seed row, now, which then clears the flag
+  s->conc.store(slots, n, *cfg, [&](int i) { s->conc.pending[slots[i]] = 1; });
+  for (int i = 0; i < n && cfg->enabled && seed_dev; ++i) {
+    HIP_CHECK(hipMemcpyAsync(s->conc.state + (size_t)slots[i] * cnk::kConcStateBytes, static_cast<const char*>(seed_dev) + (size_t)i * seed_ld,
+                             (size_t)cnk::kConcStateBytes, hipMemcpyDeviceToDevice, st));
+    s->conc.pending[slots[i]] = 0;
   }
-}
-
-void get_conceal(const conan_streams* s, int slot, conan_conceal_cfg* out) {
-  if (!s || !out) throw Error(CONAN_ERR_INVALID, "null argument");
-  if (slot < 0 || slot >= s->max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
-  if (s->conc.cfg.empty()) memset(out, 0, sizeof(*out));
-  else *out = s->conc.cfg[slot];
 }
 
 void repair(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, void* wav_dev, int64_t wav_ld, const int32_t* lost_dev, int64_t lost_ld,
@@ -328,9 +310,7 @@ void state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64
   wavio::check_slot_list(s, slots, n);
   for (int i = 0; i < n; ++i)
     if (!s->conc.on(slots[i])) throw Error(CONAN_ERR_STATE, "conan_streams_conceal_state: slot " + std::to_string(slots[i]) + " has no concealment (conan_streams_set_conceal)");
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  hipStream_t st = (hipStream_t)stream;
-  s->join(st);
+  hipStream_t st = s->enter(stream);
   for (int i = 0; i < n; ++i) {
     char* dst = static_cast<char*>(state_dev) + (size_t)i * ld;
     if (s->conc.pending[slots[i]]) HIP_CHECK(hipMemsetAsync(dst, 0, (size_t)cnk::kConcStateBytes, st));
@@ -345,6 +325,5 @@ void conan_streams::conceal_init() {
   conc.state = reinterpret_cast<char*>(alloc((size_t)max_slots * cnk::kConcStateBytes / sizeof(float)));      // zeroed (counted by state_bytes)
   conc.sets.init(max_slots, allocs);
   state_bytes += (int64_t)kStageSets * max_slots * sizeof(cnk::ConcRow);
-  conc.cfg.assign(max_slots, conan_conceal_cfg{});
-  conc.pending.assign(max_slots, 0);
+  conc.assign(max_slots);
 }

@@ -1,6 +1,6 @@
 // Source-pitch following (include/conan_hip.h, conan_f0_cfg): the YIN tracker's kernel, the whole-signal entry point conan_f0 and the
-// host side of conan_streams_set_pitch_follow.  The wav-in steps launch the kernel behind their front-end launch (wavio.hip); the
-// decoder step reads what it wrote through PitchHeadArgs::trk_f0 / trk_uv (rowops.h, pitch_law).
+// host side of conan_streams_set_pitch_follow.  The wav-in steps launch the kernel behind their front-end launch (f0::WavStage
+// below); the decoder step reads what it wrote through PitchHeadArgs::trk_f0 / trk_uv (rowops.h, pitch_law).
 #include <cmath>
 
 #include "streams.h"
@@ -171,44 +171,69 @@ void set_follow(conan_streams* s, const int32_t* slots, int n, const conan_f0_cf
   if (!s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, "conan_streams_set_pitch_follow: the stream-set has no streaming front-end (all three models)");
   check_cfg(*cfg, 50.0 * s->ctx->hop, cnk::kF0MaxFft, "conan_streams_set_pitch_follow");
   wavio::check_slot_list(s, slots, n);
-  if (!cfg->enabled && s->follow.cfg.empty()) return;      // a stream-set that never followed: nothing to allocate, nothing to write
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  hipStream_t st = (hipStream_t)stream;
-  s->join(st);
+  if (!cfg->enabled && !s->follow.allocated()) return;      // a stream-set that never followed: nothing to allocate, nothing to write
+  hipStream_t st = s->enter(stream);
   s->follow_init();
-  conan_f0_cfg c = *cfg;
-  if (!c.enabled) memset(&c, 0, sizeof(c));
+  s->follow.store(slots, n, *cfg);
   std::vector<conan_pitch_cfg> cfgs((size_t)n);
-  for (int i = 0; i < n; ++i) {
-    s->follow.n_on += c.enabled - s->follow.cfg[slots[i]].enabled;
-    s->follow.cfg[slots[i]] = c;
-    cfgs[i] = s->pt_cfg[slots[i]];
-  }
+  for (int i = 0; i < n; ++i) cfgs[i] = s->pt_cfg[slots[i]];
   s->pitch_write(slots, n, cfgs.data(), st);      // (the follow flag is the sixth word of the slots' pitch-table entries)
-}
-
-void get_follow(const conan_streams* s, int slot, conan_f0_cfg* out) {
-  if (!s || !out) throw Error(CONAN_ERR_INVALID, "null argument");
-  if (slot < 0 || slot >= s->max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
-  if (!s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, "conan_streams_pitch_follow: the stream-set has no streaming front-end (all three models)");
-  if (s->follow.cfg.empty()) memset(out, 0, sizeof(*out));
-  else *out = s->follow.cfg[slot];
 }
 
 // the contour the last wav-in call handed the decoder, in call order: rows of `seg`, zeros where a row did not follow or did not emit
 void contour(conan_streams* s, float* f0_dev, float* uv_dev, void* stream) {
   if (!s || !f0_dev || !uv_dev) throw Error(CONAN_ERR_INVALID, "null argument");
-  if (!s->wav_in.fe_chunk || s->wav_in.fe_last_n == 0) throw Error(CONAN_ERR_STATE, "conan_step_wav_contour: no conan_step_wav call yet");
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  hipStream_t st = (hipStream_t)stream;
-  s->join(st);
+  hipStream_t st = wavio::begin_last_call(s, "conan_step_wav_contour", stream);
   const int seg = s->ctx->cfg.emf_segment, n = s->wav_in.fe_last_n;
-  HIP_CHECK(hipMemsetAsync(f0_dev, 0, (size_t)n * seg * sizeof(float), st));
-  HIP_CHECK(hipMemsetAsync(uv_dev, 0, (size_t)n * seg * sizeof(float), st));
-  for (const conan_streams::Follow::LastRow& r : s->follow.last) {
-    HIP_CHECK(hipMemcpyAsync(f0_dev + (size_t)r.row * seg, s->follow.ct_f0[r.set] + (size_t)r.src * seg, (size_t)r.emit * sizeof(float), hipMemcpyDeviceToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(uv_dev + (size_t)r.row * seg, s->follow.ct_uv[r.set] + (size_t)r.src * seg, (size_t)r.emit * sizeof(float), hipMemcpyDeviceToDevice, st));
+  copy_last_rows(s->follow.last, f0_dev, n, seg, s->follow.ct_f0, seg, 0, st);
+  copy_last_rows(s->follow.last, uv_dev, n, seg, s->follow.ct_uv, seg, 0, st);
+}
+
+void WavStage::plan(const conan_streams* s, const WavCall& c) {
+  if (s->follow.n_on < 1) return;
+  const double sr = 50.0 * c.hop;
+  for (int i = 0; i < c.n; ++i) {
+    if (!s->follow.on(c.slots[i])) continue;
+    if (c.mel.sample_rate != 50 * c.hop) throw Error(CONAN_ERR_INVALID, c.who + ": slot " + std::to_string(c.slots[i]) + " follows the source pitch: conan_mel_cfg.sample_rate must be 50 * hop_size");
+    check_cfg(s->follow.cfg[c.slots[i]], sr, c.N, c.who.c_str());
   }
+  group.assign(c.groups.size(), 0);
+  c.each_chunk_row([&](int g, int, int i, int at) {
+    const int slot = c.slots[i];
+    if (!s->follow.on(slot)) return;
+    const FePlan& p = c.pl[i];
+    if (p.R - std::max(0ll, (long long)p.pos * c.hop - c.N / 2) > s->wav_in.fe_LA)
+      throw Error(CONAN_ERR_UNSUPPORTED, c.who + ": slot " + std::to_string(slot) + " follows the source pitch: the chunk's frames have left the audio ring at this fft_size");
+    cnk::F0Row r = row(s->follow.cfg[slot], sr);
+    r.src_off = (long long)slot * s->wav_in.fe_LA; r.valid = p.R; r.mask = s->wav_in.fe_LA - 1;
+    r.f_first = p.pos; r.nframes = p.emit; r.job0 = jobs; r.out_off = at * c.seg;
+    jobs += p.emit;
+    flops += 3.0 * r.nframes * (double)(c.N - r.tmax - 1) * (r.tmax + 2);
+    rows.push_back(r);
+    last.push_back({i, 0, at, p.emit});
+    group[g] = 1;
+    if (s->reg.on(slot)) reg_rows.push_back(reg::wav_row(s, slot, r.out_off, p.emit));
+  });
+}
+
+// the tracker, behind the front-end launch: the call's samples are in the audio rings
+void WavStage::enqueue(conan_streams* s, const WavCall& c, hipStream_t cst, FrontWork& front, std::vector<conan_streams::OutPlan>&) {
+  if (rows.empty()) return;
+  q = s->follow.sets.begin(rows.data(), (int)rows.size(), cst);
+  for (LastRow& r : last) r.set = q;
+  ct_f0 = s->follow.ct_f0[q]; ct_uv = s->follow.ct_uv[q];
+  cnk::F0Args a;
+  memset(&a, 0, sizeof(a));
+  a.src = s->wav_in.fe_audio; a.out_f0 = s->follow.ct_f0[q]; a.out_uv = s->follow.ct_uv[q];
+  a.tab = s->follow.sets.rows[q]; a.rows = (int)rows.size(); a.jobs = jobs; a.n_fft = c.N; a.hop = c.hop; a.sr = 50.0 * c.hop;
+  front.at[kFrF0] = [s, a, flops = flops](hipStream_t st) { s->profiled("f0_yin_kernel", flops, st, [&] { cnk::launch_f0(a, st); }); };
+  reg::wav_enqueue(s, reg_rows, q, cst, front);
+}
+
+void WavStage::commit(conan_streams* s, hipStream_t dec, hipStream_t) {
+  if (!rows.empty()) s->follow.sets.end(q, dec);      // (behind the call's last decoder step, the contour's last reader)
+  s->follow.last = std::move(last);
+  reg::wav_commit(s, reg_rows);
 }
 
 }  // namespace f0
@@ -218,5 +243,5 @@ void conan_streams::follow_init() {
   const size_t floats = (size_t)max_slots * ctx->cfg.emf_segment;
   for (int q = 0; q < kStageSets; ++q) { follow.ct_f0[q] = alloc(floats); follow.ct_uv[q] = alloc(floats); }      // (counted by state_bytes)
   follow.sets.init(max_slots, allocs);
-  follow.cfg.assign(max_slots, conan_f0_cfg{});
+  follow.assign(max_slots);
 }

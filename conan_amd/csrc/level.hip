@@ -1,12 +1,13 @@
 // Streaming leveller (conan_level, conan_streams_set_input_level): the causal BS.1770 leveller that include/conan_hip.h defines
 // (conan_level_cfg).  The plan is in kernels.h (LvState, LvCall); lv_chunk is the one routine that level_stream_kernel (a wav-in
 // call's rows) and level_signal_kernel (whole signals, one update interval at a time) both call, so the two agree bit for bit.
-// The host side of the streaming form is wavio.hip's; conan_ctx_level below is conan_level's body.
+// The host side of the streaming form follows the kernels (the setter, the query and level::WavStage, the leveller's part of a wav-in
+// call); conan_ctx_level below is conan_level's body.
 #include <climits>
 #include <cmath>
 
-#include "host_common.h"
 #include "level_dev.h"
+#include "streams.h"
 
 namespace cnk {
 
@@ -153,7 +154,93 @@ cnk::LvCall plan_call(long long pos0, int m, int U, double fs) {
   return c;
 }
 
+void check_common(const conan_streams* s, const int32_t* slots, int n, const std::string& who) {
+  for (int i = 1; i < n && s->in_lv.n_on > 0; ++i) {
+    const conan_level_cfg &l0 = s->in_lv.cfg[slots[0]], &l = s->in_lv.cfg[slots[i]];
+    if (l.enabled != l0.enabled || (l.enabled && memcmp(&l, &l0, sizeof(l))))
+      throw Error(CONAN_ERR_INVALID, who + ": the slots of one call must share one input level configuration (conan_streams_set_input_level)");
+  }
+}
+
+void set_input_level(conan_streams* s, const int32_t* slots, int n, const conan_level_cfg* cfg) {
+  if (!s || !slots || !cfg) throw Error(CONAN_ERR_INVALID, "null argument");
+  check_cfg(*cfg, "conan_streams_set_input_level");
+  if (!s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, "conan_streams_set_input_level: the stream-set has no streaming front-end (all three models)");
+  wavio::check_slot_list(s, slots, n);
+  cnk::LvFilter f;
+  if (cfg->enabled) f = filter(s->ctx, "conan_streams_set_input_level");
+  wavio::check_utterance_start(s, slots, n, "conan_streams_set_input_level");
+  if (!cfg->enabled && !s->in_lv.allocated()) return;      // a stream-set that never had a leveller: nothing to allocate
+  if (cfg->enabled) {
+    HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+    s->level_init(f);
+  }
+  s->in_lv.store(slots, n, *cfg);
+}
+
+void input_level(conan_streams* s, const int32_t* slots, int n, double* stats_dev, void* stream) {
+  if (!s || !slots || !stats_dev) throw Error(CONAN_ERR_INVALID, "null argument");
+  wavio::check_slot_list(s, slots, n);
+  std::vector<cnk::LvRow> rows((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    if (!s->in_lv.on(slots[i])) throw Error(CONAN_ERR_STATE, "conan_streams_input_level: slot " + std::to_string(slots[i]) + " has no leveller (conan_streams_set_input_level)");
+    memset(&rows[i], 0, sizeof(cnk::LvRow));
+    rows[i].cfg = kernel_cfg(s->in_lv.cfg[slots[i]]);
+    rows[i].slot = slots[i]; rows[i].row = i; rows[i].fresh = s->wav_in.fe_slot[slots[i]].recv == 0;
+  }
+  hipStream_t st = s->enter(stream);
+  const int q = s->in_lv.sets.begin(rows.data(), n, st);
+  cnk::LevelStatsArgs a;
+  a.state = s->in_lv.state; a.state_stride = s->in_lv.stride; a.rows = s->in_lv.sets.rows[q]; a.n = n; a.out = stats_dev;
+  cnk::launch_level_stats(a, st);
+  HIP_CHECK(hipGetLastError());
+  s->in_lv.sets.end(q, st);
+}
+
+void WavStage::plan(const conan_streams* s, const WavCall& c) {
+  bool any = false;
+  for (int i = 0; i < c.n && s->in_lv.n_on > 0; ++i) any = any || (s->in_lv.on(c.slots[i]) && c.samples[i] > 0);
+  stages = any && !c.rs_launch;
+  for (int i = 0; i < c.n && any; ++i) {
+    const bool on = s->in_lv.on(c.slots[i]);
+    if (c.samples[i] < 1 || (!on && !stages)) continue;
+    cnk::LvRow R;
+    memset(&R, 0, sizeof(R));
+    if (on) {
+      R.c = plan_call(s->wav_in.fe_slot[c.slots[i]].recv, c.samples[i], s->in_lv.filter.U, 50.0 * c.hop);
+      R.cfg = kernel_cfg(s->in_lv.cfg[c.slots[i]]);
+    } else {
+      R.c.m = c.samples[i]; R.copy = 1;
+    }
+    R.slot = c.slots[i]; R.row = i;
+    rows.push_back(R);
+  }
+}
+
+// the leveller, between the resampler's launch (or the caller's rows) and the front-end's, which is the last reader of its rows
+void WavStage::enqueue(conan_streams* s, const WavCall& c, hipStream_t cst, FrontWork& front, std::vector<conan_streams::OutPlan>&) {
+  if (rows.empty()) return;
+  const int q = s->in_lv.sets.begin(rows.data(), (int)rows.size(), cst);
+  cnk::LevelStreamArgs a;
+  a.y = s->wav_in.rs_wav[c.rs_q]; a.y_ld = c.common ? c.samples[0] : c.seg * c.hop;
+  a.x = stages ? c.wav_dev : a.y; a.x_ld = stages ? c.wav_ld : a.y_ld;
+  a.state = s->in_lv.state; a.state_stride = s->in_lv.stride; a.zcap = CONAN_LEVEL_MAX_BLOCKS + cnk::kLvRingPad;
+  a.rows = s->in_lv.sets.rows[q]; a.n = (int)rows.size(); a.f = s->in_lv.filter;
+  front.at[kFrLevel] = [s, a](hipStream_t st) { s->profiled("level_stream_kernel", 0.0, st, [&] { cnk::launch_level_stream(a, st); }); };
+  front.at[kFrLevelEnd] = [s, q](hipStream_t st) { s->in_lv.sets.end(q, st); };
+}
+
 }  // namespace level
+
+void conan_streams::level_init(const cnk::LvFilter& f) {
+  rs_stage_init();
+  if (in_lv.state) return;
+  in_lv.filter = f;
+  in_lv.stride = (long long)cnk::lv_state_bytes(CONAN_LEVEL_MAX_BLOCKS + cnk::kLvRingPad);
+  in_lv.state = reinterpret_cast<char*>(alloc((size_t)max_slots * in_lv.stride / sizeof(float)));        // stream state (state_bytes)
+  in_lv.sets.init(max_slots, allocs);
+  in_lv.assign(max_slots);
+}
 
 void conan_ctx_level(conan_ctx* ctx, const conan_level_cfg& c, const float* x, int64_t x_ld, int n, const int64_t* samples, float* y, int64_t y_ld,
                      double* trace, int64_t trace_ld, hipStream_t st) {

@@ -149,27 +149,13 @@ void set_level(conan_streams* s, const int32_t* slots, int n, const conan_level_
     if (s->wav_out.voc_samples[slots[i]] != 0)
       throw Error(CONAN_ERR_STATE, "conan_streams_set_output_level: slot " + std::to_string(slots[i]) +
                                        " is not at the start of its vocoder stream (reset it with CONAN_MODEL_HIFIGAN first, or seed it)");
-  if (!cfg->enabled && s->out_lv.cfg.empty()) return;      // a stream-set that never levelled: nothing to allocate, nothing to write
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  hipStream_t st = (hipStream_t)stream;
-  s->join(st);      // (rows of pipelined steps in flight were built from the old setting, and their meters write the state)
+  if (!cfg->enabled && !s->out_lv.allocated()) return;      // a stream-set that never levelled: nothing to allocate, nothing to write
+  hipStream_t st = s->enter(stream);      // (rows of pipelined steps in flight were built from the old setting, and their meters write the state)
   if (cfg->enabled) s->out_level_init(f);
-  conan_level_cfg c = *cfg;
-  if (!c.enabled) memset(&c, 0, sizeof(c));
-  for (int i = 0; i < n; ++i) {
-    s->out_lv.n_on += c.enabled - s->out_lv.cfg[slots[i]].enabled;
-    s->out_lv.cfg[slots[i]] = c;
-    if (c.enabled && seed_dev)
-      HIP_CHECK(hipMemcpyAsync(s->out_lv.state + (size_t)slots[i] * s->out_lv.stride, static_cast<const char*>(seed_dev) + (size_t)i * seed_ld, (size_t)bytes,
-                               hipMemcpyDeviceToDevice, st));
-  }
-}
-
-void get_level(const conan_streams* s, int slot, conan_level_cfg* out) {
-  if (!s || !out) throw Error(CONAN_ERR_INVALID, "null argument");
-  if (slot < 0 || slot >= s->max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
-  if (s->out_lv.cfg.empty()) memset(out, 0, sizeof(*out));
-  else *out = s->out_lv.cfg[slot];
+  s->out_lv.store(slots, n, *cfg);
+  for (int i = 0; i < n && cfg->enabled && seed_dev; ++i)
+    HIP_CHECK(hipMemcpyAsync(s->out_lv.state + (size_t)slots[i] * s->out_lv.stride, static_cast<const char*>(seed_dev) + (size_t)i * seed_ld, (size_t)bytes,
+                             hipMemcpyDeviceToDevice, st));
 }
 
 void stats(conan_streams* s, const int32_t* slots, int n, double* stats_dev, void* stream) {
@@ -184,9 +170,7 @@ void stats(conan_streams* s, const int32_t* slots, int n, double* stats_dev, voi
     // after a whole row the meter has already formed the NEXT instant's stats: the reading is the one it kept as prev
     rows[i].c.pos0 = pos; rows[i].slot = slots[i]; rows[i].on = 1; rows[i].prev = pos % s->out_lv.filter.U == 0; rows[i].state_row = i;
   }
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  hipStream_t st = (hipStream_t)stream;
-  s->join(st);
+  hipStream_t st = s->enter(stream);
   const int q = s->out_lv.sets.begin(rows.data(), n, st);
   cnk::LevelOutStatsArgs a;
   a.state = s->out_lv.state; a.state_stride = s->out_lv.stride; a.zcap = kZcap; a.tab = s->out_lv.sets.rows[q]; a.n = n; a.out = stats_dev;
@@ -203,9 +187,7 @@ void state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64
     throw Error(CONAN_ERR_INVALID, "conan_streams_output_level_state: rows are conan_streams_output_level_state_bytes bytes, 8-byte aligned, ld apart");
   for (int i = 0; i < n; ++i)
     if (!s->out_lv.on(slots[i])) throw Error(CONAN_ERR_STATE, "conan_streams_output_level_state: slot " + std::to_string(slots[i]) + " has no leveller (conan_streams_set_output_level)");
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  hipStream_t st = (hipStream_t)stream;
-  s->join(st);
+  hipStream_t st = s->enter(stream);
   for (int i = 0; i < n; ++i)
     HIP_CHECK(hipMemcpyAsync(static_cast<char*>(state_dev) + (size_t)i * ld, s->out_lv.state + (size_t)slots[i] * s->out_lv.stride, (size_t)bytes,
                              hipMemcpyDeviceToDevice, st));
@@ -221,5 +203,5 @@ void conan_streams::out_level_init(const cnk::LvFilter& f) {
   for (int q = 0; q < kActSets; ++q) out_lv.stage[q] = alloc((size_t)max_slots * f.U);
   out_lv.sets.init(max_slots, allocs);
   state_bytes += (int64_t)kActSets * max_slots * sizeof(cnk::OlRow);
-  out_lv.cfg.assign(max_slots, conan_level_cfg{});
+  out_lv.assign(max_slots);
 }

@@ -1,6 +1,6 @@
 // Register matching for pitch following (include/conan_hip.h, conan_register_cfg): the kernel that rewrites a tracked contour with the
 // causal log-f0 mean transform, the whole-signal entry point conan_f0_register and the host side of conan_streams_set_pitch_register.
-// The wav-in steps launch the kernel behind the tracker's launch on the rows of the call's contour staging (wavio.hip), so the decoder
+// The wav-in steps launch the kernel behind the tracker's launch on the rows of the call's contour staging (reg::wav_enqueue below), so the decoder
 // step reads matched values through PitchHeadArgs::trk_f0 / trk_uv.
 #include <climits>
 #include <cmath>
@@ -135,46 +135,17 @@ void whole(conan_ctx* ctx, const conan_register_cfg* cfg, const float* f0_dev, c
 void set_register(conan_streams* s, const int32_t* slots, int n, const conan_register_cfg* cfg, void* stream) {
   if (!s || !slots || !cfg) throw Error(CONAN_ERR_INVALID, "null argument");
   check_cfg(*cfg, "conan_streams_set_pitch_register");      // (before the handle is touched, before any GPU use)
-  if (!s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, "conan_streams_set_pitch_register: the stream-set has no streaming front-end (all three models)");
-  wavio::check_slot_list(s, slots, n);
-  if (!cfg->enabled && s->reg.cfg.empty()) return;      // a stream-set that never matched: nothing to allocate, nothing to write
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  s->join((hipStream_t)stream);      // (rows of pipelined calls in flight were built from the old setting)
+  if (!wavio::begin_setter(s, slots, n, cfg->enabled != 0, s->reg.allocated(), "conan_streams_set_pitch_register", stream)) return;
   s->register_init();
-  conan_register_cfg c = *cfg;
-  if (!c.enabled) memset(&c, 0, sizeof(c));
-  const bool reseed = c.reseed != 0;
-  c.reseed = 0;
-  for (int i = 0; i < n; ++i) {
-    conan_register_cfg& o = s->reg.cfg[slots[i]];
-    s->reg.n_on += c.enabled - o.enabled;
-    if (c.enabled && (reseed || !o.enabled)) s->reg.pending[slots[i]] = 1;      // the restart travels in the slot's next register row
-    o = c;
-  }
-}
-
-void get_register(const conan_streams* s, int slot, conan_register_cfg* out) {
-  if (!s || !out) throw Error(CONAN_ERR_INVALID, "null argument");
-  if (slot < 0 || slot >= s->max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
-  if (!s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, "conan_streams_pitch_register: the stream-set has no streaming front-end (all three models)");
-  if (s->reg.cfg.empty()) memset(out, 0, sizeof(*out));
-  else *out = s->reg.cfg[slot];
+  s->reg.store_restarting(slots, n, *cfg);      // the restart travels in the slot's next register row
 }
 
 // rows without frames: a pending slot's row starts from the seed and names no slot, any other reads its state (and writes it back as it is)
 void state(conan_streams* s, const int32_t* slots, int n, int64_t* state_dev, void* stream) {
   if (!s || !slots || !state_dev) throw Error(CONAN_ERR_INVALID, "null argument");
   wavio::check_slot_list(s, slots, n);
-  std::vector<cnk::RegRow> rows((size_t)n);
-  for (int i = 0; i < n; ++i) {
-    if (!s->reg.on(slots[i])) throw Error(CONAN_ERR_STATE, "conan_streams_pitch_register_state: slot " + std::to_string(slots[i]) + " has no register matching (conan_streams_set_pitch_register)");
-    rows[i] = row(s->reg.cfg[slots[i]]);
-    rows[i].state_row = i;
-    if (!s->reg.pending[slots[i]]) { rows[i].slot = slots[i]; rows[i].reseed = 0; }
-  }
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  hipStream_t st = (hipStream_t)stream;
-  s->join(st);
+  const std::vector<cnk::RegRow> rows = s->reg.state_rows<cnk::RegRow>(slots, n, row, "conan_streams_pitch_register_state", " has no register matching (conan_streams_set_pitch_register)");
+  hipStream_t st = s->enter(stream);
   const int q = s->reg.sets.begin(rows.data(), n, st);
   cnk::RegArgs a;
   memset(&a, 0, sizeof(a));
@@ -184,6 +155,30 @@ void state(conan_streams* s, const int32_t* slots, int n, int64_t* state_dev, vo
   s->reg.sets.end(q, st);
 }
 
+cnk::RegRow wav_row(const conan_streams* s, int slot, long long off, int nframes) {
+  cnk::RegRow r = row(s->reg.cfg[slot]);
+  r.in_off = off; r.out_off = off; r.nframes = nframes; r.slot = slot; r.reseed = s->reg.pending[slot];
+  return r;
+}
+
+// directly behind the tracker: the decoder stage reads the matched rows
+void wav_enqueue(conan_streams* s, const std::vector<cnk::RegRow>& rows, int contour_set, hipStream_t cst, FrontWork& front) {
+  if (rows.empty()) return;
+  const int q = s->reg.sets.begin(rows.data(), (int)rows.size(), cst);
+  cnk::RegArgs a;
+  memset(&a, 0, sizeof(a));
+  a.f0 = s->follow.ct_f0[contour_set]; a.uv = s->follow.ct_uv[contour_set]; a.out = s->follow.ct_f0[contour_set]; a.state = s->reg.state;
+  a.tab = s->reg.sets.rows[q]; a.rows = (int)rows.size();
+  front.at[kFrRegister] = [s, a, q](hipStream_t st) {
+    s->profiled("f0_register_kernel", 0.0, st, [&] { cnk::launch_f0_register(a, st); });
+    s->reg.sets.end(q, st);
+  };
+}
+
+void wav_commit(conan_streams* s, const std::vector<cnk::RegRow>& rows) {
+  for (const cnk::RegRow& r : rows) s->reg.pending[r.slot] = 0;      // (the rows carried the restarts)
+}
+
 }  // namespace reg
 
 void conan_streams::register_init() {
@@ -191,6 +186,5 @@ void conan_streams::register_init() {
   reg.state = reinterpret_cast<long long*>(alloc((size_t)max_slots * 4));      // 16 bytes per slot, zeroed (counted by state_bytes)
   reg.sets.init(max_slots, allocs);
   state_bytes += (int64_t)kStageSets * max_slots * sizeof(cnk::RegRow);
-  reg.cfg.assign(max_slots, conan_register_cfg{});
-  reg.pending.assign(max_slots, 0);
+  reg.assign(max_slots);
 }

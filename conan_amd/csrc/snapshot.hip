@@ -100,7 +100,7 @@ int present_of(const conan_streams* s, int slot) {
   }
   if (!s->wav_in.rs_slot.empty() && s->wav_in.rs_slot[slot].f) p |= (1 << snap::SEC_RS_IN) | (1 << snap::SEC_FE);
   if (!s->wav_out.or_slot.empty() && s->wav_out.or_slot[slot].f) p |= 1 << snap::SEC_RS_OUT;
-  if (s->wav_in.levelled(slot)) p |= 1 << snap::SEC_LEVEL;
+  if (s->in_lv.on(slot)) p |= 1 << snap::SEC_LEVEL;
   return p;
 }
 
@@ -117,7 +117,7 @@ void check_blob(const void* blob, int64_t ld, const char* who) {
 // its id) whether or not this stream-set has allocated them yet.
 void conan_streams::snapshot_build() {
   Snap& sn = snapshot;
-  if (sn.lay_ok && sn.lay_rs == wav_in.rs_ring && sn.lay_or == wav_out.or_ring && sn.lay_lv == wav_in.lv_state) return;
+  if (sn.lay_ok && sn.lay_rs == wav_in.rs_ring && sn.lay_or == wav_out.or_ring && sn.lay_lv == in_lv.state) return;
   snap::Layout l;
   const conan_cfg& c = ctx->cfg;
   int* pos_arr[3] = {pos_emf, pos_dec, pos_voc};
@@ -149,14 +149,14 @@ void conan_streams::snapshot_build() {
   }
   if (wav_in.fe_audio) {      // the leveller's block (not part of the id: snapshot_layout.h)
     const long long lv_bytes = (long long)cnk::lv_state_bytes(CONAN_LEVEL_MAX_BLOCKS + cnk::kLvRingPad);
-    snap::add_whole(l, wav_in.lv_state, lv_bytes, (int)lv_bytes, snap::SEC_LEVEL);
+    snap::add_whole(l, in_lv.state, lv_bytes, (int)lv_bytes, snap::SEC_LEVEL);
   }
   for (int sec = 1; sec < snap::SEC_COUNT; ++sec) if (l.sec_end[sec] == 0) l.sec_end[sec] = l.sec_end[sec - 1];
   const int32_t words[] = {(int32_t)kVersion, c.models, c.hidden_size, c.num_mels, c.emf_input_dim, c.emf_layers, c.emf_segment, c.emf_left_context,
                            c.emf_right_context, c.emf_max_memory_size, c.voc_upsample, c.voc_resblock, ctx->hop, rb_limb ? 2 : 1, S_max};
   snap::finish(l, words, (int)(sizeof(words) / sizeof(words[0])));
   sn.layout = std::move(l);
-  sn.lay_ok = true; sn.lay_rs = wav_in.rs_ring; sn.lay_or = wav_out.or_ring; sn.lay_lv = wav_in.lv_state;
+  sn.lay_ok = true; sn.lay_rs = wav_in.rs_ring; sn.lay_or = wav_out.or_ring; sn.lay_lv = in_lv.state;
   sn.built = false;      // (the device tables follow on the next export / import)
 }
 
@@ -204,7 +204,7 @@ void export_slots(conan_streams* s, const int32_t* slots, int n, void* blob_dev,
       m.or_out = o.out; m.or_flushed = o.flushed;
       if (o.f) m.out_cfg = s->snapshot.out_cfg[slot];
     }
-    if (s->wav_in.levelled(slot)) m.lv = s->wav_in.lv_cfg[slot];
+    if (s->in_lv.on(slot)) m.lv = s->in_lv.cfg[slot];
     if (!s->pt_cfg.empty() && s->pt_cfg[slot].enabled) m.pt = s->pt_cfg[slot];
     m.checksum = meta_sum(m);
     memcpy(&meta[i], &m, sizeof(m));
@@ -285,10 +285,7 @@ void import_slots(conan_streams* s, const int32_t* slots, int n, const void* blo
       s->snapshot.in_cfg.resize(s->max_slots, conan_resample_cfg{});
       s->snapshot.in_cfg[slot] = m.in_cfg;
     }
-    if (!s->wav_in.lv_cfg.empty()) {      // (a record without a leveller turns the slot's off)
-      s->wav_in.lv_n += (m.lv.enabled != 0) - (s->wav_in.lv_cfg[slot].enabled != 0);
-      s->wav_in.lv_cfg[slot] = m.lv;
-    }
+    if (s->in_lv.allocated()) s->in_lv.store(&slot, 1, m.lv);      // (a record without a leveller turns the slot's off)
     if (!s->wav_out.or_slot.empty()) {
       s->wav_out.or_slot[slot] = conan_streams::OrSlot{tout[i], m.or_out, m.or_flushed};
       s->snapshot.out_cfg.resize(s->max_slots, conan_resample_cfg{});

@@ -103,6 +103,62 @@ struct StageSets {
   ~StageSets() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
+// ---- the per-slot source features (level.hip, f0.hip, register.hip, activity.hip, bypass.hip, conceal.hip, level_out.hip) share one
+// slot-setting type.  cfg: per slot the configuration as set (zeros: off; `reseed` kept 0), which persists across resets; n_on: slots
+// with the feature on (On: the cfg field that says so).  Empty until the feature's first enabling call (assign(), from its *_init()
+// beside the device state and row tables).  pending: the slot's state restarts in its next kernel row, which clears the flag - a host
+// flag, no launch; restart() sets it (a reset with CONAN_MODEL_FRONTEND), and when a setter call does is each feature's own rule.
+template <typename Cfg, int32_t Cfg::*On = &Cfg::enabled>
+struct SlotSetting {
+  std::vector<Cfg> cfg;
+  std::vector<char> pending;
+  int n_on = 0;
+  bool allocated() const { return !cfg.empty(); }
+  bool on(int slot) const { return n_on > 0 && cfg[slot].*On != 0; }
+  void assign(int max_slots) { cfg.assign(max_slots, Cfg{}); pending.assign(max_slots, 0); }
+  // c (zeros where it turns the feature off) -> the listed slots; went_on(i) for each list entry whose slot was off and is on now
+  template <typename F>
+  void store(const int32_t* slots, int n, const Cfg& c, F&& went_on) {
+    Cfg v = c;
+    if (!(c.*On)) memset(&v, 0, sizeof(v));
+    for (int i = 0; i < n; ++i) {
+      Cfg& o = cfg[slots[i]];
+      const bool was = o.*On != 0;
+      n_on += (v.*On != 0) - was;
+      o = v;
+      if (v.*On && !was) went_on(i);
+    }
+  }
+  void store(const int32_t* slots, int n, const Cfg& c) { store(slots, n, c, [](int) {}); }
+  // the rule of a cfg with a `reseed` field: a reseeding call and an off-to-on change restart the slot
+  void store_restarting(const int32_t* slots, int n, Cfg c) {
+    const bool reseed = c.*On && c.reseed != 0;
+    c.reseed = 0;
+    store(slots, n, c, [&](int i) { pending[slots[i]] = 1; });
+    for (int i = 0; i < n && reseed; ++i) pending[slots[i]] = 1;
+  }
+  void restart(const int32_t* slots, int n) { for (int i = 0; i < n && allocated(); ++i) pending[slots[i]] = 1; }
+  // the zero-frame rows of a state query (make: the feature's row(), which starts from the seed and names no slot): row i reports to
+  // state_row i; a slot that is not pending reads its state (and writes it back as it is).  missing: the error's text behind the slot
+  template <typename Row, typename Make>
+  std::vector<Row> state_rows(const int32_t* slots, int n, Make make, const char* who, const char* missing) const {
+    std::vector<Row> rows((size_t)n);
+    for (int i = 0; i < n; ++i) {
+      if (!on(slots[i])) throw Error(CONAN_ERR_STATE, std::string(who) + ": slot " + std::to_string(slots[i]) + missing);
+      rows[i] = make(cfg[slots[i]]);
+      rows[i].state_row = i;
+      if (!pending[slots[i]]) { rows[i].slot = slots[i]; rows[i].reseed = 0; }
+    }
+    return rows;
+  }
+  void get(int slot, Cfg* out) const {
+    if (allocated()) *out = cfg[slot];
+    else memset(out, 0, sizeof(*out));
+  }
+};
+// A row of a feature's most recent wav-in call, for the conan_step_wav_* hooks: call row, the staging set, the chunk row there, frames
+struct LastRow { int row, set, src, emit; };
+
 struct conan_streams {
   conan_ctx* ctx = nullptr;
   std::atomic<int>* live = nullptr;            // this device's count of live stream-sets (device_live_streams)
@@ -190,110 +246,75 @@ struct conan_streams {
     // launch is today's).
     std::vector<unsigned char> in_fmt;
     int in_fmt_n = 0;
-    // input leveller (conan_streams_set_input_level; level.hip): per slot its cfg (enabled = 0: none), which persists across resets;
-    // lv_n: slots with one.  The first enabling call allocates the per-slot state ([max_slots] of lv_stride bytes: cnk::LvState and
-    // the two block rings; stream state) and, per call, a row table (set q of lv_sets; the set's event follows the front-end launch).
-    // The kernel works in place on the resampler's staging rows (rs_wav), so such a stream-set has those too.
-    std::vector<conan_level_cfg> lv_cfg;
-    int lv_n = 0;
-    char* lv_state = nullptr; long long lv_stride = 0;
-    StageSets<cnk::LvRow> lv_sets;
-    cnk::LvFilter lv_filter;
-    bool levelled(int slot) const { return lv_n > 0 && lv_cfg[slot].enabled; }
   } wav_in;
-  void level_init(const cnk::LvFilter& f);      // the leveller's state and row tables (conan_streams_set_input_level)
-  // source-pitch following (conan_streams_set_pitch_follow; f0.hip): per slot its cfg (enabled = 0: none), which persists across resets;
-  // n_on: slots with one.  The tracker keeps no state of its own: a wav-in call that emits a chunk tracks the chunk's frames from the
-  // slot's audio ring.  Per call a row table (set q of `sets`) and beside it the contour the call's decoder steps read, ct_f0 / ct_uv
-  // [q][chunk row][seg] (chunk row = the row's place in the call's emit groups, as fe_chunk); the set's event follows the last decoder
-  // step of the call, so the contour of a pipelined call outlives the front-ends of the calls behind it.  Allocated by the first
-  // enabling call; the contour sets count as stream state.  last: the rows of the most recent wav-in call that followed
-  // (conan_step_wav_contour).
-  struct Follow {
-    std::vector<conan_f0_cfg> cfg;
-    int n_on = 0;
+  // --- the per-slot source features: each a SlotSetting (above) with its device state, its per-call row tables (set q of `sets`) and
+  // the staging beside them, allocated by the first enabling call (*_init()).  What differs:
+  // input leveller (conan_streams_set_input_level; level.hip).  state: [max_slots] of `stride` bytes (cnk::LvState and the two block
+  // rings; stream state).  The kernel works in place on the resampler's staging rows (wav_in.rs_wav), so such a stream-set has those
+  // too.  Rows: the levelled call rows with samples (and copy rows, see level::WavStage).  Event: behind the front-end launch.
+  struct InLevel : SlotSetting<conan_level_cfg> {
+    char* state = nullptr; long long stride = 0;
+    StageSets<cnk::LvRow> sets;
+    cnk::LvFilter filter;
+  } in_lv;
+  void level_init(const cnk::LvFilter& f);
+  // source-pitch following (conan_streams_set_pitch_follow; f0.hip).  The tracker keeps no state: a wav-in call that emits a chunk
+  // tracks the chunk's frames from the slot's audio ring.  Rows: one per following call row that emits; beside the table the contour
+  // the call's decoder steps read, ct_f0 / ct_uv [q][chunk row][seg] (chunk row = the row's place in the call's emit groups, as
+  // fe_chunk; stream state).  Event: behind the last decoder step of the call, so the contour of a pipelined call outlives the
+  // front-ends of the calls behind it.  last: conan_step_wav_contour.
+  struct Follow : SlotSetting<conan_f0_cfg> {
     float* ct_f0[kStageSets] = {}; float* ct_uv[kStageSets] = {};
     StageSets<cnk::F0Row> sets;
-    struct LastRow { int row, set, src, emit; };
     std::vector<LastRow> last;
-    bool on(int slot) const { return n_on > 0 && cfg[slot].enabled; }
   } follow;
   void follow_init();
-  // register matching (conan_streams_set_pitch_register; register.hip): per slot its cfg as set (enabled = 0: none; reseed kept 0),
-  // which persists across resets; n_on: slots with one.  pending: the slot's estimate restarts from the cfg's seed in its next
-  // register row (set by an enabling or reseeding setter call and by a reset with CONAN_MODEL_FRONTEND; a host flag, no launch).
-  // state: [max_slots][2] = (n, S) on the device, read and written by the rows of f0_register_kernel in the order of the front-end
-  // launches.  Per call a row table (set q of `sets`; the set's event follows the kernel's launch).  Allocated by the first enabling
-  // call; state and row tables count as stream state.
-  struct Register {
-    std::vector<conan_register_cfg> cfg;
-    std::vector<char> pending;
-    int n_on = 0;
+  // register matching (conan_streams_set_pitch_register; register.hip).  state: [max_slots][2] = (n, S), read and written by the rows
+  // of f0_register_kernel in the order of the front-end launches; pending restarts it from the cfg's seed.  Rows: one per following
+  // row whose slot has the register on; it rewrites its place in the contour.  Event: behind the kernel's launch.
+  struct Register : SlotSetting<conan_register_cfg> {
     long long* state = nullptr;
     StageSets<cnk::RegRow> sets;
-    bool on(int slot) const { return n_on > 0 && cfg[slot].enabled; }
   } reg;
   void register_init();
-  // source activity (conan_streams_set_activity; activity.hip): per slot its cfg as set (mode = 0: none; reseed kept 0), which persists
-  // across resets; n_on: slots with one.  pending: the slot's state restarts from the cfg's seed in its next detector row (set by an
-  // enabling or reseeding setter call and by a reset with CONAN_MODEL_FRONTEND; a host flag, no launch).  state: [max_slots] on the
-  // device, read and written by the rows of activity_kernel in the order of the front-end launches.  Per call a row table (set q of
-  // `sets`: one row per emitting call row in chunk-row order, mode 0 for a slot without the feature) and beside it the flags
-  // [q][chunk row][seg] and the levels [q][chunk row][seg + 1] (word 0: the level before the chunk) on their way from the front-end
-  // stage to the vocoder stage of the same call, whose gate reads table and levels: the set's event is recorded on the stream of the
-  // call's last vocoder step, behind the gate launch, so under pipelining a set outlives the front-ends of the calls behind it
-  // (kActSets sets, not kStageSets: see there).
-  // Allocated by the first enabling call; state, staging and row tables count as stream state.  last: the rows of the most recent
-  // wav-in call that detected (conan_step_wav_activity).
-  struct Activity {
-    std::vector<conan_activity_cfg> cfg;
-    std::vector<char> pending;
-    int n_on = 0;
+  // source activity (conan_streams_set_activity; activity.hip; on: mode != 0).  state: [max_slots], read and written by the rows of
+  // activity_kernel in the order of the front-end launches; pending restarts it from the cfg's seed.  Rows: one per emitting call row
+  // in chunk-row order, mode 0 for a slot without the feature; beside the table the flags [q][chunk row][seg] and the levels
+  // [q][chunk row][seg + 1] (word 0: the level before the chunk) on their way from the front-end stage to the vocoder stage of the
+  // same call, whose gate reads table and levels.  Event: on the stream of the call's last vocoder step, behind the gate launch, so
+  // under pipelining a set outlives the front-ends of the calls behind it (kActSets sets, not kStageSets: see there).
+  // last: conan_step_wav_activity.
+  struct Activity : SlotSetting<conan_activity_cfg, &conan_activity_cfg::mode> {
     cnk::ActState* state = nullptr;
     int* flags[kActSets] = {}; int* levels[kActSets] = {};
     StageSets<cnk::ActRow, kActSets> sets;
-    struct LastRow { int row, set, src, emit; };
     std::vector<LastRow> last;
-    bool on(int slot) const { return n_on > 0 && cfg[slot].mode != 0; }
   } act;
   void activity_init();
-  // source bypass (conan_streams_set_bypass; bypass.hip): per slot its cfg as set (enabled = 0: none; reseed kept 0), which persists
-  // across resets; n_on: slots with one; pending: the slot's state restarts from the cfg's seed in its next stage row (as act.pending).
-  // state: [max_slots] on the device, read and written by the rows of bypass_stage_kernel in the order of the front-end launches.  Per
-  // call a row table (set q of `sets`: one row per emitting call row in chunk-row order, mode 0 for a slot without the feature) and
-  // beside it the wet and effective dry levels [q][chunk row][seg + 1] (word 0: the level before the chunk) and the dry samples
-  // [q][chunk row][seg * hop] on their way from the front-end stage to the vocoder stage of the same call.  The samples are staged, not
-  // read from the audio ring by the mix: under pipelining the vocoder runs several calls behind the front-end that overwrites the
-  // ring.  The set's event is recorded behind the call's last vocoder step; kActSets sets for the reason given there.  Allocated by the
-  // first enabling call; state, staging and row tables count as stream state.  last: the rows of the most recent wav-in call that
-  // mixed (conan_step_wav_bypass).
-  struct Bypass {
-    std::vector<conan_bypass_cfg> cfg;
-    std::vector<char> pending;
-    int n_on = 0;
+  // source bypass (conan_streams_set_bypass; bypass.hip).  state: [max_slots], read and written by the rows of bypass_stage_kernel in
+  // the order of the front-end launches; pending restarts it from the cfg's seed.  Rows: as the activity table's; beside the table
+  // the wet and effective dry levels [q][chunk row][seg + 1] (word 0: the level before the chunk) and the dry samples
+  // [q][chunk row][seg * hop] on their way to the vocoder stage of the same call.  The samples are staged, not read from the audio
+  // ring by the mix: under pipelining the vocoder runs several calls behind the front-end that overwrites the ring.  Event: behind
+  // the call's last vocoder step; kActSets sets for the reason given there.  last: conan_step_wav_bypass.
+  struct Bypass : SlotSetting<conan_bypass_cfg> {
     cnk::BypState* state = nullptr;
     int* wet_lvl[kActSets] = {}; int* dry_lvl[kActSets] = {}; float* dry[kActSets] = {};
     StageSets<cnk::BypRow, kActSets> sets;
-    struct LastRow { int row, set, src, emit; };
     std::vector<LastRow> last;
-    bool on(int slot) const { return n_on > 0 && cfg[slot].enabled; }
   } byp;
   void bypass_init();
-  // input loss concealment (conan_streams_set_conceal; conceal.hip): per slot its cfg as set (enabled = 0: none), which persists across
-  // resets; n_on: slots with one; pending: the slot's state restarts from zeros in its next repair row (set when a slot that was off
-  // is enabled and by a reset with CONAN_MODEL_FRONTEND; a host flag, no launch).  state: [max_slots] records of cnk::kConcStateBytes
-  // on the device, read and written by the rows of conceal_kernel in the order of the caller's stream.  Per repair call a row table
-  // (set q of `sets`; the set's event follows the kernel's launch).  No step path reads any of it: the repair works on the caller's
-  // rows in front of the step call.  Allocated by the first enabling call; state and row tables count as stream state.
-  struct Conceal {
-    std::vector<conan_conceal_cfg> cfg;
-    std::vector<char> pending;
-    int n_on = 0;
+  // input loss concealment (conan_streams_set_conceal; conceal.hip).  state: [max_slots] records of cnk::kConcStateBytes, read and
+  // written by the rows of conceal_kernel in the order of the caller's stream; pending restarts it from zeros (set when a slot that
+  // was off is enabled without a seed; a seed clears it).  Rows: per repair call; event: behind the kernel's launch.  No step path
+  // reads any of it: the repair works on the caller's rows in front of the step call.
+  struct Conceal : SlotSetting<conan_conceal_cfg> {
     char* state = nullptr;
     StageSets<cnk::ConcRow> sets;
-    bool on(int slot) const { return n_on > 0 && cfg[slot].enabled; }
   } conc;
   void conceal_init();
+  // a reset with CONAN_MODEL_FRONTEND: the settings stay; the states restart in the slots' next rows (host flags: no launch)
+  void restart_features(const int32_t* slots, int n) { reg.restart(slots, n); act.restart(slots, n); byp.restart(slots, n); conc.restart(slots, n); }
   void ragged_init();
   void resample_init();        // staging, row tables and the history ring (conan_streams_set_input_rate)
   void rs_stage_init();        // staging and row tables only (conan_streams_set_input_format: no stream state)
@@ -316,8 +337,7 @@ struct conan_streams {
     std::vector<unsigned char> out_fmt;
     int out_fmt_n = 0;
   } wav_out;
-  // output leveller (conan_streams_set_output_level; level_out.hip): per slot its cfg as set (enabled = 0: none), which persists across
-  // resets; n_on: slots with one.  state: [max_slots] of `stride` bytes on the device (cnk::LvState, the two block rings, the previous
+  // output leveller (conan_streams_set_output_level; level_out.hip), a SlotSetting as the source features.  state: [max_slots] of `stride` bytes on the device (cnk::LvState, the two block rings, the previous
   // instant's stats), written by level_out_meter_kernel and read by the next step's level_out_apply_kernel in stream order.  The
   // restart of a reset with CONAN_MODEL_HIFIGAN needs no flag of its own: it returns voc_samples to 0, and a row at position 0
   // starts meter and gain in both kernels.  Per vocoder step with a levelled row a row table (set q of `sets`: one row per step row,
@@ -325,14 +345,11 @@ struct conan_streams {
   // samples for the meter - staged, not read from the step's rows, because the meter runs behind the apply, the gate and the mix,
   // which all work in place.  The set's event is recorded behind the meter launch.  Allocated by the first enabling call; state,
   // staging and row tables count as stream state.
-  struct OutLevel {
-    std::vector<conan_level_cfg> cfg;
-    int n_on = 0;
+  struct OutLevel : SlotSetting<conan_level_cfg> {
     char* state = nullptr; long long stride = 0;
     float* stage[kActSets] = {};
     StageSets<cnk::OlRow, kActSets> sets;
     cnk::LvFilter filter;
-    bool on(int slot) const { return n_on > 0 && cfg[slot].enabled; }
   } out_lv;
   void out_level_init(const cnk::LvFilter& f);
   void out_stage_init();
@@ -362,13 +379,15 @@ struct conan_streams {
     float* base = nullptr; long long ld = 0;
     int tiles = 1, win = 0;
     double flops = 0;
-    // the step's output gate (activity.hip; set by the wav-in step for a group with a gated row): the group's rows of the call's
+    // the step's output gate (activity.hip; filled by act::WavStage for a group with a gated row): the group's rows of the call's
     // activity table and of its level staging; hifigan_step launches activity_gate_kernel on the rows conv_post wrote
-    const cnk::ActRow* gate_tab = nullptr; const int* gate_lvl = nullptr; int gate_lvl_ld = 0;
-    // the step's wet/dry mix (bypass.hip; set by the wav-in step for a group with a bypass row): the group's rows of the call's bypass
+    struct Gate { const cnk::ActRow* tab = nullptr; const int* lvl = nullptr; int lvl_ld = 0; } gate;
+    // the step's wet/dry mix (bypass.hip; filled by byp::WavStage for a group with a bypass row): the group's rows of the call's bypass
     // table, of its level staging and of its dry staging; hifigan_step launches bypass_mix_kernel behind the gate
-    const cnk::BypRow* byp_tab = nullptr; const int* byp_wet_lvl = nullptr; const int* byp_dry_lvl = nullptr; const float* byp_dry = nullptr;
-    int byp_lvl_ld = 0; long long byp_dry_ld = 0;
+    struct Mix {
+      const cnk::BypRow* tab = nullptr; const int* wet_lvl = nullptr; const int* dry_lvl = nullptr; const float* dry = nullptr;
+      int lvl_ld = 0; long long dry_ld = 0;
+    } mix;
     // the step's output levelling (level_out.hip; out_plan's, for a step with a levelled row): one table row per step row;
     // hifigan_step launches level_out_apply_kernel behind conv_post and level_out_meter_kernel behind the step's last launch
     std::vector<cnk::OlRow> lvl_rows;
@@ -469,6 +488,8 @@ struct conan_streams {
   bool tl_on = false; int tl_n = 0;
   void async_init();
   void join(hipStream_t st);                   // make `st` wait for everything enqueued by conan_step_async
+  // what a stream-ordered entry point does once its arguments have passed: the device, check_fault(), join -> the stream
+  hipStream_t enter(void* stream) { HIP_CHECK(hipSetDevice(ctx->device)); check_fault(); join((hipStream_t)stream); return (hipStream_t)stream; }
 
   void mega_print_stamps();
   ~conan_streams() {
@@ -598,11 +619,86 @@ void step_pipelined(conan_streams* s, const int32_t* slots, int n, int emit, con
                     float* wav_out_dev, void* stream, const std::function<void(hipStream_t)>& pre, const conan_streams::OutPlan& op,
                     const float* trk_f0 = nullptr, const float* trk_uv = nullptr);
 
+// ---- the wav-in step and its call stages (wavio.hip: step_wav).  One slot's front-end plan for a call that gives it `samples` (model
+// rate) and `final_`.  Centred framing: frame f needs the samples up to f * hop + n_fft / 2 - 1, or the final call: every frame of
+// 1 + samples / hop, zero padding past the end.  R = samples received after the call, total = R once final (-1 before); frames [0, fc)
+// complete, [f0, f0 + nnew) of them new in this call; chunk t = chunks emitted so far starts at frame pos and is ready once frames
+// [pos, pos + seg + rc) are complete or - after the final call - any frame is left (emit frames, rows [0, real) backed by frames: the
+// short last chunks of engine.chunks, repeat-last padding).
+struct FePlan { long long R, total; int fc, f0, nnew, pos, emit, real; };
+// What step_wav has worked out before its features plan their part.  groups: the call rows per emit group, largest emit first; a row's
+// place in the groups in this order is its chunk row (as fe_chunk's).  rs_q: the resampler's staging set, once step_wav has taken it.
+struct WavCall {
+  const int32_t* slots; int n;
+  const std::vector<FePlan>& pl;
+  const std::vector<std::vector<int>>& groups;
+  int seg, hop, N;
+  const conan_mel_cfg& mel;
+  const std::string& who;
+  bool rs_launch; const int32_t* samples;      // the resampler's plan: it launches in this call; per row the samples the front-end gets
+  bool common; const float* wav_dev; long long wav_ld;
+  int rs_q = 0;
+  template <typename F> void each_group(F&& f) const {      // f(g, the group's first chunk row)
+    for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g) f(g, off);
+  }
+  template <typename F> void each_chunk_row(F&& f) const {      // f(g, k, call row, chunk row): row k of group g
+    each_group([&](int g, int off) { for (int k = 0; k < (int)groups[g].size(); ++k) f(g, k, groups[g][k], off + k); });
+  }
+  // one table row per emitting call row in chunk-row order: fill(g, call row, chunk row, r) writes the row of a slot with the feature
+  // (-> true); any other slot gets the row that holds its place (mode 0, slot -1, state_row -1)
+  template <typename Row, typename F> std::vector<Row> table_rows(F&& fill) const {
+    std::vector<Row> rows;
+    each_chunk_row([&](int g, int, int i, int at) {
+      Row r;
+      if (!fill(g, i, at, r)) { memset(&r, 0, sizeof(r)); r.slot = -1; r.state_row = -1; }
+      rows.push_back(r);
+    });
+    return rows;
+  }
+};
+// The front-end work of a wav-in call: at most one entry per position, run in this order on one stream (the caller's, or as
+// step_pipelined's `pre`).  The ...End entries record the events of the sets the mel front-end launch is the last to read.
+enum FrontPos { kFrResample, kFrLevel, kFrMel, kFrLevelEnd, kFrResampleEnd, kFrF0, kFrRegister, kFrActivity, kFrBypass, kFrCount };
+struct FrontWork {
+  std::function<void(hipStream_t)> at[kFrCount];
+  void run(hipStream_t st) const { for (const auto& f : at) if (f) f(st); }
+};
+// Each feature of the wav-in step has a per-call WavStage in its own file (level::, f0:: with reg::'s rows, act::, byp::), all of one
+// shape, called by step_wav in that order:
+//   plan      the call's host rows, per-group flags and FLOPs; throws on anything refused.  const with respect to the stream-set and
+//             run for every feature before any staging set is taken or any state changes: a refused call leaves everything as it was
+//   enqueue   takes the staging set on the caller's stream cst (sets.begin), adds the feature's launch to the front-end work and hands
+//             the groups' rows of table and staging to their vocoder steps' OutPlans
+//   commit    records the set's event where the front-end work does not (dec / last: the streams of the call's last decoder and vocoder
+//             step), clears pending for the rows that carried a restart and stores `last`
+// The body of the conan_step_wav_* hooks: zero the caller's [n][seg] rows, then each LastRow's emitted words from the staging of its
+// set (src_ld words per chunk row, the first at src_off)
+template <typename T>
+inline void copy_last_rows(const std::vector<LastRow>& last, T* dst_dev, int n, int seg, T* const* staging, int src_ld, int src_off, hipStream_t st) {
+  HIP_CHECK(hipMemsetAsync(dst_dev, 0, (size_t)n * seg * sizeof(T), st));
+  for (const LastRow& r : last)
+    HIP_CHECK(hipMemcpyAsync(dst_dev + (size_t)r.row * seg, staging[r.set] + (size_t)r.src * src_ld + src_off, (size_t)r.emit * sizeof(T), hipMemcpyDeviceToDevice, st));
+}
+
 // ---- waveform I/O host layer (wavio.hip): the bodies of api.hip's wav-in steps, rate / stride / format setters and output queries
 namespace wavio {
+// What the feature setters share behind their null and cfg checks, in this order: the streaming front-end, the slot list, the early
+// return (false) of a call that turns off what the stream-set never had, then enter() (rows in flight were built from the old setting)
+bool begin_setter(conan_streams* s, const int32_t* slots, int n, bool enabling, bool allocated, const char* who, void* stream);
+// a feature's getter (zeros where the stream-set never enabled it).  front_end_who: the entry point of a feature that needs the
+// streaming front-end (null: one that does not)
+template <typename Set, typename Cfg>
+void get_setting(const conan_streams* s, Set conan_streams::*set, int slot, Cfg* out, const char* front_end_who) {
+  if (!s || !out) throw Error(CONAN_ERR_INVALID, "null argument");
+  if (slot < 0 || slot >= s->max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
+  if (front_end_who && !s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, std::string(front_end_who) + ": the stream-set has no streaming front-end (all three models)");
+  (s->*set).get(slot, out);
+}
+hipStream_t begin_last_call(conan_streams* s, const char* who, void* stream);      // the conan_step_wav_* hooks: the no-call-yet check, enter()
 int bytes_per_sample(int fmt);      // of a CONAN_SAMPLE_* / cnk::kFmt* code
 void check_format(int format, const char* who);
 void check_slot_list(const conan_streams* s, const int32_t* slots, int n);      // count, range, duplicates
+void check_utterance_start(const conan_streams* s, const int32_t* slots, int n, const char* who);
 const ch::RsTable* rate_table(conan_streams* s, const conan_resample_cfg& c, const char* who);      // null at the model rate
 void store_format(std::vector<unsigned char>& fmt, int& not_f32, const int32_t* slots, int n, int format);
 void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, int n, const int32_t* in_samples, const int32_t* in_final, const float* wav_dev,
@@ -615,13 +711,28 @@ void set_input_rate(conan_streams* s, const int32_t* slots, int n, const conan_r
 void set_output_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg);
 void set_output_ld(conan_streams* s, int64_t ld);
 void set_input_format(conan_streams* s, const int32_t* slots, int n, int format);
-void set_input_level(conan_streams* s, const int32_t* slots, int n, const conan_level_cfg* cfg);
-void input_level(conan_streams* s, const int32_t* slots, int n, double* stats_dev, void* stream);
 void set_output_format(conan_streams* s, const int32_t* slots, int n, int format);
 int output_samples(conan_streams* s, int32_t* counts, int cap);      // -> rows of the most recent step call
 void output_pending(conan_streams* s, const int32_t* slots, int n, int32_t* counts);
 void flush_output(conan_streams* s, const int32_t* slots, int n, float* wav_out_dev, int64_t wav_ld, void* stream);
 }  // namespace wavio
+
+// ---- input leveller (level.hip): the kernel's host side and the bodies of api.hip's entry points
+namespace level {
+void check_common(const conan_streams* s, const int32_t* slots, int n, const std::string& who);      // conan_step_wav: one configuration per call
+void set_input_level(conan_streams* s, const int32_t* slots, int n, const conan_level_cfg* cfg);
+void input_level(conan_streams* s, const int32_t* slots, int n, double* stats_dev, void* stream);
+// The levelled slots that hand their front-end samples this call.  Behind a resampler launch the kernel works in place on the staged
+// rows; in a call without one (stages) it reads the caller's rows and writes the staging itself - step_wav takes the resampler's set
+// for it - so the call's unlevelled rows with samples ride along as copy rows and the front-end still finds every row in one place.
+struct WavStage {
+  std::vector<cnk::LvRow> rows;
+  bool stages = false;
+  void plan(const conan_streams* s, const WavCall& c);
+  void enqueue(conan_streams* s, const WavCall& c, hipStream_t cst, FrontWork& front, std::vector<conan_streams::OutPlan>& ops);
+  void commit(conan_streams*, hipStream_t, hipStream_t) {}      // (no host state; the set's event rides in the front-end work)
+};
+}  // namespace level
 
 // ---- slot snapshots (snapshot.hip): the bodies of api.hip's export / import entry points
 namespace snapshot {
@@ -658,8 +769,24 @@ cnk::F0Row row(const conan_f0_cfg& c, double sr);      // the cfg's fields of a 
 void whole(conan_ctx* ctx, const conan_mel_cfg* mel, const conan_f0_cfg* cfg, const float* wav_dev, int n, int samples, float* f0_out_dev, float* uv_out_dev,
            int32_t* frames_out, void* stream);
 void set_follow(conan_streams* s, const int32_t* slots, int n, const conan_f0_cfg* cfg, void* stream);
-void get_follow(const conan_streams* s, int slot, conan_f0_cfg* out);
 void contour(conan_streams* s, float* f0_dev, float* uv_dev, void* stream);
+// The following slots that emit have their chunk's frames tracked, from their audio rings, into the call's contour rows; every such
+// row whose slot has the register on also gets a register row (reg::wav_row), launched directly behind the tracker.
+struct WavStage {
+  std::vector<cnk::F0Row> rows;
+  std::vector<cnk::RegRow> reg_rows;
+  std::vector<LastRow> last;
+  std::vector<char> group;      // per emit group: a row of it follows (empty: none does)
+  int jobs = 0, q = 0;
+  double flops = 0.0;
+  const float* ct_f0 = nullptr; const float* ct_uv = nullptr;      // the call's contour set (enqueue)
+  // the contour rows of group g, whose first chunk row is off (null: no row of it follows, and the group's decoder keeps its program)
+  const float* trk_f0(int g, int off, int seg) const { return !group.empty() && group[g] ? ct_f0 + (size_t)off * seg : nullptr; }
+  const float* trk_uv(int g, int off, int seg) const { return !group.empty() && group[g] ? ct_uv + (size_t)off * seg : nullptr; }
+  void plan(const conan_streams* s, const WavCall& c);
+  void enqueue(conan_streams* s, const WavCall& c, hipStream_t cst, FrontWork& front, std::vector<conan_streams::OutPlan>& ops);
+  void commit(conan_streams* s, hipStream_t dec, hipStream_t last_st);
+};
 }  // namespace f0
 
 // ---- register matching (register.hip): the kernel's host side and the bodies of api.hip's entry points
@@ -669,8 +796,12 @@ cnk::RegRow row(const conan_register_cfg& c);      // the cfg's fields of a kern
 void whole(conan_ctx* ctx, const conan_register_cfg* cfg, const float* f0_dev, const float* uv_dev, int n, const int32_t* frames, int64_t ld,
            float* f0_out_dev, int64_t* state_out_dev, void* stream);
 void set_register(conan_streams* s, const int32_t* slots, int n, const conan_register_cfg* cfg, void* stream);
-void get_register(const conan_streams* s, int slot, conan_register_cfg* out);
 void state(conan_streams* s, const int32_t* slots, int n, int64_t* state_dev, void* stream);
+// the register's part of f0::WavStage: the row that rewrites `nframes` frames at `off` of the call's contour, carrying the slot's
+// pending restart; the launch behind the tracker's with its set's event; the restarts the rows carried
+cnk::RegRow wav_row(const conan_streams* s, int slot, long long off, int nframes);
+void wav_enqueue(conan_streams* s, const std::vector<cnk::RegRow>& rows, int contour_set, hipStream_t cst, FrontWork& front);
+void wav_commit(conan_streams* s, const std::vector<cnk::RegRow>& rows);
 }  // namespace reg
 
 // ---- source activity (activity.hip): the kernels' host side and the bodies of api.hip's entry points
@@ -683,9 +814,19 @@ void whole(conan_ctx* ctx, const conan_mel_cfg* mel, const conan_activity_cfg* c
 void gate(conan_ctx* ctx, int hop, const float* wav_dev, int n, int64_t samples, int64_t ld, const int32_t* level_dev, int64_t level_ld, int32_t start_level,
           float* out_dev, void* stream);
 void set_activity(conan_streams* s, const int32_t* slots, int n, const conan_activity_cfg* cfg, void* stream);
-void get_activity(const conan_streams* s, int slot, conan_activity_cfg* out);
 void state(conan_streams* s, const int32_t* slots, int n, conan_activity_state* state_dev, void* stream);
 void last_call(conan_streams* s, int32_t* act_dev, int32_t* level_dev, void* stream);
+// A call in which a slot with the detector emits has one table row per emitting call row (WavCall::table_rows), so that a group's
+// gate finds its rows by their place; the groups with a gated row take their rows of the table and of the level staging along.
+struct WavStage {
+  std::vector<cnk::ActRow> rows;
+  std::vector<LastRow> last;
+  std::vector<char> gate;       // per emit group: a row of it is gated (empty: no table)
+  int q = 0;
+  void plan(const conan_streams* s, const WavCall& c);
+  void enqueue(conan_streams* s, const WavCall& c, hipStream_t cst, FrontWork& front, std::vector<conan_streams::OutPlan>& ops);
+  void commit(conan_streams* s, hipStream_t dec, hipStream_t last_st);
+};
 }  // namespace act
 
 // ---- source bypass (bypass.hip): the kernels' host side and the bodies of api.hip's entry points
@@ -695,9 +836,22 @@ cnk::BypRow row(const conan_bypass_cfg& c);      // the cfg's fields of a stage 
 void mix(conan_ctx* ctx, int hop, const float* wet_dev, int64_t wet_ld, const float* dry_dev, int64_t dry_ld, int n, int64_t samples, const int32_t* wet_lvl_dev,
          const int32_t* dry_lvl_dev, int64_t lvl_ld, int32_t start_wet, int32_t start_dry, float* out_dev, int64_t out_ld, void* stream);
 void set_bypass(conan_streams* s, const int32_t* slots, int n, const conan_bypass_cfg* cfg, void* stream);
-void get_bypass(const conan_streams* s, int slot, conan_bypass_cfg* out);
 void state(conan_streams* s, const int32_t* slots, int n, conan_bypass_state* state_dev, void* stream);
 void last_call(conan_streams* s, int32_t* wet_lvl_dev, int32_t* dry_lvl_dev, void* stream);
+// As the activity table: one row per emitting call row in a call in which a slot with the feature emits; the stage kernel runs
+// behind the detector, whose levels of the same call a filling row reads (gate_stage: the call's activity stage, enqueued before);
+// the groups with a bypass row take their rows of table, levels and dry samples along.
+struct WavStage {
+  std::vector<cnk::BypRow> rows;
+  std::vector<LastRow> last;
+  std::vector<char> mix;        // per emit group: a row of it mixes (empty: no table)
+  bool fill = false;            // a row fills from the gate's levels
+  int q = 0;
+  const act::WavStage* gate_stage = nullptr;
+  void plan(const conan_streams* s, const WavCall& c);
+  void enqueue(conan_streams* s, const WavCall& c, hipStream_t cst, FrontWork& front, std::vector<conan_streams::OutPlan>& ops);
+  void commit(conan_streams* s, hipStream_t dec, hipStream_t last_st);
+};
 }  // namespace byp
 
 // ---- input loss concealment (conceal.hip): the kernel's host side and the bodies of api.hip's entry points
@@ -707,7 +861,6 @@ cnk::ConcRow row(const conan_conceal_cfg& c);      // the cfg's fields of a row 
 void whole(conan_ctx* ctx, const conan_conceal_cfg* cfg, int format, void* x_dev, int64_t ld, int n, const int64_t* samples, const int32_t* lost_dev,
            int64_t lost_ld, void* stream);
 void set_conceal(conan_streams* s, const int32_t* slots, int n, const conan_conceal_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream);
-void get_conceal(const conan_streams* s, int slot, conan_conceal_cfg* out);
 void repair(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, void* wav_dev, int64_t wav_ld, const int32_t* lost_dev, int64_t lost_ld,
             void* stream);
 void state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream);
@@ -719,7 +872,6 @@ namespace olv {
 // CONAN_ERR_UNSUPPORTED for a levelled row the split form does not cover.  Nothing changes.
 std::vector<cnk::OlRow> step_rows(const conan_streams* s, const int32_t* slots, int n, int frames, const std::string& who);
 void set_level(conan_streams* s, const int32_t* slots, int n, const conan_level_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream);
-void get_level(const conan_streams* s, int slot, conan_level_cfg* out);
 void stats(conan_streams* s, const int32_t* slots, int n, double* stats_dev, void* stream);
 int64_t state_bytes(const conan_streams* s);
 void state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream);

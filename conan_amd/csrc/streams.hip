@@ -629,16 +629,16 @@ void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float*
       l.tab = out_lv.sets.rows[lq]; l.n = n; l.samples = T; l.U = out_lv.filter.U;
       profiled("level_out_apply_kernel", 0.0, st, [&] { cnk::launch_level_out_apply(l, st); });
     }
-    if (op && op->gate_tab) {      // the output gate of a wav-in step (activity.hip), in place on the rows just written: [n][T], staged or the caller's
+    if (op && op->gate.tab) {      // the output gate of a wav-in step (activity.hip), in place on the rows just written: [n][T], staged or the caller's
       cnk::ActGateArgs g; memset(&g, 0, sizeof(g));
-      g.x = a.wav; g.y = a.wav; g.lvl = op->gate_lvl; g.tab = op->gate_tab; g.ld = T; g.ld_y = T; g.lvl_ld = op->gate_lvl_ld; g.samples = T;
+      g.x = a.wav; g.y = a.wav; g.lvl = op->gate.lvl; g.tab = op->gate.tab; g.ld = T; g.ld_y = T; g.lvl_ld = op->gate.lvl_ld; g.samples = T;
       g.n = n; g.hop = ctx->hop; g.start_in_lvl = 1;
       profiled("activity_gate_kernel", 0.0, st, [&] { cnk::launch_activity_gate(g, st); });
     }
-    if (op && op->byp_tab) {      // the wet/dry mix of a wav-in step (bypass.hip), behind the gate, in place on the same rows
+    if (op && op->mix.tab) {      // the wet/dry mix of a wav-in step (bypass.hip), behind the gate, in place on the same rows
       cnk::BypMixArgs b; memset(&b, 0, sizeof(b));
-      b.wet = a.wav; b.out = a.wav; b.dry = op->byp_dry; b.wet_lvl = op->byp_wet_lvl; b.dry_lvl = op->byp_dry_lvl; b.tab = op->byp_tab;
-      b.wet_ld = T; b.out_ld = T; b.dry_ld = op->byp_dry_ld; b.lvl_ld = op->byp_lvl_ld; b.samples = T; b.n = n; b.hop = ctx->hop; b.start_in_lvl = 1;
+      b.wet = a.wav; b.out = a.wav; b.dry = op->mix.dry; b.wet_lvl = op->mix.wet_lvl; b.dry_lvl = op->mix.dry_lvl; b.tab = op->mix.tab;
+      b.wet_ld = T; b.out_ld = T; b.dry_ld = op->mix.dry_ld; b.lvl_ld = op->mix.lvl_ld; b.samples = T; b.n = n; b.hop = ctx->hop; b.start_in_lvl = 1;
       profiled("bypass_mix_kernel", 0.0, st, [&] { cnk::launch_bypass_mix(b, st); });
     }
     if (out_rows) resample_out(*op, oq, T, st);

@@ -43,6 +43,29 @@ void check_format(int format, const char* who) {
 static_assert(CONAN_SAMPLE_F32 == cnk::kFmtF32 && CONAN_SAMPLE_S16 == cnk::kFmtS16 && CONAN_SAMPLE_ULAW == cnk::kFmtUlaw && CONAN_SAMPLE_ALAW == cnk::kFmtAlaw,
               "the kernels' format codes are the header's");
 
+// a setter of what the front-end's input goes through: every listed slot is at the start of an utterance
+void check_utterance_start(const conan_streams* s, const int32_t* slots, int n, const char* who) {
+  for (int i = 0; i < n; ++i) {
+    const conan_streams::FeSlot& o = s->wav_in.fe_slot[slots[i]];
+    const bool rs_fresh = s->wav_in.rs_slot.empty() || (s->wav_in.rs_slot[slots[i]].in == 0 && s->wav_in.rs_slot[slots[i]].phase == 0);
+    if (o.recv != 0 || o.phase != 0 || o.frames != 0 || o.chunks != 0 || !rs_fresh)
+      throw Error(CONAN_ERR_STATE, std::string(who) + ": slot " + std::to_string(slots[i]) + " is not at the start of an utterance (reset it with CONAN_MODEL_FRONTEND first)");
+  }
+}
+
+bool begin_setter(conan_streams* s, const int32_t* slots, int n, bool enabling, bool allocated, const char* who, void* stream) {
+  if (!s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, std::string(who) + ": the stream-set has no streaming front-end (all three models)");
+  check_slot_list(s, slots, n);
+  if (!enabling && !allocated) return false;
+  s->enter(stream);
+  return true;
+}
+
+hipStream_t begin_last_call(conan_streams* s, const char* who, void* stream) {
+  if (!s->wav_in.fe_chunk || s->wav_in.fe_last_n == 0) throw Error(CONAN_ERR_STATE, std::string(who) + ": no conan_step_wav call yet");
+  return s->enter(stream);
+}
+
 // Input resampler of a wav-in call (conan_streams_set_input_rate).  Per call row: the model-rate samples and final flag the front-end
 // gets - a row without a rate passes its own; a row with one hands over the longest prefix of outputs whose last tap has arrived (at
 // most seg * hop; after the input's final call, what is left, seg * hop at a time, final on the call that delivers the last sample).
@@ -121,20 +144,13 @@ static RsPlan rs_plan(const conan_streams* s, const int32_t* slots, int n, const
   return P;
 }
 
-// The launch of the plan whose rows went to set q of rs_sets (begin); `mel_front` (may be empty) follows it on the same stream, then
-// the set's event.
-static std::function<void(hipStream_t)> rs_front(conan_streams* s, const RsPlan& P, int n, int q, const float* wav_dev, long long wav_ld, long long out_ld,
-                                                 std::function<void(hipStream_t)> mel_front) {
+// The launch of the plan whose rows went to set q of rs_sets (begin), first of the call's front-end work
+static void rs_enqueue(conan_streams* s, const RsPlan& P, int n, int q, const float* wav_dev, long long wav_ld, long long out_ld, FrontWork& front) {
   cnk::ResampleStreamArgs a;
   a.wav = wav_dev ? wav_dev : s->wav_in.rs_wav[q]; a.wav_ld = wav_dev ? wav_ld : 0;
   a.ring = s->wav_in.rs_ring; a.out = s->wav_in.rs_wav[q]; a.out_ld = out_ld;
   a.rows = s->wav_in.rs_sets.rows[q]; a.n = n; a.tiles = P.tiles; a.win = P.win;
-  const double flops = P.flops;
-  return [s, a, flops, mel_front, q](hipStream_t st) {
-    s->profiled("resample_stream_kernel", flops, st, [&] { cnk::launch_resample_stream(a, st); });
-    if (mel_front) mel_front(st);
-    s->wav_in.rs_sets.end(q, st);
-  };
+  front.at[kFrResample] = [s, a, flops = P.flops](hipStream_t st) { s->profiled("resample_stream_kernel", flops, st, [&] { cnk::launch_resample_stream(a, st); }); };
 }
 
 static void rs_commit(conan_streams* s, const int32_t* slots, int n, const RsPlan& P, const int32_t* final_) {
@@ -157,13 +173,7 @@ static void check_mel_stream(const conan_streams* s, const conan_mel_cfg& m, con
     throw Error(CONAN_ERR_INVALID, "mel front-end configuration");
 }
 
-// One slot's front-end plan for a wav-in call that gives it `samples` (model rate) and `final_`.  Centred framing: frame f needs the
-// samples up to f * hop + n_fft / 2 - 1, or the final call: every frame of 1 + samples / hop, zero padding past the end.  R = samples
-// received after the call, total = R once final (-1 before); frames [0, fc) complete, [f0, f0 + nnew) of them new in this call; chunk
-// t = chunks emitted so far starts at frame pos and is ready once frames [pos, pos + seg + rc) are complete or - after the final call -
-// any frame is left (emit frames, rows [0, real) backed by frames: the short last chunks of engine.chunks, repeat-last padding).
-struct FePlan { long long R, total; int fc, f0, nnew, pos, emit, real; };
-
+// One slot's front-end plan (FePlan, streams.h) for a wav-in call that gives it `samples` (model rate) and `final_`; nothing changes.
 static FePlan fe_plan(const conan_streams* s, const conan_streams::FeSlot& o, int samples, int final_, int n_fft, const std::string& who) {
   const int seg = s->ctx->cfg.emf_segment, rc = s->ctx->cfg.emf_right_context, hop = s->ctx->hop, N = n_fft;
   FePlan p;
@@ -206,6 +216,8 @@ static void fe_commit(conan_streams* s, const int32_t* slots, int n, const std::
 // contiguously into fe_chunk; the outputs are rows of a full chunk ([n][seg]).  A call whose slots all emit a full chunk is one group
 // in call order and writes the caller's buffers directly; the groups of any other call write staging (set q of rg_sets) and
 // wav_rows_scatter_kernel puts the rows in call order.
+// The per-slot source features take part through their WavStage (streams.h): every plan() before anything changes, enqueue() into the
+// front-end work in front of the group steps, commit() behind them.
 void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, int n, const int32_t* in_samples, const int32_t* in_final, const float* wav_dev,
               long long wav_ld, const conan_mel_cfg* mel, int32_t* codes_dev, float* mel_out_dev, float* wav_out_dev, int32_t* emit_out, void* stream,
               bool pipelined, bool common) {
@@ -231,11 +243,7 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
       if (r.f != r0.f || (r.f && (r.in != r0.in || r.out != r0.out || r.phase != r0.phase)))
         throw Error(CONAN_ERR_INVALID, who + ": the slots of one call must share one input rate configuration (conan_streams_set_input_rate) and position");
     }
-    for (int i = 1; i < n && s->wav_in.lv_n > 0; ++i) {
-      const conan_level_cfg &l0 = s->wav_in.lv_cfg[slots[0]], &l = s->wav_in.lv_cfg[slots[i]];
-      if (l.enabled != l0.enabled || (l.enabled && memcmp(&l, &l0, sizeof(l))))
-        throw Error(CONAN_ERR_INVALID, who + ": the slots of one call must share one input level configuration (conan_streams_set_input_level)");
-    }
+    level::check_common(s, slots, n, who);
   }
   // the input resampler's rows first: what each slot's front-end gets this call
   const RsPlan P = rs_plan(s, slots, n, in_samples, in_final, wav_dev, wav_ld, m, who.c_str());
@@ -261,27 +269,6 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
     pl[i] = fe_plan(s, o, sm, fin, N, who);
     run = run || pl[i].nnew > 0 || sm > 0 || pl[i].emit > 0;
   }
-  // the leveller's rows: the levelled slots that hand their front-end samples this call.  Behind a resampler launch the kernel works
-  // in place on the staged rows; in a call without one it reads the caller's rows and writes the staging itself, so the call's
-  // unlevelled rows with samples ride along as copy rows and the front-end still finds every row in one place.
-  std::vector<cnk::LvRow> lv_rows;
-  bool lv_any = false;
-  for (int i = 0; i < n && s->wav_in.lv_n > 0; ++i) lv_any = lv_any || (s->wav_in.levelled(slots[i]) && samples[i] > 0);
-  const bool lv_stages = lv_any && !P.launch;
-  for (int i = 0; i < n && lv_any; ++i) {
-    const bool on = s->wav_in.levelled(slots[i]);
-    if (samples[i] < 1 || (!on && !lv_stages)) continue;
-    cnk::LvRow R;
-    memset(&R, 0, sizeof(R));
-    if (on) {
-      R.c = level::plan_call(s->wav_in.fe_slot[slots[i]].recv, samples[i], s->wav_in.lv_filter.U, 50.0 * hop);
-      R.cfg = level::kernel_cfg(s->wav_in.lv_cfg[slots[i]]);
-    } else {
-      R.c.m = samples[i]; R.copy = 1;
-    }
-    R.slot = slots[i]; R.row = i;
-    lv_rows.push_back(R);
-  }
   // emit groups, largest emit first; a group's rows keep call order
   std::vector<std::vector<int>> groups;      // call rows per group
   for (int e = seg; e >= 1; --e) {
@@ -305,112 +292,11 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
     const int e = pl[groups[g][0]].emit;
     ops.push_back(s->out_plan(gs.data(), (int)gs.size(), e, wav_out_dev, route ? (long long)seg * hop : (long long)e * hop, route ? &groups[g] : nullptr, who));
   }
-  // source-pitch following (f0.hip): the following slots that emit have their chunk's frames tracked, from their audio rings, into
-  // the call's contour rows (chunk row = the row's place in the emit groups, as fe_chunk's)
-  std::vector<cnk::F0Row> f0_rows;
-  std::vector<conan_streams::Follow::LastRow> f0_last;
-  std::vector<char> f0_group(groups.size(), 0);
-  int f0_jobs = 0;
-  // register matching (register.hip): every such row whose slot has the register on gets a row that rewrites its place in the contour
-  std::vector<cnk::RegRow> reg_rows;
-  if (s->follow.n_on > 0) {
-    const double sr = 50.0 * hop;
-    for (int i = 0; i < n; ++i) {
-      if (!s->follow.on(slots[i])) continue;
-      if (m.sample_rate != 50 * hop) throw Error(CONAN_ERR_INVALID, who + ": slot " + std::to_string(slots[i]) + " follows the source pitch: conan_mel_cfg.sample_rate must be 50 * hop_size");
-      f0::check_cfg(s->follow.cfg[slots[i]], sr, N, who.c_str());
-    }
-    for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g)
-      for (int k = 0; k < (int)groups[g].size(); ++k) {
-        const int i = groups[g][k];
-        if (!s->follow.on(slots[i])) continue;
-        const FePlan& p = pl[i];
-        if (p.R - std::max(0ll, (long long)p.pos * hop - N / 2) > s->wav_in.fe_LA)
-          throw Error(CONAN_ERR_UNSUPPORTED, who + ": slot " + std::to_string(slots[i]) + " follows the source pitch: the chunk's frames have left the audio ring at this fft_size");
-        cnk::F0Row r = f0::row(s->follow.cfg[slots[i]], sr);
-        r.src_off = (long long)slots[i] * s->wav_in.fe_LA; r.valid = p.R; r.mask = s->wav_in.fe_LA - 1;
-        r.f_first = p.pos; r.nframes = p.emit; r.job0 = f0_jobs; r.out_off = (off + k) * seg;
-        f0_jobs += p.emit;
-        f0_rows.push_back(r);
-        f0_last.push_back({i, 0, off + k, p.emit});
-        f0_group[g] = 1;
-        if (s->reg.on(slots[i])) {
-          cnk::RegRow rr = reg::row(s->reg.cfg[slots[i]]);
-          rr.in_off = r.out_off; rr.out_off = r.out_off; rr.nframes = p.emit; rr.slot = slots[i]; rr.reseed = s->reg.pending[slots[i]];
-          reg_rows.push_back(rr);
-        }
-      }
-  }
-  // source activity (activity.hip): a call in which a slot with the detector emits has one table row per emitting call row, in
-  // chunk-row order - the detector's rows, and mode-0 rows for the other slots so that a group's gate finds its rows by their place
-  std::vector<cnk::ActRow> act_rows;
-  std::vector<conan_streams::Activity::LastRow> act_last;
-  std::vector<char> act_gate(groups.size(), 0);
-  if (s->act.n_on > 0) {
-    bool any = false;
-    for (int i = 0; i < n; ++i) {
-      if (!s->act.on(slots[i])) continue;
-      if (m.sample_rate != 50 * hop) throw Error(CONAN_ERR_INVALID, who + ": slot " + std::to_string(slots[i]) + " detects source activity: conan_mel_cfg.sample_rate must be 50 * hop_size");
-      const FePlan& p = pl[i];
-      if (p.emit < 1) continue;
-      if (p.R - std::max(0ll, (long long)p.pos * hop - N / 2) > s->wav_in.fe_LA)
-        throw Error(CONAN_ERR_UNSUPPORTED, who + ": slot " + std::to_string(slots[i]) + " detects source activity: the chunk's frames have left the audio ring at this fft_size");
-      any = true;
-    }
-    for (int g = 0, off = 0; any && g < (int)groups.size(); off += (int)groups[g].size(), ++g)
-      for (int k = 0; k < (int)groups[g].size(); ++k) {
-        const int i = groups[g][k];
-        const FePlan& p = pl[i];
-        cnk::ActRow r;
-        memset(&r, 0, sizeof(r));      // (mode 0, no frames, no slot)
-        r.slot = -1; r.state_row = -1;
-        if (s->act.on(slots[i])) {
-          r = act::row(s->act.cfg[slots[i]]);
-          r.src_off = (long long)slots[i] * s->wav_in.fe_LA; r.valid = p.R; r.mask = s->wav_in.fe_LA - 1;
-          r.f_first = p.pos; r.nframes = p.emit; r.slot = slots[i]; r.reseed = s->act.pending[slots[i]]; r.start_lvl = 1;
-          act_last.push_back({i, 0, off + k, p.emit});
-          if (r.mode == 2) act_gate[g] = 1;
-        }
-        r.out_off = (long long)(off + k) * seg; r.lvl_off = (long long)(off + k) * (seg + 1) + 1;
-        act_rows.push_back(r);
-      }
-  }
-  // source bypass (bypass.hip): a call in which a slot with the feature emits has one table row per emitting call row, in chunk-row
-  // order, as the activity table: the stage rows, and mode-0 rows for the other slots so that a group's mix finds its rows by their place
-  std::vector<cnk::BypRow> byp_rows;
-  std::vector<conan_streams::Bypass::LastRow> byp_last;
-  std::vector<char> byp_mix(groups.size(), 0);
-  bool byp_fill = false;
-  if (s->byp.n_on > 0) {
-    bool any = false;
-    for (int i = 0; i < n; ++i) {
-      const FePlan& p = pl[i];
-      if (!s->byp.on(slots[i]) || p.emit < 1) continue;
-      if (p.R - (long long)p.pos * hop > s->wav_in.fe_LA)
-        throw Error(CONAN_ERR_UNSUPPORTED, who + ": slot " + std::to_string(slots[i]) + " mixes its source: the chunk's samples have left the audio ring");
-      any = true;
-    }
-    for (int g = 0, off = 0; any && g < (int)groups.size(); off += (int)groups[g].size(), ++g)
-      for (int k = 0; k < (int)groups[g].size(); ++k) {
-        const int i = groups[g][k];
-        const FePlan& p = pl[i];
-        cnk::BypRow r;
-        memset(&r, 0, sizeof(r));      // (mode 0, no frames, no slot)
-        r.slot = -1; r.state_row = -1;
-        if (s->byp.on(slots[i])) {
-          r = byp::row(s->byp.cfg[slots[i]]);
-          r.src_off = (long long)slots[i] * s->wav_in.fe_LA; r.valid = p.R; r.mask = s->wav_in.fe_LA - 1; r.s_first = (long long)p.pos * hop;
-          r.nframes = p.emit; r.slot = slots[i]; r.reseed = s->byp.pending[slots[i]];
-          // (the fill reads the gate's levels of this call: the activity table has the same rows in the same order; a slot that
-          // is not in activity mode 2 has no gate, which counts as open)
-          if (r.fill) r.fill = s->act.on(slots[i]) && s->act.cfg[slots[i]].mode == 2 ? 1 : 2;
-          byp_fill = byp_fill || r.fill == 1;
-          byp_last.push_back({i, 0, off + k, p.emit});
-          byp_mix[g] = 1;
-        }
-        byp_rows.push_back(r);
-      }
-  }
+  // the features' part of the call, each in its own file, in the order of their launches: every plan before anything changes
+  WavCall call{slots, n, pl, groups, seg, hop, N, m, who, P.launch, samples, common, wav_dev, wav_ld};
+  level::WavStage lv; f0::WavStage follow; act::WavStage activity; byp::WavStage bypass;
+  bypass.gate_stage = &activity;
+  lv.plan(s, call); follow.plan(s, call); activity.plan(s, call); bypass.plan(s, call);
   const int nm_in = m.num_mels, nm = c.num_mels;
   int jobs = 0;
   std::vector<RgRow> tab;
@@ -428,34 +314,33 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
       d[cnk::kRgJob] = jobs;
       jobs += p.nnew;
     }
-    for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g)
-      for (int k = 0; k < (int)groups[g].size(); ++k) {
-        int* d = tab[groups[g][k]].data();
-        d[cnk::kRgChunk] = off + k; d[cnk::kRgGroup] = off; d[cnk::kRgIndex] = k;
-      }
+    call.each_chunk_row([&](int, int k, int i, int at) {
+      int* d = tab[i].data();
+      d[cnk::kRgChunk] = at; d[cnk::kRgGroup] = at - k; d[cnk::kRgIndex] = k;
+    });
   }
   HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
   hipStream_t cst = (hipStream_t)stream;
   if (!pipelined || groups.empty()) s->join(cst);
   s->wav_out.out_counts.assign(n, 0);      // (rows that emit no frame; hifigan_step fills the others)
-  // a ragged call's row table and staging (set q); the resampler's rows and staging (set rq), read by the launches `front` holds
+  // a ragged call's row table and staging (set q); the resampler's rows and staging (set rs_q), read by the front-end work
   const std::string k = run ? s->ctx->mel_tables(m) : std::string();      // (may throw: before a staging set is taken)
-  int q = 0, rq = 0;
+  const bool staged = P.launch || lv.stages;      // (a leveller alone takes the resampler's set for its staging)
+  int q = 0;
   if (!common) {
     s->ragged_init();
     q = s->wav_in.rg_sets.begin(tab.data(), n, cst);
   }
-  if (P.launch || lv_stages) rq = s->wav_in.rs_sets.begin(P.rows.data(), n, cst);      // (a leveller alone takes the set for its staging)
-  const int lq = lv_rows.empty() ? 0 : s->wav_in.lv_sets.begin(lv_rows.data(), (int)lv_rows.size(), cst);
-  const int fq = f0_rows.empty() ? 0 : s->follow.sets.begin(f0_rows.data(), (int)f0_rows.size(), cst);
-  const int gq = reg_rows.empty() ? 0 : s->reg.sets.begin(reg_rows.data(), (int)reg_rows.size(), cst);
-  const int aq = act_rows.empty() ? 0 : s->act.sets.begin(act_rows.data(), (int)act_rows.size(), cst);
-  const int bq = byp_rows.empty() ? 0 : s->byp.sets.begin(byp_rows.data(), (int)byp_rows.size(), cst);
+  if (staged) call.rs_q = s->wav_in.rs_sets.begin(P.rows.data(), n, cst);
   const int* rg_tab = reinterpret_cast<const int*>(s->wav_in.rg_sets.rows[q]);
-  std::function<void(hipStream_t)> front;
+  // the front-end work, in the order of FrontPos (the same-position kernel reads the resampler's rows [n][samples], the ragged one
+  // [n][seg * hop])
+  FrontWork front;
+  if (P.launch) rs_enqueue(s, P, n, call.rs_q, wav_dev, wav_ld, common ? samples[0] : seg * hop, front);
+  if (staged) front.at[kFrResampleEnd] = [s, rq = call.rs_q](hipStream_t st) { s->wav_in.rs_sets.end(rq, st); };
   if (run) {
     const float* rg = s->ctx->vec(k + ".range");
-    const float* wav = P.launch || lv_stages ? s->wav_in.rs_wav[rq] : wav_dev;
+    const float* wav = staged ? s->wav_in.rs_wav[call.rs_q] : wav_dev;
     auto fill = [&](auto& a) {      // the fields both front-end kernels share
       a.wav = wav; a.aring = s->wav_in.fe_audio; a.mring = s->wav_in.fe_mel; a.chunk = s->wav_in.fe_chunk; a.n = n;
       a.win = s->ctx->vec(k + ".win"); a.tw = reinterpret_cast<const double2*>(s->ctx->vec(k + ".tw")); a.fb = s->ctx->vec(k + ".fb");
@@ -470,122 +355,46 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
       a.slots = s->d_slots; a.r_prev = s->wav_in.fe_slot[slots[0]].recv; a.total = p.total;
       a.m = samples[0]; a.f0 = p.f0; a.nnew = p.nnew; a.pos = p.pos; a.rows = p.emit > 0 ? rows : 0; a.real = p.real;
       const double flops = 4.0 * n * p.nnew * (double)(N / 2 + 1) * N;
-      front = [s, a, flops](hipStream_t st) {
+      front.at[kFrMel] = [s, a, flops](hipStream_t st) {
         if (a.nnew > 0) s->profiled("mel_stream_kernel", flops, st, [&] { cnk::launch_mel_stream(a, st); });
         else s->profiled("mel_stream_copy_kernel", 0.0, st, [&] { cnk::launch_mel_stream_copy(a, st); });
       };
     } else {
       cnk::MelRaggedArgs a;
       fill(a);
-      a.tab = rg_tab; a.jobs = jobs; a.wstride = P.launch || lv_stages ? seg * hop : (int)wav_ld;
+      a.tab = rg_tab; a.jobs = jobs; a.wstride = staged ? seg * hop : (int)wav_ld;
       const double flops = 4.0 * jobs * (double)(N / 2 + 1) * N;
-      front = [s, a, flops](hipStream_t st) { s->profiled("mel_stream_ragged_kernel", flops, st, [&] { cnk::launch_mel_ragged(a, st); }); };
+      front.at[kFrMel] = [s, a, flops](hipStream_t st) { s->profiled("mel_stream_ragged_kernel", flops, st, [&] { cnk::launch_mel_ragged(a, st); }); };
     }
   }
-  // the leveller, between the resampler's launch (or the caller's rows) and the front-end's
-  if (!lv_rows.empty()) {
-    cnk::LevelStreamArgs a;
-    a.y = s->wav_in.rs_wav[rq]; a.y_ld = common ? samples[0] : seg * hop;
-    a.x = lv_stages ? wav_dev : a.y; a.x_ld = lv_stages ? wav_ld : a.y_ld;
-    a.state = s->wav_in.lv_state; a.state_stride = s->wav_in.lv_stride; a.zcap = CONAN_LEVEL_MAX_BLOCKS + cnk::kLvRingPad;
-    a.rows = s->wav_in.lv_sets.rows[lq]; a.n = (int)lv_rows.size(); a.f = s->wav_in.lv_filter;
-    front = [s, a, lq, rq, lv_stages, mel_front = front](hipStream_t st) {
-      s->profiled("level_stream_kernel", 0.0, st, [&] { cnk::launch_level_stream(a, st); });
-      mel_front(st);
-      s->wav_in.lv_sets.end(lq, st);
-      if (lv_stages) s->wav_in.rs_sets.end(rq, st);
-    };
-  }
-  // (the same-position kernel reads the resampler's rows [n][samples], the ragged one [n][seg * hop])
-  if (P.launch) front = rs_front(s, P, n, rq, wav_dev, wav_ld, common ? samples[0] : seg * hop, front);
-  // the tracker, behind the front-end launch: the call's samples are in the audio rings
-  if (!f0_rows.empty()) {
-    cnk::F0Args a;
-    memset(&a, 0, sizeof(a));
-    a.src = s->wav_in.fe_audio; a.out_f0 = s->follow.ct_f0[fq]; a.out_uv = s->follow.ct_uv[fq];
-    a.tab = s->follow.sets.rows[fq]; a.rows = (int)f0_rows.size(); a.jobs = f0_jobs; a.n_fft = N; a.hop = hop; a.sr = 50.0 * hop;
-    double flops = 0.0;
-    for (const cnk::F0Row& r : f0_rows) flops += 3.0 * r.nframes * (double)(N - r.tmax - 1) * (r.tmax + 2);
-    front = [s, a, flops, mel_front = front](hipStream_t st) {
-      if (mel_front) mel_front(st);
-      s->profiled("f0_yin_kernel", flops, st, [&] { cnk::launch_f0(a, st); });
-    };
-  }
-  // register matching, directly behind the tracker: the decoder stage reads the matched rows
-  if (!reg_rows.empty()) {
-    cnk::RegArgs a;
-    memset(&a, 0, sizeof(a));
-    a.f0 = s->follow.ct_f0[fq]; a.uv = s->follow.ct_uv[fq]; a.out = s->follow.ct_f0[fq]; a.state = s->reg.state;
-    a.tab = s->reg.sets.rows[gq]; a.rows = (int)reg_rows.size();
-    front = [s, a, gq, f0_front = front](hipStream_t st) {
-      f0_front(st);
-      s->profiled("f0_register_kernel", 0.0, st, [&] { cnk::launch_f0_register(a, st); });
-      s->reg.sets.end(gq, st);
-    };
-  }
-  // the activity detector, behind the front-end launch (and the tracker's and the register's): the call's samples are in the audio
-  // rings; the groups with a gated row take their rows of the table and of the level staging along to their vocoder step
-  if (!act_rows.empty()) {
-    cnk::ActArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = s->wav_in.fe_audio; a.act = s->act.flags[aq]; a.lvl = s->act.levels[aq]; a.state = s->act.state;
-    a.tab = s->act.sets.rows[aq]; a.rows = (int)act_rows.size(); a.n_fft = N; a.hop = hop;
-    front = [s, a, before = front](hipStream_t st) {
-      if (before) before(st);
-      s->profiled("activity_kernel", 0.0, st, [&] { cnk::launch_activity(a, st); });
-    };
-    for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g) {
-      if (!act_gate[g]) continue;
-      ops[g].gate_tab = s->act.sets.rows[aq] + off; ops[g].gate_lvl = s->act.levels[aq] + (size_t)off * (seg + 1) + 1; ops[g].gate_lvl_ld = seg + 1;
-    }
-  }
-  // the bypass stage, behind the detector (whose levels a filling row reads): the slew, and the chunk's source samples out of the audio
-  // rings into the set's dry staging; the groups with a bypass row take their rows of table, levels and samples along to their vocoder step
-  if (!byp_rows.empty()) {
-    cnk::BypStageArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = s->wav_in.fe_audio; a.dry = s->byp.dry[bq]; a.wet_lvl = s->byp.wet_lvl[bq]; a.dry_lvl = s->byp.dry_lvl[bq];
-    a.gate_lvl = byp_fill ? s->act.levels[aq] : nullptr; a.state = s->byp.state;
-    a.tab = s->byp.sets.rows[bq]; a.rows = (int)byp_rows.size(); a.seg = seg; a.hop = hop;
-    front = [s, a, before = front](hipStream_t st) {
-      if (before) before(st);
-      s->profiled("bypass_stage_kernel", 0.0, st, [&] { cnk::launch_bypass_stage(a, st); });
-    };
-    for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g) {
-      if (!byp_mix[g]) continue;
-      ops[g].byp_tab = s->byp.sets.rows[bq] + off; ops[g].byp_lvl_ld = seg + 1; ops[g].byp_dry_ld = (long long)seg * hop;
-      ops[g].byp_wet_lvl = s->byp.wet_lvl[bq] + (size_t)off * (seg + 1) + 1; ops[g].byp_dry_lvl = s->byp.dry_lvl[bq] + (size_t)off * (seg + 1) + 1;
-      ops[g].byp_dry = s->byp.dry[bq] + (size_t)off * seg * hop;
-    }
-  }
+  lv.enqueue(s, call, cst, front, ops); follow.enqueue(s, call, cst, front, ops); activity.enqueue(s, call, cst, front, ops); bypass.enqueue(s, call, cst, front, ops);
+  const std::function<void(hipStream_t)> pre = [&front](hipStream_t st) { front.run(st); }, none;
   cnk::WavScatterArgs sc;
   sc.tab = rg_tab; sc.n = n; sc.seg = seg; sc.nm = nm; sc.hop = hop;
   sc.codes_src = s->wav_in.rg_codes[q]; sc.mel_src = s->wav_in.rg_mel[q]; sc.wav_src = s->wav_in.rg_wav[q];
   sc.codes = codes_dev; sc.mel = mel_out_dev; sc.wav = route ? nullptr : wav_out_dev;
-  auto group_step = [&](int g, int off, hipStream_t st) {
+  const bool piped = pipelined && !groups.empty();      // (the first group's step_pipelined runs the front-end work)
+  if (!piped) {
+    if (common) s->set_slots(slots, n, cst);      // (mel_stream_kernel reads the slot table)
+    front.run(cst);
+  }
+  call.each_group([&](int g, int off) {
     const std::vector<int32_t>& gs = gslots[g];
     const int ng = (int)gs.size(), e = pl[groups[g][0]].emit;
     const float* chunk = s->wav_in.fe_chunk + (size_t)off * rows * nm_in;
     int32_t* cd = direct ? codes_dev : s->wav_in.rg_codes[q] + (size_t)off * seg;
     float* md = direct ? mel_out_dev : s->wav_in.rg_mel[q] + (size_t)off * seg * nm;
     float* wd = direct ? wav_out_dev : s->wav_in.rg_wav[q] + (size_t)off * seg * hop;
-    const float* tf = f0_group[g] ? s->follow.ct_f0[fq] + (size_t)off * seg : nullptr;      // (a group without a following row keeps its program)
-    const float* tu = f0_group[g] ? s->follow.ct_uv[fq] + (size_t)off * seg : nullptr;
+    const float *tf = follow.trk_f0(g, off, seg), *tu = follow.trk_uv(g, off, seg);
     if (pipelined) {
-      step_pipelined(s, gs.data(), ng, e, chunk, cd, md, wd, stream, g == 0 ? front : std::function<void(hipStream_t)>(), ops[g], tf, tu);
+      step_pipelined(s, gs.data(), ng, e, chunk, cd, md, wd, stream, g == 0 ? pre : none, ops[g], tf, tu);
     } else {
-      s->set_slots(gs.data(), ng, st);
-      step_blocking(s, ng, e, chunk, cd, md, wd, st, ops[g], tf, tu);
+      s->set_slots(gs.data(), ng, cst);
+      step_blocking(s, ng, e, chunk, cd, md, wd, cst, ops[g], tf, tu);
     }
-  };
-  const bool piped = pipelined && !groups.empty();      // (the first group's step_pipelined runs `front`)
-  if (!piped) {
-    if (common) s->set_slots(slots, n, cst);      // (mel_stream_kernel reads the slot table)
-    if (front) front(cst);
-  }
-  for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g) group_step(g, off, cst);
-  // the stream the call's last launches go to (read behind the group steps: a stream-set's first pipelined step creates st_voc)
-  hipStream_t last = piped ? s->st_voc : cst;
+  });
+  // the streams the call's last launches went to (read behind the group steps: a stream-set's first pipelined step creates them)
+  hipStream_t last = piped ? s->st_voc : cst, dec = piped ? s->st_front : cst;
   if (scatter && piped) {
     cnk::launch_wav_scatter(sc, last);
     // join() waits for the last step's vocoder event: it now covers the scatter too
@@ -594,18 +403,7 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
     s->profiled("wav_rows_scatter_kernel", 0.0, cst, [&] { cnk::launch_wav_scatter(sc, cst); });
   }
   if (!common) s->wav_in.rg_sets.end(q, last);
-  if (!f0_rows.empty()) s->follow.sets.end(fq, piped ? s->st_front : cst);      // (behind the call's last decoder step, the contour's last reader)
-  for (conan_streams::Follow::LastRow& r : f0_last) r.set = fq;
-  s->follow.last = std::move(f0_last);
-  for (const cnk::RegRow& rr : reg_rows) s->reg.pending[rr.slot] = 0;      // (the rows carried the restarts)
-  if (!act_rows.empty()) s->act.sets.end(aq, last);      // (behind the call's last vocoder step: the gate is the last reader of table and levels)
-  for (const cnk::ActRow& ar : act_rows) if (ar.slot >= 0) s->act.pending[ar.slot] = 0;
-  for (conan_streams::Activity::LastRow& r : act_last) r.set = aq;
-  s->act.last = std::move(act_last);
-  if (!byp_rows.empty()) s->byp.sets.end(bq, last);      // (behind the call's last vocoder step: the mix is the last reader of table, levels and samples)
-  for (const cnk::BypRow& br : byp_rows) if (br.slot >= 0) s->byp.pending[br.slot] = 0;
-  for (conan_streams::Bypass::LastRow& r : byp_last) r.set = bq;
-  s->byp.last = std::move(byp_last);
+  lv.commit(s, dec, last); follow.commit(s, dec, last); activity.commit(s, dec, last); bypass.commit(s, dec, last);
   if (scatter && !route) {      // (each group's step counted its own rows, in group order: back to the call's rows)
     s->wav_out.out_counts.assign(n, 0);
     for (int i = 0; i < n; ++i) s->wav_out.out_counts[i] = pl[i].emit * hop;
@@ -634,8 +432,7 @@ void step_wav_chunk(conan_streams* s, float* chunk_dev, void* stream) {
   if (!s || !chunk_dev) throw Error(CONAN_ERR_INVALID, "null argument");
   if (!s->wav_in.fe_chunk || s->wav_in.fe_last_n == 0) throw Error(CONAN_ERR_STATE, "conan_step_wav_chunk: no conan_step_wav call yet");
   if (s->wav_in.fe_last_ragged) throw Error(CONAN_ERR_STATE, "conan_step_wav_chunk: the last wav-in call was conan_step_wav_ragged, whose chunk rows are grouped by emit");
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  s->join((hipStream_t)stream);
+  s->enter(stream);
   const size_t floats = (size_t)s->wav_in.fe_last_n * (s->ctx->cfg.emf_segment + s->ctx->cfg.emf_right_context) * s->ctx->cfg.emf_input_dim;
   HIP_CHECK(hipMemcpyAsync(chunk_dev, s->wav_in.fe_chunk, floats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
 }
@@ -657,12 +454,7 @@ void set_input_rate(conan_streams* s, const int32_t* slots, int n, const conan_r
     const long long s_in = num / c.out_rate;
     if (t->length(s_in) - t->ready(s_in) > S) throw Error(CONAN_ERR_INVALID, "conan_streams_set_input_rate: the filter's look-ahead is longer than segment * hop samples");
   }
-  for (int i = 0; i < n; ++i) {
-    const conan_streams::FeSlot& o = s->wav_in.fe_slot[slots[i]];
-    const bool rs_fresh = s->wav_in.rs_slot.empty() || (s->wav_in.rs_slot[slots[i]].in == 0 && s->wav_in.rs_slot[slots[i]].phase == 0);
-    if (o.recv != 0 || o.phase != 0 || o.frames != 0 || o.chunks != 0 || !rs_fresh)
-      throw Error(CONAN_ERR_STATE, "conan_streams_set_input_rate: slot " + std::to_string(slots[i]) + " is not at the start of an utterance (reset it with CONAN_MODEL_FRONTEND first)");
-  }
+  check_utterance_start(s, slots, n, "conan_streams_set_input_rate");
   HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
   s->resample_init();
   for (int i = 0; i < n; ++i) s->wav_in.rs_slot[slots[i]] = conan_streams::RsSlot{t, 0, 0, 0};
@@ -715,53 +507,6 @@ void set_input_format(conan_streams* s, const int32_t* slots, int n, int format)
   store_format(s->wav_in.in_fmt, s->wav_in.in_fmt_n, slots, n, format);
 }
 
-void set_input_level(conan_streams* s, const int32_t* slots, int n, const conan_level_cfg* cfg) {
-  if (!s || !slots || !cfg) throw Error(CONAN_ERR_INVALID, "null argument");
-  level::check_cfg(*cfg, "conan_streams_set_input_level");
-  if (!s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, "conan_streams_set_input_level: the stream-set has no streaming front-end (all three models)");
-  check_slot_list(s, slots, n);
-  cnk::LvFilter f;
-  if (cfg->enabled) f = level::filter(s->ctx, "conan_streams_set_input_level");
-  for (int i = 0; i < n; ++i) {
-    const conan_streams::FeSlot& o = s->wav_in.fe_slot[slots[i]];
-    const bool rs_fresh = s->wav_in.rs_slot.empty() || (s->wav_in.rs_slot[slots[i]].in == 0 && s->wav_in.rs_slot[slots[i]].phase == 0);
-    if (o.recv != 0 || o.phase != 0 || o.frames != 0 || o.chunks != 0 || !rs_fresh)
-      throw Error(CONAN_ERR_STATE, "conan_streams_set_input_level: slot " + std::to_string(slots[i]) + " is not at the start of an utterance (reset it with CONAN_MODEL_FRONTEND first)");
-  }
-  if (!cfg->enabled && s->wav_in.lv_cfg.empty()) return;      // a stream-set that never had a leveller: nothing to allocate
-  if (cfg->enabled) {
-    HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-    s->level_init(f);
-  }
-  conan_level_cfg c = *cfg;
-  if (!c.enabled) memset(&c, 0, sizeof(c));
-  for (int i = 0; i < n; ++i) {
-    s->wav_in.lv_n += c.enabled - s->wav_in.lv_cfg[slots[i]].enabled;
-    s->wav_in.lv_cfg[slots[i]] = c;
-  }
-}
-
-void input_level(conan_streams* s, const int32_t* slots, int n, double* stats_dev, void* stream) {
-  if (!s || !slots || !stats_dev) throw Error(CONAN_ERR_INVALID, "null argument");
-  check_slot_list(s, slots, n);
-  std::vector<cnk::LvRow> rows((size_t)n);
-  for (int i = 0; i < n; ++i) {
-    if (!s->wav_in.levelled(slots[i])) throw Error(CONAN_ERR_STATE, "conan_streams_input_level: slot " + std::to_string(slots[i]) + " has no leveller (conan_streams_set_input_level)");
-    memset(&rows[i], 0, sizeof(cnk::LvRow));
-    rows[i].cfg = level::kernel_cfg(s->wav_in.lv_cfg[slots[i]]);
-    rows[i].slot = slots[i]; rows[i].row = i; rows[i].fresh = s->wav_in.fe_slot[slots[i]].recv == 0;
-  }
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  hipStream_t st = (hipStream_t)stream;
-  s->join(st);
-  const int q = s->wav_in.lv_sets.begin(rows.data(), n, st);
-  cnk::LevelStatsArgs a;
-  a.state = s->wav_in.lv_state; a.state_stride = s->wav_in.lv_stride; a.rows = s->wav_in.lv_sets.rows[q]; a.n = n; a.out = stats_dev;
-  cnk::launch_level_stats(a, st);
-  HIP_CHECK(hipGetLastError());
-  s->wav_in.lv_sets.end(q, st);
-}
-
 void set_output_format(conan_streams* s, const int32_t* slots, int n, int format) {
   if (!s || !slots) throw Error(CONAN_ERR_INVALID, "null argument");
   if (!(s->ctx->cfg.models & CONAN_MODEL_HIFIGAN)) throw Error(CONAN_ERR_STATE, "conan_streams_set_output_format: context holds no HiFi-GAN model");
@@ -789,9 +534,7 @@ void flush_output(conan_streams* s, const int32_t* slots, int n, float* wav_out_
   if (wav_ld < 0 || wav_ld > INT_MAX) throw Error(CONAN_ERR_INVALID, "conan_streams_flush_output: wav_ld out of range");
   check_slot_list(s, slots, n);
   const conan_streams::OutPlan P = s->out_plan(slots, n, 0, wav_out_dev, wav_ld, nullptr, "conan_streams_flush_output");
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  hipStream_t st = (hipStream_t)stream;
-  s->join(st);
+  hipStream_t st = s->enter(stream);
   if (P.active) {
     s->out_stage_init();
     s->resample_out(P, s->wav_out.or_sets.begin(P.rows.data(), n, st), 0, st);
@@ -808,16 +551,6 @@ void flush_output(conan_streams* s, const int32_t* slots, int n, float* wav_out_
 void conan_streams::resample_init() {
   rs_stage_init();
   if (!wav_in.rs_ring) wav_in.rs_ring = alloc((size_t)max_slots * cnk::kRsRing);        // stream state (state_bytes)
-}
-
-void conan_streams::level_init(const cnk::LvFilter& f) {
-  rs_stage_init();
-  if (wav_in.lv_state) return;
-  wav_in.lv_filter = f;
-  wav_in.lv_stride = (long long)cnk::lv_state_bytes(CONAN_LEVEL_MAX_BLOCKS + cnk::kLvRingPad);
-  wav_in.lv_state = reinterpret_cast<char*>(alloc((size_t)max_slots * wav_in.lv_stride / sizeof(float)));        // stream state (state_bytes)
-  wav_in.lv_sets.init(max_slots, allocs);
-  wav_in.lv_cfg.assign(max_slots, conan_level_cfg{});
 }
 
 void conan_streams::out_ring_init() {
