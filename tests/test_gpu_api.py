@@ -197,8 +197,11 @@ def test_pipelined_step_matches_fused_step():
 def test_wav2mel_frontend_matches_oracle():
     """conan_wav2mel (frames -> f64 DFT sums -> magnitude -> f64 filterbank sums -> log10 / clip, all on the GPU) against
     the numpy restatement of librosa_wav2spec (oracle/frontend.py, itself pinned against transformers.audio_utils and
-    torch.stft in tests/test_oracle_frontend.py).  Tolerance 1e-5 in log10 units everywhere, including a pure tone whose
-    quiet mel bins lie 6 decades below the peak (measured: <= 1e-6)."""
+    torch.stft in tests/test_oracle_frontend.py).  That oracle calls np.fft.rfft on float32 frames - a float32 FFT under
+    numpy 2, librosa's own arithmetic - so it is no more exact than the kernels, and this test shows agreement with librosa's
+    rounding, not the accuracy of the f64 DFT sums: tolerance 1e-5 in log10 units everywhere, including a pure tone whose
+    quiet mel bins lie 6 decades below the peak.  The kernels are held to a float64 reference, within a derived bound
+    (about 6e-7 at these defaults) and across the configuration range, in tests/test_gpu_frontend_f64.py."""
     from conan_amd import configs
     from conan_amd.runtime import Context
     from oracle import frontend as ofe

@@ -51,6 +51,42 @@ def _calls(N):
     return out + [(last, N, True)]
 
 
+def _stream_frames(eng, wav, mel=None, pipelined=False):
+    """One utterance [B, N] through step_wav (step_wav_async and a join per call when pipelined), drain included, on eng.slots (already
+    started) -> (got: (emit, chunk) per emitting call, frames: the emitted rows of those chunks, first_emit, ncalls, fdone,
+    with_frames, copy_only): the calls that completed frames / only copied, by the frames-complete rule of the configuration `mel`."""
+    B, N = wav.shape
+    half = (mel or {}).get("fft_size", 1024) // 2
+    step = eng.st.step_wav_async if pipelined else eng.st.step_wav
+    got, ncalls, frames = [], 0, []
+    calls = _calls(N)
+    drained = False
+    recv, fdone, with_frames, copy_only = 0, 0, 0, 0
+    while not drained:
+        if calls:
+            a, b, fin = calls.pop(0)
+            emit, _, _, _ = step(eng.slots, wav[:, a:b], final=fin, mel=mel)
+        else:
+            a = b = N
+            emit, _, _, _ = step(eng.slots, wav[:, :0], final=True, mel=mel)
+            drained = emit == 0
+        if pipelined:
+            eng.st.join()
+        recv += b - a
+        fc = 1 + recv // HOP if fin else max(0, (recv - half) // HOP + 1)      # frames complete (half = fft_size / 2)
+        with_frames += fc > fdone
+        copy_only += fc <= fdone and ((b > a) or emit > 0)
+        fdone = max(fdone, fc)
+        ncalls += 1
+        if ncalls == 1:
+            first_emit = emit
+        if emit:
+            ch = eng.st.wav_chunk(B)
+            got.append((emit, ch))
+            frames.append(ch[:, :emit])
+    return got, frames, first_emit, ncalls, fdone, with_frames, copy_only
+
+
 @pytest.mark.parametrize("B", [1, 4, 64])
 def test_frames_bitwise_equal_wav2mel(ctx, B):
     eng = StreamingVoiceConversionEngine(ctx, B, max_ref_frames=64)
@@ -60,30 +96,7 @@ def test_frames_bitwise_equal_wav2mel(ctx, B):
         want = list(eng.chunks(whole))
         eng.start_wav(_ref(B))
         eng.st.profile_begin()
-        got, ncalls, frames = [], 0, []
-        calls = _calls(N)
-        drained = False
-        recv, fdone, with_frames, copy_only = 0, 0, 0, 0
-        while not drained:
-            if calls:
-                a, b, fin = calls.pop(0)
-                emit, _, _, _ = eng.st.step_wav(eng.slots, wav[:, a:b], final=fin)
-            else:
-                a = b = N
-                emit, _, _, _ = eng.st.step_wav(eng.slots, wav[:, :0], final=True)
-                drained = emit == 0
-            recv += b - a
-            fc = 1 + recv // HOP if fin else max(0, (recv - 512) // HOP + 1)      # frames complete (fft_size 1024)
-            with_frames += fc > fdone
-            copy_only += fc <= fdone and ((b > a) or emit > 0)
-            fdone = max(fdone, fc)
-            ncalls += 1
-            if ncalls == 1:
-                first_emit = emit
-            if emit:
-                ch = eng.st.wav_chunk(B)
-                got.append((emit, ch))
-                frames.append(ch[:, :emit])
+        got, frames, first_emit, ncalls, fdone, with_frames, copy_only = _stream_frames(eng, wav)
         eng.st.profile_end()
         launches = {k[0]: k[3] for k in eng.st.profile_kernels()}
         assert len(got) == len(want), (N, len(got), len(want))
