@@ -160,6 +160,13 @@ _PROTOS = {
     "conan_step_wav_bypass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_bypass_mix": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                    C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "conan_streams_set_comfort": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "conan_streams_comfort": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "conan_streams_comfort_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "conan_step_wav_comfort": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_comfort_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_comfort_fill": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_streams_set_output_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_streams_output_level_cfg": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "conan_streams_output_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -528,6 +535,68 @@ def bypass_keywords(c):
     k / 2^20, which rint(share * 2^20) maps back to k): the form Streams.bypass reports a setting in."""
     return dict(wet=c.wet_target / ACTIVITY_FULL, dry=c.dry_target / ACTIVITY_FULL, step=int(c.step), fill_gate=bool(c.fill_gate),
                 start=(int(c.seed_wet), int(c.seed_dry)))
+
+
+class ComfortCfg(C.Structure):
+    """conan_comfort_cfg (include/conan_hip.h)."""
+    _fields_ = [("mode", C.c_int32), ("reseed", C.c_int32), ("level", C.c_int32), ("offset", C.c_int32), ("l_min", C.c_int32), ("l_max", C.c_int32),
+                ("up_step", C.c_int32), ("down_step", C.c_int32), ("colour", C.c_int32), ("seed_level", C.c_int32), ("norm", C.c_float),
+                ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
+class ComfortState(C.Structure):
+    """conan_comfort_state (include/conan_hip.h)."""
+    _fields_ = [("level", C.c_int32), ("reserved", C.c_int32), ("idle_frames", C.c_int64)]
+
+
+COMFORT_LEVEL_MIN = -16384
+COMFORT_UNITS_PER_DB = 256.0 / (10.0 * math.log10(2.0))      # about 85.04: levels are 1/256 octaves of power
+COMFORT_TAPS = ((1,), (1, 2, 1), (1, 2, 3, 2, 1))
+
+
+def comfort_level(db):
+    """A decibel figure (dBov: 0 = full scale; or a difference in dB) as the law's integer level, 1/256 octave of power: rint(db *
+    85.04), converted once on the host.  Host only."""
+    return int(round(float(db) * COMFORT_UNITS_PER_DB))
+
+
+def comfort_norm(colour):
+    """The amplitude of one unit of the coloured noise v at level 0, so that its rms is 1 there: the f32 of 1 / (sqrt((65536^2 - 1) /
+    6) * sqrt(sum c^2)) - w is the sum of two uniform 16-bit words less its mean - formed once on the host."""
+    return C.c_float(1.0 / (math.sqrt((65536.0 ** 2 - 1.0) / 6.0) * math.sqrt(float(sum(c * c for c in COMFORT_TAPS[int(colour)]))))).value
+
+
+def comfort_seed(slot):
+    """The default seed of a slot's white source: derived from the slot's index, so that two slots do not share a sequence."""
+    return 0x636F6D666F727400 + int(slot)
+
+
+def comfort_cfg(follow=True, level_db=-60.0, offset_db=-3.0, min_db=-90.0, max_db=-30.0, rise_db=0.25, fall_db=2.0, colour=1, start_db=-70.0,
+                seed=0, reseed=False, level=None, offset=None, l_min=None, l_max=None, up_step=None, down_step=None, start=None, norm=None):
+    """An enabled conan_comfort_cfg: follow the source's background (mode 2) or hold level_db (follow=False: mode 1).  offset_db: added
+    to the frame power of an inactive frame; min_db / max_db: the level's limits in dBov; rise_db / fall_db: its largest rise and fall
+    per 20 ms frame; colour: 0 white, 1 and 2 low-passed by the taps {1, 2, 1} / {1, 2, 3, 2, 1}; start_db: the level a restart
+    begins from; seed: of the white source.  The defaults - follow, 3 dB under the background, -90 .. -30 dBov, a rise of 0.25 dB and
+    a fall of 2 dB per frame, colour 1, a start at -70 dBov - are choices, not measurements.  Every decibel figure is converted to
+    the law's integer levels once (comfort_level); the integer keywords (level, offset, l_min, l_max, up_step, down_step, start) give
+    a field directly and win over their dB forms, and norm= over comfort_norm(colour)."""
+    pick = lambda direct, db: comfort_level(db) if direct is None else int(direct)      # noqa: E731
+    step = lambda direct, db: max(1, comfort_level(db)) if direct is None else int(direct)      # noqa: E731
+    return ComfortCfg(2 if follow else 1, int(bool(reseed)), pick(level, level_db), pick(offset, offset_db), pick(l_min, min_db), pick(l_max, max_db),
+                      step(up_step, rise_db), step(down_step, fall_db), int(colour), pick(start, start_db),
+                      comfort_norm(colour) if norm is None else float(norm), 0, int(seed) & ((1 << 64) - 1))
+
+
+def comfort_keywords(c):
+    """comfort_cfg's keywords of an enabled ComfortCfg in the integer forms that give the same fields back exactly: the form
+    Streams.comfort reports a setting in."""
+    return dict(follow=c.mode == 2, level=int(c.level), offset=int(c.offset), l_min=int(c.l_min), l_max=int(c.l_max), up_step=int(c.up_step),
+                down_step=int(c.down_step), colour=int(c.colour), start=int(c.seed_level), norm=float(c.norm), seed=int(c.seed))
+
+
+def comfort_dbov(level):
+    """The RFC 3389 noise level byte of a comfort level L (Streams.step_wav_comfort, comfort_state): -dBov, rounded, in 0 .. 127."""
+    return max(0, min(127, int(round(-float(level) / COMFORT_UNITS_PER_DB))))
 
 
 CONCEAL_MAX_LAG, CONCEAL_MAX_WINDOW = 1024, 1024

@@ -338,6 +338,7 @@ void WavStage::enqueue(conan_streams* s, const WavCall& c, hipStream_t cst, Fron
   cnk::ActArgs a;
   memset(&a, 0, sizeof(a));
   a.src = s->wav_in.fe_audio; a.act = s->act.flags[q]; a.lvl = s->act.levels[q]; a.state = s->act.state;
+  a.power = power;      // (comfort.hip: a following row of the call reads the frame powers; null otherwise)
   a.tab = s->act.sets.rows[q]; a.rows = (int)rows.size(); a.n_fft = c.N; a.hop = c.hop;
   front.at[kFrActivity] = [s, a](hipStream_t st) { s->profiled("activity_kernel", 0.0, st, [&] { cnk::launch_activity(a, st); }); };
   c.each_group([&](int g, int off) {

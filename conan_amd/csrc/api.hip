@@ -513,6 +513,31 @@ int conan_step_wav_bypass(conan_streams* s, int32_t* wet_lvl_dev, int32_t* dry_l
   return guarded([&] { byp::last_call(s, wet_lvl_dev, dry_lvl_dev, stream); });
 }
 
+int conan_streams_set_comfort(conan_streams* s, const int32_t* slots, int n, const conan_comfort_cfg* cfg, void* stream) {
+  return guarded([&] { comfort::set_comfort(s, slots, n, cfg, stream); });
+}
+
+int conan_streams_comfort(const conan_streams* s, int slot, conan_comfort_cfg* cfg_out) { return guarded([&] { wavio::get_setting(s, &conan_streams::cmf, slot, cfg_out, "conan_streams_comfort"); }); }
+
+int conan_streams_comfort_state(conan_streams* s, const int32_t* slots, int n, conan_comfort_state* state_dev, void* stream) {
+  return guarded([&] { comfort::state(s, slots, n, state_dev, stream); });
+}
+
+int conan_step_wav_comfort(conan_streams* s, int32_t* level_dev, void* stream) { return guarded([&] { comfort::last_call(s, level_dev, stream); }); }
+
+int conan_comfort_track(conan_ctx* ctx, const conan_comfort_cfg* cfg, const int32_t* act_dev, const double* power_dev, int n, int64_t frames, int64_t ld,
+                        int32_t* level_out_dev, conan_comfort_state* state_out_dev, void* stream) {
+  return guarded([&] { comfort::track(ctx, cfg, act_dev, power_dev, n, frames, ld, level_out_dev, state_out_dev, stream); });
+}
+
+int conan_comfort_fill(conan_ctx* ctx, int hop, const conan_comfort_cfg* cfg, const uint64_t* seeds, const float* wav_dev, int64_t ld, int n, int64_t samples,
+                       int64_t pos0, const int32_t* gate_lvl_dev, const int32_t* comfort_lvl_dev, int64_t lvl_ld, int32_t start_gate_level,
+                       int32_t start_comfort_level, float* out_dev, int64_t out_ld, void* stream) {
+  return guarded([&] {
+    comfort::fill(ctx, hop, cfg, seeds, wav_dev, ld, n, samples, pos0, gate_lvl_dev, comfort_lvl_dev, lvl_ld, start_gate_level, start_comfort_level, out_dev, out_ld, stream);
+  });
+}
+
 int conan_bypass_mix(conan_ctx* ctx, int hop, const float* wet_dev, int64_t wet_ld, const float* dry_dev, int64_t dry_ld, int n, int64_t samples,
                      const int32_t* wet_lvl_dev, const int32_t* dry_lvl_dev, int64_t lvl_ld, int32_t start_wet, int32_t start_dry, float* out_dev,
                      int64_t out_ld, void* stream) {

@@ -559,6 +559,48 @@ struct BypMixArgs {
 constexpr int kBypMixThreads = 256;
 void launch_bypass_mix(const BypMixArgs& a, hipStream_t st);
 
+// Comfort noise (comfort.hip; include/conan_hip.h, conan_comfort_cfg).  comfort_track_kernel: one thread per row.  A row runs the
+// tracker over its nframes frames - the detector's flags act[in_off + f] and, in follow mode, powers power[in_off + f] - from
+// state[slot] (reseed = 0 and slot >= 0) or from its seed, writes the frame-end levels to lvl[lvl_off + f] and - start_lvl = 1 - the
+// level before the row's first frame to lvl[lvl_off - 1], and the state after the row to state[slot] (slot >= 0) and
+// state_out[state_row] (state_row >= 0).  mode = 0: a row of a slot without the feature (or without a detector), which holds its
+// place in the table so that the fill finds row i of a vocoder step at entry i.  fill = 1: the slot's output is gated (activity
+// mode 2) and the vocoder step fills the row; any other row is skipped there.  pos0: the utterance sample index of the row's first
+// sample in the fill (the front-end's frame position * hop).
+struct CmfState { int level, reserved; long long idle_frames; };
+static_assert(sizeof(CmfState) == 16, "conan_comfort_state");
+struct CmfRow {
+  unsigned long long seed;
+  long long pos0, in_off, lvl_off;
+  CmfState seed_state;
+  int nframes, slot, reseed, state_row, mode, start_lvl;
+  int level, offset, l_min, l_max, up_step, down_step;
+  int colour, fill;
+  float norm;
+  int pad_;
+};
+static_assert(sizeof(CmfRow) == 112, "uploaded as 28 ints");
+struct CmfTrackArgs {
+  const int* act; const double* power;      // power may be null when no row follows
+  int* lvl;
+  CmfState* state;          // [max_slots], indexed by slot; may be null when no row names a slot
+  CmfState* state_out;      // [rows]; may be null when no row has a state_row
+  const CmfRow* tab; int rows;
+};
+constexpr int kCmfTrackThreads = 64;
+void launch_comfort_track(const CmfTrackArgs& a, hipStream_t st);
+// The fill: row i of the launch is x + i * ld -> y + i * ld_y (y may equal x), `samples` samples, sample s being sample tab[i].pos0 + s
+// of the white source; its gate levels are gate_lvl[i * lvl_ld + f] after frame f and before frame 0 start_gate (start_in_lvl = 0) or
+// gate_lvl[i * lvl_ld - 1] (start_in_lvl = 1: the detector's staging rows); its comfort levels cmf_lvl[i * lvl_ld + f].  Rows with
+// tab[i].mode == 0 or fill != 1 are skipped and keep their bits.
+struct CmfFillArgs {
+  const float* x; float* y; const int* gate_lvl; const int* cmf_lvl; const CmfRow* tab;
+  long long ld, ld_y, lvl_ld, samples;
+  int n, hop, start_gate, start_in_lvl;
+};
+constexpr int kCmfFillThreads = 256, kCmfFillPer = 8;
+void launch_comfort_fill(const CmfFillArgs& a, hipStream_t st);
+
 // Input loss concealment (conceal.hip; include/conan_hip.h, conan_conceal_cfg).  conceal_kernel: one workgroup per table row, which
 // repairs `samples` samples of row `row` of the caller's buffer (wav + row * wav_ld dwords, in format fmt) in place from the flags
 // lost[row * lost_ld + m], packet m = samples [m * packet, (m + 1) * packet) of the row.  The state - header, template, the last

@@ -304,6 +304,19 @@ struct conan_streams {
     std::vector<LastRow> last;
   } byp;
   void bypass_init();
+  // comfort noise (conan_streams_set_comfort; comfort.hip; on: mode != 0).  state: [max_slots], read and written by the rows of
+  // comfort_track_kernel in the order of the front-end launches; pending restarts it from the cfg's seed_level.  Rows: as the activity
+  // table's (a slot without a detector holds its place only); beside the table the frame-end levels [q][chunk row][seg + 1] (word 0: the
+  // level before the chunk) on their way to the vocoder stage of the same call, whose fill reads table, levels and the activity set's
+  // gate levels, and the powers [q][chunk row][seg] the detector of a call with a following row stages for the tracker.  Event: behind
+  // the call's last vocoder step; kActSets sets for the reason given there.  last: conan_step_wav_comfort.
+  struct Comfort : SlotSetting<conan_comfort_cfg, &conan_comfort_cfg::mode> {
+    cnk::CmfState* state = nullptr;
+    int* levels[kActSets] = {}; double* powers[kActSets] = {};
+    StageSets<cnk::CmfRow, kActSets> sets;
+    std::vector<LastRow> last;
+  } cmf;
+  void comfort_init();
   // input loss concealment (conan_streams_set_conceal; conceal.hip).  state: [max_slots] records of cnk::kConcStateBytes, read and
   // written by the rows of conceal_kernel in the order of the caller's stream; pending restarts it from zeros (set when a slot that
   // was off is enabled without a seed; a seed clears it).  Rows: per repair call; event: behind the kernel's launch.  No step path
@@ -314,7 +327,7 @@ struct conan_streams {
   } conc;
   void conceal_init();
   // a reset with CONAN_MODEL_FRONTEND: the settings stay; the states restart in the slots' next rows (host flags: no launch)
-  void restart_features(const int32_t* slots, int n) { reg.restart(slots, n); act.restart(slots, n); byp.restart(slots, n); conc.restart(slots, n); }
+  void restart_features(const int32_t* slots, int n) { reg.restart(slots, n); act.restart(slots, n); byp.restart(slots, n); cmf.restart(slots, n); conc.restart(slots, n); }
   void ragged_init();
   void resample_init();        // staging, row tables and the history ring (conan_streams_set_input_rate)
   void rs_stage_init();        // staging and row tables only (conan_streams_set_input_format: no stream state)
@@ -388,6 +401,10 @@ struct conan_streams {
       const cnk::BypRow* tab = nullptr; const int* wet_lvl = nullptr; const int* dry_lvl = nullptr; const float* dry = nullptr;
       int lvl_ld = 0; long long dry_ld = 0;
     } mix;
+    // the step's comfort noise (comfort.hip; filled by comfort::WavStage for a group with a filled row): the group's rows of the call's
+    // comfort table and level staging and of the activity set's gate levels (one stride: both stagings have rows of seg + 1 words);
+    // hifigan_step launches comfort_fill_kernel behind the mix
+    struct Fill { const cnk::CmfRow* tab = nullptr; const int* cmf_lvl = nullptr; const int* gate_lvl = nullptr; int lvl_ld = 0; } fill;
     // the step's output levelling (level_out.hip; out_plan's, for a step with a levelled row): one table row per step row;
     // hifigan_step launches level_out_apply_kernel behind conv_post and level_out_meter_kernel behind the step's last launch
     std::vector<cnk::OlRow> lvl_rows;
@@ -658,7 +675,7 @@ struct WavCall {
 };
 // The front-end work of a wav-in call: at most one entry per position, run in this order on one stream (the caller's, or as
 // step_pipelined's `pre`).  The ...End entries record the events of the sets the mel front-end launch is the last to read.
-enum FrontPos { kFrResample, kFrLevel, kFrMel, kFrLevelEnd, kFrResampleEnd, kFrF0, kFrRegister, kFrActivity, kFrBypass, kFrCount };
+enum FrontPos { kFrResample, kFrLevel, kFrMel, kFrLevelEnd, kFrResampleEnd, kFrF0, kFrRegister, kFrActivity, kFrBypass, kFrComfort, kFrCount };
 struct FrontWork {
   std::function<void(hipStream_t)> at[kFrCount];
   void run(hipStream_t st) const { for (const auto& f : at) if (f) f(st); }
@@ -823,6 +840,7 @@ struct WavStage {
   std::vector<LastRow> last;
   std::vector<char> gate;       // per emit group: a row of it is gated (empty: no table)
   int q = 0;
+  double* power = nullptr;      // the call's power staging (comfort::WavStage::take: a row of the call follows), in the flags' row layout
   void plan(const conan_streams* s, const WavCall& c);
   void enqueue(conan_streams* s, const WavCall& c, hipStream_t cst, FrontWork& front, std::vector<conan_streams::OutPlan>& ops);
   void commit(conan_streams* s, hipStream_t dec, hipStream_t last_st);
@@ -853,6 +871,36 @@ struct WavStage {
   void commit(conan_streams* s, hipStream_t dec, hipStream_t last_st);
 };
 }  // namespace byp
+
+// ---- comfort noise (comfort.hip): the kernels' host side and the bodies of api.hip's entry points
+namespace comfort {
+void check_cfg(const conan_comfort_cfg& c, const char* who);      // host only
+cnk::CmfRow row(const conan_comfort_cfg& c);      // the cfg's fields of a tracker row that starts from the seed and names no slot
+void track(conan_ctx* ctx, const conan_comfort_cfg* cfg, const int32_t* act_dev, const double* power_dev, int n, int64_t frames, int64_t ld,
+           int32_t* level_out_dev, conan_comfort_state* state_out_dev, void* stream);
+void fill(conan_ctx* ctx, int hop, const conan_comfort_cfg* cfg, const uint64_t* seeds, const float* wav_dev, int64_t ld, int n, int64_t samples, int64_t pos0,
+          const int32_t* gate_lvl_dev, const int32_t* comfort_lvl_dev, int64_t lvl_ld, int32_t start_gate_level, int32_t start_comfort_level, float* out_dev,
+          int64_t out_ld, void* stream);
+void set_comfort(conan_streams* s, const int32_t* slots, int n, const conan_comfort_cfg* cfg, void* stream);
+void state(conan_streams* s, const int32_t* slots, int n, conan_comfort_state* state_dev, void* stream);
+void last_call(conan_streams* s, int32_t* level_dev, void* stream);
+// As the activity table, and with its rows: one row per emitting call row in a call in which a slot with the feature and a detector
+// emits.  take() runs in front of the detector's enqueue: it takes the staging set and returns the power staging the detector is to
+// write (null: no row of the call follows).  The tracker runs behind the detector (gate_stage: the call's activity stage) and the
+// bypass's stage; the groups with a filled row take their rows of table, levels and gate levels along.
+struct WavStage {
+  std::vector<cnk::CmfRow> rows;
+  std::vector<LastRow> last;
+  std::vector<char> fill;       // per emit group: a row of it is filled (empty: no table)
+  bool follows = false;         // a row reads the detector's powers
+  int q = 0;
+  const act::WavStage* gate_stage = nullptr;
+  void plan(const conan_streams* s, const WavCall& c);
+  double* take(conan_streams* s, hipStream_t cst);
+  void enqueue(conan_streams* s, const WavCall& c, hipStream_t cst, FrontWork& front, std::vector<conan_streams::OutPlan>& ops);
+  void commit(conan_streams* s, hipStream_t dec, hipStream_t last_st);
+};
+}  // namespace comfort
 
 // ---- input loss concealment (conceal.hip): the kernel's host side and the bodies of api.hip's entry points
 namespace conc {

@@ -641,6 +641,12 @@ void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float*
       b.wet_ld = T; b.out_ld = T; b.dry_ld = op->mix.dry_ld; b.lvl_ld = op->mix.lvl_ld; b.samples = T; b.n = n; b.hop = ctx->hop; b.start_in_lvl = 1;
       profiled("bypass_mix_kernel", 0.0, st, [&] { cnk::launch_bypass_mix(b, st); });
     }
+    if (op && op->fill.tab) {      // the comfort noise of a wav-in step (comfort.hip), behind the mix, in place on the same rows
+      cnk::CmfFillArgs f; memset(&f, 0, sizeof(f));
+      f.x = a.wav; f.y = a.wav; f.gate_lvl = op->fill.gate_lvl; f.cmf_lvl = op->fill.cmf_lvl; f.tab = op->fill.tab;
+      f.ld = T; f.ld_y = T; f.lvl_ld = op->fill.lvl_ld; f.samples = T; f.n = n; f.hop = ctx->hop; f.start_in_lvl = 1;
+      profiled("comfort_fill_kernel", 0.0, st, [&] { cnk::launch_comfort_fill(f, st); });
+    }
     if (out_rows) resample_out(*op, oq, T, st);
     if (levelled) {      // ... and its meter, off the audio's path: the staged samples into the slots' state, for the next step's ramp
       cnk::LevelOutMeterArgs l; memset(&l, 0, sizeof(l));

@@ -229,6 +229,7 @@ class StreamingVoiceConversionEngine:
         self._activity = False      # set_activity has been called on the stream-set
         self._bypass = False        # set_bypass has been called on the stream-set
         self._conceal = False       # set_conceal has been called on the stream-set
+        self._comfort = False       # set_comfort has been called on the stream-set
 
     @staticmethod
     def _check_voice(ref_mel, voice):
@@ -281,7 +282,7 @@ class StreamingVoiceConversionEngine:
         self._set_out_level(self.slots, out_level)
 
     def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, **filter):
+                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
         in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
         in_format: the input's sample format (None: float32; 's16' takes int16 rows, 'ulaw' / 'alaw' uint8), decoded on the GPU.
@@ -301,7 +302,9 @@ class StreamingVoiceConversionEngine:
         True: enabled at full wet (a later set_bypass toggles it); a dict of set_bypass's keywords.  chunk_bypass() reads
         the last call's levels.  conceal: loss concealment of the input rows (Streams.set_conceal) - None / False: none; True: the
         defaults of the slot's input rate; a dict of conan_conceal_cfg's fields over them.  feed(lost=...) then repairs the packets
-        that never arrived, on the GPU in front of the step.
+        that never arrived, on the GPU in front of the step.  comfort: comfort noise in the closed activity gate
+        (Streams.set_comfort; activity= beside it) - None / False: none; True: the defaults; a dict of set_comfort's keywords; the
+        seed defaults to one derived from the slot's index.  chunk_comfort() reads the last call's levels.
         There is no trim= here: silence trimming (infer_wav(trim=True)) moves audio forward over pauses it has seen whole, and a
         stream cannot drop time it has not heard yet; activity= is what a live call has in its place."""
         self._check_voice(ref_mel, voice)
@@ -309,6 +312,7 @@ class StreamingVoiceConversionEngine:
         activities = self._activities(self.slots, activity)
         bypasses = self._bypasses(self.slots, bypass)
         conceals = self._conceals(self.slots, conceal)
+        comforts = self._comforts(self.slots, comfort)
         if isinstance(in_format, (list, tuple)) or isinstance(level, (list, tuple)):
             raise ValueError("in_format / level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
         self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice,
@@ -321,6 +325,7 @@ class StreamingVoiceConversionEngine:
         self._set_activity(self.slots, activities)
         self._set_bypass(self.slots, bypasses)
         self._set_conceal(self.slots, conceals, [in_rate] * len(self.slots))
+        self._set_comfort(self.slots, comforts)
 
     @staticmethod
     def _activities(slots, activity):
@@ -386,6 +391,46 @@ class StreamingVoiceConversionEngine:
         its levels and slews to the new targets - the toggle).  In force from the next emitted chunk."""
         self._bypass = True
         self.st.set_bypass(self.slots if slots is None else slots, cfg, **kw)
+
+    @staticmethod
+    def _comforts(slots, comfort):
+        """comfort= (one value or one per slot) -> per slot None or a dict of Streams.set_comfort's keywords.  Host only."""
+        values = list(comfort) if isinstance(comfort, (list, tuple)) else [comfort] * len(slots)
+        if len(values) != len(slots):
+            raise ValueError(f"comfort: {len(values)} values for {len(slots)} slots")
+        out = []
+        for b in values:
+            if b is None or b is False:
+                out.append(None)
+            elif b is True:
+                out.append({})
+            elif isinstance(b, dict):
+                out.append(dict(b))
+            else:
+                raise ValueError(f"comfort: {b!r} (True, a dict of set_comfort's keywords or None)")
+        return out
+
+    def _set_comfort(self, slots, comforts):
+        """The slots' comfort noise from _comforts' list, behind the slots' reset: the levels restart from their start level at the
+        first emitted chunk.  A slot's seed defaults to _lib.comfort_seed(slot).  A stream-set that never used it is left alone."""
+        if all(b is None for b in comforts) and not self._comfort:
+            return
+        self._comfort = True
+        for slot, b in zip(slots, comforts):
+            self.st.set_comfort([slot], cfg=None if b is None else dict(dict(seed=_lib.comfort_seed(slot)), **b))
+
+    def set_comfort(self, slots=None, cfg=True, **kw):
+        """A live change of the slots' comfort noise (all slots by default) between feed / feed_ragged calls, also mid-utterance and
+        with pipelined steps in flight: Streams.set_comfort's arguments (cfg=None turns it off; without reseed=True an enabled slot
+        keeps its level).  In force from the next emitted chunk."""
+        self._comfort = True
+        self.st.set_comfort(self.slots if slots is None else slots, cfg, **kw)
+
+    def chunk_comfort(self):
+        """The frame-end comfort levels of the last feed / feed_ragged call (Streams.step_wav_comfort; joins pipelined work): [n, seg]
+        int32 in the call's row order, zeros for rows without the feature and past a row's frames; _lib.comfort_dbov(level) is the
+        RFC 3389 noise level byte of a frame."""
+        return self.st.step_wav_comfort()
 
     @staticmethod
     def _conceals(slots, conceal):
@@ -712,7 +757,7 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
                   out_format=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None, register=None, activity=None,
-                  activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, **filter):
+                  activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, comfort=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] (or None with voice = (bank, ids): start) -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
@@ -744,6 +789,7 @@ class StreamingVoiceConversionEngine:
         self._activities(self.slots, activity)
         self._bypasses(self.slots, bypass)
         self._conceals(self.slots, conceal)
+        self._comforts(self.slots, comfort)
         self._check_lost(lost, conceal, loud_norm, trim)
         trim = self._trim_keywords(trim)
         if trim is not None:
@@ -752,7 +798,7 @@ class StreamingVoiceConversionEngine:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
                        pitch=pitch, voice=voice, follow=follow, register=register, activity=activity, bypass=bypass, out_level=out_level, conceal=conceal,
-                       **filter)
+                       comfort=comfort, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -784,7 +830,7 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, **filter):
+                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
         rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
@@ -803,6 +849,7 @@ class StreamingVoiceConversionEngine:
         activities = self._activities(slots, activity)
         bypasses = self._bypasses(slots, bypass)
         conceals = self._conceals(slots, conceal)
+        comforts = self._comforts(slots, comfort)
         self.st.reset(slots, which=7 | 8)
         self._reference(slots, ref_mel, ref_len, voice)
         self._set_out_rate(slots, out_rate, out_filter)
@@ -817,6 +864,7 @@ class StreamingVoiceConversionEngine:
         self._set_activity(slots, activities)
         self._set_bypass(slots, bypasses)
         self._set_conceal(slots, conceals, _per_slot(in_rate, len(slots)))
+        self._set_comfort(slots, comforts)
         self._set_out_level(slots, out_level)
 
     @torch.no_grad()
@@ -840,7 +888,7 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
                             in_formats=None, out_formats=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None,
-                            register=None, activity=None, activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, **filter):
+                            register=None, activity=None, activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, comfort=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -876,6 +924,7 @@ class StreamingVoiceConversionEngine:
         registers = self._registers(range(U), register, voice)      # (host checks before anything runs; per utterance, as dicts)
         activities = self._activities(range(U), activity)
         bypasses = self._bypasses(range(U), bypass)
+        comforts = self._comforts(range(U), comfort)
         if activity_log is not None:
             activity_log[:] = [[] for _ in range(U)]
         follows = list(follow) if isinstance(follow, (list, tuple)) else [follow] * U
@@ -909,7 +958,7 @@ class StreamingVoiceConversionEngine:
                                 out_format=[ofmts[u] for u in new], level=[levels[u] for u in new], pitch=[pitches[u] for u in new],
                                 follow=[follows[u] for u in new], register=[registers[u] for u in new], activity=[activities[u] for u in new],
                                 bypass=[bypasses[u] for u in new], out_level=[out_levels[u] for u in new], conceal=[conceals[u] for u in new],
-                                **filter)
+                                comfort=[comforts[u] for u in new], **filter)
             if not live:
                 tick += 1
                 continue

@@ -37,6 +37,14 @@ def _activity_states(buf):
     return [_lib.activity_state_dict(_lib.ActivityState.from_buffer_copy(raw[i * size:(i + 1) * size])) for i in range(buf.shape[0])]
 
 
+def _comfort_states(buf):
+    """uint8 [n, sizeof(conan_comfort_state)] on the device -> a list of dict(level, idle_frames) (synchronises)."""
+    raw = buf.cpu().numpy().tobytes()
+    size = C.sizeof(_lib.ComfortState)
+    states = [_lib.ComfortState.from_buffer_copy(raw[i * size:(i + 1) * size]) for i in range(buf.shape[0])]
+    return [dict(level=int(s.level), idle_frames=int(s.idle_frames)) for s in states]
+
+
 # torch dtype of a row in each sample format (conan_streams_set_input_format / _output_format, conan_convert_samples)
 SAMPLE_DTYPES = {"f32": torch.float32, "s16": torch.int16, "ulaw": torch.uint8, "alaw": torch.uint8}
 
@@ -417,6 +425,72 @@ class Context:
                 raise ValueError("bypass_mix: out must be a float32 tensor of wet's shape on the device, contiguous or a 2-D view with contiguous rows")
         _lib.check(self.lib.conan_bypass_mix(self.h, int(hop_size or self.hop), _ptr(x), x_ld, _ptr(d), d_ld, n, N, _ptr(lw), _ptr(ldv), lw_ld,
                                              int(start[0]), int(start[1]), _ptr(y), y_ld, _stream()))
+        return y
+
+    def comfort_track(self, act, power, cfg=None, return_state=False, **kw):
+        """The comfort noise's tracker on whole signals (conan_comfort_track; include/conan_hip.h, conan_comfort_cfg): act [..., F]
+        int32 and power [..., F] float64 as Context.activity returns them -> the frame-end comfort levels [..., F] int32, every row
+        from the cfg's start level.  cfg: an _lib.ComfortCfg, or **kw: _lib.comfort_cfg's keywords.  return_state=True appends the
+        rows' states, a list of dict(level, idle_frames).  It is what a wav-in slot with Streams.set_comfort tracks, bit for bit."""
+        dev = torch.device("cuda", self.device)
+        c = cfg if cfg is not None else _lib.comfort_cfg(**kw)
+        a = act.to(dev, torch.int32).contiguous()
+        lead, F = a.shape[:-1], a.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        p = None
+        if power is not None:
+            p = power.to(dev, torch.float64).contiguous()
+            if p.shape != a.shape:
+                raise ValueError(f"comfort_track: act {tuple(a.shape)} and power {tuple(p.shape)} differ in shape")
+        out = torch.empty(a.shape, dtype=torch.int32, device=dev)
+        st = torch.empty(n, 16, dtype=torch.uint8, device=dev) if return_state else None
+        _lib.check(self.lib.conan_comfort_track(self.h, C.byref(c), _ptr(a), _ptr(p), n, F, F, _ptr(out), _ptr(st), _stream()))
+        if not return_state:
+            return out
+        return out, _comfort_states(st)
+
+    def comfort_fill(self, wav, gate_levels, comfort_levels, cfg=None, seeds=None, start=(_lib.ACTIVITY_FULL, 0), pos0=0, hop_size=None, out=None, **kw):
+        """The comfort noise's fill on whole signals (conan_comfort_fill): wav [..., N] float32 (the audio behind the gate and the
+        mix) with the frame-end gate levels gate_levels [..., >= ceil(N / hop)] int32 in 0 .. 2^20 (Streams.step_wav_activity's) and
+        comfort levels comfort_levels (Streams.step_wav_comfort's, or comfort_track's); start = (gate level, comfort level) before
+        frame 0 -> [..., N].  Sample s of a row is sample pos0 + s of the white source.  cfg: an _lib.ComfortCfg, or **kw:
+        _lib.comfort_cfg's keywords (colour, norm and seed are read); seeds: one seed per row instead of the cfg's.  A 2-D operand
+        whose rows are contiguous keeps its row stride; out=wav fills in place.  An open gate keeps wav's bits.  It is what a wav-in
+        slot with Streams.set_comfort computes, bit for bit."""
+        dev = torch.device("cuda", self.device)
+        c = cfg if cfg is not None else _lib.comfort_cfg(**kw)
+
+        def rows(t, dtype):
+            t = t.to(dev, dtype)
+            if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
+                return t, t.stride(0)
+            t = t.contiguous()
+            return t, t.shape[-1]
+
+        x, x_ld = rows(wav, torch.float32)
+        lg, lg_ld = rows(gate_levels, torch.int32)
+        lc, lc_ld = rows(comfort_levels, torch.int32)
+        lead, N = x.shape[:-1], x.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        if lg.shape[:-1] != lead or lc.shape != lg.shape:
+            raise ValueError(f"comfort_fill: wav {tuple(x.shape)}, gate_levels {tuple(lg.shape)} and comfort_levels {tuple(lc.shape)} do not match")
+        if lc_ld != lg_ld:
+            lg, lc = lg.contiguous(), lc.contiguous()
+            lg_ld = lc_ld = lg.shape[-1]
+        sd = None
+        if seeds is not None:
+            sd = np.ascontiguousarray(np.asarray([int(v) & ((1 << 64) - 1) for v in seeds], dtype=np.uint64))
+            if sd.shape[0] != n:
+                raise ValueError(f"comfort_fill: {sd.shape[0]} seeds for {n} rows")
+        if out is None:
+            y, y_ld = torch.empty(x.shape, dtype=torch.float32, device=dev), N
+        else:
+            y, y_ld = (out, out.stride(0)) if out.dim() == 2 and out.stride(1) == 1 else (out, N)
+            if y.shape != x.shape or y.dtype != torch.float32 or y.device != dev or not (y.is_contiguous() or (y.dim() == 2 and y.stride(1) == 1 and y_ld >= N)):
+                raise ValueError("comfort_fill: out must be a float32 tensor of wav's shape on the device, contiguous or a 2-D view with contiguous rows")
+        _lib.check(self.lib.conan_comfort_fill(self.h, int(hop_size or self.hop), C.byref(c), sd.ctypes.data_as(C.c_void_p) if sd is not None else None,
+                                               _ptr(x), x_ld, n, N, int(pos0), _ptr(lg), _ptr(lc), lg_ld, int(start[0]), int(start[1]), _ptr(y), y_ld,
+                                               _stream()))
         return y
 
     def register_of(self, wav, **f0_keywords):
@@ -1068,6 +1142,59 @@ class Streams:
         _lib.check(self.lib.conan_step_wav_bypass(self.h, _ptr(wet), _ptr(dry), _stream()))
         self._release()
         return wet[:n], dry[:n]
+
+    def set_comfort(self, slots, cfg=True, **kw):
+        """conan_streams_set_comfort: comfort noise in place of the silence of a closed activity gate (wav-in steps only; the slot needs
+        set_activity beside it, and is filled where that gates the output).  Synthetic noise at the level of the source's background
+        - tracked per frame from the detector's flags and frame powers - is cross-faded against the gate's ramp, behind the wet/dry
+        mix and in front of the output resampler and encoder; nothing of the caller's room passes.  **kw / a dict in cfg:
+        _lib.comfort_cfg's keywords (follow, level_db, offset_db, min_db, max_db, rise_db, fall_db, colour, start_db, seed, reseed);
+        cfg may also be an _lib.ComfortCfg; only cfg=None turns it off.  The defaults are choices, not measurements.
+        It may be called at any time (it joins pipelined work); the change takes effect from the next emitted chunk and survives
+        resets.  The level restarts from the start level when a slot is enabled, after reseed=True and at the first chunk after a
+        reset of the front-end; reseed=False on an enabled slot replaces the parameters and keeps the level.  Slot snapshots do not
+        carry it: query comfort_state, export, import, then set_comfort(start=level, reseed=True)."""
+        a, p = _i32(slots)
+        if cfg is None:
+            if kw:
+                raise ValueError("set_comfort: cfg=None turns the comfort noise off and takes no keywords")
+            c = _lib.ComfortCfg()      # (mode = 0)
+        elif isinstance(cfg, _lib.ComfortCfg):
+            c = cfg
+        else:
+            c = _lib.comfort_cfg(**dict({} if cfg is True else cfg, **kw))
+        _lib.check(self.lib.conan_streams_set_comfort(self.h, p, len(a), C.byref(c), _stream()))
+        self._release()
+
+    def comfort(self, slots):
+        """conan_streams_comfort: per slot the setting as _lib.comfort_keywords reports it (set_comfort takes it back), None for a slot
+        without the feature."""
+        out = []
+        for slot in slots:
+            c = _lib.ComfortCfg()
+            _lib.check(self.lib.conan_streams_comfort(self.h, int(slot), C.byref(c)))
+            out.append(_lib.comfort_keywords(c) if c.mode else None)
+        return out
+
+    def comfort_state(self, slots):
+        """conan_streams_comfort_state (joins pipelined work, synchronises): per slot dict(level, idle_frames), the comfort level after
+        the slot's last emitted frame; a slot whose level is about to restart reports its start level.  A slot without the feature
+        is an error."""
+        a, p = _i32(slots)
+        buf = torch.empty(len(a), 16, dtype=torch.uint8, device=self.dev)
+        _lib.check(self.lib.conan_streams_comfort_state(self.h, p, len(a), _ptr(buf), _stream()))
+        self._release()
+        return _comfort_states(buf)
+
+    def step_wav_comfort(self):
+        """The frame-end comfort levels the last wav-in call produced (conan_step_wav_comfort; joins pipelined work) -> [n, seg] int32
+        in call order; rows without the feature (or without a detector), rows that emitted nothing and entries past a row's emitted
+        frames are 0.  _lib.comfort_dbov turns a level into the RFC 3389 noise level byte."""
+        n = self._last_wav_n
+        lvl = torch.empty(max(n, 1), self.seg, dtype=torch.int32, device=self.dev)      # (before any wav-in call the library answers CONAN_ERR_STATE)
+        _lib.check(self.lib.conan_step_wav_comfort(self.h, _ptr(lvl), _stream()))
+        self._release()
+        return lvl[:n]
 
     def step_wav_contour(self):
         """The contour the last wav-in call handed the decoder (conan_step_wav_contour; joins pipelined work) -> (f0 [n, seg] log2 Hz,

@@ -1056,6 +1056,109 @@ int conan_bypass_mix(conan_ctx* ctx, int hop, const float* wet_dev, int64_t wet_
                      const int32_t* wet_lvl_dev, const int32_t* dry_lvl_dev, int64_t lvl_ld, int32_t start_wet, int32_t start_dry, float* out_dev,
                      int64_t out_ld, void* stream);
 
+/* Comfort noise (added within ABI 9: a caller detects it by the symbol conan_streams_set_comfort; no existing struct or call changes).
+ * A synthetic fill for the closed activity gate: noise at the level of the source's background, cross-faded against the gate's ramp so
+ * that nothing clicks, in front of the output resampler and the format encoder - and per frame a level the host can send as RFC 3389
+ * SID packets while it does not transmit.  Unlike the bypass's fill_gate it passes nothing of the caller's room.  The law
+ * (tests/comfort_ref.py restates it in numpy with Python integers) is integer operations and single correctly rounded IEEE
+ * operations; no libm function is part of it and nothing has a tolerance:
+ *   Levels are integers L in units of 1/256 octave of power relative to full scale: L = 0 is power 1.0, -256 is power 0.5, about 85.04
+ *     units are one dB.  Every level of the cfg and of the state lies in -16384 .. 0.
+ *   Quantising.  With P the detector's P of the frame (conan_activity_cfg's law; a double >= 0) and bits(P) its raw 64-bit word:
+ *     Lq(P) = (int)(bits(P) >> 44) - (1023 << 8), the biased exponent and the top 8 mantissa bits.  Zeros and denormals give about
+ *     -261888; the clamp takes them.
+ *   Tracker, per emitted frame f, with act_f and P_f of the slot's detector in the same call.  mode 2 (follow) and act_f == 0:
+ *     target = clamp(Lq(P_f) + offset, l_min, l_max), L += clamp(target - L, -down_step, up_step), idle_frames += 1; act_f == 1: L
+ *     holds.  mode 1 (fixed): L = clamp(level, l_min, l_max) on every frame.  A slot without a detector has no frames here: L holds.
+ *   Amplitude of frame f, from the level L after the tracker's step of that frame (L <= 0): e = floor(L / 512), r = L - 512 * e in
+ *     0 .. 511, a = ldexpf((float)(512 + r), e - 9), which is exact: the octave in e, a linear piece inside it; A_f = a * norm, one f32
+ *     product, with norm the cfg's f32: the amplitude of one unit of v at L = 0.
+ *   White source.  j = the utterance sample index f * hop + k, f being the front-end frame index the gate uses, taken as int64 in
+ *     two's complement (the taps before sample 0 have j < 0); all arithmetic in uint64:
+ *       z = seed + (uint64)(j + 1) * 0x9E3779B97F4A7C15;  z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;
+ *       z *= 0x94D049BB133111EB;  z ^= z >> 31;  w(j) = (int)(z & 0xFFFF) + (int)((z >> 16) & 0xFFFF) - 65535,
+ *     triangular in -65535 .. 65535.  A sample depends on seed and j alone, never on the launch, the call cut or the other rows.
+ *   Colour.  v(j) = sum_i c[i] * w(j - i) with the integer taps {1} (colour 0), {1, 2, 1} (1) or {1, 2, 3, 2, 1} (2); |v| <= 9 * 65535,
+ *     so (float)v is exact.
+ *   Fill.  With l the gate's integer of the sample, lvl_prev * (hop - 1 - k) + lvl' * (k + 1) as in the activity section's gain law,
+ *     and y the sample behind the gate and the wet/dry mix: lc = ((int64)hop << 20) - l; gc = (float)((double)lc / (double)(hop << 20));
+ *     t = (float)v * A_f (one f32 product); out = lc == 0 ? y : fmaf(t, gc, y).  An open gate keeps y's bits, and so does an absent
+ *     one: a slot that is not in activity mode 2 counts as open (the bypass's fill_gate rule).  Where both of a frame's gate levels are
+ *     2^20 nothing is hashed.
+ *   Restart.  The state restarts from level = seed_level, idle_frames = 0 at the slot's first emitted chunk after a reset that includes
+ *     CONAN_MODEL_FRONTEND, after a setter call with reseed = 1 and when a slot that was off is enabled.  A setter call with reseed = 0
+ *     on an enabled slot replaces the parameters and keeps L.
+ * conan_amd/_lib.py's comfort_cfg takes decibels and forms norm = (float)(1 / (sqrt((65536^2 - 1) / 6) * sqrt(sum c^2))) once on the
+ * host (the rms of v is 1 at L = 0); it gives follow mode, an offset of -3 dB, limits of -90 .. -30 dBov, a rise of 0.25 dB and a fall
+ * of 2 dB per frame, colour 1 and a seed level of -70 dBov.  Those defaults are choices, not measurements. */
+typedef struct conan_comfort_cfg {
+  int32_t  mode;           /* 0: off (other fields ignored), 1: fixed level, 2: follow the source's background */
+  int32_t  reseed;         /* 0 | 1: the state restarts from seed_level */
+  int32_t  level;          /* -16384 .. 0: the fixed mode's level */
+  int32_t  offset;         /* -16384 .. 16384: added to the quantised frame power in follow mode */
+  int32_t  l_min, l_max;   /* -16384 .. 0, l_min <= l_max */
+  int32_t  up_step, down_step;   /* 1 .. 16384: the level's largest rise and fall per 20 ms frame */
+  int32_t  colour;         /* 0 .. 2 */
+  int32_t  seed_level;     /* -16384 .. 0 */
+  float    norm;           /* finite, > 0 */
+  int32_t  reserved;       /* must be 0 */
+  uint64_t seed;           /* of the white source */
+} conan_comfort_cfg;       /* 56 bytes */
+typedef struct conan_comfort_state {
+  int32_t level;           /* L after the last emitted frame */
+  int32_t reserved;
+  int64_t idle_frames;     /* inactive frames followed since the restart */
+} conan_comfort_state;     /* 16 bytes */
+/* Sets (cfg->mode = 1 | 2) or removes (0) the comfort noise for `slots`.  Every argument is checked before anything changes
+ * (CONAN_ERR_INVALID: mode not 0 .. 2, reseed not 0 / 1, a level outside -16384 .. 0, l_min > l_max, offset outside -16384 .. 16384, a
+ * step outside 1 .. 16384, colour outside 0 .. 2, norm not finite or <= 0, reserved not 0), a stream-set without the streaming
+ * front-end is CONAN_ERR_STATE, and pending pipelined work is joined; it may be called at any time, also mid-utterance.  The change
+ * takes effect from the next emitted chunk and persists across resets.
+ * What a slot with the feature does.  Every conan_step_wav[_async] / conan_step_wav_ragged[_ld][_async] call that emits a chunk for it
+ * while it also has an activity detector (conan_streams_set_activity, mode 1 or 2) runs the tracker over the chunk's frames - those
+ * the detector saw, whose flags and, for a following slot, powers it reads: ONE more launch per call (cnk::comfort_track_kernel,
+ * behind the detector's and the bypass's stage; none in calls in which no such slot emits); the detector of such a call also stages
+ * its frame powers, with the same kernel.  There is no ring requirement beyond the detector's.  Where the slot is in activity mode 2
+ * the chunk's vocoder step fills the rows conv_post wrote, in place, behind the activity gate and the wet/dry mix and in front of the
+ * output resampler and the format encoder: ONE more launch (cnk::comfort_fill_kernel) per vocoder step in which such a row takes part
+ * - each emit group of a ragged call is such a step - and none otherwise; rows without the feature or without a gate are skipped and
+ * keep their bits.  conan_streams_flush_output and the resampler's ring see filled audio.  The mel-in steps (conan_step[_async]) and
+ * conan_hifigan_step* take no waveform: they neither track nor fill.
+ * Memory: the first enabling call allocates 16 bytes of state per slot, 8 staging sets of (segment + 1) int32 and segment doubles per
+ * slot, and 8 row tables; conan_streams_state_bytes counts them from then on.  A stream-set that never calls the setter allocates
+ * nothing and runs exactly the launches it ran before.
+ * Snapshots carry neither the setting nor the state (the 256-byte host record is full); conan_streams_layout_id and
+ * conan_streams_snapshot_bytes do not change.  The hand-over: conan_streams_comfort_state, export, import, then this setter with
+ * seed_level = the queried level and reseed = 1 (beside the activity hand-over).  The noise's position needs nothing: it is the
+ * front-end's frame position, which snapshots carry. */
+int conan_streams_set_comfort(conan_streams* s, const int32_t* slots, int n, const conan_comfort_cfg* cfg, void* stream);
+/* Host only: the comfort cfg of `slot` as set, reseed = 0 (mode = 0 and zeros for a slot without one). */
+int conan_streams_comfort(const conan_streams* s, int slot, conan_comfort_cfg* cfg_out);
+/* The states of `slots` -> state_dev[n], in the order of `stream` behind a join of pipelined work; a slot whose state is about to
+ * restart reports its seed.  A slot without the feature is CONAN_ERR_STATE. */
+int conan_streams_comfort_state(conan_streams* s, const int32_t* slots, int n, conan_comfort_state* state_dev, void* stream);
+/* The frame-end comfort levels the last wav-in call produced, in call order (joins first): level_dev[n][seg], int32.  Rows without
+ * the feature (or without a detector), rows that emitted nothing and positions behind the emitted frames read zero.  CONAN_ERR_STATE
+ * before any wav-in call. */
+int conan_step_wav_comfort(conan_streams* s, int32_t* level_dev, void* stream);
+/* The whole-signal tracker, on conan_activity's outputs: act_dev[n][.] (int32) and power_dev[n][.] (double; may be NULL in fixed
+ * mode), `frames` frames per row, row stride ld >= frames -> level_out_dev[n][.] (int32, row stride ld: the level after each frame)
+ * and state_out_dev[n] (may be NULL).  Every row starts from seed_level.  cfg->mode must be 1 or 2; n in 1 .. 65535.  One launch
+ * (cnk::comfort_track_kernel) on `stream`. */
+int conan_comfort_track(conan_ctx* ctx, const conan_comfort_cfg* cfg, const int32_t* act_dev, const double* power_dev, int n, int64_t frames, int64_t ld,
+                        int32_t* level_out_dev, conan_comfort_state* state_out_dev, void* stream);
+/* The fill on whole signals, and the bit-exact yardstick of the streaming one: row i of wav_dev (n rows in 1 .. 65535 of `samples`
+ * samples, row stride ld; sample s of a row is sample pos0 + s of the white source, pos0 >= 0, and frame s / hop of the levels) with the
+ * frame-end gate levels gate_lvl_dev[i][.] (int32, 0 .. 2^20) and comfort levels comfort_lvl_dev[i][.] (int32, -16384 .. 0), both of row
+ * stride lvl_ld >= ceil(samples / hop), and start_gate_level as the gate level before frame 0 -> out_dev (row stride out_ld; may equal
+ * wav_dev with out_ld = ld).  start_comfort_level (-16384 .. 0) is the comfort level before frame 0: it is checked, and the law does
+ * not read it, because a frame's amplitude is that of its own frame-end level.  seeds: host, n entries (row i's seed), or NULL: every
+ * row takes cfg->seed.  Of cfg, colour, norm and seed are read (mode must be 1 or 2).  A last frame that the samples cover only partly
+ * is filled over the part they cover.  One launch (cnk::comfort_fill_kernel) on `stream`. */
+int conan_comfort_fill(conan_ctx* ctx, int hop, const conan_comfort_cfg* cfg, const uint64_t* seeds, const float* wav_dev, int64_t ld, int n, int64_t samples,
+                       int64_t pos0, const int32_t* gate_lvl_dev, const int32_t* comfort_lvl_dev, int64_t lvl_ld, int32_t start_gate_level,
+                       int32_t start_comfort_level, float* out_dev, int64_t out_ld, void* stream);
+
 /* Live output levelling (added within ABI 9: a caller detects it by the symbol conan_streams_set_output_level; no existing struct or
  * call changes).  conan_level_cfg's law, exactly as stated above, on the slot's own vocoder audio, with three substitutions: x_t is
  * the slot's model-rate vocoder sample t as conv_post wrote it, position 0 being the slot's first sample after a reset that
