@@ -8,6 +8,7 @@ import ctypes as C
 import math
 import os
 import re
+import typing
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libconan_hip.so")
@@ -103,8 +104,6 @@ _PROTOS = {
     "conan_resample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_loud_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "conan_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
-    "conan_streams_set_input_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "conan_streams_input_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "conan_streams_set_input_rate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "conan_streams_set_output_rate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "conan_streams_set_output_ld": (C.c_int, [C.c_void_p, C.c_int64]),
@@ -134,49 +133,26 @@ _PROTOS = {
     "conan_streams_import_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "conan_slot_meta_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "conan_slot_meta_level": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "conan_streams_set_pitch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "conan_streams_pitch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "conan_decoder_step_pitch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
     "conan_slot_meta_pitch": (C.c_int, [C.c_void_p, C.c_void_p]),
     "conan_f0": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
-    "conan_streams_set_pitch_follow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "conan_streams_pitch_follow": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "conan_step_wav_contour": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_f0_register": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "conan_streams_set_pitch_register": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "conan_streams_pitch_register": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
-    "conan_streams_pitch_register_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "conan_activity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_int32), C.c_void_p]),
     "conan_activity_gate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
-    "conan_streams_set_activity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "conan_streams_activity": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
-    "conan_streams_activity_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "conan_step_wav_activity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "conan_streams_set_bypass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "conan_streams_bypass": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
-    "conan_streams_bypass_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "conan_step_wav_bypass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_bypass_mix": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                    C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
-    "conan_streams_set_comfort": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "conan_streams_comfort": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
-    "conan_streams_comfort_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "conan_step_wav_comfort": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_comfort_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_comfort_fill": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                      C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
-    "conan_streams_set_output_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "conan_streams_output_level_cfg": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
-    "conan_streams_output_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "conan_streams_output_level_state_bytes": (C.c_int64, [C.c_void_p]),
-    "conan_streams_output_level_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
-    "conan_streams_set_conceal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "conan_streams_conceal_cfg": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "conan_streams_conceal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_conceal_state_bytes": (C.c_int64, []),
-    "conan_streams_conceal_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_conceal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_trim_silence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
@@ -630,6 +606,66 @@ def conceal_cfg(rate=None, **kw):
     if missing:
         raise ValueError(f"conceal: without a rate the fields {missing} must be given")
     return ConcealCfg(1, *[int(f[n]) for n in names])
+
+
+class SlotFeature(typing.NamedTuple):
+    """One per-slot feature of a stream-set, as Streams and the engine read it.  A symbol the library does not have is None."""
+    keyword: str                  # the engine's keyword (start_wav, open_slots, ...)
+    noun: str                     # "cfg=None turns {noun} off and takes no keywords"; None: such a call is accepted
+    cfg: type                     # the Cfg struct; zeroed, it is "off"
+    on: str                       # the struct's field that says "on": 'enabled' or 'mode'
+    build: typing.Callable        # keywords -> an enabled struct
+    keywords: typing.Callable     # an enabled struct -> the keywords it is reported in
+    setter: str                   # (h, slots, n, cfg [, seed rows, stride] [, stream])
+    getter: str = None            # (h, slot, cfg)
+    state: str = None             # (h, slots, n, rows, stream)
+    rows: object = None           # what `state` fills: a State struct (rows read as dicts) or (dtype, columns) of a numeric tensor
+    seed_state: str = None        # (h, slots, n, rows, bytes, stream): opaque rows, which the setter takes back as seed rows with a stride
+    seed_bytes: str = None        # the bytes of such a row
+    last: str = None              # the rows of the last wav-in call
+    meta: str = None              # (slot meta, cfg): the setting in a slot snapshot's host record
+    stream: bool = True           # the setter takes a stream (and joins pipelined work: the buffers in flight are released)
+    release: bool = True          # ... unless the setter leaves them alone
+    mirror: str = None            # the Streams dict slot -> keywords, for the features that keep one
+
+    @property
+    def method(self):
+        """The name of Streams' setter."""
+        return self.setter[len("conan_streams_"):]
+
+
+# in the order open_slots applies them
+SLOT_FEATURES = {f.keyword: f for f in (
+    SlotFeature("level", "the leveller", LevelCfg, "enabled", level_cfg, level_keywords, "conan_streams_set_input_level",
+                state="conan_streams_input_level", rows=("float64", 4), meta="conan_slot_meta_level", stream=False, release=False,
+                mirror="input_levels"),
+    SlotFeature("pitch", "the pitch control", PitchCfg, "enabled", pitch_cfg, pitch_keywords, "conan_streams_set_pitch", "conan_streams_pitch",
+                meta="conan_slot_meta_pitch", mirror="pitch_cfgs"),
+    SlotFeature("follow", "following", F0Cfg, "enabled", f0_cfg, f0_keywords, "conan_streams_set_pitch_follow", "conan_streams_pitch_follow",
+                last="conan_step_wav_contour"),
+    SlotFeature("register", None, RegisterCfg, "enabled", register_cfg, register_keywords, "conan_streams_set_pitch_register",
+                "conan_streams_pitch_register", "conan_streams_pitch_register_state", ("int64", 2)),
+    SlotFeature("activity", "the detector", ActivityCfg, "mode", activity_cfg, activity_keywords, "conan_streams_set_activity",
+                "conan_streams_activity", "conan_streams_activity_state", ActivityState, last="conan_step_wav_activity"),
+    SlotFeature("bypass", None, BypassCfg, "enabled", bypass_cfg, bypass_keywords, "conan_streams_set_bypass", "conan_streams_bypass",
+                "conan_streams_bypass_state", BypassState, last="conan_step_wav_bypass"),
+    SlotFeature("conceal", "the concealment", ConcealCfg, "enabled", conceal_cfg, conceal_keywords, "conan_streams_set_conceal",
+                "conan_streams_conceal_cfg", seed_state="conan_streams_conceal_state", seed_bytes="conan_conceal_state_bytes"),
+    SlotFeature("comfort", "the comfort noise", ComfortCfg, "mode", comfort_cfg, comfort_keywords, "conan_streams_set_comfort",
+                "conan_streams_comfort", "conan_streams_comfort_state", ComfortState, last="conan_step_wav_comfort"),
+    SlotFeature("out_level", "the leveller", LevelCfg, "enabled", level_cfg, level_keywords, "conan_streams_set_output_level",
+                "conan_streams_output_level_cfg", "conan_streams_output_level", ("float64", 4), "conan_streams_output_level_state",
+                "conan_streams_output_level_state_bytes", release=False, mirror="output_levels"),
+)}
+
+for _f in SLOT_FEATURES.values():      # the three regular families of _PROTOS: a symbol's shape is stated once, in SlotFeature
+    _PROTOS[_f.setter] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_void_p, C.c_int64] * bool(_f.seed_state) + [C.c_void_p] * _f.stream)
+    if _f.getter:
+        _PROTOS[_f.getter] = (C.c_int, [C.c_void_p, C.c_int, C.c_void_p])
+    if _f.state:
+        _PROTOS[_f.state] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])
+    if _f.seed_state:
+        _PROTOS[_f.seed_state] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p])
 
 
 class DecoderTaps(C.Structure):

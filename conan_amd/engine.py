@@ -211,6 +211,44 @@ def _by_value(slots, values):
     return [(v, [s for s, x in zip(slots, values) if x == v]) for v in dict.fromkeys(values)]
 
 
+# what True means to a feature's Streams setter, by engine keyword (register= has no True: a scalar is its target)
+_TRUE = dict(level=True, pitch=True, follow=True, out_level=True, activity=dict(gate=True), bypass={}, conceal={}, comfort={})
+
+
+def _accept(keyword, v, k, n, voice):
+    """What value v (not None / False) of keyword= means for the k-th of n slots: the cfg of the feature's Streams setter.  A dict is
+    the setter's keywords; True, a string and a scalar are the feature's own.  Host only: register="voice" is looked up in
+    bank.registers of voice = (bank, ids) and is a ValueError where that has nothing to give."""
+    forms = f"True, a dict of {_lib.SLOT_FEATURES[keyword].method}'s keywords"
+    if isinstance(v, dict):
+        return dict(v)
+    if keyword == "register":
+        if not isinstance(v, str):
+            return dict(target=float(v))
+        if v != "voice":
+            raise ValueError(f"register: {v!r} (a target in log2 Hz, 'voice', a dict of set_pitch_register's keywords or None)")
+        if voice is None:
+            raise ValueError("register='voice' needs voice=(bank, ids)")
+        bank, ids = voice
+        if len(ids) != n:
+            raise ValueError(f"register='voice': {len(ids)} voice ids for {n} slots")
+        target = bank.registers.get(int(ids[k]))
+        if target is None:
+            raise ValueError(f"register='voice': voice {int(ids[k])} has no register (VoiceBank.enroll_wav(register=True))")
+        return dict(target=target)
+    if v is True:
+        return dict(_TRUE[keyword]) if isinstance(_TRUE[keyword], dict) else True
+    if keyword == "activity":
+        if isinstance(v, str) and v == "detect":
+            return dict(gate=False)
+        forms = "True, 'detect', a dict of set_activity's keywords"
+    if keyword == "conceal":
+        if isinstance(v, _lib.ConcealCfg):
+            return v
+        forms = "True, a dict of conan_conceal_cfg's fields, an _lib.ConcealCfg"
+    raise ValueError(f"{keyword}: {v!r} ({forms} or None)")
+
+
 class StreamingVoiceConversionEngine:
     """The chunk loop of StreamingVoiceConversion.infer_once (inference/Conan.py:72-166) for many
     streams at once: mel in -> (wav, mel, codes) out, state carried in a conan_streams handle."""
@@ -224,12 +262,7 @@ class StreamingVoiceConversionEngine:
                               flags=flags, dev_plan=dev_plan)
         self.slots = list(range(n_streams))
         self.seg, self.rc = ctx.cfg.emf_segment, ctx.cfg.emf_right_context
-        self._followed = False      # set_pitch_follow has been called on the stream-set
-        self._registered = False    # set_pitch_register has been called on the stream-set
-        self._activity = False      # set_activity has been called on the stream-set
-        self._bypass = False        # set_bypass has been called on the stream-set
-        self._conceal = False       # set_conceal has been called on the stream-set
-        self._comfort = False       # set_comfort has been called on the stream-set
+        self._used = set()          # the keywords of _lib.SLOT_FEATURES whose setter has been called on the stream-set (_apply)
 
     @staticmethod
     def _check_voice(ref_mel, voice):
@@ -274,12 +307,13 @@ class StreamingVoiceConversionEngine:
             raise ValueError("out_rate / out_format: one value for all slots here (feed / infer return one [B, count] block); open_slots and "
                              "infer_wav_staggered take one per slot / utterance")
         self._check_voice(ref_mel, voice)
+        values = self._host_checks(len(self.slots), pitch=pitch, out_level=out_level)
         self.st.reset(self.slots, which=which)
         self._reference(self.slots, ref_mel, ref_len, voice)
         self._set_out_rate(self.slots, out_rate, out_filter)
         self._set_format(self.slots, out_format, self.st.output_formats, self.st.set_output_format)
-        self._set_pitch(self.slots, pitch)
-        self._set_out_level(self.slots, out_level)
+        for keyword in values:      # (pitch, out_level)
+            self._apply(keyword, self.slots, values[keyword])
 
     def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, **filter):
@@ -308,123 +342,71 @@ class StreamingVoiceConversionEngine:
         There is no trim= here: silence trimming (infer_wav(trim=True)) moves audio forward over pauses it has seen whole, and a
         stream cannot drop time it has not heard yet; activity= is what a live call has in its place."""
         self._check_voice(ref_mel, voice)
-        registers = self._registers(self.slots, register, voice)
-        activities = self._activities(self.slots, activity)
-        bypasses = self._bypasses(self.slots, bypass)
-        conceals = self._conceals(self.slots, conceal)
-        comforts = self._comforts(self.slots, comfort)
         if isinstance(in_format, (list, tuple)) or isinstance(level, (list, tuple)):
             raise ValueError("in_format / level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
+        values = self._host_checks(len(self.slots), voice, level=level, follow=follow, register=register, activity=activity, bypass=bypass,
+                                   conceal=conceal, comfort=comfort)
         self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice,
                    out_level=out_level)
         self._set_rate(self.slots, in_rate, filter)
         self._set_format(self.slots, in_format, self.st.input_formats, self.st.set_input_format)
-        self._set_level(self.slots, level)
-        self._set_follow(self.slots, follow)
-        self._set_register(self.slots, registers)
-        self._set_activity(self.slots, activities)
-        self._set_bypass(self.slots, bypasses)
-        self._set_conceal(self.slots, conceals, [in_rate] * len(self.slots))
-        self._set_comfort(self.slots, comforts)
+        for keyword in values:      # (pitch and out_level went in with start(), in front of the input rate)
+            self._apply(keyword, self.slots, values[keyword], [in_rate] * len(self.slots))
 
     @staticmethod
-    def _activities(slots, activity):
-        """activity= (one value or one per slot) -> per slot None or a dict of Streams.set_activity's keywords.  Host only."""
-        values = list(activity) if isinstance(activity, (list, tuple)) else [activity] * len(slots)
-        if len(values) != len(slots):
-            raise ValueError(f"activity: {len(values)} values for {len(slots)} slots")
-        out = []
-        for a in values:
-            if a is None or a is False:
-                out.append(None)
-            elif a is True:
-                out.append(dict(gate=True))
-            elif isinstance(a, str):
-                if a != "detect":
-                    raise ValueError(f"activity: {a!r} (True, 'detect', a dict of set_activity's keywords or None)")
-                out.append(dict(gate=False))
-            elif isinstance(a, dict):
-                out.append(dict(a))
-            else:
-                raise ValueError(f"activity: {a!r} (True, 'detect', a dict of set_activity's keywords or None)")
-        return out
+    def _values(keyword, value, n, what="slots", voice=None):
+        """keyword= (one value or one per slot) -> per slot None (None / False: none) or the cfg of the feature's Streams setter
+        (_accept).  Host only."""
+        values = list(value) if isinstance(value, (list, tuple)) else [value] * n
+        if len(values) != n:
+            raise ValueError(f"{keyword}: {len(values)} values for {n} {what}")
+        return [None if v is None or v is False else _accept(keyword, v, k, n, voice) for k, v in enumerate(values)]
 
-    def _set_activity(self, slots, activities):
-        """The slots' detector from _activities' list, behind the slots' reset: the states restart from their seeds at the first
-        emitted chunk.  A stream-set that never used it is left alone."""
-        if all(a is None for a in activities) and not self._activity:
-            return
-        self._activity = True
-        for slot, a in zip(slots, activities):
-            self.st.set_activity([slot], cfg=a)
+    @classmethod
+    def _host_checks(cls, n, voice=None, utterances=(), **given):
+        """The host checks of the given per-slot keywords, before anything runs: keyword -> _values' list, in the order of
+        _lib.SLOT_FEATURES.  utterances: the keywords whose n counts utterances in the error's text."""
+        return {k: cls._values(k, given[k], n, "utterances" if k in utterances else "slots", voice) for k in _lib.SLOT_FEATURES if k in given}
 
-    @staticmethod
-    def _bypasses(slots, bypass):
-        """bypass= (one value or one per slot) -> per slot None or a dict of Streams.set_bypass's keywords.  Host only."""
-        values = list(bypass) if isinstance(bypass, (list, tuple)) else [bypass] * len(slots)
-        if len(values) != len(slots):
-            raise ValueError(f"bypass: {len(values)} values for {len(slots)} slots")
-        out = []
-        for b in values:
-            if b is None or b is False:
-                out.append(None)
-            elif b is True:
-                out.append({})
-            elif isinstance(b, dict):
-                out.append(dict(b))
-            else:
-                raise ValueError(f"bypass: {b!r} (True, a dict of set_bypass's keywords or None)")
-        return out
+    def _apply(self, keyword, slots, values, rates=None):
+        """The slots' feature from _values' list, one setter call per slot, behind the slots' reset (states restart from their seeds at
+        the first emitted chunk).  A feature with a Streams dict (level, pitch, out_level): a slot that never had one is left alone.
+        The others: a stream-set that never used the feature gets no setter call at all; once used, None turns a slot off.  rates:
+        the slots' input rates (None: the model rate), for the concealment's defaults.  A comfort seed defaults to
+        _lib.comfort_seed(slot)."""
+        f = _lib.SLOT_FEATURES[keyword]
+        if not f.mirror:
+            if all(v is None for v in values) and keyword not in self._used:
+                return
+            self._used.add(keyword)
+        for k, (slot, v) in enumerate(zip(slots, values)):
+            if v is None and f.mirror and int(slot) not in getattr(self.st, f.mirror):
+                continue
+            kw = {}
+            if keyword == "conceal":
+                v, kw = None if v is None else (v or True), dict(rate=rates[k])      # ({}: True, the defaults of the slot's rate)
+            elif keyword == "comfort" and v is not None:
+                v = dict(dict(seed=_lib.comfort_seed(slot)), **v)
+            getattr(self.st, f.method)([slot], cfg=v, **kw)
 
-    def _set_bypass(self, slots, bypasses):
-        """The slots' bypass from _bypasses' list, behind the slots' reset: the levels restart from their seeds at the first emitted
-        chunk.  A stream-set that never used it is left alone."""
-        if all(b is None for b in bypasses) and not self._bypass:
-            return
-        self._bypass = True
-        for slot, b in zip(slots, bypasses):
-            self.st.set_bypass([slot], cfg=b)
+    def _live(self, keyword, slots, *args, **kw):
+        """A live setter: the feature's Streams setter on `slots` (all slots by default), which counts as use of the feature."""
+        f = _lib.SLOT_FEATURES[keyword]
+        if not f.mirror:
+            self._used.add(keyword)
+        getattr(self.st, f.method)(self.slots if slots is None else slots, *args, **kw)
 
     def set_bypass(self, slots=None, cfg=True, **kw):
         """A live change of the slots' bypass (all slots by default) between feed / feed_ragged calls, also mid-utterance and with
         pipelined steps in flight: Streams.set_bypass's arguments (cfg=None turns it off; without reseed=True an enabled slot keeps
         its levels and slews to the new targets - the toggle).  In force from the next emitted chunk."""
-        self._bypass = True
-        self.st.set_bypass(self.slots if slots is None else slots, cfg, **kw)
-
-    @staticmethod
-    def _comforts(slots, comfort):
-        """comfort= (one value or one per slot) -> per slot None or a dict of Streams.set_comfort's keywords.  Host only."""
-        values = list(comfort) if isinstance(comfort, (list, tuple)) else [comfort] * len(slots)
-        if len(values) != len(slots):
-            raise ValueError(f"comfort: {len(values)} values for {len(slots)} slots")
-        out = []
-        for b in values:
-            if b is None or b is False:
-                out.append(None)
-            elif b is True:
-                out.append({})
-            elif isinstance(b, dict):
-                out.append(dict(b))
-            else:
-                raise ValueError(f"comfort: {b!r} (True, a dict of set_comfort's keywords or None)")
-        return out
-
-    def _set_comfort(self, slots, comforts):
-        """The slots' comfort noise from _comforts' list, behind the slots' reset: the levels restart from their start level at the
-        first emitted chunk.  A slot's seed defaults to _lib.comfort_seed(slot).  A stream-set that never used it is left alone."""
-        if all(b is None for b in comforts) and not self._comfort:
-            return
-        self._comfort = True
-        for slot, b in zip(slots, comforts):
-            self.st.set_comfort([slot], cfg=None if b is None else dict(dict(seed=_lib.comfort_seed(slot)), **b))
+        self._live("bypass", slots, cfg, **kw)
 
     def set_comfort(self, slots=None, cfg=True, **kw):
         """A live change of the slots' comfort noise (all slots by default) between feed / feed_ragged calls, also mid-utterance and
         with pipelined steps in flight: Streams.set_comfort's arguments (cfg=None turns it off; without reseed=True an enabled slot
         keeps its level).  In force from the next emitted chunk."""
-        self._comfort = True
-        self.st.set_comfort(self.slots if slots is None else slots, cfg, **kw)
+        self._live("comfort", slots, cfg, **kw)
 
     def chunk_comfort(self):
         """The frame-end comfort levels of the last feed / feed_ragged call (Streams.step_wav_comfort; joins pipelined work): [n, seg]
@@ -432,39 +414,10 @@ class StreamingVoiceConversionEngine:
         RFC 3389 noise level byte of a frame."""
         return self.st.step_wav_comfort()
 
-    @staticmethod
-    def _conceals(slots, conceal):
-        """conceal= (one value or one per slot) -> per slot None, a dict of conan_conceal_cfg's fields (over the defaults of the slot's
-        input rate) or an _lib.ConcealCfg.  Host only."""
-        values = list(conceal) if isinstance(conceal, (list, tuple)) else [conceal] * len(slots)
-        if len(values) != len(slots):
-            raise ValueError(f"conceal: {len(values)} values for {len(slots)} slots")
-        out = []
-        for c in values:
-            if c is None or c is False:
-                out.append(None)
-            elif c is True:
-                out.append({})
-            elif isinstance(c, (dict, _lib.ConcealCfg)):
-                out.append(c)
-            else:
-                raise ValueError(f"conceal: {c!r} (True, a dict of conan_conceal_cfg's fields, an _lib.ConcealCfg or None)")
-        return out
-
-    def _set_conceal(self, slots, conceals, rates):
-        """The slots' loss concealment from _conceals' list, behind the slots' reset (which restarts the state); rates: the slots'
-        input rates (None: the model rate).  A stream-set that never used it is left alone."""
-        if all(c is None for c in conceals) and not self._conceal:
-            return
-        self._conceal = True
-        for slot, c, rate in zip(slots, conceals, rates):
-            self.st.set_conceal([slot], cfg=c if c is None or isinstance(c, _lib.ConcealCfg) else (c or True), rate=rate)
-
     def set_conceal(self, slots=None, cfg=True, **kw):
         """A live change of the slots' loss concealment (all slots by default) between feed / feed_ragged calls, also mid-utterance:
         Streams.set_conceal's arguments (cfg=None turns it off; an enabled slot keeps its state)."""
-        self._conceal = True
-        self.st.set_conceal(self.slots if slots is None else slots, cfg, **kw)
+        self._live("conceal", slots, cfg, **kw)
 
     def _lost_rows(self, slots, lost, pos, counts):
         """The flags of one call's rows cut from whole-utterance flags: row i takes lost[i] from sample position pos[i] on, counts[i]
@@ -496,128 +449,34 @@ class StreamingVoiceConversionEngine:
         """A live change of the slots' activity detector (all slots by default) between feed / feed_ragged calls, also mid-utterance
         and with pipelined steps in flight: Streams.set_activity's arguments (cfg=None turns it off; without reseed=True an enabled
         slot keeps its state).  In force from the next emitted chunk."""
-        self._activity = True
-        self.st.set_activity(self.slots if slots is None else slots, cfg, **kw)
+        self._live("activity", slots, cfg, **kw)
 
     def chunk_activity(self):
         """The flags and frame-end gate levels of the last feed / feed_ragged call (Streams.step_wav_activity; joins pipelined work):
         (act [n, seg], level [n, seg]) int32 in the call's row order, zeros for rows without the detector and past a row's frames."""
         return self.st.step_wav_activity()
 
-    @staticmethod
-    def _registers(slots, register, voice):
-        """register= (one value or one per slot) -> per slot None or a dict of Streams.set_pitch_register's keywords.  Host only:
-        "voice" is looked up in bank.registers of voice = (bank, ids) and is a ValueError where that has nothing to give."""
-        values = list(register) if isinstance(register, (list, tuple)) else [register] * len(slots)
-        if len(values) != len(slots):
-            raise ValueError(f"register: {len(values)} values for {len(slots)} slots")
-        out = []
-        for k, r in enumerate(values):
-            if r is None or r is False:
-                out.append(None)
-            elif isinstance(r, str):
-                if r != "voice":
-                    raise ValueError(f"register: {r!r} (a target in log2 Hz, 'voice', a dict of set_pitch_register's keywords or None)")
-                if voice is None:
-                    raise ValueError("register='voice' needs voice=(bank, ids)")
-                bank, ids = voice
-                if len(ids) != len(slots):
-                    raise ValueError(f"register='voice': {len(ids)} voice ids for {len(slots)} slots")
-                target = bank.registers.get(int(ids[k]))
-                if target is None:
-                    raise ValueError(f"register='voice': voice {int(ids[k])} has no register (VoiceBank.enroll_wav(register=True))")
-                out.append(dict(target=target))
-            elif isinstance(r, dict):
-                out.append(dict(r))
-            else:
-                out.append(dict(target=float(r)))
-        return out
-
-    def _set_register(self, slots, registers):
-        """The slots' register matching from _registers' list, behind the slots' reset: the estimates restart from their seeds at
-        the first emitted chunk.  A stream-set that never used it is left alone."""
-        if all(r is None for r in registers) and not self._registered:
-            return
-        self._registered = True
-        for slot, r in zip(slots, registers):
-            if r is None:
-                self.st.set_pitch_register([slot], cfg=None)
-            else:
-                self.st.set_pitch_register([slot], cfg=r)
-
     def set_pitch_register(self, slots=None, **kw):
         """A live change of the slots' register matching (all slots by default) between feed / feed_ragged calls, also mid-utterance
         and with pipelined steps in flight: Streams.set_pitch_register's keywords (cfg=None turns it off; without reseed=True an
         enabled slot keeps its estimate: the voice change in the middle of a call).  In force from the next emitted chunk."""
-        self._registered = True
-        self.st.set_pitch_register(self.slots if slots is None else slots, **kw)
-
-    def _set_follow(self, slots, follow):
-        """The slots' source-pitch following (None / False: none; True: the defaults; a dict of Streams.set_pitch_follow's keywords),
-        one value or one per slot.  A stream-set that never followed is left alone."""
-        follows = list(follow) if isinstance(follow, (list, tuple)) else [follow] * len(slots)
-        assert len(follows) == len(slots), (len(follows), len(slots))
-        if all(f is None or f is False for f in follows) and not self._followed:
-            return
-        self._followed = True
-        for slot, fo in zip(slots, follows):
-            self.st.set_pitch_follow([slot], None if fo is None or fo is False else (True if fo is True else dict(fo)))
+        self._live("register", slots, **kw)
 
     def set_pitch_follow(self, slots=None, cfg=True, **kw):
         """A live change of the slots' source-pitch following (all slots by default) between feed / feed_ragged calls, also
         mid-utterance and with pipelined steps in flight: Streams.set_pitch_follow's arguments (cfg=None turns it off).  In force
         from the next emitted chunk."""
-        self._followed = True
-        self.st.set_pitch_follow(self.slots if slots is None else slots, cfg, **kw)
-
-    def _set_level(self, slots, level):
-        """The slots' input leveller (None / False: none; True: the defaults; a dict of Streams.set_input_level's keywords), one value
-        or one per slot.  Slots that never had one are left alone."""
-        levels = list(level) if isinstance(level, (list, tuple)) else [level] * len(slots)
-        assert len(levels) == len(slots), (len(levels), len(slots))
-        for slot, lv in zip(slots, levels):
-            if lv is None or lv is False:
-                if int(slot) in self.st.input_levels:
-                    self.st.set_input_level([slot], None)
-            else:
-                self.st.set_input_level([slot], True if lv is True else dict(lv))
-
-    def _set_out_level(self, slots, out_level):
-        """The slots' output leveller (None / False: none; True: the defaults; a dict of Streams.set_output_level's keywords), one value
-        or one per slot, behind the slots' reset (the vocoder streams are at position 0).  Slots that never had one are left alone."""
-        levels = list(out_level) if isinstance(out_level, (list, tuple)) else [out_level] * len(slots)
-        if len(levels) != len(slots):
-            raise ValueError(f"out_level: {len(levels)} values for {len(slots)} slots")
-        for slot, lv in zip(slots, levels):
-            if lv is None or lv is False:
-                if int(slot) in self.st.output_levels:
-                    self.st.set_output_level([slot], None)
-            elif lv is True or isinstance(lv, dict):
-                self.st.set_output_level([slot], True if lv is True else dict(lv))
-            else:
-                raise ValueError(f"out_level: {lv!r} (True, a dict of set_output_level's keywords or None)")
+        self._live("follow", slots, cfg, **kw)
 
     def set_output_level(self, slots=None, cfg=True, seed=None, **kw):
         """The slots' output leveller (all slots by default) between utterances, or mid-utterance with seed= (a hand-over):
         Streams.set_output_level's arguments (cfg=None turns it off).  Joins pipelined steps in flight."""
-        self.st.set_output_level(self.slots if slots is None else slots, cfg, seed=seed, **kw)
-
-    def _set_pitch(self, slots, pitch):
-        """The slots' pitch control (None / False: none; True: the defaults; a dict of Streams.set_pitch's keywords), one value or one
-        per slot.  Slots that never had one are left alone."""
-        pitches = list(pitch) if isinstance(pitch, (list, tuple)) else [pitch] * len(slots)
-        assert len(pitches) == len(slots), (len(pitches), len(slots))
-        for slot, pt in zip(slots, pitches):
-            if pt is None or pt is False:
-                if int(slot) in self.st.pitch_cfgs:
-                    self.st.set_pitch([slot], None)
-            else:
-                self.st.set_pitch([slot], True if pt is True else dict(pt))
+        self._live("out_level", slots, cfg, seed=seed, **kw)
 
     def set_pitch(self, slots=None, **kw):
         """A live change of the slots' pitch control (all slots by default) between feed / feed_ragged calls, also mid-utterance and
         with pipelined steps in flight: Streams.set_pitch's keywords; no keyword at all turns it off.  In force from the next call."""
-        self.st.set_pitch(self.slots if slots is None else slots, dict(kw) if kw else None)
+        self._live("pitch", slots, dict(kw) if kw else None)
 
     @staticmethod
     def _set_format(slots, fmt, table, setter):
@@ -785,11 +644,8 @@ class StreamingVoiceConversionEngine:
         of infer_wav(ctx.conceal(src_wav, lost, cfg, in_format), ...) bit for bit.  Not with loud_norm or trim, which hold the
         utterance whole: repair it whole first (Context.conceal)."""
         self._check_voice(ref_mel, voice)
-        self._registers(self.slots, register, voice)      # (host checks before anything runs)
-        self._activities(self.slots, activity)
-        self._bypasses(self.slots, bypass)
-        self._conceals(self.slots, conceal)
-        self._comforts(self.slots, comfort)
+        self._host_checks(len(self.slots), voice, level=level, pitch=pitch, follow=follow, register=register, activity=activity, bypass=bypass,
+                          conceal=conceal, comfort=comfort, out_level=out_level)      # (before anything runs)
         self._check_lost(lost, conceal, loud_norm, trim)
         trim = self._trim_keywords(trim)
         if trim is not None:
@@ -845,11 +701,8 @@ class StreamingVoiceConversionEngine:
         No trim=, as in start_wav: the slots stream, and a stream cannot drop time (infer_wav_staggered(trim=True) trims utterances
         it holds whole)."""
         self._check_voice(ref_mel, voice)
-        registers = self._registers(slots, register, voice)
-        activities = self._activities(slots, activity)
-        bypasses = self._bypasses(slots, bypass)
-        conceals = self._conceals(slots, conceal)
-        comforts = self._comforts(slots, comfort)
+        values = self._host_checks(len(slots), voice, level=level, pitch=pitch, follow=follow, register=register, activity=activity, bypass=bypass,
+                                   conceal=conceal, comfort=comfort, out_level=out_level)
         self.st.reset(slots, which=7 | 8)
         self._reference(slots, ref_mel, ref_len, voice)
         self._set_out_rate(slots, out_rate, out_filter)
@@ -857,15 +710,8 @@ class StreamingVoiceConversionEngine:
         self._set_format(slots, out_format, self.st.output_formats, self.st.set_output_format)
         for r, group in _by_value(slots, _per_slot(in_rate, len(slots))):
             self._set_rate(group, r, filter)
-        self._set_level(slots, level)
-        self._set_pitch(slots, pitch)
-        self._set_follow(slots, follow)
-        self._set_register(slots, registers)
-        self._set_activity(slots, activities)
-        self._set_bypass(slots, bypasses)
-        self._set_conceal(slots, conceals, _per_slot(in_rate, len(slots)))
-        self._set_comfort(slots, comforts)
-        self._set_out_level(slots, out_level)
+        for keyword in values:      # (the order of _lib.SLOT_FEATURES: pitch behind level, out_level last)
+            self._apply(keyword, slots, values[keyword], _per_slot(in_rate, len(slots)))
 
     @torch.no_grad()
     def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None, lost=None):
@@ -914,22 +760,14 @@ class StreamingVoiceConversionEngine:
         utterance whole)."""
         voice = self._check_voice(ref_mel, voice)
         U = len(src_wavs)
-        conceals = self._conceals(range(U), conceal)
+        # (host checks before anything runs; per utterance, in the form open_slots takes back)
+        values = self._host_checks(U, voice, ("out_level",), level=level, pitch=pitch, follow=follow, register=register, activity=activity,
+                                   bypass=bypass, conceal=conceal, comfort=comfort, out_level=out_level)
         self._check_lost(lost, conceal, loud_norm, trim)
         if lost is not None and len(lost) != U:
             raise ValueError(f"lost: {len(lost)} values for {U} utterances")
-        out_levels = list(out_level) if isinstance(out_level, (list, tuple)) else [out_level] * U
-        if len(out_levels) != U:
-            raise ValueError(f"out_level: {len(out_levels)} values for {U} utterances")
-        registers = self._registers(range(U), register, voice)      # (host checks before anything runs; per utterance, as dicts)
-        activities = self._activities(range(U), activity)
-        bypasses = self._bypasses(range(U), bypass)
-        comforts = self._comforts(range(U), comfort)
         if activity_log is not None:
             activity_log[:] = [[] for _ in range(U)]
-        follows = list(follow) if isinstance(follow, (list, tuple)) else [follow] * U
-        levels = list(level) if isinstance(level, (list, tuple)) else [level] * U
-        pitches = list(pitch) if isinstance(pitch, (list, tuple)) else [pitch] * U
         ifmts, ofmts, orates, rates = (list(v) if v is not None else [None] * U for v in (in_formats, out_formats, out_rates, in_rates))
         trim = self._trim_keywords(trim)
         if trim is not None:
@@ -955,10 +793,7 @@ class StreamingVoiceConversionEngine:
                 self.open_slots([live[u][0] for u in new], torch.stack([ref_mel[u] for u in new]) if voice is None else None,
                                 voice=None if voice is None else (voice[0], [voice[1][u] for u in new]), in_rate=[rates[u] for u in new],
                                 out_rate=[orates[u] for u in new], out_filter=out_filter, in_format=[ifmts[u] for u in new],
-                                out_format=[ofmts[u] for u in new], level=[levels[u] for u in new], pitch=[pitches[u] for u in new],
-                                follow=[follows[u] for u in new], register=[registers[u] for u in new], activity=[activities[u] for u in new],
-                                bypass=[bypasses[u] for u in new], out_level=[out_levels[u] for u in new], conceal=[conceals[u] for u in new],
-                                comfort=[comforts[u] for u in new], **filter)
+                                out_format=[ofmts[u] for u in new], **{k: [v[u] for u in new] for k, v in values.items()}, **filter)
             if not live:
                 tick += 1
                 continue

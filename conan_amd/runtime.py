@@ -30,19 +30,25 @@ def _i32(a):
     return a, a.ctypes.data_as(C.c_void_p)
 
 
-def _activity_states(buf):
-    """uint8 [n, sizeof(conan_activity_state)] on the device -> a list of dicts (synchronises)."""
+def _struct_rows(buf, State):
+    """uint8 [n, sizeof(State)] on the device -> a list of dicts of the State struct's fields but `reserved` (synchronises)."""
     raw = buf.cpu().numpy().tobytes()
-    size = C.sizeof(_lib.ActivityState)
-    return [_lib.activity_state_dict(_lib.ActivityState.from_buffer_copy(raw[i * size:(i + 1) * size])) for i in range(buf.shape[0])]
+    size = C.sizeof(State)
+    states = [State.from_buffer_copy(raw[i * size:(i + 1) * size]) for i in range(buf.shape[0])]
+    return [{name: getattr(s, name) for name, _ in State._fields_ if name != "reserved"} for s in states]
 
 
-def _comfort_states(buf):
-    """uint8 [n, sizeof(conan_comfort_state)] on the device -> a list of dict(level, idle_frames) (synchronises)."""
-    raw = buf.cpu().numpy().tobytes()
-    size = C.sizeof(_lib.ComfortState)
-    states = [_lib.ComfortState.from_buffer_copy(raw[i * size:(i + 1) * size]) for i in range(buf.shape[0])]
-    return [dict(level=int(s.level), idle_frames=int(s.idle_frames)) for s in states]
+def _feature_cfg(f, cfg, kw, defaults=()):
+    """The Cfg struct of a setter of feature f (an _lib.SlotFeature) from its (cfg, **kw): None is the zeroed struct, "off", and takes
+    no keywords; a struct passes; True, a dict and the keywords go to the feature's builder over the method's own `defaults`, a dict's
+    entries over those and the keywords over the dict's."""
+    if cfg is None:
+        if kw and f.noun:
+            raise ValueError(f"{f.method}: cfg=None turns {f.noun} off and takes no keywords")
+        return f.cfg()
+    if isinstance(cfg, f.cfg):
+        return cfg
+    return f.build(**dict(defaults, **dict({} if cfg is True else cfg, **kw)))
 
 
 # torch dtype of a row in each sample format (conan_streams_set_input_format / _output_format, conan_convert_samples)
@@ -314,7 +320,7 @@ class Context:
         _lib.check(self.lib.conan_activity(self.h, C.byref(mc), C.byref(c), _ptr(x), n, N, _ptr(act), _ptr(lvl), _ptr(pw), _ptr(sbuf), C.byref(got),
                                            _stream()))
         assert got.value == frames
-        out = (act.reshape(*lead, frames), lvl.reshape(*lead, frames), _activity_states(sbuf) if state else None)
+        out = (act.reshape(*lead, frames), lvl.reshape(*lead, frames), _struct_rows(sbuf, _lib.ActivityState) if state else None)
         return out + (pw.reshape(*lead, frames),) if power else out
 
     def activity_gate(self, wav, level, start_level=0, hop_size=None, out=None):
@@ -447,7 +453,7 @@ class Context:
         _lib.check(self.lib.conan_comfort_track(self.h, C.byref(c), _ptr(a), _ptr(p), n, F, F, _ptr(out), _ptr(st), _stream()))
         if not return_state:
             return out
-        return out, _comfort_states(st)
+        return out, _struct_rows(st, _lib.ComfortState)
 
     def comfort_fill(self, wav, gate_levels, comfort_levels, cfg=None, seeds=None, start=(_lib.ACTIVITY_FULL, 0), pos0=0, hop_size=None, out=None, **kw):
         """The comfort noise's fill on whole signals (conan_comfort_fill): wav [..., N] float32 (the audio behind the gate and the
@@ -592,13 +598,12 @@ class SlotSnapshot:
         out = _lib.SlotInfo()
         _lib.check(_lib.lib().conan_slot_meta_info(C.byref(rec), C.byref(out)))
         names = {v: k for k, v in _lib.SAMPLE_FORMATS.items()}
-        lv = _lib.LevelCfg()
-        level = None
-        if _lib.check(_lib.lib().conan_slot_meta_level(C.byref(rec), C.byref(lv))):
-            level = _lib.level_keywords(lv)
-        pt = _lib.PitchCfg()
-        pitch = _lib.pitch_keywords(pt) if _lib.check(_lib.lib().conan_slot_meta_pitch(C.byref(rec), C.byref(pt))) else None
-        return dict(level=level, pitch=pitch, layout_id=int(out.layout_id), bytes=int(out.bytes), has_ref=bool(out.has_ref), in_format=names[out.in_format],
+
+        def setting(f):
+            c = f.cfg()
+            return f.keywords(c) if _lib.check(getattr(_lib.lib(), f.meta)(C.byref(rec), C.byref(c))) else None
+
+        return dict(level=setting(_lib.SLOT_FEATURES["level"]), pitch=setting(_lib.SLOT_FEATURES["pitch"]), layout_id=int(out.layout_id), bytes=int(out.bytes), has_ref=bool(out.has_ref), in_format=names[out.in_format],
                     out_format=names[out.out_format],
                     in_rate=out.in_rate.in_rate if out.in_rate.in_rate != out.in_rate.out_rate else None,
                     out_rate=out.out_rate.out_rate if out.out_rate.in_rate != out.out_rate.out_rate else None,
@@ -864,14 +869,74 @@ class Streams:
                 self.output_rates[int(slot)] = int(info["out_rate"])
             else:
                 self.output_rates.pop(int(slot), None)
-            if info["level"] is not None:
-                self.input_levels[int(slot)] = info["level"]
-            else:
-                self.input_levels.pop(int(slot), None)
-            if info["pitch"] is not None:
-                self.pitch_cfgs[int(slot)] = info["pitch"]
-            else:
-                self.pitch_cfgs.pop(int(slot), None)
+            for key in ("level", "pitch"):
+                self._note_cfg(_lib.SLOT_FEATURES[key], slot, info[key])
+
+    def _note_cfg(self, f, slot, keywords):
+        """The slot's entry in the dict slot -> keywords of a feature that keeps one: the keywords, or none for a slot without it."""
+        if keywords is not None:
+            getattr(self, f.mirror)[int(slot)] = keywords
+        else:
+            getattr(self, f.mirror).pop(int(slot), None)
+
+    def _set_feature(self, key, slots, cfg, kw, defaults=(), seed=None):
+        """A feature's setter: the struct of (cfg, **kw) over `defaults` (_feature_cfg) goes to the slots, with the seed rows where
+        the feature takes them; pipelined buffers are released where the call joined them; the slots' keywords are noted."""
+        f = _lib.SLOT_FEATURES[key]
+        a, p = _i32(slots)
+        c = _feature_cfg(f, cfg, kw, defaults)
+        args = [self.h, p, len(a), C.byref(c)]
+        if f.seed_state:
+            reader = f.seed_state[len("conan_streams_"):]
+            if seed is not None and (seed.dtype != torch.uint8 or seed.dim() != 2 or seed.shape[0] != len(a) or not seed.is_cuda or seed.stride(1) != 1):
+                raise ValueError(f"{f.method}: seed must be a cuda uint8 [n, bytes] tensor, as {reader} returns it")
+            args += [_ptr(seed), int(seed.stride(0))] if seed is not None else [None, 0]
+        _lib.check(getattr(self.lib, f.setter)(*args, *([_stream()] if f.stream else [])))
+        if f.release:
+            self._release()
+        if f.mirror:
+            for slot in a:
+                self._note_cfg(f, slot, f.keywords(c) if getattr(c, f.on) else None)
+
+    def _get_feature(self, key, slots, report=None):
+        """A feature's cfg getter: per slot what `report` (default: the feature's keywords) makes of the struct, None for a slot
+        without the feature."""
+        f = _lib.SLOT_FEATURES[key]
+        out = []
+        for slot in slots:
+            c = f.cfg()
+            _lib.check(getattr(self.lib, f.getter)(self.h, int(slot), C.byref(c)))
+            out.append((report or f.keywords)(c) if getattr(c, f.on) else None)
+        return out
+
+    def _feature_state(self, key, slots):
+        """A feature's state rows (joins pipelined work): a numeric tensor [n, columns] (cuda), or for struct rows a list of dicts
+        (synchronises)."""
+        f = _lib.SLOT_FEATURES[key]
+        a, p = _i32(slots)
+        struct = isinstance(f.rows, type)
+        buf = torch.empty(len(a), C.sizeof(f.rows) if struct else f.rows[1], dtype=torch.uint8 if struct else getattr(torch, f.rows[0]), device=self.dev)
+        _lib.check(getattr(self.lib, f.state)(self.h, p, len(a), _ptr(buf), _stream()))
+        self._release()
+        return _struct_rows(buf, f.rows) if struct else buf
+
+    def _feature_seed_rows(self, key, slots):
+        """A feature's opaque state rows uint8 [n, bytes] (cuda), which its setter takes back as seed=.  Joins pipelined work."""
+        f = _lib.SLOT_FEATURES[key]
+        a, p = _i32(slots)
+        nbytes = int(_lib.check(getattr(self.lib, f.seed_bytes)(*([self.h] if _lib._PROTOS[f.seed_bytes][1] else []))))
+        out = torch.empty(len(a), nbytes, dtype=torch.uint8, device=self.dev)
+        _lib.check(getattr(self.lib, f.seed_state)(self.h, p, len(a), _ptr(out), nbytes, _stream()))
+        self._release()
+        return out
+
+    def _last_rows(self, key, k, dtype=torch.int32):
+        """What the last wav-in call left for a feature (joins pipelined work): k tensors [n, seg] in call order."""
+        n = self._last_wav_n
+        bufs = [torch.empty(max(n, 1), self.seg, dtype=dtype, device=self.dev) for _ in range(k)]      # (before any wav-in call the library answers CONAN_ERR_STATE)
+        _lib.check(getattr(self.lib, _lib.SLOT_FEATURES[key].last)(self.h, *[_ptr(b) for b in bufs], _stream()))
+        self._release()
+        return tuple(b[:n] for b in bufs)
 
     def _release(self):
         """Buffers of pipelined steps may be dropped once the current torch stream waits for the library's internal
@@ -929,19 +994,7 @@ class Streams:
         Context.level's defaults, so set_input_level(slots) is the default leveller.  Only cfg=None turns it off.
         The slots must be at the start of an utterance; the setting survives resets, which clear the meter.
         input_levels[slot] holds every keyword of a levelled slot, as SlotSnapshot.info reports them."""
-        a, p = _i32(slots)
-        if cfg is None:
-            if kw:
-                raise ValueError("set_input_level: cfg=None turns the leveller off and takes no keywords")
-            c = _lib.LevelCfg()      # (enabled = 0)
-        else:
-            c = _lib.level_cfg(**dict({} if cfg is True else cfg, **kw))
-        _lib.check(self.lib.conan_streams_set_input_level(self.h, p, len(a), C.byref(c)))
-        for slot in a:
-            if c.enabled:
-                self.input_levels[int(slot)] = _lib.level_keywords(c)
-            else:
-                self.input_levels.pop(int(slot), None)
+        self._set_feature("level", slots, cfg, kw)
 
     def set_pitch(self, slots, cfg=True, **kw):
         """conan_streams_set_pitch: the slots' pitch control in the decoder step - shift_semitones (a key change), range (the
@@ -949,20 +1002,7 @@ class Streams:
         exceeds it: +inf voices every frame whose code is not the silent token, -inf whispers) - as keywords or as a dict in cfg;
         those not given keep _lib.pitch_cfg's defaults.  Only cfg=None turns it off.  It may be called at any time, also
         mid-utterance (it joins pipelined work); the change takes effect from the next step and survives resets."""
-        a, p = _i32(slots)
-        if cfg is None:
-            if kw:
-                raise ValueError("set_pitch: cfg=None turns the pitch control off and takes no keywords")
-            c = _lib.PitchCfg()      # (enabled = 0)
-        else:
-            c = _lib.pitch_cfg(**dict({} if cfg is True else cfg, **kw))
-        _lib.check(self.lib.conan_streams_set_pitch(self.h, p, len(a), C.byref(c), _stream()))
-        self._release()
-        for slot in a:
-            if c.enabled:
-                self.pitch_cfgs[int(slot)] = _lib.pitch_keywords(c)
-            else:
-                self.pitch_cfgs.pop(int(slot), None)
+        self._set_feature("pitch", slots, cfg, kw)
 
     def set_pitch_follow(self, slots, cfg=True, **kw):
         """conan_streams_set_pitch_follow: the slots' decoder steps take f0 / uv from the YIN contour of their own input (wav-in steps
@@ -970,25 +1010,12 @@ class Streams:
         tracker keywords (fmin, fmax, threshold, floor_db) as keywords or as a dict in cfg; those not given keep the defaults.  Only
         cfg=None turns it off.  It may be called at any time, also mid-utterance (it joins pipelined work); the change takes effect
         from the next emitted chunk and survives resets.  Slot snapshots do not carry it."""
-        a, p = _i32(slots)
-        if cfg is None:
-            if kw:
-                raise ValueError("set_pitch_follow: cfg=None turns following off and takes no keywords")
-            c = _lib.F0Cfg()      # (enabled = 0)
-        else:
-            c = _lib.f0_cfg(**dict({} if cfg is True else cfg, **kw))
-        _lib.check(self.lib.conan_streams_set_pitch_follow(self.h, p, len(a), C.byref(c), _stream()))
-        self._release()
+        self._set_feature("follow", slots, cfg, kw)
 
     def pitch_follow(self, slots):
         """conan_streams_pitch_follow: per slot the tracker's keywords as set_pitch_follow takes them, None for a slot that does not
         follow."""
-        out = []
-        for slot in slots:
-            c = _lib.F0Cfg()
-            _lib.check(self.lib.conan_streams_pitch_follow(self.h, int(slot), C.byref(c)))
-            out.append(_lib.f0_keywords(c) if c.enabled else None)
-        return out
+        return self._get_feature("follow", slots)
 
     def set_pitch_register(self, slots, target=None, cfg=True, max_shift=2.0, prior=None, prior_frames=50, seed=None, reseed=False):
         """conan_streams_set_pitch_register: register matching for slots that follow (set_pitch_follow) - the causal log-f0 mean
@@ -998,35 +1025,16 @@ class Streams:
         (default: the target).  cfg: a dict of these keywords instead; cfg=None turns it off.  It restarts from the seed when a slot
         is enabled, after reseed=True and at the first chunk after a reset of the front-end; a call with reseed=False on an enabled
         slot changes target / max_shift from the next emitted chunk and keeps the estimate.  Slot snapshots do not carry it."""
-        a, p = _i32(slots)
-        if cfg is None:
-            c = _lib.RegisterCfg()      # (enabled = 0)
-        else:
-            kw = dict(target=target, max_shift=max_shift, prior=prior, prior_frames=prior_frames, seed=seed, reseed=reseed)
-            if cfg is not True:
-                kw.update(cfg)
-            c = _lib.register_cfg(**kw)
-        _lib.check(self.lib.conan_streams_set_pitch_register(self.h, p, len(a), C.byref(c), _stream()))
-        self._release()
+        self._set_feature("register", slots, cfg, {}, dict(target=target, max_shift=max_shift, prior=prior, prior_frames=prior_frames, seed=seed, reseed=reseed))
 
     def pitch_register(self, slots):
         """Per slot dict(target, max_shift, count, sum, mean, shift) - the setting (conan_streams_pitch_register) and the estimate
         (conan_streams_pitch_register_state; joins pipelined work, synchronises): (count, sum) = the state, mean = sum / (count * 2^22)
         in log2 Hz and shift = the clamped target - mean in octaves (None while count is 0) - or None for a slot without the register."""
         slots = [int(x) for x in slots]
-        cfgs = []
-        for slot in slots:
-            c = _lib.RegisterCfg()
-            _lib.check(self.lib.conan_streams_pitch_register(self.h, slot, C.byref(c)))
-            cfgs.append(c if c.enabled else None)
+        cfgs = self._get_feature("register", slots, report=lambda c: c)
         on = [slot for slot, c in zip(slots, cfgs) if c is not None]
-        states = {}
-        if on:
-            a, p = _i32(on)
-            buf = torch.empty(len(on), 2, dtype=torch.int64, device=self.dev)
-            _lib.check(self.lib.conan_streams_pitch_register_state(self.h, p, len(on), _ptr(buf), _stream()))
-            self._release()
-            states = dict(zip(on, buf.cpu().tolist()))
+        states = dict(zip(on, self._feature_state("register", on).cpu().tolist())) if on else {}
         out = []
         for slot, c in zip(slots, cfgs):
             if c is None:
@@ -1047,47 +1055,23 @@ class Streams:
         survives resets.  The state restarts from the seed when a slot is enabled, after reseed=True and at the first chunk after a
         reset of the front-end; reseed=False on an enabled slot replaces the parameters and keeps the state.  Slot snapshots do not
         carry it: query activity_state, export, import, then set_activity(seed=state, reseed=True)."""
-        a, p = _i32(slots)
-        if cfg is None:
-            if kw:
-                raise ValueError("set_activity: cfg=None turns the detector off and takes no keywords")
-            c = _lib.ActivityCfg()      # (mode = 0)
-        elif isinstance(cfg, _lib.ActivityCfg):
-            c = cfg
-        else:
-            c = _lib.activity_cfg(**dict(dict(gate=gate), **dict({} if cfg is True else cfg, **kw)))
-        _lib.check(self.lib.conan_streams_set_activity(self.h, p, len(a), C.byref(c), _stream()))
-        self._release()
+        self._set_feature("activity", slots, cfg, kw, dict(gate=gate))
 
     def activity(self, slots):
         """conan_streams_activity: per slot the setting as _lib.activity_keywords reports it (set_activity takes it back), None for a
         slot without the detector."""
-        out = []
-        for slot in slots:
-            c = _lib.ActivityCfg()
-            _lib.check(self.lib.conan_streams_activity(self.h, int(slot), C.byref(c)))
-            out.append(_lib.activity_keywords(c) if c.mode else None)
-        return out
+        return self._get_feature("activity", slots)
 
     def activity_state(self, slots):
         """conan_streams_activity_state (joins pipelined work, synchronises): per slot dict(active, hang, level, floor, frames,
         active_frames); a slot whose state is about to restart reports its seed.  A slot without the detector is an error."""
-        a, p = _i32(slots)
-        buf = torch.empty(len(a), C.sizeof(_lib.ActivityState), dtype=torch.uint8, device=self.dev)
-        _lib.check(self.lib.conan_streams_activity_state(self.h, p, len(a), _ptr(buf), _stream()))
-        self._release()
-        return _activity_states(buf)
+        return self._feature_state("activity", slots)
 
     def step_wav_activity(self):
         """The flags and frame-end gate levels the last wav-in call produced (conan_step_wav_activity; joins pipelined work) ->
         (act [n, seg] int32, level [n, seg] int32) in call order; rows without the detector, rows that emitted nothing and entries
         past a row's emitted frames are 0."""
-        n = self._last_wav_n
-        act = torch.empty(max(n, 1), self.seg, dtype=torch.int32, device=self.dev)      # (before any wav-in call the library answers CONAN_ERR_STATE)
-        lvl = torch.empty(max(n, 1), self.seg, dtype=torch.int32, device=self.dev)
-        _lib.check(self.lib.conan_step_wav_activity(self.h, _ptr(act), _ptr(lvl), _stream()))
-        self._release()
-        return act[:n], lvl[:n]
+        return self._last_rows("activity", 2)
 
     def set_bypass(self, slots, cfg=True, wet=1.0, dry=0.0, ramp_ms=40.0, fill_gate=False, start=None, reseed=False, **kw):
         """conan_streams_set_bypass: a latency-matched dry path and a wet/dry mix on the slots' output (wav-in steps only).  The chunk's
@@ -1102,46 +1086,23 @@ class Streams:
         resets.  The levels restart from `start` when a slot is enabled, after reseed=True and at the first chunk after a reset of the
         front-end; reseed=False on an enabled slot replaces targets, ramp and fill_gate and keeps the levels - the toggle.  Slot
         snapshots do not carry it: query bypass_state, export, import, then set_bypass(start=(wet, dry), reseed=True)."""
-        a, p = _i32(slots)
-        if cfg is None:
-            c = _lib.BypassCfg()      # (enabled = 0)
-        elif isinstance(cfg, _lib.BypassCfg):
-            c = cfg
-        else:
-            base = dict(wet=wet, dry=dry, ramp_ms=ramp_ms, fill_gate=fill_gate, start=start, reseed=reseed)
-            c = _lib.bypass_cfg(**dict(base, **dict({} if cfg is True else cfg, **kw)))
-        _lib.check(self.lib.conan_streams_set_bypass(self.h, p, len(a), C.byref(c), _stream()))
-        self._release()
+        self._set_feature("bypass", slots, cfg, kw, dict(wet=wet, dry=dry, ramp_ms=ramp_ms, fill_gate=fill_gate, start=start, reseed=reseed))
 
     def bypass(self, slots):
         """conan_streams_bypass: per slot the setting as _lib.bypass_keywords reports it (set_bypass takes it back), None for a slot
         without the feature."""
-        out = []
-        for slot in slots:
-            c = _lib.BypassCfg()
-            _lib.check(self.lib.conan_streams_bypass(self.h, int(slot), C.byref(c)))
-            out.append(_lib.bypass_keywords(c) if c.enabled else None)
-        return out
+        return self._get_feature("bypass", slots)
 
     def bypass_state(self, slots):
         """conan_streams_bypass_state (joins pipelined work, synchronises): per slot dict(wet, dry, dry_eff), the levels after the
         slot's last emitted frame; a slot whose levels are about to restart reports its seed.  A slot without the feature is an error."""
-        a, p = _i32(slots)
-        buf = torch.empty(len(a), 4, dtype=torch.int32, device=self.dev)
-        _lib.check(self.lib.conan_streams_bypass_state(self.h, p, len(a), _ptr(buf), _stream()))
-        self._release()
-        return [dict(wet=int(r[0]), dry=int(r[1]), dry_eff=int(r[2])) for r in buf.cpu().tolist()]
+        return self._feature_state("bypass", slots)
 
     def step_wav_bypass(self):
         """The frame-end wet and effective dry levels the last wav-in call produced (conan_step_wav_bypass; joins pipelined work) ->
         (wet [n, seg] int32, dry [n, seg] int32) in call order; rows without the feature, rows that emitted nothing and entries past a
         row's emitted frames are 0."""
-        n = self._last_wav_n
-        wet = torch.empty(max(n, 1), self.seg, dtype=torch.int32, device=self.dev)      # (before any wav-in call the library answers CONAN_ERR_STATE)
-        dry = torch.empty(max(n, 1), self.seg, dtype=torch.int32, device=self.dev)
-        _lib.check(self.lib.conan_step_wav_bypass(self.h, _ptr(wet), _ptr(dry), _stream()))
-        self._release()
-        return wet[:n], dry[:n]
+        return self._last_rows("bypass", 2)
 
     def set_comfort(self, slots, cfg=True, **kw):
         """conan_streams_set_comfort: comfort noise in place of the silence of a closed activity gate (wav-in steps only; the slot needs
@@ -1154,75 +1115,38 @@ class Streams:
         resets.  The level restarts from the start level when a slot is enabled, after reseed=True and at the first chunk after a
         reset of the front-end; reseed=False on an enabled slot replaces the parameters and keeps the level.  Slot snapshots do not
         carry it: query comfort_state, export, import, then set_comfort(start=level, reseed=True)."""
-        a, p = _i32(slots)
-        if cfg is None:
-            if kw:
-                raise ValueError("set_comfort: cfg=None turns the comfort noise off and takes no keywords")
-            c = _lib.ComfortCfg()      # (mode = 0)
-        elif isinstance(cfg, _lib.ComfortCfg):
-            c = cfg
-        else:
-            c = _lib.comfort_cfg(**dict({} if cfg is True else cfg, **kw))
-        _lib.check(self.lib.conan_streams_set_comfort(self.h, p, len(a), C.byref(c), _stream()))
-        self._release()
+        self._set_feature("comfort", slots, cfg, kw)
 
     def comfort(self, slots):
         """conan_streams_comfort: per slot the setting as _lib.comfort_keywords reports it (set_comfort takes it back), None for a slot
         without the feature."""
-        out = []
-        for slot in slots:
-            c = _lib.ComfortCfg()
-            _lib.check(self.lib.conan_streams_comfort(self.h, int(slot), C.byref(c)))
-            out.append(_lib.comfort_keywords(c) if c.mode else None)
-        return out
+        return self._get_feature("comfort", slots)
 
     def comfort_state(self, slots):
         """conan_streams_comfort_state (joins pipelined work, synchronises): per slot dict(level, idle_frames), the comfort level after
         the slot's last emitted frame; a slot whose level is about to restart reports its start level.  A slot without the feature
         is an error."""
-        a, p = _i32(slots)
-        buf = torch.empty(len(a), 16, dtype=torch.uint8, device=self.dev)
-        _lib.check(self.lib.conan_streams_comfort_state(self.h, p, len(a), _ptr(buf), _stream()))
-        self._release()
-        return _comfort_states(buf)
+        return self._feature_state("comfort", slots)
 
     def step_wav_comfort(self):
         """The frame-end comfort levels the last wav-in call produced (conan_step_wav_comfort; joins pipelined work) -> [n, seg] int32
         in call order; rows without the feature (or without a detector), rows that emitted nothing and entries past a row's emitted
         frames are 0.  _lib.comfort_dbov turns a level into the RFC 3389 noise level byte."""
-        n = self._last_wav_n
-        lvl = torch.empty(max(n, 1), self.seg, dtype=torch.int32, device=self.dev)      # (before any wav-in call the library answers CONAN_ERR_STATE)
-        _lib.check(self.lib.conan_step_wav_comfort(self.h, _ptr(lvl), _stream()))
-        self._release()
-        return lvl[:n]
+        return self._last_rows("comfort", 1)[0]
 
     def step_wav_contour(self):
         """The contour the last wav-in call handed the decoder (conan_step_wav_contour; joins pipelined work) -> (f0 [n, seg] log2 Hz,
         uv [n, seg]) in call order; rows that do not follow, and entries past a row's emitted frames, are 0."""
-        n = self._last_wav_n
-        f0 = torch.empty(max(n, 1), self.seg, device=self.dev)      # (before any wav-in call the library answers CONAN_ERR_STATE)
-        uv = torch.empty(max(n, 1), self.seg, device=self.dev)
-        _lib.check(self.lib.conan_step_wav_contour(self.h, _ptr(f0), _ptr(uv), _stream()))
-        self._release()
-        return f0[:n], uv[:n]
+        return self._last_rows("follow", 2, torch.float32)
 
     def pitch(self, slots):
         """conan_streams_pitch: per slot the pitch control's keywords as set_pitch takes them, None for a slot without one."""
-        out = []
-        for slot in slots:
-            c = _lib.PitchCfg()
-            _lib.check(self.lib.conan_streams_pitch(self.h, int(slot), C.byref(c)))
-            out.append(_lib.pitch_keywords(c) if c.enabled else None)
-        return out
+        return self._get_feature("pitch", slots)
 
     def input_level(self, slots):
         """conan_streams_input_level: float64 [n, 4] (cuda) rows (L_k, G_k, P_k, J_k) of the slots' latest update instants - the
         loudness read, the gain the current ramp ends at, the peak so far, the complete blocks.  Joins pipelined work."""
-        a, p = _i32(slots)
-        out = torch.empty(len(a), 4, dtype=torch.float64, device=self.dev)
-        _lib.check(self.lib.conan_streams_input_level(self.h, p, len(a), _ptr(out), _stream()))
-        self._release()
-        return out
+        return self._feature_state("level", slots)
 
     def set_output_level(self, slots, cfg=True, seed=None, **kw):
         """conan_streams_set_output_level: the same causal BS.1770 leveller on the slots' own vocoder audio, between conv_post and the
@@ -1231,43 +1155,17 @@ class Streams:
         must be at the start of their vocoder streams; seed: uint8 [n, bytes] (cuda) rows of output_level_state from a stream at the
         same position (a hand-over).  The setting survives resets, which restart the meter.  output_levels[slot] holds every keyword
         of a levelled slot."""
-        a, p = _i32(slots)
-        if cfg is None:
-            if kw:
-                raise ValueError("set_output_level: cfg=None turns the leveller off and takes no keywords")
-            c = _lib.LevelCfg()      # (enabled = 0)
-        else:
-            c = _lib.level_cfg(**dict({} if cfg is True else cfg, **kw))
-        sp, ld = None, 0
-        if seed is not None:
-            if seed.dtype != torch.uint8 or seed.dim() != 2 or seed.shape[0] != len(a) or not seed.is_cuda or seed.stride(1) != 1:
-                raise ValueError("set_output_level: seed must be a cuda uint8 [n, bytes] tensor, as output_level_state returns it")
-            sp, ld = _ptr(seed), int(seed.stride(0))
-        _lib.check(self.lib.conan_streams_set_output_level(self.h, p, len(a), C.byref(c), sp, ld, _stream()))
-        for slot in a:
-            if c.enabled:
-                self.output_levels[int(slot)] = _lib.level_keywords(c)
-            else:
-                self.output_levels.pop(int(slot), None)
+        self._set_feature("out_level", slots, cfg, kw, seed=seed)
 
     def output_level(self, slots):
         """conan_streams_output_level: float64 [n, 4] (cuda) rows (L_k, G_k, P_k, J_k) of the instant the slots' latest ramps end at.
         Joins pipelined work."""
-        a, p = _i32(slots)
-        out = torch.empty(len(a), 4, dtype=torch.float64, device=self.dev)
-        _lib.check(self.lib.conan_streams_output_level(self.h, p, len(a), _ptr(out), _stream()))
-        self._release()
-        return out
+        return self._feature_state("out_level", slots)
 
     def output_level_state(self, slots):
         """conan_streams_output_level_state: uint8 [n, bytes] (cuda), the slots' leveller states for set_output_level(seed=).  Joins
         pipelined work."""
-        a, p = _i32(slots)
-        nbytes = int(_lib.check(self.lib.conan_streams_output_level_state_bytes(self.h)))
-        out = torch.empty(len(a), nbytes, dtype=torch.uint8, device=self.dev)
-        _lib.check(self.lib.conan_streams_output_level_state(self.h, p, len(a), _ptr(out), nbytes, _stream()))
-        self._release()
-        return out
+        return self._feature_seed_rows("out_level", slots)
 
     def set_conceal(self, slots, cfg=True, rate=None, seed=None, **kw):
         """conan_streams_set_conceal: loss concealment on the slots' wav-in rows (include/conan_hip.h, conan_conceal_cfg).  cfg: True
@@ -1276,31 +1174,11 @@ class Streams:
         conceal_state (a hand-over).  It may be called at any time (it joins pipelined work) and survives resets; the state restarts
         when a slot that was off is enabled and at the first repair after a reset of the front-end.  Slot snapshots do not carry it.
         The repair itself is conceal(), or lost= on the wav-in steps."""
-        a, p = _i32(slots)
-        if cfg is None:
-            if kw:
-                raise ValueError("set_conceal: cfg=None turns the concealment off and takes no keywords")
-            c = _lib.ConcealCfg()      # (enabled = 0)
-        elif isinstance(cfg, _lib.ConcealCfg):
-            c = cfg
-        else:
-            c = _conceal_cfg(dict({} if cfg is True else cfg, **kw), self.model_rate if rate is None else int(rate))
-        sp, ld = None, 0
-        if seed is not None:
-            if seed.dtype != torch.uint8 or seed.dim() != 2 or seed.shape[0] != len(a) or not seed.is_cuda or seed.stride(1) != 1:
-                raise ValueError("set_conceal: seed must be a cuda uint8 [n, bytes] tensor, as conceal_state returns it")
-            sp, ld = _ptr(seed), int(seed.stride(0))
-        _lib.check(self.lib.conan_streams_set_conceal(self.h, p, len(a), C.byref(c), sp, ld, _stream()))
-        self._release()
+        self._set_feature("conceal", slots, cfg, kw, dict(rate=self.model_rate if rate is None else int(rate)), seed=seed)
 
     def conceal_cfg(self, slots):
         """conan_streams_conceal_cfg: per slot the dict of its fields (set_conceal takes it back), None for a slot without the feature."""
-        out = []
-        for slot in slots:
-            c = _lib.ConcealCfg()
-            _lib.check(self.lib.conan_streams_conceal_cfg(self.h, int(slot), C.byref(c)))
-            out.append(_lib.conceal_keywords(c) if c.enabled else None)
-        return out
+        return self._get_feature("conceal", slots)
 
     def conceal(self, slots, wav, samples, lost):
         """conan_streams_conceal: repairs the lost packets of the rows IN PLACE, in front of the step call that takes them.  wav: a
@@ -1323,12 +1201,7 @@ class Streams:
     def conceal_state(self, slots):
         """conan_streams_conceal_state: uint8 [n, bytes] (cuda), the slots' concealment states for set_conceal(seed=).  Joins pipelined
         work."""
-        a, p = _i32(slots)
-        nbytes = int(self.lib.conan_conceal_state_bytes())
-        out = torch.empty(len(a), nbytes, dtype=torch.uint8, device=self.dev)
-        _lib.check(self.lib.conan_streams_conceal_state(self.h, p, len(a), _ptr(out), nbytes, _stream()))
-        self._release()
-        return out
+        return self._feature_seed_rows("conceal", slots)
 
     def set_output_format(self, slots, fmt):
         """conan_streams_set_output_format: the slots' audio leaves every step (and flush_output) as 'f32', 's16', 'ulaw' or 'alaw',

@@ -165,9 +165,9 @@ def _engine(n):
 
 def test_engine_activity_values():
     from conan_amd.engine import StreamingVoiceConversionEngine as Engine
-    got = Engine._activities([4, 5, 6, 7, 8], [None, True, "detect", dict(hold_frames=3, gate=False), False])
+    got = Engine._values("activity", [None, True, "detect", dict(hold_frames=3, gate=False), False], 5)
     assert got == [None, dict(gate=True), dict(gate=False), dict(hold_frames=3, gate=False), None]
-    assert Engine._activities([0, 1], "detect") == [dict(gate=False)] * 2
+    assert Engine._values("activity", "detect", 2) == [dict(gate=False)] * 2
     eng = _engine(2)
     calls = [lambda **kw: eng.start_wav(kw.pop("ref_mel"), **kw), lambda **kw: eng.open_slots([0, 1], kw.pop("ref_mel"), **kw),
              lambda **kw: eng.infer_wav(None, kw.pop("ref_mel"), **kw), lambda **kw: eng.infer_wav_staggered([None, None], [0, 1], kw.pop("ref_mel"), **kw)]
@@ -179,14 +179,14 @@ def test_engine_activity_values():
         with pytest.raises(ValueError, match="activity: 2.5"):
             call(ref_mel=object(), activity=2.5)
     # a stream-set that never used it is left alone: no setter call at all
-    eng._activity = False
+    eng._used = set()
     eng.st = types.SimpleNamespace()      # (any attribute access would raise)
-    eng._set_activity(eng.slots, [None, None])
-    assert eng._activity is False
+    eng._apply("activity", eng.slots, [None, None])
+    assert "activity" not in eng._used
     # once used, None turns a slot off and a dict travels as the cfg
     seen = []
     eng.st = types.SimpleNamespace(set_activity=lambda slots, cfg=True, **kw: seen.append((list(slots), cfg, kw)))
-    eng._set_activity(eng.slots, [dict(gate=False), None])
-    assert eng._activity is True and seen == [([0], dict(gate=False), {}), ([1], None, {})]
+    eng._apply("activity", eng.slots, [dict(gate=False), None])
+    assert "activity" in eng._used and seen == [([0], dict(gate=False), {}), ([1], None, {})]
     eng.set_activity([1], hold_frames=2)
     assert seen[-1] == ([1], True, dict(hold_frames=2))

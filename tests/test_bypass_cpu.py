@@ -144,9 +144,9 @@ def _engine(n):
 
 def test_engine_bypass_values():
     from conan_amd.engine import StreamingVoiceConversionEngine as Engine
-    got = Engine._bypasses([4, 5, 6, 7], [None, True, dict(wet=0.5, dry=0.5), False])
+    got = Engine._values("bypass", [None, True, dict(wet=0.5, dry=0.5), False], 4)
     assert got == [None, {}, dict(wet=0.5, dry=0.5), None]
-    assert Engine._bypasses([0, 1], dict(dry=0.1)) == [dict(dry=0.1)] * 2
+    assert Engine._values("bypass", dict(dry=0.1), 2) == [dict(dry=0.1)] * 2
     eng = _engine(2)
     calls = [lambda **kw: eng.start_wav(kw.pop("ref_mel"), **kw), lambda **kw: eng.open_slots([0, 1], kw.pop("ref_mel"), **kw),
              lambda **kw: eng.infer_wav(None, kw.pop("ref_mel"), **kw), lambda **kw: eng.infer_wav_staggered([None, None], [0, 1], kw.pop("ref_mel"), **kw)]
@@ -156,14 +156,14 @@ def test_engine_bypass_values():
         with pytest.raises(ValueError, match="bypass: 'dry'"):
             call(ref_mel=object(), bypass="dry")
     # a stream-set that never used it is left alone: no setter call at all
-    eng._bypass = False
+    eng._used = set()
     eng.st = types.SimpleNamespace()      # (any attribute access would raise)
-    eng._set_bypass(eng.slots, [None, None])
-    assert eng._bypass is False
+    eng._apply("bypass", eng.slots, [None, None])
+    assert "bypass" not in eng._used
     # once used, None turns a slot off and a dict travels as the cfg
     seen = []
     eng.st = types.SimpleNamespace(set_bypass=lambda slots, cfg=True, **kw: seen.append((list(slots), cfg, kw)))
-    eng._set_bypass(eng.slots, [dict(dry=0.2), None])
-    assert eng._bypass is True and seen == [([0], dict(dry=0.2), {}), ([1], None, {})]
+    eng._apply("bypass", eng.slots, [dict(dry=0.2), None])
+    assert "bypass" in eng._used and seen == [([0], dict(dry=0.2), {}), ([1], None, {})]
     eng.set_bypass([1], wet=0.0, dry=1.0)
     assert seen[-1] == ([1], True, dict(wet=0.0, dry=1.0))

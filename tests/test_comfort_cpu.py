@@ -162,9 +162,9 @@ def _engine(n):
 
 def test_engine_comfort_values():
     from conan_amd.engine import StreamingVoiceConversionEngine as Engine
-    got = Engine._comforts([4, 5, 6, 7], [None, True, dict(level_db=-50.0, follow=False), False])
+    got = Engine._values("comfort", [None, True, dict(level_db=-50.0, follow=False), False], 4)
     assert got == [None, {}, dict(level_db=-50.0, follow=False), None]
-    assert Engine._comforts([0, 1], dict(colour=2)) == [dict(colour=2)] * 2
+    assert Engine._values("comfort", dict(colour=2), 2) == [dict(colour=2)] * 2
     eng = _engine(2)
     calls = [lambda **kw: eng.start_wav(kw.pop("ref_mel"), **kw), lambda **kw: eng.open_slots([0, 1], kw.pop("ref_mel"), **kw),
              lambda **kw: eng.infer_wav(None, kw.pop("ref_mel"), **kw), lambda **kw: eng.infer_wav_staggered([None, None], [0, 1], kw.pop("ref_mel"), **kw)]
@@ -174,15 +174,15 @@ def test_engine_comfort_values():
         with pytest.raises(ValueError, match="comfort: 'pink'"):
             call(ref_mel=object(), comfort="pink")
     # a stream-set that never used it is left alone: no setter call at all
-    eng._comfort = False
+    eng._used = set()
     eng.st = types.SimpleNamespace()      # (any attribute access would raise)
-    eng._set_comfort(eng.slots, [None, None])
-    assert eng._comfort is False
+    eng._apply("comfort", eng.slots, [None, None])
+    assert "comfort" not in eng._used
     # once used, None turns a slot off and a dict travels as the cfg, with a seed of the slot's own unless one is given
     seen = []
     eng.st = types.SimpleNamespace(set_comfort=lambda slots, cfg=True, **kw: seen.append((list(slots), cfg, kw)))
-    eng._set_comfort([3, 4, 5], [dict(colour=0), None, dict(seed=9)])
-    assert eng._comfort is True
+    eng._apply("comfort", [3, 4, 5], [dict(colour=0), None, dict(seed=9)])
+    assert "comfort" in eng._used
     assert seen == [([3], dict(colour=0, seed=_lib.comfort_seed(3)), {}), ([4], None, {}), ([5], dict(seed=9), {})]
     eng.set_comfort([1], follow=False, level_db=-40.0)
     assert seen[-1] == ([1], True, dict(follow=False, level_db=-40.0))

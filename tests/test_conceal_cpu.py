@@ -138,9 +138,9 @@ def _engine(n):
 def test_engine_conceal_values():
     from conan_amd.engine import StreamingVoiceConversionEngine as Engine
     cfg = _lib.conceal_cfg(8000)
-    got = Engine._conceals([4, 5, 6, 7, 8], [None, True, dict(fade=0), False, cfg])
+    got = Engine._values("conceal", [None, True, dict(fade=0), False, cfg], 5)
     assert got == [None, {}, dict(fade=0), None, cfg]
-    assert Engine._conceals([0, 1], dict(hold=3)) == [dict(hold=3)] * 2
+    assert Engine._values("conceal", dict(hold=3), 2) == [dict(hold=3)] * 2
     eng = _engine(2)
     calls = [lambda **kw: eng.start_wav(kw.pop("ref_mel"), **kw), lambda **kw: eng.open_slots([0, 1], kw.pop("ref_mel"), **kw),
              lambda **kw: eng.infer_wav(None, kw.pop("ref_mel"), **kw), lambda **kw: eng.infer_wav_staggered([None, None], [0, 1], kw.pop("ref_mel"), **kw)]
@@ -157,16 +157,16 @@ def test_engine_conceal_values():
         with pytest.raises(ValueError, match="need conceal="):
             call(ref_mel=object(), lost=[object(), object()])
     # a stream-set that never used it is left alone: no setter call at all
-    eng._conceal = False
+    eng._used = set()
     eng.st = types.SimpleNamespace()      # (any attribute access would raise)
-    eng._set_conceal(eng.slots, [None, None], [None, None])
-    assert eng._conceal is False
+    eng._apply("conceal", eng.slots, [None, None], [None, None])
+    assert "conceal" not in eng._used
     # once used, None turns a slot off, a dict travels as the cfg and True stands for the rate's defaults
     seen = []
     eng.st = types.SimpleNamespace(set_conceal=lambda slots, cfg=True, **kw: seen.append((list(slots), cfg, kw)))
-    eng._set_conceal(eng.slots, [dict(fade=0), None], [8000, None])
-    assert eng._conceal is True and seen == [([0], dict(fade=0), dict(rate=8000)), ([1], None, dict(rate=None))]
-    eng._set_conceal(eng.slots, [{}, cfg], [48000, None])
+    eng._apply("conceal", eng.slots, [dict(fade=0), None], [8000, None])
+    assert "conceal" in eng._used and seen == [([0], dict(fade=0), dict(rate=8000)), ([1], None, dict(rate=None))]
+    eng._apply("conceal", eng.slots, [{}, cfg], [48000, None])
     assert seen[2:] == [([0], True, dict(rate=48000)), ([1], cfg, dict(rate=None))]
     eng.set_conceal([1], hold=0)
     assert seen[-1] == ([1], True, dict(hold=0))

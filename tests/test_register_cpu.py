@@ -145,13 +145,13 @@ def test_engine_register_voice_needs_a_voice_with_a_register():
 def test_engine_register_values():
     from conan_amd.engine import StreamingVoiceConversionEngine as Engine
     bank = _Bank()
-    got = Engine._registers([4, 5, 6, 7], [None, 7.25, "voice", dict(target=6.0, max_shift=0.5)], (bank, [0, 0, 2, 0]))
+    got = Engine._values("register", [None, 7.25, "voice", dict(target=6.0, max_shift=0.5)], 4, voice=(bank, [0, 0, 2, 0]))
     assert got == [None, dict(target=7.25), dict(target=8.25), dict(target=6.0, max_shift=0.5)]
-    assert Engine._registers([0, 1], False, None) == [None, None]
-    assert Engine._registers([0, 1], "voice", (bank, [2, 0])) == [dict(target=8.25), dict(target=7.5)]
+    assert Engine._values("register", False, 2) == [None, None]
+    assert Engine._values("register", "voice", 2, voice=(bank, [2, 0])) == [dict(target=8.25), dict(target=7.5)]
     # a stream-set that never used it is left alone: no setter call at all
     eng = _engine(2)
-    eng._registered = False
+    eng._used = set()
     eng.st = types.SimpleNamespace()      # (any attribute access would raise)
-    eng._set_register(eng.slots, [None, None])
-    assert eng._registered is False
+    eng._apply("register", eng.slots, [None, None])
+    assert "register" not in eng._used
