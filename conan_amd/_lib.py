@@ -153,6 +153,8 @@ _PROTOS = {
     "conan_streams_output_level_state_bytes": (C.c_int64, [C.c_void_p]),
     "conan_streams_conceal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_conceal_state_bytes": (C.c_int64, []),
+    "conan_denoise_state_bytes": (C.c_int64, []),
+    "conan_mel_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_conceal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_trim_silence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
@@ -608,6 +610,68 @@ def conceal_cfg(rate=None, **kw):
     return ConcealCfg(1, *[int(f[n]) for n in names])
 
 
+class DenoiseCfg(C.Structure):
+    """conan_denoise_cfg (include/conan_hip.h)."""
+    _fields_ = [("enabled", C.c_int32), ("reseed", C.c_int32), ("bias", C.c_int32), ("knee", C.c_int32), ("slope", C.c_int32), ("depth", C.c_int32),
+                ("close_step", C.c_int32), ("open_step", C.c_int32), ("rise", C.c_int32), ("fall_shift", C.c_int32), ("floor_min", C.c_int32),
+                ("smooth", C.c_int32), ("out_floor", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+DENOISE_MAX_BINS = 256
+
+
+class DenoiseState(C.Structure):
+    """conan_denoise_state (include/conan_hip.h): a row of Streams.denoise_state / Context.mel_denoise(state=True)."""
+    _fields_ = [("frames", C.c_int64), ("bins", C.c_int32), ("reserved", C.c_int32), ("floor", C.c_int32 * DENOISE_MAX_BINS),
+                ("att", C.c_int32 * DENOISE_MAX_BINS)]
+
+
+DENOISE_FULL = 1 << 20
+# (field, lowest, highest) of an enabled conan_denoise_cfg's integer fields
+DENOISE_RANGES = (("bias", 0, DENOISE_FULL), ("knee", 0, DENOISE_FULL), ("slope", 0, 1 << 16), ("depth", 1, DENOISE_FULL),
+                  ("close_step", 1, DENOISE_FULL), ("open_step", 1, DENOISE_FULL), ("rise", 0, DENOISE_FULL), ("fall_shift", 0, 8),
+                  ("floor_min", -DENOISE_FULL, DENOISE_FULL), ("smooth", 0, 1))
+
+
+def denoise_level(db, natural_log=False):
+    """A decibel figure as the suppressor's integer level: 1024 steps per unit of the mel's logarithm, which is 20 dB for log10 and
+    20 / ln(10) = 8.686 dB for the natural logarithm.  Converted once, on the host."""
+    return int(round(float(db) * 1024.0 / (20.0 / math.log(10.0) if natural_log else 20.0)))
+
+
+def denoise_cfg(natural_log=False, mel_vmin=-6.0, eps=1e-6, bias_db=3.0, knee_db=6.0, slope=512, depth_db=18.0, close_db=4.5, open_db=None,
+                rise_db=0.05, fall_shift=1, floor_min_db=-100.0, smooth=True, out_floor=None, reseed=False, bias=None, knee=None, depth=None,
+                close_step=None, open_step=None, rise=None, floor_min=None):
+    """An enabled conan_denoise_cfg for a mel of the given log base (conan_mel_cfg.natural_log, .vmin, .eps).  bias_db: the floor is
+    read this much higher; knee_db: the SNR under which a bin begins to close; slope: Q8 attenuation per step under the knee (512: 2 dB
+    per dB); depth_db: the largest attenuation; close_db / open_db: its largest rise and fall per frame (open_db=None: the depth, a bin
+    opens within the frame that needs it); rise_db: the floor's rise per frame; fall_shift: the floor falls by ceil(distance /
+    2^fall_shift); floor_min_db: the floor's lowest level; smooth: the 1-2-1 average of the attenuation across bins; out_floor: the
+    smallest value an attenuated bin takes (None: max(mel_vmin, log(eps)) in f32).  The defaults are choices, not measurements.
+    Every decibel figure is converted once (denoise_level); the integer keywords (bias, knee, depth, close_step, open_step, rise,
+    floor_min) give a field directly and win over their dB forms.  A field outside its range is a ValueError."""
+    pick = lambda direct, db: denoise_level(db, natural_log) if direct is None else int(direct)      # noqa: E731
+    step = lambda direct, db: max(1, denoise_level(db, natural_log)) if direct is None else int(direct)      # noqa: E731
+    d = step(depth, depth_db)
+    if out_floor is None:
+        out_floor = max(float(mel_vmin), math.log(float(eps)) if natural_log else math.log10(float(eps)))
+    c = DenoiseCfg(1, int(bool(reseed)), pick(bias, bias_db), pick(knee, knee_db), int(slope), d, step(close_step, close_db),
+                   d if open_step is None and open_db is None else step(open_step, open_db), pick(rise, rise_db), int(fall_shift),
+                   pick(floor_min, floor_min_db), int(bool(smooth)), float(out_floor), (C.c_int32 * 3)(0, 0, 0))
+    for name, lo, hi in DENOISE_RANGES:
+        if not lo <= getattr(c, name) <= hi:
+            raise ValueError(f"denoise: {name} = {getattr(c, name)} is outside {lo} .. {hi}")
+    if not math.isfinite(c.out_floor):
+        raise ValueError(f"denoise: out_floor = {out_floor!r} is not finite")
+    return c
+
+
+def denoise_keywords(c):
+    """denoise_cfg's keywords of an enabled DenoiseCfg in the integer forms that give the same fields back exactly: the form
+    Streams.denoise reports a setting in."""
+    return dict({name: int(getattr(c, name)) for name, _, _ in DENOISE_RANGES}, smooth=bool(c.smooth), out_floor=float(c.out_floor))
+
+
 class SlotFeature(typing.NamedTuple):
     """One per-slot feature of a stream-set, as Streams and the engine read it.  A symbol the library does not have is None."""
     keyword: str                  # the engine's keyword (start_wav, open_slots, ...)
@@ -651,6 +715,8 @@ SLOT_FEATURES = {f.keyword: f for f in (
                 "conan_streams_bypass_state", BypassState, last="conan_step_wav_bypass"),
     SlotFeature("conceal", "the concealment", ConcealCfg, "enabled", conceal_cfg, conceal_keywords, "conan_streams_set_conceal",
                 "conan_streams_conceal_cfg", seed_state="conan_streams_conceal_state", seed_bytes="conan_conceal_state_bytes"),
+    SlotFeature("denoise", "the noise suppression", DenoiseCfg, "enabled", denoise_cfg, denoise_keywords, "conan_streams_set_denoise",
+                "conan_streams_denoise", seed_state="conan_streams_denoise_state", seed_bytes="conan_denoise_state_bytes"),
     SlotFeature("comfort", "the comfort noise", ComfortCfg, "mode", comfort_cfg, comfort_keywords, "conan_streams_set_comfort",
                 "conan_streams_comfort", "conan_streams_comfort_state", ComfortState, last="conan_step_wav_comfort"),
     SlotFeature("out_level", "the leveller", LevelCfg, "enabled", level_cfg, level_keywords, "conan_streams_set_output_level",

@@ -780,6 +780,25 @@ int conan_conceal(conan_ctx* ctx, const conan_conceal_cfg* cfg, int format, void
   return guarded([&] { conc::whole(ctx, cfg, format, x_dev, ld, n, samples, lost_dev, lost_ld, stream); });
 }
 
+// ---- input noise suppression (denoise.hip): conan_mel_denoise, conan_streams_set_denoise, conan_streams_denoise,
+// conan_denoise_state_bytes, conan_streams_denoise_state
+int conan_mel_denoise(conan_ctx* ctx, const conan_denoise_cfg* cfg, const float* mel_dev, int n, const int32_t* frames, int64_t ld, int num_mels,
+                      const conan_denoise_state* seed_dev, float* out_dev, conan_denoise_state* state_out_dev, void* stream) {
+  return guarded([&] { denoise::whole(ctx, cfg, mel_dev, n, frames, ld, num_mels, seed_dev, out_dev, state_out_dev, stream); });
+}
+
+int conan_streams_set_denoise(conan_streams* s, const int32_t* slots, int n, const conan_denoise_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream) {
+  return guarded([&] { denoise::set_denoise(s, slots, n, cfg, seed_dev, seed_ld, stream); });
+}
+
+int conan_streams_denoise(const conan_streams* s, int slot, conan_denoise_cfg* cfg_out) { return guarded([&] { wavio::get_setting(s, &conan_streams::dn, slot, cfg_out, "conan_streams_denoise"); }); }
+
+int64_t conan_denoise_state_bytes(void) { return (int64_t)sizeof(cnk::DnState); }
+
+int conan_streams_denoise_state(conan_streams* s, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream) {
+  return guarded([&] { denoise::state(s, slots, n, rows_dev, ld, stream); });
+}
+
 int conan_streams_set_input_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg) {
   return guarded([&] { wavio::set_input_rate(s, slots, n, cfg); });
 }

@@ -627,6 +627,38 @@ struct ConcArgs {
 };
 void launch_conceal(const ConcArgs& a, hipStream_t st);
 
+// Input noise suppression (denoise.hip; include/conan_hip.h, conan_denoise_cfg): the spectral gate on log-mel frames of nm bins.  One
+// workgroup of 64 * ceil(nm / 64) lanes per table row; lane b keeps the floor and the attenuation of bin b in registers across the
+// row's frames.  DnState is the published conan_denoise_state; a record whose `bins` is not nm is the state before the first frame.
+//   denoise_signal_kernel: row i of x [n][.][nm] (stride ld floats), nnew frames from frame 0, into y (may be x); the state starts
+//     from seed[row] (seed given and reseed = 0) or before the first frame and goes to state_out[state_row] (state_row >= 0).
+//   denoise_stream_kernel: the frames [f0, f0 + nnew) of slot's mel ring in place (frame f at f & (LM - 1)), from state[slot]
+//     (reseed = 0) or before the first frame, written back to state[slot]; then chunk row r < rows of block `chunk` of fe_chunk <-
+//     ring frame pos + min(r, real - 1).
+//   Both read the record once, in front of a barrier, and write one behind it: seed may be state_out.  floor and att of a record are
+//   read clamped to -2^20 .. 2^20 and 0 .. 2^20, the range the law keeps them in.
+constexpr int kDnMaxBins = 256;
+struct DnState { long long frames; int bins, reserved; int floor[kDnMaxBins], att[kDnMaxBins]; };
+static_assert(sizeof(DnState) == 2064, "conan_denoise_state");
+struct DnRow {
+  int bias, knee, slope, depth, close_step, open_step, rise, fall_shift, floor_min, smooth;
+  float out_floor;
+  int slot, state_row, reseed;
+  int row, f0, nnew, pos, rows, real, chunk, pad_;
+};
+static_assert(sizeof(DnRow) == 88, "uploaded as 22 ints");
+struct DnSignalArgs {
+  const float* x; float* y; long long ld;
+  const DnState* seed; DnState* state_out;
+  const DnRow* tab; int rows, nm;
+};
+struct DnStreamArgs {
+  float* mring; float* chunk; DnState* state;
+  const DnRow* tab; int rows, nm, LM, pad_;
+};
+void launch_denoise_signal(const DnSignalArgs& a, hipStream_t st);
+void launch_denoise_stream(const DnStreamArgs& a, hipStream_t st);
+
 // Silence trimming (trim.hip; include/conan_hip.h, conan_trim_cfg).  Row i has lens[i] samples at wav + i * ld and F = 1 + lens[i] / hop
 // frames; its flags are act[i * act_ld + f] (any non-zero counts as 1).  The plan kernel (one workgroup per row) writes the row's two
 // prefix arrays pa / pb [i * pre_ld + 0 .. F] (scratch: the prefixes of act and of m1), the kept-frame mask m2 to mask[i * mask_ld + f]

@@ -103,7 +103,7 @@ struct StageSets {
   ~StageSets() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
-// ---- the per-slot source features (level.hip, f0.hip, register.hip, activity.hip, bypass.hip, conceal.hip, level_out.hip) share one
+// ---- the per-slot source features (level.hip, f0.hip, register.hip, activity.hip, bypass.hip, conceal.hip, denoise.hip, level_out.hip) share one
 // slot-setting type.  cfg: per slot the configuration as set (zeros: off; `reseed` kept 0), which persists across resets; n_on: slots
 // with the feature on (On: the cfg field that says so).  Empty until the feature's first enabling call (assign(), from its *_init()
 // beside the device state and row tables).  pending: the slot's state restarts in its next kernel row, which clears the flag - a host
@@ -326,8 +326,17 @@ struct conan_streams {
     StageSets<cnk::ConcRow> sets;
   } conc;
   void conceal_init();
+  // input noise suppression (conan_streams_set_denoise; denoise.hip).  state: [max_slots] records of conan_denoise_state, read and
+  // written by the rows of denoise_stream_kernel in the order of the front-end launches; pending restarts it before the slot's next
+  // frame (a seed row becomes the state at once and clears the flag).  Rows: one per suppressing call row that completes a frame or
+  // emits.  Event: behind the kernel's launch, in the front-end work.
+  struct Denoise : SlotSetting<conan_denoise_cfg> {
+    cnk::DnState* state = nullptr;
+    StageSets<cnk::DnRow> sets;
+  } dn;
+  void denoise_init();
   // a reset with CONAN_MODEL_FRONTEND: the settings stay; the states restart in the slots' next rows (host flags: no launch)
-  void restart_features(const int32_t* slots, int n) { reg.restart(slots, n); act.restart(slots, n); byp.restart(slots, n); cmf.restart(slots, n); conc.restart(slots, n); }
+  void restart_features(const int32_t* slots, int n) { reg.restart(slots, n); act.restart(slots, n); byp.restart(slots, n); cmf.restart(slots, n); conc.restart(slots, n); dn.restart(slots, n); }
   void ragged_init();
   void resample_init();        // staging, row tables and the history ring (conan_streams_set_input_rate)
   void rs_stage_init();        // staging and row tables only (conan_streams_set_input_format: no stream state)
@@ -675,12 +684,12 @@ struct WavCall {
 };
 // The front-end work of a wav-in call: at most one entry per position, run in this order on one stream (the caller's, or as
 // step_pipelined's `pre`).  The ...End entries record the events of the sets the mel front-end launch is the last to read.
-enum FrontPos { kFrResample, kFrLevel, kFrMel, kFrLevelEnd, kFrResampleEnd, kFrF0, kFrRegister, kFrActivity, kFrBypass, kFrComfort, kFrCount };
+enum FrontPos { kFrResample, kFrLevel, kFrMel, kFrDenoise, kFrLevelEnd, kFrResampleEnd, kFrF0, kFrRegister, kFrActivity, kFrBypass, kFrComfort, kFrCount };
 struct FrontWork {
   std::function<void(hipStream_t)> at[kFrCount];
   void run(hipStream_t st) const { for (const auto& f : at) if (f) f(st); }
 };
-// Each feature of the wav-in step has a per-call WavStage in its own file (level::, f0:: with reg::'s rows, act::, byp::), all of one
+// Each feature of the wav-in step has a per-call WavStage in its own file (level::, f0:: with reg::'s rows, act::, byp::, comfort::, denoise::), all of one
 // shape, called by step_wav in that order:
 //   plan      the call's host rows, per-group flags and FLOPs; throws on anything refused.  const with respect to the stream-set and
 //             run for every feature before any staging set is taken or any state changes: a refused call leaves everything as it was
@@ -913,6 +922,24 @@ void repair(conan_streams* s, const int32_t* slots, int n, const int32_t* sample
             void* stream);
 void state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream);
 }  // namespace conc
+
+// ---- input noise suppression (denoise.hip): the kernels' host side and the bodies of api.hip's entry points
+namespace denoise {
+void check_cfg(const conan_denoise_cfg& c, const char* who);      // host only
+cnk::DnRow row(const conan_denoise_cfg& c);      // the cfg's fields of a row that starts before its first frame and names no slot
+void whole(conan_ctx* ctx, const conan_denoise_cfg* cfg, const float* mel_dev, int n, const int32_t* frames, int64_t ld, int num_mels,
+           const conan_denoise_state* seed_dev, float* out_dev, conan_denoise_state* state_out_dev, void* stream);
+void set_denoise(conan_streams* s, const int32_t* slots, int n, const conan_denoise_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream);
+void state(conan_streams* s, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream);
+// The suppressing slots that complete a frame or emit get one table row each; the launch sits directly behind the mel front-end's
+// (kFrDenoise) and records its set's event itself.
+struct WavStage {
+  std::vector<cnk::DnRow> rows;
+  void plan(const conan_streams* s, const WavCall& c);
+  void enqueue(conan_streams* s, const WavCall& c, hipStream_t cst, FrontWork& front, std::vector<conan_streams::OutPlan>& ops);
+  void commit(conan_streams* s, hipStream_t dec, hipStream_t last_st);
+};
+}  // namespace denoise
 
 // ---- output leveller (level_out.hip): the kernels' host side and the bodies of api.hip's entry points
 namespace olv {

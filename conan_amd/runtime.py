@@ -553,6 +553,49 @@ class Context:
                                               flags.shape[1], _stream()))
         return buf.view(SAMPLE_DTYPES[fmt])[:, :N].reshape(*lead, N)
 
+    def mel_denoise(self, mel, lens=None, cfg=None, seed=None, out=None, state=False, **kw):
+        """conan_mel_denoise: the noise suppressor's law (include/conan_hip.h, conan_denoise_cfg) on whole log-mel rows, one launch.
+        mel [n, T, num_mels] (or [T, num_mels]) float32; a 3-D view whose rows are contiguous keeps its row stride.  lens: per row
+        the frames to take (default T; the frames behind them come back as they came).  cfg: an _lib.DenoiseCfg, or **kw:
+        _lib.denoise_cfg's keywords (natural_log, mel_vmin and eps are the mel's own).  seed: uint8 [n, bytes] (cuda) rows of conan_denoise_state the rows start from (mel_denoise(state=True)
+        or Streams.denoise_state); None: every row starts before its first frame.  out: a tensor of mel's shape and strides (out=mel:
+        in place).  -> the suppressed mel, and with state=True also the rows' states uint8 [n, bytes] (_lib.DenoiseState reads one).
+        It is what a wav-in slot with Streams.set_denoise computes on its frames, bit for bit, and what a caller with mel-in slots
+        streams through seed and state."""
+        dev = torch.device("cuda", self.device)
+        c = cfg if cfg is not None else _lib.denoise_cfg(**kw)
+        x = mel.to(dev, torch.float32)
+        if x.dim() == 2:
+            x = x[None]
+        if x.dim() != 3:
+            raise ValueError(f"mel_denoise: mel must be [n, T, num_mels] or [T, num_mels], got {tuple(mel.shape)}")
+        n, T, nm = x.shape
+        if not (x.stride(2) == 1 and x.stride(1) == nm and x.stride(0) >= T * nm) and n * T * nm:
+            x = x.contiguous()
+        ld = x.stride(0) if n > 1 else max(T * nm, 1)
+        if out is None:
+            y = torch.empty_strided(x.shape, (ld, nm, 1), dtype=torch.float32, device=dev) if n > 1 else torch.empty_like(x)
+            if lens is not None:
+                y.copy_(x)      # (the frames past a row's length come back as they came)
+        else:
+            y = out if out.dim() == 3 else out[None]
+            if y.shape != x.shape or y.dtype != torch.float32 or y.device != dev or (n * T * nm and (y.stride(2) != 1 or y.stride(1) != nm or (n > 1 and y.stride(0) != ld))):
+                raise ValueError("mel_denoise: out must be a float32 tensor of mel's shape and strides on the device")
+        fr = np.full(n, T, dtype=np.int32) if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.int32).reshape(n))
+        if fr.min(initial=0) < 0 or fr.max(initial=0) > T:
+            raise ValueError(f"mel_denoise: lens must be in 0 .. {T}")
+        size = C.sizeof(_lib.DenoiseState)
+        if seed is not None and (seed.dtype != torch.uint8 or not seed.is_cuda or tuple(seed.shape) != (n, size) or not seed.is_contiguous()):
+            raise ValueError(f"mel_denoise: seed must be a contiguous cuda uint8 [{n}, {size}] tensor, as state=True returns it")
+        st = torch.empty(n, size, dtype=torch.uint8, device=dev) if state else None
+        if n * T * nm == 0 and state:      # (no frame anywhere: the states are the seeds, or the record before the first frame)
+            st = seed.clone() if seed is not None else torch.zeros_like(st)
+        if n * T * nm:
+            _lib.check(self.lib.conan_mel_denoise(self.h, C.byref(c), _ptr(x), n, fr.ctypes.data_as(C.c_void_p), ld, nm, _ptr(seed), _ptr(y), _ptr(st),
+                                                  _stream()))
+        y = out if out is not None else (y[0] if mel.dim() == 2 else y)
+        return (y, st) if state else y
+
     def streams(self, max_slots, max_frames=4, max_ref_frames=256, arith="auto", flags=0, dev_plan=None):
         """A stream-set.  arith: 'auto' (library default), 'f32' (f32-input MFMA everywhere) or 'limb' (fp32 products of the
         vocoder's matrix kernels as bf16 limb products) - conan_streams_opts.arith; flags: _lib.STREAMS_*; dev_plan: developer /
@@ -706,7 +749,7 @@ class VoiceBank:
         for i in a:
             self.registers.pop(int(i), None)      # (the id holds another voice now; enroll_wav(register=True) measures it)
 
-    def enroll_wav(self, ids, wav, via=None, sample_rate=None, loud_norm=False, register=False, trim=False, **mel):
+    def enroll_wav(self, ids, wav, via=None, sample_rate=None, loud_norm=False, register=False, trim=False, denoise=False, **mel):
         """Context.wav2mel of wav [n, samples] - resampled from sample_rate to the mel front-end's rate, loudness-normalised and
         trimmed first where asked - then enroll.  **mel: wav2mel's keywords.  trim: True, or a dict of Context.trim_silence's
         keywords: the long pauses of each clip are cut out (behind resampling and loud_norm) so that they neither dilute the style
@@ -714,7 +757,9 @@ class VoiceBank:
         is that of enroll(ids, wav2mel(trimmed rows), ref_len) bit for bit.  The front-end's rate must be 50 * hop_size, and a clip
         without any activity is an error.  register=True also measures each voice's register
         (Context.register_of of the same prepared wav, which must then be at the model rate) into the host dict self.registers[id] -
-        what register="voice" of the engine's wav-in calls looks up; export / import_voices do not carry it."""
+        what register="voice" of the engine's wav-in calls looks up; export / import_voices do not carry it.  denoise: True, or a
+        dict of _lib.denoise_cfg's keywords: the noise suppressor (Context.mel_denoise, with the mel's own log base, vmin and eps)
+        runs on each clip's mel, over its own frames, in front of enroll."""
         rate = int(mel.get("sample_rate", 16000))
         wav = wav.to(self.dev, torch.float32)
         if wav.dim() == 1:
@@ -732,7 +777,11 @@ class VoiceBank:
             if int(kept.min()) < 1:
                 raise ValueError("enroll_wav(trim=): a clip has no activity, nothing is left of it")
             ref_len = [1 + int(k) // hop for k in kept]
-        self.enroll(ids, self.ctx.wav2mel(wav, **mel), ref_len, via=via)
+        ref_mel = self.ctx.wav2mel(wav, **mel)
+        if denoise:
+            own = dict(natural_log=bool(mel.get("natural_log", False)), mel_vmin=mel.get("mel_vmin", -6.0), eps=mel.get("eps", 1e-6))
+            ref_mel = self.ctx.mel_denoise(ref_mel, lens=ref_len, out=ref_mel, **dict(own, **({} if denoise is True else dict(denoise))))
+        self.enroll(ids, ref_mel, ref_len, via=via)
         if register:
             for i, r in zip(ids, self.ctx.register_of(wav, hop_size=mel.get("hop_size"))):
                 self.registers[int(i)] = r
@@ -1202,6 +1251,29 @@ class Streams:
         """conan_streams_conceal_state: uint8 [n, bytes] (cuda), the slots' concealment states for set_conceal(seed=).  Joins pipelined
         work."""
         return self._feature_seed_rows("conceal", slots)
+
+    def set_denoise(self, slots, cfg=True, seed=None, **kw):
+        """conan_streams_set_denoise: noise suppression on the slots' wav-in frames (include/conan_hip.h, conan_denoise_cfg): a causal
+        spectral gate on the log-mel frames the front-end has just computed, under a per-band noise floor tracked per frame, in place
+        in the slot's mel ring and in the chunk the step consumes.  No latency, no second spectral pipeline; the audio ring, and with
+        it the f0 tracker, the detector, the dry path and the leveller, is untouched.  **kw / a dict in cfg: _lib.denoise_cfg's
+        keywords; cfg may also be an _lib.DenoiseCfg; only cfg=None turns it off.  The defaults are choices, not measurements.
+        It may be called at any time (it joins pipelined work) and survives resets.  The state restarts at the slot's next frame
+        when a slot is enabled, after reseed=True and after a reset of the front-end - from its row of seed (uint8 [n, bytes] cuda
+        rows of denoise_state) where one is given; reseed=False on an enabled slot replaces the parameters and keeps the state.
+        Slot snapshots do not carry it: query denoise_state, export, import, then set_denoise(seed=rows, reseed=True)."""
+        self._set_feature("denoise", slots, cfg, kw, seed=seed)
+
+    def denoise(self, slots):
+        """conan_streams_denoise: per slot the setting as _lib.denoise_keywords reports it (set_denoise takes it back), None for a slot
+        without the feature."""
+        return self._get_feature("denoise", slots)
+
+    def denoise_state(self, slots):
+        """conan_streams_denoise_state: uint8 [n, bytes] (cuda), the slots' conan_denoise_state records (_lib.DenoiseState reads one:
+        frames, bins, the noise floor and the attenuation per bin) for set_denoise(seed=) and Context.mel_denoise(seed=).  Joins
+        pipelined work."""
+        return self._feature_seed_rows("denoise", slots)
 
     def set_output_format(self, slots, fmt):
         """conan_streams_set_output_format: the slots' audio leaves every step (and flush_output) as 'f32', 's16', 'ulaw' or 'alaw',

@@ -1390,6 +1390,95 @@ int conan_voices_import(conan_voices* v, const int32_t* ids, int n, const void* 
 /* Host only, no handle: what a caller may read out of a record (enrolled = 1).  CONAN_ERR_INVALID for what is not one. */
 int conan_voice_meta_info(const conan_voice_meta* meta, conan_voice_info* out);
 
+/* Input noise suppression (added within ABI 9: a caller detects it by the symbol conan_streams_set_denoise; no existing struct or call
+ * changes).  A causal spectral gate on the log-mel frames of a wav-in slot: the model only ever sees those frames, so the suppressor
+ * keeps no STFT of its own, no phase, no overlap-add and no look-ahead.  It rewrites the frames conan_step_wav's front-end has just
+ * written into the slot's mel ring, in place, and the chunk the step consumes; the audio ring - and with it the f0 tracker, the
+ * activity detector, the dry path and the leveller - and the decoder's mel_out and the vocoder are untouched.
+ * The law (tests/denoise_ref.py restates it in numpy with int64).  Levels are integers in Q10 of the mel's log unit: 1024 steps per
+ * unit, that is 20 dB per unit for log10 and 8.686 dB per unit for natural_log (conan_amd._lib.denoise_cfg converts once; no libm
+ * function is part of the law).  A row has nm = num_mels bins, 1 .. 256, and its frames are taken in order.  State per bin b: the
+ * noise floor N[b] and the attenuation A[b]; per row the count `frames`.  For frame f with values v[b]:
+ *   Level.   L[b] = (int32) rint(fmin(fmax((double)v[b], -1024.0), 1024.0) * 1024.0), ties to even; through IEEE fmax a NaN reads as
+ *            -1024.
+ *   Start.   If this is the row's first frame since a restart and no seed was given: N[b] = max(L[b], floor_min), A[b] = 0, before
+ *            anything else.
+ *   SNR.     With the floor as it was before this frame: snr = L - (N + bias), d = max(knee - snr, 0),
+ *            a = min((d * slope) >> 8, depth), the product in int64.
+ *   Across bins (smooth = 1).  a2[b] = (a[max(b-1, 0)] + 2 a[b] + a[min(b+1, nm-1)] + 2) >> 2; otherwise a2 = a.
+ *   Across time.  A' = a2 > A ? min(A + close_step, a2) : max(A - open_step, a2).
+ *   Output.  A' == 0: y = v, the bin keeps its bits whatever they are.  Otherwise
+ *            y = fmaxf((float)((double)(L - A') * 0.0009765625), out_floor): one rounding.
+ *   Floor.   L < N: N' = N - ((N - L + (1 << fall_shift) - 1) >> fall_shift); otherwise N' = min(L, N + rise); then
+ *            N' = max(N', floor_min).
+ *   frames += 1.
+ * Every operation is an integer one or a single correctly rounded IEEE operation, so the streamed form, the whole-signal form and
+ * the numpy reference agree bit for bit however the frames are cut into calls.
+ * Defaults (conan_amd._lib.denoise_cfg): bias 3 dB, knee 6 dB, slope 512 (2 dB of attenuation per dB under the knee), depth 18 dB,
+ * close 4.5 dB per frame, open = depth (a bin opens within the frame that needs it), rise 0.05 dB per frame, fall_shift 1, floor_min
+ * -100 dB, smooth 1, out_floor = max(mel vmin, log(eps)) in f32.  They are choices, not measurements: this repository holds synthetic
+ * weights and no speech corpus, so whether they improve real conversions cannot be measured with what it holds. */
+typedef struct conan_denoise_cfg {
+  int32_t enabled;     /* 0: off (other fields ignored) | 1 */
+  int32_t reseed;      /* 0 | 1: the state restarts (setter only) */
+  int32_t bias;        /* 0 .. 2^20: the floor is read this much higher */
+  int32_t knee;        /* 0 .. 2^20: SNR under which the gate begins to close */
+  int32_t slope;       /* Q8, 0 .. 2^16: attenuation per step under the knee */
+  int32_t depth;       /* 1 .. 2^20: the largest attenuation */
+  int32_t close_step;  /* 1 .. 2^20: per frame */
+  int32_t open_step;   /* 1 .. 2^20: per frame */
+  int32_t rise;        /* 0 .. 2^20: the floor's rise per frame */
+  int32_t fall_shift;  /* 0 .. 8: the floor falls by ceil((N - L) / 2^fall_shift) */
+  int32_t floor_min;   /* -2^20 .. 2^20 */
+  int32_t smooth;      /* 0 | 1: the 1-2-1 average across bins */
+  float out_floor;     /* finite: the smallest value an attenuated bin takes */
+  int32_t reserved[3]; /* must be 0 */
+} conan_denoise_cfg; /* 64 bytes */
+/* Published, so a host can read the noise spectrum.  A record whose `bins` is not the row's num_mels (the zero record among them) is
+ * the state before the first frame: the next frame applies Start.  Entries past `bins` are 0.  A seed is a record this library wrote
+ * (the zero record among them): of any other, floor[] is read clamped to -2^20 .. 2^20 and att[] to 0 .. 2^20, the ranges the law
+ * keeps them in, and `frames` counts modulo 2^64. */
+typedef struct conan_denoise_state {
+  int64_t frames;
+  int32_t bins, reserved;
+  int32_t floor[256], att[256];
+} conan_denoise_state; /* 2064 bytes */
+/* The law on whole rows, and the bit-exact yardstick of the streaming form: row i (n rows in 1 .. 65535) holds frames[i] (host,
+ * >= 0) frames of num_mels (1 .. 256) floats at mel_dev + i * ld floats (ld >= frames[i] * num_mels); out_dev has the same shape and
+ * may equal mel_dev; an out_dev that overlaps mel_dev in any other way is undefined (rows of one buffer cannot overlap: ld holds
+ * every row).  cfg->enabled must be 1; cfg->reseed is ignored.  seed_dev (may be null): conan_denoise_state[n], the state row i
+ * starts from; without it every row starts before its first frame.  state_out_dev (may be null): conan_denoise_state[n], the state
+ * behind each row's last frame; it may equal seed_dev, and any other overlap of the two is undefined.  ONE launch
+ * (cnk::denoise_signal_kernel, one workgroup per row) on `stream`; the row table goes through the context's workspace, which
+ * conan_wav2mel, conan_loud_norm and conan_activity share: calls on one context are ordered by the caller.  A caller with mel-in
+ * slots streams this call through seed and state. */
+int conan_mel_denoise(conan_ctx* ctx, const conan_denoise_cfg* cfg, const float* mel_dev, int n, const int32_t* frames, int64_t ld, int num_mels,
+                      const conan_denoise_state* seed_dev, float* out_dev, conan_denoise_state* state_out_dev, void* stream);
+/* Sets (cfg->enabled = 1) or removes (0) the suppressor for `slots`.  Every argument is checked before anything changes
+ * (CONAN_ERR_INVALID: a field outside its range, a non-zero reserved word, a seed that is misaligned or whose rows are too close;
+ * CONAN_ERR_UNSUPPORTED: a front-end of more than 256 mel bins), a stream-set without the streaming front-end is CONAN_ERR_STATE, and
+ * pending pipelined work is joined; it may be called at any time, also mid-utterance, and the setting persists across resets.  The
+ * state restarts at the slot's next frame after a reset that includes CONAN_MODEL_FRONTEND, after a setter call with reseed = 1 and
+ * when a slot that was off is enabled; a setter call with reseed = 0 on an enabled slot changes the parameters from the next frame
+ * and keeps the state.  seed_dev (may be null): row i at seed_dev + i * seed_ld bytes is a conan_denoise_state, and is what the state
+ * of slots[i] restarts from (on `stream`) in a call that restarts it; in a call that keeps the state it is not read.
+ * Launches: one more per wav-in call in which a suppressing slot completes a frame or emits (cnk::denoise_stream_kernel, directly
+ * behind the mel front-end's), none otherwise; conan_step_wav_chunk returns the suppressed chunk.
+ * Memory: the first enabling call allocates conan_denoise_state_bytes() per slot and 4 row tables; conan_streams_state_bytes counts
+ * them from then on.  A stream-set that never calls the setter allocates nothing and runs exactly the launches it ran before.
+ * Snapshots: the mel ring, which holds suppressed frames, travels as before; a snapshot carries neither the setting nor the state, and
+ * conan_streams_layout_id and conan_streams_snapshot_bytes do not change.  The hand-over: conan_streams_denoise_state, export, import,
+ * then this setter with the record as seed_dev and reseed = 1. */
+int conan_streams_set_denoise(conan_streams* s, const int32_t* slots, int n, const conan_denoise_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream);
+/* Host only: the suppressor's cfg of `slot` as set (zeros for a slot without one; reseed reads 0). */
+int conan_streams_denoise(const conan_streams* s, int slot, conan_denoise_cfg* cfg_out);
+/* sizeof(conan_denoise_state). */
+int64_t conan_denoise_state_bytes(void);
+/* The states of `slots` -> row i at rows_dev + i * ld bytes (8-byte aligned, ld a multiple of 8 and at least the record's bytes), on
+ * `stream` behind a join of pipelined work.  A slot about to restart reports the zero record; a slot without the feature is
+ * CONAN_ERR_STATE. */
+int conan_streams_denoise_state(conan_streams* s, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
