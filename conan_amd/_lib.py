@@ -155,6 +155,11 @@ _PROTOS = {
     "conan_conceal_state_bytes": (C.c_int64, []),
     "conan_denoise_state_bytes": (C.c_int64, []),
     "conan_mel_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_watermark_state_bytes": (C.c_int64, []),
+    "conan_watermark_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_watermark_detect": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p]),
+    "conan_watermark_decide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
     "conan_conceal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_trim_silence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
@@ -672,6 +677,52 @@ def denoise_keywords(c):
     return dict({name: int(getattr(c, name)) for name, _, _ in DENOISE_RANGES}, smooth=bool(c.smooth), out_floor=float(c.out_floor))
 
 
+class WatermarkCfg(C.Structure):
+    """conan_watermark_cfg (include/conan_hip.h)."""
+    _fields_ = [("enabled", C.c_int32), ("reseed", C.c_int32), ("key", C.c_uint64), ("id", C.c_int32), ("gain", C.c_float), ("floor", C.c_float),
+                ("reserved", C.c_int32 * 9)]
+
+
+class WatermarkState(C.Structure):
+    """conan_watermark_state (include/conan_hip.h): a row of Streams.watermark_state / Context.watermark_embed(state=True)."""
+    _fields_ = [("pos", C.c_int64), ("env", C.c_float), ("reserved", C.c_int32)]
+
+
+class WatermarkHit(C.Structure):
+    """conan_watermark_hit (include/conan_hip.h): the detector's record of a row."""
+    _fields_ = [("offset", C.c_int32), ("blocks", C.c_int32), ("peak", C.c_int64)]
+
+
+class WatermarkResult(C.Structure):
+    """conan_watermark_result (include/conan_hip.h): conan_watermark_decide's answer."""
+    _fields_ = [("present", C.c_int32), ("id", C.c_int32), ("offset", C.c_int32), ("rotation", C.c_int32), ("blocks", C.c_int32), ("reserved", C.c_int32),
+                ("marker_score", C.c_int64), ("z", C.c_double)]
+
+
+WATERMARK_BLOCK = 2048
+WATERMARK_THRESHOLD = 11.5      # CONAN_WATERMARK_THRESHOLD
+
+
+def watermark_cfg(key=0, id=0, gain=0.1, floor=0.0, reseed=False):
+    """An enabled conan_watermark_cfg.  key: the 64-bit key of the chip sequence; id: the 16 bits the mark carries; gain: the mark's
+    amplitude under the causal peak envelope (0.1: -20 dB); floor: its smallest amplitude (0: digital silence stays digital silence).
+    The defaults are choices, not measurements.  A field outside its range is a ValueError."""
+    if not 0 <= int(key) < 1 << 64:
+        raise ValueError(f"watermark: key = {key!r} is outside 0 .. 2^64 - 1")
+    if not 0 <= int(id) <= 65535:
+        raise ValueError(f"watermark: id = {id!r} is outside 0 .. 65535")
+    for name, v in (("gain", gain), ("floor", floor)):
+        if not (math.isfinite(float(v)) and 0.0 <= float(v) <= 1.0):
+            raise ValueError(f"watermark: {name} = {v!r} is outside 0 .. 1")
+    return WatermarkCfg(1, int(bool(reseed)), int(key), int(id), float(gain), float(floor), (C.c_int32 * 9)())
+
+
+def watermark_keywords(c):
+    """watermark_cfg's keywords of an enabled WatermarkCfg, which give the same fields back exactly: the form Streams.watermark
+    reports a setting in."""
+    return dict(key=int(c.key), id=int(c.id), gain=float(c.gain), floor=float(c.floor))
+
+
 class SlotFeature(typing.NamedTuple):
     """One per-slot feature of a stream-set, as Streams and the engine read it.  A symbol the library does not have is None."""
     keyword: str                  # the engine's keyword (start_wav, open_slots, ...)
@@ -722,6 +773,8 @@ SLOT_FEATURES = {f.keyword: f for f in (
     SlotFeature("out_level", "the leveller", LevelCfg, "enabled", level_cfg, level_keywords, "conan_streams_set_output_level",
                 "conan_streams_output_level_cfg", "conan_streams_output_level", ("float64", 4), "conan_streams_output_level_state",
                 "conan_streams_output_level_state_bytes", release=False, mirror="output_levels"),
+    SlotFeature("watermark", "the watermark", WatermarkCfg, "enabled", watermark_cfg, watermark_keywords, "conan_streams_set_watermark",
+                "conan_streams_watermark", seed_state="conan_streams_watermark_state", seed_bytes="conan_watermark_state_bytes"),
 )}
 
 for _f in SLOT_FEATURES.values():      # the three regular families of _PROTOS: a symbol's shape is stated once, in SlotFeature

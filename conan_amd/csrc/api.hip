@@ -333,6 +333,7 @@ int conan_streams_reset(conan_streams* s, const int32_t* slots, int n, int which
       for (int i = 0; i < n; ++i) s->voc_fresh[slots[i]] = 1;
       // the output rate stays; the output resampler restarts (output index 0, inputs before the first are zero: the ring needs no clearing)
       for (int i = 0; i < n; ++i) s->wav_out.voc_samples[slots[i]] = 0;
+      s->wm.restart(slots, n);      // the watermark's setting stays; its state restarts in the slots' next step rows
       if (!s->wav_out.or_slot.empty())
         for (int i = 0; i < n; ++i) { conan_streams::OrSlot& o = s->wav_out.or_slot[slots[i]]; o.out = 0; o.flushed = 0; }
     }
@@ -987,6 +988,41 @@ int conan_profile_mark(conan_streams* s, void* stream) {
     HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
     cnk::launch_profile_mark((hipStream_t)stream);
   });
+}
+
+// ---- output watermark (watermark.hip): conan_watermark_embed, conan_watermark_detect, conan_watermark_decide,
+// conan_streams_set_watermark, conan_streams_watermark, conan_watermark_state_bytes, conan_streams_watermark_state
+int conan_watermark_embed(conan_ctx* ctx, const conan_watermark_cfg* cfg, const float* x_dev, int n, const int64_t* samples, int64_t ld,
+                          const conan_watermark_state* seed_dev, float* out_dev, conan_watermark_state* state_out_dev, void* stream) {
+  return guarded([&] { wmark::embed(ctx, cfg, x_dev, n, samples, ld, seed_dev, out_dev, state_out_dev, stream); });
+}
+
+int conan_watermark_detect(conan_ctx* ctx, uint64_t key, int format, const void* x_dev, int64_t ld, int n, const int64_t* samples,
+                           int64_t* score_dev, int64_t* soft_dev, int64_t soft_ld, conan_watermark_hit* hit_dev, void* stream) {
+  return guarded([&] { wmark::detect(ctx, key, format, x_dev, ld, n, samples, score_dev, soft_dev, soft_ld, hit_dev, stream); });
+}
+
+int conan_watermark_decide(const int64_t* score, const int64_t* soft, const conan_watermark_hit* hit, double threshold, conan_watermark_result* out) {
+  try {      // (host only, and no launch to answer for: it also runs where no device is)
+    wmark::decide(score, soft, hit, threshold, out);
+    return CONAN_OK;
+  } catch (const ch::Error& e) {
+    g_err = e.what();
+    return e.code;
+  }
+}
+
+int conan_streams_set_watermark(conan_streams* s, const int32_t* slots, int n, const conan_watermark_cfg* cfg, const void* seed_dev, int64_t seed_ld,
+                                void* stream) {
+  return guarded([&] { wmark::set_watermark(s, slots, n, cfg, seed_dev, seed_ld, stream); });
+}
+
+int conan_streams_watermark(const conan_streams* s, int slot, conan_watermark_cfg* cfg_out) { return guarded([&] { wavio::get_setting(s, &conan_streams::wm, slot, cfg_out, nullptr); }); }
+
+int64_t conan_watermark_state_bytes(void) { return (int64_t)sizeof(cnk::WmState); }
+
+int conan_streams_watermark_state(conan_streams* s, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream) {
+  return guarded([&] { wmark::state(s, slots, n, rows_dev, ld, stream); });
 }
 
 int conan_hop_size(const conan_ctx* ctx) { return ctx ? ctx->hop : 0; }

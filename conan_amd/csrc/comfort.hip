@@ -7,6 +7,7 @@
 #include <cmath>
 
 #include "streams.h"
+#include "hash_dev.h"
 
 namespace cnk {
 
@@ -38,11 +39,9 @@ __global__ __launch_bounds__(kCmfTrackThreads) void comfort_track_kernel(const C
   if (r.state_row >= 0) a.state_out[r.state_row] = s;
 }
 
-// the law's white source: the finaliser of splitmix64 on seed + (j + 1) * golden, folded to a triangular value
+// the law's white source: the finaliser of splitmix64 on seed + (j + 1) * golden (hash_dev.h), folded to a triangular value
 __device__ __forceinline__ int comfort_white(unsigned long long z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
+  z = hash64_mix(z);
   return (int)(z & 0xFFFFu) + (int)((z >> 16) & 0xFFFFu) - 65535;
 }
 
@@ -106,12 +105,12 @@ __global__ __launch_bounds__(kCmfFillThreads) void comfort_fill_kernel(const Cmf
   if (any) {
     // w(j) for j = j0 - 4 .. j0 + PER - 1, of which a colour reads the last PER + 2 * colour
     const int first = 4 - 2 * r.colour;
-    unsigned long long z = r.seed + (unsigned long long)(r.pos0 + s0 - 4 + first + 1) * 0x9E3779B97F4A7C15ull;
+    unsigned long long z = r.seed + (unsigned long long)(r.pos0 + s0 - 4 + first + 1) * kHashGolden;
     int w[PER + 4];
 #pragma unroll
     for (int t = 0; t < PER + 4; ++t) {
       w[t] = 0;
-      if (t >= first) { w[t] = comfort_white(z); z += 0x9E3779B97F4A7C15ull; }      // (uniform in the workgroup)
+      if (t >= first) { w[t] = comfort_white(z); z += kHashGolden; }      // (uniform in the workgroup)
     }
     const int c1 = r.colour >= 1 ? 2 : 0, c2 = r.colour == 2 ? 3 : (r.colour == 1 ? 1 : 0), c3 = r.colour == 2 ? 2 : 0, c4 = r.colour == 2 ? 1 : 0;
 #pragma unroll

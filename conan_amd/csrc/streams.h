@@ -374,6 +374,17 @@ struct conan_streams {
     cnk::LvFilter filter;
   } out_lv;
   void out_level_init(const cnk::LvFilter& f);
+  // output watermark (conan_streams_set_watermark; watermark.hip), a SlotSetting as the others.  state: [max_slots] records of
+  // conan_watermark_state, read and written by the rows of watermark_embed_kernel in the order of the vocoder steps; pending restarts
+  // it from zeros in the slot's next step row (set when a slot that was off is enabled, by reseed = 1 without a seed and by a reset
+  // with CONAN_MODEL_HIFIGAN; a seed row becomes the state at once and clears the flag).  Per vocoder step with a marked row a row
+  // table (set q of `sets`: one row per step row, on = 0 for a slot without the feature); the set's event is recorded behind the
+  // embed launch.  Allocated by the first enabling call; state and row tables count as stream state.
+  struct Watermark : SlotSetting<conan_watermark_cfg> {
+    cnk::WmState* state = nullptr;
+    StageSets<cnk::WmRow, kActSets> sets;
+  } wm;
+  void watermark_init();
   void out_stage_init();
   void out_ring_init();        // the output resampler's history ring (conan_streams_set_output_rate with a real rate)
   // --- slot snapshots (snapshot.hip).  rings: every ring of mk_ring in creation order with its position counter (0 pos_emf,
@@ -417,6 +428,9 @@ struct conan_streams {
     // the step's output levelling (level_out.hip; out_plan's, for a step with a levelled row): one table row per step row;
     // hifigan_step launches level_out_apply_kernel behind conv_post and level_out_meter_kernel behind the step's last launch
     std::vector<cnk::OlRow> lvl_rows;
+    // the step's watermark (watermark.hip; out_plan's, for a step with a marked row): one table row per step row; hifigan_step
+    // launches watermark_embed_kernel behind the fill and in front of the output resampler
+    std::vector<cnk::WmRow> wm_rows;
   };
   OutPlan out_plan(const int32_t* slots, int n, int frames, float* wav_out_dev, long long natural_ld, const std::vector<int>* dst, const std::string& who) const;
   // the plan's resample_out_kernel launch behind or_sets.begin() = q, then the set's event; src_ld: stride of the staged rows (a flush: 0)
@@ -951,6 +965,21 @@ void stats(conan_streams* s, const int32_t* slots, int n, double* stats_dev, voi
 int64_t state_bytes(const conan_streams* s);
 void state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream);
 }  // namespace olv
+
+// ---- output watermark (watermark.hip): the kernels' host side and the bodies of api.hip's entry points
+namespace wmark {
+void check_cfg(const conan_watermark_cfg& c, const char* who);      // host only
+cnk::WmRow row(const conan_watermark_cfg& c);      // the cfg's fields of a row that starts from {0, 0} and names no slot
+// the table rows of a vocoder step that gives each of `slots` `frames` frames (empty: no marked slot among them).  Nothing changes.
+std::vector<cnk::WmRow> step_rows(const conan_streams* s, const int32_t* slots, int n, int frames, const std::string& who);
+void embed(conan_ctx* ctx, const conan_watermark_cfg* cfg, const float* x_dev, int n, const int64_t* samples, int64_t ld, const conan_watermark_state* seed_dev,
+           float* out_dev, conan_watermark_state* state_out_dev, void* stream);
+void detect(conan_ctx* ctx, uint64_t key, int format, const void* x_dev, int64_t ld, int n, const int64_t* samples, int64_t* score_dev, int64_t* soft_dev,
+            int64_t soft_ld, conan_watermark_hit* hit_dev, void* stream);
+void decide(const int64_t* score, const int64_t* soft, const conan_watermark_hit* hit, double threshold, conan_watermark_result* out);      // host only
+void set_watermark(conan_streams* s, const int32_t* slots, int n, const conan_watermark_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream);
+void state(conan_streams* s, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream);
+}  // namespace wmark
 
 // ---- silence trimming (trim.hip): the kernels' host side and the body of api.hip's entry point
 namespace trim {

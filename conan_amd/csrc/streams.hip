@@ -647,6 +647,14 @@ void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float*
       f.ld = T; f.ld_y = T; f.lvl_ld = op->fill.lvl_ld; f.samples = T; f.n = n; f.hop = ctx->hop; f.start_in_lvl = 1;
       profiled("comfort_fill_kernel", 0.0, st, [&] { cnk::launch_comfort_fill(f, st); });
     }
+    if (op && !op->wm_rows.empty()) {      // the watermark (watermark.hip), behind the last in-place stage, in front of the resampler and the encoders
+      const int wq = wm.sets.begin(op->wm_rows.data(), n, st);
+      cnk::WmEmbedArgs w; memset(&w, 0, sizeof(w));
+      w.x = a.wav; w.y = a.wav; w.ld = T; w.ld_y = T; w.state = wm.state; w.tab = wm.sets.rows[wq]; w.n = n;
+      profiled("watermark_embed_kernel", 0.0, st, [&] { cnk::launch_watermark_embed(w, st); });
+      wm.sets.end(wq, st);
+      for (const cnk::WmRow& r : op->wm_rows) if (r.on) wm.pending[r.slot] = 0;      // (the rows carried the restarts)
+    }
     if (out_rows) resample_out(*op, oq, T, st);
     if (levelled) {      // ... and its meter, off the audio's path: the staged samples into the slots' state, for the next step's ramp
       cnk::LevelOutMeterArgs l; memset(&l, 0, sizeof(l));

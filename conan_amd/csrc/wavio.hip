@@ -609,6 +609,7 @@ conan_streams::OutPlan conan_streams::out_plan(const int32_t* slots, int n, int 
     any = any || (!wav_out.or_slot.empty() && wav_out.or_slot[slots[i]].f) || wav_out.out_fmt[slots[i]];      // (a format alone sends the step through the copy rows)
   }
   if (!flush) P.lvl_rows = olv::step_rows(this, slots, n, frames, who);      // (checked here, before anything changes: CONAN_ERR_UNSUPPORTED rows)
+  if (!flush) P.wm_rows = wmark::step_rows(this, slots, n, frames, who);
   P.active = any || dst || P.ld != T;
   if (flush) P.active = false;
   if (!P.active && !flush) return P;

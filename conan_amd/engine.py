@@ -212,7 +212,7 @@ def _by_value(slots, values):
 
 
 # what True means to a feature's Streams setter, by engine keyword (register= has no True: a scalar is its target)
-_TRUE = dict(level=True, pitch=True, follow=True, out_level=True, activity=dict(gate=True), bypass={}, conceal={}, denoise={}, comfort={})
+_TRUE = dict(level=True, pitch=True, follow=True, out_level=True, activity=dict(gate=True), bypass={}, conceal={}, denoise={}, comfort={}, watermark={})
 
 
 def _accept(keyword, v, k, n, voice):
@@ -291,7 +291,7 @@ class StreamingVoiceConversionEngine:
             raise ValueError("set_voice: bank= and ids= are required")
         self.st.set_voice(self.slots if slots is None else slots, bank, ids)
 
-    def start(self, ref_mel, ref_len=None, which=7, out_rate=None, out_filter=None, out_format=None, pitch=None, voice=None, out_level=None):
+    def start(self, ref_mel, ref_len=None, which=7, out_rate=None, out_filter=None, out_format=None, pitch=None, voice=None, out_level=None, watermark=None):
         """voice: (bank, ids) - enrolled voices of a runtime.VoiceBank, one id per slot, in place of ref_mel (then None).
         pitch: the slots' pitch control in the decoder step (Streams.set_pitch) - None / False: none; a dict of its keywords
         (shift_semitones, range, pivot, uv_threshold), or a list with one per slot.
@@ -300,27 +300,31 @@ class StreamingVoiceConversionEngine:
         out_format: the sample format the audio leaves in ('f32' | 's16' | 'ulaw' | 'alaw'; None: float32), encoded on the GPU.
         out_level: the output leveller (Streams.set_output_level) - None / False: none; True: Context.level's defaults; a dict: its
         keywords.  The same causal BS.1770 leveller as start_wav(level=...), on the converted voice: on the GPU between the vocoder
-        and the gate, the mix, the output resampler and the encoders, without look-ahead or added latency."""
+        and the gate, the mix, the output resampler and the encoders, without look-ahead or added latency.
+        watermark: the output watermark (Streams.set_watermark) - None / False: none; a dict of its keywords (key, id, gain, floor),
+        or a list with one per slot; True: the defaults, key 0 and id 0.  The mark goes into the audio on the GPU behind the last
+        in-place stage, in front of the output resampler and the encoders: the returned model-rate wav is ctx.watermark_embed of the
+        unmarked one, bit for bit, and Context.watermark_detect finds it again."""
         if isinstance(out_level, (list, tuple)):
             raise ValueError("out_level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
         if isinstance(out_rate, (list, tuple)) or isinstance(out_format, (list, tuple)):
             raise ValueError("out_rate / out_format: one value for all slots here (feed / infer return one [B, count] block); open_slots and "
                              "infer_wav_staggered take one per slot / utterance")
         self._check_voice(ref_mel, voice)
-        values = self._host_checks(len(self.slots), pitch=pitch, out_level=out_level)
+        values = self._host_checks(len(self.slots), pitch=pitch, out_level=out_level, watermark=watermark)
         self.st.reset(self.slots, which=which)
         self._reference(self.slots, ref_mel, ref_len, voice)
         self._set_out_rate(self.slots, out_rate, out_filter)
         self._set_format(self.slots, out_format, self.st.output_formats, self.st.set_output_format)
-        for keyword in values:      # (pitch, out_level)
+        for keyword in values:      # (pitch, out_level, watermark)
             self._apply(keyword, self.slots, values[keyword])
 
     def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, denoise=None, **filter):
+                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, denoise=None, watermark=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
         in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
         in_format: the input's sample format (None: float32; 's16' takes int16 rows, 'ulaw' / 'alaw' uint8), decoded on the GPU.
-        out_rate / out_filter / out_format / out_level: as in start().
+        out_rate / out_filter / out_format / out_level / watermark: as in start().
         level: the input leveller (Streams.set_input_level) - None / False: none; True: Context.level's defaults; a dict: its
         keywords.  It runs on the GPU on the decoded, resampled samples in front of the front-end, causally: feed() gains no latency.
         pitch, voice: as in start().
@@ -350,7 +354,7 @@ class StreamingVoiceConversionEngine:
         values = self._host_checks(len(self.slots), voice, level=level, follow=follow, register=register, activity=activity, bypass=bypass,
                                    conceal=conceal, comfort=comfort, denoise=denoise)
         self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice,
-                   out_level=out_level)
+                   out_level=out_level, watermark=watermark)
         self._set_rate(self.slots, in_rate, filter)
         self._set_format(self.slots, in_format, self.st.input_formats, self.st.set_input_format)
         for keyword in values:      # (pitch and out_level went in with start(), in front of the input rate)
@@ -481,6 +485,12 @@ class StreamingVoiceConversionEngine:
         """The slots' output leveller (all slots by default) between utterances, or mid-utterance with seed= (a hand-over):
         Streams.set_output_level's arguments (cfg=None turns it off).  Joins pipelined steps in flight."""
         self._live("out_level", slots, cfg, seed=seed, **kw)
+
+    def set_watermark(self, slots=None, cfg=True, seed=None, **kw):
+        """A live change of the slots' output watermark (all slots by default) between calls, also mid-utterance and with pipelined
+        steps in flight: Streams.set_watermark's arguments (cfg=None turns it off; without reseed=True an enabled slot keeps its
+        position and envelope; seed= is a hand-over).  In force from the next vocoder step."""
+        self._live("watermark", slots, cfg, seed=seed, **kw)
 
     def set_pitch(self, slots=None, **kw):
         """A live change of the slots' pitch control (all slots by default) between feed / feed_ragged calls, also mid-utterance and
@@ -625,7 +635,7 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
                   out_format=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None, register=None, activity=None,
-                  activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, comfort=None, denoise=None, **filter):
+                  activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, comfort=None, denoise=None, watermark=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] (or None with voice = (bank, ids): start) -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
@@ -652,10 +662,11 @@ class StreamingVoiceConversionEngine:
         conceal + lost: loss concealment (start_wav) with lost [B, packets], the flags of the whole utterance: the results are those
         of infer_wav(ctx.conceal(src_wav, lost, cfg, in_format), ...) bit for bit.  Not with loud_norm or trim, which hold the
         utterance whole: repair it whole first (Context.conceal).  denoise: the noise suppressor (start_wav): the results are those of
-        infer(ctx.mel_denoise(ctx.wav2mel(x)), ...) bit for bit, x = the samples the front-end reads."""
+        infer(ctx.mel_denoise(ctx.wav2mel(x)), ...) bit for bit, x = the samples the front-end reads.  watermark: the output watermark
+        (start): the returned model-rate wav is ctx.watermark_embed of the unmarked one, bit for bit."""
         self._check_voice(ref_mel, voice)
         self._host_checks(len(self.slots), voice, level=level, pitch=pitch, follow=follow, register=register, activity=activity, bypass=bypass,
-                          conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level)      # (before anything runs)
+                          conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark)      # (before anything runs)
         self._check_lost(lost, conceal, loud_norm, trim)
         trim = self._trim_keywords(trim)
         if trim is not None:
@@ -664,7 +675,7 @@ class StreamingVoiceConversionEngine:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
                        pitch=pitch, voice=voice, follow=follow, register=register, activity=activity, bypass=bypass, out_level=out_level, conceal=conceal,
-                       comfort=comfort, denoise=denoise, **filter)
+                       comfort=comfort, denoise=denoise, watermark=watermark, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -696,7 +707,7 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, denoise=None, **filter):
+                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, denoise=None, watermark=None, **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
         rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
@@ -709,11 +720,12 @@ class StreamingVoiceConversionEngine:
         slots' wet/dry mix (start_wav), one value or a list with one per slot.  out_level: the slots' output leveller (start), one
         value or a list with one per slot.  conceal: the slots' loss concealment (start_wav), one value or a list with one per slot.
         denoise: the slots' noise suppression (start_wav), one value or a list with one per slot.
+        watermark: the slots' output watermark (start), one value or a list with one per slot.
         No trim=, as in start_wav: the slots stream, and a stream cannot drop time (infer_wav_staggered(trim=True) trims utterances
         it holds whole)."""
         self._check_voice(ref_mel, voice)
         values = self._host_checks(len(slots), voice, level=level, pitch=pitch, follow=follow, register=register, activity=activity, bypass=bypass,
-                                   conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level)
+                                   conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark)
         self.st.reset(slots, which=7 | 8)
         self._reference(slots, ref_mel, ref_len, voice)
         self._set_out_rate(slots, out_rate, out_filter)
@@ -721,7 +733,7 @@ class StreamingVoiceConversionEngine:
         self._set_format(slots, out_format, self.st.output_formats, self.st.set_output_format)
         for r, group in _by_value(slots, _per_slot(in_rate, len(slots))):
             self._set_rate(group, r, filter)
-        for keyword in values:      # (the order of _lib.SLOT_FEATURES: pitch behind level, out_level last)
+        for keyword in values:      # (the order of _lib.SLOT_FEATURES: pitch behind level, out_level and watermark last)
             self._apply(keyword, slots, values[keyword], _per_slot(in_rate, len(slots)))
 
     @torch.no_grad()
@@ -745,7 +757,7 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
                             in_formats=None, out_formats=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None,
-                            register=None, activity=None, activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, comfort=None, denoise=None, **filter):
+                            register=None, activity=None, activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, comfort=None, denoise=None, watermark=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -768,12 +780,13 @@ class StreamingVoiceConversionEngine:
         utterance or a list with one per utterance.  out_level: the output leveller (start), one value for every utterance or a
         list with one per utterance.  conceal: loss concealment (start_wav), one value for every utterance or a list with one per
         utterance; lost: per utterance its whole flags (a 1-D tensor) or None.  Not with loud_norm or trim (Context.conceal repairs an
-        utterance whole).  denoise: the noise suppression (start_wav), one value for every utterance or a list with one per utterance."""
+        utterance whole).  denoise: the noise suppression (start_wav), one value for every utterance or a list with one per utterance.
+        watermark: the output watermark (start), one value for every utterance or a list with one per utterance."""
         voice = self._check_voice(ref_mel, voice)
         U = len(src_wavs)
         # (host checks before anything runs; per utterance, in the form open_slots takes back)
         values = self._host_checks(U, voice, ("out_level",), level=level, pitch=pitch, follow=follow, register=register, activity=activity,
-                                   bypass=bypass, conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level)
+                                   bypass=bypass, conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark)
         self._check_lost(lost, conceal, loud_norm, trim)
         if lost is not None and len(lost) != U:
             raise ValueError(f"lost: {len(lost)} values for {U} utterances")
@@ -888,7 +901,7 @@ class StreamingVoiceConversionEngine:
 
     @torch.no_grad()
     def infer(self, src_mel, ref_mel, ref_len=None, pipelined=True, out_rate=None, out_filter=None, out_format=None, pitch=None, voice=None,
-              out_level=None):
+              out_level=None, watermark=None):
         """src_mel [B,T,80], ref_mel [B,Tr,80] (cuda) -> wav [B, T*hop], mel [B,T,80], codes [B,T].
 
         The whole source is available here, so by default the chunks are issued as pipelined steps
@@ -896,9 +909,13 @@ class StreamingVoiceConversionEngine:
         results are bit-identical to the blocking loop (pipelined=False).  out_rate (+ out_filter): the returned wav is the
         whole utterance at that rate, ctx.resample of the model-rate wav bit for bit.  out_format: the returned wav's sample format.
         pitch: the slots' pitch control in the decoder step (start).  voice: (bank, ids) in place of ref_mel (then None; start).
-        out_level: the output leveller (start): the returned model-rate wav is ctx.level of the unlevelled one, bit for bit."""
+        out_level: the output leveller (start): the returned model-rate wav is ctx.level of the unlevelled one, bit for bit.
+        watermark: the output watermark (start): the returned model-rate wav is ctx.watermark_embed of the unmarked one, bit for bit."""
         self._check_voice(ref_mel, voice)
         if self.ctx.cfg.voc_upsample == 2:
+            if watermark not in (None, False):
+                raise ValueError("watermark with an upsample 'nn' vocoder: its steps are whole prefixes, not update intervals; mark the returned wav "
+                                 "with Context.watermark_embed instead")
             if out_level not in (None, False):
                 raise ValueError("out_level with an upsample 'nn' vocoder: its steps are whole prefixes, not update intervals; level the returned wav "
                                  "with Context.level instead")
@@ -906,7 +923,7 @@ class StreamingVoiceConversionEngine:
                 raise ValueError("out_format with an upsample 'nn' vocoder: convert the returned wav with Context.convert_samples instead")
             self._set_out_rate(self.slots, out_rate, out_filter)      # (refuses a rate; restores the model rate)
             return self._infer_prefix_vocoder(src_mel, ref_mel, ref_len, pitch, voice)
-        self.start(ref_mel, ref_len, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice, out_level=out_level)
+        self.start(ref_mel, ref_len, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice, out_level=out_level, watermark=watermark)
         B = src_mel.shape[0]
         hop, nm = self.ctx.hop, self.ctx.cfg.num_mels
         wavs, mels, codes = [], [], []

@@ -596,6 +596,96 @@ class Context:
         y = out if out is not None else (y[0] if mel.dim() == 2 else y)
         return (y, st) if state else y
 
+    def watermark_embed(self, x, lens=None, cfg=None, seed=None, out=None, state=False, **kw):
+        """conan_watermark_embed: the watermark's embedder (include/conan_hip.h, conan_watermark_cfg) on whole signals at 16 kHz, one
+        launch.  x [n, N] (or [N]) float32; a 2-D view whose rows are contiguous keeps its row stride.  lens: per row the samples to
+        mark (default N; the samples behind them come back as they came).  cfg: an _lib.WatermarkCfg, or **kw: _lib.watermark_cfg's
+        keywords (key, id, gain, floor).  seed: uint8 [n, 16] (cuda) rows of conan_watermark_state the rows start from
+        (watermark_embed(state=True) or Streams.watermark_state); None: every row starts at position 0.  out: a tensor of x's shape
+        and strides (out=x: in place).  -> the marked audio, and with state=True also the rows' states uint8 [n, 16]
+        (_lib.WatermarkState reads one).  It is what a slot with Streams.set_watermark adds to its vocoder audio, bit for bit."""
+        dev = torch.device("cuda", self.device)
+        c = cfg if cfg is not None else _lib.watermark_cfg(**kw)
+        v = x.to(dev, torch.float32)
+        if v.dim() == 1:
+            v = v[None]
+        if v.dim() != 2:
+            raise ValueError(f"watermark_embed: x must be [n, N] or [N], got {tuple(x.shape)}")
+        n, N = v.shape
+        if not (v.stride(1) == 1 and v.stride(0) >= N) and n * N:
+            v = v.contiguous()
+        ld = v.stride(0) if n > 1 else max(N, 1)
+        if out is None:
+            y = torch.empty_strided(v.shape, (ld, 1), dtype=torch.float32, device=dev) if n > 1 else torch.empty_like(v)
+            if lens is not None:
+                y.copy_(v)
+        else:
+            y = out if out.dim() == 2 else out[None]
+            if y.shape != v.shape or y.dtype != torch.float32 or y.device != dev or (n * N and (y.stride(1) != 1 or (n > 1 and y.stride(0) != ld))):
+                raise ValueError("watermark_embed: out must be a float32 tensor of x's shape and strides on the device")
+        sm = np.full(n, N, dtype=np.int64) if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.int64).reshape(n))
+        if sm.min(initial=0) < 0 or sm.max(initial=0) > N:
+            raise ValueError(f"watermark_embed: lens must be in 0 .. {N}")
+        size = C.sizeof(_lib.WatermarkState)
+        if seed is not None and (seed.dtype != torch.uint8 or not seed.is_cuda or tuple(seed.shape) != (n, size) or not seed.is_contiguous()):
+            raise ValueError(f"watermark_embed: seed must be a contiguous cuda uint8 [{n}, {size}] tensor, as state=True returns it")
+        st = torch.empty(n, size, dtype=torch.uint8, device=dev) if state else None
+        if n:
+            _lib.check(self.lib.conan_watermark_embed(self.h, C.byref(c), _ptr(v), n, sm.ctypes.data_as(C.c_void_p), ld, _ptr(seed), _ptr(y), _ptr(st),
+                                                      _stream()))
+        y = out if out is not None else (y[0] if x.dim() == 1 else y)
+        return (y, st) if state else y
+
+    def watermark_detect(self, x, key, format="f32", rate=16000, threshold=None, lens=None, raw=False):
+        """conan_watermark_detect and conan_watermark_decide: the watermark's detector on x [n, N] (or [N]) of `format` ('f32' float32,
+        's16' int16, 'ulaw' / 'alaw' uint8) at `rate` Hz; audio at another rate is decoded and brought to 16 kHz with the library's
+        own resampler first (the offset search absorbs the filter's delay).  key: the embedder's; threshold: None is the library's
+        default (_lib.WATERMARK_THRESHOLD); lens: per row the samples to read (default N).  -> one dict per row: present, z, id,
+        offset, rotation, marker_score, blocks; with raw=True also S (int64 [2048]), soft (int64 [blocks]) and peak, the detector's
+        integers.  Rows under two blocks (4096 samples) report present = 0, blocks = 0.  Synchronises."""
+        f = _lib.sample_format(format)
+        dev = torch.device("cuda", self.device)
+        v = x.to(dev)
+        if v.dtype != SAMPLE_DTYPES[format]:
+            raise ValueError(f"watermark_detect: format {format!r} takes {SAMPLE_DTYPES[format]} samples, got {v.dtype}")
+        if v.dim() == 1:
+            v = v[None]
+        if v.dim() != 2:
+            raise ValueError(f"watermark_detect: x must be [n, N] or [N], got {tuple(x.shape)}")
+        n, N = v.shape
+        sm = np.full(n, N, dtype=np.int64) if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.int64).reshape(n))
+        if sm.min(initial=0) < 0 or sm.max(initial=0) > N:
+            raise ValueError(f"watermark_detect: lens must be in 0 .. {N}")
+        if int(rate) != 16000:
+            if lens is not None:
+                raise ValueError("watermark_detect: lens needs rate=16000 (resample the rows one by one)")
+            v = self.resample(v if format == "f32" else self.convert_samples(v, format, "f32"), int(rate), 16000)
+            f, format, N = _lib.sample_format("f32"), "f32", v.shape[1]
+            sm = np.full(n, N, dtype=np.int64)
+        ld = max((N * _lib.SAMPLE_BYTES[format] + 3) // 4, 1)
+        buf = _row_bytes(v.reshape(n, N), n, ld, dev)
+        kmax = max(int(sm.max(initial=0)) // _lib.WATERMARK_BLOCK - 1, 0)
+        score = torch.empty(n, _lib.WATERMARK_BLOCK, dtype=torch.int64, device=dev)
+        soft = torch.empty(n, max(kmax, 1), dtype=torch.int64, device=dev)
+        hit = torch.empty(n, C.sizeof(_lib.WatermarkHit), dtype=torch.uint8, device=dev)
+        results = []
+        if n:
+            _lib.check(self.lib.conan_watermark_detect(self.h, int(key) & ((1 << 64) - 1), f, _ptr(buf), ld, n, sm.ctypes.data_as(C.c_void_p), _ptr(score),
+                                                       _ptr(soft), soft.shape[1], _ptr(hit), _stream()))
+        S, sf, hits = score.cpu().numpy(), soft.cpu().numpy(), hit.cpu().numpy().tobytes()
+        th = _lib.WATERMARK_THRESHOLD if threshold is None else float(threshold)
+        for i in range(n):
+            h = _lib.WatermarkHit.from_buffer_copy(hits[i * 16:(i + 1) * 16])
+            r = _lib.WatermarkResult()
+            s_row, f_row = np.ascontiguousarray(S[i]), np.ascontiguousarray(sf[i])
+            _lib.check(self.lib.conan_watermark_decide(s_row.ctypes.data_as(C.c_void_p), f_row.ctypes.data_as(C.c_void_p), C.byref(h), th, C.byref(r)))
+            d = dict(present=bool(r.present), z=float(r.z), id=int(r.id), offset=int(r.offset), rotation=int(r.rotation), marker_score=int(r.marker_score),
+                     blocks=int(r.blocks))
+            if raw:
+                d.update(S=s_row, soft=f_row[:h.blocks].copy(), peak=int(h.peak))
+            results.append(d)
+        return results
+
     def streams(self, max_slots, max_frames=4, max_ref_frames=256, arith="auto", flags=0, dev_plan=None):
         """A stream-set.  arith: 'auto' (library default), 'f32' (f32-input MFMA everywhere) or 'limb' (fp32 products of the
         vocoder's matrix kernels as bf16 limb products) - conan_streams_opts.arith; flags: _lib.STREAMS_*; dev_plan: developer /
@@ -1274,6 +1364,28 @@ class Streams:
         frames, bins, the noise floor and the attenuation per bin) for set_denoise(seed=) and Context.mel_denoise(seed=).  Joins
         pipelined work."""
         return self._feature_seed_rows("denoise", slots)
+
+    def set_watermark(self, slots, cfg=True, seed=None, **kw):
+        """conan_streams_set_watermark: a keyed mark in the audio the slots emit (include/conan_hip.h, conan_watermark_cfg): a +-1
+        chip sequence under a causal peak envelope, added on the GPU behind the comfort fill and in front of the output resampler and
+        the encoders, one more launch per vocoder step that carries a marked row, in every step entry point.  Context.watermark_detect
+        finds it again.  **kw / a dict in cfg: _lib.watermark_cfg's keywords (key, id, gain, floor); cfg may also be an
+        _lib.WatermarkCfg; only cfg=None turns it off.  The defaults are choices, not measurements.  It may be called at any time
+        (it joins pipelined work) and survives resets.  The state (position and envelope) restarts when a slot that was off is
+        enabled, after reseed=True and after a reset with the vocoder - from seed (uint8 [n, 16] cuda: rows of watermark_state) where
+        one is given; reseed=False on an enabled slot replaces key, id, gain and floor and keeps the state.  Slot snapshots do not
+        carry it: query watermark_state, export, import, then set_watermark(seed=rows, reseed=True)."""
+        self._set_feature("watermark", slots, cfg, kw, seed=seed)
+
+    def watermark(self, slots):
+        """conan_streams_watermark: per slot the setting as _lib.watermark_keywords reports it (set_watermark takes it back), None for
+        a slot without the mark."""
+        return self._get_feature("watermark", slots)
+
+    def watermark_state(self, slots):
+        """conan_streams_watermark_state: uint8 [n, 16] (cuda), the slots' conan_watermark_state records (_lib.WatermarkState reads
+        one: pos, env) for set_watermark(seed=) and Context.watermark_embed(seed=).  Joins pipelined work."""
+        return self._feature_seed_rows("watermark", slots)
 
     def set_output_format(self, slots, fmt):
         """conan_streams_set_output_format: the slots' audio leaves every step (and flush_output) as 'f32', 's16', 'ulaw' or 'alaw',

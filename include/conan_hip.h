@@ -1479,6 +1479,108 @@ int64_t conan_denoise_state_bytes(void);
  * CONAN_ERR_STATE. */
 int conan_streams_denoise_state(conan_streams* s, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream);
 
+/* Output watermark (added within ABI 9: a caller detects it by the symbol conan_streams_set_watermark; no existing struct or call
+ * changes).  A keyed mark in the audio a slot emits, which says "synthesised, and by whom": a +-1 chip sequence under a causal peak
+ * envelope, added on the GPU at the model rate (16 kHz) in f32 behind the slot's last in-place stage (the comfort fill) and in front of
+ * the output resampler and the encoders, and a detector that finds it again in 16-bit audio of any CONAN_SAMPLE_* format.
+ * tests/watermark_ref.py restates both laws in numpy with Python integers.
+ * Constants.  CHIP = 4 samples per chip; BLK = 2048 samples per block (512 chips, 128 ms); SUB = 64 samples per envelope sub-block;
+ *   W = 24 blocks per word (3.07 s).  The word is the marker 1,0,1,1,0,1,0,1 followed by the 16 bits of id, MSB first; bits map to +-1.
+ *   chip(key, m), m in 0 .. 511, is +1 if bit 63 of the comfort noise's hash of (key, m) is set, else -1: z = key + (m + 1) *
+ *   0x9E3779B97F4A7C15; z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31 (mod 2^64).
+ *   The sign of utterance sample j is s(j) = chip(key, (j mod BLK) / CHIP) * word[(j / BLK) mod W].
+ * Embed.  State {pos, env}, starting at {0, 0}.  For each sub-block b of a row, in order: p = max |y_j| over the sub-block;
+ *   env = fmaxf(p, env * 0.875f) (one f32 product); a = fmaxf(env * gain, floor) (one f32 product); y'_j = y_j + s(pos + j) * a (one
+ *   f32 add; the sign is exact).  After the row pos += samples.  A row's last sub-block may be short in the whole-signal form only;
+ *   streaming rows are whole hops (a multiple of SUB), so any cut into steps gives the same bits.  There is no clamp: the encoders
+ *   clamp, and f32 callers see the sum.  Every operation is a single correctly rounded one in a fixed order.
+ *   Defaults (conan_amd._lib.watermark_cfg): gain 0.1, that is -20 dB under the causal peak envelope; floor 0: digital silence stays
+ *   digital silence.  They are choices, not measurements: nobody has listened to the result, and this repository holds synthetic
+ *   weights and no speech corpus.
+ * Detect.  Integers on the 16-bit view q of a 16 kHz row of n samples: q = clamp(rint(x * 32768), -32768, 32767) (ties to even) for
+ *   f32, the decoded code otherwise.  d_j = 16 q_j - 15 q_{j-1} (q_{-1} = 0); u_j = d_j + d_{j+1} + d_{j+2} + d_{j+3};
+ *   K = max(0, n / BLK - 1) blocks; R[k][o] = sum over m < 512 of chip(key, m) * u[k * BLK + o + 4 m] for o in 0 .. BLK-1.
+ *   |u| <= 4 * 31 * 32768, so |R| <= 31 * 32768 * 4 * 512 = 2080374784 < 2^31: int32 accumulation is exact.  The block weight is
+ *   n_k = bit_length(sum of |d_j| over j in [k * BLK, (k + 2) * BLK)), at least 1; Rn = sign(R) * ((|R| << 12) >> n_k);
+ *   S[o] = sum over k of |Rn[k][o]|; o* = argmax S, the lowest index on ties; soft[k] = Rn[k][o*].
+ * Decide (host).  z = (S[o*] - mean S) / std S in f64 (population std; sums sequential in index order; 0 where std is 0).  For each
+ *   rotation r in 0 .. W-1 soft is folded into acc[(k + r) mod W] and the marker scored, sum of marker_i * acc[i]; the highest score
+ *   wins, the lowest r on ties; id is read from the signs of acc[8 .. 23] (> 0: 1).  present = z >= threshold.
+ *   CONAN_WATERMARK_THRESHOLD is about midway between the two groups DESIGN.md 4.23 measured with the reference: marked rows of 4 s
+ *   and 8 s through s16, mu-law at 16 kHz and mu-law at 8 kHz gave z = 17.6 .. 22.0, unmarked rows and rows marked with another key
+ *   3.0 .. 5.7.
+ * Out of scope: clock drift, time-scale changes, and marks cropped to under two blocks.  Audio at another rate comes back to 16 kHz
+ * through conan_resample first; the offset search absorbs the filter's delay. */
+#define CONAN_WATERMARK_THRESHOLD 11.5
+typedef struct conan_watermark_cfg {
+  int32_t enabled;     /* 0: off (other fields ignored) | 1 */
+  int32_t reseed;      /* 0 | 1: the state restarts (setter only) */
+  uint64_t key;
+  int32_t id;          /* 0 .. 65535 */
+  float gain;          /* finite, 0 .. 1 */
+  float floor;         /* finite, 0 .. 1 */
+  int32_t reserved[9]; /* must be 0 */
+} conan_watermark_cfg; /* 64 bytes */
+typedef struct conan_watermark_state {
+  int64_t pos;         /* utterance samples marked so far, >= 0 */
+  float env;           /* the envelope behind the last sub-block */
+  int32_t reserved;
+} conan_watermark_state; /* 16 bytes */
+typedef struct conan_watermark_hit {
+  int32_t offset, blocks;   /* o*, K */
+  int64_t peak;             /* S[o*] */
+} conan_watermark_hit; /* 16 bytes */
+typedef struct conan_watermark_result {
+  int32_t present, id, offset, rotation, blocks, reserved;
+  int64_t marker_score;
+  double z;
+} conan_watermark_result; /* 40 bytes */
+/* The embedder on whole signals, and the bit-exact yardstick of the streaming form: row i (n rows in 1 .. 65535) holds samples[i]
+ * (host, 0 .. 2^31 - 1) floats at x_dev + i * ld floats (ld >= every samples[i]); out_dev has the same shape and may equal x_dev.
+ * cfg->enabled must be 1; cfg->reseed is ignored.  seed_dev (may be null): conan_watermark_state[n], the state row i starts from
+ * (pos >= 0); without it every row starts at {0, 0}.  state_out_dev (may be null): the state behind each row; it may equal seed_dev.
+ * Both 8-byte aligned.  ONE launch (cnk::watermark_embed_kernel, one workgroup per row) on `stream`; the row table goes through the
+ * context's workspace, which conan_wav2mel, conan_loud_norm and conan_activity share: calls on one context are ordered by the caller. */
+int conan_watermark_embed(conan_ctx* ctx, const conan_watermark_cfg* cfg, const float* x_dev, int n, const int64_t* samples, int64_t ld,
+                          const conan_watermark_state* seed_dev, float* out_dev, conan_watermark_state* state_out_dev, void* stream);
+/* The detector's device half: row i (n rows in 1 .. 4096) holds samples[i] (host, 0 .. 2^26) samples of `format` at x_dev + i * ld * 4
+ * bytes (4-byte aligned; ld dwords hold every row).  score_dev: int64 [n][2048], S; soft_dev: int64 rows soft_ld apart (soft_ld >=
+ * the largest K of the call), soft[k] for k < K and 0 from there to the call's largest K; hit_dev: conan_watermark_hit[n]; all three
+ * 8-byte aligned.  A row with K = 0 reports zeros.  Two launches on `stream` (cnk::watermark_corr_kernel, none when every K is 0, and
+ * cnk::watermark_peak_kernel); Rn goes through the context's workspace as int32 (|Rn| < 2^12, because |R| is at most the window's sum
+ * of |d|): 8 KiB per row and block, at most 2 GiB per call (CONAN_ERR_INVALID beyond: split the call); calls on one context are
+ * ordered by the caller, as above. */
+int conan_watermark_detect(conan_ctx* ctx, uint64_t key, int format, const void* x_dev, int64_t ld, int n, const int64_t* samples,
+                           int64_t* score_dev, int64_t* soft_dev, int64_t soft_ld, conan_watermark_hit* hit_dev, void* stream);
+/* Host only: the decision from one row's S [2048], soft [blocks] and record.  threshold: CONAN_WATERMARK_THRESHOLD unless the caller
+ * has measured its own.  blocks = 0 reports present = 0, blocks = 0 and reads nothing. */
+int conan_watermark_decide(const int64_t* score, const int64_t* soft, const conan_watermark_hit* hit, double threshold, conan_watermark_result* out);
+/* Sets (cfg->enabled = 1) or removes (0) the mark for `slots`.  Every argument is checked before anything changes (CONAN_ERR_INVALID:
+ * a field outside its range, a non-zero reserved word, a seed that is misaligned or whose rows are too close; CONAN_ERR_UNSUPPORTED:
+ * the whole-prefix vocoder of upsample 'nn', whose steps are not update intervals - as for the output leveller; CONAN_ERR_STATE: a
+ * context without a HiFi-GAN model), and pending pipelined work is joined; it may be called at any time, also mid-utterance, and the
+ * setting persists across resets.
+ * A marked slot costs one more launch (cnk::watermark_embed_kernel) per vocoder step that carries one, in every step entry point,
+ * mel-in ones included: behind the comfort fill and in front of the output resampler.  The output leveller's meter reads its stage as
+ * before: unmarked audio.  The state restarts when a slot that was off is enabled, on reseed = 1 (from seed_dev's row where one is
+ * given: row i at seed_dev + i * seed_ld bytes, on `stream`) and on a reset that includes CONAN_MODEL_HIFIGAN (from {0, 0}).  A call
+ * with reseed = 0 on an enabled slot changes key, id, gain and floor from the next step and keeps pos and env; its seed row is not read.
+ * Memory: the first enabling call allocates the states and 8 row tables; conan_streams_state_bytes counts them from then on.  A
+ * stream-set that never calls the setter allocates nothing and runs exactly the launches it ran before; a slot that does not ask
+ * keeps its bits.  Snapshots carry neither the setting nor the state, and conan_streams_layout_id and conan_streams_snapshot_bytes do
+ * not change.  The hand-over: conan_streams_watermark_state, export, import, then this setter with the record as seed_dev and
+ * reseed = 1. */
+int conan_streams_set_watermark(conan_streams* s, const int32_t* slots, int n, const conan_watermark_cfg* cfg, const void* seed_dev, int64_t seed_ld,
+                                void* stream);
+/* Host only: the mark's cfg of `slot` as set (zeros for a slot without one; reseed reads 0). */
+int conan_streams_watermark(const conan_streams* s, int slot, conan_watermark_cfg* cfg_out);
+/* sizeof(conan_watermark_state). */
+int64_t conan_watermark_state_bytes(void);
+/* The states of `slots` -> row i at rows_dev + i * ld bytes (8-byte aligned, ld a multiple of 8 and at least the record's bytes), on
+ * `stream` behind a join of pipelined work.  A slot about to restart reports the zero record; a slot without the feature is
+ * CONAN_ERR_STATE. */
+int conan_streams_watermark_state(conan_streams* s, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
