@@ -160,6 +160,12 @@ _PROTOS = {
     "conan_watermark_detect": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                          C.c_void_p, C.c_void_p]),
     "conan_watermark_decide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    "conan_tone_table": (C.c_int, [C.c_int, C.c_void_p]),
+    "conan_tones": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_tone_fill": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                  C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "conan_step_wav_tones": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_conceal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_trim_silence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
@@ -723,6 +729,74 @@ def watermark_keywords(c):
     return dict(key=int(c.key), id=int(c.id), gain=float(c.gain), floor=float(c.floor))
 
 
+class ToneState(C.Structure):
+    """conan_tone_state (include/conan_hip.h)."""
+    _fields_ = [("cand", C.c_int32), ("run", C.c_int32), ("cur", C.c_int32), ("miss", C.c_int32), ("held", C.c_int32), ("sound", C.c_int32),
+                ("level", C.c_int32), ("reserved", C.c_int32), ("events", C.c_int64), ("frames", C.c_int64)]
+
+
+class ToneCfg(C.Structure):
+    """conan_tone_cfg (include/conan_hip.h)."""
+    _fields_ = [("mode", C.c_int32), ("reseed", C.c_int32), ("thr", C.c_int64), ("twist_fwd_q8", C.c_int32), ("twist_rev_q8", C.c_int32), ("sel", C.c_int32),
+                ("share_q8", C.c_int32), ("on_frames", C.c_int32), ("off_frames", C.c_int32), ("min_frames", C.c_int32), ("step", C.c_int32),
+                ("gain", C.c_float), ("reserved", C.c_int32), ("seed", ToneState)]
+
+
+TONE_FULL = 1 << 20
+TONE_HOP_MAX = 512
+TONE_KEYS = "123A456B789C*0#D"      # frame digit d = 4 * row + column
+TONE_FIELDS = ("thr", "twist_fwd_q8", "twist_rev_q8", "sel", "share_q8", "on_frames", "off_frames", "min_frames", "step")
+TONE_SEED = dict(cand=-1, run=0, cur=-1, miss=0, held=0, sound=-1, level=0, events=0, frames=0)
+
+
+def tone_cfg(regenerate=True, hop=320, level_db=-40.0, twist_db=(4.0, 8.0), sel=8, share=0.5, on_frames=2, off_frames=2, min_frames=3, ramp_ms=0.0,
+             gain=0.125, seed=None, reseed=False, thr=None, twist_fwd_q8=None, twist_rev_q8=None, share_q8=None, step=None):
+    """An enabled conan_tone_cfg: detect and regenerate (mode 2) or detect only (regenerate=False: mode 1).  level_db: the least level
+    of each tone in dBFS at frames of `hop` samples (thr = (A hop / 8)^2, A = 32768 * 10^(level_db / 20)); twist_db: by how much the
+    high tone may exceed the low one, and the low one the high one; sel: a group's peak over each of its other three; share: the
+    pair's least share of the frame's energy; on_frames / off_frames / min_frames: the debounce in 20 ms frames; ramp_ms: the time
+    the regenerated pair takes to full level, in steps of one frame (0: at once); gain: each regenerated tone's amplitude (0.125:
+    -18 dBFS).  seed: a state dict (Streams.tone_state's) a restart begins from.  The integer keywords (thr, twist_fwd_q8,
+    twist_rev_q8, share_q8, step) give a field directly and win over their other forms.  The defaults are choices: talk-off against
+    real speech has not been measured."""
+    if thr is None:
+        thr = int(round((32768.0 * 10.0 ** (float(level_db) / 20.0) * int(hop) / 8.0) ** 2))
+    q8 = lambda db: int(round(256.0 * 10.0 ** (float(db) / 10.0)))      # noqa: E731
+    if step is None:
+        step = TONE_FULL if float(ramp_ms) <= 20.0 else max(1, int(math.ceil(TONE_FULL * 20.0 / float(ramp_ms))))      # (the ramp is complete after ramp_ms / 20 frames)
+    st = ToneState()
+    for name, v in dict(TONE_SEED, **{k: v for k, v in (seed or {}).items() if k != "reserved"}).items():
+        setattr(st, name, int(v))
+    return ToneCfg(2 if regenerate else 1, int(bool(reseed)), int(thr), q8(twist_db[0]) if twist_fwd_q8 is None else int(twist_fwd_q8),
+                   q8(twist_db[1]) if twist_rev_q8 is None else int(twist_rev_q8), int(sel), int(round(256.0 * float(share))) if share_q8 is None else int(share_q8),
+                   int(on_frames), int(off_frames), int(min_frames), int(step), float(gain), 0, st)
+
+
+def tone_keywords(c):
+    """tone_cfg's keywords of an enabled ToneCfg in the integer forms that give the same fields back exactly: the form Streams.tones
+    reports a setting in."""
+    return dict({name: int(getattr(c, name)) for name in TONE_FIELDS}, regenerate=c.mode == 2, gain=float(c.gain),
+                seed={name: int(getattr(c.seed, name)) for name in TONE_SEED})
+
+
+def tone_events(digit_rows):
+    """Per row of per-frame digits (Streams.step_wav_tones' / Context.tones', the calls' rows of a slot joined in time; -1: none) the
+    key presses [(key, first frame, frames)], keys from '123A456B789C*0#D': what a host sends as RFC 4733 events, 20 ms per frame.
+    A digit still held in the last frame is reported with the frames seen so far.  A single row (a 1-D array, tensor or list of
+    integers) gives one list, rows (2-D, or a list of rows of their own lengths) a list per row.  Host only: tensors on the CPU."""
+    single = len(digit_rows) > 0 and not isinstance(digit_rows[0], (list, tuple)) and getattr(digit_rows[0], "ndim", 0) == 0
+    out = []
+    for row in ([digit_rows] if single else digit_rows):
+        ev, prev, start = [], -1, 0
+        for f, d in enumerate([int(v) for v in row] + [-1]):
+            if d != prev:
+                if prev >= 0:
+                    ev.append((TONE_KEYS[prev], start, f - start))
+                prev, start = d, f
+        out.append(ev)
+    return out[0] if single else out
+
+
 class SlotFeature(typing.NamedTuple):
     """One per-slot feature of a stream-set, as Streams and the engine read it.  A symbol the library does not have is None."""
     keyword: str                  # the engine's keyword (start_wav, open_slots, ...)
@@ -770,6 +844,8 @@ SLOT_FEATURES = {f.keyword: f for f in (
                 "conan_streams_denoise", seed_state="conan_streams_denoise_state", seed_bytes="conan_denoise_state_bytes"),
     SlotFeature("comfort", "the comfort noise", ComfortCfg, "mode", comfort_cfg, comfort_keywords, "conan_streams_set_comfort",
                 "conan_streams_comfort", "conan_streams_comfort_state", ComfortState, last="conan_step_wav_comfort"),
+    SlotFeature("tones", "the tone detector", ToneCfg, "mode", tone_cfg, tone_keywords, "conan_streams_set_tones", "conan_streams_tones",
+                "conan_streams_tone_state", ToneState, last="conan_step_wav_tones"),
     SlotFeature("out_level", "the leveller", LevelCfg, "enabled", level_cfg, level_keywords, "conan_streams_set_output_level",
                 "conan_streams_output_level_cfg", "conan_streams_output_level", ("float64", 4), "conan_streams_output_level_state",
                 "conan_streams_output_level_state_bytes", release=False, mirror="output_levels"),

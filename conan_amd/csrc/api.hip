@@ -1025,6 +1025,44 @@ int conan_streams_watermark_state(conan_streams* s, const int32_t* slots, int n,
   return guarded([&] { wmark::state(s, slots, n, rows_dev, ld, stream); });
 }
 
+// ---- signalling tones (tone.hip): conan_tone_table, conan_tones, conan_tone_fill, conan_streams_set_tones, conan_streams_tones,
+// conan_streams_tone_state, conan_step_wav_tones
+int conan_tone_table(int sample_rate, int16_t* table_out) {
+  try {      // (host only, and no launch to answer for: it also runs where no device is)
+    tone::table_out(sample_rate, table_out);
+    return CONAN_OK;
+  } catch (const ch::Error& e) {
+    g_err = e.what();
+    return e.code;
+  }
+}
+
+int conan_tones(conan_ctx* ctx, int hop, const conan_tone_cfg* cfg, const float* wav_dev, int64_t ld, int n, const int64_t* samples,
+                const conan_tone_state* seed_dev, int32_t* digit_dev, int32_t* sound_dev, int32_t* level_dev, int64_t out_ld,
+                conan_tone_state* state_out_dev, int64_t* frames_out, void* stream) {
+  return guarded([&] { tone::whole(ctx, hop, cfg, wav_dev, ld, n, samples, seed_dev, digit_dev, sound_dev, level_dev, out_ld, state_out_dev, frames_out, stream); });
+}
+
+int conan_tone_fill(conan_ctx* ctx, int hop, const conan_tone_cfg* cfg, const float* wav_dev, int64_t ld, int n, int64_t samples, const int64_t* pos0,
+                    const int32_t* sound_dev, const int32_t* level_dev, int64_t lvl_ld, int32_t start_level, int32_t start_sound, float* out_dev,
+                    int64_t out_ld, void* stream) {
+  return guarded([&] { tone::fill(ctx, hop, cfg, wav_dev, ld, n, samples, pos0, sound_dev, level_dev, lvl_ld, start_level, start_sound, out_dev, out_ld, stream); });
+}
+
+int conan_streams_set_tones(conan_streams* s, const int32_t* slots, int n, const conan_tone_cfg* cfg, void* stream) {
+  return guarded([&] { tone::set_tones(s, slots, n, cfg, stream); });
+}
+
+int conan_streams_tones(const conan_streams* s, int slot, conan_tone_cfg* cfg_out) { return guarded([&] { wavio::get_setting(s, &conan_streams::tn, slot, cfg_out, "conan_streams_tones"); }); }
+
+int conan_streams_tone_state(conan_streams* s, const int32_t* slots, int n, conan_tone_state* state_dev, void* stream) {
+  return guarded([&] { tone::state(s, slots, n, state_dev, stream); });
+}
+
+int conan_step_wav_tones(conan_streams* s, int32_t* digit_dev, int32_t* sound_dev, int32_t* level_dev, void* stream) {
+  return guarded([&] { tone::last_call(s, digit_dev, sound_dev, level_dev, stream); });
+}
+
 int conan_hop_size(const conan_ctx* ctx) { return ctx ? ctx->hop : 0; }
 int64_t conan_ctx_weight_bytes(const conan_ctx* ctx) { return ctx ? ctx->weight_bytes : 0; }
 int64_t conan_streams_state_bytes(const conan_streams* s) { return s ? s->state_bytes : 0; }

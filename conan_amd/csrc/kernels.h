@@ -1013,6 +1013,47 @@ struct WmDetectArgs {
 void launch_watermark_corr(const WmDetectArgs& a, hipStream_t st);
 void launch_watermark_peak(const WmDetectArgs& a, hipStream_t st);
 
+// ---- signalling tones (tone.hip; include/conan_hip.h, conan_tone_cfg): the DTMF detector of a row's source frames and the
+// regeneration of a confirmed digit on the vocoder's audio.
+//   tone_kernel: one workgroup per table row, the table W in LDS.  A row runs the law over its nframes frames - samples
+//     src[src_off + (j & mask)] for j < valid, zero beyond, frame f_first + k (f_first < 0: the state's `frames`) - from state[slot]
+//     (reseed = 0 and slot >= 0) or from its seed record (seed[row] of a whole-signal call where given), writes digit[out_off + k],
+//     sound[lvl_off + k], level[lvl_off + k] and - start_lvl = 1 - the sound and level before the row's first frame to word
+//     lvl_off - 1, and the state after the row to state[slot] / state_out[state_row].  mode = 0: a row of a slot without the feature,
+//     which holds its place in the table so that the fill finds row i of a vocoder step at entry i.
+//   tone_fill_kernel: row i of the launch is x + i * ld -> y + i * ld_y (y may equal x), `samples` samples, sample s being utterance
+//     sample tab[i].pos0 + s; sound[i * lvl_ld + f] and level[i * lvl_ld + f] after frame f, and before frame 0 start_sound /
+//     start_level (start_in_lvl = 0) or word -1 of the rows (start_in_lvl = 1: the detector's staging rows).  Rows with
+//     tab[i].mode != 2 are skipped and keep their bits.
+constexpr int kToneFreqs = 8, kToneSums = 2 * kToneFreqs + 1, kToneTile = 64, kToneFull = 1 << 20, kToneHopMax = 512;
+struct ToneState { int cand, run, cur, miss, held, sound, level, reserved; long long events, frames; };
+static_assert(sizeof(ToneState) == 48, "conan_tone_state");
+struct ToneRow {
+  long long src_off, valid, out_off, lvl_off, f_first, thr, pos0;
+  ToneState seed;
+  int mask, nframes, slot, reseed, state_row, mode, start_lvl;
+  int twist_fwd, twist_rev, sel, share, on_frames, off_frames, min_frames, step;
+  float gain;
+};
+static_assert(sizeof(ToneRow) == 168, "uploaded as 42 ints");
+struct ToneArgs {
+  const float* src; const short* table;
+  int* digit; int* sound; int* level;
+  ToneState* state;             // [max_slots], indexed by slot; may be null when no row names a slot
+  const ToneState* seed;        // [rows] of a whole-signal call; may be null
+  ToneState* state_out;         // [rows]; may be null when no row has a state_row
+  const ToneRow* tab; int rows, hop, M;
+  int long_rows;                // 1: rows of many frames (a whole signal): workgroups of kActThreads; 0: of kActStreamThreads
+};
+void launch_tone(const ToneArgs& a, hipStream_t st);
+struct ToneFillArgs {
+  const float* x; float* y; const int* sound; const int* level; const short* table; const ToneRow* tab;
+  long long ld, ld_y, lvl_ld, samples;
+  int n, hop, M, start_level, start_sound, start_in_lvl;
+};
+constexpr int kToneFillThreads = 256;
+void launch_tone_fill(const ToneFillArgs& a, hipStream_t st);
+
 // ---- style pass (per utterance) helpers
 struct RowMaskArgs { TRef x; TRef m; const int* lens; int T, n, C; int mode; };  // mode 0: sum|x|>0, 1: x[0]!=0
 void launch_rowmask(const RowMaskArgs& a, hipStream_t st);

@@ -317,6 +317,19 @@ struct conan_streams {
     std::vector<LastRow> last;
   } cmf;
   void comfort_init();
+  // signalling tones (conan_streams_set_tones; tone.hip; on: mode != 0).  state: [max_slots], read and written by the rows of
+  // tone_kernel in the order of the front-end launches; pending restarts it from the cfg's seed.  Rows: as the activity table's;
+  // beside the table the frame digits [q][chunk row][seg] and the sounds and levels [q][chunk row][seg + 1] (word 0: the value
+  // before the chunk) on their way to the vocoder stage of the same call, whose fill reads table, sounds and levels.  Event: behind
+  // the call's last vocoder step; kActSets sets for the reason given there.  last: conan_step_wav_tones.
+  struct Tones : SlotSetting<conan_tone_cfg, &conan_tone_cfg::mode> {
+    cnk::ToneState* state = nullptr;
+    const short* table = nullptr;
+    int* digit[kActSets] = {}; int* sound[kActSets] = {}; int* level[kActSets] = {};
+    StageSets<cnk::ToneRow, kActSets> sets;
+    std::vector<LastRow> last;
+  } tn;
+  void tones_init();
   // input loss concealment (conan_streams_set_conceal; conceal.hip).  state: [max_slots] records of cnk::kConcStateBytes, read and
   // written by the rows of conceal_kernel in the order of the caller's stream; pending restarts it from zeros (set when a slot that
   // was off is enabled without a seed; a seed clears it).  Rows: per repair call; event: behind the kernel's launch.  No step path
@@ -336,7 +349,7 @@ struct conan_streams {
   } dn;
   void denoise_init();
   // a reset with CONAN_MODEL_FRONTEND: the settings stay; the states restart in the slots' next rows (host flags: no launch)
-  void restart_features(const int32_t* slots, int n) { reg.restart(slots, n); act.restart(slots, n); byp.restart(slots, n); cmf.restart(slots, n); conc.restart(slots, n); dn.restart(slots, n); }
+  void restart_features(const int32_t* slots, int n) { reg.restart(slots, n); act.restart(slots, n); byp.restart(slots, n); cmf.restart(slots, n); conc.restart(slots, n); dn.restart(slots, n); tn.restart(slots, n); }
   void ragged_init();
   void resample_init();        // staging, row tables and the history ring (conan_streams_set_input_rate)
   void rs_stage_init();        // staging and row tables only (conan_streams_set_input_format: no stream state)
@@ -431,6 +444,10 @@ struct conan_streams {
     // the step's watermark (watermark.hip; out_plan's, for a step with a marked row): one table row per step row; hifigan_step
     // launches watermark_embed_kernel behind the fill and in front of the output resampler
     std::vector<cnk::WmRow> wm_rows;
+    // the step's regenerated tones (tone.hip; filled by tone::WavStage for a group with a mode-2 row): the group's rows of the call's
+    // tone table and of its sound and level staging; hifigan_step launches tone_fill_kernel behind the watermark, as the last
+    // in-place stage in front of the output resampler
+    struct Tone { const cnk::ToneRow* tab = nullptr; const int* sound = nullptr; const int* level = nullptr; int lvl_ld = 0; } tone;
   };
   OutPlan out_plan(const int32_t* slots, int n, int frames, float* wav_out_dev, long long natural_ld, const std::vector<int>* dst, const std::string& who) const;
   // the plan's resample_out_kernel launch behind or_sets.begin() = q, then the set's event; src_ld: stride of the staged rows (a flush: 0)
@@ -698,7 +715,7 @@ struct WavCall {
 };
 // The front-end work of a wav-in call: at most one entry per position, run in this order on one stream (the caller's, or as
 // step_pipelined's `pre`).  The ...End entries record the events of the sets the mel front-end launch is the last to read.
-enum FrontPos { kFrResample, kFrLevel, kFrMel, kFrDenoise, kFrLevelEnd, kFrResampleEnd, kFrF0, kFrRegister, kFrActivity, kFrBypass, kFrComfort, kFrCount };
+enum FrontPos { kFrResample, kFrLevel, kFrMel, kFrDenoise, kFrLevelEnd, kFrResampleEnd, kFrF0, kFrRegister, kFrActivity, kFrBypass, kFrComfort, kFrTones, kFrCount };
 struct FrontWork {
   std::function<void(hipStream_t)> at[kFrCount];
   void run(hipStream_t st) const { for (const auto& f : at) if (f) f(st); }
@@ -924,6 +941,34 @@ struct WavStage {
   void commit(conan_streams* s, hipStream_t dec, hipStream_t last_st);
 };
 }  // namespace comfort
+
+// ---- signalling tones (tone.hip): the kernels' host side and the bodies of api.hip's entry points
+namespace tone {
+void check_cfg(const conan_tone_cfg& c, const char* who);      // host only
+void check_rate(int hop, const char* who);                     // host only: CONAN_ERR_UNSUPPORTED outside the table's range
+std::vector<short> host_table(int M);                          // host only
+const short* table(conan_ctx* ctx, int M);                     // the context's device copy, built on first use per rate
+cnk::ToneRow row(const conan_tone_cfg& c);      // the cfg's fields of a detector row that starts from the seed and names no slot
+void table_out(int sample_rate, int16_t* out);
+void whole(conan_ctx* ctx, int hop, const conan_tone_cfg* cfg, const float* wav_dev, int64_t ld, int n, const int64_t* samples, const conan_tone_state* seed_dev,
+           int32_t* digit_dev, int32_t* sound_dev, int32_t* level_dev, int64_t out_ld, conan_tone_state* state_out_dev, int64_t* frames_out, void* stream);
+void fill(conan_ctx* ctx, int hop, const conan_tone_cfg* cfg, const float* wav_dev, int64_t ld, int n, int64_t samples, const int64_t* pos0, const int32_t* sound_dev,
+          const int32_t* level_dev, int64_t lvl_ld, int32_t start_level, int32_t start_sound, float* out_dev, int64_t out_ld, void* stream);
+void set_tones(conan_streams* s, const int32_t* slots, int n, const conan_tone_cfg* cfg, void* stream);
+void state(conan_streams* s, const int32_t* slots, int n, conan_tone_state* state_dev, void* stream);
+void last_call(conan_streams* s, int32_t* digit_dev, int32_t* sound_dev, int32_t* level_dev, void* stream);
+// As the activity table: one row per emitting call row in a call in which a slot with the feature emits.  The detector runs behind
+// the front-end launch; the groups with a mode-2 row take their rows of table, sounds and levels along to their vocoder steps.
+struct WavStage {
+  std::vector<cnk::ToneRow> rows;
+  std::vector<LastRow> last;
+  std::vector<char> fill;       // per emit group: a row of it regenerates (empty: no table)
+  int q = 0;
+  void plan(const conan_streams* s, const WavCall& c);
+  void enqueue(conan_streams* s, const WavCall& c, hipStream_t cst, FrontWork& front, std::vector<conan_streams::OutPlan>& ops);
+  void commit(conan_streams* s, hipStream_t dec, hipStream_t last_st);
+};
+}  // namespace tone
 
 // ---- input loss concealment (conceal.hip): the kernel's host side and the bodies of api.hip's entry points
 namespace conc {

@@ -655,6 +655,12 @@ void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float*
       wm.sets.end(wq, st);
       for (const cnk::WmRow& r : op->wm_rows) if (r.on) wm.pending[r.slot] = 0;      // (the rows carried the restarts)
     }
+    if (op && op->tone.tab) {      // the regenerated tones of a wav-in step (tone.hip): the last in-place stage, behind the watermark
+      cnk::ToneFillArgs f; memset(&f, 0, sizeof(f));
+      f.x = a.wav; f.y = a.wav; f.sound = op->tone.sound; f.level = op->tone.level; f.table = tn.table; f.tab = op->tone.tab;
+      f.ld = T; f.ld_y = T; f.lvl_ld = op->tone.lvl_ld; f.samples = T; f.n = n; f.hop = ctx->hop; f.M = 50 * ctx->hop; f.start_in_lvl = 1;
+      profiled("tone_fill_kernel", 0.0, st, [&] { cnk::launch_tone_fill(f, st); });
+    }
     if (out_rows) resample_out(*op, oq, T, st);
     if (levelled) {      // ... and its meter, off the audio's path: the staged samples into the slots' state, for the next step's ramp
       cnk::LevelOutMeterArgs l; memset(&l, 0, sizeof(l));

@@ -294,9 +294,9 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
   }
   // the features' part of the call, each in its own file, in the order of their launches: every plan before anything changes
   WavCall call{slots, n, pl, groups, seg, hop, N, m, who, P.launch, samples, common, wav_dev, wav_ld};
-  level::WavStage lv; f0::WavStage follow; act::WavStage activity; byp::WavStage bypass; comfort::WavStage noise; denoise::WavStage suppress;
+  level::WavStage lv; f0::WavStage follow; act::WavStage activity; byp::WavStage bypass; comfort::WavStage noise; denoise::WavStage suppress; tone::WavStage tones;
   bypass.gate_stage = &activity; noise.gate_stage = &activity;
-  lv.plan(s, call); follow.plan(s, call); activity.plan(s, call); bypass.plan(s, call); noise.plan(s, call); suppress.plan(s, call);
+  lv.plan(s, call); follow.plan(s, call); activity.plan(s, call); bypass.plan(s, call); noise.plan(s, call); suppress.plan(s, call); tones.plan(s, call);
   const int nm_in = m.num_mels, nm = c.num_mels;
   int jobs = 0;
   std::vector<RgRow> tab;
@@ -369,7 +369,7 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
   }
   activity.power = noise.take(s, cst);      // (a following comfort row reads the frame powers: the detector stages them in this call)
   lv.enqueue(s, call, cst, front, ops); follow.enqueue(s, call, cst, front, ops); activity.enqueue(s, call, cst, front, ops); bypass.enqueue(s, call, cst, front, ops);
-  noise.enqueue(s, call, cst, front, ops); suppress.enqueue(s, call, cst, front, ops);
+  noise.enqueue(s, call, cst, front, ops); suppress.enqueue(s, call, cst, front, ops); tones.enqueue(s, call, cst, front, ops);
   const std::function<void(hipStream_t)> pre = [&front](hipStream_t st) { front.run(st); }, none;
   cnk::WavScatterArgs sc;
   sc.tab = rg_tab; sc.n = n; sc.seg = seg; sc.nm = nm; sc.hop = hop;
@@ -405,7 +405,7 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
     s->profiled("wav_rows_scatter_kernel", 0.0, cst, [&] { cnk::launch_wav_scatter(sc, cst); });
   }
   if (!common) s->wav_in.rg_sets.end(q, last);
-  lv.commit(s, dec, last); follow.commit(s, dec, last); activity.commit(s, dec, last); bypass.commit(s, dec, last); noise.commit(s, dec, last); suppress.commit(s, dec, last);
+  lv.commit(s, dec, last); follow.commit(s, dec, last); activity.commit(s, dec, last); bypass.commit(s, dec, last); noise.commit(s, dec, last); suppress.commit(s, dec, last); tones.commit(s, dec, last);
   if (scatter && !route) {      // (each group's step counted its own rows, in group order: back to the call's rows)
     s->wav_out.out_counts.assign(n, 0);
     for (int i = 0; i < n; ++i) s->wav_out.out_counts[i] = pl[i].emit * hop;

@@ -212,7 +212,7 @@ def _by_value(slots, values):
 
 
 # what True means to a feature's Streams setter, by engine keyword (register= has no True: a scalar is its target)
-_TRUE = dict(level=True, pitch=True, follow=True, out_level=True, activity=dict(gate=True), bypass={}, conceal={}, denoise={}, comfort={}, watermark={})
+_TRUE = dict(level=True, pitch=True, follow=True, out_level=True, activity=dict(gate=True), bypass={}, conceal={}, denoise={}, comfort={}, watermark={}, tones={})
 
 
 def _accept(keyword, v, k, n, voice):
@@ -320,7 +320,7 @@ class StreamingVoiceConversionEngine:
             self._apply(keyword, self.slots, values[keyword])
 
     def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, denoise=None, watermark=None, **filter):
+                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, denoise=None, watermark=None, tones=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
         in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
         in_format: the input's sample format (None: float32; 's16' takes int16 rows, 'ulaw' / 'alaw' uint8), decoded on the GPU.
@@ -346,13 +346,15 @@ class StreamingVoiceConversionEngine:
         denoise: noise suppression of the input's log-mel frames (Streams.set_denoise) - None / False: none; True: the defaults for
         the default mel front-end (log10, vmin -6, eps 1e-6); a dict of _lib.denoise_cfg's keywords (a feed(mel=...) with another
         log base or floor names it there: natural_log, mel_vmin, eps).  The Emformer then sees the suppressed frames.
+        tones: DTMF detection and regeneration (Streams.set_tones) - None / False: none; True: detect and regenerate with the
+        defaults; a dict of set_tones's keywords (regenerate=False only detects).  chunk_tones() reads the last call's rows.
         There is no trim= here: silence trimming (infer_wav(trim=True)) moves audio forward over pauses it has seen whole, and a
         stream cannot drop time it has not heard yet; activity= is what a live call has in its place."""
         self._check_voice(ref_mel, voice)
         if isinstance(in_format, (list, tuple)) or isinstance(level, (list, tuple)):
             raise ValueError("in_format / level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
         values = self._host_checks(len(self.slots), voice, level=level, follow=follow, register=register, activity=activity, bypass=bypass,
-                                   conceal=conceal, comfort=comfort, denoise=denoise)
+                                   conceal=conceal, comfort=comfort, denoise=denoise, tones=tones)
         self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice,
                    out_level=out_level, watermark=watermark)
         self._set_rate(self.slots, in_rate, filter)
@@ -420,6 +422,18 @@ class StreamingVoiceConversionEngine:
         int32 in the call's row order, zeros for rows without the feature and past a row's frames; _lib.comfort_dbov(level) is the
         RFC 3389 noise level byte of a frame."""
         return self.st.step_wav_comfort()
+
+    def set_tones(self, slots=None, cfg=True, **kw):
+        """A live change of the slots' DTMF detection and regeneration (all slots by default) between feed / feed_ragged calls, also
+        mid-utterance and with pipelined steps in flight: Streams.set_tones's arguments (cfg=None turns it off; without reseed=True
+        an enabled slot keeps its state).  In force from the next emitted chunk."""
+        self._live("tones", slots, cfg, **kw)
+
+    def chunk_tones(self):
+        """The tone rows of the last feed / feed_ragged call (Streams.step_wav_tones; joins pipelined work): (digit, sound, level),
+        each [n, seg] int32 in the call's row order; digit is the confirmed key of each 20 ms frame (-1: none) and
+        _lib.tone_events(rows) lists the presses a host sends as RFC 4733 events."""
+        return self.st.step_wav_tones()
 
     def set_denoise(self, slots=None, cfg=True, **kw):
         """A live change of the slots' noise suppression (all slots by default) between feed / feed_ragged calls, also mid-utterance
@@ -635,7 +649,7 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
                   out_format=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None, register=None, activity=None,
-                  activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, comfort=None, denoise=None, watermark=None, **filter):
+                  activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, comfort=None, denoise=None, watermark=None, tones=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] (or None with voice = (bank, ids): start) -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
@@ -666,7 +680,7 @@ class StreamingVoiceConversionEngine:
         (start): the returned model-rate wav is ctx.watermark_embed of the unmarked one, bit for bit."""
         self._check_voice(ref_mel, voice)
         self._host_checks(len(self.slots), voice, level=level, pitch=pitch, follow=follow, register=register, activity=activity, bypass=bypass,
-                          conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark)      # (before anything runs)
+                          conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones)      # (before anything runs)
         self._check_lost(lost, conceal, loud_norm, trim)
         trim = self._trim_keywords(trim)
         if trim is not None:
@@ -675,7 +689,7 @@ class StreamingVoiceConversionEngine:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
                        pitch=pitch, voice=voice, follow=follow, register=register, activity=activity, bypass=bypass, out_level=out_level, conceal=conceal,
-                       comfort=comfort, denoise=denoise, watermark=watermark, **filter)
+                       comfort=comfort, denoise=denoise, watermark=watermark, tones=tones, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -707,7 +721,7 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, denoise=None, watermark=None, **filter):
+                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, denoise=None, watermark=None, tones=None, **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
         rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
@@ -725,7 +739,7 @@ class StreamingVoiceConversionEngine:
         it holds whole)."""
         self._check_voice(ref_mel, voice)
         values = self._host_checks(len(slots), voice, level=level, pitch=pitch, follow=follow, register=register, activity=activity, bypass=bypass,
-                                   conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark)
+                                   conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones)
         self.st.reset(slots, which=7 | 8)
         self._reference(slots, ref_mel, ref_len, voice)
         self._set_out_rate(slots, out_rate, out_filter)
@@ -757,7 +771,7 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
                             in_formats=None, out_formats=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None,
-                            register=None, activity=None, activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, comfort=None, denoise=None, watermark=None, **filter):
+                            register=None, activity=None, activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, comfort=None, denoise=None, watermark=None, tones=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -786,7 +800,7 @@ class StreamingVoiceConversionEngine:
         U = len(src_wavs)
         # (host checks before anything runs; per utterance, in the form open_slots takes back)
         values = self._host_checks(U, voice, ("out_level",), level=level, pitch=pitch, follow=follow, register=register, activity=activity,
-                                   bypass=bypass, conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark)
+                                   bypass=bypass, conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones)
         self._check_lost(lost, conceal, loud_norm, trim)
         if lost is not None and len(lost) != U:
             raise ValueError(f"lost: {len(lost)} values for {U} utterances")

@@ -499,6 +499,94 @@ class Context:
                                                _stream()))
         return y
 
+    def tone_table(self, sample_rate=None):
+        """conan_tone_table: the tone table of `sample_rate` (default: the model rate), W[m] = rint(2^14 cos(2 pi m / M)) -> int16 numpy
+        [sample_rate].  Host only."""
+        M = self.hop * 50 if sample_rate is None else int(sample_rate)
+        out = np.zeros(max(M, 1), dtype=np.int16)
+        _lib.check(self.lib.conan_tone_table(M, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def tones(self, wav, lens=None, cfg=None, seed=None, hop_size=None, return_state=False, **kw):
+        """conan_tones: the DTMF detector (include/conan_hip.h, conan_tone_cfg) on whole signals at 50 * hop Hz, one launch.  wav [n, N]
+        (or [N]) float32; a 2-D view whose rows are contiguous keeps its row stride.  lens: per row the samples to read (default N).
+        cfg: an _lib.ToneCfg, or **kw: _lib.tone_cfg's keywords.  seed: uint8 [n, 48] (cuda) rows of conan_tone_state the rows start
+        from (tones(return_state=True)'s second form below), None: the cfg's seed; a row's first frame has index seed.frames, so a
+        signal cut at frame boundaries and chained through the state gives the whole signal's rows.  -> (digit, sound, level) int32
+        [n, F] with F = the longest row's ceil(len / hop) frames, -1 / -1 / 0 behind a shorter row's frames; with return_state=True
+        also (states, rows): a list of dict(cand, run, cur, miss, held, sound, level, events, frames) (synchronises) and the same
+        states as uint8 [n, 48].  _lib.tone_events(digit) lists the key presses.  It is what a wav-in slot with Streams.set_tones
+        detects, bit for bit."""
+        dev = torch.device("cuda", self.device)
+        hop = int(hop_size or self.hop)
+        c = cfg if cfg is not None else _lib.tone_cfg(**dict(dict(hop=hop), **kw))
+        v = wav.to(dev, torch.float32)
+        if v.dim() == 1:
+            v = v[None]
+        if v.dim() != 2:
+            raise ValueError(f"tones: wav must be [n, N] or [N], got {tuple(wav.shape)}")
+        n, N = v.shape
+        if not (v.stride(1) == 1 and v.stride(0) >= N) and n * N:
+            v = v.contiguous()
+        ld = v.stride(0) if n > 1 else max(N, 1)
+        sm = np.full(n, N, dtype=np.int64) if lens is None else np.ascontiguousarray(np.asarray(lens, dtype=np.int64).reshape(n))
+        if sm.min(initial=0) < 0 or sm.max(initial=0) > N:
+            raise ValueError(f"tones: lens must be in 0 .. {N}")
+        size = C.sizeof(_lib.ToneState)
+        if seed is not None and (seed.dtype != torch.uint8 or not seed.is_cuda or tuple(seed.shape) != (n, size) or not seed.is_contiguous()):
+            raise ValueError(f"tones: seed must be a contiguous cuda uint8 [{n}, {size}] tensor, as return_state=True returns it")
+        F = max(int((int(sm.max(initial=0)) + hop - 1) // hop), 1)
+        digit = torch.full((n, F), -1, dtype=torch.int32, device=dev)
+        sound = torch.full((n, F), -1, dtype=torch.int32, device=dev)
+        level = torch.zeros(n, F, dtype=torch.int32, device=dev)
+        st = torch.empty(n, size, dtype=torch.uint8, device=dev) if return_state else None
+        frames = np.zeros(n, dtype=np.int64)
+        if n:
+            _lib.check(self.lib.conan_tones(self.h, hop, C.byref(c), _ptr(v), ld, n, sm.ctypes.data_as(C.c_void_p), _ptr(seed), _ptr(digit), _ptr(sound),
+                                            _ptr(level), F, _ptr(st), frames.ctypes.data_as(C.c_void_p), _stream()))
+        if not return_state:
+            return digit, sound, level
+        return digit, sound, level, (_struct_rows(st, _lib.ToneState), st)
+
+    def tone_fill(self, wav, sound, level, cfg=None, start=(0, -1), pos0=0, hop_size=None, out=None, **kw):
+        """conan_tone_fill: the regeneration on whole signals.  wav [..., N] float32 (the audio behind every other in-place stage) with
+        sound [..., >= ceil(N / hop)] and level (int32; Streams.step_wav_tones' or Context.tones'); start = (level, sound) before
+        frame 0; pos0: the utterance index of a row's first sample, one value or one per row -> [..., N].  cfg: an _lib.ToneCfg, or
+        **kw: _lib.tone_cfg's keywords (gain is read).  A 2-D operand whose rows are contiguous keeps its row stride; out=wav fills in
+        place.  Frames with level 0 at both ends keep wav's bits.  It is what a wav-in slot with Streams.set_tones (mode 2) puts out,
+        bit for bit."""
+        dev = torch.device("cuda", self.device)
+        hop = int(hop_size or self.hop)
+        c = cfg if cfg is not None else _lib.tone_cfg(**dict(dict(hop=hop), **kw))
+
+        def rows(t, dtype):
+            t = t.to(dev, dtype)
+            if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
+                return t, t.stride(0)
+            t = t.contiguous()
+            return t, t.shape[-1]
+
+        x, x_ld = rows(wav, torch.float32)
+        sd, sd_ld = rows(sound, torch.int32)
+        lv, lv_ld = rows(level, torch.int32)
+        lead, N = x.shape[:-1], x.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        if sd.shape[:-1] != lead or lv.shape != sd.shape:
+            raise ValueError(f"tone_fill: wav {tuple(x.shape)}, sound {tuple(sd.shape)} and level {tuple(lv.shape)} do not match")
+        if sd_ld != lv_ld:
+            sd, lv = sd.contiguous(), lv.contiguous()
+            sd_ld = lv_ld = sd.shape[-1]
+        ps = np.ascontiguousarray(np.broadcast_to(np.asarray(pos0, dtype=np.int64), (n,)))
+        if out is None:
+            y, y_ld = torch.empty(x.shape, dtype=torch.float32, device=dev), N
+        else:
+            y, y_ld = (out, out.stride(0)) if out.dim() == 2 and out.stride(1) == 1 else (out, N)
+            if y.shape != x.shape or y.dtype != torch.float32 or y.device != dev or not (y.is_contiguous() or (y.dim() == 2 and y.stride(1) == 1 and y_ld >= N)):
+                raise ValueError("tone_fill: out must be a float32 tensor of wav's shape on the device, contiguous or a 2-D view with contiguous rows")
+        _lib.check(self.lib.conan_tone_fill(self.h, hop, C.byref(c), _ptr(x), x_ld, n, N, ps.ctypes.data_as(C.c_void_p), _ptr(sd), _ptr(lv), sd_ld,
+                                            int(start[0]), int(start[1]), _ptr(y), y_ld, _stream()))
+        return y
+
     def register_of(self, wav, **f0_keywords):
         """The register of wav [n, N] (or [N]) at the model rate: per row the mean log2 Hz of its voiced frames - Context.f0 followed
         by the measurement of f0_register - or None for a row without a counted frame.  **f0_keywords: Context.f0's."""
@@ -1272,6 +1360,37 @@ class Streams:
         in call order; rows without the feature (or without a detector), rows that emitted nothing and entries past a row's emitted
         frames are 0.  _lib.comfort_dbov turns a level into the RFC 3389 noise level byte."""
         return self._last_rows("comfort", 1)[0]
+
+    def set_tones(self, slots, cfg=True, **kw):
+        """conan_streams_set_tones: a DTMF detector on the slots' own input (wav-in steps only), on the audio the activity detector
+        reads, one more launch per call; regenerate=True (mode 2, the default) also replaces the slots' output, while a digit is
+        confirmed, by a tone pair synthesised from a table, behind every other in-place stage and in front of the output resampler
+        and encoder, so that a DTMF receiver behind the engine hears the key; regenerate=False (mode 1) only detects.  Nothing of the
+        source audio passes.  **kw / a dict in cfg: _lib.tone_cfg's keywords (level_db, twist_db, sel, share, on_frames, off_frames,
+        min_frames, ramp_ms, gain, seed=, reseed=); cfg may also be an _lib.ToneCfg; only cfg=None turns it off.  The defaults are
+        choices: talk-off against real speech has not been measured.
+        It may be called at any time (it joins pipelined work); the change takes effect from the next emitted chunk and survives
+        resets.  The state restarts from the seed when a slot is enabled, after reseed=True and at the first chunk after a reset of the
+        front-end; reseed=False on an enabled slot replaces the parameters and keeps the state.  Slot snapshots do not carry it:
+        query tone_state, export, import, then set_tones(seed=state, reseed=True)."""
+        self._set_feature("tones", slots, cfg, kw, dict(hop=self.model_rate // 50))
+
+    def tones(self, slots):
+        """conan_streams_tones: per slot the setting as _lib.tone_keywords reports it (set_tones takes it back), None for a slot
+        without the detector."""
+        return self._get_feature("tones", slots)
+
+    def tone_state(self, slots):
+        """conan_streams_tone_state (joins pipelined work, synchronises): per slot dict(cand, run, cur, miss, held, sound, level, events,
+        frames); a slot whose state is about to restart reports its seed.  A slot without the detector is an error."""
+        return self._feature_state("tones", slots)
+
+    def step_wav_tones(self):
+        """The frame rows the last wav-in call produced (conan_step_wav_tones; joins pipelined work) -> (digit [n, seg], sound [n, seg],
+        level [n, seg]) int32 in call order: the confirmed digit of each frame (-1: none; _lib.TONE_KEYS[d] is its key and
+        _lib.tone_events lists the presses), the pair the regeneration sounds and its level.  Rows without the detector, rows that
+        emitted nothing and entries past a row's emitted frames are 0."""
+        return self._last_rows("tones", 3)
 
     def step_wav_contour(self):
         """The contour the last wav-in call handed the decoder (conan_step_wav_contour; joins pipelined work) -> (f0 [n, seg] log2 Hz,

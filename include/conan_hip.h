@@ -1581,6 +1581,142 @@ int64_t conan_watermark_state_bytes(void);
  * CONAN_ERR_STATE. */
 int conan_streams_watermark_state(conan_streams* s, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream);
 
+/* Signalling tones (added within ABI 9: a caller detects it by the symbol conan_streams_set_tones; no existing struct or call changes).
+ * A DTMF key press in a slot's source goes through mel, Emformer, decoder and vocoder like any other sound and leaves as something no
+ * DTMF receiver accepts.  A slot with this feature detects the sixteen tone pairs in its own input (mode 1: the host learns the keys
+ * and can send them as RFC 4733 events) and - mode 2 - replaces its output, while a digit is confirmed, by a tone pair synthesised
+ * from a table: what a media gateway does when it plays out such an event.  Nothing of the source audio reaches the output through
+ * this feature.  The law (tests/tone_ref.py restates it in numpy with Python integers) is integer sums - associative, so no order of
+ * lanes, waves or tiles is part of it - and for the regeneration single correctly rounded IEEE operations; nothing has a tolerance.
+ * With M the model's sample rate and hop = M / 50 (20 ms frames, as conan_activity requires):
+ *   Table.  W[m] = rint(2^14 * cos(2 pi m / M)), m = 0 .. M - 1, int16, built once on the host in f64 (conan_tone_table exports it).
+ *     M must be a multiple of 4 (a quarter period is M / 4 entries) and hop in 2 .. CONAN_TONE_HOP_MAX = 512, else
+ *     CONAN_ERR_UNSUPPORTED: the int64 bounds below hold up to hop = 1024, and the table (2 M bytes) with a workgroup's tile staging
+ *     stays inside 64 KB of LDS up to hop = 512, which is the range accepted.  For M = 16000 no 2^14 cos value lies closer than 1e-5
+ *     to a half-integer, so every correctly rounded cos gives the same table.
+ *   Frame.  Tone frame f of a slot's utterance is source samples [f hop, (f + 1) hop) at the model rate: the audio the activity
+ *     detector and the dry path read, behind decoding, the input resampler, concealment and the leveller, in the slot's audio ring;
+ *     zero at and beyond the samples received.  q[j] = clamp(rint(x[j] * 32768), -32768, 32767) in f32, ties to even: the library's
+ *     s16 value of the sample.
+ *   Sums, over the absolute utterance index j of the frame's samples (frames are phase-continuous):  E = sum q^2, and for each of
+ *     F = 697, 770, 852, 941 (rows 0 .. 3) and 1209, 1336, 1477, 1633 Hz (columns 0 .. 3):
+ *       C = sum q[j] W[(F j) mod M],  S = sum q[j] W[(F j - M / 4) mod M],  c = C >> 16, s = S >> 16 (arithmetic),  P = c^2 + s^2,
+ *     all int64.  |C| <= hop 2^29, |c| <= hop 2^13, P <= hop^2 2^27 and E <= hop 2^30 (at hop = 320: |c| <= 2.7e6, P <= 1.5e13).
+ *   Frame digit.  r = argmax of the four row P, c = argmax of the four column P, the lowest index on a tie.  d = 4 r + c if all of
+ *       P_r >= thr and P_c >= thr;
+ *       P_c 256 <= P_r twist_fwd_q8 and P_r 256 <= P_c twist_rev_q8      (twist);
+ *       P_o sel <= P_peak for the three others o of each group           (selectivity);
+ *       (P_r + P_c) 32 256 >= share_q8 hop E                             (the pair's share of the frame's energy: for a pure pair
+ *                                                                         (P_r + P_c) 2^32 = 2^28 (hop / 2) E, so share_q8 / 256 is
+ *                                                                         the share in 0 .. 1)
+ *     hold, else d = -1.  With twist_*_q8 and sel <= 65535 and share_q8 <= 256 the largest product is P 65535 < hop^2 2^43 <= 2^63 for
+ *     hop <= 1024.  There is no second-harmonic test: 2 * 770 Hz sits 63 Hz from 1477 Hz, which a 20 ms rectangular frame cannot
+ *     separate.  Keys: d = 0 .. 15 is "123A456B789C*0#D"[d].
+ *   Debounce.  State: cand, run, cur, miss, held, sound, level, events, frames.  Per frame, in this order:
+ *       run.      d >= 0 and d == cand: run += 1 (it stops at 2^30); d >= 0 otherwise: cand = d, run = 1; d < 0: cand = -1, run = 0.
+ *       holding.  cur >= 0: held += 1 (it stops at 2^30); miss = d == cur ? 0 : miss + 1 (misses in a row); if miss >= off_frames and
+ *                 held >= min_frames the digit ends: cur = -1, miss = 0, held = 0.
+ *       confirm.  cur < 0 and run >= on_frames: cur = cand, events += 1, held = 0, miss = 0 (a run that was waiting while another
+ *                 digit held takes over in the frame that digit ends).
+ *       digit[f] = cur.   level += clamp((cur >= 0 ? 2^20 : 0) - level, -step, step).
+ *       sound.    cur >= 0: sound = cur; otherwise sound = -1 once level == 0.  sound[f] = sound, level[f] = level, frames += 1.
+ *     sound[f] = -1 exactly where cur < 0 and level[f] == 0.
+ *   Regeneration (mode 2).  Output sample j of the utterance lies in frame f = j / hop at k = j - f hop.  With level[f - 1] and
+ *     level[f] the levels before and after frame f: l = level[f - 1] (hop - 1 - k) + level[f] (k + 1), the gate's interpolation.  The
+ *     frame's pair is g = sound[f] >= 0 ? sound[f] : sound[f - 1] (a frame that ends at level 0 fades the pair it began with), its
+ *     row and column frequencies F_r, F_c.  With y the sample behind every other in-place stage:
+ *       syn = (float)(W[(F_r j - M / 4) mod M] + W[(F_c j - M / 4) mod M]) * kf,  kf = gain * 2^-14 (exact scaling: one f32 product);
+ *       g_t = (float)((double)l / (double)(hop << 20)),  g_y = (float)((double)((hop << 20) - l) / (double)(hop << 20));
+ *       out = l == 0 ? y : fma(syn, g_t, y * g_y)      (one f32 product, one fused multiply-add).
+ *     A frame with both levels 0 keeps y's bits; at l = hop << 20 the output is syn in value, whatever finite y is.
+ *   Restart.  The state restarts from cfg.seed at the slot's first emitted chunk after a reset that includes CONAN_MODEL_FRONTEND,
+ *     after a setter call with reseed = 1 and when a slot that was off is enabled.  A setter call with reseed = 0 on an enabled slot
+ *     replaces mode and parameters and keeps the state.  In a stream j is the utterance's sample index (the front-end's frame
+ *     position), whatever the state's `frames` says; a whole-signal row starts at frame seed.frames.
+ * The defaults of the Python layer (_lib.tone_cfg: -40 dBFS per tone, twist 4 dB / 8 dB, sel 8, share 1/2, 2 frames on, 2 off, 3
+ * held, an unramped level, gain 0.125) are choices: talk-off against real speech has not been measured by anyone. */
+#define CONAN_TONE_HOP_MAX 512
+#define CONAN_TONE_FULL (1 << 20)
+typedef struct conan_tone_state {
+  int32_t cand, run;       /* the current run of equal frame digits: the digit (-1: none) and its length */
+  int32_t cur;             /* the confirmed digit, -1: none */
+  int32_t miss, held;      /* while a digit holds: frames in a row that were not it; frames since it was confirmed */
+  int32_t sound;           /* the pair the regeneration sounds, -1: none */
+  int32_t level;           /* 0 .. 2^20 */
+  int32_t reserved;
+  int64_t events;          /* digits confirmed */
+  int64_t frames;          /* frames seen; a whole-signal row's first frame index */
+} conan_tone_state;        /* 48 bytes */
+typedef struct conan_tone_cfg {
+  int32_t mode;            /* 0: off (other fields ignored) | 1: detect | 2: detect and regenerate */
+  int32_t reseed;          /* 0 | 1: the state restarts from the seed */
+  int64_t thr;             /* 0 .. 2^62: the least P of a tone */
+  int32_t twist_fwd_q8;    /* 256 .. 65535: the column tone may exceed the row tone by this ratio of powers, in 1/256 */
+  int32_t twist_rev_q8;    /* 256 .. 65535: the row tone over the column tone */
+  int32_t sel;             /* 1 .. 65535 */
+  int32_t share_q8;        /* 0 .. 256 */
+  int32_t on_frames;       /* 1 .. 2^20 */
+  int32_t off_frames;      /* 1 .. 2^20 */
+  int32_t min_frames;      /* 0 .. 2^20 */
+  int32_t step;            /* 1 .. 2^20: levels per 20 ms frame */
+  float gain;              /* 0 .. 0.5: each tone's amplitude (the pair's peak is twice that) */
+  int32_t reserved;
+  conan_tone_state seed;   /* cand, cur, sound in -1 .. 15; run, miss, held in 0 .. 2^30; level in 0 .. 2^20; events, frames in 0 .. 2^40 */
+} conan_tone_cfg;          /* 104 bytes */
+/* Host only: the table of `sample_rate` -> table_out[sample_rate] (CONAN_ERR_UNSUPPORTED: a rate that is not 50 * hop with hop in
+ * 2 .. 512, or not a multiple of 4). */
+int conan_tone_table(int sample_rate, int16_t* table_out);
+/* The detector on whole signals, and the bit-exact yardstick of the streaming one: row i of wav_dev (n rows in 1 .. 65535, row stride
+ * ld floats) holds samples[i] samples (host array; 0 .. ld) at 50 * hop Hz and has ceil(samples[i] / hop) frames, the last one zero
+ * beyond the samples -> digit_dev[i][f], sound_dev[i][f], level_dev[i][f] (int32, row stride out_ld >= the longest row's frames;
+ * nothing is written behind a row's frames), the state after the row -> state_out_dev[i] (may be null) and frames_out[i] (host, may
+ * be null).  Row i starts from seed_dev[i] (device; null: from cfg->seed), at frame index seed.frames: a signal cut into calls at
+ * frame boundaries and chained through the state gives the whole signal's rows.  cfg->mode must be 1 or 2.  One launch
+ * (cnk::tone_kernel) on `stream`. */
+int conan_tones(conan_ctx* ctx, int hop, const conan_tone_cfg* cfg, const float* wav_dev, int64_t ld, int n, const int64_t* samples,
+                const conan_tone_state* seed_dev, int32_t* digit_dev, int32_t* sound_dev, int32_t* level_dev, int64_t out_ld,
+                conan_tone_state* state_out_dev, int64_t* frames_out, void* stream);
+/* The regeneration on whole signals, and the bit-exact yardstick of the streaming one: row i of wav_dev (n rows in 1 .. 65535 of
+ * `samples` samples, row stride ld) with sound_dev[i][f] and level_dev[i][f] after frame f (int32, -1 .. 15 and 0 .. 2^20, row stride
+ * lvl_ld >= ceil(samples / hop)) and start_level / start_sound as the values before frame 0 -> out_dev (row stride out_ld; may equal
+ * wav_dev with out_ld = ld).  Sample s of row i is utterance sample pos0[i] + s (host array, each in 0 .. 2^62; null: 0); frames
+ * count from the row's first sample.  Of cfg only gain is read.  A last frame that the samples cover only partly is filled over the
+ * part they cover.  One launch (cnk::tone_fill_kernel) on `stream`. */
+int conan_tone_fill(conan_ctx* ctx, int hop, const conan_tone_cfg* cfg, const float* wav_dev, int64_t ld, int n, int64_t samples, const int64_t* pos0,
+                    const int32_t* sound_dev, const int32_t* level_dev, int64_t lvl_ld, int32_t start_level, int32_t start_sound, float* out_dev,
+                    int64_t out_ld, void* stream);
+/* Sets (cfg->mode = 1 | 2) or removes (0) the feature for `slots`.  Every argument is checked before anything changes
+ * (CONAN_ERR_INVALID: a field outside its range; CONAN_ERR_UNSUPPORTED: the model's hop or rate outside the table's range), a
+ * stream-set without the streaming front-end is CONAN_ERR_STATE, and pending pipelined work is joined; it may be called at any time,
+ * also mid-utterance.  The change takes effect from the next emitted chunk and persists across resets.
+ * What a slot with the feature does.  Every conan_step_wav[_async] / conan_step_wav_ragged[_ld][_async] call that emits a chunk for
+ * it runs ONE more launch (cnk::tone_kernel, behind the front-end launch, beside the activity detector's) over the chunk's frames, read
+ * from the slot's audio ring.  The ring requirement is the dry path's: a chunk whose samples had left the ring would make the call
+ * CONAN_ERR_UNSUPPORTED before anything changes, but no call reaches that today - a call that is not final takes at most
+ * segment * hop samples, so an emitted chunk begins at most (segment + right context - 1) * hop + fft_size / 2 + segment * hop
+ * samples behind the samples received, 3840 at the largest front-end accepted, and the ring holds 4096.  The check guards a later
+ * change of either figure and is not a condition a caller has to handle.  In mode 2 the chunk's vocoder step regenerates in place on the rows conv_post wrote, behind the gate, the mix, the comfort fill and the
+ * watermark, as the last in-place stage in front of the output resampler and the format encoder - the pair leaves clean at the slot's
+ * own rate and format, flush included, and the mark's state advances as it did before: ONE more launch (cnk::tone_fill_kernel) per
+ * vocoder step in which a mode-2 row takes part; rows of other slots and frames with level 0 at both ends keep their bits.  The
+ * mel-in steps (conan_step[_async]) and conan_hifigan_step* take no waveform: they neither detect nor fill.
+ * Memory: the first enabling call allocates 48 bytes of state per slot, 8 staging sets of 3 * segment + 2 int32 per slot and 8 row
+ * tables; conan_streams_state_bytes counts them from then on (the table belongs to the context: one copy per rate, built on first
+ * use).  A stream-set that never calls the setter allocates nothing and runs exactly the launches it ran before.
+ * Snapshots carry neither the setting nor the state (the 256-byte host record is full); conan_streams_layout_id and
+ * conan_streams_snapshot_bytes do not change.  The hand-over: conan_streams_tone_state, export, import, then this setter with
+ * seed = the queried state and reseed = 1. */
+int conan_streams_set_tones(conan_streams* s, const int32_t* slots, int n, const conan_tone_cfg* cfg, void* stream);
+/* Host only: the tone cfg of `slot` as set, reseed = 0 (mode = 0 and zeros for a slot without one). */
+int conan_streams_tones(const conan_streams* s, int slot, conan_tone_cfg* cfg_out);
+/* The states of `slots` -> state_dev[n], in the order of `stream` behind a join of pipelined work; a slot whose state is about to
+ * restart reports its seed.  A slot without the feature is CONAN_ERR_STATE. */
+int conan_streams_tone_state(conan_streams* s, const int32_t* slots, int n, conan_tone_state* state_dev, void* stream);
+/* The frame rows the last wav-in call produced, in call order (joins first): digit_dev[n][seg], sound_dev[n][seg] and
+ * level_dev[n][seg], int32.  Rows without the feature, rows that emitted nothing and positions behind the emitted frames read zero
+ * (a digit row of a slot with the feature reads -1 where no digit holds).  CONAN_ERR_STATE before any wav-in call. */
+int conan_step_wav_tones(conan_streams* s, int32_t* digit_dev, int32_t* sound_dev, int32_t* level_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
