@@ -166,6 +166,9 @@ _PROTOS = {
     "conan_tone_fill": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                   C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_step_wav_tones": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_eq_design": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    "conan_eq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_eq_state_bytes": (C.c_int64, []),
     "conan_conceal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_trim_silence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
@@ -797,6 +800,59 @@ def tone_events(digit_rows):
     return out[0] if single else out
 
 
+class EqCfg(C.Structure):
+    """conan_eq_cfg (include/conan_hip.h)."""
+    _fields_ = [("enabled", C.c_int32), ("sections", C.c_int32), ("origin", C.c_int64), ("pos", C.c_int64), ("coef", (C.c_double * 5) * 4),
+                ("reserved", C.c_int32 * 4)]
+
+
+class EqState(C.Structure):
+    """conan_eq_state (include/conan_hip.h)."""
+    _fields_ = [("origin", C.c_int64), ("pos", C.c_int64), ("carry", (C.c_double * 2) * 4), ("tail", C.c_float * 128)]
+
+
+EQ_MAX_SECTIONS, EQ_SEG, EQ_MAX_COEF = 4, 128, 65536.0
+EQ_KINDS = {"lowpass": 0, "highpass": 1, "bandpass": 2, "notch": 3, "peak": 4, "lowshelf": 5, "highshelf": 6, "dcblock": 7, "deemphasis": 8}
+
+
+def eq_section(kind, rate, f, q=0.7071067811865476, gain_db=0.0):
+    """conan_eq_design, the one implementation of the design formulas: the section {b0, b1, b2, a1, a2} / a0 of `kind` (a key of
+    EQ_KINDS) at `rate` Hz with corner or centre f, quality q and - peak and shelves - gain_db, as a tuple of five floats.  Host
+    only: no device is needed."""
+    if kind not in EQ_KINDS:
+        raise ValueError("eq section kind must be one of %s, got %r" % (sorted(EQ_KINDS), kind))
+    out = (C.c_double * 5)()
+    check(lib().conan_eq_design(EQ_KINDS[kind], float(rate), float(f), float(q), float(gain_db), out))
+    return tuple(float(v) for v in out)
+
+
+def eq_cfg(sections=None, rate=None, origin=0, pos=None):
+    """An enabled conan_eq_cfg of 1 .. 4 sections.  A section is a raw 5-tuple (b0, b1, b2, a1, a2), normalised by a0 and taken as
+    given, or a dict(kind=, f=, q=, gain_db=) that eq_section designs at `rate` Hz (the rate of the audio the cascade filters: a
+    slot's model rate).  origin / pos: the grid's origin and the position of the first sample, for a row that continues a seed
+    record (pos defaults to origin: a row that starts from zero).  Any example cascade is a choice: nobody has listened to one."""
+    secs = list(sections or ())
+    if not 1 <= len(secs) <= EQ_MAX_SECTIONS:
+        raise ValueError(f"eq_cfg: 1 .. {EQ_MAX_SECTIONS} sections, got {len(secs)}")
+    c = EqCfg()
+    c.enabled, c.sections, c.origin, c.pos = 1, len(secs), int(origin), int(origin if pos is None else pos)
+    for k, sec in enumerate(secs):
+        if isinstance(sec, dict):
+            if rate is None:
+                raise ValueError("eq_cfg: a section given as a dict needs the rate of the audio it filters")
+            sec = eq_section(rate=rate, **sec)
+        if len(sec) != 5:
+            raise ValueError("eq_cfg: a raw section is (b0, b1, b2, a1, a2)")
+        for i, v in enumerate(sec):
+            c.coef[k][i] = float(v)
+    return c
+
+
+def eq_keywords(c):
+    """eq_cfg's keywords of an enabled EqCfg, the sections as raw 5-tuples: the form that gives the same bytes back."""
+    return dict(sections=[tuple(float(c.coef[k][i]) for i in range(5)) for k in range(int(c.sections))], origin=int(c.origin), pos=int(c.pos))
+
+
 class SlotFeature(typing.NamedTuple):
     """One per-slot feature of a stream-set, as Streams and the engine read it.  A symbol the library does not have is None."""
     keyword: str                  # the engine's keyword (start_wav, open_slots, ...)
@@ -825,6 +881,8 @@ class SlotFeature(typing.NamedTuple):
 
 # in the order open_slots applies them
 SLOT_FEATURES = {f.keyword: f for f in (
+    SlotFeature("eq", "the equaliser", EqCfg, "enabled", eq_cfg, eq_keywords, "conan_streams_set_input_eq", "conan_streams_input_eq",
+                seed_state="conan_streams_input_eq_state", seed_bytes="conan_eq_state_bytes"),
     SlotFeature("level", "the leveller", LevelCfg, "enabled", level_cfg, level_keywords, "conan_streams_set_input_level",
                 state="conan_streams_input_level", rows=("float64", 4), meta="conan_slot_meta_level", stream=False, release=False,
                 mirror="input_levels"),
@@ -846,6 +904,8 @@ SLOT_FEATURES = {f.keyword: f for f in (
                 "conan_streams_comfort", "conan_streams_comfort_state", ComfortState, last="conan_step_wav_comfort"),
     SlotFeature("tones", "the tone detector", ToneCfg, "mode", tone_cfg, tone_keywords, "conan_streams_set_tones", "conan_streams_tones",
                 "conan_streams_tone_state", ToneState, last="conan_step_wav_tones"),
+    SlotFeature("out_eq", "the equaliser", EqCfg, "enabled", eq_cfg, eq_keywords, "conan_streams_set_output_eq", "conan_streams_output_eq",
+                seed_state="conan_streams_output_eq_state", seed_bytes="conan_eq_state_bytes"),
     SlotFeature("out_level", "the leveller", LevelCfg, "enabled", level_cfg, level_keywords, "conan_streams_set_output_level",
                 "conan_streams_output_level_cfg", "conan_streams_output_level", ("float64", 4), "conan_streams_output_level_state",
                 "conan_streams_output_level_state_bytes", release=False, mirror="output_levels"),

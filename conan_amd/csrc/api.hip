@@ -334,6 +334,7 @@ int conan_streams_reset(conan_streams* s, const int32_t* slots, int n, int which
       // the output rate stays; the output resampler restarts (output index 0, inputs before the first are zero: the ring needs no clearing)
       for (int i = 0; i < n; ++i) s->wav_out.voc_samples[slots[i]] = 0;
       s->wm.restart(slots, n);      // the watermark's setting stays; its state restarts in the slots' next step rows
+      s->out_eq.restart(slots, n);  // ... and the output equaliser's
       if (!s->wav_out.or_slot.empty())
         for (int i = 0; i < n; ++i) { conan_streams::OrSlot& o = s->wav_out.or_slot[slots[i]]; o.out = 0; o.flushed = 0; }
     }
@@ -1061,6 +1062,45 @@ int conan_streams_tone_state(conan_streams* s, const int32_t* slots, int n, cona
 
 int conan_step_wav_tones(conan_streams* s, int32_t* digit_dev, int32_t* sound_dev, int32_t* level_dev, void* stream) {
   return guarded([&] { tone::last_call(s, digit_dev, sound_dev, level_dev, stream); });
+}
+
+// ---- equaliser (eq.hip): conan_eq_design, conan_eq, conan_eq_state_bytes, conan_streams_set_input_eq / _set_output_eq and their getters and
+// state queries
+int conan_eq_design(int kind, double rate, double f0, double q, double gain_db, double out[5]) {
+  try {      // (host only, and no launch to answer for: it also runs where no device is)
+    eq::design(kind, rate, f0, q, gain_db, out);
+    return CONAN_OK;
+  } catch (const ch::Error& e) {
+    g_err = e.what();
+    return e.code;
+  }
+}
+
+int conan_eq(conan_ctx* ctx, const conan_eq_cfg* cfg, const float* x_dev, int64_t x_ld, int n, const int64_t* samples, float* y_dev, int64_t y_ld,
+             conan_eq_state* state_out_dev, const conan_eq_state* seed_dev, void* stream) {
+  return guarded([&] { eq::whole(ctx, cfg, x_dev, x_ld, n, samples, y_dev, y_ld, state_out_dev, seed_dev, stream); });
+}
+
+int64_t conan_eq_state_bytes(void) { return (int64_t)sizeof(conan_eq_state); }
+
+int conan_streams_set_input_eq(conan_streams* s, const int32_t* slots, int n, const conan_eq_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream) {
+  return guarded([&] { eq::set_eq(s, false, slots, n, cfg, seed_dev, seed_ld, stream); });
+}
+
+int conan_streams_input_eq(const conan_streams* s, int slot, conan_eq_cfg* cfg_out) { return guarded([&] { eq::get_eq(s, false, slot, cfg_out); }); }
+
+int conan_streams_input_eq_state(conan_streams* s, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream) {
+  return guarded([&] { eq::state(s, false, slots, n, rows_dev, ld, stream); });
+}
+
+int conan_streams_set_output_eq(conan_streams* s, const int32_t* slots, int n, const conan_eq_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream) {
+  return guarded([&] { eq::set_eq(s, true, slots, n, cfg, seed_dev, seed_ld, stream); });
+}
+
+int conan_streams_output_eq(const conan_streams* s, int slot, conan_eq_cfg* cfg_out) { return guarded([&] { eq::get_eq(s, true, slot, cfg_out); }); }
+
+int conan_streams_output_eq_state(conan_streams* s, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream) {
+  return guarded([&] { eq::state(s, true, slots, n, rows_dev, ld, stream); });
 }
 
 int conan_hop_size(const conan_ctx* ctx) { return ctx ? ctx->hop : 0; }

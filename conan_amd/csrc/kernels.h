@@ -1054,6 +1054,71 @@ struct ToneFillArgs {
 constexpr int kToneFillThreads = 256;
 void launch_tone_fill(const ToneFillArgs& a, hipStream_t st);
 
+// ---- equaliser (eq.hip, eq_dev.h; include/conan_hip.h, conan_eq_cfg): a cascade of up to kEqMaxSec biquad sections in f64, every
+// product and sum rounded on its own.  A row's stream is cut into segments of kEqSeg samples from its origin; eq_chunk (eq_dev.h) is
+// the one copy of the section passes: per section a zero-state pass over the chunk's complete segments (one lane each), a scan with
+// the section's transition matrix from the carried state, and an output pass from every segment's start state that overwrites the
+// LDS buffer for the next section.  An incomplete last segment is emitted from its start state and its inputs stay in the state's
+// tail; the call that completes it runs it again and emits the new samples only.  One workgroup of kEqThreads per row.
+constexpr int kEqSeg = 128;                      // samples per segment: a constant of the law (tests/eq_ref.py, SEG)
+constexpr int kEqStride = kEqSeg + 1;            // LDS doubles between two lanes' segments: lane l, step t on bank pair (l + t) mod 32
+constexpr int kEqSegs = 16;                      // LDS segments of a chunk: pending tail + the call's samples
+constexpr int kEqMaxCall = (kEqSegs - 1) * kEqSeg;      // 1920: the samples one chunk takes
+constexpr int kEqMaxSec = 4;
+constexpr int kEqThreads = 256;
+struct EqSec { double b0, b1, b2, a1, a2; double M[4]; };      // M: row-major 2x2 transition matrix of kEqSeg zero inputs
+struct EqState {                                 // conan_eq_state
+  long long origin, pos;                         // the grid's first sample; the samples filtered so far (both utterance indices)
+  double carry[kEqMaxSec][2];                    // per section: the state at the start of the segment that holds `pos`
+  float tail[kEqSeg];                            // that segment's inputs so far (behind the non-finite rule): (pos - origin) % kEqSeg entries, zeros behind
+};
+static_assert(sizeof(EqState) == 16 + 64 + 4 * kEqSeg && sizeof(EqState) % 16 == 0, "EqState is sized in include/conan_hip.h");
+struct EqCall {                                  // one chunk's plan, built by the host (or by the whole-signal kernel's lane 0): never read from the state
+  long long origin, pos0;                        // the chunk's first sample is utterance sample pos0
+  int m, tail;                                   // new samples (0 .. kEqMaxCall); pending samples in front of them ((pos0 - origin) % kEqSeg)
+  int fresh, nsec;                               // fresh: the carries count as zero (tail is 0 then)
+};
+struct EqSigRow { long long samples; };
+struct EqSignalArgs {
+  const float* x; long long x_ld;
+  float* y; long long y_ld;                      // may be x
+  const EqSigRow* rows; int n;
+  const EqState* seed;                           // [n]; may be null: every row starts from zero at origin
+  EqState* state_out;                            // [n]; may be null (then the rows' states live in `work`)
+  EqState* work;                                 // [n] scratch states when state_out is null
+  long long origin, pos0;                        // of every row
+  int nsec;
+  EqSec sec[kEqMaxSec];
+};
+void launch_eq_signal(const EqSignalArgs& a, hipStream_t st);
+// The streaming forms (conan_streams_set_input_eq / _output_eq): a slot's state is state[slot] and its sections sec[slot * kEqMaxSec + k],
+// both written by eq_set_kernel in stream order.
+//   eq_stream_kernel: one workgroup per table row; row R filters R.c.m samples x + R.row * x_ld -> y + R.row * y_ld (y may be x) through
+//     eq_chunk; on = 0: a row that holds its place; copy = 1: an unfiltered row on its way to the staging the front-end reads.
+//   eq_set_kernel: one workgroup per listed slot.  mode 0: the zero state at c.pos0; mode 1, the live change: the c.tail pending samples
+//     are closed with the OLD sections (the carries advance over them by the direct recursion through the c.nsec old sections), the
+//     origin moves to c.pos0, the first `keep` sections keep their carries and the others start at zero; mode 2: seed row R.row
+//     becomes the state.  Then the new sections - the kEqMaxSec EqSec records behind the table's n rows - become the slot's.
+//   eq_state_kernel: row R -> out + R.row * ld bytes: the slot's record, or (mode 0: a slot about to restart) the zero record at c.pos0.
+struct EqRow {                                   // uploaded through PinRing
+  EqCall c;
+  int slot, row, on, copy;
+  int mode, keep, pad_[2];
+};
+static_assert(sizeof(EqRow) == 64 && sizeof(EqCall) == 32, "EqRow is uploaded as 16 ints");
+constexpr int kEqSecRows = (int)((kEqMaxSec * sizeof(EqSec) + sizeof(EqRow) - 1) / sizeof(EqRow));      // table rows the setter's sections take
+struct EqStreamArgs {
+  const float* x; long long x_ld;
+  float* y; long long y_ld;
+  EqState* state; const EqSec* sec;
+  const EqRow* rows; int n;
+};
+void launch_eq_stream(const EqStreamArgs& a, hipStream_t st);
+struct EqSetArgs { EqState* state; EqSec* sec; const EqRow* rows; int n; const char* seed; long long seed_ld; };
+void launch_eq_set(const EqSetArgs& a, hipStream_t st);
+struct EqStateArgs { const EqState* state; const EqRow* rows; int n; char* out; long long ld; };
+void launch_eq_state(const EqStateArgs& a, hipStream_t st);
+
 // ---- style pass (per utterance) helpers
 struct RowMaskArgs { TRef x; TRef m; const int* lens; int T, n, C; int mode; };  // mode 0: sum|x|>0, 1: x[0]!=0
 void launch_rowmask(const RowMaskArgs& a, hipStream_t st);

@@ -200,7 +200,7 @@ void input_level(conan_streams* s, const int32_t* slots, int n, double* stats_de
 void WavStage::plan(const conan_streams* s, const WavCall& c) {
   bool any = false;
   for (int i = 0; i < c.n && s->in_lv.n_on > 0; ++i) any = any || (s->in_lv.on(c.slots[i]) && c.samples[i] > 0);
-  stages = any && !c.rs_launch;
+  stages = any && !c.rs_launch && !c.pre_staged;
   for (int i = 0; i < c.n && any; ++i) {
     const bool on = s->in_lv.on(c.slots[i]);
     if (c.samples[i] < 1 || (!on && !stages)) continue;

@@ -349,7 +349,7 @@ struct conan_streams {
   } dn;
   void denoise_init();
   // a reset with CONAN_MODEL_FRONTEND: the settings stay; the states restart in the slots' next rows (host flags: no launch)
-  void restart_features(const int32_t* slots, int n) { reg.restart(slots, n); act.restart(slots, n); byp.restart(slots, n); cmf.restart(slots, n); conc.restart(slots, n); dn.restart(slots, n); tn.restart(slots, n); }
+  void restart_features(const int32_t* slots, int n) { reg.restart(slots, n); act.restart(slots, n); byp.restart(slots, n); cmf.restart(slots, n); conc.restart(slots, n); dn.restart(slots, n); tn.restart(slots, n); in_eq.restart(slots, n); }
   void ragged_init();
   void resample_init();        // staging, row tables and the history ring (conan_streams_set_input_rate)
   void rs_stage_init();        // staging and row tables only (conan_streams_set_input_format: no stream state)
@@ -398,6 +398,20 @@ struct conan_streams {
     StageSets<cnk::WmRow, kActSets> sets;
   } wm;
   void watermark_init();
+  // equaliser (conan_streams_set_input_eq / conan_streams_set_output_eq; eq.hip), a SlotSetting on each side.  state: [max_slots]
+  // records of conan_eq_state; sec: [max_slots][kEqMaxSec] sections with their transition matrices, written by the setter's launch in
+  // stream order; origin: per slot the grid's first sample as the host knows it (the kernels take every index from the call rows).
+  // pending restarts the state in the slot's next row, at that row's position (a reset with CONAN_MODEL_FRONTEND / CONAN_MODEL_HIFIGAN).
+  // Source side: position = fe_slot.recv, rows: the filtered call rows with samples (and copy rows, see eq::WavStage), event behind the
+  // launch.  Output side: position = voc_samples, one row per step row (on = 0: a slot without the feature), event behind the launch.
+  // Allocated by a side's first enabling call; state, sections and row tables count as stream state.
+  struct Eq : SlotSetting<conan_eq_cfg> {
+    cnk::EqState* state = nullptr;
+    cnk::EqSec* sec = nullptr;
+    std::vector<long long> origin;
+    StageSets<cnk::EqRow, kActSets> sets;
+  } in_eq, out_eq;
+  void eq_init(Eq& e);
   void out_stage_init();
   void out_ring_init();        // the output resampler's history ring (conan_streams_set_output_rate with a real rate)
   // --- slot snapshots (snapshot.hip).  rings: every ring of mk_ring in creation order with its position counter (0 pos_emf,
@@ -448,6 +462,9 @@ struct conan_streams {
     // tone table and of its sound and level staging; hifigan_step launches tone_fill_kernel behind the watermark, as the last
     // in-place stage in front of the output resampler
     struct Tone { const cnk::ToneRow* tab = nullptr; const int* sound = nullptr; const int* level = nullptr; int lvl_ld = 0; } tone;
+    // the step's equaliser (eq.hip; out_plan's, for a step with a filtered row): one table row per step row; hifigan_step launches
+    // eq_stream_kernel directly behind conv_post, in front of the output leveller's ramp
+    std::vector<cnk::EqRow> eq_rows;
   };
   OutPlan out_plan(const int32_t* slots, int n, int frames, float* wav_out_dev, long long natural_ld, const std::vector<int>* dst, const std::string& who) const;
   // the plan's resample_out_kernel launch behind or_sets.begin() = q, then the set's event; src_ld: stride of the staged rows (a flush: 0)
@@ -695,6 +712,7 @@ struct WavCall {
   bool rs_launch; const int32_t* samples;      // the resampler's plan: it launches in this call; per row the samples the front-end gets
   bool common; const float* wav_dev; long long wav_ld;
   int rs_q = 0;
+  bool pre_staged = false;      // the equaliser writes the staging in this call: a leveller behind it works in place, as behind a resampler launch
   template <typename F> void each_group(F&& f) const {      // f(g, the group's first chunk row)
     for (int g = 0, off = 0; g < (int)groups.size(); off += (int)groups[g].size(), ++g) f(g, off);
   }
@@ -715,7 +733,7 @@ struct WavCall {
 };
 // The front-end work of a wav-in call: at most one entry per position, run in this order on one stream (the caller's, or as
 // step_pipelined's `pre`).  The ...End entries record the events of the sets the mel front-end launch is the last to read.
-enum FrontPos { kFrResample, kFrLevel, kFrMel, kFrDenoise, kFrLevelEnd, kFrResampleEnd, kFrF0, kFrRegister, kFrActivity, kFrBypass, kFrComfort, kFrTones, kFrCount };
+enum FrontPos { kFrResample, kFrEq, kFrLevel, kFrMel, kFrDenoise, kFrLevelEnd, kFrResampleEnd, kFrF0, kFrRegister, kFrActivity, kFrBypass, kFrComfort, kFrTones, kFrCount };
 struct FrontWork {
   std::function<void(hipStream_t)> at[kFrCount];
   void run(hipStream_t st) const { for (const auto& f : at) if (f) f(st); }
@@ -1025,6 +1043,34 @@ void decide(const int64_t* score, const int64_t* soft, const conan_watermark_hit
 void set_watermark(conan_streams* s, const int32_t* slots, int n, const conan_watermark_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream);
 void state(conan_streams* s, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream);
 }  // namespace wmark
+
+// ---- equaliser (eq.hip): the kernel's host side and the bodies of api.hip's entry points
+namespace eq {
+void check_cfg(const conan_eq_cfg& c, const char* who);      // host only
+void sections(const conan_eq_cfg& c, cnk::EqSec* out);       // host only: out[kEqMaxSec], the coefficients and the transition matrices
+void design(int kind, double rate, double f0, double q, double gain_db, double* out);      // host only
+void whole(conan_ctx* ctx, const conan_eq_cfg* cfg, const float* x_dev, int64_t x_ld, int n, const int64_t* samples, float* y_dev, int64_t y_ld,
+           conan_eq_state* state_out_dev, const conan_eq_state* seed_dev, void* stream);
+// the two sides' setters, getters and state queries (output = false: the source side)
+void set_eq(conan_streams* s, bool output, const int32_t* slots, int n, const conan_eq_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream);
+void get_eq(const conan_streams* s, bool output, int slot, conan_eq_cfg* cfg_out);
+void state(conan_streams* s, bool output, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream);
+// the table rows of a vocoder step that gives each of `slots` `frames` frames (empty: no filtered slot among them).  Nothing changes.
+std::vector<cnk::EqRow> step_rows(const conan_streams* s, const int32_t* slots, int n, int frames, const std::string& who);
+// hifigan_step's part: the row table travels ahead of the step's kernels (step_begin -> the set q), the launch sits behind conv_post
+int step_begin(conan_streams* s, const std::vector<cnk::EqRow>& rows, hipStream_t st);
+void step_launch(conan_streams* s, const std::vector<cnk::EqRow>& rows, int q, float* wav, long long ld, hipStream_t st);
+// The filtered slots that hand their front-end samples this call, in front of the leveller.  Behind a resampler launch the kernel
+// works in place on the staged rows; in a call without one (stages) it reads the caller's rows and writes the staging itself -
+// step_wav takes the resampler's set for it - and the call's other rows with samples ride along as copy rows.
+struct WavStage {
+  std::vector<cnk::EqRow> rows;
+  bool stages = false;
+  void plan(const conan_streams* s, const WavCall& c);
+  void enqueue(conan_streams* s, const WavCall& c, hipStream_t cst, FrontWork& front, std::vector<conan_streams::OutPlan>& ops);
+  void commit(conan_streams* s, hipStream_t dec, hipStream_t last_st);
+};
+}  // namespace eq
 
 // ---- silence trimming (trim.hip): the kernels' host side and the body of api.hip's entry point
 namespace trim {

@@ -495,6 +495,9 @@ void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float*
   // a step with a levelled row (level_out.hip): its row table travels ahead of the step's kernels too
   const bool levelled = op && !op->lvl_rows.empty();
   const int lq = levelled ? out_lv.sets.begin(op->lvl_rows.data(), n, st) : -1;
+  // ... and a step with a filtered row (eq.hip) likewise
+  const bool filtered = op && !op->eq_rows.empty();
+  const int eq_q = filtered ? eq::step_begin(this, op->eq_rows, st) : -1;
   {  // mel chunk -> ring (conv_pre needs 6 frames of left context)
     cnk::CopyArgs ca; memset(&ca, 0, sizeof(ca));
     ca.x = ch::lin_ref(const_cast<float*>(mel_dev), frames, c.num_mels); ca.y = v_mel.ref();
@@ -623,6 +626,7 @@ void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float*
     // the step's last kernel also advances the per-slot frame counters (one launch less)
     a.adv_pos = pos_voc; a.adv_delta = frames; a.adv_ticket = cp_ticket[ws_index(st)];
     cnk::launch_conv_post(a, st);
+    if (filtered) eq::step_launch(this, op->eq_rows, eq_q, a.wav, T, st);      // the equaliser (eq.hip), in place on the rows just written, in front of the leveller: a boost does not defeat the level it promises
     if (levelled) {      // the output leveller's ramp (level_out.hip), in place on the rows just written, in front of gate, mix and resampler
       cnk::LevelOutApplyArgs l; memset(&l, 0, sizeof(l));
       l.x = a.wav; l.ld = T; l.stage = out_lv.stage[lq]; l.stage_ld = out_lv.filter.U; l.state = out_lv.state; l.state_stride = out_lv.stride;

@@ -294,8 +294,9 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
   }
   // the features' part of the call, each in its own file, in the order of their launches: every plan before anything changes
   WavCall call{slots, n, pl, groups, seg, hop, N, m, who, P.launch, samples, common, wav_dev, wav_ld};
-  level::WavStage lv; f0::WavStage follow; act::WavStage activity; byp::WavStage bypass; comfort::WavStage noise; denoise::WavStage suppress; tone::WavStage tones;
+  eq::WavStage equal; level::WavStage lv; f0::WavStage follow; act::WavStage activity; byp::WavStage bypass; comfort::WavStage noise; denoise::WavStage suppress; tone::WavStage tones;
   bypass.gate_stage = &activity; noise.gate_stage = &activity;
+  equal.plan(s, call); call.pre_staged = equal.stages;
   lv.plan(s, call); follow.plan(s, call); activity.plan(s, call); bypass.plan(s, call); noise.plan(s, call); suppress.plan(s, call); tones.plan(s, call);
   const int nm_in = m.num_mels, nm = c.num_mels;
   int jobs = 0;
@@ -325,7 +326,7 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
   s->wav_out.out_counts.assign(n, 0);      // (rows that emit no frame; hifigan_step fills the others)
   // a ragged call's row table and staging (set q); the resampler's rows and staging (set rs_q), read by the front-end work
   const std::string k = run ? s->ctx->mel_tables(m) : std::string();      // (may throw: before a staging set is taken)
-  const bool staged = P.launch || lv.stages;      // (a leveller alone takes the resampler's set for its staging)
+  const bool staged = P.launch || equal.stages || lv.stages;      // (an equaliser or a leveller alone takes the resampler's set for its staging)
   int q = 0;
   if (!common) {
     s->ragged_init();
@@ -368,7 +369,7 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
     }
   }
   activity.power = noise.take(s, cst);      // (a following comfort row reads the frame powers: the detector stages them in this call)
-  lv.enqueue(s, call, cst, front, ops); follow.enqueue(s, call, cst, front, ops); activity.enqueue(s, call, cst, front, ops); bypass.enqueue(s, call, cst, front, ops);
+  equal.enqueue(s, call, cst, front, ops); lv.enqueue(s, call, cst, front, ops); follow.enqueue(s, call, cst, front, ops); activity.enqueue(s, call, cst, front, ops); bypass.enqueue(s, call, cst, front, ops);
   noise.enqueue(s, call, cst, front, ops); suppress.enqueue(s, call, cst, front, ops); tones.enqueue(s, call, cst, front, ops);
   const std::function<void(hipStream_t)> pre = [&front](hipStream_t st) { front.run(st); }, none;
   cnk::WavScatterArgs sc;
@@ -405,7 +406,7 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
     s->profiled("wav_rows_scatter_kernel", 0.0, cst, [&] { cnk::launch_wav_scatter(sc, cst); });
   }
   if (!common) s->wav_in.rg_sets.end(q, last);
-  lv.commit(s, dec, last); follow.commit(s, dec, last); activity.commit(s, dec, last); bypass.commit(s, dec, last); noise.commit(s, dec, last); suppress.commit(s, dec, last); tones.commit(s, dec, last);
+  equal.commit(s, dec, last); lv.commit(s, dec, last); follow.commit(s, dec, last); activity.commit(s, dec, last); bypass.commit(s, dec, last); noise.commit(s, dec, last); suppress.commit(s, dec, last); tones.commit(s, dec, last);
   if (scatter && !route) {      // (each group's step counted its own rows, in group order: back to the call's rows)
     s->wav_out.out_counts.assign(n, 0);
     for (int i = 0; i < n; ++i) s->wav_out.out_counts[i] = pl[i].emit * hop;
@@ -610,6 +611,7 @@ conan_streams::OutPlan conan_streams::out_plan(const int32_t* slots, int n, int 
   }
   if (!flush) P.lvl_rows = olv::step_rows(this, slots, n, frames, who);      // (checked here, before anything changes: CONAN_ERR_UNSUPPORTED rows)
   if (!flush) P.wm_rows = wmark::step_rows(this, slots, n, frames, who);
+  if (!flush) P.eq_rows = eq::step_rows(this, slots, n, frames, who);
   P.active = any || dst || P.ld != T;
   if (flush) P.active = false;
   if (!P.active && !flush) return P;

@@ -236,6 +236,8 @@ def _accept(keyword, v, k, n, voice):
         if target is None:
             raise ValueError(f"register='voice': voice {int(ids[k])} has no register (VoiceBank.enroll_wav(register=True))")
         return dict(target=target)
+    if keyword in ("eq", "out_eq"):      # (no True: there is no default cascade, and a bare list would read as one value per slot)
+        raise ValueError(f"{keyword}: {v!r} (a dict(sections=[...]) of {_lib.SLOT_FEATURES[keyword].method}'s keywords, a list with one per slot, or None)")
     if v is True:
         return dict(_TRUE[keyword]) if isinstance(_TRUE[keyword], dict) else True
     if keyword == "activity":
@@ -291,7 +293,7 @@ class StreamingVoiceConversionEngine:
             raise ValueError("set_voice: bank= and ids= are required")
         self.st.set_voice(self.slots if slots is None else slots, bank, ids)
 
-    def start(self, ref_mel, ref_len=None, which=7, out_rate=None, out_filter=None, out_format=None, pitch=None, voice=None, out_level=None, watermark=None):
+    def start(self, ref_mel, ref_len=None, which=7, out_rate=None, out_filter=None, out_format=None, pitch=None, voice=None, out_level=None, watermark=None, out_eq=None):
         """voice: (bank, ids) - enrolled voices of a runtime.VoiceBank, one id per slot, in place of ref_mel (then None).
         pitch: the slots' pitch control in the decoder step (Streams.set_pitch) - None / False: none; a dict of its keywords
         (shift_semitones, range, pivot, uv_threshold), or a list with one per slot.
@@ -301,6 +303,10 @@ class StreamingVoiceConversionEngine:
         out_level: the output leveller (Streams.set_output_level) - None / False: none; True: Context.level's defaults; a dict: its
         keywords.  The same causal BS.1770 leveller as start_wav(level=...), on the converted voice: on the GPU between the vocoder
         and the gate, the mix, the output resampler and the encoders, without look-ahead or added latency.
+        out_eq: the output equaliser (Streams.set_output_eq) - None / False: none; a dict(sections=[...]) of 1 .. 4 biquad sections
+        (raw 5-tuples or dict(kind=, f=, q=, gain_db=) designed at the model rate), or a list with one dict per slot.  It runs on the
+        GPU directly behind the vocoder, in front of the output leveller: the returned model-rate wav is ctx.eq of the unfiltered one,
+        bit for bit.  Any cascade is the caller's choice: the library ships no preset, and nobody has listened to one.
         watermark: the output watermark (Streams.set_watermark) - None / False: none; a dict of its keywords (key, id, gain, floor),
         or a list with one per slot; True: the defaults, key 0 and id 0.  The mark goes into the audio on the GPU behind the last
         in-place stage, in front of the output resampler and the encoders: the returned model-rate wav is ctx.watermark_embed of the
@@ -311,7 +317,7 @@ class StreamingVoiceConversionEngine:
             raise ValueError("out_rate / out_format: one value for all slots here (feed / infer return one [B, count] block); open_slots and "
                              "infer_wav_staggered take one per slot / utterance")
         self._check_voice(ref_mel, voice)
-        values = self._host_checks(len(self.slots), pitch=pitch, out_level=out_level, watermark=watermark)
+        values = self._host_checks(len(self.slots), pitch=pitch, out_level=out_level, watermark=watermark, out_eq=out_eq)
         self.st.reset(self.slots, which=which)
         self._reference(self.slots, ref_mel, ref_len, voice)
         self._set_out_rate(self.slots, out_rate, out_filter)
@@ -320,7 +326,7 @@ class StreamingVoiceConversionEngine:
             self._apply(keyword, self.slots, values[keyword])
 
     def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, denoise=None, watermark=None, tones=None, **filter):
+                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
         in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
         in_format: the input's sample format (None: float32; 's16' takes int16 rows, 'ulaw' / 'alaw' uint8), decoded on the GPU.
@@ -348,15 +354,18 @@ class StreamingVoiceConversionEngine:
         log base or floor names it there: natural_log, mel_vmin, eps).  The Emformer then sees the suppressed frames.
         tones: DTMF detection and regeneration (Streams.set_tones) - None / False: none; True: detect and regenerate with the
         defaults; a dict of set_tones's keywords (regenerate=False only detects).  chunk_tones() reads the last call's rows.
+        eq: the source-side equaliser (Streams.set_input_eq) - None / False: none; a dict(sections=[...]) as out_eq's (start).  It
+        filters the decoded, resampled samples in front of the leveller and the front-end: everything that reads the slot's audio
+        sees ctx.eq of the source.
         There is no trim= here: silence trimming (infer_wav(trim=True)) moves audio forward over pauses it has seen whole, and a
         stream cannot drop time it has not heard yet; activity= is what a live call has in its place."""
         self._check_voice(ref_mel, voice)
         if isinstance(in_format, (list, tuple)) or isinstance(level, (list, tuple)):
             raise ValueError("in_format / level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
         values = self._host_checks(len(self.slots), voice, level=level, follow=follow, register=register, activity=activity, bypass=bypass,
-                                   conceal=conceal, comfort=comfort, denoise=denoise, tones=tones)
+                                   conceal=conceal, comfort=comfort, denoise=denoise, tones=tones, eq=eq)
         self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice,
-                   out_level=out_level, watermark=watermark)
+                   out_level=out_level, watermark=watermark, out_eq=out_eq)
         self._set_rate(self.slots, in_rate, filter)
         self._set_format(self.slots, in_format, self.st.input_formats, self.st.set_input_format)
         for keyword in values:      # (pitch and out_level went in with start(), in front of the input rate)
@@ -434,6 +443,18 @@ class StreamingVoiceConversionEngine:
         each [n, seg] int32 in the call's row order; digit is the confirmed key of each 20 ms frame (-1: none) and
         _lib.tone_events(rows) lists the presses a host sends as RFC 4733 events."""
         return self.st.step_wav_tones()
+
+    def set_eq(self, slots=None, cfg=True, seed=None, **kw):
+        """A live change of the slots' source-side equaliser (all slots by default) between feed / feed_ragged calls, also
+        mid-utterance and with pipelined steps in flight: Streams.set_input_eq's arguments (sections=[...]; cfg=None turns it off).
+        An enabled slot's pending tail closes with the old coefficients and the sections keep their state words: the change does
+        not click.  In force from the next call."""
+        self._live("eq", slots, cfg, seed=seed, **kw)
+
+    def set_out_eq(self, slots=None, cfg=True, seed=None, **kw):
+        """A live change of the slots' output equaliser - the tone control - as set_eq: Streams.set_output_eq's arguments.  In force
+        from the next vocoder step."""
+        self._live("out_eq", slots, cfg, seed=seed, **kw)
 
     def set_denoise(self, slots=None, cfg=True, **kw):
         """A live change of the slots' noise suppression (all slots by default) between feed / feed_ragged calls, also mid-utterance
@@ -649,7 +670,7 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
                   out_format=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None, register=None, activity=None,
-                  activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, comfort=None, denoise=None, watermark=None, tones=None, **filter):
+                  activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] (or None with voice = (bank, ids): start) -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
@@ -680,7 +701,7 @@ class StreamingVoiceConversionEngine:
         (start): the returned model-rate wav is ctx.watermark_embed of the unmarked one, bit for bit."""
         self._check_voice(ref_mel, voice)
         self._host_checks(len(self.slots), voice, level=level, pitch=pitch, follow=follow, register=register, activity=activity, bypass=bypass,
-                          conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones)      # (before anything runs)
+                          conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq)      # (before anything runs)
         self._check_lost(lost, conceal, loud_norm, trim)
         trim = self._trim_keywords(trim)
         if trim is not None:
@@ -689,7 +710,7 @@ class StreamingVoiceConversionEngine:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
                        pitch=pitch, voice=voice, follow=follow, register=register, activity=activity, bypass=bypass, out_level=out_level, conceal=conceal,
-                       comfort=comfort, denoise=denoise, watermark=watermark, tones=tones, **filter)
+                       comfort=comfort, denoise=denoise, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -721,7 +742,7 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, denoise=None, watermark=None, tones=None, **filter):
+                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
         rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
@@ -739,7 +760,7 @@ class StreamingVoiceConversionEngine:
         it holds whole)."""
         self._check_voice(ref_mel, voice)
         values = self._host_checks(len(slots), voice, level=level, pitch=pitch, follow=follow, register=register, activity=activity, bypass=bypass,
-                                   conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones)
+                                   conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq)
         self.st.reset(slots, which=7 | 8)
         self._reference(slots, ref_mel, ref_len, voice)
         self._set_out_rate(slots, out_rate, out_filter)
@@ -771,7 +792,7 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
                             in_formats=None, out_formats=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None,
-                            register=None, activity=None, activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, comfort=None, denoise=None, watermark=None, tones=None, **filter):
+                            register=None, activity=None, activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -800,7 +821,7 @@ class StreamingVoiceConversionEngine:
         U = len(src_wavs)
         # (host checks before anything runs; per utterance, in the form open_slots takes back)
         values = self._host_checks(U, voice, ("out_level",), level=level, pitch=pitch, follow=follow, register=register, activity=activity,
-                                   bypass=bypass, conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones)
+                                   bypass=bypass, conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq)
         self._check_lost(lost, conceal, loud_norm, trim)
         if lost is not None and len(lost) != U:
             raise ValueError(f"lost: {len(lost)} values for {U} utterances")
@@ -915,7 +936,7 @@ class StreamingVoiceConversionEngine:
 
     @torch.no_grad()
     def infer(self, src_mel, ref_mel, ref_len=None, pipelined=True, out_rate=None, out_filter=None, out_format=None, pitch=None, voice=None,
-              out_level=None, watermark=None):
+              out_level=None, watermark=None, out_eq=None):
         """src_mel [B,T,80], ref_mel [B,Tr,80] (cuda) -> wav [B, T*hop], mel [B,T,80], codes [B,T].
 
         The whole source is available here, so by default the chunks are issued as pipelined steps
@@ -927,6 +948,9 @@ class StreamingVoiceConversionEngine:
         watermark: the output watermark (start): the returned model-rate wav is ctx.watermark_embed of the unmarked one, bit for bit."""
         self._check_voice(ref_mel, voice)
         if self.ctx.cfg.voc_upsample == 2:
+            if out_eq not in (None, False):
+                raise ValueError("out_eq with an upsample 'nn' vocoder: its steps are whole prefixes, not update intervals; filter the returned wav "
+                                 "with Context.eq instead")
             if watermark not in (None, False):
                 raise ValueError("watermark with an upsample 'nn' vocoder: its steps are whole prefixes, not update intervals; mark the returned wav "
                                  "with Context.watermark_embed instead")
@@ -937,7 +961,7 @@ class StreamingVoiceConversionEngine:
                 raise ValueError("out_format with an upsample 'nn' vocoder: convert the returned wav with Context.convert_samples instead")
             self._set_out_rate(self.slots, out_rate, out_filter)      # (refuses a rate; restores the model rate)
             return self._infer_prefix_vocoder(src_mel, ref_mel, ref_len, pitch, voice)
-        self.start(ref_mel, ref_len, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice, out_level=out_level, watermark=watermark)
+        self.start(ref_mel, ref_len, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice, out_level=out_level, watermark=watermark, out_eq=out_eq)
         B = src_mel.shape[0]
         hop, nm = self.ctx.hop, self.ctx.cfg.num_mels
         wavs, mels, codes = [], [], []

@@ -249,6 +249,47 @@ class Context:
             y = y.reshape(*lead, y.shape[-1])
         return (y, trace.reshape(*lead, K, 2)) if return_trace else y
 
+    def eq(self, x, sections=None, cfg=None, lengths=None, rate=None, seed=None, return_state=False, out=None):
+        """The equaliser on whole signals (conan_eq; include/conan_hip.h, conan_eq_cfg), one launch: x [n, N] (or [N]) float32 -> the
+        rows through a cascade of 1 .. 4 biquad sections in f64.  sections: raw 5-tuples (b0, b1, b2, a1, a2) or dicts
+        (kind=, f=, q=, gain_db=) designed at `rate` Hz (default: the model rate, 50 * hop); or cfg: an _lib.EqCfg.  A 2-D view whose
+        rows are contiguous keeps its row stride.  lengths: samples per row (default N; the floats behind a row's length come back
+        as x's).  seed: uint8 [n, 592] (cuda) rows of conan_eq_state the rows continue from, with the cfg's origin and pos naming
+        their origin and position (eq_cfg(..., origin=, pos=)); None: every row starts from zero.  out: a cuda float32 [n, ld]
+        buffer (it may be x itself: in place).  -> y, and with return_state=True (y, states uint8 [n, 592]): a signal cut anywhere and
+        chained through the state gives the whole signal's bits."""
+        dev = torch.device("cuda", self.device)
+        c = cfg if cfg is not None else _lib.eq_cfg(sections, rate=float(self.hop * 50 if rate is None else rate))
+        v = x.to(dev, torch.float32)
+        one = v.dim() == 1
+        if one:
+            v = v[None]
+        if v.dim() != 2:
+            raise ValueError(f"eq: x must be [n, N] or [N], got {tuple(x.shape)}")
+        n, N = v.shape
+        if not (v.stride(1) == 1 and v.stride(0) >= N) and n * N:
+            v = v.contiguous()
+        x_ld = v.stride(0) if n > 1 else max(N, 1)
+        lens = np.full(n, N, dtype=np.int64) if lengths is None else np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+        if lens.shape[0] != n or lens.min(initial=0) < 0 or lens.max(initial=0) > N:
+            raise ValueError(f"eq: lengths must be {n} values in 0 .. {N}")
+        if out is not None:
+            y = out if out.dim() == 2 else out[None]
+            if not (y.is_cuda and y.dtype == torch.float32 and y.shape[0] == n and y.shape[1] >= N and (y.stride(1) == 1 or y.shape[1] <= 1)):
+                raise ValueError("eq: out must be a cuda float32 [n, >= N] buffer with unit column stride")
+        else:
+            y = v.clone() if lengths is not None else torch.empty(n, N, dtype=torch.float32, device=dev)
+        y_ld = y.stride(0) if n > 1 else max(y.shape[1], 1)
+        size = C.sizeof(_lib.EqState)
+        if seed is not None and (seed.dtype != torch.uint8 or not seed.is_cuda or tuple(seed.shape) != (n, size) or not seed.is_contiguous()):
+            raise ValueError(f"eq: seed must be a contiguous cuda uint8 [{n}, {size}] tensor, as return_state=True returns it")
+        st = torch.empty(n, size, dtype=torch.uint8, device=dev) if return_state else None
+        if n:
+            _lib.check(self.lib.conan_eq(self.h, C.byref(c), _ptr(v), x_ld, n, lens.ctypes.data_as(C.c_void_p), _ptr(y), y_ld, _ptr(st), _ptr(seed), _stream()))
+        if out is None and one:
+            y = y[0]
+        return (y, st) if return_state else y
+
     def f0(self, wav, fmin=50.0, fmax=900.0, threshold=0.15, floor_db=-60.0, fft_size=1024, hop_size=None):
         """The source-pitch tracker on whole signals (conan_f0; include/conan_hip.h, conan_f0_cfg): wav [..., N] float32 at the model
         rate (50 * hop_size; hop_size defaults to the vocoder's hop) -> (f0 [..., 1 + N // hop_size] in log2 Hz, 0 where unvoiced;
@@ -927,7 +968,7 @@ class VoiceBank:
         for i in a:
             self.registers.pop(int(i), None)      # (the id holds another voice now; enroll_wav(register=True) measures it)
 
-    def enroll_wav(self, ids, wav, via=None, sample_rate=None, loud_norm=False, register=False, trim=False, denoise=False, **mel):
+    def enroll_wav(self, ids, wav, via=None, sample_rate=None, loud_norm=False, register=False, trim=False, denoise=False, eq=None, **mel):
         """Context.wav2mel of wav [n, samples] - resampled from sample_rate to the mel front-end's rate, loudness-normalised and
         trimmed first where asked - then enroll.  **mel: wav2mel's keywords.  trim: True, or a dict of Context.trim_silence's
         keywords: the long pauses of each clip are cut out (behind resampling and loud_norm) so that they neither dilute the style
@@ -937,13 +978,17 @@ class VoiceBank:
         (Context.register_of of the same prepared wav, which must then be at the model rate) into the host dict self.registers[id] -
         what register="voice" of the engine's wav-in calls looks up; export / import_voices do not carry it.  denoise: True, or a
         dict of _lib.denoise_cfg's keywords: the noise suppressor (Context.mel_denoise, with the mel's own log base, vmin and eps)
-        runs on each clip's mel, over its own frames, in front of enroll."""
+        runs on each clip's mel, over its own frames, in front of enroll.  eq: a dict(sections=[...]) of _lib.eq_cfg's keywords: the
+        equaliser's whole-signal form (Context.eq, sections designed at the front-end's rate) on each clip behind the resampling and
+        in front of loud_norm - where a wav-in slot's source-side equaliser stands."""
         rate = int(mel.get("sample_rate", 16000))
         wav = wav.to(self.dev, torch.float32)
         if wav.dim() == 1:
             wav = wav[None]
         if sample_rate is not None and int(sample_rate) != rate:
             wav = self.ctx.resample(wav, int(sample_rate), rate)
+        if eq:
+            wav = self.ctx.eq(wav, cfg=_lib.eq_cfg(**dict(dict(rate=float(rate)), **dict(eq))))
         if loud_norm:
             wav = self.ctx.loud_norm(wav, rate)
         ref_len = None
@@ -1483,6 +1528,44 @@ class Streams:
         frames, bins, the noise floor and the attenuation per bin) for set_denoise(seed=) and Context.mel_denoise(seed=).  Joins
         pipelined work."""
         return self._feature_seed_rows("denoise", slots)
+
+    def set_input_eq(self, slots, cfg=True, seed=None, **kw):
+        """conan_streams_set_input_eq: an equaliser on the slots' SOURCE audio (wav-in steps only; include/conan_hip.h, conan_eq_cfg):
+        a cascade of 1 .. 4 biquad sections in f64 on the model-rate samples the front-end is about to read, one more launch per
+        call, in front of the leveller - so the audio ring and everything that reads it see the filtered source.  **kw / a dict in
+        cfg: _lib.eq_cfg's keywords (sections=[...]: raw 5-tuples or dict(kind=, f=, q=, gain_db=) designed at the model rate); cfg
+        may also be an _lib.EqCfg; only cfg=None turns it off.  No cascade is a default: any example is a choice nobody has
+        listened to.  It may be called at any time (it joins pipelined work) and survives resets.  Enabling starts from zero at the
+        current position; changing an enabled slot closes its pending tail with the old coefficients and keeps the sections' state
+        words - the live tone control, no click.  seed: uint8 [n, 592] cuda rows of input_eq_state with origin= and pos= as
+        input_eq reports them: the slot continues that stream.  Slot snapshots do not carry it: query input_eq and input_eq_state,
+        export, import, then set_input_eq(cfg=the keywords, seed=rows)."""
+        self._set_feature("eq", slots, cfg, kw, dict(rate=self.model_rate), seed=seed)
+
+    def input_eq(self, slots):
+        """conan_streams_input_eq: per slot the setting as _lib.eq_keywords reports it - the sections as raw 5-tuples, the grid's
+        origin and the slot's position (set_input_eq takes it back) - None for a slot without the feature."""
+        return self._get_feature("eq", slots)
+
+    def input_eq_state(self, slots):
+        """conan_streams_input_eq_state: uint8 [n, 592] (cuda), the slots' conan_eq_state records (_lib.EqState reads one) for
+        set_input_eq(seed=) and Context.eq(seed=).  Joins pipelined work."""
+        return self._feature_seed_rows("eq", slots)
+
+    def set_output_eq(self, slots, cfg=True, seed=None, **kw):
+        """conan_streams_set_output_eq: the same equaliser on the audio the slots emit - a tone control, a telephone band, a
+        de-emphasis - in place directly behind the vocoder and in front of the output leveller, the gate, the mix, the output
+        resampler and the encoders: one more launch per vocoder step with a filtered row, in every step entry point.  Arguments,
+        live changes, seed and hand-over as set_input_eq (output_eq, output_eq_state)."""
+        self._set_feature("out_eq", slots, cfg, kw, dict(rate=self.model_rate), seed=seed)
+
+    def output_eq(self, slots):
+        """conan_streams_output_eq: as input_eq."""
+        return self._get_feature("out_eq", slots)
+
+    def output_eq_state(self, slots):
+        """conan_streams_output_eq_state: as input_eq_state."""
+        return self._feature_seed_rows("out_eq", slots)
 
     def set_watermark(self, slots, cfg=True, seed=None, **kw):
         """conan_streams_set_watermark: a keyed mark in the audio the slots emit (include/conan_hip.h, conan_watermark_cfg): a +-1

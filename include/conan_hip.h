@@ -1717,6 +1717,117 @@ int conan_streams_tone_state(conan_streams* s, const int32_t* slots, int n, cona
  * (a digit row of a slot with the feature reads -1 where no digit holds).  CONAN_ERR_STATE before any wav-in call. */
 int conan_step_wav_tones(conan_streams* s, int32_t* digit_dev, int32_t* sound_dev, int32_t* level_dev, void* stream);
 
+/* Equaliser (added within ABI 9: a caller detects it by the symbol conan_eq; no existing struct or call changes).  A cascade of up to
+ * CONAN_EQ_MAX_SECTIONS = 4 biquad sections on audio that exists only on the device: a high-pass against DC and rumble, a notch
+ * against hum, a tone control, a telephone band - on the source side of a wav-in slot (conan_streams_set_input_eq), on its output
+ * (conan_streams_set_output_eq) and on whole signals (conan_eq, the bit-exact yardstick of both).  tests/eq_ref.py restates the law
+ * in Python floats (IEEE doubles, never fused), bit for bit.
+ *   Coefficients.  A section is five doubles {b0, b1, b2, a1, a2}, normalised by a0, taken as given: how they were designed is not
+ *     part of the law.  Each is finite and at most CONAN_EQ_MAX_COEF = 65536 in magnitude (a cookbook section with |gain| <= 60 dB
+ *     stays far inside), and each section is stable: |a2| < 1 and |a1| < 1 + a2.
+ *   One step.  Transposed direct form II in f64, every product and every sum rounded on its own - no fused multiply-add anywhere:
+ *       y = b0 x + s0;   s0' = (b1 x - a1 y) + s1;   s1' = b2 x - a2 y.
+ *     Section k + 1 reads section k's f64 output.  The input is the f32 sample widened, a non-finite sample counts as 0 (one bad
+ *     sample must not poison a recursive state), and the result is the last section's output rounded once to f32.  There is no
+ *     clip: a boost may exceed 1.0.  f64 denormals are kept.
+ *   The segment grid.  A row's grid of CONAN_EQ_SEG = 128 samples starts at its origin.  Per section, with c the state at a
+ *     segment's start, e the end state of the zero-state run over that segment's true inputs (the section's inputs: the output of
+ *     the section in front of it) and M the section's 2x2 transition matrix of 128 zero inputs - built on the host in double by
+ *     applying the step to the unit states (1, 0) and (0, 1), which give M's columns - the state at the next segment's start is
+ *       c0' = (M00 c0 + M01 c1) + e0,   c1' = (M10 c0 + M11 c1) + e1       (each product and sum rounded on its own).
+ *     Every output sample comes from the direct recursion from its segment's start state; the state at the origin is zero.
+ *   The pending tail.  An incomplete last segment is emitted from its start state and its inputs (behind the non-finite rule) stay
+ *     in the state's tail; when more samples arrive the segment is run again from the same start state and only the new samples
+ *     are emitted.  So the output never depends on how a stream was cut into calls, down to cuts of one sample.
+ * The state record holds the origin, the position, the per-section carries (the start state of the segment that holds the position;
+ * zeros behind the cfg's last section) and the tail ((pos - origin) mod 128 entries, zeros behind them). */
+#define CONAN_EQ_MAX_SECTIONS 4
+#define CONAN_EQ_SEG 128
+#define CONAN_EQ_MAX_COEF 65536.0
+typedef struct conan_eq_cfg {
+  int32_t enabled;         /* 0: off (other fields ignored) | 1 */
+  int32_t sections;        /* 1 .. CONAN_EQ_MAX_SECTIONS */
+  int64_t origin;          /* the grid's first sample; with a seed: the origin its record reports.  0 <= origin <= pos <= 2^62 */
+  int64_t pos;             /* the position of the first sample filtered: equal to origin without a seed, the seed record's pos with one */
+  double coef[CONAN_EQ_MAX_SECTIONS][5];   /* {b0, b1, b2, a1, a2} per section; zeros behind the last one */
+  int32_t reserved[4];     /* must be 0 */
+} conan_eq_cfg;            /* 200 bytes */
+typedef struct conan_eq_state {
+  int64_t origin, pos;
+  double carry[CONAN_EQ_MAX_SECTIONS][2];
+  float tail[CONAN_EQ_SEG];
+} conan_eq_state;          /* 592 bytes */
+/* sizeof(conan_eq_state). */
+int64_t conan_eq_state_bytes(void);
+#define CONAN_EQ_LOWPASS 0
+#define CONAN_EQ_HIGHPASS 1
+#define CONAN_EQ_BANDPASS 2    /* 0 dB peak gain */
+#define CONAN_EQ_NOTCH 3
+#define CONAN_EQ_PEAK 4
+#define CONAN_EQ_LOWSHELF 5
+#define CONAN_EQ_HIGHSHELF 6
+#define CONAN_EQ_DCBLOCK 7     /* first order (b2 = a2 = 0): g (1 - z^-1) / (1 - R z^-1), R = exp(-2 pi f0 / rate), g = (1 + R) / 2 */
+#define CONAN_EQ_DEEMPHASIS 8  /* first order (b2 = a2 = 0): (1 - p) / (1 - p z^-1), p = exp(-2 pi f0 / rate); 50 us is f0 = 3183.1 Hz */
+/* Host only, no handle, no GPU: one section {b0, b1, b2, a1, a2} / a0 -> out[5], by the Audio EQ Cookbook's forms (R. Bristow-Johnson)
+ * with w0 = 2 pi f0 / rate, alpha = sin w0 / (2 q) and A = 10^(gain_db / 40); gain_db is read by the peak and the shelves, q by
+ * every second-order kind.  CONAN_ERR_INVALID: an unknown kind, a non-finite argument, f0 outside (0, rate / 2), q <= 0 (for every
+ * kind), |gain_db| > 60.  The design is not part of the bit-exact law: libm decides its last bits. */
+int conan_eq_design(int kind, double rate, double f0, double q, double gain_db, double out[5]);
+/* The law on whole signals: row i (n rows in 1 .. 65535) holds samples[i] (host, 0 .. 2^31 - 1) floats at x_dev + i * x_ld and is
+ * written to y_dev + i * y_ld (strides in floats, each >= every samples[i]); y_dev may equal x_dev with the same stride: in place.
+ * cfg->enabled must be 1.  seed_dev (may be null): conan_eq_state[n], the record row i continues from; cfg->origin and cfg->pos then
+ * name the origin and position of every seed row (the caller vouches: the library does not read device memory to plan), so a
+ * signal cut anywhere and chained through the state gives the whole signal's bits.  Without a seed every row starts from zero at
+ * cfg->origin = cfg->pos.  state_out_dev (may be null; may equal seed_dev): the record behind each row.  Both 8-byte aligned.
+ * ONE launch (cnk::eq_signal_kernel, one workgroup of 256 lanes per row, chunks of 1920 samples through cnk::eq_chunk) on `stream`;
+ * the row table goes through the context's workspace, which conan_wav2mel, conan_loud_norm and conan_activity share: calls on one
+ * context are ordered by the caller. */
+int conan_eq(conan_ctx* ctx, const conan_eq_cfg* cfg, const float* x_dev, int64_t x_ld, int n, const int64_t* samples, float* y_dev, int64_t y_ld,
+             conan_eq_state* state_out_dev, const conan_eq_state* seed_dev, void* stream);
+/* Sets (cfg->enabled = 1) or removes (0) the SOURCE-side equaliser for `slots` (wav-in steps only).  Every argument is checked before
+ * anything changes (CONAN_ERR_INVALID: a cfg outside the ranges above, a seed that is misaligned or whose rows are too close, a seeded
+ * slot that is not at cfg->pos; CONAN_ERR_UNSUPPORTED: segment * hop above 1920 = (16 - 1) * CONAN_EQ_SEG samples, which is what a
+ * call row holds; CONAN_ERR_STATE: a stream-set without the streaming front-end), and pending pipelined work is joined; it may be
+ * called at any time, also mid-utterance, and the setting persists across resets.
+ * What a slot with the feature does.  Every conan_step_wav[_async] / conan_step_wav_ragged[_ld][_async] call that hands it samples
+ * runs ONE more launch (cnk::eq_stream_kernel, one workgroup of 256 lanes per row) between the input resampler's launch and the
+ * leveller's, on the model-rate rows the front-end is about to read: the audio ring and everything that reads it - the leveller,
+ * the mel frames, the follower, the activity and tone detectors, the comfort tracker, the dry path - see the filtered source.  Behind
+ * a resampler launch it works in place on the staged rows; in a call without one it reads the caller's rows and writes the
+ * resampler's staging set, and the call's other rows ride along as copy rows (as for the leveller, which then works in place behind
+ * it).  The slot's position is the model-rate samples its front-end has received.  Slots of one call may carry different cascades.
+ * Enabling a slot that was off starts it from the zero state with the origin at its current position.  Changing an enabled slot is
+ * the live tone control and does not click: one small launch (cnk::eq_set_kernel) on `stream` closes the pending tail with the OLD
+ * coefficients - the carries advance over it by the direct recursion - the origin moves to the current position, section k keeps
+ * its two state words for k below both section counts and new sections start at zero (tests/eq_ref.py, Stream.change).  With
+ * seed_dev (row i at seed_dev + i * seed_ld bytes, a record queried from a stream at the same position: the caller vouches) the
+ * slot continues that stream: cfg->origin names the record's origin and cfg->pos its position, which must be the slot's.  Without
+ * a seed cfg->origin and cfg->pos take no part, but the cfg check still holds them to 0 <= origin <= pos (zeros pass).  The state restarts at the slot's next row after a reset that includes
+ * CONAN_MODEL_FRONTEND, with the origin at that row's first sample.  enabled = 0 restores the path without the feature.
+ * Memory: the first enabling call allocates 592 bytes of state and 288 bytes of sections per slot and 8 row tables;
+ * conan_streams_state_bytes counts them from then on.  A stream-set that never calls the setter allocates nothing and runs exactly
+ * the launches it ran before; a slot that does not ask keeps its bits.  Snapshots carry neither the setting nor the state, and
+ * conan_streams_layout_id and conan_streams_snapshot_bytes do not change.  The hand-over: conan_streams_input_eq (origin, pos) and
+ * conan_streams_input_eq_state, export, import, then this setter with the record as seed_dev. */
+int conan_streams_set_input_eq(conan_streams* s, const int32_t* slots, int n, const conan_eq_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream);
+/* Host only: the cfg of `slot` as set, with origin and pos as they stand now (zeros for a slot without the feature). */
+int conan_streams_input_eq(const conan_streams* s, int slot, conan_eq_cfg* cfg_out);
+/* The records of `slots` -> row i at rows_dev + i * ld bytes (8-byte aligned, ld a multiple of 8 and at least conan_eq_state_bytes), on
+ * `stream` behind a join of pipelined work.  A slot about to restart reports the zero record at its position; a slot without the
+ * feature is CONAN_ERR_STATE. */
+int conan_streams_input_eq_state(conan_streams* s, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream);
+/* The OUTPUT-side equaliser: the same setter, getter and state query for the slot's own vocoder audio.  A slot with the feature
+ * costs ONE more launch (cnk::eq_stream_kernel) per vocoder step in which it takes part, in every step entry point, the mel-in ones
+ * included: in place on the [n][T] rows conv_post wrote, directly behind it and in front of the output leveller's ramp - so a boost
+ * does not defeat the level the leveller promises - and of the gate, the mix, the fill, the mark, the output resampler and the
+ * encoders.  The slot's position is the model-rate samples its vocoder has produced since its last reset with CONAN_MODEL_HIFIGAN,
+ * which is also what restarts the state.  CONAN_ERR_UNSUPPORTED: the whole-prefix vocoder of upsample 'nn' (as for the output
+ * leveller), and a stream-set whose max_frames * hop exceeds 1920; CONAN_ERR_STATE: a context without a HiFi-GAN model.  Memory,
+ * snapshots and the hand-over are the source side's. */
+int conan_streams_set_output_eq(conan_streams* s, const int32_t* slots, int n, const conan_eq_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream);
+int conan_streams_output_eq(const conan_streams* s, int slot, conan_eq_cfg* cfg_out);
+int conan_streams_output_eq_state(conan_streams* s, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
