@@ -153,6 +153,9 @@ _PROTOS = {
     "conan_streams_output_level_state_bytes": (C.c_int64, [C.c_void_p]),
     "conan_streams_conceal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_conceal_state_bytes": (C.c_int64, []),
+    "conan_streams_echo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "conan_echo_state_bytes": (C.c_int64, []),
+    "conan_echo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_denoise_state_bytes": (C.c_int64, []),
     "conan_mel_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_watermark_state_bytes": (C.c_int64, []),
@@ -624,6 +627,46 @@ def conceal_cfg(rate=None, **kw):
     return ConcealCfg(1, *[int(f[n]) for n in names])
 
 
+ECHO_BLOCK, ECHO_MAX_TAPS, ECHO_MAX_DELAY, ECHO_MAX_SHIFT, ECHO_HISTORY = 64, 2048, 4096, 12, 6208
+
+
+class EchoCfg(C.Structure):
+    """conan_echo_cfg (include/conan_hip.h)."""
+    _fields_ = [("enabled", C.c_int32), ("taps", C.c_int32), ("delay", C.c_int32), ("mu_shift", C.c_int32), ("dt_num", C.c_int32),
+                ("dt_den", C.c_int32), ("hang", C.c_int32), ("reserved", C.c_int32), ("reg", C.c_int64), ("far_min", C.c_int64)]
+
+
+_ECHO_FIELDS = ("taps", "delay", "mu_shift", "dt_num", "dt_den", "hang", "reg", "far_min")
+
+
+def echo_keywords(rate):
+    """The documented defaults of the echo canceller for an input rate, or - given an enabled EchoCfg - its fields: the keywords
+    echo_cfg takes.  A 64 ms filter (a multiple of 64 taps, at most 2048), no bulk delay, step shift 4, a Geigel threshold of 1/2
+    with 50 ms of hang-over, reg = taps * 4096 and far_min = taps * 1024.  They are choices, not measurements."""
+    if isinstance(rate, EchoCfg):
+        return {f: int(getattr(rate, f)) for f in _ECHO_FIELDS}
+    r = int(rate)
+    taps = min(ECHO_MAX_TAPS, max(ECHO_BLOCK, (r * 64 // 1000 + 32) // 64 * 64))
+    return dict(taps=taps, delay=0, mu_shift=4, dt_num=1, dt_den=2, hang=(r // 20 + ECHO_BLOCK - 1) // ECHO_BLOCK, reg=taps * 4096, far_min=taps * 1024)
+
+
+def echo_cfg(rate=None, **kw):
+    """An enabled conan_echo_cfg: echo_keywords(rate) with the given fields replaced (rate=None: every field must be given)."""
+    base = echo_keywords(rate) if rate is not None else {}
+    f = dict(base, **kw)
+    unknown = sorted(set(f) - set(_ECHO_FIELDS))
+    if unknown:
+        raise ValueError(f"echo: unknown fields {unknown}")
+    missing = [n for n in _ECHO_FIELDS if n not in f]
+    if missing:
+        raise ValueError(f"echo: without a rate the fields {missing} must be given")
+    c = EchoCfg()
+    c.enabled = 1
+    for n in _ECHO_FIELDS:
+        setattr(c, n, int(f[n]))
+    return c
+
+
 class DenoiseCfg(C.Structure):
     """conan_denoise_cfg (include/conan_hip.h)."""
     _fields_ = [("enabled", C.c_int32), ("reseed", C.c_int32), ("bias", C.c_int32), ("knee", C.c_int32), ("slope", C.c_int32), ("depth", C.c_int32),
@@ -898,6 +941,8 @@ SLOT_FEATURES = {f.keyword: f for f in (
                 "conan_streams_bypass_state", BypassState, last="conan_step_wav_bypass"),
     SlotFeature("conceal", "the concealment", ConcealCfg, "enabled", conceal_cfg, conceal_keywords, "conan_streams_set_conceal",
                 "conan_streams_conceal_cfg", seed_state="conan_streams_conceal_state", seed_bytes="conan_conceal_state_bytes"),
+    SlotFeature("echo", "the echo canceller", EchoCfg, "enabled", echo_cfg, echo_keywords, "conan_streams_set_echo",
+                "conan_streams_echo_cfg", seed_state="conan_streams_echo_state", seed_bytes="conan_echo_state_bytes"),
     SlotFeature("denoise", "the noise suppression", DenoiseCfg, "enabled", denoise_cfg, denoise_keywords, "conan_streams_set_denoise",
                 "conan_streams_denoise", seed_state="conan_streams_denoise_state", seed_bytes="conan_denoise_state_bytes"),
     SlotFeature("comfort", "the comfort noise", ComfortCfg, "mode", comfort_cfg, comfort_keywords, "conan_streams_set_comfort",

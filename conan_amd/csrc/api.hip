@@ -782,6 +782,30 @@ int conan_conceal(conan_ctx* ctx, const conan_conceal_cfg* cfg, int format, void
   return guarded([&] { conc::whole(ctx, cfg, format, x_dev, ld, n, samples, lost_dev, lost_ld, stream); });
 }
 
+// ---- echo cancellation (echo.hip): conan_streams_set_echo, conan_streams_echo_cfg, conan_streams_echo, conan_echo_state_bytes,
+// conan_streams_echo_state, conan_echo
+int conan_streams_set_echo(conan_streams* s, const int32_t* slots, int n, const conan_echo_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream) {
+  return guarded([&] { echo::set_echo(s, slots, n, cfg, seed_dev, seed_ld, stream); });
+}
+
+int conan_streams_echo_cfg(const conan_streams* s, int slot, conan_echo_cfg* cfg_out) { return guarded([&] { wavio::get_setting(s, &conan_streams::ec, slot, cfg_out, nullptr); }); }
+
+int conan_streams_echo(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, void* wav_dev, int64_t wav_ld, const void* far_dev,
+                       int64_t far_ld, int64_t* stats_dev, void* stream) {
+  return guarded([&] { echo::cancel(s, slots, n, samples, wav_dev, wav_ld, far_dev, far_ld, stats_dev, stream); });
+}
+
+int64_t conan_echo_state_bytes(void) { return (int64_t)cnk::kEchoStateBytes; }
+
+int conan_streams_echo_state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream) {
+  return guarded([&] { echo::state(s, slots, n, state_dev, ld, stream); });
+}
+
+int conan_echo(conan_ctx* ctx, const conan_echo_cfg* cfg, int format, void* x_dev, int64_t ld, const void* far_dev, int64_t far_ld, int n,
+               const int64_t* samples, int64_t* stats_dev, void* stream) {
+  return guarded([&] { echo::whole(ctx, cfg, format, x_dev, ld, far_dev, far_ld, n, samples, stats_dev, stream); });
+}
+
 // ---- input noise suppression (denoise.hip): conan_mel_denoise, conan_streams_set_denoise, conan_streams_denoise,
 // conan_denoise_state_bytes, conan_streams_denoise_state
 int conan_mel_denoise(conan_ctx* ctx, const conan_denoise_cfg* cfg, const float* mel_dev, int n, const int32_t* frames, int64_t ld, int num_mels,

@@ -627,6 +627,36 @@ struct ConcArgs {
 };
 void launch_conceal(const ConcArgs& a, hipStream_t st);
 
+// Echo cancellation (echo.hip; include/conan_hip.h, conan_echo_cfg).  echo_kernel: one workgroup of kEchoThreads lanes per table row,
+// which cancels `samples` samples of row `row` of the caller's buffer (wav + row * wav_ld dwords, in format fmt) in place from the far
+// row (far + row * far_ld dwords, same format).  The state - header, weights, the pending block's e, the last kEchoHist far samples -
+// is read from state[slot] (restart = 0 and slot >= 0) or starts as the restart state, and is written back to state[slot] (slot >= 0).
+// Every index the kernel forms comes from the row: taps, delay and phase (= pos mod 64, the pending block's fill) are the host's; of
+// the record only values are read.  A row is walked in tiles of kEchoTile samples and, inside, block by block, so a whole signal
+// (slot = -1, restart = 1) and a chunk take the same path.
+constexpr int kEchoBlock = 64, kEchoMaxTaps = 2048, kEchoMaxDelay = 4096, kEchoMaxShift = 12;      // CONAN_ECHO_*
+constexpr int kEchoHist = 6208;                                                                    // CONAN_ECHO_HISTORY
+constexpr int kEchoTile = 2048, kEchoThreads = 256;
+static_assert(kEchoHist >= kEchoMaxTaps + kEchoBlock - 1 + kEchoMaxDelay && kEchoHist % 4 == 0, "the window of the oldest tap of a block's first sample");
+struct EchoHead { long long pos; int shift, hcnt; long long adapted, frozen, trips, D, E; int dmax, reserved; };      // the first 64 bytes of a record
+static_assert(sizeof(EchoHead) == 64, "the header's record");
+constexpr long long kEchoStateBytes = (long long)sizeof(EchoHead) + (kEchoMaxTaps + kEchoBlock) * 4ll + kEchoHist * 2ll;
+struct EchoRow {
+  long long samples, pos, reg, far_min;      // pos: the slot's position at the row's first sample
+  int row, slot, restart, fmt;
+  int taps, delay, phase, mu_shift;
+  int dt_num, dt_den, hang, pad_;
+};
+static_assert(sizeof(EchoRow) == 80, "uploaded as 20 ints");
+struct EchoArgs {
+  void* wav; long long wav_ld;              // the caller's rows, stride in dwords
+  const void* far; long long far_ld;        // the far rows, stride in dwords
+  char* state;                              // [max_slots][kEchoStateBytes]; may be null when no row names a slot
+  long long* stats;                         // [call rows][4] or null
+  const EchoRow* tab; int rows;
+};
+void launch_echo(const EchoArgs& a, hipStream_t st);
+
 // Input noise suppression (denoise.hip; include/conan_hip.h, conan_denoise_cfg): the spectral gate on log-mel frames of nm bins.  One
 // workgroup of 64 * ceil(nm / 64) lanes per table row; lane b keeps the floor and the attenuation of bin b in registers across the
 // row's frames.  DnState is the published conan_denoise_state; a record whose `bins` is not nm is the state before the first frame.

@@ -1,5 +1,5 @@
 // Device routines of the sample formats (include/conan_hip.h, CONAN_SAMPLE_*), shared by resample.hip (the wav-in and wav-out rows,
-// conan_convert_samples) and conceal.hip (the repair works on a row in its own format).
+// conan_convert_samples), conceal.hip and echo.hip (the repair and the canceller work on a row in its own format).
 #pragma once
 #include "kernels.h"
 

@@ -212,7 +212,7 @@ def _by_value(slots, values):
 
 
 # what True means to a feature's Streams setter, by engine keyword (register= has no True: a scalar is its target)
-_TRUE = dict(level=True, pitch=True, follow=True, out_level=True, activity=dict(gate=True), bypass={}, conceal={}, denoise={}, comfort={}, watermark={}, tones={})
+_TRUE = dict(level=True, pitch=True, follow=True, out_level=True, activity=dict(gate=True), bypass={}, conceal={}, echo={}, denoise={}, comfort={}, watermark={}, tones={})
 
 
 def _accept(keyword, v, k, n, voice):
@@ -248,6 +248,10 @@ def _accept(keyword, v, k, n, voice):
         if isinstance(v, _lib.ConcealCfg):
             return v
         forms = "True, a dict of conan_conceal_cfg's fields, an _lib.ConcealCfg"
+    if keyword == "echo":
+        if isinstance(v, _lib.EchoCfg):
+            return v
+        forms = "True, a dict of conan_echo_cfg's fields, an _lib.EchoCfg"
     raise ValueError(f"{keyword}: {v!r} ({forms} or None)")
 
 
@@ -326,7 +330,7 @@ class StreamingVoiceConversionEngine:
             self._apply(keyword, self.slots, values[keyword])
 
     def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
+                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, echo=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
         in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
         in_format: the input's sample format (None: float32; 's16' takes int16 rows, 'ulaw' / 'alaw' uint8), decoded on the GPU.
@@ -346,7 +350,10 @@ class StreamingVoiceConversionEngine:
         True: enabled at full wet (a later set_bypass toggles it); a dict of set_bypass's keywords.  chunk_bypass() reads
         the last call's levels.  conceal: loss concealment of the input rows (Streams.set_conceal) - None / False: none; True: the
         defaults of the slot's input rate; a dict of conan_conceal_cfg's fields over them.  feed(lost=...) then repairs the packets
-        that never arrived, on the GPU in front of the step.  comfort: comfort noise in the closed activity gate
+        that never arrived, on the GPU in front of the step.  echo: echo cancellation of the input rows (Streams.set_echo) - None /
+        False: none; True: the defaults of the slot's input rate; a dict of conan_echo_cfg's fields over them.  feed(far=...) then
+        cancels what the far end's audio left in the rows, on the GPU behind the repair and in front of the step.
+        comfort: comfort noise in the closed activity gate
         (Streams.set_comfort; activity= beside it) - None / False: none; True: the defaults; a dict of set_comfort's keywords; the
         seed defaults to one derived from the slot's index.  chunk_comfort() reads the last call's levels.
         denoise: noise suppression of the input's log-mel frames (Streams.set_denoise) - None / False: none; True: the defaults for
@@ -363,7 +370,7 @@ class StreamingVoiceConversionEngine:
         if isinstance(in_format, (list, tuple)) or isinstance(level, (list, tuple)):
             raise ValueError("in_format / level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
         values = self._host_checks(len(self.slots), voice, level=level, follow=follow, register=register, activity=activity, bypass=bypass,
-                                   conceal=conceal, comfort=comfort, denoise=denoise, tones=tones, eq=eq)
+                                   conceal=conceal, echo=echo, comfort=comfort, denoise=denoise, tones=tones, eq=eq)
         self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice,
                    out_level=out_level, watermark=watermark, out_eq=out_eq)
         self._set_rate(self.slots, in_rate, filter)
@@ -390,7 +397,7 @@ class StreamingVoiceConversionEngine:
         """The slots' feature from _values' list, one setter call per slot, behind the slots' reset (states restart from their seeds at
         the first emitted chunk).  A feature with a Streams dict (level, pitch, out_level): a slot that never had one is left alone.
         The others: a stream-set that never used the feature gets no setter call at all; once used, None turns a slot off.  rates:
-        the slots' input rates (None: the model rate), for the concealment's defaults.  A comfort seed defaults to
+        the slots' input rates (None: the model rate), for the concealment's and the canceller's defaults.  A comfort seed defaults to
         _lib.comfort_seed(slot)."""
         f = _lib.SLOT_FEATURES[keyword]
         if not f.mirror:
@@ -401,7 +408,7 @@ class StreamingVoiceConversionEngine:
             if v is None and f.mirror and int(slot) not in getattr(self.st, f.mirror):
                 continue
             kw = {}
-            if keyword == "conceal":
+            if keyword in ("conceal", "echo"):
                 v, kw = None if v is None else (v or True), dict(rate=rates[k])      # ({}: True, the defaults of the slot's rate)
             elif keyword == "comfort" and v is not None:
                 v = dict(dict(seed=_lib.comfort_seed(slot)), **v)
@@ -466,6 +473,12 @@ class StreamingVoiceConversionEngine:
         """A live change of the slots' loss concealment (all slots by default) between feed / feed_ragged calls, also mid-utterance:
         Streams.set_conceal's arguments (cfg=None turns it off; an enabled slot keeps its state)."""
         self._live("conceal", slots, cfg, **kw)
+
+    def set_echo(self, slots=None, cfg=True, **kw):
+        """A live change of the slots' echo canceller (all slots by default) between feed / feed_ragged calls, also mid-utterance:
+        Streams.set_echo's arguments (cfg=None turns it off; an enabled slot keeps its state, and a changed taps the weights that
+        still exist)."""
+        self._live("echo", slots, cfg, **kw)
 
     def _lost_rows(self, slots, lost, pos, counts):
         """The flags of one call's rows cut from whole-utterance flags: row i takes lost[i] from sample position pos[i] on, counts[i]
@@ -595,7 +608,7 @@ class StreamingVoiceConversionEngine:
         return L if in_rate is None else L * int(in_rate) // self.st.model_rate
 
     @torch.no_grad()
-    def feed(self, wav_chunk, final=False, pipelined=False, mel=None, lost=None):
+    def feed(self, wav_chunk, final=False, pipelined=False, mel=None, lost=None, far=None):
         """Streaming waveform input (conan_step_wav): wav_chunk [B, seg*hop] (cuda; 0 .. seg*hop samples when final; at an input
         rate set by start_wav, seg*hop*in_rate/model_rate) ->
         (wav [B, emit*hop], mel [B, emit, 80], codes [B, emit]) of the chunk this call emitted (emit = 0 on the first call: one
@@ -610,11 +623,16 @@ class StreamingVoiceConversionEngine:
         the recording afterwards with those flags (Context.trim_silence(flags=...)) without detecting again.
         lost: [B, packets] integer or bool (cuda), non-zero = that packet of the row never arrived: the slots with start_wav(conceal=...)
         repair them on the GPU in front of the step (Streams.conceal; packets count from the start of the row).  The chunk is
-        copied first: the caller's tensor keeps its samples."""
+        copied first: the caller's tensor keeps its samples.
+        far: [B, samples] in wav_chunk's dtype, what went to each caller's earpiece while the row was recorded: the slots with
+        start_wav(echo=...) cancel its echo on the GPU behind the repair and in front of the step (Streams.echo).  The chunk is
+        copied first here too."""
         fn = self.st.step_wav_async if pipelined else self.st.step_wav
         st = self.st
         if lost is not None:
             wav_chunk, fn = wav_chunk.clone(), functools.partial(fn, lost=lost)
+        if far is not None:
+            wav_chunk, fn = (wav_chunk if lost is not None else wav_chunk.clone()), functools.partial(fn, far=far)
         if not (st.output_ld or st.output_formats):
             emit, c, m, w = fn(self.slots, wav_chunk, final=final, mel=mel)
             return w, m, c[:, :emit]
@@ -635,6 +653,17 @@ class StreamingVoiceConversionEngine:
         if loud_norm or (trim is not None and trim is not False):
             raise ValueError("lost: loud_norm and trim hold the utterance whole, in front of the streaming repair: repair it whole first "
                              "(Context.conceal) and pass the repaired utterance without lost=")
+
+    @staticmethod
+    def _check_far(far, echo, loud_norm, trim):
+        """far= of the whole-utterance calls: it needs echo=, and cannot go with loud_norm or trim.  Host only."""
+        if far is None:
+            return
+        if echo is None or echo is False:
+            raise ValueError("far: the far end needs echo= (True, or conan_echo_cfg's fields)")
+        if loud_norm or (trim is not None and trim is not False):
+            raise ValueError("far: loud_norm and trim hold the utterance whole, in front of the streaming canceller: cancel it whole first "
+                             "(Context.echo) and pass the cancelled utterance without far=")
 
     @torch.no_grad()
     def _loud_norm(self, wav, in_rate, in_format):
@@ -670,7 +699,7 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
                   out_format=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None, register=None, activity=None,
-                  activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
+                  activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, echo=None, far=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
         """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] (or None with voice = (bank, ids): start) -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
@@ -698,11 +727,16 @@ class StreamingVoiceConversionEngine:
         of infer_wav(ctx.conceal(src_wav, lost, cfg, in_format), ...) bit for bit.  Not with loud_norm or trim, which hold the
         utterance whole: repair it whole first (Context.conceal).  denoise: the noise suppressor (start_wav): the results are those of
         infer(ctx.mel_denoise(ctx.wav2mel(x)), ...) bit for bit, x = the samples the front-end reads.  watermark: the output watermark
-        (start): the returned model-rate wav is ctx.watermark_embed of the unmarked one, bit for bit."""
+        (start): the returned model-rate wav is ctx.watermark_embed of the unmarked one, bit for bit.
+        echo + far: echo cancellation (start_wav) with far [B, N], the far end of the whole utterance in src_wav's format: the
+        results are those of infer_wav(ctx.echo(src_wav, far, cfg, in_format), ...) bit for bit.  Not with loud_norm or trim."""
         self._check_voice(ref_mel, voice)
         self._host_checks(len(self.slots), voice, level=level, pitch=pitch, follow=follow, register=register, activity=activity, bypass=bypass,
-                          conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq)      # (before anything runs)
+                          conceal=conceal, echo=echo, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq)      # (before anything runs)
         self._check_lost(lost, conceal, loud_norm, trim)
+        self._check_far(far, echo, loud_norm, trim)
+        if far is not None and tuple(far.shape) != tuple(src_wav.shape):
+            raise ValueError(f"far: {tuple(far.shape)} for a src_wav of {tuple(src_wav.shape)}: the far end is the utterance's, sample for sample")
         trim = self._trim_keywords(trim)
         if trim is not None:
             src_wav = self._trim(src_wav, in_rate, in_format, trim)[0]
@@ -710,7 +744,7 @@ class StreamingVoiceConversionEngine:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
                        pitch=pitch, voice=voice, follow=follow, register=register, activity=activity, bypass=bypass, out_level=out_level, conceal=conceal,
-                       comfort=comfort, denoise=denoise, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq, **filter)
+                       echo=echo, comfort=comfort, denoise=denoise, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -720,11 +754,11 @@ class StreamingVoiceConversionEngine:
         pos, final = 0, False
         while True:
             if pos < last:
-                w, m, c = self.feed(src_wav[:, pos:pos + L], pipelined=pipelined, mel=mel, lost=cut(pos, L))
+                w, m, c = self.feed(src_wav[:, pos:pos + L], pipelined=pipelined, mel=mel, lost=cut(pos, L), far=None if far is None else far[:, pos:pos + L])
                 pos += L
             else:
                 w, m, c = self.feed(src_wav[:, pos:] if not final else empty, final=True, pipelined=pipelined, mel=mel,
-                                    lost=None if final else cut(pos, N - pos))
+                                    lost=None if final else cut(pos, N - pos), far=None if final or far is None else far[:, pos:])
                 pos, done, final = N, final and m.shape[1] == 0, True
                 if done:
                     break
@@ -742,7 +776,7 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
+                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, echo=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
         """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
         rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
@@ -760,7 +794,7 @@ class StreamingVoiceConversionEngine:
         it holds whole)."""
         self._check_voice(ref_mel, voice)
         values = self._host_checks(len(slots), voice, level=level, pitch=pitch, follow=follow, register=register, activity=activity, bypass=bypass,
-                                   conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq)
+                                   conceal=conceal, echo=echo, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq)
         self.st.reset(slots, which=7 | 8)
         self._reference(slots, ref_mel, ref_len, voice)
         self._set_out_rate(slots, out_rate, out_filter)
@@ -772,7 +806,7 @@ class StreamingVoiceConversionEngine:
             self._apply(keyword, slots, values[keyword], _per_slot(in_rate, len(slots)))
 
     @torch.no_grad()
-    def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None, lost=None):
+    def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None, lost=None, far=None):
         """Streaming waveform input for slots at different positions of their utterances (conan_step_wav_ragged): slot i takes the
         first samples[i] samples of wav row i (wav [n, <= seg*hop] cuda, or a list of 1-D rows, each in its slot's input format's
         dtype) with its own final flag; the rules per slot are feed()'s.
@@ -781,18 +815,19 @@ class StreamingVoiceConversionEngine:
         As in feed(), the reference's whole-utterance loud_norm cannot run here (infer_wav_staggered(loud_norm=True) holds the
         utterances whole); open_slots(level=...) gives a slot the causal input leveller, which can, and a call may mix levelled
         and unlevelled slots.  lost: [n, packets] integer or bool (cuda), as feed()'s: the rows of slots with the concealment are
-        repaired in front of the step, the others keep their bytes."""
+        repaired in front of the step, the others keep their bytes.  far: the rows' far end in wav's form (feed()'s): the rows
+        of slots with the canceller are cancelled behind the repair, the others keep their bytes."""
         fn = self.st.step_wav_ragged_async if pipelined else self.st.step_wav_ragged
-        if lost is not None and isinstance(wav, torch.Tensor):
+        if (lost is not None or far is not None) and isinstance(wav, torch.Tensor):
             wav = wav.clone()      # (a list of rows is packed into a buffer of its own anyway)
-        emit, c, m, w = fn(slots, wav, samples, final, mel=mel, lost=lost)
+        emit, c, m, w = fn(slots, wav, samples, final, mel=mel, lost=lost, far=far)
         counts = self.st.output_samples()        # (emit * hop for a slot without an output rate)
         return [(self.st.wav_row(w, i, slots[i], counts[i]), m[i, :e], c[i, :e]) for i, e in enumerate(emit)]
 
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
                             in_formats=None, out_formats=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None,
-                            register=None, activity=None, activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
+                            register=None, activity=None, activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, echo=None, far=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -816,15 +851,21 @@ class StreamingVoiceConversionEngine:
         list with one per utterance.  conceal: loss concealment (start_wav), one value for every utterance or a list with one per
         utterance; lost: per utterance its whole flags (a 1-D tensor) or None.  Not with loud_norm or trim (Context.conceal repairs an
         utterance whole).  denoise: the noise suppression (start_wav), one value for every utterance or a list with one per utterance.
-        watermark: the output watermark (start), one value for every utterance or a list with one per utterance."""
+        watermark: the output watermark (start), one value for every utterance or a list with one per utterance.
+        echo: echo cancellation (start_wav), one value for every utterance or a list with one per utterance; far: per utterance its
+        whole far end (a 1-D tensor as long as the utterance, in its format) or None, which stands for a silent far end.  Not with
+        loud_norm or trim."""
         voice = self._check_voice(ref_mel, voice)
         U = len(src_wavs)
         # (host checks before anything runs; per utterance, in the form open_slots takes back)
         values = self._host_checks(U, voice, ("out_level",), level=level, pitch=pitch, follow=follow, register=register, activity=activity,
-                                   bypass=bypass, conceal=conceal, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq)
+                                   bypass=bypass, conceal=conceal, echo=echo, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq)
         self._check_lost(lost, conceal, loud_norm, trim)
         if lost is not None and len(lost) != U:
             raise ValueError(f"lost: {len(lost)} values for {U} utterances")
+        self._check_far(far, echo, loud_norm, trim)
+        if far is not None and len(far) != U:
+            raise ValueError(f"far: {len(far)} values for {U} utterances")
         if activity_log is not None:
             activity_log[:] = [[] for _ in range(U)]
         ifmts, ofmts, orates, rates = (list(v) if v is not None else [None] * U for v in (in_formats, out_formats, out_rates, in_rates))
@@ -857,7 +898,7 @@ class StreamingVoiceConversionEngine:
                 tick += 1
                 continue
             us = list(live)
-            rows, samples, final, draining, first = [], [], [], [], []
+            rows, samples, final, draining, first, frows = [], [], [], [], [], []
             width = max(Ls[u] for u in us)
             for u in us:
                 x, (slot, pos, fin) = src_wavs[u], live[u]
@@ -876,10 +917,14 @@ class StreamingVoiceConversionEngine:
                     final.append(1)
                 samples.append(piece.shape[0])
                 rows.append(piece if self.st.input_formats else torch.nn.functional.pad(piece, (0, width - piece.shape[0])))
+                if far is not None:      # (the far end of the same samples; none: the format's silence, which leaves the row's bytes alone)
+                    quiet = {"ulaw": 0xFF, "alaw": 0xD5}.get(ifmts[u], 0)
+                    fpiece = torch.full_like(piece, quiet) if far[u] is None else far[u][first[-1]:first[-1] + piece.shape[0]]
+                    frows.append(fpiece if self.st.input_formats else torch.nn.functional.pad(fpiece, (0, width - fpiece.shape[0])))
             # (rows of several dtypes travel as a list, each packed in its slot's format)
             flags = None if lost is None else self._lost_rows([live[u][0] for u in us], [lost[u] for u in us], first, samples)
             res = self.feed_ragged([live[u][0] for u in us], rows if self.st.input_formats else torch.stack(rows), samples, final, pipelined=pipelined, mel=mel,
-                                   lost=flags)
+                                   lost=flags, far=None if far is None else (frows if self.st.input_formats else torch.stack(frows)))
             if activity_log is not None and any(m.shape[0] for _, m, _ in res):
                 fl, lv = self.chunk_activity()
                 for r, (u, (_, m, _)) in enumerate(zip(us, res)):

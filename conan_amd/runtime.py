@@ -84,6 +84,22 @@ def _conceal_cfg(cfg, rate=None):
     raise ValueError(f"conceal: {cfg!r} is neither an _lib.ConcealCfg, a dict of its fields, a rate nor True")
 
 
+def _echo_cfg(cfg, rate=None):
+    """An enabled _lib.EchoCfg of: one itself; True (the defaults of `rate`); an integer rate; a dict of fields over the defaults of
+    `rate` (without a rate every field must be given)."""
+    if isinstance(cfg, _lib.EchoCfg):
+        return cfg
+    if cfg is True:
+        if rate is None:
+            raise ValueError("echo: True stands for a rate's defaults, and no rate is known here")
+        return _lib.echo_cfg(rate)
+    if isinstance(cfg, dict):
+        return _lib.echo_cfg(rate, **cfg)
+    if isinstance(cfg, (int, np.integer)) and not isinstance(cfg, bool):
+        return _lib.echo_cfg(int(cfg))
+    raise ValueError(f"echo: {cfg!r} is neither an _lib.EchoCfg, a dict of its fields, a rate nor True")
+
+
 def mel_cfg(fft_size=1024, hop_size=320, win_length=1024, num_mels=80, fmin=80, fmax=7600, sample_rate=16000, eps=1e-6,
             mel_vmin=-6.0, mel_vmax=1.5, framing=0, natural_log=False, mag_eps=0.0):
     """conan_mel_cfg with Context.wav2mel's defaults (inference/Conan.py:57-70)."""
@@ -681,6 +697,31 @@ class Context:
             _lib.check(self.lib.conan_conceal(self.h, C.byref(c), f, _ptr(buf), max(ld, 1), n, sm.ctypes.data_as(C.c_void_p), _ptr(flags),
                                               flags.shape[1], _stream()))
         return buf.view(SAMPLE_DTYPES[fmt])[:, :N].reshape(*lead, N)
+
+    def echo(self, mic, far, cfg, fmt="f32", lengths=None, stats=False):
+        """conan_echo: the echo canceller's law (include/conan_hip.h, conan_echo_cfg) on whole signals from the zero state.  mic, far
+        [..., N] of format `fmt` ('f32' float32, 's16' int16, 'ulaw' / 'alaw' uint8): the microphone rows and what went to the
+        earpiece, sample for sample; cfg: an _lib.EchoCfg, a dict of its fields, or an input rate, which stands for that rate's
+        defaults (_lib.echo_keywords); lengths: per row the samples to cancel (default N).  -> the cancelled signals [..., N] in
+        fmt's dtype (mic itself is left alone), and with stats=True also int64 [n, 4] (cuda): per row sum d^2, sum e^2, blocks
+        adapted, blocks frozen.  It is what a slot with Streams.set_echo computes over its rows, bit for bit."""
+        c = _echo_cfg(cfg)
+        f = _lib.sample_format(fmt)
+        dev = torch.device("cuda", self.device)
+        mic, far = mic.to(dev), far.to(dev)
+        if mic.dtype != SAMPLE_DTYPES[fmt] or far.dtype != SAMPLE_DTYPES[fmt] or mic.shape != far.shape:
+            raise ValueError(f"echo: format {fmt!r} takes {SAMPLE_DTYPES[fmt]} samples in mic and far rows of one shape, got {mic.dtype} {tuple(mic.shape)} and {far.dtype} {tuple(far.shape)}")
+        lead, N = mic.shape[:-1], mic.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        ld = max((N * _lib.SAMPLE_BYTES[fmt] + 3) // 4, 1)
+        buf = _row_bytes(mic.reshape(n, N), n, ld, dev)
+        fbuf = _row_bytes(far.reshape(n, N), n, ld, dev)
+        st = torch.zeros(n, 4, dtype=torch.int64, device=dev)
+        sm = np.full(n, N, dtype=np.int64) if lengths is None else np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(n))
+        if n and N:
+            _lib.check(self.lib.conan_echo(self.h, C.byref(c), f, _ptr(buf), ld, _ptr(fbuf), ld, n, sm.ctypes.data_as(C.c_void_p), _ptr(st), _stream()))
+        out = buf.view(SAMPLE_DTYPES[fmt])[:, :N].reshape(*lead, N)
+        return (out, st) if stats else out
 
     def mel_denoise(self, mel, lens=None, cfg=None, seed=None, out=None, state=False, **kw):
         """conan_mel_denoise: the noise suppressor's law (include/conan_hip.h, conan_denoise_cfg) on whole log-mel rows, one launch.
@@ -1506,6 +1547,44 @@ class Streams:
         work."""
         return self._feature_seed_rows("conceal", slots)
 
+    def set_echo(self, slots, cfg=True, rate=None, seed=None, **kw):
+        """conan_streams_set_echo: echo cancellation on the slots' wav-in rows (include/conan_hip.h, conan_echo_cfg).  cfg: True (the
+        defaults of `rate`, the slots' input rate; None: the model rate), a dict of fields over those defaults, an _lib.EchoCfg, or
+        None, which turns the feature off; keywords are fields too.  seed: uint8 [n, bytes] (cuda) rows of echo_state (a
+        hand-over).  It may be called at any time (it joins pipelined work) and survives resets; an enabled slot keeps its state (a
+        changed taps keeps the weights that still exist), which restarts when a slot that was off is enabled and at the first echo
+        call after a reset of the front-end.  Slot snapshots do not carry it.  The cancellation itself is echo(), or far= on the
+        wav-in steps."""
+        self._set_feature("echo", slots, cfg, kw, dict(rate=self.model_rate if rate is None else int(rate)), seed=seed)
+
+    def echo_cfg(self, slots):
+        """conan_streams_echo_cfg: per slot the dict of its fields (set_echo takes it back), None for a slot without the feature."""
+        return self._get_feature("echo", slots)
+
+    def echo(self, slots, wav, samples, far, stats=None):
+        """conan_streams_echo: cancels the far end's echo in the rows IN PLACE, in front of the step call that takes them and behind
+        conceal().  wav, far: 2-D cuda tensors with one row per slot, contiguous rows a multiple of 4 bytes apart, row i in the
+        format of slots[i] (as conceal()'s wav); samples: an int or one per row; stats: an int64 cuda tensor [n, 4] to fill (per row
+        sum d^2, sum e^2, blocks adapted and frozen in this call) or None.  Rows of slots without the feature and rows without
+        samples keep their bytes.  -> wav"""
+        a, p = _i32(slots)
+        n = len(a)
+        for name, t in (("wav", wav), ("far", far)):
+            if not (t.is_cuda and t.dim() == 2 and t.shape[0] == n and (t.shape[1] < 2 or t.stride(1) == 1)
+                    and t.stride(0) * t.element_size() % 4 == 0 and t.data_ptr() % 4 == 0):
+                raise ValueError(f"echo: {name} must be a 2-D cuda tensor [n, .] with contiguous rows a multiple of 4 bytes apart")
+        if stats is not None and not (stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous() and tuple(stats.shape) == (n, 4)):
+            raise ValueError("echo: stats must be a contiguous int64 cuda tensor [n, 4]")
+        sm, sp = _i32([int(samples)] * n if isinstance(samples, (int, np.integer)) else samples)
+        assert len(sm) == n, (n, len(sm))
+        _lib.check(self.lib.conan_streams_echo(self.h, p, n, sp, _ptr(wav), wav.stride(0) * wav.element_size() // 4, _ptr(far),
+                                               far.stride(0) * far.element_size() // 4, _ptr(stats), _stream()))
+        return wav
+
+    def echo_state(self, slots):
+        """conan_streams_echo_state: uint8 [n, bytes] (cuda), the slots' canceller states for set_echo(seed=).  Joins pipelined work."""
+        return self._feature_seed_rows("echo", slots)
+
     def set_denoise(self, slots, cfg=True, seed=None, **kw):
         """conan_streams_set_denoise: noise suppression on the slots' wav-in frames (include/conan_hip.h, conan_denoise_cfg): a causal
         spectral gate on the log-mel frames the front-end has just computed, under a per-band noise floor tracked per frame, in place
@@ -1901,19 +1980,20 @@ class Streams:
                 _lib.check(self.lib.conan_streams_output_fence(self.h, C.c_void_p(out_fence.cuda_stream)))
         _lib.check(self.lib.conan_step_async(self.h, p, n, emit, _ptr(mel_chunk), _ptr(codes), _ptr(mel_out), _ptr(wav_out), _stream()))
 
-    def step_wav(self, slots, wav, final=False, codes=None, mel_out=None, wav_out=None, mel=None, lost=None):
+    def step_wav(self, slots, wav, final=False, codes=None, mel_out=None, wav_out=None, mel=None, lost=None, far=None, echo_stats=None):
         """Waveform-in chunk step (conan_step_wav): wav [n, samples] cuda float32, samples = seg*hop (0 .. seg*hop when final);
         slots with an input rate (set_input_rate) take seg*hop*rate/model_rate samples instead.
         -> (emit, codes [n, seg], mel [n, emit, 80], wav [n, emit*hop]); emit = 0: no chunk this call (the first call, the end of a
         drain).  mel: dict of Context.wav2mel's front-end keywords (framing 0 only).  Slots with an input format (set_input_format)
         take int16 ('s16') or uint8 ('ulaw' / 'alaw') rows; with an output rate, stride or format wav is a list of 1-D rows, each
         in its slot's dtype.  lost: the packet flags of the rows [n, packets] (conceal(), on the rows as packed for the library, in
-        front of the step; a contiguous float32 wav on the device is its own packed form and is repaired in place)."""
-        return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, False, lost)
+        front of the step; a contiguous float32 wav on the device is its own packed form and is repaired in place).  far: the far
+        end of the rows, shaped and typed as wav (echo(), behind the repair and in front of the step); echo_stats: echo()'s stats."""
+        return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, False, lost, far, echo_stats)
 
-    def step_wav_async(self, slots, wav, final=False, codes=None, mel_out=None, wav_out=None, mel=None, lost=None):
+    def step_wav_async(self, slots, wav, final=False, codes=None, mel_out=None, wav_out=None, mel=None, lost=None, far=None, echo_stats=None):
         """Pipelined step_wav (conan_step_wav_async): the outputs are complete after join(); same return value."""
-        return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, True, lost)
+        return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, True, lost, far, echo_stats)
 
     def _wav_in_call(self, n, wav, codes, mel_out, wav_out, mel, pipelined, call):
         """What the wav-in steps share: the default output buffers and their lifetime (a pipelined call's are kept until the next
@@ -1933,7 +2013,7 @@ class Streams:
             self._release()
         return codes, mel_out, wav_out
 
-    def _step_wav(self, slots, wav, final, codes, mel_out, wav_out, mel, pipelined, lost=None):
+    def _step_wav(self, slots, wav, final, codes, mel_out, wav_out, mel, pipelined, lost=None, far=None, echo_stats=None):
         a, p = _i32(slots)
         n = len(a)
         hop, nm = self.ctx.hop, self.ctx.cfg.num_mels
@@ -1942,6 +2022,9 @@ class Streams:
         wav, _, _ = self._in_rows(a, wav, samples)      # (rows samples * 4 bytes apart, whatever the format)
         if lost is not None and samples:
             self.conceal(a, wav, samples, lost)
+        if far is not None and samples:
+            assert far.dim() == 2 and tuple(far.shape) == (n, samples), far.shape
+            self.echo(a, wav, samples, self._in_rows(a, far, samples)[0], echo_stats)
         emit = C.c_int32(0)
         fn = self.lib.conan_step_wav_async if pipelined else self.lib.conan_step_wav
         codes, mel_out, wav_out = self._wav_in_call(n, wav, codes, mel_out, wav_out, mel, pipelined, lambda mc, c, m, w: _lib.check(
@@ -1953,7 +2036,7 @@ class Streams:
             w = wav_out.view(-1)[:n * e * hop].view(n, e * hop)
         return e, codes, mel_out.view(-1)[:n * e * nm].view(n, e, nm), w
 
-    def step_wav_ragged(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None, lost=None):
+    def step_wav_ragged(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None, lost=None, far=None, echo_stats=None):
         """Waveform-in chunk step for slots at different positions of their utterances (conan_step_wav_ragged): slot i takes the
         first samples[i] samples of wav row i (wav [n, <= seg*hop] cuda float32, or None when every samples[i] is 0) and is stepped
         as step_wav([slot], samples[i], final[i]) alone would step it.  Rows wider than seg*hop (slots with an input rate above the
@@ -1961,14 +2044,14 @@ class Streams:
         dtype of its slot's input format (float32, int16, uint8): they are packed from the start of rows a whole number of 4-byte
         units apart.  -> (emit: list of n ints, codes [n, seg], mel [n, seg, 80], wav [n, seg*hop] float32 storage): row i holds
         emit[i] frames (wav_row(wav, i, slot, count) gives it in the slot's output dtype); the rest of the row is left as it was.
-        lost: as step_wav's."""
-        return self._step_wav_ragged(slots, wav, samples, final, codes, mel_out, wav_out, mel, False, lost)
+        lost, far, echo_stats: as step_wav's (far in wav's form: one tensor or a list of rows)."""
+        return self._step_wav_ragged(slots, wav, samples, final, codes, mel_out, wav_out, mel, False, lost, far, echo_stats)
 
-    def step_wav_ragged_async(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None, lost=None):
+    def step_wav_ragged_async(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None, lost=None, far=None, echo_stats=None):
         """Pipelined step_wav_ragged (conan_step_wav_ragged_async): the outputs are complete after join(); same return value."""
-        return self._step_wav_ragged(slots, wav, samples, final, codes, mel_out, wav_out, mel, True, lost)
+        return self._step_wav_ragged(slots, wav, samples, final, codes, mel_out, wav_out, mel, True, lost, far, echo_stats)
 
-    def _step_wav_ragged(self, slots, wav, samples, final, codes, mel_out, wav_out, mel, pipelined, lost=None):
+    def _step_wav_ragged(self, slots, wav, samples, final, codes, mel_out, wav_out, mel, pipelined, lost=None, far=None, echo_stats=None):
         a, p = _i32(slots)
         n = len(a)
         L = self.seg * self.ctx.hop
@@ -1980,6 +2063,8 @@ class Streams:
             wav, ld, _ = self._in_rows(a, wav, L)
             if lost is not None:
                 self.conceal(a, wav, sm, lost)
+            if far is not None:
+                self.echo(a, wav, sm, self._in_rows(a, far, ld)[0], echo_stats)
         emit = (C.c_int32 * n)()
         if ld == L:
             fn, stride = self.lib.conan_step_wav_ragged_async if pipelined else self.lib.conan_step_wav_ragged, ()

@@ -1283,6 +1283,95 @@ int conan_streams_conceal_state(conan_streams* s, const int32_t* slots, int n, v
 int conan_conceal(conan_ctx* ctx, const conan_conceal_cfg* cfg, int format, void* x_dev, int64_t ld, int n, const int64_t* samples, const int32_t* lost_dev,
                   int64_t lost_ld, void* stream);
 
+/* Acoustic echo cancellation (added within ABI 9: a caller detects it by the symbol conan_streams_set_echo; no existing struct or call
+ * changes).  The far party's audio leaves the caller's loudspeaker and comes back in the caller's microphone; left alone it is converted
+ * and sent back, opens the activity gate and is metered as speech.  The canceller is an integer block-NLMS filter per slot: it runs on
+ * the caller's device row IN FRONT OF the wav-in step call and behind conan_streams_conceal, in place, in the slot's input format and at
+ * its input rate, from a second row that holds what the host sent to this caller's earpiece.  No step path changes.
+ * The law (tests/echo_ref.py restates it in numpy with int64 integers).  Everything is per slot; positions t = 0, 1, ... count from the
+ * last restart.  dec / enc are the sample formats' rules as in the concealment, q(v) = clamp(rint(v * 32768), -32768, 32767) its 16-bit
+ * view.  Mic: m[t] = dec(row[t]) in f32 with a non-finite value counted as 0, d[t] = q(m[t]).  Far end: x[t] = q(dec(far[t])) (a
+ * non-finite value counts as 0), x[t] = 0 for t < 0, delayed: x'[t] = x[t - delay].  The far row has the mic row's format, rate and
+ * length (conan_resample / conan_convert_samples bring it there).  B = CONAN_ECHO_BLOCK, L = taps, the weights w[k] are int32 in Q24.
+ *   Filter, for every t: S = sum over k < L of w[k] * x'[t-k] in int64 (|S| < 2^57); yh = clamp(floor((S + 2^23) / 2^24), -32768,
+ *     32767); e[t] = d[t] - yh; the row's sample becomes enc(m[t] - (float)yh * 2^-15) - one f32 subtraction, the second operand is
+ *     exact.  A sample with yh = 0 is NOT written and keeps its bytes.  w is constant within a block [jB, (j+1)B), so a sample is
+ *     emitted in the call that brings it, whatever the cut: no pending output, no latency.
+ *   End of a complete block [b0, b1): D = sum d^2, E = sum e^2 (int64) and dmax = max |d| over the block; P = sum of x'[u]^2 for u in
+ *     [b1-L, b1-1]; xmax = max |x'[u]| for u in [b0-L+1, b1-1].  Then, in this order:
+ *     1. Guard.  If E > 4 * D + 4096: w = 0, shift = min(shift + 1, CONAN_ECHO_MAX_SHIFT), trips += 1, and NOTHING else happens in this
+ *        block (the detector's hcnt keeps its value).
+ *     2. Double talk (Geigel).  cond = dt_den > 0 and dmax * dt_den > xmax * dt_num (int64 products).  The block is frozen when cond
+ *        holds or hcnt > 0 (its value BEFORE this step).  Then: if cond, hcnt = hang; else if hcnt > 0, hcnt -= 1.  A frozen block
+ *        counts frozen += 1 and has no update.
+ *     3. Idle far end.  P < far_min: no update.
+ *     4. Update.  G[k] = sum over t in the block of e[t] * x'[t-k] (int64, |G| < 2^37); w[k] = clamp(w[k] + (G[k] * 2^(24 - shift)) /
+ *        (P + reg), -(2^31 - 1), 2^31 - 1) with C's int64 division (toward zero; |numerator| < 2^61); adapted += 1.
+ * shift starts at mu_shift.  All sums are exact integers: every reduction order and every cut into calls gives the same bits.
+ * B = 64 and Q24 are choices; no other value was built or timed.
+ * The state restarts (all zero, shift = mu_shift) at the slot's first echo call after a reset that includes CONAN_MODEL_FRONTEND and
+ * when a slot that was off is enabled; a seed replaces it with the seeded record.
+ * Defaults for a rate R (conan_amd._lib.echo_keywords): taps = min(2048, 64 ms rounded to a multiple of 64), delay 0, mu_shift 4,
+ * dt 1/2, hang = 50 ms in blocks (rounded up), reg = taps * 4096, far_min = taps * 1024.  Choices, not measurements. */
+#define CONAN_ECHO_BLOCK 64
+#define CONAN_ECHO_MAX_TAPS 2048
+#define CONAN_ECHO_MAX_DELAY 4096
+#define CONAN_ECHO_MAX_SHIFT 12
+#define CONAN_ECHO_HISTORY 6208 /* far samples a state record keeps: >= MAX_TAPS + BLOCK - 1 + MAX_DELAY */
+typedef struct conan_echo_cfg {
+  int32_t enabled;   /* 0: off (other fields ignored) | 1 */
+  int32_t taps;      /* filter length L: a multiple of 64 in 64 .. CONAN_ECHO_MAX_TAPS */
+  int32_t delay;     /* 0 .. CONAN_ECHO_MAX_DELAY: bulk delay of the far end, in samples */
+  int32_t mu_shift;  /* 0 .. CONAN_ECHO_MAX_SHIFT: starting value of shift */
+  int32_t dt_num;    /* >= 0: Geigel numerator */
+  int32_t dt_den;    /* >= 0: Geigel denominator; 0 turns the detector off */
+  int32_t hang;      /* >= 0: hang-over, in blocks */
+  int32_t reserved;  /* ignored */
+  int64_t reg;       /* 1 .. 2^60: regulariser */
+  int64_t far_min;   /* >= 0: idle threshold on P */
+} conan_echo_cfg; /* 48 bytes */
+/* Sets (cfg->enabled = 1) or removes (0) the canceller for `slots`, with conan_streams_set_conceal's semantics point for point: every
+ * argument is checked before anything changes (CONAN_ERR_INVALID: a field outside its range, a seed that is misaligned or whose rows are
+ * too close), a stream-set without the streaming front-end is CONAN_ERR_STATE, pending pipelined work is joined, and the setting
+ * persists across resets.  A setter call on an enabled slot without a seed replaces the fields and keeps the state: a changed `taps`
+ * keeps the weights that still exist and zeroes the rest (a record always holds zeros in w[taps ..]), a changed `delay` reads the far
+ * history the record already holds, and shift keeps its value.
+ * seed_dev (may be null): row i at seed_dev + i * seed_ld bytes is a record as conan_streams_echo_state writes it and becomes the state
+ * of slots[i] on `stream`; the call reads each seed's `pos` back (one small copy and a wait on `stream`), because the host, not the
+ * record, tells the kernel where in a block a slot stands.
+ * Memory: the first enabling call allocates conan_echo_state_bytes() per slot and 4 row tables; conan_streams_state_bytes counts them
+ * from then on.  A stream-set that never calls the setter allocates nothing and runs exactly the launches it ran before; the step
+ * calls of a stream-set that does run exactly the launches they ran before, too.  Snapshots carry neither the setting nor the state. */
+int conan_streams_set_echo(conan_streams* s, const int32_t* slots, int n, const conan_echo_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream);
+/* Host only: the echo cfg of `slot` as set (zeros for a slot without one). */
+int conan_streams_echo_cfg(const conan_streams* s, int slot, conan_echo_cfg* cfg_out);
+/* Cancels row i in place: samples[i] (host, >= 0) samples in the input format of slots[i] at wav_dev + i * wav_ld * 4 bytes (the step
+ * calls' row stride), the far end in the same format at far_dev + i * far_ld * 4 bytes.  ONE launch (cnk::echo_kernel, one workgroup
+ * per cancelled row) on `stream`; rows of slots without the feature and rows with samples[i] = 0 are skipped and keep their bytes, and
+ * a call with no row to cancel launches nothing and returns CONAN_OK.  The caller orders it in front of the step call and behind
+ * conan_streams_conceal on the same stream.
+ * stats_dev (may be null): int64 [n][4], row i = {sum d^2, sum e^2 over this call's samples, blocks adapted, blocks frozen that
+ * completed in this call}; the host forms ERLE = 10 log10(sum d^2 / sum e^2) from them.  A skipped row reports zeros (when a call
+ * skips a row, the table is cleared by one memset in front of the launch). */
+int conan_streams_echo(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, void* wav_dev, int64_t wav_ld, const void* far_dev,
+                       int64_t far_ld, int64_t* stats_dev, void* stream);
+/* Bytes of one slot's canceller state: a fixed-size, position-independent record, little endian -
+ *   0  int64 pos (samples since the restart; pos mod 64 values of e are pending)    8  int32 shift   12  int32 hcnt
+ *  16  int64 adapted, frozen, trips      40  int64 D, E of the pending block        56  int32 dmax   60  int32 reserved (0)
+ *  64  int32 w[CONAN_ECHO_MAX_TAPS] (zeros from `taps` on)      then int32 e[CONAN_ECHO_BLOCK] of the pending block (zeros behind them)
+ *  then int16 x[CONAN_ECHO_HISTORY]: the last far samples before `pos`, oldest first, UNdelayed (the law reads the last taps + 63 + delay). */
+int64_t conan_echo_state_bytes(void);
+/* The states of `slots` -> row i at state_dev + i * ld bytes (8-byte aligned, ld a multiple of 8 and at least the record's bytes), on
+ * `stream` behind a join of pipelined work.  A slot about to restart reports the restart state (zeros, shift = mu_shift); a slot
+ * without the feature is CONAN_ERR_STATE. */
+int conan_streams_echo_state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream);
+/* The law on whole signals from the zero state, in place, and the bit-exact yardstick of the streaming form: row i (n rows in
+ * 1 .. 65535) holds samples[i] (host) samples of `format` (CONAN_SAMPLE_*) at x_dev + i * ld * 4 bytes, its far end lies at
+ * far_dev + i * far_ld * 4 bytes.  cfg->enabled must be 1.  stats_dev as above (may be null).  One launch of the same kernel, which
+ * walks a row block by block. */
+int conan_echo(conan_ctx* ctx, const conan_echo_cfg* cfg, int format, void* x_dev, int64_t ld, const void* far_dev, int64_t far_ld, int n,
+               const int64_t* samples, int64_t* stats_dev, void* stream);
+
 /* Silence trimming (added within ABI 9: a caller detects it by the exported symbol; no existing struct or call changes).  The offline
  * half of source activity: the reference's trim_long_sil (utils/audio/vad.py, trim_long_silences) cuts the long pauses out of a whole
  * recording - a moving average over an external detector's flags, a dilation that keeps short pauses, a hard cut - and this call does
