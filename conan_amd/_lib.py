@@ -102,6 +102,14 @@ _PROTOS = {
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_resample_length": (C.c_int64, [C.c_void_p, C.c_int64]),
     "conan_resample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_resample_drift_length": (C.c_int64, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]),
+    "conan_resample_drift_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "conan_resample_drift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_int64, C.c_void_p, C.c_void_p]),
+    "conan_streams_set_input_drift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "conan_streams_input_drift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "conan_streams_set_output_drift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "conan_streams_output_drift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_loud_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "conan_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_streams_set_input_rate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -247,6 +255,50 @@ RESAMPLE_PRESETS = {
 }
 
 
+# conan_resample_drift: the side a drift describes, the law's limits, and the schedule a caller writes in ppm
+DRIFT_SOURCE, DRIFT_SINK = 0, 1
+DRIFT_SIDES = {"source": DRIFT_SOURCE, "sink": DRIFT_SINK}
+DRIFT_MAX_PPB = 2000000
+DRIFT_MAX_SEGMENTS = 32
+DRIFT_PHASES = 1024
+
+
+def drift_ppb(ppm):
+    """ppm (float) -> the law's integer ppb, round(ppm * 1000); |ppb| <= DRIFT_MAX_PPB."""
+    ppb = int(round(float(ppm) * 1000))
+    if abs(ppb) > DRIFT_MAX_PPB:
+        raise ValueError("drift must be within +-%g ppm, got %r" % (DRIFT_MAX_PPB / 1000.0, ppm))
+    return ppb
+
+
+def drift_ppb_rows(ppm, n):
+    """One ppm for all of n slots, or one per slot -> int32 [n] ppb."""
+    import numpy as np
+    vals = [ppm] * n if isinstance(ppm, (int, float)) else list(ppm)
+    if len(vals) != n:
+        raise ValueError("%d drift values for %d slots" % (len(vals), n))
+    return np.ascontiguousarray([drift_ppb(v) for v in vals], dtype=np.int32)
+
+
+def drift_side(side):
+    if side not in DRIFT_SIDES:
+        raise ValueError("side must be one of %s, got %r" % (sorted(DRIFT_SIDES), side))
+    return DRIFT_SIDES[side]
+
+
+def drift_schedule(drift):
+    """A ppm float, or a list of (output_index, ppm) -> (at int64 [n_seg], ppb int32 [n_seg]) as conan_resample_drift takes them."""
+    import numpy as np
+    seq = [(0, drift)] if isinstance(drift, (int, float)) else [(int(a), p) for a, p in drift]
+    if not seq or seq[0][0] != 0:
+        raise ValueError("a drift schedule starts at output index 0")
+    if any(b[0] <= a[0] for a, b in zip(seq, seq[1:])):
+        raise ValueError("the output indices of a drift schedule must be strictly ascending")
+    if len(seq) > DRIFT_MAX_SEGMENTS:
+        raise ValueError("a drift schedule has at most %d segments" % DRIFT_MAX_SEGMENTS)
+    return (np.ascontiguousarray([a for a, _ in seq], dtype=np.int64), np.ascontiguousarray([drift_ppb(p) for _, p in seq], dtype=np.int32))
+
+
 # CONAN_SAMPLE_*: the sample formats of the audio rows (conan_streams_set_input_format / _output_format, conan_convert_samples)
 SAMPLE_F32, SAMPLE_S16, SAMPLE_ULAW, SAMPLE_ALAW = 0, 1, 2, 3
 SAMPLE_FORMATS = {"f32": SAMPLE_F32, "s16": SAMPLE_S16, "ulaw": SAMPLE_ULAW, "alaw": SAMPLE_ALAW}
@@ -280,6 +332,27 @@ def resample_cfg(orig_freq, new_freq=16000, lowpass_filter_width=6, rolloff=0.99
     window = RESAMPLE_HANN if resampling_method == "sinc_interp_hann" else RESAMPLE_KAISER
     return ResampleCfg(int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff), window,
                        float(beta) if beta is not None else 0.0, (C.c_int32 * 2)(0, 0))
+
+
+def resample_drift_table(orig_freq, new_freq=16000, **filter):
+    """conan_resample_drift_table (host only; needs no device): the drift resampler's f32 table, numpy [1025, 2W]."""
+    import numpy as np
+    cfg = resample_cfg(orig_freq, new_freq, **filter)
+    W = C.c_int32(0)
+    count = check(lib().conan_resample_drift_table(C.byref(cfg), C.byref(W), None, 0))
+    tab = np.empty(count, dtype=np.float32)
+    check(lib().conan_resample_drift_table(C.byref(cfg), C.byref(W), tab.ctypes.data, count))
+    return tab.reshape(DRIFT_PHASES + 1, 2 * W.value)
+
+
+def resample_drift_length(orig_freq, new_freq, samples, drift, side="source", **filter):
+    """conan_resample_drift_length (host only, exact): the outputs of `samples` inputs under the schedule (Context.resample_drift's)."""
+    cfg = resample_cfg(orig_freq, new_freq, **filter)
+    at, ppb = drift_schedule(drift)
+    n = lib().conan_resample_drift_length(C.byref(cfg), drift_side(side), int(samples), at.ctypes.data, ppb.ctypes.data, len(at))
+    if n < 0:
+        raise ValueError("resample_drift_length: the library refuses this configuration or schedule")
+    return n
 
 
 SLOT_META_BYTES = 256

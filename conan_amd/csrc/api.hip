@@ -336,7 +336,7 @@ int conan_streams_reset(conan_streams* s, const int32_t* slots, int n, int which
       s->wm.restart(slots, n);      // the watermark's setting stays; its state restarts in the slots' next step rows
       s->out_eq.restart(slots, n);  // ... and the output equaliser's
       if (!s->wav_out.or_slot.empty())
-        for (int i = 0; i < n; ++i) { conan_streams::OrSlot& o = s->wav_out.or_slot[slots[i]]; o.out = 0; o.flushed = 0; }
+        for (int i = 0; i < n; ++i) { conan_streams::OrSlot& o = s->wav_out.or_slot[slots[i]]; o.out = 0; o.flushed = 0; o.dr.restart(); }
     }
     if (models & CONAN_MODEL_EMFORMER) zero(s->emf_state, s->pos_emf);
     if (models & CONAN_MODEL_CONAN) zero(s->dec_state, s->pos_dec);
@@ -347,7 +347,7 @@ int conan_streams_reset(conan_streams* s, const int32_t* slots, int n, int which
       for (int i = 0; i < n; ++i) s->wav_in.fe_slot[slots[i]] = conan_streams::FeSlot();
       // the input rate stays; the resampler's history restarts (inputs before the first are zero, the ring needs no clearing)
       if (!s->wav_in.rs_slot.empty())
-        for (int i = 0; i < n; ++i) { conan_streams::RsSlot& r = s->wav_in.rs_slot[slots[i]]; r.in = 0; r.out = 0; r.phase = 0; }
+        for (int i = 0; i < n; ++i) { conan_streams::RsSlot& r = s->wav_in.rs_slot[slots[i]]; r.in = 0; r.out = 0; r.phase = 0; r.dr.restart(); }
       // the features' settings stay; their states restart in the slots' next rows
       s->restart_features(slots, n);
     }
@@ -712,6 +712,25 @@ int conan_resample(conan_ctx* ctx, const conan_resample_cfg* cfg, const float* x
   });
 }
 
+int conan_resample_drift(conan_ctx* ctx, const conan_resample_cfg* cfg, int side, const float* x_dev, int n, int64_t samples, const int64_t* at,
+                         const int32_t* ppb, int n_seg, float* y_dev, int64_t y_ld, int64_t* out_samples, void* stream) {
+  return guarded([&] {
+    if (!ctx || !cfg || !x_dev || !y_dev || !at || !ppb) throw Error(CONAN_ERR_INVALID, "null argument");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    conan_ctx_resample_drift(ctx, *cfg, side, x_dev, n, samples, at, ppb, n_seg, y_dev, y_ld, out_samples, (hipStream_t)stream);
+  });
+}
+
+int64_t conan_resample_drift_table(const conan_resample_cfg* cfg, int32_t* W, float* table, int64_t cap) {
+  try {      // (host only, and no launch to answer for: it also runs where no device is)
+    if (!cfg) throw Error(CONAN_ERR_INVALID, "null argument");
+    return conan_ctx_resample_drift_table(*cfg, W, table, cap);
+  } catch (const ch::Error& e) {
+    g_err = e.what();
+    return e.code;
+  }
+}
+
 int conan_loud_norm(conan_ctx* ctx, const conan_loudness_cfg* cfg, const float* x_dev, int64_t x_ld, int n, const int64_t* samples, float* y_dev,
                     int64_t y_ld, double* stats_dev, void* stream) {
   return guarded([&] {
@@ -827,6 +846,22 @@ int conan_streams_denoise_state(conan_streams* s, const int32_t* slots, int n, v
 
 int conan_streams_set_input_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg) {
   return guarded([&] { wavio::set_input_rate(s, slots, n, cfg); });
+}
+
+int conan_streams_set_input_drift(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg, const int32_t* ppb) {
+  return guarded([&] { wavio::set_drift(s, CONAN_DRIFT_SOURCE, slots, n, cfg, ppb); });
+}
+
+int conan_streams_set_output_drift(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg, const int32_t* ppb) {
+  return guarded([&] { wavio::set_drift(s, CONAN_DRIFT_SINK, slots, n, cfg, ppb); });
+}
+
+int conan_streams_input_drift(conan_streams* s, const int32_t* slots, int n, int32_t* ppb_out, int64_t* in_out, int64_t* out_out) {
+  return guarded([&] { wavio::get_drift(s, CONAN_DRIFT_SOURCE, slots, n, ppb_out, in_out, out_out); });
+}
+
+int conan_streams_output_drift(conan_streams* s, const int32_t* slots, int n, int32_t* ppb_out, int64_t* in_out, int64_t* out_out) {
+  return guarded([&] { wavio::get_drift(s, CONAN_DRIFT_SINK, slots, n, ppb_out, in_out, out_out); });
 }
 
 int conan_streams_set_output_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg) {

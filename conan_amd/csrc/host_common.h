@@ -109,6 +109,33 @@ struct RsTable {
     return best;
   }
 };
+// One drift-resampler configuration (resample.hip): the f32 table of the law, [kDrPhases + 1][2W] on the host, and its device form.
+struct DrTable {
+  std::vector<float> host;
+  const float2* dev = nullptr;        // (T, D) at k * kDrPhases + p
+  int W = 0, in_rate = 0, out_rate = 0;
+};
+// A stream slot's place in the drift law: since the last change of ppb, output j >= out0 sits at (n0 << 32) + f0 + (j - out0) * step.
+// Output 0 sits at position 0; a change takes effect at the next output, one new step past the last one produced.
+struct DriftPos {
+  typedef unsigned __int128 u128;
+  const DrTable* d = nullptr;         // null: the slot has no drift
+  int ppb = 0, win = 0;               // win: LDS floats of a tile's window at the side's largest step
+  unsigned long long step = 0;
+  long long out0 = 0, n0 = 0; unsigned f0 = 0;
+  u128 pos(long long j) const { return (((u128)n0 << 32) | f0) + (u128)(j - out0) * step; }
+  // the first output j >= out0 whose input index n_j is at or past `limit`
+  long long first_at(long long limit) const {
+    const u128 base = pos(out0), end = limit > 0 ? (u128)limit << 32 : 0;
+    return end <= base ? out0 : out0 + (long long)((end - base + step - 1) / step);
+  }
+  // ppb changes in front of output `next` (the slot's next one)
+  void retime(int new_ppb, unsigned long long new_step, long long next) {
+    if (next > 0) { const u128 p = pos(next - 1) + new_step; n0 = (long long)(p >> 32); f0 = (unsigned)p; out0 = next; }
+    ppb = new_ppb; step = new_step;
+  }
+  void restart() { out0 = 0; n0 = 0; f0 = 0; }
+};
 // Pinned staging of a whole-signal call's host table (loudness.hip): a buffer is reused only after the copy that read it has
 // completed (the wait is on the host, for a copy four calls old).
 struct TableStage {
@@ -174,12 +201,22 @@ struct conan_ctx {
   // resampler (resample.hip): taps built on first use per configuration (CONAN_ERR_INVALID for a configuration it refuses)
   std::map<std::string, ch::RsTable> rs_tabs;
   const ch::RsTable& resample_table(const conan_resample_cfg& c);
+  std::map<std::string, ch::DrTable> dr_tabs;              // drift resampler: table built on first use per configuration
+  const ch::DrTable& drift_table(const conan_resample_cfg& c);
   ch::TableStage loud_stage;                               // conan_loud_norm's per-call table (loudness.hip)
   ~conan_ctx();
 };
 
 // conan_resample's body (resample.hip)
 void conan_ctx_resample(conan_ctx* ctx, const conan_resample_cfg& c, const float* x, int n, int64_t samples, float* y, int64_t* out_samples, hipStream_t st);
+// conan_resample_drift's and conan_resample_drift_table's bodies (resample.hip)
+void conan_ctx_resample_drift(conan_ctx* ctx, const conan_resample_cfg& c, int side, const float* x, int n, int64_t samples, const int64_t* at,
+                              const int32_t* ppb, int n_seg, float* y, int64_t y_ld, int64_t* out_samples, hipStream_t st);
+int64_t conan_ctx_resample_drift_table(const conan_resample_cfg& c, int32_t* W_out, float* table, int64_t cap);
+namespace drift {
+unsigned long long step(const conan_resample_cfg& c, int side, int ppb);      // the law's step; CONAN_ERR_INVALID for a side or ppb it refuses
+int tile_window(const conan_resample_cfg& c, int side);                       // LDS floats of a tile at the side's largest step
+}  // namespace drift
 // the K-weighting biquads at rate fs and the transition matrix M[16] of kLdSeg zero inputs (loudness.hip; shared with level.hip)
 void conan_k_weighting(double fs, cnk::LdBiquad& shelf, cnk::LdBiquad& hp, double* M);
 // conan_level's body, and the leveller's host arithmetic that wavio.hip shares (level.hip)

@@ -825,6 +825,10 @@ struct RsFilter {
 // other than f32 is packed from the row's first byte; row strides stay in 4-byte units, so every row starts on a dword.
 constexpr int kFmtF32 = 0, kFmtS16 = 1, kFmtUlaw = 2, kFmtAlaw = 3;
 constexpr int kRsCopy = 1, kRsFmtShift = 8;      // RsRow::mode: bit 0 = the row has no rate, bits 8.. = the format of the caller's row
+// A drift row (conan_streams_set_input_drift / _output_drift; RsRow::mode bit 1, RsOutRow::L == kOrDriftL) reuses the rational fields:
+// taps = the drift table (float2), ph = the step (its 64 bits in the pointer), out0 = the input index n of the call's first output,
+// orig = that output's 32-bit fraction, w = W; output t of the call sits at (out0 << 32) + orig + t * step.
+constexpr int kRsDrift = 2, kOrDriftL = -1;
 constexpr int kOrDstBits = 24;                   // RsOutRow::dst: the row index in the low 24 bits, the format of the caller's row above
 struct RsRow {                        // one call row of resample_stream_kernel (16 ints, uploaded through PinRing)
   long long in0, out0;                // input samples received before this call; model-rate samples handed over before it
@@ -857,6 +861,24 @@ struct ResampleOutArgs {
   const RsOutRow* rows; int n, tiles, win;
 };
 void launch_resample_out(const ResampleOutArgs& a, hipStream_t st);
+// Drift resampler (conan_resample_drift; the law is include/conan_hip.h's): output j sits at the 32.32 fixed-point input position pos_j;
+// its 2W taps are row p = frac >> 22 of a table of kDrPhases + 1 phases, interpolated towards row p + 1 by the low 22 bits.  The device
+// table holds (T[p][k], T[p + 1][k] - T[p][k]) as one float2 at k * kDrPhases + p (phase-fastest).  A workgroup takes kRsTile outputs of
+// one row; positions are monotone, so the tile's window is [n_first - W + 1, n_last + W].
+constexpr int kDrPhases = 1024, kDrFracBits = 22;
+constexpr int kDrMaxTaps = 512;       // 2W at most
+constexpr int kDrMaxSeg = 32;         // segments of a whole-signal schedule (passed by value)
+struct DrSchedule {                   // segment q: outputs [at[q], at[q + 1]) at pos[q] + (j - at[q]) * step[q]
+  long long at[kDrMaxSeg];
+  unsigned long long pos[kDrMaxSeg], step[kDrMaxSeg];
+  int n;
+};
+struct ResampleDriftArgs {
+  const float* x; float* y; long long samples, nout, y_ld;     // x [n][samples] -> y rows at y_ld floats
+  const float2* tab; int W, win;                               // win: LDS floats of a tile's window (upper bound)
+  DrSchedule s;
+};
+void launch_resample_drift(const ResampleDriftArgs& a, int n, hipStream_t st);
 // Whole signals from one sample format to another through the float rule (conan_convert_samples): n rows of `samples`, strides in dwords.
 struct ConvertSamplesArgs { const void* src; void* dst; long long src_ld, dst_ld, samples; int src_fmt, dst_fmt; };
 void launch_convert_samples(const ConvertSamplesArgs& a, int n, hipStream_t st);

@@ -51,6 +51,49 @@ __device__ __forceinline__ float rs_output(float* lds, long long j0, long long j
   return rs_dot(w, (int)(first - lo), wlen, f.taps, f.nph, p, f.L, cnt);
 }
 
+// Drift resampler: the output at 32.32 position (nb << 32) + rel of one row (the caller clamps it into the tile's valid outputs).
+// rel_first and rel_last belong to the tile's first and last valid output (block-uniform): positions are monotone, so the tile's
+// input window is [n_first - W + 1, n_last + W], loaded once with fetch(i) (input i, zero outside the signal).  The tap loop's trip
+// count, 2W, is uniform; its window index is clamped, so every load stays inside the window whatever the position.  Every thread
+// of the block must call it (barrier).  Shared by the whole-signal kernel and both stream kernels: one sum, the same bits.
+template <class Fetch>
+__device__ __forceinline__ float dr_output(float* w, long long nb, unsigned long long rel_first, unsigned long long rel_last, unsigned long long rel, int W,
+                                           const float2* __restrict__ tab, int win, const Fetch& fetch) {
+  const long long lo = nb + (long long)(rel_first >> 32) - W + 1;
+  const int wlen = max(1, min((int)(nb + (long long)(rel_last >> 32) + W - lo) + 1, win));
+  for (int t = threadIdx.x; t < wlen; t += blockDim.x) w[t] = fetch(lo + t);
+  __syncthreads();
+  const unsigned f = (unsigned)rel;
+  const int p = (int)(f >> kDrFracBits);
+  const float mu = (float)(f & ((1u << kDrFracBits) - 1)) * (1.f / (float)(1 << kDrFracBits));      // exact: 22 bits
+  const int off = (int)(nb + (long long)(rel >> 32) - W + 1 - lo);
+  float acc = 0.f;
+#pragma unroll 8      // the loads of 8 taps issue together; the FMA chain keeps its order
+  for (int k = 0; k < 2 * W; ++k) {
+    const float2 td = tab[(size_t)k * kDrPhases + p];
+    const float h = fmaf(mu, td.y, td.x);
+    const float x = w[min(max(off + k, 0), wlen - 1)];
+    acc = fmaf(h, x, acc);
+  }
+  return acc;
+}
+
+// A drift row of the stream kernels: output t of the call (t < h) sits at (n0 << 32) + f0 + t * step
+struct DrRow { long long n0; unsigned long long step; unsigned f0; int W; const float2* tab; };
+template <class Row>
+__device__ __forceinline__ DrRow dr_row(const Row& R) {
+  DrRow d;
+  d.n0 = R.out0; d.step = (unsigned long long)reinterpret_cast<uintptr_t>(R.ph); d.f0 = (unsigned)R.orig; d.W = R.w;
+  d.tab = reinterpret_cast<const float2*>(R.taps);
+  return d;
+}
+template <class Fetch>
+__device__ __forceinline__ float dr_stream_output(float* lds, const DrRow& d, int tile0, int t, int h, int win, const Fetch& fetch) {
+  const int tl = min(tile0 + kRsTile - 1, h - 1), tc = min(t, tl);
+  return dr_output(lds, d.n0, d.f0 + (unsigned long long)tile0 * d.step, d.f0 + (unsigned long long)tl * d.step, d.f0 + (unsigned long long)tc * d.step,
+                   d.W, d.tab, win, fetch);
+}
+
 __global__ __launch_bounds__(kRsTile) void resample_kernel(const ResampleArgs a) {
   extern __shared__ float lds[];
   const long long j0 = (long long)blockIdx.x * kRsTile, jt = j0 + threadIdx.x;
@@ -93,9 +136,14 @@ __global__ __launch_bounds__(kRsTile) void resample_stream_kernel(const Resample
       const float vr = ring[i & (kRsRing - 1)];
       return (i < 0 || i >= end) ? 0.f : (d >= 0 ? vw : vr);
     };
-    RsFilter f; f.taps = R.taps; f.ph = R.ph; f.orig = R.orig; f.nph = R.nph; f.w = R.w; f.L = R.L;
-    const float y = rs_output(lds, j0, act ? jt : R.out0 + R.h - 1, f, a.win, fetch);
-    if (act) out[jt - R.out0] = y;
+    if (R.mode & kRsDrift) {                      // uniform per block: a drift row (out0 = the first output's input index)
+      const float y = dr_stream_output(lds, dr_row(R), (int)blockIdx.x * kRsTile, t0, R.h, a.win + 2, fetch);
+      if (act) out[t0] = y;
+    } else {
+      RsFilter f; f.taps = R.taps; f.ph = R.ph; f.orig = R.orig; f.nph = R.nph; f.w = R.w; f.L = R.L;
+      const float y = rs_output(lds, j0, act ? jt : R.out0 + R.h - 1, f, a.win, fetch);
+      if (act) out[jt - R.out0] = y;
+    }
   }
   for (int t = t0; t < R.m; t += stride) ring[(R.in0 + t) & (kRsRing - 1)] = load_sample(fmt, wav, t);
 }
@@ -131,11 +179,41 @@ __global__ __launch_bounds__(kRsTile) void resample_out_kernel(const ResampleOut
       const float vr = ring[i & mask];
       return (i < 0 || i >= end) ? 0.f : (d >= 0 ? vw : vr);
     };
-    RsFilter f; f.taps = R.taps; f.ph = R.ph; f.orig = R.orig; f.nph = R.nph; f.w = R.w; f.L = R.L;
-    const float y = rs_output(lds, j0, act ? jt : R.out0 + R.h - 1, f, a.win, fetch);
+    float y;
+    if (R.L == kOrDriftL) {                       // uniform per block: a drift row (out0 = the first output's input index)
+      y = dr_stream_output(lds, dr_row(R), (int)blockIdx.x * kRsTile, t0, R.h, a.win + 2, fetch);
+    } else {
+      RsFilter f; f.taps = R.taps; f.ph = R.ph; f.orig = R.orig; f.nph = R.nph; f.w = R.w; f.L = R.L;
+      y = rs_output(lds, j0, act ? jt : R.out0 + R.h - 1, f, a.win, fetch);
+    }
     store_sample(fmt, out, t0, R.h, y);           // (every thread of the block: t0 >= h stores nothing)
   }
   for (int t = t0; t < R.m; t += stride) ring[(R.in0 + t) & mask] = wav[t];
+}
+
+// position of output j under a whole-signal schedule (every load uniform: the selects keep the last segment that starts at or before j)
+__device__ __forceinline__ unsigned long long dr_schedule_pos(const DrSchedule& s, long long j) {
+  unsigned long long pos = (unsigned long long)j * s.step[0];
+  for (int q = 1; q < s.n; ++q) {
+    const unsigned long long c = s.pos[q] + (unsigned long long)(j - s.at[q]) * s.step[q];
+    pos = j >= s.at[q] ? c : pos;
+  }
+  return pos;
+}
+
+__global__ __launch_bounds__(kRsTile) void resample_drift_kernel(const ResampleDriftArgs a) {
+  extern __shared__ float lds[];
+  const long long j0 = (long long)blockIdx.x * kRsTile, jt = j0 + threadIdx.x;
+  const long long jl = min(j0 + kRsTile - 1, a.nout - 1);
+  const bool act = jt < a.nout;
+  const float* x = a.x + (size_t)blockIdx.y * a.samples;
+  const long long N = a.samples;
+  auto fetch = [&](long long i) {
+    const float v = x[i < 0 ? 0 : (i >= N ? N - 1 : i)];
+    return (i >= 0 && i < N) ? v : 0.f;
+  };
+  const float y = dr_output(lds, 0, dr_schedule_pos(a.s, j0), dr_schedule_pos(a.s, jl), dr_schedule_pos(a.s, act ? jt : jl), a.W, a.tab, a.win, fetch);
+  if (act) a.y[(size_t)blockIdx.y * a.y_ld + jt] = y;
 }
 
 // conan_convert_samples: row r (blockIdx.y), samples [0, samples) in groups of four per lane group, any format to any format.
@@ -158,6 +236,11 @@ void launch_resample_stream(const ResampleStreamArgs& a, hipStream_t st) {
 
 void launch_resample_out(const ResampleOutArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(resample_out_kernel, dim3((unsigned)a.tiles, (unsigned)a.n), dim3(kRsTile), (size_t)(a.win + 2) * sizeof(float), st, a);
+}
+
+void launch_resample_drift(const ResampleDriftArgs& a, int n, hipStream_t st) {
+  const dim3 grid((unsigned)((a.nout + kRsTile - 1) / kRsTile), (unsigned)n);
+  hipLaunchKernelGGL(resample_drift_kernel, grid, dim3(kRsTile), (size_t)a.win * sizeof(float), st, a);
 }
 
 void launch_convert_samples(const ConvertSamplesArgs& a, int n, hipStream_t st) {
@@ -284,6 +367,171 @@ void conan_ctx_resample(conan_ctx* ctx, const conan_resample_cfg& c, const float
   cnk::ResampleArgs a;
   a.x = x; a.y = y; a.samples = samples; a.nout = nout; a.f = t.f; a.win = t.win;
   cnk::launch_resample(a, n, st);
+  HIP_CHECK(hipGetLastError());
+  if (out_samples) *out_samples = nout;
+}
+
+// ---- drift resampler (conan_resample_drift*): the law is include/conan_hip.h's.  All position arithmetic is in integers; the host's
+// counts come from the closed-form positions, in 128 bits where a product can pass 64.
+namespace drift {
+
+using ch::Error;
+typedef unsigned __int128 u128;
+
+// W and base / in_rate of a configuration; CONAN_ERR_INVALID for one the drift resampler refuses
+static int shape(const conan_resample_cfg& c, double* scale) {
+  (void)rs_shape(c);      // the rate, width, rolloff and window limits are conan_resample's
+  const double base = (double)std::min(c.in_rate, c.out_rate) * (double)c.rolloff;
+  const int W = (int)std::ceil(c.lowpass_filter_width * (double)c.in_rate / base);
+  if (2 * W > cnk::kDrMaxTaps) throw Error(CONAN_ERR_INVALID, "resample_drift: more than 512 taps (2W) for these rates and this filter");
+  if (scale) *scale = base / c.in_rate;
+  return W;
+}
+
+static void check_ppb(int side, long long ppb) {
+  if (side != CONAN_DRIFT_SOURCE && side != CONAN_DRIFT_SINK) throw Error(CONAN_ERR_INVALID, "resample_drift: side must be CONAN_DRIFT_SOURCE or CONAN_DRIFT_SINK");
+  if (ppb < -CONAN_DRIFT_MAX_PPB || ppb > CONAN_DRIFT_MAX_PPB) throw Error(CONAN_ERR_INVALID, "resample_drift: |ppb| must be at most 2 000 000");
+}
+
+unsigned long long step(const conan_resample_cfg& c, int side, int ppb) {
+  check_ppb(side, ppb);
+  const u128 G = 1000000000u;
+  const u128 num = side == CONAN_DRIFT_SOURCE ? (u128)c.in_rate * (u128)(1000000000ll + ppb) : (u128)c.in_rate * G;
+  const u128 den = side == CONAN_DRIFT_SOURCE ? (u128)c.out_rate * G : (u128)c.out_rate * (u128)(1000000000ll + ppb);
+  return (unsigned long long)((num << 32) / den);
+}
+
+// LDS floats of a tile's window at the largest step the side can have
+int tile_window(const conan_resample_cfg& c, int side) {
+  const int W = shape(c, nullptr);
+  const unsigned long long smax = step(c, side, side == CONAN_DRIFT_SOURCE ? CONAN_DRIFT_MAX_PPB : -CONAN_DRIFT_MAX_PPB);
+  const u128 span = (u128)(cnk::kRsTile - 1) * smax;
+  const long long win = (long long)((span + 0xffffffffu) >> 32) + 2 * W + 2;
+  if (win > cnk::kRsMaxWindow) throw Error(CONAN_ERR_INVALID, "resample_drift: input window of a tile too large");
+  return (int)win;
+}
+
+// the schedule's checks; the position of each segment's first output (128 bits: a long signal's positions pass 2^64)
+static void positions(const conan_resample_cfg& c, int side, const int64_t* at, const int32_t* ppb, int n_seg, std::vector<u128>& pos,
+                      std::vector<unsigned long long>& st) {
+  if (!at || !ppb) throw Error(CONAN_ERR_INVALID, "null argument");
+  if (n_seg < 1 || n_seg > CONAN_DRIFT_MAX_SEGMENTS) throw Error(CONAN_ERR_INVALID, "resample_drift: n_seg must be in 1 .. CONAN_DRIFT_MAX_SEGMENTS");
+  if (at[0] != 0) throw Error(CONAN_ERR_INVALID, "resample_drift: at[0] must be 0");
+  pos.assign(n_seg, 0); st.assign(n_seg, 0);
+  for (int k = 0; k < n_seg; ++k) {
+    if (k && at[k] <= at[k - 1]) throw Error(CONAN_ERR_INVALID, "resample_drift: at[] must be strictly ascending");
+    st[k] = step(c, side, ppb[k]);
+    // output at[k] is the first at the new step: one step of segment k past the last output of segment k - 1
+    if (k) pos[k] = pos[k - 1] + (u128)(at[k] - 1 - at[k - 1]) * st[k - 1] + st[k];
+  }
+}
+
+// outputs j with pos_j >> 32 < samples
+static long long length(const std::vector<u128>& pos, const std::vector<unsigned long long>& st, const int64_t* at, int64_t samples) {
+  const u128 end = (u128)samples << 32;
+  const int n_seg = (int)pos.size();
+  for (int k = 0; k < n_seg; ++k) {
+    if (pos[k] >= end) return at[k];
+    const u128 cnt = (end - pos[k] + st[k] - 1) / st[k];      // outputs of an unbounded segment k below `end`
+    if (k + 1 == n_seg || cnt < (u128)(at[k + 1] - at[k])) return (long long)(at[k] + (long long)cnt);
+  }
+  return 0;
+}
+
+// T[p][k], p = 0 .. kDrPhases, k = 0 .. 2W - 1, in double, rounded once
+static void host_table(const conan_resample_cfg& c, int& W, std::vector<float>& tab) {
+  double scale;
+  W = shape(c, &scale);
+  const int lpw = c.lowpass_filter_width;
+  const double beta = c.window == CONAN_RESAMPLE_KAISER ? (c.beta > 0.f ? (double)c.beta : kKaiserBeta) : 0.0;
+  const double PI = 3.14159265358979323846, i0b = beta > 0 ? bessel_i0(beta) : 1.0;
+  tab.assign((size_t)(cnk::kDrPhases + 1) * 2 * W, 0.f);
+  for (int p = 0; p <= cnk::kDrPhases; ++p)
+    for (int k = 0; k < 2 * W; ++k) {
+      const double t = ((double)(k - W + 1) - (double)p / cnk::kDrPhases) * scale;
+      if (!(std::fabs(t) < lpw)) continue;
+      const double u = t / lpw;
+      const double window = beta > 0 ? bessel_i0(beta * std::sqrt(1.0 - u * u)) / i0b : std::pow(std::cos(t * PI / lpw / 2), 2);
+      // sin(pi t) through t's distance r from the nearest integer m: (-1)^m sin(pi r), exactly 0 at an integer t
+      const double m = std::nearbyint(t), r = t - m;
+      const double sn = std::fmod(m, 2.0) != 0.0 ? -std::sin(PI * r) : std::sin(PI * r);
+      const double sinc = t == 0 ? 1.0 : sn / (PI * t);
+      tab[(size_t)p * 2 * W + k] = (float)(sinc * (window * scale));
+    }
+}
+
+}  // namespace drift
+
+const ch::DrTable& conan_ctx::drift_table(const conan_resample_cfg& c) {
+  (void)drift::shape(c, nullptr);
+  const double beta = c.window == CONAN_RESAMPLE_KAISER ? (c.beta > 0.f ? (double)c.beta : kKaiserBeta) : 0.0;
+  char key[160];
+  snprintf(key, sizeof(key), "dr.%d.%d.%d.%.9g.%d.%.17g", c.in_rate, c.out_rate, c.lowpass_filter_width, (double)c.rolloff, c.window, beta);
+  auto it = dr_tabs.find(key);
+  if (it != dr_tabs.end()) return it->second;
+  ch::DrTable t;
+  drift::host_table(c, t.W, t.host);
+  const int L = 2 * t.W, P = cnk::kDrPhases;
+  std::vector<float> td((size_t)2 * L * P);
+  for (int k = 0; k < L; ++k)
+    for (int p = 0; p < P; ++p) {
+      const float a = t.host[(size_t)p * L + k], b = t.host[(size_t)(p + 1) * L + k];
+      td[2 * ((size_t)k * P + p)] = a;
+      td[2 * ((size_t)k * P + p) + 1] = b - a;
+    }
+  float* d = dev_alloc(td.size(), false);
+  HIP_CHECK(hipMemcpy(d, td.data(), td.size() * sizeof(float), hipMemcpyHostToDevice));
+  t.dev = reinterpret_cast<const float2*>(d);
+  t.in_rate = c.in_rate; t.out_rate = c.out_rate;
+  return dr_tabs[key] = std::move(t);
+}
+
+int64_t conan_resample_drift_length(const conan_resample_cfg* cfg, int side, int64_t samples, const int64_t* at, const int32_t* ppb, int n_seg) {
+  if (!cfg || samples < 0) return -1;
+  try {
+    (void)drift::shape(*cfg, nullptr);
+    std::vector<drift::u128> pos; std::vector<unsigned long long> st;
+    drift::positions(*cfg, side, at, ppb, n_seg, pos, st);
+    return drift::length(pos, st, at, samples);
+  } catch (...) {
+    return -1;
+  }
+}
+
+int64_t conan_ctx_resample_drift_table(const conan_resample_cfg& c, int32_t* W_out, float* table, int64_t cap) {
+  int W; std::vector<float> tab;
+  drift::host_table(c, W, tab);
+  if (W_out) *W_out = W;
+  if (table) {
+    if (cap < (int64_t)tab.size()) throw ch::Error(CONAN_ERR_INVALID, "conan_resample_drift_table: cap below (1024 + 1) * 2W floats");
+    memcpy(table, tab.data(), tab.size() * sizeof(float));
+  }
+  return (int64_t)tab.size();
+}
+
+void conan_ctx_resample_drift(conan_ctx* ctx, const conan_resample_cfg& c, int side, const float* x, int n, int64_t samples, const int64_t* at,
+                              const int32_t* ppb, int n_seg, float* y, int64_t y_ld, int64_t* out_samples, hipStream_t st) {
+  using ch::Error;
+  if (n < 1 || n > 65535) throw Error(CONAN_ERR_INVALID, "resample_drift: n must be in 1 .. 65535");
+  if (samples < 1 || samples >= (1ll << 31) - cnk::kDrMaxTaps) throw Error(CONAN_ERR_INVALID, "resample_drift: samples must be in 1 .. 2^31 - 513");
+  const int W = drift::shape(c, nullptr);
+  const int win = drift::tile_window(c, side);
+  std::vector<drift::u128> pos; std::vector<unsigned long long> steps;
+  drift::positions(c, side, at, ppb, n_seg, pos, steps);
+  const long long nout = drift::length(pos, steps, at, samples);
+  if (nout < 1 || (nout + cnk::kRsTile - 1) / cnk::kRsTile > INT_MAX) throw Error(CONAN_ERR_INVALID, "resample_drift: signal too long");
+  if (y_ld < nout) throw Error(CONAN_ERR_INVALID, "resample_drift: y_ld below the output length (conan_resample_drift_length)");
+  const ch::DrTable& t = ctx->drift_table(c);
+  cnk::ResampleDriftArgs a;
+  a.x = x; a.y = y; a.samples = samples; a.nout = nout; a.y_ld = y_ld; a.tab = t.dev; a.W = W; a.win = win;
+  // segments that start at or past the end produce nothing: the kernel sees the ones below it (their positions fit 64 bits)
+  a.s.n = 0;
+  for (int k = 0; k < n_seg && at[k] < nout; ++k) {
+    a.s.at[k] = at[k]; a.s.pos[k] = (unsigned long long)pos[k]; a.s.step[k] = steps[k];
+    a.s.n = k + 1;
+  }
+  for (int k = a.s.n; k < cnk::kDrMaxSeg; ++k) { a.s.at[k] = 0; a.s.pos[k] = 0; a.s.step[k] = 0; }
+  cnk::launch_resample_drift(a, n, st);
   HIP_CHECK(hipGetLastError());
   if (out_samples) *out_samples = nout;
 }

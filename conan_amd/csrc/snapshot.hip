@@ -169,6 +169,9 @@ void export_slots(conan_streams* s, const int32_t* slots, int n, void* blob_dev,
   if (!s || !slots || !blob_dev || !meta) throw Error(CONAN_ERR_INVALID, "null argument");
   wavio::check_slot_list(s, slots, n);
   check_blob(blob_dev, blob_ld, "conan_streams_export_slots");
+  for (int i = 0; i < n; ++i)      // (a drift slot's position is not part of the record)
+    if ((!s->wav_in.rs_slot.empty() && s->wav_in.rs_slot[slots[i]].dr.d) || (!s->wav_out.or_slot.empty() && s->wav_out.or_slot[slots[i]].dr.d))
+      throw Error(CONAN_ERR_UNSUPPORTED, "conan_streams_export_slots: slot " + std::to_string(slots[i]) + " has a drift resampler (conan_streams_set_input_drift / _set_output_drift): not in slot snapshots");
   s->snapshot_build();
   const snap::Layout& l = s->snapshot.layout;
   std::vector<snap::CallRow> rows(n);

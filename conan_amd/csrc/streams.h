@@ -222,7 +222,8 @@ struct conan_streams {
   // ring of computed log-mel frames (frame f at f & (fe_LM - 1)); fe_chunk = the [n][seg + rc][num_mels] chunk the step consumes.  Host
   // side, per slot: samples received, frames computed, chunks emitted, phase (0 open, 1 the final call has come, 2 drained)
   struct FeSlot { long long recv = 0; int frames = 0, chunks = 0, phase = 0; };
-  struct RsSlot { const ch::RsTable* f = nullptr; long long in = 0, out = 0; int phase = 0; };
+  // (dr: the slot's drift resampler, conan_streams_set_input_drift - it replaces f, and a rate setter removes it)
+  struct RsSlot { const ch::RsTable* f = nullptr; long long in = 0, out = 0; int phase = 0; ch::DriftPos dr; int s_in = 0; bool rated() const { return f || dr.d; } };
   struct WavIn {
     float* fe_audio = nullptr; float* fe_mel = nullptr; float* fe_chunk = nullptr;
     int fe_LA = 0, fe_LM = 0, fe_last_n = 0;
@@ -370,7 +371,8 @@ struct conan_streams {
   // memory).  The history ring ([max_slots][or_ring_len], stream state) is allocated by the first conan_streams_set_output_rate with a
   // real rate; conv_post's staging rows and the row table (set q of or_sets; the set's event follows the resample_out_kernel launch
   // that read it) by the first vocoder step that needs them.
-  struct OrSlot { const ch::RsTable* f = nullptr; long long out = 0; int flushed = 0; };
+  // (dr: the slot's drift resampler, conan_streams_set_output_drift - it replaces f, and a rate setter removes it)
+  struct OrSlot { const ch::RsTable* f = nullptr; long long out = 0; int flushed = 0; ch::DriftPos dr; int out_rate = 0; bool rated() const { return f || dr.d; } };
   struct WavOut {
     std::vector<OrSlot> or_slot;
     std::vector<long long> voc_samples;
@@ -795,6 +797,8 @@ void step_wav_common(conan_streams* s, const int32_t* slots, int n, int samples,
 void step_wav_chunk(conan_streams* s, float* chunk_dev, void* stream);
 void set_input_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg);
 void set_output_rate(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg);
+void set_drift(conan_streams* s, int side, const int32_t* slots, int n, const conan_resample_cfg* cfg, const int32_t* ppb);      // side: CONAN_DRIFT_*
+void get_drift(conan_streams* s, int side, const int32_t* slots, int n, int32_t* ppb_out, int64_t* in_out, int64_t* out_out);
 void set_output_ld(conan_streams* s, int64_t ld);
 void set_input_format(conan_streams* s, const int32_t* slots, int n, int format);
 void set_output_format(conan_streams* s, const int32_t* slots, int n, int format);

@@ -679,7 +679,7 @@ void conan_streams::hifigan_step(int n, int frames, const float* mel_dev, float*
       const int slot = h_slots[i];
       wav_out.voc_samples[slot] += T;
       if (!op) continue;
-      if (!wav_out.or_slot.empty() && wav_out.or_slot[slot].f && out_rows) wav_out.or_slot[slot].out += op->counts[i];
+      if (!wav_out.or_slot.empty() && wav_out.or_slot[slot].rated() && out_rows) wav_out.or_slot[slot].out += op->counts[i];
       wav_out.out_counts[op->dst.empty() ? i : op->dst[i]] = op->counts[i];
     }
   }

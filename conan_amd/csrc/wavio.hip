@@ -103,6 +103,36 @@ static RsPlan rs_plan(const conan_streams* s, const int32_t* slots, int n, const
       if ((uintptr_t)wav_dev & 3) throw Error(CONAN_ERR_INVALID, std::string(who) + ": wav_dev must be 4-byte aligned");
       if (!r.f) P.launch = true;      // a format alone: the copy rows decode into staging
     }
+    if (r.dr.d) {      // a drift slot (conan_streams_set_input_drift): the counts come from the law's closed-form positions
+      const ch::DriftPos& D = r.dr;
+      auto bad = [&](const std::string& what) {
+        throw Error(CONAN_ERR_INVALID, std::string(who) + ": slot " + std::to_string(slots[i]) + " (input at " + std::to_string(D.d->in_rate) + " Hz with drift): " + what);
+      };
+      const int sm = samples[i], fin = final_[i], W = D.d->W;
+      if (fin != 0 && fin != 1) bad("final must be 0 or 1");
+      if (m.sample_rate != D.d->out_rate) bad("conan_mel_cfg.sample_rate must be the resampler's out_rate");
+      if (r.phase == 1 && (!fin || sm != 0)) bad("after the final call only samples = 0, final = 1 may follow");
+      if (sm < 0 || sm > 2 * r.s_in) bad("a call takes 0 .. 2 * segment * hop * in_rate / out_rate samples");
+      if ((long long)sm * bps > wav_ld * 4) bad("the row holds more samples than the row stride of wav_dev");
+      if (sm > 0 && !wav_dev) throw Error(CONAN_ERR_INVALID, "null argument (wav_dev with samples > 0)");
+      const long long I = r.in + sm;
+      const long long T = std::max(D.first_at(fin ? I : I - W), r.out);      // outputs that exist (final) or are ready
+      const long long J = std::min(T, r.out + S);
+      P.ff[i] = fin && J == T;
+      const ch::DriftPos::u128 p0 = D.pos(r.out);
+      const long long n_first = (long long)(p0 >> 32);
+      if (I - std::max(0ll, n_first - W + 1) > cnk::kRsRing)
+        throw Error(CONAN_ERR_UNSUPPORTED, std::string(who) + ": slot " + std::to_string(slots[i]) + ": unread input history would leave the resampler's ring (the slot is owed too much output)");
+      P.mm[i] = (int)(J - r.out);
+      P.rate[i] = 1; P.in_after[i] = I;
+      row.taps = reinterpret_cast<const float*>(D.d->dev); row.ph = reinterpret_cast<const int*>((uintptr_t)D.step);
+      row.in0 = r.in; row.out0 = n_first; row.orig = (int)(unsigned)p0; row.w = W;
+      row.m = sm; row.h = P.mm[i]; row.mode = cnk::kRsDrift | (fmt << cnk::kRsFmtShift);
+      P.launch = P.launch || sm > 0 || P.mm[i] > 0;
+      P.win = std::max(P.win, D.win);
+      P.flops += 8.0 * P.mm[i] * W;
+      continue;
+    }
     if (!r.f) continue;
     const ch::RsTable& t = *r.f;
     auto bad = [&](const std::string& what) {
@@ -240,6 +270,9 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
     }
     for (int i = 1; i < n && !s->wav_in.rs_slot.empty(); ++i) {
       const conan_streams::RsSlot &r0 = s->wav_in.rs_slot[slots[0]], &r = s->wav_in.rs_slot[slots[i]];
+      const ch::DriftPos &d0 = r0.dr, &d = r.dr;
+      if (d.d != d0.d || (d.d && (d.ppb != d0.ppb || d.out0 != d0.out0 || d.n0 != d0.n0 || d.f0 != d0.f0 || r.in != r0.in || r.out != r0.out || r.phase != r0.phase)))
+        throw Error(CONAN_ERR_INVALID, who + ": the slots of one call must share one input drift configuration (conan_streams_set_input_drift), ppb and position");
       if (r.f != r0.f || (r.f && (r.in != r0.in || r.out != r0.out || r.phase != r0.phase)))
         throw Error(CONAN_ERR_INVALID, who + ": the slots of one call must share one input rate configuration (conan_streams_set_input_rate) and position");
     }
@@ -283,7 +316,7 @@ void step_wav(conan_streams* s, const std::string& who, const int32_t* slots, in
   // its call-order rows of wav_out_dev (the scatter then places codes and mel only); otherwise no group's plan is active
   bool route = scatter && s->wav_out.out_ld != 0;
   for (int g = 0; scatter && g < (int)groups.size(); ++g)
-    for (int i : groups[g]) route = route || (!s->wav_out.or_slot.empty() && s->wav_out.or_slot[slots[i]].f) || s->wav_out.out_fmt[slots[i]];
+    for (int i : groups[g]) route = route || (!s->wav_out.or_slot.empty() && s->wav_out.or_slot[slots[i]].rated()) || s->wav_out.out_fmt[slots[i]];
   std::vector<conan_streams::OutPlan> ops;
   std::vector<std::vector<int32_t>> gslots(groups.size());
   for (int g = 0; g < (int)groups.size(); ++g) {
@@ -485,6 +518,80 @@ void set_output_rate(conan_streams* s, const int32_t* slots, int n, const conan_
   for (int i = 0; i < n; ++i) s->snapshot.out_cfg[slots[i]] = c;
 }
 
+// conan_streams_set_input_drift / _set_output_drift.  cfg: configure (the slots at the start of their utterance / vocoder stream, as for
+// the rate setters); null: a live change of ppb, host state only - it takes effect at the slot's next output.
+void set_drift(conan_streams* s, int side, const int32_t* slots, int n, const conan_resample_cfg* cfg, const int32_t* ppb) {
+  const bool in = side == CONAN_DRIFT_SOURCE;
+  const std::string who = in ? "conan_streams_set_input_drift" : "conan_streams_set_output_drift";
+  if (!s || !slots || !ppb) throw Error(CONAN_ERR_INVALID, "null argument");
+  if (in && !s->wav_in.fe_audio) throw Error(CONAN_ERR_STATE, who + ": the stream-set has no streaming front-end (all three models)");
+  if (!in && !(s->ctx->cfg.models & CONAN_MODEL_HIFIGAN)) throw Error(CONAN_ERR_STATE, who + ": context holds no HiFi-GAN model");
+  check_slot_list(s, slots, n);
+  for (int i = 0; i < n; ++i)
+    if (ppb[i] < -CONAN_DRIFT_MAX_PPB || ppb[i] > CONAN_DRIFT_MAX_PPB) throw Error(CONAN_ERR_INVALID, who + ": |ppb| must be at most 2 000 000");
+  auto slot_dr = [&](int slot) -> ch::DriftPos* {
+    if (in) return s->wav_in.rs_slot.empty() ? nullptr : &s->wav_in.rs_slot[slot].dr;
+    return s->wav_out.or_slot.empty() ? nullptr : &s->wav_out.or_slot[slot].dr;
+  };
+  if (!cfg) {
+    for (int i = 0; i < n; ++i) {
+      const ch::DriftPos* d = slot_dr(slots[i]);
+      if (!d || !d->d) throw Error(CONAN_ERR_STATE, who + ": slot " + std::to_string(slots[i]) + " has no drift resampler (configure it with a cfg first)");
+    }
+    for (int i = 0; i < n; ++i) {
+      ch::DriftPos& d = *slot_dr(slots[i]);
+      conan_resample_cfg c{};
+      c.in_rate = d.d->in_rate; c.out_rate = d.d->out_rate;
+      d.retime(ppb[i], drift::step(c, side, ppb[i]), in ? s->wav_in.rs_slot[slots[i]].out : s->wav_out.or_slot[slots[i]].out);
+    }
+    return;
+  }
+  const conan_resample_cfg& c = *cfg;
+  const int S = s->ctx->cfg.emf_segment * s->ctx->hop, model_rate = 50 * s->ctx->hop;
+  if (in && c.out_rate != model_rate) throw Error(CONAN_ERR_INVALID, who + ": out_rate must be the model rate (hop * 50 = " + std::to_string(model_rate) + " Hz)");
+  if (!in && c.in_rate != model_rate) throw Error(CONAN_ERR_INVALID, who + ": in_rate must be the model rate (hop * 50 = " + std::to_string(model_rate) + " Hz)");
+  const int win = drift::tile_window(c, side);      // (the configuration's checks; before any GPU use)
+  if (in && ((long long)S * c.in_rate) % c.out_rate) throw Error(CONAN_ERR_INVALID, who + ": segment * hop samples at the model rate must be a whole number of input samples");
+  if (in) check_utterance_start(s, slots, n, who.c_str());
+  for (int i = 0; i < n && !in; ++i)
+    if (s->wav_out.voc_samples[slots[i]] != 0)
+      throw Error(CONAN_ERR_STATE, who + ": slot " + std::to_string(slots[i]) + " is not at the start of its vocoder stream (reset it with CONAN_MODEL_HIFIGAN first)");
+  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
+  const ch::DrTable& t = s->ctx->drift_table(c);
+  if (in) s->resample_init(); else s->out_ring_init();
+  for (int i = 0; i < n; ++i) {
+    ch::DriftPos d;
+    d.d = &t; d.win = win; d.ppb = ppb[i]; d.step = drift::step(c, side, ppb[i]);
+    if (in) {
+      conan_streams::RsSlot& r = s->wav_in.rs_slot[slots[i]];
+      r = conan_streams::RsSlot{nullptr, 0, 0, 0};
+      r.dr = d; r.s_in = (int)((long long)S * c.in_rate / c.out_rate);
+    } else {
+      conan_streams::OrSlot& o = s->wav_out.or_slot[slots[i]];
+      o = conan_streams::OrSlot{nullptr, 0, 0};
+      o.dr = d; o.out_rate = c.out_rate;
+    }
+  }
+  // (slot snapshots refuse a drift slot; its rate record reads "none")
+  std::vector<conan_resample_cfg>& rec = in ? s->snapshot.in_cfg : s->snapshot.out_cfg;
+  rec.resize(s->max_slots, conan_resample_cfg{});
+  for (int i = 0; i < n; ++i) rec[slots[i]] = conan_resample_cfg{};
+}
+
+void get_drift(conan_streams* s, int side, const int32_t* slots, int n, int32_t* ppb_out, int64_t* in_out, int64_t* out_out) {
+  const bool in = side == CONAN_DRIFT_SOURCE;
+  const std::string who = in ? "conan_streams_input_drift" : "conan_streams_output_drift";
+  if (!s || !slots) throw Error(CONAN_ERR_INVALID, "null argument");
+  check_slot_list(s, slots, n);
+  for (int i = 0; i < n; ++i) {
+    const bool has = in ? (!s->wav_in.rs_slot.empty() && s->wav_in.rs_slot[slots[i]].dr.d) : (!s->wav_out.or_slot.empty() && s->wav_out.or_slot[slots[i]].dr.d);
+    if (!has) throw Error(CONAN_ERR_STATE, who + ": slot " + std::to_string(slots[i]) + " has no drift resampler");
+    if (ppb_out) ppb_out[i] = in ? s->wav_in.rs_slot[slots[i]].dr.ppb : s->wav_out.or_slot[slots[i]].dr.ppb;
+    if (in_out) in_out[i] = in ? s->wav_in.rs_slot[slots[i]].in : s->wav_out.voc_samples[slots[i]];
+    if (out_out) out_out[i] = in ? s->wav_in.rs_slot[slots[i]].out : s->wav_out.or_slot[slots[i]].out;
+  }
+}
+
 void set_output_ld(conan_streams* s, int64_t ld) {
   if (!s) throw Error(CONAN_ERR_INVALID, "null streams");
   if (ld < 0 || ld > INT_MAX) throw Error(CONAN_ERR_INVALID, "conan_streams_set_output_ld: ld out of range");
@@ -544,7 +651,7 @@ void flush_output(conan_streams* s, const int32_t* slots, int n, float* wav_out_
   }
   for (int i = 0; i < n && !s->wav_out.or_slot.empty(); ++i) {
     conan_streams::OrSlot& o = s->wav_out.or_slot[slots[i]];
-    if (!o.f || s->wav_out.voc_samples[slots[i]] == 0) continue;
+    if (!o.rated() || s->wav_out.voc_samples[slots[i]] == 0) continue;
     o.out += P.counts[i]; o.flushed = 1;
   }
 }
@@ -607,7 +714,7 @@ conan_streams::OutPlan conan_streams::out_plan(const int32_t* slots, int n, int 
   bool any = false;
   for (int i = 0; i < n && (!wav_out.or_slot.empty() || wav_out.out_fmt_n); ++i) {      // (the mel-in entry points come here before set_slots has seen the list)
     if (slots[i] < 0 || slots[i] >= max_slots) throw Error(CONAN_ERR_INVALID, "slot index out of range");
-    any = any || (!wav_out.or_slot.empty() && wav_out.or_slot[slots[i]].f) || wav_out.out_fmt[slots[i]];      // (a format alone sends the step through the copy rows)
+    any = any || (!wav_out.or_slot.empty() && wav_out.or_slot[slots[i]].rated()) || wav_out.out_fmt[slots[i]];      // (a format alone sends the step through the copy rows)
   }
   if (!flush) P.lvl_rows = olv::step_rows(this, slots, n, frames, who);      // (checked here, before anything changes: CONAN_ERR_UNSUPPORTED rows)
   if (!flush) P.wm_rows = wmark::step_rows(this, slots, n, frames, who);
@@ -623,7 +730,28 @@ conan_streams::OutPlan conan_streams::out_plan(const int32_t* slots, int n, int 
     const int fmt = wav_out.out_fmt[slots[i]], bps = wavio::bytes_per_sample(fmt);
     row.slot = slots[i]; row.m = T; row.h = T; row.dst = (dst ? (*dst)[i] : i) | (fmt << cnk::kOrDstBits);
     if (fmt != cnk::kFmtF32 && ((uintptr_t)wav_out_dev & 3)) throw Error(CONAN_ERR_INVALID, who + ": wav_out_dev must be 4-byte aligned");
-    if (!wav_out.or_slot.empty() && wav_out.or_slot[slots[i]].f) {
+    if (!wav_out.or_slot.empty() && wav_out.or_slot[slots[i]].dr.d) {      // a drift slot (conan_streams_set_output_drift)
+      const OrSlot& o = wav_out.or_slot[slots[i]];
+      const ch::DriftPos& D = o.dr;
+      const int W = D.d->W;
+      const std::string where = who + ": slot " + std::to_string(slots[i]) + " (output at " + std::to_string(o.out_rate) + " Hz with drift): ";
+      const long long in0 = wav_out.voc_samples[slots[i]], I = in0 + T;
+      long long J = o.out;
+      if (flush) { if (!o.flushed) J = std::max(D.first_at(I), o.out); }
+      else {
+        if (o.flushed) throw Error(CONAN_ERR_STATE, where + "conan_streams_flush_output has ended the utterance; reset the slot with CONAN_MODEL_HIFIGAN first");
+        J = std::max(D.first_at(I - W), o.out);
+      }
+      const ch::DriftPos::u128 p0 = D.pos(o.out);
+      const long long n_first = (long long)(p0 >> 32);
+      if (I - std::max(0ll, n_first - W + 1) > wav_out.or_ring_len) throw Error(CONAN_ERR_UNSUPPORTED, where + "resampler history ring too small for this configuration");
+      if (J - o.out > INT_MAX || (ch::DriftPos::u128)(J - o.out) * D.step >> 62) throw Error(CONAN_ERR_INVALID, where + "too many samples in one call");
+      row.taps = reinterpret_cast<const float*>(D.d->dev); row.ph = reinterpret_cast<const int*>((uintptr_t)D.step);
+      row.in0 = in0; row.out0 = n_first; row.orig = (int)(unsigned)p0; row.w = W; row.L = cnk::kOrDriftL; row.h = (int)(J - o.out);
+      P.active = P.active || row.h > 0;
+      P.win = std::max(P.win, D.win);
+      P.flops += 8.0 * row.h * W;
+    } else if (!wav_out.or_slot.empty() && wav_out.or_slot[slots[i]].f) {
       const OrSlot& o = wav_out.or_slot[slots[i]];
       const ch::RsTable& t = *o.f;
       const std::string where = who + ": slot " + std::to_string(slots[i]) + " (output at " + std::to_string(t.out_rate) + " Hz): ";

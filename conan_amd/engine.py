@@ -297,8 +297,11 @@ class StreamingVoiceConversionEngine:
             raise ValueError("set_voice: bank= and ids= are required")
         self.st.set_voice(self.slots if slots is None else slots, bank, ids)
 
-    def start(self, ref_mel, ref_len=None, which=7, out_rate=None, out_filter=None, out_format=None, pitch=None, voice=None, out_level=None, watermark=None, out_eq=None):
-        """voice: (bank, ids) - enrolled voices of a runtime.VoiceBank, one id per slot, in place of ref_mel (then None).
+    def start(self, ref_mel, ref_len=None, which=7, out_rate=None, out_filter=None, out_format=None, pitch=None, voice=None, out_level=None, watermark=None, out_eq=None,
+              drift=None):
+        """drift: the far device's clock error in ppm (> 0: it runs fast; None: no compensation) - the audio then leaves through the
+        drift resampler (Streams.set_output_drift) at out_rate, also at the model rate; set_drift changes it between steps.
+        voice: (bank, ids) - enrolled voices of a runtime.VoiceBank, one id per slot, in place of ref_mel (then None).
         pitch: the slots' pitch control in the decoder step (Streams.set_pitch) - None / False: none; a dict of its keywords
         (shift_semitones, range, pivot, uv_threshold), or a list with one per slot.
         out_rate: the sample rate the audio leaves at (None: the model rate), resampled on the GPU behind the vocoder; out_filter:
@@ -321,17 +324,25 @@ class StreamingVoiceConversionEngine:
             raise ValueError("out_rate / out_format: one value for all slots here (feed / infer return one [B, count] block); open_slots and "
                              "infer_wav_staggered take one per slot / utterance")
         self._check_voice(ref_mel, voice)
+        if isinstance(drift, (list, tuple)):
+            raise ValueError("drift: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
+        drifts = self._drift_values(drift, len(self.slots))
         values = self._host_checks(len(self.slots), pitch=pitch, out_level=out_level, watermark=watermark, out_eq=out_eq)
         self.st.reset(self.slots, which=which)
         self._reference(self.slots, ref_mel, ref_len, voice)
         self._set_out_rate(self.slots, out_rate, out_filter)
+        self._set_drift(self.slots, drifts, out=(out_rate, out_filter))
         self._set_format(self.slots, out_format, self.st.output_formats, self.st.set_output_format)
         for keyword in values:      # (pitch, out_level, watermark)
             self._apply(keyword, self.slots, values[keyword])
 
     def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, echo=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
+                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, echo=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None,
+                  drift=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
+        drift: the far device's clock error in ppm (start), on both sides of the slots: the input goes through the drift resampler
+        too (Streams.set_input_drift, at in_rate or the model rate).  feed() then takes 0 .. 2 x 80 ms of samples per call and may
+        emit nothing in a call; set_drift changes the value between calls.
         in_rate: the input's sample rate (None: the model rate), resampled on the GPU; filter: Context.resample's filter keywords.
         in_format: the input's sample format (None: float32; 's16' takes int16 rows, 'ulaw' / 'alaw' uint8), decoded on the GPU.
         out_rate / out_filter / out_format / out_level / watermark: as in start().
@@ -367,13 +378,17 @@ class StreamingVoiceConversionEngine:
         There is no trim= here: silence trimming (infer_wav(trim=True)) moves audio forward over pauses it has seen whole, and a
         stream cannot drop time it has not heard yet; activity= is what a live call has in its place."""
         self._check_voice(ref_mel, voice)
+        if isinstance(drift, (list, tuple)):
+            raise ValueError("drift: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
+        self._drift_values(drift, len(self.slots))
         if isinstance(in_format, (list, tuple)) or isinstance(level, (list, tuple)):
             raise ValueError("in_format / level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
         values = self._host_checks(len(self.slots), voice, level=level, follow=follow, register=register, activity=activity, bypass=bypass,
                                    conceal=conceal, echo=echo, comfort=comfort, denoise=denoise, tones=tones, eq=eq)
         self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice,
-                   out_level=out_level, watermark=watermark, out_eq=out_eq)
+                   out_level=out_level, watermark=watermark, out_eq=out_eq, drift=drift)
         self._set_rate(self.slots, in_rate, filter)
+        self._set_drift(self.slots, self._drift_values(drift, len(self.slots)), inp=(in_rate, filter))
         self._set_format(self.slots, in_format, self.st.input_formats, self.st.set_input_format)
         for keyword in values:      # (pitch and out_level went in with start(), in front of the input rate)
             self._apply(keyword, self.slots, values[keyword], [in_rate] * len(self.slots))
@@ -570,8 +585,58 @@ class StreamingVoiceConversionEngine:
         st = self.st
         L = self.seg * self.ctx.hop
         ld = max([L] + [-(-L * r // st.model_rate) + 2 for r in st.output_rates.values()]) if st.output_rates else 0
+        # (a drift slot's sink may run fast by _lib.DRIFT_MAX_PPB: its chunk is that much longer)
+        ld = max([ld] + [-(-L * st.output_rates[s] * (10 ** 9 + _lib.DRIFT_MAX_PPB) // (st.model_rate * 10 ** 9)) + 3 for s in getattr(st, "output_drifts", ())])      # (a Streams stand-in that predates drift has no such set)
         if ld != st.output_ld:
             st.set_output_ld(ld)
+
+    @staticmethod
+    def _drift_values(drift, n, what="slots"):
+        """drift= (ppm: one value or one per slot; None / False: none) -> per slot None or the ppm as a float.  Host only."""
+        values = _per_slot(drift, n)
+        if len(values) != n:
+            raise ValueError(f"drift: {len(values)} values for {n} {what}")
+        out = []
+        for v in values:
+            if v is None or v is False:
+                out.append(None)
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise ValueError(f"drift: {v!r} (the far device's clock error in ppm, > 0: it runs fast; or None)")
+            _lib.drift_ppb(v)      # (the range check)
+            out.append(float(v))
+        return out
+
+    def _set_drift(self, slots, values, out=None, inp=None):
+        """The slots' drift resamplers from _drift_values' list, behind the rate setters (which remove them).  out = (out_rate,
+        out_filter): the output side at the slots' output rate; inp = (in_rate, filter): the input side at their input rate
+        (None in either: the model rate)."""
+        st = self.st
+        if all(v is None for v in values):
+            return
+        outs, ins = _per_slot(out[0] if out else None, len(slots)), _per_slot(inp[0] if inp else None, len(slots))
+        for slot, v, ro, ri in zip(slots, values, outs, ins):
+            if v is None:
+                continue
+            if out is not None:
+                st.set_output_drift([slot], v, rate=ro or st.model_rate, **(out[1] or {}))
+            if inp is not None:
+                st.set_input_drift([slot], v, rate=ri or st.model_rate, **(inp[1] or {}))
+        self._fit_output_ld()
+
+    def set_drift(self, slots=None, ppm=0.0):
+        """A live change of the slots' clock drift (all slots by default) between feed / feed_ragged / step calls, on both sides
+        where the slot has a drift resampler (start / start_wav / open_slots(drift=...)): in force from the slot's next output."""
+        st = self.st
+        slots = [int(s) for s in (self.slots if slots is None else slots)]
+        ins, outs = [s for s in slots if s in st.input_drifts], [s for s in slots if s in st.output_drifts]
+        if len(set(ins) | set(outs)) != len(slots):
+            raise ValueError("set_drift: a slot without drift (give drift= when the utterance starts)")
+        _lib.drift_ppb(ppm)
+        if ins:
+            st.set_input_drift(ins, ppm)
+        if outs:
+            st.set_output_drift(outs, ppm)
 
     def export_streams(self, slots):
         """The streams in `slots` as a runtime.SlotSnapshot (Streams.export_slots): park them, move them to another engine, rank or
@@ -699,8 +764,12 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
                   out_format=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None, register=None, activity=None,
-                  activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, echo=None, far=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
-        """src_wav [B, N] (cuda), ref_mel [B, Tr, 80] (or None with voice = (bank, ids): start) -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
+                  activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, echo=None, far=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None,
+                  drift=None, **filter):
+        """drift: the far device's clock error in ppm on both sides of the slots (start_wav), one value: the results are those of
+        infer_wav(ctx.resample_drift(x, in_rate, model_rate, drift), ...), x the decoded utterance, and the returned wav is
+        ctx.resample_drift(model-rate wav, model_rate, out_rate, drift, side='sink'), bit for bit.
+        src_wav [B, N] (cuda), ref_mel [B, Tr, 80] (or None with voice = (bank, ids): start) -> (wav, mel, codes) of the utterance fed 80 ms at a time and drained:
         the results of infer(ctx.wav2mel(src_wav), ref_mel) bit for bit.  in_rate (+ filter keywords): src_wav's sample rate,
         resampled on the GPU; the results are those of infer_wav(ctx.resample(src_wav, in_rate, **filter), ref_mel) bit for bit.
         out_rate (+ out_filter): the returned wav is the whole utterance at that rate, ctx.resample of the model-rate wav bit for bit.
@@ -744,7 +813,7 @@ class StreamingVoiceConversionEngine:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
                        pitch=pitch, voice=voice, follow=follow, register=register, activity=activity, bypass=bypass, out_level=out_level, conceal=conceal,
-                       echo=echo, comfort=comfort, denoise=denoise, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq, **filter)
+                       echo=echo, comfort=comfort, denoise=denoise, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq, drift=drift, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -776,8 +845,10 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, echo=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
-        """Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
+                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, echo=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None,
+                   drift=None, **filter):
+        """drift: the slots' clock drift in ppm (start_wav), one value or a list with one per slot, on both sides of each slot.
+        Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
         which = 7 | 8) and their references (ref_mel [len(slots), Tr, 80]).  in_rate: the slots' input rate (None: the model
         rate), one value or one per slot; filter: Context.resample's filter keywords.  out_rate / out_filter: the slots' output rate
         (None: the model rate), one value or one per slot.  in_format / out_format: the slots' sample formats (None: float32), one
@@ -793,6 +864,7 @@ class StreamingVoiceConversionEngine:
         No trim=, as in start_wav: the slots stream, and a stream cannot drop time (infer_wav_staggered(trim=True) trims utterances
         it holds whole)."""
         self._check_voice(ref_mel, voice)
+        drifts = self._drift_values(drift, len(slots))
         values = self._host_checks(len(slots), voice, level=level, pitch=pitch, follow=follow, register=register, activity=activity, bypass=bypass,
                                    conceal=conceal, echo=echo, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq)
         self.st.reset(slots, which=7 | 8)
@@ -802,6 +874,7 @@ class StreamingVoiceConversionEngine:
         self._set_format(slots, out_format, self.st.output_formats, self.st.set_output_format)
         for r, group in _by_value(slots, _per_slot(in_rate, len(slots))):
             self._set_rate(group, r, filter)
+        self._set_drift(slots, drifts, out=(out_rate, out_filter), inp=(in_rate, filter))
         for keyword in values:      # (the order of _lib.SLOT_FEATURES: pitch behind level, out_level and watermark last)
             self._apply(keyword, slots, values[keyword], _per_slot(in_rate, len(slots)))
 
@@ -981,8 +1054,10 @@ class StreamingVoiceConversionEngine:
 
     @torch.no_grad()
     def infer(self, src_mel, ref_mel, ref_len=None, pipelined=True, out_rate=None, out_filter=None, out_format=None, pitch=None, voice=None,
-              out_level=None, watermark=None, out_eq=None):
+              out_level=None, watermark=None, out_eq=None, drift=None):
         """src_mel [B,T,80], ref_mel [B,Tr,80] (cuda) -> wav [B, T*hop], mel [B,T,80], codes [B,T].
+        drift: the far device's clock error in ppm on the output side (start): the returned wav is ctx.resample_drift(side='sink') of
+        the model-rate wav at out_rate, bit for bit.
 
         The whole source is available here, so by default the chunks are issued as pipelined steps
         (conan_step_async): the Emformer + decoder of chunk t+1 overlap the vocoder of chunk t.  The
@@ -993,6 +1068,9 @@ class StreamingVoiceConversionEngine:
         watermark: the output watermark (start): the returned model-rate wav is ctx.watermark_embed of the unmarked one, bit for bit."""
         self._check_voice(ref_mel, voice)
         if self.ctx.cfg.voc_upsample == 2:
+            if drift not in (None, False):
+                raise ValueError("drift with an upsample 'nn' vocoder: its steps are whole prefixes; run Context.resample_drift(side='sink') over the "
+                                 "returned wav instead")
             if out_eq not in (None, False):
                 raise ValueError("out_eq with an upsample 'nn' vocoder: its steps are whole prefixes, not update intervals; filter the returned wav "
                                  "with Context.eq instead")
@@ -1006,7 +1084,8 @@ class StreamingVoiceConversionEngine:
                 raise ValueError("out_format with an upsample 'nn' vocoder: convert the returned wav with Context.convert_samples instead")
             self._set_out_rate(self.slots, out_rate, out_filter)      # (refuses a rate; restores the model rate)
             return self._infer_prefix_vocoder(src_mel, ref_mel, ref_len, pitch, voice)
-        self.start(ref_mel, ref_len, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice, out_level=out_level, watermark=watermark, out_eq=out_eq)
+        self.start(ref_mel, ref_len, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice, out_level=out_level, watermark=watermark, out_eq=out_eq,
+                   drift=drift)
         B = src_mel.shape[0]
         hop, nm = self.ctx.hop, self.ctx.cfg.num_mels
         wavs, mels, codes = [], [], []

@@ -186,6 +186,33 @@ class Context:
             assert got.value == nout
         return y
 
+    def resample_drift(self, x, orig_freq, new_freq, drift, side="source", **filter):
+        """conan_resample_drift: x [..., N] float32 resampled from orig_freq to new_freq with the far device's clock drift taken out -
+        a windowed sinc at an arbitrary position (the law of include/conan_hip.h).  drift: ppm (> 0: the device runs fast), or a
+        list of (output_index, ppm) that starts at output 0; ppm becomes the law's ppb by round(ppm * 1000).  side: 'source' (the
+        device sampled x) or 'sink' (the device plays the result).  filter: Context.resample's filter keywords.  The filter runs at
+        equal rates too, and drift 0 is not bit-equal to Context.resample."""
+        cfg = _lib.resample_cfg(orig_freq, new_freq, **filter)
+        sd = _lib.drift_side(side)
+        at, ppb = _lib.drift_schedule(drift)
+        x = x.to(torch.device("cuda", self.device), torch.float32).contiguous()
+        lead, N = x.shape[:-1], x.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        nout = self.lib.conan_resample_drift_length(C.byref(cfg), sd, N, at.ctypes.data, ppb.ctypes.data, len(at))
+        if nout < 0:
+            raise ValueError("resample_drift: the library refuses this configuration or schedule")
+        y = torch.empty(*lead, nout, device=x.device)
+        if n and N:
+            got = C.c_int64(0)
+            _lib.check(self.lib.conan_resample_drift(self.h, C.byref(cfg), sd, _ptr(x), n, N, at.ctypes.data, ppb.ctypes.data, len(at), _ptr(y),
+                                                     nout, C.byref(got), _stream()))
+            assert got.value == nout
+        return y
+
+    def resample_drift_table(self, orig_freq, new_freq, **filter):
+        """conan_resample_drift_table (host only): the law's f32 table as numpy [1025, 2W] - row p holds the taps at phase p / 1024."""
+        return _lib.resample_drift_table(orig_freq, new_freq, **filter)
+
     def _loud_call(self, x, sample_rate, target, peak_limit, lengths, out, measure_only):
         """One conan_loud_norm call over the rows of x -> (y or None, stats float64 [n, 4], the leading shape)."""
         dev = torch.device("cuda", self.device)
@@ -1119,6 +1146,7 @@ class Streams:
         self.seg, self.rc = c.emf_segment, c.emf_right_context
         self.input_rate_set = False      # set_input_rate has run on this stream-set (its history ring exists)
         self.output_rates = {}           # slot -> output rate, for the slots whose audio leaves at another rate than the model's
+        self.input_drifts, self.output_drifts = set(), set()      # the slots with a drift resampler (set_input_drift / set_output_drift)
         self.output_ld = 0               # set_output_ld: row stride of every step's wav (0: each step's own)
         self.input_formats = {}          # slot -> 's16' | 'ulaw' | 'alaw', for the slots whose wav-in rows are not float32
         self.output_formats = {}         # slot -> the same, for the slots whose audio leaves in another format
@@ -1174,6 +1202,8 @@ class Streams:
         self._release()
         for i, slot in enumerate(a):      # the Python-side mirrors of the slot configuration that travelled
             info = snap.info(i)
+            self._drift_slots("input").discard(int(slot))      # (a snapshot carries no drift resampler: the import replaces the slot's)
+            self._drift_slots("output").discard(int(slot))
             self._note_format(self.input_formats, [slot], info["in_format"])
             self._note_format(self.output_formats, [slot], info["out_format"])
             if info["in_rate"] is not None:
@@ -1278,6 +1308,7 @@ class Streams:
         cfg = _lib.resample_cfg(rate, self.model_rate, **filter)
         _lib.check(self.lib.conan_streams_set_input_rate(self.h, p, len(a), C.byref(cfg)))
         self.input_rate_set = True
+        self._drift_slots("input").difference_update(int(s) for s in a)
 
     def set_output_rate(self, slots, rate, **filter):
         """conan_streams_set_output_rate: the slots' audio leaves every step at `rate` Hz, resampled on the GPU behind the vocoder.
@@ -1287,11 +1318,58 @@ class Streams:
         a, p = _i32(slots)
         cfg = _lib.resample_cfg(self.model_rate, rate, **filter)
         _lib.check(self.lib.conan_streams_set_output_rate(self.h, p, len(a), C.byref(cfg)))
+        self._drift_slots("output").difference_update(int(s) for s in a)
         for slot in a:
             if int(rate) != self.model_rate:
                 self.output_rates[int(slot)] = int(rate)
             else:
                 self.output_rates.pop(int(slot), None)
+
+    def _drift_slots(self, side):
+        """The set of slots with a drift resampler on `side` ('input' / 'output'): the attributes input_drifts / output_drifts."""
+        return self.__dict__.setdefault(side + "_drifts", set())
+
+    def set_input_drift(self, slots, ppm, rate=None, **filter):
+        """conan_streams_set_input_drift: clock-drift compensation of the slots' wav-in input.  ppm: the far device's clock error
+        (> 0: it runs fast; one value or one per slot; round(ppm * 1000) ppb).  rate given: configure - the input arrives at `rate`
+        Hz (the model rate is allowed) and goes through the drift resampler (filter: Context.resample's keywords) in place of the
+        rational one; the slots must be at the start of an utterance.  rate=None: a live change between calls, taking effect at the
+        slot's next output.  A configured slot takes 0 .. 2 * (80 ms) samples per call and may emit no frame in a call."""
+        a, p = _i32(slots)
+        ppb = _lib.drift_ppb_rows(ppm, len(a))
+        cfg = _lib.resample_cfg(rate, self.model_rate, **filter) if rate is not None else None
+        _lib.check(self.lib.conan_streams_set_input_drift(self.h, p, len(a), C.byref(cfg) if cfg is not None else None, ppb.ctypes.data))
+        if rate is not None:
+            self.input_rate_set = True
+            self._drift_slots("input").update(int(s) for s in a)
+
+    def _drift_query(self, fn, slots):
+        a, p = _i32(slots)
+        ppb, i, o = np.zeros(len(a), dtype=np.int32), np.zeros(len(a), dtype=np.int64), np.zeros(len(a), dtype=np.int64)
+        _lib.check(fn(self.h, p, len(a), ppb.ctypes.data, i.ctypes.data, o.ctypes.data))
+        return [(int(ppb[k]) / 1000.0, int(i[k]), int(o[k])) for k in range(len(a))]
+
+    def input_drift(self, slots):
+        """conan_streams_input_drift: per slot (ppm in force, input samples received, model-rate samples handed to the front-end)."""
+        return self._drift_query(self.lib.conan_streams_input_drift, slots)
+
+    def set_output_drift(self, slots, ppm, rate=None, **filter):
+        """conan_streams_set_output_drift: clock-drift compensation of the slots' audio output, as set_input_drift: rate given
+        configures (the slots at the start of their vocoder stream; the audio leaves at `rate` Hz through the drift resampler),
+        rate=None changes ppm between steps.  A step delivers what is ready (output_samples) and flush_output the tail; a fast
+        sink takes more than frames * hop samples per step: set_output_ld."""
+        a, p = _i32(slots)
+        ppb = _lib.drift_ppb_rows(ppm, len(a))
+        cfg = _lib.resample_cfg(self.model_rate, rate, **filter) if rate is not None else None
+        _lib.check(self.lib.conan_streams_set_output_drift(self.h, p, len(a), C.byref(cfg) if cfg is not None else None, ppb.ctypes.data))
+        if rate is not None:
+            for slot in a:
+                self.output_rates[int(slot)] = int(rate)      # (the steps' wav is then a list of rows trimmed to their counts)
+                self._drift_slots("output").add(int(slot))
+
+    def output_drift(self, slots):
+        """conan_streams_output_drift: per slot (ppm in force, model-rate samples produced, output samples delivered)."""
+        return self._drift_query(self.lib.conan_streams_output_drift, slots)
 
     def set_input_format(self, slots, fmt):
         """conan_streams_set_input_format: the slots' wav-in rows arrive as 'f32' (float32), 's16' (int16), 'ulaw' or 'alaw' (uint8,

@@ -457,6 +457,77 @@ int conan_streams_output_pending(conan_streams* s, const int32_t* slots, int n, 
  * CONAN_ERR_STATE until a reset that includes CONAN_MODEL_HIFIGAN. */
 int conan_streams_flush_output(conan_streams* s, const int32_t* slots, int n, float* wav_out_dev, int64_t wav_ld, void* stream);
 
+/* Clock-drift compensation: a resampler whose ratio is in_rate / out_rate corrected by an integer ppb (parts per billion) that may
+ * change along the signal (added within ABI 9: a caller detects it by the symbol conan_resample_drift).  ppb describes the far
+ * device's clock, ppb > 0 = the device runs fast: on the source side (CONAN_DRIFT_SOURCE, the device samples the input) it delivers
+ * in_rate * (1 + ppb * 1e-9) samples per server second; on the sink side (CONAN_DRIFT_SINK, the device plays the output) it consumes
+ * out_rate * (1 + ppb * 1e-9).  One number per device serves both directions.  |ppb| <= CONAN_DRIFT_MAX_PPB.
+ * The law.  All position arithmetic is in exact integers.
+ *   step, in units of 2^-32 input samples per output sample, in 128-bit integers:
+ *     source:  step = floor(((in_rate * (10^9 + ppb)) << 32) / (out_rate * 10^9))
+ *     sink:    step = floor(((in_rate * 10^9) << 32) / (out_rate * (10^9 + ppb)))
+ *   position: output 0 sits at position 0, output j at pos_j = pos_{j-1} + step_j, step_j = the step of the ppb in force at output j
+ *     (a change takes effect at the next output).  n = pos >> 32, f = pos & 0xffffffff, p = f >> 22 (1024 phases),
+ *     mu = float(f & 0x3fffff) * 2^-22 (exact in f32).
+ *   width, from the nominal rates: base = min(in_rate, out_rate) * rolloff, W = ceil(lpw * in_rate / base); 2W taps over the inputs
+ *     i = n - W + 1 + k, k = 0 .. 2W - 1.  2W > 512 is CONAN_ERR_INVALID, and so is a tile window,
+ *     ceil(255 * step / 2^32) + 2W + 2 at the side's largest step, above 16384.
+ *   table T[p][k], p = 0 .. 1024: conan_resample_cfg's kernel at t = ((k - W + 1) - p / 1024) * base / in_rate, that is
+ *     sinc(pi t) * window(t / lpw) * base / in_rate (hann: cos(pi t / (2 lpw))^2; kaiser: I0(beta sqrt(1 - (t / lpw)^2)) / I0(beta)),
+ *     zero for |t| >= lpw; built in double on the host - sin(pi t) from t's distance to the nearest integer, so an integer t gives an
+ *     exact zero - and rounded once to f32.  D[p][k] = T[p + 1][k] - T[p][k], one f32 subtraction.
+ *   sum: acc = 0; for k ascending: h = fmaf(mu, D[p][k], T[p][k]); acc = fmaf(h, x[i], acc); x[i] = 0 outside the signal.
+ *   existence: in a whole signal of N inputs, output j exists iff n_j < N.
+ *   readiness: in a stream, output j is ready once input n_j + W has arrived; after the input's final call (or in a flush) everything
+ *     that exists is ready.  The result does not depend on how a stream is cut into calls.
+ * Consequences: ppb = 0 is NOT bit-equal to conan_resample (the table is interpolated and every output has 2W taps); the filter runs
+ * even at in_rate == out_rate; with rolloff = 1, ppb = 0 and equal rates the taps are a unit impulse and the output equals the input
+ * bit for bit (a -0.0 sample leaves as +0.0: the sum starts at +0).  The interpolated table's distance from the exact kernel is
+ * measured in DESIGN.md 4.28.
+ * Out of scope: estimating the drift (the host's jitter-buffer level is the servo signal), slot snapshots of a drift slot
+ * (conan_streams_export_slots returns CONAN_ERR_UNSUPPORTED before anything changes), the watermark detector under drift, Kaiser
+ * widths beyond 512 taps. */
+#define CONAN_DRIFT_SOURCE 0
+#define CONAN_DRIFT_SINK 1
+#define CONAN_DRIFT_MAX_PPB 2000000
+#define CONAN_DRIFT_MAX_SEGMENTS 32
+/* Host only, exact: the outputs of a whole signal of `samples` inputs under the schedule (below); -1 for an invalid configuration,
+ * side or schedule, or samples < 0.  samples up to 2^40 and beyond are counted in 128 bits. */
+int64_t conan_resample_drift_length(const conan_resample_cfg* cfg, int side, int64_t samples, const int64_t* at, const int32_t* ppb, int n_seg);
+/* Host only.  The law's f32 table T, [1025][2W] row-major, into table[cap] (table may be NULL: only the size); *W (may be NULL)
+ * receives W.  Returns 1025 * 2W, or a negative conan_status (cap too small: CONAN_ERR_INVALID). */
+int64_t conan_resample_drift_table(const conan_resample_cfg* cfg, int32_t* W, float* table, int64_t cap);
+/* Whole signals under a piecewise-constant schedule: segment k holds ppb[k] from output at[k] on (host arrays; at[0] = 0, strictly
+ * ascending, 1 <= n_seg <= CONAN_DRIFT_MAX_SEGMENTS).  x_dev[n][samples] -> row r of y_dev at r * y_ld floats,
+ * conan_resample_drift_length outputs each (*out_samples, may be NULL; y_ld below it is CONAN_ERR_INVALID), on `stream`.
+ * 1 <= samples < 2^31 - 512.  One launch. */
+int conan_resample_drift(conan_ctx* ctx, const conan_resample_cfg* cfg, int side, const float* x_dev, int n, int64_t samples,
+                         const int64_t* at, const int32_t* ppb, int n_seg, float* y_dev, int64_t y_ld, int64_t* out_samples, void* stream);
+/* Streams: a drift resampler per slot in place of the rational one, on the input side (conan_step_wav*) and on the output side (every
+ * entry point that writes wav_out_dev).  A drift row is a row mode of the resampler launch the call makes anyway: no new launch, and
+ * a stream-set that never asks allocates nothing and launches exactly what it launched before.  Rows without drift keep their bits.
+ * conan_streams_set_input_drift.  cfg non-null configures the slots with ppb[i] each: cfg->out_rate must be the model rate (hop * 50),
+ * in_rate == out_rate is allowed, seg * hop * in_rate / out_rate (s_in, the nominal 80 ms) must be whole, the slots must be at an
+ * utterance start (CONAN_ERR_STATE otherwise), as for conan_streams_set_input_rate, whose ring and staging it shares.  cfg == NULL
+ * changes only ppb, at any time between calls, host state only; it takes effect at the slot's next output; a slot without a drift
+ * resampler is CONAN_ERR_STATE.  On any error no slot changes.  conan_streams_set_input_rate at an utterance start removes the drift
+ * resampler.  The setting survives CONAN_MODEL_FRONTEND resets, which put the position back to 0.
+ * Call contract of an input-drift slot: a call, final or not, takes 0 .. 2 * s_in samples.  The front-end gets the ready outputs not
+ * yet handed over, at most seg * hop; the rest is owed to later calls (a call with 0 samples collects them).  So a call may emit 0
+ * frames when the host's servo lags (fewer than seg * hop outputs became ready), and the front-end sees `final` on the call that
+ * hands over the last existing output.  Unread history that would leave the 32768-sample ring is CONAN_ERR_UNSUPPORTED before anything
+ * changes.  conan_step_wav (same position) wants the same configuration, ppb and position in all of its slots.
+ * conan_streams_input_drift: per slot the current ppb, the inputs received and the outputs handed over since the last reset (each
+ * array may be NULL) - what a host servo and the tests need to restate the schedule.  A slot without drift is CONAN_ERR_STATE.
+ * conan_streams_set_output_drift / conan_streams_output_drift: the same against conan_streams_set_output_rate: cfg->in_rate must be
+ * the model rate, the slots at the start of their vocoder stream; inputs = model-rate samples produced, outputs = samples delivered.
+ * Every step delivers what is ready (conan_streams_output_samples; a fast sink takes more than frames * hop samples per step, so set
+ * conan_streams_set_output_ld), conan_streams_flush_output delivers the tail and conan_streams_output_pending counts it. */
+int conan_streams_set_input_drift(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg, const int32_t* ppb);
+int conan_streams_input_drift(conan_streams* s, const int32_t* slots, int n, int32_t* ppb_out, int64_t* in_out, int64_t* out_out);
+int conan_streams_set_output_drift(conan_streams* s, const int32_t* slots, int n, const conan_resample_cfg* cfg, const int32_t* ppb);
+int conan_streams_output_drift(conan_streams* s, const int32_t* slots, int n, int32_t* ppb_out, int64_t* in_out, int64_t* out_out);
+
 /* Sample formats of the audio rows (added within ABI 9: a caller detects it by the exported symbols).  wav_dev and wav_out_dev carry
  * [-1, 1] floats by default; a slot can take and deliver 16-bit PCM or G.711 instead, converted on the GPU by the arithmetic below,
  * the same in every entry point. */
