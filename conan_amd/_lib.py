@@ -164,6 +164,14 @@ _PROTOS = {
     "conan_streams_echo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "conan_echo_state_bytes": (C.c_int64, []),
     "conan_echo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (the estimator is bound here, not through SLOT_FEATURES: it is no stage of the wav-in chain)
+    "conan_streams_set_echo_delay": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "conan_streams_echo_delay_cfg": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "conan_streams_echo_delay": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "conan_echo_delay_state_bytes": (C.c_int64, []),
+    "conan_streams_echo_delay_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "conan_echo_delay": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                   C.c_void_p, C.c_void_p]),
     "conan_denoise_state_bytes": (C.c_int64, []),
     "conan_mel_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "conan_watermark_state_bytes": (C.c_int64, []),
@@ -738,6 +746,71 @@ def echo_cfg(rate=None, **kw):
     for n in _ECHO_FIELDS:
         setattr(c, n, int(f[n]))
     return c
+
+
+ECHO_DELAY_FRAME, ECHO_DELAY_MAX_LAGS = 1024, 6144
+ECHO_DELAY_REPORT = ("est", "age", "cand", "run", "last_pk", "last_s")      # the columns of a report row
+
+
+class EchoDelayCfg(C.Structure):
+    """conan_echo_delay_cfg (include/conan_hip.h)."""
+    _fields_ = [("enabled", C.c_int32), ("n_lags", C.c_int32), ("thr", C.c_int32), ("leak", C.c_int32), ("ratio", C.c_int32),
+                ("min_peak", C.c_int32), ("hold", C.c_int32), ("tol", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+_ECHO_DELAY_FIELDS = ("n_lags", "thr", "leak", "ratio", "min_peak", "hold", "tol")
+_ECHO_DELAY_RANGES = dict(n_lags=(64, ECHO_DELAY_MAX_LAGS), thr=(1, 32767), leak=(1, 8), ratio=(1, 2**31 - 1), min_peak=(1, 2**31 - 1),
+                          hold=(1, 2**31 - 1), tol=(0, 2**31 - 1))
+
+
+def echo_delay_keywords(rate):
+    """The documented defaults of the echo-delay estimator for an input rate, or - given an enabled EchoDelayCfg - its fields: the
+    keywords echo_delay_cfg takes.  Lags over 384 ms (a multiple of 64, at most 6144), a ternary threshold of 16, leak 5, a peak
+    of 10 times the mean and at least 1024, 4 frames to confirm within 2 ms.  They are choices, not measurements."""
+    if isinstance(rate, EchoDelayCfg):
+        return {f: int(getattr(rate, f)) for f in _ECHO_DELAY_FIELDS}
+    r = int(rate)
+    n_lags = min(ECHO_DELAY_MAX_LAGS, max(64, (r * 384 // 1000 + 32) // 64 * 64))
+    return dict(n_lags=n_lags, thr=16, leak=5, ratio=10, min_peak=1024, hold=4, tol=r * 2 // 1000)
+
+
+def echo_delay_cfg(rate=None, **kw):
+    """An enabled conan_echo_delay_cfg: echo_delay_keywords(rate) with the given fields replaced (rate=None: every field must be
+    given).  A field outside the header's range is a ValueError here, before any library call."""
+    base = echo_delay_keywords(rate) if rate is not None else {}
+    f = dict(base, **kw)
+    unknown = sorted(set(f) - set(_ECHO_DELAY_FIELDS))
+    if unknown:
+        raise ValueError(f"echo_delay: unknown fields {unknown}")
+    missing = [n for n in _ECHO_DELAY_FIELDS if n not in f]
+    if missing:
+        raise ValueError(f"echo_delay: without a rate the fields {missing} must be given")
+    c = EchoDelayCfg()
+    c.enabled = 1
+    for n in _ECHO_DELAY_FIELDS:
+        lo, hi = _ECHO_DELAY_RANGES[n]
+        if not lo <= int(f[n]) <= hi or (n == "n_lags" and int(f[n]) % 64):
+            raise ValueError(f"echo_delay: {n} = {f[n]!r} is outside {lo} .. {hi}" + (" in steps of 64" if n == "n_lags" else ""))
+        setattr(c, n, int(f[n]))
+    return c
+
+
+def echo_delay_follow(est, age, in_force, lead, hyst, max_age):
+    """The host rule between calls: from an estimator's report (est, age) and the canceller's delay in force, the delay to set, or
+    None to leave it.  target = clamp(est - lead, 0, ECHO_MAX_DELAY), so that the filter's first taps lie `lead` samples in front of
+    the estimated lag; it is applied when there is an estimate (est >= 0) that is no older than max_age frames and the target is
+    more than hyst samples from the delay in force.  Pure: no state, no device."""
+    est, age, in_force = int(est), int(age), int(in_force)
+    if est < 0 or age > int(max_age):
+        return None
+    target = min(max(est - int(lead), 0), ECHO_MAX_DELAY)
+    return target if abs(target - in_force) > int(hyst) else None
+
+
+def echo_delay_follow_keywords(rate):
+    """The defaults of the engine's follow rule for an input rate: lead 8 ms, hyst 4 ms, max_age 64 frames.  Choices."""
+    r = int(rate)
+    return dict(lead=r * 8 // 1000, hyst=r * 4 // 1000, max_age=64)
 
 
 class DenoiseCfg(C.Structure):

@@ -825,6 +825,32 @@ int conan_echo(conan_ctx* ctx, const conan_echo_cfg* cfg, int format, void* x_de
   return guarded([&] { echo::whole(ctx, cfg, format, x_dev, ld, far_dev, far_ld, n, samples, stats_dev, stream); });
 }
 
+// ---- echo delay (echo_delay.hip): conan_streams_set_echo_delay, conan_streams_echo_delay_cfg, conan_streams_echo_delay,
+// conan_echo_delay_state_bytes, conan_streams_echo_delay_state, conan_echo_delay
+int conan_streams_set_echo_delay(conan_streams* s, const int32_t* slots, int n, const conan_echo_delay_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream) {
+  return guarded([&] { echo_delay::set_echo_delay(s, slots, n, cfg, seed_dev, seed_ld, stream); });
+}
+
+int conan_streams_echo_delay_cfg(const conan_streams* s, int slot, conan_echo_delay_cfg* cfg_out) {
+  return guarded([&] { wavio::get_setting(s, &conan_streams::ed, slot, cfg_out, nullptr); });
+}
+
+int conan_streams_echo_delay(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const void* wav_dev, int64_t wav_ld, const void* far_dev,
+                             int64_t far_ld, int64_t* report_dev, void* stream) {
+  return guarded([&] { echo_delay::estimate(s, slots, n, samples, wav_dev, wav_ld, far_dev, far_ld, report_dev, stream); });
+}
+
+int64_t conan_echo_delay_state_bytes(void) { return (int64_t)cnk::kEdStateBytes; }
+
+int conan_streams_echo_delay_state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream) {
+  return guarded([&] { echo_delay::state(s, slots, n, state_dev, ld, stream); });
+}
+
+int conan_echo_delay(conan_ctx* ctx, const conan_echo_delay_cfg* cfg, int format, const void* mic_dev, int64_t ld, const void* far_dev, int64_t far_ld, int n,
+                     const int64_t* samples, int64_t* track_dev, int64_t track_ld, int64_t* report_dev, void* stream) {
+  return guarded([&] { echo_delay::whole(ctx, cfg, format, mic_dev, ld, far_dev, far_ld, n, samples, track_dev, track_ld, report_dev, stream); });
+}
+
 // ---- input noise suppression (denoise.hip): conan_mel_denoise, conan_streams_set_denoise, conan_streams_denoise,
 // conan_denoise_state_bytes, conan_streams_denoise_state
 int conan_mel_denoise(conan_ctx* ctx, const conan_denoise_cfg* cfg, const float* mel_dev, int n, const int32_t* frames, int64_t ld, int num_mels,

@@ -9,10 +9,6 @@
 
 namespace cnk {
 
-// the 16-bit view of a decoded sample; a non-finite value counts as 0
-__device__ __forceinline__ float echo_finite(float v) { return fabsf(v) <= 3.402823466e38f ? v : 0.f; }
-__device__ __forceinline__ int echo_q(float v) { return (int)(short)encode_sample(kFmtS16, v); }
-
 // One sample of the row becomes enc(v).  Halfword and byte stores: the neighbours in the same dword keep their bytes.
 __device__ __forceinline__ void echo_put(int fmt, char* row, long long t, float v) {
   if (fmt == kFmtF32) { reinterpret_cast<float*>(row)[t] = v; return; }

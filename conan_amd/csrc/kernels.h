@@ -657,6 +657,36 @@ struct EchoArgs {
 };
 void launch_echo(const EchoArgs& a, hipStream_t st);
 
+// Echo delay (echo_delay.hip; include/conan_hip.h, conan_echo_delay_cfg).  echo_delay_kernel: one workgroup of kEdThreads lanes per
+// table row, which reads `samples` samples of row `row` of the mic buffer (wav + row * wav_ld dwords, in format fmt) and of the far
+// buffer and writes neither.  The state - header, A[kEdMaxLags], the far end's last ternary values - is read from state[slot]
+// (restart = 0 and slot >= 0) or starts as the restart state, and is written back to state[slot] (slot >= 0).  Every index the kernel
+// forms comes from the row: n_lags and phase (= pos mod kEdFrame) are the host's; of the record only values are read.  A row is
+// walked in tiles of kEdTile samples and, inside, segment by segment up to the next frame end, so a whole signal (slot = -1,
+// restart = 1) and a chunk take the same path.  track (may be null): [call rows] of track_ld int64, six per frame end of the row.
+constexpr int kEdFrame = 1024, kEdMaxLags = 6144, kEdTile = 4096, kEdThreads = 256;      // CONAN_ECHO_DELAY_*
+constexpr int kEdPerLane = kEdMaxLags / kEdThreads;
+static_assert(kEdMaxLags == kEchoMaxDelay + kEchoMaxTaps && kEdMaxLags % kEdThreads == 0 && kEdTile % kEdThreads == 0, "lane i owns lags i + 256 k");
+struct EdHead { long long pos; int est, age, cand, run; long long frames, last_pk, last_s; long long reserved[2]; };      // the first 64 bytes of a record
+static_assert(sizeof(EdHead) == 64, "the header's record");
+constexpr long long kEdStateBytes = (long long)sizeof(EdHead) + kEdMaxLags * 4ll + kEdMaxLags;
+struct EdRow {
+  long long samples, pos;      // pos: the slot's position at the row's first sample
+  int row, slot, restart, fmt;
+  int n_lags, phase, thr, leak;
+  int ratio, min_peak, hold, tol;
+};
+static_assert(sizeof(EdRow) == 64, "uploaded as 16 ints");
+struct EdArgs {
+  const void* wav; long long wav_ld;        // the mic rows, stride in dwords
+  const void* far; long long far_ld;        // the far rows, stride in dwords
+  char* state;                              // [max_slots][kEdStateBytes]; may be null when no row names a slot
+  long long* report;                        // [call rows][6] or null
+  long long* track; long long track_ld;     // [call rows][track_ld] or null
+  const EdRow* tab; int rows;
+};
+void launch_echo_delay(const EdArgs& a, hipStream_t st);
+
 // Input noise suppression (denoise.hip; include/conan_hip.h, conan_denoise_cfg): the spectral gate on log-mel frames of nm bins.  One
 // workgroup of 64 * ceil(nm / 64) lanes per table row; lane b keeps the floor and the attenuation of bin b in registers across the
 // row's frames.  DnState is the published conan_denoise_state; a record whose `bins` is not nm is the state before the first frame.

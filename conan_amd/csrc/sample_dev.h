@@ -1,5 +1,5 @@
 // Device routines of the sample formats (include/conan_hip.h, CONAN_SAMPLE_*), shared by resample.hip (the wav-in and wav-out rows,
-// conan_convert_samples), conceal.hip and echo.hip (the repair and the canceller work on a row in its own format).
+// conan_convert_samples), conceal.hip, echo.hip and echo_delay.hip (the repair, the canceller and its delay estimator work on a row in its own format).
 #pragma once
 #include "kernels.h"
 
@@ -51,6 +51,10 @@ __device__ __forceinline__ unsigned encode_sample(int fmt, float x) {
   const unsigned a = (unsigned)((seg << 4) | ((seg < 2 ? p >> 1 : p >> seg) & 15));
   return a ^ (neg ? 0x55u : 0xD5u);
 }
+
+// the 16-bit view of a decoded sample, as the echo canceller and its delay estimator read a row; a non-finite value counts as 0
+__device__ __forceinline__ float echo_finite(float v) { return fabsf(v) <= 3.402823466e38f ? v : 0.f; }
+__device__ __forceinline__ int echo_q(float v) { return (int)(short)encode_sample(kFmtS16, v); }
 
 // Sample i of a row of n samples in format fmt (uniform over the caller's wave).  Every lane of an aligned group of four consecutive
 // samples must call it together (lane = i mod 4, also the lanes with i >= n, which store nothing): 16- and 8-bit codes travel to the

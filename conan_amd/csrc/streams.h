@@ -103,7 +103,7 @@ struct StageSets {
   ~StageSets() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
-// ---- the per-slot source features (level.hip, f0.hip, register.hip, activity.hip, bypass.hip, conceal.hip, echo.hip, denoise.hip, level_out.hip) share one
+// ---- the per-slot source features (level.hip, f0.hip, register.hip, activity.hip, bypass.hip, conceal.hip, echo.hip, echo_delay.hip, denoise.hip, level_out.hip) share one
 // slot-setting type.  cfg: per slot the configuration as set (zeros: off; `reseed` kept 0), which persists across resets; n_on: slots
 // with the feature on (On: the cfg field that says so).  Empty until the feature's first enabling call (assign(), from its *_init()
 // beside the device state and row tables).  pending: the slot's state restarts in its next kernel row, which clears the flag - a host
@@ -351,6 +351,15 @@ struct conan_streams {
     StageSets<cnk::EchoRow> sets;
   } ec;
   void echo_init();
+  // echo delay (conan_streams_set_echo_delay; echo_delay.hip).  state: [max_slots] records of cnk::kEdStateBytes, read and written by
+  // the rows of echo_delay_kernel in the order of the caller's stream; pending and pos as the canceller's (the kernel takes the
+  // frame's fill from the call row).  Rows: per estimator call; event: behind the kernel's launch.  No step path reads any of it.
+  struct EchoDelay : SlotSetting<conan_echo_delay_cfg> {
+    char* state = nullptr;
+    std::vector<long long> pos;
+    StageSets<cnk::EdRow> sets;
+  } ed;
+  void echo_delay_init();
   // input noise suppression (conan_streams_set_denoise; denoise.hip).  state: [max_slots] records of conan_denoise_state, read and
   // written by the rows of denoise_stream_kernel in the order of the front-end launches; pending restarts it before the slot's next
   // frame (a seed row becomes the state at once and clears the flag).  Rows: one per suppressing call row that completes a frame or
@@ -361,7 +370,7 @@ struct conan_streams {
   } dn;
   void denoise_init();
   // a reset with CONAN_MODEL_FRONTEND: the settings stay; the states restart in the slots' next rows (host flags: no launch)
-  void restart_features(const int32_t* slots, int n) { reg.restart(slots, n); act.restart(slots, n); byp.restart(slots, n); cmf.restart(slots, n); conc.restart(slots, n); ec.restart(slots, n); dn.restart(slots, n); tn.restart(slots, n); in_eq.restart(slots, n); }
+  void restart_features(const int32_t* slots, int n) { reg.restart(slots, n); act.restart(slots, n); byp.restart(slots, n); cmf.restart(slots, n); conc.restart(slots, n); ec.restart(slots, n); ed.restart(slots, n); dn.restart(slots, n); tn.restart(slots, n); in_eq.restart(slots, n); }
   void ragged_init();
   void resample_init();        // staging, row tables and the history ring (conan_streams_set_input_rate)
   void rs_stage_init();        // staging and row tables only (conan_streams_set_input_format: no stream state)
@@ -1026,6 +1035,18 @@ void cancel(conan_streams* s, const int32_t* slots, int n, const int32_t* sample
             int64_t* stats_dev, void* stream);
 void state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream);
 }  // namespace echo
+
+// ---- echo delay (echo_delay.hip): the kernel's host side and the bodies of api.hip's entry points
+namespace echo_delay {
+void check_cfg(const conan_echo_delay_cfg& c, const char* who);      // host only
+cnk::EdRow row(const conan_echo_delay_cfg& c);      // the cfg's fields of a row that starts from the restart state and names no slot
+void whole(conan_ctx* ctx, const conan_echo_delay_cfg* cfg, int format, const void* mic_dev, int64_t ld, const void* far_dev, int64_t far_ld, int n,
+           const int64_t* samples, int64_t* track_dev, int64_t track_ld, int64_t* report_dev, void* stream);
+void set_echo_delay(conan_streams* s, const int32_t* slots, int n, const conan_echo_delay_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream);
+void estimate(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const void* wav_dev, int64_t wav_ld, const void* far_dev, int64_t far_ld,
+              int64_t* report_dev, void* stream);
+void state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream);
+}  // namespace echo_delay
 
 // ---- input noise suppression (denoise.hip): the kernels' host side and the bodies of api.hip's entry points
 namespace denoise {

@@ -6,6 +6,7 @@ so the compute path has no collective.  The only exchange is the gather of finis
 rank 0 (RCCL `gather` over xGMI on GPUs, gloo in the CPU tests)."""
 import functools
 import os
+import types
 
 import numpy as np
 import torch
@@ -211,6 +212,8 @@ def _by_value(slots, values):
     return [(v, [s for s, x in zip(slots, values) if x == v]) for v in dict.fromkeys(values)]
 
 
+_FOLLOW_KEYS = ("lead", "hyst", "max_age")      # the follow rule's keywords inside echo_delay= (_lib.echo_delay_follow)
+
 # what True means to a feature's Streams setter, by engine keyword (register= has no True: a scalar is its target)
 _TRUE = dict(level=True, pitch=True, follow=True, out_level=True, activity=dict(gate=True), bypass={}, conceal={}, echo={}, denoise={}, comfort={}, watermark={}, tones={})
 
@@ -269,6 +272,9 @@ class StreamingVoiceConversionEngine:
         self.slots = list(range(n_streams))
         self.seg, self.rc = ctx.cfg.emf_segment, ctx.cfg.emf_right_context
         self._used = set()          # the keywords of _lib.SLOT_FEATURES whose setter has been called on the stream-set (_apply)
+        # the echo-delay estimator (echo_delay=): whether its setter has been called, per slot the follow rule's keywords and the
+        # last report read (est, age), and the report of the last far= call on its way to the host (_note_report)
+        self._ed = types.SimpleNamespace(used=False, follow={}, last={}, pending=None)
 
     @staticmethod
     def _check_voice(ref_mel, voice):
@@ -337,7 +343,7 @@ class StreamingVoiceConversionEngine:
             self._apply(keyword, self.slots, values[keyword])
 
     def start_wav(self, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, echo=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None,
+                  pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, echo=None, echo_delay=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None,
                   drift=None, **filter):
         """start() plus a fresh streaming front-end (CONAN_MODEL_FRONTEND): the next feed() is the utterance's first audio.
         drift: the far device's clock error in ppm (start), on both sides of the slots: the input goes through the drift resampler
@@ -364,6 +370,11 @@ class StreamingVoiceConversionEngine:
         that never arrived, on the GPU in front of the step.  echo: echo cancellation of the input rows (Streams.set_echo) - None /
         False: none; True: the defaults of the slot's input rate; a dict of conan_echo_cfg's fields over them.  feed(far=...) then
         cancels what the far end's audio left in the rows, on the GPU behind the repair and in front of the step.
+        echo_delay: the echo-delay estimator beside the canceller (Streams.set_echo_delay; it needs echo=) - None / False: none;
+        True: the defaults of the slot's input rate; a dict of conan_echo_delay_cfg's fields over them and of the follow rule's
+        keywords lead, hyst, max_age (_lib.echo_delay_follow_keywords: 8 ms, 4 ms, 64 frames - choices).  feed(far=...) then runs
+        the estimator in front of the canceller, and between calls the engine moves the canceller's delay where the rule
+        (_lib.echo_delay_follow) says; echo_delays() reads the result.
         comfort: comfort noise in the closed activity gate
         (Streams.set_comfort; activity= beside it) - None / False: none; True: the defaults; a dict of set_comfort's keywords; the
         seed defaults to one derived from the slot's index.  chunk_comfort() reads the last call's levels.
@@ -385,6 +396,7 @@ class StreamingVoiceConversionEngine:
             raise ValueError("in_format / level: one value for all slots here; open_slots and infer_wav_staggered take one per slot / utterance")
         values = self._host_checks(len(self.slots), voice, level=level, follow=follow, register=register, activity=activity, bypass=bypass,
                                    conceal=conceal, echo=echo, comfort=comfort, denoise=denoise, tones=tones, eq=eq)
+        delays = self._echo_delay_values(echo_delay, echo, len(self.slots))
         self.start(ref_mel, ref_len, which=7 | 8, out_rate=out_rate, out_filter=out_filter, out_format=out_format, pitch=pitch, voice=voice,
                    out_level=out_level, watermark=watermark, out_eq=out_eq, drift=drift)
         self._set_rate(self.slots, in_rate, filter)
@@ -392,6 +404,7 @@ class StreamingVoiceConversionEngine:
         self._set_format(self.slots, in_format, self.st.input_formats, self.st.set_input_format)
         for keyword in values:      # (pitch and out_level went in with start(), in front of the input rate)
             self._apply(keyword, self.slots, values[keyword], [in_rate] * len(self.slots))
+        self._apply_echo_delay(self.slots, delays, [in_rate] * len(self.slots))
 
     @staticmethod
     def _values(keyword, value, n, what="slots", voice=None):
@@ -435,6 +448,106 @@ class StreamingVoiceConversionEngine:
         if not f.mirror:
             self._used.add(keyword)
         getattr(self.st, f.method)(self.slots if slots is None else slots, *args, **kw)
+
+    @staticmethod
+    def _echo_delay_values(echo_delay, echo, n, what="slots"):
+        """echo_delay= (one value or one per slot) -> per slot None (None / False: none) or a dict of conan_echo_delay_cfg's fields
+        and the follow rule's keywords.  A slot with one needs echo=: the estimate steers the canceller's delay.  Host only."""
+        values, echoes = _per_slot(echo_delay, n), _per_slot(echo, n)
+        if len(values) != n:
+            raise ValueError(f"echo_delay: {len(values)} values for {n} {what}")
+        known = set(_lib._ECHO_DELAY_FIELDS) | set(_FOLLOW_KEYS)
+        out = []
+        for k, v in enumerate(values):
+            if v is None or v is False:
+                out.append(None)
+                continue
+            if k >= len(echoes) or echoes[k] is None or echoes[k] is False:
+                raise ValueError("echo_delay: the estimate steers the canceller's delay and needs echo= (True, or conan_echo_cfg's fields)")
+            if isinstance(v, _lib.EchoDelayCfg):
+                v = _lib.echo_delay_keywords(v)
+            elif v is True:
+                v = {}
+            elif not isinstance(v, dict):
+                raise ValueError(f"echo_delay: {v!r} (True, a dict of conan_echo_delay_cfg's fields and lead / hyst / max_age, an _lib.EchoDelayCfg or None)")
+            if set(v) - known:
+                raise ValueError(f"echo_delay: unknown fields {sorted(set(v) - known)}")
+            out.append(dict(v))
+        return out
+
+    def _apply_echo_delay(self, slots, values, rates, live=False):
+        """The slots' estimator from _echo_delay_values' list, behind the slots' reset.  A stream-set that never used it gets no
+        setter call at all; once used, None turns a slot off.  rates: the slots' input rates (None: the model rate), for the
+        defaults.  live: a change between calls - an enabled slot keeps its last report."""
+        if all(v is None for v in values) and not self._ed.used:
+            return
+        self._ed.used = True
+        if self._ed.pending is not None and not live:      # (a report of the slots' earlier utterances says nothing about the new ones)
+            self._ed.pending[0][:] = [None if s in slots else s for s in self._ed.pending[0]]
+        for slot, v, rate in zip(slots, values, rates):
+            rate = int(rate or self.st.model_rate)
+            if v is None:
+                self.st.set_echo_delay([slot], None)
+                self._ed.follow.pop(slot, None)
+                self._ed.last.pop(slot, None)
+                continue
+            self.st.set_echo_delay([slot], {k: x for k, x in v.items() if k not in _FOLLOW_KEYS} or True, rate=rate)
+            self._ed.follow[slot] = dict(_lib.echo_delay_follow_keywords(rate), **{k: int(v[k]) for k in _FOLLOW_KEYS if k in v})
+            if not live or slot not in self._ed.last:
+                self._ed.last[slot] = (-1, 0)
+
+    def set_echo_delay(self, slots=None, cfg=True, rate=None, **kw):
+        """A live change of the slots' echo-delay estimator (all slots by default) between feed / feed_ragged calls, also
+        mid-utterance: start_wav's echo_delay= values, keywords on top (cfg=None turns it off; an enabled slot keeps its state, and a
+        changed n_lags the sums that still exist).  rate: the slots' input rate, for the defaults (None: the model rate)."""
+        slots = self.slots if slots is None else list(slots)
+        v = self._echo_delay_values(cfg, True, 1)[0]
+        self._follow_pending()
+        self._apply_echo_delay(slots, [None if v is None else dict(v, **kw)] * len(slots), [rate] * len(slots), live=True)
+
+    def _far_report(self, slots):
+        """The report tensor of a far= call: int64 [n, 6] on the device when a slot of the call follows its estimate, else None."""
+        if not any(s in self._ed.follow for s in slots):
+            return None
+        return torch.zeros(len(slots), 6, dtype=torch.int64, device=self.st.dev)
+
+    def _note_report(self, slots, samples, rep):
+        """The call's report starts for the host (pinned, behind the estimator on the current stream); _follow_pending reads it."""
+        host = torch.empty(tuple(rep.shape), dtype=rep.dtype, pin_memory=True)
+        host.copy_(rep, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._ed.pending = ([s if m > 0 else None for s, m in zip(slots, samples)], host, ev, rep)
+
+    def _follow_pending(self):
+        """The follow rule on the last far= call's report, between calls: it waits for that call's estimator launch - work on the
+        caller's stream in front of the call's step, not the pipelined steps themselves - and moves a canceller's delay
+        (Streams.set_echo, fields only: the canceller's own guard deals with the stale weights) where the rule says."""
+        if self._ed.pending is None:
+            return
+        slots, host, ev, _ = self._ed.pending
+        self._ed.pending = None
+        ev.synchronize()
+        for slot, row in zip(slots, host.tolist()):
+            f = self._ed.follow.get(slot)
+            if slot is None or f is None:      # (a row without samples reports zeros, not an estimate)
+                continue
+            self._ed.last[slot] = (row[0], row[1])
+            cfg = self.st.echo_cfg([slot])[0]
+            d = None if cfg is None else _lib.echo_delay_follow(row[0], row[1], cfg["delay"], **f)
+            if d is not None:
+                self.st.set_echo([slot], dict(cfg, delay=d))
+
+    def echo_delays(self, slots=None):
+        """Per slot (all slots by default) (est, age, delay in force): the estimator's confirmed lag in samples (-1: none yet) and
+        its age in frames as of the last far= call, and the canceller's bulk delay after the follow rule has seen them (None for a
+        slot without a canceller).  It waits for the last call's report."""
+        self._follow_pending()
+        out = []
+        for slot in (self.slots if slots is None else slots):
+            cfg = self.st.echo_cfg([slot])[0]
+            out.append(self._ed.last.get(slot, (-1, 0)) + (None if cfg is None else cfg["delay"],))
+        return out
 
     def set_bypass(self, slots=None, cfg=True, **kw):
         """A live change of the slots' bypass (all slots by default) between feed / feed_ragged calls, also mid-utterance and with
@@ -673,7 +786,7 @@ class StreamingVoiceConversionEngine:
         return L if in_rate is None else L * int(in_rate) // self.st.model_rate
 
     @torch.no_grad()
-    def feed(self, wav_chunk, final=False, pipelined=False, mel=None, lost=None, far=None):
+    def feed(self, wav_chunk, final=False, pipelined=False, mel=None, lost=None, far=None, echo_stats=None):
         """Streaming waveform input (conan_step_wav): wav_chunk [B, seg*hop] (cuda; 0 .. seg*hop samples when final; at an input
         rate set by start_wav, seg*hop*in_rate/model_rate) ->
         (wav [B, emit*hop], mel [B, emit, 80], codes [B, emit]) of the chunk this call emitted (emit = 0 on the first call: one
@@ -691,20 +804,29 @@ class StreamingVoiceConversionEngine:
         copied first: the caller's tensor keeps its samples.
         far: [B, samples] in wav_chunk's dtype, what went to each caller's earpiece while the row was recorded: the slots with
         start_wav(echo=...) cancel its echo on the GPU behind the repair and in front of the step (Streams.echo).  The chunk is
-        copied first here too."""
+        copied first here too.  Slots with start_wav(echo_delay=...) run their estimator in front of the canceller, and the call
+        first applies the follow rule to the previous far= call's report (_follow_pending).  echo_stats: Streams.echo's stats tensor
+        for this call's rows (int64 [B, 4] on the device) or None."""
         fn = self.st.step_wav_async if pipelined else self.st.step_wav
         st = self.st
         if lost is not None:
             wav_chunk, fn = wav_chunk.clone(), functools.partial(fn, lost=lost)
+        rep = None
         if far is not None:
-            wav_chunk, fn = (wav_chunk if lost is not None else wav_chunk.clone()), functools.partial(fn, far=far)
+            self._follow_pending()
+            rep = self._far_report(self.slots)
+            wav_chunk, fn = (wav_chunk if lost is not None else wav_chunk.clone()), functools.partial(fn, far=far, **({} if rep is None else dict(echo_delay_report=rep)), **({} if echo_stats is None else dict(echo_stats=echo_stats)))
         if not (st.output_ld or st.output_formats):
             emit, c, m, w = fn(self.slots, wav_chunk, final=final, mel=mel)
+            if rep is not None:
+                self._note_report(self.slots, [wav_chunk.shape[1]] * len(self.slots), rep)
             return w, m, c[:, :emit]
         # output rates / formats: rows at the stride in force, all slots at one position, rate and format here (a view: pipelined
         # steps complete at join())
         buf = torch.empty(len(self.slots), st.output_ld or self.seg * self.ctx.hop, device=wav_chunk.device)
         emit, c, m, _ = fn(self.slots, wav_chunk, final=final, mel=mel, wav_out=buf)
+        if rep is not None:
+            self._note_report(self.slots, [wav_chunk.shape[1]] * len(self.slots), rep)
         w = st.wav_block(buf, self.slots, st.output_samples()[0] if emit else 0, st.output_ld or (emit or self.seg) * self.ctx.hop)
         return w, m, c[:, :emit]
 
@@ -764,7 +886,7 @@ class StreamingVoiceConversionEngine:
     @torch.no_grad()
     def infer_wav(self, src_wav, ref_mel, ref_len=None, pipelined=True, mel=None, in_rate=None, out_rate=None, out_filter=None, in_format=None,
                   out_format=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None, register=None, activity=None,
-                  activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, echo=None, far=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None,
+                  activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, echo=None, far=None, echo_delay=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None,
                   drift=None, **filter):
         """drift: the far device's clock error in ppm on both sides of the slots (start_wav), one value: the results are those of
         infer_wav(ctx.resample_drift(x, in_rate, model_rate, drift), ...), x the decoded utterance, and the returned wav is
@@ -798,12 +920,15 @@ class StreamingVoiceConversionEngine:
         infer(ctx.mel_denoise(ctx.wav2mel(x)), ...) bit for bit, x = the samples the front-end reads.  watermark: the output watermark
         (start): the returned model-rate wav is ctx.watermark_embed of the unmarked one, bit for bit.
         echo + far: echo cancellation (start_wav) with far [B, N], the far end of the whole utterance in src_wav's format: the
-        results are those of infer_wav(ctx.echo(src_wav, far, cfg, in_format), ...) bit for bit.  Not with loud_norm or trim."""
+        results are those of infer_wav(ctx.echo(src_wav, far, cfg, in_format), ...) bit for bit.  Not with loud_norm or trim.
+        echo_delay: the estimator beside the canceller (start_wav): the canceller's delay then follows the estimate from call to
+        call, so the results are those of the whole-signal canceller only until the first change."""
         self._check_voice(ref_mel, voice)
         self._host_checks(len(self.slots), voice, level=level, pitch=pitch, follow=follow, register=register, activity=activity, bypass=bypass,
                           conceal=conceal, echo=echo, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq)      # (before anything runs)
         self._check_lost(lost, conceal, loud_norm, trim)
         self._check_far(far, echo, loud_norm, trim)
+        self._echo_delay_values(echo_delay, echo, len(self.slots))
         if far is not None and tuple(far.shape) != tuple(src_wav.shape):
             raise ValueError(f"far: {tuple(far.shape)} for a src_wav of {tuple(src_wav.shape)}: the far end is the utterance's, sample for sample")
         trim = self._trim_keywords(trim)
@@ -813,7 +938,7 @@ class StreamingVoiceConversionEngine:
             src_wav = self._loud_norm(src_wav, in_rate, in_format)
         self.start_wav(ref_mel, ref_len, in_rate, out_rate=out_rate, out_filter=out_filter, in_format=in_format, out_format=out_format, level=level,
                        pitch=pitch, voice=voice, follow=follow, register=register, activity=activity, bypass=bypass, out_level=out_level, conceal=conceal,
-                       echo=echo, comfort=comfort, denoise=denoise, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq, drift=drift, **filter)
+                       echo=echo, echo_delay=echo_delay, comfort=comfort, denoise=denoise, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq, drift=drift, **filter)
         B, N = src_wav.shape
         L = self._in_len(in_rate)
         last = (N - 1) // L * L                       # the final call takes the remaining 1 .. L samples
@@ -845,7 +970,7 @@ class StreamingVoiceConversionEngine:
         return torch.cat(wavs, 1), torch.cat(mels, 1), torch.cat(codes, 1)
 
     def open_slots(self, slots, ref_mel, ref_len=None, in_rate=None, out_rate=None, out_filter=None, in_format=None, out_format=None, level=None,
-                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, echo=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None,
+                   pitch=None, voice=None, follow=None, register=None, activity=None, bypass=None, out_level=None, conceal=None, echo=None, echo_delay=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None,
                    drift=None, **filter):
         """drift: the slots' clock drift in ppm (start_wav), one value or a list with one per slot, on both sides of each slot.
         Start new utterances in `slots` while the other slots are mid-utterance: a full reset (models and streaming front-end,
@@ -861,12 +986,14 @@ class StreamingVoiceConversionEngine:
         value or a list with one per slot.  conceal: the slots' loss concealment (start_wav), one value or a list with one per slot.
         denoise: the slots' noise suppression (start_wav), one value or a list with one per slot.
         watermark: the slots' output watermark (start), one value or a list with one per slot.
+        echo_delay: the slots' echo-delay estimator (start_wav; it needs echo= on the same slot), one value or a list with one per slot.
         No trim=, as in start_wav: the slots stream, and a stream cannot drop time (infer_wav_staggered(trim=True) trims utterances
         it holds whole)."""
         self._check_voice(ref_mel, voice)
         drifts = self._drift_values(drift, len(slots))
         values = self._host_checks(len(slots), voice, level=level, pitch=pitch, follow=follow, register=register, activity=activity, bypass=bypass,
                                    conceal=conceal, echo=echo, comfort=comfort, denoise=denoise, out_level=out_level, watermark=watermark, tones=tones, eq=eq, out_eq=out_eq)
+        delays = self._echo_delay_values(echo_delay, echo, len(slots))
         self.st.reset(slots, which=7 | 8)
         self._reference(slots, ref_mel, ref_len, voice)
         self._set_out_rate(slots, out_rate, out_filter)
@@ -877,9 +1004,10 @@ class StreamingVoiceConversionEngine:
         self._set_drift(slots, drifts, out=(out_rate, out_filter), inp=(in_rate, filter))
         for keyword in values:      # (the order of _lib.SLOT_FEATURES: pitch behind level, out_level and watermark last)
             self._apply(keyword, slots, values[keyword], _per_slot(in_rate, len(slots)))
+        self._apply_echo_delay(slots, delays, _per_slot(in_rate, len(slots)))
 
     @torch.no_grad()
-    def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None, lost=None, far=None):
+    def feed_ragged(self, slots, wav, samples, final, pipelined=False, mel=None, lost=None, far=None, echo_stats=None):
         """Streaming waveform input for slots at different positions of their utterances (conan_step_wav_ragged): slot i takes the
         first samples[i] samples of wav row i (wav [n, <= seg*hop] cuda, or a list of 1-D rows, each in its slot's input format's
         dtype) with its own final flag; the rules per slot are feed()'s.
@@ -889,18 +1017,25 @@ class StreamingVoiceConversionEngine:
         utterances whole); open_slots(level=...) gives a slot the causal input leveller, which can, and a call may mix levelled
         and unlevelled slots.  lost: [n, packets] integer or bool (cuda), as feed()'s: the rows of slots with the concealment are
         repaired in front of the step, the others keep their bytes.  far: the rows' far end in wav's form (feed()'s): the rows
-        of slots with the canceller are cancelled behind the repair, the others keep their bytes."""
+        of slots with the canceller are cancelled behind the repair, the others keep their bytes.  echo_stats: as feed()'s."""
         fn = self.st.step_wav_ragged_async if pipelined else self.st.step_wav_ragged
         if (lost is not None or far is not None) and isinstance(wav, torch.Tensor):
             wav = wav.clone()      # (a list of rows is packed into a buffer of its own anyway)
-        emit, c, m, w = fn(slots, wav, samples, final, mel=mel, lost=lost, far=far)
+        rep = None
+        if far is not None:
+            self._follow_pending()
+            rep = self._far_report(slots)
+        emit, c, m, w = fn(slots, wav, samples, final, mel=mel, lost=lost, far=far, **({} if rep is None else dict(echo_delay_report=rep)),
+                        **({} if echo_stats is None else dict(echo_stats=echo_stats)))
+        if rep is not None:
+            self._note_report(slots, samples, rep)
         counts = self.st.output_samples()        # (emit * hop for a slot without an output rate)
         return [(self.st.wav_row(w, i, slots[i], counts[i]), m[i, :e], c[i, :e]) for i, e in enumerate(emit)]
 
     @torch.no_grad()
     def infer_wav_staggered(self, src_wavs, starts, ref_mel, pipelined=True, mel=None, in_rates=None, out_rates=None, out_filter=None,
                             in_formats=None, out_formats=None, loud_norm=False, trim=False, level=None, pitch=None, voice=None, follow=None,
-                            register=None, activity=None, activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, echo=None, far=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
+                            register=None, activity=None, activity_log=None, bypass=None, out_level=None, conceal=None, lost=None, echo=None, far=None, echo_delay=None, comfort=None, denoise=None, watermark=None, tones=None, eq=None, out_eq=None, **filter):
         """Utterances that start at different times, served together: src_wavs = list of 1-D cuda waveforms, starts[u] = the tick
         (one feed_ragged call, 80 ms of audio) at which utterance u's first audio arrives, ref_mel [U, Tr, 80] (one reference each).
         Utterance u takes the lowest free slot of self.slots at its start tick (a slot is free again once its drain has emitted 0
@@ -927,7 +1062,8 @@ class StreamingVoiceConversionEngine:
         watermark: the output watermark (start), one value for every utterance or a list with one per utterance.
         echo: echo cancellation (start_wav), one value for every utterance or a list with one per utterance; far: per utterance its
         whole far end (a 1-D tensor as long as the utterance, in its format) or None, which stands for a silent far end.  Not with
-        loud_norm or trim."""
+        loud_norm or trim.  echo_delay: the estimator beside the canceller (start_wav), one value for every utterance or a list with
+        one per utterance."""
         voice = self._check_voice(ref_mel, voice)
         U = len(src_wavs)
         # (host checks before anything runs; per utterance, in the form open_slots takes back)
@@ -939,6 +1075,7 @@ class StreamingVoiceConversionEngine:
         self._check_far(far, echo, loud_norm, trim)
         if far is not None and len(far) != U:
             raise ValueError(f"far: {len(far)} values for {U} utterances")
+        delays = self._echo_delay_values(echo_delay, echo, U, "utterances")
         if activity_log is not None:
             activity_log[:] = [[] for _ in range(U)]
         ifmts, ofmts, orates, rates = (list(v) if v is not None else [None] * U for v in (in_formats, out_formats, out_rates, in_rates))
@@ -966,7 +1103,8 @@ class StreamingVoiceConversionEngine:
                 self.open_slots([live[u][0] for u in new], torch.stack([ref_mel[u] for u in new]) if voice is None else None,
                                 voice=None if voice is None else (voice[0], [voice[1][u] for u in new]), in_rate=[rates[u] for u in new],
                                 out_rate=[orates[u] for u in new], out_filter=out_filter, in_format=[ifmts[u] for u in new],
-                                out_format=[ofmts[u] for u in new], **{k: [v[u] for u in new] for k, v in values.items()}, **filter)
+                                out_format=[ofmts[u] for u in new], echo_delay=[delays[u] for u in new],
+                                **{k: [v[u] for u in new] for k, v in values.items()}, **filter)
             if not live:
                 tick += 1
                 continue

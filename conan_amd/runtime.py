@@ -100,6 +100,22 @@ def _echo_cfg(cfg, rate=None):
     raise ValueError(f"echo: {cfg!r} is neither an _lib.EchoCfg, a dict of its fields, a rate nor True")
 
 
+def _echo_delay_cfg(cfg, rate=None):
+    """An enabled _lib.EchoDelayCfg of: one itself; True (the defaults of `rate`); an integer rate; a dict of fields over the defaults
+    of `rate` (without a rate every field must be given)."""
+    if isinstance(cfg, _lib.EchoDelayCfg):
+        return cfg
+    if cfg is True:
+        if rate is None:
+            raise ValueError("echo_delay: True stands for a rate's defaults, and no rate is known here")
+        return _lib.echo_delay_cfg(rate)
+    if isinstance(cfg, dict):
+        return _lib.echo_delay_cfg(rate, **cfg)
+    if isinstance(cfg, (int, np.integer)) and not isinstance(cfg, bool):
+        return _lib.echo_delay_cfg(int(cfg))
+    raise ValueError(f"echo_delay: {cfg!r} is neither an _lib.EchoDelayCfg, a dict of its fields, a rate nor True")
+
+
 def mel_cfg(fft_size=1024, hop_size=320, win_length=1024, num_mels=80, fmin=80, fmax=7600, sample_rate=16000, eps=1e-6,
             mel_vmin=-6.0, mel_vmax=1.5, framing=0, natural_log=False, mag_eps=0.0):
     """conan_mel_cfg with Context.wav2mel's defaults (inference/Conan.py:57-70)."""
@@ -750,6 +766,33 @@ class Context:
         out = buf.view(SAMPLE_DTYPES[fmt])[:, :N].reshape(*lead, N)
         return (out, st) if stats else out
 
+    def echo_delay(self, mic, far, cfg, fmt="f32", lengths=None):
+        """conan_echo_delay: the echo-delay estimator's law (include/conan_hip.h, conan_echo_delay_cfg) on whole signals from the zero
+        state.  mic, far [..., N] of format `fmt`, as Context.echo takes them (both are only read); cfg: an _lib.EchoDelayCfg, a dict
+        of its fields, or an input rate, which stands for that rate's defaults (_lib.echo_delay_keywords); lengths: per row the
+        samples to take (default N).  -> (track int64 [n, N // 1024, 6] (cuda): per row the report after each frame end, zeros
+        behind a shorter row's frames; report int64 [n, 6]: est, age, cand, run, last_pk, last_s after the last sample).  It is
+        what a slot with Streams.set_echo_delay computes over its rows, bit for bit."""
+        c = _echo_delay_cfg(cfg)
+        f = _lib.sample_format(fmt)
+        dev = torch.device("cuda", self.device)
+        mic, far = mic.to(dev), far.to(dev)
+        if mic.dtype != SAMPLE_DTYPES[fmt] or far.dtype != SAMPLE_DTYPES[fmt] or mic.shape != far.shape:
+            raise ValueError(f"echo_delay: format {fmt!r} takes {SAMPLE_DTYPES[fmt]} samples in mic and far rows of one shape, got {mic.dtype} {tuple(mic.shape)} and {far.dtype} {tuple(far.shape)}")
+        lead, N = mic.shape[:-1], mic.shape[-1]
+        n = int(np.prod(lead)) if len(lead) else 1
+        ld = max((N * _lib.SAMPLE_BYTES[fmt] + 3) // 4, 1)
+        buf = _row_bytes(mic.reshape(n, N), n, ld, dev)
+        fbuf = _row_bytes(far.reshape(n, N), n, ld, dev)
+        frames = N // _lib.ECHO_DELAY_FRAME
+        track = torch.zeros(n, frames, 6, dtype=torch.int64, device=dev)
+        report = torch.zeros(n, 6, dtype=torch.int64, device=dev)
+        sm = np.full(n, N, dtype=np.int64) if lengths is None else np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(n))
+        if n and N:
+            _lib.check(self.lib.conan_echo_delay(self.h, C.byref(c), f, _ptr(buf), ld, _ptr(fbuf), ld, n, sm.ctypes.data_as(C.c_void_p),
+                                                 _ptr(track) if frames else None, frames * 6, _ptr(report), _stream()))
+        return track, report
+
     def mel_denoise(self, mel, lens=None, cfg=None, seed=None, out=None, state=False, **kw):
         """conan_mel_denoise: the noise suppressor's law (include/conan_hip.h, conan_denoise_cfg) on whole log-mel rows, one launch.
         mel [n, T, num_mels] (or [T, num_mels]) float32; a 3-D view whose rows are contiguous keeps its row stride.  lens: per row
@@ -1147,6 +1190,7 @@ class Streams:
         self.input_rate_set = False      # set_input_rate has run on this stream-set (its history ring exists)
         self.output_rates = {}           # slot -> output rate, for the slots whose audio leaves at another rate than the model's
         self.input_drifts, self.output_drifts = set(), set()      # the slots with a drift resampler (set_input_drift / set_output_drift)
+        self.echo_delays = set()                                  # the slots with an echo-delay estimator (set_echo_delay)
         self.output_ld = 0               # set_output_ld: row stride of every step's wav (0: each step's own)
         self.input_formats = {}          # slot -> 's16' | 'ulaw' | 'alaw', for the slots whose wav-in rows are not float32
         self.output_formats = {}         # slot -> the same, for the slots whose audio leaves in another format
@@ -1663,6 +1707,73 @@ class Streams:
         """conan_streams_echo_state: uint8 [n, bytes] (cuda), the slots' canceller states for set_echo(seed=).  Joins pipelined work."""
         return self._feature_seed_rows("echo", slots)
 
+    def set_echo_delay(self, slots, cfg=True, rate=None, seed=None, **fields):
+        """conan_streams_set_echo_delay: the echo-delay estimator on the slots' wav-in rows (include/conan_hip.h,
+        conan_echo_delay_cfg).  cfg: True (the defaults of `rate`, the slots' input rate; None: the model rate), a dict of fields
+        over those defaults, an _lib.EchoDelayCfg, or None, which turns the feature off; keywords are fields too.  seed: uint8
+        [n, bytes] (cuda) rows of echo_delay_state (a hand-over).  It may be called at any time (it joins pipelined work) and
+        survives resets; an enabled slot keeps its state (a changed n_lags keeps the sums that still exist), which restarts when a
+        slot that was off is enabled and at the first estimator call after a reset of the front-end.  Slot snapshots do not carry
+        it, and the slot needs no canceller.  The estimate itself is echo_delay(), or far= on the wav-in steps."""
+        a, p = _i32(slots)
+        if cfg is None or cfg is False:
+            if fields:
+                raise ValueError("set_echo_delay: cfg=None turns the estimator off and takes no keywords")
+            c = _lib.EchoDelayCfg()
+        else:
+            if fields:
+                cfg = dict(_lib.echo_delay_keywords(cfg) if isinstance(cfg, _lib.EchoDelayCfg) else cfg if isinstance(cfg, dict) else {}, **fields)
+            c = _echo_delay_cfg(cfg, self.model_rate if rate is None else int(rate))
+        if seed is not None and (seed.dtype != torch.uint8 or seed.dim() != 2 or seed.shape[0] != len(a) or not seed.is_cuda or seed.stride(1) != 1):
+            raise ValueError("set_echo_delay: seed must be a cuda uint8 [n, bytes] tensor, as echo_delay_state returns it")
+        _lib.check(self.lib.conan_streams_set_echo_delay(self.h, p, len(a), C.byref(c), _ptr(seed), int(seed.stride(0)) if seed is not None else 0, _stream()))
+        self._release()
+        (self.echo_delays.update if c.enabled else self.echo_delays.difference_update)(int(s) for s in a)
+
+    def echo_delay_cfg(self, slots):
+        """conan_streams_echo_delay_cfg: per slot the dict of its fields (set_echo_delay takes it back), None for a slot without."""
+        out = []
+        for slot in slots:
+            c = _lib.EchoDelayCfg()
+            _lib.check(self.lib.conan_streams_echo_delay_cfg(self.h, int(slot), C.byref(c)))
+            out.append(_lib.echo_delay_keywords(c) if c.enabled else None)
+        return out
+
+    def echo_delay(self, slots, wav, samples, far, report=None):
+        """conan_streams_echo_delay: the estimator READS the rows and the far rows - in front of echo(), which rewrites wav, and
+        behind conceal() - and updates the slots' states.  wav, far, samples: as echo()'s; report: an int64 cuda tensor [n, 6] to
+        fill (per row est, age, cand, run, last_pk, last_s after the call; _lib.ECHO_DELAY_REPORT) or None.  Rows of slots without
+        the feature and rows without samples are skipped and report zeros.  -> report"""
+        a, p = _i32(slots)
+        n = len(a)
+        for name, t in (("wav", wav), ("far", far)):
+            if not (t.is_cuda and t.dim() == 2 and t.shape[0] == n and (t.shape[1] < 2 or t.stride(1) == 1)
+                    and t.stride(0) * t.element_size() % 4 == 0 and t.data_ptr() % 4 == 0):
+                raise ValueError(f"echo_delay: {name} must be a 2-D cuda tensor [n, .] with contiguous rows a multiple of 4 bytes apart")
+        if report is not None and not (report.is_cuda and report.dtype == torch.int64 and report.is_contiguous() and tuple(report.shape) == (n, 6)):
+            raise ValueError("echo_delay: report must be a contiguous int64 cuda tensor [n, 6]")
+        sm, sp = _i32([int(samples)] * n if isinstance(samples, (int, np.integer)) else samples)
+        assert len(sm) == n, (n, len(sm))
+        _lib.check(self.lib.conan_streams_echo_delay(self.h, p, n, sp, _ptr(wav), wav.stride(0) * wav.element_size() // 4, _ptr(far),
+                                                     far.stride(0) * far.element_size() // 4, _ptr(report), _stream()))
+        return report
+
+    def echo_delay_state(self, slots):
+        """conan_streams_echo_delay_state: uint8 [n, bytes] (cuda), the slots' estimator states for set_echo_delay(seed=).  Joins
+        pipelined work."""
+        a, p = _i32(slots)
+        nbytes = int(_lib.check(self.lib.conan_echo_delay_state_bytes()))
+        out = torch.empty(len(a), nbytes, dtype=torch.uint8, device=self.dev)
+        _lib.check(self.lib.conan_streams_echo_delay_state(self.h, p, len(a), _ptr(out), nbytes, _stream()))
+        self._release()
+        return out
+
+    def _far_stages(self, a, wav, samples, far_rows, echo_stats, echo_delay_report):
+        """far= of a wav-in step: the delay estimator of the slots that have one reads the rows, then the canceller rewrites them."""
+        if self.echo_delays:
+            self.echo_delay(a, wav, samples, far_rows, echo_delay_report)
+        self.echo(a, wav, samples, far_rows, echo_stats)
+
     def set_denoise(self, slots, cfg=True, seed=None, **kw):
         """conan_streams_set_denoise: noise suppression on the slots' wav-in frames (include/conan_hip.h, conan_denoise_cfg): a causal
         spectral gate on the log-mel frames the front-end has just computed, under a per-band noise floor tracked per frame, in place
@@ -2058,7 +2169,7 @@ class Streams:
                 _lib.check(self.lib.conan_streams_output_fence(self.h, C.c_void_p(out_fence.cuda_stream)))
         _lib.check(self.lib.conan_step_async(self.h, p, n, emit, _ptr(mel_chunk), _ptr(codes), _ptr(mel_out), _ptr(wav_out), _stream()))
 
-    def step_wav(self, slots, wav, final=False, codes=None, mel_out=None, wav_out=None, mel=None, lost=None, far=None, echo_stats=None):
+    def step_wav(self, slots, wav, final=False, codes=None, mel_out=None, wav_out=None, mel=None, lost=None, far=None, echo_stats=None, echo_delay_report=None):
         """Waveform-in chunk step (conan_step_wav): wav [n, samples] cuda float32, samples = seg*hop (0 .. seg*hop when final);
         slots with an input rate (set_input_rate) take seg*hop*rate/model_rate samples instead.
         -> (emit, codes [n, seg], mel [n, emit, 80], wav [n, emit*hop]); emit = 0: no chunk this call (the first call, the end of a
@@ -2066,12 +2177,13 @@ class Streams:
         take int16 ('s16') or uint8 ('ulaw' / 'alaw') rows; with an output rate, stride or format wav is a list of 1-D rows, each
         in its slot's dtype.  lost: the packet flags of the rows [n, packets] (conceal(), on the rows as packed for the library, in
         front of the step; a contiguous float32 wav on the device is its own packed form and is repaired in place).  far: the far
-        end of the rows, shaped and typed as wav (echo(), behind the repair and in front of the step); echo_stats: echo()'s stats."""
-        return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, False, lost, far, echo_stats)
+        end of the rows, shaped and typed as wav (echo_delay() for the slots with an estimator, then echo(), behind the repair and in
+        front of the step); echo_stats: echo()'s stats; echo_delay_report: echo_delay()'s report."""
+        return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, False, lost, far, echo_stats, echo_delay_report)
 
-    def step_wav_async(self, slots, wav, final=False, codes=None, mel_out=None, wav_out=None, mel=None, lost=None, far=None, echo_stats=None):
+    def step_wav_async(self, slots, wav, final=False, codes=None, mel_out=None, wav_out=None, mel=None, lost=None, far=None, echo_stats=None, echo_delay_report=None):
         """Pipelined step_wav (conan_step_wav_async): the outputs are complete after join(); same return value."""
-        return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, True, lost, far, echo_stats)
+        return self._step_wav(slots, wav, final, codes, mel_out, wav_out, mel, True, lost, far, echo_stats, echo_delay_report)
 
     def _wav_in_call(self, n, wav, codes, mel_out, wav_out, mel, pipelined, call):
         """What the wav-in steps share: the default output buffers and their lifetime (a pipelined call's are kept until the next
@@ -2091,7 +2203,7 @@ class Streams:
             self._release()
         return codes, mel_out, wav_out
 
-    def _step_wav(self, slots, wav, final, codes, mel_out, wav_out, mel, pipelined, lost=None, far=None, echo_stats=None):
+    def _step_wav(self, slots, wav, final, codes, mel_out, wav_out, mel, pipelined, lost=None, far=None, echo_stats=None, echo_delay_report=None):
         a, p = _i32(slots)
         n = len(a)
         hop, nm = self.ctx.hop, self.ctx.cfg.num_mels
@@ -2102,7 +2214,7 @@ class Streams:
             self.conceal(a, wav, samples, lost)
         if far is not None and samples:
             assert far.dim() == 2 and tuple(far.shape) == (n, samples), far.shape
-            self.echo(a, wav, samples, self._in_rows(a, far, samples)[0], echo_stats)
+            self._far_stages(a, wav, samples, self._in_rows(a, far, samples)[0], echo_stats, echo_delay_report)
         emit = C.c_int32(0)
         fn = self.lib.conan_step_wav_async if pipelined else self.lib.conan_step_wav
         codes, mel_out, wav_out = self._wav_in_call(n, wav, codes, mel_out, wav_out, mel, pipelined, lambda mc, c, m, w: _lib.check(
@@ -2114,7 +2226,7 @@ class Streams:
             w = wav_out.view(-1)[:n * e * hop].view(n, e * hop)
         return e, codes, mel_out.view(-1)[:n * e * nm].view(n, e, nm), w
 
-    def step_wav_ragged(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None, lost=None, far=None, echo_stats=None):
+    def step_wav_ragged(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None, lost=None, far=None, echo_stats=None, echo_delay_report=None):
         """Waveform-in chunk step for slots at different positions of their utterances (conan_step_wav_ragged): slot i takes the
         first samples[i] samples of wav row i (wav [n, <= seg*hop] cuda float32, or None when every samples[i] is 0) and is stepped
         as step_wav([slot], samples[i], final[i]) alone would step it.  Rows wider than seg*hop (slots with an input rate above the
@@ -2122,14 +2234,14 @@ class Streams:
         dtype of its slot's input format (float32, int16, uint8): they are packed from the start of rows a whole number of 4-byte
         units apart.  -> (emit: list of n ints, codes [n, seg], mel [n, seg, 80], wav [n, seg*hop] float32 storage): row i holds
         emit[i] frames (wav_row(wav, i, slot, count) gives it in the slot's output dtype); the rest of the row is left as it was.
-        lost, far, echo_stats: as step_wav's (far in wav's form: one tensor or a list of rows)."""
-        return self._step_wav_ragged(slots, wav, samples, final, codes, mel_out, wav_out, mel, False, lost, far, echo_stats)
+        lost, far, echo_stats, echo_delay_report: as step_wav's (far in wav's form: one tensor or a list of rows)."""
+        return self._step_wav_ragged(slots, wav, samples, final, codes, mel_out, wav_out, mel, False, lost, far, echo_stats, echo_delay_report)
 
-    def step_wav_ragged_async(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None, lost=None, far=None, echo_stats=None):
+    def step_wav_ragged_async(self, slots, wav, samples, final, codes=None, mel_out=None, wav_out=None, mel=None, lost=None, far=None, echo_stats=None, echo_delay_report=None):
         """Pipelined step_wav_ragged (conan_step_wav_ragged_async): the outputs are complete after join(); same return value."""
-        return self._step_wav_ragged(slots, wav, samples, final, codes, mel_out, wav_out, mel, True, lost, far, echo_stats)
+        return self._step_wav_ragged(slots, wav, samples, final, codes, mel_out, wav_out, mel, True, lost, far, echo_stats, echo_delay_report)
 
-    def _step_wav_ragged(self, slots, wav, samples, final, codes, mel_out, wav_out, mel, pipelined, lost=None, far=None, echo_stats=None):
+    def _step_wav_ragged(self, slots, wav, samples, final, codes, mel_out, wav_out, mel, pipelined, lost=None, far=None, echo_stats=None, echo_delay_report=None):
         a, p = _i32(slots)
         n = len(a)
         L = self.seg * self.ctx.hop
@@ -2142,7 +2254,7 @@ class Streams:
             if lost is not None:
                 self.conceal(a, wav, sm, lost)
             if far is not None:
-                self.echo(a, wav, sm, self._in_rows(a, far, ld)[0], echo_stats)
+                self._far_stages(a, wav, sm, self._in_rows(a, far, ld)[0], echo_stats, echo_delay_report)
         emit = (C.c_int32 * n)()
         if ld == L:
             fn, stride = self.lib.conan_step_wav_ragged_async if pipelined else self.lib.conan_step_wav_ragged, ()

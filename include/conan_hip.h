@@ -1443,6 +1443,91 @@ int conan_streams_echo_state(conan_streams* s, const int32_t* slots, int n, void
 int conan_echo(conan_ctx* ctx, const conan_echo_cfg* cfg, int format, void* x_dev, int64_t ld, const void* far_dev, int64_t far_ld, int n,
                const int64_t* samples, int64_t* stats_dev, void* stream);
 
+/* Echo delay (added within ABI 9: a caller detects it by the symbol conan_streams_set_echo_delay; no existing struct or call changes).
+ * The canceller above cancels what lies inside `taps` samples behind a bulk `delay` the host must supply, and the host cannot know it:
+ * it is the round trip through the far device's playout buffer, loudspeaker, room, microphone, the network and the jitter buffer,
+ * typically 50 to 300 ms, and it moves during a call.  It can only be measured by comparing the mic row with the far row, and no
+ * sample of a slot reaches the host.  The estimator does that per slot on the GPU: it READS the rows in front of the canceller and
+ * reports a lag; the host turns the report into the canceller's `delay` (conan_amd._lib.echo_delay_follow is one rule).
+ * The law (tests/echo_delay_ref.py restates it in numpy with Python / int64 integers).  Everything is per slot, at the slot's input
+ * rate, in positions t = 0, 1, ... since the last restart.  d[t] = q(dec(mic[t])) and x[t] = q(dec(far[t])) are the canceller's 16-bit
+ * views (q, dec and the non-finite -> 0 rule as above); x[t] = 0 for t < 0.
+ *   Ternary signs: sgn(v) = +1 if v >= thr, -1 if v <= -thr, else 0.  An idle far end, or A-law's 8-LSB silence under a thr above 8,
+ *     contributes nothing: there is no separate idle test.
+ *   Accumulation, for every t and every lag l in 0 .. n_lags - 1: A[l] += sgn(d[t]) * sgn(x[t - l]).  A is int32, and A[l] = 0 for
+ *     l >= n_lags, always (a setter can change n_lags without touching the rest; the rule of w[taps ..] above).
+ *   Frame end, W = CONAN_ECHO_DELAY_FRAME: when the sample at position t with (t + 1) mod W == 0 has been added, in this order:
+ *     1. a[l] = |A[l]|; p = the smallest l < n_lags that maximises a; pk = a[p]; s = sum of a (int64).
+ *     2. ok = pk >= min_peak and pk * n_lags > ratio * s (int64 products).
+ *     3. If ok and cand >= 0 and |p - cand| <= tol: run += 1; else if ok: run = 1; else run = 0.  Then cand = ok ? p : -1.
+ *     4. If run >= hold: est = p, age = 0; else if est >= 0: age = min(age + 1, 2^31 - 1).
+ *     5. frames += 1, last_pk = pk, last_s = s.
+ *     6. Leak: A[l] -= A[l] >> leak for l < n_lags (an arithmetic shift: it floors).
+ *   The restart value is all zero with est = cand = -1.
+ * Bounds: a frame adds at most W to |A[l]| and the leak takes floor(A / 2^leak), so |A| <= (W + 1) * 2^leak (<= 262400 at leak 8: int32
+ * with room); with leak <= 8 and n_lags <= 6144, s <= 6144 * 262400 < 2^31.6, so s and both products need int64 (pk * n_lags < 2^31,
+ * ratio * s < 2^63).  All sums are exact integers and the leak and the decision happen only at fixed multiples of W: every reduction
+ * order and every cut into calls gives the same bits.  W = 1024 and the ternary signs are choices; nothing else was built or timed.
+ * The state restarts at the slot's first estimator call after a reset that includes CONAN_MODEL_FRONTEND and when a slot that was off
+ * is enabled; a seed replaces it with the seeded record.
+ * Defaults for a rate R (conan_amd._lib.echo_delay_keywords): n_lags = min(6144, 384 ms rounded to a multiple of 64), thr 16, leak 5,
+ * ratio 10, min_peak 1024, hold 4, tol = 2 ms.  Choices, not measurements (DESIGN.md 4.29 says what the reference measures with them). */
+#define CONAN_ECHO_DELAY_FRAME 1024
+#define CONAN_ECHO_DELAY_MAX_LAGS 6144 /* CONAN_ECHO_MAX_DELAY + CONAN_ECHO_MAX_TAPS */
+typedef struct conan_echo_delay_cfg {
+  int32_t enabled;     /* 0: off (other fields ignored) | 1 */
+  int32_t n_lags;      /* lags 0 .. n_lags - 1: a multiple of 64 in 64 .. CONAN_ECHO_DELAY_MAX_LAGS */
+  int32_t thr;         /* 1 .. 32767: the ternary threshold on the 16-bit view */
+  int32_t leak;        /* 1 .. 8: A loses A >> leak at every frame end */
+  int32_t ratio;       /* >= 1: the peak must exceed `ratio` times the mean of |A| */
+  int32_t min_peak;    /* >= 1: ... and reach this value */
+  int32_t hold;        /* >= 1: frames in a row a candidate must stand before it becomes est */
+  int32_t tol;         /* >= 0: how far a candidate may move between frames, in samples */
+  int32_t reserved[4]; /* ignored */
+} conan_echo_delay_cfg; /* 48 bytes */
+/* Sets (cfg->enabled = 1) or removes (0) the estimator for `slots`, with conan_streams_set_echo's semantics point for point: every
+ * argument is checked before anything changes, a stream-set without the streaming front-end is CONAN_ERR_STATE, pending pipelined work
+ * is joined, the setting persists across resets.  A setter call on an enabled slot without a seed replaces the fields and keeps the
+ * state: a changed n_lags keeps A[l] for l below both values and zeroes the rest.  seed_dev (may be null): row i at seed_dev + i *
+ * seed_ld bytes is a record as conan_streams_echo_delay_state writes it and becomes the state of slots[i] on `stream` (with A[n_lags ..]
+ * cleared, should the record come from a slot with more lags); the call reads
+ * each seed's `pos` back (one small copy and a wait on `stream`), because the host tells the kernel where in a frame a slot stands.
+ * Memory: the first enabling call allocates conan_echo_delay_state_bytes() per slot and 4 row tables; conan_streams_state_bytes counts
+ * them from then on.  A stream-set that never calls the setter allocates nothing and runs exactly the launches it ran before; the step
+ * calls of one that does run exactly the launches they ran before, too.  Snapshots carry neither the setting nor the state.  The slot
+ * needs no canceller. */
+int conan_streams_set_echo_delay(conan_streams* s, const int32_t* slots, int n, const conan_echo_delay_cfg* cfg, const void* seed_dev, int64_t seed_ld,
+                                 void* stream);
+/* Host only: the estimator's cfg of `slot` as set (zeros for a slot without one). */
+int conan_streams_echo_delay_cfg(const conan_streams* s, int slot, conan_echo_delay_cfg* cfg_out);
+/* Reads row i - samples[i] (host, >= 0) samples in the input format of slots[i] at wav_dev + i * wav_ld * 4 bytes, the far end in the
+ * same format at far_dev + i * far_ld * 4 bytes - and writes NEITHER.  ONE launch (cnk::echo_delay_kernel, one workgroup per row) on
+ * `stream`; rows of slots without the feature and rows with samples[i] = 0 are skipped, and a call with no row to do launches nothing
+ * and returns CONAN_OK.  The caller orders it behind conan_streams_conceal and IN FRONT OF conan_streams_echo on the same stream: the
+ * canceller rewrites the mic row.
+ * report_dev (may be null): int64 [n][6], row i = {est, age, cand, run, last_pk, last_s} after the call; est is the confirmed lag in
+ * samples or -1, age the frames since it was last confirmed.  A skipped row reports zeros (when a call skips a row, the table is
+ * cleared by one memset in front of the launch). */
+int conan_streams_echo_delay(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const void* wav_dev, int64_t wav_ld, const void* far_dev,
+                             int64_t far_ld, int64_t* report_dev, void* stream);
+/* Bytes of one slot's estimator state: a fixed-size, position-independent record, little endian -
+ *   0  int64 pos (samples since the restart; pos mod 1024 of them lie in the open frame)
+ *   8  int32 est   12  int32 age   16  int32 cand   20  int32 run      24  int64 frames, last_pk, last_s      48  16 bytes reserved (0)
+ *  64  int32 A[CONAN_ECHO_DELAY_MAX_LAGS] (zeros from n_lags on)
+ *  then int8 h[CONAN_ECHO_DELAY_MAX_LAGS]: h[0] = 0, h[1 ..] the far end's last 6143 ternary values before `pos`, oldest first. */
+int64_t conan_echo_delay_state_bytes(void);
+/* The states of `slots` -> row i at state_dev + i * ld bytes (8-byte aligned, ld a multiple of 8 and at least the record's bytes), on
+ * `stream` behind a join of pipelined work.  A slot about to restart reports the restart state; a slot without the feature is
+ * CONAN_ERR_STATE. */
+int conan_streams_echo_delay_state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream);
+/* The law on whole signals from the zero state, and the bit-exact yardstick of the streaming form: row i (n rows in 1 .. 65535) holds
+ * samples[i] (host) samples of `format` (CONAN_SAMPLE_*) at mic_dev + i * ld * 4 bytes, its far end lies at far_dev + i * far_ld * 4
+ * bytes.  cfg->enabled must be 1.  track_dev (may be null): int64 rows track_ld apart (in int64), row i holds the report after each of
+ * its samples[i] / 1024 frame ends, six values per frame; track_ld must hold them.  report_dev (may be null): as above, after the last
+ * sample.  One launch of the same kernel, which walks a row frame by frame. */
+int conan_echo_delay(conan_ctx* ctx, const conan_echo_delay_cfg* cfg, int format, const void* mic_dev, int64_t ld, const void* far_dev, int64_t far_ld, int n,
+                     const int64_t* samples, int64_t* track_dev, int64_t track_ld, int64_t* report_dev, void* stream);
+
 /* Silence trimming (added within ABI 9: a caller detects it by the exported symbol; no existing struct or call changes).  The offline
  * half of source activity: the reference's trim_long_sil (utils/audio/vad.py, trim_long_silences) cuts the long pauses out of a whole
  * recording - a moving average over an external detector's flags, a dilation that keeps short pauses, a hard cut - and this call does
