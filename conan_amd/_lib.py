@@ -164,12 +164,8 @@ _PROTOS = {
     "conan_streams_echo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "conan_echo_state_bytes": (C.c_int64, []),
     "conan_echo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    # (the estimator is bound here, not through SLOT_FEATURES: it is no stage of the wav-in chain)
-    "conan_streams_set_echo_delay": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "conan_streams_echo_delay_cfg": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "conan_streams_echo_delay": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "conan_echo_delay_state_bytes": (C.c_int64, []),
-    "conan_streams_echo_delay_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "conan_echo_delay": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
                                    C.c_void_p, C.c_void_p]),
     "conan_denoise_state_bytes": (C.c_int64, []),
@@ -1061,6 +1057,7 @@ class SlotFeature(typing.NamedTuple):
     stream: bool = True           # the setter takes a stream (and joins pipelined work: the buffers in flight are released)
     release: bool = True          # ... unless the setter leaves them alone
     mirror: str = None            # the Streams dict slot -> keywords, for the features that keep one
+    engine_own: bool = False      # the engine applies it itself, by rules of its own (echo_delay=), not as one of the table's keywords
 
     @property
     def method(self):
@@ -1068,7 +1065,7 @@ class SlotFeature(typing.NamedTuple):
         return self.setter[len("conan_streams_"):]
 
 
-# in the order open_slots applies them
+# in the order open_slots applies them (echo_delay: behind them all, by the engine's own rules)
 SLOT_FEATURES = {f.keyword: f for f in (
     SlotFeature("eq", "the equaliser", EqCfg, "enabled", eq_cfg, eq_keywords, "conan_streams_set_input_eq", "conan_streams_input_eq",
                 seed_state="conan_streams_input_eq_state", seed_bytes="conan_eq_state_bytes"),
@@ -1095,6 +1092,9 @@ SLOT_FEATURES = {f.keyword: f for f in (
                 "conan_streams_comfort", "conan_streams_comfort_state", ComfortState, last="conan_step_wav_comfort"),
     SlotFeature("tones", "the tone detector", ToneCfg, "mode", tone_cfg, tone_keywords, "conan_streams_set_tones", "conan_streams_tones",
                 "conan_streams_tone_state", ToneState, last="conan_step_wav_tones"),
+    SlotFeature("echo_delay", "the estimator", EchoDelayCfg, "enabled", echo_delay_cfg, echo_delay_keywords, "conan_streams_set_echo_delay",
+                "conan_streams_echo_delay_cfg", seed_state="conan_streams_echo_delay_state", seed_bytes="conan_echo_delay_state_bytes",
+                engine_own=True),
     SlotFeature("out_eq", "the equaliser", EqCfg, "enabled", eq_cfg, eq_keywords, "conan_streams_set_output_eq", "conan_streams_output_eq",
                 seed_state="conan_streams_output_eq_state", seed_bytes="conan_eq_state_bytes"),
     SlotFeature("out_level", "the leveller", LevelCfg, "enabled", level_cfg, level_keywords, "conan_streams_set_output_level",

@@ -3,7 +3,7 @@
 // in front of the wav-in step calls, in place and in the slot's input format; no step path reads anything of it.
 #include <climits>
 
-#include "streams.h"
+#include "prestep.h"
 #include "sample_dev.h"
 
 namespace cnk {
@@ -184,7 +184,6 @@ namespace conc {
 
 static_assert(sizeof(conan_conceal_cfg) == 32, "eight int32 fields");
 static_assert(CONAN_CONCEAL_MAX_LAG == cnk::kConcMaxLag && CONAN_CONCEAL_MAX_WINDOW == cnk::kConcMaxWindow, "the kernel's limits are the header's");
-constexpr int64_t kMaxSamples = 1ll << 40, kMaxStride = 1ll << 40;
 
 void check_cfg(const conan_conceal_cfg& c, const char* who) {
   const std::string w = std::string(who) + ": ";
@@ -209,121 +208,45 @@ cnk::ConcRow row(const conan_conceal_cfg& c) {
 
 static int64_t packets(int64_t samples, int packet) { return (samples + packet - 1) / packet; }
 
+// The feature's part of the pre-step row call (prestep.h): the second buffer holds the caller's packet flags, one int per packet
+struct Stage {
+  using Cfg = conan_conceal_cfg; using Row = cnk::ConcRow; using Args = cnk::ConcArgs;
+  struct Call { void* wav; int64_t wav_ld; const int32_t* aux; int64_t aux_ld; };
+  static constexpr const char *kName = "conceal", *kWhole = "conan_conceal", *kSet = "conan_streams_set_conceal", *kCall = "conan_streams_conceal";
+  static constexpr const char *kAux = "lost", *kKernel = "conceal_kernel";
+  static constexpr bool kAuxAudio = false;
+  static constexpr int kReport = 0, kBlock = 0;
+  static constexpr auto set = &conan_streams::conc;
+  static constexpr auto check_cfg = &conc::check_cfg;
+  static constexpr auto row = &conc::row;
+  static constexpr auto launch = &cnk::launch_conceal;
+  static const char* check_call(const Call&) { return nullptr; }
+  static const char* check_row(const Cfg& c, int64_t samples, const Call& b) {
+    return packets(samples, c.packet) > b.aux_ld ? "lost_ld must cover ceil(samples / packet) flags" : nullptr;
+  }
+  static void fill(Args& a, const Call& b) { a.wav = b.wav; a.wav_ld = b.wav_ld; a.lost = b.aux; a.lost_ld = b.aux_ld; }
+};
+
 void whole(conan_ctx* ctx, const conan_conceal_cfg* cfg, int format, void* x_dev, int64_t ld, int n, const int64_t* samples, const int32_t* lost_dev,
            int64_t lost_ld, void* stream) {
-  if (!ctx || !cfg || !x_dev || !samples || !lost_dev) throw Error(CONAN_ERR_INVALID, "null argument");
-  check_cfg(*cfg, "conan_conceal");
-  if (!cfg->enabled) throw Error(CONAN_ERR_INVALID, "conan_conceal: cfg.enabled must be 1");
-  wavio::check_format(format, "conan_conceal");
-  if (n < 1 || n > 65535) throw Error(CONAN_ERR_INVALID, "conan_conceal: n must be in 1 .. 65535");
-  if (ld < 0 || ld > kMaxStride || lost_ld < 0 || lost_ld > kMaxStride) throw Error(CONAN_ERR_INVALID, "conan_conceal: ld and lost_ld must be in 0 .. 2^40");
-  if ((uintptr_t)x_dev & 3) throw Error(CONAN_ERR_INVALID, "conan_conceal: x_dev must be 4-byte aligned");
-  const int bps = wavio::bytes_per_sample(format);
-  for (int i = 0; i < n; ++i) {
-    if (samples[i] < 0 || samples[i] > kMaxSamples) throw Error(CONAN_ERR_INVALID, "conan_conceal: row " + std::to_string(i) + ": samples must be in 0 .. 2^40");
-    if (samples[i] * bps > ld * 4) throw Error(CONAN_ERR_INVALID, "conan_conceal: row " + std::to_string(i) + " holds more bytes than the row stride (ld x 4 bytes)");
-    if (packets(samples[i], cfg->packet) > lost_ld) throw Error(CONAN_ERR_INVALID, "conan_conceal: lost_ld must cover ceil(samples / packet) flags of every row");
-  }
-  HIP_CHECK(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  const size_t table = (size_t)n * sizeof(cnk::ConcRow);
-  cnk::ConcRow* h = static_cast<cnk::ConcRow*>(ctx->loud_stage.take(table));
-  const cnk::ConcRow proto = row(*cfg);
-  int rows = 0;
-  for (int i = 0; i < n; ++i) {
-    if (samples[i] < 1) continue;
-    h[rows] = proto;
-    h[rows].samples = samples[i]; h[rows].row = i; h[rows].fmt = format;
-    ++rows;
-  }
-  if (rows < 1) return;
-  char* ws = reinterpret_cast<char*>(ctx->workspace((table + 3) / sizeof(float), st));
-  HIP_CHECK(hipMemcpyAsync(ws, h, (size_t)rows * sizeof(cnk::ConcRow), hipMemcpyHostToDevice, st));
-  ctx->loud_stage.sent(st);
-  cnk::ConcArgs a;
-  memset(&a, 0, sizeof(a));
-  a.wav = x_dev; a.wav_ld = ld; a.lost = lost_dev; a.lost_ld = lost_ld; a.state = nullptr;
-  a.tab = reinterpret_cast<const cnk::ConcRow*>(ws); a.rows = rows;
-  cnk::launch_conceal(a, st);
-  HIP_CHECK(hipGetLastError());
-}
-
-static void check_seed(const char* who, const void* p, int64_t ld) {
-  if (ld < cnk::kConcStateBytes || ((uintptr_t)p & 7) || (ld & 7))
-    throw Error(CONAN_ERR_INVALID, std::string(who) + ": rows are conan_conceal_state_bytes bytes, 8-byte aligned, ld apart");
+  prestep::whole<Stage>(ctx, cfg, format, {x_dev, ld, lost_dev, lost_ld}, n, samples, stream);
 }
 
 void set_conceal(conan_streams* s, const int32_t* slots, int n, const conan_conceal_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream) {
-  if (!s || !slots || !cfg) throw Error(CONAN_ERR_INVALID, "null argument");
-  check_cfg(*cfg, "conan_streams_set_conceal");      // (before the handle is touched, before any GPU use)
-  if (seed_dev) check_seed("conan_streams_set_conceal", seed_dev, seed_ld);
-  if (!wavio::begin_setter(s, slots, n, cfg->enabled != 0, s->conc.allocated(), "conan_streams_set_conceal", stream)) return;
-  hipStream_t st = (hipStream_t)stream;
+  if (!prestep::begin_set<Stage>(s, slots, n, cfg, seed_dev, seed_ld, stream)) return;
   s->conceal_init();
   // a slot that was off restarts from zeros in its next repair row - or from its seed row, now, which then clears the flag
   s->conc.store(slots, n, *cfg, [&](int i) { s->conc.pending[slots[i]] = 1; });
-  for (int i = 0; i < n && cfg->enabled && seed_dev; ++i) {
-    HIP_CHECK(hipMemcpyAsync(s->conc.state + (size_t)slots[i] * cnk::kConcStateBytes, static_cast<const char*>(seed_dev) + (size_t)i * seed_ld,
-                             (size_t)cnk::kConcStateBytes, hipMemcpyDeviceToDevice, st));
-    s->conc.pending[slots[i]] = 0;
-  }
+  if (cfg->enabled && seed_dev) s->conc.seed(slots, n, seed_dev, seed_ld, (hipStream_t)stream, [](int) { return true; });
 }
 
 void repair(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, void* wav_dev, int64_t wav_ld, const int32_t* lost_dev, int64_t lost_ld,
             void* stream) {
-  if (!s || !slots || !samples) throw Error(CONAN_ERR_INVALID, "null argument");
-  wavio::check_slot_list(s, slots, n);
-  if (wav_ld < 0 || wav_ld > kMaxStride || lost_ld < 0 || lost_ld > kMaxStride) throw Error(CONAN_ERR_INVALID, "conan_streams_conceal: wav_ld and lost_ld must be in 0 .. 2^40");
-  std::vector<cnk::ConcRow> rows;
-  for (int i = 0; i < n; ++i) {
-    if (samples[i] < 0) throw Error(CONAN_ERR_INVALID, "conan_streams_conceal: samples must be >= 0");
-    if (!s->conc.on(slots[i]) || samples[i] == 0) continue;      // the row keeps its bytes
-    const conan_conceal_cfg& c = s->conc.cfg[slots[i]];
-    const int fmt = s->wav_in.in_fmt[slots[i]];
-    const std::string where = "conan_streams_conceal: slot " + std::to_string(slots[i]) + ": ";
-    if ((long long)samples[i] * wavio::bytes_per_sample(fmt) > wav_ld * 4) throw Error(CONAN_ERR_INVALID, where + "the row holds more bytes than the row stride of wav_dev (wav_ld x 4 bytes)");
-    if (packets(samples[i], c.packet) > lost_ld) throw Error(CONAN_ERR_INVALID, where + "lost_ld must cover ceil(samples / packet) flags");
-    cnk::ConcRow r = row(c);
-    r.samples = samples[i]; r.row = i; r.slot = slots[i]; r.restart = s->conc.pending[slots[i]]; r.fmt = fmt;
-    rows.push_back(r);
-  }
-  if (rows.empty()) return;      // no row to repair: no launch
-  if (!wav_dev || !lost_dev) throw Error(CONAN_ERR_INVALID, "null argument (wav_dev / lost_dev with a row to repair)");
-  if ((uintptr_t)wav_dev & 3) throw Error(CONAN_ERR_INVALID, "conan_streams_conceal: wav_dev must be 4-byte aligned");
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  hipStream_t st = (hipStream_t)stream;
-  const int q = s->conc.sets.begin(rows.data(), (int)rows.size(), st);
-  cnk::ConcArgs a;
-  memset(&a, 0, sizeof(a));
-  a.wav = wav_dev; a.wav_ld = wav_ld; a.lost = lost_dev; a.lost_ld = lost_ld; a.state = s->conc.state;
-  a.tab = s->conc.sets.rows[q]; a.rows = (int)rows.size();
-  s->profiled("conceal_kernel", 0.0, st, [&] { cnk::launch_conceal(a, st); });
-  HIP_CHECK(hipGetLastError());
-  s->conc.sets.end(q, st);
-  for (const cnk::ConcRow& r : rows) s->conc.pending[r.slot] = 0;
+  prestep::call<Stage>(s, slots, n, samples, {wav_dev, wav_ld, lost_dev, lost_ld}, stream);
 }
 
-// a slot about to restart reports the zero state; any other its record, in the order of `stream`
 void state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream) {
-  if (!s || !slots || !state_dev) throw Error(CONAN_ERR_INVALID, "null argument");
-  check_seed("conan_streams_conceal_state", state_dev, ld);
-  wavio::check_slot_list(s, slots, n);
-  for (int i = 0; i < n; ++i)
-    if (!s->conc.on(slots[i])) throw Error(CONAN_ERR_STATE, "conan_streams_conceal_state: slot " + std::to_string(slots[i]) + " has no concealment (conan_streams_set_conceal)");
-  hipStream_t st = s->enter(stream);
-  for (int i = 0; i < n; ++i) {
-    char* dst = static_cast<char*>(state_dev) + (size_t)i * ld;
-    if (s->conc.pending[slots[i]]) HIP_CHECK(hipMemsetAsync(dst, 0, (size_t)cnk::kConcStateBytes, st));
-    else HIP_CHECK(hipMemcpyAsync(dst, s->conc.state + (size_t)slots[i] * cnk::kConcStateBytes, (size_t)cnk::kConcStateBytes, hipMemcpyDeviceToDevice, st));
-  }
+  record_state(s, &conan_streams::conc, "conceal", slots, n, state_dev, ld, stream, fresh_zeros);
 }
 
 }  // namespace conc
-
-void conan_streams::conceal_init() {
-  if (conc.state) return;
-  conc.state = reinterpret_cast<char*>(alloc((size_t)max_slots * cnk::kConcStateBytes / sizeof(float)));      // zeroed (counted by state_bytes)
-  conc.sets.init(max_slots, allocs);
-  state_bytes += (int64_t)kStageSets * max_slots * sizeof(cnk::ConcRow);
-  conc.assign(max_slots);
-}

@@ -136,7 +136,6 @@ namespace denoise {
 static_assert(sizeof(conan_denoise_cfg) == 64, "sixteen 32-bit fields");
 static_assert(sizeof(conan_denoise_state) == sizeof(cnk::DnState), "the kernels' state is the header's");
 constexpr int kMax = 1 << 20;
-constexpr int64_t kStateBytes = (int64_t)sizeof(cnk::DnState);
 
 void check_cfg(const conan_denoise_cfg& c, const char* who) {
   const std::string w = std::string(who) + ": ";
@@ -197,42 +196,22 @@ void whole(conan_ctx* ctx, const conan_denoise_cfg* cfg, const float* mel_dev, i
   HIP_CHECK(hipGetLastError());
 }
 
-static void check_rows(const char* who, const void* p, int64_t ld) {
-  if (ld < kStateBytes || ((uintptr_t)p & 7) || (ld & 7))
-    throw Error(CONAN_ERR_INVALID, std::string(who) + ": rows are conan_denoise_state_bytes bytes, 8-byte aligned, ld apart");
-}
-
 void set_denoise(conan_streams* s, const int32_t* slots, int n, const conan_denoise_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream) {
   if (!s || !slots || !cfg) throw Error(CONAN_ERR_INVALID, "null argument");
   check_cfg(*cfg, "conan_streams_set_denoise");      // (before the handle is touched, before any GPU use)
-  if (seed_dev) check_rows("conan_streams_set_denoise", seed_dev, seed_ld);
+  if (seed_dev) conan_streams::Denoise::check_rows("conan_streams_set_", "denoise", "", seed_dev, seed_ld);
   if (cfg->enabled && s->ctx->cfg.emf_input_dim > cnk::kDnMaxBins) throw Error(CONAN_ERR_UNSUPPORTED, "conan_streams_set_denoise: the front-end has more than 256 mel bins");
   if (!wavio::begin_setter(s, slots, n, cfg->enabled != 0, s->dn.allocated(), "conan_streams_set_denoise", stream)) return;
-  hipStream_t st = (hipStream_t)stream;
   s->denoise_init();
   std::vector<char> restarts((size_t)n);
   for (int i = 0; i < n; ++i) restarts[i] = cfg->enabled && (cfg->reseed != 0 || !s->dn.on(slots[i]));
   s->dn.store_restarting(slots, n, *cfg);      // the restart travels in the slot's next row ...
-  for (int i = 0; i < n && seed_dev; ++i) {      // ... or the seed row becomes the state, now
-    if (!restarts[i]) continue;      // the call keeps this slot's state: its seed row is not read
-    HIP_CHECK(hipMemcpyAsync(s->dn.state + slots[i], static_cast<const char*>(seed_dev) + (size_t)i * seed_ld, (size_t)kStateBytes, hipMemcpyDeviceToDevice, st));
-    s->dn.pending[slots[i]] = 0;
-  }
+  // ... or the seed row becomes the state, now (a slot whose state the call keeps: its seed row is not read)
+  if (seed_dev) s->dn.seed(slots, n, seed_dev, seed_ld, (hipStream_t)stream, [&](int i) { return restarts[i] != 0; });
 }
 
-// a slot about to restart reports the zero record; any other its record, in the order of `stream`
 void state(conan_streams* s, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream) {
-  if (!s || !slots || !rows_dev) throw Error(CONAN_ERR_INVALID, "null argument");
-  check_rows("conan_streams_denoise_state", rows_dev, ld);
-  wavio::check_slot_list(s, slots, n);
-  for (int i = 0; i < n; ++i)
-    if (!s->dn.on(slots[i])) throw Error(CONAN_ERR_STATE, "conan_streams_denoise_state: slot " + std::to_string(slots[i]) + " has no noise suppression (conan_streams_set_denoise)");
-  hipStream_t st = s->enter(stream);
-  for (int i = 0; i < n; ++i) {
-    char* dst = static_cast<char*>(rows_dev) + (size_t)i * ld;
-    if (s->dn.pending[slots[i]]) HIP_CHECK(hipMemsetAsync(dst, 0, (size_t)kStateBytes, st));
-    else HIP_CHECK(hipMemcpyAsync(dst, s->dn.state + slots[i], (size_t)kStateBytes, hipMemcpyDeviceToDevice, st));
-  }
+  record_state(s, &conan_streams::dn, "denoise", slots, n, rows_dev, ld, stream, fresh_zeros);
 }
 
 // One table row per call row whose slot suppresses and either completes a frame or emits: its new frames in the ring, then its chunk
@@ -271,11 +250,3 @@ void WavStage::commit(conan_streams* s, hipStream_t, hipStream_t) {
 }
 
 }  // namespace denoise
-
-void conan_streams::denoise_init() {
-  if (dn.state) return;
-  dn.state = reinterpret_cast<cnk::DnState*>(alloc((size_t)max_slots * sizeof(cnk::DnState) / sizeof(float)));      // zeroed (counted by state_bytes)
-  dn.sets.init(max_slots, allocs);
-  state_bytes += (int64_t)kStageSets * max_slots * sizeof(cnk::DnRow);
-  dn.assign(max_slots);
-}

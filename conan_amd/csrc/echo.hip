@@ -4,7 +4,7 @@
 #include <climits>
 #include <cstddef>
 
-#include "streams.h"
+#include "prestep.h"
 #include "sample_dev.h"
 
 namespace cnk {
@@ -224,7 +224,6 @@ namespace echo {
 static_assert(sizeof(conan_echo_cfg) == 48, "eight int32 and two int64 fields");
 static_assert(CONAN_ECHO_BLOCK == cnk::kEchoBlock && CONAN_ECHO_MAX_TAPS == cnk::kEchoMaxTaps && CONAN_ECHO_MAX_DELAY == cnk::kEchoMaxDelay &&
               CONAN_ECHO_MAX_SHIFT == cnk::kEchoMaxShift && CONAN_ECHO_HISTORY == cnk::kEchoHist, "the kernel's limits are the header's");
-constexpr int64_t kMaxSamples = 1ll << 40, kMaxStride = 1ll << 40;
 
 void check_cfg(const conan_echo_cfg& c, const char* who) {
   const std::string w = std::string(who) + ": ";
@@ -248,143 +247,51 @@ cnk::EchoRow row(const conan_echo_cfg& c) {
   return r;
 }
 
+// The feature's part of the pre-step row call (prestep.h): the second buffer holds the far rows; the report is the call's stats
+struct Stage {
+  using Cfg = conan_echo_cfg; using Row = cnk::EchoRow; using Args = cnk::EchoArgs;
+  struct Call { void* wav; int64_t wav_ld; const void* aux; int64_t aux_ld; int64_t* report; };
+  static constexpr const char *kName = "echo", *kWhole = "conan_echo", *kSet = "conan_streams_set_echo", *kCall = "conan_streams_echo";
+  static constexpr const char *kAux = "far", *kReportArg = "stats_dev", *kKernel = "echo_kernel";
+  static constexpr bool kAuxAudio = true;
+  static constexpr int kReport = 4, kBlock = cnk::kEchoBlock;
+  static constexpr auto set = &conan_streams::ec;
+  static constexpr auto check_cfg = &echo::check_cfg;
+  static constexpr auto row = &echo::row;
+  static constexpr auto launch = &cnk::launch_echo;
+  static const char* check_call(const Call&) { return nullptr; }
+  static const char* check_row(const Cfg&, int64_t, const Call&) { return nullptr; }
+  static void fill(Args& a, const Call& b) {
+    a.wav = b.wav; a.wav_ld = b.wav_ld; a.far = b.aux; a.far_ld = b.aux_ld; a.stats = reinterpret_cast<long long*>(b.report);
+  }
+};
+
 void whole(conan_ctx* ctx, const conan_echo_cfg* cfg, int format, void* x_dev, int64_t ld, const void* far_dev, int64_t far_ld, int n, const int64_t* samples,
            int64_t* stats_dev, void* stream) {
-  if (!ctx || !cfg || !x_dev || !far_dev || !samples) throw Error(CONAN_ERR_INVALID, "null argument");
-  check_cfg(*cfg, "conan_echo");
-  if (!cfg->enabled) throw Error(CONAN_ERR_INVALID, "conan_echo: cfg.enabled must be 1");
-  wavio::check_format(format, "conan_echo");
-  if (n < 1 || n > 65535) throw Error(CONAN_ERR_INVALID, "conan_echo: n must be in 1 .. 65535");
-  if (ld < 0 || ld > kMaxStride || far_ld < 0 || far_ld > kMaxStride) throw Error(CONAN_ERR_INVALID, "conan_echo: ld and far_ld must be in 0 .. 2^40");
-  if (((uintptr_t)x_dev & 3) || ((uintptr_t)far_dev & 3)) throw Error(CONAN_ERR_INVALID, "conan_echo: x_dev and far_dev must be 4-byte aligned");
-  if ((uintptr_t)stats_dev & 7) throw Error(CONAN_ERR_INVALID, "conan_echo: stats_dev must be 8-byte aligned");
-  const int bps = wavio::bytes_per_sample(format);
-  for (int i = 0; i < n; ++i) {
-    if (samples[i] < 0 || samples[i] > kMaxSamples) throw Error(CONAN_ERR_INVALID, "conan_echo: row " + std::to_string(i) + ": samples must be in 0 .. 2^40");
-    if (samples[i] * bps > ld * 4 || samples[i] * bps > far_ld * 4)
-      throw Error(CONAN_ERR_INVALID, "conan_echo: row " + std::to_string(i) + " holds more bytes than a row stride (ld, far_ld x 4 bytes)");
-  }
-  HIP_CHECK(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  const size_t table = (size_t)n * sizeof(cnk::EchoRow);
-  cnk::EchoRow* h = static_cast<cnk::EchoRow*>(ctx->loud_stage.take(table));
-  const cnk::EchoRow proto = row(*cfg);
-  int rows = 0;
-  for (int i = 0; i < n; ++i) {
-    if (samples[i] < 1) continue;
-    h[rows] = proto;
-    h[rows].samples = samples[i]; h[rows].row = i; h[rows].fmt = format;
-    ++rows;
-  }
-  if (stats_dev && rows < n) HIP_CHECK(hipMemsetAsync(stats_dev, 0, (size_t)n * 4 * sizeof(int64_t), st));
-  if (rows < 1) return;
-  char* ws = reinterpret_cast<char*>(ctx->workspace((table + 3) / sizeof(float), st));
-  HIP_CHECK(hipMemcpyAsync(ws, h, (size_t)rows * sizeof(cnk::EchoRow), hipMemcpyHostToDevice, st));
-  ctx->loud_stage.sent(st);
-  cnk::EchoArgs a;
-  memset(&a, 0, sizeof(a));
-  a.wav = x_dev; a.wav_ld = ld; a.far = far_dev; a.far_ld = far_ld; a.state = nullptr; a.stats = reinterpret_cast<long long*>(stats_dev);
-  a.tab = reinterpret_cast<const cnk::EchoRow*>(ws); a.rows = rows;
-  cnk::launch_echo(a, st);
-  HIP_CHECK(hipGetLastError());
-}
-
-static void check_seed(const char* who, const void* p, int64_t ld) {
-  if (ld < cnk::kEchoStateBytes || ((uintptr_t)p & 7) || (ld & 7))
-    throw Error(CONAN_ERR_INVALID, std::string(who) + ": rows are conan_echo_state_bytes bytes, 8-byte aligned, ld apart");
+  prestep::whole<Stage>(ctx, cfg, format, {x_dev, ld, far_dev, far_ld, stats_dev}, n, samples, stream);
 }
 
 void set_echo(conan_streams* s, const int32_t* slots, int n, const conan_echo_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream) {
-  if (!s || !slots || !cfg) throw Error(CONAN_ERR_INVALID, "null argument");
-  check_cfg(*cfg, "conan_streams_set_echo");      // (before the handle is touched, before any GPU use)
-  if (seed_dev) check_seed("conan_streams_set_echo", seed_dev, seed_ld);
-  if (!wavio::begin_setter(s, slots, n, cfg->enabled != 0, s->ec.allocated(), "conan_streams_set_echo", stream)) return;
+  if (!prestep::begin_set<Stage>(s, slots, n, cfg, seed_dev, seed_ld, stream)) return;
   hipStream_t st = (hipStream_t)stream;
   s->echo_init();
   // a slot that was off restarts in its next row - or from its seed row, now, which then clears the flag
   s->ec.store(slots, n, *cfg, [&](int i) { s->ec.pending[slots[i]] = 1; });
   if (!cfg->enabled || !seed_dev) return;
-  // the host, not the record, tells the kernel where in a block a slot stands: the seeds' positions are read back
-  std::vector<long long> pos((size_t)n);
-  for (int i = 0; i < n; ++i) {
-    const char* src = static_cast<const char*>(seed_dev) + (size_t)i * seed_ld;
-    HIP_CHECK(hipMemcpyAsync(s->ec.state + (size_t)slots[i] * cnk::kEchoStateBytes, src, (size_t)cnk::kEchoStateBytes, hipMemcpyDeviceToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(&pos[i], src, sizeof(long long), hipMemcpyDeviceToHost, st));
-  }
-  HIP_CHECK(hipStreamSynchronize(st));
-  for (int i = 0; i < n; ++i) {
-    s->ec.pos[slots[i]] = pos[i] < 0 ? 0 : pos[i];      // (a record the kernel cannot have written: any position serves)
-    s->ec.pending[slots[i]] = 0;
-  }
+  s->ec.seed(slots, n, seed_dev, seed_ld, st, [](int) { return true; });
+  prestep::read_seed_pos<Stage>(s, slots, n, seed_dev, seed_ld, st);
 }
 
 void cancel(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, void* wav_dev, int64_t wav_ld, const void* far_dev, int64_t far_ld,
             int64_t* stats_dev, void* stream) {
-  if (!s || !slots || !samples) throw Error(CONAN_ERR_INVALID, "null argument");
-  wavio::check_slot_list(s, slots, n);
-  if (wav_ld < 0 || wav_ld > kMaxStride || far_ld < 0 || far_ld > kMaxStride) throw Error(CONAN_ERR_INVALID, "conan_streams_echo: wav_ld and far_ld must be in 0 .. 2^40");
-  if ((uintptr_t)stats_dev & 7) throw Error(CONAN_ERR_INVALID, "conan_streams_echo: stats_dev must be 8-byte aligned");
-  std::vector<cnk::EchoRow> rows;
-  for (int i = 0; i < n; ++i) {
-    if (samples[i] < 0) throw Error(CONAN_ERR_INVALID, "conan_streams_echo: samples must be >= 0");
-    if (!s->ec.on(slots[i]) || samples[i] == 0) continue;      // the row keeps its bytes
-    const int fmt = s->wav_in.in_fmt[slots[i]];
-    const long long bytes = (long long)samples[i] * wavio::bytes_per_sample(fmt);
-    if (bytes > wav_ld * 4 || bytes > far_ld * 4)
-      throw Error(CONAN_ERR_INVALID, "conan_streams_echo: slot " + std::to_string(slots[i]) + ": the row holds more bytes than a row stride (wav_ld, far_ld x 4 bytes)");
-    cnk::EchoRow r = row(s->ec.cfg[slots[i]]);
-    r.restart = s->ec.pending[slots[i]];
-    r.pos = r.restart ? 0 : s->ec.pos[slots[i]];
-    r.phase = (int)(r.pos % cnk::kEchoBlock);
-    r.samples = samples[i]; r.row = i; r.slot = slots[i]; r.fmt = fmt;
-    rows.push_back(r);
-  }
-  hipStream_t st = (hipStream_t)stream;
-  if (stats_dev && (int)rows.size() < n && n > 0) {
-    HIP_CHECK(hipSetDevice(s->ctx->device));
-    HIP_CHECK(hipMemsetAsync(stats_dev, 0, (size_t)n * 4 * sizeof(int64_t), st));
-  }
-  if (rows.empty()) return;      // no row to cancel: no launch
-  if (!wav_dev || !far_dev) throw Error(CONAN_ERR_INVALID, "null argument (wav_dev / far_dev with a row to cancel)");
-  if (((uintptr_t)wav_dev & 3) || ((uintptr_t)far_dev & 3)) throw Error(CONAN_ERR_INVALID, "conan_streams_echo: wav_dev and far_dev must be 4-byte aligned");
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  const int q = s->ec.sets.begin(rows.data(), (int)rows.size(), st);
-  cnk::EchoArgs a;
-  memset(&a, 0, sizeof(a));
-  a.wav = wav_dev; a.wav_ld = wav_ld; a.far = far_dev; a.far_ld = far_ld; a.state = s->ec.state; a.stats = reinterpret_cast<long long*>(stats_dev);
-  a.tab = s->ec.sets.rows[q]; a.rows = (int)rows.size();
-  s->profiled("echo_kernel", 0.0, st, [&] { cnk::launch_echo(a, st); });
-  HIP_CHECK(hipGetLastError());
-  s->ec.sets.end(q, st);
-  for (const cnk::EchoRow& r : rows) { s->ec.pending[r.slot] = 0; s->ec.pos[r.slot] = r.pos + r.samples; }
+  prestep::call<Stage>(s, slots, n, samples, {wav_dev, wav_ld, far_dev, far_ld, stats_dev}, stream);
 }
 
-// a slot about to restart reports the restart state; any other its record, in the order of `stream`
+// the restart state: zeros, and the slot's step size
 void state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream) {
-  if (!s || !slots || !state_dev) throw Error(CONAN_ERR_INVALID, "null argument");
-  check_seed("conan_streams_echo_state", state_dev, ld);
-  wavio::check_slot_list(s, slots, n);
-  for (int i = 0; i < n; ++i)
-    if (!s->ec.on(slots[i])) throw Error(CONAN_ERR_STATE, "conan_streams_echo_state: slot " + std::to_string(slots[i]) + " has no echo canceller (conan_streams_set_echo)");
-  hipStream_t st = s->enter(stream);
-  for (int i = 0; i < n; ++i) {
-    char* dst = static_cast<char*>(state_dev) + (size_t)i * ld;
-    if (s->ec.pending[slots[i]]) {
-      HIP_CHECK(hipMemsetAsync(dst, 0, (size_t)cnk::kEchoStateBytes, st));
-      HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dst + offsetof(cnk::EchoHead, shift)), s->ec.cfg[slots[i]].mu_shift, 1, st));
-    } else {
-      HIP_CHECK(hipMemcpyAsync(dst, s->ec.state + (size_t)slots[i] * cnk::kEchoStateBytes, (size_t)cnk::kEchoStateBytes, hipMemcpyDeviceToDevice, st));
-    }
-  }
+  record_state(s, &conan_streams::ec, "echo", slots, n, state_dev, ld, stream, [&](int slot, char* dst, hipStream_t st) {
+    HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dst + offsetof(cnk::EchoHead, shift)), s->ec.cfg[slot].mu_shift, 1, st));
+  });
 }
 
 }  // namespace echo
-
-void conan_streams::echo_init() {
-  if (ec.state) return;
-  ec.state = reinterpret_cast<char*>(alloc((size_t)max_slots * cnk::kEchoStateBytes / sizeof(float)));      // zeroed (counted by state_bytes)
-  ec.sets.init(max_slots, allocs);
-  state_bytes += (int64_t)kStageSets * max_slots * sizeof(cnk::EchoRow);
-  ec.assign(max_slots);
-  ec.pos.assign(max_slots, 0);
-}

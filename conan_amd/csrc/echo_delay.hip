@@ -4,7 +4,7 @@
 #include <climits>
 #include <cstddef>
 
-#include "streams.h"
+#include "prestep.h"
 #include "sample_dev.h"
 
 namespace cnk {
@@ -224,7 +224,6 @@ namespace echo_delay {
 
 static_assert(sizeof(conan_echo_delay_cfg) == 48, "twelve int32 fields");
 static_assert(CONAN_ECHO_DELAY_FRAME == cnk::kEdFrame && CONAN_ECHO_DELAY_MAX_LAGS == cnk::kEdMaxLags, "the kernel's limits are the header's");
-constexpr int64_t kMaxSamples = 1ll << 40, kMaxStride = 1ll << 40;
 
 void check_cfg(const conan_echo_delay_cfg& c, const char* who) {
   const std::string w = std::string(who) + ": ";
@@ -248,159 +247,68 @@ cnk::EdRow row(const conan_echo_delay_cfg& c) {
   return r;
 }
 
+// The feature's part of the pre-step row call (prestep.h): the second buffer holds the far rows; the whole-signal call also has a
+// track of 6 int64 per frame end and row
+struct Stage {
+  using Cfg = conan_echo_delay_cfg; using Row = cnk::EdRow; using Args = cnk::EdArgs;
+  struct Call { const void* wav; int64_t wav_ld; const void* aux; int64_t aux_ld; int64_t* report; int64_t* track; int64_t track_ld; };
+  static constexpr const char *kName = "echo_delay", *kWhole = "conan_echo_delay", *kSet = "conan_streams_set_echo_delay", *kCall = "conan_streams_echo_delay";
+  static constexpr const char *kAux = "far", *kReportArg = "report_dev", *kKernel = "echo_delay_kernel";
+  static constexpr bool kAuxAudio = true;
+  static constexpr int kReport = 6, kBlock = cnk::kEdFrame;
+  static constexpr auto set = &conan_streams::ed;
+  static constexpr auto check_cfg = &echo_delay::check_cfg;
+  static constexpr auto row = &echo_delay::row;
+  static constexpr auto launch = &cnk::launch_echo_delay;
+  static const char* check_call(const Call& b) {
+    if (!prestep::stride_ok(b.track_ld)) return "track_ld must be in 0 .. 2^40";
+    return ((uintptr_t)b.track & 7) ? "track_dev must be 8-byte aligned" : nullptr;
+  }
+  static const char* check_row(const Cfg&, int64_t samples, const Call& b) {
+    return b.track && samples / CONAN_ECHO_DELAY_FRAME * 6 > b.track_ld ? "the row ends more frames than track_ld holds (6 int64 per frame)" : nullptr;
+  }
+  static void fill(Args& a, const Call& b) {
+    a.wav = b.wav; a.wav_ld = b.wav_ld; a.far = b.aux; a.far_ld = b.aux_ld; a.report = reinterpret_cast<long long*>(b.report);
+    a.track = reinterpret_cast<long long*>(b.track); a.track_ld = b.track_ld;
+  }
+};
+
 void whole(conan_ctx* ctx, const conan_echo_delay_cfg* cfg, int format, const void* mic_dev, int64_t ld, const void* far_dev, int64_t far_ld, int n,
            const int64_t* samples, int64_t* track_dev, int64_t track_ld, int64_t* report_dev, void* stream) {
-  if (!ctx || !cfg || !mic_dev || !far_dev || !samples) throw Error(CONAN_ERR_INVALID, "null argument");
-  check_cfg(*cfg, "conan_echo_delay");
-  if (!cfg->enabled) throw Error(CONAN_ERR_INVALID, "conan_echo_delay: cfg.enabled must be 1");
-  wavio::check_format(format, "conan_echo_delay");
-  if (n < 1 || n > 65535) throw Error(CONAN_ERR_INVALID, "conan_echo_delay: n must be in 1 .. 65535");
-  if (ld < 0 || ld > kMaxStride || far_ld < 0 || far_ld > kMaxStride || track_ld < 0 || track_ld > kMaxStride)
-    throw Error(CONAN_ERR_INVALID, "conan_echo_delay: ld, far_ld and track_ld must be in 0 .. 2^40");
-  if (((uintptr_t)mic_dev & 3) || ((uintptr_t)far_dev & 3)) throw Error(CONAN_ERR_INVALID, "conan_echo_delay: mic_dev and far_dev must be 4-byte aligned");
-  if (((uintptr_t)track_dev & 7) || ((uintptr_t)report_dev & 7)) throw Error(CONAN_ERR_INVALID, "conan_echo_delay: track_dev and report_dev must be 8-byte aligned");
-  const int bps = wavio::bytes_per_sample(format);
-  for (int i = 0; i < n; ++i) {
-    if (samples[i] < 0 || samples[i] > kMaxSamples) throw Error(CONAN_ERR_INVALID, "conan_echo_delay: row " + std::to_string(i) + ": samples must be in 0 .. 2^40");
-    if (samples[i] * bps > ld * 4 || samples[i] * bps > far_ld * 4)
-      throw Error(CONAN_ERR_INVALID, "conan_echo_delay: row " + std::to_string(i) + " holds more bytes than a row stride (ld, far_ld x 4 bytes)");
-    if (track_dev && samples[i] / CONAN_ECHO_DELAY_FRAME * 6 > track_ld)
-      throw Error(CONAN_ERR_INVALID, "conan_echo_delay: row " + std::to_string(i) + " ends more frames than track_ld holds (6 int64 per frame)");
-  }
-  HIP_CHECK(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  const size_t table = (size_t)n * sizeof(cnk::EdRow);
-  cnk::EdRow* h = static_cast<cnk::EdRow*>(ctx->loud_stage.take(table));
-  const cnk::EdRow proto = row(*cfg);
-  int rows = 0;
-  for (int i = 0; i < n; ++i) {
-    if (samples[i] < 1) continue;
-    h[rows] = proto;
-    h[rows].samples = samples[i]; h[rows].row = i; h[rows].fmt = format;
-    ++rows;
-  }
-  if (report_dev && rows < n) HIP_CHECK(hipMemsetAsync(report_dev, 0, (size_t)n * 6 * sizeof(int64_t), st));
-  if (rows < 1) return;
-  char* ws = reinterpret_cast<char*>(ctx->workspace((table + 3) / sizeof(float), st));
-  HIP_CHECK(hipMemcpyAsync(ws, h, (size_t)rows * sizeof(cnk::EdRow), hipMemcpyHostToDevice, st));
-  ctx->loud_stage.sent(st);
-  cnk::EdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.wav = mic_dev; a.wav_ld = ld; a.far = far_dev; a.far_ld = far_ld; a.state = nullptr; a.report = reinterpret_cast<long long*>(report_dev);
-  a.track = reinterpret_cast<long long*>(track_dev); a.track_ld = track_ld;
-  a.tab = reinterpret_cast<const cnk::EdRow*>(ws); a.rows = rows;
-  cnk::launch_echo_delay(a, st);
-  HIP_CHECK(hipGetLastError());
+  prestep::whole<Stage>(ctx, cfg, format, {mic_dev, ld, far_dev, far_ld, report_dev, track_dev, track_ld}, n, samples, stream);
 }
 
-static void check_seed(const char* who, const void* p, int64_t ld) {
-  if (ld < cnk::kEdStateBytes || ((uintptr_t)p & 7) || (ld & 7))
-    throw Error(CONAN_ERR_INVALID, std::string(who) + ": rows are conan_echo_delay_state_bytes bytes, 8-byte aligned, ld apart");
+// zeros in A[from, to) of a slot's record: the kernel keeps a lag from n_lags on at 0 and relies on finding it so
+static void zero_lags(conan_streams* s, int slot, int from, int to, hipStream_t st) {
+  if (from < to) HIP_CHECK(hipMemsetAsync(s->ed.record(slot) + sizeof(cnk::EdHead) + (size_t)from * 4, 0, (size_t)(to - from) * 4, st));
 }
 
 void set_echo_delay(conan_streams* s, const int32_t* slots, int n, const conan_echo_delay_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream) {
-  if (!s || !slots || !cfg) throw Error(CONAN_ERR_INVALID, "null argument");
-  check_cfg(*cfg, "conan_streams_set_echo_delay");      // (before the handle is touched, before any GPU use)
-  if (seed_dev) check_seed("conan_streams_set_echo_delay", seed_dev, seed_ld);
-  if (!wavio::begin_setter(s, slots, n, cfg->enabled != 0, s->ed.allocated(), "conan_streams_set_echo_delay", stream)) return;
+  if (!prestep::begin_set<Stage>(s, slots, n, cfg, seed_dev, seed_ld, stream)) return;
   hipStream_t st = (hipStream_t)stream;
   s->echo_delay_init();
-  // a live slot whose n_lags shrinks: the record holds zeros in A[n_lags ..] from now on (a seed or a restart replaces it anyway)
-  for (int i = 0; i < n && cfg->enabled && !seed_dev; ++i) {
-    const int was = s->ed.cfg[slots[i]].n_lags;
-    if (!s->ed.on(slots[i]) || s->ed.pending[slots[i]] || cfg->n_lags >= was) continue;
-    char* A = s->ed.state + (size_t)slots[i] * cnk::kEdStateBytes + sizeof(cnk::EdHead);
-    HIP_CHECK(hipMemsetAsync(A + (size_t)cfg->n_lags * 4, 0, (size_t)(was - cfg->n_lags) * 4, st));
-  }
+  // a live slot whose n_lags shrinks (a seed or a restart replaces its record anyway)
+  for (int i = 0; i < n && cfg->enabled && !seed_dev; ++i)
+    if (s->ed.on(slots[i]) && !s->ed.pending[slots[i]]) zero_lags(s, slots[i], cfg->n_lags, s->ed.cfg[slots[i]].n_lags, st);
   // a slot that was off restarts in its next row - or from its seed row, now, which then clears the flag
   s->ed.store(slots, n, *cfg, [&](int i) { s->ed.pending[slots[i]] = 1; });
   if (!cfg->enabled || !seed_dev) return;
-  // the host, not the record, tells the kernel where in a frame a slot stands: the seeds' positions are read back
-  std::vector<long long> pos((size_t)n);
-  for (int i = 0; i < n; ++i) {
-    const char* src = static_cast<const char*>(seed_dev) + (size_t)i * seed_ld;
-    char* rec = s->ed.state + (size_t)slots[i] * cnk::kEdStateBytes;
-    HIP_CHECK(hipMemcpyAsync(rec, src, (size_t)cnk::kEdStateBytes, hipMemcpyDeviceToDevice, st));
-    if (cfg->n_lags < cnk::kEdMaxLags)      // (a seed from a slot with more lags: zeros in A[n_lags ..] here too)
-      HIP_CHECK(hipMemsetAsync(rec + sizeof(cnk::EdHead) + (size_t)cfg->n_lags * 4, 0, (size_t)(cnk::kEdMaxLags - cfg->n_lags) * 4, st));
-    HIP_CHECK(hipMemcpyAsync(&pos[i], src, sizeof(long long), hipMemcpyDeviceToHost, st));
-  }
-  HIP_CHECK(hipStreamSynchronize(st));
-  for (int i = 0; i < n; ++i) {
-    s->ed.pos[slots[i]] = pos[i] < 0 ? 0 : pos[i];      // (a record the kernel cannot have written: any position serves)
-    s->ed.pending[slots[i]] = 0;
-  }
+  s->ed.seed(slots, n, seed_dev, seed_ld, st, [](int) { return true; });
+  for (int i = 0; i < n; ++i) zero_lags(s, slots[i], cfg->n_lags, cnk::kEdMaxLags, st);      // (a seed from a slot with more lags)
+  prestep::read_seed_pos<Stage>(s, slots, n, seed_dev, seed_ld, st);
 }
 
 void estimate(conan_streams* s, const int32_t* slots, int n, const int32_t* samples, const void* wav_dev, int64_t wav_ld, const void* far_dev, int64_t far_ld,
               int64_t* report_dev, void* stream) {
-  if (!s || !slots || !samples) throw Error(CONAN_ERR_INVALID, "null argument");
-  wavio::check_slot_list(s, slots, n);
-  if (wav_ld < 0 || wav_ld > kMaxStride || far_ld < 0 || far_ld > kMaxStride) throw Error(CONAN_ERR_INVALID, "conan_streams_echo_delay: wav_ld and far_ld must be in 0 .. 2^40");
-  if ((uintptr_t)report_dev & 7) throw Error(CONAN_ERR_INVALID, "conan_streams_echo_delay: report_dev must be 8-byte aligned");
-  std::vector<cnk::EdRow> rows;
-  for (int i = 0; i < n; ++i) {
-    if (samples[i] < 0) throw Error(CONAN_ERR_INVALID, "conan_streams_echo_delay: samples must be >= 0");
-    if (!s->ed.on(slots[i]) || samples[i] == 0) continue;
-    const int fmt = s->wav_in.in_fmt[slots[i]];
-    const long long bytes = (long long)samples[i] * wavio::bytes_per_sample(fmt);
-    if (bytes > wav_ld * 4 || bytes > far_ld * 4)
-      throw Error(CONAN_ERR_INVALID, "conan_streams_echo_delay: slot " + std::to_string(slots[i]) + ": the row holds more bytes than a row stride (wav_ld, far_ld x 4 bytes)");
-    cnk::EdRow r = row(s->ed.cfg[slots[i]]);
-    r.restart = s->ed.pending[slots[i]];
-    r.pos = r.restart ? 0 : s->ed.pos[slots[i]];
-    r.phase = (int)(r.pos % cnk::kEdFrame);
-    r.samples = samples[i]; r.row = i; r.slot = slots[i]; r.fmt = fmt;
-    rows.push_back(r);
-  }
-  hipStream_t st = (hipStream_t)stream;
-  if (report_dev && (int)rows.size() < n && n > 0) {
-    HIP_CHECK(hipSetDevice(s->ctx->device));
-    HIP_CHECK(hipMemsetAsync(report_dev, 0, (size_t)n * 6 * sizeof(int64_t), st));
-  }
-  if (rows.empty()) return;      // no row to do: no launch
-  if (!wav_dev || !far_dev) throw Error(CONAN_ERR_INVALID, "null argument (wav_dev / far_dev with a row to do)");
-  if (((uintptr_t)wav_dev & 3) || ((uintptr_t)far_dev & 3)) throw Error(CONAN_ERR_INVALID, "conan_streams_echo_delay: wav_dev and far_dev must be 4-byte aligned");
-  HIP_CHECK(hipSetDevice(s->ctx->device)); s->check_fault();
-  const int q = s->ed.sets.begin(rows.data(), (int)rows.size(), st);
-  cnk::EdArgs a;
-  memset(&a, 0, sizeof(a));
-  a.wav = wav_dev; a.wav_ld = wav_ld; a.far = far_dev; a.far_ld = far_ld; a.state = s->ed.state; a.report = reinterpret_cast<long long*>(report_dev);
-  a.tab = s->ed.sets.rows[q]; a.rows = (int)rows.size();
-  s->profiled("echo_delay_kernel", 0.0, st, [&] { cnk::launch_echo_delay(a, st); });
-  HIP_CHECK(hipGetLastError());
-  s->ed.sets.end(q, st);
-  for (const cnk::EdRow& r : rows) { s->ed.pending[r.slot] = 0; s->ed.pos[r.slot] = r.pos + r.samples; }
+  prestep::call<Stage>(s, slots, n, samples, {wav_dev, wav_ld, far_dev, far_ld, report_dev, nullptr, 0}, stream);
 }
 
-// a slot about to restart reports the restart state; any other its record, in the order of `stream`
+// the restart state: zeros, and no estimate and no candidate
 void state(conan_streams* s, const int32_t* slots, int n, void* state_dev, int64_t ld, void* stream) {
-  if (!s || !slots || !state_dev) throw Error(CONAN_ERR_INVALID, "null argument");
-  check_seed("conan_streams_echo_delay_state", state_dev, ld);
-  wavio::check_slot_list(s, slots, n);
-  for (int i = 0; i < n; ++i)
-    if (!s->ed.on(slots[i]))
-      throw Error(CONAN_ERR_STATE, "conan_streams_echo_delay_state: slot " + std::to_string(slots[i]) + " has no delay estimator (conan_streams_set_echo_delay)");
-  hipStream_t st = s->enter(stream);
-  for (int i = 0; i < n; ++i) {
-    char* dst = static_cast<char*>(state_dev) + (size_t)i * ld;
-    if (s->ed.pending[slots[i]]) {
-      HIP_CHECK(hipMemsetAsync(dst, 0, (size_t)cnk::kEdStateBytes, st));
-      HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dst + offsetof(cnk::EdHead, est)), -1, 1, st));
-      HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dst + offsetof(cnk::EdHead, cand)), -1, 1, st));
-    } else {
-      HIP_CHECK(hipMemcpyAsync(dst, s->ed.state + (size_t)slots[i] * cnk::kEdStateBytes, (size_t)cnk::kEdStateBytes, hipMemcpyDeviceToDevice, st));
-    }
-  }
+  record_state(s, &conan_streams::ed, "echo_delay", slots, n, state_dev, ld, stream, [](int, char* dst, hipStream_t st) {
+    HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dst + offsetof(cnk::EdHead, est)), -1, 1, st));
+    HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dst + offsetof(cnk::EdHead, cand)), -1, 1, st));
+  });
 }
 
 }  // namespace echo_delay
-
-void conan_streams::echo_delay_init() {
-  if (ed.state) return;
-  ed.state = reinterpret_cast<char*>(alloc((size_t)max_slots * cnk::kEdStateBytes / sizeof(float)));      // zeroed (counted by state_bytes)
-  ed.sets.init(max_slots, allocs);
-  state_bytes += (int64_t)kStageSets * max_slots * sizeof(cnk::EdRow);
-  ed.assign(max_slots);
-  ed.pos.assign(max_slots, 0);
-}

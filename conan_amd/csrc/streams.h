@@ -156,6 +156,34 @@ struct SlotSetting {
     else memset(out, 0, sizeof(*out));
   }
 };
+// A SlotSetting whose per-slot state is an opaque device record of kBytes that the setter takes back as seed rows and a state query
+// hands out (conceal.hip, echo.hip, echo_delay.hip, denoise.hip, watermark.hip; `name`: the feature's in conan_streams_set_<name>,
+// conan_streams_<name>_state and conan_<name>_state_bytes).  With it go the row tables of the feature's launches; conan_streams::
+// records_init() allocates both and record_state() (below) is the state query.
+template <typename Cfg, typename RowT, typename Rec, int kSetsN = kStageSets, size_t kBytes = sizeof(Rec)>
+struct RecordSetting : SlotSetting<Cfg> {
+  using Row = RowT;
+  static constexpr size_t kRecBytes = kBytes;
+  static constexpr int kSets = kSetsN;
+  Rec* state = nullptr;      // [max_slots] records; stream state
+  StageSets<Row, kSets> sets;
+  char* record(int slot) const { return reinterpret_cast<char*>(state) + (size_t)slot * kBytes; }
+  // seed rows and state rows: at least a record apart, pointer and stride 8-byte aligned
+  // (the entry point's name in three parts - "conan_streams_set_", name, "" - so that a call that passes builds no string)
+  static void check_rows(const char* who_head, const char* name, const char* who_tail, const void* p, int64_t ld) {
+    if (ld < (int64_t)kBytes || ((uintptr_t)p & 7) || (ld & 7))
+      throw Error(CONAN_ERR_INVALID, std::string(who_head) + name + who_tail + ": rows are conan_" + name + "_state_bytes bytes, 8-byte aligned, ld apart");
+  }
+  // seed row i becomes the record of slots[i], now, and the slot restarts no more - for the list entries that take(i) names
+  template <typename Take>
+  void seed(const int32_t* slots, int n, const void* seed_dev, int64_t seed_ld, hipStream_t st, Take&& take) {
+    for (int i = 0; i < n; ++i) {
+      if (!take(i)) continue;
+      HIP_CHECK(hipMemcpyAsync(record(slots[i]), static_cast<const char*>(seed_dev) + (size_t)i * seed_ld, kBytes, hipMemcpyDeviceToDevice, st));
+      this->pending[slots[i]] = 0;
+    }
+  }
+};
 // A row of a feature's most recent wav-in call, for the conan_step_wav_* hooks: call row, the staging set, the chunk row there, frames
 struct LastRow { int row, set, src, emit; };
 
@@ -331,44 +359,42 @@ struct conan_streams {
     std::vector<LastRow> last;
   } tn;
   void tones_init();
-  // input loss concealment (conan_streams_set_conceal; conceal.hip).  state: [max_slots] records of cnk::kConcStateBytes, read and
-  // written by the rows of conceal_kernel in the order of the caller's stream; pending restarts it from zeros (set when a slot that
-  // was off is enabled without a seed; a seed clears it).  Rows: per repair call; event: behind the kernel's launch.  No step path
-  // reads any of it: the repair works on the caller's rows in front of the step call.
-  struct Conceal : SlotSetting<conan_conceal_cfg> {
-    char* state = nullptr;
-    StageSets<cnk::ConcRow> sets;
-  } conc;
-  void conceal_init();
-  // echo cancellation (conan_streams_set_echo; echo.hip).  state: [max_slots] records of cnk::kEchoStateBytes, read and written by the
-  // rows of echo_kernel in the order of the caller's stream; pending restarts it (set when a slot that was off is enabled without a
-  // seed; a seed clears it).  pos: per slot the samples cancelled since its restart as the host counts them (a seed's is read back):
-  // the kernel takes the pending block's fill from the call row, never from the record.  Rows: per echo call; event: behind the
-  // kernel's launch.  No step path reads any of it.
-  struct Echo : SlotSetting<conan_echo_cfg> {
-    char* state = nullptr;
+  // The shared *_init() of a RecordSetting, behind the feature's first enabling call: the zeroed records and the row tables, both
+  // stream state (kSets is spelt out where it is called: the tables' count is part of what state_bytes reports); false: done before
+  template <int kSets, typename R>
+  bool records_init(R& r) {
+    static_assert(kSets == R::kSets, "the feature's own number of row tables");
+    if (r.state) return false;
+    r.state = reinterpret_cast<decltype(r.state)>(alloc((size_t)max_slots * R::kRecBytes / sizeof(float)));
+    r.sets.init(max_slots, allocs);
+    state_bytes += (int64_t)kSets * max_slots * sizeof(typename R::Row);
+    r.assign(max_slots);
+    return true;
+  }
+  // --- the pre-step row features (prestep.h): each a RecordSetting whose kernel works on the caller's device rows in front of the
+  // wav-in step calls, in the order of the caller's stream; no step path reads any of it.  pending restarts the record in the slot's
+  // next row (set when a slot that was off is enabled without a seed; a seed clears it).  Rows: per call; event: behind the kernel's
+  // launch.  What differs:
+  // input loss concealment (conan_streams_set_conceal; conceal.hip): restarts from zeros, keeps no position.
+  struct Conceal : RecordSetting<conan_conceal_cfg, cnk::ConcRow, char, kStageSets, cnk::kConcStateBytes> {} conc;
+  void conceal_init() { records_init<kStageSets>(conc); }
+  // echo cancellation (conan_streams_set_echo; echo.hip).  pos: per slot the samples cancelled since its restart as the host counts
+  // them (a seed's is read back): the kernel takes the pending block's fill from the call row, never from the record.
+  struct Echo : RecordSetting<conan_echo_cfg, cnk::EchoRow, char, kStageSets, cnk::kEchoStateBytes> {
     std::vector<long long> pos;
-    StageSets<cnk::EchoRow> sets;
   } ec;
-  void echo_init();
-  // echo delay (conan_streams_set_echo_delay; echo_delay.hip).  state: [max_slots] records of cnk::kEdStateBytes, read and written by
-  // the rows of echo_delay_kernel in the order of the caller's stream; pending and pos as the canceller's (the kernel takes the
-  // frame's fill from the call row).  Rows: per estimator call; event: behind the kernel's launch.  No step path reads any of it.
-  struct EchoDelay : SlotSetting<conan_echo_delay_cfg> {
-    char* state = nullptr;
+  void echo_init() { if (records_init<kStageSets>(ec)) ec.pos.assign(max_slots, 0); }
+  // echo delay (conan_streams_set_echo_delay; echo_delay.hip).  pos: as the canceller's, for the pending frame's fill.
+  struct EchoDelay : RecordSetting<conan_echo_delay_cfg, cnk::EdRow, char, kStageSets, cnk::kEdStateBytes> {
     std::vector<long long> pos;
-    StageSets<cnk::EdRow> sets;
   } ed;
-  void echo_delay_init();
+  void echo_delay_init() { if (records_init<kStageSets>(ed)) ed.pos.assign(max_slots, 0); }
   // input noise suppression (conan_streams_set_denoise; denoise.hip).  state: [max_slots] records of conan_denoise_state, read and
   // written by the rows of denoise_stream_kernel in the order of the front-end launches; pending restarts it before the slot's next
   // frame (a seed row becomes the state at once and clears the flag).  Rows: one per suppressing call row that completes a frame or
   // emits.  Event: behind the kernel's launch, in the front-end work.
-  struct Denoise : SlotSetting<conan_denoise_cfg> {
-    cnk::DnState* state = nullptr;
-    StageSets<cnk::DnRow> sets;
-  } dn;
-  void denoise_init();
+  struct Denoise : RecordSetting<conan_denoise_cfg, cnk::DnRow, cnk::DnState> {} dn;
+  void denoise_init() { records_init<kStageSets>(dn); }
   // a reset with CONAN_MODEL_FRONTEND: the settings stay; the states restart in the slots' next rows (host flags: no launch)
   void restart_features(const int32_t* slots, int n) { reg.restart(slots, n); act.restart(slots, n); byp.restart(slots, n); cmf.restart(slots, n); conc.restart(slots, n); ec.restart(slots, n); ed.restart(slots, n); dn.restart(slots, n); tn.restart(slots, n); in_eq.restart(slots, n); }
   void ragged_init();
@@ -415,11 +441,8 @@ struct conan_streams {
   // with CONAN_MODEL_HIFIGAN; a seed row becomes the state at once and clears the flag).  Per vocoder step with a marked row a row
   // table (set q of `sets`: one row per step row, on = 0 for a slot without the feature); the set's event is recorded behind the
   // embed launch.  Allocated by the first enabling call; state and row tables count as stream state.
-  struct Watermark : SlotSetting<conan_watermark_cfg> {
-    cnk::WmState* state = nullptr;
-    StageSets<cnk::WmRow, kActSets> sets;
-  } wm;
-  void watermark_init();
+  struct Watermark : RecordSetting<conan_watermark_cfg, cnk::WmRow, cnk::WmState, kActSets> {} wm;
+  void watermark_init() { records_init<kActSets>(wm); }
   // equaliser (conan_streams_set_input_eq / conan_streams_set_output_eq; eq.hip), a SlotSetting on each side.  state: [max_slots]
   // records of conan_eq_state; sec: [max_slots][kEqMaxSec] sections with their transition matrices, written by the setter's launch in
   // stream order; origin: per slot the grid's first sample as the host knows it (the kernels take every index from the call rows).
@@ -815,6 +838,29 @@ int output_samples(conan_streams* s, int32_t* counts, int cap);      // -> rows 
 void output_pending(conan_streams* s, const int32_t* slots, int n, int32_t* counts);
 void flush_output(conan_streams* s, const int32_t* slots, int n, float* wav_out_dev, int64_t wav_ld, void* stream);
 }  // namespace wavio
+
+// The state query of a RecordSetting (conan_streams_<name>_state): a slot about to restart reports the fresh record - zeros, and what
+// fresh(slot, dst, st) writes over them - any other its record, in the order of `stream`
+template <typename R, typename Fresh>
+void record_state(conan_streams* s, R conan_streams::*set, const char* name, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream, Fresh&& fresh) {
+  if (!s || !slots || !rows_dev) throw Error(CONAN_ERR_INVALID, "null argument");
+  R::check_rows("conan_streams_", name, "_state", rows_dev, ld);
+  wavio::check_slot_list(s, slots, n);
+  R& r = s->*set;
+  for (int i = 0; i < n; ++i)
+    if (!r.on(slots[i])) throw Error(CONAN_ERR_STATE, std::string("conan_streams_") + name + "_state: slot " + std::to_string(slots[i]) + " has the feature off (conan_streams_set_" + name + ")");
+  hipStream_t st = s->enter(stream);
+  for (int i = 0; i < n; ++i) {
+    char* dst = static_cast<char*>(rows_dev) + (size_t)i * ld;
+    if (r.pending[slots[i]]) {
+      HIP_CHECK(hipMemsetAsync(dst, 0, R::kRecBytes, st));
+      fresh(slots[i], dst, st);
+    } else {
+      HIP_CHECK(hipMemcpyAsync(dst, r.record(slots[i]), R::kRecBytes, hipMemcpyDeviceToDevice, st));
+    }
+  }
+}
+inline void fresh_zeros(int, char*, hipStream_t) {}      // the fresh record of a feature that restarts from zeros
 
 // ---- input leveller (level.hip): the kernel's host side and the bodies of api.hip's entry points
 namespace level {

@@ -227,7 +227,6 @@ static_assert(sizeof(conan_watermark_hit) == sizeof(cnk::WmHit), "the kernels' r
 static_assert(sizeof(conan_watermark_result) == 40, "six 32-bit fields, the score and z");
 static_assert(31ll * 32768 * 4 * cnk::kWmChips < (1ll << 31), "the correlation fits int32");
 static_assert(2ll * cnk::kWmBlk * 31 * 32768 < (1ll << 32), "the window's sum of |d| fits 32 bits");
-constexpr int64_t kStateBytes = (int64_t)sizeof(cnk::WmState);
 constexpr int kMarker = 0xB5;      // 1,0,1,1,0,1,0,1, the first block in the top bit
 constexpr int64_t kMaxDetectSamples = (int64_t)1 << 26, kMaxDetectWorkspace = (int64_t)1 << 31;
 
@@ -379,15 +378,10 @@ void decide(const int64_t* score, const int64_t* soft, const conan_watermark_hit
   out->marker_score = best; out->z = z;
 }
 
-static void check_rows(const char* who, const void* p, int64_t ld) {
-  if (ld < kStateBytes || ((uintptr_t)p & 7) || (ld & 7))
-    throw Error(CONAN_ERR_INVALID, std::string(who) + ": rows are conan_watermark_state_bytes bytes, 8-byte aligned, ld apart");
-}
-
 void set_watermark(conan_streams* s, const int32_t* slots, int n, const conan_watermark_cfg* cfg, const void* seed_dev, int64_t seed_ld, void* stream) {
   if (!s || !slots || !cfg) throw Error(CONAN_ERR_INVALID, "null argument");
   check_cfg(*cfg, "conan_streams_set_watermark");      // (before the handle is touched, before any GPU use)
-  if (seed_dev) check_rows("conan_streams_set_watermark", seed_dev, seed_ld);
+  if (seed_dev) conan_streams::Watermark::check_rows("conan_streams_set_", "watermark", "", seed_dev, seed_ld);
   if (!(s->ctx->cfg.models & CONAN_MODEL_HIFIGAN)) throw Error(CONAN_ERR_STATE, "conan_streams_set_watermark: context holds no HiFi-GAN model");
   wavio::check_slot_list(s, slots, n);
   if (cfg->enabled && s->ctx->cfg.voc_upsample == 2)
@@ -399,34 +393,12 @@ void set_watermark(conan_streams* s, const int32_t* slots, int n, const conan_wa
   std::vector<char> restarts((size_t)n);
   for (int i = 0; i < n; ++i) restarts[i] = cfg->enabled && (cfg->reseed != 0 || !s->wm.on(slots[i]));
   s->wm.store_restarting(slots, n, *cfg);      // the restart travels in the slot's next step row ...
-  for (int i = 0; i < n && seed_dev; ++i) {      // ... or the seed row becomes the state, now
-    if (!restarts[i]) continue;      // the call keeps this slot's state: its seed row is not read
-    HIP_CHECK(hipMemcpyAsync(s->wm.state + slots[i], static_cast<const char*>(seed_dev) + (size_t)i * seed_ld, (size_t)kStateBytes, hipMemcpyDeviceToDevice, st));
-    s->wm.pending[slots[i]] = 0;
-  }
+  // ... or the seed row becomes the state, now (a slot whose state the call keeps: its seed row is not read)
+  if (seed_dev) s->wm.seed(slots, n, seed_dev, seed_ld, st, [&](int i) { return restarts[i] != 0; });
 }
 
-// a slot about to restart reports the zero record; any other its record, in the order of `stream`
 void state(conan_streams* s, const int32_t* slots, int n, void* rows_dev, int64_t ld, void* stream) {
-  if (!s || !slots || !rows_dev) throw Error(CONAN_ERR_INVALID, "null argument");
-  check_rows("conan_streams_watermark_state", rows_dev, ld);
-  wavio::check_slot_list(s, slots, n);
-  for (int i = 0; i < n; ++i)
-    if (!s->wm.on(slots[i])) throw Error(CONAN_ERR_STATE, "conan_streams_watermark_state: slot " + std::to_string(slots[i]) + " has no watermark (conan_streams_set_watermark)");
-  hipStream_t st = s->enter(stream);
-  for (int i = 0; i < n; ++i) {
-    char* dst = static_cast<char*>(rows_dev) + (size_t)i * ld;
-    if (s->wm.pending[slots[i]]) HIP_CHECK(hipMemsetAsync(dst, 0, (size_t)kStateBytes, st));
-    else HIP_CHECK(hipMemcpyAsync(dst, s->wm.state + slots[i], (size_t)kStateBytes, hipMemcpyDeviceToDevice, st));
-  }
+  record_state(s, &conan_streams::wm, "watermark", slots, n, rows_dev, ld, stream, fresh_zeros);
 }
 
 }  // namespace wmark
-
-void conan_streams::watermark_init() {
-  if (wm.state) return;
-  wm.state = reinterpret_cast<cnk::WmState*>(alloc((size_t)max_slots * sizeof(cnk::WmState) / sizeof(float)));      // zeroed (counted by state_bytes)
-  wm.sets.init(max_slots, allocs);
-  state_bytes += (int64_t)kActSets * max_slots * sizeof(cnk::WmRow);
-  wm.assign(max_slots);
-}

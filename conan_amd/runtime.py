@@ -68,52 +68,40 @@ def _row_bytes(rows, n, ld, device):
     return buf
 
 
-def _conceal_cfg(cfg, rate=None):
-    """An enabled _lib.ConcealCfg of: one itself; True (the defaults of `rate`); an integer rate; a dict of fields over the defaults of
-    `rate` (without a rate every field must be given)."""
-    if isinstance(cfg, _lib.ConcealCfg):
+def _rate_cfg(key, cfg, rate=None):
+    """An enabled Cfg struct of a feature of _lib.SLOT_FEATURES whose defaults follow the input rate (conceal, echo, echo_delay), of:
+    one itself; True (the defaults of `rate`); an integer rate; a dict of fields over the defaults of `rate` (without a rate every
+    field must be given)."""
+    f = _lib.SLOT_FEATURES[key]
+    if isinstance(cfg, f.cfg):
         return cfg
     if cfg is True:
         if rate is None:
-            raise ValueError("conceal: True stands for a rate's defaults, and no rate is known here")
-        return _lib.conceal_cfg(rate)
+            raise ValueError(f"{key}: True stands for a rate's defaults, and no rate is known here")
+        return f.build(rate)
     if isinstance(cfg, dict):
-        return _lib.conceal_cfg(rate, **cfg)
+        return f.build(rate, **cfg)
     if isinstance(cfg, (int, np.integer)) and not isinstance(cfg, bool):
-        return _lib.conceal_cfg(int(cfg))
-    raise ValueError(f"conceal: {cfg!r} is neither an _lib.ConcealCfg, a dict of its fields, a rate nor True")
+        return f.build(int(cfg))
+    raise ValueError(f"{key}: {cfg!r} is neither an _lib.{f.cfg.__name__}, a dict of its fields, a rate nor True")
 
 
-def _echo_cfg(cfg, rate=None):
-    """An enabled _lib.EchoCfg of: one itself; True (the defaults of `rate`); an integer rate; a dict of fields over the defaults of
-    `rate` (without a rate every field must be given)."""
-    if isinstance(cfg, _lib.EchoCfg):
-        return cfg
-    if cfg is True:
-        if rate is None:
-            raise ValueError("echo: True stands for a rate's defaults, and no rate is known here")
-        return _lib.echo_cfg(rate)
-    if isinstance(cfg, dict):
-        return _lib.echo_cfg(rate, **cfg)
-    if isinstance(cfg, (int, np.integer)) and not isinstance(cfg, bool):
-        return _lib.echo_cfg(int(cfg))
-    raise ValueError(f"echo: {cfg!r} is neither an _lib.EchoCfg, a dict of its fields, a rate nor True")
-
-
-def _echo_delay_cfg(cfg, rate=None):
-    """An enabled _lib.EchoDelayCfg of: one itself; True (the defaults of `rate`); an integer rate; a dict of fields over the defaults
-    of `rate` (without a rate every field must be given)."""
-    if isinstance(cfg, _lib.EchoDelayCfg):
-        return cfg
-    if cfg is True:
-        if rate is None:
-            raise ValueError("echo_delay: True stands for a rate's defaults, and no rate is known here")
-        return _lib.echo_delay_cfg(rate)
-    if isinstance(cfg, dict):
-        return _lib.echo_delay_cfg(rate, **cfg)
-    if isinstance(cfg, (int, np.integer)) and not isinstance(cfg, bool):
-        return _lib.echo_delay_cfg(int(cfg))
-    raise ValueError(f"echo_delay: {cfg!r} is neither an _lib.EchoDelayCfg, a dict of its fields, a rate nor True")
+def _pack_signals(who, fmt, dev, lengths, **rows):
+    """The whole-signal calls' rows (keyword -> [..., N] samples of format `fmt`, all of one shape) packed for the library ->
+    (the format's code, the packed uint8 buffers in the keywords' order, the leading shape, n, N, the row stride in dwords, the
+    int64 lengths: `lengths` per row, default N)."""
+    f = _lib.sample_format(fmt)
+    rows = {k: v.to(dev) for k, v in rows.items()}
+    first = next(iter(rows.values()))
+    if any(v.dtype != SAMPLE_DTYPES[fmt] or v.shape != first.shape for v in rows.values()):
+        got = " and ".join(f"{v.dtype} {tuple(v.shape)}" for v in rows.values())
+        raise ValueError(f"{who}: format {fmt!r} takes {SAMPLE_DTYPES[fmt]} samples in {' and '.join(rows)} rows of one shape, got {got}")
+    lead, N = first.shape[:-1], first.shape[-1]
+    n = int(np.prod(lead)) if len(lead) else 1
+    ld = max((N * _lib.SAMPLE_BYTES[fmt] + 3) // 4, 1)
+    bufs = [_row_bytes(v.reshape(n, N), n, ld, dev) for v in rows.values()]
+    sm = np.full(n, N, dtype=np.int64) if lengths is None else np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(n))
+    return f, bufs, lead, n, N, ld, sm
 
 
 def mel_cfg(fft_size=1024, hop_size=320, win_length=1024, num_mels=80, fmin=80, fmax=7600, sample_rate=16000, eps=1e-6,
@@ -724,21 +712,12 @@ class Context:
         that rate's defaults (_lib.conceal_keywords); lengths: per row the samples to repair (default N).  -> the repaired signals
         [..., N] in fmt's dtype (x itself is left alone: the rows are packed into a buffer of the library's row stride first).  It
         is what a slot with Streams.set_conceal computes over its rows, bit for bit."""
-        c = _conceal_cfg(cfg)
-        f = _lib.sample_format(fmt)
+        c = _rate_cfg("conceal", cfg)
         dev = torch.device("cuda", self.device)
-        x = x.to(dev)
-        if x.dtype != SAMPLE_DTYPES[fmt]:
-            raise ValueError(f"conceal: format {fmt!r} takes {SAMPLE_DTYPES[fmt]} samples, got {x.dtype}")
-        lead, N = x.shape[:-1], x.shape[-1]
-        n = int(np.prod(lead)) if len(lead) else 1
-        ld = (N * _lib.SAMPLE_BYTES[fmt] + 3) // 4
-        buf = _row_bytes(x.reshape(n, N), n, max(ld, 1), dev)
+        f, (buf,), lead, n, N, ld, sm = _pack_signals("conceal", fmt, dev, lengths, x=x)
         flags = lost.to(dev).reshape(n, -1).to(torch.int32).contiguous()
-        sm = np.full(n, N, dtype=np.int64) if lengths is None else np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(n))
         if n and N:
-            _lib.check(self.lib.conan_conceal(self.h, C.byref(c), f, _ptr(buf), max(ld, 1), n, sm.ctypes.data_as(C.c_void_p), _ptr(flags),
-                                              flags.shape[1], _stream()))
+            _lib.check(self.lib.conan_conceal(self.h, C.byref(c), f, _ptr(buf), ld, n, sm.ctypes.data_as(C.c_void_p), _ptr(flags), flags.shape[1], _stream()))
         return buf.view(SAMPLE_DTYPES[fmt])[:, :N].reshape(*lead, N)
 
     def echo(self, mic, far, cfg, fmt="f32", lengths=None, stats=False):
@@ -748,19 +727,10 @@ class Context:
         defaults (_lib.echo_keywords); lengths: per row the samples to cancel (default N).  -> the cancelled signals [..., N] in
         fmt's dtype (mic itself is left alone), and with stats=True also int64 [n, 4] (cuda): per row sum d^2, sum e^2, blocks
         adapted, blocks frozen.  It is what a slot with Streams.set_echo computes over its rows, bit for bit."""
-        c = _echo_cfg(cfg)
-        f = _lib.sample_format(fmt)
+        c = _rate_cfg("echo", cfg)
         dev = torch.device("cuda", self.device)
-        mic, far = mic.to(dev), far.to(dev)
-        if mic.dtype != SAMPLE_DTYPES[fmt] or far.dtype != SAMPLE_DTYPES[fmt] or mic.shape != far.shape:
-            raise ValueError(f"echo: format {fmt!r} takes {SAMPLE_DTYPES[fmt]} samples in mic and far rows of one shape, got {mic.dtype} {tuple(mic.shape)} and {far.dtype} {tuple(far.shape)}")
-        lead, N = mic.shape[:-1], mic.shape[-1]
-        n = int(np.prod(lead)) if len(lead) else 1
-        ld = max((N * _lib.SAMPLE_BYTES[fmt] + 3) // 4, 1)
-        buf = _row_bytes(mic.reshape(n, N), n, ld, dev)
-        fbuf = _row_bytes(far.reshape(n, N), n, ld, dev)
+        f, (buf, fbuf), lead, n, N, ld, sm = _pack_signals("echo", fmt, dev, lengths, mic=mic, far=far)
         st = torch.zeros(n, 4, dtype=torch.int64, device=dev)
-        sm = np.full(n, N, dtype=np.int64) if lengths is None else np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(n))
         if n and N:
             _lib.check(self.lib.conan_echo(self.h, C.byref(c), f, _ptr(buf), ld, _ptr(fbuf), ld, n, sm.ctypes.data_as(C.c_void_p), _ptr(st), _stream()))
         out = buf.view(SAMPLE_DTYPES[fmt])[:, :N].reshape(*lead, N)
@@ -773,21 +743,12 @@ class Context:
         samples to take (default N).  -> (track int64 [n, N // 1024, 6] (cuda): per row the report after each frame end, zeros
         behind a shorter row's frames; report int64 [n, 6]: est, age, cand, run, last_pk, last_s after the last sample).  It is
         what a slot with Streams.set_echo_delay computes over its rows, bit for bit."""
-        c = _echo_delay_cfg(cfg)
-        f = _lib.sample_format(fmt)
+        c = _rate_cfg("echo_delay", cfg)
         dev = torch.device("cuda", self.device)
-        mic, far = mic.to(dev), far.to(dev)
-        if mic.dtype != SAMPLE_DTYPES[fmt] or far.dtype != SAMPLE_DTYPES[fmt] or mic.shape != far.shape:
-            raise ValueError(f"echo_delay: format {fmt!r} takes {SAMPLE_DTYPES[fmt]} samples in mic and far rows of one shape, got {mic.dtype} {tuple(mic.shape)} and {far.dtype} {tuple(far.shape)}")
-        lead, N = mic.shape[:-1], mic.shape[-1]
-        n = int(np.prod(lead)) if len(lead) else 1
-        ld = max((N * _lib.SAMPLE_BYTES[fmt] + 3) // 4, 1)
-        buf = _row_bytes(mic.reshape(n, N), n, ld, dev)
-        fbuf = _row_bytes(far.reshape(n, N), n, ld, dev)
+        f, (buf, fbuf), lead, n, N, ld, sm = _pack_signals("echo_delay", fmt, dev, lengths, mic=mic, far=far)
         frames = N // _lib.ECHO_DELAY_FRAME
         track = torch.zeros(n, frames, 6, dtype=torch.int64, device=dev)
         report = torch.zeros(n, 6, dtype=torch.int64, device=dev)
-        sm = np.full(n, N, dtype=np.int64) if lengths is None else np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(n))
         if n and N:
             _lib.check(self.lib.conan_echo_delay(self.h, C.byref(c), f, _ptr(buf), ld, _ptr(fbuf), ld, n, sm.ctypes.data_as(C.c_void_p),
                                                  _ptr(track) if frames else None, frames * 6, _ptr(report), _stream()))
@@ -1284,6 +1245,23 @@ class Streams:
         if f.mirror:
             for slot in a:
                 self._note_cfg(f, slot, f.keywords(c) if getattr(c, f.on) else None)
+        return c
+
+    def _call_rows(self, who, slots, samples, report=None, width=0, **rows):
+        """The arguments of a pre-step row call (conceal, echo, echo_delay): rows (keyword -> a 2-D cuda tensor with one row per
+        slot, contiguous rows a multiple of 4 bytes apart), samples (an int or one per row) and the optional int64 [n, width] report
+        tensor -> (the slot array's pointer, n, the samples' pointer, per row tensor its pointer and its stride in dwords)."""
+        a, p = _i32(slots)
+        n = len(a)
+        for name, t in rows.items():
+            if not (t.is_cuda and t.dim() == 2 and t.shape[0] == n and (t.shape[1] < 2 or t.stride(1) == 1)
+                    and t.stride(0) * t.element_size() % 4 == 0 and t.data_ptr() % 4 == 0):
+                raise ValueError(f"{who}: {name} must be a 2-D cuda tensor [n, .] with contiguous rows a multiple of 4 bytes apart")
+        if report is not None and not (report.is_cuda and report.dtype == torch.int64 and report.is_contiguous() and tuple(report.shape) == (n, width)):
+            raise ValueError(f"{who}: the report must be a contiguous int64 cuda tensor [n, {width}]")
+        sm, sp = _i32([int(samples)] * n if isinstance(samples, (int, np.integer)) else samples)
+        assert len(sm) == n, (n, len(sm))
+        return (p, n, sp) + tuple(x for t in rows.values() for x in (_ptr(t), t.stride(0) * t.element_size() // 4))
 
     def _get_feature(self, key, slots, report=None):
         """A feature's cfg getter: per slot what `report` (default: the feature's keywords) makes of the struct, None for a slot
@@ -1652,16 +1630,9 @@ class Streams:
         float32 tensor for f32 slots; for other or mixed formats the packed uint8 rows the steps build); samples: an int or one per
         row; lost [n, >= ceil(samples / packet)] integer or bool, non-zero = lost.  Rows of slots without the feature and rows
         without samples keep their bytes.  -> wav"""
-        a, p = _i32(slots)
-        n = len(a)
-        if not (wav.is_cuda and wav.dim() == 2 and wav.shape[0] == n and (wav.shape[1] < 2 or wav.stride(1) == 1)
-                and wav.stride(0) * wav.element_size() % 4 == 0 and wav.data_ptr() % 4 == 0):
-            raise ValueError("conceal: wav must be a 2-D cuda tensor [n, .] with contiguous rows a multiple of 4 bytes apart")
-        sm, sp = _i32([int(samples)] * n if isinstance(samples, (int, np.integer)) else samples)
-        assert len(sm) == n, (n, len(sm))
-        flags = lost.to(self.dev).reshape(n, -1).to(torch.int32).contiguous()
-        _lib.check(self.lib.conan_streams_conceal(self.h, p, n, sp, _ptr(wav), wav.stride(0) * wav.element_size() // 4, _ptr(flags), flags.shape[1],
-                                                  _stream()))
+        args = self._call_rows("conceal", slots, samples, wav=wav)
+        flags = lost.to(self.dev).reshape(args[1], -1).to(torch.int32).contiguous()
+        _lib.check(self.lib.conan_streams_conceal(self.h, *args, _ptr(flags), flags.shape[1], _stream()))
         return wav
 
     def conceal_state(self, slots):
@@ -1689,18 +1660,8 @@ class Streams:
         format of slots[i] (as conceal()'s wav); samples: an int or one per row; stats: an int64 cuda tensor [n, 4] to fill (per row
         sum d^2, sum e^2, blocks adapted and frozen in this call) or None.  Rows of slots without the feature and rows without
         samples keep their bytes.  -> wav"""
-        a, p = _i32(slots)
-        n = len(a)
-        for name, t in (("wav", wav), ("far", far)):
-            if not (t.is_cuda and t.dim() == 2 and t.shape[0] == n and (t.shape[1] < 2 or t.stride(1) == 1)
-                    and t.stride(0) * t.element_size() % 4 == 0 and t.data_ptr() % 4 == 0):
-                raise ValueError(f"echo: {name} must be a 2-D cuda tensor [n, .] with contiguous rows a multiple of 4 bytes apart")
-        if stats is not None and not (stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous() and tuple(stats.shape) == (n, 4)):
-            raise ValueError("echo: stats must be a contiguous int64 cuda tensor [n, 4]")
-        sm, sp = _i32([int(samples)] * n if isinstance(samples, (int, np.integer)) else samples)
-        assert len(sm) == n, (n, len(sm))
-        _lib.check(self.lib.conan_streams_echo(self.h, p, n, sp, _ptr(wav), wav.stride(0) * wav.element_size() // 4, _ptr(far),
-                                               far.stride(0) * far.element_size() // 4, _ptr(stats), _stream()))
+        args = self._call_rows("echo", slots, samples, stats, 4, wav=wav, far=far)
+        _lib.check(self.lib.conan_streams_echo(self.h, *args, _ptr(stats), _stream()))
         return wav
 
     def echo_state(self, slots):
@@ -1715,58 +1676,33 @@ class Streams:
         survives resets; an enabled slot keeps its state (a changed n_lags keeps the sums that still exist), which restarts when a
         slot that was off is enabled and at the first estimator call after a reset of the front-end.  Slot snapshots do not carry
         it, and the slot needs no canceller.  The estimate itself is echo_delay(), or far= on the wav-in steps."""
-        a, p = _i32(slots)
-        if cfg is None or cfg is False:
-            if fields:
-                raise ValueError("set_echo_delay: cfg=None turns the estimator off and takes no keywords")
-            c = _lib.EchoDelayCfg()
-        else:
+        slots = [int(s) for s in slots]
+        if cfg is None or cfg is False:      # (False: the engine's "none")
+            cfg = None
+        else:      # a struct from every form _rate_cfg takes; keywords go over a struct's fields as over a dict's
             if fields:
                 cfg = dict(_lib.echo_delay_keywords(cfg) if isinstance(cfg, _lib.EchoDelayCfg) else cfg if isinstance(cfg, dict) else {}, **fields)
-            c = _echo_delay_cfg(cfg, self.model_rate if rate is None else int(rate))
-        if seed is not None and (seed.dtype != torch.uint8 or seed.dim() != 2 or seed.shape[0] != len(a) or not seed.is_cuda or seed.stride(1) != 1):
-            raise ValueError("set_echo_delay: seed must be a cuda uint8 [n, bytes] tensor, as echo_delay_state returns it")
-        _lib.check(self.lib.conan_streams_set_echo_delay(self.h, p, len(a), C.byref(c), _ptr(seed), int(seed.stride(0)) if seed is not None else 0, _stream()))
-        self._release()
-        (self.echo_delays.update if c.enabled else self.echo_delays.difference_update)(int(s) for s in a)
+            cfg, fields = _rate_cfg("echo_delay", cfg, self.model_rate if rate is None else int(rate)), {}
+        c = self._set_feature("echo_delay", slots, cfg, fields, seed=seed)
+        (self.echo_delays.update if c.enabled else self.echo_delays.difference_update)(slots)
 
     def echo_delay_cfg(self, slots):
         """conan_streams_echo_delay_cfg: per slot the dict of its fields (set_echo_delay takes it back), None for a slot without."""
-        out = []
-        for slot in slots:
-            c = _lib.EchoDelayCfg()
-            _lib.check(self.lib.conan_streams_echo_delay_cfg(self.h, int(slot), C.byref(c)))
-            out.append(_lib.echo_delay_keywords(c) if c.enabled else None)
-        return out
+        return self._get_feature("echo_delay", slots)
 
     def echo_delay(self, slots, wav, samples, far, report=None):
         """conan_streams_echo_delay: the estimator READS the rows and the far rows - in front of echo(), which rewrites wav, and
         behind conceal() - and updates the slots' states.  wav, far, samples: as echo()'s; report: an int64 cuda tensor [n, 6] to
         fill (per row est, age, cand, run, last_pk, last_s after the call; _lib.ECHO_DELAY_REPORT) or None.  Rows of slots without
         the feature and rows without samples are skipped and report zeros.  -> report"""
-        a, p = _i32(slots)
-        n = len(a)
-        for name, t in (("wav", wav), ("far", far)):
-            if not (t.is_cuda and t.dim() == 2 and t.shape[0] == n and (t.shape[1] < 2 or t.stride(1) == 1)
-                    and t.stride(0) * t.element_size() % 4 == 0 and t.data_ptr() % 4 == 0):
-                raise ValueError(f"echo_delay: {name} must be a 2-D cuda tensor [n, .] with contiguous rows a multiple of 4 bytes apart")
-        if report is not None and not (report.is_cuda and report.dtype == torch.int64 and report.is_contiguous() and tuple(report.shape) == (n, 6)):
-            raise ValueError("echo_delay: report must be a contiguous int64 cuda tensor [n, 6]")
-        sm, sp = _i32([int(samples)] * n if isinstance(samples, (int, np.integer)) else samples)
-        assert len(sm) == n, (n, len(sm))
-        _lib.check(self.lib.conan_streams_echo_delay(self.h, p, n, sp, _ptr(wav), wav.stride(0) * wav.element_size() // 4, _ptr(far),
-                                                     far.stride(0) * far.element_size() // 4, _ptr(report), _stream()))
+        args = self._call_rows("echo_delay", slots, samples, report, 6, wav=wav, far=far)
+        _lib.check(self.lib.conan_streams_echo_delay(self.h, *args, _ptr(report), _stream()))
         return report
 
     def echo_delay_state(self, slots):
         """conan_streams_echo_delay_state: uint8 [n, bytes] (cuda), the slots' estimator states for set_echo_delay(seed=).  Joins
         pipelined work."""
-        a, p = _i32(slots)
-        nbytes = int(_lib.check(self.lib.conan_echo_delay_state_bytes()))
-        out = torch.empty(len(a), nbytes, dtype=torch.uint8, device=self.dev)
-        _lib.check(self.lib.conan_streams_echo_delay_state(self.h, p, len(a), _ptr(out), nbytes, _stream()))
-        self._release()
-        return out
+        return self._feature_seed_rows("echo_delay", slots)
 
     def _far_stages(self, a, wav, samples, far_rows, echo_stats, echo_delay_report):
         """far= of a wav-in step: the delay estimator of the slots that have one reads the rows, then the canceller rewrites them."""

@@ -123,9 +123,16 @@ def test_follow_rule():
 
 
 def test_the_feature_table_is_unchanged():
-    assert list(_lib.SLOT_FEATURES) == ["eq", "level", "pitch", "follow", "register", "activity", "bypass", "conceal", "echo", "denoise", "comfort",
-                                        "tones", "out_eq", "out_level", "watermark"]
-    assert not any("echo_delay" in (f.setter or "") for f in _lib.SLOT_FEATURES.values())
+    """The keywords the engine applies from the table are what they were; the estimator is a row of it that the engine applies itself,
+    and its prototypes - the table's loop fills four of them - are the ones that were written out before."""
+    assert [k for k, f in _lib.SLOT_FEATURES.items() if not f.engine_own] == ["eq", "level", "pitch", "follow", "register", "activity", "bypass", "conceal",
+                                                                             "echo", "denoise", "comfort", "tones", "out_eq", "out_level", "watermark"]
+    assert [k for k, f in _lib.SLOT_FEATURES.items() if f.engine_own] == ["echo_delay"]
+    f = _lib.SLOT_FEATURES["echo_delay"]
+    assert (f.cfg, f.on, f.build, f.keywords, f.noun) == (_lib.EchoDelayCfg, "enabled", _lib.echo_delay_cfg, _lib.echo_delay_keywords, "the estimator")
+    assert (f.setter, f.getter, f.seed_state, f.seed_bytes) == ("conan_streams_set_echo_delay", "conan_streams_echo_delay_cfg", "conan_streams_echo_delay_state",
+                                                                "conan_echo_delay_state_bytes")
+    assert f.method == "set_echo_delay" and f.state is None and f.last is None and f.meta is None and f.stream and f.release and f.mirror is None
     v = C.c_void_p
     assert _lib._PROTOS["conan_streams_set_echo_delay"] == (C.c_int, [v, v, C.c_int, v, v, C.c_int64, v])
     assert _lib._PROTOS["conan_streams_echo_delay_cfg"] == (C.c_int, [v, C.c_int, v])

@@ -464,7 +464,7 @@ def test_hand_over_of_everything_at_once(full, refs, blocking):
     b = full.streams(W.MAX_SLOTS + 2, W.MAX_FRAMES, W.MAX_REF, flags=_lib.STREAMS_FIXED_PLAN)
     b.import_slots([2], snap)
     assert b.layout_id == a.layout_id
-    for key, f in _lib.SLOT_FEATURES.items():      # (the walk is over the table: a feature without a protocol fails here)
+    for key, f in W.CHAIN_FEATURES.items():      # (the walk is over the table: a feature without a protocol fails here)
         assert key in HAND_OVER, f"{key}: no hand-over protocol in this test"
         assert HAND_OVER[key] is not None or not f.seed_state, f"{key} has a seed_state and is not handed over"
         if HAND_OVER[key] is not None:
@@ -493,7 +493,7 @@ def test_an_engine_utterance_with_every_feature_keyword(full, refs, blocking):
     u = W.utterances()[1]
     kw = {k: (dict(v) or True) for k, v in W.SETTINGS[1].items()}
     kw.update(conceal=True, echo={k: v for k, v in W.SETTINGS[1]["echo"].items() if k != "rate"})      # (the engine names the slot's rate itself)
-    assert set(kw) == set(_lib.SLOT_FEATURES)
+    assert set(kw) == set(W.CHAIN_FEATURES)
     n = W.MAX_SLOTS      # (a fixed plan follows max_slots: an engine of the stream-set's size, the utterance in every row)
     eng = StreamingVoiceConversionEngine(full, n, max_ref_frames=W.MAX_REF, flags=_lib.STREAMS_FIXED_PLAN)
     src, far, lost = (torch.from_numpy(u[k].copy()).cuda()[None].repeat(n, 1) for k in ("wav", "far", "lost"))

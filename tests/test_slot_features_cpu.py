@@ -1,5 +1,5 @@
-"""The Python layer of the nine per-slot features (input level, pitch, pitch follow, register, activity, bypass, comfort, output level,
-concealment), characterised without a GPU and without the built library: (a) runtime.Streams over a library stand-in that records every
+"""The Python layer of ten per-slot features (input level, pitch, pitch follow, register, activity, bypass, comfort, output level,
+concealment, echo delay), characterised without a GPU and without the built library: (a) runtime.Streams over a library stand-in that records every
 C call - the symbol, the slot array, the cfg's bytes, the seed rows, the stream argument, the release of pipelined buffers - and (b) the
 engine over a Streams stand-in that records every method call, bound through the real method's signature (so a cfg handed over by
 position and one handed over by keyword read the same).  The expectations are built from _lib's builders, never from the code under
@@ -55,7 +55,7 @@ def st(monkeypatch):
     s = runtime.Streams.__new__(runtime.Streams)
     s.lib, s.h, s.dev, s._keep = Lib(), H, torch.device("cpu"), []
     s.ctx = types.SimpleNamespace(hop=320)      # (model_rate = 16000)
-    s.input_levels, s.output_levels, s.pitch_cfgs = {}, {}, {}
+    s.input_levels, s.output_levels, s.pitch_cfgs, s.echo_delays = {}, {}, {}, set()
     s.input_formats, s.output_formats, s.output_rates, s.input_rate_set = {}, {}, {}, False
     s.seg, s._last_wav_n = 4, 0
     s._release = lambda: s.lib.calls.append(("_release", []))
@@ -78,9 +78,9 @@ class Seed:
         return 0x5000
 
 
-L, P, F0, R, A, B, CF, CC = (_lib.level_cfg, _lib.pitch_cfg, _lib.f0_cfg, _lib.register_cfg, _lib.activity_cfg, _lib.bypass_cfg, _lib.comfort_cfg,
-                             _lib.conceal_cfg)
-_A_STRUCT, _B_STRUCT, _CF_STRUCT, _CC_STRUCT = A(hold_frames=3), B(wet=0.25), CF(colour=2), CC(8000, fade=0)
+L, P, F0, R, A, B, CF, CC, ED = (_lib.level_cfg, _lib.pitch_cfg, _lib.f0_cfg, _lib.register_cfg, _lib.activity_cfg, _lib.bypass_cfg, _lib.comfort_cfg,
+                                 _lib.conceal_cfg, _lib.echo_delay_cfg)
+_A_STRUCT, _B_STRUCT, _CF_STRUCT, _CC_STRUCT, _ED_STRUCT = A(hold_frames=3), B(wet=0.25), CF(colour=2), CC(8000, fade=0), ED(8000, leak=3)
 
 # (method, positional arguments after slots, keywords, the struct the C call must carry)
 SETTER_CASES = [
@@ -140,6 +140,17 @@ SETTER_CASES = [
     ("set_conceal", (_CC_STRUCT,), {}, _CC_STRUCT),
     ("set_conceal", (None,), {}, _lib.ConcealCfg()),
     ("set_conceal", (None,), dict(rate=8000), _lib.ConcealCfg()),      # (rate= is no keyword of **kw)
+    ("set_echo_delay", (), {}, ED(16000)),
+    ("set_echo_delay", (), dict(rate=8000), ED(8000)),
+    ("set_echo_delay", (True,), dict(rate=8000, leak=3), ED(8000, leak=3)),
+    ("set_echo_delay", (dict(leak=3),), {}, ED(16000, leak=3)),
+    ("set_echo_delay", (dict(leak=3, hold=3),), dict(hold=5, rate=48000), ED(48000, leak=3, hold=5)),
+    ("set_echo_delay", (_ED_STRUCT,), {}, _ED_STRUCT),
+    ("set_echo_delay", (_ED_STRUCT,), dict(hold=5), ED(8000, leak=3, hold=5)),      # (keywords over a struct's fields, as over a dict's)
+    ("set_echo_delay", (None,), {}, _lib.EchoDelayCfg()),
+    ("set_echo_delay", (False,), {}, _lib.EchoDelayCfg()),      # (the engine's "none")
+    ("set_echo_delay", (None,), dict(rate=8000), _lib.EchoDelayCfg()),      # (rate= is no keyword of **fields)
+    ("set_echo_delay", (8000,), {}, ED(8000)),      # (an integer rate stands for its defaults, as in Context.echo_delay)
 ]
 # method -> (symbol, a stream argument, seed rows and a stride, the release of pipelined buffers, the slot-to-keywords dict and its reporter)
 SETTERS = {
@@ -152,6 +163,7 @@ SETTERS = {
     "set_comfort": ("conan_streams_set_comfort", True, False, True, None),
     "set_output_level": ("conan_streams_set_output_level", True, True, False, ("output_levels", _lib.level_keywords)),
     "set_conceal": ("conan_streams_set_conceal", True, True, True, None),
+    "set_echo_delay": ("conan_streams_set_echo_delay", True, True, True, None),
 }
 
 
@@ -178,6 +190,22 @@ def test_streams_setter_calls(st, case):
     for name in ("input_levels", "output_levels", "pitch_cfgs"):
         want = {5: mirror[1](cfg), 2: mirror[1](cfg)} if mirror and mirror[0] == name and on else {}
         assert getattr(st, name) == want
+    assert st.echo_delays == ({5, 2} if method == "set_echo_delay" and on else set())      # the set _far_stages reads
+
+
+def test_streams_echo_delays_follow_the_setter(st):
+    st.set_echo_delay([1, 2, 3], dict(leak=3))
+    st.set_echo_delay([2], True)
+    st.set_echo_delay([3, 7], None)
+    assert st.echo_delays == {1, 2}
+    st.set_echo_delay([1], False)
+    assert st.echo_delays == {2}
+    st.set_echo_delay(iter([4, 6]))      # (the slots may be any iterable: the set is kept from the list the call was made with)
+    assert st.echo_delays == {2, 4, 6} and st.lib.calls[-2][1][1] == [4, 6]
+    del st.lib.calls[:]
+    with pytest.raises(ValueError, match="^echo_delay: 'on' is neither an _lib.EchoDelayCfg, a dict of its fields, a rate nor True$"):
+        st.set_echo_delay([1], "on")
+    assert st.lib.calls == [] and st.echo_delays == {2, 4, 6}
 
 
 def test_streams_setters_keep_their_slot_dicts(st):
@@ -197,10 +225,10 @@ def test_streams_setters_keep_their_slot_dicts(st):
 
 @pytest.mark.parametrize("method, noun", [("set_input_level", "the leveller"), ("set_pitch", "the pitch control"), ("set_pitch_follow", "following"),
                                           ("set_activity", "the detector"), ("set_comfort", "the comfort noise"), ("set_output_level", "the leveller"),
-                                          ("set_conceal", "the concealment")])
+                                          ("set_conceal", "the concealment"), ("set_echo_delay", "the estimator")])
 def test_streams_setters_off_takes_no_keywords(st, method, noun):
     kw = {"set_input_level": dict(target=-20.0), "set_pitch": dict(range=0.5), "set_pitch_follow": dict(fmin=60.0), "set_activity": dict(hold_frames=2),
-          "set_comfort": dict(colour=0), "set_output_level": dict(clip=True), "set_conceal": dict(fade=0)}[method]
+          "set_comfort": dict(colour=0), "set_output_level": dict(clip=True), "set_conceal": dict(fade=0), "set_echo_delay": dict(leak=3)}[method]
     with pytest.raises(ValueError) as e:
         getattr(st, method)([0], None, **kw)
     assert str(e.value) == f"{method}: cfg=None turns {noun} off and takes no keywords"
@@ -213,11 +241,13 @@ def test_streams_register_needs_a_target(st):
     assert st.lib.calls == []
 
 
-@pytest.mark.parametrize("method, reader", [("set_output_level", "output_level_state"), ("set_conceal", "conceal_state")])
+@pytest.mark.parametrize("method, reader", [("set_output_level", "output_level_state"), ("set_conceal", "conceal_state"),
+                                            ("set_echo_delay", "echo_delay_state")])
 def test_streams_seeded_setters(st, method, reader):
     seed = Seed()
-    cfg = _lib.level_cfg(target=-18.0) if method == "set_output_level" else _lib.conceal_cfg(16000, fade=0)
-    getattr(st, method)([5, 2], dict(target=-18.0) if method == "set_output_level" else dict(fade=0), seed=seed)
+    fields, cfg = {"set_output_level": (dict(target=-18.0), L(target=-18.0)), "set_conceal": (dict(fade=0), CC(16000, fade=0)),
+                   "set_echo_delay": (dict(leak=3), ED(16000, leak=3))}[method]
+    getattr(st, method)([5, 2], fields, seed=seed)
     assert _seen(st.lib.calls) == _expect_setter(method, [5, 2], cfg, seed)
     del st.lib.calls[:]
     getattr(st, method)([5, 2], None, seed=seed)      # (the library decides what a seed beside "off" means)
@@ -244,11 +274,35 @@ def _fill(struct):
     ("activity", "conan_streams_activity", A(gate=False, hold_frames=3), _lib.activity_keywords),
     ("bypass", "conan_streams_bypass", B(wet=0.25, dry=0.5), _lib.bypass_keywords),
     ("comfort", "conan_streams_comfort", CF(follow=False, colour=2), _lib.comfort_keywords),
-    ("conceal_cfg", "conan_streams_conceal_cfg", CC(8000, fade=0), _lib.conceal_keywords)])
+    ("conceal_cfg", "conan_streams_conceal_cfg", CC(8000, fade=0), _lib.conceal_keywords),
+    ("echo_delay_cfg", "conan_streams_echo_delay_cfg", ED(8000, leak=3), _lib.echo_delay_keywords)])
 def test_streams_cfg_getters(st, method, symbol, struct, report):
     st.lib.script[symbol] = _fill(struct)
     assert getattr(st, method)([0, 6]) == [report(struct), None]
     assert [(name, args[:2], type(args[2])) for name, args in st.lib.calls] == [(symbol, [H, 0], type(struct)), (symbol, [H, 6], type(struct))]
+
+
+@pytest.mark.parametrize("key, build, fields", [("conceal", _lib.conceal_cfg, dict(fade=0)), ("echo", _lib.echo_cfg, dict(mu_shift=2)),
+                                                ("echo_delay", _lib.echo_delay_cfg, dict(leak=3))])
+def test_rate_cfg_is_the_builder(key, build, fields):
+    """runtime._rate_cfg, the cfg of the whole-signal calls: every form it takes gives the struct of the feature's _lib builder, byte for byte."""
+    f = _lib.SLOT_FEATURES[key]
+    assert f.build is build
+    every = f.keywords(build(8000, **fields))      # every field, so no rate is needed
+    struct = build(8000, **fields)
+    for form, rate, want in ((True, 8000, build(8000)), (8000, None, build(8000)), (np.int64(48000), None, build(48000)), (8000, 16000, build(8000)),
+                             (dict(fields), 8000, build(8000, **fields)), (every, None, build(8000, **fields)), (struct, None, struct), (struct, 16000, struct)):
+        got = runtime._rate_cfg(key, form, rate)
+        assert type(got) is f.cfg and bytes(got) == bytes(want), (key, form, rate)
+    assert runtime._rate_cfg(key, struct) is struct
+    with pytest.raises(ValueError) as e:
+        runtime._rate_cfg(key, True)
+    assert str(e.value) == f"{key}: True stands for a rate's defaults, and no rate is known here"
+    for bad in (False, None, 8000.0, "on"):
+        with pytest.raises(ValueError, match=f"^{key}: .* is neither an _lib.{f.cfg.__name__}, a dict of its fields, a rate nor True$"):
+            runtime._rate_cfg(key, bad)
+    with pytest.raises(ValueError, match="without a rate"):
+        runtime._rate_cfg(key, dict(fields))      # a dict of some fields and no rate
 
 
 def _rows(data):
@@ -304,7 +358,8 @@ def test_streams_level_rows(st, method, symbol):
 
 @pytest.mark.parametrize("method, symbol, size_symbol, size_args", [
     ("output_level_state", "conan_streams_output_level_state", "conan_streams_output_level_state_bytes", [H]),
-    ("conceal_state", "conan_streams_conceal_state", "conan_conceal_state_bytes", [])])
+    ("conceal_state", "conan_streams_conceal_state", "conan_conceal_state_bytes", []),
+    ("echo_delay_state", "conan_streams_echo_delay_state", "conan_echo_delay_state_bytes", [])])
 def test_streams_seed_rows(st, method, symbol, size_symbol, size_args):
     st.lib.script[size_symbol] = lambda *a: 24
     st.lib.script[symbol] = _rows([bytes(range(24)), bytes(range(24, 48))])

@@ -48,8 +48,13 @@ RATES = ("in_rate", "out_rate", "in_format", "out_format")
 DIGIT = "5"
 
 
+# the chain's features: the table's rows that the engine applies as the table's keywords (the echo-delay estimator, which the engine
+# steers by rules of its own and which changes no sample, has its own tests)
+CHAIN_FEATURES = {k: f for k, f in _lib.SLOT_FEATURES.items() if not f.engine_own}
+
+
 def every_feature(rate):
-    """Every row of _lib.SLOT_FEATURES, keyword -> the keywords of its Streams setter; conceal and echo at `rate` (None: the model's)."""
+    """Every row of CHAIN_FEATURES, keyword -> the keywords of its Streams setter; conceal and echo at `rate` (None: the model's)."""
     return dict(
         eq=dict(sections=[dict(kind="highpass", f=120.0)]),
         level=dict(target=-26.0, initial_gain_db=-4.0),      # (the rows end before the meter's first block of 400 ms: the initial gain is what acts)
